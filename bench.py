@@ -7,6 +7,7 @@ ciphertexts that are already resident in HBM (config 3 of BASELINE.json: N=2^15,
 |Bsk|=8, 7 key digits, t=786433, PARITY mode = bit-exact with the reference).
 
     python bench.py --gpus N --steps K --warmup W [--batch B] [--config 3|4|5] [--mode parity|strict] [--force-dist]
+                    [--dump-outputs DIR]
 
 --config selects the BASELINE.json line (default 3, the one the metric is quoted on; the driver's command is
 unchanged): 4 = CKKS N=2^15, 12 primes, Evaluator::rotate_vector over the rank's share of the 8192 ciphertexts with the
@@ -29,12 +30,20 @@ items 0, B/2, B-1 and the first and last item of every arena chunk the operation
 back to the host and compared word for word with the CPU oracle's result for the same inputs, on the thread pool the CPU
 baseline uses (`verified_count`, `verified_items`); a mismatch fails the run.
 
+--dump-outputs DIR: right after the timed region, what its last step handed the caller -- the size-2 result ciphertexts of
+the rank's batch, words below the primes -- is written to DIR as float64 .npy files, exactly: `ciphertexts_hi.npy` and
+`ciphertexts_lo.npy` hold the high and low 32 bits of every word, `ciphertexts_index.npy` the word's flat index into the
+(batch, 2, primes, N) result. All the words when they fit into 64 MB, otherwise a fixed seeded sample of 2^21 positions.
+The inputs are seeded, so two builds run with the same arguments can be compared file for file. Under N > 1 ranks every
+rank writes its own files (`_rank<r>` before the extension).
+
 `pcie_inclusive` (N = 1): the same step through the library's host-pointer entries on separately allocated pageable host
 ciphertexts (what a std::vector<seal::Ciphertext> is), H2D and D2H included -- reported next to `value`, never as it.
 
 Rank 0 prints one JSON line; see DESIGN.md "Measurement" for every field.
 """
 import argparse
+import contextlib
 import ctypes as C
 import hashlib
 import json
@@ -165,12 +174,22 @@ def gather_digests(digest):
     return [int(t.item()) for t in out]
 
 
+def rank_barrier():
+    """dist.barrier(), except on gloo (the stub's CPU ranks): there the ranks meet in an all_reduce of one CPU word, because
+    barrier() asks torch for the accelerator, which on ROCm opens the GPU in every rank."""
+    if dist.get_backend() == "gloo":
+        dist.all_reduce(torch.zeros(1, dtype=torch.int64))
+    else:
+        dist.barrier()
+
+
 def barrier_sync():
-    if torch.cuda.is_available() and torch.cuda.is_initialized():
+    # is_initialized() only: on ROCm is_available() opens the device, and the stub's ranks must never hold the GPU
+    if torch.cuda.is_initialized():
         torch.cuda.synchronize()
     if _dist_on():
-        dist.barrier()
-    if torch.cuda.is_available() and torch.cuda.is_initialized():
+        rank_barrier()
+    if torch.cuda.is_initialized():
         torch.cuda.synchronize()
 
 
@@ -233,6 +252,32 @@ def fill_mod_rows(t, moduli):
 
 def host_u64(t):
     return np.ascontiguousarray(t.detach().cpu().numpy()).view(np.uint64)
+
+
+DUMP_WORDS = 1 << 21  # three float64 values per word: 48 MB, inside the 64 MB budget of --dump-outputs
+DUMP_SEED = 20261015
+
+
+def dump_outputs(w, out_dir, suffix=""):
+    """--dump-outputs: the size-2 results of the last step (w.results()[:, :2], what a caller gets back) as exact float64
+    .npy files -- high and low 32 bits of every word and its flat index; a fixed seeded sample when the words exceed
+    DUMP_WORDS. Returns the number of words written."""
+    stream = torch.cuda.stream(w.stream) if getattr(w, "stream", None) is not None else contextlib.nullcontext()
+    with stream:
+        res = w.results()[:, :2]
+        shape = tuple(res.shape)
+        total = int(np.prod(shape))
+        if total <= DUMP_WORDS:
+            idx = np.arange(total, dtype=np.int64)
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_WORDS, replace=False)).astype(np.int64)
+        coords = tuple(torch.from_numpy(c).to(res.device) for c in np.unravel_index(idx, shape))
+        words = host_u64(res[coords])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("ciphertexts_hi", words >> np.uint64(32)), ("ciphertexts_lo", words & np.uint64(0xFFFFFFFF)),
+                      ("ciphertexts_index", idx)):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr.astype(np.float64))
+    return len(idx)
 
 
 # ------------------------------------------------------------------ the checker leg (oracle = CPU "port")
@@ -667,9 +712,11 @@ class StubWorkload:
     def finish(self):
         pass
 
+    def results(self):
+        return self.a if self.cfg["op"] == "rotate" else self.out
+
     def result_slice(self, count):
-        src = self.a if self.cfg["op"] == "rotate" else self.out
-        return src[:count, :2].contiguous()
+        return self.results()[:count, :2].contiguous()
 
     def key_digest(self):
         return cheap_digest(self.key[0, 0, :1])
@@ -712,7 +759,12 @@ def parse_args(argv=None):
                          "command at batch 256) and record them in profiles/traffic.json; roofline.traffic then comes "
                          "from this run's own measurement")
     ap.add_argument("--stub", action="store_true", help="CPU stand-in workload + gloo (tests of the rank logic only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the size-2 results of the last timed step to DIR as float64 .npy files (exact 32-bit "
+                         "halves of every word; a fixed seeded sample of 2^21 words of a larger batch)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     if args.batch is None:
         env = os.environ.get("SEALHIP_BENCH_BATCH")
@@ -775,6 +827,8 @@ def main(argv=None):
         prof = w.ctx.profile_fetch()
         w.ctx.profile_enable(False)
     w.finish()
+    if args.dump_outputs:
+        dump_outputs(w, args.dump_outputs, "_rank%d" % rank if world > 1 else "")
     dt = max_over_ranks(dt)
     value = world * B * args.steps / dt
 
@@ -1000,7 +1054,7 @@ def main(argv=None):
             line["stub"] = True
         print(json.dumps(line), flush=True)
     if _dist_on():
-        dist.barrier()
+        rank_barrier()
         dist.destroy_process_group()
     if verified is False:
         raise SystemExit("bench.py: the timed path's output differs from the CPU oracle (items %s of the %d checked on rank %d)"

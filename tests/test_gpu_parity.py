@@ -2690,6 +2690,26 @@ def test_bench_rccl_path_with_one_rank(launcher):
     assert line["key_replicated"] is True and line["roofline"]["kernel"] == "ntt_fwd_half"
 
 
+def test_bench_dump_outputs_are_the_verified_words(tmp_path):
+    """bench.py --dump-outputs on the engine: a batch of two ciphertexts (both verified against the oracle) is small enough
+    to be dumped whole; the words put back together from their 32-bit halves lie below their primes and are the results
+    the run digested itself (rank_digests: the size-2 results of the first four items)."""
+    import torch
+
+    import bench
+
+    d = str(tmp_path / "dump")
+    line = _bench_child(["--gpus", "1", "--batch", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                         "--ntt-polys", "0", "--verify-items", "2", "--pcie-pairs", "0", "--dump-outputs", d])
+    assert line["verified_vs_oracle"] is True and line["verified_items"] == [0, 1]
+    hi, lo, idx = (np.load(os.path.join(d, "ciphertexts_%s.npy" % s)) for s in ("hi", "lo", "index"))
+    n, k = 1 << 15, 7
+    assert hi.dtype == lo.dtype == idx.dtype == np.float64 and np.array_equal(idx, np.arange(2 * 2 * k * n))
+    words = hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64)
+    assert (words.reshape(2, 2, k, n) < np.array(bench.CFG3_PRIMES[:k], dtype=np.uint64)[:, None]).all()
+    assert "%016x" % bench.cheap_digest(torch.from_numpy(words.view(np.int64))) == line["rank_digests"][0]
+
+
 def test_latency_mode_tool_runs_its_all_reduce_on_rccl():
     """tools/latency_mode.py (the digits of one key switch split over the ranks, partial products summed by
     all_reduce over RCCL, the rest on every rank) as a child process under torch.distributed.run with one rank: the

@@ -283,6 +283,59 @@ def test_bench_force_dist_runs_the_collectives_with_one_rank_gloo():
     assert line["dist_initialized"] is False and line["gather"] is None and line["rccl_ranks_seen"] == 1
 
 
+def _dumped(d, suffix=""):
+    hi, lo, idx = (np.load(os.path.join(d, "ciphertexts_%s%s.npy" % (n, suffix))) for n in ("hi", "lo", "index"))
+    assert hi.dtype == lo.dtype == idx.dtype == np.float64 and hi.shape == lo.shape == idx.shape
+    assert (hi < 2**32).all() and (lo < 2**32).all()
+    return hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64), idx.astype(np.int64)
+
+
+def test_bench_dump_outputs_stub(tmp_path):
+    """--dump-outputs DIR: the size-2 results of the last timed step as float64 .npy files (exact 32-bit halves and flat
+    indices), the same for two runs with the same arguments, one more step of the in-place rotate (config 4) gives other
+    words, every rank writes its own files, and a batch over the budget is a fixed seeded sample under 64 MB."""
+    import subprocess
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--config", "4", "--warmup", "1", "--batch", "4"]
+    runs = {}
+    for name, argv in (("a", ["--gpus", "1", "--steps", "2"]), ("b", ["--gpus", "1", "--steps", "2"]),
+                       ("c", ["--gpus", "1", "--steps", "3"]), ("r", ["--gpus", "2", "--steps", "2"])):
+        d = str(tmp_path / name)
+        out = subprocess.run(base + argv + ["--dump-outputs", d], capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stdout + out.stderr
+        runs[name] = d
+    words, idx = _dumped(runs["a"])
+    w = bench.StubWorkload(bench.parse_args(["--stub", "--config", "4", "--batch", "4"]), 0, 0)
+    for _ in range(3):  # warmup + steps
+        w.step()
+    want = w.results()[:, :2].reshape(-1).numpy().view(np.uint64)
+    assert np.array_equal(idx, np.arange(want.size)) and np.array_equal(words, want)
+    assert all(np.array_equal(x, y) for x, y in zip(_dumped(runs["b"]), (words, idx)))
+    assert not np.array_equal(_dumped(runs["c"])[0], words)
+    assert np.array_equal(_dumped(runs["r"], "_rank0")[0], words)
+    assert not np.array_equal(_dumped(runs["r"], "_rank1")[0], words)
+    # over the budget: a sorted seeded sample, the same each time, whose words are those at its indices
+    w = bench.StubWorkload(bench.parse_args(["--stub", "--batch", "8300"]), 0, 0)
+    w.step()
+    flat = w.results()[:, :2].reshape(-1).numpy().view(np.uint64)
+    assert flat.size > bench.DUMP_WORDS
+    for d in ("s1", "s2"):
+        n = bench.dump_outputs(w, str(tmp_path / d))
+        assert n == bench.DUMP_WORDS
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= 64e6
+    s, sidx = _dumped(str(tmp_path / "s1"))
+    assert (np.diff(sidx) > 0).all() and sidx[-1] < flat.size and np.array_equal(s, flat[sidx])
+    assert all(np.array_equal(x, y) for x, y in zip(_dumped(str(tmp_path / "s2")), (s, sidx)))
+    # --steps is the number of timed steps: none is not a run
+    out = subprocess.run(base + ["--gpus", "1", "--steps", "0"], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr, out.stderr
+
+
 def _build_adapter(tmp_path):
     import subprocess
 
