@@ -2429,6 +2429,13 @@ namespace sealhip
             static const bool off = std::getenv("SEALHIP_NTT_NO_FP64") != nullptr;
             return !off;
         }
+        // SEALHIP_NTT_EXACT_FWD: the forward transform's shortcuts off (the reference's own sequence). Read once per process,
+        // here only: the STRICT-drop rule, the dense schedule and ntt_strict_top_done_ok must agree about it within a process
+        inline bool exact_fwd()
+        {
+            static const bool on = std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr;
+            return on;
+        }
 
         template <int LOGN>
         hipError_t launch_half_inv(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags,
@@ -2640,8 +2647,7 @@ namespace sealhip
             // the flag is dropped for the launch (round 4). The `_lazy` entries and the 60-bit rows keep the corrected sequence.
             if ((flags & kNttStrict) != 0 && (flags & (kNttAnyRep | kNttCanonical | kNttApprox)) != 0 && (flags & kNttReduceOut) == 0)
             {
-                static const bool exact_fwd = std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr;
-                bool ok = !exact_fwd;
+                bool ok = !exact_fwd();
                 for (int i = 0; ok && i < live.n; i++)
                     ok = bounds::fwd_canon_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
                 if (ok)
@@ -2652,7 +2658,7 @@ namespace sealhip
             // ntt_bounds.hpp section 2b instead of a conditional subtraction per butterfly -- the reference's own butterfly,
             // every word brought back below 2p before rounds 2 and 3 and in the store. Same residues, nothing wraps.
             bool dense = SEALHIP_NTT_FWD_DENSE_DEFAULT && (flags & kNttStrict) != 0 && (flags & kNttReduceOut) != 0 && (flags & kNttAnyRep) != 0 &&
-                         (flags & kNttCanonical) == 0 && !src.base[0] && std::getenv("SEALHIP_NTT_EXACT_FWD") == nullptr;
+                         (flags & kNttCanonical) == 0 && !src.base[0] && !exact_fwd();
             for (int i = 0; dense && i < live.n; i++)
                 dense = bounds::fwd_dense_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
             // SEALHIP_NTT_NO_TICKET=1 (A/B of the hand-off cost) re-opens the race: read by the measurement-only build alone
@@ -2757,8 +2763,7 @@ namespace sealhip
             {
                 // the last layer may keep its first operand unreduced only if the grown values cannot wrap
                 // (below (2 log n + 3) p < 2^64 for p < 2^58) and nothing expects the [0, 4p) output range
-                static const bool exact_only = std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr;
-                bool ok = !exact_only && (flags & (kNttCanonical | kNttStrict)) == 0;
+                bool ok = !exact_fwd() && (flags & (kNttCanonical | kNttStrict)) == 0;
                 for (int i = 0; ok && i < live.n; i++)
                     ok = bounds::fwd_lazy_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
                 if (!ok)
@@ -2779,7 +2784,7 @@ namespace sealhip
             // lies in [0, 3p), every layer adds 3p instead of 2p and the outputs are below 50p (kNttAnyRep) or 5p. Only where
             // the consumer reduces whatever representative it reads, nothing expects the [0, 4p) range (no canonicalising
             // wrapper, no kNttReduceOut) and 50p cannot wrap: every live prime below 2^58.
-            static const bool no_apx = std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr;
+            const bool no_apx = exact_fwd();
             bool apx = !no_apx && (flags & kNttApprox) != 0 && (flags & (kNttStrict | kNttCanonical | kNttReduceOut)) == 0 &&
                        red != 4 && red != 5 && red != 7;
             for (int i = 0; apx && i < live.n; i++)
@@ -3020,6 +3025,8 @@ namespace sealhip
         };
         // (round 4: the two-pass split for logn > 13 -- strided columns, then contiguous rows -- went with its switch
         //  SEALHIP_NTT_TWO_PASS: rings of 2^14 .. 2^16 are served by the single-pass kernels below, nothing else reached it)
+        // (unreachable: launch_ntt serves rings above 2^13 with the single-pass kernels, the empty batch included, and
+        //  refuses them itself before it gets here; this throw must never escape a hipError_t launcher)
         if (logn > kTileBitsMax)
             throw std::logic_error("plan_ntt: rings above 2^13 take the single-pass kernels");
         plan.npass = 1;
@@ -3252,7 +3259,7 @@ namespace sealhip
     // dense lazy schedule has an instance that starts below it (launch_half)
     bool ntt_strict_top_done_ok(const Engine &e, const RowMap &map)
     {
-        if (!SEALHIP_NTT_FWD_DENSE_DEFAULT || !e.use_half_kernel || e.logn < 14 || e.logn > 16 || std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr)
+        if (!SEALHIP_NTT_FWD_DENSE_DEFAULT || !e.use_half_kernel || e.logn < 14 || e.logn > 16 || exact_fwd())
             return false;
         for (int r = 0; r < map.rows; r++)
             if (map.prime[r] != kSkipRow && !bounds::fwd_dense_admits(e.tables[map.prime[r]].p, e.logn))
@@ -3316,9 +3323,11 @@ namespace sealhip
 
     hipError_t launch_ntt(const Engine &e, u64 *data, size_t nrows, const RowMap &map, bool inverse, int flags)
     {
+        if (nrows == 0)
+            return hipSuccess; // the reference's loops over an empty range (every ring size: plan_ntt serves 2^13 and below only)
         if (e.mode_strict)
             flags |= kNttStrict;
-        if (!inverse && e.use_half_kernel && nrows > 0)
+        if (!inverse && e.use_half_kernel)
         {
             // single-pass forward transform for the large rings
             NttSource none{};
@@ -3329,7 +3338,7 @@ namespace sealhip
             if (e.logn == 16)
                 return launch_half<16>(e, data, nrows, map, flags, none);
         }
-        if (inverse && e.use_half_kernel && nrows > 0)
+        if (inverse && e.use_half_kernel)
         {
             if (e.logn == 14)
                 return launch_half_inv<14>(e, data, nrows, map, flags);
@@ -3338,6 +3347,8 @@ namespace sealhip
             if (e.logn == 16)
                 return launch_half_inv<16>(e, data, nrows, map, flags);
         }
+        if (e.logn > kTileBitsMax)
+            return hipErrorInvalidValue; // (no single-pass kernel for this ring: never plan_ntt's throw)
         const NttPlan plan = plan_ntt(e.logn, inverse, flags);
         return inverse ? launch_dir<1>(e, data, nrows, map, plan) : launch_dir<0>(e, data, nrows, map, plan);
     }

@@ -6,12 +6,16 @@
 //    operations as devmath.hpp: multiply, fma, rint) on adversarial operands against exact __int128 arithmetic, and whole
 //    transforms run through the schedules with every intermediate magnitude tracked -- none may exceed what the
 //    recurrence predicts, and every value must stay congruent to an exact integer shadow.
+// 4. --classes: prints, as JSON, the largest prime value each predicate of the standalone NTT entries' dispatch admits at
+//    log n = 14, 15, 16 (tests/golden/ntt_instance_classes.json; the GPU matrix of tests/test_gpu_parity.py takes its
+//    prime classes from that fixture, and tests/test_host.py requires this output to equal it).
 // Invariant restated: native/src/seal/util/defines.h:52-53 (lazy arithmetic fits the word), butterflies util/ntt.cpp:245-281.
 #include <cfenv>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "../gemini-seal_amd/csrc/ntt_bounds.hpp"
@@ -597,8 +601,57 @@ static void dotacc_execution()
     CHECK(!dotacc_ok(8, kDotAccOperandBits + 1), "DotAcc predicate not tight at 62 bits");
 }
 
-int main()
+// ---- 4. the instance classes of the standalone entries (launch_half / launch_half_inv in ntt.hip, flags kNttCanonical):
+// the largest value p for which each admission holds, found by bisection over [lo, 2^61] from an admitted lo (every predicate
+// here is monotone above it: the recurrences grow with p, the single-precision quotient loss shrinks with it)
+template <class Pred>
+static u64 largest_admitted(Pred pred, u64 lo)
 {
+    const u64 top = u64(1) << kMaxPrimeBits;
+    if (!pred(lo))
+        return 0;
+    if (pred(top))
+        return top;
+    u64 a = lo, b = top; // pred(a), !pred(b)
+    while (b - a > 1)
+    {
+        const u64 m = a + (b - a) / 2;
+        (pred(m) ? a : b) = m;
+    }
+    return a;
+}
+
+static int print_classes()
+{
+    const u64 lo = kSmallQuotMinPrime; // 2^45: admitted by every predicate below
+    std::printf("{\n");
+    for (int logn = kMinHalfLogn; logn <= kMaxHalfLogn; logn++)
+    {
+        // the inverse launcher's standalone shapes: the whole-row form at 2^14 / 2^15 (kInvLayers<LOGN + 1> = log n layers,
+        // admitted only if the half-row shape's predicate holds too), the quarter-row form at 2^16 (kInvLayers<15> = 14)
+        const int T = logn <= 15 ? logn : logn - 2, T_half = logn - 1;
+        const bool whole = logn <= 15;
+        auto inv_lazy = [&](u64 p) { return inv_lazy_admits(T, p) && (!whole || inv_lazy_admits(T_half, p)); };
+        auto inv_dense = [&](u64 p) {
+            return inv_dense_admits(T, p) && (!whole || inv_lazy_admits(T_half, p) || inv_dense_admits(T_half, p));
+        };
+        const u64 fp = (u64(1) << kFpPrimeBits) - 1; // engine.hpp kFpPrimeBound: p below 2^50
+        const u64 canon = largest_admitted([&](u64 p) { return fwd_canon_admits(p, logn); }, lo);
+        const u64 sq = largest_admitted([&](u64 p) { return small_quot_admits(p, fwd_canon_output_mult(logn)); }, lo);
+        const u64 dense = largest_admitted([&](u64 p) { return fwd_dense_admits(p, logn); }, lo);
+        const u64 il = largest_admitted(inv_lazy, lo), id = largest_admitted(inv_dense, lo);
+        std::printf("  \"%d\": {\"fp64\": %llu, \"fwd_canon\": %llu, \"fwd_canon_small_quot\": %llu, \"fwd_dense\": %llu, "
+                    "\"inv_lazy\": %llu, \"inv_dense\": %llu, \"inv_shape\": \"%s\", \"inv_layers\": %d}%s\n",
+                    logn, fp, canon, sq, dense, il, id, whole ? "whole-row" : "quarter-row", T, logn < kMaxHalfLogn ? "," : "");
+    }
+    std::printf("}\n");
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && std::string(argv[1]) == "--classes")
+        return print_classes();
     std::fesetround(FE_TONEAREST);
     dotacc_execution();
     enumerate_predicates();

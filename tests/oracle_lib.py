@@ -471,3 +471,133 @@ def negacyclic_mod_t(a, b, t):
     for i in range(n, 2 * n - 1):
         res[i - n] -= int(full[i])
     return np.array([v % t for v in res], dtype=np.uint64)
+
+
+# ---------------------------------------------------------------- the negacyclic NTT from its definition (no oracle tables)
+# util/ntt.cpp above ntt_negacyclic_harvey_lazy: the forward transform maps a(x) in Z_p[x]/(x^N + 1) to
+# A[j] = a(psi^(2 bitrev(j) + 1)) mod p, psi the minimal primitive 2N-th root of unity mod p; the inverse maps back (n^-1
+# included). Python integers throughout: exact for every prime, whatever the reference's lazy words do.
+_MR_BASES = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41)  # deterministic Miller-Rabin below 3.3e24
+
+
+def is_prime(v):
+    v = int(v)
+    if v < 2:
+        return False
+    for b in _MR_BASES:
+        if v % b == 0:
+            return v == b
+    d, s = v - 1, 0
+    while d % 2 == 0:
+        d, s = d // 2, s + 1
+    for b in _MR_BASES:
+        x = pow(b, d, v)
+        if x in (1, v - 1):
+            continue
+        for _ in range(s - 1):
+            x = x * x % v
+            if x == v - 1:
+                break
+        else:
+            return False
+    return True
+
+
+def ntt_primes_around(value, logn):
+    """The three largest NTT primes (p = 1 mod 2N) at most `value`, and the three smallest above it."""
+    m = 2 << logn
+    below, above = [], []
+    c = (int(value) - 1) // m * m + 1
+    while len(below) < 3 and c > m:
+        if is_prime(c):
+            below.append(c)
+        c -= m
+    c = (int(value) - 1) // m * m + 1 + m
+    while len(above) < 3:
+        if is_prime(c):
+            above.append(c)
+        c += m
+    return below, above
+
+
+def bitrev(j, logn):
+    return int(format(j, "0%db" % logn)[::-1], 2) if logn else 0
+
+
+def minimal_psi(p, logn):
+    """The minimal primitive 2N-th root of unity mod p, from scratch: one primitive root psi0 (psi0^N = -1 is enough for a
+    power of two), then the smallest of its odd powers -- the primitive 2N-th roots are exactly those."""
+    n2 = 2 << logn
+    assert (p - 1) % n2 == 0 and is_prime(p), (p, logn)
+    g = 2
+    while True:
+        psi0 = pow(g, (p - 1) // n2, p)
+        if pow(psi0, n2 // 2, p) == p - 1:
+            break
+        g += 1
+    best, r, step = psi0, psi0, psi0 * psi0 % p
+    for _ in range(n2 // 2 - 1):
+        r = r * step % p
+        best = min(best, r)
+    return best
+
+
+class MathNtt:
+    """Radix-2 negacyclic transforms over Python integers (numpy object arrays), and the O(N) evaluation of the definition
+    at single indices that pins them."""
+
+    def __init__(self, logn, p):
+        self.logn, self.n, self.p = logn, 1 << logn, int(p)
+        self.psi = minimal_psi(self.p, logn)
+        self.psi_inv = pow(self.psi, self.p - 2, self.p)
+        self.n_inv = pow(self.n, self.p - 2, self.p)
+        pw, pwi, a, b = [], [], 1, 1
+        for _ in range(self.n):
+            pw.append(a)
+            pwi.append(b)
+            a, b = a * self.psi % self.p, b * self.psi_inv % self.p
+        br = [bitrev(i, logn) for i in range(self.n)]
+        self.w = np.array([pw[br[i]] for i in range(self.n)], dtype=object)  # psi^bitrev(i)
+        self.wi = np.array([pwi[br[i]] for i in range(self.n)], dtype=object)
+        self.br = br
+
+    def forward(self, a):
+        p, x = self.p, np.array([int(v) % self.p for v in a], dtype=object)
+        m, t = 1, self.n
+        while m < self.n:
+            t //= 2
+            v = x.reshape(m, 2, t)
+            u, y = v[:, 0, :].copy(), v[:, 1, :] * self.w[m:2 * m].reshape(m, 1) % p
+            v[:, 0, :], v[:, 1, :] = (u + y) % p, (u - y) % p
+            m *= 2
+        return x
+
+    def inverse(self, a):
+        p, x = self.p, np.array([int(v) % self.p for v in a], dtype=object)
+        m, t = self.n // 2, 1
+        while m >= 1:
+            v = x.reshape(m, 2, t)
+            u, y = v[:, 0, :].copy(), v[:, 1, :].copy()
+            v[:, 0, :], v[:, 1, :] = (u + y) % p, (u - y) * self.wi[m:2 * m].reshape(m, 1) % p
+            m //= 2
+            t *= 2
+        return x * self.n_inv % p
+
+    def forward_at(self, a, j):
+        """A[j] = a(psi^(2 bitrev(j) + 1)), Horner over the N coefficients"""
+        z, acc = pow(self.psi, 2 * self.br[j] + 1, self.p), 0
+        for c in reversed([int(v) for v in a]):
+            acc = (acc * z + c) % self.p
+        return acc
+
+    def inverse_at(self, A, i):
+        """a[i] = n^-1 sum_j A[j] psi^(-(2 bitrev(j) + 1) i)"""
+        y = pow(self.psi_inv, i, self.p)
+        y2, odd, acc = y * y % self.p, y, 0
+        pows = []
+        for _ in range(self.n):
+            pows.append(odd)
+            odd = odd * y2 % self.p
+        for j, v in enumerate(A):
+            acc += int(v) * pows[self.br[j]]
+        return acc % self.p * self.n_inv % self.p

@@ -2838,13 +2838,14 @@ def test_exact_ntt_variants_still_match_the_golden_digests():
     """The lazy-sum inverse and the last-layer shortcut of the forward transform are switched off with
     SEALHIP_NTT_EXACT_INV / SEALHIP_NTT_EXACT_FWD, the canonical transform's approximate-quotient schedule (round 3) with
     SEALHIP_NTT_CANON_EXACT (read once per process, hence the child process): the exact kernels
-    must reproduce the same golden digests of the compiled reference as the default ones do in this process."""
+    must reproduce the same golden digests of the compiled reference as the default ones do in this process, and the NTT
+    entries' matrix over the documented operand ranges must pass as it does here."""
     import subprocess
     import sys
 
     env = dict(os.environ, SEALHIP_NTT_EXACT_INV="1", SEALHIP_NTT_EXACT_FWD="1", SEALHIP_NTT_CANON_EXACT="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-p", "no:cacheprovider",
-                        "-k", "end_to_end_golden_digests or ntt_golden_digests or ntt_all_variants"],
+                        "-k", "end_to_end_golden_digests or ntt_golden_digests or ntt_all_variants or ntt_entries_over_the_documented_range or ntt_entries_on_key_and_bsk or transform_to_and_from_ntt"],
                        env=env, cwd=os.path.dirname(HERE), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     tail = r.stdout.decode("utf-8", "replace")[-400:]
     assert r.returncode == 0 and " passed" in tail, tail
@@ -2858,13 +2859,386 @@ def test_integer_instances_instead_of_fp64_still_match_the_golden_digests():
     SEALHIP_KS_MODDOWN_STORE_UNFUSED, SEALHIP_TENSOR_UNFUSED, SEALHIP_NTT_WHOLE_ROW, SEALHIP_NTT_TWO_PASS, SEALHIP_RNS_UNFUSED
     -- are gone from it: the first five exist in the measurement-only build alone, the last two were deleted with the
     two-launch transform. The forms they restored are still reached by PARAMETERS -- primes of 59+ bits, operand sizes
-    other than 2, nsp > 1, N = 2^16 and N = 2^14, STRICT mode, k > 16 -- and the tests with such parameters cover them.)"""
+    other than 2, nsp > 1, N = 2^16 and N = 2^14, STRICT mode, k > 16 -- and the tests with such parameters cover them.) The NTT
+    entries' matrix over the documented operand ranges runs here too: its FP64-class rows then take the integer instances."""
     import subprocess
     import sys
 
     env = dict(os.environ, SEALHIP_NTT_NO_FP64="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-p", "no:cacheprovider",
-                        "-k", "end_to_end_golden_digests or ntt_golden_digests or bench_launch_shapes or cfg4_rotate_large_batch"],
+                        "-k", "end_to_end_golden_digests or ntt_golden_digests or bench_launch_shapes or cfg4_rotate_large_batch or ntt_entries_over_the_documented_range or ntt_entries_on_key_and_bsk or transform_to_and_from_ntt"],
                        env=env, cwd=os.path.dirname(HERE), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     tail = r.stdout.decode("utf-8", "replace")[-400:]
     assert r.returncode == 0 and " passed" in tail, tail
+
+
+# ------------------------------------------------------------------ the four NTT entries over their documented operand ranges
+# include/sealhip.h: forward inputs below 4p, inverse inputs below 2p; `_lazy` = the reference's words (wrapped ones included),
+# canonical = the residues those words reduce to. launch_half / launch_half_inv pick an instance per prime class; every instance
+# is exact only inside a bound stated on that input range. The classes at 2^14..2^16 come from the predicates themselves
+# (tests/golden/ntt_instance_classes.json, pinned to csrc/ntt_bounds.hpp by tests/test_host.py).
+CLASSES = json.load(open(os.path.join(HERE, "golden", "ntt_instance_classes.json")))
+MATRIX_FIXED_BITS = (30, 49, 55, 59, 60, 61)
+_MATH = {}
+
+
+def _math(logn, p):
+    if (logn, p) not in _MATH:
+        if len(_MATH) >= 4:  # (the tables of a 2^16 prime are Python integers: keep a few)
+            _MATH.clear()
+        _MATH[(logn, p)] = O.MathNtt(logn, p)
+    return _MATH[(logn, p)]
+
+
+def ntt_matrix_classes(logn):
+    """[(label, three primes)] for one ring size: fixed sizes below 2^14; from 2^14 the three largest primes each predicate
+    admits and the three smallest it refuses (below 2^61), a 30-bit class, the largest 60- and 61-bit primes, and the largest
+    primes one bit above the canonical forward's limit (its predicate is stated in bits: the worst a one-bit slip admits)."""
+    top = lambda bits: O.ntt_primes_around((1 << bits) - 1, logn)[0]
+    if logn < 14:
+        return [("%dbit" % b, top(b)) for b in MATRIX_FIXED_BITS]
+    c = CLASSES[str(logn)]
+    out = []
+    for key in ("fp64", "fwd_canon", "fwd_canon_small_quot", "fwd_dense", "inv_lazy", "inv_dense"):
+        below, above = O.ntt_primes_around(c[key], logn)
+        out.append((key + "_max", below))
+        if max(above) < 1 << 61:
+            out.append((key + "_min_refused", above))
+    out += [("30bit", top(30)), ("60bit_max", top(60)), ("61bit_max", top(61)),
+            ("fwd_canon_next_bit_max", top(c["fwd_canon"].bit_length() + 1))]
+    seen, uniq = set(), []
+    for label, ps in out:
+        if tuple(ps) not in seen:
+            seen.add(tuple(ps))
+            uniq.append((label, ps))
+    return uniq
+
+
+def _special_prime(logn, avoid):
+    return next(p for p in O.ntt_primes_around((1 << 40) - 1, logn)[0] if p not in avoid)
+
+
+def ntt_range_patterns(rng, mods, n, mult, count=7):
+    """count polynomials x len(mods) rows over [0, mult p): residues; every word mult p - 1; alternating 0 / mult p - 1;
+    half 0, half mult p - 1; words across [(mult - 1) p, mult p); random over [0, mult p); and 0, p - 1, p, 2p, 3p (those below
+    mult p) and mult p - 1 planted at 0, N/4, N/2, N - 1 (and next to them) on a random background. Further polynomials
+    repeat the kinds with fresh random words."""
+    x = np.zeros((count, len(mods), n), dtype=np.uint64)
+    for c in range(count):
+        kind = c % 7 if count > 1 else 6
+        for i, p in enumerate(mods):
+            top = mult * p - 1
+            if kind == 0:
+                x[c, i] = rng.integers(0, p, n, dtype=np.uint64)
+            elif kind == 1:
+                x[c, i] = top
+            elif kind == 2:
+                x[c, i, ::2] = top
+            elif kind == 3:
+                x[c, i, n // 2:] = top
+            elif kind == 4:
+                x[c, i] = rng.integers((mult - 1) * p, mult * p, n, dtype=np.uint64)
+            else:
+                x[c, i] = rng.integers(0, mult * p, n, dtype=np.uint64)
+            if kind == 6:
+                vals = [v for v in (0, p - 1, p, 2 * p, 3 * p) if v < top] + [top]
+                spots = [0, 1, n // 4, n // 4 + 1, n // 2, n // 2 + 1, n - 2, n - 1]
+                for j, s in enumerate(spots):
+                    x[c, i, s] = vals[(j + i) % len(vals)]
+    return x
+
+
+def _oracle_rows(x, tabs, fn):
+    e = x.copy()
+    for c in range(e.shape[0]):
+        for i, t in enumerate(tabs):
+            fn(O.ptr(e[c, i]), C.byref(t))
+    return e
+
+
+_INV_CACHE = {}
+
+
+def _oracle_inverse(x, tabs, fn):
+    """the inverse words do not depend on the mode: one oracle run per input for PARITY and STRICT"""
+    key = (id(fn), tuple(int(t.mod.value) for t in tabs), x.shape, hash(x.tobytes()))
+    if key not in _INV_CACHE:
+        if len(_INV_CACHE) > 16:
+            _INV_CACHE.clear()
+        _INV_CACHE[key] = _oracle_rows(x, tabs, fn)
+    return _INV_CACHE[key]
+
+
+_MATH_ROWS = {}
+
+
+def _math_row(logn, p, row, inverse):
+    """the math reference of one row, computed once for PARITY and STRICT"""
+    key = (logn, p, inverse, hash(row.tobytes()))
+    if key not in _MATH_ROWS:
+        if len(_MATH_ROWS) >= 16:
+            _MATH_ROWS.clear()
+        M = _math(logn, p)
+        _MATH_ROWS[key] = np.array(M.inverse(row) if inverse else M.forward(row), dtype=np.uint64)
+    return _MATH_ROWS[key]
+
+
+FWD_LAZY = {0: lambda r, t: L.ref_ntt_forward_lazy(r, t, 0), 1: lambda r, t: L.ref_ntt_forward_lazy(r, t, 1)}
+FWD = {0: lambda r, t: L.ref_ntt_forward(r, t, 0), 1: lambda r, t: L.ref_ntt_forward(r, t, 1)}
+INV_LAZY, INV = L.ref_ntt_inverse_lazy, L.ref_ntt_inverse
+
+
+def check_four_entries(sealhip, ctx, mods, tabs, k, base, strict, x_fwd, x_inv, what, math_rows=()):
+    """The four entries on x_fwd ([0, 4p)) / x_inv ([0, 2p)), count = x.shape[0], word for word against the oracle
+    (PARITY: the reference's words; STRICT: Harvey's corrected forward sequence, i.e. the mathematics). `math_rows`:
+    (poly, row) pairs whose canonical results must also equal the math reference."""
+    count = x_fwd.shape[0]
+    mcol = np.array(mods, dtype=np.uint64).reshape(1, -1, 1)
+    s = 1 if strict else 0
+    results = {}
+    for name, fn, x, ref in (("fwd_lazy", ctx.ntt_negacyclic_harvey_lazy, x_fwd, FWD_LAZY[s]),
+                             ("fwd", ctx.ntt_negacyclic_harvey, x_fwd, FWD[s]),
+                             ("inv_lazy", ctx.inverse_ntt_negacyclic_harvey_lazy, x_inv, INV_LAZY),
+                             ("inv", ctx.inverse_ntt_negacyclic_harvey, x_inv, INV)):
+        d = ctx.upload(x)
+        fn(d, count, k, base)
+        got = d.download(x.shape)
+        exp = _oracle_inverse(x, tabs, ref) if name.startswith("inv") else _oracle_rows(x, tabs, ref)
+        bad = np.argwhere((got != exp).any(axis=2))
+        assert bad.size == 0, (what, name, "strict" if strict else "parity", "(poly, row) differing:", bad[:8].tolist())
+        results[name] = got
+    if strict:  # the lazy words lie in the documented output ranges and reduce to the canonical results
+        assert (results["fwd_lazy"] < 4 * mcol).all() and (results["inv_lazy"] < 2 * mcol).all(), what
+        assert np.array_equal(results["fwd_lazy"] % mcol, results["fwd"]), what
+        assert np.array_equal(results["inv_lazy"] % mcol, results["inv"]), what
+    logn = int(x_fwd.shape[2]).bit_length() - 1
+    for c, i in math_rows:
+        assert np.array_equal(_math_row(logn, mods[i], x_fwd[c, i], False), results["fwd"][c, i]), (what, "math fwd", c, i)
+        assert np.array_equal(_math_row(logn, mods[i], x_inv[c, i], True), results["inv"][c, i]), (what, "math inv", c, i)
+    return results
+
+
+def _fwd_cannot_wrap(logn, p):
+    """the reference's forward words on inputs below 4p stay below (4 + 2 log n) p (ForwardLazy adds 2p per layer)"""
+    return (4 + 2 * logn) * p < 1 << 64
+
+
+@pytest.mark.parametrize("logn", [3, 4, 8, 12, 13, 14, 15, 16])
+def test_ntt_entries_over_the_documented_range_per_instance_class(sealhip, logn):
+    """Every NTT entry on BASE_Q, PARITY and STRICT, for each prime class of the ring size (context: three primes of the class
+    and a special prime), on inputs over the whole documented operand range with the extremes planted; count 7 (21 rows:
+    the eight XCD row chunks are not filled evenly) and count 1. PARITY: every word equals the oracle's, wrapped ones included,
+    and where the reference cannot wrap the canonical results of one row per class equal the math reference. STRICT: the
+    `_lazy` forward is Harvey's sequence word for word, the canonical results are the mathematics for every class -- 60-61
+    bits included, where PARITY wraps -- and the lazy words lie in [0, 4p) / [0, 2p)."""
+    n = 1 << logn
+    rng = np.random.default_rng(4000 + logn)
+    for label, mods in ntt_matrix_classes(logn):
+        kmods = list(mods) + [_special_prime(logn, mods)]
+        tabs = [O.Tables(logn, p) for p in mods]
+        traw = [t.t for t in tabs]
+        for count in (7, 1):
+            x_fwd = ntt_range_patterns(rng, mods, n, 4, count)
+            x_inv = ntt_range_patterns(rng, mods, n, 2, count)
+            for strict in (False, True):
+                ctx = sealhip.Context(sealhip.SCHEME_CKKS, logn, kmods, 1, 0,
+                                      mode=sealhip.MODE_STRICT if strict else sealhip.MODE_PARITY)
+                math_rows = ()
+                if count == 1 and (strict or all(_fwd_cannot_wrap(logn, p) for p in mods)):
+                    math_rows = [(0, 0)]
+                check_four_entries(sealhip, ctx, mods, traw, 3, sealhip.BASE_Q, strict, x_fwd, x_inv,
+                                   "logn=%d %s %s count=%d" % (logn, label, [p.bit_length() for p in mods], count), math_rows)
+    if logn == 15:  # an odd count of 37 polynomials (111 rows) at the canonical forward's boundary class
+        label, mods = next(c for c in ntt_matrix_classes(logn) if c[0] == "fwd_canon_max")
+        ctx = sealhip.Context(sealhip.SCHEME_CKKS, logn, list(mods) + [_special_prime(logn, mods)], 1, 0)
+        tabs = [O.Tables(logn, p) for p in mods]
+        check_four_entries(sealhip, ctx, mods, [t.t for t in tabs], 3, sealhip.BASE_Q, False,
+                           ntt_range_patterns(rng, mods, n, 4, 37), ntt_range_patterns(rng, mods, n, 2, 37), "count=37")
+
+
+@pytest.mark.parametrize("logn", [14, 15, 16])
+@pytest.mark.parametrize("strict", [False, True], ids=["parity", "strict"])
+def test_ntt_entries_on_key_and_bsk_bases_and_mixed_launches(sealhip, logn, strict):
+    """The four entries on BASE_KEY (every key prime, the special one included) and BASE_BSK (the 60-bit Bsk rows of a BFV
+    context) against the oracle's key / Bsk tables, and on BASE_Q of a context whose rows mix an FP64-class prime, a
+    sparse-lazy-class prime and a 60-bit prime: one launch is split into the floating-point rows and the integer rows
+    (split_by_fp), each row checked on its own. Inputs over [0, 4p) / [0, 2p), extremes planted, odd counts."""
+    n = 1 << logn
+    mode = sealhip.MODE_STRICT if strict else sealhip.MODE_PARITY
+    rng = np.random.default_rng(5000 + logn + 7 * strict)
+    top = lambda bits: O.ntt_primes_around((1 << bits) - 1, logn)[0][0]
+    kmods = [top(49), top(55), top(60), top(61)]
+    ctx = sealhip.Context(sealhip.SCHEME_CKKS, logn, kmods, 1, 0, mode=mode)
+    tabs = [O.Tables(logn, p) for p in kmods]
+    traw = [t.t for t in tabs]
+    # BASE_Q: FP64 + sparse + 60-bit rows in one launch
+    check_four_entries(sealhip, ctx, kmods[:3], traw[:3], 3, sealhip.BASE_Q, strict, ntt_range_patterns(rng, kmods[:3], n, 4, 5),
+                       ntt_range_patterns(rng, kmods[:3], n, 2, 5), "mixed BASE_Q", math_rows=[(4, 0), (4, 1)] if strict else [(4, 0)])
+    # BASE_KEY: all four key primes, at the top level and one below (the special prime stays in the base)
+    for k in (3, 2):
+        rows = kmods[:k] + kmods[3:]
+        check_four_entries(sealhip, ctx, rows, traw[:k] + traw[3:], k, sealhip.BASE_KEY, strict,
+                           ntt_range_patterns(rng, rows, n, 4, 3), ntt_range_patterns(rng, rows, n, 2, 3), "BASE_KEY k=%d" % k)
+    # BASE_BSK of a BFV context: the 60-bit Bsk primes (PARITY wraps there; the oracle's words are the yardstick)
+    bmods = O.coeff_modulus_create(n, [50, 50, 51])
+    bctx = sealhip.Context(sealhip.SCHEME_BFV, logn, bmods, 1, 65537, mode=mode)
+    ref = O.RefContext(1, logn, bmods, 1, 65537, mode=1 if strict else 0)
+    k = 2
+    rt = ref.rns_tool(k)
+    nb = bctx.bsk_size(k)
+    bsk = [int(rt.contents.Bsk[i].value) for i in range(nb)]
+    check_four_entries(sealhip, bctx, bsk, [rt.contents.Bsk_ntt[i] for i in range(nb)], k, sealhip.BASE_BSK, strict,
+                       ntt_range_patterns(rng, bsk, n, 4, 3), ntt_range_patterns(rng, bsk, n, 2, 3), "BASE_BSK")
+
+
+@pytest.mark.parametrize("logn,strict", [(12, False), (14, True), (15, False), (16, False)])
+def test_transform_to_and_from_ntt(sealhip, logn, strict):
+    """Evaluator::transform_to_ntt_inplace / transform_from_ntt_inplace (evaluator.cpp:1746-1839): ciphertexts of size 2 and 3,
+    an odd count, at the top level and one below it; polynomial by polynomial the same words as the canonical entries and as
+    the oracle's transforms."""
+    n = 1 << logn
+    kmods = O.coeff_modulus_create(n, [49, 55, 58, 60])
+    mode = sealhip.MODE_STRICT if strict else sealhip.MODE_PARITY
+    ctx = sealhip.Context(sealhip.SCHEME_CKKS, logn, kmods, 1, 0, mode=mode)
+    ev = sealhip.Evaluator(ctx)
+    tabs = [O.Tables(logn, p) for p in kmods]
+    rng = np.random.default_rng(6000 + logn)
+    count = 3
+    for k in (3, 2):
+        for size in (2, 3):
+            x = ntt_range_patterns(rng, kmods[:k], n, 1, count * size).reshape(count, size, k, n)
+            d = ctx.upload(x)
+            ev.transform_to_ntt_inplace(d, size, k, count)
+            fwd = d.download(x.shape)
+            e = ctx.upload(x)
+            ctx.ntt_negacyclic_harvey(e, count * size, k)
+            assert np.array_equal(fwd, e.download(x.shape)), (k, size)
+            exp = _oracle_rows(x.reshape(count * size, k, n), [t.t for t in tabs[:k]], FWD[1 if strict else 0])
+            assert np.array_equal(fwd.reshape(exp.shape), exp), (k, size)
+            ev.transform_from_ntt_inplace(d, size, k, count)
+            back = d.download(x.shape)
+            ctx.inverse_ntt_negacyclic_harvey(e, count * size, k)
+            assert np.array_equal(back, e.download(x.shape)), (k, size)
+            assert np.array_equal(back, x), (k, size)
+
+
+def _empty_batch_calls(S, ctx, scheme, b, i32, n_key, k):
+    """(name, thunk) for every entry of include/sealhip.h that takes a count, with count = 0 and valid arguments"""
+    Lb = S.lib()
+    h, n = ctx.handle, ctx.n
+    key = S.KSwitchKeys(ctx, np.zeros((ctx.kswitch_digits(k), 2, n_key, n), dtype=np.uint64))
+    keys = (C.c_void_p * 1)(key.handle)
+    elt = ctx.galois_elt_from_step(1)
+    elts = (C.c_uint32 * 1)(elt)
+    o = b + 8 * (4 * n_key * n)  # outputs: the second half of the buffer (no entry sees an aliased operand)
+    host = np.zeros(8, dtype=np.uint64)
+    hp = (C.c_void_p * 1)(host.ctypes.data)
+    flags = np.zeros(1, dtype=np.uint8)
+    bfv, ckks = scheme == S.SCHEME_BFV, scheme == S.SCHEME_CKKS
+    calls = []
+    bases = [S.BASE_Q, S.BASE_KEY] + ([S.BASE_BSK] if bfv else [])
+    for base in bases:
+        for name in ("ntt_negacyclic_harvey_lazy", "ntt_negacyclic_harvey", "inverse_ntt_negacyclic_harvey_lazy",
+                     "inverse_ntt_negacyclic_harvey"):
+            calls.append(("%s base=%d" % (name, base), lambda f=getattr(Lb, "sealhip_" + name), base=base: f(h, b, 0, k, base)))
+        calls += [
+            ("dyadic_product base=%d" % base, lambda base=base: Lb.sealhip_dyadic_product_coeffmod(h, b, b, 0, k, base, o)),
+            ("multiply_poly_scalar base=%d" % base, lambda base=base: Lb.sealhip_multiply_poly_scalar_coeffmod(h, b, 0, k, base, 3, o)),
+            ("add_poly base=%d" % base, lambda base=base: Lb.sealhip_add_poly_coeffmod(h, b, b, 0, k, base, o)),
+            ("sub_poly base=%d" % base, lambda base=base: Lb.sealhip_sub_poly_coeffmod(h, b, b, 0, k, base, o)),
+            ("negate_poly base=%d" % base, lambda base=base: Lb.sealhip_negate_poly_coeffmod(h, b, 0, k, base, o)),
+            ("modulo_poly_coeffs_63 base=%d" % base, lambda base=base: Lb.sealhip_modulo_poly_coeffs_63(h, b, 0, k, base, o)),
+        ]
+    E = Lb
+    calls += [
+        ("transform_to_ntt", lambda: E.sealhip_evaluator_transform_to_ntt(h, k, b, 2, 0)),
+        ("transform_from_ntt", lambda: E.sealhip_evaluator_transform_from_ntt(h, k, b, 2, 0)),
+        ("apply_galois", lambda: E.sealhip_apply_galois(h, b, 0, k, elt, o)),
+        ("apply_galois_ntt", lambda: E.sealhip_apply_galois_ntt(h, b, 0, k, elt, o)),
+        ("modup_rns", lambda: E.sealhip_modup_rns(h, k, 0, b, 0)),
+        ("rescale_special_rns_inplace", lambda: E.sealhip_rescale_special_rns_inplace(h, k, b, 0)),
+        ("switch_key_inplace", lambda: E.sealhip_switch_key_inplace(h, k, b, o, 0, key.handle)),
+        ("switch_key_partial", lambda: E.sealhip_switch_key_partial(h, k, b, 0, key.handle, 0, 1, o)),
+        ("switch_key_finish", lambda: E.sealhip_switch_key_finish(h, k, b, o, 0, 1)),
+        ("multiply", lambda: E.sealhip_evaluator_multiply(h, k, b, 2, b, 2, 0, o)),
+        ("square", lambda: E.sealhip_evaluator_square(h, k, b, 2, 0, o)),
+        ("relinearize", lambda: E.sealhip_evaluator_relinearize(h, k, b, 3, 0, keys, 1)),
+        ("mod_switch_to_next", lambda: E.sealhip_evaluator_mod_switch_to_next(h, k, b, 2, 0, o)),
+        ("mod_switch_to_next_strided", lambda: E.sealhip_evaluator_mod_switch_to_next_strided(h, k, b, 2, 2 * k * n, 0, o)),
+        ("apply_galois (evaluator)", lambda: E.sealhip_evaluator_apply_galois(h, k, b, 0, elt, key.handle)),
+        ("rotate_vector", lambda: E.sealhip_evaluator_rotate_vector(h, k, b, 0, 1, elts, keys, 1)),
+        ("multiply_host", lambda: E.sealhip_evaluator_multiply_host(h, k, hp, 2, hp, 2, 0, hp, keys, 1)),
+        ("relinearize_host", lambda: E.sealhip_evaluator_relinearize_host(h, k, hp, 3, 0, keys, 1)),
+        ("rotate_vector_host", lambda: E.sealhip_evaluator_rotate_vector_host(h, k, hp, 0, 1, elts, keys, 1)),
+        ("mod_switch_to_next_host", lambda: E.sealhip_evaluator_mod_switch_to_next_host(h, k, hp, 2, 0, hp)),
+        ("negate", lambda: E.sealhip_evaluator_negate(h, k, b, 2, 0, o)),
+        ("add", lambda: E.sealhip_evaluator_add(h, k, b, 2, b, 2, 0, o)),
+        ("sub", lambda: E.sealhip_evaluator_sub(h, k, b, 2, b, 2, 0, o)),
+        ("multiply_plain_ntt", lambda: E.sealhip_evaluator_multiply_plain_ntt(h, k, b, 2, 0, o, 0)),
+        ("add_plain", lambda: E.sealhip_evaluator_add_plain(h, k, b, 2, 0, o, k * n if ckks else n, 0)),
+        ("is_transparent", lambda: E.sealhip_is_transparent(h, k, b, 2, 0, flags.ctypes.data)),
+        ("is_data_valid_for", lambda: E.sealhip_is_data_valid_for(h, k, b, 2, 0, flags.ctypes.data)),
+        ("ciphertext_resize", lambda: E.sealhip_ciphertext_resize(h, k, b, 2, o, 3, 0)),
+        ("dot_product_ct_sk", lambda: E.sealhip_decryptor_dot_product_ct_sk(h, k, b, 2, 0, b, 1, o)),
+        ("encrypt_zero_symmetric", lambda: E.sealhip_encrypt_zero_symmetric(h, k, 1, b, i32, b, 0, o)),
+        ("encrypt_zero_asymmetric", lambda: E.sealhip_encrypt_zero_asymmetric(h, k, 1, b, i32, i32, 0, o)),
+    ]
+    if bfv:
+        calls += [
+            ("multiply_many", lambda: E.sealhip_evaluator_multiply_many(h, k, (C.c_void_p * 2)(b, b), 2, 0, keys, 1, o)),
+            ("exponentiate", lambda: E.sealhip_evaluator_exponentiate(h, k, b, 3, 0, keys, 1, o)),
+            ("multiply_plain", lambda: E.sealhip_evaluator_multiply_plain(h, k, b, 2, 0, o, 0)),
+            ("fastbconv_m_tilde", lambda: E.sealhip_fastbconv_m_tilde(h, k, b, 0, o)),
+            ("sm_mrq", lambda: E.sealhip_sm_mrq(h, k, b, 0, o)),
+            ("fast_floor", lambda: E.sealhip_fast_floor(h, k, b, 0, o)),
+            ("fastbconv_sk", lambda: E.sealhip_fastbconv_sk(h, k, b, 0, o)),
+            ("divide_and_round_q_last_inplace", lambda: E.sealhip_divide_and_round_q_last_inplace(h, k, b, 0)),
+            ("divide_and_round_q_last_ntt_inplace", lambda: E.sealhip_divide_and_round_q_last_ntt_inplace(h, k, b, 0)),
+            ("decrypt_scale_and_round", lambda: E.sealhip_decrypt_scale_and_round(h, k, b, 0, o)),
+            ("multiply_add_plain_with_scaling_variant",
+             lambda: E.sealhip_multiply_add_plain_with_scaling_variant(h, k, b, n, o, 2, 0, 0)),
+            ("batch_encode", lambda: E.sealhip_batch_encode(h, b, n, 0, o)),
+            ("batch_decode", lambda: E.sealhip_batch_decode(h, b, 0, o)),
+            ("batch_encode_int64", lambda: E.sealhip_batch_encode_int64(h, b, n, 0, o)),
+            ("batch_decode_int64", lambda: E.sealhip_batch_decode_int64(h, b, 0, o)),
+        ]
+    if ckks:
+        calls += [
+            ("rescale_to_next", lambda: E.sealhip_evaluator_rescale_to_next(h, k, b, 2, 0, o)),
+            ("rescale_to_next_strided", lambda: E.sealhip_evaluator_rescale_to_next_strided(h, k, b, 2, 2 * k * n, 0, o)),
+            ("rescale_to_next_host", lambda: E.sealhip_evaluator_rescale_to_next_host(h, k, hp, 2, 0, hp)),
+            ("ckks_encode", lambda: E.sealhip_ckks_encode(h, k, b, 4, 0, 2.0 ** 30, o)),
+            ("ckks_decode", lambda: E.sealhip_ckks_decode(h, k, b, 0, 2.0 ** 30, o)),
+            ("ckks_encode_value", lambda: E.sealhip_ckks_encode_value(h, k, 1.5, 2.0 ** 30, 0, o)),
+            ("ckks_encode_int64", lambda: E.sealhip_ckks_encode_int64(h, k, 7, 0, o)),
+        ]
+    return calls, (key, keys, host, hp, flags)
+
+
+@pytest.mark.parametrize("logn", [10, 14, 15, 16])
+@pytest.mark.parametrize("strict", [False, True], ids=["parity", "strict"])
+def test_every_counted_entry_accepts_an_empty_batch(sealhip, logn, strict):
+    """count = 0 is a no-op on every entry that takes a count, like the reference's loops over empty ranges -- at the ring
+    sizes of the single-pass NTT kernels too, where launch_ntt once fell through to the tiled planner and returned
+    COR_E_INVALIDOPERATION. Each call returns S_OK and the sentinel-filled buffer it is handed stays unchanged.
+    (2^10: the tiled kernels' sizes, the control.)"""
+    n = 1 << logn
+    mode = sealhip.MODE_STRICT if strict else sealhip.MODE_PARITY
+    failures = []
+    for scheme, bits, t in ((sealhip.SCHEME_BFV, [50, 50, 51], 786433), (sealhip.SCHEME_CKKS, [50, 40, 51], 0)):
+        kmods = O.coeff_modulus_create(n, bits)
+        ctx = sealhip.Context(scheme, logn, kmods, 1, t, mode=mode)
+        k = len(kmods) - 1
+        words = 8 * 4 * len(kmods) * n
+        sentinel = (np.arange(words, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) | np.uint64(1 << 63)
+        buf = ctx.upload(sentinel)
+        i32 = ctx.upload_i32(np.full(4 * n, -7, dtype=np.int32))
+        calls, keep = _empty_batch_calls(sealhip, ctx, scheme, buf.ptr, i32.ptr, len(kmods), k)
+        for name, fn in calls:
+            rc = fn() & 0xFFFFFFFF
+            if rc != 0:
+                failures.append((scheme, name, "0x%08x" % rc, sealhip.lib().sealhip_last_error_string().decode()))
+        ctx.synchronize()
+        assert np.array_equal(buf.download(), sentinel), (scheme, "the buffer changed")
+        del keep, calls
+    assert not failures, failures

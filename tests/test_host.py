@@ -370,6 +370,29 @@ def test_shortcut_bounds_are_proved_not_sampled(tmp_path):
     assert out.returncode == 0 and "bounds_check: OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_ntt_instance_classes_fixture_follows_the_predicates(tmp_path):
+    """tests/golden/ntt_instance_classes.json is what `bounds_check --classes` prints: per ring size 2^14..2^16, the largest
+    prime value each predicate of the standalone NTT entries' dispatch admits (FP64 bound, fwd_canon_admits, small_quot_admits
+    at fwd_canon_output_mult, fwd_dense_admits, inv_lazy_admits / inv_dense_admits for the inverse launcher's standalone
+    shapes). The GPU matrix takes its prime classes from the fixture: a change to a predicate fails here until the fixture,
+    and with it the matrix, follows."""
+    import json
+    import subprocess
+
+    exe = str(tmp_path / "bounds_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe,
+                           os.path.join(ROOT, "tests", "bounds_check.cpp")])
+    out = subprocess.run([exe, "--classes"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    with open(os.path.join(ROOT, "tests", "golden", "ntt_instance_classes.json")) as f:
+        committed = f.read()
+    assert out.stdout == committed
+    classes = json.loads(committed)
+    assert sorted(classes) == ["14", "15", "16"]
+    for logn, c in classes.items():
+        assert c["fp64"] == (1 << 50) - 1 and c["fwd_canon"] < c["fwd_dense"] < 1 << 60, (logn, c)
+
+
 # ---------------------------------------------------------------- SURVEY 8(f3): ciphertext wire format (host parsing, no GPU)
 def _wire():
     import importlib.util

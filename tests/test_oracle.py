@@ -693,3 +693,62 @@ def test_f4_ckks_encoder_slotwise_product():
         L.ref_dyadic_product_coeffmod(O.ptr(pa[r]), O.ptr(pb[r]), n, C.byref(ref.c.key_mod[r]), O.ptr(prod[r]))
     got = ck.decode(prod, scale * scale)
     assert np.max(np.abs(got - a * b)) < 1e-3 * np.max(np.abs(a * b))
+
+
+def test_math_reference_of_the_ntt_equals_the_oracle():
+    """oracle_lib.MathNtt (the negacyclic transform from its definition over Python integers, psi found from scratch) against
+    the oracle's ref_ntt_forward / ref_ntt_inverse on residues at log n = 3..16, for primes where the reference's lazy sums
+    cannot wrap (forward words below (4 + 2 log n) p < 2^64); its radix-2 form pinned by the O(N) evaluation of
+    A[j] = a(psi^(2 bitrev(j) + 1)) at sampled indices. Also: the STRICT (Harvey-corrected) oracle equals it at 60-61-bit
+    primes, where PARITY's words wrap; the GPU matrix uses the math reference as the yardstick there. Cost: one 2^16 row
+    must stay well under a second (the GPU tests budget on it)."""
+    import time
+
+    rng = np.random.default_rng(316)
+    for logn in range(3, 17):
+        n = 1 << logn
+        for bits in (30, 50, 56) if logn <= 12 else (50,):
+            p = O.ntt_primes_around((1 << bits) - 1, logn)[0][0]
+            assert (4 + 2 * logn) * p < 1 << 64
+            t0 = time.perf_counter()
+            M = O.MathNtt(logn, p)
+            x = rng.integers(0, p, n, dtype=np.uint64)
+            f = M.forward(x)
+            cost = time.perf_counter() - t0
+            if logn == 16:
+                assert cost < 0.8, cost
+            T = O.Tables(logn, p)
+            assert int(T.t.root) == M.psi
+            e = x.copy()
+            L.ref_ntt_forward(O.ptr(e), C.byref(T.t), 0)
+            assert np.array_equal(np.array(f, dtype=np.uint64), e), (logn, p)
+            i = e.copy()
+            L.ref_ntt_inverse(O.ptr(i), C.byref(T.t))
+            assert np.array_equal(i, x)
+            assert np.array_equal(np.array(M.inverse(e), dtype=np.uint64), x), (logn, p)
+            for j in sorted({0, 1, n // 2, n - 1, int(rng.integers(0, n))}):
+                assert M.forward_at(x, j) == int(e[j]), (logn, p, j)
+                if logn <= 12:
+                    assert M.inverse_at(e, j) == int(x[j]), (logn, p, j)
+    for logn in (4, 10, 12):
+        n = 1 << logn
+        for bits in (60, 61):
+            p = O.ntt_primes_around((1 << bits) - 1, logn)[0][0]
+            M, T = O.MathNtt(logn, p), O.Tables(logn, p)
+            x = rng.integers(0, 4 * p, n, dtype=np.uint64)
+            x[:4] = [4 * p - 1, 3 * p, 4 * p - 1, p]
+            s = x.copy()
+            L.ref_ntt_forward(O.ptr(s), C.byref(T.t), 1)
+            assert np.array_equal(np.array(M.forward(x), dtype=np.uint64), s), (logn, p)
+            y = x % np.uint64(2 * p)
+            L.ref_ntt_inverse(O.ptr(y), C.byref(T.t))
+            assert np.array_equal(np.array(M.inverse(x % np.uint64(2 * p)), dtype=np.uint64), y), (logn, p)
+
+
+def test_ntt_primes_around():
+    below, above = O.ntt_primes_around(1 << 40, 12)
+    assert len(below) == len(above) == 3 and below == sorted(below, reverse=True) and above == sorted(above)
+    assert below[0] < 1 << 40 < above[0] and all(O.is_prime(p) and p % (2 << 12) == 1 for p in below + above)
+    m = 2 << 12
+    assert not any(O.is_prime(c) for c in range(below[0] + m, above[0], m))
+    assert O.get_primes(1 << 12, 40, 3) == below  # the reference's own search, downwards from 2^40
