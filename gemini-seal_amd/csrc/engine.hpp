@@ -71,32 +71,19 @@ namespace sealhip
     };
     constexpr unsigned short kSrcReduce = 0x4000, kSrcSecond = 0x8000; // kSrcReduce: informational (rows that need it)
 
-    // A/B knobs (SEALHIP_NTT_NO_TICKET, _GATHER_TICKET, _POLY_MAJOR, _POLY_GROUP, _WHOLE_ROW, _CANON_BARRETT,
-    // SEALHIP_KS_MAC_GROUP, _KS_MODDOWN_UNFUSED, _KS_MODDOWN_STORE_UNFUSED, SEALHIP_LIFT_TOP_OFF) exist in the measurement-only
-    // build (`make exp`, -DSEALHIP_NTT_EXPERIMENT) alone: the shipping library reads none of them, so no environment variable
-    // can re-open a race or switch a proved path off. What the shipping library does read: the resource knobs
-    // SEALHIP_WORKSPACE_MB / SEALHIP_HOST_CHUNK / SEALHIP_HOST_THREADS and the switches that run the REFERENCE'S OWN operation
-    // sequences instead of the proved shortcuts: SEALHIP_NTT_EXACT_FWD, SEALHIP_NTT_EXACT_INV, SEALHIP_NTT_CANON_EXACT,
-    // SEALHIP_NTT_NO_FP64.
-    inline const char *exp_env(const char *name)
-    {
-#ifdef SEALHIP_NTT_EXPERIMENT
-        return std::getenv(name);
-#else
-        (void)name;
-        return nullptr;
-#endif
-    }
+    // Environment variables the library reads: the resource knobs SEALHIP_WORKSPACE_MB / SEALHIP_HOST_CHUNK /
+    // SEALHIP_HOST_THREADS and the switches that run the REFERENCE'S OWN operation sequences instead of the proved shortcuts:
+    // SEALHIP_NTT_EXACT_FWD, SEALHIP_NTT_EXACT_INV, SEALHIP_NTT_CANON_EXACT, SEALHIP_NTT_NO_FP64. Nothing else: no variable
+    // can re-open a race or switch a proved path off. (The A/B knobs of earlier rounds are gone with their
+    // measurement-only build; what they measured is recorded in DESIGN.md and profiles/.)
 
     constexpr int kNttCanonical = 1; // fuse the canonicalising wrapper (ntt.h:236-245 / :328-333)
     constexpr int kNttStrict = 2;    // Harvey-corrected forward butterflies
     constexpr int kNttAnyRep = 8;    // inverse: the consumer canonicalises, any representative below 2p may be stored
     constexpr int kNttReduceOut = 0x10; // forward, single-pass kernel: one more conditional subtraction, outputs in [0, 2p)
     constexpr int kNttApprox = 0x20;   // forward, with kNttAnyRep or a consumer that takes outputs below (2 + g) p: approximate quotient (ntt_bounds.hpp section 2)
-    constexpr int kNttPolyMajor = 0x4000;        // forward half kernel: live positions grouped item by item (ntt.hip half_block_map; group size in bits 16-23)
-    constexpr int kNttPolyMajorRequest = 0x8000; // (launcher-internal: resolved per arithmetic instance)
+    constexpr int kNttPolyMajor = 0x4000;        // forward half kernel: live positions grouped item by item (ntt_half.hpp half_block_map; group size in bits 16-23)
     constexpr int kNttSmallQuot = 0x1000000;     // (launcher-internal) canonical approximate-quotient launch: single-precision quotient estimate in the store
-    constexpr int kNttXchgTop = 0x2000000;       // (launcher-internal, SEALHIP_NTT_XCHG_TOP builds) the two workgroups of a row share the top layer
     constexpr int kNttDebugNoSignal = 0x40; // forward half kernel: never send the hand-off signal (tests of the time-out path)
     // forward, single-pass kernel, with kNttReduceOut, in place: the producer of the rows has already applied the top layer
     // (gap N/2) -- bfv_lift2 does for the Bsk rows it writes. Each workgroup then loads its own half only: no second read of

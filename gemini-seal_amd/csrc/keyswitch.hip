@@ -453,10 +453,6 @@ namespace sealhip
         // slices this kernel reads (2 * nd * rows rows) are too large to stay in the memory-side cache between groups
         // (profiles/r02/ks_mac_group.txt: config 4, 69 MB of key: 9.15 -> 7.96 ms per step; config 5, 251 MB: 9.38 -> 7.66;
         // config 3, 29 MB: 3.68 -> 3.60 at 16, but 3.9-4.1 at 32)
-        static const std::size_t forced = [] {
-            const char *env = exp_env("SEALHIP_KS_MAC_GROUP"); // (measurement-only build)
-            return env ? static_cast<std::size_t>(std::strtoull(env, nullptr, 10)) : std::size_t(0);
-        }();
         const std::size_t key_bytes = (2ull * h.nd * (h.k + h.nsp)) << (e.logn + 3);
         // (the largest candidate that still leaves 4096 workgroups -- two full rounds of the chip's resident set)
         const std::size_t cap = key_bytes > (std::size_t(48) << 20) ? 64 : 16;
@@ -467,8 +463,6 @@ namespace sealhip
                 mac_group = g;
                 break;
             }
-        if (forced)
-            mac_group = forced;
         const std::size_t groups = (count + mac_group - 1) / mac_group;
         const std::size_t glanes = (groups * static_cast<std::size_t>(h.k + h.nsp)) << e.logn;
 #define SEALHIP_KS_MAC(ND)                                                                                          \

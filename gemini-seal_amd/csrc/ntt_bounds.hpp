@@ -149,10 +149,7 @@ namespace sealhip
         //                units short of floor(y w / p) at most, quotient_shortfall below);
         //   unreduced gathered inputs (key-switch mod-up without the conditional subtraction): inputs below 2p not p.
         // All log n layers count (the top one is applied on load).
-#ifndef SEALHIP_NTT_APX
-#define SEALHIP_NTT_APX 2
-#endif
-        constexpr int kFwdApxLevel = SEALHIP_NTT_APX;
+        constexpr int kFwdApxLevel = 2;
         static_assert(kFwdApxLevel == 1 || kFwdApxLevel == 2, "approximate-quotient form");
         // how far below floor(y w / p) the quotient estimate can fall, as the number of dropped terms that each lose less
         // than one unit: Shoup's floor(w 2^64 / p) itself (1), hi32(y0 s0) (level 1 and 2: together with the floor of the

@@ -292,7 +292,7 @@ namespace sealhip
             // The gathered transform is handed the integer P - r < P instead of the residue (-(s mod P)) mod q_i: the same
             // word wherever P <= q_i; where q_i < P < 2 q_i it is an unreduced input below 2 q_i, which the lazy forward
             // transform takes as it is only while nothing can wrap (ntt_bounds.hpp section 2, inputs below 2p).
-            bool fold_ok = ckks && e.nsp == 1 && ntt_can_gather(e) && exp_env("SEALHIP_KS_MODDOWN_UNFUSED") == nullptr;
+            bool fold_ok = ckks && e.nsp == 1 && ntt_can_gather(e);
             for (int r = 0; fold_ok && r < k; r++)
             {
                 const u64 q = e.key_moduli[h.row_prime[r]];

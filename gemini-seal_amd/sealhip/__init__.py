@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SEALHIP_LIBRARY selects another build of the same HIP library (tools/: the measurement-only build); there is no
+# SEALHIP_LIBRARY selects another build of the same HIP library (tools/ab_build.sh, the sanitizer build); there is no
 # non-HIP implementation to select.
 LIB_PATH = os.environ.get("SEALHIP_LIBRARY") or os.path.join(os.path.dirname(_HERE), "lib", "libsealhip.so")
 

@@ -2857,7 +2857,7 @@ def test_integer_instances_instead_of_fp64_still_match_the_golden_digests():
     reference's own sequences. Child process (read once): the golden digests of the compiled reference must come out as
     they do here. (Round 4: the A/B knobs that restored REPLACED forms -- SEALHIP_LIFT_TOP_OFF, SEALHIP_KS_MODDOWN_UNFUSED,
     SEALHIP_KS_MODDOWN_STORE_UNFUSED, SEALHIP_TENSOR_UNFUSED, SEALHIP_NTT_WHOLE_ROW, SEALHIP_NTT_TWO_PASS, SEALHIP_RNS_UNFUSED
-    -- are gone from it: the first five exist in the measurement-only build alone, the last two were deleted with the
+    -- are gone from it: the first five were deleted with the measurement-only build that read them, the last two with the
     two-launch transform. The forms they restored are still reached by PARAMETERS -- primes of 59+ bits, operand sizes
     other than 2, nsp > 1, N = 2^16 and N = 2^14, STRICT mode, k > 16 -- and the tests with such parameters cover them.) The NTT
     entries' matrix over the documented operand ranges runs here too: its FP64-class rows then take the integer instances."""

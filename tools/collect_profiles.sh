@@ -45,7 +45,6 @@ find $out/stats4 -name "*kernel_stats.csv" -exec cp {} $out/cfg4_rotate_kernel_s
 rm -rf $out/stats4
 cd $root
 rm -rf $out/stats
-# 7. (round 4) STRICT mode through bench.py, and the quarter-row projection at N = 2^16 (needs lib/libsealhip_exp.so)
+# 7. (round 4) STRICT mode through bench.py
 python3 bench.py --mode strict > $out/bench_strict.jsonl 2> $out/bench_strict.err
-[ -f gemini-seal_amd/lib/libsealhip_exp.so ] && tools/n65536_projection.sh > $out/n65536_quarter_row_projection.txt 2>&1
 ls -la $out

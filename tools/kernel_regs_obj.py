@@ -1,5 +1,6 @@
 """Register / spill / scratch / LDS report of the gfx950 kernels in a BUILT object (what really ships), no recompilation:
-    python tools/kernel_regs_obj.py [gemini-seal_amd/build/ntt.hip.o] [--filter substr] [--spills-only]
+    python tools/kernel_regs_obj.py [object.o ...] [--filter substr] [--spills-only]
+(default: the NTT objects gemini-seal_amd/build/ntt.hip.o, ntt_fwd.hip.o and ntt_inv.hip.o)
 Unbundles the gfx950 code object from .hip_fatbin and reads its AMDGPU metadata notes (llvm-readelf --notes).
 tools/kernel_regs.py does the same from a hipcc -S assembly file."""
 import os
@@ -36,9 +37,10 @@ def kernels(path):
 
 def main():
     args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith("--") and sys.argv[i] != "--filter"]
-    path = args[0] if args else os.path.join(os.path.dirname(__file__), "..", "gemini-seal_amd", "build", "ntt.hip.o")
+    build = os.path.join(os.path.dirname(__file__), "..", "gemini-seal_amd", "build")
+    paths = args or [os.path.join(build, f) for f in ("ntt.hip.o", "ntt_fwd.hip.o", "ntt_inv.hip.o")]
     flt = sys.argv[sys.argv.index("--filter") + 1] if "--filter" in sys.argv else ""
-    recs = kernels(path)
+    recs = [r for path in paths for r in kernels(path)]
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in recs), capture_output=True,
                            text=True).stdout.splitlines()
     rows = []

@@ -101,7 +101,7 @@ out += ["```", "", "FP64 against integer NTT instances on 50-bit primes, same bo
         "Standalone transforms (`ntt_only.txt`: N = 2^15 on config 3's 55-bit primes = integer instances; 2^14 / 2^16 on 50-bit primes = FP64):", "```"]
 out += [l[:100] for l in rd("ntt_only.txt").splitlines() if l.startswith("logn")]
 out += ["```", "", "Round-4 experiment records in this directory:",
-        "- `fwd_quotient_ab.txt` (`tools/ab_r04_fwd.sh`, one box, three interleaved rounds, 57 344 rows per launch): the standalone canonical forward "
+        "- `fwd_quotient_ab.txt` (`tools/ab_r04_fwd.sh`, since removed; one box, three interleaved rounds, 57 344 rows per launch): the standalone canonical forward "
         "transform -- round 3's kernel (level-1 quotient, Barrett step in the store) 0.378-0.381, level-2 quotient on zero-high pairs 0.389-0.391, "
         "+ single-precision quotient estimate in the store **0.395** (+4.0 %).",
         "- `step_ab_vs_r03_kernels.txt` (`tools/ab_step.sh 1024 libsealhip.so libsealhip_apx1.so`): config 3 step over 1024 pairs, this round's transforms "
@@ -114,7 +114,7 @@ out += ["```", "", "Round-4 experiment records in this directory:",
         "- `bconv_mfma_ab.txt` (`tools/ubench_bconv_mfma.hip`, VERDICT r03 item 5): config 3's q -> Bsk base conversion as int8-MFMA byte-limb products, "
         "bit-exact against the shipped carry-free vector-ALU form on 134 M words: alone (memory-bound) it takes 158 % of the shipped form's time; repeated 4 x "
         "on the loaded words (arithmetic-bound, like the fused kernels) 92 %: -8 %, below the 15 % the verdict set as the bar. Closed.",
-        "- `n65536_quarter_row_projection.txt` (`tools/n65536_projection.sh`, VERDICT r03 item 2): the quarter-row inverse at N = 2^16 IS the N = 2^15 "
+        "- `n65536_quarter_row_projection.txt` (`tools/n65536_projection.sh`, since removed; VERDICT r03 item 2): the quarter-row inverse at N = 2^16 IS the N = 2^15 "
         "half-row kernel; on the same bytes it runs at 0.51 (FP64) / 0.40 (integer) against 0.38 / 0.30 for the 1024-lane half-row kernel at 2^16: "
         "projected standalone 2^16 inverse 0.27 / 0.24 against 0.237 / 0.205. **Then built** (quarter-row kernels + one streaming radix-4 pass, "
         "the default for standalone inverses at 2^16): the file shows both forms on one box -- measured **0.27 / 0.24**, the projection to the digit. "
