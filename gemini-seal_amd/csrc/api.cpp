@@ -557,6 +557,24 @@ long sealhip_debug_rns_constants(sealhip_context *ctx, uint32_t k, uint32_t whic
     });
 }
 
+long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t size_a, uint32_t size_b, int32_t square,
+                                     int32_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        Engine &e = *ctx->engine;
+        check_level(e, k);
+        if (size_a < 2 || size_b < 2 || size_a + size_b - 1 > 16) // check_multiply_args
+            throw std::invalid_argument("encrypted1 or encrypted2 is not valid for encryption parameters");
+        const BfvMulPlan p = plan_bfv_multiply(e, static_cast<int>(k), static_cast<int>(size_a), static_cast<int>(size_b),
+                                               square != 0);
+        const int32_t v[13] = { p.k, p.B, p.nB, p.square, p.redc_small, p.gather, p.defer, p.fused_tensor, p.tensor_apx,
+                                p.lift_top, p.lift_kernel, p.floor_kernel, p.deferred_top };
+        std::memcpy(out, v, sizeof v);
+    });
+}
+
 /* ---------------------------------------------------------------- NTT */
 long sealhip_ntt_negacyclic_harvey_lazy(sealhip_context *ctx, uint64_t *data, size_t count, uint32_t k, uint32_t base)
 {

@@ -599,14 +599,8 @@ namespace sealhip
                 rd.dsr_gamma = hr.gamma;
                 rd.gamma_prime = static_cast<unsigned>(n_key + 1); // aux primes: m_sk, gamma, B...
             }
-            // REDC lands below 2p iff (sum of the bounds of the variable factors) <= 2^64:
-            //   lift rows:   k terms t_i < q_i plus temp < b_j;  floor Bsk rows: in < b_j plus k terms < q_i;
-            //   conv_sk: B terms < b;  out rows: B terms tb_j < b_j plus alpha-term < m_sk
-            const u128 lim = static_cast<u128>(1) << 64;
-            // (with a deferred top layer the Bsk operand of the floor rows is a lazy value below 2 b_j)
-            const u128 s1 = static_cast<u128>(k) * max_q + 2 * static_cast<u128>(max_b);
-            const u128 s2 = static_cast<u128>(B + 1) * max_b;
-            rd.redc_small = (s1 <= lim && s2 <= lim) ? 1 : 0;
+            // every REDC of the fused kernels lands below 2p (ntt_bounds.hpp section 7; the same call as plan_bfv_multiply)
+            rd.redc_small = bounds::behz_redc_small(k, B, max_q, max_b) ? 1 : 0;
         }
         lt.h_rns = rd;
         lt.d_rns = upload<RnsDev>(*this, lt.owned, &rd, 1);

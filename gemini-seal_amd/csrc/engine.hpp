@@ -410,24 +410,45 @@ namespace sealhip
                                         std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count);
     hipError_t launch_sm_mrq(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in, std::size_t in_stride,
                              u64 *out, std::size_t out_stride, std::size_t count);
-    // fused fastbconv_m_tilde + sm_mrq: in k rows -> out |Bsk| rows
-    // top_layer: also apply the forward NTT's top layer to the rows written (exact-k instances only; the caller then
+    // The dispatch of one BFV multiply / square at level k (op_bfv_multiply): the pipeline forks and the instances of the
+    // two fused BEHZ kernels. op_bfv_multiply and the two launchers below consume it; sealhip_debug_bfv_multiply_plan
+    // reports it (host constants only: it works on host-only contexts).
+    constexpr int kBehzGeneric = 32; // instance codes: 1..bounds::kBehzExactMaxK exact k, 32 the run-time-k one (k <= 32),
+    constexpr int kBehzStepwise = 64; // 64 the step-by-step kernels (k > 32)
+    struct BfvMulPlan
+    {
+        int k, B, nB;       // level, |B|, |Bsk| = |B| + 1
+        bool square;        // the square path (size-2 operand, b == nullptr)
+        bool redc_small;    // bounds::behz_redc_small: every REDC of the fused kernels lands below 2p
+        bool gather;        // q rows gathered from the operands by the forward NTT
+        bool defer;         // inverse NTT leaves its top layer to the floor kernel
+        bool fused_tensor;  // tensor product formed by the inverse NTT on load (launch_intt_tensor)
+        bool tensor_apx;    // ... with the approximate-quotient forward transform
+        bool lift_top;      // lift applies the forward NTT's top layer (kNttTopDone)
+        int lift_kernel;    // instance code of the lift (above)
+        int floor_kernel;   // instance code of the floor
+        int deferred_top;   // floor input: 0 canonical, 1 top layer deferred, 2 and Montgomery-scaled (fused tensor)
+    };
+    BfvMulPlan plan_bfv_multiply(Engine &e, int k, int sa, int sb, bool square);
+
+    // fused fastbconv_m_tilde + sm_mrq: in k rows -> out |Bsk| rows, instance plan.lift_kernel
+    // plan.lift_top: also apply the forward NTT's top layer to the rows written (exact-k instances only; the caller then
     // transforms them with kNttTopDone). -> bfv_lift_can_apply_top tells whether this level has such an instance.
-    bool bfv_lift_can_apply_top(const Engine &e, const RnsDev &h);
+    bool bfv_lift_can_apply_top(const Engine &e, int k, bool redc_small);
     hipError_t launch_bfv_lift(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in, std::size_t in_stride,
-                               u64 *out, std::size_t out_stride, std::size_t count, bool top_layer = false);
+                               u64 *out, std::size_t out_stride, std::size_t count, const BfvMulPlan &plan);
     hipError_t launch_fast_floor(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in,
                                  std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count,
                                  int mul_t);
     hipError_t launch_fastbconv_sk(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in,
                                    std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count);
-    // fused (x t) + fast_floor + fastbconv_sk: in (k+|Bsk|) rows -> out k rows
-    // deferred_top != 0: `in` holds the output of the single-pass inverse kernel WITHOUT its top layer; the kernel
+    // fused (x t) + fast_floor + fastbconv_sk: in (k+|Bsk|) rows -> out k rows, instance plan.floor_kernel
+    // plan.deferred_top != 0: `in` holds the output of the single-pass inverse kernel WITHOUT its top layer; the kernel
     // applies that layer and the canonicalising subtraction while loading (needs ntt_can_defer_top(e))
-    // deferred_top == 2: as 1, and every input word carries the Montgomery factor 2^-64 (launch_intt_tensor)
+    // plan.deferred_top == 2: as 1, and every input word carries the Montgomery factor 2^-64 (launch_intt_tensor)
     hipError_t launch_bfv_floor_sk(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in,
                                    std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count,
-                                   int deferred_top = 0);
+                                   const BfvMulPlan &plan);
     bool ntt_can_defer_top(const Engine &e, int k);
     // reduce mode 7 available for a gathered launch over the first k ciphertext primes with this special prime?
     bool ntt_can_fuse_moddown(const Engine &e, int k, u64 p_special);

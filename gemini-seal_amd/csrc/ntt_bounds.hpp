@@ -437,5 +437,30 @@ namespace sealhip
                                      static_cast<long double>(mult) * (0x1p-20L + 3 * 0x1p-24L + 0x1p-51L);
             return loss <= 0.5L;
         }
+
+        // =====================================================================================================
+        // 7. The fused BEHZ kernels' Montgomery reductions (rns.hip bfv_lift2_kernel / bfv_floor_sk2_kernel, devmath.hpp
+        // redc128 + redc_finish). A REDC of acc = sum_i x_i c_i modulo p, with every constant c_i < p (host-folded
+        // Montgomery forms) and every variable factor x_i < X_i, returns (acc + m p) / 2^64 with m < 2^64, so it lands below
+        // acc / 2^64 + p < p (sum_i X_i / 2^64 + 1): below 2p whenever S = sum_i X_i <= 2^64. The sums, per stage:
+        //   lift Bsk rows:   k terms t_i < q_i, plus temp < b_j (the centred r_m_tilde)            S <= k max_q + max_b
+        //   floor Bsk rows:  k terms < q_i, plus the Bsk input < 2 b_j (a lazy value when the inverse NTT deferred its
+        //                    top layer)                                                                S <= k max_q + 2 max_b
+        //   conv_sk:         B terms tb_j < b_j                                                        S <= B max_b
+        //   floor q rows:    B terms tb_j < b_j, plus the alpha term < m_sk                            S <= (B + 1) max_b
+        // where max_q bounds the level's k ciphertext primes and max_b the |Bsk| = B + 1 auxiliary ones. The first two
+        // are dominated by s1 = k max_q + 2 max_b, the last two by s2 = (B + 1) max_b. When this holds the exact-k
+        // instances skip redc_finish's second reduction (RnsDev::redc_small); otherwise the generic instance keeps it.
+        constexpr bool behz_redc_small(int k, int B, u64 max_q, u64 max_b)
+        {
+            const u128 s1 = static_cast<u128>(k) * max_q + 2 * static_cast<u128>(max_b);
+            const u128 s2 = static_cast<u128>(B + 1) * max_b;
+            return k >= 1 && B >= 1 && s1 <= kWord && s2 <= kWord;
+        }
+        // max_b is m_sk, the largest 60-bit prime = 1 (mod 2N) (engine.cpp: get_primes(n, 60, ...)), within 2^55 of 2^60 at
+        // every ring size: s2 at |B| = 16 is then above 2^64, so no level with k >= 16 (|B| >= k) has an exact-k instance
+        static_assert(!behz_redc_small(15, 16, u64(1) << 40, (u64(1) << 60) - (u64(1) << 55)),
+                      "s2 at |B| = 16 for every m_sk");
+        constexpr int kBehzExactMaxK = 15; // the largest k with an exact-k BEHZ instance (rns.hip)
     } // namespace bounds
 } // namespace sealhip

@@ -407,6 +407,63 @@ namespace sealhip
     // b == nullptr: bfv_square of a size-2 ciphertext (evaluator.cpp:560-702) -- the two polynomials of `a` are lifted and
     // transformed once (:604-634) and the tensor product is c_0 = x_0^2, c_1 = x_0 x_1 added to itself, c_2 = x_1^2
     // (:644-657); everything after it is bfv_multiply's tail.
+    BfvMulPlan plan_bfv_multiply(Engine &e, int k, int sa, int sb, bool square)
+    {
+        if (e.scheme != 1)
+            throw std::invalid_argument("plan_bfv_multiply: BFV contexts only");
+        if (sa < 2 || sb < 2 || (square && (sa != 2 || sb != 2)))
+            throw std::invalid_argument("plan_bfv_multiply: operand sizes (the square path takes size-2 operands)");
+        LevelTools &lt = e.level_host(k);
+        const HostRnsTool &hr = *lt.host_rns;
+        BfvMulPlan p{};
+        p.k = k;
+        p.B = static_cast<int>(hr.B_size);
+        p.nB = static_cast<int>(hr.Bsk.size());
+        p.square = square;
+        u64 max_q = 0, max_b = 0;
+        for (int i = 0; i < k; i++)
+            max_q = std::max(max_q, hr.q[i]);
+        for (int j = 0; j < p.nB; j++)
+            max_b = std::max(max_b, hr.Bsk[j]);
+        p.redc_small = bounds::behz_redc_small(k, p.B, max_q, max_b);
+        const int kb = k + p.nB, sin = square ? sa : sa + sb, dest = sa + sb - 1;
+        // steps (1)-(3) (:335-353): the q rows are gathered straight from the operands by the forward NTT (no set_poly copy)
+        // when the single-pass kernel is available and one launch can describe all sin * (k + |Bsk|) rows of an item
+        p.gather = ntt_can_gather(e) && sin * kb <= kMaxRows;
+        // the single-pass inverse leaves its top layer (and the canonicalisation) to bfv_floor_sk, which applies it on load
+        p.defer = ntt_can_defer_top(e, k);
+        // with two size-2 operands the tensor product (step 4) is formed by the inverse NTT while it loads its rows (no
+        // separate pass over 7 rows per prime; launch_intt_tensor). Its Montgomery reduction lands below 2p on operands below
+        // 4p for ciphertext primes under 2^59 (the exact forward sequence), on operands below (2 + g) p -- what an
+        // approximate-quotient launch without kNttAnyRep stores -- for primes under 2^57 (ntt_bounds.hpp section 3:
+        // tensor_admits_apx); the Bsk rows are stored below 2p
+        p.fused_tensor = p.gather && p.defer && sa == 2 && sb == 2 && dest * kb <= kMaxRows;
+        p.tensor_apx = true;
+        for (int r = 0; r < k; r++)
+        {
+            p.fused_tensor = p.fused_tensor && bounds::tensor_admits_4p(e.key_moduli[r]);
+            p.tensor_apx = p.tensor_apx && bounds::tensor_admits_apx(e.key_moduli[r]);
+        }
+        for (int j = 0; j < p.nB; j++)
+            p.fused_tensor = p.fused_tensor && bounds::tensor_admits_2p(e.tables[lt.map_qbsk.prime[k + j]].p);
+        // the lift applies the forward transform's top layer to the Bsk rows it writes (kNttTopDone)
+        p.lift_top = p.fused_tensor && bfv_lift_can_apply_top(e, k, p.redc_small);
+        if (p.lift_top && e.mode_strict)
+        {
+            RowMap bsk{};
+            bsk.rows = p.nB;
+            for (int j = 0; j < p.nB; j++)
+                bsk.prime[j] = lt.map_qbsk.prime[k + j];
+            p.lift_top = ntt_strict_top_done_ok(e, bsk);
+        }
+        // the fused kernels: an exact-k instance where every REDC provably lands below 2p, else the run-time-k one; past
+        // k = 32 the step-by-step kernels (rns.hip launch_bfv_lift / launch_bfv_floor_sk)
+        const int code = k > 32 ? kBehzStepwise : p.redc_small && k <= bounds::kBehzExactMaxK ? k : kBehzGeneric;
+        p.lift_kernel = p.floor_kernel = code;
+        p.deferred_top = p.fused_tensor ? 2 : p.defer ? 1 : 0;
+        return p;
+    }
+
     void op_bfv_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out)
     {
         LevelTools &lt = e.level(k);
@@ -415,6 +472,11 @@ namespace sealhip
         const bool sq = b == nullptr;
         if (sq && (sa != 2 || sb != 2))
             throw std::logic_error("op_bfv_multiply: the square path takes size-2 operands");
+        const BfvMulPlan plan = plan_bfv_multiply(e, k, sa, sb, sq);
+        if (plan.nB != h.nB || plan.redc_small != (h.redc_small != 0))
+            throw std::logic_error("op_bfv_multiply: the plan and the level's device constants disagree");
+        const bool gather = plan.gather, defer = plan.defer, fused_tensor = plan.fused_tensor, tensor_apx = plan.tensor_apx,
+                   lift_top = plan.lift_top;
         const int nB = h.nB, kb = k + nB, sin = sq ? sa : sa + sb, dest = sa + sb - 1;
         const std::size_t w_x = static_cast<std::size_t>(sin) * kb * N;
         const std::size_t w_d = static_cast<std::size_t>(dest) * kb * N;
@@ -426,35 +488,7 @@ namespace sealhip
             e.ws_reset();
             u64 *X = e.ws_alloc(w_x * m);
             u64 *D = e.ws_alloc(w_d * m);
-            // steps (1)-(3) (:335-353): lift to Bsk (fastbconv_m_tilde + sm_mrq) and one lazy NTT over all rows;
-            // the q rows are gathered straight from the operands by the NTT kernel (no set_poly copy) when the
-            // single-pass kernel is available
-            const bool gather = ntt_can_gather(e) && sin * kb <= kMaxRows;
-            // With the single-pass kernels and two size-2 operands the tensor product (step 4) is formed by the inverse
-            // NTT while it loads its rows (no separate pass over 7 rows per prime; launch_intt_tensor)
-            const bool defer = ntt_can_defer_top(e, k);
-            bool fused_tensor = gather && defer && sa == 2 && sb == 2 && dest * kb <= kMaxRows;
-            // its Montgomery reduction lands below 2p on operands below 4p for ciphertext primes under 2^59 (the exact forward
-            // sequence), on operands below (2 + g) p -- what an approximate-quotient launch without kNttAnyRep stores --
-            // for primes under 2^57 (ntt_bounds.hpp section 3: tensor_admits_apx); the Bsk rows are stored below 2p
-            bool tensor_apx = true;
-            for (int r = 0; r < k; r++)
-            {
-                fused_tensor = fused_tensor && bounds::tensor_admits_4p(e.key_moduli[r]);
-                tensor_apx = tensor_apx && bounds::tensor_admits_apx(e.key_moduli[r]);
-            }
-            for (int j = 0; j < nB; j++)
-                fused_tensor = fused_tensor && bounds::tensor_admits_2p(e.tables[lt.map_qbsk.prime[k + j]].p);
-            // the lift applies the forward transform's top layer to the Bsk rows it writes (kNttTopDone below)
-            bool lift_top = fused_tensor && bfv_lift_can_apply_top(e, h);
-            if (lift_top && e.mode_strict)
-            {
-                RowMap bsk{};
-                bsk.rows = nB;
-                for (int j = 0; j < nB; j++)
-                    bsk.prime[j] = lt.map_qbsk.prime[k + j];
-                lift_top = ntt_strict_top_done_ok(e, bsk);
-            }
+            // steps (1)-(3) (:335-353): lift to Bsk (fastbconv_m_tilde + sm_mrq) and one lazy NTT over all rows
             for (int s = 0; s < sin; s++)
             {
                 const bool first = s < sa;
@@ -463,7 +497,7 @@ namespace sealhip
                 u64 *dst = X + s * poly_x;
                 if (!gather)
                     check(launch_copy_rows(e, src, src_stride, dst, w_x, m, k), "copy");
-                check(launch_bfv_lift(e, lt.d_rns, h, src, src_stride, dst + poly_q, w_x, m, lift_top), "bfv_lift");
+                check(launch_bfv_lift(e, lt.d_rns, h, src, src_stride, dst + poly_q, w_x, m, plan), "bfv_lift");
             }
             if (gather)
             {
@@ -531,7 +565,7 @@ namespace sealhip
                 {
                     SinkArm arm(e, I >= 1 ? sink_at(e, off) : nullptr); // polynomials 1.. of the product
                     check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, out + off * dest * poly_q + I * poly_q,
-                                              dest * poly_q, m, 2),
+                                              dest * poly_q, m, plan),
                           "floor_sk");
                 }
                 continue;
@@ -560,7 +594,7 @@ namespace sealhip
             {
                 SinkArm arm(e, I >= 1 ? sink_at(e, off) : nullptr);
                 check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, out + off * dest * poly_q + I * poly_q,
-                                          dest * poly_q, m, defer ? 1 : 0),
+                                          dest * poly_q, m, plan),
                       "floor_sk");
             }
         }

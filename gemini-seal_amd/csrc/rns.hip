@@ -852,26 +852,39 @@ namespace sealhip
         }
     } // namespace
 
-    bool bfv_lift_can_apply_top(const Engine &e, const RnsDev &h)
+    bool bfv_lift_can_apply_top(const Engine &e, int k, bool redc_small)
     {
         // (STRICT: the caller also asks ntt_strict_top_done_ok -- only the dense forward schedule starts below the top layer;
         //  the layer itself is the same butterfly on canonical words either way: nothing can wrap in it)
-        return h.redc_small && h.k >= 1 && h.k <= 16 && e.logn >= 14;
+        return redc_small && k >= 1 && k <= bounds::kBehzExactMaxK && e.logn >= 14;
+    }
+
+    // the instance code a plan names must be one this level can run (plan_bfv_multiply, pipeline.cpp)
+    static bool behz_instance_ok(const RnsDev &h, const BfvMulPlan &plan, int code)
+    {
+        if (plan.k != h.k || plan.redc_small != (h.redc_small != 0))
+            return false;
+        if (code == kBehzStepwise)
+            return h.k > 32;
+        if (code == kBehzGeneric)
+            return h.k <= 32;
+        return code == h.k && h.redc_small && h.k <= bounds::kBehzExactMaxK;
     }
 
     hipError_t launch_bfv_lift(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in, std::size_t in_stride,
-                               u64 *out, std::size_t out_stride, std::size_t count, bool top_layer)
+                               u64 *out, std::size_t out_stride, std::size_t count, const BfvMulPlan &plan)
     {
         if (!count)
             return hipSuccess;
-        if (top_layer && !bfv_lift_can_apply_top(e, h))
+        const bool top_layer = plan.lift_top;
+        if (!behz_instance_ok(h, plan, plan.lift_kernel) || (top_layer && !bfv_lift_can_apply_top(e, h.k, h.redc_small)))
             return hipErrorInvalidValue;
         const unsigned grid = blocks_for(count, top_layer ? e.logn - 1 : e.logn);
         ProfScope prof(e, "bfv_lift", 0);
-        if (h.k <= 32)
+        if (plan.lift_kernel != kBehzStepwise)
         {
 #define SEALHIP_LIFT2(KM) lift2_launch<KM>(e, d, in, in_stride, out, out_stride, count, grid, top_layer)
-            switch (h.redc_small ? h.k : 0)
+            switch (plan.lift_kernel)
             {
             case 1: SEALHIP_LIFT2(-1); break;
             case 2: SEALHIP_LIFT2(-2); break;
@@ -888,7 +901,6 @@ namespace sealhip
             case 13: SEALHIP_LIFT2(-13); break;
             case 14: SEALHIP_LIFT2(-14); break;
             case 15: SEALHIP_LIFT2(-15); break;
-            case 16: SEALHIP_LIFT2(-16); break;
             default: SEALHIP_LIFT2(32); break;
             }
 #undef SEALHIP_LIFT2
@@ -923,16 +935,19 @@ namespace sealhip
 
     hipError_t launch_bfv_floor_sk(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in,
                                    std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count,
-                                   int deferred_top)
+                                   const BfvMulPlan &plan)
     {
         if (!count)
             return hipSuccess;
+        const int deferred_top = plan.deferred_top;
+        if (!behz_instance_ok(h, plan, plan.floor_kernel))
+            return hipErrorInvalidValue;
         const unsigned grid = blocks_for(count, e.logn);
         // transparency sink armed for this launch (pipeline.cpp SinkArm: polynomials 1.. of a product): the fused kernel
         // notes non-zero words as it stores them; the step-by-step kernels are followed by the read pass instead
         unsigned *tflags = e.lane().tsink_arm;
         ProfScope prof(e, "bfv_floor_sk", 0);
-        if (h.k <= 32)
+        if (plan.floor_kernel != kBehzStepwise)
         {
 #define SEALHIP_FLOOR2(KM)                                                                                          \
     do                                                                                                               \
@@ -945,7 +960,7 @@ namespace sealhip
             bfv_floor_sk2_kernel<KM, false><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,      \
                                                                             out_stride, count, e.logn, 0, tflags);  \
     } while (0)
-            switch (h.redc_small ? h.k : 0)
+            switch (plan.floor_kernel)
             {
             case 1: SEALHIP_FLOOR2(-1); break;
             case 2: SEALHIP_FLOOR2(-2); break;
@@ -962,7 +977,6 @@ namespace sealhip
             case 13: SEALHIP_FLOOR2(-13); break;
             case 14: SEALHIP_FLOOR2(-14); break;
             case 15: SEALHIP_FLOOR2(-15); break;
-            case 16: SEALHIP_FLOOR2(-16); break;
             default: SEALHIP_FLOOR2(32); break;
             }
 #undef SEALHIP_FLOOR2

@@ -72,6 +72,7 @@ SYMBOLS = {
     "sealhip_profile_fetch": [_vp, C.c_char_p, _sz],
     "sealhip_debug_ntt_table": [_vp, _u32, _u32, _vp, _sz],
     "sealhip_debug_rns_constants": [_vp, _u32, _u32, _vp, _sz, C.POINTER(_sz)],
+    "sealhip_debug_bfv_multiply_plan": [_vp, _u32, _u32, _u32, _i32, _vp],
     "sealhip_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_ntt_negacyclic_harvey": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_inverse_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
@@ -416,6 +417,16 @@ class Context:
         w = C.c_size_t()
         _check(lib().sealhip_debug_rns_constants(self.handle, k, which, out.ctypes.data, out.size, C.byref(w)))
         return out[: w.value].copy()
+
+    BFV_PLAN_FIELDS = ("k", "B", "nB", "square", "redc_small", "gather", "defer", "fused_tensor", "tensor_apx", "lift_top",
+                       "lift_kernel", "floor_kernel", "deferred_top")
+
+    def debug_bfv_multiply_plan(self, k, size_a=2, size_b=2, square=False):
+        """{field: int} -- the dispatch of a BFV multiply (square: of one size-2 operand) at level k
+        (sealhip_debug_bfv_multiply_plan; instance 1..15 exact k, 32 run-time k, 64 step-by-step)"""
+        out = np.zeros(len(self.BFV_PLAN_FIELDS), dtype=np.int32)
+        _check(lib().sealhip_debug_bfv_multiply_plan(self.handle, k, size_a, size_b, 1 if square else 0, out.ctypes.data))
+        return dict(zip(self.BFV_PLAN_FIELDS, (int(x) for x in out)))
 
     def galois_elt_from_step(self, step):
         v = C.c_uint32()

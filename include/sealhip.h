@@ -138,6 +138,12 @@ long sealhip_debug_ntt_table(sealhip_context *ctx, uint32_t prime_index, uint32_
    11 q->m_tilde row, 12 B->m_sk row */
 long sealhip_debug_rns_constants(sealhip_context *ctx, uint32_t k, uint32_t which, uint64_t *out_host,
                                  size_t capacity, size_t *written);
+/* The dispatch of a BFV multiply (square != 0: the square of one size-2 operand) at level k with operands of sizes size_a
+   and size_b (works on host-only contexts). out[0..12]: k, |B|, |Bsk|, square, redc_small, gather, defer, fused_tensor,
+   tensor_apx, lift_top, lift instance, floor instance, deferred_top; instance 1..15 is the exact-k kernel, 32 the run-time-k
+   kernel, 64 the step-by-step kernels. */
+long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t size_a, uint32_t size_b, int32_t square,
+                                     int32_t *out);
 
 /* ---------------------------------------------------------------- L2: NTT (util/ntt.h:189-368)
    data: count polynomials x rows x N, in place. `base` selects the primes of the `rows` rows of one

@@ -9,6 +9,11 @@
 // 4. --classes: prints, as JSON, the largest prime value each predicate of the standalone NTT entries' dispatch admits at
 //    log n = 14, 15, 16 (tests/golden/ntt_instance_classes.json; the GPU matrix of tests/test_gpu_parity.py takes its
 //    prime classes from that fixture, and tests/test_host.py requires this output to equal it).
+// 5. The fused BEHZ kernels' REDC predicate (ntt_bounds.hpp section 7, behz_redc_small): redc128 + redc_finish(small) modelled
+//    in __int128 on the worst accumulator of every stage at k = 1..33, |B| = k and k + 1, the largest and the smallest
+//    auxiliary prime at log n 3..16: admitted => the word is below 2p and congruent; and a slack of a few units of the sum
+//    past the admitted max_q (max_b) some realizable accumulator gives a word of 2p or more. --behz-classes prints the
+//    largest admitted max_q per (log n, k, |B|) as JSON (tests/golden/behz_instance_classes.json).
 // Invariant restated: native/src/seal/util/defines.h:52-53 (lazy arithmetic fits the word), butterflies util/ntt.cpp:245-281.
 #include <cfenv>
 #include <cmath>
@@ -648,8 +653,187 @@ static int print_classes()
     return 0;
 }
 
+// ---- 5. BEHZ REDC predicate (behz_redc_small). The auxiliary primes exactly as engine.cpp asks for them: get_primes(n, 60, c)
+static u64 mulmod_u128(u64 a, u64 b, u64 m) { return static_cast<u64>(static_cast<u128>(a) * b % m); }
+static bool is_prime_u64(u64 n)
+{
+    if (n < 2)
+        return false;
+    for (u64 p : {2ull, 3ull, 5ull, 7ull, 11ull, 13ull, 17ull, 19ull, 23ull, 29ull, 31ull, 37ull})
+        if (n % p == 0)
+            return n == p;
+    u64 d = n - 1;
+    int r = 0;
+    while ((d & 1) == 0)
+        d >>= 1, r++;
+    for (u64 a : {2ull, 3ull, 5ull, 7ull, 11ull, 13ull, 17ull, 19ull, 23ull, 29ull, 31ull, 37ull})
+    {
+        u64 x = 1, b = a % n, e = d;
+        for (; e; e >>= 1, b = mulmod_u128(b, b, n))
+            if (e & 1)
+                x = mulmod_u128(x, b, n);
+        if (x == 1 || x == n - 1)
+            continue;
+        bool comp = true;
+        for (int i = 1; i < r && comp; i++)
+            if ((x = mulmod_u128(x, x, n)) == n - 1)
+                comp = false;
+        if (comp)
+            return false;
+    }
+    return true;
+}
+static std::vector<u64> aux_primes(int logn, int count)
+{
+    std::vector<u64> out;
+    const u64 step = u64(2) << logn;
+    for (u64 c = (u64(1) << 60) - step + 1; static_cast<int>(out.size()) < count; c -= step)
+        if (is_prime_u64(c))
+            out.push_back(c);
+    return out;
+}
+constexpr int kBehzAuxCount = 64 + 3; // kMaxModuli key primes + 3 (engine.cpp)
+
+// devmath.hpp redc128 then redc_finish(small = true) on the 128-bit accumulator acc (hi:lo), modulus p
+static u64 redc_model(u128 acc, u64 p, bool &wrapped)
+{
+    u64 ninv = p; // -p^-1 mod 2^64, as engine.cpp computes it
+    for (int it = 0; it < 6; it++)
+        ninv *= 2 - p * ninv;
+    ninv = 0 - ninv;
+    const u64 lo = static_cast<u64>(acc), hi = static_cast<u64>(acc >> 64);
+    const u64 m = lo * ninv;
+    const u128 t = static_cast<u128>(hi) + static_cast<u64>((static_cast<u128>(m) * p) >> 64) + (lo != 0);
+    wrapped = t >> 64 != 0; // the kernel's 64-bit sum would have wrapped
+    const u64 w = static_cast<u64>(t);
+    return w >= p ? w - p : w; // small = true: one conditional subtraction
+}
+// the accumulator in [0, acc_max] whose REDC is largest: acc = p (mod 2^64) makes m = 2^64 - 1 (output (acc + (2^64 - 1) p) / 2^64)
+static u128 worst_acc(u128 acc_max, u64 p)
+{
+    if (acc_max < p)
+        return acc_max;
+    return acc_max - ((acc_max - p) & ~u64(0));
+}
+// one stage: nterms variable factors with bounds X[i] (x < X[i]) times constants below p; every accumulator up to the largest
+// such sum (p - 1) sum (X[i] - 1) must give a canonical word (below p after the one subtraction) congruent to acc 2^-64
+static bool stage_ok(const std::vector<u128> &X, u64 p)
+{
+    u128 acc_max = 0;
+    for (u128 x : X)
+        acc_max += (x - 1) * (p - 1);
+    for (u128 acc : {acc_max, worst_acc(acc_max, p), acc_max - acc_max / 3})
+    {
+        bool wrapped = false;
+        const u64 w = redc_model(acc, p, wrapped);
+        if (wrapped || w >= p || (static_cast<u128>(w) * (static_cast<u128>(1) << 64) % p) != acc % p)
+            return false;
+    }
+    return true;
+}
+// ... and one that does not: past the bound, the worst accumulator the same bounds allow gives a word of 2p or more
+static bool stage_breaks(const std::vector<u128> &X, u64 p)
+{
+    u128 acc_max = 0;
+    for (u128 x : X)
+        acc_max += (x - 1) * (p - 1);
+    bool wrapped = false;
+    const u64 w = redc_model(worst_acc(acc_max, p), p, wrapped);
+    return wrapped || w >= p;
+}
+// the stages of ntt_bounds.hpp section 7 at (k, B, max_q, max_b): the REDC moduli are the largest b (Bsk rows, conv_sk) and
+// the largest q (floor q rows)
+static std::vector<std::pair<std::vector<u128>, u64>> behz_stages(int k, int B, u64 max_q, u64 max_b)
+{
+    std::vector<u128> lift(k, max_q), floor_b(k, max_q), conv(B, max_b), floor_q(B + 1, max_b);
+    lift.push_back(max_b);        // temp < b_j
+    floor_b.push_back(2 * static_cast<u128>(max_b)); // the lazy Bsk input
+    return {{lift, max_b}, {floor_b, max_b}, {conv, max_b}, {floor_q, max_q}};
+}
+static u64 behz_largest_max_q(int k, int B, u64 max_b)
+{
+    const u64 top = (u64(1) << kMaxPrimeBits) - 1; // the context takes primes below 2^61
+    if (!behz_redc_small(k, B, 2, max_b))
+        return 0;
+    if (behz_redc_small(k, B, top, max_b))
+        return top;
+    u64 a = 2, b = top;
+    while (b - a > 1)
+        (behz_redc_small(k, B, a + (b - a) / 2, max_b) ? a : b) = a + (b - a) / 2;
+    return a;
+}
+static void behz_redc_execution()
+{
+    int admitted = 0, broken = 0;
+    for (int logn = 3; logn <= 16; logn++)
+    {
+        const std::vector<u64> aux = aux_primes(logn, kBehzAuxCount);
+        CHECK(!behz_redc_small(15, 16, 1, aux[0]) && !behz_redc_small(16, 16, 1, aux.back()),
+              "an exact-k instance at k = 16 or at (15, |B| 16) is reachable, logn=%d", logn);
+        for (const u64 max_b : {aux[0], aux.back()})
+            for (int k = 1; k <= 33; k++)
+                for (int B = k; B <= k + 1; B++)
+                {
+                    const u64 mq = behz_largest_max_q(k, B, max_b);
+                    if (!mq)
+                    {
+                        // s2 rejects: one |B| lower must be admitted or the sum (B + 1) max_b is past 2^64 by the slack
+                        CHECK(static_cast<u128>(B + 1) * max_b > kWord, "s2 logn=%d k=%d B=%d", logn, k, B);
+                        continue;
+                    }
+                    admitted++;
+                    // admitted: every stage at the largest admitted max_q (and at a small one) lands below 2p
+                    for (const u64 q : {(mq - 1) | 1, (u64(1) << 20) + 7})
+                        for (const auto &st : behz_stages(k, B, q, max_b))
+                            CHECK(stage_ok(st.first, st.second), "REDC past 2p: logn=%d k=%d B=%d max_q=%llu max_b=%llu", logn,
+                                  k, B, q, max_b);
+                    // tight up to a slack of T + 2^64 / p + 2 units of the sum (T terms of one unit each: the factors are
+                    // strictly below their bounds): past it the first stage breaks
+                    if (mq < (u64(1) << kMaxPrimeBits) - 1)
+                    {
+                        const int T = k + 1;
+                        const u64 slack = static_cast<u64>(T) + 16 + 2 + 1;
+                        const u64 q2 = mq + (slack + k - 1) / k + 1;
+                        CHECK(!behz_redc_small(k, B, mq + 1, max_b), "not the largest max_q");
+                        const auto st = behz_stages(k, B, q2, max_b);
+                        const bool b1 = stage_breaks(st[1].first, st[1].second);
+                        CHECK(b1, "s1 not tight: logn=%d k=%d B=%d max_q=%llu", logn, k, B, q2);
+                        broken += b1;
+                    }
+                }
+        // s2 tight: at the largest |B| the predicate admits for this m_sk, one more row breaks the floor's q rows
+        int Bmax = 1;
+        while (behz_redc_small(1, Bmax + 1, 2, aux[0]))
+            Bmax++;
+        const u64 mb2 = static_cast<u64>((kWord + (Bmax + 1) * 20) / (Bmax + 2)); // (Bmax + 2) * mb2 past 2^64 by the slack
+        CHECK(!behz_redc_small(1, Bmax + 1, 2, mb2), "s2 step logn=%d", logn);
+        // (the floor's q rows reduce modulo a ciphertext prime: 2^61 - 1, the largest the context takes, is one)
+        const u64 q61 = (u64(1) << 61) - 1;
+        CHECK(stage_breaks(behz_stages(1, Bmax + 1, q61, mb2)[3].first, q61), "s2 not tight logn=%d B=%d", logn, Bmax + 1);
+    }
+    CHECK(admitted > 0 && broken > 0, "BEHZ predicate: nothing exercised");
+}
+
+static int print_behz_classes()
+{
+    std::printf("{\n");
+    for (int logn = 3; logn <= 16; logn++)
+    {
+        const std::vector<u64> aux = aux_primes(logn, kBehzAuxCount);
+        std::printf("  \"%d\": {\"m_sk\": %llu, \"max_q\": {", logn, aux[0]);
+        for (int k = 1; k <= 33; k++)
+            std::printf("\"%d\": [%llu, %llu]%s", k, behz_largest_max_q(k, k, aux[0]), behz_largest_max_q(k, k + 1, aux[0]),
+                        k < 33 ? ", " : "");
+        std::printf("}}%s\n", logn < 16 ? "," : "");
+    }
+    std::printf("}\n");
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "--behz-classes")
+        return print_behz_classes();
     if (argc > 1 && std::string(argv[1]) == "--classes")
         return print_classes();
     std::fesetround(FE_TONEAREST);
@@ -679,6 +863,7 @@ int main(int argc, char **argv)
         inv_lazy_execution(T, max_prime_of_bits(inv_lazy_prime_bits(T, 1)), 1); // dense schedule at the largest 60-bit value
         inv_lazy_execution(T, (u64(1) << 59) + 12345, 1);
     }
+    behz_redc_execution();
     std::printf(failures ? "bounds_check: %d FAILURES\n" : "bounds_check: OK\n", failures);
     return failures ? 1 : 0;
 }

@@ -3,6 +3,7 @@
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg. The product (gemini-seal_amd/) never imports this module.
 """
+import functools
 import ctypes as C
 import os
 import subprocess
@@ -601,3 +602,104 @@ class MathNtt:
         for j, v in enumerate(A):
             acc += int(v) * pows[self.br[j]]
         return acc % self.p * self.n_inv % self.p
+
+
+# ---- BFV multiply dispatch, restated (pipeline.cpp plan_bfv_multiply, rns.hip launch_bfv_lift / launch_bfv_floor_sk,
+# ntt_bounds.hpp behz_redc_small / tensor_admits_* / fwd_dense_admits). Plain integers, no native code: tests/test_host.py
+# compares it with sealhip_debug_bfv_multiply_plan, and the GPU matrix derives its cases from it.
+BEHZ_EXACT_MAX_K, BEHZ_GENERIC, BEHZ_STEPWISE = 15, 32, 64
+MAX_ROWS = 136  # engine.hpp kMaxRows
+
+
+@functools.lru_cache(maxsize=None)
+def aux_primes(n, count):
+    """get_primes(n, 60, count): the 60-bit primes = 1 (mod 2n), largest first (m_sk, gamma, B_0, B_1, ...)"""
+    out, c = [], (1 << 60) - 2 * n + 1
+    while len(out) < count:
+        if is_prime(c):
+            out.append(c)
+        c -= 2 * n
+    return tuple(out)
+
+
+def base_b_size(q, t):
+    """HostRnsTool::base_B_size (rns.cpp:568-573): |B| = k, or k + 1 when 32 + bits(t) + bits(prod q) >= 61 (k + 1)"""
+    prod = 1
+    for p in q:
+        prod *= p
+    return len(q) + (1 if 32 + int(t).bit_length() + prod.bit_length() >= 61 * len(q) + 61 else 0)
+
+
+def behz_redc_small(k, B, max_q, max_b):
+    """every REDC of the fused BEHZ kernels lands below 2p: k max_q + 2 max_b <= 2^64 and (B + 1) max_b <= 2^64"""
+    return k * max_q + 2 * max_b <= 1 << 64 and (B + 1) * max_b <= 1 << 64
+
+
+def bfv_multiply_plan(logn, key_moduli, t, k, sa, sb, square=False, strict=False):
+    """the dispatch of op_bfv_multiply at level k of a BFV context (key_moduli includes the one special prime), as a dict
+    with the fields of sealhip Context.debug_bfv_multiply_plan"""
+    n = 1 << logn
+    q = [int(p) for p in key_moduli[:k]]
+    aux = aux_primes(n, len(key_moduli) + 3)
+    B = base_b_size(q, t)
+    bsk = list(aux[2:2 + B]) + [aux[0]]
+    nB = B + 1
+    redc_small = behz_redc_small(k, B, max(q), max(bsk))
+    kb, sin, dest = k + nB, (sa if square else sa + sb), sa + sb - 1
+    single_pass = 14 <= logn <= 16  # ntt_can_gather: the single-pass NTT kernels
+    gather = single_pass and sin * kb <= MAX_ROWS
+    defer = single_pass and k <= 32
+    fused = (gather and defer and sa == 2 and sb == 2 and dest * kb <= MAX_ROWS and all(p < 1 << 59 for p in q)
+             and all(b < 1 << 60 for b in bsk))
+    tensor_apx = all(p < 1 << 57 for p in q)
+    lift_top = fused and redc_small and 1 <= k <= BEHZ_EXACT_MAX_K and logn >= 14
+    if lift_top and strict:
+        # ntt_strict_top_done_ok: the dense forward schedule admits every Bsk prime (peak 14p, 16p at 2^16)
+        mult = 16 if logn == 16 else 14
+        lift_top = all(1 << 45 <= b < 1 << 60 and mult * b <= 1 << 64 for b in bsk)
+    code = BEHZ_STEPWISE if k > 32 else k if redc_small and k <= BEHZ_EXACT_MAX_K else BEHZ_GENERIC
+    return {"k": k, "B": B, "nB": nB, "square": int(square), "redc_small": int(redc_small), "gather": int(gather),
+            "defer": int(defer), "fused_tensor": int(fused), "tensor_apx": int(tensor_apx), "lift_top": int(lift_top),
+            "lift_kernel": code, "floor_kernel": code, "deferred_top": 2 if fused else 1 if defer else 0}
+
+
+def bfv_plan_cell(plan, sa, sb):
+    """what a GPU case of the multiply matrix covers: the kernel instances and pipeline forks it runs, and |B| relative to k
+    (the operand shape only through the forks it decides)"""
+    return (plan["square"], plan["B"] - plan["k"], plan["lift_kernel"], plan["floor_kernel"],
+            plan["lift_top"], plan["deferred_top"], plan["gather"], plan["fused_tensor"], plan["tensor_apx"] if plan["fused_tensor"] else 0)
+
+
+BFV_PLAN_LOGNS = (12, 14, 15, 16)
+BFV_PLAN_T = (786433, (1 << 59) - 55)  # a small batching modulus and a 59-bit one (|B| = k + 1 with 59-bit q)
+BFV_PLAN_SHAPES = ((2, 2, False), (2, 3, False), (3, 3, False), (2, 2, True))  # (size_a, size_b, square)
+BFV_PLAN_LEVELS = 33  # 34 key primes, one special: k_first = 33, the step-by-step kernels at k = 33
+
+
+def ntt_primes_below(n, top, count):
+    """the largest `count` primes = 1 (mod 2n) below `top`, largest first"""
+    out, c = [], (top - 1) // (2 * n) * (2 * n) + 1
+    while len(out) < count:
+        if c < top and is_prime(c):
+            out.append(c)
+        c -= 2 * n
+    return out
+
+
+def bfv_plan_contexts(behz_classes):
+    """[(logn, class name, key moduli, t)] of the dispatch grid: prime classes 50 (the FP64 NTT), 55, 58, 59 and 61 bits, and
+    at the s1 edge of k = 15 (tests/golden/behz_instance_classes.json) the largest admitted and the first rejected NTT
+    prime, followed by 59-bit ones; the largest primes come first, so every level sees its class"""
+    out = []
+    for logn in BFV_PLAN_LOGNS:
+        n = 1 << logn
+        edge = behz_classes[str(logn)]["max_q"]["15"][0]
+        classes = [(str(b), ntt_primes_below(n, 1 << b, BFV_PLAN_LEVELS + 1)) for b in (50, 55, 58, 59, 61)]
+        below = ntt_primes_below(n, edge + 1, 1)[0]
+        above = next(c for c in range((edge // (2 * n)) * 2 * n + 1, 1 << 61, 2 * n) if c > edge and is_prime(c))
+        fill = ntt_primes_below(n, 1 << 59, BFV_PLAN_LEVELS)
+        classes += [("edge_admitted", [below] + fill), ("edge_rejected", [above] + fill)]
+        for name, mods in classes:
+            for t in BFV_PLAN_T:
+                out.append((logn, name, mods, t))
+    return out

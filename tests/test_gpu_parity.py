@@ -3242,3 +3242,209 @@ def test_every_counted_entry_accepts_an_empty_batch(sealhip, logn, strict):
         assert np.array_equal(buf.download(), sentinel), (scheme, "the buffer changed")
         del keep, calls
     assert not failures, failures
+
+
+# ---------------------------------------------------------------- BFV multiply / square at every BEHZ plan cell
+_BEHZ_GENERIC_LEVELS = range(17, 33)  # the run-time-k instance's levels past the exact range's k = 15 / 16 cells
+
+
+def _behz_plan_cases():
+    """(required coverage, cases by grid context). Required: every (cell, log n) that oracle_lib.bfv_plan_cell reaches on
+    the dispatch grid of tests/test_host.py (PARITY); every level 17..32 of the run-time-k instance with (2,2) and with
+    square, spread over the rings 2^14..2^16; and each operand shape on both sides of each fork edge the restatement
+    derives (gather per shape, fused_tensor for square, defer at 32 / 33), at a ring chosen by the edge level. Each
+    requirement is met by its cheapest case."""
+    grid = O.bfv_plan_contexts(json.load(open(os.path.join(HERE, "golden", "behz_instance_classes.json"))))
+    plans = {}
+    for ci, (logn, name, mods, t) in enumerate(grid):
+        for k in range(1, O.BFV_PLAN_LEVELS + 1):
+            for sa, sb, sq in O.BFV_PLAN_SHAPES:
+                plans[ci, k, sa, sb, sq] = O.bfv_multiply_plan(logn, mods, t, k, sa, sb, sq)
+
+    def cost(key):
+        ci, k, sa, sb, sq = key
+        return ((1 << grid[ci][0]) * k * (sa + sb), key)
+
+    best = {}
+
+    def want(req, key):
+        if req not in best or cost(key) < cost(best[req]):
+            best[req] = key
+
+    edges = {}  # (shape, fork) -> the levels where it flips, on the class "58" at t = 786433 of each ring
+    for key, plan in plans.items():
+        ci, k, sa, sb, sq = key
+        logn = grid[ci][0]
+        want(("cell", O.bfv_plan_cell(plan, sa, sb), logn), key)
+        if k in _BEHZ_GENERIC_LEVELS and (sa, sb) == (2, 2) and logn == 14 + k % 3:
+            want(("generic", k, sq), key)
+        if grid[ci][1] == "58" and grid[ci][3] == O.BFV_PLAN_T[0] and logn >= 14 and k > 1:
+            prev = plans[ci, k - 1, sa, sb, sq]
+            for fork in ("gather", "fused_tensor", "defer"):
+                if prev[fork] != plan[fork] and logn == 14 + (k - 1) % 3:
+                    edges[(sa, sb, sq), fork] = k - 1
+                    for kk in (k - 1, k):
+                        want(("edge", (sa, sb, sq), fork, kk), (ci, kk, sa, sb, sq))
+    assert {f for _, f in edges} == {"gather", "fused_tensor", "defer"}, edges
+    cases = {}
+    for req, (ci, k, sa, sb, sq) in best.items():
+        cases.setdefault(ci, set()).add((k, sa, sb, sq))
+    return set(best), best, plans, [(grid[ci], sorted(v)) for ci, v in sorted(cases.items())]
+
+
+def _behz_operand(rng, mods, size, n, pattern):
+    """one ciphertext of `size` polynomials: 0 every word q - 1, 1 q - 1 alternating with 0, 2 upper half q - 1 (lower
+    half 0), 3 zero, 4 random"""
+    if pattern == 4:
+        return _rand_ct(rng, mods, size, n, 1)[0]
+    top = np.stack([np.full((size, n), p - 1, dtype=np.uint64) for p in mods], axis=1)
+    if pattern == 1:
+        top[:, :, 1::2] = 0
+    elif pattern == 2:
+        top[:, :, : n // 2] = 0
+    elif pattern == 3:
+        top[:] = 0
+    return top
+
+
+# item patterns (a, b): the worst case, two independent random operands, then one of the mixed pairs
+_BEHZ_MIXED = ((1, 2), (2, 1), (1, 4), (3, 0), (2, 4), (4, 1))
+
+
+def _behz_run(sealhip, ctx, ref, logn, mods, k, sa, sb, sq, items, seed, pool):
+    n = 1 << logn
+    rng = np.random.default_rng(seed)
+    count = len(items)
+    a = np.stack([_behz_operand(rng, mods[:k], sa, n, pa) for pa, _ in items])
+    b = np.stack([_behz_operand(rng, mods[:k], sb, n, pb) for _, pb in items])
+    dest = sa + sb - 1
+    out = ctx.alloc(count * dest * k * n)
+    ev = sealhip.Evaluator(ctx)
+    if sq:
+        ev.square(ctx.upload(a), 2, k, count, out)
+    else:
+        ev.multiply(ctx.upload(a), sa, ctx.upload(b), sb, k, count, out)
+    got = out.download((count, dest, k, n))
+    ref.rns_tool(k)  # built here, once: the oracle calls below run on several threads and only read the context
+
+    def oracle(i):
+        exp = np.zeros((dest, k, n), dtype=np.uint64)
+        if sq:
+            assert L.ref_bfv_square(C.byref(ref.c), k, O.ptr(a[i]), 2, O.ptr(exp)) == 0
+        else:
+            assert L.ref_bfv_multiply(C.byref(ref.c), k, O.ptr(a[i]), sa, O.ptr(b[i]), sb, O.ptr(exp)) == 0
+        return exp
+
+    return [(got[i], pool.submit(oracle, i), (logn, k, sa, sb, sq, items[i])) for i in range(count)]
+
+
+def test_bfv_multiply_every_behz_plan_cell(sealhip):
+    """BFV multiply / square bit-exact against the oracle at every reachable cell of the dispatch (oracle_lib.bfv_plan_cell:
+    lift and floor instance -- exact k = 1..15, run-time k, step-by-step --, |B| = k or k + 1, the lift's top layer,
+    deferred_top 0 / 1 / 2, gather, fused tensor product and its approximate-quotient form, square) on EACH ring log n =
+    12, 14, 15, 16 where it is reachable; every level 17..32 of the run-time-k instance; and the operand shapes on both
+    sides of each fork edge. Each on its cheapest case of the grid of tests/test_host.py (prime classes 50..61 bits and
+    the s1 edge primes, t = 786433 and a 59-bit t, levels 1..33 of a 34-prime context). Every case runs three items: all
+    words q - 1 in both operands, two independent random operands, and a mixed pair (q - 1 alternating with 0, upper half
+    q - 1, zero, random); cases with the lift's top layer run a single worst-case item as well (odd item counts for the
+    paired-column grid). The plans the engine reports for the chosen cases must cover the required set before any
+    arithmetic is compared: a dispatch change that moves a case off its cell fails as a coverage error."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    required, best, plans, cases = _behz_plan_cases()
+    grid = O.bfv_plan_contexts(json.load(open(os.path.join(HERE, "golden", "behz_instance_classes.json"))))
+    ctxs = {}
+    ran = set()
+    for req, (ci, k, sa, sb, sq) in sorted(best.items(), key=lambda r: r[1]):
+        logn, name, mods, t = grid[ci]
+        if ci not in ctxs:
+            ctxs = {ci: sealhip.Context(sealhip.SCHEME_BFV, logn, mods, 1, t)}  # one context alive at a time
+        got = ctxs[ci].debug_bfv_multiply_plan(k, sa, sb, sq)
+        ran.add(("cell", O.bfv_plan_cell(got, sa, sb), logn))
+        if got["floor_kernel"] == O.BEHZ_GENERIC and k in _BEHZ_GENERIC_LEVELS and (sa, sb) == (2, 2) and logn == 14 + k % 3:
+            ran.add(("generic", k, sq))
+        if req[0] == "edge":
+            # the engine's own plan flips the fork between this level and its neighbour on the other side of the edge
+            _, shape, fork, kk = req
+            lo = min(k for r, (c2, k, *_) in best.items() if r[:3] == req[:3])
+            other = ctxs[ci].debug_bfv_multiply_plan(lo + 1 if k == lo else lo, sa, sb, sq)
+            if other[fork] != got[fork]:
+                ran.add(req)
+    del ctxs
+    assert ran == required, ("not run", sorted(map(str, required - ran)), "not reachable", sorted(map(str, ran - required)))
+    assert {r[2] for r in required if r[0] == "cell"} == {12, 14, 15, 16}
+    assert {(r[1], r[2]) for r in required if r[0] == "generic"} == {(k, sq) for k in _BEHZ_GENERIC_LEVELS for sq in (0, 1)}
+    seed = 0
+    with ThreadPoolExecutor(8) as pool:
+        for (logn, name, mods, t), todo in cases:
+            ctx = sealhip.Context(sealhip.SCHEME_BFV, logn, mods, 1, t)
+            ref = O.RefContext(1, logn, mods, nsp=1, t=t)
+            pending = []
+            for k, sa, sb, sq in todo:
+                seed += 1
+                items = [(0, 0), (4, 4), _BEHZ_MIXED[seed % len(_BEHZ_MIXED)]]
+                pending += _behz_run(sealhip, ctx, ref, logn, mods, k, sa, sb, sq, items, seed, pool)
+                if ctx.debug_bfv_multiply_plan(k, sa, sb, sq)["lift_top"]:
+                    pending += _behz_run(sealhip, ctx, ref, logn, mods, k, sa, sb, sq, [(0, 0)], seed, pool)
+                if sum(g.nbytes for g, _, _ in pending) > 1 << 29:  # bound the words held for comparison
+                    for got, fut, what in pending:
+                        assert np.array_equal(got, fut.result()), (name, t) + what
+                    pending = []
+            for got, fut, what in pending:
+                assert np.array_equal(got, fut.result()), (name, t) + what
+
+
+@pytest.mark.parametrize("logn,bits", [(14, 59), (15, 55)])
+def test_bfv_multiply_behz_strict(sealhip, logn, bits):
+    """STRICT mode at the exact instances' edges (k = 1, 14, 15), the run-time-k instance (16, 32) and the step-by-step
+    kernels (33): (2,2) and square against the oracle, whose STRICT sequence it must match."""
+    n = 1 << logn
+    mods = O.ntt_primes_below(n, 1 << bits, O.BFV_PLAN_LEVELS + 1)
+    t = O.BFV_PLAN_T[1]
+    ctx = sealhip.Context(sealhip.SCHEME_BFV, logn, mods, 1, t, mode=sealhip.MODE_STRICT)
+    ref = O.RefContext(1, logn, mods, nsp=1, t=t, mode=1)
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(8) as pool:
+        pending = []
+        for j, k in enumerate((1, 14, 15, 16, 32, 33)):
+            for sq in (False, True):
+                items = [(0, 0), (4, 4), _BEHZ_MIXED[j % len(_BEHZ_MIXED)]]
+                pending += _behz_run(sealhip, ctx, ref, logn, mods, k, 2, 2, sq, items, 100 * logn + 2 * j + sq, pool)
+        for got, fut, what in pending:
+            assert np.array_equal(got, fut.result()), what
+
+
+@pytest.mark.parametrize("k", [16, 33])
+def test_transparency_flags_at_generic_and_stepwise_behz_levels(sealhip, k):
+    """The transparency sink of multiply and square at the run-time-k floor (k = 16) and the step-by-step floor followed by
+    the separate read pass (k = 33, launch_nonzero_words): items whose second polynomials are zero have zero polynomials
+    1.. of the product; the flags must equal that pattern and the device reduction sealhip_is_transparent.
+    (test_transparency_is_a_flag_output_of_the_operations covers the exact-k levels.)"""
+    logn, n, t = 14, 1 << 14, 786433
+    mods = O.ntt_primes_below(n, 1 << 50, O.BFV_PLAN_LEVELS + 1)
+    ctx = sealhip.Context(sealhip.SCHEME_BFV, logn, mods, 1, t)
+    assert ctx.debug_bfv_multiply_plan(k)["floor_kernel"] == (O.BEHZ_GENERIC if k <= 32 else O.BEHZ_STEPWISE)
+    ev = sealhip.Evaluator(ctx)
+    rng = np.random.default_rng(k)
+    count, zero_items = 5, [1, 4]
+    a = _rand_ct(rng, mods[:k], 2, n, count)
+    b = _rand_ct(rng, mods[:k], 2, n, count)
+    for i in zero_items:
+        a[i, 1] = 0
+        b[i, 1] = 0
+    want = [i not in zero_items for i in range(count)]
+    flags = ctx.alloc((count + 1) // 2)
+    flags.upload(np.full((count + 1) // 2, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64))
+    ctx.transparency_sink(flags, count)
+    try:
+        for op in ("multiply", "square"):
+            prod = ctx.alloc(count * 3 * k * n)
+            if op == "multiply":
+                ev.multiply(ctx.upload(a), 2, ctx.upload(b), 2, k, count, prod)
+            else:
+                ev.square(ctx.upload(a), 2, k, count, prod)
+            got = (flags.download().view(np.uint32)[:count] != 0).tolist()
+            assert got == want == [not v for v in ctx.is_transparent(prod, 3, k, count).tolist()], op
+    finally:
+        ctx.transparency_sink(None, 0)

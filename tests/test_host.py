@@ -491,3 +491,73 @@ def test_f3_seed_expansion_blake2xb_known_answers_and_oracle():
                 assert all((got[j] < mods[j]).all() for j in range(rows))
     with pytest.raises(ValueError):
         S.blake2xb(0, b"")
+
+
+# ---------------------------------------------------------------- BFV multiply dispatch (pipeline.cpp plan_bfv_multiply)
+def _behz_bounds_exe(tmp_path):
+    import subprocess
+
+    exe = str(tmp_path / "bounds_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe,
+                           os.path.join(ROOT, "tests", "bounds_check.cpp")])
+    return exe
+
+
+def test_behz_instance_classes_fixture_follows_the_predicate(tmp_path):
+    """tests/golden/behz_instance_classes.json is what `bounds_check --behz-classes` prints: per log n 3..16, m_sk and the
+    largest max_q behz_redc_small (ntt_bounds.hpp section 7) admits at k = 1..33 with |B| = k and k + 1 (0: none). The plan
+    grid below takes its s1 edge primes from it."""
+    import json
+    import subprocess
+
+    out = subprocess.run([_behz_bounds_exe(tmp_path), "--behz-classes"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    with open(os.path.join(ROOT, "tests", "golden", "behz_instance_classes.json")) as f:
+        committed = f.read()
+    assert out.stdout == committed
+    classes = json.loads(committed)
+    assert sorted(map(int, classes)) == list(range(3, 17))
+    for logn, c in classes.items():
+        mq = c["max_q"]
+        # every exact instance k <= 15 is admitted with |B| = k; none at k >= 16 (the removed case 16), nor at (15, |B| 16)
+        assert all(mq[str(k)][0] > 0 for k in range(1, 16)) and mq["15"][1] == 0, (logn, mq)
+        assert all(mq[str(k)] == [0, 0] for k in range(16, 34)), (logn, mq)
+
+
+def _plan_grid():
+    import json
+
+    import oracle_lib as O
+
+    with open(os.path.join(ROOT, "tests", "golden", "behz_instance_classes.json")) as f:
+        return O.bfv_plan_contexts(json.load(f))
+
+
+def test_bfv_multiply_plan_matches_the_restatement():
+    """sealhip_debug_bfv_multiply_plan (the dispatch op_bfv_multiply and the BEHZ launchers consume) against the plain
+    restatement oracle_lib.bfv_multiply_plan on host-only contexts: log n 12, 14, 15, 16 x prime classes 50 (FP64 NTT), 55,
+    58, 59, 61 bits and the two primes around the s1 edge of k = 15 x t = 786433 and a 59-bit t x (2,2), (2,3), (3,3),
+    square x PARITY / STRICT x every level k = 1..33 of a context with 34 key primes. Then the reachable instances: exact k
+    = 1..15 (k = 1..14 also with |B| = k + 1, which 59-bit q with a 59-bit t give), never k = 16; the run-time-k instance with
+    and without the top layer applied by the lift; the step-by-step kernels at k = 33."""
+    import oracle_lib as O
+    import sealhip as S
+
+    reach = {}
+    for logn, name, mods, t in _plan_grid():
+        for mode in (S.MODE_PARITY, S.MODE_STRICT):
+            ctx = S.Context(S.SCHEME_BFV, logn, mods, 1, t, mode=mode, device=-1)
+            for k in range(1, O.BFV_PLAN_LEVELS + 1):
+                for sa, sb, sq in O.BFV_PLAN_SHAPES:
+                    got = ctx.debug_bfv_multiply_plan(k, sa, sb, sq)
+                    want = O.bfv_multiply_plan(logn, mods, t, k, sa, sb, sq, strict=mode == S.MODE_STRICT)
+                    assert got == want, (logn, name, t, mode, k, sa, sb, sq)
+                    reach.setdefault((got["lift_kernel"], got["B"] - k, got["lift_top"], got["deferred_top"]), []).append(logn)
+    exact = {c[0] for c in reach if c[0] <= O.BEHZ_EXACT_MAX_K}
+    assert exact == set(range(1, 16))
+    assert {c[0] for c in reach if c[1] == 1 and c[0] <= 15} == set(range(1, 15))
+    for k in range(1, 16):
+        # each exact instance: with TOP (deferred_top 2), without it at deferred_top 1, and at log n 12 (no deferral)
+        assert {(1, 2), (0, 1), (0, 0)} <= {(c[2], c[3]) for c in reach if c[0] == k}, k
+    assert {(c[2], c[3]) for c in reach if c[0] == O.BEHZ_GENERIC} == {(0, 0), (0, 1), (0, 2)}
+    assert {(c[2], c[3]) for c in reach if c[0] == O.BEHZ_STEPWISE} == {(0, 0)}
