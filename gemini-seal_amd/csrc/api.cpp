@@ -25,6 +25,8 @@ namespace sealhip
     void wire_peek(const void *bytes, std::size_t len, sealhip_ciphertext_info *info);
     void wire_load(Engine &e, const void *bytes, std::size_t len, sealhip_ciphertext_info *info, u64 *dst,
                    std::size_t capacity_words);
+    void wire_load_many(Engine &e, const void *const *streams, const std::size_t *lens, std::size_t count,
+                        sealhip_ciphertext_info *infos, u64 *dst, std::size_t stride);
     std::size_t wire_save_size(std::uint32_t size, std::uint32_t k, std::size_t n);
     std::size_t wire_save(Engine &e, const sealhip_ciphertext_info &ci, const u64 *src, void *bytes, std::size_t capacity);
     std::uint32_t wire_load_kswitch_key(Engine &e, const void *bytes, std::size_t len, std::uint32_t index, u64 **d_out,
@@ -2045,6 +2047,23 @@ long sealhip_ciphertext_load(sealhip_context *ctx, const void *bytes, size_t len
     });
 }
 
+long sealhip_ciphertext_load_many(sealhip_context *ctx, const void *const *streams, const size_t *lens, size_t count,
+                                  sealhip_ciphertext_info *infos, uint64_t *dst_device, size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(streams);
+    REQUIRE_PTR(lens);
+    REQUIRE_PTR(infos);
+    REQUIRE_PTR(dst_device);
+    for (size_t i = 0; i < count; i++)
+        if (!streams[i])
+            return fail(SEALHIP_E_POINTER, "streams[" + std::to_string(i) + "] is null");
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        wire_load_many(e, streams, lens, count, infos, reinterpret_cast<u64 *>(dst_device), item_stride_words);
+    });
+}
+
 long sealhip_ciphertext_save_size(const sealhip_context *ctx, uint32_t size, uint32_t k, size_t *bytes)
 {
     REQUIRE_PTR(ctx);
@@ -2112,6 +2131,36 @@ long sealhip_expand_seed_host(sealhip_context *ctx, uint32_t rows, const uint64_
             throw std::invalid_argument("level k out of range");
         const std::vector<u64> c1 = wire_expand_seed(e, static_cast<int>(rows), reinterpret_cast<const unsigned char *>(seed));
         std::memcpy(out_host, c1.data(), c1.size() * sizeof(u64));
+    });
+}
+
+long sealhip_expand_seed(sealhip_context *ctx, uint32_t rows, const uint64_t *seeds_host, size_t count, uint64_t *out_device,
+                         size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(out_device);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (rows < 1 || static_cast<int>(rows) > e.n_key)
+            throw std::invalid_argument("level k out of range");
+        const std::size_t words = static_cast<std::size_t>(rows) * e.n;
+        if (item_stride_words && item_stride_words < words)
+            throw std::invalid_argument("item stride is below rows x N");
+        const std::size_t stride = item_stride_words ? item_stride_words : words;
+        std::vector<SeedJob> jobs(count);
+        for (std::size_t i = 0; i < count; i++)
+            jobs[i] = SeedJob{ seeds_host + 8 * i, reinterpret_cast<u64 *>(out_device) + i * stride };
+        op_expand_seeds(e, static_cast<int>(rows), jobs.data(), count);
+    });
+}
+
+long sealhip_debug_seed_slack(sealhip_context *ctx, int64_t extra_candidates_per_seed)
+{
+    REQUIRE_PTR(ctx);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        e.lane().seed_slack = extra_candidates_per_seed < 0 ? -1 : extra_candidates_per_seed;
     });
 }
 

@@ -161,6 +161,10 @@ namespace sealhip
         }
         if (stage)
             free_host_stage(stage);
+        if (seed_pin_done)
+            (void)hipEventDestroy(seed_pin_done);
+        if (seed_pin)
+            (void)hipHostFree(seed_pin);
         if (ws)
             (void)hipFree(ws);
         if (d_tickets)

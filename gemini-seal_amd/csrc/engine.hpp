@@ -263,6 +263,13 @@ namespace sealhip
         // (batch size, items per arena chunk) of the last operations that walked a batch in chunks (pipeline.cpp plan_chunk;
         // sealhip_debug_chunk_log): lets a caller that verifies its results pick the items at the chunk boundaries
         std::vector<std::pair<std::size_t, std::size_t>> chunk_log;
+        // seed expansion (seed_expand.hip): pinned staging of the seed records, reused once the event that follows their
+        // copy has completed; seed_slack = candidates provisioned per seed beyond rows x N (< 0: the computed default;
+        // sealhip_debug_seed_slack)
+        std::uint64_t *seed_pin = nullptr;
+        std::size_t seed_pin_words = 0;
+        hipEvent_t seed_pin_done = nullptr;
+        std::int64_t seed_slack = -1;
         std::recursive_mutex busy; // held for the duration of an operation (a graph may be launched from another thread)
         ~Lane();
     };
@@ -631,6 +638,19 @@ namespace sealhip
                         u64 *plain);
     // values out: count x N/2 complex doubles
     void op_ckks_decode(Engine &e, int k, const u64 *plain, std::size_t count, double scale, double *values);
+
+    // ---- Ciphertext::expand_seed on the device (seed_expand.hip) ----
+    // dst of job i receives the rows x N words of c_1 re-sampled from the 64-byte seed (8 words, random_seed_type) of job i:
+    // sample_poly_uniform(BlakePrng(seed), first `rows` key primes), word for word. Stream-ordered on the calling thread's
+    // lane; the seeds are staged, so the caller's seed memory may go away when this returns.
+    struct SeedJob
+    {
+        const void *seed; // host, 64 bytes (any alignment: seeds inside a byte stream are not word-aligned)
+        u64 *dst;                  // device
+    };
+    void op_expand_seeds(Engine &e, int rows, const SeedJob *jobs, std::size_t count);
+    // items of `bytes_per_item` arena bytes per chunk of a batch of `count` (pipeline.cpp; logged in Lane::chunk_log)
+    std::size_t ws_plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers);
 
     std::unique_ptr<Engine> make_engine(int scheme, int logn, const u64 *key_moduli, int n_key, int nsp, u64 t,
                                         bool strict, int device);

@@ -76,6 +76,11 @@ namespace sealhip
         }
     } // namespace
 
+    std::size_t ws_plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers)
+    {
+        return plan_chunk(e, count, bytes_per_item, n_buffers);
+    }
+
     // bytes of arena one item of op_switch_key needs (shared with op_apply_galois, which must size the arena
     // before it parks its own scratch at the front)
     static std::size_t switch_key_item_bytes(Engine &e, int k)

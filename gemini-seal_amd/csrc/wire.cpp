@@ -8,6 +8,7 @@
 #include "../../include/sealhip.h"
 
 #include <cstring>
+#include <map>
 
 #include "blake2xb.hpp"
 #include "engine.hpp"
@@ -132,7 +133,8 @@ namespace sealhip
     } // namespace
 
     // Ciphertext::expand_seed (ciphertext.cpp:126-133): the rows x N words of c_1 from the 64-byte seed that follows the
-    // single stored polynomial of a seeded ciphertext (:296-309). Host work (BLAKE2Xb, sequential rejection sampling).
+    // single stored polynomial of a seeded ciphertext (:296-309). Host work (BLAKE2Xb, sequential rejection sampling): the
+    // reference the device expander (seed_expand.hip) is tested against, and sealhip_expand_seed_host's path.
     std::vector<u64> wire_expand_seed(const Engine &e, int rows, const unsigned char *seed_bytes)
     {
         std::uint64_t seed[8];
@@ -159,36 +161,77 @@ namespace sealhip
         *info = parse(bytes, len).info;
     }
 
-    // Ciphertext::load (ciphertext.cpp:228-330) with the words landing in HBM
+    namespace
+    {
+        // Ciphertext::load's checks (ciphertext.cpp:228-330) of one stream against the context and a destination of
+        // `capacity_words`; *info is filled as soon as the stream parses
+        struct Checked
+        {
+            Parsed ps;
+            int k;
+            std::uint64_t total; // size x k x N
+        };
+        Checked check_load(Engine &e, const void *bytes, std::size_t len, sealhip_ciphertext_info *info,
+                           std::size_t capacity_words)
+        {
+            const Parsed ps = parse(bytes, len);
+            *info = ps.info;
+            const int k = level_of(e, ps.info);
+            const std::uint64_t total = static_cast<std::uint64_t>(ps.info.size) * e.n * k;
+            if (ps.info.data_words > total)
+                throw std::logic_error("unexpected size"); // intarray.h:633-638
+            if (total > capacity_words)
+                throw std::invalid_argument("destination buffer is too small");
+            if (ps.info.seeded)
+            {
+                // one stored polynomial + the seed of c_1 (ciphertext.cpp:296-309)
+                if (ps.info.size != 2 || ps.info.data_words != static_cast<std::uint64_t>(k) * e.n)
+                    throw std::logic_error("ciphertext data is invalid");
+            }
+            else if (ps.info.data_words != total)
+                throw std::logic_error("ciphertext data is invalid"); // is_buffer_valid, valcheck.cpp:228-240
+            return Checked{ ps, k, total };
+        }
+
+        // enqueues the stored words; a seeded stream's c_1 becomes a job of the device expander (SeedJob::seed points into
+        // the stream, which the caller keeps alive until op_expand_seeds has staged it)
+        void enqueue_load(Engine &e, const Checked &c, u64 *dst, std::vector<SeedJob> *jobs)
+        {
+            const std::size_t words = static_cast<std::size_t>(c.ps.info.data_words);
+            if (words)
+                SEALHIP_CHECK(hipMemcpyAsync(dst, c.ps.words, words * 8, hipMemcpyHostToDevice, e.lane().stream));
+            if (c.ps.info.seeded)
+                jobs->push_back(SeedJob{ c.ps.words + words * 8, dst + words });
+        }
+    } // namespace
+
+    // Ciphertext::load (ciphertext.cpp:228-330) with the words landing in HBM; a seeded stream's c_1 is expanded on the
+    // device (Ciphertext::expand_seed, :126-133 -> seed_expand.hip)
     void wire_load(Engine &e, const void *bytes, std::size_t len, sealhip_ciphertext_info *info, u64 *dst,
                    std::size_t capacity_words)
     {
-        const Parsed ps = parse(bytes, len);
-        *info = ps.info;
-        const int k = level_of(e, ps.info);
-        const std::uint64_t total = static_cast<std::uint64_t>(ps.info.size) * e.n * k;
-        if (ps.info.data_words > total)
-            throw std::logic_error("unexpected size"); // intarray.h:633-638
-        if (total > capacity_words)
-            throw std::invalid_argument("destination buffer is too small");
-        if (ps.info.seeded)
-        {
-            // one stored polynomial + the seed: c_0 comes from the stream, c_1 is re-sampled from the seed
-            // (ciphertext.cpp:296-309 -> expand_seed :126-133)
-            const std::size_t half = static_cast<std::size_t>(k) * e.n;
-            if (ps.info.size != 2 || ps.info.data_words != half)
-                throw std::logic_error("ciphertext data is invalid");
-            const std::vector<u64> c1 = wire_expand_seed(e, k, ps.words + half * 8);
-            SEALHIP_CHECK(hipMemcpyAsync(dst, ps.words, half * 8, hipMemcpyHostToDevice, e.lane().stream));
-            SEALHIP_CHECK(hipMemcpyAsync(dst + half, c1.data(), half * 8, hipMemcpyHostToDevice, e.lane().stream));
-            SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream));
-            return;
-        }
-        if (ps.info.data_words != total)
-            throw std::logic_error("ciphertext data is invalid"); // is_buffer_valid, valcheck.cpp:228-240
-        if (total)
-            SEALHIP_CHECK(hipMemcpyAsync(dst, ps.words, total * 8, hipMemcpyHostToDevice, e.lane().stream));
+        const Checked c = check_load(e, bytes, len, info, capacity_words);
+        std::vector<SeedJob> jobs;
+        enqueue_load(e, c, dst, &jobs);
+        op_expand_seeds(e, c.k, jobs.data(), jobs.size());
         SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream)); // the caller's buffer may go away after the call
+    }
+
+    // Ciphertext::load for a batch: item i lands at dst + i * stride. Every stream is checked before anything is written;
+    // the seeded items of one level are expanded together, and the call synchronises once.
+    void wire_load_many(Engine &e, const void *const *streams, const std::size_t *lens, std::size_t count,
+                        sealhip_ciphertext_info *infos, u64 *dst, std::size_t stride)
+    {
+        std::vector<Checked> checked;
+        checked.reserve(count);
+        for (std::size_t i = 0; i < count; i++)
+            checked.push_back(check_load(e, streams[i], lens[i], &infos[i], stride));
+        std::map<int, std::vector<SeedJob>> jobs; // by level
+        for (std::size_t i = 0; i < count; i++)
+            enqueue_load(e, checked[i], dst + i * stride, &jobs[checked[i].k]);
+        for (const auto &kv : jobs)
+            op_expand_seeds(e, kv.first, kv.second.data(), kv.second.size());
+        SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream)); // the callers' buffers may go away after the call
     }
 
     std::size_t wire_save_size(std::uint32_t size, std::uint32_t k, std::size_t n)
@@ -371,6 +414,7 @@ namespace sealhip
                 SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&guard.dev), dim2 * digit_words * sizeof(u64)));
             }
             u64 *const dev = guard.dev;
+            std::vector<SeedJob> jobs; // the seeded digits' c_1, expanded together after the loop
             for (std::uint64_t j = 0; j < dim2; j++)
             {
                 {
@@ -386,12 +430,9 @@ namespace sealhip
                             // keys saved through Serializable<> carry c_1 as a seed (keygenerator.cpp:325-369 with save_seed)
                             if (ps.info.data_words != digit_words / 2)
                                 throw std::logic_error("kswitch_keys is not valid for encryption parameters");
-                            const std::vector<u64> c1 = wire_expand_seed(e, e.n_key, ps.words + (digit_words / 2) * 8);
                             SEALHIP_CHECK(hipMemcpyAsync(dev + j * digit_words, ps.words, (digit_words / 2) * sizeof(u64),
                                                          hipMemcpyHostToDevice, e.lane().stream));
-                            SEALHIP_CHECK(hipMemcpyAsync(dev + j * digit_words + digit_words / 2, c1.data(),
-                                                         (digit_words / 2) * sizeof(u64), hipMemcpyHostToDevice, e.lane().stream));
-                            SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream)); // c1 is a local buffer
+                            jobs.push_back(SeedJob{ ps.words + (digit_words / 2) * 8, dev + j * digit_words + digit_words / 2 });
                         }
                         else
                         {
@@ -404,6 +445,7 @@ namespace sealhip
                     p += ps.info.total_bytes;
                 }
             }
+            op_expand_seeds(e, e.n_key, jobs.data(), jobs.size()); // (no jobs: nothing is launched)
             if (i == index)
             {
                 SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream));

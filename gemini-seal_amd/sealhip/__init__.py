@@ -147,6 +147,9 @@ SYMBOLS = {
     "sealhip_ciphertext_resize": [_vp, _u32, _vp, _u32, _vp, _u32, _sz],
     "sealhip_kswitch_key_load_stream": [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_u64)],
     "sealhip_expand_seed_host": [_vp, _u32, _vp, _vp],
+    "sealhip_expand_seed": [_vp, _u32, _vp, _sz, _vp, _sz],
+    "sealhip_debug_seed_slack": [_vp, C.c_int64],
+    "sealhip_ciphertext_load_many": [_vp, _vp, _vp, _sz, _vp, _vp, _sz],
     "sealhip_host_register": [_vp, _vp, _sz],
     "sealhip_host_unregister": [_vp, _vp],
     "sealhip_debug_blake2xb": [_vp, _sz, _vp, _sz, _vp, _sz],
@@ -562,6 +565,28 @@ class Context:
         cap = dst.words if capacity_words is None else capacity_words
         _check(lib().sealhip_ciphertext_load(self.handle, C.addressof(buf), len(raw), C.addressof(info), _ptr(dst), cap))
         return info
+
+    def expand_seeds(self, rows, seeds, out, item_stride=0):
+        """Ciphertext::expand_seed on the device (sealhip_expand_seed): seeds = count x 8 words; out + i * item_stride
+        (0: rows x N) receives the rows x N words of c_1 for seed i"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        _check(lib().sealhip_expand_seed(self.handle, rows, seeds.ctypes.data, seeds.shape[0], _ptr(out), item_stride))
+
+    def debug_seed_slack(self, extra):
+        """candidates provisioned per seed beyond rows x N on this thread's lane (< 0: the default; sealhip_debug_seed_slack)"""
+        _check(lib().sealhip_debug_seed_slack(self.handle, int(extra)))
+
+    def load_ciphertexts(self, raws, dst, item_stride):
+        """Ciphertext::load for a batch (sealhip_ciphertext_load_many): stream i lands at dst + i * item_stride words;
+        returns the list of CiphertextInfo"""
+        n = len(raws)
+        bufs = [(C.c_char * max(1, len(r))).from_buffer_copy(r) if r else (C.c_char * 1)() for r in raws]
+        ptrs = (C.c_void_p * max(1, n))(*[C.addressof(b) for b in bufs])
+        lens = (C.c_size_t * max(1, n))(*[len(r) for r in raws])
+        infos = (CiphertextInfo * max(1, n))()
+        _check(lib().sealhip_ciphertext_load_many(self.handle, C.addressof(ptrs), C.addressof(lens), n, C.addressof(infos),
+                                                  _ptr(dst), item_stride))
+        return [infos[i] for i in range(n)]
 
     def save_ciphertext(self, info, src):
         """Ciphertext::save (ciphertext.cpp:170-226), uncompressed -> bytes"""

@@ -473,11 +473,19 @@ long sealhip_ciphertext_peek(const void *bytes, size_t len, sealhip_ciphertext_i
 /* Ciphertext::load (ciphertext.cpp:228-330, uncompressed stream): validates the metadata against the context and
    copies the coefficient words from `bytes` (host) straight into dst_device (capacity in words). A seeded ciphertext
    (info->seeded: one stored polynomial + a 64-byte seed, what Encryptor::encrypt_symmetric(...).save() writes) is expanded
-   like Ciphertext::expand_seed does (:126-133): c_1 is re-sampled on the host from the seed with the reference's
-   BlakePRNG (BLAKE2Xb, randomgen.cpp:63-73) and sample_poly_uniform (util/rlwe.cpp:101-129), re-implemented in
-   csrc/blake2xb.cpp from the BLAKE2 specifications; dst_device receives both polynomials. */
+   like Ciphertext::expand_seed does (:126-133): c_1 is re-sampled on the device from the seed (sealhip_expand_seed) with
+   the reference's BlakePRNG (BLAKE2Xb, randomgen.cpp:63-73) and sample_poly_uniform (util/rlwe.cpp:101-129), the same words
+   as the host implementation csrc/blake2xb.cpp; dst_device receives both polynomials. */
 long sealhip_ciphertext_load(sealhip_context *ctx, const void *bytes, size_t len, sealhip_ciphertext_info *info,
                              uint64_t *dst_device, size_t capacity_words);
+/* Ciphertext::load for a batch of `count` streams (a std::vector<Ciphertext> arriving from clients): stream i (lens[i]
+   bytes) lands at dst_device + i * item_stride_words and its metadata in infos[i]. Seeded and unseeded streams may be mixed.
+   Every stream is checked as sealhip_ciphertext_load checks it, with the same errors and messages, before anything is
+   written: when stream i fails the call returns its error and dst_device is unchanged. A stride below an item's size x k x N
+   is "destination buffer is too small". The seeded items of one level are expanded in one sealhip_expand_seed launch (per
+   arena chunk); the call synchronises once, at the end. */
+long sealhip_ciphertext_load_many(sealhip_context *ctx, const void *const *streams, const size_t *lens, size_t count,
+                                  sealhip_ciphertext_info *infos, uint64_t *dst_device, size_t item_stride_words);
 /* Ciphertext::save_size(compr_mode_type::none) (ciphertext.cpp:135-168) and Ciphertext::save: the stream is written
    into `bytes` (host) with the coefficient words copied straight from src_device. */
 long sealhip_ciphertext_save_size(const sealhip_context *ctx, uint32_t size, uint32_t k, size_t *bytes);
@@ -487,13 +495,26 @@ long sealhip_ciphertext_save(sealhip_context *ctx, const sealhip_ciphertext_info
    index = key_power - 2 (relinkeys.h:61-68), GaloisKeys: index = (galois_elt - 1) / 2 (galoiskeys.h:52-55) -- with its
    decomposition digits concatenated straight from the stream into HBM. *key = NULL when that slot is empty; n_slots (may
    be NULL) receives keys_.size(). Needs the key level's parms_id registered (k = n_key_moduli). Seeded digits (keys saved
-   as Serializable<RelinKeys>) are expanded as in sealhip_ciphertext_load. */
+   as Serializable<RelinKeys>) are expanded on the device as in sealhip_ciphertext_load, all digits of the slot in one
+   launch. */
 long sealhip_kswitch_key_load_stream(sealhip_context *ctx, const void *bytes, size_t len, uint32_t index,
                                      sealhip_kswitch_key **key, uint64_t *n_slots);
 /* Ciphertext::expand_seed on the host (works on host-only contexts): out_host[rows][N] = the words of c_1 for `seed`
    (random_seed_type: 8 x uint64) over the first `rows` key primes. sealhip_debug_blake2xb: the BLAKE2Xb function under it. */
 long sealhip_expand_seed_host(sealhip_context *ctx, uint32_t rows, const uint64_t seed[8], uint64_t *out_host);
 long sealhip_debug_blake2xb(void *out, size_t outlen, const void *in, size_t inlen, const void *key, size_t keylen);
+/* Ciphertext::expand_seed on the device for a batch: out_device + i * item_stride_words receives the rows x N words of c_1
+   for seed i (seeds_host: count x 8 words, the random_seed_type layout), word for word what sealhip_expand_seed_host
+   computes. item_stride_words 0 means rows x N; 2 x k x N with out_device = ct + k x N fills the c_1 of a ciphertext batch.
+   rows outside 1..n_key_moduli, or a nonzero stride below rows x N -> E_INVALIDARG (null pointers -> E_POINTER first);
+   count 0 -> S_OK, nothing launched. Runs on the calling thread's lane in stream order (the seeds are staged before it
+   returns). DESIGN.md "Seed expansion" describes the kernels. */
+long sealhip_expand_seed(sealhip_context *ctx, uint32_t rows, const uint64_t *seeds_host, size_t count, uint64_t *out_device,
+                         size_t item_stride_words);
+/* Test hook of sealhip_expand_seed for the calling thread's lane: candidates provisioned per seed beyond rows x N (rounded
+   up to whole 4096-byte PRNG buffers). < 0 restores the computed default; 0 sends every rejection through the in-kernel
+   continuation. It never changes the words, only which path produces them. */
+long sealhip_debug_seed_slack(sealhip_context *ctx, int64_t extra_candidates_per_seed);
 /* KSwitchKeys::save (kswitchkeys.cpp:43-85 under Serialization::Save, uncompressed): writes a RelinKeys / GaloisKeys stream
    whose keys_[i] is keys[i] (NULL = unused slot, keys_dim2 = 0) with the digit words copied straight from HBM. bytes == NULL:
    only the size is reported in *written. Needs the key level's parms_id registered. The stream round-trips through

@@ -1,0 +1,334 @@
+"""Seed expansion on the device (seed_expand.hip): sealhip_expand_seed, the seeded branches of sealhip_ciphertext_load and
+sealhip_kswitch_key_load_stream, and sealhip_ciphertext_load_many. Every word is compared with the oracle's
+Ciphertext::expand_seed (oracle_lib.expand_seed) and with the library's host expansion (ctx.expand_seed)."""
+import ctypes as C
+import hashlib
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from test_seed_expand_host import reject_chain, restated_expand
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+@pytest.fixture(scope="module")
+def S():
+    import sealhip
+
+    assert sealhip.num_devices() >= 1
+    return sealhip
+
+
+def wire():
+    spec = importlib.util.spec_from_file_location("wire_format", os.path.join(ROOT, "oracle", "wire_format.py"))
+    W = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(W)
+    return W
+
+
+def golden_seeds():
+    vec = json.load(open(os.path.join(HERE, "golden", "prng_vectors.json")))
+    return [[int(x) for x in t["seed"]] for t in vec["prng"]]
+
+
+def rand_seeds(rng, count):
+    return rng.integers(0, 2**63, size=(count, 8), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(count, 8),
+                                                                                                   dtype=np.uint64)
+
+
+def d2h(ctx, S, buf, off_words, words):
+    out = np.empty(words, dtype=np.uint64)
+    ctx.synchronize()
+    S._check(S.lib().sealhip_memcpy_d2h(ctx.handle, out.ctypes.data, buf.ptr + 8 * off_words, words * 8))
+    return out
+
+
+def cfg3(S):
+    logn, n = 15, 1 << 15
+    mods = O.coeff_modulus_create(n, [55] * 8)
+    return S.Context(S.SCHEME_BFV, logn, mods, 1, 786433), mods, n
+
+
+@pytest.mark.parametrize("logn", [3, 12, 15, 16])
+def test_device_expansion_word_for_word(S, logn):
+    n = 1 << logn
+    rng = np.random.default_rng(100 + logn)
+    chains = [O.coeff_modulus_create(n, [20, 36, 50, 55, 60]), reject_chain(logn, 5)]
+    seeds = [[0] * 8] + golden_seeds() + [list(map(int, s)) for s in rand_seeds(rng, 2)]
+    for mods in chains:
+        ctx = S.Context(S.SCHEME_CKKS, logn, mods, 1, 0)
+        for rows in (1, len(mods) - 1, len(mods)):
+            out = ctx.alloc(len(seeds) * rows * n)
+            ctx.expand_seeds(rows, np.array(seeds, dtype=np.uint64), out)
+            got = out.download((len(seeds), rows, n))
+            for i, seed in enumerate(seeds):
+                want = O.expand_seed(seed, mods[:rows], n)
+                assert np.array_equal(got[i], want), (logn, rows, i, mods)
+                assert np.array_equal(got[i], ctx.expand_seed(rows, seed))
+
+
+def test_cfg3_batches_1_3_1024(S):
+    ctx, mods, n = cfg3(S)
+    k = 7
+    rng = np.random.default_rng(7)
+    for count in (1, 3):
+        seeds = rand_seeds(rng, count)
+        out = ctx.alloc(count * k * n)
+        ctx.expand_seeds(k, seeds, out)
+        got = out.download((count, k, n))
+        for i in range(count):
+            assert np.array_equal(got[i], O.expand_seed(seeds[i], mods[:k], n))
+            assert np.array_equal(got[i], ctx.expand_seed(k, seeds[i]))
+    count = 1024
+    seeds = rand_seeds(rng, count)
+    out = ctx.alloc(count * k * n)
+    ctx.expand_seeds(k, seeds, out)
+    ctx.synchronize()
+
+    def ref_digest(i):
+        return hashlib.sha256(O.expand_seed(seeds[i], mods[:k], n).tobytes()).hexdigest()
+
+    with ThreadPoolExecutor(16) as pool:  # the oracle's ctypes calls release the GIL
+        want = list(pool.map(ref_digest, range(count)))
+    for i in range(count):
+        got = d2h(ctx, S, out, i * k * n, k * n)
+        assert hashlib.sha256(got.tobytes()).hexdigest() == want[i], i
+    for i in (0, 1, 511, 512, 777, count - 1):  # full words of a spread of items, against the host expansion too
+        got = d2h(ctx, S, out, i * k * n, k * n).reshape(k, n)
+        assert np.array_equal(got, ctx.expand_seed(k, seeds[i]))
+
+
+def test_strided_output_into_ciphertext_c1(S):
+    logn, n = 12, 4096
+    mods = O.coeff_modulus_create(n, [36, 36, 37, 40])
+    ctx = S.Context(S.SCHEME_BFV, logn, mods, 1, 65537)
+    k, count = 3, 5
+    rng = np.random.default_rng(3)
+    seeds = rand_seeds(rng, count)
+    sentinel = np.full((count, 2, k, n), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    ct = ctx.upload(sentinel)
+    ctx.expand_seeds(k, seeds, ct.ptr + 8 * k * n, item_stride=2 * k * n)
+    got = ct.download((count, 2, k, n))
+    assert np.array_equal(got[:, 0], sentinel[:, 0])  # c_0 untouched
+    for i in range(count):
+        assert np.array_equal(got[i, 1], O.expand_seed(seeds[i], mods[:k], n))
+    # a stride of count x 2kN leaves everything past the last item alone
+    big = ctx.upload(np.full(3 * 2 * k * n + 17, 7, dtype=np.uint64))
+    ctx.expand_seeds(k, seeds[:3], big, item_stride=2 * k * n)
+    b = big.download()
+    for i in range(3):
+        assert np.array_equal(b[i * 2 * k * n:i * 2 * k * n + k * n].reshape(k, n), O.expand_seed(seeds[i], mods[:k], n))
+        assert (b[i * 2 * k * n + k * n:(i + 1) * 2 * k * n] == 7).all()
+    assert (b[3 * 2 * k * n:] == 7).all()
+
+
+def test_continuation_path_gives_the_same_words(S):
+    """debug_seed_slack(0) provisions exactly rows x N candidates: every rejection is made up by the in-kernel generator"""
+    logn, n = 12, 4096
+    mods = reject_chain(logn, 5)
+    ctx = S.Context(S.SCHEME_CKKS, logn, mods, 1, 0)
+    rng = np.random.default_rng(11)
+    seeds = rand_seeds(rng, 4)
+    rows = len(mods)
+    rejected = sum(restated_expand(S, s, mods, n)[1] for s in seeds)
+    assert rejected > 4 * rows * n // 20  # about 11 % of the candidates were rejected: the continuation had work to do
+    for slack in (0, 1, 511, -1):
+        ctx.debug_seed_slack(slack)
+        out = ctx.alloc(len(seeds) * rows * n)
+        ctx.expand_seeds(rows, seeds, out)
+        got = out.download((len(seeds), rows, n))
+        for i in range(len(seeds)):
+            assert np.array_equal(got[i], O.expand_seed(seeds[i], mods, n)), (slack, i)
+    ctx.debug_seed_slack(-1)
+
+
+CHUNK_CHILD = r"""
+import json, sys
+import numpy as np
+sys.path[:0] = [{root!r}, {tests!r}, {pkg!r}]
+import oracle_lib as O
+import sealhip as S
+logn, n, k, count = 15, 1 << 15, 7, 100
+mods = O.coeff_modulus_create(n, [55] * 8)
+ctx = S.Context(S.SCHEME_BFV, logn, mods, 1, 786433)
+rng = np.random.default_rng(5)
+seeds = rng.integers(0, 2**63, size=(count, 8), dtype=np.uint64)
+out = ctx.alloc(count * k * n)
+ctx.chunk_log()
+ctx.expand_seeds(k, seeds, out)
+log = ctx.chunk_log()
+got = out.download((count, k, n))
+bad = [i for i in range(count) if not np.array_equal(got[i], O.expand_seed(seeds[i], mods[:k], n))]
+print(json.dumps({{"log": log, "bad": bad}}))
+"""
+
+
+def test_chunked_batch_in_a_small_arena(S):
+    env = dict(os.environ, SEALHIP_WORKSPACE_MB="64")
+    code = CHUNK_CHILD.format(root=ROOT, tests=HERE, pkg=os.path.join(ROOT, "gemini-seal_amd"))
+    res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    r = json.loads(res.stdout.strip().splitlines()[-1])
+    (batch, chunk), = r["log"]
+    assert batch == 100 and 1 <= chunk < 100  # more than one chunk
+    assert r["bad"] == []
+
+
+def test_load_many_mixed_errors_and_stride(S):
+    W = wire()
+    logn, n = 12, 4096
+    mods = O.coeff_modulus_create(n, [36, 36, 37, 40])
+    ctx = S.Context(S.SCHEME_BFV, logn, mods, 1, 65537)
+    ids = {3: (1, 2, 3, 4), 2: (5, 6, 7, 8)}
+    for kk, pid in ids.items():
+        ctx.set_parms_id(kk, pid)
+    rng = np.random.default_rng(23)
+    k = 3
+    stride = 2 * k * n + 64
+    raws, expect_c1 = [], {}
+    for i in range(9):
+        c0 = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in mods[:k]])
+        if i % 3 == 1:  # unseeded
+            c1 = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in mods[:k]])
+            raws.append(W.save_ciphertext(ids[k], True, 2, n, k, 1.0, np.concatenate([c0, c1]).reshape(-1)))
+        else:
+            seed = rng.integers(0, 2**63, size=8, dtype=np.uint64)
+            raws.append(W.save_ciphertext(ids[k], True, 2, n, k, 1.0, c0.reshape(-1), seed=seed.astype("<u8").tobytes()))
+            expect_c1[i] = O.expand_seed(seed, mods[:k], n)
+    # a level-2 item in the same batch is expanded in its own launch
+    seed2 = rng.integers(0, 2**63, size=8, dtype=np.uint64)
+    c0_2 = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in mods[:2]])
+    raws.append(W.save_ciphertext(ids[2], True, 2, n, 2, 1.0, c0_2.reshape(-1), seed=seed2.astype("<u8").tobytes()))
+    count = len(raws)
+    dst = ctx.upload(np.full(count * stride, 3, dtype=np.uint64))
+    infos = ctx.load_ciphertexts(raws, dst, stride)
+    got = dst.download((count, stride))
+    one = ctx.alloc(2 * k * n)
+    for i, raw in enumerate(raws):
+        info = ctx.load_ciphertext(raw, one)
+        kk = info.coeff_modulus_size
+        assert (infos[i].seeded, infos[i].size, infos[i].coeff_modulus_size) == (info.seeded, info.size, kk)
+        assert np.array_equal(got[i, :2 * kk * n], one.download()[:2 * kk * n]), i
+        assert (got[i, 2 * kk * n:] == 3).all()
+        if i in expect_c1:
+            assert np.array_equal(got[i, k * n:2 * k * n].reshape(k, n), expect_c1[i])
+    assert np.array_equal(got[count - 1, 2 * n:4 * n].reshape(2, n), O.expand_seed(seed2, mods[:2], n))
+    # a malformed stream in the middle: its error, and nothing written
+    before = np.full(count * stride, 9, dtype=np.uint64)
+    dst2 = ctx.upload(before)
+    bad = list(raws)
+    bad[4] = bad[4][:-8]
+    with pytest.raises(RuntimeError, match="I/O error"):
+        ctx.load_ciphertexts(bad, dst2, stride)
+    bad[4] = W.save_ciphertext((7, 7, 7, 7), True, 2, n, k, 1.0, np.zeros(2 * k * n, dtype=np.uint64))
+    with pytest.raises(S.LogicError, match="ciphertext data is invalid"):
+        ctx.load_ciphertexts(bad, dst2, stride)
+    assert np.array_equal(dst2.download(), before)
+    with pytest.raises(ValueError, match="destination buffer is too small"):
+        ctx.load_ciphertexts(raws, dst2, 2 * k * n - 1)
+    assert np.array_equal(dst2.download(), before)
+    assert ctx.load_ciphertexts([], dst2, stride) == []
+
+
+def _seeded_key_stream(W, key_id, digits0, seeds, n, n_key):
+    import struct
+
+    body = struct.pack("<4Q", *key_id) + struct.pack("<Q", 1) + struct.pack("<Q", len(digits0))
+    for c0, sd in zip(digits0, seeds):
+        body += W.save_ciphertext(key_id, True, 2, n, n_key, 1.0, c0.reshape(-1), seed=np.array(sd, dtype="<u8").tobytes())
+    return W.header(16 + len(body)) + body
+
+
+@pytest.mark.parametrize("nsp,n_key", [(2, 8), (3, 9)])
+def test_seeded_key_streams_with_several_special_primes(S, nsp, n_key):
+    W = wire()
+    logn, n, t = 12, 4096, 65537
+    kmods = O.coeff_modulus_create(n, [40] * n_key)
+    ctx = S.Context(S.SCHEME_BFV, logn, kmods, nsp, t)
+    ev = S.Evaluator(ctx)
+    rng = np.random.default_rng(nsp)
+    k = n_key - nsp
+    key_id = (9, 10, 11, 12)
+    ctx.set_parms_id(n_key, key_id)
+    d = (k + nsp - 1) // nsp
+    assert d >= 2
+    digits0 = [np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in kmods]) for _ in range(d)]
+    seeds = [[int(x) for x in rng.integers(0, 2**63, size=8)] for _ in range(d)]
+    full = np.stack([np.stack([digits0[j], O.expand_seed(seeds[j], kmods, n)]) for j in range(d)])
+    rk_seeded = S.KSwitchKeys.from_stream(ctx, _seeded_key_stream(W, key_id, digits0, seeds, n, n_key), 0)
+    ct = np.stack([np.stack([np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in kmods[:k]])
+                             for _ in range(3)]) for _ in range(2)])
+    a, b = ctx.upload(ct), ctx.upload(ct)
+    ev.relinearize_inplace(a, 3, k, 2, [rk_seeded])
+    ev.relinearize_inplace(b, 3, k, 2, [S.KSwitchKeys(ctx, full)])
+    assert np.array_equal(a.download(), b.download())
+    # the loaded key is the expanded key: save it and compare the words
+    raw = S.save_kswitch_keys(ctx, [rk_seeded])
+    raw_full = S.save_kswitch_keys(ctx, [S.KSwitchKeys(ctx, full)])
+    assert raw == raw_full
+
+
+def test_two_threads_expand_on_their_own_lanes(S):
+    ctx, mods, n = cfg3(S)
+    k = 7
+    rng = np.random.default_rng(31)
+    batches = [rand_seeds(rng, 6), rand_seeds(rng, 9)]
+    outs = [ctx.alloc(len(b) * k * n) for b in batches]
+    errors = []
+    barrier = threading.Barrier(2)
+
+    def work(i):
+        try:
+            barrier.wait()
+            for _ in range(3):
+                ctx.expand_seeds(k, batches[i], outs[i])
+            ctx.synchronize()
+        except Exception as e:  # surfaced below
+            errors.append(e)
+
+    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    assert not errors, errors
+    for b, out in zip(batches, outs):
+        got = out.download((len(b), k, n))
+        for i in range(len(b)):
+            assert np.array_equal(got[i], O.expand_seed(b[i], mods[:k], n))
+
+
+def test_edge_cases(S):
+    L = S.lib()
+    for logn, bits in ((15, [55] * 4), (16, [50] * 4)):
+        n = 1 << logn
+        mods = O.coeff_modulus_create(n, bits)
+        ctx = S.Context(S.SCHEME_BFV, logn, mods, 1, 786433)
+        out = ctx.alloc(4 * n)
+        seeds = np.zeros((1, 8), dtype=np.uint64)
+        S._check(L.sealhip_expand_seed(ctx.handle, 2, seeds.ctypes.data, 0, out.ptr, 0))  # count 0: S_OK
+        ctx.expand_seeds(2, seeds[:0], out)
+        ctx.synchronize()
+        for rows in (0, len(mods) + 1):
+            with pytest.raises(ValueError):
+                ctx.expand_seeds(rows, seeds, out)
+        with pytest.raises(ValueError):
+            ctx.expand_seeds(2, seeds, out, item_stride=2 * n - 1)
+        with pytest.raises(TypeError):
+            S._check(L.sealhip_expand_seed(ctx.handle, 2, None, 1, out.ptr, 0))
+        with pytest.raises(TypeError):
+            S._check(L.sealhip_expand_seed(ctx.handle, 2, seeds.ctypes.data, 1, None, 0))
+        ctx.expand_seeds(len(mods), seeds, out)  # a valid call after the refused ones
+        assert np.array_equal(out.download((len(mods), n)), O.expand_seed([0] * 8, mods, n))

@@ -45,7 +45,7 @@ def main():
                            text=True).stdout.splitlines()
     rows = []
     for r, n in zip(recs, names):
-        n = re.sub(r"^void sealhip::\(anonymous namespace\)::", "", n)
+        n = re.sub(r"^(void )?sealhip::\(anonymous namespace\)::", "", n)
         n = re.sub(r"\(.*$", "", n)
         spill = int(r.get("vgpr_spill_count", 0))
         if (flt and flt not in n) or ("--spills-only" in sys.argv and spill == 0):
