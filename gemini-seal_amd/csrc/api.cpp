@@ -1553,6 +1553,58 @@ long sealhip_evaluator_multiply_plain(sealhip_context *ctx, uint32_t k, uint64_t
     });
 }
 
+long sealhip_evaluator_transform_plain_to_ntt(sealhip_context *ctx, uint32_t k, const uint64_t *plain, size_t plain_coeff_count,
+                                              size_t plain_stride, size_t count, uint64_t *plain_ntt)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plain);
+    REQUIRE_PTR(plain_ntt);
+    return guarded([&] {
+        // (the argument checks need no device: they come before the host-only context's refusal)
+        const Engine &h = *ctx->engine;
+        check_level(h, k);
+        if (plain_coeff_count > h.n)
+            throw std::invalid_argument("plain is not valid for encryption parameters"); // valcheck.cpp:236-281
+        if (plain_stride != 0 && plain_stride < plain_coeff_count)
+            throw std::invalid_argument("plain_stride is smaller than one plaintext");
+        if (h.scheme != 1 && plain_coeff_count > 0)
+            throw std::invalid_argument("plain is not valid for encryption parameters"); // plain_modulus 0 (valcheck.cpp:266-279)
+        const std::size_t out_words = count * k * h.n;
+        const std::size_t in_words = count ? (count - 1) * (plain_stride ? plain_stride : plain_coeff_count) + plain_coeff_count : 0;
+        if (in_words && out_words && plain < plain_ntt + out_words && plain_ntt < plain + in_words)
+            throw std::invalid_argument("plain and plain_ntt overlap");
+        Engine &e = device_engine(ctx);
+        op_transform_plain_to_ntt(e, static_cast<int>(k), reinterpret_cast<const u64 *>(plain), plain_coeff_count, plain_stride,
+                                  count, reinterpret_cast<u64 *>(plain_ntt));
+    });
+}
+
+long sealhip_evaluator_mod_switch_plain_to(sealhip_context *ctx, uint32_t k_from, const uint64_t *plain, size_t count,
+                                          uint32_t k_to, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plain);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        const Engine &h = *ctx->engine;
+        check_level(h, k_from);
+        if (k_to > k_from)
+            throw std::invalid_argument("cannot switch to higher level modulus"); // evaluator.cpp:1079-1082
+        if (k_to < 1)
+            throw std::invalid_argument("end of modulus switching chain reached"); // :967-970
+        const std::size_t in_words = count * k_from * h.n, out_words = count * k_to * h.n;
+        const bool in_place_ok = plain == out && (k_to == k_from || count <= 1); // (every word goes back where it was read)
+        if (count && !in_place_ok && plain < out + out_words && out < plain + in_words)
+            throw std::invalid_argument("plain and out overlap");
+        Engine &e = device_engine(ctx);
+        // mod_switch_drop_to_next (evaluator.cpp:959-994) per level: Plaintext::resize keeps the leading rows
+        check_launch(launch_copy_rows(e, reinterpret_cast<const u64 *>(plain), static_cast<std::size_t>(k_from) * e.n,
+                                      reinterpret_cast<u64 *>(out), static_cast<std::size_t>(k_to) * e.n, count,
+                                      static_cast<int>(k_to)),
+                     "mod_switch_plain");
+    });
+}
+
 long sealhip_transparency_sink(sealhip_context *ctx, uint32_t *nonzero_flags, size_t capacity)
 {
     REQUIRE_PTR(ctx);

@@ -494,6 +494,9 @@ namespace sealhip
                                    const RowMap &map, unsigned *flags);
     hipError_t launch_plain_lift(const Engine &e, const u64 *plain, std::size_t plain_stride, u64 *out, std::size_t nplains,
                                  const RowMap &map, u64 t);
+    // transform_to_ntt(Plaintext)'s lift (both reference branches, one formula: poly.hip): out[nplains][map.rows][N]
+    hipError_t launch_plain_lift_centered(const Engine &e, const u64 *plain, std::size_t coeff_count, std::size_t plain_stride,
+                                          u64 *out, std::size_t nplains, const RowMap &map, u64 t);
     hipError_t launch_galois(const Engine &e, const u64 *in, u64 *out, std::size_t nrows, const RowMap &map,
                              std::uint32_t elt, const std::uint32_t *table /* null: coefficient form */);
 
@@ -575,6 +578,9 @@ namespace sealhip
     void op_apply_galois(Engine &e, int k, u64 *ct, std::size_t count, std::uint32_t elt, const KSwitchKey &key);
     void op_multiply_plain(Engine &e, int k, u64 *ct, int size, std::size_t count, const u64 *plain,
                            std::size_t plain_stride);
+    // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV: plain_ntt[count][k][N]
+    void op_transform_plain_to_ntt(Engine &e, int k, const u64 *plain, std::size_t coeff_count, std::size_t plain_stride,
+                                   std::size_t count, u64 *plain_ntt);
     // Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265) and RNSTool::decrypt_scale_and_round
     void op_dot_product_ct_sk(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,
                               bool is_ntt_form, u64 *out);

@@ -810,6 +810,21 @@ namespace sealhip
               "dyadic(plain)");
         check(launch_ntt(e, ct, count * size * k, map_q, true, kNttCanonical), "intt(ct)");
     }
+    // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV, every parameter set: each plaintext lifted to
+    // the k primes of the level (one formula serves the fast and the general branch, poly.hip) straight into the
+    // destination, then the canonical transform in place. (A lift fused into the single-pass transform's load phase was
+    // built and measured: faster than this, slower than the transform alone -- not adopted)
+    void op_transform_plain_to_ntt(Engine &e, int k, const u64 *plain, std::size_t coeff_count, std::size_t plain_stride,
+                                   std::size_t count, u64 *plain_ntt)
+    {
+        if (count == 0)
+            return;
+        const RowMap map_q = e.level_host(k).map_q;
+        check(launch_plain_lift_centered(e, plain, coeff_count, plain_stride ? plain_stride : coeff_count, plain_ntt, count,
+                                         map_q, e.t),
+              "plain_lift");
+        check(launch_ntt(e, plain_ntt, count * k, map_q, false, kNttCanonical), "ntt(plain)");
+    }
     // Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i in the
     // form of the ciphertext. sk_powers = (size-1) polynomials s, s^2, ... in NTT form with key-level row stride.
     void op_dot_product_ct_sk(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,

@@ -316,6 +316,33 @@ namespace sealhip
             }
         }
 
+        // transform_to_ntt(Plaintext)'s lift (evaluator.cpp:1682-1737). Both reference branches -- v + (q_r - t) for
+        // v >= thr when every q_r > t, the multi-word v + (Q - t) decomposed otherwise -- give the canonical residue of
+        // the centred value: out = (v - t [v >= thr]) mod q_r, formed as the canonical residue of
+        // v + (q_r - t mod q_r) [v >= thr] < t + q_r < 2^62 (t < 2^61). Coefficients at or beyond coeff_count are zero and
+        // are not read.
+        __global__ __launch_bounds__(kThreads) void plain_lift_centered_kernel(const u64 *__restrict__ plain,
+                                                                               std::size_t coeff_count, std::size_t plain_stride,
+                                                                               u64 *__restrict__ out,
+                                                                               const PrimeDev *__restrict__ primes, RowMap map,
+                                                                               int logn, u64 t, u64 threshold, std::size_t nplains)
+        {
+            const std::size_t n = static_cast<std::size_t>(1) << logn;
+            const std::size_t total = nplains * map.rows * n;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total;
+                 i += stride)
+            {
+                const std::size_t c = i & (n - 1);
+                const std::size_t row = i >> logn;
+                const std::size_t item = row / map.rows;
+                const PrimeDev &P = primes[map.prime[row % map.rows]];
+                const u64 v = c < coeff_count ? plain[item * plain_stride + c] : 0;
+                const u64 inc = P.p - barrett_reduce_63(t, P.p, P.cr1);
+                out[i] = barrett_reduce_63(v + (v >= threshold ? inc : 0), P.p, P.cr1);
+            }
+        }
+
         // Decryptor::dot_product_ct_sk_array (decryptor.cpp:246-256, :265): out = sum_{i>=1} ct_i (.) s^i, each term
         // reduced (dyadic_product_coeffmod) and accumulated with add_poly_coeffmod; with add_c0 also + ct_0 (NTT-form
         // ciphertexts; coefficient-form ones add c_0 after the inverse NTT). ct polys 1.. may hold lazy NTT values.
@@ -540,6 +567,18 @@ namespace sealhip
         ProfScope prof(e, "plain_lift", 0);
         plain_lift_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(plain, plain_stride, out, e.d_primes, map, e.logn, t,
                                                                     (t + 1) >> 1, nplains);
+        return hipGetLastError();
+    }
+    hipError_t launch_plain_lift_centered(const Engine &e, const u64 *plain, std::size_t coeff_count, std::size_t plain_stride,
+                                          u64 *out, std::size_t nplains, const RowMap &map, u64 t)
+    {
+        const std::size_t total = (nplains * map.rows) << e.logn;
+        if (total == 0)
+            return hipSuccess;
+        ProfScope prof(e, "plain_lift_centered", 0);
+        plain_lift_centered_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(plain, coeff_count, plain_stride, out,
+                                                                                       e.d_primes, map, e.logn, t, (t + 1) >> 1,
+                                                                                       nplains);
         return hipGetLastError();
     }
     hipError_t launch_dot_sk(const Engine &e, const u64 *ct, int size, std::size_t ct_item_stride, const u64 *sk_powers,

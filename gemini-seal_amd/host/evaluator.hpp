@@ -4,8 +4,8 @@
 // subclass: it is a class with the same method names and argument meaning for the hot-path operations
 // (evaluator.h:246-298 multiply/square, :344-371 relinearize, :396-430 mod_switch_to_next, :479-502 mod_switch_to, :565-583
 // rescale_to_next, :606-629 rescale_to, :183 add_many, :902-947 transform_to/from_ntt, :984-1021 apply_galois, :1057-1103
-// rotate_rows, :1131-1173 rotate_columns, :1201-1239 rotate_vector, :1269-1308 complex_conjugate, and every
-// destination-taking variant), doing
+// rotate_rows, :1131-1173 rotate_columns, :1201-1239 rotate_vector, :1269-1308 complex_conjugate, :859-900 transform_to_ntt
+// and :430-548 mod_switch_to(_next) of plaintexts, and every destination-taking variant), doing
 // the same metadata checks on the host and forwarding raw pointers to the ABI. It is a template over the
 // ciphertext type so that it compiles both against seal::Ciphertext (where the reference headers exist) and
 // against the plain sealhip::HostCiphertext below (everywhere else, e.g. the GPU box).
@@ -77,7 +77,8 @@ namespace sealhip_host
     class Context
     {
     public:
-        explicit Context(const sealhip_params &p) : scheme_(p.scheme), n_(std::size_t(1) << p.log_n)
+        explicit Context(const sealhip_params &p)
+            : scheme_(p.scheme), n_(std::size_t(1) << p.log_n), t_(p.plain_modulus), n_key_(p.n_key_moduli)
         {
             throw_on(sealhip_context_create(&p, &ctx_));
         }
@@ -91,11 +92,15 @@ namespace sealhip_host
         sealhip_context *get() const { return ctx_; }
         std::uint32_t scheme() const { return scheme_; }
         std::size_t n() const { return n_; }
+        std::uint64_t plain_modulus() const { return t_; }
+        std::size_t n_key() const { return n_key_; } // the highest level the ABI names (key level)
 
     private:
         sealhip_context *ctx_ = nullptr;
         std::uint32_t scheme_;
         std::size_t n_;
+        std::uint64_t t_;
+        std::size_t n_key_;
     };
 
     // device staging of one host object
@@ -581,6 +586,77 @@ namespace sealhip_host
         {
             plain_linear(encrypted, plain, plain_is_ntt_form, true);
         }
+        // Evaluator::transform_to_ntt(Plaintext, parms_id) (evaluator.cpp:1648-1744), BFV, with or without fast plain lift.
+        // plain: coeff_count coefficients in coefficient form (Plaintext::coeff_count()); destination_ntt: k*N words, the
+        // plaintext at level k (k primes) in NTT form, ready for multiply_plain on an NTT-form ciphertext of that level.
+        void transform_to_ntt(const std::uint64_t *plain, std::size_t coeff_count, std::size_t k, std::uint64_t *destination_ntt)
+        {
+            check_plain(plain, coeff_count);
+            if (k < 1 || k > ctx_.n_key())
+                throw std::invalid_argument("parms_id is not valid for the current context"); // :1657-1661
+            const std::size_t n = ctx_.n();
+            Staged p(ctx_, coeff_count ? coeff_count : 1), o(ctx_, k * n);
+            if (coeff_count)
+                p.up(plain, coeff_count);
+            throw_on(sealhip_evaluator_transform_plain_to_ntt(ctx_.get(), std::uint32_t(k), p.ptr(), coeff_count, 0, 1, o.ptr()));
+            o.down(destination_ntt, k * n);
+        }
+        // transform_to_ntt_inplace(Plaintext &, parms_id): plain holds plain.size() coefficients and is resized to k*N words
+        // like Plaintext::resize (:1682-1683); is_ntt_form plays Plaintext::is_ntt_form() and is set on success.
+        void transform_to_ntt_inplace(std::vector<std::uint64_t> &plain, std::size_t k, bool &is_ntt_form)
+        {
+            check_plain(plain.data(), plain.size());
+            if (k < 1 || k > ctx_.n_key())
+                throw std::invalid_argument("parms_id is not valid for the current context");
+            if (is_ntt_form)
+                throw std::invalid_argument("plain is already in NTT form"); // :1662-1665
+            std::vector<std::uint64_t> out(k * ctx_.n());
+            transform_to_ntt(plain.data(), plain.size(), k, out.data());
+            plain.swap(out);
+            is_ntt_form = true;
+        }
+        // Evaluator::mod_switch_to_inplace(Plaintext &, parms_id) (evaluator.cpp:1062-1088) on an NTT-form plaintext of
+        // plain.size() / N primes: the leading target_coeff_modulus_size rows stay (mod_switch_drop_to_next, :959-994).
+        void mod_switch_to_inplace(std::vector<std::uint64_t> &plain, bool is_ntt_form, std::size_t target_coeff_modulus_size)
+        {
+            const std::size_t k = plain_level(plain);
+            if (target_coeff_modulus_size < 1 || target_coeff_modulus_size > ctx_.n_key())
+                throw std::invalid_argument("parms_id is not valid for encryption parameters"); // :1071-1074
+            if (!is_ntt_form)
+                throw std::invalid_argument("plain is not in NTT form"); // :1075-1078
+            if (k < target_coeff_modulus_size)
+                throw std::invalid_argument("cannot switch to higher level modulus"); // :1079-1082
+            if (k == target_coeff_modulus_size)
+                return;
+            const std::size_t n = ctx_.n();
+            Staged in(ctx_, k * n), out(ctx_, target_coeff_modulus_size * n);
+            in.up(plain.data(), k * n);
+            throw_on(sealhip_evaluator_mod_switch_plain_to(ctx_.get(), std::uint32_t(k), in.ptr(), 1,
+                                                           std::uint32_t(target_coeff_modulus_size), out.ptr()));
+            plain.resize(target_coeff_modulus_size * n);
+            out.down(plain.data(), target_coeff_modulus_size * n);
+        }
+        void mod_switch_to(const std::vector<std::uint64_t> &plain, bool is_ntt_form, std::size_t target_coeff_modulus_size,
+                           std::vector<std::uint64_t> &destination)
+        {
+            destination = plain;
+            mod_switch_to_inplace(destination, is_ntt_form, target_coeff_modulus_size);
+        }
+        // Evaluator::mod_switch_to_next_inplace(Plaintext &) (evaluator.h:430-438, evaluator.cpp:959-994)
+        void mod_switch_to_next_inplace(std::vector<std::uint64_t> &plain, bool is_ntt_form)
+        {
+            const std::size_t k = plain_level(plain);
+            if (!is_ntt_form)
+                throw std::invalid_argument("plain is not in NTT form"); // :963-966
+            if (k < 2)
+                throw std::invalid_argument("end of modulus switching chain reached"); // :967-970
+            mod_switch_to_inplace(plain, true, k - 1);
+        }
+        void mod_switch_to_next(const std::vector<std::uint64_t> &plain, bool is_ntt_form, std::vector<std::uint64_t> &destination)
+        {
+            destination = plain;
+            mod_switch_to_next_inplace(destination, is_ntt_form);
+        }
         // Ciphertext::is_transparent (ciphertext.h:471-476) evaluated on the device copy
         bool is_transparent(const CT &encrypted)
         {
@@ -638,6 +714,24 @@ namespace sealhip_host
                                                                            o.ptr()));
             a.resize_raw(so, k); // :131-132
             o.down(a.data(), so * k * n);
+        }
+        // is_valid_for(Plaintext) (valcheck.cpp:236-281) in coefficient form: at most N coefficients, each below t
+        // (plain_modulus 0 under CKKS: no non-empty coefficient-form plaintext is valid)
+        void check_plain(const std::uint64_t *plain, std::size_t coeff_count) const
+        {
+            if (coeff_count > ctx_.n())
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            for (std::size_t i = 0; i < coeff_count; i++)
+                if (plain[i] >= ctx_.plain_modulus())
+                    throw std::invalid_argument("plain is not valid for encryption parameters");
+        }
+        // level (number of primes) of an NTT-form plaintext: k*N words, 1 <= k <= n_key
+        std::size_t plain_level(const std::vector<std::uint64_t> &plain) const
+        {
+            const std::size_t n = ctx_.n(), k = plain.size() / n;
+            if (plain.size() % n != 0 || k < 1 || k > ctx_.n_key())
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            return k;
         }
         void check_pair(const CT &a, const CT &b) const
         {

@@ -121,6 +121,8 @@ SYMBOLS = {
     "sealhip_evaluator_sub": [_vp, _u32, _vp, _u32, _vp, _u32, _sz, _vp],
     "sealhip_evaluator_multiply_plain_ntt": [_vp, _u32, _vp, _u32, _sz, _vp, _sz],
     "sealhip_evaluator_multiply_plain": [_vp, _u32, _vp, _u32, _sz, _vp, _sz],
+    "sealhip_evaluator_transform_plain_to_ntt": [_vp, _u32, _vp, _sz, _sz, _sz, _vp],
+    "sealhip_evaluator_mod_switch_plain_to": [_vp, _u32, _vp, _sz, _u32, _vp],
     "sealhip_is_transparent": [_vp, _u32, _vp, _u32, _sz, _vp],
     "sealhip_transparency_sink": [_vp, _vp, _sz],
     "sealhip_debug_butterfly_rate": [_vp, _u32, _u32, _vp],
@@ -822,6 +824,17 @@ class Evaluator:
             ntt_form = self.ctx.scheme == SCHEME_CKKS
         fn = lib().sealhip_evaluator_multiply_plain_ntt if ntt_form else lib().sealhip_evaluator_multiply_plain
         _check(fn(self.ctx.handle, k, _ptr(ct), size, count, _ptr(plain), plain_stride))
+
+    def transform_plain_to_ntt(self, plain, coeff_count, k, count, plain_ntt, plain_stride=0):
+        """Evaluator::transform_to_ntt(Plaintext, parms_id) (evaluator.cpp:1648-1744), BFV: `count` plaintexts of coeff_count
+        coefficients < t (plain_stride words apart, 0 = coeff_count) -> plain_ntt[count][k][N] in NTT form at level k"""
+        _check(lib().sealhip_evaluator_transform_plain_to_ntt(self.ctx.handle, k, _ptr(plain), coeff_count, plain_stride, count,
+                                                               _ptr(plain_ntt)))
+
+    def mod_switch_plain_to(self, plain, k_from, count, k_to, out):
+        """Evaluator::mod_switch_to(Plaintext, parms_id) (evaluator.cpp:1062-1088): NTT-form plain[count][k_from][N] ->
+        out[count][k_to][N]"""
+        _check(lib().sealhip_evaluator_mod_switch_plain_to(self.ctx.handle, k_from, _ptr(plain), count, k_to, _ptr(out)))
 
     def add_plain_inplace(self, ct, size, k, count, plain, plain_stride=None, subtract=False):
         """Evaluator::add_plain_inplace / sub_plain_inplace (evaluator.cpp:1290-1435): BFV plain = N coefficients < t,

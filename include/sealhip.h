@@ -339,6 +339,21 @@ long sealhip_evaluator_multiply_plain_ntt(sealhip_context *ctx, uint32_t k, uint
    otherwise COR_E_INVALIDOPERATION. */
 long sealhip_evaluator_multiply_plain(sealhip_context *ctx, uint32_t k, uint64_t *ct, uint32_t size, size_t count,
                                       const uint64_t *plain, size_t plain_stride);
+/* Evaluator::transform_to_ntt(Plaintext, parms_id) (evaluator.cpp:1648-1744), BFV: plaintext i = plain_coeff_count
+   coefficients < t at plain + i * plain_stride (0 = plain_coeff_count); plain_ntt[count][k][N] receives it lifted to
+   level k and in NTT form. Coefficients >= t: unspecified words (as multiply_plain). Device memory. Every parameter set,
+   with or without fast plain lift: (v - t [v >= (t+1)/2]) mod q_i, the residue both reference branches compute. CKKS:
+   E_INVALIDARG for plain_coeff_count > 0 (plain_modulus 0, valcheck.cpp:266-279); an empty plaintext gives zero rows.
+   E_INVALIDARG also for plain_coeff_count > N, a nonzero stride below it, and plain overlapping plain_ntt. count 0 does
+   nothing. Runs on the calling thread's lane and synchronises nothing (capturable). */
+long sealhip_evaluator_transform_plain_to_ntt(sealhip_context *ctx, uint32_t k, const uint64_t *plain,
+                                              size_t plain_coeff_count, size_t plain_stride, size_t count,
+                                              uint64_t *plain_ntt);
+/* Evaluator::mod_switch_to(_inplace)(Plaintext, parms_id) / mod_switch_to_next (evaluator.cpp:959-994, 1062-1088):
+   NTT-form plain[count][k_from][N] -> out[count][k_to][N], the leading k_to rows of each (Plaintext::resize). E_INVALIDARG
+   "cannot switch to higher level modulus" for k_to > k_from, "end of modulus switching chain reached" for k_to < 1. */
+long sealhip_evaluator_mod_switch_plain_to(sealhip_context *ctx, uint32_t k_from, const uint64_t *plain, size_t count,
+                                           uint32_t k_to, uint64_t *out);
 /* Ciphertext::is_transparent (ciphertext.h:471-476) per ciphertext of the batch: transparent[i] = 1 when polynomials
    1.. are identically zero (or size < 2). `transparent` is HOST memory (count bytes); the call synchronises.
    The reference throws logic_error("result ciphertext is transparent") after every operation when built with
