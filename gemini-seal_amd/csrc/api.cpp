@@ -31,10 +31,10 @@ namespace sealhip
     std::size_t wire_save(Engine &e, const sealhip_ciphertext_info &ci, const u64 *src, void *bytes, std::size_t capacity);
     std::uint32_t wire_load_kswitch_key(Engine &e, const void *bytes, std::size_t len, std::uint32_t index, u64 **d_out,
                                         std::size_t *words_out, std::uint64_t *dim1_out);
-    std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots);
+    std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, bool seeded);
     std::vector<u64> wire_expand_seed(const Engine &e, int rows, const unsigned char *seed_bytes);
     std::size_t wire_save_kswitch_keys(Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, void *bytes,
-                                       std::size_t capacity);
+                                       std::size_t capacity, bool seeded);
 } // namespace sealhip
 
 struct sealhip_context
@@ -2230,10 +2230,120 @@ long sealhip_kswitch_keys_save(sealhip_context *ctx, const sealhip_kswitch_key *
             raw[i] = keys[i] ? &keys[i]->key : nullptr;
         if (!bytes) // size query
         {
-            *written = wire_kswitch_save_size(e, raw.data(), n_slots);
+            *written = wire_kswitch_save_size(e, raw.data(), n_slots, false);
             return;
         }
-        *written = wire_save_kswitch_keys(e, raw.data(), n_slots, bytes, capacity);
+        *written = wire_save_kswitch_keys(e, raw.data(), n_slots, bytes, capacity, false);
+    });
+}
+
+/* ---------------------------------------------------------------- KeyGenerator (keygenerator.cpp:146-240, :325-369) */
+// elts == nullptr: relin keys sk^2 .. sk^(n_keys+1); otherwise the Galois keys of elts. Every check runs on the host before
+// any device work (so host-only contexts report them too); on any failure every keys[i] stays NULL.
+static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const uint32_t *elts, bool galois, size_t n_keys,
+                          const uint64_t *seeds_host, const int32_t *noise, int32_t keep_seeds, sealhip_kswitch_key **keys)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(sk_ntt);
+    if (n_keys)
+    {
+        if (galois)
+            REQUIRE_PTR(elts);
+        REQUIRE_PTR(seeds_host);
+        REQUIRE_PTR(noise);
+        REQUIRE_PTR(keys);
+        std::fill(keys, keys + n_keys, nullptr);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (galois)
+        {
+            std::vector<uint32_t> seen(elts, elts + n_keys);
+            for (uint32_t elt : seen)
+                if (!(elt & 1) || elt >= 2 * h.n)
+                    throw std::invalid_argument("Galois element is not valid"); // keygenerator.cpp:213-216
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+                throw std::invalid_argument("Galois elements must be distinct (one key per element)");
+            if (h.scheme == 1 && h.plain_prime < 0) // CKKS always batches (context.cpp:351-352)
+                throw std::logic_error("encryption parameters do not support batching"); // :198-201
+        }
+        else if (n_keys > 14) // SEAL_CIPHERTEXT_SIZE_MAX - 2, :152-155
+            throw std::invalid_argument("invalid count");
+        // (using_keyswitching, :327-330, holds for every context: sealhip_context_create refuses a single prime)
+        Engine &e = device_engine(ctx);
+        if (n_keys == 0)
+            return;
+        if (e.lane().capturing)
+            throw std::logic_error("key generation allocates and synchronises: it cannot be captured in a graph");
+        const uint32_t digits = static_cast<uint32_t>((e.k_first + e.nsp - 1) / e.nsp);
+        const std::size_t words = static_cast<std::size_t>(digits) * 2 * e.n_key * e.n;
+        std::vector<std::unique_ptr<sealhip_kswitch_key>> made(n_keys);
+        std::vector<u64 *> data(n_keys, nullptr);
+        auto release = [&] {
+            for (auto &k : made)
+                if (k && k->key.d_data)
+                    (void)hipFree(k->key.d_data);
+        };
+        try
+        {
+            for (size_t i = 0; i < n_keys; i++)
+            {
+                made[i] = std::make_unique<sealhip_kswitch_key>();
+                made[i]->key.n_digits = digits;
+                made[i]->key.words = words;
+                SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&made[i]->key.d_data), words * sizeof(u64)));
+                data[i] = made[i]->key.d_data;
+                // (save_seed is dropped below n_key x N = 9 words, rlwe.cpp:225-230: every context has at least 2 x 8)
+                if (keep_seeds)
+                    made[i]->key.seeds.assign(seeds_host + i * digits * 8, seeds_host + (i + 1) * digits * 8);
+            }
+            op_generate_kswitch_keys(e, reinterpret_cast<const u64 *>(sk_ntt), galois ? elts : nullptr, n_keys, seeds_host,
+                                     noise, data.data());
+            e.sync_and_check();
+        }
+        catch (...)
+        {
+            (void)hipStreamSynchronize(e.lane().stream); // nothing may still write into a buffer that is freed
+            release();
+            throw;
+        }
+        for (size_t i = 0; i < n_keys; i++)
+            keys[i] = made[i].release();
+    });
+}
+
+long sealhip_generate_relin_keys(sealhip_context *ctx, const uint64_t *sk_ntt, uint32_t count, const uint64_t *seeds_host,
+                                 const int32_t *noise, int32_t keep_seeds, sealhip_kswitch_key **keys)
+{
+    return generate_keys(ctx, sk_ntt, nullptr, false, count, seeds_host, noise, keep_seeds, keys);
+}
+
+long sealhip_generate_galois_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const uint32_t *galois_elts, uint32_t n_elts,
+                                  const uint64_t *seeds_host, const int32_t *noise, int32_t keep_seeds,
+                                  sealhip_kswitch_key **keys)
+{
+    return generate_keys(ctx, sk_ntt, galois_elts, true, n_elts, seeds_host, noise, keep_seeds, keys);
+}
+
+long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots,
+                                      void *bytes, size_t capacity, size_t *written)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(written);
+    if (n_slots)
+        REQUIRE_PTR(keys);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        std::vector<const KSwitchKey *> raw(n_slots, nullptr);
+        for (uint32_t i = 0; i < n_slots; i++)
+            raw[i] = keys[i] ? &keys[i]->key : nullptr;
+        if (!bytes) // size query
+        {
+            *written = wire_kswitch_save_size(e, raw.data(), n_slots, true);
+            return;
+        }
+        *written = wire_save_kswitch_keys(e, raw.data(), n_slots, bytes, capacity, true);
     });
 }
 

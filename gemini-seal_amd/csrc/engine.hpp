@@ -214,6 +214,9 @@ namespace sealhip
         u64 *d_data = nullptr;
         std::uint32_t n_digits = 0;
         std::size_t words = 0;
+        // keys made with save_seed (sealhip_generate_*_keys): the seed of c_1 of every digit, 8 words each (host memory);
+        // empty otherwise. What the seeded save writes in place of c_1 (ciphertext.cpp:189-208).
+        std::vector<std::uint64_t> seeds;
     };
 
     // Optional per-launch timing with HIP events on the launch stream (bench.py's roofline line).
@@ -655,6 +658,24 @@ namespace sealhip
         u64 *dst;                  // device
     };
     void op_expand_seeds(Engine &e, int rows, const SeedJob *jobs, std::size_t count);
+
+    // ---- KeyGenerator::generate_one_kswitch_key for a batch of keys (keygen.hip, composition in pipeline.cpp) ----
+    constexpr int kKeygenMaxKeys = 32; // keys per assemble launch (kernel-argument table)
+    struct KeygenArgs
+    {
+        u64 *key[kKeygenMaxKeys];         // digits x 2 x n_key x N each
+        const u64 *s_new[kKeygenMaxKeys]; // new key source, n_key rows of N (NTT form): sk (Galois) or a power of sk (relin)
+        std::uint32_t elt[kKeygenMaxKeys]; // s_new is read through the NTT-form Galois permutation of elt (1: identity)
+        const u64 *sk;                     // n_key x N, NTT form
+        u64 factor[kMaxModuli];            // prod of the special primes mod q_r, r < n_ct (keygenerator.cpp:355-359)
+        int n_keys, digits, n_key, nsp, n_ct;
+    };
+    hipError_t launch_keygen_assemble(const Engine &e, const KeygenArgs &a);
+    // Key i (key_data[i]: digits x 2 x n_key x N words of device memory) for the new key apply_galois_ntt(sk, elts[i]), or,
+    // with elts == nullptr, sk^(i+2) (relin_keys, keygenerator.cpp:146-175). seeds_host: n_keys x digits x 8 words (the
+    // seeds of c_1), noise: n_keys x digits x N small signed samples (device). Stream-ordered on the calling thread's lane.
+    void op_generate_kswitch_keys(Engine &e, const u64 *sk_ntt, const std::uint32_t *elts, std::size_t n_keys,
+                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data);
     // items of `bytes_per_item` arena bytes per chunk of a batch of `count` (pipeline.cpp; logged in Lane::chunk_log)
     std::size_t ws_plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers);
 

@@ -908,6 +908,81 @@ namespace sealhip
         }
     }
 
+    // KeyGenerator::generate_one_kswitch_key (keygenerator.cpp:325-369) for every key of the batch, in the key buffers:
+    //   1. c0 of every digit = NTT(lift(e_j)) over all key rows: the lift stage and the forward transform of
+    //      encrypt_zero_symmetric (rlwe.cpp:266-278) with the key's digit stride 2 x n_key x N;
+    //   2. c1 of every digit = sample_poly_uniform(BlakePRNG(seed_j)) (rlwe.cpp:245-249): one seed-expansion job list;
+    //   3. kswitch_keygen_assemble: c0 = -(c0 + c1 (.) s), plus factor_r * new_key[r] on the digit's rows (:350-366).
+    // The new key is read through the Galois permutation inside the kernel (no rotated secret key is stored); the relin
+    // keys' powers sk^2.. are built once by dyadic products (compute_secret_key_array, :262-323).
+    void op_generate_kswitch_keys(Engine &e, const u64 *sk_ntt, const std::uint32_t *elts, std::size_t n_keys,
+                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data)
+    {
+        if (n_keys == 0)
+            return;
+        const int nk = e.n_key;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(nk) * N, digit_words = 2 * poly;
+        const int digits = (e.k_first + e.nsp - 1) / e.nsp;
+        RlweArgs a{};
+        a.ct_item_stride = digit_words;
+        a.ct_poly_stride = poly;
+        a.polys = 1;
+        a.rows = nk;
+        a.e_item_stride = N;
+        const RowMap c0_rows = ct_row_map(nk, 2, 0);
+        for (std::size_t i = 0; i < n_keys; i++)
+        {
+            a.ct = key_data[i];
+            a.e = noise + i * digits * N;
+            check(launch_rlwe_stage(e, 0, a, digits), "lift(e)");
+            check(launch_ntt(e, key_data[i], static_cast<std::size_t>(digits) * 2 * nk, c0_rows, false, kNttCanonical),
+                  "ntt(e)");
+        }
+        std::vector<SeedJob> jobs(n_keys * digits);
+        for (std::size_t i = 0; i < n_keys; i++)
+            for (int j = 0; j < digits; j++)
+                jobs[i * digits + j] = SeedJob{ seeds_host + 8 * (i * digits + j), key_data[i] + j * digit_words + poly };
+        op_expand_seeds(e, nk, jobs.data(), jobs.size());
+
+        hipError_t err = hipSuccess;
+        u64 *powers = nullptr; // relin keys: sk^2 .. sk^(n_keys+1), in the lane's arena (free again once expansion is enqueued)
+        if (!elts)
+        {
+            e.ws_reset();
+            e.ws_reserve(e.lane().ws_floor + n_keys * poly * sizeof(u64) + 256);
+            powers = e.ws_alloc(n_keys * poly);
+            const RowMap rows = ct_row_map(nk, 1, -1);
+            for (std::size_t i = 0; i < n_keys && err == hipSuccess; i++)
+                err = launch_poly_op(e, PolyOp::Dyadic, i ? powers + (i - 1) * poly : sk_ntt, sk_ntt, 0, powers + i * poly, nk,
+                                     rows);
+        }
+        KeygenArgs g{};
+        g.sk = sk_ntt;
+        g.digits = digits;
+        g.n_key = nk;
+        g.nsp = e.nsp;
+        g.n_ct = e.k_first;
+        for (int r = 0; r < e.k_first; r++)
+        {
+            u64 f = 1;
+            for (int k = 0; k < e.nsp; k++)
+                f = mulmod(f, e.key_moduli[e.k_first + k], e.key_moduli[r]); // multiply_uint_mod, keygenerator.cpp:355-359
+            g.factor[r] = f;
+        }
+        for (std::size_t off = 0; off < n_keys && err == hipSuccess; off += kKeygenMaxKeys)
+        {
+            g.n_keys = static_cast<int>(std::min<std::size_t>(kKeygenMaxKeys, n_keys - off));
+            for (int i = 0; i < g.n_keys; i++)
+            {
+                g.key[i] = key_data[off + i];
+                g.s_new[i] = elts ? sk_ntt : powers + (off + i) * poly;
+                g.elt[i] = elts ? elts[off + i] : 1u;
+            }
+            err = launch_keygen_assemble(e, g);
+        }
+        check(err, "kswitch_keygen_assemble");
+    }
+
     void op_encrypt_zero_asymmetric(Engine &e, int rows, bool is_ntt_form, const u64 *pk, const std::int32_t *u,
                                     const std::int32_t *noise, std::size_t count, u64 *ct)
     {

@@ -284,16 +284,32 @@ namespace sealhip
     // KSwitchKeys::save (kswitchkeys.cpp:43-85 inside Serialization::Save): outer header, parms_id, keys_dim1, then per slot
     // keys_dim2 and that many PublicKey = Ciphertext streams (size 2, key level, NTT form, scale 1.0), whose words are copied
     // straight from the resident K1 buffer. keys[i] == nullptr: an unused slot (keys_dim2 = 0), as GaloisKeys has.
-    std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots)
+    // seeded: the Serializable<> form of keys generated with save_seed -- every digit is written the way Ciphertext::save_members
+    // writes a ciphertext with the seed marker (ciphertext.cpp:189-208): metadata of size 2, the words of c_0 only, then
+    // the 64-byte seed of c_1.
+    namespace
+    {
+        std::size_t digit_save_size(const Engine &e, bool seeded)
+        {
+            const auto nk = static_cast<std::uint32_t>(e.n_key);
+            return seeded ? wire_save_size(1, nk, e.n) + kSeedBytes : wire_save_size(2, nk, e.n);
+        }
+    } // namespace
+
+    std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, bool seeded)
     {
         std::size_t total = sizeof(Header) + 32 + 8;
         for (std::size_t i = 0; i < n_slots; i++)
-            total += 8 + (keys[i] ? keys[i]->n_digits * wire_save_size(2, static_cast<std::uint32_t>(e.n_key), e.n) : 0);
+        {
+            if (seeded && keys[i] && keys[i]->seeds.size() != static_cast<std::size_t>(keys[i]->n_digits) * 8)
+                throw std::invalid_argument("key " + std::to_string(i) + " carries no seeds (generate it with keep_seeds)");
+            total += 8 + (keys[i] ? keys[i]->n_digits * digit_save_size(e, seeded) : 0);
+        }
         return total;
     }
 
     std::size_t wire_save_kswitch_keys(Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, void *bytes,
-                                       std::size_t capacity)
+                                       std::size_t capacity, bool seeded)
     {
         std::array<std::uint64_t, 4> pid{};
         {
@@ -303,7 +319,7 @@ namespace sealhip
                 throw std::logic_error("the key level's parms_id is not registered (sealhip_context_set_parms_id)");
             pid = it->second;
         }
-        const std::size_t total = wire_kswitch_save_size(e, keys, n_slots);
+        const std::size_t total = wire_kswitch_save_size(e, keys, n_slots, seeded);
         if (capacity < total)
             throw std::invalid_argument("destination buffer is too small");
         const std::size_t digit_words = static_cast<std::size_t>(2) * e.n_key * e.n;
@@ -325,7 +341,8 @@ namespace sealhip
             {
                 if (keys[i]->words != dim2 * digit_words)
                     throw std::logic_error("kswitch_keys is not valid for encryption parameters");
-                const std::size_t ct_total = wire_save_size(2, static_cast<std::uint32_t>(e.n_key), e.n);
+                const std::size_t ct_total = digit_save_size(e, seeded);
+                const std::size_t stored_words = seeded ? digit_words / 2 : digit_words;
                 const Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, ct_total };
                 std::memcpy(p, &h, sizeof(h));
                 p += sizeof(h);
@@ -338,15 +355,20 @@ namespace sealhip
                 std::memcpy(p + 16, &k64, 8);
                 std::memcpy(p + 24, &one, 8);
                 p += 32;
-                const Header inner{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, sizeof(Header) + 8 + digit_words * 8 };
+                const Header inner{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, sizeof(Header) + 8 + stored_words * 8 };
                 std::memcpy(p, &inner, sizeof(inner));
                 p += sizeof(inner);
-                const std::uint64_t count = digit_words;
+                const std::uint64_t count = stored_words;
                 std::memcpy(p, &count, 8);
                 p += 8;
-                SEALHIP_CHECK(hipMemcpyAsync(p, keys[i]->d_data + j * digit_words, digit_words * 8, hipMemcpyDeviceToHost,
+                SEALHIP_CHECK(hipMemcpyAsync(p, keys[i]->d_data + j * digit_words, stored_words * 8, hipMemcpyDeviceToHost,
                                              e.lane().stream));
-                p += digit_words * 8;
+                p += stored_words * 8;
+                if (seeded)
+                {
+                    std::memcpy(p, keys[i]->seeds.data() + 8 * j, kSeedBytes);
+                    p += kSeedBytes;
+                }
             }
         }
         e.sync_and_check();

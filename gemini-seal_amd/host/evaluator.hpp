@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -138,6 +139,7 @@ namespace sealhip_host
             if (key_)
                 sealhip_kswitch_key_destroy(c_.get(), key_);
         }
+        KSwitchKeys(const Context &c, sealhip_kswitch_key *adopt) : c_(c), key_(adopt) {} // a handle the ABI made
         KSwitchKeys(const KSwitchKeys &) = delete;
         const sealhip_kswitch_key *get() const { return key_; }
 
@@ -762,5 +764,136 @@ namespace sealhip_host
             c.down(ct.data(), size * k * n);
         }
         const Context &ctx_;
+    };
+
+    // KeyGenerator (keygenerator.h / keygenerator.cpp:105-240) over a context and a secret key in NTT form (n_key x N words,
+    // host). Sampling stays with the caller: `sampler(seed, noise)` is asked once per encrypt_zero_symmetric, in the
+    // reference's order (key by key, digit by digit), for the 8-word BlakePRNGFactory().create() seed of c_1 and the N
+    // signed values of sample_poly_normal. The keys are made on the device (sealhip_generate_*_keys).
+    class KeyGenerator
+    {
+    public:
+        using Sampler = std::function<void(std::uint64_t *seed, std::int32_t *noise)>;
+        using Keys = std::vector<std::unique_ptr<KSwitchKeys>>;
+        using GaloisKeys = std::map<std::uint32_t, std::unique_ptr<KSwitchKeys>>; // galois_elt -> key (GaloisKeys::get_index)
+
+        KeyGenerator(const Context &context, const std::uint64_t *secret_key_ntt, Sampler sampler)
+            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n()), sampler_(std::move(sampler))
+        {}
+
+        // relin_keys(count, save_seed) (:146-175): keys[i] is the key of sk^(i+2) (RelinKeys::get_index(i + 2) = i)
+        Keys relin_keys(std::size_t count, bool save_seed = false)
+        {
+            if (!count || count > 14) // SEAL_CIPHERTEXT_SIZE_MAX - 2
+                throw std::invalid_argument("invalid count");
+            return generate(nullptr, count, save_seed);
+        }
+
+        // galois_keys(galois_elts, save_seed) (:177-240): invalid elements throw before any sample is drawn; an element that
+        // is already present is skipped and draws no samples (has_key)
+        GaloisKeys galois_keys(const std::vector<std::uint32_t> &galois_elts, bool save_seed = false)
+        {
+            std::int32_t batching = 0;
+            throw_on(sealhip_context_using_batching(ctx_.get(), &batching));
+            if (!batching && ctx_.scheme() == SEALHIP_SCHEME_BFV)
+                throw std::logic_error("encryption parameters do not support batching");
+            std::vector<std::uint32_t> elts;
+            for (std::uint32_t elt : galois_elts)
+            {
+                if (!(elt & 1) || elt >= 2 * ctx_.n())
+                    throw std::invalid_argument("Galois element is not valid");
+                if (std::find(elts.begin(), elts.end(), elt) == elts.end())
+                    elts.push_back(elt);
+            }
+            Keys made = generate(elts.data(), elts.size(), save_seed);
+            GaloisKeys out;
+            for (std::size_t i = 0; i < elts.size(); i++)
+                out.emplace(elts[i], std::move(made[i]));
+            return out;
+        }
+        // galois_keys(steps) (keygenerator.h:180-208): GaloisTool::get_elts_from_steps
+        GaloisKeys galois_keys(const std::vector<int> &steps, bool save_seed = false)
+        {
+            std::vector<std::uint32_t> elts;
+            for (int step : steps)
+            {
+                std::uint32_t elt = 0;
+                throw_on(sealhip_galois_elt_from_step(ctx_.get(), step, &elt));
+                elts.push_back(elt);
+            }
+            return galois_keys(elts, save_seed);
+        }
+        // galois_keys() (keygenerator.h:224-247): GaloisTool::get_elts_all (galois.cpp:102-127), in its order
+        GaloisKeys galois_keys(bool save_seed = false) { return galois_keys(elts_all(), save_seed); }
+
+        // generate_pk (keygenerator.cpp:105-136): encrypt_zero_symmetric at the key level in NTT form, no seed kept; returns
+        // the 2 x n_key x N words of the public key
+        std::vector<std::uint64_t> public_key()
+        {
+            const std::size_t n = ctx_.n(), nk = ctx_.n_key();
+            std::uint64_t seed[8];
+            std::vector<std::int32_t> noise(n);
+            sampler_(seed, noise.data());
+            Staged sk(ctx_, nk * n), a(ctx_, nk * n), e(ctx_, (n + 1) / 2), ct(ctx_, 2 * nk * n);
+            sk.up(sk_.data(), nk * n);
+            throw_on(sealhip_memcpy_h2d(ctx_.get(), e.ptr(), noise.data(), n * sizeof(std::int32_t)));
+            throw_on(sealhip_expand_seed(ctx_.get(), std::uint32_t(nk), seed, 1, a.ptr(), 0));
+            throw_on(sealhip_encrypt_zero_symmetric(ctx_.get(), std::uint32_t(nk), 1, a.ptr(),
+                                                    reinterpret_cast<const std::int32_t *>(e.ptr()), sk.ptr(), 1, ct.ptr()));
+            std::vector<std::uint64_t> pk(2 * nk * n);
+            ct.down(pk.data(), pk.size());
+            return pk;
+        }
+
+        std::vector<std::uint32_t> elts_all() const
+        {
+            const std::uint64_t m = 2 * static_cast<std::uint64_t>(ctx_.n());
+            std::uint64_t pos = 5, neg = 1; // neg = 5^-1 mod m = 5^(N/2 - 1): the order of 5 is N/2
+            for (std::size_t i = 0; i + 1 < ctx_.n() / 2; i++)
+                neg = (neg * 5) & (m - 1);
+            std::vector<std::uint32_t> out{ static_cast<std::uint32_t>(m - 1) };
+            for (std::size_t i = 0; (std::size_t(2) << i) < ctx_.n(); i++) // coeff_count_power - 1 rounds
+            {
+                out.push_back(static_cast<std::uint32_t>(pos));
+                pos = (pos * pos) & (m - 1);
+                out.push_back(static_cast<std::uint32_t>(neg));
+                neg = (neg * neg) & (m - 1);
+            }
+            return out;
+        }
+
+    private:
+        Keys generate(const std::uint32_t *elts, std::size_t n_keys, bool save_seed)
+        {
+            Keys out;
+            if (!n_keys)
+                return out;
+            std::uint32_t k_first = 0, digits = 0;
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
+            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), d = digits, items = n_keys * d;
+            std::vector<std::uint64_t> seeds(items * 8);
+            std::vector<std::int32_t> noise(items * n);
+            for (std::size_t i = 0; i < items; i++)
+                sampler_(seeds.data() + 8 * i, noise.data() + n * i);
+            Staged sk(ctx_, nk * n), e(ctx_, (items * n + 1) / 2);
+            sk.up(sk_.data(), nk * n);
+            throw_on(sealhip_memcpy_h2d(ctx_.get(), e.ptr(), noise.data(), noise.size() * sizeof(std::int32_t)));
+            std::vector<sealhip_kswitch_key *> raw(n_keys, nullptr);
+            const auto *en = reinterpret_cast<const std::int32_t *>(e.ptr());
+            if (elts)
+                throw_on(sealhip_generate_galois_keys(ctx_.get(), sk.ptr(), elts, std::uint32_t(n_keys), seeds.data(), en,
+                                                      save_seed ? 1 : 0, raw.data()));
+            else
+                throw_on(sealhip_generate_relin_keys(ctx_.get(), sk.ptr(), std::uint32_t(n_keys), seeds.data(), en,
+                                                     save_seed ? 1 : 0, raw.data()));
+            for (auto *h : raw)
+                out.push_back(std::make_unique<KSwitchKeys>(ctx_, h));
+            return out;
+        }
+
+        const Context &ctx_;
+        std::vector<std::uint64_t> sk_;
+        Sampler sampler_;
     };
 } // namespace sealhip_host

@@ -156,6 +156,9 @@ SYMBOLS = {
     "sealhip_host_unregister": [_vp, _vp],
     "sealhip_debug_blake2xb": [_vp, _sz, _vp, _sz, _vp, _sz],
     "sealhip_kswitch_keys_save": [_vp, C.POINTER(_vp), _u32, _vp, _sz, C.POINTER(_sz)],
+    "sealhip_kswitch_keys_save_seeded": [_vp, C.POINTER(_vp), _u32, _vp, _sz, C.POINTER(_sz)],
+    "sealhip_generate_relin_keys": [_vp, _vp, _u32, _vp, _vp, _i32, C.POINTER(_vp)],
+    "sealhip_generate_galois_keys": [_vp, _vp, _vp, _u32, _vp, _vp, _i32, C.POINTER(_vp)],
     "sealhip_graph_capture_begin": [_vp],
     "sealhip_graph_capture_end": [_vp, C.POINTER(_vp)],
     "sealhip_graph_launch": [_vp, _vp],
@@ -296,6 +299,12 @@ class KSwitchKeys:
         self.ctx, self.handle, self.n_slots = ctx, h.value, slots.value
         return self
 
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        self = cls.__new__(cls)
+        self.ctx, self.handle = ctx, handle
+        return self
+
     def __del__(self):
         try:
             if self.handle:
@@ -312,16 +321,23 @@ def blake2xb(outlen, data, key=b""):
     return out.raw
 
 
-def save_kswitch_keys(ctx, keys):
+def save_kswitch_keys(ctx, keys, seeded=False):
     """KSwitchKeys::save (kswitchkeys.cpp:43-85): keys = list of KSwitchKeys or None (unused slot) -> the reference's byte
-    stream, digit words copied straight from HBM"""
+    stream, digit words copied straight from HBM. seeded: the Serializable<> form (sealhip_kswitch_keys_save_seeded: c_0
+    and the seed of c_1 per digit) of keys generated with keep_seeds"""
+    fn = lib().sealhip_kswitch_keys_save_seeded if seeded else lib().sealhip_kswitch_keys_save
     arr = (C.c_void_p * max(1, len(keys)))(*[(k.handle if k is not None else None) for k in keys])
     need = _sz(0)
-    _check(lib().sealhip_kswitch_keys_save(ctx.handle, arr, len(keys), None, 0, C.byref(need)))
+    _check(fn(ctx.handle, arr, len(keys), None, 0, C.byref(need)))
     buf = (C.c_char * need.value)()
     written = _sz(0)
-    _check(lib().sealhip_kswitch_keys_save(ctx.handle, arr, len(keys), C.addressof(buf), need.value, C.byref(written)))
+    _check(fn(ctx.handle, arr, len(keys), C.addressof(buf), need.value, C.byref(written)))
     return bytes(buf[: written.value])
+
+
+def save_kswitch_keys_seeded(ctx, keys):
+    """Serializable<RelinKeys / GaloisKeys>::save of generated keys (sealhip_kswitch_keys_save_seeded)"""
+    return save_kswitch_keys(ctx, keys, seeded=True)
 
 
 class Graph:
@@ -573,6 +589,27 @@ class Context:
         (0: rows x N) receives the rows x N words of c_1 for seed i"""
         seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
         _check(lib().sealhip_expand_seed(self.handle, rows, seeds.ctypes.data, seeds.shape[0], _ptr(out), item_stride))
+
+    # ---- KeyGenerator (keygenerator.cpp:146-240, :325-369) with the samples handed in
+    def generate_relin_keys(self, sk_ntt, count, seeds, noise, keep_seeds=False):
+        """KeyGenerator::relin_keys(count, save_seed): keys for sk^2 .. sk^(count+1). sk_ntt: n_key x N (device); seeds:
+        count x d x 8 words (host); noise: count x d x N int32 (device, e.g. upload_i32). Returns count KSwitchKeys."""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        out = (C.c_void_p * max(1, count))()
+        _check(lib().sealhip_generate_relin_keys(self.handle, _ptr(sk_ntt), count, seeds.ctypes.data if seeds.size else None,
+                                                 _ptr(noise) if noise is not None else None, 1 if keep_seeds else 0, out))
+        return [KSwitchKeys._adopt(self, out[i]) for i in range(count)]
+
+    def generate_galois_keys(self, sk_ntt, galois_elts, seeds, noise, keep_seeds=False):
+        """KeyGenerator::galois_keys(galois_elts, save_seed) without the duplicate skipping (distinct elements only): key i is
+        for apply_galois_ntt(sk, galois_elts[i]). Layouts as generate_relin_keys. Returns one KSwitchKeys per element."""
+        elts = np.ascontiguousarray(np.asarray(galois_elts, dtype=np.uint32).reshape(-1))
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        out = (C.c_void_p * max(1, elts.size))()
+        _check(lib().sealhip_generate_galois_keys(self.handle, _ptr(sk_ntt), elts.ctypes.data if elts.size else None, elts.size,
+                                                  seeds.ctypes.data if seeds.size else None,
+                                                  _ptr(noise) if noise is not None else None, 1 if keep_seeds else 0, out))
+        return [KSwitchKeys._adopt(self, out[i]) for i in range(elts.size)]
 
     def debug_seed_slack(self, extra):
         """candidates provisioned per seed beyond rows x N on this thread's lane (< 0: the default; sealhip_debug_seed_slack)"""

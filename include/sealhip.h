@@ -536,6 +536,38 @@ long sealhip_debug_seed_slack(sealhip_context *ctx, int64_t extra_candidates_per
    sealhip_kswitch_key_load_stream and is what the reference's KSwitchKeys::load reads. */
 long sealhip_kswitch_keys_save(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots, void *bytes,
                                size_t capacity, size_t *written);
+/* ---------------------------------------------------------------- KeyGenerator (keygenerator.cpp:146-240, :325-398) */
+/* KeyGenerator::relin_keys(count, save_seed) (keygenerator.cpp:146-175) and galois_keys(galois_elts, save_seed) (:177-240)
+   with the random samples handed in: keys[i] receives an ordinary key-switch key handle (usable by relinearize, apply_galois,
+   rotate_vector, the saves and sealhip_kswitch_key_destroy, like a loaded one) whose digits are generate_one_kswitch_key
+   (:325-369) for the new key sk^(i+2) (relin; slot index i) or apply_galois_ntt(sk, galois_elts[i]) (Galois; slot index
+   (elt - 1) / 2). For digit j < d = ceil(n_ct / nsp):
+     c1 = sample_poly_uniform(BlakePRNG(seed_j)) over the n_key key primes, taken as NTT form (util/rlwe.cpp:245-249),
+     c0 = -(NTT(e_j) + c1 * sk) (:266-284), and c0[r] += (prod of the special primes mod q_r) * new_key[r] for r in
+     [j*nsp, min((j+1)*nsp, n_ct)) (keygenerator.cpp:350-366).
+   sk_ntt: n_key x N, NTT form (device). seeds_host: n_keys x d x 8 words (random_seed_type, BlakePRNGFactory().create()'s
+   seed; host). noise: n_keys x d x N int32 (sample_poly_normal's signed values; device). Every word equals the reference's
+   given the same samples. keep_seeds: save_seed -- the handle keeps the d seeds (host memory) for
+   sealhip_kswitch_keys_save_seeded (the reference drops save_seed below n_key x N = 9 words, rlwe.cpp:225-230, which no
+   context reaches: n_key >= 2, N >= 8).
+   Checks before any device work (also on host-only contexts): null pointers -> E_POINTER; an even element, one >= 2N or a
+   repeated one -> E_INVALIDARG ("Galois element is not valid"); count > 14 -> E_INVALIDARG ("invalid count"); parameters
+   without batching (Galois keys) -> COR_E_INVALIDOPERATION. Every context uses key switching (sealhip_context_create
+   refuses a single prime). count / n_elts = 0 -> S_OK, nothing launched (on a device context). On any error every keys[i] is NULL and nothing
+   leaks. Runs on the calling thread's lane and synchronises once, at the end; not capturable. Creating keys does not
+   make captured graphs stale (sealhip_kswitch_key_load does not either); destroying them does. */
+long sealhip_generate_relin_keys(sealhip_context *ctx, const uint64_t *sk_ntt, uint32_t count, const uint64_t *seeds_host,
+                                 const int32_t *noise, int32_t keep_seeds, sealhip_kswitch_key **keys);
+long sealhip_generate_galois_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const uint32_t *galois_elts, uint32_t n_elts,
+                                  const uint64_t *seeds_host, const int32_t *noise, int32_t keep_seeds,
+                                  sealhip_kswitch_key **keys);
+/* Serializable<RelinKeys / GaloisKeys>::save (KSwitchKeys::save with seeded digits): sealhip_kswitch_keys_save's stream,
+   but every digit is written as Ciphertext::save_members writes a ciphertext with the seed marker (ciphertext.cpp:189-208):
+   metadata of size 2, the words of c0 only, then the 64-byte seed of c1. Every non-NULL key must carry seeds (made with
+   keep_seeds), else E_INVALIDARG. bytes == NULL: size query. Round-trips through sealhip_kswitch_key_load_stream, which
+   expands the seeds on the device. */
+long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots,
+                                      void *bytes, size_t capacity, size_t *written);
 /* is_data_valid_for (valcheck.cpp:284-317) on device-resident ciphertexts: valid[i] = 1 iff every coefficient of
    ciphertext i is below its row's prime (what an ingesting service checks before evaluating untrusted input). */
 long sealhip_is_data_valid_for(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,
