@@ -1714,6 +1714,57 @@ long sealhip_decrypt_scale_and_round(sealhip_context *ctx, uint32_t k, const uin
     });
 }
 
+namespace
+{
+    // Decryptor's checks (decryptor.cpp:53-57, :271-285) before any device work, also on host-only contexts
+    void check_decrypt_args(const Engine &e, uint32_t k, uint32_t size)
+    {
+        check_level(e, k);
+        if (size < 2 || size > 16) // SEAL_CIPHERTEXT_SIZE_MIN / _MAX (ciphertext.h:474)
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+    }
+} // namespace
+
+long sealhip_decryptor_invariant_noise_budget(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
+                                              size_t count, const uint64_t *sk_powers_ntt, int32_t *budgets)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(sk_powers_ntt);
+    REQUIRE_PTR(budgets);
+    return guarded([&] {
+        check_decrypt_args(*ctx->engine, k, size);
+        if (ctx->engine->scheme != SEALHIP_SCHEME_BFV)
+            throw std::logic_error("unsupported scheme"); // :276-279
+        Engine &e = device_engine(ctx);
+        if (count == 0)
+            return;
+        op_invariant_noise_budget(e, static_cast<int>(k), reinterpret_cast<const u64 *>(ct), static_cast<int>(size), count,
+                                  reinterpret_cast<const u64 *>(sk_powers_ntt), budgets);
+    });
+}
+
+long sealhip_decryptor_decrypt(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,
+                               const uint64_t *sk_powers_ntt, int32_t is_ntt_form, uint64_t *plain)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(sk_powers_ntt);
+    REQUIRE_PTR(plain);
+    return guarded([&] {
+        check_decrypt_args(*ctx->engine, k, size);
+        if (ctx->engine->scheme == SEALHIP_SCHEME_BFV && is_ntt_form)
+            throw std::invalid_argument("encrypted cannot be in NTT form"); // :79-82
+        if (ctx->engine->scheme == SEALHIP_SCHEME_CKKS && !is_ntt_form)
+            throw std::invalid_argument("encrypted must be in NTT form"); // :124-127
+        Engine &e = device_engine(ctx);
+        if (count == 0)
+            return;
+        op_decrypt(e, static_cast<int>(k), reinterpret_cast<const u64 *>(ct), static_cast<int>(size), count,
+                   reinterpret_cast<const u64 *>(sk_powers_ntt), reinterpret_cast<u64 *>(plain));
+    });
+}
+
 /* ------------------------------------------------------------------ HIP graphs */
 
 long sealhip_graph_capture_begin(sealhip_context *ctx)

@@ -382,6 +382,8 @@ namespace sealhip
             (void)hipFree(d_ckks_inv_roots);
         for (auto &kv : ckks_decode)
             (void)hipFree(kv.second);
+        for (auto &kv : noise_budget)
+            (void)hipFree(kv.second);
     }
 
     LevelTools &Engine::level_host(int k)
@@ -804,6 +806,44 @@ namespace sealhip
             }
             return q;
         }
+
+        // RNSBase of the first k moduli (rns.cpp:237-290) as compose_array uses it: q, upper_half_threshold (q + 1) >> 1,
+        // the limbs of q / q_i (row i at i * stride) and (q / q_i)^{-1} mod q_i
+        void crt_compose_consts(const std::vector<u64> &moduli, int k, int stride, u64 *q_out, u64 *half, u64 *punct,
+                                u64 *inv_punct)
+        {
+            const std::vector<u64> q = big_product(moduli, k);
+            u128 carry = 1;
+            std::vector<u64> plus(static_cast<std::size_t>(k) + 1, 0);
+            for (int l = 0; l < k; l++)
+            {
+                carry += q[l];
+                plus[l] = static_cast<u64>(carry);
+                carry >>= 64;
+            }
+            plus[k] = static_cast<u64>(carry);
+            for (int l = 0; l < k; l++)
+            {
+                q_out[l] = q[l];
+                half[l] = (plus[l] >> 1) | (plus[l + 1] << 63);
+            }
+            for (int i = 0; i < k; i++)
+            {
+                const u64 qi = moduli[i];
+                u128 rem = 0;
+                for (int l = k; l-- > 0;) // q / q_i
+                {
+                    const u128 cur = (rem << 64) | q[l];
+                    punct[i * stride + l] = static_cast<u64>(cur / qi);
+                    rem = cur % qi;
+                }
+                u128 r = 0;
+                for (int l = k; l-- > 0;)
+                    r = ((r << 64) | punct[i * stride + l]) % qi;
+                if (!invmod(static_cast<u64>(r), qi, inv_punct[i]))
+                    throw std::invalid_argument("coefficient moduli are not coprime");
+            }
+        }
     } // namespace
 
     int Engine::total_coeff_modulus_bit_count(int k)
@@ -835,42 +875,37 @@ namespace sealhip
         auto h = std::make_unique<CkksDecodeDev>();
         std::memset(h.get(), 0, sizeof(CkksDecodeDev));
         h->k = k;
-        const std::vector<u64> q = big_product(key_moduli, k);
-        u128 carry = 1; // (q + 1) >> 1
-        std::vector<u64> plus(static_cast<std::size_t>(k) + 1, 0);
-        for (int l = 0; l < k; l++)
-        {
-            carry += q[l];
-            plus[l] = static_cast<u64>(carry);
-            carry >>= 64;
-        }
-        plus[k] = static_cast<u64>(carry);
-        for (int l = 0; l < k; l++)
-        {
-            h->q[l] = q[l];
-            h->half[l] = (plus[l] >> 1) | (plus[l + 1] << 63);
-        }
-        for (int i = 0; i < k; i++)
-        {
-            const u64 qi = key_moduli[i];
-            u128 rem = 0;
-            for (int l = k; l-- > 0;) // q / q_i
-            {
-                const u128 cur = (rem << 64) | q[l];
-                h->punct[i * kCkksMaxLimbs + l] = static_cast<u64>(cur / qi);
-                rem = cur % qi;
-            }
-            u128 r = 0;
-            for (int l = k; l-- > 0;)
-                r = ((r << 64) | h->punct[i * kCkksMaxLimbs + l]) % qi;
-            if (!invmod(static_cast<u64>(r), qi, h->inv_punct[i]))
-                throw std::invalid_argument("coefficient moduli are not coprime");
-        }
+        crt_compose_consts(key_moduli, k, kCkksMaxLimbs, h->q, h->half, h->punct, h->inv_punct);
         SEALHIP_CHECK(hipSetDevice(device));
         CkksDecodeDev *dev = nullptr;
         SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev), sizeof(CkksDecodeDev)));
         SEALHIP_CHECK(hipMemcpy(dev, h.get(), sizeof(CkksDecodeDev), hipMemcpyHostToDevice));
         ckks_decode.emplace(k, dev);
+        return dev;
+    }
+
+    const NoiseBudgetDev *Engine::noise_budget_consts(int k)
+    {
+        if (k < 1 || k > n_key)
+            throw std::invalid_argument("level k out of range");
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = noise_budget.find(k);
+        if (it != noise_budget.end())
+            return it->second;
+        auto h = std::make_unique<NoiseBudgetDev>();
+        std::memset(h.get(), 0, sizeof(NoiseBudgetDev));
+        h->k = k;
+        crt_compose_consts(key_moduli, k, kMaxModuli, h->q, h->half, h->punct, h->t_inv_punct);
+        for (int i = 0; i < k; i++) // fold t: multiply_poly_scalar_coeffmod (decryptor.cpp:305) then compose_array
+        {
+            const u64 qi = key_moduli[i];
+            h->t_inv_punct[i] = static_cast<u64>(static_cast<u128>(t % qi) * h->t_inv_punct[i] % qi);
+        }
+        SEALHIP_CHECK(hipSetDevice(device));
+        NoiseBudgetDev *dev = nullptr;
+        SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev), sizeof(NoiseBudgetDev)));
+        SEALHIP_CHECK(hipMemcpy(dev, h.get(), sizeof(NoiseBudgetDev), hipMemcpyHostToDevice));
+        noise_budget.emplace(k, dev);
         return dev;
     }
 

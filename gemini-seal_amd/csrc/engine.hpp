@@ -198,6 +198,16 @@ namespace sealhip
         u64 punct[kCkksMaxLimbs * kCkksMaxLimbs]; // q / q_i, limbs of row i at i * kCkksMaxLimbs
     };
 
+    // ---- Decryptor::invariant_noise_budget constants for the first k primes (decryptor.cpp:269-325), any level
+    struct NoiseBudgetDev
+    {
+        int k;
+        u64 q[kMaxModuli];           // total_coeff_modulus, little-endian limbs
+        u64 half[kMaxModuli];        // upper_half_threshold = (q + 1) >> 1 (polyarithmod.cpp:27)
+        u64 t_inv_punct[kMaxModuli]; // t * (q / q_i)^{-1} mod q_i: multiply_poly_scalar_coeffmod folded into compose_array
+        u64 punct[kMaxModuli * kMaxModuli]; // q / q_i, limbs of row i at i * kMaxModuli
+    };
+
     struct LevelTools
     {
         std::unique_ptr<HostRnsTool> host_rns; // BFV + CKKS (CKKS only uses inv_q_last_mod_q)
@@ -326,6 +336,8 @@ namespace sealhip
         std::map<int, int> total_bits; // significant bits of q_0...q_{k-1} (context.cpp:178)
         void ckks_tables();
         const CkksDecodeDev *ckks_decode_consts(int k);
+        std::map<int, NoiseBudgetDev *> noise_budget;
+        const NoiseBudgetDev *noise_budget_consts(int k); // BFV
         int total_coeff_modulus_bit_count(int k);
         int plain_prime = -1;                  // prime id of the plain modulus when batching is possible (context.cpp:262-275)
         std::uint32_t *d_batch_map = nullptr;  // BatchEncoder::matrix_reps_index_map_ (batchencoder.cpp:70-94)
@@ -647,6 +659,18 @@ namespace sealhip
                         u64 *plain);
     // values out: count x N/2 complex doubles
     void op_ckks_decode(Engine &e, int k, const u64 *plain, std::size_t count, double scale, double *values);
+
+    // ---- Decryptor (decrypt.hip, pipeline.cpp) ----
+    // bits_out[i] = max(bits_out[i], bits of the largest centred |t v| of item i), v = count x k x N dot products
+    hipError_t launch_noise_bits(const Engine &e, const NoiseBudgetDev *d, int k, const u64 *v, std::size_t count,
+                                 int *bits_out);
+    // Decryptor::invariant_noise_budget (decryptor.cpp:269-325), BFV, ct[count][size][k][N] in coefficient form; budgets in host
+    // memory; synchronises once
+    void op_invariant_noise_budget(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,
+                                   std::int32_t *budgets);
+    // Decryptor::decrypt (decryptor.cpp:51-150): BFV plain[count][N] mod t from coefficient form, CKKS plain[count][k][N] in
+    // NTT form; stream-ordered
+    void op_decrypt(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers, u64 *plain);
 
     // ---- Ciphertext::expand_seed on the device (seed_expand.hip) ----
     // dst of job i receives the rows x N words of c_1 re-sampled from the 64-byte seed (8 words, random_seed_type) of job i:

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 namespace sealhip
 {
@@ -825,6 +826,26 @@ namespace sealhip
               "plain_lift");
         check(launch_ntt(e, plain_ntt, count * k, map_q, false, kNttCanonical), "ntt(plain)");
     }
+    namespace
+    {
+        // dot_product_ct_sk_array of m coefficient-form items of size >= 2 into out[m][k][N]: copies of c_1.. go to (lazy)
+        // NTT form (decryptor.cpp:241-244), the sum comes back canonical (:258-262), then + c_0 (:265). copy: (size-1) x k x N
+        // words per item of scratch.
+        void dot_product_coeff_chunk(Engine &e, int k, const RowMap &map_q, const u64 *ct, int size, std::size_t m,
+                                     const u64 *sk_powers, u64 *copy, u64 *out)
+        {
+            const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+            const std::size_t sk_stride = static_cast<std::size_t>(e.n_key) * N;
+            const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+            check(launch_copy_rows(e, ct + poly, item, copy, tail, m, (size - 1) * k), "copy(c1..)");
+            check(launch_ntt(e, copy, m * (size - 1) * k, map_q, false, kNttAnyRep), "ntt(c1..)"); // (the dot product reduces)
+            // the kernel indexes polynomials 1.. of an item: hand it a base one polynomial before the copies
+            check(launch_dot_sk(e, copy - poly, size, tail, sk_powers, sk_stride, out, m, map_q, 0), "dot_sk");
+            check(launch_ntt(e, out, m * k, map_q, true, kNttCanonical), "intt(dot)");
+            check(launch_dot_sk(e, ct, 1, item, sk_powers, sk_stride, out, m, map_q, 2), "add c0");
+        }
+    } // namespace
+
     // Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i in the
     // form of the ciphertext. sk_powers = (size-1) polynomials s, s^2, ... in NTT form with key-level row stride.
     void op_dot_product_ct_sk(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,
@@ -839,8 +860,6 @@ namespace sealhip
             check(launch_dot_sk(e, ct, size, item, sk_powers, sk_stride, out, count, map_q, 1), "dot_sk");
             return;
         }
-        // coefficient form: copies of c_1.. go to (lazy) NTT form (:241-244), the sum comes back canonical (:258-262),
-        // then + c_0 (:265)
         const std::size_t tail = static_cast<std::size_t>(size - 1) * poly;
         const std::size_t chunk = plan_chunk(e, count, tail * sizeof(u64), 1);
         for (std::size_t off = 0; off < count; off += chunk)
@@ -848,12 +867,73 @@ namespace sealhip
             const std::size_t m = std::min(chunk, count - off);
             e.ws_reset();
             u64 *copy = e.ws_alloc(tail * m);
-            check(launch_copy_rows(e, ct + off * item + poly, item, copy, tail, m, (size - 1) * k), "copy(c1..)");
-            check(launch_ntt(e, copy, m * (size - 1) * k, map_q, false, kNttAnyRep), "ntt(c1..)"); // (the dot product reduces)
-            // the kernel indexes polynomials 1.. of an item: hand it a base one polynomial before the copies
-            check(launch_dot_sk(e, copy - poly, size, tail, sk_powers, sk_stride, out + off * poly, m, map_q, 0), "dot_sk");
-            check(launch_ntt(e, out + off * poly, m * k, map_q, true, kNttCanonical), "intt(dot)");
-            check(launch_dot_sk(e, ct + off * item, 1, item, sk_powers, sk_stride, out + off * poly, m, map_q, 2), "add c0");
+            dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers, copy, out + off * poly);
+        }
+    }
+
+    void op_invariant_noise_budget(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,
+                                   std::int32_t *budgets)
+    {
+        const NoiseBudgetDev *consts = e.noise_budget_consts(k);
+        const int q_bits = e.total_coeff_modulus_bit_count(k);
+        RowMap map_q{}; // rows 0..k-1 of the key primes (the level's BEHZ tools are not needed, nor built)
+        map_q.rows = k;
+        for (int r = 0; r < k; r++)
+            map_q.prime[r] = static_cast<unsigned short>(r);
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+        // one bit count per item, at the FRONT of the arena (ws_floor) for the whole batch; the chunks use the rest
+        const std::size_t flag_bytes = (count * sizeof(int) + 255) & ~static_cast<std::size_t>(255);
+        struct FloorGuard
+        {
+            Engine &e;
+            std::size_t saved;
+            ~FloorGuard()
+            {
+                e.lane().ws_floor = saved;
+            }
+        } guard{ e, e.lane().ws_floor };
+        e.lane().ws_floor = guard.saved + flag_bytes;
+        const std::size_t chunk = plan_chunk(e, count, (tail + poly) * sizeof(u64), 2); // (may move the arena: flags after)
+        int *bits = reinterpret_cast<int *>(static_cast<char *>(e.lane().ws) + guard.saved);
+        check(hipMemsetAsync(bits, 0, count * sizeof(int), e.lane().stream), "memset(bits)");
+        for (std::size_t off = 0; off < count; off += chunk)
+        {
+            const std::size_t m = std::min(chunk, count - off);
+            e.ws_reset();
+            u64 *copy = e.ws_alloc(tail * m);
+            u64 *v = e.ws_alloc(poly * m);
+            dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers, copy, v);
+            check(launch_noise_bits(e, consts, k, v, m, bits + off), "noise_budget");
+        }
+        std::vector<int> host(count);
+        check(hipMemcpyAsync(host.data(), bits, count * sizeof(int), hipMemcpyDeviceToHost, e.lane().stream), "d2h(bits)");
+        e.sync_and_check();
+        // decryptor.cpp:318-324: the -1 accounts for scaling the invariant noise by 2
+        for (std::size_t i = 0; i < count; i++)
+            budgets[i] = std::max(0, q_bits - host[i] - 1);
+    }
+
+    void op_decrypt(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers, u64 *plain)
+    {
+        if (e.scheme == 2) // ckks_decrypt (:122-150): the dot product in NTT form is the plaintext
+        {
+            op_dot_product_ct_sk(e, k, ct, size, count, sk_powers, true, plain);
+            return;
+        }
+        LevelTools &lt = e.level(k);
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+        // bfv_decrypt (:77-120): dot product, then decrypt_scale_and_round into the plaintext
+        const std::size_t chunk = plan_chunk(e, count, (tail + poly) * sizeof(u64), 2);
+        for (std::size_t off = 0; off < count; off += chunk)
+        {
+            const std::size_t m = std::min(chunk, count - off);
+            e.ws_reset();
+            u64 *copy = e.ws_alloc(tail * m);
+            u64 *v = e.ws_alloc(poly * m);
+            dot_product_coeff_chunk(e, k, lt.map_q, ct + off * item, size, m, sk_powers, copy, v);
+            check(launch_decrypt_scale_and_round(e, lt.d_rns, lt.h_rns, v, plain + off * N, m), "decrypt_scale_and_round");
         }
     }
     // ---------------------------------------------------------------- encrypt-side arithmetic

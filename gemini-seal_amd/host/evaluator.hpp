@@ -766,6 +766,138 @@ namespace sealhip_host
         const Context &ctx_;
     };
 
+    // Decryptor (decryptor.h / decryptor.cpp) over a context and the secret key in NTT form (n_key x N words, host). The powers
+    // s^1..s^m live on the device and grow on demand, as compute_secret_key_array does (:152-216), by dyadic products on the
+    // device. A plaintext is a vector of words: BFV, the coefficients mod t trimmed like bfv_decrypt (:112-116); CKKS, the
+    // k x N words in NTT form. The batch overloads decrypt runs of ciphertexts of equal level and size with one call each.
+    template <class CT>
+    class Decryptor
+    {
+    public:
+        Decryptor(const Context &context, const std::uint64_t *secret_key_ntt)
+            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n())
+        {}
+
+        // decrypt (:51-75)
+        void decrypt(const CT &encrypted, std::vector<std::uint64_t> &destination)
+        {
+            std::vector<std::vector<std::uint64_t>> out;
+            decrypt(std::vector<const CT *>{ &encrypted }, out);
+            destination.swap(out[0]);
+        }
+        void decrypt(const std::vector<const CT *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
+        {
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            for (const CT *ct : encrypted)
+            {
+                check_valid(*ct);
+                if (bfv && ct->is_ntt_form())
+                    throw std::invalid_argument("encrypted cannot be in NTT form"); // :79-82
+                if (!bfv && !ct->is_ntt_form())
+                    throw std::invalid_argument("encrypted must be in NTT form"); // :124-127
+            }
+            destination.assign(encrypted.size(), {});
+            for_runs(encrypted, [&](std::size_t first, std::size_t count, std::size_t k, std::size_t size, const std::uint64_t *c,
+                                    const std::uint64_t *powers) {
+                const std::size_t n = ctx_.n(), words = bfv ? n : k * n;
+                Staged o(ctx_, count * words);
+                throw_on(sealhip_decryptor_decrypt(ctx_.get(), std::uint32_t(k), c, std::uint32_t(size), count, powers,
+                                                   bfv ? 0 : 1, o.ptr()));
+                std::vector<std::uint64_t> all(count * words);
+                o.down(all.data(), all.size());
+                for (std::size_t i = 0; i < count; i++)
+                {
+                    const std::uint64_t *p = all.data() + i * words;
+                    std::size_t keep = words;
+                    if (bfv) // get_significant_uint64_count_uint, at least one coefficient (:112-116)
+                    {
+                        while (keep > 1 && p[keep - 1] == 0)
+                            keep--;
+                    }
+                    destination[first + i].assign(p, p + keep);
+                }
+            });
+        }
+
+        // invariant_noise_budget (:269-325)
+        int invariant_noise_budget(const CT &encrypted)
+        {
+            return invariant_noise_budget(std::vector<const CT *>{ &encrypted })[0];
+        }
+        std::vector<int> invariant_noise_budget(const std::vector<const CT *> &encrypted)
+        {
+            for (const CT *ct : encrypted)
+            {
+                check_valid(*ct);
+                if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
+                    throw std::logic_error("unsupported scheme"); // :276-279
+                if (ct->is_ntt_form())
+                    throw std::invalid_argument("encrypted cannot be in NTT form"); // :280-283
+            }
+            std::vector<int> out(encrypted.size(), 0);
+            for_runs(encrypted, [&](std::size_t first, std::size_t count, std::size_t k, std::size_t size, const std::uint64_t *c,
+                                    const std::uint64_t *powers) {
+                std::vector<std::int32_t> b(count);
+                throw_on(sealhip_decryptor_invariant_noise_budget(ctx_.get(), std::uint32_t(k), c, std::uint32_t(size), count,
+                                                                  powers, b.data()));
+                std::copy(b.begin(), b.end(), out.begin() + static_cast<std::ptrdiff_t>(first));
+            });
+            return out;
+        }
+
+    private:
+        // is_valid_for (valcheck.cpp), the metadata the ABI cannot see
+        void check_valid(const CT &ct) const
+        {
+            if (ct.size() < 2 || ct.size() > 16 || ct.coeff_modulus_size() < 1 || ct.coeff_modulus_size() > ctx_.n_key() ||
+                ct.poly_modulus_degree() != ctx_.n())
+                throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        }
+
+        // compute_secret_key_array (:152-216): s^1..s^max_power on the device, kept, and rebuilt longer on demand
+        const std::uint64_t *powers(std::size_t max_power)
+        {
+            if (max_power <= n_powers_)
+                return powers_->ptr();
+            const std::size_t poly = ctx_.n_key() * ctx_.n();
+            std::uint32_t k_first = 0; // the key base of the first data level: all n_key key primes
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            auto next = std::make_unique<Staged>(ctx_, max_power * poly);
+            next->up(sk_.data(), poly);
+            for (std::size_t i = 1; i < max_power; i++)
+                throw_on(sealhip_dyadic_product_coeffmod(ctx_.get(), next->ptr() + (i - 1) * poly, next->ptr(), 1, k_first,
+                                                         SEALHIP_BASE_KEY, next->ptr() + i * poly));
+            powers_ = std::move(next);
+            n_powers_ = max_power;
+            return powers_->ptr();
+        }
+
+        // calls body(first, count, k, size, device ciphertexts, device powers) for each run of equal level and size
+        template <class F>
+        void for_runs(const std::vector<const CT *> &encrypted, F &&body)
+        {
+            for (std::size_t first = 0; first < encrypted.size();)
+            {
+                const std::size_t k = encrypted[first]->coeff_modulus_size(), size = encrypted[first]->size();
+                std::size_t end = first + 1;
+                while (end < encrypted.size() && encrypted[end]->coeff_modulus_size() == k && encrypted[end]->size() == size)
+                    end++;
+                const std::size_t words = size * k * ctx_.n(), count = end - first;
+                const std::uint64_t *pw = powers(size - 1);
+                Staged c(ctx_, count * words);
+                for (std::size_t i = 0; i < count; i++)
+                    throw_on(sealhip_memcpy_h2d(ctx_.get(), c.ptr() + i * words, encrypted[first + i]->data(), words * 8));
+                body(first, count, k, size, c.ptr(), pw);
+                first = end;
+            }
+        }
+
+        const Context &ctx_;
+        std::vector<std::uint64_t> sk_;
+        std::unique_ptr<Staged> powers_;
+        std::size_t n_powers_ = 0;
+    };
+
     // KeyGenerator (keygenerator.h / keygenerator.cpp:105-240) over a context and a secret key in NTT form (n_key x N words,
     // host). Sampling stays with the caller: `sampler(seed, noise)` is asked once per encrypt_zero_symmetric, in the
     // reference's order (key by key, digit by digit), for the 8-word BlakePRNGFactory().create() seed of c_1 and the N

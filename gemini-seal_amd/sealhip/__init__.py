@@ -131,6 +131,8 @@ SYMBOLS = {
     "sealhip_evaluator_rotate_vector": [_vp, _u32, _vp, _sz, _i32, C.POINTER(_u32), C.POINTER(_vp), _u32],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
+    "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
+    "sealhip_decryptor_decrypt": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_encrypt_zero_symmetric": [_vp, _u32, _i32, _vp, _vp, _vp, _sz, _vp],
     "sealhip_encrypt_zero_asymmetric": [_vp, _u32, _i32, _vp, _vp, _vp, _sz, _vp],
     "sealhip_multiply_add_plain_with_scaling_variant": [_vp, _u32, _vp, _sz, _vp, _u32, _sz, _i32],
@@ -501,6 +503,18 @@ class Context:
     def decrypt_scale_and_round(self, k, poly, count, out):
         """RNSTool::decrypt_scale_and_round (rns.cpp:1070-1126)"""
         _check(lib().sealhip_decrypt_scale_and_round(self.handle, k, _ptr(poly), count, _ptr(out)))
+
+    def invariant_noise_budget(self, ct, size, k, count, sk_powers_ntt):
+        """Decryptor::invariant_noise_budget (decryptor.cpp:269-325) per BFV ciphertext of the batch -> numpy int32 array"""
+        budgets = np.zeros(max(1, count), dtype=np.int32)
+        _check(lib().sealhip_decryptor_invariant_noise_budget(self.handle, k, _ptr(ct), size, count, _ptr(sk_powers_ntt),
+                                                              budgets.ctypes.data))
+        return budgets[:count]
+
+    def decrypt(self, ct, size, k, count, sk_powers_ntt, is_ntt_form, plain):
+        """Decryptor::decrypt (decryptor.cpp:51-150): BFV plain[count][N] mod t, CKKS plain[count][k][N] (NTT form)"""
+        _check(lib().sealhip_decryptor_decrypt(self.handle, k, _ptr(ct), size, count, _ptr(sk_powers_ntt),
+                                               1 if is_ntt_form else 0, _ptr(plain)))
 
     # ---- SURVEY 8(f2): encrypt-side arithmetic (the random samples come from the caller)
     def encrypt_zero_symmetric(self, rows, is_ntt_form, a_ntt, noise, sk_ntt, count, ct):

@@ -388,6 +388,21 @@ long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const
                                          const uint64_t *sk_powers_ntt, int32_t is_ntt_form, uint64_t *out);
 /* RNSTool::decrypt_scale_and_round (rns.cpp:1070-1126), BFV: in[count][k][N] -> out[count][N] coefficients mod t */
 long sealhip_decrypt_scale_and_round(sealhip_context *ctx, uint32_t k, const uint64_t *in, size_t count, uint64_t *out);
+/* Decryptor::invariant_noise_budget (decryptor.cpp:269-325) for a BFV batch: budgets[i] (host memory) of ciphertext i,
+   ct[count][size][k][N] in coefficient form, sk_powers_ntt as for sealhip_decryptor_dot_product_ct_sk.
+   Synchronises once; not capturable. */
+long sealhip_decryptor_invariant_noise_budget(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
+                                              size_t count, const uint64_t *sk_powers_ntt, int32_t *budgets);
+/* Decryptor::decrypt (decryptor.cpp:51-150): BFV (is_ntt_form must be 0): plain[count][N] coefficients mod t
+   (dot product + decrypt_scale_and_round); CKKS (is_ntt_form must be 1): plain[count][k][N] in NTT form.
+   Device memory, temporaries from the lane arena, no synchronisation (capturable).
+   Both entries: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside 1..n_key_moduli or size outside
+   2..16 -> E_INVALIDARG ("encrypted is not valid for encryption parameters"); a CKKS context asking for a noise budget ->
+   COR_E_INVALIDOPERATION ("unsupported scheme"); a BFV decrypt with is_ntt_form != 0 or a CKKS decrypt with is_ntt_form
+   == 0 -> E_INVALIDARG; then a host-only context -> COR_E_INVALIDOPERATION. count = 0 -> S_OK, nothing launched. A batch
+   larger than the lane's arena is processed in chunks. */
+long sealhip_decryptor_decrypt(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,
+                               const uint64_t *sk_powers_ntt, int32_t is_ntt_form, uint64_t *plain);
 
 /* ---------------------------------------------------------------- HIP graphs for launch-bound small batches */
 /* Small batches are bound by kernel launches (one multiply+relinearize of a single N=2^15 ciphertext is ~25 launches):

@@ -1,0 +1,171 @@
+// The C++ host adapter's Decryptor (gemini-seal_amd/host/evaluator.hpp). Without arguments, on host-only contexts: the
+// reference's checks and messages (decryptor.cpp:51-150, :269-325). With a device (argv[1] = ordinal, argv[2] = input file
+// written by tests/test_gpu_decryptor.py): the budgets and FNV-1a digests of the decrypted plaintexts of a batch, one
+// ciphertext at a time and as one batch, which the test compares with the C ABI's outputs for the same inputs.
+//
+// Input file, little-endian 64-bit words: scheme, log_n, n_key, nsp, t, key moduli [n_key], secret key (NTT form)
+// [n_key x N], k, size, count, ciphertexts [count x size x k x N].
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../gemini-seal_amd/host/evaluator.hpp"
+
+using namespace sealhip_host;
+
+static std::uint64_t digest(const std::vector<std::uint64_t> &w)
+{
+    std::uint64_t h = 0xcbf29ce484222325ULL;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(w.data());
+    for (std::size_t i = 0; i < w.size() * 8; i++)
+    {
+        h ^= p[i];
+        h *= 0x100000001b3ULL;
+    }
+    return h;
+}
+
+template <class E, class F>
+static bool throws(F &&f, const char *msg)
+{
+    try
+    {
+        f();
+    }
+    catch (const E &e)
+    {
+        if (std::strncmp(e.what(), msg, std::strlen(msg)) == 0)
+            return true;
+        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
+        return false;
+    }
+    catch (const std::exception &e)
+    {
+        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
+        return false;
+    }
+    std::printf("no exception (want '%s')\n", msg);
+    return false;
+}
+
+static HostCiphertext make_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
+{
+    HostCiphertext ct;
+    ct.n_ = n;
+    ct.size_ = size;
+    ct.k_ = k;
+    ct.ntt_form_ = ntt;
+    ct.words.assign(size * k * n, 0);
+    return ct;
+}
+
+static int host_checks()
+{
+    const std::uint64_t mods[4] = { 1073738753ULL, 1099511603713ULL, 1152921504606830593ULL, 1152921504606844417ULL };
+    const std::size_t n = 256;
+    sealhip_params bp{ SEALHIP_SCHEME_BFV, 8, 4, 2, mods, 786433, SEALHIP_MODE_PARITY, -1 };
+    sealhip_params cp{ SEALHIP_SCHEME_CKKS, 8, 4, 2, mods, 0, SEALHIP_MODE_PARITY, -1 };
+    Context bfv(bp), ckks(cp);
+    std::vector<std::uint64_t> sk(4 * n, 1), plain;
+    Decryptor<HostCiphertext> db(bfv, sk.data()), dc(ckks, sk.data());
+    const char *invalid = "encrypted is not valid for encryption parameters";
+    bool ok = true;
+    HostCiphertext one = make_ct(1, 2, n, false), wide = make_ct(17, 2, n, false), deep = make_ct(2, 5, n, false);
+    HostCiphertext ring = make_ct(2, 2, n / 2, false), coeff = make_ct(2, 2, n, false), ntt = make_ct(2, 2, n, true);
+    for (const HostCiphertext *bad : { &one, &wide, &deep, &ring })
+    {
+        ok &= throws<std::invalid_argument>([&] { db.decrypt(*bad, plain); }, invalid);
+        ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(*bad); }, invalid);
+        ok &= throws<std::invalid_argument>([&] { dc.invariant_noise_budget(*bad); }, invalid);
+    }
+    ok &= throws<std::invalid_argument>([&] { db.decrypt(ntt, plain); }, "encrypted cannot be in NTT form");
+    ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(ntt); }, "encrypted cannot be in NTT form");
+    ok &= throws<std::invalid_argument>([&] { dc.decrypt(coeff, plain); }, "encrypted must be in NTT form");
+    ok &= throws<std::logic_error>([&] { dc.invariant_noise_budget(ntt); }, "unsupported scheme");
+    ok &= throws<std::logic_error>([&] { dc.invariant_noise_budget(coeff); }, "unsupported scheme");
+    // a batch is checked whole before any device work
+    ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(std::vector<const HostCiphertext *>{ &coeff, &ntt }); },
+                                        "encrypted cannot be in NTT form");
+    // valid arguments reach the device: a host-only context refuses them
+    ok &= throws<std::logic_error>([&] { db.decrypt(coeff, plain); }, "host-only");
+    ok &= throws<std::logic_error>([&] { db.invariant_noise_budget(coeff); }, "host-only");
+    ok &= throws<std::logic_error>([&] { dc.decrypt(ntt, plain); }, "host-only");
+    if (!ok)
+        return 1;
+    std::printf("host-only decrypt checks ok\n");
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc < 3)
+        return host_checks();
+    try
+    {
+        std::FILE *f = std::fopen(argv[2], "rb");
+        if (!f)
+            return 2;
+        std::vector<std::uint64_t> in;
+        std::uint64_t w;
+        while (std::fread(&w, 8, 1, f) == 1)
+            in.push_back(w);
+        std::fclose(f);
+        std::size_t at = 0;
+        auto next = [&] { return in.at(at++); };
+        const std::uint32_t scheme = std::uint32_t(next()), log_n = std::uint32_t(next());
+        const std::uint32_t n_key = std::uint32_t(next()), nsp = std::uint32_t(next());
+        const std::uint64_t t = next();
+        std::vector<std::uint64_t> mods(n_key);
+        for (auto &m : mods)
+            m = next();
+        const std::size_t n = std::size_t(1) << log_n;
+        sealhip_params p{ scheme, log_n, n_key, nsp, mods.data(), t, SEALHIP_MODE_PARITY, std::atoi(argv[1]) };
+        Context ctx(p);
+        const std::uint64_t *sk = in.data() + at;
+        at += n_key * n;
+        const std::size_t k = next(), size = next(), count = next();
+        std::vector<HostCiphertext> cts;
+        for (std::size_t i = 0; i < count; i++)
+        {
+            cts.push_back(make_ct(size, k, n, scheme == SEALHIP_SCHEME_CKKS));
+            std::memcpy(cts.back().words.data(), in.data() + at, size * k * n * 8);
+            at += size * k * n;
+        }
+        Decryptor<HostCiphertext> dec(ctx, sk);
+        std::vector<const HostCiphertext *> batch;
+        for (auto &c : cts)
+            batch.push_back(&c);
+        std::vector<int> budgets;
+        if (scheme == SEALHIP_SCHEME_BFV)
+            budgets = dec.invariant_noise_budget(batch);
+        std::vector<std::vector<std::uint64_t>> plains;
+        dec.decrypt(batch, plains);
+        for (std::size_t i = 0; i < count; i++)
+        {
+            std::vector<std::uint64_t> single;
+            dec.decrypt(cts[i], single);
+            if (single != plains[i])
+            {
+                std::printf("single and batch decrypt differ at %zu\n", i);
+                return 1;
+            }
+            if (scheme == SEALHIP_SCHEME_BFV)
+            {
+                if (dec.invariant_noise_budget(cts[i]) != budgets[i])
+                {
+                    std::printf("single and batch budget differ at %zu\n", i);
+                    return 1;
+                }
+                std::printf("budget %zu %d\n", i, budgets[i]);
+            }
+            std::printf("plain %zu %zu %llu\n", i, plains[i].size(), static_cast<unsigned long long>(digest(plains[i])));
+        }
+        std::printf("device decrypt ok\n");
+    }
+    catch (const std::exception &e)
+    {
+        std::printf("exception: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
