@@ -29,6 +29,9 @@ namespace sealhip
                         sealhip_ciphertext_info *infos, u64 *dst, std::size_t stride);
     std::size_t wire_save_size(std::uint32_t size, std::uint32_t k, std::size_t n);
     std::size_t wire_save(Engine &e, const sealhip_ciphertext_info &ci, const u64 *src, void *bytes, std::size_t capacity);
+    std::size_t wire_save_seeded_size(const Engine &e, const sealhip_ciphertext_info &ci);
+    std::size_t wire_save_seeded(Engine &e, const sealhip_ciphertext_info &ci, const u64 *src, const std::uint64_t *seed,
+                                 void *bytes, std::size_t capacity);
     std::uint32_t wire_load_kswitch_key(Engine &e, const void *bytes, std::size_t len, std::uint32_t index, u64 **d_out,
                                         std::size_t *words_out, std::uint64_t *dim1_out);
     std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, bool seeded);
@@ -1899,6 +1902,62 @@ long sealhip_multiply_add_plain_with_scaling_variant(sealhip_context *ctx, uint3
     });
 }
 
+namespace
+{
+    // Encryptor's checks (encryptor.cpp:117-121, :185-208, :227-238) before any device work, also on host-only contexts
+    void check_encrypt_args(const Engine &e, uint32_t k, bool has_plain)
+    {
+        if (e.scheme != SEALHIP_SCHEME_BFV && e.scheme != SEALHIP_SCHEME_CKKS)
+            throw std::invalid_argument("unsupported scheme");
+        if (k < 1 || static_cast<int>(k) > e.n_key)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        // BFV encrypts at the first level; a CKKS plaintext lives at a data level (is_metadata_valid_for, no key levels)
+        if (has_plain && (e.scheme == SEALHIP_SCHEME_BFV ? static_cast<int>(k) != e.k_first : static_cast<int>(k) > e.k_first))
+            throw std::invalid_argument("plain is not valid for encryption parameters");
+    }
+} // namespace
+
+long sealhip_encryptor_encrypt(sealhip_context *ctx, uint32_t k, const uint64_t *pk_ntt, const uint64_t *plain,
+                               size_t plain_item_stride, const int32_t *u, const int32_t *noise, size_t count,
+                               uint64_t *ct)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(pk_ntt);
+    REQUIRE_PTR(u);
+    REQUIRE_PTR(noise);
+    REQUIRE_PTR(ct);
+    return guarded([&] {
+        check_encrypt_args(*ctx->engine, k, plain != nullptr);
+        Engine &e = device_engine(ctx);
+        if (count == 0)
+            return;
+        op_encrypt(e, static_cast<int>(k), reinterpret_cast<const u64 *>(pk_ntt), reinterpret_cast<const u64 *>(plain),
+                   plain_item_stride, u, noise, count, reinterpret_cast<u64 *>(ct));
+    });
+}
+
+long sealhip_encryptor_encrypt_symmetric(sealhip_context *ctx, uint32_t k, const uint64_t *sk_ntt,
+                                         const uint64_t *plain, size_t plain_item_stride, const uint64_t *seeds_host,
+                                         const int32_t *noise, int32_t save_seed, size_t count, uint64_t *ct)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(sk_ntt);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(noise);
+    REQUIRE_PTR(ct);
+    return guarded([&] {
+        check_encrypt_args(*ctx->engine, k, plain != nullptr);
+        Engine &e = device_engine(ctx);
+        if (count == 0)
+            return;
+        // the seeded branch only changes BFV (CKKS samples NTT form either way), and is dropped below 9 words (:225-230)
+        const bool seeded = save_seed && e.scheme == SEALHIP_SCHEME_BFV && static_cast<std::size_t>(k) * e.n >= 9;
+        op_encrypt_symmetric(e, static_cast<int>(k), reinterpret_cast<const u64 *>(sk_ntt),
+                             reinterpret_cast<const u64 *>(plain), plain_item_stride, seeds_host, noise, seeded, count,
+                             reinterpret_cast<u64 *>(ct));
+    });
+}
+
 long sealhip_evaluator_add_plain(sealhip_context *ctx, uint32_t k, uint64_t *ct, uint32_t size, size_t count,
                                  const uint64_t *plain, size_t plain_item_stride, int32_t subtract)
 {
@@ -2186,6 +2245,26 @@ long sealhip_ciphertext_save(sealhip_context *ctx, const sealhip_ciphertext_info
     return guarded([&] {
         Engine &e = device_engine(ctx);
         *written = wire_save(e, *info, reinterpret_cast<const u64 *>(src_device), bytes, capacity);
+    });
+}
+
+long sealhip_ciphertext_save_seeded(sealhip_context *ctx, const sealhip_ciphertext_info *info,
+                                    const uint64_t *src_device, const uint64_t seed[8], void *bytes,
+                                    size_t capacity, size_t *written)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(info);
+    REQUIRE_PTR(src_device);
+    REQUIRE_PTR(seed);
+    REQUIRE_PTR(written);
+    return guarded([&] {
+        if (!bytes) // size query
+        {
+            *written = wire_save_seeded_size(*ctx->engine, *info);
+            return;
+        }
+        Engine &e = device_engine(ctx);
+        *written = wire_save_seeded(e, *info, reinterpret_cast<const u64 *>(src_device), seed, bytes, capacity);
     });
 }
 

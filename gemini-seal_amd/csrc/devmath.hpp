@@ -225,6 +225,11 @@ namespace sealhip
     {
         return a ? p - a : 0;
     }
+    // the residue sample_poly_ternary / sample_poly_normal store for a small signed value (rlwe.cpp:25-95)
+    __device__ __forceinline__ u64 lift_small(int v, u64 p)
+    {
+        return v >= 0 ? static_cast<u64>(v) : p - static_cast<u64>(-static_cast<long long>(v));
+    }
 
     // ---------------------------------------------------------------------------------------------
     // Hand-selected instruction sequences for the NTT butterflies. The compiler's expansion of a 64-bit

@@ -628,6 +628,30 @@ namespace sealhip
         u64 t, t_cr0, t_cr1, q_mod_t, threshold;
         u64 div[kMaxModuli]; // floor(q / t) mod q_j  (context.cpp:303-321)
     };
+    // scalingvariant.cpp:31-51: fix = floor((m * (q mod t) + upper_half_increment) / t) for one plaintext coefficient m;
+    // the quotient of barrett_reduce_128 (uintarithsmallmod.h:140-178) kept instead of thrown away, one correction
+    // (numerator < t^2 + t < 2^123, quotient <= t). Shared by scaling_variant_kernel and the fused encrypt kernels.
+    __device__ __forceinline__ u64 scaling_variant_fix(const ScalingArgs &a, u64 m)
+    {
+        u64 lo = 0, hi = 0;
+        mac128(lo, hi, m, a.q_mod_t);
+        const u64 lo2 = lo + a.threshold;
+        hi += lo2 < lo;
+        lo = lo2;
+        const u64 carry0 = mulhi(lo, a.t_cr0);
+        const u64 t1lo = lo * a.t_cr1, t1hi = mulhi(lo, a.t_cr1);
+        const u64 tmp1 = t1lo + carry0;
+        const u64 tmp3 = t1hi + (tmp1 < t1lo);
+        const u64 ulo = hi * a.t_cr0, uhi = mulhi(hi, a.t_cr0);
+        const u64 tmp1b = tmp1 + ulo;
+        const u64 carry1 = uhi + (tmp1b < tmp1);
+        u64 fix = hi * a.t_cr1 + tmp3 + carry1;
+        const u64 rem = lo - fix * a.t;
+        fix += rem >= a.t;
+        return fix;
+    }
+    // the scaling constants of level k (floor(q / t) mod q_j, q mod t, t's Barrett constants; context.cpp:303-321)
+    void fill_scaling_args(const Engine &e, int k, ScalingArgs &a);
     hipError_t launch_rlwe_stage(const Engine &e, int stage, const RlweArgs &a, std::size_t count);
     hipError_t launch_scaling_variant(const Engine &e, const ScalingArgs &a, std::size_t count);
     hipError_t launch_batch_permute(const Engine &e, bool encode, const u64 *in, std::size_t in_item_stride,
@@ -643,6 +667,41 @@ namespace sealhip
     // util/scalingvariant.cpp:15-92 on the c0 of every item (ct_item_stride words apart)
     void op_scaling_variant(Engine &e, int k, const u64 *plain, std::size_t plain_item_stride, u64 *ct,
                             std::size_t ct_item_stride, std::size_t count, bool sub);
+
+    // ---- Encryptor (encrypt.hip, pipeline.cpp) ----
+    enum class EncryptFinish
+    {
+        AsymBfv,
+        SymBfv,
+        AsymCkks,
+        SymCkks
+    };
+    struct EncryptArgs
+    {
+        u64 *ct; // [item][2][k][N]; the symmetric kernels work in place on c_0
+        std::size_t ct_item_stride;
+        int k, rows;                 // ciphertext level; rows of src per polynomial (asymmetric: k + 1 divides by q_k)
+        const u64 *src;              // asymmetric: [item][2][rows][N] (src_item_stride); symmetric CKKS: the secret key
+        std::size_t src_item_stride;
+        const u64 *temp;             // asymmetric CKKS: lazy NTT of the rescale_pre output, [item][2][k][N]
+        const std::int32_t *e;       // BFV: small signed noise, [item][2][N] (asymmetric) or [item][N] (symmetric)
+        const u64 *plain;            // nullptr: encrypt_zero. BFV: [item][N] < t; CKKS: [item][k][N] NTT form
+        std::size_t plain_item_stride;
+        u64 inv_q_last[kMaxModuli];  // q_k^{-1} mod q_i of level k + 1 (inv_q_last_mod_q, rns.cpp:719-728)
+        ScalingArgs sc;              // BFV: the scaling constants of level k (only the constant fields are read)
+    };
+    hipError_t launch_encrypt_finish(const Engine &e, EncryptFinish kind, const EncryptArgs &a, std::size_t count);
+    // Encryptor::encrypt / encrypt_zero with a public key (encryptor.cpp:141-176, :205-253) at level k: encrypt_zero_asymmetric
+    // over the k + 1 rows of the previous level (k = n_key: k rows), divide_and_round_q_last(_ntt) and, with plain, the
+    // plaintext step. pk = 2 x n_key x N (NTT form), u = count x N, noise = count x 2 x N; ct = count x 2 x k x N.
+    void op_encrypt(Engine &e, int k, const u64 *pk, const u64 *plain, std::size_t plain_item_stride, const std::int32_t *u,
+                    const std::int32_t *noise, std::size_t count, u64 *ct);
+    // Encryptor::encrypt_symmetric / encrypt_zero_symmetric (rlwe.cpp:204-300) at level k: c_1 expanded from seeds_host
+    // (count x 8 words), sk = n_key x N (NTT form), noise = count x N. seeded: the BFV save_seed branch (a sampled in
+    // coefficient form); the caller has already dropped it where k x N < 9.
+    void op_encrypt_symmetric(Engine &e, int k, const u64 *sk, const u64 *plain, std::size_t plain_item_stride,
+                              const std::uint64_t *seeds_host, const std::int32_t *noise, bool seeded, std::size_t count,
+                              u64 *ct);
     // batchencoder.cpp:113-154 / :339-376 (needs a prime plain modulus = 1 mod 2N: Engine::plain_prime >= 0)
     void op_batch_encode(Engine &e, const u64 *values, std::size_t nvalues, std::size_t count, u64 *plain, bool is_signed = false);
     void op_batch_decode(Engine &e, const u64 *plain, std::size_t count, u64 *values, bool is_signed = false);

@@ -1113,18 +1113,9 @@ namespace sealhip
         }
     }
 
-    void op_scaling_variant(Engine &e, int k, const u64 *plain, std::size_t plain_item_stride, u64 *ct,
-                            std::size_t ct_item_stride, std::size_t count, bool sub)
+    void fill_scaling_args(const Engine &e, int k, ScalingArgs &a)
     {
-        if (e.scheme != 1)
-            throw std::invalid_argument("unsupported scheme");
-        ScalingArgs a{};
-        a.plain = plain;
-        a.plain_item_stride = plain_item_stride;
-        a.c0 = ct;
-        a.c0_item_stride = ct_item_stride;
         a.k = k;
-        a.sub = sub ? 1 : 0;
         a.t = e.t;
         HostModulus tm(e.t);
         a.t_cr0 = tm.cr0;
@@ -1158,7 +1149,190 @@ namespace sealhip
                 r = ((r << 64) | quot[l]) % e.key_moduli[j];
             a.div[j] = static_cast<u64>(r);
         }
+    }
+
+    void op_scaling_variant(Engine &e, int k, const u64 *plain, std::size_t plain_item_stride, u64 *ct,
+                            std::size_t ct_item_stride, std::size_t count, bool sub)
+    {
+        if (e.scheme != 1)
+            throw std::invalid_argument("unsupported scheme");
+        ScalingArgs a{};
+        fill_scaling_args(e, k, a);
+        a.plain = plain;
+        a.plain_item_stride = plain_item_stride;
+        a.c0 = ct;
+        a.c0_item_stride = ct_item_stride;
+        a.sub = sub ? 1 : 0;
         check(launch_scaling_variant(e, a, count), "scaling_variant");
+    }
+
+    // ---------------------------------------------------------------- Encryptor (encryptor.cpp:106-259)
+    // Public key, per chunk of items:
+    //   1. u to RNS + NTT form over the R = k + 1 rows of the previous level (k = n_key: R = k) (rlwe.cpp:161-170);
+    //   2. BFV: P_j = INTT(u (.) pk_j) (:171-201); the fused tail adds e_j, divides by q_k (rns.cpp:731-775) and adds
+    //      Delta m (scalingvariant.cpp:31-51) straight into ct;
+    //      CKKS: P_j = NTT(lift(e_j)) + u (.) pk_j; the last row goes through divide_and_round_q_last_ntt_inplace
+    //      (rns.cpp:777-851) up to its forward transforms, and the fused tail (rescale_post) writes ct and adds the plaintext.
+    // The previous level of the first level has k_first + 1 rows, whatever nsp is (context.cpp:524-538 moves first_parms_id
+    // forward by nsp - 1 levels), so the prime dropped can be a special prime.
+    void op_encrypt(Engine &e, int k, const u64 *pk, const u64 *plain, std::size_t plain_item_stride, const std::int32_t *u,
+                    const std::int32_t *noise, std::size_t count, u64 *ct)
+    {
+        const bool ckks = e.scheme == 2;
+        const int R = k < e.n_key ? k + 1 : k;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(R) * N, out_poly = static_cast<std::size_t>(k) * N;
+        const std::size_t pk_poly = static_cast<std::size_t>(e.n_key) * N;
+        const bool divide = R == k + 1;
+        EncryptArgs f{};
+        f.k = k;
+        f.rows = R;
+        f.ct_item_stride = 2 * out_poly;
+        f.src_item_stride = 2 * poly;
+        f.plain = plain;
+        f.plain_item_stride = plain_item_stride;
+        LevelTools *lt = nullptr; // CKKS: the previous level's device constants for rescale_pre
+        if (divide)
+        {
+            // inv_q_last_mod_q of the previous level (rns.cpp:719-728); BFV needs no other RNSTool constant of that level
+            for (int i = 0; i < k; i++)
+                if (!invmod(e.key_moduli[k], e.key_moduli[i], f.inv_q_last[i]))
+                    throw std::logic_error("invalid rns bases");
+            if (ckks)
+                lt = &e.level(R);
+        }
+        RowMap map_low{};
+        if (ckks && divide)
+            map_low = e.level_host(k).map_q;
+        if (!ckks && plain)
+            fill_scaling_args(e, k, f.sc);
+        // CKKS at the key level: encrypt_zero_asymmetric straight into ct (no plaintext is valid there)
+        const bool direct = ckks && !divide;
+        const std::size_t per_item = poly + (direct ? 0 : 2 * poly) + (ckks && divide ? 2 * out_poly : 0);
+        const std::size_t chunk = plan_chunk(e, count, per_item * sizeof(u64), 3);
+        for (std::size_t off = 0; off < count; off += chunk)
+        {
+            const std::size_t m = std::min(chunk, count - off);
+            e.ws_reset();
+            u64 *u_ntt = e.ws_alloc(poly * m);
+            u64 *P = direct ? ct + off * 2 * out_poly : e.ws_alloc(2 * poly * m);
+            RlweArgs a{};
+            a.ct = u_ntt;
+            a.ct_item_stride = poly;
+            a.polys = 1;
+            a.rows = R;
+            a.e = u + off * N;
+            a.e_item_stride = N;
+            check(launch_rlwe_stage(e, 0, a, m), "lift(u)");
+            check(launch_ntt(e, u_ntt, m * R, ct_row_map(R, 1, -1), false, kNttCanonical), "ntt(u)");
+            a = RlweArgs{};
+            a.ct = P;
+            a.ct_item_stride = 2 * poly;
+            a.ct_poly_stride = poly;
+            a.polys = 2;
+            a.rows = R;
+            a.x = u_ntt;
+            a.x_item_stride = poly;
+            a.y = pk;
+            a.y_poly_stride = pk_poly;
+            a.e = noise + off * 2 * N;
+            a.e_item_stride = 2 * N;
+            a.e_poly_stride = N;
+            const RowMap both = ct_row_map(R, 2, -1);
+            f.ct = ct + off * 2 * out_poly;
+            f.src = P;
+            f.e = a.e;
+            f.plain = plain ? plain + off * plain_item_stride : nullptr;
+            if (!ckks)
+            {
+                check(launch_rlwe_stage(e, 1, a, m), "u*pk");
+                check(launch_ntt(e, P, m * 2 * R, both, true, kNttCanonical), "intt(c)");
+                check(launch_encrypt_finish(e, EncryptFinish::AsymBfv, f, m), "encrypt_asym_bfv_finish");
+                continue;
+            }
+            check(launch_rlwe_stage(e, 0, a, m), "lift(e)");
+            check(launch_ntt(e, P, m * 2 * R, both, false, kNttCanonical), "ntt(e)");
+            check(launch_rlwe_stage(e, 2, a, m), "c = e + u*pk");
+            if (direct)
+                continue;
+            u64 *temp = e.ws_alloc(2 * out_poly * m);
+            check(launch_ntt(e, P, m * 2 * R, skip_map(lt->map_q, R - 1, R), true, kNttCanonical), "intt(last)");
+            check(launch_rescale_pre(e, lt->d_rns, lt->h_rns, P + out_poly, poly, temp, out_poly, m * 2), "rescale_pre");
+            check(launch_ntt(e, temp, m * 2 * k, map_low, false, 0), "ntt(temp)");
+            f.temp = temp;
+            check(launch_encrypt_finish(e, EncryptFinish::AsymCkks, f, m), "encrypt_asym_ckks_finish");
+        }
+    }
+
+    // Secret key (rlwe.cpp:204-300), for the whole batch at once:
+    //   c_1 = sample_poly_uniform(BlakePRNG(seed)) expanded on the device (one seed job list);
+    //   BFV: c_0 = INTT(A (.) s) with A = c_1 (taken as NTT form), or NTT(c_1) in the arena when seeded (c_1 stays the
+    //        coefficient-form sample, :233-243); unseeded c_1 goes back to coefficient form (:286-293); the fused tail
+    //        negates, adds e and Delta m;
+    //   CKKS: c_0 = NTT(lift(e)), then the fused tail c_0 = -(c_0 + c_1 (.) s) + plain.
+    void op_encrypt_symmetric(Engine &e, int k, const u64 *sk, const u64 *plain, std::size_t plain_item_stride,
+                              const std::uint64_t *seeds_host, const std::int32_t *noise, bool seeded, std::size_t count,
+                              u64 *ct)
+    {
+        const bool ckks = e.scheme == 2;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        std::vector<SeedJob> jobs(count);
+        for (std::size_t i = 0; i < count; i++)
+            jobs[i] = SeedJob{ seeds_host + 8 * i, ct + i * 2 * poly + poly };
+        op_expand_seeds(e, k, jobs.data(), count);
+        EncryptArgs f{};
+        f.k = k;
+        f.rows = k;
+        f.ct = ct;
+        f.ct_item_stride = 2 * poly;
+        f.e = noise;
+        f.plain = plain;
+        f.plain_item_stride = plain_item_stride;
+        RlweArgs a{};
+        a.ct = ct;
+        a.ct_item_stride = 2 * poly;
+        a.polys = 1;
+        a.rows = k;
+        a.e = noise;
+        a.e_item_stride = N;
+        if (ckks)
+        {
+            f.src = sk;
+            check(launch_rlwe_stage(e, 0, a, count), "lift(e)");
+            check(launch_ntt(e, ct, count * 2 * k, ct_row_map(k, 2, 0), false, kNttCanonical), "ntt(e)");
+            check(launch_encrypt_finish(e, EncryptFinish::SymCkks, f, count), "encrypt_sym_ckks_finish");
+            return;
+        }
+        if (plain)
+            fill_scaling_args(e, k, f.sc);
+        a.y = sk;
+        if (!seeded)
+        {
+            a.x = ct + poly;
+            a.x_item_stride = 2 * poly;
+            check(launch_rlwe_stage(e, 1, a, count), "a*s");
+            check(launch_ntt(e, ct, count * 2 * k, ct_row_map(k, 2, -1), true, kNttCanonical), "intt(c0, c1)");
+            check(launch_encrypt_finish(e, EncryptFinish::SymBfv, f, count), "encrypt_sym_bfv_finish");
+            return;
+        }
+        const std::size_t chunk = plan_chunk(e, count, poly * sizeof(u64), 1);
+        for (std::size_t off = 0; off < count; off += chunk)
+        {
+            const std::size_t m = std::min(chunk, count - off);
+            e.ws_reset();
+            u64 *a_ntt = e.ws_alloc(poly * m);
+            u64 *c = ct + off * 2 * poly;
+            check(launch_copy_rows(e, c + poly, 2 * poly, a_ntt, poly, m, k), "copy(a)");
+            check(launch_ntt(e, a_ntt, m * k, ct_row_map(k, 1, -1), false, kNttCanonical), "ntt(a)");
+            a.ct = c;
+            a.x = a_ntt;
+            a.x_item_stride = poly;
+            check(launch_rlwe_stage(e, 1, a, m), "a*s");
+            check(launch_ntt(e, c, m * 2 * k, ct_row_map(k, 2, 0), true, kNttCanonical), "intt(c0)");
+            f.ct = c;
+            f.e = noise + off * N;
+            f.plain = plain ? plain + off * plain_item_stride : nullptr;
+            check(launch_encrypt_finish(e, EncryptFinish::SymBfv, f, m), "encrypt_sym_bfv_finish");
+        }
     }
 
     // ---------------------------------------------------------------- BatchEncoder

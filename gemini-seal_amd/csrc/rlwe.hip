@@ -19,12 +19,6 @@ namespace sealhip
             return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
         }
 
-        // the residue sample_poly_ternary / sample_poly_normal store for a small signed value (rlwe.cpp:25-95)
-        __device__ __forceinline__ u64 lift_small(int v, u64 p)
-        {
-            return v >= 0 ? static_cast<u64>(v) : p - static_cast<u64>(-static_cast<long long>(v));
-        }
-
         // One lane per coefficient pair of (item, poly j < polys, row r < rows). Row r uses prime id r.
         //   STAGE 0: ct = lift(e)                         STAGE 1: ct = x (.) y
         //   STAGE 2: ct = [-] (ct + x (.) y)              STAGE 3: ct = [-] (lift(e) + ct)
@@ -95,25 +89,7 @@ namespace sealhip
             {
                 const std::size_t item = i >> logn, c = i & (n - 1);
                 const u64 m = a.plain[item * a.plain_item_stride + c];
-                u64 lo = 0, hi = 0;
-                mac128(lo, hi, m, a.q_mod_t);
-                const u64 lo2 = lo + a.threshold;
-                hi += lo2 < lo;
-                lo = lo2;
-                // quotient of barrett_reduce_128 (uintarithsmallmod.h:140-178) kept instead of thrown away
-                u64 fix;
-                {
-                    const u64 carry0 = mulhi(lo, a.t_cr0);
-                    const u64 t1lo = lo * a.t_cr1, t1hi = mulhi(lo, a.t_cr1);
-                    const u64 tmp1 = t1lo + carry0;
-                    const u64 tmp3 = t1hi + (tmp1 < t1lo);
-                    const u64 ulo = hi * a.t_cr0, uhi = mulhi(hi, a.t_cr0);
-                    const u64 tmp1b = tmp1 + ulo;
-                    const u64 carry1 = uhi + (tmp1b < tmp1);
-                    fix = hi * a.t_cr1 + tmp3 + carry1;
-                    const u64 rem = lo - fix * a.t;
-                    fix += rem >= a.t;
-                }
+                const u64 fix = scaling_variant_fix(a, m);
                 u64 *dst = a.c0 + item * a.c0_item_stride + c;
                 for (int j = 0; j < a.k; j++)
                 {

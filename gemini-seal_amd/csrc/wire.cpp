@@ -289,12 +289,75 @@ namespace sealhip
     // the 64-byte seed of c_1.
     namespace
     {
+        std::size_t size2_stream_size(const Engine &e, int k, bool seeded)
+        {
+            const auto k32 = static_cast<std::uint32_t>(k);
+            return seeded ? wire_save_size(1, k32, e.n) + kSeedBytes : wire_save_size(2, k32, e.n);
+        }
         std::size_t digit_save_size(const Engine &e, bool seeded)
         {
-            const auto nk = static_cast<std::uint32_t>(e.n_key);
-            return seeded ? wire_save_size(1, nk, e.n) + kSeedBytes : wire_save_size(2, nk, e.n);
+            return size2_stream_size(e, e.n_key, seeded);
+        }
+
+        // One Ciphertext::save_members stream of size 2 at k rows (ciphertext.cpp:170-226), starting at p: both
+        // polynomials, or -- seed != nullptr -- the words of c_0 and then the 64-byte seed of c_1 (:189-208). The words are
+        // copied from src on the lane's stream: the caller synchronises before it reads them. Returns the end of the stream.
+        unsigned char *write_size2_stream(Engine &e, unsigned char *p, const void *parms_id, bool is_ntt_form, int k,
+                                          double scale, const u64 *src, const void *seed)
+        {
+            const std::size_t ct_total = size2_stream_size(e, k, seed != nullptr);
+            const std::size_t stored_words = static_cast<std::size_t>(seed ? 1 : 2) * k * e.n;
+            const Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, ct_total };
+            std::memcpy(p, &h, sizeof(h));
+            p += sizeof(h);
+            std::memcpy(p, parms_id, 32);
+            p += 32;
+            *p++ = is_ntt_form ? 1 : 0;
+            const std::uint64_t size64 = 2, n64 = e.n, k64 = static_cast<std::uint64_t>(k);
+            std::memcpy(p, &size64, 8);
+            std::memcpy(p + 8, &n64, 8);
+            std::memcpy(p + 16, &k64, 8);
+            std::memcpy(p + 24, &scale, 8);
+            p += 32;
+            const Header inner{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, sizeof(Header) + 8 + stored_words * 8 };
+            std::memcpy(p, &inner, sizeof(inner));
+            p += sizeof(inner);
+            const std::uint64_t count = stored_words;
+            std::memcpy(p, &count, 8);
+            p += 8;
+            SEALHIP_CHECK(hipMemcpyAsync(p, src, stored_words * 8, hipMemcpyDeviceToHost, e.lane().stream));
+            p += stored_words * 8;
+            if (seed)
+            {
+                std::memcpy(p, seed, kSeedBytes);
+                p += kSeedBytes;
+            }
+            return p;
         }
     } // namespace
+
+    // Serializable<Ciphertext>::save of a seeded encryption (rlwe.cpp:295-300 + ciphertext.cpp:189-208)
+    std::size_t wire_save_seeded_size(const Engine &e, const sealhip_ciphertext_info &ci)
+    {
+        const int k = level_of(e, ci);
+        if (ci.size != 2)
+            throw std::invalid_argument("a seeded ciphertext has size 2");
+        if (static_cast<std::size_t>(k) * e.n < 9) // rlwe.cpp:225-230: no room for the marker and the seed
+            throw std::invalid_argument("polynomial is too small to store a seed");
+        return size2_stream_size(e, k, true);
+    }
+
+    std::size_t wire_save_seeded(Engine &e, const sealhip_ciphertext_info &ci, const u64 *src, const std::uint64_t *seed,
+                                 void *bytes, std::size_t capacity)
+    {
+        const std::size_t total = wire_save_seeded_size(e, ci);
+        if (capacity < total)
+            throw std::invalid_argument("destination buffer is too small");
+        write_size2_stream(e, static_cast<unsigned char *>(bytes), ci.parms_id, ci.is_ntt_form != 0, level_of(e, ci), ci.scale,
+                           src, seed);
+        e.sync_and_check(); // the words become host-visible here
+        return total;
+    }
 
     std::size_t wire_kswitch_save_size(const Engine &e, const KSwitchKey *const *keys, std::size_t n_slots, bool seeded)
     {
@@ -341,34 +404,9 @@ namespace sealhip
             {
                 if (keys[i]->words != dim2 * digit_words)
                     throw std::logic_error("kswitch_keys is not valid for encryption parameters");
-                const std::size_t ct_total = digit_save_size(e, seeded);
-                const std::size_t stored_words = seeded ? digit_words / 2 : digit_words;
-                const Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, ct_total };
-                std::memcpy(p, &h, sizeof(h));
-                p += sizeof(h);
-                std::memcpy(p, pid.data(), 32);
-                p += 32;
-                *p++ = 1; // keys are kept in NTT form (keygenerator.cpp:347-352)
-                const std::uint64_t size64 = 2, n64 = e.n, k64 = static_cast<std::uint64_t>(e.n_key);
-                std::memcpy(p, &size64, 8);
-                std::memcpy(p + 8, &n64, 8);
-                std::memcpy(p + 16, &k64, 8);
-                std::memcpy(p + 24, &one, 8);
-                p += 32;
-                const Header inner{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, sizeof(Header) + 8 + stored_words * 8 };
-                std::memcpy(p, &inner, sizeof(inner));
-                p += sizeof(inner);
-                const std::uint64_t count = stored_words;
-                std::memcpy(p, &count, 8);
-                p += 8;
-                SEALHIP_CHECK(hipMemcpyAsync(p, keys[i]->d_data + j * digit_words, stored_words * 8, hipMemcpyDeviceToHost,
-                                             e.lane().stream));
-                p += stored_words * 8;
-                if (seeded)
-                {
-                    std::memcpy(p, keys[i]->seeds.data() + 8 * j, kSeedBytes);
-                    p += kSeedBytes;
-                }
+                // keys are kept in NTT form (keygenerator.cpp:347-352)
+                p = write_size2_stream(e, p, pid.data(), true, e.n_key, one, keys[i]->d_data + j * digit_words,
+                                       seeded ? keys[i]->seeds.data() + 8 * j : nullptr);
             }
         }
         e.sync_and_check();

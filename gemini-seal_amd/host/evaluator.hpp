@@ -898,6 +898,235 @@ namespace sealhip_host
         std::size_t n_powers_ = 0;
     };
 
+    // A plaintext as Encryptor takes it: BFV, up to N coefficients < t in coefficient form (shorter is zero-padded);
+    // CKKS, the k x N words of an NTT-form plaintext at level k, with its scale.
+    struct HostPlaintext
+    {
+        std::vector<std::uint64_t> words;
+        std::size_t k = 0; // CKKS: the level (coeff_modulus_size); BFV: unused
+        bool ntt_form = false;
+        double scale = 1.0;
+    };
+
+    // Encryptor (encryptor.h / encryptor.cpp:106-259) over a context and an optional public key (2 x n_key x N host words,
+    // as KeyGenerator::public_key() returns) and an optional secret key (n_key x N, NTT form). Sampling stays with the
+    // caller: asym_sampler(u, e0, e1) is asked once per public-key encryption for the N ternary values of
+    // u and the N + N values of e_0, e_1; sym_sampler(seed, noise) once per secret-key encryption for the 8-word
+    // BlakePRNGFactory().create() seed of c_1 and the N values of e. Ciphertexts are made on the device
+    // (sealhip_encryptor_encrypt, sealhip_encryptor_encrypt_symmetric); the batch overloads make one call per run of equal
+    // level. The seeded forms return the Serializable<Ciphertext> stream (the level's parms_id must be registered with
+    // sealhip_context_set_parms_id).
+    template <class CT>
+    class Encryptor
+    {
+    public:
+        using AsymSampler = std::function<void(std::int32_t *u, std::int32_t *e0, std::int32_t *e1)>;
+        using SymSampler = std::function<void(std::uint64_t *seed, std::int32_t *noise)>;
+
+        Encryptor(const Context &context, const std::uint64_t *public_key, const std::uint64_t *secret_key_ntt,
+                  AsymSampler asym_sampler, SymSampler sym_sampler)
+            : ctx_(context), asym_(std::move(asym_sampler)), sym_(std::move(sym_sampler))
+        {
+            const std::size_t n = context.n(), nk = context.n_key();
+            if (public_key)
+                pk_.assign(public_key, public_key + 2 * nk * n);
+            if (secret_key_ntt)
+                sk_.assign(secret_key_ntt, secret_key_ntt + nk * n);
+            std::uint32_t k_first = 0;
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            k_first_ = k_first;
+        }
+        void set_public_key(const std::uint64_t *public_key)
+        {
+            pk_.assign(public_key, public_key + 2 * ctx_.n_key() * ctx_.n());
+        }
+        void set_secret_key(const std::uint64_t *secret_key_ntt)
+        {
+            sk_.assign(secret_key_ntt, secret_key_ntt + ctx_.n_key() * ctx_.n());
+        }
+
+        // encrypt (:205-253) / encrypt_zero() at the first level / encrypt_zero(parms_id) at level k
+        void encrypt(const HostPlaintext &plain, CT &destination) { encrypt(std::vector<const HostPlaintext *>{ &plain }, one(destination)); }
+        void encrypt(const std::vector<const HostPlaintext *> &plain, std::vector<CT *> destination)
+        {
+            run(true, plain, destination, 0, false);
+        }
+        void encrypt_zero(CT &destination) { encrypt_zero(k_first_, destination); }
+        void encrypt_zero(std::size_t k, CT &destination) { encrypt_zero(k, one(destination)); }
+        void encrypt_zero(std::size_t k, std::vector<CT *> destination) { run(true, {}, destination, k, false); }
+
+        // encrypt_symmetric / encrypt_zero_symmetric (rlwe.cpp:204-300)
+        void encrypt_symmetric(const HostPlaintext &plain, CT &destination)
+        {
+            encrypt_symmetric(std::vector<const HostPlaintext *>{ &plain }, one(destination));
+        }
+        void encrypt_symmetric(const std::vector<const HostPlaintext *> &plain, std::vector<CT *> destination)
+        {
+            run(false, plain, destination, 0, false);
+        }
+        void encrypt_zero_symmetric(CT &destination) { encrypt_zero_symmetric(k_first_, destination); }
+        void encrypt_zero_symmetric(std::size_t k, CT &destination) { encrypt_zero_symmetric(k, one(destination)); }
+        void encrypt_zero_symmetric(std::size_t k, std::vector<CT *> destination) { run(false, {}, destination, k, false); }
+
+        // encrypt_symmetric(plain) returning Serializable<Ciphertext> (encryptor.h:371-376): the stream of c_0 and the seed.
+        // parms_id: that of the ciphertext's level (it is written into the stream and must be registered with
+        // sealhip_context_set_parms_id); destination (optional) receives the ciphertext with c_1 expanded.
+        std::vector<unsigned char> encrypt_symmetric_seeded(const HostPlaintext &plain, const std::uint64_t parms_id[4],
+                                                            CT *destination = nullptr)
+        {
+            return seeded(&plain, k_first_, parms_id, destination);
+        }
+        std::vector<unsigned char> encrypt_zero_symmetric_seeded(std::size_t k, const std::uint64_t parms_id[4],
+                                                                 CT *destination = nullptr)
+        {
+            return seeded(nullptr, k, parms_id, destination);
+        }
+
+    private:
+        static std::vector<CT *> one(CT &c) { return std::vector<CT *>{ &c }; }
+
+        // is_metadata_valid_for / the form checks of encrypt_internal (:185-238) on the host; returns the level
+        std::size_t check_plain(const HostPlaintext &p) const
+        {
+            const std::size_t n = ctx_.n();
+            if (ctx_.scheme() == SEALHIP_SCHEME_BFV)
+            {
+                if (p.words.size() > n || std::any_of(p.words.begin(), p.words.end(),
+                                                      [&](std::uint64_t v) { return v >= ctx_.plain_modulus(); }))
+                    throw std::invalid_argument("plain is not valid for encryption parameters");
+                if (p.ntt_form)
+                    throw std::invalid_argument("plain cannot be in NTT form");
+                return k_first_;
+            }
+            if (p.k < 1 || p.k > k_first_ || p.words.size() != p.k * n)
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            if (!p.ntt_form)
+                throw std::invalid_argument("plain must be in NTT form");
+            return p.k;
+        }
+        void check_keys(bool asymmetric) const
+        {
+            if (asymmetric && pk_.empty())
+                throw std::logic_error("public key is not set");
+            if (!asymmetric && sk_.empty())
+                throw std::logic_error("secret key is not set");
+        }
+
+        // one device call per run of plaintexts of equal level (plain empty: destination.size() zero encryptions at k)
+        void run(bool asymmetric, const std::vector<const HostPlaintext *> &plain, std::vector<CT *> &destination,
+                 std::size_t k_zero, bool save_seed, std::vector<std::uint64_t> *seeds_out = nullptr)
+        {
+            check_keys(asymmetric);
+            const bool zero = plain.empty();
+            if (!zero && plain.size() != destination.size())
+                throw std::invalid_argument("destination count does not match");
+            if (zero && (k_zero < 1 || k_zero > ctx_.n_key()))
+                throw std::invalid_argument("parms_id is not valid for encryption parameters");
+            std::vector<std::size_t> level(destination.size(), k_zero);
+            for (std::size_t i = 0; !zero && i < plain.size(); i++)
+                level[i] = check_plain(*plain[i]);
+            const std::size_t n = ctx_.n(), nk = ctx_.n_key();
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            std::unique_ptr<Staged> key(new Staged(ctx_, (asymmetric ? 2 : 1) * nk * n));
+            key->up(asymmetric ? pk_.data() : sk_.data(), (asymmetric ? 2 : 1) * nk * n);
+            for (std::size_t first = 0; first < destination.size();)
+            {
+                const std::size_t k = level[first];
+                std::size_t end = first + 1;
+                while (end < destination.size() && level[end] == k)
+                    end++;
+                const std::size_t count = end - first, words = 2 * k * n;
+                const std::size_t pw = bfv ? n : k * n; // plaintext words per item
+                std::vector<std::uint64_t> host_plain(zero ? 0 : count * pw, 0);
+                for (std::size_t i = 0; !zero && i < count; i++) // BFV plaintexts shorter than N are zero-padded
+                    std::copy(plain[first + i]->words.begin(), plain[first + i]->words.end(), host_plain.begin() + i * pw);
+                std::unique_ptr<Staged> dp(zero ? nullptr : new Staged(ctx_, host_plain.size()));
+                if (dp)
+                    dp->up(host_plain.data(), host_plain.size());
+                Staged ct(ctx_, count * words);
+                if (asymmetric)
+                {
+                    std::vector<std::int32_t> u(count * n), e(count * 2 * n);
+                    for (std::size_t i = 0; i < count; i++)
+                        asym_(u.data() + i * n, e.data() + 2 * i * n, e.data() + (2 * i + 1) * n);
+                    Staged du(ctx_, (u.size() + 1) / 2), de(ctx_, (e.size() + 1) / 2);
+                    throw_on(sealhip_memcpy_h2d(ctx_.get(), du.ptr(), u.data(), u.size() * 4));
+                    throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
+                    throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key->ptr(), dp ? dp->ptr() : nullptr, pw,
+                                                       reinterpret_cast<const std::int32_t *>(du.ptr()),
+                                                       reinterpret_cast<const std::int32_t *>(de.ptr()), count, ct.ptr()));
+                }
+                else
+                {
+                    std::vector<std::uint64_t> seeds(count * 8);
+                    std::vector<std::int32_t> e(count * n);
+                    for (std::size_t i = 0; i < count; i++)
+                        sym_(seeds.data() + 8 * i, e.data() + i * n);
+                    Staged de(ctx_, (e.size() + 1) / 2);
+                    throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
+                    throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key->ptr(),
+                                                                 dp ? dp->ptr() : nullptr, pw, seeds.data(),
+                                                                 reinterpret_cast<const std::int32_t *>(de.ptr()),
+                                                                 save_seed ? 1 : 0, count, ct.ptr()));
+                    if (seeds_out)
+                        seeds_out->insert(seeds_out->end(), seeds.begin(), seeds.end());
+                }
+                for (std::size_t i = 0; i < count; i++)
+                {
+                    CT &d = *destination[first + i];
+                    d.resize_raw(2, k);
+                    throw_on(sealhip_memcpy_d2h(ctx_.get(), d.data(), ct.ptr() + i * words, words * 8));
+                    d.is_ntt_form() = !bfv;
+                    // encrypt_zero_* set 1.0; CKKS encrypt takes the plaintext's scale (:252)
+                    d.scale() = (!zero && !bfv) ? plain[first + i]->scale : 1.0;
+                }
+                first = end;
+            }
+        }
+
+        std::vector<unsigned char> seeded(const HostPlaintext *plain, std::size_t k, const std::uint64_t *pid, CT *destination)
+        {
+            CT local{};
+            CT &d = destination ? *destination : local;
+            if (!destination)
+                prepare(local);
+            std::vector<CT *> dst{ &d };
+            std::vector<std::uint64_t> seed;
+            if (plain)
+                run(false, std::vector<const HostPlaintext *>{ plain }, dst, 0, true, &seed);
+            else
+                run(false, {}, dst, k, true, &seed);
+            const std::size_t kk = d.coeff_modulus_size(), n = ctx_.n();
+            if (kk * n < 9) // rlwe.cpp:225-230: the reference drops save_seed and saves both polynomials
+                throw std::logic_error("polynomial is too small to store a seed");
+            sealhip_ciphertext_info info{};
+            std::copy(pid, pid + 4, info.parms_id);
+            info.is_ntt_form = d.is_ntt_form() ? 1 : 0;
+            info.size = 2;
+            info.coeff_modulus_size = std::uint32_t(kk);
+            info.poly_modulus_degree = n;
+            info.scale = d.scale();
+            Staged c(ctx_, 2 * kk * n);
+            c.up(d.data(), 2 * kk * n);
+            std::size_t need = 0;
+            throw_on(sealhip_ciphertext_save_seeded(ctx_.get(), &info, c.ptr(), seed.data(), nullptr, 0, &need));
+            std::vector<unsigned char> bytes(need);
+            std::size_t written = 0;
+            throw_on(sealhip_ciphertext_save_seeded(ctx_.get(), &info, c.ptr(), seed.data(), bytes.data(), need, &written));
+            bytes.resize(written);
+            return bytes;
+        }
+        template <class C = CT>
+        auto prepare(C &c) -> decltype(c.n_ = 0, void()) { c.n_ = ctx_.n(); }
+        void prepare(...) {}
+
+        const Context &ctx_;
+        std::vector<std::uint64_t> pk_, sk_;
+        AsymSampler asym_;
+        SymSampler sym_;
+        std::size_t k_first_ = 0;
+    };
+
     // KeyGenerator (keygenerator.h / keygenerator.cpp:105-240) over a context and a secret key in NTT form (n_key x N words,
     // host). Sampling stays with the caller: `sampler(seed, noise)` is asked once per encrypt_zero_symmetric, in the
     // reference's order (key by key, digit by digit), for the 8-word BlakePRNGFactory().create() seed of c_1 and the N

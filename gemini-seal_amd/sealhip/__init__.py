@@ -135,6 +135,8 @@ SYMBOLS = {
     "sealhip_decryptor_decrypt": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_encrypt_zero_symmetric": [_vp, _u32, _i32, _vp, _vp, _vp, _sz, _vp],
     "sealhip_encrypt_zero_asymmetric": [_vp, _u32, _i32, _vp, _vp, _vp, _sz, _vp],
+    "sealhip_encryptor_encrypt": [_vp, _u32, _vp, _vp, _sz, _vp, _vp, _sz, _vp],
+    "sealhip_encryptor_encrypt_symmetric": [_vp, _u32, _vp, _vp, _sz, _vp, _vp, _i32, _sz, _vp],
     "sealhip_multiply_add_plain_with_scaling_variant": [_vp, _u32, _vp, _sz, _vp, _u32, _sz, _i32],
     "sealhip_evaluator_add_plain": [_vp, _u32, _vp, _u32, _sz, _vp, _sz, _i32],
     "sealhip_context_using_batching": [_vp, C.POINTER(_i32)],
@@ -147,6 +149,7 @@ SYMBOLS = {
     "sealhip_ciphertext_load": [_vp, _vp, _sz, _vp, _vp, _sz],
     "sealhip_ciphertext_save_size": [_vp, _u32, _u32, C.POINTER(_sz)],
     "sealhip_ciphertext_save": [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)],
+    "sealhip_ciphertext_save_seeded": [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)],
     "sealhip_is_data_valid_for": [_vp, _u32, _vp, _u32, _sz, _vp],
     "sealhip_ciphertext_resize": [_vp, _u32, _vp, _u32, _vp, _u32, _sz],
     "sealhip_kswitch_key_load_stream": [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_u64)],
@@ -521,6 +524,41 @@ class Context:
         """util::encrypt_zero_symmetric (util/rlwe.cpp:204-300); noise = int32 device words (count x N)"""
         _check(lib().sealhip_encrypt_zero_symmetric(self.handle, rows, 1 if is_ntt_form else 0, _ptr(a_ntt), _ptr(noise),
                                                     _ptr(sk_ntt), count, _ptr(ct)))
+
+    # ---- Encryptor (encryptor.cpp:106-259) with the samples handed in
+    def encrypt(self, k, pk_ntt, plain, u, noise, count, ct, plain_item_stride=None):
+        """Encryptor::encrypt / encrypt_zero(parms_id) with a public key: ct[count][2][k][N] (device). pk_ntt: 2 x n_key x N
+        (NTT form); plain: None (encrypt_zero), BFV count x N < t at the first level, CKKS count x k x N in NTT form;
+        plain_item_stride: words between plaintexts (None: back to back, 0: one for all); u: count x N, noise: count x 2 x N
+        int32 (device, e.g. upload_i32)"""
+        if plain_item_stride is None:
+            plain_item_stride = self.n if self.scheme == SCHEME_BFV else k * self.n
+        _check(lib().sealhip_encryptor_encrypt(self.handle, k, _ptr(pk_ntt), _ptr(plain) if plain is not None else None,
+                                               plain_item_stride, _ptr(u), _ptr(noise), count, _ptr(ct)))
+
+    def encrypt_symmetric(self, k, sk_ntt, plain, seeds, noise, count, ct, save_seed=False, plain_item_stride=None):
+        """Encryptor::encrypt_symmetric / encrypt_zero_symmetric: c_1 expanded on the device from seeds (count x 8 words,
+        host), sk_ntt: n_key x N (NTT form), noise: count x N int32 (device). save_seed: the reference's seeded branch
+        (BFV: a sampled in coefficient form; dropped when k x N < 9). ct receives both polynomials."""
+        if plain_item_stride is None:
+            plain_item_stride = self.n if self.scheme == SCHEME_BFV else k * self.n
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        _check(lib().sealhip_encryptor_encrypt_symmetric(self.handle, k, _ptr(sk_ntt),
+                                                         _ptr(plain) if plain is not None else None, plain_item_stride,
+                                                         seeds.ctypes.data, _ptr(noise), 1 if save_seed else 0, count,
+                                                         _ptr(ct)))
+
+    def save_seeded(self, info, src, seed_words):
+        """Serializable<Ciphertext>::save of a seeded encryption (ciphertext.cpp:189-208): c_0 from src, then the seed"""
+        seed = np.ascontiguousarray(np.array([int(x) for x in seed_words], dtype=np.uint64))
+        need = _sz(0)
+        _check(lib().sealhip_ciphertext_save_seeded(self.handle, C.addressof(info), _ptr(src), seed.ctypes.data, None, 0,
+                                                    C.byref(need)))
+        buf = (C.c_char * need.value)()
+        written = _sz(0)
+        _check(lib().sealhip_ciphertext_save_seeded(self.handle, C.addressof(info), _ptr(src), seed.ctypes.data,
+                                                    C.addressof(buf), need.value, C.byref(written)))
+        return bytes(buf[: written.value])
 
     def encrypt_zero_asymmetric(self, rows, is_ntt_form, pk_ntt, u, noise, count, ct):
         """util::encrypt_zero_asymmetric (util/rlwe.cpp:140-202); u = count x N, noise = count x 2 x N int32"""

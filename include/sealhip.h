@@ -445,6 +445,34 @@ long sealhip_multiply_add_plain_with_scaling_variant(sealhip_context *ctx, uint3
 long sealhip_evaluator_add_plain(sealhip_context *ctx, uint32_t k, uint64_t *ct, uint32_t size, size_t count,
                                  const uint64_t *plain, size_t plain_item_stride, int32_t subtract);
 
+/* ---------------------------------------------------------------- Encryptor (encryptor.cpp:106-259), batched */
+/* Encryptor::encrypt / encrypt_zero(parms_id) with a public key, for a batch: ct[count][2][k][N] at level k.
+   pk_ntt: the key-level public key, 2 x n_key x N, NTT form (device). Below the key level the zero encryption runs over
+   the k + 1 primes of the previous level and is divided and rounded by q_k (encryptor.cpp:141-176): with nsp special
+   primes the previous level of the first level has k_first + 1 rows, not n_key.
+   plain == NULL: encrypt_zero at level k (1..n_key). Otherwise BFV: plain[count][N] < t, k must be the first level
+   (k_first = n_key - nsp); CKKS: plain[count][k][N] in NTT form at level k (1..k_first). plain_item_stride: words between
+   consecutive plaintexts, 0 = one plaintext for all. u[count][N] (sample_poly_ternary), noise[count][2][N] (e_0, e_1 of
+   sample_poly_normal): int32 samples (device). BFV ciphertexts come out in coefficient form, CKKS in NTT form.
+   Checks, before any device work: NULL ctx / pk_ntt / u / noise / ct -> E_POINTER; k outside 1..n_key -> E_INVALIDARG
+   ("parms_id is not valid for encryption parameters"); a plaintext at a level it cannot take -> E_INVALIDARG ("plain is
+   not valid for encryption parameters"); then a host-only context -> COR_E_INVALIDOPERATION. count = 0 -> S_OK, nothing
+   launched. Stream-ordered on the calling thread's lane; temporaries from its arena, in chunks. */
+long sealhip_encryptor_encrypt(sealhip_context *ctx, uint32_t k, const uint64_t *pk_ntt, const uint64_t *plain,
+                               size_t plain_item_stride, const int32_t *u, const int32_t *noise, size_t count,
+                               uint64_t *ct);
+/* Encryptor::encrypt_symmetric / encrypt_zero_symmetric (rlwe.cpp:204-300) for a batch at level k, same plaintext rules:
+   c_1 = sample_poly_uniform(BlakePRNG(seed_i)) expanded on the device from seeds_host[count][8] (host; the seed
+   BlakePRNGFactory().create() drew), c_0 = -(a s + e) [+ the plaintext]. sk_ntt: n_key x N (NTT form, device);
+   noise[count][N] int32 (device). save_seed != 0 selects the reference's seeded branch: for BFV, a is sampled in coefficient
+   form and c_1 stays that sample; the branch is dropped when k x N < 9 words (:225-230), as the reference drops it. ct
+   always receives both polynomials (c_1 as Ciphertext::expand_seed would restore it); write the Serializable<> stream with
+   sealhip_ciphertext_save_seeded. Checks as sealhip_encryptor_encrypt (NULL seeds_host / sk_ntt / noise / ct ->
+   E_POINTER). Not capturable (the seeds are staged on the host). */
+long sealhip_encryptor_encrypt_symmetric(sealhip_context *ctx, uint32_t k, const uint64_t *sk_ntt,
+                                         const uint64_t *plain, size_t plain_item_stride, const uint64_t *seeds_host,
+                                         const int32_t *noise, int32_t save_seed, size_t count, uint64_t *ct);
+
 /* ---------------------------------------------------------------- BatchEncoder */
 /* 1 when the context can batch: BFV with a prime plain modulus = 1 (mod 2N) (context.cpp:262-275, qualifiers().using_batching) */
 long sealhip_context_using_batching(const sealhip_context *ctx, int32_t *using_batching);
@@ -521,6 +549,13 @@ long sealhip_ciphertext_load_many(sealhip_context *ctx, const void *const *strea
 long sealhip_ciphertext_save_size(const sealhip_context *ctx, uint32_t size, uint32_t k, size_t *bytes);
 long sealhip_ciphertext_save(sealhip_context *ctx, const sealhip_ciphertext_info *info, const uint64_t *src_device,
                              void *bytes, size_t capacity, size_t *written);
+/* Serializable<Ciphertext>::save (ciphertext.cpp:189-208) of a seeded encryption: the metadata of info (size must be 2),
+   the k x N words of c_0 from src_device, then the 64-byte seed of c_1. Stream size:
+   sealhip_ciphertext_save_size(ctx, 1, k) + 64; bytes == NULL: size query. Synchronises once. Loads back through
+   sealhip_ciphertext_load, which expands the seed. */
+long sealhip_ciphertext_save_seeded(sealhip_context *ctx, const sealhip_ciphertext_info *info,
+                                    const uint64_t *src_device, const uint64_t seed[8], void *bytes,
+                                    size_t capacity, size_t *written);
 /* KSwitchKeys::load (kswitchkeys.cpp:87-150; RelinKeys / GaloisKeys streams, uncompressed): loads keys_[index] -- RelinKeys:
    index = key_power - 2 (relinkeys.h:61-68), GaloisKeys: index = (galois_elt - 1) / 2 (galoiskeys.h:52-55) -- with its
    decomposition digits concatenated straight from the stream into HBM. *key = NULL when that slot is empty; n_slots (may
