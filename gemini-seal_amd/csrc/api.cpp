@@ -453,6 +453,63 @@ long sealhip_memcpy_d2h(sealhip_context *ctx, void *dst_host, const void *src_de
     });
 }
 
+long sealhip_pool_alloc(sealhip_context *ctx, size_t bytes, void **dptr)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(dptr);
+    *dptr = nullptr;
+    return guarded([&] {
+        if (bytes == 0 || bytes > kPoolMaxBytes)
+            throw std::invalid_argument("pool block size out of range (1 byte .. 2^46 bytes)");
+        *dptr = pool_alloc(device_engine(ctx), bytes);
+    });
+}
+
+long sealhip_pool_release(sealhip_context *ctx, void *dptr)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(dptr);
+    return guarded([&] {
+        pool_check_held(*ctx->engine, dptr); // (a host-only context never handed a block out)
+        pool_release(device_engine(ctx), dptr);
+    });
+}
+
+long sealhip_pool_trim(sealhip_context *ctx)
+{
+    REQUIRE_PTR(ctx);
+    return guarded([&] { pool_trim(device_engine(ctx)); });
+}
+
+long sealhip_pool_stats(sealhip_context *ctx, struct sealhip_pool_stats *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        DevicePool &P = *ctx->engine->pool;
+        std::lock_guard<std::mutex> lock(P.mu);
+        out->bytes_in_use = P.in_use;
+        out->bytes_cached = P.cached;
+        out->device_mallocs = P.mallocs;
+        out->device_frees = P.frees;
+        out->hits = P.hits;
+        out->misses = P.misses;
+        out->cross_lane_hits = P.cross_lane_hits;
+    });
+}
+
+long sealhip_memcpy_d2d(sealhip_context *ctx, void *dst_dev, const void *src_dev, size_t bytes)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(dst_dev);
+    REQUIRE_PTR(src_dev);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (bytes && dst_dev != src_dev)
+            SEALHIP_CHECK(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, e.lane().stream));
+    });
+}
+
 long sealhip_profile_enable(sealhip_context *ctx, int32_t enable)
 {
     REQUIRE_PTR(ctx);
@@ -1620,6 +1677,20 @@ long sealhip_transparency_sink(sealhip_context *ctx, uint32_t *nonzero_flags, si
         l.tsink = reinterpret_cast<unsigned *>(nonzero_flags);
         l.tsink_cap = nonzero_flags ? capacity : 0;
         l.tsink_cur = l.tsink_arm = nullptr;
+    });
+}
+
+long sealhip_transparency_note(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    return guarded([&] {
+        check_level(*ctx->engine, k);
+        if (size < 1 || size > 16)
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        sink.read_pass(reinterpret_cast<const u64 *>(ct), size, static_cast<std::size_t>(k) * e.n, count);
     });
 }
 

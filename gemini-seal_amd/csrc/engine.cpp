@@ -365,6 +365,7 @@ namespace sealhip
             lanes->idle.clear();
         }
         lanes.reset();
+        pool_free_all(*this); // (every stream has drained)
         for (auto &kv : levels)
             for (void *p : kv.second->owned)
                 (void)hipFree(p);

@@ -286,6 +286,30 @@ namespace sealhip
         std::recursive_mutex busy; // held for the duration of an operation (a graph may be launched from another thread)
         ~Lane();
     };
+    // ---- pooled device memory of a context (pool.cpp; sealhip_pool_* in include/sealhip.h) ----
+    constexpr std::size_t kPoolMaxBytes = std::size_t(1) << 46;
+    struct PoolBlock
+    {
+        std::size_t bytes = 0;          // its size class
+        Lane *lane = nullptr;           // the lane that took it (held) or released it (cached)
+        bool held = false;
+        hipEvent_t released = nullptr;  // recorded on that lane's stream at the release; another lane's reuse waits on it
+    };
+    struct DevicePool
+    {
+        std::mutex mu;
+        std::map<void *, PoolBlock> blocks;                                      // every block the pool holds
+        std::map<Lane *, std::map<std::size_t, std::vector<void *>>> free;       // per lane, per size class
+        std::uint64_t in_use = 0, cached = 0, mallocs = 0, frees = 0, hits = 0, misses = 0, cross_lane_hits = 0;
+    };
+    struct Engine;
+    std::size_t pool_size_class(std::size_t bytes);
+    void *pool_alloc(const Engine &e, std::size_t bytes);
+    void pool_check_held(const Engine &e, const void *ptr); // E_INVALIDARG cases, before the device is needed
+    void pool_release(const Engine &e, void *ptr);
+    void pool_trim(const Engine &e);
+    void pool_free_all(Engine &e);
+
     struct LanePool
     {
         std::mutex mu;
@@ -311,6 +335,7 @@ namespace sealhip
         // device
         std::shared_ptr<LanePool> lanes;
         Lane &lane() const; // the calling thread's lane of this context (created on first use)
+        std::unique_ptr<DevicePool> pool{ new DevicePool }; // sealhip_pool_* blocks (pool.cpp)
         // Device-side failures are reported through the lane's sticky flag (Lane::h_fault): kernels store to it, every entry
         // point that makes results host-visible reads it after its stream synchronisation (sync_and_check) and fails with
         // E_UNEXPECTED. all_lanes: every lane is synchronised and every lane's flag is read (and cleared).

@@ -18,12 +18,17 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/sealhip.h"
@@ -59,6 +64,7 @@ namespace sealhip_host
         bool &is_ntt_form() { return ntt_form_; }
         bool is_ntt_form() const { return ntt_form_; }
         double &scale() { return scale_; }
+        double scale() const { return scale_; }
         void resize_raw(std::size_t size, std::size_t k)
         {
             // like IntArray::resize: keeps the leading words, zero-fills the rest (ciphertext.cpp:84-133)
@@ -86,7 +92,7 @@ namespace sealhip_host
         ~Context()
         {
             if (ctx_)
-                sealhip_context_destroy(ctx_);
+                sealhip_context_destroy(ctx_); // (frees every pool block, the transparency rings' included)
         }
         Context(const Context &) = delete;
         Context &operator=(const Context &) = delete;
@@ -96,35 +102,451 @@ namespace sealhip_host
         std::uint64_t plain_modulus() const { return t_; }
         std::size_t n_key() const { return n_key_; } // the highest level the ABI names (key level)
 
+        // SEALContext's parms_id of level k (sealhip_context_set_parms_id), kept for DeviceCiphertext::save
+        void set_parms_id(std::size_t k, const std::uint64_t parms_id[4])
+        {
+            throw_on(sealhip_context_set_parms_id(ctx_, std::uint32_t(k), parms_id));
+            std::lock_guard<std::mutex> lock(mu_);
+            std::copy(parms_id, parms_id + 4, parms_ids_[k].begin());
+        }
+        bool parms_id(std::size_t k, std::uint64_t out[4]) const
+        {
+            std::lock_guard<std::mutex> lock(mu_);
+            auto it = parms_ids_.find(k);
+            if (it == parms_ids_.end())
+                return false;
+            std::copy(it->second.begin(), it->second.end(), out);
+            return true;
+        }
+
+        // The deferred transparency check of the resident Evaluator overloads (SEAL_THROW_ON_TRANSPARENT_CIPHERTEXT,
+        // evaluator.cpp:265-271 and the other #ifdef blocks): a ring of flag words in a pool block per (Evaluator, calling
+        // thread). Each checked operation gets its own slot as the lane's transparency sink; the sink writes a non-zero word
+        // for a result that is NOT transparent. The slots are read at the thread's next host-visible point.
+        static constexpr std::size_t kRingSlots = 256;
+        std::uint32_t *transparency_slot(const void *evaluator) const
+        {
+            Ring &r = ring(evaluator);
+            if (r.used == kRingSlots)
+                check_transparency(); // a full ring is a host-visible point
+            return r.flags + r.used++;
+        }
+        void transparency_unslot(const void *evaluator) const // the operation failed before its result existed
+        {
+            Ring &r = ring(evaluator);
+            if (r.used)
+                r.used--;
+        }
+        // reads the calling thread's rings (one synchronisation each); throws the reference's std::logic_error when a
+        // checked result was transparent
+        void check_transparency() const
+        {
+            std::vector<std::pair<std::uint32_t *, std::size_t>> todo;
+            {
+                std::lock_guard<std::mutex> lock(mu_);
+                for (auto &kv : rings_)
+                    if (kv.first.second == std::this_thread::get_id() && kv.second.used)
+                    {
+                        todo.emplace_back(kv.second.flags, kv.second.used);
+                        kv.second.used = 0;
+                    }
+            }
+            bool transparent = false;
+            for (auto &t : todo)
+            {
+                std::vector<std::uint32_t> host(t.second);
+                throw_on(sealhip_memcpy_d2h(ctx_, host.data(), t.first, host.size() * sizeof(std::uint32_t)));
+                transparent = transparent || std::find(host.begin(), host.end(), 0u) != host.end();
+            }
+            if (transparent)
+                throw std::logic_error("result ciphertext is transparent");
+        }
+        // The Evaluator goes away: its rings go back to the pool. Every lane is waited for first (no stream still writes a
+        // flag into them); flags not yet read are dropped unread -- a destructor does not throw, so call
+        // Evaluator::synchronize() before destroying an Evaluator whose resident results must be checked.
+        void drop_transparency(const void *evaluator) const
+        {
+            bool any = false;
+            {
+                std::lock_guard<std::mutex> lock(mu_);
+                for (auto &kv : rings_)
+                    any = any || kv.first.first == evaluator;
+            }
+            if (any)
+                (void)sealhip_synchronize(ctx_);
+            std::lock_guard<std::mutex> lock(mu_);
+            for (auto it = rings_.begin(); it != rings_.end();)
+                if (it->first.first == evaluator)
+                {
+                    sealhip_pool_release(ctx_, it->second.flags);
+                    it = rings_.erase(it);
+                }
+                else
+                    ++it;
+        }
+
     private:
+        struct Ring
+        {
+            std::uint32_t *flags = nullptr;
+            std::size_t used = 0;
+        };
+        Ring &ring(const void *evaluator) const
+        {
+            std::lock_guard<std::mutex> lock(mu_);
+            Ring &r = rings_[{ evaluator, std::this_thread::get_id() }];
+            if (!r.flags)
+            {
+                void *p = nullptr;
+                throw_on(sealhip_pool_alloc(ctx_, kRingSlots * sizeof(std::uint32_t), &p));
+                r.flags = static_cast<std::uint32_t *>(p);
+            }
+            return r;
+        }
+
         sealhip_context *ctx_ = nullptr;
         std::uint32_t scheme_;
         std::size_t n_;
         std::uint64_t t_;
         std::size_t n_key_;
+        mutable std::mutex mu_;
+        std::map<std::size_t, std::array<std::uint64_t, 4>> parms_ids_;
+        mutable std::map<std::pair<const void *, std::thread::id>, Ring> rings_;
     };
 
-    // device staging of one host object
+    // device staging of one host object, in a block of the context's pool (sealhip_pool_alloc): released stream-ordered,
+    // so the host path makes no allocator call once the pool is warm
     class Staged
     {
     public:
         Staged(const Context &c, std::size_t words) : c_(c), words_(words)
         {
-            throw_on(sealhip_malloc(c.get(), words * 8, &d_));
+            throw_on(sealhip_pool_alloc(c.get(), (words ? words : 1) * 8, &d_));
         }
         ~Staged()
         {
             if (d_)
-                sealhip_free(c_.get(), d_);
+                sealhip_pool_release(c_.get(), d_);
         }
+        Staged(const Staged &) = delete;
+        Staged &operator=(const Staged &) = delete;
         void up(const std::uint64_t *h, std::size_t words) { throw_on(sealhip_memcpy_h2d(c_.get(), d_, h, words * 8)); }
         void down(std::uint64_t *h, std::size_t words) { throw_on(sealhip_memcpy_d2h(c_.get(), h, d_, words * 8)); }
         std::uint64_t *ptr() { return static_cast<std::uint64_t *>(d_); }
+        std::size_t words() const { return words_; }
+        void *release() // the block changes owner (a DeviceCiphertext adopts it)
+        {
+            void *p = d_;
+            d_ = nullptr;
+            return p;
+        }
 
     private:
         const Context &c_;
         void *d_ = nullptr;
         std::size_t words_;
+    };
+
+    namespace detail
+    {
+        // HostCiphertext needs its N before resize_raw; seal::Ciphertext gets it from its parms_id
+        template <class C>
+        auto prepare_host(C &c, std::size_t n) -> decltype(c.n_ = n, void())
+        {
+            c.n_ = n;
+        }
+        inline void prepare_host(...) {}
+    } // namespace detail
+
+    // A ciphertext resident on the device: size x k x N words in a block of the context's pool, with the
+    // metadata of seal::Ciphertext the adapter uses (size, level k, N, NTT form, scale). Copies take a pool block and a
+    // stream-ordered device copy; moves swap. Only download / save / load synchronise (the host-visible points).
+    class DeviceCiphertext
+    {
+    public:
+        explicit DeviceCiphertext(const Context &context) : ctx_(&context), n_(context.n()) {}
+        DeviceCiphertext(const DeviceCiphertext &o) : ctx_(o.ctx_), n_(o.n_) { *this = o; }
+        DeviceCiphertext(DeviceCiphertext &&o) noexcept { swap(o); }
+        ~DeviceCiphertext() { release(); }
+        DeviceCiphertext &operator=(const DeviceCiphertext &o)
+        {
+            if (this == &o)
+                return *this;
+            if (ctx_ != o.ctx_)
+            {
+                release(); // (to the pool it came from)
+                ctx_ = o.ctx_;
+            }
+            n_ = o.n_;
+            reserve(o.words());
+            if (o.words())
+                throw_on(sealhip_memcpy_d2d(ctx_->get(), ptr_, o.ptr_, o.words() * 8));
+            size_ = o.size_;
+            k_ = o.k_;
+            ntt_ = o.ntt_;
+            scale_ = o.scale_;
+            return *this;
+        }
+        DeviceCiphertext &operator=(DeviceCiphertext &&o) noexcept
+        {
+            swap(o); // o releases what this held
+            return *this;
+        }
+        void swap(DeviceCiphertext &o) noexcept
+        {
+            std::swap(ctx_, o.ctx_);
+            std::swap(ptr_, o.ptr_);
+            std::swap(cap_, o.cap_);
+            std::swap(size_, o.size_);
+            std::swap(k_, o.k_);
+            std::swap(n_, o.n_);
+            std::swap(ntt_, o.ntt_);
+            std::swap(scale_, o.scale_);
+        }
+
+        std::uint64_t *data() { return ptr_; } // a DEVICE pointer
+        const std::uint64_t *data() const { return ptr_; }
+        std::size_t size() const { return size_; }
+        std::size_t coeff_modulus_size() const { return k_; }
+        std::size_t poly_modulus_degree() const { return n_; }
+        bool &is_ntt_form() { return ntt_; }
+        bool is_ntt_form() const { return ntt_; }
+        double &scale() { return scale_; }
+        double scale() const { return scale_; }
+        const Context &context() const { return *ctx_; }
+
+        // host ciphertext -> device (one synchronous copy)
+        template <class H>
+        void upload(const H &h)
+        {
+            if (h.poly_modulus_degree() != n_)
+                throw std::invalid_argument("encrypted is not valid for encryption parameters");
+            const std::size_t words = h.size() * h.coeff_modulus_size() * n_;
+            reserve(words);
+            if (words)
+                throw_on(sealhip_memcpy_h2d(ctx_->get(), ptr_, h.data(), words * 8));
+            size_ = h.size();
+            k_ = h.coeff_modulus_size();
+            ntt_ = h.is_ntt_form();
+            scale_ = h.scale();
+        }
+        // device -> host ciphertext; a host-visible point of the calling thread's deferred transparency checks
+        template <class H>
+        void download(H &h) const
+        {
+            ctx_->check_transparency();
+            detail::prepare_host(h, n_);
+            h.resize_raw(size_, k_);
+            if (words())
+                throw_on(sealhip_memcpy_d2h(ctx_->get(), h.data(), ptr_, words() * 8));
+            h.is_ntt_form() = ntt_;
+            h.scale() = scale_;
+        }
+        // Ciphertext::load (ciphertext.cpp:228-330) straight into the block (sealhip_ciphertext_load)
+        void load(const void *bytes, std::size_t len)
+        {
+            sealhip_ciphertext_info info{};
+            throw_on(sealhip_ciphertext_peek(bytes, len, &info));
+            if (info.poly_modulus_degree != n_)
+                throw std::logic_error("ciphertext data is invalid");
+            reserve(std::size_t(info.size) * info.coeff_modulus_size * n_);
+            throw_on(sealhip_ciphertext_load(ctx_->get(), bytes, len, &info, ptr_, cap_));
+            size_ = info.size;
+            k_ = info.coeff_modulus_size;
+            ntt_ = info.is_ntt_form != 0;
+            scale_ = info.scale;
+        }
+        // Ciphertext::save (compr_mode_type::none) straight from the block (sealhip_ciphertext_save); the level's parms_id
+        // comes from Context::set_parms_id. A host-visible point.
+        void save(std::vector<std::uint8_t> &out) const
+        {
+            ctx_->check_transparency();
+            sealhip_ciphertext_info info{};
+            if (!ctx_->parms_id(k_, info.parms_id))
+                throw std::logic_error("the level's parms_id is not registered (Context::set_parms_id)");
+            info.is_ntt_form = ntt_ ? 1 : 0;
+            info.size = std::uint32_t(size_);
+            info.coeff_modulus_size = std::uint32_t(k_);
+            info.poly_modulus_degree = n_;
+            info.scale = scale_;
+            std::size_t need = 0, written = 0;
+            throw_on(sealhip_ciphertext_save_size(ctx_->get(), std::uint32_t(size_), std::uint32_t(k_), &need));
+            out.resize(need);
+            throw_on(sealhip_ciphertext_save(ctx_->get(), &info, ptr_, out.data(), need, &written));
+            out.resize(written);
+        }
+        // Ciphertext::resize (ciphertext.cpp:84-133): polynomials it adds are zero (sealhip_ciphertext_resize)
+        void resize(std::size_t size)
+        {
+            if (size == size_)
+                return;
+            if ((size < 2 && size != 0) || size > 16)
+                throw std::invalid_argument("invalid size");
+            Staged next(*ctx_, size * k_ * n_);
+            throw_on(sealhip_ciphertext_resize(ctx_->get(), std::uint32_t(k_), ptr_ ? ptr_ : next.ptr(), std::uint32_t(size_),
+                                               next.ptr(), std::uint32_t(size), 1));
+            adopt(next.release(), next.words(), size, k_);
+        }
+
+        // (Evaluator) the result in `block` (a pool block of cap_words words) replaces the words; the old block is
+        // released stream-ordered
+        void adopt(void *block, std::size_t cap_words, std::size_t size, std::size_t k)
+        {
+            release();
+            ptr_ = static_cast<std::uint64_t *>(block);
+            cap_ = cap_words;
+            size_ = size;
+            k_ = k;
+        }
+        void set_size(std::size_t size) { size_ = size; } // (Evaluator) fewer polynomials, the leading words kept
+        void copy_meta(const DeviceCiphertext &o) // (Evaluator) NTT form and scale, not the words
+        {
+            ntt_ = o.ntt_;
+            scale_ = o.scale_;
+        }
+
+    private:
+        std::size_t words() const { return size_ * k_ * n_; }
+        void reserve(std::size_t words)
+        {
+            if (words <= cap_ && ptr_)
+                return;
+            void *p = nullptr;
+            throw_on(sealhip_pool_alloc(ctx_->get(), (words ? words : 1) * 8, &p));
+            release();
+            ptr_ = static_cast<std::uint64_t *>(p);
+            cap_ = words;
+        }
+        void release()
+        {
+            if (ptr_ && ctx_)
+                sealhip_pool_release(ctx_->get(), ptr_);
+            ptr_ = nullptr;
+            cap_ = 0;
+        }
+
+        const Context *ctx_ = nullptr;
+        std::uint64_t *ptr_ = nullptr;
+        std::size_t cap_ = 0, size_ = 0, k_ = 0, n_ = 0;
+        bool ntt_ = false;
+        double scale_ = 1.0;
+    };
+
+    // A plaintext resident on the device, in a pool block: coefficient form (N words, each below t; a shorter plaintext is
+    // zero-padded) or NTT form at level k (k x N words). It serves the plain operations of the resident Evaluator overloads,
+    // transform_to_ntt and mod_switch_to(_next) of plaintexts. upload checks the words like is_valid_for (coefficient form:
+    // every word below t) and is the only call that synchronises.
+    class DevicePlaintext
+    {
+    public:
+        explicit DevicePlaintext(const Context &context) : ctx_(&context) {}
+        DevicePlaintext(const DevicePlaintext &o) : ctx_(o.ctx_) { *this = o; }
+        DevicePlaintext(DevicePlaintext &&o) noexcept { swap(o); }
+        ~DevicePlaintext() { release(); }
+        DevicePlaintext &operator=(const DevicePlaintext &o)
+        {
+            if (this == &o)
+                return *this;
+            if (ctx_ != o.ctx_)
+            {
+                release();
+                ctx_ = o.ctx_;
+            }
+            reserve(o.words_);
+            if (o.words_)
+                throw_on(sealhip_memcpy_d2d(ctx_->get(), ptr_, o.ptr_, o.words_ * 8));
+            words_ = o.words_;
+            k_ = o.k_;
+            ntt_ = o.ntt_;
+            return *this;
+        }
+        DevicePlaintext &operator=(DevicePlaintext &&o) noexcept
+        {
+            swap(o);
+            return *this;
+        }
+        void swap(DevicePlaintext &o) noexcept
+        {
+            std::swap(ctx_, o.ctx_);
+            std::swap(ptr_, o.ptr_);
+            std::swap(cap_, o.cap_);
+            std::swap(words_, o.words_);
+            std::swap(k_, o.k_);
+            std::swap(ntt_, o.ntt_);
+        }
+        // coefficient form: up to N coefficients below t; NTT form: k x N words (k = words.size() / N)
+        void upload(const std::vector<std::uint64_t> &words, bool ntt_form)
+        {
+            const std::size_t n = ctx_->n();
+            std::vector<std::uint64_t> padded;
+            const std::uint64_t *src = words.data();
+            std::size_t count = words.size(), k = 0;
+            if (ntt_form)
+            {
+                k = count / n;
+                if (count % n != 0 || k < 1 || k > ctx_->n_key())
+                    throw std::invalid_argument("plain is not valid for encryption parameters");
+            }
+            else
+            {
+                if (count > n || std::any_of(words.begin(), words.end(),
+                                             [&](std::uint64_t v) { return v >= ctx_->plain_modulus(); }))
+                    throw std::invalid_argument("plain is not valid for encryption parameters"); // valcheck.cpp:236-281
+                padded.assign(n, 0);
+                std::copy(words.begin(), words.end(), padded.begin());
+                src = padded.data();
+                count = n;
+            }
+            reserve(count);
+            throw_on(sealhip_memcpy_h2d(ctx_->get(), ptr_, src, count * 8));
+            words_ = count;
+            k_ = k;
+            ntt_ = ntt_form;
+        }
+        void download(std::vector<std::uint64_t> &out) const
+        {
+            out.resize(words_);
+            if (words_)
+                throw_on(sealhip_memcpy_d2h(ctx_->get(), out.data(), ptr_, words_ * 8));
+        }
+        const std::uint64_t *data() const { return ptr_; } // a DEVICE pointer
+        std::size_t words() const { return words_; }
+        std::size_t coeff_modulus_size() const { return k_; } // NTT form: its level; coefficient form: 0
+        bool is_ntt_form() const { return ntt_; }
+        // (Evaluator) the words in `block` replace these
+        void adopt(void *block, std::size_t cap_words, std::size_t words, std::size_t k, bool ntt_form)
+        {
+            release();
+            ptr_ = static_cast<std::uint64_t *>(block);
+            cap_ = cap_words;
+            words_ = words;
+            k_ = k;
+            ntt_ = ntt_form;
+        }
+
+    private:
+        void reserve(std::size_t words)
+        {
+            if (words <= cap_ && ptr_)
+                return;
+            void *p = nullptr;
+            throw_on(sealhip_pool_alloc(ctx_->get(), (words ? words : 1) * 8, &p));
+            release();
+            ptr_ = static_cast<std::uint64_t *>(p);
+            cap_ = words;
+        }
+        void release()
+        {
+            if (ptr_ && ctx_)
+                sealhip_pool_release(ctx_->get(), ptr_);
+            ptr_ = nullptr;
+            cap_ = 0;
+        }
+
+        const Context *ctx_ = nullptr;
+        std::uint64_t *ptr_ = nullptr;
+        std::size_t cap_ = 0, words_ = 0, k_ = 0;
+        bool ntt_ = false;
     };
 
     class KSwitchKeys // one key of RelinKeys / GaloisKeys (kswitchkeys.h:92-130), resident on the device
@@ -153,35 +575,63 @@ namespace sealhip_host
     {
     public:
         explicit Evaluator(const Context &context) : ctx_(context) {}
+        ~Evaluator() { ctx_.drop_transparency(this); }
 
-        // Evaluator::multiply_inplace (evaluator.cpp:235-272)
-        void multiply_inplace(CT &encrypted1, const CT &encrypted2)
+        // Every method on CT has an overload on DeviceCiphertext (the same template): the same host checks and messages,
+        // the same ABI entries, but the operands are used in place in their pool blocks. Once the pool is warm a resident
+        // call makes no hipMalloc / hipFree, no host<->device copy and no synchronisation; a result that grows or moves to
+        // another level gets a pool block and the old one is released stream-ordered. Resident results are also checked
+        // for transparency as under SEAL_THROW_ON_TRANSPARENT_CIPHERTEXT (after exactly the operations the reference
+        // checks), but LATE: the std::logic_error("result ciphertext is transparent") arrives at the calling thread's next
+        // host-visible point -- DeviceCiphertext::download / save, Evaluator::synchronize(), or a full ring of flags. The
+        // host overloads do not check (as before). Plaintext operands are host words, staged through the pool per call.
+        template <class C>
+        using IfCt = typename std::enable_if<std::is_same<C, CT>::value || std::is_same<C, DeviceCiphertext>::value, int>::type;
+        // a plaintext operand: host words (staged through the pool per call) or a DevicePlaintext (used in place)
+        template <class P>
+        using IfPlain = typename std::enable_if<std::is_convertible<P, const std::uint64_t *>::value ||
+                                                    std::is_same<P, DevicePlaintext>::value,
+                                                int>::type;
+
+        // waits for this thread's work on the context; a host-visible point of the deferred transparency check
+        void synchronize()
         {
-            check_pair(encrypted1, encrypted2);
-            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            if (bfv && (encrypted1.is_ntt_form() || encrypted2.is_ntt_form()))
-                throw std::invalid_argument("encrypted1 or encrypted2 cannot be in NTT form"); // :276-279
-            if (!bfv && !(encrypted1.is_ntt_form() && encrypted2.is_ntt_form()))
-                throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form"); // :449-452
-            const std::size_t k = encrypted1.coeff_modulus_size(), n = ctx_.n();
-            const std::size_t s1 = encrypted1.size(), s2 = encrypted2.size(), dest = s1 + s2 - 1;
-            Staged a(ctx_, s1 * k * n), b(ctx_, s2 * k * n), o(ctx_, dest * k * n);
-            a.up(encrypted1.data(), s1 * k * n);
-            b.up(encrypted2.data(), s2 * k * n);
-            throw_on(sealhip_evaluator_multiply(ctx_.get(), std::uint32_t(k), a.ptr(), std::uint32_t(s1), b.ptr(),
-                                                std::uint32_t(s2), 1, o.ptr()));
-            encrypted1.resize_raw(dest, k); // :324 / :484
-            o.down(encrypted1.data(), dest * k * n);
+            throw_on(sealhip_synchronize(ctx_.get()));
+            ctx_.check_transparency();
         }
 
-        void square_inplace(CT &encrypted)
+        // Evaluator::multiply_inplace (evaluator.cpp:235-272)
+        template <class C, IfCt<C> = 0>
+        void multiply_inplace(C &encrypted1, const C &encrypted2)
         {
-            const CT copy = encrypted;
-            multiply_inplace(encrypted, copy); // same canonical residues as bfv_square / ckks_square (:560-770)
+            check_multiply(encrypted1, encrypted2);
+            const std::size_t k = encrypted1.coeff_modulus_size(), n = ctx_.n();
+            const std::size_t s1 = encrypted1.size(), s2 = encrypted2.size(), dest = s1 + s2 - 1;
+            Dev a = dev_in(encrypted1, s1 * k * n), b = dev_in(encrypted2, s2 * k * n), o = dev_out(dest * k * n);
+            Check chk = checked(encrypted1);
+            throw_on(sealhip_evaluator_multiply(ctx_.get(), std::uint32_t(k), a.ptr(), std::uint32_t(s1), b.ptr(),
+                                                std::uint32_t(s2), 1, o.ptr()));
+            chk.done();
+            commit(encrypted1, o, dest, k); // :324 / :484
+        }
+
+        // Evaluator::square_inplace (evaluator.cpp:529-558) on its own entry (bfv_square / ckks_square, :560-770): the same
+        // canonical residues as multiply_inplace(encrypted, encrypted)
+        template <class C, IfCt<C> = 0>
+        void square_inplace(C &encrypted)
+        {
+            check_multiply(encrypted, encrypted);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), s = encrypted.size(), dest = 2 * s - 1;
+            Dev a = dev_in(encrypted, s * k * n), o = dev_out(dest * k * n);
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_square(ctx_.get(), std::uint32_t(k), a.ptr(), std::uint32_t(s), 1, o.ptr()));
+            chk.done();
+            commit(encrypted, o, dest, k);
         }
 
         // Evaluator::relinearize_inplace (evaluator.cpp:772-827); relin_keys[i] = key of get_index(i + 2)
-        void relinearize_inplace(CT &encrypted, const std::vector<const KSwitchKeys *> &relin_keys)
+        template <class C, IfCt<C> = 0>
+        void relinearize_inplace(C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys)
         {
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
             if (size < 2)
@@ -193,27 +643,32 @@ namespace sealhip_host
             std::vector<const sealhip_kswitch_key *> raw;
             for (auto *rk : relin_keys)
                 raw.push_back(rk ? rk->get() : nullptr);
-            Staged c(ctx_, size * k * n);
-            c.up(encrypted.data(), size * k * n);
+            Dev c = dev_in(encrypted, size * k * n);
+            Check chk = checked(encrypted);
             throw_on(sealhip_evaluator_relinearize(ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1,
                                                    raw.data(), std::uint32_t(raw.size())));
-            c.down(encrypted.data(), size * k * n);
-            encrypted.resize_raw(2, k); // :819
+            chk.done();
+            dev_back(encrypted, c, size * k * n);
+            shrink(encrypted, 2); // :819
         }
 
         // Evaluator::mod_switch_to_next_inplace (evaluator.cpp:996-1036)
-        void mod_switch_to_next_inplace(CT &encrypted) { switch_level(encrypted, false); }
+        template <class C, IfCt<C> = 0>
+        void mod_switch_to_next_inplace(C &encrypted) { switch_level(encrypted, false); }
         // Evaluator::rescale_to_next_inplace (evaluator.cpp:1090-1126); the caller updates scale() /= q_last (:889-890)
-        void rescale_to_next_inplace(CT &encrypted) { switch_level(encrypted, true); }
+        template <class C, IfCt<C> = 0>
+        void rescale_to_next_inplace(C &encrypted) { switch_level(encrypted, true); }
 
-        void transform_to_ntt_inplace(CT &encrypted)
+        template <class C, IfCt<C> = 0>
+        void transform_to_ntt_inplace(C &encrypted)
         {
             if (encrypted.is_ntt_form())
                 throw std::invalid_argument("encrypted is already in NTT form"); // :1759-1762
             transform(encrypted, true);
             encrypted.is_ntt_form() = true;
         }
-        void transform_from_ntt_inplace(CT &encrypted_ntt)
+        template <class C, IfCt<C> = 0>
+        void transform_from_ntt_inplace(C &encrypted_ntt)
         {
             if (!encrypted_ntt.is_ntt_form())
                 throw std::invalid_argument("encrypted_ntt is not in NTT form"); // :1807-1810
@@ -222,27 +677,31 @@ namespace sealhip_host
         }
 
         // Evaluator::apply_galois_inplace (evaluator.cpp:1841-1943)
-        void apply_galois_inplace(CT &encrypted, std::uint32_t galois_elt, const KSwitchKeys &galois_key)
+        template <class C, IfCt<C> = 0>
+        void apply_galois_inplace(C &encrypted, std::uint32_t galois_elt, const KSwitchKeys &galois_key)
         {
             if (encrypted.size() > 2)
                 throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
-            Staged c(ctx_, 2 * k * n);
-            c.up(encrypted.data(), 2 * k * n);
+            Dev c = dev_in(encrypted, 2 * k * n);
+            Check chk = checked(encrypted);
             throw_on(sealhip_evaluator_apply_galois(ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elt,
                                                     galois_key.get()));
-            c.down(encrypted.data(), 2 * k * n);
+            chk.done();
+            dev_back(encrypted, c, 2 * k * n);
         }
 
         // Evaluator::rotate_vector_inplace (evaluator.h:1201-1211): CKKS only, then rotate_internal
-        void rotate_vector_inplace(CT &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C, IfCt<C> = 0>
+        void rotate_vector_inplace(C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
                 throw std::logic_error("unsupported scheme"); // :1205-1208
             rotate_vector_like(encrypted, steps, galois_keys);
         }
         // rotate_internal (evaluator.cpp:1945-2000): one automorphism when its key is present, else the NAF of the step count
-        void rotate_vector_like(CT &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C, IfCt<C> = 0>
+        void rotate_vector_like(C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             if (steps == 0)
                 return;
@@ -269,7 +728,8 @@ namespace sealhip_host
         }
 
         // Evaluator::rotate_rows_inplace (evaluator.h:1057-1067): BFV only, then rotate_internal like rotate_vector
-        void rotate_rows_inplace(CT &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C, IfCt<C> = 0>
+        void rotate_rows_inplace(C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
                 throw std::logic_error("unsupported scheme"); // :1061-1064
@@ -277,14 +737,16 @@ namespace sealhip_host
         }
         // Evaluator::rotate_columns_inplace (evaluator.h:1131-1139): BFV only; conjugate_internal = apply_galois with
         // get_elt_from_step(0) = 2N - 1 (:1343-1363)
-        void rotate_columns_inplace(CT &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C, IfCt<C> = 0>
+        void rotate_columns_inplace(C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
                 throw std::logic_error("unsupported scheme"); // :1134-1137
             conjugate_internal(encrypted, galois_keys);
         }
         // Evaluator::complex_conjugate_inplace (evaluator.h:1269-1277): CKKS only, the same automorphism
-        void complex_conjugate_inplace(CT &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C, IfCt<C> = 0>
+        void complex_conjugate_inplace(C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
                 throw std::logic_error("unsupported scheme"); // :1272-1275
@@ -294,7 +756,8 @@ namespace sealhip_host
         // Evaluator::mod_switch_to_inplace (evaluator.cpp:1038-1060) / rescale_to_inplace (:1128-1165). The ABI names a level by
         // its number of primes k (the chain drops one prime per level, context.cpp:423-431); for seal::Ciphertext the
         // binding maps the parms_id argument to it.
-        void mod_switch_to_inplace(CT &encrypted, std::size_t target_coeff_modulus_size)
+        template <class C, IfCt<C> = 0>
+        void mod_switch_to_inplace(C &encrypted, std::size_t target_coeff_modulus_size)
         {
             if (target_coeff_modulus_size < 1)
                 throw std::invalid_argument("parms_id is not valid for encryption parameters"); // :1047-1050
@@ -303,7 +766,8 @@ namespace sealhip_host
             while (encrypted.coeff_modulus_size() != target_coeff_modulus_size)
                 mod_switch_to_next_inplace(encrypted); // :1056-1059
         }
-        void rescale_to_inplace(CT &encrypted, std::size_t target_coeff_modulus_size)
+        template <class C, IfCt<C> = 0>
+        void rescale_to_inplace(C &encrypted, std::size_t target_coeff_modulus_size)
         {
             if (target_coeff_modulus_size < 1)
                 throw std::invalid_argument("parms_id is not valid for encryption parameters"); // :1137-1140
@@ -315,11 +779,12 @@ namespace sealhip_host
                 rescale_to_next_inplace(encrypted);
         }
         // Evaluator::add_many (evaluator.cpp:153-172)
-        void add_many(const std::vector<CT> &encrypteds, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void add_many(const std::vector<C> &encrypteds, C &destination)
         {
             if (encrypteds.empty())
                 throw std::invalid_argument("encrypteds cannot be empty"); // :155-158
-            for (const CT &c : encrypteds)
+            for (const C &c : encrypteds)
                 if (&c == &destination)
                     throw std::invalid_argument("encrypteds must be different from destination"); // :159-165
             destination = encrypteds[0];
@@ -329,8 +794,10 @@ namespace sealhip_host
 
         // ---- destination-taking variants (evaluator.h:121-126, :156-168, :214-226, :268-284, :317-322, :371-376, :396-430,
         // :565-583, :916-947, :1021-1027, :1097-1103, :1167-1173, :1239-1245, :1302-1308): copy, then the in-place form
-        void negate(const CT &encrypted, CT &destination) { destination = encrypted; negate_inplace(destination); }
-        void add(const CT &encrypted1, const CT &encrypted2, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void negate(const C &encrypted, C &destination) { destination = encrypted; negate_inplace(destination); }
+        template <class C, IfCt<C> = 0>
+        void add(const C &encrypted1, const C &encrypted2, C &destination)
         {
             if (&encrypted2 == &destination) // (:160-163: addition commutes, the alias is kept valid)
                 add_inplace(destination, encrypted1);
@@ -340,7 +807,8 @@ namespace sealhip_host
                 add_inplace(destination, encrypted2);
             }
         }
-        void sub(const CT &encrypted1, const CT &encrypted2, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void sub(const C &encrypted1, const C &encrypted2, C &destination)
         {
             if (&encrypted2 == &destination) // :216-222: destination = -(encrypted2 - encrypted1)
             {
@@ -353,7 +821,8 @@ namespace sealhip_host
                 sub_inplace(destination, encrypted2);
             }
         }
-        void multiply(const CT &encrypted1, const CT &encrypted2, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void multiply(const C &encrypted1, const C &encrypted2, C &destination)
         {
             if (&encrypted2 == &destination) // :272-275
                 multiply_inplace(destination, encrypted1);
@@ -363,109 +832,129 @@ namespace sealhip_host
                 multiply_inplace(destination, encrypted2);
             }
         }
-        void square(const CT &encrypted, CT &destination) { destination = encrypted; square_inplace(destination); }
-        void relinearize(const CT &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void square(const C &encrypted, C &destination) { destination = encrypted; square_inplace(destination); }
+        template <class C, IfCt<C> = 0>
+        void relinearize(const C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
             destination = encrypted;
             relinearize_inplace(destination, relin_keys);
         }
-        void mod_switch_to_next(const CT &encrypted, CT &destination) { destination = encrypted; mod_switch_to_next_inplace(destination); }
-        void rescale_to_next(const CT &encrypted, CT &destination) { destination = encrypted; rescale_to_next_inplace(destination); }
-        void mod_switch_to(const CT &encrypted, std::size_t target_coeff_modulus_size, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void mod_switch_to_next(const C &encrypted, C &destination) { destination = encrypted; mod_switch_to_next_inplace(destination); }
+        template <class C, IfCt<C> = 0>
+        void rescale_to_next(const C &encrypted, C &destination) { destination = encrypted; rescale_to_next_inplace(destination); }
+        template <class C, IfCt<C> = 0>
+        void mod_switch_to(const C &encrypted, std::size_t target_coeff_modulus_size, C &destination)
         {
             destination = encrypted;
             mod_switch_to_inplace(destination, target_coeff_modulus_size);
         }
-        void rescale_to(const CT &encrypted, std::size_t target_coeff_modulus_size, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void rescale_to(const C &encrypted, std::size_t target_coeff_modulus_size, C &destination)
         {
             destination = encrypted;
             rescale_to_inplace(destination, target_coeff_modulus_size);
         }
-        void transform_to_ntt(const CT &encrypted, CT &destination_ntt) { destination_ntt = encrypted; transform_to_ntt_inplace(destination_ntt); }
-        void transform_from_ntt(const CT &encrypted_ntt, CT &destination) { destination = encrypted_ntt; transform_from_ntt_inplace(destination); }
-        void apply_galois(const CT &encrypted, std::uint32_t galois_elt, const KSwitchKeys &galois_key, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void transform_to_ntt(const C &encrypted, C &destination_ntt) { destination_ntt = encrypted; transform_to_ntt_inplace(destination_ntt); }
+        template <class C, IfCt<C> = 0>
+        void transform_from_ntt(const C &encrypted_ntt, C &destination) { destination = encrypted_ntt; transform_from_ntt_inplace(destination); }
+        template <class C, IfCt<C> = 0>
+        void apply_galois(const C &encrypted, std::uint32_t galois_elt, const KSwitchKeys &galois_key, C &destination)
         {
             destination = encrypted;
             apply_galois_inplace(destination, galois_elt, galois_key);
         }
-        void rotate_vector(const CT &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void rotate_vector(const C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination)
         {
             destination = encrypted;
             rotate_vector_inplace(destination, steps, galois_keys);
         }
-        void rotate_rows(const CT &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void rotate_rows(const C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination)
         {
             destination = encrypted;
             rotate_rows_inplace(destination, steps, galois_keys);
         }
-        void rotate_columns(const CT &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void rotate_columns(const C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination)
         {
             destination = encrypted;
             rotate_columns_inplace(destination, galois_keys);
         }
-        void complex_conjugate(const CT &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void complex_conjugate(const C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination)
         {
             destination = encrypted;
             complex_conjugate_inplace(destination, galois_keys);
         }
-        void multiply_plain(const CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form, CT &destination)
+        template <class C, class P, IfCt<C> = 0>
+        void multiply_plain(const C &encrypted, const P &plain, bool plain_is_ntt_form, C &destination)
         {
             destination = encrypted;
             multiply_plain_inplace(destination, plain, plain_is_ntt_form);
         }
-        void add_plain(const CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form, CT &destination)
+        template <class C, class P, IfCt<C> = 0>
+        void add_plain(const C &encrypted, const P &plain, bool plain_is_ntt_form, C &destination)
         {
             destination = encrypted;
             add_plain_inplace(destination, plain, plain_is_ntt_form);
         }
-        void sub_plain(const CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form, CT &destination)
+        template <class C, class P, IfCt<C> = 0>
+        void sub_plain(const C &encrypted, const P &plain, bool plain_is_ntt_form, C &destination)
         {
             destination = encrypted;
             sub_plain_inplace(destination, plain, plain_is_ntt_form);
         }
-        void exponentiate(const CT &encrypted, std::uint64_t exponent, const std::vector<const KSwitchKeys *> &relin_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void exponentiate(const C &encrypted, std::uint64_t exponent, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
             destination = encrypted; // :719-726
             exponentiate_inplace(destination, exponent, relin_keys);
         }
 
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
-        void multiply_many(const std::vector<CT> &encrypteds, const std::vector<const KSwitchKeys *> &relin_keys, CT &destination)
+        template <class C, IfCt<C> = 0>
+        void multiply_many(const std::vector<C> &encrypteds, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
             if (encrypteds.empty())
                 throw std::invalid_argument("encrypteds vector must not be empty"); // :1185-1188
-            for (const CT &c : encrypteds)
+            for (const C &c : encrypteds)
                 if (&c == &destination)
                     throw std::invalid_argument("encrypteds must be different from destination"); // :1193-1199
             const std::size_t k = encrypteds[0].coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n;
-            std::vector<std::unique_ptr<Staged>> dev;
+            std::vector<Dev> dev;
             std::vector<const std::uint64_t *> ptrs;
-            for (const CT &c : encrypteds)
+            for (const C &c : encrypteds)
             {
                 if (c.size() != 2 || c.coeff_modulus_size() != k || c.poly_modulus_degree() != n)
                     throw std::invalid_argument("encrypteds is not valid for encryption parameters");
-                dev.emplace_back(new Staged(ctx_, words));
-                dev.back()->up(c.data(), words);
-                ptrs.push_back(dev.back()->ptr());
+                dev.push_back(dev_in(c, words));
+                ptrs.push_back(dev.back().ptr());
             }
             std::vector<const sealhip_kswitch_key *> raw;
             for (auto *rk : relin_keys)
                 raw.push_back(rk ? rk->get() : nullptr);
-            Staged o(ctx_, words);
+            Dev o = dev_out(words);
+            Check chk = checked(destination); // the composite entry leaves the sink alone: the read pass notes the product
             throw_on(sealhip_evaluator_multiply_many(ctx_.get(), std::uint32_t(k), ptrs.data(), std::uint32_t(ptrs.size()), 1,
                                                      raw.data(), std::uint32_t(raw.size()), o.ptr()));
-            destination = encrypteds[0];
-            destination.resize_raw(2, k);
-            o.down(destination.data(), words);
+            chk.note(k, o.ptr(), 2);
+            chk.done();
+            take_meta(destination, encrypteds[0]);
+            commit(destination, o, 2, k);
         }
         // Evaluator::exponentiate_inplace (evaluator.cpp:1257-1288)
-        void exponentiate_inplace(CT &encrypted, std::uint64_t exponent, const std::vector<const KSwitchKeys *> &relin_keys)
+        template <class C, IfCt<C> = 0>
+        void exponentiate_inplace(C &encrypted, std::uint64_t exponent, const std::vector<const KSwitchKeys *> &relin_keys)
         {
             if (exponent == 0)
                 throw std::invalid_argument("exponent cannot be 0"); // :1275-1278
             if (exponent == 1)
                 return; // :1281-1284
-            const std::vector<CT> copies(static_cast<std::size_t>(exponent), encrypted);
+            const std::vector<C> copies(static_cast<std::size_t>(exponent), encrypted);
             multiply_many(copies, relin_keys, encrypted);
         }
 
@@ -552,41 +1041,107 @@ namespace sealhip_host
 
         // ---- the rest of the Evaluator surface
         // Evaluator::negate_inplace (evaluator.cpp:65-88)
-        void negate_inplace(CT &encrypted)
+        template <class C, IfCt<C> = 0>
+        void negate_inplace(C &encrypted)
         {
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
-            Staged c(ctx_, size * k * n);
-            c.up(encrypted.data(), size * k * n);
+            Dev c = dev_in(encrypted, size * k * n);
+            Check chk = checked(encrypted);
             throw_on(sealhip_evaluator_negate(ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1, c.ptr()));
-            c.down(encrypted.data(), size * k * n);
+            chk.done();
+            dev_back(encrypted, c, size * k * n);
         }
         // Evaluator::add_inplace (evaluator.cpp:90-151) / sub_inplace (:174-233)
-        void add_inplace(CT &encrypted1, const CT &encrypted2) { add_sub(encrypted1, encrypted2, false); }
-        void sub_inplace(CT &encrypted1, const CT &encrypted2) { add_sub(encrypted1, encrypted2, true); }
+        template <class C, IfCt<C> = 0>
+        void add_inplace(C &encrypted1, const C &encrypted2) { add_sub(encrypted1, encrypted2, false); }
+        template <class C, IfCt<C> = 0>
+        void sub_inplace(C &encrypted1, const C &encrypted2) { add_sub(encrypted1, encrypted2, true); }
         // Evaluator::multiply_plain_inplace (evaluator.cpp:1438-1473). plain: NTT form -> k*N words (multiply_plain_ntt,
-        // :1605-1646), coefficient form -> N coefficients below t (multiply_plain_normal, :1475-1603).
-        void multiply_plain_inplace(CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form)
+        // :1605-1646), coefficient form -> N coefficients below t (multiply_plain_normal, :1475-1603). Host words; the
+        // resident overloads stage them through a pool block too.
+        template <class C, class P, IfCt<C> = 0, IfPlain<P> = 0>
+        void multiply_plain_inplace(C &encrypted, const P &plain, bool plain_is_ntt_form)
         {
             if (encrypted.is_ntt_form() != plain_is_ntt_form)
                 throw std::invalid_argument("NTT form mismatch"); // :1449-1452
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
             const std::size_t pw = plain_is_ntt_form ? k * n : n;
-            Staged c(ctx_, size * k * n), p(ctx_, pw);
-            c.up(encrypted.data(), size * k * n);
-            p.up(plain, pw);
+            Dev c = dev_in(encrypted, size * k * n), p = dev_plain(plain, pw, plain_is_ntt_form);
+            Check chk = checked(encrypted);
             throw_on((plain_is_ntt_form ? sealhip_evaluator_multiply_plain_ntt : sealhip_evaluator_multiply_plain)(
                 ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1, p.ptr(), 0));
-            c.down(encrypted.data(), size * k * n);
+            chk.done();
+            dev_back(encrypted, c, size * k * n);
         }
         // Evaluator::add_plain_inplace (evaluator.cpp:1290-1362) / sub_plain_inplace (:1364-1435). BFV: plain = N
         // coefficients below t, ciphertext in coefficient form; CKKS: plain = k*N words in NTT form, same level.
-        void add_plain_inplace(CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form)
+        template <class C, class P, IfCt<C> = 0, IfPlain<P> = 0>
+        void add_plain_inplace(C &encrypted, const P &plain, bool plain_is_ntt_form)
         {
             plain_linear(encrypted, plain, plain_is_ntt_form, false);
         }
-        void sub_plain_inplace(CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form)
+        template <class C, class P, IfCt<C> = 0, IfPlain<P> = 0>
+        void sub_plain_inplace(C &encrypted, const P &plain, bool plain_is_ntt_form)
         {
             plain_linear(encrypted, plain, plain_is_ntt_form, true);
+        }
+        // the resident plaintext names its own form
+        void multiply_plain_inplace(DeviceCiphertext &encrypted, const DevicePlaintext &plain)
+        {
+            multiply_plain_inplace(encrypted, plain, plain.is_ntt_form());
+        }
+        void add_plain_inplace(DeviceCiphertext &encrypted, const DevicePlaintext &plain)
+        {
+            add_plain_inplace(encrypted, plain, plain.is_ntt_form());
+        }
+        void sub_plain_inplace(DeviceCiphertext &encrypted, const DevicePlaintext &plain)
+        {
+            sub_plain_inplace(encrypted, plain, plain.is_ntt_form());
+        }
+        // transform_to_ntt(Plaintext, parms_id) (evaluator.cpp:1648-1744) on a resident coefficient-form plaintext
+        void transform_to_ntt(const DevicePlaintext &plain, std::size_t k, DevicePlaintext &destination_ntt)
+        {
+            if (plain.is_ntt_form())
+                throw std::invalid_argument("plain is already in NTT form"); // :1662-1665
+            if (k < 1 || k > ctx_.n_key())
+                throw std::invalid_argument("parms_id is not valid for the current context"); // :1657-1661
+            const std::size_t n = ctx_.n();
+            Staged o(ctx_, k * n);
+            throw_on(sealhip_evaluator_transform_plain_to_ntt(ctx_.get(), std::uint32_t(k), plain.data(), plain.words(), 0, 1,
+                                                              o.ptr()));
+            destination_ntt.adopt(o.release(), k * n, k * n, k, true);
+        }
+        void transform_to_ntt_inplace(DevicePlaintext &plain, std::size_t k) { transform_to_ntt(plain, k, plain); }
+        // mod_switch_to(Plaintext &, parms_id) (evaluator.cpp:1062-1088) / mod_switch_to_next (:959-994), resident
+        void mod_switch_to_inplace(DevicePlaintext &plain, std::size_t target_coeff_modulus_size)
+        {
+            const std::size_t k = plain.coeff_modulus_size();
+            if (target_coeff_modulus_size < 1 || target_coeff_modulus_size > ctx_.n_key())
+                throw std::invalid_argument("parms_id is not valid for encryption parameters"); // :1071-1074
+            if (!plain.is_ntt_form())
+                throw std::invalid_argument("plain is not in NTT form"); // :1075-1078
+            if (k < target_coeff_modulus_size)
+                throw std::invalid_argument("cannot switch to higher level modulus"); // :1079-1082
+            if (k == target_coeff_modulus_size)
+                return;
+            const std::size_t n = ctx_.n(), words = target_coeff_modulus_size * n;
+            Staged o(ctx_, words);
+            throw_on(sealhip_evaluator_mod_switch_plain_to(ctx_.get(), std::uint32_t(k), plain.data(), 1,
+                                                           std::uint32_t(target_coeff_modulus_size), o.ptr()));
+            plain.adopt(o.release(), words, words, target_coeff_modulus_size, true);
+        }
+        void mod_switch_to(const DevicePlaintext &plain, std::size_t target_coeff_modulus_size, DevicePlaintext &destination)
+        {
+            destination = plain;
+            mod_switch_to_inplace(destination, target_coeff_modulus_size);
+        }
+        void mod_switch_to_next_inplace(DevicePlaintext &plain)
+        {
+            if (!plain.is_ntt_form())
+                throw std::invalid_argument("plain is not in NTT form"); // :963-966
+            if (plain.coeff_modulus_size() < 2)
+                throw std::invalid_argument("end of modulus switching chain reached"); // :967-970
+            mod_switch_to_inplace(plain, plain.coeff_modulus_size() - 1);
         }
         // Evaluator::transform_to_ntt(Plaintext, parms_id) (evaluator.cpp:1648-1744), BFV, with or without fast plain lift.
         // plain: coeff_count coefficients in coefficient form (Plaintext::coeff_count()); destination_ntt: k*N words, the
@@ -660,19 +1215,140 @@ namespace sealhip_host
             mod_switch_to_next_inplace(destination, is_ntt_form);
         }
         // Ciphertext::is_transparent (ciphertext.h:471-476) evaluated on the device copy
-        bool is_transparent(const CT &encrypted)
+        template <class C, IfCt<C> = 0>
+        bool is_transparent(const C &encrypted)
         {
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
-            Staged c(ctx_, size * k * n);
-            c.up(encrypted.data(), size * k * n);
+            Dev c = dev_in(encrypted, size * k * n);
             std::uint8_t flag = 0;
             throw_on(sealhip_is_transparent(ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1, &flag));
             return flag != 0;
         }
 
     private:
+        // The words of an operand on the device for one call: a host ciphertext is staged through a pool block (up, and
+        // down again for an in-place result), a resident one is its own block.
+        struct Dev
+        {
+            std::unique_ptr<Staged> st;
+            std::uint64_t *p = nullptr;
+            std::uint64_t *ptr() const { return p; }
+        };
+        Dev dev_in(const CT &c, std::size_t words)
+        {
+            Dev d;
+            d.st.reset(new Staged(ctx_, words));
+            d.st->up(c.data(), words);
+            d.p = d.st->ptr();
+            return d;
+        }
+        Dev dev_in(const DeviceCiphertext &c, std::size_t)
+        {
+            Dev d;
+            d.p = const_cast<std::uint64_t *>(c.data());
+            return d;
+        }
+        Dev dev_plain(const std::uint64_t *plain, std::size_t words, bool)
+        {
+            Dev d;
+            d.st.reset(new Staged(ctx_, words));
+            d.st->up(plain, words);
+            d.p = d.st->ptr();
+            return d;
+        }
+        Dev dev_plain(const DevicePlaintext &plain, std::size_t words, bool ntt_form)
+        {
+            if (plain.is_ntt_form() != ntt_form || plain.words() != words)
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            Dev d;
+            d.p = const_cast<std::uint64_t *>(plain.data());
+            return d;
+        }
+        Dev dev_out(std::size_t words)
+        {
+            Dev d;
+            d.st.reset(new Staged(ctx_, words));
+            d.p = d.st->ptr();
+            return d;
+        }
+        void dev_back(CT &c, Dev &d, std::size_t words) { d.st->down(c.data(), words); }
+        void dev_back(DeviceCiphertext &, Dev &, std::size_t) {}
+        // the result of `size` polynomials at level k in `o` replaces the operand's words
+        void commit(CT &c, Dev &o, std::size_t size, std::size_t k)
+        {
+            c.resize_raw(size, k);
+            o.st->down(c.data(), size * k * ctx_.n());
+        }
+        void commit(DeviceCiphertext &c, Dev &o, std::size_t size, std::size_t k)
+        {
+            const std::size_t words = o.st->words();
+            c.adopt(o.st->release(), words, size, k);
+        }
+        // the destination takes the metadata of `src` (host: as the whole object, like before)
+        void take_meta(CT &dst, const CT &src) { dst = src; }
+        void take_meta(DeviceCiphertext &dst, const DeviceCiphertext &src) { dst.copy_meta(src); }
+        // fewer polynomials at the same level, the leading words kept (relinearize)
+        void shrink(CT &c, std::size_t size) { c.resize_raw(size, c.coeff_modulus_size()); }
+        void shrink(DeviceCiphertext &c, std::size_t size) { c.set_size(size); }
+
+        // The deferred transparency check of one resident result (see the class comment): a slot of this Evaluator's ring
+        // is the lane's sink while the operation runs; none is left installed afterwards. Inert for host operands.
+        class Check
+        {
+        public:
+            Check() = default;
+            Check(const Context &c, const void *owner) : c_(&c), owner_(owner)
+            {
+                std::uint32_t *slot = c.transparency_slot(owner);
+                const long hr = sealhip_transparency_sink(c.get(), slot, 1);
+                if (hr != SEALHIP_S_OK)
+                {
+                    c.transparency_unslot(owner);
+                    c_ = nullptr;
+                    throw_on(hr);
+                }
+            }
+            Check(const Check &) = delete;
+            Check &operator=(const Check &) = delete;
+            // entries that leave the sink alone: the read pass over their result
+            void note(std::size_t k, const std::uint64_t *ct, std::size_t size)
+            {
+                if (c_)
+                    throw_on(sealhip_transparency_note(c_->get(), std::uint32_t(k), ct, std::uint32_t(size), 1));
+            }
+            void done() { ok_ = true; }
+            ~Check()
+            {
+                if (!c_)
+                    return;
+                (void)sealhip_transparency_sink(c_->get(), nullptr, 0);
+                if (!ok_)
+                    c_->transparency_unslot(owner_);
+            }
+
+        private:
+            const Context *c_ = nullptr;
+            const void *owner_ = nullptr;
+            bool ok_ = false;
+        };
+        Check checked(const CT &) { return Check(); }
+        Check checked(const DeviceCiphertext &) { return Check(ctx_, this); }
+
+        // the host checks of multiply / square (evaluator.cpp:238-249, :276-279, :449-452)
+        template <class C>
+        void check_multiply(const C &encrypted1, const C &encrypted2) const
+        {
+            check_pair(encrypted1, encrypted2);
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            if (bfv && (encrypted1.is_ntt_form() || encrypted2.is_ntt_form()))
+                throw std::invalid_argument("encrypted1 or encrypted2 cannot be in NTT form"); // :276-279
+            if (!bfv && !(encrypted1.is_ntt_form() && encrypted2.is_ntt_form()))
+                throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form"); // :449-452
+        }
+
         // conjugate_internal (evaluator.h:1343-1363): the automorphism x -> x^(2N-1), i.e. get_elt_from_step(0)
-        void conjugate_internal(CT &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
+        template <class C>
+        void conjugate_internal(C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
             std::uint32_t elt = 0;
             throw_on(sealhip_galois_elt_from_step(ctx_.get(), 0, &elt));
@@ -681,7 +1357,8 @@ namespace sealhip_host
                 throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
             apply_galois_inplace(encrypted, elt, *it->second);
         }
-        void plain_linear(CT &encrypted, const std::uint64_t *plain, bool plain_is_ntt_form, bool sub)
+        template <class C, class P>
+        void plain_linear(C &encrypted, const P &plain, bool plain_is_ntt_form, bool sub)
         {
             if (ctx_.scheme() == SEALHIP_SCHEME_BFV && encrypted.is_ntt_form())
                 throw std::invalid_argument("BFV encrypted cannot be in NTT form"); // :1304-1307
@@ -691,14 +1368,16 @@ namespace sealhip_host
                 throw std::invalid_argument("NTT form mismatch"); // :1312-1315
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
             const std::size_t pw = plain_is_ntt_form ? k * n : n;
-            Staged c(ctx_, size * k * n), p(ctx_, pw);
-            c.up(encrypted.data(), size * k * n);
-            p.up(plain, pw);
+            Dev c = dev_in(encrypted, size * k * n), p = dev_plain(plain, pw, plain_is_ntt_form);
+            Check chk = checked(encrypted); // (the entry has no sink: the read pass notes the result)
             throw_on(sealhip_evaluator_add_plain(ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1, p.ptr(), pw,
                                                  sub ? 1 : 0));
-            c.down(encrypted.data(), size * k * n);
+            chk.note(k, c.ptr(), size);
+            chk.done();
+            dev_back(encrypted, c, size * k * n);
         }
-        void add_sub(CT &a, const CT &b, bool sub)
+        template <class C>
+        void add_sub(C &a, const C &b, bool sub)
         {
             if (a.poly_modulus_degree() != ctx_.n() || b.poly_modulus_degree() != ctx_.n() || a.size() < 1 || b.size() < 1)
                 throw std::invalid_argument("encrypted1 is not valid for encryption parameters"); // :93-100
@@ -708,14 +1387,13 @@ namespace sealhip_host
                 throw std::invalid_argument("NTT form mismatch"); // :105-108
             const std::size_t k = a.coeff_modulus_size(), n = ctx_.n(), sa = a.size(), sb = b.size();
             const std::size_t so = sa > sb ? sa : sb;
-            Staged x(ctx_, sa * k * n), y(ctx_, sb * k * n), o(ctx_, so * k * n);
-            x.up(a.data(), sa * k * n);
-            y.up(b.data(), sb * k * n);
+            Dev x = dev_in(a, sa * k * n), y = dev_in(b, sb * k * n), o = dev_out(so * k * n);
+            Check chk = checked(a);
             throw_on((sub ? sealhip_evaluator_sub : sealhip_evaluator_add)(ctx_.get(), std::uint32_t(k), x.ptr(),
                                                                            std::uint32_t(sa), y.ptr(), std::uint32_t(sb), 1,
                                                                            o.ptr()));
-            a.resize_raw(so, k); // :131-132
-            o.down(a.data(), so * k * n);
+            chk.done();
+            commit(a, o, so, k); // :131-132
         }
         // is_valid_for(Plaintext) (valcheck.cpp:236-281) in coefficient form: at most N coefficients, each below t
         // (plain_modulus 0 under CKKS: no non-empty coefficient-form plaintext is valid)
@@ -735,33 +1413,38 @@ namespace sealhip_host
                 throw std::invalid_argument("plain is not valid for encryption parameters");
             return k;
         }
-        void check_pair(const CT &a, const CT &b) const
+        template <class C>
+        void check_pair(const C &a, const C &b) const
         {
             if (a.poly_modulus_degree() != ctx_.n() || b.poly_modulus_degree() != ctx_.n() || a.size() < 2 || b.size() < 2)
                 throw std::invalid_argument("encrypted1 is not valid for encryption parameters"); // :238-245
             if (a.coeff_modulus_size() != b.coeff_modulus_size())
                 throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch"); // :246-249
         }
-        void switch_level(CT &ct, bool rescale)
+        template <class C>
+        void switch_level(C &ct, bool rescale)
         {
             const std::size_t k = ct.coeff_modulus_size(), n = ctx_.n(), size = ct.size();
             if (k < 2)
                 throw std::invalid_argument("end of modulus switching chain reached"); // :1005-1008
-            Staged c(ctx_, size * k * n), o(ctx_, size * (k - 1) * n);
-            c.up(ct.data(), size * k * n);
+            Dev c = dev_in(ct, size * k * n), o = dev_out(size * (k - 1) * n);
+            Check chk = checked(ct);
             throw_on((rescale ? sealhip_evaluator_rescale_to_next : sealhip_evaluator_mod_switch_to_next)(
                 ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1, o.ptr()));
-            ct.resize_raw(size, k - 1); // :879
-            o.down(ct.data(), size * (k - 1) * n);
+            chk.done();
+            commit(ct, o, size, k - 1); // :879
         }
-        void transform(CT &ct, bool to_ntt)
+        template <class C>
+        void transform(C &ct, bool to_ntt)
         {
             const std::size_t k = ct.coeff_modulus_size(), n = ctx_.n(), size = ct.size();
-            Staged c(ctx_, size * k * n);
-            c.up(ct.data(), size * k * n);
+            Dev c = dev_in(ct, size * k * n);
+            Check chk = checked(ct); // (the transforms have no sink: the read pass notes the result)
             throw_on((to_ntt ? sealhip_evaluator_transform_to_ntt : sealhip_evaluator_transform_from_ntt)(
                 ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1));
-            c.down(ct.data(), size * k * n);
+            chk.note(k, c.ptr(), size);
+            chk.done();
+            dev_back(ct, c, size * k * n);
         }
         const Context &ctx_;
     };
@@ -778,7 +1461,8 @@ namespace sealhip_host
             : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n())
         {}
 
-        // decrypt (:51-75)
+        // decrypt (:51-75). The DeviceCiphertext overloads read the resident words in place (no upload) and are a
+        // host-visible point of the Evaluator's deferred transparency check.
         void decrypt(const CT &encrypted, std::vector<std::uint64_t> &destination)
         {
             std::vector<std::vector<std::uint64_t>> out;
@@ -787,8 +1471,40 @@ namespace sealhip_host
         }
         void decrypt(const std::vector<const CT *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
         {
+            decrypt_impl(encrypted, destination);
+        }
+        void decrypt(const DeviceCiphertext &encrypted, std::vector<std::uint64_t> &destination)
+        {
+            std::vector<std::vector<std::uint64_t>> out;
+            decrypt_impl(std::vector<const DeviceCiphertext *>{ &encrypted }, out);
+            destination.swap(out[0]);
+        }
+        void decrypt(const std::vector<const DeviceCiphertext *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
+        {
+            decrypt_impl(encrypted, destination);
+        }
+
+        // invariant_noise_budget (:269-325)
+        int invariant_noise_budget(const CT &encrypted)
+        {
+            return invariant_noise_budget(std::vector<const CT *>{ &encrypted })[0];
+        }
+        std::vector<int> invariant_noise_budget(const std::vector<const CT *> &encrypted) { return budget_impl(encrypted); }
+        int invariant_noise_budget(const DeviceCiphertext &encrypted)
+        {
+            return budget_impl(std::vector<const DeviceCiphertext *>{ &encrypted })[0];
+        }
+        std::vector<int> invariant_noise_budget(const std::vector<const DeviceCiphertext *> &encrypted)
+        {
+            return budget_impl(encrypted);
+        }
+
+    private:
+        template <class C>
+        void decrypt_impl(const std::vector<const C *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
+        {
             const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            for (const CT *ct : encrypted)
+            for (const C *ct : encrypted)
             {
                 check_valid(*ct);
                 if (bfv && ct->is_ntt_form())
@@ -819,14 +1535,10 @@ namespace sealhip_host
             });
         }
 
-        // invariant_noise_budget (:269-325)
-        int invariant_noise_budget(const CT &encrypted)
+        template <class C>
+        std::vector<int> budget_impl(const std::vector<const C *> &encrypted)
         {
-            return invariant_noise_budget(std::vector<const CT *>{ &encrypted })[0];
-        }
-        std::vector<int> invariant_noise_budget(const std::vector<const CT *> &encrypted)
-        {
-            for (const CT *ct : encrypted)
+            for (const C *ct : encrypted)
             {
                 check_valid(*ct);
                 if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
@@ -845,9 +1557,9 @@ namespace sealhip_host
             return out;
         }
 
-    private:
         // is_valid_for (valcheck.cpp), the metadata the ABI cannot see
-        void check_valid(const CT &ct) const
+        template <class C>
+        void check_valid(const C &ct) const
         {
             if (ct.size() < 2 || ct.size() > 16 || ct.coeff_modulus_size() < 1 || ct.coeff_modulus_size() > ctx_.n_key() ||
                 ct.poly_modulus_degree() != ctx_.n())
@@ -872,6 +1584,18 @@ namespace sealhip_host
             return powers_->ptr();
         }
 
+        // resident ciphertexts: each is its own run, read in place
+        template <class F>
+        void for_runs(const std::vector<const DeviceCiphertext *> &encrypted, F &&body)
+        {
+            ctx_.check_transparency();
+            for (std::size_t i = 0; i < encrypted.size(); i++)
+            {
+                const DeviceCiphertext &c = *encrypted[i];
+                const std::uint64_t *pw = powers(c.size() - 1);
+                body(i, 1, c.coeff_modulus_size(), c.size(), c.data(), pw);
+            }
+        }
         // calls body(first, count, k, size, device ciphertexts, device powers) for each run of equal level and size
         template <class F>
         void for_runs(const std::vector<const CT *> &encrypted, F &&body)
@@ -939,10 +1663,36 @@ namespace sealhip_host
         void set_public_key(const std::uint64_t *public_key)
         {
             pk_.assign(public_key, public_key + 2 * ctx_.n_key() * ctx_.n());
+            dpk_.reset();
         }
         void set_secret_key(const std::uint64_t *secret_key_ntt)
         {
             sk_.assign(secret_key_ntt, secret_key_ntt + ctx_.n_key() * ctx_.n());
+            dsk_.reset();
+        }
+
+        // the same into resident ciphertexts: the words stay on the device (the samples still come from the samplers)
+        void encrypt(const HostPlaintext &plain, DeviceCiphertext &destination)
+        {
+            std::vector<DeviceCiphertext *> d{ &destination };
+            run(true, std::vector<const HostPlaintext *>{ &plain }, d, 0, false);
+        }
+        void encrypt_zero(DeviceCiphertext &destination) { encrypt_zero(k_first_, destination); }
+        void encrypt_zero(std::size_t k, DeviceCiphertext &destination)
+        {
+            std::vector<DeviceCiphertext *> d{ &destination };
+            run(true, {}, d, k, false);
+        }
+        void encrypt_symmetric(const HostPlaintext &plain, DeviceCiphertext &destination)
+        {
+            std::vector<DeviceCiphertext *> d{ &destination };
+            run(false, std::vector<const HostPlaintext *>{ &plain }, d, 0, false);
+        }
+        void encrypt_zero_symmetric(DeviceCiphertext &destination) { encrypt_zero_symmetric(k_first_, destination); }
+        void encrypt_zero_symmetric(std::size_t k, DeviceCiphertext &destination)
+        {
+            std::vector<DeviceCiphertext *> d{ &destination };
+            run(false, {}, d, k, false);
         }
 
         // encrypt (:205-253) / encrypt_zero() at the first level / encrypt_zero(parms_id) at level k
@@ -1013,7 +1763,40 @@ namespace sealhip_host
         }
 
         // one device call per run of plaintexts of equal level (plain empty: destination.size() zero encryptions at k)
-        void run(bool asymmetric, const std::vector<const HostPlaintext *> &plain, std::vector<CT *> &destination,
+        // the key on the device, uploaded once and kept across calls
+        const std::uint64_t *device_key(bool asymmetric)
+        {
+            const std::size_t words = (asymmetric ? 2 : 1) * ctx_.n_key() * ctx_.n();
+            std::unique_ptr<Staged> &key = asymmetric ? dpk_ : dsk_;
+            if (!key)
+            {
+                std::unique_ptr<Staged> up(new Staged(ctx_, words));
+                up->up(asymmetric ? pk_.data() : sk_.data(), words);
+                key = std::move(up);
+            }
+            return key->ptr();
+        }
+        // item i of the `count` encryptions in `ct` becomes the destination's words
+        void deliver(CT &d, Staged &ct, std::size_t i, std::size_t count, std::size_t words, std::size_t k)
+        {
+            (void)count;
+            d.resize_raw(2, k);
+            throw_on(sealhip_memcpy_d2h(ctx_.get(), d.data(), ct.ptr() + i * words, words * 8));
+        }
+        void deliver(DeviceCiphertext &d, Staged &ct, std::size_t i, std::size_t count, std::size_t words, std::size_t k)
+        {
+            if (count == 1) // the block itself changes owner
+            {
+                d.adopt(ct.release(), ct.words(), 2, k);
+                return;
+            }
+            Staged one(ctx_, words);
+            throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), ct.ptr() + i * words, words * 8));
+            d.adopt(one.release(), words, 2, k);
+        }
+
+        template <class D>
+        void run(bool asymmetric, const std::vector<const HostPlaintext *> &plain, std::vector<D *> &destination,
                  std::size_t k_zero, bool save_seed, std::vector<std::uint64_t> *seeds_out = nullptr)
         {
             check_keys(asymmetric);
@@ -1025,10 +1808,9 @@ namespace sealhip_host
             std::vector<std::size_t> level(destination.size(), k_zero);
             for (std::size_t i = 0; !zero && i < plain.size(); i++)
                 level[i] = check_plain(*plain[i]);
-            const std::size_t n = ctx_.n(), nk = ctx_.n_key();
+            const std::size_t n = ctx_.n();
             const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            std::unique_ptr<Staged> key(new Staged(ctx_, (asymmetric ? 2 : 1) * nk * n));
-            key->up(asymmetric ? pk_.data() : sk_.data(), (asymmetric ? 2 : 1) * nk * n);
+            const std::uint64_t *key = device_key(asymmetric);
             for (std::size_t first = 0; first < destination.size();)
             {
                 const std::size_t k = level[first];
@@ -1052,7 +1834,7 @@ namespace sealhip_host
                     Staged du(ctx_, (u.size() + 1) / 2), de(ctx_, (e.size() + 1) / 2);
                     throw_on(sealhip_memcpy_h2d(ctx_.get(), du.ptr(), u.data(), u.size() * 4));
                     throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
-                    throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key->ptr(), dp ? dp->ptr() : nullptr, pw,
+                    throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key, dp ? dp->ptr() : nullptr, pw,
                                                        reinterpret_cast<const std::int32_t *>(du.ptr()),
                                                        reinterpret_cast<const std::int32_t *>(de.ptr()), count, ct.ptr()));
                 }
@@ -1064,7 +1846,7 @@ namespace sealhip_host
                         sym_(seeds.data() + 8 * i, e.data() + i * n);
                     Staged de(ctx_, (e.size() + 1) / 2);
                     throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
-                    throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key->ptr(),
+                    throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key,
                                                                  dp ? dp->ptr() : nullptr, pw, seeds.data(),
                                                                  reinterpret_cast<const std::int32_t *>(de.ptr()),
                                                                  save_seed ? 1 : 0, count, ct.ptr()));
@@ -1073,9 +1855,8 @@ namespace sealhip_host
                 }
                 for (std::size_t i = 0; i < count; i++)
                 {
-                    CT &d = *destination[first + i];
-                    d.resize_raw(2, k);
-                    throw_on(sealhip_memcpy_d2h(ctx_.get(), d.data(), ct.ptr() + i * words, words * 8));
+                    D &d = *destination[first + i];
+                    deliver(d, ct, i, count, words, k);
                     d.is_ntt_form() = !bfv;
                     // encrypt_zero_* set 1.0; CKKS encrypt takes the plaintext's scale (:252)
                     d.scale() = (!zero && !bfv) ? plain[first + i]->scale : 1.0;
@@ -1122,6 +1903,7 @@ namespace sealhip_host
 
         const Context &ctx_;
         std::vector<std::uint64_t> pk_, sk_;
+        std::unique_ptr<Staged> dpk_, dsk_; // the keys on the device (device_key)
         AsymSampler asym_;
         SymSampler sym_;
         std::size_t k_first_ = 0;

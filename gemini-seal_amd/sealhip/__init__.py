@@ -172,7 +172,19 @@ SYMBOLS = {
     "sealhip_ckks_decode": [_vp, _u32, _vp, _sz, C.c_double, _vp],
     "sealhip_ckks_encode_value": [_vp, _u32, C.c_double, C.c_double, _sz, _vp],
     "sealhip_ckks_encode_int64": [_vp, _u32, C.c_int64, _sz, _vp],
+    "sealhip_pool_alloc": [_vp, _sz, C.POINTER(_vp)],
+    "sealhip_pool_release": [_vp, _vp],
+    "sealhip_pool_trim": [_vp],
+    "sealhip_pool_stats": [_vp, _vp],
+    "sealhip_memcpy_d2d": [_vp, _vp, _vp, _sz],
+    "sealhip_transparency_note": [_vp, _u32, _vp, _u32, _sz],
 }
+
+
+class PoolStats(C.Structure):
+    """struct sealhip_pool_stats"""
+    _fields_ = [("bytes_in_use", C.c_uint64), ("bytes_cached", C.c_uint64), ("device_mallocs", C.c_uint64),
+                ("device_frees", C.c_uint64), ("hits", C.c_uint64), ("misses", C.c_uint64), ("cross_lane_hits", C.c_uint64)]
 
 
 class CiphertextInfo(C.Structure):
@@ -273,6 +285,22 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class PoolBuffer(DeviceBuffer):
+    """uint64 words in a block of the context's pool (sealhip_pool_alloc); free() releases it to the pool, stream-ordered
+    on the calling thread's lane"""
+
+    def __init__(self, ctx, words):
+        self.ctx, self.words = ctx, int(words)
+        p = C.c_void_p()
+        _check(lib().sealhip_pool_alloc(ctx.handle, self.words * 8, C.byref(p)))
+        self.ptr = p.value
+
+    def free(self):
+        if self.ptr:
+            ptr, self.ptr = self.ptr, None
+            _check(lib().sealhip_pool_release(self.ctx.handle, ptr))
 
 
 class KSwitchKeys:
@@ -393,6 +421,31 @@ class Context:
 
     def synchronize(self):
         _check(lib().sealhip_synchronize(self.handle))
+
+    # -- pooled device memory (include/sealhip.h, sealhip_pool_*)
+    def pool_alloc(self, words):
+        """a PoolBuffer of `words` uint64 words; its free() releases the block to the pool"""
+        return PoolBuffer(self, words)
+
+    def pool_release(self, ptr):
+        _check(lib().sealhip_pool_release(self.handle, _ptr(ptr)))
+
+    def pool_trim(self):
+        _check(lib().sealhip_pool_trim(self.handle))
+
+    def pool_stats(self):
+        """{bytes_in_use, bytes_cached, device_mallocs, device_frees, hits, misses, cross_lane_hits}"""
+        st = PoolStats()
+        _check(lib().sealhip_pool_stats(self.handle, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in PoolStats._fields_}
+
+    def memcpy_d2d(self, dst, src, words):
+        """stream-ordered device-to-device copy of `words` uint64 words"""
+        _check(lib().sealhip_memcpy_d2d(self.handle, _ptr(dst), _ptr(src), int(words) * 8))
+
+    def transparency_note(self, k, ct, size, count):
+        """the transparency read pass over `count` ciphertexts into the installed sink (sealhip_transparency_note)"""
+        _check(lib().sealhip_transparency_note(self.handle, k, _ptr(ct), size, count))
 
     def set_stream(self, stream_ptr):
         """hipStream_t of the calling thread's lane (None/0: back to a private stream)"""

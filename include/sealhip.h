@@ -100,6 +100,43 @@ long sealhip_free(sealhip_context *ctx, void *dptr);
 long sealhip_memcpy_h2d(sealhip_context *ctx, void *dst_dev, const void *src_host, size_t bytes);
 long sealhip_memcpy_d2h(sealhip_context *ctx, void *dst_host, const void *src_dev, size_t bytes);
 
+/* Pooled, stream-ordered device memory. Blocks come from slabs the pool allocates with hipMalloc (never from
+   hipMallocAsync / hipMemPool) and are cached after release instead of being freed.
+   - Size classes: a request is rounded up to a multiple of 256 bytes, then to the next m * 2^e with m in {4, 5, 6, 7}
+     (four classes per doubling), so a block is less than 25 % larger than the rounded request. 1 byte .. 2^46 bytes.
+   - Every lane (calling thread) keeps its own free lists, one per size class. sealhip_pool_release is stream-ordered on
+     the calling thread's lane: it never synchronises and never calls hipFree. A later sealhip_pool_alloc on the same
+     lane reuses the block with no wait; one on another lane makes its stream wait (hipStreamWaitEvent, no host block) on
+     an event recorded at the release. The threading rule above still holds for the words of a block: hand them to
+     another thread only after sealhip_synchronize().
+   - A miss calls hipMalloc; when the device is out of memory the lane's cached blocks are freed once and the allocation
+     retried, then SEALHIP_E_OUTOFMEMORY. A miss during a graph capture is COR_E_INVALIDOPERATION (run the sequence once
+     before capturing); the capture is discarded. So is a release during a capture (the graph would keep using the block).
+   - Releasing a pointer the pool did not hand out, or releasing it twice, is E_INVALIDARG and frees nothing.
+   - sealhip_pool_trim synchronises the context and hipFree's every cached block; sealhip_context_destroy frees every
+     block, held ones included. sealhip_pool_stats reports the counters (zeros on a host-only context). */
+struct sealhip_pool_stats
+{
+    uint64_t bytes_in_use;    /* size classes of the blocks handed out and not released            */
+    uint64_t bytes_cached;    /* size classes of the blocks on the free lists                        */
+    uint64_t device_mallocs;  /* hipMalloc calls the pool made                                        */
+    uint64_t device_frees;    /* hipFree calls the pool made (trim, out-of-memory retry)             */
+    uint64_t hits;            /* allocations served from a free list (either lane)                   */
+    uint64_t misses;          /* allocations that called hipMalloc                                   */
+    uint64_t cross_lane_hits; /* hits on a block another lane released (the ones that wait an event)  */
+};
+long sealhip_pool_alloc(sealhip_context *ctx, size_t bytes, void **dptr);
+long sealhip_pool_release(sealhip_context *ctx, void *dptr);
+long sealhip_pool_trim(sealhip_context *ctx);
+long sealhip_pool_stats(sealhip_context *ctx, struct sealhip_pool_stats *out);
+/* stream-ordered device-to-device copy on the calling thread's lane; does not synchronise */
+long sealhip_memcpy_d2d(sealhip_context *ctx, void *dst_dev, const void *src_dev, size_t bytes);
+/* The transparency read pass of the sink-capable entries (sealhip_transparency_sink) on `count` ciphertexts of `size`
+   polynomials at level k, into the installed sink, stream-ordered. The composite entries (multiply_many, exponentiate) and
+   the entries without a sink (add_plain, transform_to_ntt / _from_ntt) leave the flags alone; a caller that wants their
+   results' flags calls this after them. No sink installed: nothing is done. */
+long sealhip_transparency_note(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count);
+
 /* Per-kernel timing with HIP events recorded on the launch stream. While enabled every kernel launch of
    the engine is bracketed by two events; sealhip_profile_fetch synchronises the stream, writes a JSON
    object {"<kernel tag>": {"launches": n, "ms": total, "units": u}, ...} (NUL-terminated) into `json`,
