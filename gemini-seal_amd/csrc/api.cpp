@@ -179,12 +179,6 @@ namespace
             throw std::invalid_argument("level k out of range");
     }
 
-    void check_launch(hipError_t err, const char *what)
-    {
-        if (err != hipSuccess)
-            throw HipError(err, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
-    }
-
     void ntt_entry(sealhip_context *ctx, uint64_t *data, size_t count, uint32_t k, uint32_t base, bool inverse,
                    int flags)
     {
@@ -193,7 +187,7 @@ namespace
         if (base == SEALHIP_BASE_BSK || base == SEALHIP_BASE_KEY)
             (void)e.level(static_cast<int>(k));
         const RowMap map = e.map_for(static_cast<int>(k), base);
-        check_launch(launch_ntt(e, reinterpret_cast<u64 *>(data), count * map.rows, map, inverse, flags), "ntt");
+        check(launch_ntt(e, reinterpret_cast<u64 *>(data), count * map.rows, map, inverse, flags), "ntt");
     }
 
     void poly_entry(sealhip_context *ctx, PolyOp op, const uint64_t *a, const uint64_t *b, uint64_t scalar,
@@ -202,9 +196,9 @@ namespace
         Engine &e = device_engine(ctx);
         check_level(e, k);
         const RowMap map = e.map_for(static_cast<int>(k), base);
-        check_launch(launch_poly_op(e, op, reinterpret_cast<const u64 *>(a), reinterpret_cast<const u64 *>(b), scalar,
-                                    reinterpret_cast<u64 *>(r), count * map.rows, map),
-                     "poly op");
+        check(launch_poly_op(e, op, reinterpret_cast<const u64 *>(a), reinterpret_cast<const u64 *>(b), scalar,
+                             reinterpret_cast<u64 *>(r), count * map.rows, map),
+              "poly op");
     }
 
     // GaloisTool::get_elt_from_step (galois.cpp:49-91), generator 5 (util/galois.h:169)
@@ -719,9 +713,9 @@ long sealhip_fastbconv_m_tilde(sealhip_context *ctx, uint32_t k, const uint64_t 
     return guarded([&] {
         Engine &e = device_engine(ctx);
         LevelTools &lt = bfv_level(e, k);
-        check_launch(launch_fastbconv_m_tilde(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), k * e.n,
-                                              reinterpret_cast<u64 *>(out), (lt.h_rns.nB + 1) * e.n, count),
-                     "fastbconv_m_tilde");
+        check(launch_fastbconv_m_tilde(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), k * e.n,
+                                       reinterpret_cast<u64 *>(out), (lt.h_rns.nB + 1) * e.n, count),
+              "fastbconv_m_tilde");
     });
 }
 long sealhip_sm_mrq(sealhip_context *ctx, uint32_t k, const uint64_t *in, size_t count, uint64_t *out)
@@ -732,9 +726,9 @@ long sealhip_sm_mrq(sealhip_context *ctx, uint32_t k, const uint64_t *in, size_t
     return guarded([&] {
         Engine &e = device_engine(ctx);
         LevelTools &lt = bfv_level(e, k);
-        check_launch(launch_sm_mrq(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), (lt.h_rns.nB + 1) * e.n,
-                                   reinterpret_cast<u64 *>(out), lt.h_rns.nB * e.n, count),
-                     "sm_mrq");
+        check(launch_sm_mrq(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), (lt.h_rns.nB + 1) * e.n,
+                            reinterpret_cast<u64 *>(out), lt.h_rns.nB * e.n, count),
+              "sm_mrq");
     });
 }
 long sealhip_fast_floor(sealhip_context *ctx, uint32_t k, const uint64_t *in, size_t count, uint64_t *out)
@@ -745,10 +739,10 @@ long sealhip_fast_floor(sealhip_context *ctx, uint32_t k, const uint64_t *in, si
     return guarded([&] {
         Engine &e = device_engine(ctx);
         LevelTools &lt = bfv_level(e, k);
-        check_launch(launch_fast_floor(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in),
-                                       (k + lt.h_rns.nB) * e.n, reinterpret_cast<u64 *>(out), lt.h_rns.nB * e.n, count,
-                                       0),
-                     "fast_floor");
+        check(launch_fast_floor(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in),
+                                (k + lt.h_rns.nB) * e.n, reinterpret_cast<u64 *>(out), lt.h_rns.nB * e.n, count,
+                                0),
+              "fast_floor");
     });
 }
 long sealhip_fastbconv_sk(sealhip_context *ctx, uint32_t k, const uint64_t *in, size_t count, uint64_t *out)
@@ -759,9 +753,9 @@ long sealhip_fastbconv_sk(sealhip_context *ctx, uint32_t k, const uint64_t *in, 
     return guarded([&] {
         Engine &e = device_engine(ctx);
         LevelTools &lt = bfv_level(e, k);
-        check_launch(launch_fastbconv_sk(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), lt.h_rns.nB * e.n,
-                                         reinterpret_cast<u64 *>(out), k * e.n, count),
-                     "fastbconv_sk");
+        check(launch_fastbconv_sk(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in), lt.h_rns.nB * e.n,
+                                  reinterpret_cast<u64 *>(out), k * e.n, count),
+              "fastbconv_sk");
     });
 }
 long sealhip_divide_and_round_q_last_inplace(sealhip_context *ctx, uint32_t k, uint64_t *data, size_t count)
@@ -775,8 +769,8 @@ long sealhip_divide_and_round_q_last_inplace(sealhip_context *ctx, uint32_t k, u
             throw std::invalid_argument("divide_and_round_q_last needs at least two primes");
         LevelTools &lt = e.level(static_cast<int>(k));
         u64 *p = reinterpret_cast<u64 *>(data);
-        check_launch(launch_divround_bfv(e, lt.d_rns, lt.h_rns, p, k * e.n, p, k * e.n, count, static_cast<int>(k)),
-                     "divide_and_round_q_last");
+        check(launch_divround_bfv(e, lt.d_rns, lt.h_rns, p, k * e.n, p, k * e.n, count, static_cast<int>(k)),
+              "divide_and_round_q_last");
     });
 }
 long sealhip_divide_and_round_q_last_ntt_inplace(sealhip_context *ctx, uint32_t k, uint64_t *data, size_t count)
@@ -815,9 +809,9 @@ static long galois_entry(sealhip_context *ctx, const uint64_t *in, size_t count,
             throw std::invalid_argument("Galois element is not valid");
         const RowMap map = e.map_for(static_cast<int>(k), SEALHIP_BASE_Q);
         const uint32_t *table = ntt_form ? e.galois_table(galois_elt) : nullptr;
-        check_launch(launch_galois(e, reinterpret_cast<const u64 *>(in), reinterpret_cast<u64 *>(out), count * k, map,
-                                   galois_elt, table),
-                     "apply_galois");
+        check(launch_galois(e, reinterpret_cast<const u64 *>(in), reinterpret_cast<u64 *>(out), count * k, map,
+                            galois_elt, table),
+              "apply_galois");
     });
 }
 long sealhip_apply_galois(sealhip_context *ctx, const uint64_t *in, size_t count, uint32_t k, uint32_t galois_elt,
@@ -1009,7 +1003,7 @@ namespace
         {
             clear();
             if (on && size >= 2 && n)
-                check_launch(launch_nonzero_tail(e, result, poly_words * size, poly_words, n, l.tsink), "transparency");
+                check(launch_nonzero_tail(e, result, poly_words * size, poly_words, n, l.tsink), "transparency");
         }
         ~SinkScope()
         {
@@ -1119,12 +1113,12 @@ namespace
             op_mod_switch_scale(e, static_cast<int>(k), in, static_cast<int>(size), count, o, item_stride);
         else if (item_stride == 0 || item_stride == size * in_poly)
             // mod_switch_drop_to_next (evaluator.cpp:894-957): keep the first k-1 rows of every polynomial
-            check_launch(launch_copy_rows(e, in, in_poly, o, out_poly, count * size, static_cast<int>(k - 1)), "mod_switch_drop");
+            check(launch_copy_rows(e, in, in_poly, o, out_poly, count * size, static_cast<int>(k - 1)), "mod_switch_drop");
         else
             for (uint32_t comp = 0; comp < size; comp++)
-                check_launch(launch_copy_rows(e, in + comp * in_poly, item_stride, o + comp * out_poly, size * out_poly, count,
-                                              static_cast<int>(k - 1)),
-                             "mod_switch_drop");
+                check(launch_copy_rows(e, in + comp * in_poly, item_stride, o + comp * out_poly, size * out_poly, count,
+                                       static_cast<int>(k - 1)),
+                      "mod_switch_drop");
     }
 } // namespace
 
@@ -1236,9 +1230,9 @@ namespace
             // (multiply(x, x) and square(x) give the same canonical residues, :1228-1235)
             do_multiply(e, k, a, 2, b, 2, count, static_cast<u64 *>(wide));
             do_relinearize(e, k, static_cast<u64 *>(wide), 3, count, relin_keys, n_relin_keys);
-            check_launch(launch_copy_rows(e, static_cast<u64 *>(wide), 3 * poly, static_cast<u64 *>(narrow), 2 * poly, count,
-                                          static_cast<int>(2 * k)),
-                         "resize");
+            check(launch_copy_rows(e, static_cast<u64 *>(wide), 3 * poly, static_cast<u64 *>(narrow), 2 * poly, count,
+                                   static_cast<int>(2 * k)),
+                  "resize");
             return static_cast<const u64 *>(narrow);
         };
         std::vector<const u64 *> queue;
@@ -1320,7 +1314,7 @@ long sealhip_evaluator_multiply_host(sealhip_context *ctx, uint32_t k, const uin
                 return do_multiply(en, k, d_in[0], size_a, d_in[1], size_b, m, d_out[0]);
             do_multiply(en, k, d_in[0], size_a, d_in[1], size_b, m, tmp);
             do_relinearize(en, k, tmp, dest, m, relin_keys, n_relin_keys);
-            check_launch(launch_copy_rows(en, tmp, dest * poly, d_out[0], 2 * poly, m, static_cast<int>(2 * k)), "resize"); // :819
+            check(launch_copy_rows(en, tmp, dest * poly, d_out[0], 2 * poly, m, static_cast<int>(2 * k)), "resize"); // :819
         });
     });
 }
@@ -1345,7 +1339,7 @@ long sealhip_evaluator_relinearize_host(sealhip_context *ctx, uint32_t k, uint64
         run_host_batch(e, io, count, [&](Engine &en, const std::vector<u64 *> &d_in, const std::vector<u64 *> &d_out, u64 *,
                                          std::size_t m) {
             do_relinearize(en, k, d_in[0], size, m, relin_keys, n_relin_keys);
-            check_launch(launch_copy_rows(en, d_in[0], size * poly, d_out[0], 2 * poly, m, static_cast<int>(2 * k)), "resize");
+            check(launch_copy_rows(en, d_in[0], size * poly, d_out[0], 2 * poly, m, static_cast<int>(2 * k)), "resize");
         });
     });
 }
@@ -1526,10 +1520,10 @@ long sealhip_evaluator_negate(sealhip_context *ctx, uint32_t k, const uint64_t *
         if (size < 1)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         SinkScope sink(e, count);
-        check_launch(launch_ct_linear(e, CtLinearOp::Negate, reinterpret_cast<const u64 *>(ct), static_cast<int>(size),
-                                      nullptr, 0, 0, reinterpret_cast<u64 *>(out), count,
-                                      e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
-                     "negate");
+        check(launch_ct_linear(e, CtLinearOp::Negate, reinterpret_cast<const u64 *>(ct), static_cast<int>(size),
+                               nullptr, 0, 0, reinterpret_cast<u64 *>(out), count,
+                               e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
+              "negate");
         sink.read_pass(reinterpret_cast<const u64 *>(out), size, static_cast<std::size_t>(k) * e.n, count);
     });
 }
@@ -1551,10 +1545,10 @@ static long add_sub_entry(sealhip_context *ctx, uint32_t k, const uint64_t *a, u
         if (out == a && size_b > size_a)
             throw std::invalid_argument("in-place result needs a destination of max(size_a, size_b) polynomials");
         SinkScope sink(e, count);
-        check_launch(launch_ct_linear(e, sub ? CtLinearOp::Sub : CtLinearOp::Add, reinterpret_cast<const u64 *>(a),
-                                      static_cast<int>(size_a), reinterpret_cast<const u64 *>(b), static_cast<int>(size_b), 0,
-                                      reinterpret_cast<u64 *>(out), count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
-                     sub ? "sub" : "add");
+        check(launch_ct_linear(e, sub ? CtLinearOp::Sub : CtLinearOp::Add, reinterpret_cast<const u64 *>(a),
+                               static_cast<int>(size_a), reinterpret_cast<const u64 *>(b), static_cast<int>(size_b), 0,
+                               reinterpret_cast<u64 *>(out), count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
+              sub ? "sub" : "add");
         sink.read_pass(reinterpret_cast<const u64 *>(out), std::max(size_a, size_b), static_cast<std::size_t>(k) * e.n, count);
     });
 }
@@ -1585,10 +1579,10 @@ long sealhip_evaluator_multiply_plain_ntt(sealhip_context *ctx, uint32_t k, uint
         if (plain_stride != 0 && plain_stride < static_cast<size_t>(k) * e.n)
             throw std::invalid_argument("plain_stride is smaller than one plaintext");
         SinkScope sink(e, count); // (capacity checked before ct is overwritten)
-        check_launch(launch_ct_linear(e, CtLinearOp::MulPlain, reinterpret_cast<const u64 *>(ct), static_cast<int>(size),
-                                      reinterpret_cast<const u64 *>(plain_ntt), 0, plain_stride, reinterpret_cast<u64 *>(ct),
-                                      count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
-                     "multiply_plain_ntt");
+        check(launch_ct_linear(e, CtLinearOp::MulPlain, reinterpret_cast<const u64 *>(ct), static_cast<int>(size),
+                               reinterpret_cast<const u64 *>(plain_ntt), 0, plain_stride, reinterpret_cast<u64 *>(ct),
+                               count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)),
+              "multiply_plain_ntt");
         sink.read_pass(reinterpret_cast<const u64 *>(ct), size, static_cast<std::size_t>(k) * e.n, count);
     });
 }
@@ -1658,10 +1652,10 @@ long sealhip_evaluator_mod_switch_plain_to(sealhip_context *ctx, uint32_t k_from
             throw std::invalid_argument("plain and out overlap");
         Engine &e = device_engine(ctx);
         // mod_switch_drop_to_next (evaluator.cpp:959-994) per level: Plaintext::resize keeps the leading rows
-        check_launch(launch_copy_rows(e, reinterpret_cast<const u64 *>(plain), static_cast<std::size_t>(k_from) * e.n,
-                                      reinterpret_cast<u64 *>(out), static_cast<std::size_t>(k_to) * e.n, count,
-                                      static_cast<int>(k_to)),
-                     "mod_switch_plain");
+        check(launch_copy_rows(e, reinterpret_cast<const u64 *>(plain), static_cast<std::size_t>(k_from) * e.n,
+                               reinterpret_cast<u64 *>(out), static_cast<std::size_t>(k_to) * e.n, count,
+                               static_cast<int>(k_to)),
+              "mod_switch_plain");
     });
 }
 
@@ -1715,8 +1709,8 @@ long sealhip_is_transparent(sealhip_context *ctx, uint32_t k, const uint64_t *ct
         e.ws_reset();
         unsigned *flags = reinterpret_cast<unsigned *>(e.ws_alloc((count * sizeof(unsigned) + 7) / 8));
         SEALHIP_CHECK(hipMemsetAsync(flags, 0, count * sizeof(unsigned), e.lane().stream));
-        check_launch(launch_nonzero_tail(e, reinterpret_cast<const u64 *>(ct), poly_words * size, poly_words, count, flags),
-                     "is_transparent");
+        check(launch_nonzero_tail(e, reinterpret_cast<const u64 *>(ct), poly_words * size, poly_words, count, flags),
+              "is_transparent");
         std::vector<unsigned> host(count);
         SEALHIP_CHECK(hipMemcpyAsync(host.data(), flags, count * sizeof(unsigned), hipMemcpyDeviceToHost, e.lane().stream));
         e.sync_and_check();
@@ -1782,9 +1776,9 @@ long sealhip_decrypt_scale_and_round(sealhip_context *ctx, uint32_t k, const uin
     return guarded([&] {
         Engine &e = device_engine(ctx);
         LevelTools &lt = bfv_level(e, k);
-        check_launch(launch_decrypt_scale_and_round(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in),
-                                                    reinterpret_cast<u64 *>(out), count),
-                     "decrypt_scale_and_round");
+        check(launch_decrypt_scale_and_round(e, lt.d_rns, lt.h_rns, reinterpret_cast<const u64 *>(in),
+                                             reinterpret_cast<u64 *>(out), count),
+              "decrypt_scale_and_round");
     });
 }
 
@@ -2054,15 +2048,15 @@ long sealhip_evaluator_add_plain(sealhip_context *ctx, uint32_t k, uint64_t *ct,
         if (plain_item_stride == static_cast<std::size_t>(k) * e.n)
         {
             // a batch of plaintexts laid out back to back is a batch of size-1 operands of add/sub (evaluator.cpp:131-143)
-            check_launch(launch_ct_linear(e, subtract ? CtLinearOp::Sub : CtLinearOp::Add, c, static_cast<int>(size), p, 1, 0, c,
-                                          count, map),
-                         "add_plain");
+            check(launch_ct_linear(e, subtract ? CtLinearOp::Sub : CtLinearOp::Add, c, static_cast<int>(size), p, 1, 0, c,
+                                   count, map),
+                  "add_plain");
             return;
         }
         for (std::size_t i = 0; i < count; i++)
-            check_launch(launch_poly_op(e, subtract ? PolyOp::Sub : PolyOp::Add, c + i * item, p + i * plain_item_stride, 0,
-                                        c + i * item, k, map),
-                         "add_plain");
+            check(launch_poly_op(e, subtract ? PolyOp::Sub : PolyOp::Add, c + i * item, p + i * plain_item_stride, 0,
+                                 c + i * item, k, map),
+                  "add_plain");
     });
 }
 
@@ -2183,7 +2177,7 @@ long sealhip_ckks_encode_value(sealhip_context *ctx, uint32_t k, double value, d
             }
             rows[j] = is_negative ? (r ? q - r : 0) : r; // negate_uint_mod, :137-140
         }
-        check_launch(launch_fill_rows(e, reinterpret_cast<u64 *>(plain), rows, static_cast<int>(k), count), "ckks encode value");
+        check(launch_fill_rows(e, reinterpret_cast<u64 *>(plain), rows, static_cast<int>(k), count), "ckks encode value");
     });
 }
 
@@ -2210,7 +2204,7 @@ long sealhip_ckks_encode_int64(sealhip_context *ctx, uint32_t k, int64_t value, 
                 tmp += q; // :254-257 (wrapping, as written there)
             rows[j] = tmp % q;
         }
-        check_launch(launch_fill_rows(e, reinterpret_cast<u64 *>(plain), rows, static_cast<int>(k), count), "ckks encode int64");
+        check(launch_fill_rows(e, reinterpret_cast<u64 *>(plain), rows, static_cast<int>(k), count), "ckks encode int64");
     });
 }
 
@@ -2245,9 +2239,9 @@ long sealhip_ciphertext_resize(sealhip_context *ctx, uint32_t k, const uint64_t 
         if (dst_size > keep)
             SEALHIP_CHECK(hipMemsetAsync(d, 0, count * dst_size * poly * sizeof(u64), e.lane().stream));
         if (keep)
-            check_launch(launch_copy_rows(e, reinterpret_cast<const u64 *>(src), src_size * poly, d, dst_size * poly, count,
-                                          static_cast<int>(keep * k)),
-                         "resize");
+            check(launch_copy_rows(e, reinterpret_cast<const u64 *>(src), src_size * poly, d, dst_size * poly, count,
+                                   static_cast<int>(keep * k)),
+                  "resize");
     });
 }
 
@@ -2559,17 +2553,14 @@ long sealhip_is_data_valid_for(sealhip_context *ctx, uint32_t k, const uint64_t 
         check_level(e, k);
         if (count == 0)
             return;
-        RowMap map{};
-        map.rows = static_cast<int>(k);
-        for (uint32_t r = 0; r < k; r++)
-            map.prime[r] = static_cast<unsigned short>(r);
+        const RowMap map = ct_row_map(static_cast<int>(k), 1, -1);
         e.ws_reserve(e.lane().ws_floor + count * sizeof(unsigned) + 512);
         e.ws_reset();
         unsigned *flags = reinterpret_cast<unsigned *>(e.ws_alloc((count * sizeof(unsigned) + 7) / 8));
         SEALHIP_CHECK(hipMemsetAsync(flags, 0, count * sizeof(unsigned), e.lane().stream));
-        check_launch(launch_out_of_range(e, reinterpret_cast<const u64 *>(ct), static_cast<std::size_t>(size) * k * e.n, count,
-                                         map, flags),
-                     "is_data_valid_for");
+        check(launch_out_of_range(e, reinterpret_cast<const u64 *>(ct), static_cast<std::size_t>(size) * k * e.n, count,
+                                  map, flags),
+              "is_data_valid_for");
         std::vector<unsigned> host(count);
         SEALHIP_CHECK(hipMemcpyAsync(host.data(), flags, count * sizeof(unsigned), hipMemcpyDeviceToHost, e.lane().stream));
         e.sync_and_check();

@@ -11,15 +11,8 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
         constexpr int kTileLog = 11; // 2048 complex numbers = 32 KiB of LDS per workgroup
-
-        inline unsigned grid_for(std::size_t work_items)
-        {
-            std::size_t blocks = (work_items + kThreads - 1) / kThreads;
-            const std::size_t cap = 256u * 32u;
-            return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-        }
+        constexpr std::size_t kMaxBlocks = 256u * 32u; // of the grid-stride launches here (twice grid_for's default)
 
         __device__ __forceinline__ double2 cmul(double2 a, double2 b) // std::complex operator* (no NaN recovery needed)
         {
@@ -366,17 +359,17 @@ namespace sealhip
                 fft_local_kernel<true><<<static_cast<unsigned>(tiles), kThreads, lds, e.lane().stream>>>(data, roots, logn, L);
                 int layer = L;
                 for (; layer + 1 < logn; layer += 2)
-                    fft_layer2_kernel<true><<<grid_for(quads), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, quads);
+                    fft_layer2_kernel<true><<<grid_for(quads, kMaxBlocks), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, quads);
                 if (layer < logn)
-                    fft_layer_kernel<true><<<grid_for(bflies), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, bflies);
+                    fft_layer_kernel<true><<<grid_for(bflies, kMaxBlocks), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, bflies);
             }
             else
             {
                 int layer = 0;
                 for (; layer + 1 < logn - L; layer += 2)
-                    fft_layer2_kernel<false><<<grid_for(quads), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, quads);
+                    fft_layer2_kernel<false><<<grid_for(quads, kMaxBlocks), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, quads);
                 if (layer < logn - L)
-                    fft_layer_kernel<false><<<grid_for(bflies), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, bflies);
+                    fft_layer_kernel<false><<<grid_for(bflies, kMaxBlocks), kThreads, 0, e.lane().stream>>>(data, roots, logn, layer, bflies);
                 fft_local_kernel<false><<<static_cast<unsigned>(tiles), kThreads, lds, e.lane().stream>>>(data, roots, logn, L);
             }
             return hipGetLastError();
@@ -392,12 +385,12 @@ namespace sealhip
             return hipSuccess;
         ProfScope prof(e, "ckks_encode_fft", static_cast<double>(total));
         double2 *c2 = reinterpret_cast<double2 *>(cv);
-        ckks_place_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(reinterpret_cast<const double2 *>(values), n_values, c2, map,
+        ckks_place_kernel<<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(reinterpret_cast<const double2 *>(values), n_values, c2, map,
                                                                       e.logn, total);
         hipError_t err = run_fft<true>(e, c2, reinterpret_cast<const double2 *>(inv_roots), count);
         if (err != hipSuccess)
             return err;
-        ckks_round_decompose_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(c2, n_inv_scale, out, rows, e.d_primes, e.logn,
+        ckks_round_decompose_kernel<<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(c2, n_inv_scale, out, rows, e.d_primes, e.logn,
                                                                                 max_bits, total);
         return hipGetLastError();
     }
@@ -412,13 +405,13 @@ namespace sealhip
         ProfScope prof(e, "ckks_decode_fft", static_cast<double>(total));
         double2 *r2 = reinterpret_cast<double2 *>(res);
         if (k <= 4)
-            ckks_compose_kernel<4><<<grid_for(total), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
+            ckks_compose_kernel<4><<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
         else if (k <= 8)
-            ckks_compose_kernel<8><<<grid_for(total), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
+            ckks_compose_kernel<8><<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
         else if (k <= 16)
-            ckks_compose_kernel<16><<<grid_for(total), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
+            ckks_compose_kernel<16><<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2, e.logn, total);
         else
-            ckks_compose_kernel<kCkksMaxLimbs><<<grid_for(total), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2,
+            ckks_compose_kernel<kCkksMaxLimbs><<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(coeff, d, e.d_primes, inv_scale, r2,
                                                                                           e.logn, total);
         hipError_t err = hipGetLastError();
         if (err != hipSuccess)
@@ -426,7 +419,7 @@ namespace sealhip
         err = run_fft<false>(e, r2, reinterpret_cast<const double2 *>(roots), count);
         if (err != hipSuccess)
             return err;
-        ckks_pick_kernel<<<grid_for(total / 2), kThreads, 0, e.lane().stream>>>(r2, reinterpret_cast<double2 *>(values), map, e.logn,
+        ckks_pick_kernel<<<grid_for(total / 2, kMaxBlocks), kThreads, 0, e.lane().stream>>>(r2, reinterpret_cast<double2 *>(values), map, e.logn,
                                                                         total / 2);
         return hipGetLastError();
     }

@@ -12,7 +12,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
         constexpr int kWave = 64;
 
         // One lane per coefficient c of item `blockIdx.x / blocks_per_item`; bits_out[item] = max(bits_out[item], bits(|W_c|)).

@@ -13,15 +13,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
-
-        inline unsigned grid_for(std::size_t work_items)
-        {
-            std::size_t blocks = (work_items + kThreads - 1) / kThreads;
-            const std::size_t cap = 256u * 16u; // grid-stride the rest
-            return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-        }
-
         // Delta m_i = floor(q / t) m + fix  (mod q_i), scalingvariant.cpp:31-51, for the lane's coefficient
         __device__ __forceinline__ u64 scaled_plain(const EncryptArgs &a, const PrimeDev &Q, int i, u64 m, u64 fix)
         {

@@ -273,7 +273,7 @@ namespace sealhip
         std::size_t ws_bytes = 0, ws_used = 0;
         std::size_t ws_floor = 0; // bytes at the front of the arena held by an enclosing operation
         std::size_t ws_budget = 0; // cap of this lane's arena, fixed at first use (pipeline.cpp)
-        // (batch size, items per arena chunk) of the last operations that walked a batch in chunks (pipeline.cpp plan_chunk;
+        // (batch size, items per arena chunk) of the last operations that walked a batch in chunks (pipeline.cpp for_chunks;
         // sealhip_debug_chunk_log): lets a caller that verifies its results pick the items at the chunk boundaries
         std::vector<std::pair<std::size_t, std::size_t>> chunk_log;
         // seed expansion (seed_expand.hip): pinned staging of the seed records, reused once the event that follows their
@@ -406,6 +406,21 @@ namespace sealhip
         if (_e != hipSuccess)                                                                        \
             throw ::sealhip::HipError(_e, (std::string(#expr) + ": " + hipGetErrorString(_e)).c_str()); \
     } while (0)
+    // the same for a launcher's return value: `what` names the launch in the message
+    inline void check(hipError_t err, const char *what)
+    {
+        if (err != hipSuccess)
+            throw HipError(err, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
+    }
+
+    // Launch shape of the elementwise kernels: kThreads lanes per block, one block per kThreads work items up to
+    // max_blocks; the kernels grid-stride the rest.
+    constexpr int kThreads = 256;
+    inline unsigned grid_for(std::size_t work_items, std::size_t max_blocks = 256u * 16u)
+    {
+        const std::size_t blocks = (work_items + kThreads - 1) / kThreads;
+        return static_cast<unsigned>(blocks < max_blocks ? (blocks ? blocks : 1) : max_blocks);
+    }
 
     struct ProfScope
     {
@@ -784,8 +799,13 @@ namespace sealhip
     // seeds of c_1), noise: n_keys x digits x N small signed samples (device). Stream-ordered on the calling thread's lane.
     void op_generate_kswitch_keys(Engine &e, const u64 *sk_ntt, const std::uint32_t *elts, std::size_t n_keys,
                                   const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data);
-    // items of `bytes_per_item` arena bytes per chunk of a batch of `count` (pipeline.cpp; logged in Lane::chunk_log)
-    std::size_t ws_plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers);
+    // The chunk loop of every operation that needs arena temporaries per item (pipeline.cpp): as many items per chunk as
+    // the lane's arena holds at `bytes_per_item` (the padded sum over the item's `n_buffers` temporaries), one
+    // (count, chunk) entry in Lane::chunk_log, then body(off, m) for the m items from item `off` with the arena reset.
+    void for_chunks(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers,
+                    const std::function<void(std::size_t off, std::size_t m)> &body);
+    // rows 0..rows-1 of the key primes for each of `polys` polynomials of an item; `only` >= 0 keeps that polynomial
+    RowMap ct_row_map(int rows, int polys, int only);
 
     std::unique_ptr<Engine> make_engine(int scheme, int logn, const u64 *key_moduli, int n_key, int nsp, u64 t,
                                         bool strict, int device);

@@ -8,15 +8,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
-
-        inline unsigned grid_for(std::size_t work_items)
-        {
-            std::size_t blocks = (work_items + kThreads - 1) / kThreads;
-            const std::size_t cap = 256u * 16u; // grid-stride the rest
-            return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-        }
-
         // reverse_bits(x, bits) of util/common.h for bits in 1..32
         __device__ __forceinline__ std::uint32_t rev_bits(std::uint32_t x, int bits)
         {

@@ -15,8 +15,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
-
         // modup constants of digit j: [inv_punch(nsp) | inv_punch_shoup(nsp) | punch[rows][nsp]]
         __device__ __forceinline__ const u64 *modup_block(const KsDev *d, int j)
         {

@@ -61,12 +61,6 @@ namespace sealhip
             return chunk;
         }
 
-        void check(hipError_t err, const char *what)
-        {
-            if (err != hipSuccess)
-                throw HipError(err, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
-        }
-
         RowMap skip_map(const RowMap &base, int keep_lo, int keep_hi)
         {
             RowMap m = base;
@@ -77,9 +71,27 @@ namespace sealhip
         }
     } // namespace
 
-    std::size_t ws_plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers)
+    void for_chunks(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers,
+                    const std::function<void(std::size_t off, std::size_t m)> &body)
     {
-        return plan_chunk(e, count, bytes_per_item, n_buffers);
+        const std::size_t chunk = plan_chunk(e, count, bytes_per_item, n_buffers);
+        for (std::size_t off = 0; off < count; off += chunk)
+        {
+            e.ws_reset();
+            body(off, std::min(chunk, count - off));
+        }
+    }
+
+    RowMap ct_row_map(int rows, int polys, int only)
+    {
+        if (rows * polys > kMaxRows)
+            throw std::invalid_argument("too many rows");
+        RowMap m{};
+        m.rows = rows * polys;
+        for (int j = 0; j < polys; j++)
+            for (int r = 0; r < rows; r++)
+                m.prime[j * rows + r] = (only < 0 || only == j) ? static_cast<unsigned short>(r) : kSkipRow;
+        return m;
     }
 
     // bytes of arena one item of op_switch_key needs (shared with op_apply_galois, which must size the arena
@@ -147,13 +159,9 @@ namespace sealhip
         const std::size_t per_item = switch_key_item_bytes(e, k);
         if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
             throw std::logic_error("internal: arena accounting mismatch");
-        const std::size_t chunk = plan_chunk(e, count, per_item, 4);
         const RowMap map_q = lt.map_q;
         const RowMap map_rows = lt.map_key;
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
             u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
             u64 *ext = e.ws_alloc(w_ext * m);
             u64 *prod = e.ws_alloc(w_prod * m);
@@ -280,7 +288,7 @@ namespace sealhip
                 check(launch_ks_mac(e, lt.d_ks, h, inb, inb_stride, ext, ext_item, ext_digit, key.d_data, prod, w_prod, m, dj0, dj1),
                       "mac");
             if (partial)
-                continue; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
+                return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
             if (!ckks)
             {
                 // BFV: every row of both products goes back to coefficient form in one launch (the reference does the
@@ -292,7 +300,7 @@ namespace sealhip
                 SinkArm arm(e, sink_at(e, off)); // (component 1 of the m ciphertexts of this chunk)
                 check(launch_ks_moddown_bfv(e, lt.d_ks, h, prod, ext_item, ctp, ct_stride, 2 * m, defer, c0p, c0_stride),
                       "moddown_bfv");
-                continue;
+                return;
             }
             const u64 p_special = (ckks && e.nsp == 1) ? e.key_moduli[h.row_prime[k]] : 0;
             // The gathered transform is handed the integer P - r < P instead of the residue (-(s mod P)) mod q_i: the same
@@ -365,7 +373,7 @@ namespace sealhip
                                              ct_stride, 2 * m, 1, c0p, c0_stride),
                       "moddown_post");
             }
-        }
+        });
     }
 
     // modup_rns as a standalone operation (multi_special_primes.cpp:151-185)
@@ -387,11 +395,7 @@ namespace sealhip
         const std::size_t N = e.n;
         const int rows = k + e.nsp;
         const std::size_t per_item = static_cast<std::size_t>(k) * N * sizeof(u64);
-        const std::size_t chunk = plan_chunk(e, count, per_item, 1);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, per_item, 1, [&](std::size_t off, std::size_t m) {
             u64 *temp = e.ws_alloc(static_cast<std::size_t>(k) * N * m);
             u64 *p = poly + off * rows * N;
             check(launch_ks_moddown_pre(e, lt.d_ks, lt.h_ks, p, static_cast<std::size_t>(rows) * N, temp,
@@ -404,7 +408,7 @@ namespace sealhip
             check(launch_ks_moddown_post(e, lt.d_ks, lt.h_ks, p, static_cast<std::size_t>(rows) * N, temp,
                                          static_cast<std::size_t>(k) * N, nullptr, 0, m, 0),
                   "moddown_post");
-        }
+        });
     }
 
     // ------------------------------------------------------------------------------------------
@@ -486,12 +490,8 @@ namespace sealhip
         const int nB = h.nB, kb = k + nB, sin = sq ? sa : sa + sb, dest = sa + sb - 1;
         const std::size_t w_x = static_cast<std::size_t>(sin) * kb * N;
         const std::size_t w_d = static_cast<std::size_t>(dest) * kb * N;
-        const std::size_t chunk = plan_chunk(e, count, (w_x + w_d) * sizeof(u64), 2);
         const std::size_t poly_q = static_cast<std::size_t>(k) * N, poly_x = static_cast<std::size_t>(kb) * N;
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, (w_x + w_d) * sizeof(u64), 2, [&](std::size_t off, std::size_t m) {
             u64 *X = e.ws_alloc(w_x * m);
             u64 *D = e.ws_alloc(w_d * m);
             // steps (1)-(3) (:335-353): lift to Bsk (fastbconv_m_tilde + sm_mrq) and one lazy NTT over all rows
@@ -574,7 +574,7 @@ namespace sealhip
                                               dest * poly_q, m, plan),
                           "floor_sk");
                 }
-                continue;
+                return;
             }
             // step (4) (:376-420)
             // (square: both operands are the same two transformed polynomials; the kernel then forms x_0 x_1 once and adds it
@@ -603,7 +603,7 @@ namespace sealhip
                                           dest * poly_q, m, plan),
                       "floor_sk");
             }
-        }
+        });
     }
 
     void op_bfv_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out)
@@ -664,6 +664,22 @@ namespace sealhip
 
     namespace
     {
+    // The CKKS division by the last prime of level k (rns.cpp:777-851) up to its forward transforms; lt = e.level(k).
+    // rescale_temp: from the coefficient-form last rows of npolys polynomials (last_stride words apart) to their correction
+    // over the k - 1 remaining primes in temp[npolys][k - 1][N], lazily transformed (rescale_post reduces).
+    void rescale_temp(Engine &e, LevelTools &lt, int k, u64 *last, std::size_t last_stride, std::size_t npolys, u64 *temp)
+    {
+        check(launch_rescale_pre(e, lt.d_rns, lt.h_rns, last, last_stride, temp, static_cast<std::size_t>(k - 1) * e.n, npolys),
+              "rescale_pre");
+        check(launch_ntt(e, temp, npolys * (k - 1), e.level_host(k - 1).map_q, false, 0), "ntt(temp)");
+    }
+    // divround_ntt_front: the same for polys[npolys][k][N] in NTT form, whose last rows go to coefficient form in place first
+    void divround_ntt_front(Engine &e, LevelTools &lt, int k, u64 *polys, std::size_t npolys, u64 *temp)
+    {
+        check(launch_ntt(e, polys, npolys * k, skip_map(lt.map_q, k - 1, k), true, kNttCanonical), "intt(last)");
+        rescale_temp(e, lt, k, polys + static_cast<std::size_t>(k - 1) * e.n, static_cast<std::size_t>(k) * e.n, npolys, temp);
+    }
+
     void mod_switch_polys(Engine &e, int k, const u64 *ct, std::size_t in_stride, u64 *out, std::size_t out_stride,
                           std::size_t npolys)
     {
@@ -678,12 +694,7 @@ namespace sealhip
         // CKKS (rns.cpp:777-851), without the reference's full copy of the ciphertext: only the last row is
         // duplicated because only it is modified
         const std::size_t per_poly = (N + static_cast<std::size_t>(k - 1) * N) * sizeof(u64);
-        const std::size_t chunk = plan_chunk(e, npolys, per_poly, 2);
-        const RowMap map_low = e.level_host(k - 1).map_q;
-        for (std::size_t off = 0; off < npolys; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, npolys - off);
-            e.ws_reset();
+        for_chunks(e, npolys, per_poly, 2, [&](std::size_t off, std::size_t m) {
             u64 *last = e.ws_alloc(N * m);
             u64 *temp = e.ws_alloc(temp_stride * m);
             check(launch_copy_rows(e, ct + off * in_stride + static_cast<std::size_t>(k - 1) * N, in_stride, last, N, m, 1),
@@ -692,12 +703,11 @@ namespace sealhip
             one.rows = 1;
             one.prime[0] = static_cast<unsigned short>(k - 1);
             check(launch_ntt(e, last, m, one, true, kNttCanonical), "intt(last)");
-            check(launch_rescale_pre(e, lt.d_rns, lt.h_rns, last, N, temp, temp_stride, m), "rescale_pre");
-            check(launch_ntt(e, temp, m * (k - 1), map_low, false, 0), "ntt(temp)");
+            rescale_temp(e, lt, k, last, N, m, temp);
             check(launch_rescale_post(e, lt.d_rns, lt.h_rns, ct + off * in_stride, in_stride, temp, temp_stride,
                                       out + off * out_stride, out_stride, m),
                   "rescale_post");
-        }
+        });
     }
     } // namespace
 
@@ -709,21 +719,12 @@ namespace sealhip
         LevelTools &lt = e.level(k);
         const std::size_t N = e.n;
         const std::size_t stride = static_cast<std::size_t>(k) * N, tstride = static_cast<std::size_t>(k - 1) * N;
-        const std::size_t chunk = plan_chunk(e, count, tstride * sizeof(u64), 1);
-        const RowMap map_low = e.level_host(k - 1).map_q;
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, tstride * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
             u64 *temp = e.ws_alloc(tstride * m);
             u64 *p = data + off * stride;
-            check(launch_ntt(e, p, m * k, skip_map(lt.map_q, k - 1, k), true, kNttCanonical), "intt(last)");
-            check(launch_rescale_pre(e, lt.d_rns, lt.h_rns, p + static_cast<std::size_t>(k - 1) * N, stride, temp,
-                                     tstride, m),
-                  "rescale_pre");
-            check(launch_ntt(e, temp, m * (k - 1), map_low, false, 0), "ntt(temp)");
+            divround_ntt_front(e, lt, k, p, m, temp);
             check(launch_rescale_post(e, lt.d_rns, lt.h_rns, p, stride, temp, tstride, p, stride, m), "rescale_post");
-        }
+        });
     }
 
     // ------------------------------------------------------------------------------------------
@@ -829,20 +830,25 @@ namespace sealhip
     namespace
     {
         // dot_product_ct_sk_array of m coefficient-form items of size >= 2 into out[m][k][N]: copies of c_1.. go to (lazy)
-        // NTT form (decryptor.cpp:241-244), the sum comes back canonical (:258-262), then + c_0 (:265). copy: (size-1) x k x N
-        // words per item of scratch.
-        void dot_product_coeff_chunk(Engine &e, int k, const RowMap &map_q, const u64 *ct, int size, std::size_t m,
-                                     const u64 *sk_powers, u64 *copy, u64 *out)
+        // NTT form (decryptor.cpp:241-244), the sum comes back canonical (:258-262), then + c_0 (:265). The body of one arena
+        // chunk: the copies ((size-1) x k x N words per item) and, when the caller passes no `out`, the result (k x N words per
+        // item, for the caller's next launch) are carved from the arena. Returns the result.
+        u64 *dot_product_coeff_chunk(Engine &e, int k, const RowMap &map_q, const u64 *ct, int size, std::size_t m,
+                                     const u64 *sk_powers, u64 *out = nullptr)
         {
             const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
             const std::size_t sk_stride = static_cast<std::size_t>(e.n_key) * N;
             const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+            u64 *copy = e.ws_alloc(tail * m);
+            if (!out)
+                out = e.ws_alloc(poly * m);
             check(launch_copy_rows(e, ct + poly, item, copy, tail, m, (size - 1) * k), "copy(c1..)");
             check(launch_ntt(e, copy, m * (size - 1) * k, map_q, false, kNttAnyRep), "ntt(c1..)"); // (the dot product reduces)
             // the kernel indexes polynomials 1.. of an item: hand it a base one polynomial before the copies
             check(launch_dot_sk(e, copy - poly, size, tail, sk_powers, sk_stride, out, m, map_q, 0), "dot_sk");
             check(launch_ntt(e, out, m * k, map_q, true, kNttCanonical), "intt(dot)");
             check(launch_dot_sk(e, ct, 1, item, sk_powers, sk_stride, out, m, map_q, 2), "add c0");
+            return out;
         }
     } // namespace
 
@@ -861,14 +867,9 @@ namespace sealhip
             return;
         }
         const std::size_t tail = static_cast<std::size_t>(size - 1) * poly;
-        const std::size_t chunk = plan_chunk(e, count, tail * sizeof(u64), 1);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
-            u64 *copy = e.ws_alloc(tail * m);
-            dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers, copy, out + off * poly);
-        }
+        for_chunks(e, count, tail * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
+            dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers, out + off * poly);
+        });
     }
 
     void op_invariant_noise_budget(Engine &e, int k, const u64 *ct, int size, std::size_t count, const u64 *sk_powers,
@@ -876,12 +877,8 @@ namespace sealhip
     {
         const NoiseBudgetDev *consts = e.noise_budget_consts(k);
         const int q_bits = e.total_coeff_modulus_bit_count(k);
-        RowMap map_q{}; // rows 0..k-1 of the key primes (the level's BEHZ tools are not needed, nor built)
-        map_q.rows = k;
-        for (int r = 0; r < k; r++)
-            map_q.prime[r] = static_cast<unsigned short>(r);
-        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
-        const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+        const RowMap map_q = ct_row_map(k, 1, -1); // (the level's BEHZ tools are not needed, nor built)
+        const std::size_t item = static_cast<std::size_t>(size) * k * e.n;
         // one bit count per item, at the FRONT of the arena (ws_floor) for the whole batch; the chunks use the rest
         const std::size_t flag_bytes = (count * sizeof(int) + 255) & ~static_cast<std::size_t>(255);
         struct FloorGuard
@@ -894,18 +891,16 @@ namespace sealhip
             }
         } guard{ e, e.lane().ws_floor };
         e.lane().ws_floor = guard.saved + flag_bytes;
-        const std::size_t chunk = plan_chunk(e, count, (tail + poly) * sizeof(u64), 2); // (may move the arena: flags after)
-        int *bits = reinterpret_cast<int *>(static_cast<char *>(e.lane().ws) + guard.saved);
-        check(hipMemsetAsync(bits, 0, count * sizeof(int), e.lane().stream), "memset(bits)");
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
-            u64 *copy = e.ws_alloc(tail * m);
-            u64 *v = e.ws_alloc(poly * m);
-            dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers, copy, v);
+        int *bits = nullptr;
+        for_chunks(e, count, item * sizeof(u64), 2, [&](std::size_t off, std::size_t m) {
+            if (off == 0) // (sizing the chunks may have moved the arena: the flags are addressed, and cleared, after it)
+            {
+                bits = reinterpret_cast<int *>(static_cast<char *>(e.lane().ws) + guard.saved);
+                check(hipMemsetAsync(bits, 0, count * sizeof(int), e.lane().stream), "memset(bits)");
+            }
+            const u64 *v = dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers);
             check(launch_noise_bits(e, consts, k, v, m, bits + off), "noise_budget");
-        }
+        });
         std::vector<int> host(count);
         check(hipMemcpyAsync(host.data(), bits, count * sizeof(int), hipMemcpyDeviceToHost, e.lane().stream), "d2h(bits)");
         e.sync_and_check();
@@ -922,34 +917,75 @@ namespace sealhip
             return;
         }
         LevelTools &lt = e.level(k);
-        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
-        const std::size_t item = static_cast<std::size_t>(size) * poly, tail = item - poly;
+        const std::size_t N = e.n, item = static_cast<std::size_t>(size) * k * N;
         // bfv_decrypt (:77-120): dot product, then decrypt_scale_and_round into the plaintext
-        const std::size_t chunk = plan_chunk(e, count, (tail + poly) * sizeof(u64), 2);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
-            u64 *copy = e.ws_alloc(tail * m);
-            u64 *v = e.ws_alloc(poly * m);
-            dot_product_coeff_chunk(e, k, lt.map_q, ct + off * item, size, m, sk_powers, copy, v);
+        for_chunks(e, count, item * sizeof(u64), 2, [&](std::size_t off, std::size_t m) {
+            const u64 *v = dot_product_coeff_chunk(e, k, lt.map_q, ct + off * item, size, m, sk_powers);
             check(launch_decrypt_scale_and_round(e, lt.d_rns, lt.h_rns, v, plain + off * N, m), "decrypt_scale_and_round");
-        }
+        });
     }
     // ---------------------------------------------------------------- encrypt-side arithmetic
     namespace
     {
-        // rows 0..rows-1 of the key primes for each of `polys` polynomials of an item; `only` >= 0 keeps that polynomial
-        RowMap ct_row_map(int rows, int polys, int only)
+        // RlweArgs of the launches that write one polynomial per item (ct_item_stride words apart) from N samples per item
+        // (e_item_stride apart)
+        RlweArgs rlwe_args(u64 *ct, std::size_t ct_item_stride, int rows, const std::int32_t *samples,
+                           std::size_t e_item_stride)
         {
-            if (rows * polys > kMaxRows)
-                throw std::invalid_argument("too many rows");
-            RowMap m{};
-            m.rows = rows * polys;
-            for (int j = 0; j < polys; j++)
-                for (int r = 0; r < rows; r++)
-                    m.prime[j * rows + r] = (only < 0 || only == j) ? static_cast<unsigned short>(r) : kSkipRow;
-            return m;
+            RlweArgs a{};
+            a.ct = ct;
+            a.ct_item_stride = ct_item_stride;
+            a.polys = 1;
+            a.rows = rows;
+            a.e = samples;
+            a.e_item_stride = e_item_stride;
+            return a;
+        }
+        // ... and of those that write both polynomials of a ciphertext from one x per item: x[item] (.) y[j] and e[item][j]
+        RlweArgs rlwe_args_pair(u64 *ct, int rows, const u64 *x, const u64 *y, std::size_t y_poly_stride,
+                                const std::int32_t *noise, std::size_t N)
+        {
+            const std::size_t poly = static_cast<std::size_t>(rows) * N;
+            RlweArgs a = rlwe_args(ct, 2 * poly, rows, noise, 2 * N);
+            a.ct_poly_stride = poly;
+            a.polys = 2;
+            a.x = x;
+            a.x_item_stride = poly;
+            a.y = y;
+            a.y_poly_stride = y_poly_stride;
+            a.e_poly_stride = N;
+            return a;
+        }
+        // small samples to RNS form in the polynomials `a` writes, then to NTT form: item_rows = the rows of one item
+        // (ct_row_map; the polynomials `a` does not write are skipped). `lift`, `ntt`: the names of the two launches.
+        void lift_to_ntt(Engine &e, const RlweArgs &a, std::size_t count, const RowMap &item_rows, const char *lift,
+                         const char *ntt)
+        {
+            check(launch_rlwe_stage(e, 0, a, count), lift);
+            check(launch_ntt(e, a.ct, count * item_rows.rows, item_rows, false, kNttCanonical), ntt);
+        }
+        // encrypt_zero_asymmetric (rlwe.cpp:161-201) for the m items of one chunk: u to RNS + NTT form in u_ntt[m][rows][N],
+        // then P[m][2][rows][N], P_j = u (.) pk_j + e_j, with the polynomials of pk pk_poly_stride words apart. ntt_form: the
+        // result stays in NTT form; else it goes back to coefficient form and e_j is added there, unless add_noise is off
+        // (the caller's finish kernel adds it).
+        void pk_product_chunk(Engine &e, int rows, const u64 *pk, std::size_t pk_poly_stride, const std::int32_t *u,
+                              const std::int32_t *noise, std::size_t m, u64 *u_ntt, u64 *P, bool ntt_form, bool add_noise)
+        {
+            const std::size_t N = e.n;
+            lift_to_ntt(e, rlwe_args(u_ntt, static_cast<std::size_t>(rows) * N, rows, u, N), m, ct_row_map(rows, 1, -1), "lift(u)",
+                        "ntt(u)");
+            const RlweArgs a = rlwe_args_pair(P, rows, u_ntt, pk, pk_poly_stride, noise, N);
+            const RowMap both = ct_row_map(rows, 2, -1);
+            if (ntt_form)
+            {
+                lift_to_ntt(e, a, m, both, "lift(e)", "ntt(e)");
+                check(launch_rlwe_stage(e, 2, a, m), "c = e + u*pk");
+                return;
+            }
+            check(launch_rlwe_stage(e, 1, a, m), "u*pk");
+            check(launch_ntt(e, P, m * 2 * rows, both, true, kNttCanonical), "intt(c)");
+            if (add_noise)
+                check(launch_rlwe_stage(e, 3, a, m), "c += e");
         }
     } // namespace
 
@@ -960,23 +996,15 @@ namespace sealhip
         u64 *c1 = ct + poly;
         if (c1 != a_ntt) // c_1 = a, sampled directly in NTT form (rlwe.cpp:245-249)
             check(launch_copy_rows(e, a_ntt, poly, c1, 2 * poly, count, rows), "copy(a)");
-        RlweArgs a{};
-        a.ct = ct;
-        a.ct_item_stride = 2 * poly;
-        a.ct_poly_stride = poly;
-        a.polys = 1;
-        a.rows = rows;
+        RlweArgs a = rlwe_args(ct, 2 * poly, rows, noise, N);
         a.x = c1;
         a.x_item_stride = 2 * poly;
         a.y = sk_ntt;
-        a.e = noise;
-        a.e_item_stride = N;
         a.negate = 1;
         if (is_ntt_form)
         {
             // noise to NTT form in the c_0 slot, then c_0 = -(noise + a*s)  (rlwe.cpp:266-284)
-            check(launch_rlwe_stage(e, 0, a, count), "lift(e)");
-            check(launch_ntt(e, ct, count * 2 * rows, ct_row_map(rows, 2, 0), false, kNttCanonical), "ntt(e)");
+            lift_to_ntt(e, a, count, ct_row_map(rows, 2, 0), "lift(e)", "ntt(e)");
             check(launch_rlwe_stage(e, 2, a, count), "c0");
         }
         else
@@ -1003,21 +1031,10 @@ namespace sealhip
         const int nk = e.n_key;
         const std::size_t N = e.n, poly = static_cast<std::size_t>(nk) * N, digit_words = 2 * poly;
         const int digits = (e.k_first + e.nsp - 1) / e.nsp;
-        RlweArgs a{};
-        a.ct_item_stride = digit_words;
-        a.ct_poly_stride = poly;
-        a.polys = 1;
-        a.rows = nk;
-        a.e_item_stride = N;
         const RowMap c0_rows = ct_row_map(nk, 2, 0);
         for (std::size_t i = 0; i < n_keys; i++)
-        {
-            a.ct = key_data[i];
-            a.e = noise + i * digits * N;
-            check(launch_rlwe_stage(e, 0, a, digits), "lift(e)");
-            check(launch_ntt(e, key_data[i], static_cast<std::size_t>(digits) * 2 * nk, c0_rows, false, kNttCanonical),
-                  "ntt(e)");
-        }
+            lift_to_ntt(e, rlwe_args(key_data[i], digit_words, nk, noise + i * digits * N, N), digits, c0_rows, "lift(e)",
+                        "ntt(e)");
         std::vector<SeedJob> jobs(n_keys * digits);
         for (std::size_t i = 0; i < n_keys; i++)
             for (int j = 0; j < digits; j++)
@@ -1067,50 +1084,10 @@ namespace sealhip
                                     const std::int32_t *noise, std::size_t count, u64 *ct)
     {
         const std::size_t N = e.n, poly = static_cast<std::size_t>(rows) * N;
-        const std::size_t chunk = plan_chunk(e, count, poly * sizeof(u64), 1);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, poly * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
             u64 *u_ntt = e.ws_alloc(poly * m);
-            RlweArgs a{};
-            // u to RNS + NTT form (rlwe.cpp:161-170)
-            a.ct = u_ntt;
-            a.ct_item_stride = poly;
-            a.polys = 1;
-            a.rows = rows;
-            a.e = u + off * N;
-            a.e_item_stride = N;
-            check(launch_rlwe_stage(e, 0, a, m), "lift(u)");
-            check(launch_ntt(e, u_ntt, m * rows, ct_row_map(rows, 1, -1), false, kNttCanonical), "ntt(u)");
-            // c_j = u * pk_j + e_j  (:171-201)
-            a = RlweArgs{};
-            a.ct = ct + off * 2 * poly;
-            a.ct_item_stride = 2 * poly;
-            a.ct_poly_stride = poly;
-            a.polys = 2;
-            a.rows = rows;
-            a.x = u_ntt;
-            a.x_item_stride = poly;
-            a.x_poly_stride = 0;
-            a.y = pk;
-            a.y_poly_stride = poly;
-            a.e = noise + off * 2 * N;
-            a.e_item_stride = 2 * N;
-            a.e_poly_stride = N;
-            if (is_ntt_form)
-            {
-                check(launch_rlwe_stage(e, 0, a, m), "lift(e)");
-                check(launch_ntt(e, a.ct, m * 2 * rows, ct_row_map(rows, 2, -1), false, kNttCanonical), "ntt(e)");
-                check(launch_rlwe_stage(e, 2, a, m), "c = e + u*pk");
-            }
-            else
-            {
-                check(launch_rlwe_stage(e, 1, a, m), "u*pk");
-                check(launch_ntt(e, a.ct, m * 2 * rows, ct_row_map(rows, 2, -1), true, kNttCanonical), "intt(c)");
-                check(launch_rlwe_stage(e, 3, a, m), "c += e");
-            }
-        }
+            pk_product_chunk(e, rows, pk, poly, u + off * N, noise + off * 2 * N, m, u_ntt, ct + off * 2 * poly, is_ntt_form, true);
+        });
     }
 
     void fill_scaling_args(const Engine &e, int k, ScalingArgs &a)
@@ -1200,67 +1177,31 @@ namespace sealhip
             if (ckks)
                 lt = &e.level(R);
         }
-        RowMap map_low{};
-        if (ckks && divide)
-            map_low = e.level_host(k).map_q;
         if (!ckks && plain)
             fill_scaling_args(e, k, f.sc);
         // CKKS at the key level: encrypt_zero_asymmetric straight into ct (no plaintext is valid there)
         const bool direct = ckks && !divide;
         const std::size_t per_item = poly + (direct ? 0 : 2 * poly) + (ckks && divide ? 2 * out_poly : 0);
-        const std::size_t chunk = plan_chunk(e, count, per_item * sizeof(u64), 3);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, per_item * sizeof(u64), 3, [&](std::size_t off, std::size_t m) {
             u64 *u_ntt = e.ws_alloc(poly * m);
             u64 *P = direct ? ct + off * 2 * out_poly : e.ws_alloc(2 * poly * m);
-            RlweArgs a{};
-            a.ct = u_ntt;
-            a.ct_item_stride = poly;
-            a.polys = 1;
-            a.rows = R;
-            a.e = u + off * N;
-            a.e_item_stride = N;
-            check(launch_rlwe_stage(e, 0, a, m), "lift(u)");
-            check(launch_ntt(e, u_ntt, m * R, ct_row_map(R, 1, -1), false, kNttCanonical), "ntt(u)");
-            a = RlweArgs{};
-            a.ct = P;
-            a.ct_item_stride = 2 * poly;
-            a.ct_poly_stride = poly;
-            a.polys = 2;
-            a.rows = R;
-            a.x = u_ntt;
-            a.x_item_stride = poly;
-            a.y = pk;
-            a.y_poly_stride = pk_poly;
-            a.e = noise + off * 2 * N;
-            a.e_item_stride = 2 * N;
-            a.e_poly_stride = N;
-            const RowMap both = ct_row_map(R, 2, -1);
             f.ct = ct + off * 2 * out_poly;
             f.src = P;
-            f.e = a.e;
+            f.e = noise + off * 2 * N;
             f.plain = plain ? plain + off * plain_item_stride : nullptr;
+            pk_product_chunk(e, R, pk, pk_poly, u + off * N, f.e, m, u_ntt, P, ckks, false);
             if (!ckks)
             {
-                check(launch_rlwe_stage(e, 1, a, m), "u*pk");
-                check(launch_ntt(e, P, m * 2 * R, both, true, kNttCanonical), "intt(c)");
                 check(launch_encrypt_finish(e, EncryptFinish::AsymBfv, f, m), "encrypt_asym_bfv_finish");
-                continue;
+                return;
             }
-            check(launch_rlwe_stage(e, 0, a, m), "lift(e)");
-            check(launch_ntt(e, P, m * 2 * R, both, false, kNttCanonical), "ntt(e)");
-            check(launch_rlwe_stage(e, 2, a, m), "c = e + u*pk");
             if (direct)
-                continue;
+                return;
             u64 *temp = e.ws_alloc(2 * out_poly * m);
-            check(launch_ntt(e, P, m * 2 * R, skip_map(lt->map_q, R - 1, R), true, kNttCanonical), "intt(last)");
-            check(launch_rescale_pre(e, lt->d_rns, lt->h_rns, P + out_poly, poly, temp, out_poly, m * 2), "rescale_pre");
-            check(launch_ntt(e, temp, m * 2 * k, map_low, false, 0), "ntt(temp)");
+            divround_ntt_front(e, *lt, R, P, m * 2, temp);
             f.temp = temp;
             check(launch_encrypt_finish(e, EncryptFinish::AsymCkks, f, m), "encrypt_asym_ckks_finish");
-        }
+        });
     }
 
     // Secret key (rlwe.cpp:204-300), for the whole batch at once:
@@ -1287,18 +1228,11 @@ namespace sealhip
         f.e = noise;
         f.plain = plain;
         f.plain_item_stride = plain_item_stride;
-        RlweArgs a{};
-        a.ct = ct;
-        a.ct_item_stride = 2 * poly;
-        a.polys = 1;
-        a.rows = k;
-        a.e = noise;
-        a.e_item_stride = N;
+        RlweArgs a = rlwe_args(ct, 2 * poly, k, noise, N);
         if (ckks)
         {
             f.src = sk;
-            check(launch_rlwe_stage(e, 0, a, count), "lift(e)");
-            check(launch_ntt(e, ct, count * 2 * k, ct_row_map(k, 2, 0), false, kNttCanonical), "ntt(e)");
+            lift_to_ntt(e, a, count, ct_row_map(k, 2, 0), "lift(e)", "ntt(e)");
             check(launch_encrypt_finish(e, EncryptFinish::SymCkks, f, count), "encrypt_sym_ckks_finish");
             return;
         }
@@ -1314,11 +1248,7 @@ namespace sealhip
             check(launch_encrypt_finish(e, EncryptFinish::SymBfv, f, count), "encrypt_sym_bfv_finish");
             return;
         }
-        const std::size_t chunk = plan_chunk(e, count, poly * sizeof(u64), 1);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, poly * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
             u64 *a_ntt = e.ws_alloc(poly * m);
             u64 *c = ct + off * 2 * poly;
             check(launch_copy_rows(e, c + poly, 2 * poly, a_ntt, poly, m, k), "copy(a)");
@@ -1332,7 +1262,7 @@ namespace sealhip
             f.e = noise + off * N;
             f.plain = plain ? plain + off * plain_item_stride : nullptr;
             check(launch_encrypt_finish(e, EncryptFinish::SymBfv, f, m), "encrypt_sym_bfv_finish");
-        }
+        });
     }
 
     // ---------------------------------------------------------------- BatchEncoder
@@ -1363,16 +1293,12 @@ namespace sealhip
     {
         const RowMap map = plain_row_map(e);
         const std::size_t N = e.n;
-        const std::size_t chunk = plan_chunk(e, count, N * sizeof(u64), 1);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, N * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
             u64 *tmp = e.ws_alloc(N * m);
             check(launch_copy_rows(e, plain + off * N, N, tmp, N, m, 1), "copy(plain)");
             check(launch_ntt(e, tmp, m, map, false, kNttCanonical), "ntt(plain)");
             check(launch_batch_permute(e, false, tmp, N, N, values + off * N, e.batch_map(), m, is_signed ? e.t : 0), "batch gather");
-        }
+        });
     }
     // ---------------------------------------------------------------- CKKSEncoder
     void op_ckks_encode(Engine &e, int k, const double *values, std::size_t n_values, std::size_t count, double scale,
@@ -1390,12 +1316,8 @@ namespace sealhip
         const std::size_t N = e.n;
         double n_inv = 1.0 / static_cast<double>(N); // :484-487
         n_inv *= scale;
-        const std::size_t chunk = plan_chunk(e, count, N * 2 * sizeof(double), 2);
         int h_max = 1;
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, N * 2 * sizeof(double), 2, [&](std::size_t off, std::size_t m) {
             int *d_max = reinterpret_cast<int *>(e.ws_alloc(1));
             double *cv = reinterpret_cast<double *>(e.ws_alloc(2 * N * m));
             SEALHIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(int), e.lane().stream));
@@ -1406,7 +1328,7 @@ namespace sealhip
             SEALHIP_CHECK(hipMemcpyAsync(&got, d_max, sizeof(int), hipMemcpyDeviceToHost, e.lane().stream));
             SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream));
             h_max = std::max(h_max, got);
-        }
+        });
         if (h_max >= total_bits)
             throw std::invalid_argument("encoded values are too large"); // :501-504
         check(launch_ntt(e, plain, count * k, map_q, false, kNttCanonical), "ntt(plain)"); // :609-613
@@ -1423,11 +1345,7 @@ namespace sealhip
         const RowMap map_q = e.level_host(k).map_q;
         const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
         const double inv_scale = 1.0 / scale; // :668
-        const std::size_t chunk = plan_chunk(e, count, poly * sizeof(u64) + N * 2 * sizeof(double), 2);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, poly * sizeof(u64) + N * 2 * sizeof(double), 2, [&](std::size_t off, std::size_t m) {
             u64 *copy = e.ws_alloc(poly * m);
             double *res = reinterpret_cast<double *>(e.ws_alloc(2 * N * m));
             if (ntt_can_gather(e)) // the single-pass inverse kernel reads the plaintext rows where they are
@@ -1439,6 +1357,6 @@ namespace sealhip
             }
             check(launch_ckks_decode_back(e, copy, consts, k, m, inv_scale, res, values + off * N, e.d_ckks_map, e.d_ckks_roots),
                   "ckks decode");
-        }
+        });
     }
 } // namespace sealhip

@@ -7,15 +7,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
-
-        inline unsigned grid_for(std::size_t work_items)
-        {
-            std::size_t blocks = (work_items + kThreads - 1) / kThreads;
-            const std::size_t cap = 256u * 16u; // grid-stride the rest
-            return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-        }
-
         template <int OP>
         __device__ __forceinline__ u64 apply_op(u64 a, u64 b, u64 scalar, const PrimeDev &P)
         {

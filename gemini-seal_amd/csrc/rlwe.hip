@@ -10,15 +10,6 @@ namespace sealhip
 {
     namespace
     {
-        constexpr int kThreads = 256;
-
-        inline unsigned grid_for(std::size_t work_items)
-        {
-            std::size_t blocks = (work_items + kThreads - 1) / kThreads;
-            const std::size_t cap = 256u * 16u; // grid-stride the rest
-            return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-        }
-
         // One lane per coefficient pair of (item, poly j < polys, row r < rows). Row r uses prime id r.
         //   STAGE 0: ct = lift(e)                         STAGE 1: ct = x (.) y
         //   STAGE 2: ct = [-] (ct + x (.) y)              STAGE 3: ct = [-] (lift(e) + ct)

@@ -22,8 +22,6 @@ namespace sealhip
             }
         }
 
-        constexpr int kThreads = 256;
-
         // The level constants never change after the context is built. Reading them through the constant address
         // space tells the compiler so: scalar loads that can be merged and hoisted above the kernel's own stores
         // (through a plain pointer every constant is re-fetched, and waited for, right before its use).

@@ -316,12 +316,6 @@ namespace sealhip
             }
             return static_cast<u64>(std::ceil(mean + 8 * std::sqrt(var))) + 64;
         }
-
-        void check(hipError_t err, const char *what)
-        {
-            if (err != hipSuccess)
-                throw HipError(err, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
-        }
     } // namespace
 
     void op_expand_seeds(Engine &e, int rows, const SeedJob *jobs, std::size_t count)
@@ -376,11 +370,7 @@ namespace sealhip
 
         // per item: candidates, buffer roots, key state, record (the padding of each array is in n_buffers)
         const std::size_t per_item = (P + nbuf * 8 + 8 + 9) * 8;
-        const std::size_t chunk = ws_plan_chunk(e, count, per_item, 4);
-        for (std::size_t off = 0; off < count; off += chunk)
-        {
-            const std::size_t m = std::min(chunk, count - off);
-            e.ws_reset();
+        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
             u64 *cand = e.ws_alloc(m * P);
             u64 *h0 = e.ws_alloc(m * nbuf * 8);
             u64 *ks = e.ws_alloc(m * 8);
@@ -411,7 +401,7 @@ namespace sealhip
                 seed_place_kernel<<<static_cast<unsigned>(m), kPlaceThreads, 0, l.stream>>>(rec, ks, cand, pa);
                 check(hipGetLastError(), "seed_place");
             }
-        }
+        });
         // every record copy has been enqueued before this: once the event completes, the staging may be rewritten
         SEALHIP_CHECK(hipEventRecord(l.seed_pin_done, l.stream));
     }
