@@ -1748,6 +1748,123 @@ long sealhip_evaluator_rotate_vector(sealhip_context *ctx, uint32_t k, uint64_t 
     });
 }
 
+/* ------------------------------------------------------------------ hoisted rotation */
+namespace
+{
+    // elts / keys: the elements to apply (zero = a copy of the input, rotate_vector_many's step 0) and their keys. The checks
+    // that need no device come first and run on host-only contexts too (the order the header documents).
+    void do_apply_galois_many(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                              const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys,
+                              uint64_t *out)
+    {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+        for (size_t i = 0; i < elts.size(); i++)
+        {
+            if (!elts[i])
+                continue;
+            if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
+                throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
+            if (keys[i]->key.n_digits < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
+        if (elts.empty() || count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (o < in + count * item && in < o + elts.size() * count * item)
+            throw std::invalid_argument("out must not overlap ct");
+        SinkScope sink(e, elts.size() * count);
+        sink.begin();
+        // every non-zero element goes through ONE hoisted call, each into its own output slot; a zero is a copy
+        std::vector<uint32_t> run_elts, run_slots;
+        std::vector<const KSwitchKey *> run_keys;
+        for (size_t i = 0; i < elts.size(); i++)
+            if (elts[i])
+            {
+                run_elts.push_back(elts[i]);
+                run_slots.push_back(static_cast<uint32_t>(i));
+                run_keys.push_back(&keys[i]->key);
+            }
+        op_apply_galois_many(e, static_cast<int>(k), in, count, run_elts.data(), run_keys.data(), run_elts.size(), o,
+                             run_slots.data());
+        for (size_t i = 0; i < elts.size(); i++)
+            if (!elts[i])
+            {
+                SEALHIP_CHECK(hipMemcpyAsync(o + i * count * item, in, count * item * sizeof(u64), hipMemcpyDeviceToDevice,
+                                             e.lane().stream));
+                if (sink.on)
+                    check(launch_nonzero_tail(e, o + i * count * item, item, item / 2, count, e.lane().tsink + i * count),
+                          "transparency");
+            }
+    }
+} // namespace
+
+long sealhip_evaluator_apply_galois_many(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                         const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                         uint32_t n_elts, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    if (n_elts)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+        for (uint32_t i = 0; i < n_elts; i++)
+            REQUIRE_PTR(galois_keys[i]);
+    }
+    return guarded([&] {
+        const std::vector<uint32_t> elts(galois_elts, galois_elts + n_elts);
+        for (uint32_t elt : elts)
+            if (!elt)
+                throw std::invalid_argument("Galois element is not valid");
+        do_apply_galois_many(ctx, k, ct, count, elts,
+                             std::vector<const sealhip_kswitch_key *>(galois_keys, galois_keys + n_elts), out);
+    });
+}
+
+long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                          const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                          const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    if (n_steps)
+        REQUIRE_PTR(steps);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        std::vector<uint32_t> elts(n_steps, 0);
+        std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
+        for (uint32_t s = 0; s < n_steps; s++)
+        {
+            if (steps[s] == 0)
+                continue; // evaluator.cpp:1958-1962
+            elts[s] = host_galois_elt_from_step(h.n, steps[s]);
+            for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
+                if (galois_elts[i] == elts[s])
+                    keys[s] = galois_keys[i];
+            if (!keys[s])
+                throw std::invalid_argument("Galois key not present");
+        }
+        do_apply_galois_many(ctx, k, ct, count, elts, keys, out);
+    });
+}
+
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
 
 long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

@@ -274,7 +274,8 @@ namespace sealhip
         std::size_t ws_floor = 0; // bytes at the front of the arena held by an enclosing operation
         std::size_t ws_budget = 0; // cap of this lane's arena, fixed at first use (pipeline.cpp)
         // (batch size, items per arena chunk) of the last operations that walked a batch in chunks (pipeline.cpp for_chunks;
-        // sealhip_debug_chunk_log): lets a caller that verifies its results pick the items at the chunk boundaries
+        // sealhip_debug_chunk_log): lets a caller that verifies its results pick the items at the chunk boundaries. The hoisted
+        // rotation, when it has to walk its element list in passes, logs (elements, elements per pass) ahead of that pair.
         std::vector<std::pair<std::size_t, std::size_t>> chunk_log;
         // seed expansion (seed_expand.hip): pinned staging of the seed records, reused once the event that follows their
         // copy has completed; seed_slack = candidates provisioned per seed beyond rows x N (< 0: the computed default;
@@ -578,6 +579,26 @@ namespace sealhip
                                       std::size_t ct_item_stride, std::size_t npolys, int add_into_ct,
                                       const u64 *c0_src = nullptr, std::size_t c0_stride = 0);
 
+    // hoisted rotation (hoist.hip): the Galois elements of one launch, by value in the kernel arguments (nothing to upload,
+    // so the launch is capturable): the NTT-form table T_g (Engine::galois_table), the key K_g, the element itself
+    constexpr int kHoistMaxElts = 16;
+    struct HoistElts
+    {
+        int n;
+        std::uint32_t elt[kHoistMaxElts];
+        const std::uint32_t *table[kHoistMaxElts];
+        const u64 *key[kHoistMaxElts];
+    };
+    // prod[element][item][2][k + nsp][N] = the inner product of the digits, read at column T_g[c], with K_g; target / ext as
+    // for launch_ks_mac
+    hipError_t launch_hoist_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
+                                std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
+                                std::size_t ext_digit_stride, const HoistElts &elts, u64 *prod, std::size_t prod_stride,
+                                std::size_t count);
+    // out[element][item][k][N] = sigma_g of component 0 of ct[item] (NTT form through T_g, else coefficient form)
+    hipError_t launch_hoist_galois_c0(const Engine &e, const u64 *ct, std::size_t ct_stride, u64 *out, std::size_t count,
+                                      const RowMap &map_q, const HoistElts &elts, bool ntt_form);
+
     // ---- batches of separately allocated host ciphertexts (hostbatch.cpp) ----
     struct HostBatchIO
     {
@@ -631,6 +652,11 @@ namespace sealhip
     void op_divround_ntt_inplace(Engine &e, int k, u64 *data, std::size_t count);
     void op_rescale_special_inplace(Engine &e, int k, u64 *poly, std::size_t count);
     void op_apply_galois(Engine &e, int k, u64 *ct, std::size_t count, std::uint32_t elt, const KSwitchKey &key);
+    // One decomposition of c_1, n_elts rotations: out[n_elts][count][2][k][N], ct is only read.
+    // Not the words of n_elts calls of op_apply_galois (the automorphism does not commute with the mod-up).
+    void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
+                              const KSwitchKey *const *keys, std::size_t n_elts, u64 *out,
+                              const std::uint32_t *slots = nullptr); // slots[i]: output slot of element i (null: i)
     void op_multiply_plain(Engine &e, int k, u64 *ct, int size, std::size_t count, const u64 *plain,
                            std::size_t plain_stride);
     // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV: plain_ntt[count][k][N]

@@ -1,0 +1,242 @@
+// hoist.hip -- kernels of the hoisted rotation: one ciphertext rotated by several Galois
+// elements with ONE decomposition of c_1 (Halevi-Shoup). The digits D_j of the key switch (evaluator.cpp:2302-2322) do not
+// depend on the element; what does is the inner product against K_g and sigma_g(c_0):
+//   prod_g[l][r][c] = ( sum_j D_j[r][T_g[c]] * K_g[j][l][row_prime r][c] ) mod p_r
+// with T_g the NTT-form table of the automorphism (galois.cpp:18-47). The gather is folded into the digit loads. T_g maps
+// every aligned block of 2^b indices onto an aligned block of 2^b indices (g * e mod 2N on the bit-reversed exponents keeps
+// the high bits of the index together), so the 64 words a wave gathers lie in the same four 128-byte lines a straight
+// read of one aligned 64-word block would touch: no traffic amplification, no LDS staging.
+#include "engine.hpp"
+
+namespace sealhip
+{
+    namespace
+    {
+        // One lane per (element, item group, row, coefficient c): the 2 * ND key words of (row, c) stay in registers across
+        // the `group` ciphertexts of the lane, two 128-bit accumulators per ciphertext, as ks_mac_items_kernel. The digit
+        // words come from column T_g[c] of ext (or of the NTT-form target row when j is the row's own digit); the key
+        // words and the stores are coalesced. prod is [element][item][2][rows][N]. Grid order (item group, row, element,
+        // coefficient): the elements of one (item group, row) are adjacent, so their re-reads of the digit rows (nd * N * 8
+        // bytes per element) come from L2. Measured against the element-major order, where an element's key stays hot
+        // instead: 8-16 % faster at 64 ciphertexts, no difference at one (profiles/r06/hoisted_rotate.txt).
+        template <int ND>
+        __global__ __launch_bounds__(kThreads) void hoist_mac_kernel(const KsDev *__restrict__ d,
+                                                                     const PrimeDev *__restrict__ primes,
+                                                                     const u64 *__restrict__ target,
+                                                                     std::size_t target_stride,
+                                                                     const u64 *__restrict__ ext, std::size_t ext_stride,
+                                                                     std::size_t ext_digit_stride, HoistElts elts,
+                                                                     u64 *__restrict__ prod, std::size_t prod_stride,
+                                                                     std::size_t count, int logn, std::size_t group,
+                                                                     std::size_t n_groups)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            // a workgroup lies inside one row (N >= kThreads, the launcher sees to it): element, row and item group come from
+            // the block index alone, so they, the row's prime and every base address are wave-uniform (scalar registers)
+            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
+            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
+            unsigned q = blockIdx.x / blocks_per_row;
+            const int el = static_cast<int>(q % elts.n);
+            q /= elts.n;
+            const int r = static_cast<int>(q % rows);
+            const std::size_t grp = q / rows;
+            if (grp >= n_groups)
+                return;
+            const std::size_t item0 = grp * group;
+            const std::size_t item1 = item0 + group < count ? item0 + group : count;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N;
+            const std::size_t src_off = row_off + elts.table[el][c];
+            const u64 *pkey = elts.key[el] + static_cast<std::size_t>(rns_idx) * N + c;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            u64 k0[ND], k1[ND], x[ND], xn[ND];
+#pragma unroll
+            for (int j = 0; j < ND; j++)
+            {
+                k0[j] = pkey[(2 * static_cast<std::size_t>(j)) * key_comp];
+                k1[j] = pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp];
+            }
+            auto load_x = [&](u64(&dst)[ND], std::size_t item) {
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                    dst[j] = j == my_digit ? target[item * target_stride + src_off]
+                                           : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
+            };
+            load_x(x, item0);
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            for (std::size_t item = item0; item < item1; item++)
+            {
+                if (item + 1 < item1)
+                    load_x(xn, item + 1);
+                u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                {
+                    mac128(lo0, hi0, x[j], k0[j]);
+                    mac128(lo1, hi1, x[j], k1[j]);
+                }
+                u64 *pp = prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + row_off + c;
+                store_stream(pp, barrett_reduce_128(lo0, hi0, p, cr0, cr1));
+                store_stream(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo1, hi1, p, cr0, cr1));
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                    x[j] = xn[j];
+            }
+        }
+
+        // Digit counts without an instance: the same lanes, the key words streamed per ciphertext (as ks_mac_kernel).
+        __global__ __launch_bounds__(kThreads) void hoist_mac_loop_kernel(const KsDev *__restrict__ d,
+                                                                          const PrimeDev *__restrict__ primes,
+                                                                          const u64 *__restrict__ target,
+                                                                          std::size_t target_stride,
+                                                                          const u64 *__restrict__ ext,
+                                                                          std::size_t ext_stride,
+                                                                          std::size_t ext_digit_stride, HoistElts elts,
+                                                                          u64 *__restrict__ prod, std::size_t prod_stride,
+                                                                          std::size_t count, int logn, int nd)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t c = i & (N - 1);
+            std::size_t q = i >> logn;
+            const int el = static_cast<int>(q % elts.n);
+            q /= elts.n;
+            const int r = static_cast<int>(q % rows);
+            const std::size_t item = q / rows;
+            if (item >= count)
+                return;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N;
+            const std::size_t src_off = row_off + elts.table[el][c];
+            const u64 *pkey = elts.key[el] + static_cast<std::size_t>(rns_idx) * N + c;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+            for (int j = 0; j < nd; j++)
+            {
+                const u64 x = j == my_digit ? target[item * target_stride + src_off]
+                                            : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
+                mac128(lo0, hi0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
+                mac128(lo1, hi1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
+            }
+            const PrimeDev &P = primes[rns_idx];
+            u64 *pp = prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + row_off + c;
+            store_stream(pp, barrett_reduce_128(lo0, hi0, P.p, P.cr0, P.cr1));
+            store_stream(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo1, hi1, P.p, P.cr0, P.cr1));
+        }
+
+        // sigma_g(c_0) of every (element, item) in one pass: out[element][item][k][N] from component 0 of ct[item]
+        // (ct_stride words apart). NTT form: out[c] = in[T_g[c]] (galois.cpp:188-214); coefficient form:
+        // out[(c * g) mod N] = +-in[c] (galois.cpp:144-186).
+        __global__ __launch_bounds__(kThreads) void hoist_galois_c0_kernel(const u64 *__restrict__ ct, std::size_t ct_stride,
+                                                                           u64 *__restrict__ out,
+                                                                           const PrimeDev *__restrict__ primes, RowMap map,
+                                                                           int logn, std::size_t count, HoistElts elts,
+                                                                           int ntt_form)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn, nmask = N - 1;
+            const int k = map.rows;
+            const std::size_t total = (static_cast<std::size_t>(elts.n) * count * k) << logn;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
+            {
+                const std::size_t c = i & nmask;
+                std::size_t q = i >> logn;
+                const int row = static_cast<int>(q % k);
+                q /= k;
+                const std::size_t item = q % count;
+                const int el = static_cast<int>(q / count);
+                const u64 *in = ct + item * ct_stride + static_cast<std::size_t>(row) * N;
+                u64 *o = out + ((static_cast<std::size_t>(el) * count + item) * k + row) * N;
+                if (ntt_form)
+                    o[c] = in[elts.table[el][c]];
+                else
+                {
+                    const u64 p = primes[map.prime[row]].p;
+                    const u64 raw = static_cast<u64>(c) * elts.elt[el];
+                    u64 v = in[c];
+                    if ((raw >> logn) & 1)
+                        v = neg_mod(v, p);
+                    o[raw & nmask] = v;
+                }
+            }
+        }
+
+        inline unsigned blocks_for(std::size_t lanes)
+        {
+            return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
+        }
+    } // namespace
+
+    hipError_t launch_hoist_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
+                                std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
+                                std::size_t ext_digit_stride, const HoistElts &elts, u64 *prod, std::size_t prod_stride,
+                                std::size_t count)
+    {
+        if (!count || !elts.n)
+            return hipSuccess;
+        if (elts.n < 0 || elts.n > kHoistMaxElts)
+            return hipErrorInvalidValue;
+        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
+        // ciphertexts per key load, as launch_ks_mac picks it: 8, or 16 / 64 when that still leaves 4096 workgroups
+        const std::size_t key_bytes = (2ull * h.nd * rows * elts.n) << (e.logn + 3);
+        const std::size_t cap = key_bytes > (std::size_t(48) << 20) ? 64 : 16;
+        std::size_t group = count < 8 ? count : 8;
+        for (std::size_t g = cap; g > 8; g >>= 1)
+            if ((((count + g - 1) / g * rows * elts.n) << e.logn) / kThreads >= 4096)
+            {
+                group = g;
+                break;
+            }
+        const std::size_t n_groups = (count + group - 1) / group;
+        const std::size_t glanes = (n_groups * rows * elts.n) << e.logn;
+        ProfScope prof(e, "hoist_mac", 0);
+#define SEALHIP_HOIST_MAC(ND)                                                                                       \
+    case ND:                                                                                                        \
+        hoist_mac_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(                                  \
+            d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, prod, prod_stride, count, \
+            e.logn, group, n_groups);                                                                \
+        break;
+        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
+        {
+            SEALHIP_HOIST_MAC(1)
+            SEALHIP_HOIST_MAC(2)
+            SEALHIP_HOIST_MAC(3)
+            SEALHIP_HOIST_MAC(4)
+            SEALHIP_HOIST_MAC(5)
+            SEALHIP_HOIST_MAC(6)
+            SEALHIP_HOIST_MAC(7)
+            SEALHIP_HOIST_MAC(8)
+            SEALHIP_HOIST_MAC(9)
+            SEALHIP_HOIST_MAC(10)
+            SEALHIP_HOIST_MAC(11)
+            SEALHIP_HOIST_MAC(12)
+            SEALHIP_HOIST_MAC(13)
+            SEALHIP_HOIST_MAC(14)
+            SEALHIP_HOIST_MAC(15)
+            SEALHIP_HOIST_MAC(16)
+        default: // more than 16 digits, or a ring smaller than a workgroup
+            hoist_mac_loop_kernel<<<blocks_for((count * rows * elts.n) << e.logn), kThreads, 0, e.lane().stream>>>(
+                d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, prod, prod_stride, count, e.logn,
+                h.nd);
+        }
+#undef SEALHIP_HOIST_MAC
+        return hipGetLastError();
+    }
+
+    hipError_t launch_hoist_galois_c0(const Engine &e, const u64 *ct, std::size_t ct_stride, u64 *out, std::size_t count,
+                                      const RowMap &map_q, const HoistElts &elts, bool ntt_form)
+    {
+        const std::size_t total = (static_cast<std::size_t>(elts.n) * count * map_q.rows) << e.logn;
+        if (total == 0)
+            return hipSuccess;
+        ProfScope prof(e, "hoist_galois", 0);
+        hoist_galois_c0_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(ct, ct_stride, out, e.d_primes, map_q, e.logn,
+                                                                                 count, elts, ntt_form ? 1 : 0);
+        return hipGetLastError();
+    }
+} // namespace sealhip

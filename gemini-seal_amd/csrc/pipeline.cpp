@@ -47,16 +47,22 @@ namespace sealhip
             return ((words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255));
         }
 
+        // one (length, entries per pass) pair of Lane::chunk_log, the oldest of 64 dropped
+        void log_chunk(Engine &e, std::size_t length, std::size_t per_pass)
+        {
+            auto &log = e.lane().chunk_log;
+            if (log.size() >= 64)
+                log.erase(log.begin());
+            log.emplace_back(length, per_pass);
+        }
+
         // how many items fit the arena, given the padded byte need of one item (sum over its buffers)
         std::size_t plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers)
         {
             const std::size_t budget = workspace_budget_bytes(e);
             std::size_t chunk = budget / (bytes_per_item ? bytes_per_item : 1);
             chunk = std::max<std::size_t>(1, std::min(chunk, count));
-            auto &log = e.lane().chunk_log;
-            if (log.size() >= 64)
-                log.erase(log.begin());
-            log.emplace_back(count, chunk);
+            log_chunk(e, count, chunk);
             e.ws_reserve(e.lane().ws_floor + chunk * bytes_per_item + static_cast<std::size_t>(n_buffers) * 256);
             return chunk;
         }
@@ -130,60 +136,32 @@ namespace sealhip
         };
     } // namespace
 
-    // ------------------------------------------------------------------------------------------
-    // switch_key_inplace (evaluator.cpp:2259-2368)
-    // ------------------------------------------------------------------------------------------
-    void op_switch_key(Engine &e, int k, u64 *ct, std::size_t ct_stride, const u64 *target, std::size_t target_stride,
-                       std::size_t count, const KSwitchKey &key, const u64 *c0_src, std::size_t c0_stride, const KsSplit *split)
+    namespace
     {
-        if (k > e.k_first)
-            throw std::invalid_argument("key switching needs a ciphertext level");
-        LevelTools &lt = e.level(k);
-        const KsDev &h = lt.h_ks;
-        const bool finish = split && split->partial_sum;   // latency mode, after the all-reduce
-        const bool partial = split && split->partial_out;  // latency mode, before it
-        if (!finish && static_cast<int>(key.n_digits) < h.nd)
-            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        const int dj0 = partial ? split->j0 : 0, dj1 = partial ? split->j1 : h.nd;
-        if (dj0 < 0 || dj0 > dj1 || dj1 > h.nd)
-            throw std::invalid_argument("digit range out of bounds");
-        const std::size_t N = e.n;
-        const int rows = k + e.nsp, nd = h.nd;
-        const bool ckks = e.scheme == 2;
-        const bool strict_bfv = e.mode_strict && !ckks;
-        // per item words
-        const std::size_t w_coeff = (ckks || strict_bfv) ? static_cast<std::size_t>(k) * N : 0;
-        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
-        const std::size_t w_prod = 2ull * rows * N;
-        const std::size_t w_temp = 2ull * k * N;
-        const std::size_t per_item = switch_key_item_bytes(e, k);
-        if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
-            throw std::logic_error("internal: arena accounting mismatch");
-        const RowMap map_q = lt.map_q;
-        const RowMap map_rows = lt.map_key;
-        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
-            u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
-            u64 *ext = e.ws_alloc(w_ext * m);
-            u64 *prod = e.ws_alloc(w_prod * m);
-            u64 *temp = e.ws_alloc(w_temp * m);
-            if (partial)
-                prod = split->partial_out + off * w_prod;
-            if (finish)
-                prod = split->partial_sum + off * w_prod;
-            const u64 *tg = finish ? nullptr : target + off * target_stride;
-            u64 *ctp = partial ? nullptr : ct + off * ct_stride;
-            const u64 *c0p = c0_src ? c0_src + off * c0_stride : nullptr;
+        // The part of the key switch that does not depend on the key (evaluator.cpp:2302-2322): the digits [dj0, dj1) of m
+        // targets, extended to every row outside their bundle and transformed, into ext (digit-major); returns the rows the
+        // inner product reads inside a bundle (the targets themselves, or their transform in coeff for STRICT BFV).
+        struct KsRows
+        {
+            const u64 *inb;
+            std::size_t inb_stride;
+        };
+        KsRows ks_digits(Engine &e, LevelTools &lt, int k, const u64 *tg, std::size_t target_stride, std::size_t m, u64 *coeff,
+                         u64 *ext, int dj0, int dj1)
+        {
+            const KsDev &h = lt.h_ks;
+            const std::size_t N = e.n;
+            const int rows = k + e.nsp;
+            const bool ckks = e.scheme == 2;
+            const bool strict_bfv = e.mode_strict && !ckks;
+            const RowMap map_q = lt.map_q;
+            const RowMap map_rows = lt.map_key;
             const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
             const std::size_t ext_digit = ext_item * m; // digit-major
-
-            if (finish)
-                // the summed canonical partials (below ranks * p < 2^63) back to canonical residues: from here on every word
-                // is what the unsplit inner product (:2341-2349) leaves
-                check(launch_poly_op(e, PolyOp::Mod63, prod, nullptr, 0, prod, m * 2 * rows, map_rows), "mod(partial sum)");
             // Step 1 (:2302-2307): CKKS bundles go back to coefficient form (canonical inverse NTT)
             const u64 *src = tg;
             std::size_t src_stride = target_stride;
-            if (ckks && !finish)
+            if (ckks)
             {
                 // (valid ciphertext rows are below p and the canonicalising top kernel follows: any representative will do)
                 if (ntt_can_gather(e)) // the inverse kernel reads the target rows where they are
@@ -227,9 +205,9 @@ namespace sealhip
                 if (bounds::fwd_lazy_admits(pmax, e.logn)) // (inputs below 2p: the case the recurrence in ntt_bounds.hpp walks)
                     modup_mode = 0;
             }
-            if (!gather && !finish)
+            if (!gather)
                 check(launch_ks_modup(e, lt.d_ks, h, src, src_stride, ext, ext_item, ext_digit, m, -1), "modup");
-            for (int j = dj0; j < dj1 && !finish; j++)
+            for (int j = dj0; j < dj1; j++)
             {
                 RowMap mj = map_rows;
                 const int r0 = j * e.nsp, r1 = std::min(r0 + e.nsp, k);
@@ -262,7 +240,7 @@ namespace sealhip
             // STRICT transforms the coefficient-form BFV rows first
             const u64 *inb = tg;
             std::size_t inb_stride = target_stride;
-            if (strict_bfv && !finish)
+            if (strict_bfv)
             {
                 if (ntt_can_gather(e))
                 {
@@ -283,12 +261,22 @@ namespace sealhip
                 inb = coeff;
                 inb_stride = static_cast<std::size_t>(k) * N;
             }
-            // Step 3b + 4 (:2326-2349): 128-bit inner product over the digits, reduced
-            if (!finish)
-                check(launch_ks_mac(e, lt.d_ks, h, inb, inb_stride, ext, ext_item, ext_digit, key.d_data, prod, w_prod, m, dj0, dj1),
-                      "mac");
-            if (partial)
-                return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
+            return KsRows{ inb, inb_stride };
+        }
+
+        // The part after the inner product (evaluator.cpp:2351-2366): the m x 2 reduced products go through
+        // rescale_special_rns_inplace and are added into the ciphertexts (or, with c0p, stored as (c0p + r0, r1)).
+        // sink: the transparency flags of these m ciphertexts (null: none).
+        void ks_finish(Engine &e, LevelTools &lt, int k, u64 *prod, u64 *temp, u64 *ctp, std::size_t ct_stride, const u64 *c0p,
+                       std::size_t c0_stride, std::size_t m, unsigned *sink)
+        {
+            const KsDev &h = lt.h_ks;
+            const std::size_t N = e.n;
+            const int rows = k + e.nsp;
+            const bool ckks = e.scheme == 2;
+            const RowMap map_q = lt.map_q;
+            const RowMap map_rows = lt.map_key;
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
             if (!ckks)
             {
                 // BFV: every row of both products goes back to coefficient form in one launch (the reference does the
@@ -297,7 +285,7 @@ namespace sealhip
                 const bool defer = ntt_can_defer_top(e, k);
                 // (ks_moddown_bfv reduces what it reads canonically: any representative below 2p will do)
                 check(launch_ntt(e, prod, m * 2 * rows, map_rows, true, (defer ? kNttDeferTop : 0) | kNttAnyRep), "intt(prod)");
-                SinkArm arm(e, sink_at(e, off)); // (component 1 of the m ciphertexts of this chunk)
+                SinkArm arm(e, sink); // (component 1 of the m ciphertexts of this chunk)
                 check(launch_ks_moddown_bfv(e, lt.d_ks, h, prod, ext_item, ctp, ct_stride, 2 * m, defer, c0p, c0_stride),
                       "moddown_bfv");
                 return;
@@ -341,7 +329,7 @@ namespace sealhip
                     ns.md.ct_stride = ct_stride;
                     ns.md.c0_src = c0p;
                     ns.md.c0_stride = c0_stride;
-                    ns.md.tflags = sink_at(e, off);
+                    ns.md.tflags = sink;
                 }
                 ns.aux_p = p_special;
                 ns.aux_cr1 = HostModulus(p_special).cr1;
@@ -368,11 +356,74 @@ namespace sealhip
             }
             if (!fold_store)
             {
-                SinkArm arm(e, sink_at(e, off));
+                SinkArm arm(e, sink);
                 check(launch_ks_moddown_post(e, lt.d_ks, h, prod, ext_item, temp, static_cast<std::size_t>(k) * N, ctp,
                                              ct_stride, 2 * m, 1, c0p, c0_stride),
                       "moddown_post");
             }
+        }
+    } // namespace
+
+    // ------------------------------------------------------------------------------------------
+    // switch_key_inplace (evaluator.cpp:2259-2368)
+    // ------------------------------------------------------------------------------------------
+    void op_switch_key(Engine &e, int k, u64 *ct, std::size_t ct_stride, const u64 *target, std::size_t target_stride,
+                       std::size_t count, const KSwitchKey &key, const u64 *c0_src, std::size_t c0_stride, const KsSplit *split)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        LevelTools &lt = e.level(k);
+        const KsDev &h = lt.h_ks;
+        const bool finish = split && split->partial_sum;   // latency mode, after the all-reduce
+        const bool partial = split && split->partial_out;  // latency mode, before it
+        if (!finish && static_cast<int>(key.n_digits) < h.nd)
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const int dj0 = partial ? split->j0 : 0, dj1 = partial ? split->j1 : h.nd;
+        if (dj0 < 0 || dj0 > dj1 || dj1 > h.nd)
+            throw std::invalid_argument("digit range out of bounds");
+        const std::size_t N = e.n;
+        const int rows = k + e.nsp, nd = h.nd;
+        const bool ckks = e.scheme == 2;
+        const bool strict_bfv = e.mode_strict && !ckks;
+        // per item words
+        const std::size_t w_coeff = (ckks || strict_bfv) ? static_cast<std::size_t>(k) * N : 0;
+        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
+        const std::size_t w_prod = 2ull * rows * N;
+        const std::size_t w_temp = 2ull * k * N;
+        const std::size_t per_item = switch_key_item_bytes(e, k);
+        if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
+            throw std::logic_error("internal: arena accounting mismatch");
+        const RowMap map_rows = lt.map_key;
+        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
+            u64 *ext = e.ws_alloc(w_ext * m);
+            u64 *prod = e.ws_alloc(w_prod * m);
+            u64 *temp = e.ws_alloc(w_temp * m);
+            if (partial)
+                prod = split->partial_out + off * w_prod;
+            if (finish)
+                prod = split->partial_sum + off * w_prod;
+            const u64 *tg = finish ? nullptr : target + off * target_stride;
+            u64 *ctp = partial ? nullptr : ct + off * ct_stride;
+            const u64 *c0p = c0_src ? c0_src + off * c0_stride : nullptr;
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            const std::size_t ext_digit = ext_item * m; // digit-major
+
+            if (finish)
+                // the summed canonical partials (below ranks * p < 2^63) back to canonical residues: from here on every word
+                // is what the unsplit inner product (:2341-2349) leaves
+                check(launch_poly_op(e, PolyOp::Mod63, prod, nullptr, 0, prod, m * 2 * rows, map_rows), "mod(partial sum)");
+            if (!finish)
+            {
+                const KsRows in_bundle = ks_digits(e, lt, k, tg, target_stride, m, coeff, ext, dj0, dj1);
+                // Step 3b + 4 (:2326-2349): 128-bit inner product over the digits, reduced
+                check(launch_ks_mac(e, lt.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_digit, key.d_data, prod,
+                                    w_prod, m, dj0, dj1),
+                      "mac");
+            }
+            if (partial)
+                return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
+            ks_finish(e, lt, k, prod, temp, ctp, ct_stride, c0p, c0_stride, m, sink_at(e, off));
         });
     }
 
@@ -784,6 +835,98 @@ namespace sealhip
             } base_reset{ e.lane() };
             op_switch_key(e, k, c, 2 * poly, scratch + poly, 2 * poly, m, key, scratch, 2 * poly);
         }
+    }
+    // ------------------------------------------------------------------------------------------
+    // Hoisted rotation: n_elts automorphisms of the same ciphertexts with one decomposition of c_1
+    // ------------------------------------------------------------------------------------------
+    // out_g = finish( (sigma_g(c_0), 0), sum_j sigma_g(D_j) (.) K_g ), D_j the digits op_switch_key forms for the target c_1.
+    // The digits are built once per item (ks_digits); per element there is the inner product, which reads them through T_g
+    // (hoist.hip), sigma_g(c_0), and the mod-down (ks_finish). out is element-major, out[slot][count][2][k][N]: element i goes
+    // to slot slots[i] (increasing; null: slot i), so a caller can leave slots out for results it fills itself
+    // (rotate_vector_many's step 0) and still have one decomposition for all the others.
+    void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
+                              const KSwitchKey *const *keys, std::size_t n_elts, u64 *out, const std::uint32_t *slots)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        const bool ckks = e.scheme == 2;
+        if (!ckks && !e.mode_strict)
+            // (the fork multiplies the coefficient-form target rows as they are, SURVEY F3: that key switch does not decrypt,
+            //  and there is no reference behaviour to reproduce for an operation the fork does not have)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
+        LevelTools &ld = e.level(k);
+        const KsDev &h = ld.h_ks;
+        const int nd = h.nd, rows = k + e.nsp;
+        for (std::size_t i = 0; i < n_elts; i++)
+        {
+            if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
+                throw std::invalid_argument("Galois element is not valid"); // :1880-1883
+            if (static_cast<int>(keys[i]->n_digits) < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        if (!n_elts || !count)
+            return;
+        std::vector<const std::uint32_t *> tables(n_elts);
+        for (std::size_t i = 0; i < n_elts; i++)
+            tables[i] = e.galois_table(elts[i]); // (resident after the first call: the condition for a capture)
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t w_coeff = poly; // (CKKS: c_1 in coefficient form; STRICT BFV: c_1 in NTT form)
+        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
+        const std::size_t w_prod = 2ull * rows * N;
+        const std::size_t w_temp = 2ull * poly;
+        // arena of one item: the digits once, and per element the products, the mod-down's temporaries and sigma_g(c_0)
+        const std::size_t base_bytes = (w_coeff + w_ext) * sizeof(u64), elt_bytes = (w_prod + w_temp + poly) * sizeof(u64);
+        // when not even one item fits with all its elements, the element list is walked in passes and the digits stay live
+        std::size_t pass = n_elts;
+        const std::size_t budget = workspace_budget_bytes(e);
+        if (base_bytes + pass * elt_bytes > budget)
+        {
+            pass = budget > base_bytes ? (budget - base_bytes) / elt_bytes : 0;
+            pass = std::max<std::size_t>(1, std::min(pass, n_elts));
+            log_chunk(e, n_elts, pass); // (the element split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        }
+        unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext, in output order
+        for_chunks(e, count, base_bytes + pass * elt_bytes, 5, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = e.ws_alloc(w_coeff * m);
+            u64 *ext = e.ws_alloc(w_ext * m);
+            u64 *prod = e.ws_alloc(w_prod * m * pass);
+            u64 *temp = e.ws_alloc(w_temp * m * pass);
+            u64 *gal = e.ws_alloc(poly * m * pass);
+            const u64 *c = ct + off * 2 * poly;
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            const KsRows in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
+            for (std::size_t e0 = 0; e0 < n_elts; e0 += pass)
+            {
+                const std::size_t n1 = std::min(pass, n_elts - e0);
+                for (std::size_t l0 = 0; l0 < n1; l0 += kHoistMaxElts)
+                {
+                    HoistElts he{};
+                    he.n = static_cast<int>(std::min<std::size_t>(kHoistMaxElts, n1 - l0));
+                    for (int i = 0; i < he.n; i++)
+                    {
+                        he.elt[i] = elts[e0 + l0 + i];
+                        he.table[i] = tables[e0 + l0 + i];
+                        he.key[i] = keys[e0 + l0 + i]->d_data;
+                    }
+                    check(launch_hoist_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m, he,
+                                           prod + l0 * m * w_prod, w_prod, m),
+                          "hoist_mac");
+                    check(launch_hoist_galois_c0(e, c, 2 * poly, gal + l0 * m * poly, m, ld.map_q, he, ckks), "galois(c0)");
+                }
+                // the back half of the key switch over the products of this pass: when the chunk is the whole batch the
+                // outputs of consecutive slots are contiguous and go as one batch, else one batch per element
+                const auto slot = [&](std::size_t i) { return slots ? static_cast<std::size_t>(slots[i]) : i; };
+                for (std::size_t l = 0, run; l < n1; l += run)
+                {
+                    run = 1;
+                    while (m == count && l + run < n1 && slot(e0 + l + run) == slot(e0 + l + run - 1) + 1)
+                        run++;
+                    const std::size_t first = slot(e0 + l) * count + off; // (output ciphertext, and its transparency flag)
+                    ks_finish(e, ld, k, prod + l * m * w_prod, temp + l * m * w_temp, out + first * 2 * poly, 2 * poly,
+                              gal + l * m * poly, poly, run * m, sink ? sink + first : nullptr);
+                }
+            }
+        });
     }
     // multiply_plain_normal (evaluator.cpp:1475-1603) for parameters with fast plain lift (every q_i > t): lift the
     // plaintext into the RNS base, canonical NTT, then per ciphertext polynomial lazy NTT -> dyadic product ->

@@ -124,18 +124,22 @@ namespace sealhip_host
         // thread). Each checked operation gets its own slot as the lane's transparency sink; the sink writes a non-zero word
         // for a result that is NOT transparent. The slots are read at the thread's next host-visible point.
         static constexpr std::size_t kRingSlots = 256;
-        std::uint32_t *transparency_slot(const void *evaluator) const
+        // (count consecutive slots for an operation with that many results: the hoisted rotations)
+        std::uint32_t *transparency_slot(const void *evaluator, std::size_t count = 1) const
         {
+            if (count > kRingSlots)
+                throw std::invalid_argument("too many results for one checked operation");
             Ring &r = ring(evaluator);
-            if (r.used == kRingSlots)
+            if (r.used + count > kRingSlots)
                 check_transparency(); // a full ring is a host-visible point
-            return r.flags + r.used++;
+            std::uint32_t *slot = r.flags + r.used;
+            r.used += count;
+            return slot;
         }
-        void transparency_unslot(const void *evaluator) const // the operation failed before its result existed
+        void transparency_unslot(const void *evaluator, std::size_t count = 1) const // the operation failed before its result existed
         {
             Ring &r = ring(evaluator);
-            if (r.used)
-                r.used--;
+            r.used -= count < r.used ? count : r.used;
         }
         // reads the calling thread's rings (one synchronisation each); throws the reference's std::logic_error when a
         // checked result was transparent
@@ -753,6 +757,66 @@ namespace sealhip_host
             conjugate_internal(encrypted, galois_keys);
         }
 
+        // Hoisted rotation (sealhip_evaluator_apply_galois_many): `encrypted` under every element of
+        // galois_elts with one decomposition of its second polynomial; destinations[i] is the result of galois_elts[i], with
+        // the operand's scale / NTT form (and, for a host type, its parms_id). The reference has no such method: each result
+        // decrypts like apply_galois's, with noise of the same bound, but is not the same words. An element without its key
+        // in galois_keys -> std::invalid_argument("Galois key not present"). BFV needs a STRICT context.
+        // The ABI writes all results back to back into one block. A resident destination owns a pool block of its own, so
+        // every result but a single one is copied once more on the device (2 k N words each, stream-ordered); and the
+        // deferred transparency check takes one ring slot per result, so a resident call takes at most 256 elements
+        // (std::invalid_argument("too many results for one checked operation")): split longer lists. Host destinations
+        // have neither: they are downloaded straight from the one block, and not checked.
+        template <class C, IfCt<C> = 0>
+        void apply_galois_many(const C &encrypted, const std::vector<std::uint32_t> &galois_elts,
+                               const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<C> &destinations)
+        {
+            check_galois_operand(encrypted);
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (std::uint32_t elt : galois_elts)
+            {
+                auto it = galois_keys.find(elt);
+                if (it == galois_keys.end() || !it->second)
+                    throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
+                raw.push_back(it->second->get());
+            }
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), count = galois_elts.size(), words = 2 * k * n;
+            if (count == 0)
+                return destinations.clear();
+            Dev c = dev_in(encrypted, words), o = dev_out(count * words);
+            Check chk = checked(encrypted, count);
+            throw_on(sealhip_evaluator_apply_galois_many(ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(), raw.data(),
+                                                         std::uint32_t(count), o.ptr()));
+            chk.done();
+            scatter(encrypted, o, count, words, destinations);
+        }
+        // The same by rotation steps (sealhip_evaluator_rotate_vector_many): rotate_vector's steps for CKKS, rotate_rows'
+        // for BFV; a step of 0 copies the operand; no non-adjacent-form fallback (a chain cannot share a decomposition)
+        template <class C, IfCt<C> = 0>
+        void rotate_vector_many(const C &encrypted, const std::vector<int> &steps,
+                                const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<C> &destinations)
+        {
+            check_galois_operand(encrypted);
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (auto &kv : galois_keys)
+                if (kv.second)
+                {
+                    elts.push_back(kv.first);
+                    raw.push_back(kv.second->get());
+                }
+            std::vector<std::int32_t> st(steps.begin(), steps.end());
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), count = st.size(), words = 2 * k * n;
+            if (count == 0)
+                return destinations.clear();
+            Dev c = dev_in(encrypted, words), o = dev_out(count * words);
+            Check chk = checked(encrypted, count);
+            throw_on(sealhip_evaluator_rotate_vector_many(ctx_.get(), std::uint32_t(k), c.ptr(), 1, st.data(), std::uint32_t(count),
+                                                          elts.data(), raw.data(), std::uint32_t(elts.size()), o.ptr()));
+            chk.done();
+            scatter(encrypted, o, count, words, destinations);
+        }
+
         // Evaluator::mod_switch_to_inplace (evaluator.cpp:1038-1060) / rescale_to_inplace (:1128-1165). The ABI names a level by
         // its number of primes k (the chain drops one prime per level, context.cpp:423-431); for seal::Ciphertext the
         // binding maps the parms_id argument to it.
@@ -1297,13 +1361,13 @@ namespace sealhip_host
         {
         public:
             Check() = default;
-            Check(const Context &c, const void *owner) : c_(&c), owner_(owner)
+            Check(const Context &c, const void *owner, std::size_t count = 1) : c_(&c), owner_(owner), count_(count)
             {
-                std::uint32_t *slot = c.transparency_slot(owner);
-                const long hr = sealhip_transparency_sink(c.get(), slot, 1);
+                std::uint32_t *slot = c.transparency_slot(owner, count);
+                const long hr = sealhip_transparency_sink(c.get(), slot, count);
                 if (hr != SEALHIP_S_OK)
                 {
-                    c.transparency_unslot(owner);
+                    c.transparency_unslot(owner, count);
                     c_ = nullptr;
                     throw_on(hr);
                 }
@@ -1323,16 +1387,56 @@ namespace sealhip_host
                     return;
                 (void)sealhip_transparency_sink(c_->get(), nullptr, 0);
                 if (!ok_)
-                    c_->transparency_unslot(owner_);
+                    c_->transparency_unslot(owner_, count_);
             }
 
         private:
             const Context *c_ = nullptr;
             const void *owner_ = nullptr;
+            std::size_t count_ = 1;
             bool ok_ = false;
         };
-        Check checked(const CT &) { return Check(); }
-        Check checked(const DeviceCiphertext &) { return Check(ctx_, this); }
+        Check checked(const CT &, std::size_t = 1) { return Check(); }
+        Check checked(const DeviceCiphertext &, std::size_t count = 1) { return Check(ctx_, this, count); }
+
+        // the n results of a hoisted rotation, back to back in `o`, become the destinations (metadata of the operand)
+        void scatter(const CT &src, Dev &o, std::size_t n, std::size_t words, std::vector<CT> &dst)
+        {
+            dst.assign(n, src);
+            for (std::size_t i = 0; i < n; i++)
+                throw_on(sealhip_memcpy_d2h(ctx_.get(), dst[i].data(), o.ptr() + i * words, words * 8));
+        }
+        void scatter(const DeviceCiphertext &src, Dev &o, std::size_t n, std::size_t words, std::vector<DeviceCiphertext> &dst)
+        {
+            std::vector<DeviceCiphertext> next;
+            next.reserve(n);
+            for (std::size_t i = 0; i < n; i++)
+            {
+                next.emplace_back(ctx_);
+                if (n == 1)
+                    next[i].adopt(o.st->release(), o.st->words(), 2, src.coeff_modulus_size());
+                else
+                {
+                    Staged one(ctx_, words); // (each destination owns a pool block of its own)
+                    throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), o.ptr() + i * words, words * 8));
+                    next[i].adopt(one.release(), words, 2, src.coeff_modulus_size());
+                }
+                next[i].copy_meta(src);
+            }
+            dst.swap(next);
+        }
+        // apply_galois_inplace's checks on the operand (evaluator.cpp:1848-1887)
+        template <class C>
+        void check_galois_operand(const C &encrypted) const
+        {
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            if (bfv && encrypted.is_ntt_form())
+                throw std::invalid_argument("BFV encrypted cannot be in NTT form");
+            if (!bfv && !encrypted.is_ntt_form())
+                throw std::invalid_argument("CKKS encrypted must be in NTT form");
+            if (encrypted.size() != 2)
+                throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
+        }
 
         // the host checks of multiply / square (evaluator.cpp:238-249, :276-279, :449-452)
         template <class C>

@@ -129,6 +129,9 @@ SYMBOLS = {
     "sealhip_debug_chunk_log": [_vp, _vp, _sz, _vp],
     "sealhip_modulo_poly_coeffs_63": [_vp, _vp, _sz, _u32, _u32, _vp],
     "sealhip_evaluator_rotate_vector": [_vp, _u32, _vp, _sz, _i32, C.POINTER(_u32), C.POINTER(_vp), _u32],
+    "sealhip_evaluator_apply_galois_many": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_rotate_vector_many": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp), _u32,
+                                             _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -908,6 +911,26 @@ class Evaluator:
         ea = (_u32 * max(1, len(elts)))(*elts)
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
         _check(lib().sealhip_evaluator_rotate_vector(self.ctx.handle, k, _ptr(ct), count, steps, ea, ka, len(elts)))
+
+    def apply_galois_many(self, ct, k, count, elts, keys, out):
+        """Hoisted rotation (sealhip_evaluator_apply_galois_many): `count` size-2 ciphertexts under every Galois element of
+        `elts` with one decomposition of c_1; keys[i] is the KSwitchKeys of elts[i]. out: len(elts) x count x 2 x k x N,
+        element-major; ct is not modified. Not the words of repeated apply_galois_inplace."""
+        elts = [int(g) for g in elts]
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[key.handle for key in keys])
+        _check(lib().sealhip_evaluator_apply_galois_many(self.ctx.handle, k, _ptr(ct), count, ea, ka, len(elts), _ptr(out)))
+
+    def rotate_vector_many(self, ct, k, count, steps, galois_keys, out):
+        """The same by rotation steps (sealhip_evaluator_rotate_vector_many): out: len(steps) x count x 2 x k x N; step 0
+        copies the input, a step without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
+        steps = [int(st) for st in steps]
+        elts = list(galois_keys.keys())
+        sa = (_i32 * max(1, len(steps)))(*steps)
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts),
+                                                          _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

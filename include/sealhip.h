@@ -152,7 +152,10 @@ long sealhip_debug_ntt_handoff(sealhip_context *ctx, uint32_t spin_limit, int32_
 /* How the calling thread's last operations walked their batches: operations whose temporaries do not fit the lane's arena for
    the whole batch process it in chunks of items. Writes up to capacity_pairs (batch size, items per
    chunk) pairs, oldest first, and clears the log (at most the last 64 operations are kept). bench.py uses it to verify the
-   first and last item of every chunk of the timed batch against the oracle. */
+   first and last item of every chunk of the timed batch against the oracle. One operation logs a second kind of pair:
+   sealhip_evaluator_apply_galois_many / _rotate_vector_many, when not even one ciphertext fits the arena with all its Galois
+   elements, walk the element list in passes and log (elements, elements per pass) immediately ahead of their
+   (batch size, items per chunk) pair -- which is then (count, 1). */
 long sealhip_debug_chunk_log(sealhip_context *ctx, size_t *count_chunk_pairs, size_t capacity_pairs, size_t *written);
 
 /* Measurement hook (bench.py roofline.valu_ceiling): the rate at which this device executes nothing but the butterflies of
@@ -416,6 +419,36 @@ long sealhip_modulo_poly_coeffs_63(sealhip_context *ctx, const uint64_t *a, size
 long sealhip_evaluator_rotate_vector(sealhip_context *ctx, uint32_t k, uint64_t *ct, size_t count, int32_t steps,
                                      const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
                                      uint32_t n_keys);
+
+/* Hoisted rotation (Halevi-Shoup): every ciphertext of the batch under n_elts Galois elements with ONE
+   decomposition of c_1. Of apply_galois_inplace + switch_key_inplace (evaluator.cpp:1841-1943, 2259-2368) the inverse
+   transform, the mod-up and the forward transforms of the digits do not depend on the element and run once; per element
+   remain the inner product with the key, sigma_g(c_0) and the mod-down. The fork has no such method, and the result is NOT
+   the words of n_elts calls of sealhip_evaluator_apply_galois (the automorphism does not commute with the mod-up): it
+   decrypts to the same plaintext with noise of the same bound. What defines it, word for word in the context's mode, is the
+   restatement over the oracle in tests/hoist_ref.py: with D_j the rows switch_key_inplace multiplies with digit j of the key
+   for target c_1 (:2302-2322) and T_g the NTT-form table of the element (galois.cpp:18-47),
+       prod_g[l][r][c] = ( sum_j D_j[r][T_g[c]] * K_g[j][l][row_prime r][c] ) mod p_r   (canonical),
+       out_g = the key switch's finish (:2351-2366) of prod_g added into (sigma_g(c_0), 0).
+   CKKS in both modes and BFV in STRICT mode; BFV in PARITY mode is E_INVALIDARG (that key switch, SURVEY F3, does not
+   decrypt, and there is no reference behaviour to reproduce for an operation the fork does not have).
+   ct: count x 2 x k x N, not modified; out: n_elts x count x 2 x k x N, ELEMENT-major (each rotation is a contiguous batch);
+   out must not overlap ct. galois_keys[i] is the key of galois_elts[i].
+   Checks: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, an even element or
+   one >= 2N, a key with fewer digits than the level, BFV in PARITY mode -> E_INVALIDARG; then n_elts == 0 or count == 0 ->
+   S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION. With a transparency sink: one flag per output
+   ciphertext, in output order (n_elts * count flags). Nothing synchronises; capturable once the Galois tables of the
+   elements are resident (after one call with them), as sealhip_evaluator_apply_galois. */
+long sealhip_evaluator_apply_galois_many(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                         const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                         uint32_t n_elts, uint64_t *out);
+/* The same by rotation steps (galois_elt_from_step, galois.cpp:49-91): out: n_steps x count x 2 x k x N. A step of 0 is a
+   copy of the input, wherever it stands in the list: all other steps still share one decomposition. galois_elts[i] is the Galois element of galois_keys[i] (n_keys of them); a step whose key is absent
+   -> E_INVALIDARG ("Galois key not present"): there is no non-adjacent-form fallback here, a chain of dependent rotations
+   cannot share a decomposition. Otherwise as sealhip_evaluator_apply_galois_many (S_OK without work when n_steps == 0). */
+long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                          const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                          const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
 
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
