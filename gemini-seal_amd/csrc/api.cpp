@@ -1865,6 +1865,111 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
     });
 }
 
+/* ------------------------------------------------------------------ weighted sums of rotations */
+namespace
+{
+    // elts: the elements (1 = the identity, which needs no key). The checks that need no device come first and run on
+    // host-only contexts too (the order the header documents).
+    void do_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                   const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys,
+                                   const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+    {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+        for (size_t i = 0; i < elts.size(); i++)
+        {
+            if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
+                throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
+            if (elts[i] != 1 && keys[i]->key.n_digits < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
+        if (count && (elts.empty() || !n_sums))
+            throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        const std::size_t out_words = n_sums * count * item, w_words = n_sums * elts.size() * e.key_moduli.size() * e.n;
+        if (o < in + count * item && in < o + out_words)
+            throw std::invalid_argument("out must not overlap ct");
+        if (o < w + w_words && w < o + out_words)
+            throw std::invalid_argument("out must not overlap plain_ntt");
+        SinkScope sink(e, static_cast<size_t>(n_sums) * count);
+        sink.begin();
+        std::vector<const KSwitchKey *> run_keys(elts.size(), nullptr);
+        for (size_t i = 0; i < elts.size(); i++)
+            if (elts[i] != 1)
+                run_keys[i] = &keys[i]->key;
+        op_apply_galois_dot_plain(e, static_cast<int>(k), in, count, elts.data(), run_keys.data(), elts.size(), w, n_sums, o);
+    }
+} // namespace
+
+long sealhip_evaluator_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                              const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                              uint32_t n_elts, const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(plain_ntt);
+    REQUIRE_PTR(out);
+    if (n_elts)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+        for (uint32_t i = 0; i < n_elts; i++)
+            if (galois_elts[i] != 1)
+                REQUIRE_PTR(galois_keys[i]);
+    }
+    return guarded([&] {
+        do_apply_galois_dot_plain(ctx, k, ct, count, std::vector<uint32_t>(galois_elts, galois_elts + n_elts),
+                                  std::vector<const sealhip_kswitch_key *>(galois_keys, galois_keys + n_elts), plain_ntt,
+                                  n_sums, out);
+    });
+}
+
+long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                               const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                               const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                               const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(plain_ntt);
+    REQUIRE_PTR(out);
+    if (n_steps)
+        REQUIRE_PTR(steps);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        std::vector<uint32_t> elts(n_steps, 1);
+        std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
+        for (uint32_t s = 0; s < n_steps; s++)
+        {
+            if (steps[s] == 0)
+                continue; // (element 1)
+            elts[s] = host_galois_elt_from_step(h.n, steps[s]);
+            for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
+                if (galois_elts[i] == elts[s])
+                    keys[s] = galois_keys[i];
+            if (!keys[s])
+                throw std::invalid_argument("Galois key not present");
+        }
+        do_apply_galois_dot_plain(ctx, k, ct, count, elts, keys, plain_ntt, n_sums, out);
+    });
+}
+
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
 
 long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

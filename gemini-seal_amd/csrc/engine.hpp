@@ -598,6 +598,27 @@ namespace sealhip
     // out[element][item][k][N] = sigma_g of component 0 of ct[item] (NTT form through T_g, else coefficient form)
     hipError_t launch_hoist_galois_c0(const Engine &e, const u64 *ct, std::size_t ct_stride, u64 *out, std::size_t count,
                                       const RowMap &map_q, const HoistElts &elts, bool ntt_form);
+    // plaintext-weighted sum of rotations: the elements of one launch with their plaintexts.
+    // w[i] = W[0][i] in key-level NTT form (n_key x N); sum s lies w_sum_stride words further. table[i] == null is the
+    // identity (the base kernel only; the inner product is never launched with one).
+    struct HoistDotElts
+    {
+        int n;
+        const std::uint32_t *table[kHoistMaxElts];
+        const u64 *key[kHoistMaxElts];
+        const u64 *w[kHoistMaxElts];
+    };
+    // acc[sum][item][2][k + nsp][N] (item stride acc_stride) = sum over the launch's elements of W[sum][i] (.) prod_{g_i},
+    // canonical; add: plus what acc holds
+    hipError_t launch_hoist_dot_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
+                                    std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
+                                    std::size_t ext_digit_stride, const HoistDotElts &elts, std::size_t w_sum_stride, u64 *acc,
+                                    std::size_t acc_stride, std::size_t count, std::size_t n_sums, bool add);
+    // out[sum * out_sum_stride + item * 2kN] = (sum_i W[sum][i] (.) sigma_i(C_0), sum_{i identity} W[sum][i] (.) C_1) on the
+    // k ciphertext rows, cn = C in NTT form (item stride 2kN); add: plus what out holds
+    hipError_t launch_hoist_dot_base(const Engine &e, const u64 *cn, const HoistDotElts &elts, std::size_t w_sum_stride,
+                                     u64 *out, std::size_t out_sum_stride, int k, std::size_t count, std::size_t n_sums,
+                                     bool add);
 
     // ---- batches of separately allocated host ciphertexts (hostbatch.cpp) ----
     struct HostBatchIO
@@ -657,6 +678,11 @@ namespace sealhip
     void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
                               const KSwitchKey *const *keys, std::size_t n_elts, u64 *out,
                               const std::uint32_t *slots = nullptr); // slots[i]: output slot of element i (null: i)
+    // sum_i W[s][i] * sigma_{g_i}(ct) with one decomposition and one mod-down per sum:
+    // out[n_sums][count][2][k][N]; plain_ntt[n_sums][n_elts][n_key][N]; keys[i] may be null where elts[i] == 1.
+    void op_apply_galois_dot_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
+                                   const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
+                                   std::size_t n_sums, u64 *out);
     void op_multiply_plain(Engine &e, int k, u64 *ct, int size, std::size_t count, const u64 *plain,
                            std::size_t plain_stride);
     // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV: plain_ntt[count][k][N]

@@ -166,6 +166,220 @@ namespace sealhip
             }
         }
 
+        // ---- plaintext-weighted sum of rotations ----
+        // acc_s[l][r][c] = sum_i W[s][i][rp(r)][c] * prod_{g_i}[l][r][c]: hoist_mac_kernel's inner product, not stored but
+        // multiplied by the plaintext word and summed over the elements of the launch in registers. A lane owns column c of
+        // one extended row for 4 / S ciphertexts and S sums: four (ciphertext, sum) slots of two 128-bit accumulators, the
+        // same 32 registers whichever way the slots are cut. The element loop is outermost and wave-uniform: the 2 * ND key
+        // words of an element are loaded once for the lane's ciphertexts, the two reduced products of a ciphertext once for
+        // the lane's sums. At most kHoistMaxElts terms below 2^122 meet in an accumulator, so it is reduced once, at the
+        // end; add != 0 adds the words a former launch of a longer element list left in acc.
+        template <int ND, int S>
+        __global__ __launch_bounds__(kThreads) void hoist_dot_mac_kernel(const KsDev *__restrict__ d,
+                                                                         const PrimeDev *__restrict__ primes,
+                                                                         const u64 *__restrict__ target,
+                                                                         std::size_t target_stride,
+                                                                         const u64 *__restrict__ ext, std::size_t ext_stride,
+                                                                         std::size_t ext_digit_stride, HoistDotElts elts,
+                                                                         std::size_t w_sum_stride, u64 *__restrict__ acc,
+                                                                         std::size_t acc_stride, std::size_t count,
+                                                                         std::size_t n_sums, int logn, int add)
+        {
+            constexpr int G = 4 / S;
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            // (a workgroup lies inside one row, as in hoist_mac_kernel: row, item group and sum group are wave-uniform)
+            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
+            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
+            unsigned q = blockIdx.x / blocks_per_row;
+            const int r = static_cast<int>(q % rows);
+            q /= rows;
+            const std::size_t sum_groups = (n_sums + S - 1) / S;
+            const std::size_t sum0 = static_cast<std::size_t>(q % sum_groups) * S;
+            const std::size_t item0 = static_cast<std::size_t>(q / sum_groups) * G;
+            if (item0 >= count)
+                return;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            u64 lo[G][S][2], hi[G][S][2];
+#pragma unroll
+            for (int g = 0; g < G; g++)
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                    lo[g][s][0] = hi[g][s][0] = lo[g][s][1] = hi[g][s][1] = 0;
+            for (int el = 0; el < elts.n; el++)
+            {
+                // Addresses are walked, not indexed: a lane's pointer advances by the wave-uniform stride from load to load.
+                // Indexed, the 2 * ND + G * ND wave-uniform offsets are loop invariants that the compiler holds in scalar
+                // registers across the element loop -- more than the 106 there are from ND = 5 on.
+                const u64 *pk = elts.key[el] + prime_off;
+                const std::size_t src_off = row_off + elts.table[el][c];
+                u64 k0[ND], k1[ND], w[S];
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                {
+                    k0[j] = pk[0];
+                    k1[j] = pk[key_comp];
+                    pk += 2 * key_comp;
+                }
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                    w[s] = sum0 + s < n_sums ? elts.w[el][(sum0 + s) * w_sum_stride + prime_off] : 0;
+                const u64 *pt = target + item0 * target_stride + src_off, *pe = ext + item0 * ext_stride + src_off;
+#pragma unroll
+                for (int g = 0; g < G; g++, pt += target_stride, pe += ext_stride)
+                {
+                    if (item0 + g >= count)
+                        break;
+                    u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+                    const u64 *px = pe;
+#pragma unroll
+                    for (int j = 0; j < ND; j++, px += ext_digit_stride)
+                    {
+                        const u64 x = j == my_digit ? *pt : *px;
+                        mac128(l0, h0, x, k0[j]);
+                        mac128(l1, h1, x, k1[j]);
+                    }
+                    const u64 p0 = barrett_reduce_128(l0, h0, p, cr0, cr1), p1 = barrett_reduce_128(l1, h1, p, cr0, cr1);
+#pragma unroll
+                    for (int s = 0; s < S; s++)
+                    {
+                        mac128(lo[g][s][0], hi[g][s][0], w[s], p0);
+                        mac128(lo[g][s][1], hi[g][s][1], w[s], p1);
+                    }
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; g++)
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                {
+                    if (item0 + g >= count || sum0 + s >= n_sums)
+                        continue;
+                    u64 *pa = acc + ((sum0 + s) * count + item0 + g) * acc_stride + row_off + c;
+                    u64 v0 = barrett_reduce_128(lo[g][s][0], hi[g][s][0], p, cr0, cr1);
+                    u64 v1 = barrett_reduce_128(lo[g][s][1], hi[g][s][1], p, cr0, cr1);
+                    if (add)
+                    {
+                        v0 = add_mod(v0, pa[0], p);
+                        v1 = add_mod(v1, pa[static_cast<std::size_t>(rows) * N], p);
+                    }
+                    store_stream(pa, v0);
+                    store_stream(pa + static_cast<std::size_t>(rows) * N, v1);
+                }
+        }
+
+        // Digit counts without an instance and rings smaller than a workgroup: one lane per (sum, item, row, c), the key
+        // words streamed per element.
+        __global__ __launch_bounds__(kThreads) void hoist_dot_mac_loop_kernel(
+            const KsDev *__restrict__ d, const PrimeDev *__restrict__ primes, const u64 *__restrict__ target,
+            std::size_t target_stride, const u64 *__restrict__ ext, std::size_t ext_stride, std::size_t ext_digit_stride,
+            HoistDotElts elts, std::size_t w_sum_stride, u64 *__restrict__ acc, std::size_t acc_stride, std::size_t count,
+            std::size_t n_sums, int logn, int nd, int add)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t c = i & (N - 1);
+            std::size_t q = i >> logn;
+            const int r = static_cast<int>(q % rows);
+            q /= rows;
+            const std::size_t item = q % count, sum = q / count;
+            if (sum >= n_sums)
+                return;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+            for (int el = 0; el < elts.n; el++)
+            {
+                const u64 *pkey = elts.key[el] + prime_off;
+                const std::size_t src_off = row_off + elts.table[el][c];
+                u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+                for (int j = 0; j < nd; j++)
+                {
+                    const u64 x = j == my_digit
+                                      ? target[item * target_stride + src_off]
+                                      : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
+                    mac128(l0, h0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
+                    mac128(l1, h1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
+                }
+                const u64 w = elts.w[el][sum * w_sum_stride + prime_off];
+                mac128(lo0, hi0, w, barrett_reduce_128(l0, h0, p, cr0, cr1));
+                mac128(lo1, hi1, w, barrett_reduce_128(l1, h1, p, cr0, cr1));
+            }
+            u64 *pa = acc + (sum * count + item) * acc_stride + row_off + c;
+            u64 v0 = barrett_reduce_128(lo0, hi0, p, cr0, cr1), v1 = barrett_reduce_128(lo1, hi1, p, cr0, cr1);
+            if (add)
+            {
+                v0 = add_mod(v0, pa[0], p);
+                v1 = add_mod(v1, pa[static_cast<std::size_t>(rows) * N], p);
+            }
+            store_stream(pa, v0);
+            store_stream(pa + static_cast<std::size_t>(rows) * N, v1);
+        }
+
+        // base_s of section 16: out[sum][item][0][r][c] = sum_i W[s][i][r][c] * C[item][0][r][T_i[c]] over every element of
+        // the launch, out[sum][item][1][r][c] = the same over the identity elements (table == null) with C[item][1][r][c].
+        // C is in NTT form, item stride 2 k N. The words of C may be any 64-bit representative: the accumulator is folded
+        // every fourth term (4 * 2^61 * 2^64 < 2^128).
+        __global__ __launch_bounds__(kThreads) void hoist_dot_base_kernel(const u64 *__restrict__ cn, HoistDotElts elts,
+                                                                          std::size_t w_sum_stride, u64 *__restrict__ out,
+                                                                          std::size_t out_sum_stride,
+                                                                          const PrimeDev *__restrict__ primes, int k, int logn,
+                                                                          std::size_t count, std::size_t n_sums, int add)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn, nmask = N - 1;
+            const std::size_t poly = static_cast<std::size_t>(k) << logn;
+            const std::size_t total = (n_sums * count * k) << logn;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
+            {
+                const std::size_t c = i & nmask;
+                std::size_t q = i >> logn;
+                const int row = static_cast<int>(q % k);
+                q /= k;
+                const std::size_t item = q % count, sum = q / count;
+                const PrimeDev &P = primes[row];
+                const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+                const std::size_t row_off = static_cast<std::size_t>(row) * N;
+                const u64 *in = cn + item * 2 * poly + row_off;
+                u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+                for (int el = 0; el < elts.n; el++)
+                {
+                    const u64 w = elts.w[el][sum * w_sum_stride + row_off + c];
+                    const std::uint32_t *tab = elts.table[el];
+                    mac128(lo0, hi0, w, in[tab ? tab[c] : c]);
+                    if (!tab)
+                        mac128(lo1, hi1, w, in[poly + c]);
+                    if ((el & 3) == 3)
+                    {
+                        lo0 = barrett_reduce_128(lo0, hi0, p, cr0, cr1);
+                        lo1 = barrett_reduce_128(lo1, hi1, p, cr0, cr1);
+                        hi0 = hi1 = 0;
+                    }
+                }
+                u64 *o = out + sum * out_sum_stride + item * 2 * poly + row_off + c;
+                u64 v0 = barrett_reduce_128(lo0, hi0, p, cr0, cr1), v1 = barrett_reduce_128(lo1, hi1, p, cr0, cr1);
+                if (add)
+                {
+                    v0 = add_mod(v0, o[0], p);
+                    v1 = add_mod(v1, o[poly], p);
+                }
+                o[0] = v0;
+                o[poly] = v1;
+            }
+        }
+
         inline unsigned blocks_for(std::size_t lanes)
         {
             return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
@@ -237,6 +451,79 @@ namespace sealhip
         ProfScope prof(e, "hoist_galois", 0);
         hoist_galois_c0_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(ct, ct_stride, out, e.d_primes, map_q, e.logn,
                                                                                  count, elts, ntt_form ? 1 : 0);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_hoist_dot_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
+                                    std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
+                                    std::size_t ext_digit_stride, const HoistDotElts &elts, std::size_t w_sum_stride, u64 *acc,
+                                    std::size_t acc_stride, std::size_t count, std::size_t n_sums, bool add)
+    {
+        if (!count || !elts.n || !n_sums)
+            return hipSuccess;
+        if (elts.n < 0 || elts.n > kHoistMaxElts)
+            return hipErrorInvalidValue;
+        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
+        // the four slots of a lane: as many sums as the call has (1, 2 or 4), the rest ciphertexts
+        const int S = n_sums >= 3 ? 4 : static_cast<int>(n_sums);
+        const std::size_t groups = ((n_sums + S - 1) / S) * ((count + 4 / S - 1) / (4 / S));
+        const std::size_t glanes = (groups * rows) << e.logn;
+        ProfScope prof(e, "hoist_dot_mac", 0);
+#define SEALHIP_HOIST_DOT_ARGS                                                                                             \
+    d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, w_sum_stride, acc, acc_stride, count, \
+        n_sums, e.logn
+#define SEALHIP_HOIST_DOT(ND)                                                                                              \
+    case ND:                                                                                                               \
+        if (S == 1)                                                                                                        \
+            hoist_dot_mac_kernel<ND, 1><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
+                                                                                              add ? 1 : 0);                \
+        else if (S == 2)                                                                                                   \
+            hoist_dot_mac_kernel<ND, 2><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
+                                                                                              add ? 1 : 0);                \
+        else                                                                                                               \
+            hoist_dot_mac_kernel<ND, 4><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
+                                                                                              add ? 1 : 0);                \
+        break;
+        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
+        {
+            SEALHIP_HOIST_DOT(1)
+            SEALHIP_HOIST_DOT(2)
+            SEALHIP_HOIST_DOT(3)
+            SEALHIP_HOIST_DOT(4)
+            SEALHIP_HOIST_DOT(5)
+            SEALHIP_HOIST_DOT(6)
+            SEALHIP_HOIST_DOT(7)
+            SEALHIP_HOIST_DOT(8)
+            SEALHIP_HOIST_DOT(9)
+            SEALHIP_HOIST_DOT(10)
+            SEALHIP_HOIST_DOT(11)
+            SEALHIP_HOIST_DOT(12)
+            SEALHIP_HOIST_DOT(13)
+            SEALHIP_HOIST_DOT(14)
+            SEALHIP_HOIST_DOT(15)
+            SEALHIP_HOIST_DOT(16)
+        default: // more than 16 digits, or a ring smaller than a workgroup
+            hoist_dot_mac_loop_kernel<<<blocks_for((n_sums * count * rows) << e.logn), kThreads, 0, e.lane().stream>>>(
+                SEALHIP_HOIST_DOT_ARGS, h.nd, add ? 1 : 0);
+        }
+#undef SEALHIP_HOIST_DOT
+#undef SEALHIP_HOIST_DOT_ARGS
+        return hipGetLastError();
+    }
+
+    hipError_t launch_hoist_dot_base(const Engine &e, const u64 *cn, const HoistDotElts &elts, std::size_t w_sum_stride,
+                                     u64 *out, std::size_t out_sum_stride, int k, std::size_t count, std::size_t n_sums,
+                                     bool add)
+    {
+        const std::size_t total = (n_sums * count * static_cast<std::size_t>(k)) << e.logn;
+        if (total == 0 || !elts.n)
+            return hipSuccess;
+        if (elts.n < 0 || elts.n > kHoistMaxElts)
+            return hipErrorInvalidValue;
+        ProfScope prof(e, "hoist_dot_base", 0);
+        hoist_dot_base_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(cn, elts, w_sum_stride, out, out_sum_stride,
+                                                                                e.d_primes, k, e.logn, count, n_sums,
+                                                                                add ? 1 : 0);
         return hipGetLastError();
     }
 } // namespace sealhip

@@ -928,6 +928,140 @@ namespace sealhip
             }
         });
     }
+    // ------------------------------------------------------------------------------------------
+    // Plaintext-weighted sum of rotations: out_s = sum_i W[s][i] * sigma_{g_i}(ct), one decomposition
+    // of c_1 per ciphertext and one mod-down per sum
+    // ------------------------------------------------------------------------------------------
+    // The plaintexts (key-level NTT form) multiply the key-switch inner products while these are still in the extended basis
+    // (hoist.hip, hoist_dot_mac); the weighted products are summed there and ks_finish brings each sum down once, adding it
+    // into base_s = (sum_i W (.) sigma_i(C_0), sum_{i identity} W (.) C_1), which the base kernel writes straight into out.
+    void op_apply_galois_dot_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
+                                   const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
+                                   std::size_t n_sums, u64 *out)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        const bool ckks = e.scheme == 2;
+        if (!ckks && !e.mode_strict)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
+        LevelTools &ld = e.level(k);
+        const KsDev &h = ld.h_ks;
+        const int nd = h.nd, rows = k + e.nsp;
+        std::size_t n_gal = 0;
+        for (std::size_t i = 0; i < n_elts; i++)
+        {
+            if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
+                throw std::invalid_argument("Galois element is not valid"); // :1880-1883
+            if (elts[i] == 1)
+                continue;
+            if (!keys[i] || static_cast<int>(keys[i]->n_digits) < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+            n_gal++;
+        }
+        if (!count)
+            return;
+        if (!n_elts || !n_sums)
+            throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        std::vector<const std::uint32_t *> tables(n_elts, nullptr);
+        for (std::size_t i = 0; i < n_elts; i++)
+            if (elts[i] != 1)
+                tables[i] = e.galois_table(elts[i]); // (resident after the first call: the condition for a capture)
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t w_plain = static_cast<std::size_t>(h.n_total) * N, w_sum_stride = n_elts * w_plain;
+        const std::size_t w_coeff = n_gal ? poly : 0;
+        const std::size_t w_ext = n_gal ? static_cast<std::size_t>(nd) * rows * N : 0;
+        const std::size_t w_cn = ckks ? 0 : 2 * poly; // (BFV: both components in NTT form)
+        const std::size_t w_prod = n_gal ? 2ull * rows * N : 0;
+        const std::size_t w_temp = n_gal ? 2ull * poly : 0;
+        // arena of one item: the digits (and BFV's transformed components) once, per sum the accumulated products and the
+        // mod-down's temporaries; base_s lives in out
+        const std::size_t base_bytes = (w_coeff + w_ext + w_cn) * sizeof(u64), sum_bytes = (w_prod + w_temp) * sizeof(u64);
+        // when not even one item fits with all its sums, the sum list is walked in passes and the digits stay live
+        std::size_t pass = n_sums;
+        const std::size_t budget = workspace_budget_bytes(e);
+        if (base_bytes + pass * sum_bytes > budget)
+        {
+            pass = budget > base_bytes ? (budget - base_bytes) / sum_bytes : 0;
+            pass = std::max<std::size_t>(1, std::min(pass, n_sums));
+            log_chunk(e, n_sums, pass); // (the sum split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        }
+        unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext, in output order
+        for_chunks(e, count, base_bytes + pass * sum_bytes, 5, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = n_gal ? e.ws_alloc(w_coeff * m) : nullptr;
+            u64 *ext = n_gal ? e.ws_alloc(w_ext * m) : nullptr;
+            u64 *cntt = w_cn ? e.ws_alloc(w_cn * m) : nullptr;
+            u64 *acc = n_gal ? e.ws_alloc(w_prod * m * pass) : nullptr;
+            u64 *temp = n_gal ? e.ws_alloc(w_temp * m * pass) : nullptr;
+            const u64 *c = ct + off * 2 * poly;
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            KsRows in_bundle{ nullptr, 0 };
+            if (n_gal)
+                in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
+            const u64 *cn = c;
+            if (cntt)
+            {
+                SEALHIP_CHECK(hipMemcpyAsync(cntt, c, m * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream));
+                check(launch_ntt(e, cntt, m * 2 * k, ld.map_q, false, kNttCanonical), "ntt(ct)");
+                cn = cntt;
+            }
+            for (std::size_t s0 = 0; s0 < n_sums; s0 += pass)
+            {
+                const std::size_t ns = std::min(pass, n_sums - s0);
+                const u64 *w0 = plain_ntt + s0 * w_sum_stride;
+                u64 *o = out + (s0 * count + off) * 2 * poly; // sum s0 + s of this chunk: o + s * count * 2 * poly
+                HoistDotElts he{};
+                const auto flush_base = [&](bool add) {
+                    check(launch_hoist_dot_base(e, cn, he, w_sum_stride, o, count * 2 * poly, k, m, ns, add), "hoist_dot_base");
+                    he.n = 0;
+                };
+                bool launched = false;
+                for (std::size_t i = 0; i < n_elts; i++)
+                {
+                    he.table[he.n] = tables[i];
+                    he.key[he.n] = nullptr;
+                    he.w[he.n++] = w0 + i * w_plain;
+                    if (he.n == kHoistMaxElts || i + 1 == n_elts)
+                    {
+                        flush_base(launched);
+                        launched = true;
+                    }
+                }
+                launched = false;
+                for (std::size_t i = 0, seen = 0; i < n_elts; i++)
+                {
+                    if (elts[i] == 1)
+                        continue;
+                    he.table[he.n] = tables[i];
+                    he.key[he.n] = keys[i]->d_data;
+                    he.w[he.n++] = w0 + i * w_plain;
+                    seen++;
+                    if (he.n == kHoistMaxElts || seen == n_gal)
+                    {
+                        check(launch_hoist_dot_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m,
+                                                   he, w_sum_stride, acc, w_prod, m, ns, launched),
+                              "hoist_dot_mac");
+                        he.n = 0;
+                        launched = true;
+                    }
+                }
+                // the back half once per sum: when the chunk is the whole batch the sums of this pass are one contiguous
+                // batch of ns * m ciphertexts, else one batch per sum
+                const std::size_t run = m == count ? ns : 1;
+                for (std::size_t s = 0; s < ns; s += run)
+                {
+                    u64 *os = o + s * count * 2 * poly;
+                    const std::size_t first = (s0 + s) * count + off; // (output ciphertext, and its transparency flag)
+                    if (!ckks)
+                        check(launch_ntt(e, os, run * m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
+                    if (n_gal)
+                        ks_finish(e, ld, k, acc + s * m * w_prod, temp + s * m * w_temp, os, 2 * poly, nullptr, 0, run * m,
+                                  sink ? sink + first : nullptr);
+                    else if (sink)
+                        check(launch_nonzero_tail(e, os, 2 * poly, poly, run * m, sink + first), "transparency");
+                }
+            }
+        });
+    }
     // multiply_plain_normal (evaluator.cpp:1475-1603) for parameters with fast plain lift (every q_i > t): lift the
     // plaintext into the RNS base, canonical NTT, then per ciphertext polynomial lazy NTT -> dyadic product ->
     // canonical inverse NTT, in place. The monomial shortcut (:1516-1553) computes the same negacyclic product

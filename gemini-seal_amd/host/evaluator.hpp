@@ -462,6 +462,7 @@ namespace sealhip_host
             words_ = o.words_;
             k_ = o.k_;
             ntt_ = o.ntt_;
+            scale_ = o.scale_;
             return *this;
         }
         DevicePlaintext &operator=(DevicePlaintext &&o) noexcept
@@ -477,6 +478,7 @@ namespace sealhip_host
             std::swap(words_, o.words_);
             std::swap(k_, o.k_);
             std::swap(ntt_, o.ntt_);
+            std::swap(scale_, o.scale_);
         }
         // coefficient form: up to N coefficients below t; NTT form: k x N words (k = words.size() / N)
         void upload(const std::vector<std::uint64_t> &words, bool ntt_form)
@@ -517,6 +519,10 @@ namespace sealhip_host
         std::size_t words() const { return words_; }
         std::size_t coeff_modulus_size() const { return k_; } // NTT form: its level; coefficient form: 0
         bool is_ntt_form() const { return ntt_; }
+        // Plaintext::scale() of a CKKS plaintext (the caller sets it next to upload; 1.0 otherwise): read by
+        // Evaluator::apply_galois_dot_plain, kept by copies
+        double &scale() { return scale_; }
+        double scale() const { return scale_; }
         // (Evaluator) the words in `block` replace these
         void adopt(void *block, std::size_t cap_words, std::size_t words, std::size_t k, bool ntt_form)
         {
@@ -551,6 +557,7 @@ namespace sealhip_host
         std::uint64_t *ptr_ = nullptr;
         std::size_t cap_ = 0, words_ = 0, k_ = 0;
         bool ntt_ = false;
+        double scale_ = 1.0;
     };
 
     class KSwitchKeys // one key of RelinKeys / GaloisKeys (kswitchkeys.h:92-130), resident on the device
@@ -815,6 +822,71 @@ namespace sealhip_host
                                                           elts.data(), raw.data(), std::uint32_t(elts.size()), o.ptr()));
             chk.done();
             scatter(encrypted, o, count, words, destinations);
+        }
+
+        // Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):
+        // destinations[s] = sum_i plains[s][i] * sigma_{galois_elts[i]}(encrypted), with one decomposition of the operand's
+        // second polynomial and one mod-down per sum. plains[s][i] is a plaintext in KEY-LEVEL NTT form (n_key x N words:
+        // what CKKSEncoder::encode and transform_to_ntt give at the key level): a DevicePlaintext, or a host plaintext of
+        // HostPlaintext's shape (words, k, ntt_form, scale). Element 1 needs no key. Each result has the operand's level
+        // and NTT form and, for CKKS, the scale encrypted.scale() * plain.scale (all plaintexts must share one scale).
+        // std::invalid_argument: a plaintext that is not key-level NTT form, a ragged plaintext matrix (a row whose length
+        // is not galois_elts.size()), CKKS plaintexts of unequal scale, an element other than 1 without its key ("Galois
+        // key not present"). The reference has no such method; the words are those of the ABI entry, not of the
+        // composition. Resident destinations: one pool block and one deferred transparency slot per sum, as
+        // apply_galois_many's.
+        template <class C, class P, IfCt<C> = 0>
+        void apply_galois_dot_plain(const C &encrypted, const std::vector<std::uint32_t> &galois_elts,
+                                    const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                    const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
+        {
+            check_galois_operand(encrypted);
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (std::uint32_t elt : galois_elts)
+            {
+                auto it = galois_keys.find(elt);
+                if (elt != 1 && (it == galois_keys.end() || !it->second))
+                    throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
+                raw.push_back(elt != 1 ? it->second->get() : nullptr);
+            }
+            const std::size_t n_elts = galois_elts.size(), n_sums = plains.size();
+            const double scale = check_dot_plains(plains, n_elts);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
+            Dev c = dev_in(encrypted, words), o = dev_out((n_sums ? n_sums : 1) * words);
+            Staged w(ctx_, n_sums * n_elts ? n_sums * n_elts * pw : 1);
+            for (std::size_t s = 0; s < n_sums; s++)
+                for (std::size_t i = 0; i < n_elts; i++)
+                    plain_to(plains[s][i], w.ptr() + (s * n_elts + i) * pw, pw);
+            Check chk = checked(encrypted, n_sums ? n_sums : 1);
+            throw_on(sealhip_evaluator_apply_galois_dot_plain(ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(),
+                                                              raw.data(), std::uint32_t(n_elts), w.ptr(), std::uint32_t(n_sums),
+                                                              o.ptr()));
+            chk.done();
+            scatter(encrypted, o, n_sums, words, destinations);
+            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
+                for (C &d : destinations)
+                    d.scale() = encrypted.scale() * scale;
+        }
+        // The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): CKKS rotate_vector's steps; step 0 is the
+        // identity; no non-adjacent-form fallback
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_vector_dot_plain(const C &encrypted, const std::vector<int> &steps,
+                                     const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                     const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            apply_galois_dot_plain(encrypted, elts_of_steps(steps), galois_keys, plains, destinations);
+        }
+        // ... and BFV rotate_rows' steps
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_rows_dot_plain(const C &encrypted, const std::vector<int> &steps,
+                                   const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                   const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1061-1064
+            apply_galois_dot_plain(encrypted, elts_of_steps(steps), galois_keys, plains, destinations);
         }
 
         // Evaluator::mod_switch_to_inplace (evaluator.cpp:1038-1060) / rescale_to_inplace (:1128-1165). The ABI names a level by
@@ -1424,6 +1496,63 @@ namespace sealhip_host
                 next[i].copy_meta(src);
             }
             dst.swap(next);
+        }
+        // the plaintexts of apply_galois_dot_plain: a DevicePlaintext, or a host plaintext of HostPlaintext's shape
+        static const std::uint64_t *plain_data(const DevicePlaintext &p) { return p.data(); }
+        static std::size_t plain_words(const DevicePlaintext &p) { return p.words(); }
+        static std::size_t plain_k(const DevicePlaintext &p) { return p.coeff_modulus_size(); }
+        static bool plain_ntt(const DevicePlaintext &p) { return p.is_ntt_form(); }
+        static double plain_scale(const DevicePlaintext &p) { return p.scale(); }
+        template <class P>
+        static const std::uint64_t *plain_data(const P &p) { return p.words.data(); }
+        template <class P>
+        static std::size_t plain_words(const P &p) { return p.words.size(); }
+        template <class P>
+        static std::size_t plain_k(const P &p) { return p.k; }
+        template <class P>
+        static bool plain_ntt(const P &p) { return p.ntt_form; }
+        template <class P>
+        static double plain_scale(const P &p) { return p.scale; }
+        void plain_to(const DevicePlaintext &p, std::uint64_t *dst, std::size_t words)
+        {
+            throw_on(sealhip_memcpy_d2d(ctx_.get(), dst, p.data(), words * 8));
+        }
+        template <class P>
+        void plain_to(const P &p, std::uint64_t *dst, std::size_t words)
+        {
+            throw_on(sealhip_memcpy_h2d(ctx_.get(), dst, p.words.data(), words * 8));
+        }
+        // every plains[s] has n_elts plaintexts in key-level NTT form; returns their common scale (CKKS; 1.0 if none)
+        template <class P>
+        double check_dot_plains(const std::vector<std::vector<P>> &plains, std::size_t n_elts) const
+        {
+            const std::size_t n_key = ctx_.n_key(), n = ctx_.n();
+            bool first = true;
+            double scale = 1.0;
+            for (const auto &row : plains)
+            {
+                if (row.size() != n_elts)
+                    throw std::invalid_argument("plains must hold one plaintext per Galois element in every sum");
+                for (const P &p : row)
+                {
+                    if (!plain_ntt(p) || plain_k(p) != n_key || plain_words(p) != n_key * n)
+                        throw std::invalid_argument("plain must be in NTT form at the key level");
+                    if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && !first && plain_scale(p) != scale)
+                        throw std::invalid_argument("scale mismatch");
+                    if (first)
+                        scale = plain_scale(p);
+                    first = false;
+                }
+            }
+            return scale;
+        }
+        std::vector<std::uint32_t> elts_of_steps(const std::vector<int> &steps) const
+        {
+            std::vector<std::uint32_t> elts(steps.size(), 1);
+            for (std::size_t i = 0; i < steps.size(); i++)
+                if (steps[i] != 0)
+                    throw_on(sealhip_galois_elt_from_step(ctx_.get(), steps[i], &elts[i]));
+            return elts;
         }
         // apply_galois_inplace's checks on the operand (evaluator.cpp:1848-1887)
         template <class C>

@@ -132,6 +132,9 @@ SYMBOLS = {
     "sealhip_evaluator_apply_galois_many": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_rotate_vector_many": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp), _u32,
                                              _vp],
+    "sealhip_evaluator_apply_galois_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32, _vp],
+    "sealhip_evaluator_rotate_vector_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp),
+                                                  _u32, _vp, _u32, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -931,6 +934,28 @@ class Evaluator:
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
         _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts),
                                                           _ptr(out)))
+
+    def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out):
+        """Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):
+        out[s] = sum_i plains[s][i] * sigma_{elts[i]}(ct) with one decomposition of c_1 and one mod-down per sum. keys[i] is
+        the KSwitchKeys of elts[i] and may be None for element 1. plains: n_sums x len(elts) x n_key x N words in key-level
+        NTT form; out: n_sums x count x 2 x k x N, sum-major; ct is not modified."""
+        elts = [int(g) for g in elts]
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[key.handle if key is not None else None for key in keys])
+        _check(lib().sealhip_evaluator_apply_galois_dot_plain(self.ctx.handle, k, _ptr(ct), count, ea, ka, len(elts),
+                                                              _ptr(plains), n_sums, _ptr(out)))
+
+    def rotate_vector_dot_plain(self, ct, k, count, steps, galois_keys, plains, n_sums, out):
+        """The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): step 0 is the identity and needs no key; a
+        step without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
+        steps = [int(st) for st in steps]
+        elts = list(galois_keys.keys())
+        sa = (_i32 * max(1, len(steps)))(*steps)
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        _check(lib().sealhip_evaluator_rotate_vector_dot_plain(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka,
+                                                               len(elts), _ptr(plains), n_sums, _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

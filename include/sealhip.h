@@ -450,6 +450,46 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
                                           const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
                                           const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
 
+/* Plaintext-weighted sums of rotations ("double hoisting", Bossuat et al.):
+       out_s = sum_i W[s][i] * sigma_{g_i}(ct)   for s < n_sums,
+   with ONE decomposition of c_1 per ciphertext and ONE mod-down per sum -- what a baby-step/giant-step matrix-vector product
+   or an inner sum wants of the hoisted rotation above. The plaintexts multiply the key-switch inner products while these are
+   still in the extended basis Q * P; the weighted products are summed there and the sum is brought down once, so the result
+   carries one rounding error of the mod-down, which no plaintext amplifies. The fork has no such method, and the words are
+   NOT those of apply_galois_many + multiply_plain_ntt + add; what defines them, word for word in the context's mode, is the
+   restatement over the oracle in tests/hoist_dot_ref.py. With nsp special primes, rows = k + nsp, rp(r) the key prime of
+   extended row r (r below k, n_key - nsp + (r - k) above), D_j and T_g as for sealhip_evaluator_apply_galois_many:
+       prod_g[l][r][c]   = ( sum_j D_j[r][T_g[c]] * K_g[j][l][rp(r)][c] ) mod p_r            for every element g != 1,
+       acc_s[l][r][c]    = ( sum_{i : g_i != 1} W[s][i][rp(r)][c] * prod_{g_i}[l][r][c] ) mod p_r,   l < 2, r < rows,
+       base_s[0][r][c]   = ( sum_i W[s][i][r][c] * C[0][r][T_{g_i}[c]] ) mod q_r             over ALL elements, r < k,
+       base_s[1][r][c]   = ( sum_{i : g_i = 1} W[s][i][r][c] * C[1][r][c] ) mod q_r,
+       out_s             = the key switch's finish (:2351-2366) of acc_s added into (base_s[0], base_s[1]),
+   every sum canonical. C is the NTT form of both input components: the components themselves for CKKS, their canonical
+   forward transform for BFV, where the canonical inverse transform is applied to base_s. If no element differs from 1 no
+   acc is formed and out_s = base_s. Element 1 (rotation step 0) needs no key: its key pointer may be NULL. Repeated
+   elements add.
+   plain_ntt: n_sums x n_elts x n_key x N words, each plaintext in KEY-LEVEL NTT form -- one integer polynomial reduced
+   modulo every key prime, special primes included, row j modulo key prime j: what sealhip_ckks_encode and
+   sealhip_evaluator_transform_plain_to_ntt write at k = n_key. The plaintexts are shared by the ciphertexts of the batch;
+   words at or above their prime give unspecified words. ct: count x 2 x k x N, not modified. out: n_sums x count x 2 x k x N,
+   SUM-major (each sum is a contiguous batch); out must overlap neither ct nor plain_ntt. Everything is device memory.
+   CKKS in both modes and BFV in STRICT mode; BFV in PARITY mode is E_INVALIDARG, as for apply_galois_many.
+   Checks: NULL pointers -> E_POINTER (a NULL key only for element 1); then, also on host-only contexts, k outside the
+   ciphertext levels, an even element or one >= 2N, a key with fewer digits than the level, BFV in PARITY mode, n_elts == 0
+   or n_sums == 0 when count > 0 (an empty sum would be a transparent zero ciphertext) -> E_INVALIDARG; then count == 0 ->
+   S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION. With a transparency sink: one flag per output
+   ciphertext, in output order (n_sums * count flags). Nothing synchronises; capturable once the Galois tables of the
+   elements are resident (after one call with them). */
+long sealhip_evaluator_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                              const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                              uint32_t n_elts, const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out);
+/* The same by rotation steps (galois_elt_from_step): plain_ntt: n_sums x n_steps x n_key x N. Step 0 is element 1 and needs
+   no key; a step whose key is absent -> E_INVALIDARG ("Galois key not present"), there is no non-adjacent-form fallback. */
+long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                               const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                               const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                               const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out);
+
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
    of the ciphertext (is_ntt_form). sk_powers_ntt = the Decryptor's secret_key_array_: (size-1) polynomials s, s^2, ...
