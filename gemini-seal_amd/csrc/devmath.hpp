@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include "ntt_bounds.hpp"
+#include "dotacc.hpp"
 
 namespace sealhip
 {
@@ -333,6 +334,17 @@ namespace sealhip
     {
         return mullo1_acc(x, mulhi_c<true>(x, rdp), neg_p);
     }
+    // Canonical acc * 2^-64 mod p for acc = (lo, hi) below p * 2^64, i.e. hi < p -- what bounds::behz_redc_small proves for
+    // every REDC of the exact-k BEHZ instances (ntt_bounds.hpp section 7). p and ninv = -p^-1 mod 2^64 are wave-uniform.
+    // With m = lo * p^-1 mod 2^64 the product m p has exactly the low word lo, so acc - m p = (hi - mulhi(m, p)) 2^64 with no
+    // borrow out of the low word and no test of lo; mulhi(m, p) < p, so the difference lies in (-p, p) and one addition of p
+    // selected by its sign gives the residue redc128 + redc_finish return (the canonical residue is unique).
+    __device__ __forceinline__ u64 redc_canonical_hs(u64 lo, u64 hi, u64 p, u64 ninv)
+    {
+        const u64 m = mullo1_acc(0, lo, 0 - ninv);
+        const u64 dd = hi - mulhi_c<true>(m, p);
+        return static_cast<long long>(dd) < 0 ? dd + p : dd;
+    }
     // x below 2^7 p, p at least 2^45 (bounds::small_quot_admits) -> the representative in [0, 2p) of the same residue class,
     // with the quotient estimated in single precision from the word's upper half: floor(fl(fl(x >> 32) * c)) is
     // floor(x / p) or one less for c = fl((2^32 / p)(1 - 2^-20)) (ntt_bounds.hpp section 6 proves both directions;
@@ -614,6 +626,8 @@ namespace sealhip
     //   L0 += t00*c0 (< 2^48)   L1 += t01*c0 (< 2^48)   H += t1*c1 (< 2^58)
     //   M[.] += t0*c1, t1*c0 (< 2^61 each; at most 8 products per accumulator)
     // and sum = L0 + L1*2^16 + (M...)*2^32 + H*2^64 is assembled once per dot product.
+    // (The exact-k BEHZ instances have moved to DotAcc31, dotacc.hpp: four multiplier instructions per term. This form
+    //  stays for tools/ubench_bconv_mfma.hip, with its predicate and tests/bounds_check.cpp.)
     struct SplitT // the per-lane factor, split once and reused by every dot product it takes part in
     {
         u32 t0, t1, t00, t01;

@@ -579,6 +579,53 @@ namespace sealhip
             rd.lift_L1m = upload<u64>(*this, lt.owned, L1m.data(), L1m.size());
             rd.floor_G2m = upload<u64>(*this, lt.owned, G2m.data(), G2m.size());
             rd.B_to_qm = upload<u64>(*this, lt.owned, BQm.data(), BQm.size());
+            // the exact-k instances read every dot product's constants as one contiguous row, pre-split for DotAcc31
+            // (dotacc.hpp dot31_pack), with the row's prime and -p^-1 mod 2^64 behind them
+            {
+                const std::size_t ls = static_cast<std::size_t>(k) + 3, qs = static_cast<std::size_t>(B) + 4;
+                std::vector<u64> lrows(nB * ls), frows(5 * nB * ls), qrows(k * qs), first(5 * static_cast<std::size_t>(k) * 3);
+                for (int j = 0; j < nB; j++)
+                {
+                    u64 *lr = &lrows[j * ls];
+                    lr[0] = dot31_pack(rd.lift_L2m[j]);
+                    for (int i = 0; i < k; i++)
+                        lr[1 + i] = dot31_pack(L1m[static_cast<std::size_t>(j) * k + i]);
+                    lr[k + 1] = rd.b_p[j];
+                    lr[k + 2] = rd.b_ninv[j];
+                    for (int sel = 0; sel < 5; sel++)
+                    {
+                        u64 *fr = &frows[(static_cast<std::size_t>(sel) * nB + j) * ls];
+                        fr[0] = dot31_pack(sel < 4 ? rd.floor_G1m_top[sel][j] : rd.floor_G1m[j]);
+                        for (int i = 0; i < k; i++)
+                            fr[1 + i] = dot31_pack(G2m[static_cast<std::size_t>(j) * k + i]);
+                        fr[k + 1] = rd.b_p[j];
+                        fr[k + 2] = rd.b_ninv[j];
+                    }
+                }
+                for (int i = 0; i < k; i++)
+                {
+                    u64 *qr = &qrows[i * qs];
+                    qr[0] = dot31_pack(rd.pBm[i]);
+                    qr[1] = dot31_pack(rd.nBm[i]);
+                    for (int j = 0; j < B; j++)
+                        qr[2 + j] = dot31_pack(BQm[static_cast<std::size_t>(i) * B + j]);
+                    qr[B + 2] = rd.q_p[i];
+                    qr[B + 3] = rd.q_ninv[i];
+                    for (int sel = 0; sel < 5; sel++)
+                    {
+                        u64 *f = &first[(static_cast<std::size_t>(sel) * k + i) * 3];
+                        f[0] = sel < 4 ? rd.floor_F0_top[sel][i] : rd.floor_F0[i];
+                        f[1] = sel < 4 ? rd.floor_F0_top_s[sel][i] : rd.floor_F0_s[i];
+                        f[2] = rd.q_p[i];
+                    }
+                }
+                for (int j = 0; j < B; j++)
+                    rd.B_to_mskp[j] = dot31_pack(rd.B_to_mskm[j]);
+                rd.lift_rows = upload<u64>(*this, lt.owned, lrows.data(), lrows.size());
+                rd.floor_rows = upload<u64>(*this, lt.owned, frows.data(), frows.size());
+                rd.q_rows = upload<u64>(*this, lt.owned, qrows.data(), qrows.size());
+                rd.floor_first = upload<u64>(*this, lt.owned, first.data(), first.size());
+            }
             // decrypt_scale_and_round constants (rns.cpp:690-716): base q -> {t, gamma}
             {
                 HostBaseConv tg;

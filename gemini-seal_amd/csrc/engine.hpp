@@ -161,6 +161,13 @@ namespace sealhip
         u64 B_to_mskm[kMaxModuli + 1];
         u64 inv_prod_B_mod_msk_s;
         u64 pBm[kMaxModuli], nBm[kMaxModuli]; // prod_B_mod_q * 2^64, (q - prod_B_mod_q) * 2^64  (mod q_i)
+        // the same constants as the exact-k instances read them: one contiguous row per dot product, every constant split
+        // for DotAcc31 (dotacc.hpp dot31_pack), followed by the row's prime p and -p^-1 mod 2^64 (not packed)
+        const u64 *lift_rows;   // [nB][k + 3]     {lift_L2m[j], lift_L1m[j][0..k-1], p, ninv}
+        const u64 *floor_rows;  // [5][nB][k + 3]  {G1[j], floor_G2m[j][0..k-1], p, ninv}; G1 = floor_G1m_top[sel] (sel < 4), floor_G1m (4)
+        const u64 *q_rows;      // [k][B + 4]      {pBm[i], nBm[i], B_to_qm[i][0..B-1], p, ninv}
+        const u64 *floor_first; // [5][k][3]       {F0, its Shoup quotient, q_i}: floor_F0_top(_s)[sel] (sel < 4), floor_F0(_s) (4); plain
+        u64 B_to_mskp[kMaxModuli + 1];
         // decrypt_scale_and_round (rns.cpp:1070-1126), constants folded where the results are canonical anyway:
         //   y_i = in_i * dsr_scale[i] mod q_i  (|gamma t|_qi times (q^_i)^{-1});  {t, gamma} part = sum_i y_i * dsr_to_t/g[i]
         u64 dsr_scale[kMaxModuli], dsr_scale_s[kMaxModuli], dsr_to_t[kMaxModuli], dsr_to_g[kMaxModuli];

@@ -417,6 +417,33 @@ namespace sealhip
             return n;
         }
         static_assert(dotacc_max_terms() >= 64, "DotAcc on 61-bit operands: at least 64 terms (the kernels use up to k + 2 <= 34)");
+        // The form the exact-k BEHZ instances use (dotacc.hpp DotAcc31<NTERMS>): both factors split at bit 31 (t = t1 2^31 + t0,
+        // c = c1 2^31 + c0, low halves below 2^31 and high halves below 2^(bits - 31)), four products per term, dealt
+        // round-robin: t0 c0 (below 2^62) over NL accumulators, the 2 NTERMS cross products (below 2^bits) over NM, t1 c1
+        // (below 2^(2 bits - 62)) over NH. Every accumulator must stay below 2^64 and the assembled sum below 2^128.
+        constexpr int dotacc31_nl(int nterms) { return (nterms + 3) / 4; }
+        constexpr int dotacc31_nm(int nterms) { return (2 * nterms + 7) / 8; }
+        constexpr int dotacc31_nh(int nterms) { return (nterms + 15) / 16; }
+        constexpr bool dotacc31_ok(int nterms, int bits)
+        {
+            if (nterms < 1 || nterms > 64 || bits < 32 || bits > 62)
+                return false;
+            const u128 lim = kWord;
+            const int nl = dotacc31_nl(nterms), nm = dotacc31_nm(nterms), nh = dotacc31_nh(nterms);
+            const u128 low = static_cast<u128>((nterms + nl - 1) / nl) << 62;
+            const u128 mid = static_cast<u128>((2 * nterms + nm - 1) / nm) << bits;
+            const u128 high = static_cast<u128>((nterms + nh - 1) / nh) << (2 * (bits - 31));
+            // the sum itself: nterms products below 2^(2 bits)
+            const bool sum_fits = 2 * bits + 6 <= 128;
+            return low <= lim && mid <= lim && high <= lim && sum_fits;
+        }
+        constexpr bool dotacc31_all_ok(int max_terms)
+        {
+            for (int t = 1; t <= max_terms; t++)
+                if (!dotacc31_ok(t, kDotAccOperandBits))
+                    return false;
+            return true;
+        }
 
         // =====================================================================================================
         // 6. Small quotients estimated in single precision (devmath.hpp reduce_small_quot): for a word x below M p the
@@ -462,5 +489,7 @@ namespace sealhip
         static_assert(!behz_redc_small(15, 16, u64(1) << 40, (u64(1) << 60) - (u64(1) << 55)),
                       "s2 at |B| = 16 for every m_sk");
         constexpr int kBehzExactMaxK = 15; // the largest k with an exact-k BEHZ instance (rns.hip)
+        static_assert(dotacc31_all_ok(kBehzExactMaxK + 2),
+                      "DotAcc31 on 61-bit operands: every term count of the exact-k instances (up to k + 2)");
     } // namespace bounds
 } // namespace sealhip

@@ -31,6 +31,23 @@ namespace sealhip
             return (const __attribute__((address_space(4))) T *)p;
         }
 
+        // One row's constants at a time: the row pointer and the row's result each pass through an empty asm statement. Such
+        // statements keep their order, so a row's scalar loads cannot be requested before the preceding row's result
+        // exists. Left alone, the straight-line row loops of the exact-K instances request every row's constants up front
+        // (sched_barrier orders the machine scheduler only, instruction selection has sunk the arithmetic below the loads
+        // by then) and spill scalar registers to vector lanes.
+        template <class T>
+        __device__ __forceinline__ const __attribute__((address_space(4))) T *row_window(
+            const __attribute__((address_space(4))) T *row)
+        {
+            asm volatile("" : "+s"(row));
+            return row;
+        }
+        __device__ __forceinline__ void row_done(u64 &v)
+        {
+            asm volatile("" : "+v"(v));
+        }
+
         struct Cols
         {
             std::size_t item, c;
@@ -209,18 +226,24 @@ namespace sealhip
             // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
             // a compile-time fact there, so the row loops carry no branch
             const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            SplitT ts[NC][KA];
+            Split31 ts[NC][KA];
             if constexpr (KMAX < 0)
                 static_for<KA>([&](auto I) {
 #pragma unroll
                     for (int h = 0; h < NC; h++)
-                        ts[h][I.value] = SplitT(t[h][I.value]);
+                        ts[h][I.value] = Split31(t[h][I.value]);
                 });
             const auto *L1m = kc(d->lift_L1m);
             const auto *L2m = kc(d->lift_L2m);
+            const auto *Lrows = kc(d->lift_rows);
             const auto row_out = [&](int j) {
-                const u64 bp = d->b_p[j];
-                const auto *row = L1m + j * k; // constants carry the factor 2^64: REDC removes it
+                // constants carry the factor 2^64: REDC removes it. Exact K: the row {L2, L1[0..K-1], p, -p^-1}, split for
+                // DotAcc31, is one contiguous run of scalar loads
+                auto *row = KMAX < 0 ? Lrows + j * (KA + 3) : L1m + j * k;
+                if constexpr (KMAX < 0)
+                    row = row_window(row);
+                const u64 bp = KMAX < 0 ? row[KA + 1] : d->b_p[j];
+                const u64 ninv = KMAX < 0 ? row[KA + 2] : d->b_ninv[j];
                 u64 v[NC];
 #pragma unroll
                 for (int h = 0; h < NC; h++)
@@ -231,9 +254,9 @@ namespace sealhip
                     u64 lo, hi;
                     if constexpr (KMAX < 0)
                     {
-                        DotAcc<KA + 1> acc2; // carry-free accumulation (devmath.hpp), same integer sum
-                        acc2.template add<0>(SplitT(temp), L2m[j]);
-                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[h][I.value], row[I.value]); });
+                        DotAcc31<KA + 1> acc2; // carry-free accumulation (dotacc.hpp), same integer sum
+                        acc2.template add<0>(Split31(temp), row[0]);
+                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[h][I.value], row[I.value + 1]); });
                         acc2.finish(lo, hi);
                     }
                     else
@@ -245,7 +268,10 @@ namespace sealhip
                             if (i < k)
                                 mac128(lo, hi, t[h][i], row[i]);
                     }
-                    v[h] = redc_finish(redc128(lo, hi, bp, d->b_ninv[j]), bp, d->b_rdp[j], small);
+                    if constexpr (KMAX < 0)
+                        v[h] = redc_canonical_hs(lo, hi, bp, ninv);
+                    else
+                        v[h] = redc_finish(redc128(lo, hi, bp, ninv), bp, d->b_rdp[j], small);
                 }
                 if constexpr (TOP)
                 {
@@ -378,48 +404,48 @@ namespace sealhip
             (void)primes;
             // the constants of the first loop, requested as one batch of scalar loads while the vector loads are in flight
             // (inside the loop every iteration waited for its own three)
-            u64 cF0[KA], cF0s[KA], cQ[KA];
+            // Exact K: {F0, its Shoup quotient, q_i} sit next to each other, one short scalar load per input row, requested
+            // as the loop goes (a batch of all 3K constants up front held 6K scalar registers through the first rows and
+            // pushed the row constants to scratch)
+            const auto *first = kc(d->floor_first) + (DEFER ? top_sel : 4) * (KA * 3);
 #pragma unroll
             for (int i = 0; i < KA; i++)
                 if (KMAX < 0 || i < k)
                 {
-                    cF0[i] = F0t[i];
-                    cF0s[i] = F0ts[i];
-                    cQ[i] = d->q_p[i];
-                }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < KA; i++)
-                if (KMAX < 0 || i < k)
-                {
-                    const u64 qp = cQ[i];
+                    const u64 cF0 = KMAX < 0 ? first[3 * i] : F0t[i], cF0s = KMAX < 0 ? first[3 * i + 1] : F0ts[i];
+                    const u64 qp = KMAX < 0 ? first[3 * i + 2] : d->q_p[i];
                     if (DEFER) // (u +- v) * (n^{-1} or w n^{-1}) * F0 with ONE canonical Shoup product
-                        t[i] = mulmod_shoup_hs(before_top<false>(ru[i], rv[i], is_hi, qp << 1), cF0[i], cF0s[i], qp);
+                        t[i] = mulmod_shoup_hs(before_top<false>(ru[i], rv[i], is_hi, qp << 1), cF0, cF0s, qp);
                     else
-                        t[i] = mulmod_shoup_hs(ru[i], cF0[i], cF0s[i], qp);
+                        t[i] = mulmod_shoup_hs(ru[i], cF0, cF0s, qp);
                 }
             u64 tb[KA + 1];
             u64 fl_sk = 0;
             // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
             // a compile-time fact there, so the row loops carry no branch
             const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            SplitT ts[KA], tbs[KA + 1];
+            Split31 ts[KA], tbs[KA + 1];
             if constexpr (KMAX < 0)
-                static_for<KA>([&](auto I) { ts[I.value] = SplitT(t[I.value]); });
+                static_for<KA>([&](auto I) { ts[I.value] = Split31(t[I.value]); });
             const auto *G1m = DEFER ? kc(d->floor_G1m_top[top_sel]) : kc(d->floor_G1m);
             const auto *G2m = kc(d->floor_G2m);
+            // Exact K: the row {G1, G2[0..K-1], p, -p^-1} of this launch's table, split for DotAcc31, in one run of scalar loads
+            const auto *Frows = kc(d->floor_rows) + (DEFER ? top_sel : 4) * (d->nB * (KA + 3));
             const auto bsk_row = [&](int j) {
                 if (le_B(j))
                 {
-                    const u64 bp = d->b_p[j];
-                    const auto *row = G2m + j * k;
+                    auto *row = KMAX < 0 ? Frows + j * (KA + 3) : G2m + j * k;
+                    if constexpr (KMAX < 0)
+                        row = row_window(row);
+                    const u64 bp = KMAX < 0 ? row[KA + 1] : d->b_p[j];
+                    const u64 ninv = KMAX < 0 ? row[KA + 2] : d->b_ninv[j];
                     const u64 x = DEFER ? before_top<true>(ru[KA + j], rv[KA + j], is_hi, bp << 1) : ru[KA + j];
                     u64 lo, hi;
                     if constexpr (KMAX < 0)
                     {
-                        DotAcc<KA + 1> acc2;
-                        acc2.template add<0>(SplitT(x), G1m[j]);
-                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[I.value], row[I.value]); });
+                        DotAcc31<KA + 1> acc2;
+                        acc2.template add<0>(Split31(x), row[0]);
+                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[I.value], row[I.value + 1]); });
                         acc2.finish(lo, hi);
                     }
                     else
@@ -431,7 +457,13 @@ namespace sealhip
                             if (i < k)
                                 mac128(lo, hi, t[i], row[i]);
                     }
-                    const u64 v = redc_finish(redc128(lo, hi, bp, d->b_ninv[j]), bp, d->b_rdp[j], small);
+                    u64 v;
+                    if constexpr (KMAX < 0)
+                        v = redc_canonical_hs(lo, hi, bp, ninv);
+                    else
+                        v = redc_finish(redc128(lo, hi, bp, ninv), bp, d->b_rdp[j], small);
+                    if constexpr (KMAX < 0)
+                        row_done(v);
                     if (lt_B(j))
                         tb[j < KA + 1 ? j : 0] = v;
                     else
@@ -449,15 +481,15 @@ namespace sealhip
                 for (int j = 0; j < KA + 2; j++)
                     bsk_row(j);
             const u64 mp = d->b_p[B];
-            const auto *BtoMsk = kc(d->B_to_mskm);
+            const auto *BtoMsk = KMAX < 0 ? kc(d->B_to_mskp) : kc(d->B_to_mskm);
             u64 lo = 0, hi = 0;
             if constexpr (KMAX < 0)
             {
                 static_for<KA + 1>([&](auto J) {
                     if (lt_B(J.value))
-                        tbs[J.value] = SplitT(tb[J.value]);
+                        tbs[J.value] = Split31(tb[J.value]);
                 });
-                DotAcc<KA + 1> acc2;
+                DotAcc31<KA + 1> acc2;
                 static_for<KA + 1>([&](auto J) {
                     if (lt_B(J.value))
                         acc2.template add<J.value>(tbs[J.value], BtoMsk[J.value]);
@@ -471,22 +503,25 @@ namespace sealhip
                     if (lt_B(j))
                         mac128(lo, hi, tb[j], BtoMsk[j]);
             }
-            const u64 conv_sk = redc_finish(redc128(lo, hi, mp, d->b_ninv[B]), mp, d->b_rdp[B], small);
+            const u64 conv_sk = KMAX < 0 ? redc_canonical_hs(lo, hi, mp, d->b_ninv[B])
+                                         : redc_finish(redc128(lo, hi, mp, d->b_ninv[B]), mp, d->b_rdp[B], small);
             const u64 alpha = mulmod_shoup(conv_sk + (mp - fl_sk), d->inv_prod_B_mod_msk, d->inv_prod_B_mod_msk_s, mp);
             const bool neg = alpha > (mp >> 1); // rns.cpp:909
             const u64 a2 = neg ? mp - alpha : alpha;
-            const SplitT a2s(a2);
+            const Split31 a2s(a2);
             const auto *pBm = kc(d->pBm);
             const auto *nBm = kc(d->nBm);
             const auto *BtoQ = kc(d->B_to_qm);
-            u64 nz = 0; // OR of the words this column stores (transparency sink)
+            const auto *Qrows = kc(d->q_rows); // exact K: rows {pB, nB, B_to_q[i][0..B-1], p, -p^-1}, split for DotAcc31
+            u64 nz = 0;                        // OR of the words this column stores (transparency sink)
             const auto q_row = [&](int i) {
-                const u64 c = neg ? pBm[i] : nBm[i];
-                const auto *mrow = BtoQ + i * B;
+                const auto *qrow = Qrows + i * (B + 4);
+                const u64 c = KMAX < 0 ? (neg ? qrow[0] : qrow[1]) : (neg ? pBm[i] : nBm[i]);
+                const auto *mrow = KMAX < 0 ? qrow + 2 : BtoQ + i * B;
                 u64 l2, h2;
                 if constexpr (KMAX < 0)
                 {
-                    DotAcc<KA + 2> acc2;
+                    DotAcc31<KA + 2> acc2;
                     acc2.template add<0>(a2s, c);
                     static_for<KA + 1>([&](auto J) {
                         if (lt_B(J.value))
@@ -503,8 +538,12 @@ namespace sealhip
                         if (lt_B(j))
                             mac128(l2, h2, tb[j], mrow[j]);
                 }
-                const u64 qp = d->q_p[i];
-                const u64 w = redc_finish(redc128(l2, h2, qp, d->q_ninv[i]), qp, d->q_rdp[i], small);
+                const u64 qp = KMAX < 0 ? qrow[B + 2] : d->q_p[i];
+                u64 w;
+                if constexpr (KMAX < 0)
+                    w = redc_canonical_hs(l2, h2, qp, qrow[B + 3]);
+                else
+                    w = redc_finish(redc128(l2, h2, qp, d->q_ninv[i]), qp, d->q_rdp[i], small);
                 pout[i * N] = w;
                 nz |= w;
                 __builtin_amdgcn_sched_barrier(0);
