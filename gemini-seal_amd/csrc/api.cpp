@@ -1970,6 +1970,141 @@ long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k,
     });
 }
 
+/* ------------------------------------------------------------------ BSGS matrix-vector product */
+namespace
+{
+    // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+    void do_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                    const std::vector<uint32_t> &baby, const std::vector<const sealhip_kswitch_key *> &bkeys,
+                                    const std::vector<uint32_t> &giant, const std::vector<const sealhip_kswitch_key *> &gkeys,
+                                    const uint64_t *plain_ntt, uint64_t *out)
+    {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+        const auto check_axis = [&](const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys) {
+            for (size_t i = 0; i < elts.size(); i++)
+            {
+                if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
+                    throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
+                if (elts[i] != 1 && keys[i]->key.n_digits < nd)
+                    throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+            }
+        };
+        check_axis(baby, bkeys);
+        check_axis(giant, gkeys);
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
+        if (count && (baby.empty() || giant.empty()))
+            throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        const std::size_t out_words = count * item, w_words = giant.size() * baby.size() * e.key_moduli.size() * e.n;
+        if (o < in + count * item && in < o + out_words)
+            throw std::invalid_argument("out must not overlap ct");
+        if (o < w + w_words && w < o + out_words)
+            throw std::invalid_argument("out must not overlap plain_ntt");
+        SinkScope sink(e, count);
+        sink.begin();
+        const auto run_keys = [](const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys) {
+            std::vector<const KSwitchKey *> r(elts.size(), nullptr);
+            for (size_t i = 0; i < elts.size(); i++)
+                if (elts[i] != 1)
+                    r[i] = &keys[i]->key;
+            return r;
+        };
+        const std::vector<const KSwitchKey *> bk = run_keys(baby, bkeys), gk = run_keys(giant, gkeys);
+        op_apply_galois_bsgs_plain(e, static_cast<int>(k), in, count, baby.data(), bk.data(), baby.size(), giant.data(), gk.data(),
+                                   giant.size(), w, o);
+    }
+} // namespace
+
+long sealhip_evaluator_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                               const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
+                                               uint32_t n_baby, const uint32_t *giant_elts,
+                                               const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
+                                               const uint64_t *plain_ntt, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(plain_ntt);
+    REQUIRE_PTR(out);
+    if (n_baby)
+    {
+        REQUIRE_PTR(baby_elts);
+        REQUIRE_PTR(baby_keys);
+        for (uint32_t i = 0; i < n_baby; i++)
+            if (baby_elts[i] != 1)
+                REQUIRE_PTR(baby_keys[i]);
+    }
+    if (n_giant)
+    {
+        REQUIRE_PTR(giant_elts);
+        REQUIRE_PTR(giant_keys);
+        for (uint32_t i = 0; i < n_giant; i++)
+            if (giant_elts[i] != 1)
+                REQUIRE_PTR(giant_keys[i]);
+    }
+    return guarded([&] {
+        do_apply_galois_bsgs_plain(ctx, k, ct, count, std::vector<uint32_t>(baby_elts, baby_elts + n_baby),
+                                   std::vector<const sealhip_kswitch_key *>(baby_keys, baby_keys + n_baby),
+                                   std::vector<uint32_t>(giant_elts, giant_elts + n_giant),
+                                   std::vector<const sealhip_kswitch_key *>(giant_keys, giant_keys + n_giant), plain_ntt, out);
+    });
+}
+
+long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
+                                                uint32_t n_giant, const uint32_t *galois_elts,
+                                                const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                const uint64_t *plain_ntt, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(plain_ntt);
+    REQUIRE_PTR(out);
+    if (n_baby)
+        REQUIRE_PTR(baby_steps);
+    if (n_giant)
+        REQUIRE_PTR(giant_steps);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        const auto axis = [&](const int32_t *steps, uint32_t n, std::vector<uint32_t> &elts,
+                              std::vector<const sealhip_kswitch_key *> &keys) {
+            elts.assign(n, 1);
+            keys.assign(n, nullptr);
+            for (uint32_t s = 0; s < n; s++)
+            {
+                if (steps[s] == 0)
+                    continue; // (element 1)
+                elts[s] = host_galois_elt_from_step(h.n, steps[s]);
+                for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
+                    if (galois_elts[i] == elts[s])
+                        keys[s] = galois_keys[i];
+                if (!keys[s])
+                    throw std::invalid_argument("Galois key not present");
+            }
+        };
+        std::vector<uint32_t> baby, giant;
+        std::vector<const sealhip_kswitch_key *> bkeys, gkeys;
+        axis(baby_steps, n_baby, baby, bkeys);
+        axis(giant_steps, n_giant, giant, gkeys);
+        do_apply_galois_bsgs_plain(ctx, k, ct, count, baby, bkeys, giant, gkeys, plain_ntt, out);
+    });
+}
+
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
 
 long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

@@ -627,6 +627,34 @@ namespace sealhip
                                      u64 *out, std::size_t out_sum_stride, int k, std::size_t count, std::size_t n_sums,
                                      bool add);
 
+    // giant steps in the extended basis: the giants of one launch. table[i] == null is the identity
+    // giant, which only adds accj[i]; else inb[i] / ext[i] are the in-bundle rows and the digits of d_i for giant i's first
+    // ciphertext (item strides inb_stride / ext_stride), key[i] its key, accj[i] its inner sum's acc (null: none was formed).
+    struct HoistGiantElts
+    {
+        int n;
+        const std::uint32_t *table[kHoistMaxElts];
+        const u64 *key[kHoistMaxElts];
+        const u64 *inb[kHoistMaxElts];
+        const u64 *ext[kHoistMaxElts];
+        const u64 *accj[kHoistMaxElts];
+    };
+    // acc[item][2][k + nsp][N] (item stride acc_stride) = the sum over the giants of their permuted inner products with
+    // their keys, plus the permuted accj[.][0] (both components of accj straight for an identity giant); add: plus what
+    // acc holds
+    hipError_t launch_hoist_giant_mac(const Engine &e, const KsDev *d, const KsDev &h, const HoistGiantElts &elts,
+                                      std::size_t inb_stride, std::size_t ext_stride, std::size_t ext_digit_stride,
+                                      std::size_t accj_stride, u64 *acc, std::size_t acc_stride, std::size_t count, bool add);
+    struct HoistGiantBases
+    {
+        int n;
+        const std::uint32_t *table[kHoistMaxElts];
+        const u64 *base[kHoistMaxElts]; // base_i of the first ciphertext, [item][2][k][N]
+    };
+    // out[item][2][k][N] = (sum_i sigma_i(base_i[0]), sum_{i identity} base_i[1]) in NTT form; add: plus what out holds
+    hipError_t launch_hoist_giant_base(const Engine &e, const HoistGiantBases &elts, u64 *out, int k, std::size_t count,
+                                       bool add);
+
     // ---- batches of separately allocated host ciphertexts (hostbatch.cpp) ----
     struct HostBatchIO
     {
@@ -690,6 +718,12 @@ namespace sealhip
     void op_apply_galois_dot_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
                                    const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
                                    std::size_t n_sums, u64 *out);
+    // sum_j sigma_{h_j}( sum_i W[j][i] * sigma_{g_i}(ct) ) with the giant steps accumulated in the extended basis and one
+    // full mod-down: out[count][2][k][N]; plain_ntt[n_giant][n_baby][n_key][N]; a key may be null
+    // where its element is 1.
+    void op_apply_galois_bsgs_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *baby_elts,
+                                    const KSwitchKey *const *baby_keys, std::size_t n_baby, const std::uint32_t *giant_elts,
+                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out);
     void op_multiply_plain(Engine &e, int k, u64 *ct, int size, std::size_t count, const u64 *plain,
                            std::size_t plain_stride);
     // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV: plain_ntt[count][k][N]

@@ -380,6 +380,217 @@ namespace sealhip
             }
         }
 
+        // ---- giant steps in the extended basis ----
+        // ACC[l][r][c] += sum over the giants h of the launch of
+        //     ( sum_t D_t(d_h)[r][T_h[c]] * K_h[t][l][rp(r)][c] ) mod p_r   (+ acc_h[0][r][T_h[c]] for l = 0),
+        // and acc_h[l][r][c] itself for an identity giant (table == null). A lane owns column c of one extended row for four
+        // ciphertexts; the giant loop is outermost and wave-uniform, so the 2 * ND key words of a giant are loaded once for the
+        // lane's ciphertexts. Every giant has digits of its own (d_h differs from giant to giant): ext[el] / inb[el] are the
+        // bases of giant el's first ciphertext, the in-bundle row is read from d_h itself (inb) as my_digit does everywhere.
+        // Accumulator bound: one giant's inner product is at most ND <= 16 products below 2^122, below 2^126, and is reduced
+        // to its canonical residue at once -- sixteen giants of sixteen digits would be 256 such products, past 2^128. The
+        // running sums s[g][l] are kept canonical with add_mod (two or three words below p < 2^61 meet per giant), so any
+        // number of giants fits; add != 0 adds the words an earlier launch left in ACC.
+        template <int ND>
+        __global__ __launch_bounds__(kThreads) void hoist_giant_mac_kernel(const KsDev *__restrict__ d,
+                                                                           const PrimeDev *__restrict__ primes,
+                                                                           HoistGiantElts elts, std::size_t inb_stride,
+                                                                           std::size_t ext_stride, std::size_t ext_digit_stride,
+                                                                           std::size_t accj_stride, u64 *__restrict__ acc,
+                                                                           std::size_t acc_stride, std::size_t count, int logn,
+                                                                           int add)
+        {
+            constexpr int G = 4;
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            // (a workgroup lies inside one row, as in hoist_mac_kernel: row and item group are wave-uniform)
+            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
+            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
+            const unsigned q = blockIdx.x / blocks_per_row;
+            const int r = static_cast<int>(q % rows);
+            const std::size_t item0 = static_cast<std::size_t>(q / rows) * G;
+            if (item0 >= count)
+                return;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N, comp = static_cast<std::size_t>(rows) * N;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            u64 s[G][2];
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                s[g][0] = s[g][1] = 0;
+            for (int el = 0; el < elts.n; el++)
+            {
+                const std::uint32_t *tab = elts.table[el];
+                const u64 *pa = elts.accj[el];
+                if (!tab) // the identity giant: acc_h as it lies
+                {
+                    pa += item0 * accj_stride + row_off + c;
+#pragma unroll
+                    for (int g = 0; g < G; g++, pa += accj_stride)
+                    {
+                        if (item0 + g >= count)
+                            break;
+                        s[g][0] = add_mod(s[g][0], pa[0], p);
+                        s[g][1] = add_mod(s[g][1], pa[comp], p);
+                    }
+                    continue;
+                }
+                // (addresses are walked, not indexed: hoist_dot_mac_kernel records why)
+                const u64 *pk = elts.key[el] + prime_off;
+                const std::size_t src_off = row_off + tab[c];
+                u64 k0[ND], k1[ND];
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                {
+                    k0[j] = pk[0];
+                    k1[j] = pk[key_comp];
+                    pk += 2 * key_comp;
+                }
+                const u64 *pt = elts.inb[el] + item0 * inb_stride + src_off, *pe = elts.ext[el] + item0 * ext_stride + src_off;
+                if (pa)
+                    pa += item0 * accj_stride + src_off;
+#pragma unroll
+                for (int g = 0; g < G; g++, pt += inb_stride, pe += ext_stride)
+                {
+                    if (item0 + g >= count)
+                        break;
+                    u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+                    const u64 *px = pe;
+#pragma unroll
+                    for (int j = 0; j < ND; j++, px += ext_digit_stride)
+                    {
+                        const u64 x = j == my_digit ? *pt : *px;
+                        mac128(l0, h0, x, k0[j]);
+                        mac128(l1, h1, x, k1[j]);
+                    }
+                    s[g][0] = add_mod(s[g][0], barrett_reduce_128(l0, h0, p, cr0, cr1), p);
+                    s[g][1] = add_mod(s[g][1], barrett_reduce_128(l1, h1, p, cr0, cr1), p);
+                    if (pa)
+                    {
+                        s[g][0] = add_mod(s[g][0], *pa, p);
+                        pa += accj_stride;
+                    }
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; g++)
+            {
+                if (item0 + g >= count)
+                    continue;
+                u64 *po = acc + (item0 + g) * acc_stride + row_off + c;
+                u64 v0 = s[g][0], v1 = s[g][1];
+                if (add)
+                {
+                    v0 = add_mod(v0, po[0], p);
+                    v1 = add_mod(v1, po[comp], p);
+                }
+                store_stream(po, v0);
+                store_stream(po + comp, v1);
+            }
+        }
+
+        // Digit counts without an instance and rings smaller than a workgroup: one lane per (item, row, c), the key words
+        // streamed per giant. The same sums in the same canonical form.
+        __global__ __launch_bounds__(kThreads) void hoist_giant_mac_loop_kernel(
+            const KsDev *__restrict__ d, const PrimeDev *__restrict__ primes, HoistGiantElts elts, std::size_t inb_stride,
+            std::size_t ext_stride, std::size_t ext_digit_stride, std::size_t accj_stride, u64 *__restrict__ acc,
+            std::size_t acc_stride, std::size_t count, int logn, int nd, int add)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t c = i & (N - 1);
+            const std::size_t q = i >> logn;
+            const int r = static_cast<int>(q % rows);
+            const std::size_t item = q / rows;
+            if (item >= count)
+                return;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N, comp = static_cast<std::size_t>(rows) * N;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            u64 s0 = 0, s1 = 0;
+            for (int el = 0; el < elts.n; el++)
+            {
+                const std::uint32_t *tab = elts.table[el];
+                const u64 *pa = elts.accj[el];
+                if (!tab)
+                {
+                    s0 = add_mod(s0, pa[item * accj_stride + row_off + c], p);
+                    s1 = add_mod(s1, pa[item * accj_stride + comp + row_off + c], p);
+                    continue;
+                }
+                const u64 *pkey = elts.key[el] + prime_off;
+                const std::size_t src_off = row_off + tab[c];
+                u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+                for (int j = 0; j < nd; j++)
+                {
+                    const u64 x = j == my_digit ? elts.inb[el][item * inb_stride + src_off]
+                                                : elts.ext[el][item * ext_stride +
+                                                               static_cast<std::size_t>(j) * ext_digit_stride + src_off];
+                    mac128(l0, h0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
+                    mac128(l1, h1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
+                }
+                s0 = add_mod(s0, barrett_reduce_128(l0, h0, p, cr0, cr1), p);
+                s1 = add_mod(s1, barrett_reduce_128(l1, h1, p, cr0, cr1), p);
+                if (pa)
+                    s0 = add_mod(s0, pa[item * accj_stride + src_off], p);
+            }
+            u64 *po = acc + item * acc_stride + row_off + c;
+            if (add)
+            {
+                s0 = add_mod(s0, po[0], p);
+                s1 = add_mod(s1, po[comp], p);
+            }
+            store_stream(po, s0);
+            store_stream(po + comp, s1);
+        }
+
+        // BASE of section 17, on the k ciphertext rows: out[item][0][r][c] = sum over the giants of the launch of
+        // base_h[item][0][r][T_h[c]], out[item][1][r][c] = the sum of base_h[item][1][r][c] over the identity giants
+        // (table == null). base_h is canonical (hoist_dot_base_kernel wrote it), item stride 2 k N like out.
+        __global__ __launch_bounds__(kThreads) void hoist_giant_base_kernel(HoistGiantBases elts, u64 *__restrict__ out,
+                                                                            const PrimeDev *__restrict__ primes, int k, int logn,
+                                                                            std::size_t count, int add)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn, nmask = N - 1;
+            const std::size_t poly = static_cast<std::size_t>(k) << logn;
+            const std::size_t total = (count * k) << logn;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
+            {
+                const std::size_t c = i & nmask;
+                const std::size_t q = i >> logn;
+                const int row = static_cast<int>(q % k);
+                const std::size_t at = (q / k) * 2 * poly + static_cast<std::size_t>(row) * N;
+                const u64 p = primes[row].p;
+                u64 v0 = 0, v1 = 0;
+                for (int el = 0; el < elts.n; el++)
+                {
+                    const u64 *in = elts.base[el] + at;
+                    const std::uint32_t *tab = elts.table[el];
+                    v0 = add_mod(v0, in[tab ? tab[c] : c], p);
+                    if (!tab)
+                        v1 = add_mod(v1, in[poly + c], p);
+                }
+                u64 *o = out + at + c;
+                if (add)
+                {
+                    v0 = add_mod(v0, o[0], p);
+                    v1 = add_mod(v1, o[poly], p);
+                }
+                o[0] = v0;
+                o[poly] = v1;
+            }
+        }
+
         inline unsigned blocks_for(std::size_t lanes)
         {
             return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
@@ -524,6 +735,65 @@ namespace sealhip
         hoist_dot_base_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(cn, elts, w_sum_stride, out, out_sum_stride,
                                                                                 e.d_primes, k, e.logn, count, n_sums,
                                                                                 add ? 1 : 0);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_hoist_giant_mac(const Engine &e, const KsDev *d, const KsDev &h, const HoistGiantElts &elts,
+                                      std::size_t inb_stride, std::size_t ext_stride, std::size_t ext_digit_stride,
+                                      std::size_t accj_stride, u64 *acc, std::size_t acc_stride, std::size_t count, bool add)
+    {
+        if (!count || !elts.n)
+            return hipSuccess;
+        if (elts.n < 0 || elts.n > kHoistMaxElts)
+            return hipErrorInvalidValue;
+        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
+        const std::size_t glanes = (((count + 3) / 4) * rows) << e.logn; // four ciphertexts per lane
+        ProfScope prof(e, "hoist_giant_mac", 0);
+#define SEALHIP_HOIST_GIANT_ARGS \
+    d, e.d_primes, elts, inb_stride, ext_stride, ext_digit_stride, accj_stride, acc, acc_stride, count, e.logn
+#define SEALHIP_HOIST_GIANT(ND)                                                                                          \
+    case ND:                                                                                                             \
+        hoist_giant_mac_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_GIANT_ARGS,       \
+                                                                                         add ? 1 : 0);                   \
+        break;
+        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
+        {
+            SEALHIP_HOIST_GIANT(1)
+            SEALHIP_HOIST_GIANT(2)
+            SEALHIP_HOIST_GIANT(3)
+            SEALHIP_HOIST_GIANT(4)
+            SEALHIP_HOIST_GIANT(5)
+            SEALHIP_HOIST_GIANT(6)
+            SEALHIP_HOIST_GIANT(7)
+            SEALHIP_HOIST_GIANT(8)
+            SEALHIP_HOIST_GIANT(9)
+            SEALHIP_HOIST_GIANT(10)
+            SEALHIP_HOIST_GIANT(11)
+            SEALHIP_HOIST_GIANT(12)
+            SEALHIP_HOIST_GIANT(13)
+            SEALHIP_HOIST_GIANT(14)
+            SEALHIP_HOIST_GIANT(15)
+            SEALHIP_HOIST_GIANT(16)
+        default: // more than 16 digits, or a ring smaller than a workgroup
+            hoist_giant_mac_loop_kernel<<<blocks_for((count * rows) << e.logn), kThreads, 0, e.lane().stream>>>(
+                SEALHIP_HOIST_GIANT_ARGS, h.nd, add ? 1 : 0);
+        }
+#undef SEALHIP_HOIST_GIANT
+#undef SEALHIP_HOIST_GIANT_ARGS
+        return hipGetLastError();
+    }
+
+    hipError_t launch_hoist_giant_base(const Engine &e, const HoistGiantBases &elts, u64 *out, int k, std::size_t count,
+                                       bool add)
+    {
+        const std::size_t total = (count * static_cast<std::size_t>(k)) << e.logn;
+        if (total == 0 || !elts.n)
+            return hipSuccess;
+        if (elts.n < 0 || elts.n > kHoistMaxElts)
+            return hipErrorInvalidValue;
+        ProfScope prof(e, "hoist_giant_base", 0);
+        hoist_giant_base_kernel<<<grid_for(total), kThreads, 0, e.lane().stream>>>(elts, out, e.d_primes, k, e.logn, count,
+                                                                                  add ? 1 : 0);
         return hipGetLastError();
     }
 } // namespace sealhip

@@ -267,16 +267,36 @@ namespace sealhip
         // The part after the inner product (evaluator.cpp:2351-2366): the m x 2 reduced products go through
         // rescale_special_rns_inplace and are added into the ciphertexts (or, with c0p, stored as (c0p + r0, r1)).
         // sink: the transparency flags of these m ciphertexts (null: none).
+        // one_component: the same launches at polynomial granularity. prod is then component 1 of the
+        // first of m products that lie 2 (k + nsp) N words apart (their components 0 are neither read nor written), ctp is
+        // m polynomials of k rows back to back (ct_stride = 2 k N: the kernels' polynomial `pl` of ciphertext `pl >> 1`
+        // lands on polynomial `pl`), temp holds m polynomials, and there is no c0p and no sink.
         void ks_finish(Engine &e, LevelTools &lt, int k, u64 *prod, u64 *temp, u64 *ctp, std::size_t ct_stride, const u64 *c0p,
-                       std::size_t c0_stride, std::size_t m, unsigned *sink)
+                       std::size_t c0_stride, std::size_t m, unsigned *sink, bool one_component = false)
         {
             const KsDev &h = lt.h_ks;
             const std::size_t N = e.n;
             const int rows = k + e.nsp;
             const bool ckks = e.scheme == 2;
             const RowMap map_q = lt.map_q;
-            const RowMap map_rows = lt.map_key;
             const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            // what the transforms of prod walk: m x 2 polynomials of `rows` rows from prod on -- or, for one component, the
+            // same rows from the skipped component 0 on, under a map of 2 * rows rows that leaves the first half alone
+            RowMap map_rows = lt.map_key;
+            u64 *const prod_rows = one_component ? prod - ext_item : prod;
+            const std::size_t npolys = one_component ? m : 2 * m, prod_stride = one_component ? 2 * ext_item : ext_item;
+            const int lead = one_component ? rows : 0; // rows of map_rows ahead of the polynomial's own
+            if (one_component)
+            {
+                if (c0p || sink || ct_stride != 2 * static_cast<std::size_t>(k) * N || 2 * rows > kMaxRows)
+                    throw std::logic_error("internal: one-component mod-down misused");
+                map_rows.rows = 2 * rows;
+                for (int r = 0; r < rows; r++)
+                {
+                    map_rows.prime[rows + r] = map_rows.prime[r];
+                    map_rows.prime[r] = kSkipRow;
+                }
+            }
             if (!ckks)
             {
                 // BFV: every row of both products goes back to coefficient form in one launch (the reference does the
@@ -284,9 +304,9 @@ namespace sealhip
                 // order of independent row transforms does not matter), then one fused mod-down kernel
                 const bool defer = ntt_can_defer_top(e, k);
                 // (ks_moddown_bfv reduces what it reads canonically: any representative below 2p will do)
-                check(launch_ntt(e, prod, m * 2 * rows, map_rows, true, (defer ? kNttDeferTop : 0) | kNttAnyRep), "intt(prod)");
+                check(launch_ntt(e, prod_rows, m * 2 * rows, map_rows, true, (defer ? kNttDeferTop : 0) | kNttAnyRep), "intt(prod)");
                 SinkArm arm(e, sink); // (component 1 of the m ciphertexts of this chunk)
-                check(launch_ks_moddown_bfv(e, lt.d_ks, h, prod, ext_item, ctp, ct_stride, 2 * m, defer, c0p, c0_stride),
+                check(launch_ks_moddown_bfv(e, lt.d_ks, h, prod, prod_stride, ctp, ct_stride, npolys, defer, c0p, c0_stride),
                       "moddown_bfv");
                 return;
             }
@@ -307,7 +327,8 @@ namespace sealhip
             const bool fold_store = fold_top && ntt_can_fuse_moddown(e, k, p_special);
             // (:2351-2355) special rows back to coefficient form (lazy)
             // (the mod-down reduces the special rows with barrett_reduce_63 / a Shoup product: canonical either way)
-            check(launch_ntt(e, prod, m * 2 * rows, skip_map(map_rows, k, rows), true, kNttAnyRep | (fold_top ? kNttDeferTop : 0)),
+            check(launch_ntt(e, prod_rows, m * 2 * rows, skip_map(map_rows, lead + k, lead + rows), true,
+                             kNttAnyRep | (fold_top ? kNttDeferTop : 0)),
                   "intt(special)");
             // Step 5 (:2361): rescale_special_rns_inplace, then add into the ciphertext (:2363-2366)
             // Step 5 for CKKS with one special prime P: temp_i = (-(special mod P)) mod q_i, then its forward transform
@@ -317,14 +338,14 @@ namespace sealhip
             {
                 NttSource ns{};
                 ns.base[0] = prod;
-                ns.poly_stride[0] = ext_item;
+                ns.poly_stride[0] = prod_stride;
                 ns.reduce_mode = fold_store ? 7 : (fold_top ? 5 : 4);
                 if (fold_store)
                 {
                     ns.md.inv_p = lt.d_ks->invP; // (addresses inside the device copy of KsDev; not dereferenced here)
                     ns.md.inv_p_shoup = lt.d_ks->invP_shoup;
                     ns.md.prod = prod;
-                    ns.md.prod_stride = ext_item;
+                    ns.md.prod_stride = prod_stride;
                     ns.md.ct = ctp;
                     ns.md.ct_stride = ct_stride;
                     ns.md.c0_src = c0p;
@@ -343,22 +364,22 @@ namespace sealhip
                 for (int r = 0; r < k; r++)
                     ns.code[r] = static_cast<unsigned short>(k); // every row of temp reads the special row of its polynomial
                 // (ks_moddown_post adds these rows to the q rows and reduces the sum canonically: any representative will do)
-                check(launch_ntt_gather(e, temp, m * 2 * k, map_q, ns, kNttAnyRep), "ntt(temp, gathered from the special row)");
+                check(launch_ntt_gather(e, temp, npolys * k, map_q, ns, kNttAnyRep), "ntt(temp, gathered from the special row)");
             }
             else
             {
-                check(launch_ks_moddown_pre(e, lt.d_ks, h, prod, ext_item, temp, static_cast<std::size_t>(k) * N, 2 * m),
+                check(launch_ks_moddown_pre(e, lt.d_ks, h, prod, prod_stride, temp, static_cast<std::size_t>(k) * N, npolys),
                       "moddown_pre");
                 if (ckks)
-                    check(launch_ntt(e, temp, m * 2 * k, map_q, false, kNttAnyRep), "ntt(temp)"); // (moddown_post reduces the sum)
+                    check(launch_ntt(e, temp, npolys * k, map_q, false, kNttAnyRep), "ntt(temp)"); // (moddown_post reduces the sum)
                 else
-                    check(launch_ntt(e, prod, m * 2 * rows, skip_map(map_rows, 0, k), true, kNttAnyRep), "intt(prod)");
+                    check(launch_ntt(e, prod_rows, m * 2 * rows, skip_map(map_rows, lead, lead + k), true, kNttAnyRep), "intt(prod)");
             }
             if (!fold_store)
             {
                 SinkArm arm(e, sink);
-                check(launch_ks_moddown_post(e, lt.d_ks, h, prod, ext_item, temp, static_cast<std::size_t>(k) * N, ctp,
-                                             ct_stride, 2 * m, 1, c0p, c0_stride),
+                check(launch_ks_moddown_post(e, lt.d_ks, h, prod, prod_stride, temp, static_cast<std::size_t>(k) * N, ctp,
+                                             ct_stride, npolys, 1, c0p, c0_stride),
                       "moddown_post");
             }
         }
@@ -1060,6 +1081,226 @@ namespace sealhip
                         check(launch_nonzero_tail(e, os, 2 * poly, poly, run * m, sink + first), "transparency");
                 }
             }
+        });
+    }
+    // ------------------------------------------------------------------------------------------
+    // Baby-step/giant-step matrix-vector product:
+    //     out = sum_j sigma_{h_j}( sum_i W[j][i] * sigma_{g_i}(ct) ), the giant steps accumulated in the extended basis
+    // ------------------------------------------------------------------------------------------
+    // Per inner sum j section 16's base_j and acc_j go to workspace. Only component 1 of a non-identity giant's inner sum is
+    // brought down (ks_finish at polynomial granularity): d_j, which the giant's key switch decomposes. Its inner product
+    // with K_h, the permuted acc_j[0] and, in Q, the permuted base_j[0] are accumulated (ACC in the arena, BASE in out), and
+    // ONE ks_finish brings the whole product down.
+    void op_apply_galois_bsgs_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *baby_elts,
+                                    const KSwitchKey *const *baby_keys, std::size_t n_baby, const std::uint32_t *giant_elts,
+                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        const bool ckks = e.scheme == 2;
+        if (!ckks && !e.mode_strict)
+            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
+        LevelTools &ld = e.level(k);
+        const KsDev &h = ld.h_ks;
+        const int nd = h.nd, rows = k + e.nsp;
+        const auto check_axis = [&](const std::uint32_t *elts, const KSwitchKey *const *keys, std::size_t n) {
+            std::size_t n_gal = 0;
+            for (std::size_t i = 0; i < n; i++)
+            {
+                if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
+                    throw std::invalid_argument("Galois element is not valid"); // :1880-1883
+                if (elts[i] == 1)
+                    continue;
+                if (!keys[i] || static_cast<int>(keys[i]->n_digits) < nd)
+                    throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+                n_gal++;
+            }
+            return n_gal;
+        };
+        const std::size_t n_gb = check_axis(baby_elts, baby_keys, n_baby), n_gg = check_axis(giant_elts, giant_keys, n_giant);
+        if (!count)
+            return;
+        if (!n_baby || !n_giant)
+            throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        std::vector<const std::uint32_t *> btab(n_baby, nullptr), gtab(n_giant, nullptr);
+        for (std::size_t i = 0; i < n_baby; i++)
+            if (baby_elts[i] != 1)
+                btab[i] = e.galois_table(baby_elts[i]); // (resident after the first call: the condition for a capture)
+        for (std::size_t j = 0; j < n_giant; j++)
+            if (giant_elts[j] != 1)
+                gtab[j] = e.galois_table(giant_elts[j]);
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t w_plain = static_cast<std::size_t>(h.n_total) * N, w_sum_stride = n_baby * w_plain;
+        const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+        const std::size_t w_digits = static_cast<std::size_t>(nd) * ext_item, w_prod = 2 * ext_item;
+        const bool any_acc = n_gb || n_gg;
+        // arena of one item. Once: the input's digits (when a baby differs from 1), BFV's transformed components, ACC and
+        // the final mod-down's temporaries (when any ACC term is formed); BASE lives in out. Per giant of a pass: base_j,
+        // acc_j (when a baby differs from 1) and, when a giant differs from 1, d_j, the one-component mod-down's
+        // temporaries and d_j's digits (identity giants leave theirs unused: one size for every giant keeps the plan simple).
+        const std::size_t w_coeff = n_gb ? poly : 0, w_ext = n_gb ? w_digits : 0;
+        const std::size_t w_cn = ckks ? 0 : 2 * poly;
+        const std::size_t w_acc = any_acc ? w_prod : 0, w_temp = any_acc ? 2 * poly : 0;
+        const std::size_t w_accj = n_gb ? w_prod : 0;
+        const std::size_t w_d = n_gg ? poly : 0, w_temp1 = n_gg && n_gb ? poly : 0;
+        const std::size_t w_coeff2 = n_gg ? poly : 0, w_ext2 = n_gg ? w_digits : 0;
+        const std::size_t base_bytes = (w_coeff + w_ext + w_cn + w_acc + w_temp) * sizeof(u64);
+        const std::size_t giant_bytes = (2 * poly + w_accj + w_d + w_temp1 + w_coeff2 + w_ext2) * sizeof(u64);
+        // when not even one item fits with all its giants, the giant list is walked in passes
+        std::size_t pass = n_giant;
+        const std::size_t budget = workspace_budget_bytes(e);
+        if (base_bytes + pass * giant_bytes > budget)
+        {
+            pass = budget > base_bytes ? (budget - base_bytes) / giant_bytes : 0;
+            pass = std::max<std::size_t>(1, std::min(pass, n_giant));
+            log_chunk(e, n_giant, pass); // (the giant split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        }
+        unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext
+        for_chunks(e, count, base_bytes + pass * giant_bytes, 11, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
+            u64 *ext = w_ext ? e.ws_alloc(w_ext * m) : nullptr;
+            u64 *cntt = w_cn ? e.ws_alloc(w_cn * m) : nullptr;
+            u64 *ACC = w_acc ? e.ws_alloc(w_acc * m) : nullptr;
+            u64 *temp = w_temp ? e.ws_alloc(w_temp * m) : nullptr;
+            u64 *bw = e.ws_alloc(2 * poly * m * pass);
+            u64 *accj = w_accj ? e.ws_alloc(w_accj * m * pass) : nullptr;
+            u64 *dbuf = w_d ? e.ws_alloc(w_d * m * pass) : nullptr;
+            u64 *temp1 = w_temp1 ? e.ws_alloc(w_temp1 * m * pass) : nullptr;
+            u64 *coeff2 = w_coeff2 ? e.ws_alloc(w_coeff2 * m * pass) : nullptr;
+            u64 *ext2 = w_ext2 ? e.ws_alloc(w_ext2 * m * pass) : nullptr;
+            const u64 *c = ct + off * 2 * poly;
+            u64 *o = out + off * 2 * poly; // BASE of this chunk, then the result
+            KsRows in_bundle{ nullptr, 0 };
+            if (n_gb)
+                in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
+            const u64 *cn = c;
+            if (cntt)
+            {
+                SEALHIP_CHECK(hipMemcpyAsync(cntt, c, m * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream));
+                check(launch_ntt(e, cntt, m * 2 * k, ld.map_q, false, kNttCanonical), "ntt(ct)");
+                cn = cntt;
+            }
+            bool acc_started = false, base_started = false;
+            for (std::size_t g0 = 0; g0 < n_giant; g0 += pass)
+            {
+                const std::size_t ng = std::min(pass, n_giant - g0);
+                const u64 *w0 = plain_ntt + g0 * w_sum_stride;
+                // base_j and acc_j of the pass's inner sums: section 16's launches, into workspace
+                HoistDotElts he{};
+                bool launched = false;
+                for (std::size_t i = 0; i < n_baby; i++)
+                {
+                    he.table[he.n] = btab[i];
+                    he.key[he.n] = nullptr;
+                    he.w[he.n++] = w0 + i * w_plain;
+                    if (he.n == kHoistMaxElts || i + 1 == n_baby)
+                    {
+                        check(launch_hoist_dot_base(e, cn, he, w_sum_stride, bw, m * 2 * poly, k, m, ng, launched),
+                              "hoist_dot_base");
+                        he.n = 0;
+                        launched = true;
+                    }
+                }
+                launched = false;
+                for (std::size_t i = 0, seen = 0; i < n_baby; i++)
+                {
+                    if (baby_elts[i] == 1)
+                        continue;
+                    he.table[he.n] = btab[i];
+                    he.key[he.n] = baby_keys[i]->d_data;
+                    he.w[he.n++] = w0 + i * w_plain;
+                    seen++;
+                    if (he.n == kHoistMaxElts || seen == n_gb)
+                    {
+                        check(launch_hoist_dot_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m,
+                                                   he, w_sum_stride, accj, w_prod, m, ng, launched),
+                              "hoist_dot_mac");
+                        he.n = 0;
+                        launched = true;
+                    }
+                }
+                // d_j of the pass's non-identity giants, back to back in dbuf (target t = slot * m + item): base_j[1], for
+                // BFV in coefficient form, plus the mod-down of acc_j[1] -- one batch per run of consecutive such giants
+                std::vector<std::size_t> slot(ng, 0);
+                std::size_t n_nz = 0;
+                for (std::size_t s = 0; s < ng; s++)
+                    if (giant_elts[g0 + s] != 1)
+                        slot[s] = n_nz++;
+                KsRows in2{ nullptr, 0 };
+                if (n_nz)
+                {
+                    const auto for_runs = [&](const std::function<void(std::size_t s, std::size_t run)> &fn) {
+                        for (std::size_t s = 0, run; s < ng; s += run)
+                        {
+                            run = 1;
+                            if (giant_elts[g0 + s] == 1)
+                                continue;
+                            while (s + run < ng && giant_elts[g0 + s + run] != 1)
+                                run++;
+                            fn(s, run);
+                        }
+                    };
+                    for_runs([&](std::size_t s, std::size_t run) {
+                        check(launch_copy_rows(e, bw + s * m * 2 * poly + poly, 2 * poly, dbuf + slot[s] * m * poly, poly, run * m,
+                                               k),
+                              "copy(base_1)");
+                    });
+                    if (!ckks)
+                        check(launch_ntt(e, dbuf, n_nz * m * k, ld.map_q, true, kNttCanonical), "intt(base_1)");
+                    if (n_gb)
+                        for_runs([&](std::size_t s, std::size_t run) {
+                            ks_finish(e, ld, k, accj + s * m * w_prod + ext_item, temp1 + slot[s] * m * poly,
+                                      dbuf + slot[s] * m * poly, 2 * poly, nullptr, 0, run * m, nullptr, true);
+                        });
+                    // the giants' decompositions: the d_j of the pass as one batch of targets
+                    in2 = ks_digits(e, ld, k, dbuf, poly, n_nz * m, coeff2, ext2, 0, nd);
+                }
+                // ACC: the giants' inner products and the acc_j (an identity giant without acc_j contributes nothing)
+                HoistGiantElts ge{};
+                std::size_t last = ng;
+                for (std::size_t s = 0; s < ng; s++)
+                    if (giant_elts[g0 + s] != 1 || n_gb)
+                        last = s;
+                for (std::size_t s = 0; s < ng && last < ng; s++)
+                {
+                    const bool ident = giant_elts[g0 + s] == 1;
+                    if (!ident || n_gb)
+                    {
+                        ge.table[ge.n] = gtab[g0 + s];
+                        ge.key[ge.n] = ident ? nullptr : giant_keys[g0 + s]->d_data;
+                        ge.inb[ge.n] = ident ? nullptr : in2.inb + slot[s] * m * in2.inb_stride;
+                        ge.ext[ge.n] = ident ? nullptr : ext2 + slot[s] * m * ext_item;
+                        ge.accj[ge.n++] = n_gb ? accj + s * m * w_prod : nullptr;
+                    }
+                    if (ge.n == kHoistMaxElts || (s == last && ge.n))
+                    {
+                        check(launch_hoist_giant_mac(e, ld.d_ks, h, ge, in2.inb_stride, ext_item, ext_item * n_nz * m, w_prod, ACC,
+                                                     w_prod, m, acc_started),
+                              "hoist_giant_mac");
+                        ge.n = 0;
+                        acc_started = true;
+                    }
+                }
+                // BASE: the permuted base_j[0], and base_j[1] of the identity giants
+                HoistGiantBases gb{};
+                for (std::size_t s = 0; s < ng; s++)
+                {
+                    gb.table[gb.n] = gtab[g0 + s];
+                    gb.base[gb.n++] = bw + s * m * 2 * poly;
+                    if (gb.n == kHoistMaxElts || s + 1 == ng)
+                    {
+                        check(launch_hoist_giant_base(e, gb, o, k, m, base_started), "hoist_giant_base");
+                        gb.n = 0;
+                        base_started = true;
+                    }
+                }
+            }
+            if (!ckks)
+                check(launch_ntt(e, o, m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
+            if (any_acc)
+                ks_finish(e, ld, k, ACC, temp, o, 2 * poly, nullptr, 0, m, sink ? sink + off : nullptr);
+            else if (sink)
+                check(launch_nonzero_tail(e, o, 2 * poly, poly, m, sink + off), "transparency");
         });
     }
     // multiply_plain_normal (evaluator.cpp:1475-1603) for parameters with fast plain lift (every q_i > t): lift the

@@ -889,6 +889,77 @@ namespace sealhip_host
             apply_galois_dot_plain(encrypted, elts_of_steps(steps), galois_keys, plains, destinations);
         }
 
+        // Baby-step/giant-step matrix-vector product (sealhip_evaluator_apply_galois_bsgs_plain):
+        // destination = sum_j sigma_{giant_elts[j]}( sum_i plains[j][i] * sigma_{baby_elts[i]}(encrypted) ), the giant steps
+        // accumulated in the extended basis and ONE full mod-down. plains[giant][baby]: key-level NTT form, DevicePlaintext
+        // or host plaintexts, as apply_galois_dot_plain's; element 1 needs no key on either axis; one set of keys serves
+        // both. The result has the operand's level and NTT form and, for CKKS, the scale encrypted.scale() * plain.scale.
+        // std::invalid_argument as apply_galois_dot_plain (a row whose length is not baby_elts.size(), a matrix without
+        // giant_elts.size() rows). The words are those of the ABI entry, not of the composition.
+        template <class C, class P, IfCt<C> = 0>
+        void apply_galois_bsgs_plain(const C &encrypted, const std::vector<std::uint32_t> &baby_elts,
+                                     const std::vector<std::uint32_t> &giant_elts,
+                                     const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                     const std::vector<std::vector<P>> &plains, C &destination)
+        {
+            check_galois_operand(encrypted);
+            const auto raw_keys = [&](const std::vector<std::uint32_t> &elts) {
+                std::vector<const sealhip_kswitch_key *> raw;
+                for (std::uint32_t elt : elts)
+                {
+                    auto it = galois_keys.find(elt);
+                    if (elt != 1 && (it == galois_keys.end() || !it->second))
+                        throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
+                    raw.push_back(elt != 1 ? it->second->get() : nullptr);
+                }
+                return raw;
+            };
+            const std::vector<const sealhip_kswitch_key *> bk = raw_keys(baby_elts), gk = raw_keys(giant_elts);
+            const std::size_t n_baby = baby_elts.size(), n_giant = giant_elts.size();
+            if (plains.size() != n_giant)
+                throw std::invalid_argument("plains must hold one row of plaintexts per giant element");
+            const double scale = check_dot_plains(plains, n_baby);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
+            Dev c = dev_in(encrypted, words), o = dev_out(words);
+            Staged w(ctx_, (n_giant && n_baby) ? n_giant * n_baby * pw : 1);
+            for (std::size_t j = 0; j < n_giant; j++)
+                for (std::size_t i = 0; i < n_baby; i++)
+                    plain_to(plains[j][i], w.ptr() + (j * n_baby + i) * pw, pw);
+            Check chk = checked(encrypted, 1);
+            throw_on(sealhip_evaluator_apply_galois_bsgs_plain(ctx_.get(), std::uint32_t(k), c.ptr(), 1, baby_elts.data(), bk.data(),
+                                                               std::uint32_t(n_baby), giant_elts.data(), gk.data(),
+                                                               std::uint32_t(n_giant), w.ptr(), o.ptr()));
+            chk.done();
+            std::vector<C> one;
+            scatter(encrypted, o, 1, words, one);
+            destination = std::move(one[0]);
+            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
+                destination.scale() = encrypted.scale() * scale;
+        }
+        // The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): CKKS rotate_vector's steps; step 0 is the
+        // identity; no non-adjacent-form fallback
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_vector_bsgs_plain(const C &encrypted, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps,
+                                      const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                      const std::vector<std::vector<P>> &plains, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            apply_galois_bsgs_plain(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains,
+                                    destination);
+        }
+        // ... and BFV rotate_rows' steps
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_rows_bsgs_plain(const C &encrypted, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps,
+                                    const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                    const std::vector<std::vector<P>> &plains, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1061-1064
+            apply_galois_bsgs_plain(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains,
+                                    destination);
+        }
+
         // Evaluator::mod_switch_to_inplace (evaluator.cpp:1038-1060) / rescale_to_inplace (:1128-1165). The ABI names a level by
         // its number of primes k (the chain drops one prime per level, context.cpp:423-431); for seal::Ciphertext the
         // binding maps the parms_id argument to it.

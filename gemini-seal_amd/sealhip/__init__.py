@@ -135,6 +135,10 @@ SYMBOLS = {
     "sealhip_evaluator_apply_galois_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32, _vp],
     "sealhip_evaluator_rotate_vector_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp),
                                                   _u32, _vp, _u32, _vp],
+    "sealhip_evaluator_apply_galois_bsgs_plain": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, C.POINTER(_u32),
+                                                  C.POINTER(_vp), _u32, _vp, _vp],
+    "sealhip_evaluator_rotate_vector_bsgs_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_i32), _u32,
+                                                   C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -956,6 +960,31 @@ class Evaluator:
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
         _check(lib().sealhip_evaluator_rotate_vector_dot_plain(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka,
                                                                len(elts), _ptr(plains), n_sums, _ptr(out)))
+
+    def apply_galois_bsgs_plain(self, ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out):
+        """Baby-step/giant-step matrix-vector product (sealhip_evaluator_apply_galois_bsgs_plain):
+        out = sum_j sigma_{giant_elts[j]}( sum_i plains[j][i] * sigma_{baby_elts[i]}(ct) ), the giant steps accumulated in the
+        extended basis and ONE full mod-down. A key may be None for element 1 on either axis. plains: len(giant_elts) x
+        len(baby_elts) x n_key x N words in key-level NTT form; out: count x 2 x k x N; ct is not modified."""
+        baby_elts, giant_elts = [int(g) for g in baby_elts], [int(g) for g in giant_elts]
+        ba = (_u32 * max(1, len(baby_elts)))(*baby_elts)
+        bk = (_vp * max(1, len(baby_elts)))(*[key.handle if key is not None else None for key in baby_keys])
+        ga = (_u32 * max(1, len(giant_elts)))(*giant_elts)
+        gk = (_vp * max(1, len(giant_elts)))(*[key.handle if key is not None else None for key in giant_keys])
+        _check(lib().sealhip_evaluator_apply_galois_bsgs_plain(self.ctx.handle, k, _ptr(ct), count, ba, bk, len(baby_elts), ga,
+                                                               gk, len(giant_elts), _ptr(plains), _ptr(out)))
+
+    def rotate_vector_bsgs_plain(self, ct, k, count, baby_steps, giant_steps, galois_keys, plains, out):
+        """The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): step 0 is the identity and needs no key; a
+        step of either axis without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
+        baby_steps, giant_steps = [int(st) for st in baby_steps], [int(st) for st in giant_steps]
+        elts = list(galois_keys.keys())
+        bs = (_i32 * max(1, len(baby_steps)))(*baby_steps)
+        gs = (_i32 * max(1, len(giant_steps)))(*giant_steps)
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        _check(lib().sealhip_evaluator_rotate_vector_bsgs_plain(self.ctx.handle, k, _ptr(ct), count, bs, len(baby_steps), gs,
+                                                                len(giant_steps), ea, ka, len(elts), _ptr(plains), _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

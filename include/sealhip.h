@@ -490,6 +490,49 @@ long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k,
                                                const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
                                                const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out);
 
+/* Baby-step/giant-step matrix-vector product with the giant steps in the extended basis:
+       out = sum_j sigma_{h_j}( sum_i W[j][i] * sigma_{g_i}(ct) )   for j < n_giant, i < n_baby,
+   the core of an encrypted linear layer. Composed from sealhip_evaluator_apply_galois_dot_plain, _apply_galois and an add
+   per giant step, every inner sum is brought down to Q, goes through a full key switch with a second mod-down and is added
+   in a pass of its own. Here only component 1 of an inner sum comes down (the giant step's decomposition needs it); its
+   component 0 is permuted and accumulated in Q * P next to the giant steps' inner products, and the whole product is brought
+   down once: n_giant half mod-downs and one full one (Lattigo's linear transforms; Bossuat et al.). The fork has no such
+   method, and the words are NOT those of the composition; what defines them, word for word in the context's mode, is the
+   restatement over the oracle in tests/hoist_bsgs_ref.py. Symbols as for sealhip_evaluator_apply_galois_dot_plain; D_t(x)
+   are the rows switch_key_inplace multiplies with digit t for the target x:
+     1. base_j (on the k rows, NTT form -- for BFV it stays in NTT form here) and acc_j (on the k + nsp rows) are base_s and
+        acc_s of sealhip_evaluator_apply_galois_dot_plain for sum j with the elements g_i.
+     2. d_j, for h_j != 1: component 1 of the key switch's finish of acc_j[1] added into base_j[1] (for BFV base_j[1] first
+        goes through the canonical inverse transform). When no g_i differs from 1 there is no acc_j and d_j = base_j[1].
+     3. Over j, every sum canonical modulo the row's prime:
+          h_j  = 1:  ACC[l] += acc_j[l], BASE[l] += base_j[l], both l;
+          h_j != 1:  ACC[l][r][c] += ( sum_t D_t(d_j)[r][T_h[c]] * K_h[t][l][rp(r)][c] ) mod p_r, both l,
+                     ACC[0][r][c] += acc_j[0][r][T_h[c]], r < k + nsp;   BASE[0][r][c] += base_j[0][r][T_h[c]], r < k.
+     4. For BFV the canonical inverse transform of BASE; out = the key switch's finish of ACC added into BASE. If no ACC
+        term was ever formed (every g_i and every h_j is 1), out = BASE.
+   Repeated elements add; element 1 needs no key on either axis (its key pointer may be NULL).
+   plain_ntt: n_giant x n_baby x n_key x N words in KEY-LEVEL NTT form, exactly sealhip_evaluator_apply_galois_dot_plain's
+   plain_ntt with n_sums = n_giant. ct: count x 2 x k x N, not modified. out: count x 2 x k x N; out must overlap neither ct
+   nor plain_ntt. Everything is device memory. CKKS in both modes and BFV in STRICT mode; BFV in PARITY mode is E_INVALIDARG.
+   Checks: NULL pointers -> E_POINTER (a NULL key only for element 1); then, also on host-only contexts, k outside the
+   ciphertext levels, an even element or one >= 2N, a key with fewer digits than the level, BFV in PARITY mode, n_baby == 0
+   or n_giant == 0 when count > 0 -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only context ->
+   COR_E_INVALIDOPERATION. With a transparency sink: one flag per output ciphertext (count flags). Nothing synchronises;
+   capturable once the Galois tables of the elements are resident (after one call with them). */
+long sealhip_evaluator_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                               const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
+                                               uint32_t n_baby, const uint32_t *giant_elts,
+                                               const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
+                                               const uint64_t *plain_ntt, uint64_t *out);
+/* The same by rotation steps (galois_elt_from_step): baby and giant steps with ONE set of keys for both axes;
+   plain_ntt: n_giant x n_baby x n_key x N. Step 0 is element 1 and needs no key; a step whose key is absent ->
+   E_INVALIDARG ("Galois key not present"), there is no non-adjacent-form fallback. */
+long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
+                                                uint32_t n_giant, const uint32_t *galois_elts,
+                                                const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                const uint64_t *plain_ntt, uint64_t *out);
+
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
    of the ciphertext (is_ntt_form). sk_powers_ntt = the Decryptor's secret_key_array_: (size-1) polynomials s, s^2, ...

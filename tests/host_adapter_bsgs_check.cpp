@@ -1,0 +1,235 @@
+// The C++ host adapter's baby-step/giant-step matrix-vector product (gemini-seal_amd/host/evaluator.hpp:
+// apply_galois_bsgs_plain, rotate_vector_bsgs_plain, rotate_rows_bsgs_plain). argv[1] = "host": on host-only contexts, the
+// operand and plaintext checks and their messages, the missing key on either axis, the wrong scheme, and a valid call
+// reaching the ABI (which has no CPU fallback). argv[1] = device ordinal, argv[2] = "ckks" or "bfv", argv[3..6] = four key
+// primes (N = 4096, one special prime; BFV in STRICT mode with t = 65537): digests of the result on the host ciphertext type
+// and on DeviceCiphertext / DevicePlaintext for seeded inputs, which the Python test compares with the C ABI's output for
+// the same inputs; the level, form and scale of the result.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../gemini-seal_amd/host/evaluator.hpp"
+
+using namespace sealhip_host;
+
+static std::uint64_t splitmix(std::uint64_t &s)
+{
+    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
+{
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
+    for (std::size_t i = 0; i < words * 8; i++)
+    {
+        h ^= p[i];
+        h *= 0x100000001b3ULL;
+    }
+    return h;
+}
+
+template <class E, class F>
+static bool throws(F &&f, const char *msg)
+{
+    try
+    {
+        f();
+    }
+    catch (const E &e)
+    {
+        if (std::strstr(e.what(), msg) != nullptr)
+            return true;
+        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
+        return false;
+    }
+    catch (const std::exception &e)
+    {
+        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
+        return false;
+    }
+    std::printf("no exception (want '%s')\n", msg);
+    return false;
+}
+
+static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
+{
+    HostCiphertext c;
+    c.n_ = n;
+    c.resize_raw(size, k);
+    c.ntt_form_ = ntt;
+    return c;
+}
+
+static HostPlaintext host_plain(std::size_t k, std::size_t n, bool ntt, double scale)
+{
+    HostPlaintext p;
+    p.words.assign(k * n, 1);
+    p.k = k;
+    p.ntt_form = ntt;
+    p.scale = scale;
+    return p;
+}
+
+using Plains = std::vector<std::vector<HostPlaintext>>;
+
+static int host_checks()
+{
+    const std::uint64_t mods[4] = { 1073738753ULL, 1099511603713ULL, 1152921504606830593ULL, 1152921504606844417ULL };
+    const std::size_t n = 256, n_key = 4;
+    bool ok = true;
+    for (std::uint32_t scheme : { SEALHIP_SCHEME_BFV, SEALHIP_SCHEME_CKKS })
+    {
+        const bool bfv = scheme == SEALHIP_SCHEME_BFV;
+        sealhip_params p{ scheme, 8, 4, 2, mods, bfv ? 786433ULL : 0ULL, SEALHIP_MODE_STRICT, -1 };
+        Context ctx(p);
+        Evaluator<HostCiphertext> ev(ctx);
+        const std::map<std::uint32_t, const KSwitchKeys *> none;
+        HostCiphertext out = host_ct(3, 1, n, false);
+        const HostCiphertext good = host_ct(2, 2, n, !bfv), wrong_form = host_ct(2, 2, n, bfv), three = host_ct(3, 2, n, !bfv);
+        const HostPlaintext w = host_plain(n_key, n, true, 4.0);
+        const Plains one{ { w } }, two{ { w, w } }, square{ { w, w }, { w, w } };
+        const char *form = bfv ? "BFV encrypted cannot be in NTT form" : "CKKS encrypted must be in NTT form";
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(wrong_form, { 1 }, { 1 }, none, one, out); }, form);
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(three, { 1 }, { 1 }, none, one, out); },
+                                            "encrypted size must be 2");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 3 }, { 1 }, none, one, out); },
+                                            "Galois key not present");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 3 }, none, one, out); },
+                                            "Galois key not present");
+        // the plaintexts: rows per giant, a ragged row, a level below the key level, coefficient form, unequal scales (CKKS)
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1, 1 }, { 1 }, none, square, out); },
+                                            "one row of plaintexts per giant element");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 1 }, none, two, out); },
+                                            "one plaintext per Galois element");
+        ok &= throws<std::invalid_argument>(
+            [&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 1 }, none, Plains{ { host_plain(2, n, true, 4.0) } }, out); },
+            "NTT form at the key level");
+        ok &= throws<std::invalid_argument>(
+            [&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 1 }, none, Plains{ { host_plain(n_key, n, false, 4.0) } }, out); },
+            "NTT form at the key level");
+        const Plains scales{ { w, host_plain(n_key, n, true, 8.0) } };
+        if (bfv) // (BFV plaintexts have no scale: the call goes on to the device, which a host-only context does not have)
+            ok &= throws<std::logic_error>([&] { ev.apply_galois_bsgs_plain(good, { 1, 1 }, { 1 }, none, scales, out); },
+                                           "host-only");
+        else
+            ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1, 1 }, { 1 }, none, scales, out); },
+                                                "scale mismatch");
+        // the steps forms name their scheme
+        if (bfv)
+            ok &= throws<std::logic_error>([&] { ev.rotate_vector_bsgs_plain(good, { 0 }, { 0 }, none, one, out); },
+                                           "unsupported scheme");
+        else
+            ok &= throws<std::logic_error>([&] { ev.rotate_rows_bsgs_plain(good, { 0 }, { 0 }, none, one, out); },
+                                           "unsupported scheme");
+        ok &= out.size() == 3 && out.coeff_modulus_size() == 1; // (a refused call leaves the destination alone)
+        // a valid call (step 0 needs no key) reaches the device, which a host-only context does not have
+        if (bfv)
+            ok &= throws<std::logic_error>([&] { ev.rotate_rows_bsgs_plain(good, { 0 }, { 0 }, none, one, out); }, "host-only");
+        else
+            ok &= throws<std::logic_error>([&] { ev.rotate_vector_bsgs_plain(good, { 0 }, { 0 }, none, one, out); }, "host-only");
+        ok &= throws<std::logic_error>([&] { ev.apply_galois_bsgs_plain(good, { 1, 1 }, { 1, 1 }, none, square, out); },
+                                       "host-only");
+    }
+    if (!ok)
+        return 1;
+    std::printf("host-only bsgs checks ok\n");
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    try
+    {
+        if (argc < 2 || std::strcmp(argv[1], "host") == 0)
+            return host_checks();
+        if (argc < 7)
+            return 2;
+        const int device = std::atoi(argv[1]);
+        const bool bfv = std::strcmp(argv[2], "bfv") == 0;
+        std::uint64_t mods[4];
+        for (int i = 0; i < 4; i++)
+            mods[i] = std::strtoull(argv[3 + i], nullptr, 10);
+        const std::size_t n = 4096, k = 3, nk = 4, nd = 3, n_giant = 3, n_baby = 2;
+        sealhip_params p{ bfv ? SEALHIP_SCHEME_BFV : SEALHIP_SCHEME_CKKS, 12, 4, 1, mods, bfv ? 65537ULL : 0ULL,
+                          bfv ? SEALHIP_MODE_STRICT : SEALHIP_MODE_PARITY, device };
+        Context ctx(p);
+        std::uint64_t state = 0x4017;
+        HostCiphertext ct = host_ct(2, k, n, !bfv);
+        ct.scale_ = bfv ? 1.0 : 1048576.0;
+        for (std::size_t r = 0; r < 2 * k; r++)
+            for (std::size_t i = 0; i < n; i++)
+                ct.words[r * n + i] = splitmix(state) % mods[r % k];
+        const int steps[3] = { 1, -2, 4 };
+        std::uint32_t elts[3];
+        std::vector<std::unique_ptr<KSwitchKeys>> keys;
+        std::map<std::uint32_t, const KSwitchKeys *> gk;
+        for (int e = 0; e < 3; e++)
+        {
+            throw_on(sealhip_galois_elt_from_step(ctx.get(), steps[e], &elts[e]));
+            std::vector<std::uint64_t> w(nd * 2 * nk * n);
+            for (std::size_t r = 0; r < nd * 2 * nk; r++)
+                for (std::size_t i = 0; i < n; i++)
+                    w[r * n + i] = splitmix(state) % mods[r % nk];
+            keys.emplace_back(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            gk[elts[e]] = keys.back().get();
+        }
+        const double pscale = bfv ? 1.0 : 1024.0;
+        Plains plains(n_giant, std::vector<HostPlaintext>(n_baby));
+        std::vector<std::vector<DevicePlaintext>> dplains(n_giant);
+        for (std::size_t s = 0; s < n_giant; s++)
+            for (std::size_t e = 0; e < n_baby; e++)
+            {
+                HostPlaintext &w = plains[s][e];
+                w.words.resize(nk * n);
+                w.k = nk;
+                w.ntt_form = true;
+                w.scale = pscale;
+                for (std::size_t r = 0; r < nk; r++)
+                    for (std::size_t i = 0; i < n; i++)
+                        w.words[r * n + i] = splitmix(state) % mods[r];
+                dplains[s].emplace_back(ctx);
+                dplains[s].back().upload(w.words, true);
+                dplains[s].back().scale() = pscale;
+            }
+        Evaluator<HostCiphertext> ev(ctx);
+        // babies: step 1 and the identity; giants: the identity, steps -2 and 4
+        const std::vector<std::uint32_t> baby{ elts[0], 1 }, giant{ 1, elts[1], elts[2] };
+        const std::vector<int> baby_steps{ 1, 0 }, giant_steps{ 0, -2, 4 };
+        auto report = [&](const char *what, const HostCiphertext &c) {
+            const std::uint64_t h = digest(0xcbf29ce484222325ULL, c.data(), c.words.size());
+            const bool meta = c.size() == 2 && c.coeff_modulus_size() == k && c.is_ntt_form() == !bfv &&
+                              (bfv || c.scale() == ct.scale() * pscale);
+            std::printf("%s digest %016llx meta %d\n", what, static_cast<unsigned long long>(h), int(meta));
+        };
+        HostCiphertext out;
+        ev.apply_galois_bsgs_plain(ct, baby, giant, gk, plains, out);
+        report("host apply_galois_bsgs_plain", out);
+        if (bfv)
+            ev.rotate_rows_bsgs_plain(ct, baby_steps, giant_steps, gk, plains, out);
+        else
+            ev.rotate_vector_bsgs_plain(ct, baby_steps, giant_steps, gk, plains, out);
+        report("host steps", out);
+        DeviceCiphertext d(ctx), dout(ctx);
+        d.upload(ct);
+        HostCiphertext back;
+        ev.apply_galois_bsgs_plain(d, baby, giant, gk, dplains, dout);
+        dout.download(back);
+        report("device apply_galois_bsgs_plain", back);
+        if (bfv)
+            ev.rotate_rows_bsgs_plain(d, baby_steps, giant_steps, gk, dplains, dout);
+        else
+            ev.rotate_vector_bsgs_plain(d, baby_steps, giant_steps, gk, dplains, dout);
+        dout.download(back);
+        report("device steps", back);
+    }
+    catch (const std::exception &e)
+    {
+        std::printf("error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
