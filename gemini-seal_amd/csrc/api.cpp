@@ -2105,6 +2105,76 @@ long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k
     });
 }
 
+/* ------------------------------------------------------------------ ciphertext inner product */
+long sealhip_evaluator_dot_product_max_terms(sealhip_context *ctx, uint32_t k, uint64_t *max_terms)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(max_terms);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        *max_terms = dot_product_max_terms(h, static_cast<int>(k));
+    });
+}
+
+long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms, const uint64_t *const *b_terms,
+                                   uint32_t n_terms, size_t count, const sealhip_kswitch_key *const *relin_keys,
+                                   uint32_t n_relin_keys, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    if (n_terms)
+    {
+        REQUIRE_PTR(a_terms);
+        REQUIRE_PTR(b_terms);
+        for (uint32_t i = 0; i < n_terms; i++)
+        {
+            REQUIRE_PTR(a_terms[i]);
+            REQUIRE_PTR(b_terms[i]);
+        }
+    }
+    if (relin_keys && n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("the inner product of BFV ciphertexts needs a STRICT context");
+        if (n_terms == 0 && count > 0)
+            throw std::invalid_argument("the term lists must not be empty");
+        if (n_terms > dot_product_max_terms(h, static_cast<int>(k)))
+            throw std::invalid_argument("too many terms for one floor at this level (sealhip_evaluator_dot_product_max_terms)");
+        if (relin_keys)
+        {
+            if (n_relin_keys == 0)
+                throw std::invalid_argument("not enough relinearization keys");
+            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+            if (relin_keys[0]->key.n_digits < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *o = reinterpret_cast<const u64 *>(out), *o_end = o + count * (relin_keys ? 2 : 3) * poly;
+        for (uint32_t i = 0; i < n_terms; i++)
+            for (const uint64_t *term : { a_terms[i], b_terms[i] })
+            {
+                const u64 *t = reinterpret_cast<const u64 *>(term);
+                if (o < t + count * 2 * poly && t < o_end)
+                    throw std::invalid_argument("out must not overlap an operand");
+            }
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        sink.begin();
+        op_dot_product(e, static_cast<int>(k), reinterpret_cast<const u64 *const *>(a_terms),
+                       reinterpret_cast<const u64 *const *>(b_terms), n_terms, count, relin_keys ? &relin_keys[0]->key : nullptr,
+                       reinterpret_cast<u64 *>(out));
+    });
+}
+
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
 
 long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

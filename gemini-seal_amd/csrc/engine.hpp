@@ -472,6 +472,21 @@ namespace sealhip
                                      std::size_t b_stride, u64 *out, std::size_t out_stride, std::size_t count,
                                      const RowMap &map, bool square = false);
     hipError_t launch_fill_rows(const Engine &e, u64 *dst, const u64 *row_values, int rows, std::size_t count);
+    // Sum of the (2,2) tensor products of a group of terms (poly.hip tensor_dot_kernel). Term t reads a[t] and b[t]: items
+    // a_stride / b_stride words apart, two polynomials of map.rows rows each. c_0, c_1 go to out01 (one polynomial apart), c_2
+    // to out2. reduce_on_load: the operands may be any 64-bit words (lazy forward transforms); otherwise they are canonical.
+    // add_partial: the canonical sums already at out01 / out2 are added in. The transparency sink, when armed, gets
+    // c_1 | c_2 of every item.
+    constexpr int kDotGroup = bounds::kDotGroupTerms;
+    struct DotTerms
+    {
+        const u64 *a[kDotGroup];
+        const u64 *b[kDotGroup];
+        int n;
+    };
+    hipError_t launch_tensor_dot(const Engine &e, const DotTerms &terms, std::size_t a_stride, std::size_t b_stride, u64 *out01,
+                                 std::size_t out01_stride, u64 *out2, std::size_t out2_stride, std::size_t count,
+                                 const RowMap &map, bool reduce_on_load, bool add_partial);
     hipError_t launch_copy_rows(const Engine &e, const u64 *src, std::size_t src_poly_stride, u64 *dst,
                                 std::size_t dst_poly_stride, std::size_t npolys, int rows);
 
@@ -700,6 +715,14 @@ namespace sealhip
     void op_modup(Engine &e, int k, int bundle, u64 *ext, std::size_t count);
     void op_bfv_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out);
     void op_ckks_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out);
+    // Ciphertext inner product: sum_i a[i] * b[i] over n_terms pairs of size-2 batches
+    // [count][2][k][N], the tensor products summed in NTT form -- for BFV (STRICT) in the extended base, so that the sum
+    // takes ONE inverse transform and ONE floor. key == nullptr: out[count][3][k][N]; else the sum is relinearized once and
+    // out is [count][2][k][N]. The operands are only read.
+    void op_dot_product(Engine &e, int k, const u64 *const *a, const u64 *const *b, std::size_t n_terms, std::size_t count,
+                        const KSwitchKey *key, u64 *out);
+    // terms a level admits (BFV: while the floor's Shenoy-Kumaresan conversion stays exact; CKKS: 2^32 - 1); host constants only
+    std::uint64_t dot_product_max_terms(Engine &e, int k);
     // Evaluator::square as its own path (evaluator.cpp:560-770): the operand is lifted / transformed once
     void op_bfv_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);
     void op_ckks_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);

@@ -294,7 +294,7 @@ namespace sealhip
             }
     }
 
-    static int product_bit_length(const std::vector<u64> &vals)
+    int product_bit_length(const std::vector<u64> &vals)
     {
         std::vector<u64> acc(1, 1);
         for (u64 v : vals)
@@ -325,6 +325,19 @@ namespace sealhip
         if (32 + t_bits + product_bit_length(q) >= 61 * static_cast<int>(q.size()) + 61)
             b++;
         return b;
+    }
+
+    std::uint64_t HostRnsTool::dot_max_terms() const
+    {
+        int t_bits = 0, logn = 0;
+        for (u64 x = t; x; x >>= 1)
+            t_bits++;
+        while ((std::size_t(1) << logn) < n)
+            logn++;
+        const int room = product_bit_length(Bsk) - (t_bits + logn + product_bit_length(q) + 4);
+        if (room <= 0)
+            return 1; // one term is bfv_multiply's own arithmetic
+        return room >= 64 ? ~std::uint64_t(0) : std::max<std::uint64_t>(1, (std::uint64_t(1) << room) - 1);
     }
 
     void HostRnsTool::build(std::size_t n_, const std::vector<u64> &q_, u64 t_, const std::vector<u64> &aux)

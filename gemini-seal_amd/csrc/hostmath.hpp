@@ -86,5 +86,9 @@ namespace sealhip
         // aux = get_primes(n, 60, count) with count >= |B| + 2
         void build(std::size_t n_, const std::vector<u64> &q_, u64 t_, const std::vector<u64> &aux);
         static std::size_t base_B_size(const std::vector<u64> &q, u64 t);
+        // terms a ciphertext inner product may sum before ONE floor at this level:
+        // room = bits(prod Bsk) - (bits(t) + log2 n + bits(prod q) + 4), max(1, 2^room - 1) saturating at 2^64 - 1
+        std::uint64_t dot_max_terms() const;
     };
+    int product_bit_length(const std::vector<u64> &vals); // bits of the product of the values
 } // namespace sealhip

@@ -491,5 +491,27 @@ namespace sealhip
         constexpr int kBehzExactMaxK = 15; // the largest k with an exact-k BEHZ instance (rns.hip)
         static_assert(dotacc31_all_ok(kBehzExactMaxK + 2),
                       "DotAcc31 on 61-bit operands: every term count of the exact-k instances (up to k + 2)");
+
+        // =====================================================================================================
+        // 8. The ciphertext inner product's plain 128-bit sums (poly.hip tensor_dot_kernel). One launch
+        // accumulates a group of `terms` tensor products with mac128 and reduces once per output word. The widest sum is
+        // c_1: two products per term, each below 2^(2 bits) for operands below 2^bits, plus the canonical partial sum of
+        // the groups before it (below 2^bits). It must stay below 2^128.
+        // The kernel's operands are canonical residues of primes below 2^61 (SEAL_MOD_BIT_COUNT_MAX): CKKS operands as the
+        // caller hands them over, BFV operands after the kernel's own reduction on load (any 64-bit word is accepted there).
+        constexpr bool dot_group_admits(int terms, int bits)
+        {
+            if (terms < 1 || bits < 1 || bits > 63)
+                return false;
+            // 2 terms 2^(2 bits) + 2^bits <= 2^128 - 1, in units that fit u128: divide by 2^bits
+            const int shift = 128 - bits; // (2 terms 2^bits + 1) 2^bits < 2^128  <=>  2 terms 2^bits + 1 <= 2^shift
+            if (shift <= bits)
+                return false;
+            return (static_cast<u128>(2 * terms) << bits) + 1 <= (static_cast<u128>(1) << shift);
+        }
+        constexpr int kDotGroupTerms = 16; // terms per launch of tensor_dot_kernel
+        static_assert(dot_group_admits(kDotGroupTerms, kDotAccOperandBits), "16 terms of 61-bit operands fit 128 bits");
+        static_assert(dot_group_admits(31, kDotAccOperandBits) && !dot_group_admits(32, kDotAccOperandBits),
+                      "this (conservative) count admits 31 terms at 61 bits: the group of 16 leaves almost a factor two");
     } // namespace bounds
 } // namespace sealhip

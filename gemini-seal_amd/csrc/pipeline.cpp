@@ -710,6 +710,185 @@ namespace sealhip
     }
 
     // ------------------------------------------------------------------------------------------
+    // Ciphertext inner product: sum_i a_i * b_i, one floor (BFV), one key switch
+    // ------------------------------------------------------------------------------------------
+    std::uint64_t dot_product_max_terms(Engine &e, int k)
+    {
+        if (e.scheme == 2)
+            return 0xFFFFFFFFull; // (modular sums of canonical residues: any number of terms)
+        return e.level_host(k).host_rns->dot_max_terms();
+    }
+
+    // The tensor products of all terms are summed in NTT form by tensor_dot_kernel, in groups of up to kDotGroup terms
+    // (later groups add the canonical partial sum in). CKKS reads the operands where they are. BFV (STRICT) lifts and
+    // transforms every term into the extended base q u Bsk with the launches of op_bfv_multiply's unfused path (steps 1-3),
+    // holds a group of terms in the arena, and sends the SUM through that path's tail once: one inverse transform of
+    // 3 (k + |Bsk|) rows and three floors, whatever the number of terms. With a key the sum's c_2 stays in the arena and the
+    // key switch adds its two polynomials into (c_0, c_1) in `out`.
+    void op_dot_product(Engine &e, int k, const u64 *const *a, const u64 *const *b, std::size_t n_terms, std::size_t count,
+                        const KSwitchKey *key, u64 *out)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("the inner product needs a ciphertext level");
+        const bool ckks = e.scheme == 2;
+        if (!ckks && !e.mode_strict)
+            // (as for the hoisted entries: the fork's BFV key switch does not decrypt, and there is no reference behaviour to
+            //  reproduce for an operation the fork does not have)
+            throw std::invalid_argument("the inner product of BFV ciphertexts needs a STRICT context");
+        if (n_terms == 0 || n_terms > dot_product_max_terms(e, k))
+            throw std::invalid_argument("number of terms out of range");
+        LevelTools &lt = e.level(k);
+        if (key && static_cast<int>(key->n_digits) < lt.h_ks.nd)
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const std::size_t N = e.n, poly_q = static_cast<std::size_t>(k) * N;
+        const std::size_t out_item = (key ? 2 : 3) * poly_q;
+        const std::size_t ks_bytes = key ? switch_key_item_bytes(e, k) : 0;
+        const std::size_t w_c2 = key ? poly_q : 0;
+        // BFV: X holds a group of terms (4 polynomials of k + |Bsk| rows each), D the sum (3 polynomials)
+        BfvMulPlan plan{};
+        int kb = k;
+        if (!ckks)
+        {
+            plan = plan_bfv_multiply(e, k, 2, 2, false);
+            if (plan.nB != lt.h_rns.nB || plan.redc_small != (lt.h_rns.redc_small != 0))
+                throw std::logic_error("op_dot_product: the plan and the level's device constants disagree");
+            plan.fused_tensor = plan.lift_top = false; // (the unfused path: the sum is formed between the transforms)
+            plan.deferred_top = plan.defer ? 1 : 0;
+            kb = k + plan.nB;
+        }
+        const std::size_t poly_x = static_cast<std::size_t>(kb) * N;
+        const std::size_t w_x = ckks ? 0 : 4 * poly_x, w_d = ckks ? 0 : 3 * poly_x;
+        // terms held at once: a full group unless the arena cannot take one item with it; D carries the canonical partial
+        // sum from one group to the next, so a pass over fewer terms is simply a smaller group
+        std::size_t group = std::min<std::size_t>(kDotGroup, n_terms);
+        if (!ckks)
+        {
+            const std::size_t budget = workspace_budget_bytes(e), fixed = (w_c2 + w_d) * sizeof(u64);
+            if (fixed + group * w_x * sizeof(u64) > budget)
+            {
+                const std::size_t fit = budget > fixed ? (budget - fixed) / (w_x * sizeof(u64)) : 0;
+                group = std::max<std::size_t>(1, std::min(fit, group));
+                log_chunk(e, n_terms, group); // (the term split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+            }
+        }
+        const std::size_t work_bytes = (group * w_x + w_d) * sizeof(u64);
+        // c_2 must survive op_switch_key, which re-plans the arena: it is carved first and the floor raised over it; the
+        // item's bytes cover the larger of this operation's temporaries and the key switch's, so the nested plan fits what
+        // is reserved here and the arena cannot move while c_2 is live
+        for_chunks(e, count, w_c2 * sizeof(u64) + std::max(work_bytes, ks_bytes), 6, [&](std::size_t off, std::size_t m) {
+            u64 *c2 = key ? e.ws_alloc(w_c2 * m) : nullptr;
+            struct FloorGuard
+            {
+                Lane &l;
+                std::size_t floor, base;
+                ~FloorGuard()
+                {
+                    l.ws_floor = floor;
+                    l.tsink_base = base;
+                }
+            } guard{ e.lane(), e.lane().ws_floor, e.lane().tsink_base };
+            u64 *o = out + off * out_item;
+            unsigned *const flags = sink_at(e, off);
+            if (ckks)
+            {
+                for (std::size_t g0 = 0; g0 < n_terms; g0 += group)
+                {
+                    DotTerms terms{};
+                    terms.n = static_cast<int>(std::min(group, n_terms - g0));
+                    for (int t = 0; t < terms.n; t++)
+                    {
+                        terms.a[t] = a[g0 + t] + off * 2 * poly_q;
+                        terms.b[t] = b[g0 + t] + off * 2 * poly_q;
+                    }
+                    // (the flags describe the result: only the last group's stores are the result's words)
+                    SinkArm arm(e, !key && g0 + group >= n_terms ? flags : nullptr);
+                    check(launch_tensor_dot(e, terms, 2 * poly_q, 2 * poly_q, o, out_item, key ? c2 : o + 2 * poly_q,
+                                            key ? poly_q : out_item, m, lt.map_q, false, g0 > 0),
+                          "tensor_dot");
+                }
+            }
+            else
+            {
+                const RnsDev &h = lt.h_rns;
+                u64 *X = e.ws_alloc(group * w_x * m);
+                u64 *D = e.ws_alloc(w_d * m);
+                for (std::size_t g0 = 0; g0 < n_terms; g0 += group)
+                {
+                    DotTerms terms{};
+                    terms.n = static_cast<int>(std::min(group, n_terms - g0));
+                    for (int t = 0; t < terms.n; t++)
+                    {
+                        // steps (1)-(3) of op_bfv_multiply's unfused path for term g0 + t
+                        u64 *Xt = X + static_cast<std::size_t>(t) * w_x * m;
+                        const u64 *pa = a[g0 + t] + off * 2 * poly_q, *pb = b[g0 + t] + off * 2 * poly_q;
+                        for (int s = 0; s < 4; s++)
+                        {
+                            const u64 *src = (s < 2 ? pa : pb) + (s & 1) * poly_q;
+                            u64 *dst = Xt + s * poly_x;
+                            if (!plan.gather)
+                                check(launch_copy_rows(e, src, 2 * poly_q, dst, w_x, m, k), "copy");
+                            check(launch_bfv_lift(e, lt.d_rns, h, src, 2 * poly_q, dst + poly_q, w_x, m, plan), "bfv_lift");
+                        }
+                        if (plan.gather)
+                        {
+                            RowMap mq{}, mb{};
+                            NttSource ns{};
+                            mq.rows = mb.rows = 4 * kb;
+                            ns.base[0] = pa;
+                            ns.base[1] = pb;
+                            ns.poly_stride[0] = ns.poly_stride[1] = 2 * poly_q;
+                            for (int s = 0; s < 4; s++)
+                                for (int r = 0; r < kb; r++)
+                                {
+                                    mq.prime[s * kb + r] = r < k ? lt.map_qbsk.prime[r] : kSkipRow;
+                                    mb.prime[s * kb + r] = r < k ? kSkipRow : lt.map_qbsk.prime[r];
+                                    ns.code[s * kb + r] =
+                                        r < k ? static_cast<unsigned short>((s < 2 ? 0 : kSrcSecond) | ((s & 1) * k + r)) : kSkipRow;
+                                }
+                            // (tensor_dot_kernel reduces what it loads: any representative will do, on both row sets)
+                            check(launch_ntt_gather(e, Xt, m * 4 * kb, mq, ns, kNttAnyRep | kNttApprox), "ntt(X, gathered q rows)");
+                            check(launch_ntt(e, Xt, m * 4 * kb, mb, false, 0), "ntt(X, Bsk rows)");
+                        }
+                        else
+                            check(launch_ntt(e, Xt, m * 4 * kb, lt.map_qbsk, false, kNttAnyRep), "ntt(X)");
+                        terms.a[t] = Xt;
+                        terms.b[t] = Xt + 2 * poly_x;
+                    }
+                    // step (4), summed over the group's terms; the operands are lazily transformed words
+                    check(launch_tensor_dot(e, terms, w_x, w_x, D, w_d, D + 2 * poly_x, w_d, m, lt.map_qbsk, true, g0 > 0),
+                          "tensor_dot");
+                }
+                // step (5), ONCE for the sum
+                if (plan.defer)
+                {
+                    RowMap mq = lt.map_qbsk, mb = lt.map_qbsk;
+                    for (int r = 0; r < kb; r++)
+                        (r < k ? mb : mq).prime[r] = kSkipRow;
+                    check(launch_ntt(e, D, m * 3 * kb, mq, true, kNttDeferTop | kNttAnyRep), "intt(D, q rows)");
+                    check(launch_ntt(e, D, m * 3 * kb, mb, true, kNttDeferTop | kNttAnyRep), "intt(D, Bsk rows)");
+                }
+                else
+                    check(launch_ntt(e, D, m * 3 * kb, lt.map_qbsk, true, kNttCanonical), "intt(D)");
+                // steps (6)-(8): three floors
+                for (int I = 0; I < 3; I++)
+                {
+                    SinkArm arm(e, !key && I >= 1 ? flags : nullptr);
+                    u64 *dst = key && I == 2 ? c2 : o + I * poly_q;
+                    check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, dst, key && I == 2 ? poly_q : out_item, m, plan),
+                          "floor_sk");
+                }
+            }
+            if (key)
+            {
+                // relinearize_internal (evaluator.cpp:811-815) of the sum: (c_0, c_1) += key switch of c_2
+                e.lane().ws_floor = guard.floor + pad256(w_c2 * m);
+                e.lane().tsink_base = guard.base + off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
+                op_switch_key(e, k, o, 2 * poly_q, c2, poly_q, m, *key);
+            }
+        });
+    }
+
+    // ------------------------------------------------------------------------------------------
     // mod_switch_scale_to_next (evaluator.cpp:829-892): BFV mod_switch_to_next / CKKS rescale_to_next
     // ------------------------------------------------------------------------------------------
     namespace

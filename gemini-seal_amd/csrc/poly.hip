@@ -133,6 +133,104 @@ namespace sealhip
             }
         }
 
+        // Ciphertext inner product: out = sum over the group's terms of the (2,2) tensor product
+        // a_t (x) b_t, one lane per coefficient pair of one row of one item, addressed as in tensor_product_kernel. The three
+        // sums c_0 = a_0 b_0, c_1 = a_1 b_0 + a_0 b_1, c_2 = a_1 b_1 are plain 128-bit integers (ntt_bounds.hpp section 8: at
+        // most kDotGroup terms of canonical operands cannot wrap) that are reduced ONCE per output word; the canonical residue
+        // is that of the composition of dyadic products and modular additions. The next term's loads are issued before the
+        // current term is accumulated. REDUCE: the operands are any 64-bit words (lazily transformed rows) and are brought to
+        // the canonical residue as they are loaded. add_partial: the canonical sums of the groups before this one are added in.
+        struct DotLoad
+        {
+            ulonglong2 a0, a1, b0, b1;
+        };
+        __device__ __forceinline__ DotLoad dot_load(const u64 *pa, const u64 *pb, std::size_t poly_words)
+        {
+            DotLoad v;
+            v.a0 = *reinterpret_cast<const ulonglong2 *>(pa);
+            v.a1 = *reinterpret_cast<const ulonglong2 *>(pa + poly_words);
+            v.b0 = *reinterpret_cast<const ulonglong2 *>(pb);
+            v.b1 = *reinterpret_cast<const ulonglong2 *>(pb + poly_words);
+            return v;
+        }
+        __device__ __forceinline__ u64 dot_canonical(u64 x, u64 p, u64 cr1)
+        {
+            const u64 r = barrett_lazy(x, cr1, p); // cr1 = floor(2^64 / p): [0, 2p) for every 64-bit x
+            return r >= p ? r - p : r;
+        }
+        __device__ __forceinline__ void dot_add_word(u64 &lo, u64 &hi, u64 w)
+        {
+            const u64 nl = lo + w;
+            hi += nl < lo;
+            lo = nl;
+        }
+        template <bool REDUCE>
+        __global__ __launch_bounds__(kThreads) void tensor_dot_kernel(DotTerms terms, std::size_t a_stride, std::size_t b_stride,
+                                                                      u64 *out01, std::size_t out01_stride,
+                                                                      u64 *out2, std::size_t out2_stride,
+                                                                      const PrimeDev *__restrict__ primes, RowMap map, int logn,
+                                                                      std::size_t npairs_per_item, std::size_t count,
+                                                                      unsigned *__restrict__ tflags, int add_partial)
+        {
+            const std::size_t total = npairs_per_item * count;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t poly_words = static_cast<std::size_t>(map.rows) << logn;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
+            {
+                const std::size_t item = i / npairs_per_item;
+                const std::size_t off = 2 * (i - item * npairs_per_item); // word offset inside one polynomial
+                const unsigned short pid = map.prime[off >> logn];
+                if (pid == kSkipRow)
+                    continue;
+                const u64 p = primes[pid].p, cr0 = primes[pid].cr0, cr1 = primes[pid].cr1;
+                const std::size_t ao = item * a_stride + off, bo = item * b_stride + off;
+                u64 lo[3][2] = {}, hi[3][2] = {};
+                DotLoad next = dot_load(terms.a[0] + ao, terms.b[0] + bo, poly_words);
+                for (int t = 0; t < terms.n; t++)
+                {
+                    DotLoad v = next;
+                    if (t + 1 < terms.n)
+                        next = dot_load(terms.a[t + 1] + ao, terms.b[t + 1] + bo, poly_words);
+                    if (REDUCE)
+                    {
+                        v.a0.x = dot_canonical(v.a0.x, p, cr1), v.a0.y = dot_canonical(v.a0.y, p, cr1);
+                        v.a1.x = dot_canonical(v.a1.x, p, cr1), v.a1.y = dot_canonical(v.a1.y, p, cr1);
+                        v.b0.x = dot_canonical(v.b0.x, p, cr1), v.b0.y = dot_canonical(v.b0.y, p, cr1);
+                        v.b1.x = dot_canonical(v.b1.x, p, cr1), v.b1.y = dot_canonical(v.b1.y, p, cr1);
+                    }
+                    mac128(lo[0][0], hi[0][0], v.a0.x, v.b0.x);
+                    mac128(lo[0][1], hi[0][1], v.a0.y, v.b0.y);
+                    mac128(lo[1][0], hi[1][0], v.a1.x, v.b0.x);
+                    mac128(lo[1][1], hi[1][1], v.a1.y, v.b0.y);
+                    mac128(lo[1][0], hi[1][0], v.a0.x, v.b1.x);
+                    mac128(lo[1][1], hi[1][1], v.a0.y, v.b1.y);
+                    mac128(lo[2][0], hi[2][0], v.a1.x, v.b1.x);
+                    mac128(lo[2][1], hi[2][1], v.a1.y, v.b1.y);
+                }
+                u64 *po0 = out01 + item * out01_stride + off, *po2 = out2 + item * out2_stride + off;
+                if (add_partial)
+                {
+                    const ulonglong2 q0 = *reinterpret_cast<const ulonglong2 *>(po0);
+                    const ulonglong2 q1 = *reinterpret_cast<const ulonglong2 *>(po0 + poly_words);
+                    const ulonglong2 q2 = *reinterpret_cast<const ulonglong2 *>(po2);
+                    dot_add_word(lo[0][0], hi[0][0], q0.x), dot_add_word(lo[0][1], hi[0][1], q0.y);
+                    dot_add_word(lo[1][0], hi[1][0], q1.x), dot_add_word(lo[1][1], hi[1][1], q1.y);
+                    dot_add_word(lo[2][0], hi[2][0], q2.x), dot_add_word(lo[2][1], hi[2][1], q2.y);
+                }
+                ulonglong2 c0, c1, c2;
+                c0.x = barrett_reduce_128(lo[0][0], hi[0][0], p, cr0, cr1);
+                c0.y = barrett_reduce_128(lo[0][1], hi[0][1], p, cr0, cr1);
+                c1.x = barrett_reduce_128(lo[1][0], hi[1][0], p, cr0, cr1);
+                c1.y = barrett_reduce_128(lo[1][1], hi[1][1], p, cr0, cr1);
+                c2.x = barrett_reduce_128(lo[2][0], hi[2][0], p, cr0, cr1);
+                c2.y = barrett_reduce_128(lo[2][1], hi[2][1], p, cr0, cr1);
+                *reinterpret_cast<ulonglong2 *>(po0) = c0;
+                *reinterpret_cast<ulonglong2 *>(po0 + poly_words) = c1;
+                *reinterpret_cast<ulonglong2 *>(po2) = c2;
+                note_nonzero(tflags, item, c1.x | c1.y | c2.x | c2.y);
+            }
+        }
+
         __global__ __launch_bounds__(kThreads) void copy_rows_kernel(const u64 *__restrict__ src,
                                                                      std::size_t src_stride, u64 *__restrict__ dst,
                                                                      std::size_t dst_stride,
@@ -419,6 +517,29 @@ namespace sealhip
         tensor_product_kernel<<<grid_for(pairs * count), kThreads, 0, e.lane().stream>>>(
             a, sa, a_stride, b, sb, b_stride, out, out_stride, e.d_primes, map, e.logn, pairs, count, e.lane().tsink_arm,
             square ? 1 : 0);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_tensor_dot(const Engine &e, const DotTerms &terms, std::size_t a_stride, std::size_t b_stride, u64 *out01,
+                                 std::size_t out01_stride, u64 *out2, std::size_t out2_stride, std::size_t count,
+                                 const RowMap &map, bool reduce_on_load, bool add_partial)
+    {
+        static_assert(bounds::dot_group_admits(kDotGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
+        if (terms.n < 1 || terms.n > kDotGroup || map.rows < 1 || map.rows > kMaxRows)
+            return hipErrorInvalidValue;
+        const std::size_t pairs = (static_cast<std::size_t>(map.rows) << e.logn) / 2;
+        if (pairs * count == 0)
+            return hipSuccess;
+        ProfScope prof(e, "tensor_dot", 0);
+        const unsigned grid = grid_for(pairs * count);
+        if (reduce_on_load)
+            tensor_dot_kernel<true><<<grid, kThreads, 0, e.lane().stream>>>(terms, a_stride, b_stride, out01, out01_stride, out2,
+                                                                            out2_stride, e.d_primes, map, e.logn, pairs, count,
+                                                                            e.lane().tsink_arm, add_partial ? 1 : 0);
+        else
+            tensor_dot_kernel<false><<<grid, kThreads, 0, e.lane().stream>>>(terms, a_stride, b_stride, out01, out01_stride, out2,
+                                                                             out2_stride, e.d_primes, map, e.logn, pairs, count,
+                                                                             e.lane().tsink_arm, add_partial ? 1 : 0);
         return hipGetLastError();
     }
 

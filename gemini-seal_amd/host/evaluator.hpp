@@ -1122,6 +1122,25 @@ namespace sealhip_host
             exponentiate_inplace(destination, exponent, relin_keys);
         }
 
+        // Ciphertext inner product (sealhip_evaluator_dot_product): destination = sum_i
+        // encrypteds1[i] * encrypteds2[i] over size-2 ciphertexts, the tensor products summed in NTT form, ONE floor (BFV,
+        // STRICT contexts only) and, in the overload with a relinearization key, ONE relinearization (size 2; size 3
+        // without). Every term is checked like multiply's operands and against the first: same level, and for CKKS one
+        // scale on each side (the products must be addable); the result has the terms' level and form and, for CKKS, the
+        // scale encrypteds1[0].scale() * encrypteds2[0].scale(). An object may appear in several terms and on both sides.
+        // The reference has no such method; for BFV the words are those of the ABI entry, not of the composition.
+        template <class C, IfCt<C> = 0>
+        void dot_product(const std::vector<C> &encrypteds1, const std::vector<C> &encrypteds2, C &destination)
+        {
+            dot_product_internal(encrypteds1, encrypteds2, nullptr, destination);
+        }
+        template <class C, IfCt<C> = 0>
+        void dot_product(const std::vector<C> &encrypteds1, const std::vector<C> &encrypteds2, const KSwitchKeys &relin_key,
+                         C &destination)
+        {
+            dot_product_internal(encrypteds1, encrypteds2, &relin_key, destination);
+        }
+
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
         template <class C, IfCt<C> = 0>
         void multiply_many(const std::vector<C> &encrypteds, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
@@ -1636,6 +1655,45 @@ namespace sealhip_host
                 throw std::invalid_argument("CKKS encrypted must be in NTT form");
             if (encrypted.size() != 2)
                 throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
+        }
+
+        template <class C>
+        void dot_product_internal(const std::vector<C> &a, const std::vector<C> &b, const KSwitchKeys *relin_key, C &destination)
+        {
+            if (a.empty() || a.size() != b.size())
+                throw std::invalid_argument("encrypteds1 and encrypteds2 must hold the same, non-zero number of terms");
+            for (std::size_t i = 0; i < a.size(); i++)
+            {
+                check_multiply(a[i], b[i]);
+                if (a[i].size() != 2 || b[i].size() != 2)
+                    throw std::invalid_argument("encrypted size must be 2");
+                if (a[i].coeff_modulus_size() != a[0].coeff_modulus_size())
+                    throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+                if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && (a[i].scale() != a[0].scale() || b[i].scale() != b[0].scale()))
+                    throw std::invalid_argument("scale mismatch");
+            }
+            const std::size_t k = a[0].coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, size = relin_key ? 2 : 3;
+            const double scale = a[0].scale() * b[0].scale();
+            std::vector<Dev> staged;
+            std::vector<const std::uint64_t *> pa, pb;
+            staged.reserve(2 * a.size());
+            for (std::size_t i = 0; i < a.size(); i++)
+            {
+                staged.push_back(dev_in(a[i], words));
+                pa.push_back(staged.back().ptr());
+                staged.push_back(dev_in(b[i], words));
+                pb.push_back(staged.back().ptr());
+            }
+            Dev o = dev_out(size * k * n);
+            const sealhip_kswitch_key *raw = relin_key ? relin_key->get() : nullptr;
+            Check chk = checked(a[0]);
+            throw_on(sealhip_evaluator_dot_product(ctx_.get(), std::uint32_t(k), pa.data(), pb.data(), std::uint32_t(a.size()), 1,
+                                                   relin_key ? &raw : nullptr, relin_key ? 1u : 0u, o.ptr()));
+            chk.done();
+            take_meta(destination, a[0]); // (every term is staged or enqueued by now: the destination may be one of them)
+            commit(destination, o, size, k);
+            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
+                destination.scale() = scale;
         }
 
         // the host checks of multiply / square (evaluator.cpp:238-249, :276-279, :449-452)

@@ -139,6 +139,8 @@ SYMBOLS = {
                                                   C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_rotate_vector_bsgs_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_i32), _u32,
                                                    C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
+    "sealhip_evaluator_dot_product_max_terms": [_vp, _u32, C.POINTER(C.c_uint64)],
+    "sealhip_evaluator_dot_product": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -985,6 +987,28 @@ class Evaluator:
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
         _check(lib().sealhip_evaluator_rotate_vector_bsgs_plain(self.ctx.handle, k, _ptr(ct), count, bs, len(baby_steps), gs,
                                                                 len(giant_steps), ea, ka, len(elts), _ptr(plains), _ptr(out)))
+
+    def dot_product_max_terms(self, k):
+        """Terms one dot_product call admits at level k (sealhip_evaluator_dot_product_max_terms): for BFV as many as keep the
+        single floor's base conversion exact, for CKKS 2^32 - 1"""
+        n = C.c_uint64(0)
+        _check(lib().sealhip_evaluator_dot_product_max_terms(self.ctx.handle, k, C.byref(n)))
+        return int(n.value)
+
+    def dot_product(self, a_terms, b_terms, k, count, out, relin_keys=None):
+        """Ciphertext inner product (sealhip_evaluator_dot_product): out = sum_i a_terms[i] * b_terms[i]
+        over device batches count x 2 x k x N of size-2 ciphertexts, the tensor products summed in NTT form, one floor (BFV
+        STRICT) and, with relin_keys (a list of KSwitchKeys, index 0 is read), one relinearization. out: count x 3 x k x N
+        without keys, count x 2 x k x N with them. The operands are not modified; buffers may repeat."""
+        if len(a_terms) != len(b_terms):
+            raise ValueError("a_terms and b_terms differ in length")
+        pa = (_vp * max(1, len(a_terms)))(*[_ptr(c) for c in a_terms])
+        pb = (_vp * max(1, len(b_terms)))(*[_ptr(c) for c in b_terms])
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        _check(lib().sealhip_evaluator_dot_product(self.ctx.handle, k, pa, pb, len(a_terms), count, keys,
+                                                   len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

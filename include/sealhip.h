@@ -533,6 +533,33 @@ long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k
                                                 const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
                                                 const uint64_t *plain_ntt, uint64_t *out);
 
+/* Ciphertext inner product: out = sum_{i < n_terms} a_terms[i] * b_terms[i], the tensor products
+   summed in NTT form by one streaming kernel, ONE floor for the whole sum (BFV) and, with relin_keys, ONE relinearization.
+   a_terms / b_terms: host arrays of device pointers, as sealhip_evaluator_multiply_many takes them; each points at a batch
+   count x 2 x k x N of size-2 ciphertexts at level k (BFV in coefficient form, CKKS in NTT form). Pointers may repeat, and
+   a_terms[i] == b_terms[i] gives a sum of squares. The operands are never modified; operand words at or above their prime
+   give unspecified words. relin_keys == NULL: out is count x 3 x k x N, the size-3 sum. Otherwise the sum is relinearized
+   once (keys as for sealhip_evaluator_relinearize; only index 0 is read) and out is count x 2 x k x N, compact. out must
+   overlap no operand.
+   CKKS, both modes: the sum of canonical residues -- word for word ckks_multiply per term, add over the products left to
+   right, then relinearize. BFV, STRICT mode only (PARITY is E_INVALIDARG, as for the hoisted entries): steps 1-3 of
+   bfv_multiply (evaluator.cpp:335-353) per term, the tensor products summed canonically over the rows of q and Bsk, then
+   bfv_multiply's tail (:423-444) ONCE. These are not the words of the composition (its floors round per term); what defines
+   them is the restatement over the oracle in tests/dot_ct_ref.py. With n_terms == 1 they are sealhip_evaluator_multiply's.
+   The floor's base conversion stays exact for at most sealhip_evaluator_dot_product_max_terms terms:
+       room = bits(prod Bsk) - (bits(t) + log2 N + bits(q_1 ... q_k) + 4),  max_terms = max(1, 2^room - 1)
+   saturating at 2^64 - 1; CKKS reports 2^32 - 1.
+   Checks: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, BFV in PARITY mode,
+   n_terms == 0 with count > 0, n_terms above max_terms, relin_keys given with n_relin_keys == 0 or a key with fewer digits
+   than the level, out overlapping an operand -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only
+   context -> COR_E_INVALIDOPERATION. Runs on the calling thread's lane and synchronises nothing; the term pointers travel
+   in kernel arguments, so the call is capturable after one warm-up call. With a transparency sink: one flag per output
+   ciphertext, written by the kernel that stores polynomials 1.. anyway. */
+long sealhip_evaluator_dot_product_max_terms(sealhip_context *ctx, uint32_t k, uint64_t *max_terms);
+long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms,
+                                   const uint64_t *const *b_terms, uint32_t n_terms, size_t count,
+                                   const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out);
+
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
    of the ciphertext (is_ntt_form). sk_powers_ntt = the Decryptor's secret_key_array_: (size-1) polynomials s, s^2, ...
