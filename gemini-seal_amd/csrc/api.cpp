@@ -1865,6 +1865,59 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
     });
 }
 
+/* ------------------------------------------------------------------ mod-down merged with the rescale */
+namespace
+{
+    // the first checks of every *_rescale entry, ahead of the unmerged entry's own: CKKS only, 2 <= k <= first level
+    void check_rescale_level(const Engine &h, uint32_t k)
+    {
+        if (h.scheme != 2)
+            throw std::invalid_argument("the merged rescale is CKKS only");
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached"); // evaluator.cpp:1005-1008
+    }
+} // namespace
+
+long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
+                                           size_t ct_item_stride, size_t count, const sealhip_kswitch_key *const *relin_keys,
+                                           uint32_t n_relin_keys, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    REQUIRE_PTR(relin_keys);
+    if (n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        check_rescale_level(h, k);
+        if (size != 3)
+            throw std::invalid_argument("encrypted must have size 3");
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        if (ct_item_stride < 3 * poly)
+            throw std::invalid_argument("item stride smaller than one ciphertext");
+        if (n_relin_keys == 0)
+            throw std::invalid_argument("not enough relinearization keys"); // evaluator.cpp:793-796
+        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+        if (relin_keys[0]->key.n_digits < nd)
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (count && o < in + (count - 1) * ct_item_stride + 3 * poly && in < o + count * 2 * (poly - h.n))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        sink.begin();
+        op_switch_key_rescale(e, static_cast<int>(k), in, ct_item_stride, in + 2 * poly, ct_item_stride, count, relin_keys[0]->key,
+                              o);
+    });
+}
+
 /* ------------------------------------------------------------------ weighted sums of rotations */
 namespace
 {
@@ -1872,9 +1925,11 @@ namespace
     // host-only contexts too (the order the header documents).
     void do_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
                                    const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys,
-                                   const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+                                   const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out, bool rescale = false)
     {
         Engine &h = *ctx->engine;
+        if (rescale)
+            check_rescale_level(h, k);
         if (k < 1 || static_cast<int>(k) > h.k_first)
             throw std::invalid_argument("level k out of range");
         const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
@@ -1889,24 +1944,94 @@ namespace
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
         if (count && (elts.empty() || !n_sums))
             throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        const std::size_t item = 2 * static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        const auto check_overlap = [&] {
+            const std::size_t out_words = n_sums * count * (rescale ? item - 2 * h.n : item),
+                              w_words = n_sums * elts.size() * h.key_moduli.size() * h.n;
+            if (o < in + count * item && in < o + out_words)
+                throw std::invalid_argument("out must not overlap ct");
+            if (o < w + w_words && w < o + out_words)
+                throw std::invalid_argument("out must not overlap plain_ntt");
+        };
+        if (rescale)
+            check_overlap(); // (the merged entries report it on host-only contexts too)
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
-        const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
-        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
-        u64 *o = reinterpret_cast<u64 *>(out);
-        const std::size_t out_words = n_sums * count * item, w_words = n_sums * elts.size() * e.key_moduli.size() * e.n;
-        if (o < in + count * item && in < o + out_words)
-            throw std::invalid_argument("out must not overlap ct");
-        if (o < w + w_words && w < o + out_words)
-            throw std::invalid_argument("out must not overlap plain_ntt");
+        if (!rescale)
+            check_overlap();
         SinkScope sink(e, static_cast<size_t>(n_sums) * count);
         sink.begin();
         std::vector<const KSwitchKey *> run_keys(elts.size(), nullptr);
         for (size_t i = 0; i < elts.size(); i++)
             if (elts[i] != 1)
                 run_keys[i] = &keys[i]->key;
-        op_apply_galois_dot_plain(e, static_cast<int>(k), in, count, elts.data(), run_keys.data(), elts.size(), w, n_sums, o);
+        op_apply_galois_dot_plain(e, static_cast<int>(k), in, count, elts.data(), run_keys.data(), elts.size(), w, n_sums, o,
+                                  rescale);
+    }
+
+    long apply_galois_dot_plain_entry(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                      const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys, uint32_t n_elts,
+                                      const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out, bool rescale)
+    {
+        REQUIRE_PTR(ctx);
+        REQUIRE_PTR(ct);
+        REQUIRE_PTR(plain_ntt);
+        REQUIRE_PTR(out);
+        if (n_elts)
+        {
+            REQUIRE_PTR(galois_elts);
+            REQUIRE_PTR(galois_keys);
+            for (uint32_t i = 0; i < n_elts; i++)
+                if (galois_elts[i] != 1)
+                    REQUIRE_PTR(galois_keys[i]);
+        }
+        return guarded([&] {
+            do_apply_galois_dot_plain(ctx, k, ct, count, std::vector<uint32_t>(galois_elts, galois_elts + n_elts),
+                                      std::vector<const sealhip_kswitch_key *>(galois_keys, galois_keys + n_elts), plain_ntt,
+                                      n_sums, out, rescale);
+        });
+    }
+
+    long rotate_vector_dot_plain_entry(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, const int32_t *steps,
+                                       uint32_t n_steps, const uint32_t *galois_elts,
+                                       const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, const uint64_t *plain_ntt,
+                                       uint32_t n_sums, uint64_t *out, bool rescale)
+    {
+        REQUIRE_PTR(ctx);
+        REQUIRE_PTR(ct);
+        REQUIRE_PTR(plain_ntt);
+        REQUIRE_PTR(out);
+        if (n_steps)
+            REQUIRE_PTR(steps);
+        if (n_keys)
+        {
+            REQUIRE_PTR(galois_elts);
+            REQUIRE_PTR(galois_keys);
+        }
+        return guarded([&] {
+            Engine &h = *ctx->engine;
+            if (rescale)
+                check_rescale_level(h, k);
+            if (k < 1 || static_cast<int>(k) > h.k_first)
+                throw std::invalid_argument("level k out of range");
+            std::vector<uint32_t> elts(n_steps, 1);
+            std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
+            for (uint32_t s = 0; s < n_steps; s++)
+            {
+                if (steps[s] == 0)
+                    continue; // (element 1)
+                elts[s] = host_galois_elt_from_step(h.n, steps[s]);
+                for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
+                    if (galois_elts[i] == elts[s])
+                        keys[s] = galois_keys[i];
+                if (!keys[s])
+                    throw std::invalid_argument("Galois key not present");
+            }
+            do_apply_galois_dot_plain(ctx, k, ct, count, elts, keys, plain_ntt, n_sums, out, rescale);
+        });
     }
 } // namespace
 
@@ -1914,23 +2039,14 @@ long sealhip_evaluator_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, 
                                               const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
                                               uint32_t n_elts, const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
 {
-    REQUIRE_PTR(ctx);
-    REQUIRE_PTR(ct);
-    REQUIRE_PTR(plain_ntt);
-    REQUIRE_PTR(out);
-    if (n_elts)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-        for (uint32_t i = 0; i < n_elts; i++)
-            if (galois_elts[i] != 1)
-                REQUIRE_PTR(galois_keys[i]);
-    }
-    return guarded([&] {
-        do_apply_galois_dot_plain(ctx, k, ct, count, std::vector<uint32_t>(galois_elts, galois_elts + n_elts),
-                                  std::vector<const sealhip_kswitch_key *>(galois_keys, galois_keys + n_elts), plain_ntt,
-                                  n_sums, out);
-    });
+    return apply_galois_dot_plain_entry(ctx, k, ct, count, galois_elts, galois_keys, n_elts, plain_ntt, n_sums, out, false);
+}
+
+long sealhip_evaluator_apply_galois_dot_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                      const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                                      uint32_t n_elts, const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+{
+    return apply_galois_dot_plain_entry(ctx, k, ct, count, galois_elts, galois_keys, n_elts, plain_ntt, n_sums, out, true);
 }
 
 long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
@@ -1938,36 +2054,17 @@ long sealhip_evaluator_rotate_vector_dot_plain(sealhip_context *ctx, uint32_t k,
                                                const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
                                                const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
 {
-    REQUIRE_PTR(ctx);
-    REQUIRE_PTR(ct);
-    REQUIRE_PTR(plain_ntt);
-    REQUIRE_PTR(out);
-    if (n_steps)
-        REQUIRE_PTR(steps);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-    }
-    return guarded([&] {
-        Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        std::vector<uint32_t> elts(n_steps, 1);
-        std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
-        for (uint32_t s = 0; s < n_steps; s++)
-        {
-            if (steps[s] == 0)
-                continue; // (element 1)
-            elts[s] = host_galois_elt_from_step(h.n, steps[s]);
-            for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
-                if (galois_elts[i] == elts[s])
-                    keys[s] = galois_keys[i];
-            if (!keys[s])
-                throw std::invalid_argument("Galois key not present");
-        }
-        do_apply_galois_dot_plain(ctx, k, ct, count, elts, keys, plain_ntt, n_sums, out);
-    });
+    return rotate_vector_dot_plain_entry(ctx, k, ct, count, steps, n_steps, galois_elts, galois_keys, n_keys, plain_ntt, n_sums,
+                                         out, false);
+}
+
+long sealhip_evaluator_rotate_vector_dot_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                       const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                                       const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                       const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out)
+{
+    return rotate_vector_dot_plain_entry(ctx, k, ct, count, steps, n_steps, galois_elts, galois_keys, n_keys, plain_ntt, n_sums,
+                                         out, true);
 }
 
 /* ------------------------------------------------------------------ BSGS matrix-vector product */
@@ -1977,9 +2074,11 @@ namespace
     void do_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
                                     const std::vector<uint32_t> &baby, const std::vector<const sealhip_kswitch_key *> &bkeys,
                                     const std::vector<uint32_t> &giant, const std::vector<const sealhip_kswitch_key *> &gkeys,
-                                    const uint64_t *plain_ntt, uint64_t *out)
+                                    const uint64_t *plain_ntt, uint64_t *out, bool rescale = false)
     {
         Engine &h = *ctx->engine;
+        if (rescale)
+            check_rescale_level(h, k);
         if (k < 1 || static_cast<int>(k) > h.k_first)
             throw std::invalid_argument("level k out of range");
         const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
@@ -1998,17 +2097,24 @@ namespace
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
         if (count && (baby.empty() || giant.empty()))
             throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
+        const std::size_t item = 2 * static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        const auto check_overlap = [&] {
+            const std::size_t out_words = count * (rescale ? item - 2 * h.n : item),
+                              w_words = giant.size() * baby.size() * h.key_moduli.size() * h.n;
+            if (o < in + count * item && in < o + out_words)
+                throw std::invalid_argument("out must not overlap ct");
+            if (o < w + w_words && w < o + out_words)
+                throw std::invalid_argument("out must not overlap plain_ntt");
+        };
+        if (rescale)
+            check_overlap(); // (the merged entries report it on host-only contexts too)
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
-        const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
-        const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
-        u64 *o = reinterpret_cast<u64 *>(out);
-        const std::size_t out_words = count * item, w_words = giant.size() * baby.size() * e.key_moduli.size() * e.n;
-        if (o < in + count * item && in < o + out_words)
-            throw std::invalid_argument("out must not overlap ct");
-        if (o < w + w_words && w < o + out_words)
-            throw std::invalid_argument("out must not overlap plain_ntt");
+        if (!rescale)
+            check_overlap();
         SinkScope sink(e, count);
         sink.begin();
         const auto run_keys = [](const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys) {
@@ -2020,11 +2126,10 @@ namespace
         };
         const std::vector<const KSwitchKey *> bk = run_keys(baby, bkeys), gk = run_keys(giant, gkeys);
         op_apply_galois_bsgs_plain(e, static_cast<int>(k), in, count, baby.data(), bk.data(), baby.size(), giant.data(), gk.data(),
-                                   giant.size(), w, o);
+                                   giant.size(), w, o, rescale);
     }
-} // namespace
 
-long sealhip_evaluator_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+long apply_galois_bsgs_plain_entry(sealhip_context *ctx, bool rescale, uint32_t k, const uint64_t *ct, size_t count,
                                                const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
                                                uint32_t n_baby, const uint32_t *giant_elts,
                                                const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
@@ -2054,11 +2159,12 @@ long sealhip_evaluator_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k,
         do_apply_galois_bsgs_plain(ctx, k, ct, count, std::vector<uint32_t>(baby_elts, baby_elts + n_baby),
                                    std::vector<const sealhip_kswitch_key *>(baby_keys, baby_keys + n_baby),
                                    std::vector<uint32_t>(giant_elts, giant_elts + n_giant),
-                                   std::vector<const sealhip_kswitch_key *>(giant_keys, giant_keys + n_giant), plain_ntt, out);
+                                   std::vector<const sealhip_kswitch_key *>(giant_keys, giant_keys + n_giant), plain_ntt, out,
+                                   rescale);
     });
 }
 
-long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+long rotate_vector_bsgs_plain_entry(sealhip_context *ctx, bool rescale, uint32_t k, const uint64_t *ct, size_t count,
                                                 const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
                                                 uint32_t n_giant, const uint32_t *galois_elts,
                                                 const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
@@ -2079,6 +2185,8 @@ long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k
     }
     return guarded([&] {
         Engine &h = *ctx->engine;
+        if (rescale)
+            check_rescale_level(h, k);
         if (k < 1 || static_cast<int>(k) > h.k_first)
             throw std::invalid_argument("level k out of range");
         const auto axis = [&](const int32_t *steps, uint32_t n, std::vector<uint32_t> &elts,
@@ -2101,8 +2209,49 @@ long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k
         std::vector<const sealhip_kswitch_key *> bkeys, gkeys;
         axis(baby_steps, n_baby, baby, bkeys);
         axis(giant_steps, n_giant, giant, gkeys);
-        do_apply_galois_bsgs_plain(ctx, k, ct, count, baby, bkeys, giant, gkeys, plain_ntt, out);
+        do_apply_galois_bsgs_plain(ctx, k, ct, count, baby, bkeys, giant, gkeys, plain_ntt, out, rescale);
     });
+}
+} // namespace
+
+long sealhip_evaluator_apply_galois_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                               const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
+                                               uint32_t n_baby, const uint32_t *giant_elts,
+                                               const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
+                                               const uint64_t *plain_ntt, uint64_t *out)
+{
+    return apply_galois_bsgs_plain_entry(ctx, false, k, ct, count, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant,
+                                         plain_ntt, out);
+}
+
+long sealhip_evaluator_apply_galois_bsgs_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                       const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
+                                                       uint32_t n_baby, const uint32_t *giant_elts,
+                                                       const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
+                                                       const uint64_t *plain_ntt, uint64_t *out)
+{
+    return apply_galois_bsgs_plain_entry(ctx, true, k, ct, count, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant,
+                                         plain_ntt, out);
+}
+
+long sealhip_evaluator_rotate_vector_bsgs_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
+                                                uint32_t n_giant, const uint32_t *galois_elts,
+                                                const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                const uint64_t *plain_ntt, uint64_t *out)
+{
+    return rotate_vector_bsgs_plain_entry(ctx, false, k, ct, count, baby_steps, n_baby, giant_steps, n_giant, galois_elts,
+                                          galois_keys, n_keys, plain_ntt, out);
+}
+
+long sealhip_evaluator_rotate_vector_bsgs_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                        const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
+                                                        uint32_t n_giant, const uint32_t *galois_elts,
+                                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                        const uint64_t *plain_ntt, uint64_t *out)
+{
+    return rotate_vector_bsgs_plain_entry(ctx, true, k, ct, count, baby_steps, n_baby, giant_steps, n_giant, galois_elts,
+                                          galois_keys, n_keys, plain_ntt, out);
 }
 
 /* ------------------------------------------------------------------ ciphertext inner product */
@@ -2118,12 +2267,16 @@ long sealhip_evaluator_dot_product_max_terms(sealhip_context *ctx, uint32_t k, u
     });
 }
 
-long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms, const uint64_t *const *b_terms,
-                                   uint32_t n_terms, size_t count, const sealhip_kswitch_key *const *relin_keys,
-                                   uint32_t n_relin_keys, uint64_t *out)
+namespace
+{
+long dot_product_entry(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms, const uint64_t *const *b_terms,
+                       uint32_t n_terms, size_t count, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                       uint64_t *out, bool rescale)
 {
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(out);
+    if (rescale)
+        REQUIRE_PTR(relin_keys); // (the merged finish is the key switch's: there is no size-3 form)
     if (n_terms)
     {
         REQUIRE_PTR(a_terms);
@@ -2139,6 +2292,8 @@ long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint6
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
+        if (rescale)
+            check_rescale_level(h, k);
         if (k < 1 || static_cast<int>(k) > h.k_first)
             throw std::invalid_argument("level k out of range");
         if (h.scheme == 1 && !h.mode_strict)
@@ -2156,7 +2311,8 @@ long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint6
                 throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         }
         const std::size_t poly = static_cast<std::size_t>(k) * h.n;
-        const u64 *o = reinterpret_cast<const u64 *>(out), *o_end = o + count * (relin_keys ? 2 : 3) * poly;
+        const u64 *o = reinterpret_cast<const u64 *>(out),
+                  *o_end = o + count * (rescale ? 2 * (poly - h.n) : (relin_keys ? 2 : 3) * poly);
         for (uint32_t i = 0; i < n_terms; i++)
             for (const uint64_t *term : { a_terms[i], b_terms[i] })
             {
@@ -2171,8 +2327,23 @@ long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint6
         sink.begin();
         op_dot_product(e, static_cast<int>(k), reinterpret_cast<const u64 *const *>(a_terms),
                        reinterpret_cast<const u64 *const *>(b_terms), n_terms, count, relin_keys ? &relin_keys[0]->key : nullptr,
-                       reinterpret_cast<u64 *>(out));
+                       reinterpret_cast<u64 *>(out), rescale);
     });
+}
+} // namespace
+
+long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms, const uint64_t *const *b_terms,
+                                   uint32_t n_terms, size_t count, const sealhip_kswitch_key *const *relin_keys,
+                                   uint32_t n_relin_keys, uint64_t *out)
+{
+    return dot_product_entry(ctx, k, a_terms, b_terms, n_terms, count, relin_keys, n_relin_keys, out, false);
+}
+
+long sealhip_evaluator_dot_product_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms,
+                                           const uint64_t *const *b_terms, uint32_t n_terms, size_t count,
+                                           const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out)
+{
+    return dot_product_entry(ctx, k, a_terms, b_terms, n_terms, count, relin_keys, n_relin_keys, out, true);
 }
 
 /* ------------------------------------------------------------------ decrypt-side arithmetic */

@@ -748,6 +748,75 @@ namespace sealhip
         return lt;
     }
 
+    // The constants of the mod-down merged with the rescale, built at the first *_rescale call of a
+    // level and not with the level: a program that never calls one allocates what it allocated before.
+    LevelTools &Engine::level_rescale(int k)
+    {
+        LevelTools &lt = level(k);
+        if (scheme != 2 || k < 2 || k > k_first)
+            throw std::invalid_argument("the merged rescale needs a CKKS ciphertext level of at least two primes");
+        std::lock_guard<std::mutex> lock(mu);
+        if (lt.d_ksr)
+            return lt;
+        if (lane().capturing) // the uploads below are synchronous copies: they would invalidate a relaxed capture
+            throw std::logic_error("the constants of this level are not built yet: run the sequence once before capturing");
+        SEALHIP_CHECK(hipSetDevice(device));
+        KsRescaleDev rs{};
+        rs.k = k;
+        rs.nsp = nsp;
+        const int nd1 = nsp + 1;
+        if (!bounds::ks_rescale_sum_fits(nd1, bounds::kDotAccOperandBits))
+            throw std::logic_error("merged rescale: the conversion sum does not fit 128 bits");
+        std::vector<u64> dp(nd1);
+        dp[0] = key_moduli[k - 1];
+        rs.drop_prime[0] = static_cast<unsigned>(k - 1);
+        for (int j = 0; j < nsp; j++)
+        {
+            dp[1 + j] = key_moduli[k_first + j];
+            rs.drop_prime[1 + j] = static_cast<unsigned>(k_first + j);
+        }
+        // prod of the dropped primes except `skip` (none: -1), modulo m
+        const auto prod_mod = [&](int skip, u64 m) {
+            u64 v = 1 % m;
+            for (int b = 0; b < nd1; b++)
+                if (b != skip)
+                    v = mulmod(v, dp[b] % m, m);
+            return v;
+        };
+        // half = (D - 1) / 2 modulo an odd m
+        const auto half_mod = [&](u64 m) { return mulmod((prod_mod(-1, m) + m - 1) % m, (m + 1) / 2, m); };
+        for (int a = 0; a < nd1; a++)
+        {
+            u64 inv;
+            if (!invmod(prod_mod(a, dp[a]), dp[a], inv))
+                throw std::logic_error("merged rescale: inverse does not exist");
+            rs.inv_hat[a] = inv;
+            rs.inv_hat_shoup[a] = shoup(inv, dp[a]);
+            rs.half_d[a] = half_mod(dp[a]);
+        }
+        std::vector<u64> hat(static_cast<std::size_t>(k - 1) * nd1, 0);
+        for (int r = 0; r < k - 1; r++)
+        {
+            const u64 qr = key_moduli[r];
+            for (int a = 0; a < nd1; a++)
+                hat[static_cast<std::size_t>(r) * nd1 + a] = prod_mod(a, qr);
+            const u64 Dq = prod_mod(-1, qr), hq = half_mod(qr);
+            rs.neg_D[r] = Dq ? qr - Dq : 0;
+            rs.neg_half[r] = hq ? qr - hq : 0;
+            rs.P_mod_q[r] = prod_mod(0, qr);
+            u64 inv;
+            if (!invmod(Dq, qr, inv))
+                throw std::logic_error("merged rescale: inverse does not exist");
+            rs.invD[r] = inv;
+            rs.invD_shoup[r] = shoup(inv, qr);
+        }
+        rs.P_mod_l = prod_mod(0, dp[0]);
+        rs.hat = upload<u64>(*this, lt.owned, hat.data(), hat.size());
+        lt.h_ksr = rs;
+        lt.d_ksr = upload<KsRescaleDev>(*this, lt.owned, &rs, 1);
+        return lt;
+    }
+
     const std::uint32_t *Engine::galois_table(std::uint32_t elt)
     {
         std::lock_guard<std::mutex> lock(mu);

@@ -194,6 +194,21 @@ namespace sealhip
         u64 invP[kMaxModuli], invP_shoup[kMaxModuli];        // [k]  P^{-1} mod q_i
     };
 
+    // ---- the mod-down merged with the CKKS rescale at level k >= 2: the dropped set is
+    // Dset = (l = q_{k-1}, p_0 .. p_{nsp-1}), D = P * l, half = floor(D / 2); index a walks Dset, index r the k - 1 kept primes
+    struct KsRescaleDev
+    {
+        int k, nsp;
+        unsigned drop_prime[kMaxModuli + 1];                           // prime id of Dset[a]
+        u64 inv_hat[kMaxModuli + 1], inv_hat_shoup[kMaxModuli + 1];    // (D / d)^-1 mod d
+        u64 half_d[kMaxModuli + 1];                                    // half mod d
+        const u64 *hat;                                                // [k - 1][nsp + 1]  (D / d) mod q_r
+        u64 neg_D[kMaxModuli], neg_half[kMaxModuli];                   // (-D) mod q_r, (-half) mod q_r
+        u64 P_mod_q[kMaxModuli];                                       // P mod q_r (r < k - 1)
+        u64 P_mod_l;                                                   // P mod l
+        u64 invD[kMaxModuli], invD_shoup[kMaxModuli];                  // D^-1 mod q_r
+    };
+
     // ---- CKKSEncoder::decode constants for the first k primes (RNSBase of the level, rns.cpp:237-290; context.cpp:370-376)
     constexpr int kCkksMaxLimbs = 32;
     struct CkksDecodeDev
@@ -221,6 +236,8 @@ namespace sealhip
         RnsDev *d_rns = nullptr;
         KsDev *d_ks = nullptr;
         KsDev h_ks{};
+        KsRescaleDev *d_ksr = nullptr; // built by Engine::level_rescale, at the first *_rescale call of the level
+        KsRescaleDev h_ksr{};
         RnsDev h_rns{};
         std::vector<void *> owned; // device allocations to free
         RowMap map_q{}, map_bsk{}, map_key{}, map_qbsk{};
@@ -389,6 +406,7 @@ namespace sealhip
         }
         LevelTools &level(int k);       // builds host + device constants on first use
         LevelTools &level_host(int k);  // host constants only
+        LevelTools &level_rescale(int k); // level(k) with the merged rescale's constants (CKKS, 2 <= k <= first level)
         const std::uint32_t *galois_table(std::uint32_t elt);
         void ws_reset() const
         {
@@ -600,6 +618,17 @@ namespace sealhip
                                       std::size_t prod_stride, const u64 *temp, std::size_t temp_stride, u64 *ct,
                                       std::size_t ct_item_stride, std::size_t npolys, int add_into_ct,
                                       const u64 *c0_src = nullptr, std::size_t c0_stride = 0);
+    // The mod-down merged with the CKKS rescale (tests/ks_rescale_ref.py). Polynomial pl is component
+    // pl & 1 of item pl >> 1: base[item][comp][k][N] at base_stride words per item, acc[pl][k + nsp][N] at acc_stride words
+    // per polynomial. fold: acc[pl][k-1] += (P mod l) * base[..][k-1] (step 1, NTT form). pre: steps 2-4 from the
+    // coefficient-form dropped rows k-1 .. k+nsp-1 of acc into temp[pl][k-1][N]. post: step 5 into out[pl][k-1][N].
+    hipError_t launch_ks_rescale_fold(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &h, const u64 *base,
+                                      std::size_t base_stride, u64 *acc, std::size_t acc_stride, std::size_t npolys);
+    hipError_t launch_ks_moddown_rescale_pre(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &h, const u64 *acc,
+                                             std::size_t acc_stride, u64 *temp, std::size_t npolys);
+    hipError_t launch_ks_moddown_rescale_post(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &h, const u64 *base,
+                                              std::size_t base_stride, const u64 *acc, std::size_t acc_stride, const u64 *temp,
+                                              u64 *out, std::size_t npolys);
 
     // hoisted rotation (hoist.hip): the Galois elements of one launch, by value in the kernel arguments (nothing to upload,
     // so the launch is capturable): the NTT-form table T_g (Engine::galois_table), the key K_g, the element itself
@@ -712,6 +741,10 @@ namespace sealhip
     void op_switch_key(Engine &e, int k, u64 *ct, std::size_t ct_stride, const u64 *target, std::size_t target_stride,
                        std::size_t count, const KSwitchKey &key, const u64 *c0_src = nullptr, std::size_t c0_stride = 0,
                        const KsSplit *split = nullptr);
+    // CKKS: out[count][2][k-1][N] = the merged mod-down and rescale of base + key switch of target;
+    // base[item] = two polynomials of k rows at base_stride words per item; nothing but out is written
+    void op_switch_key_rescale(Engine &e, int k, const u64 *base, std::size_t base_stride, const u64 *target,
+                               std::size_t target_stride, std::size_t count, const KSwitchKey &key, u64 *out);
     void op_modup(Engine &e, int k, int bundle, u64 *ext, std::size_t count);
     void op_bfv_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out);
     void op_ckks_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out);
@@ -720,7 +753,7 @@ namespace sealhip
     // takes ONE inverse transform and ONE floor. key == nullptr: out[count][3][k][N]; else the sum is relinearized once and
     // out is [count][2][k][N]. The operands are only read.
     void op_dot_product(Engine &e, int k, const u64 *const *a, const u64 *const *b, std::size_t n_terms, std::size_t count,
-                        const KSwitchKey *key, u64 *out);
+                        const KSwitchKey *key, u64 *out, bool rescale = false);
     // terms a level admits (BFV: while the floor's Shenoy-Kumaresan conversion stays exact; CKKS: 2^32 - 1); host constants only
     std::uint64_t dot_product_max_terms(Engine &e, int k);
     // Evaluator::square as its own path (evaluator.cpp:560-770): the operand is lifted / transformed once
@@ -740,13 +773,14 @@ namespace sealhip
     // out[n_sums][count][2][k][N]; plain_ntt[n_sums][n_elts][n_key][N]; keys[i] may be null where elts[i] == 1.
     void op_apply_galois_dot_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
                                    const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
-                                   std::size_t n_sums, u64 *out);
+                                   std::size_t n_sums, u64 *out, bool rescale = false);
     // sum_j sigma_{h_j}( sum_i W[j][i] * sigma_{g_i}(ct) ) with the giant steps accumulated in the extended basis and one
     // full mod-down: out[count][2][k][N]; plain_ntt[n_giant][n_baby][n_key][N]; a key may be null
     // where its element is 1.
     void op_apply_galois_bsgs_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *baby_elts,
                                     const KSwitchKey *const *baby_keys, std::size_t n_baby, const std::uint32_t *giant_elts,
-                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out);
+                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out,
+                                    bool rescale = false);
     void op_multiply_plain(Engine &e, int k, u64 *ct, int size, std::size_t count, const u64 *plain,
                            std::size_t plain_stride);
     // Evaluator::transform_to_ntt(Plaintext) (evaluator.cpp:1648-1744), BFV: plain_ntt[count][k][N]

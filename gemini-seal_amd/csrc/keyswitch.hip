@@ -414,6 +414,133 @@ namespace sealhip
                 note_nonzero(tflags, poly >> 1, nz);
         }
 
+        // ---- the mod-down merged with the CKKS rescale (tests/ks_rescale_ref.py) ----
+        // step 1's fold: acc[pl][k-1] += (P mod l) * base[..][k-1], NTT form, canonical. One lane per (polynomial, coefficient).
+        __global__ __launch_bounds__(kThreads) void ks_rescale_fold_kernel(const KsRescaleDev *__restrict__ d,
+                                                                           const PrimeDev *__restrict__ primes,
+                                                                           const u64 *__restrict__ base, std::size_t base_stride,
+                                                                           u64 *__restrict__ acc, std::size_t acc_stride,
+                                                                           std::size_t npolys, int logn)
+        {
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t poly = i >> logn;
+            if (poly >= npolys)
+                return;
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const std::size_t c = i & (N - 1);
+            const int k = d->k;
+            const PrimeDev &L = primes[d->drop_prime[0]];
+            const u64 b = base[(poly >> 1) * base_stride + ((poly & 1) * static_cast<std::size_t>(k) + (k - 1)) * N + c];
+            u64 *pa = acc + poly * acc_stride + static_cast<std::size_t>(k - 1) * N + c;
+            *pa = mul_add_mod(b, d->P_mod_l, *pa, L.p, L.cr0, L.cr1);
+        }
+
+        // step 2 for dropped prime a, and step 3's term floor(z * C_d / 2^64) = z * cr1 + mulhi(z, cr0) added into (slo, shi):
+        // z < d and C_d = cr1 * 2^64 + cr0 <= 2^128 / d, so z * cr1 < 2^64 and the term fits one word
+        __device__ __forceinline__ u64 rescale_z(const KsRescaleDev *__restrict__ d, const PrimeDev *__restrict__ primes, int a,
+                                                 u64 y, u64 &slo, u64 &shi)
+        {
+            const PrimeDev &S = primes[d->drop_prime[a]];
+            const u64 z = mulmod_shoup(add_mod(y, d->half_d[a], S.p), d->inv_hat[a], d->inv_hat_shoup[a], S.p);
+            const u64 t = z * S.cr1 + mulhi(z, S.cr0);
+            const u64 nl = slo + t;
+            shi += nl < slo;
+            slo = nl;
+            return z;
+        }
+
+        // steps 2-4 up to the forward transform: one lane per (polynomial, coefficient) computes z_d and the exact quotient v
+        // once and walks the k - 1 kept primes. ND1 = |Dset| = nsp + 1 in 2..4 keeps z_d in registers; ND1 = 0 is the loop
+        // form for larger sets, which re-reads the dropped rows per kept prime (the lane's own addresses: L1 hits) as
+        // ks_moddown_pre_kernel does -- no array indexed by a run-time value.
+        // The sum of step 4 is at most (nsp + 1) (2^61)^2 + (nsp + 1) 2^61 + 2^61 < 2^128 for nsp + 1 <= 64 primes of 61 bits
+        // (bounds::ks_rescale_sum_fits, executed by tests/ks_rescale_bounds_check.cpp).
+        template <int ND1>
+        __global__ __launch_bounds__(kThreads) void ks_moddown_rescale_pre_kernel(const KsRescaleDev *__restrict__ d,
+                                                                                  const PrimeDev *__restrict__ primes,
+                                                                                  const u64 *__restrict__ acc,
+                                                                                  std::size_t acc_stride, u64 *__restrict__ temp,
+                                                                                  std::size_t npolys, int logn)
+        {
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t poly = i >> logn;
+            if (poly >= npolys)
+                return;
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const std::size_t c = i & (N - 1);
+            const int k = d->k, nd1 = d->nsp + 1;
+            const u64 *dp = acc + poly * acc_stride + static_cast<std::size_t>(k - 1) * N + c; // dropped row a: dp[a * N]
+            u64 *pt = temp + poly * static_cast<std::size_t>(k - 1) * N + c;
+            u64 slo = 0, shi = 0;
+            if constexpr (ND1 > 0)
+            {
+                u64 z[ND1];
+#pragma unroll
+                for (int a = 0; a < ND1; a++)
+                    z[a] = rescale_z(d, primes, a, dp[a * N], slo, shi);
+                const u64 v = shi; // step 3: the sum's second word
+                for (int r = 0; r < k - 1; r++)
+                {
+                    const PrimeDev &Q = primes[r];
+                    const u64 *hat = d->hat + static_cast<std::size_t>(r) * ND1;
+                    u64 lo = d->neg_half[r], hi = 0;
+#pragma unroll
+                    for (int a = 0; a < ND1; a++)
+                        mac128(lo, hi, z[a], hat[a]);
+                    mac128(lo, hi, v, d->neg_D[r]);
+                    pt[r * N] = barrett_reduce_128(lo, hi, Q.p, Q.cr0, Q.cr1);
+                }
+            }
+            else
+            {
+                for (int a = 0; a < nd1; a++)
+                    rescale_z(d, primes, a, dp[a * N], slo, shi);
+                const u64 v = shi;
+                for (int r = 0; r < k - 1; r++)
+                {
+                    const PrimeDev &Q = primes[r];
+                    const u64 *hat = d->hat + static_cast<std::size_t>(r) * nd1;
+                    u64 lo = d->neg_half[r], hi = 0, s0 = 0, s1 = 0;
+                    for (int a = 0; a < nd1; a++)
+                        mac128(lo, hi, rescale_z(d, primes, a, dp[a * N], s0, s1), hat[a]);
+                    mac128(lo, hi, v, d->neg_D[r]);
+                    pt[r * N] = barrett_reduce_128(lo, hi, Q.p, Q.cr0, Q.cr1);
+                }
+            }
+        }
+
+        // step 5: out[pl][r] = (acc[pl][r] + (P mod q_r) * base[..][r] - temp[pl][r]) * D^-1 mod q_r; temp is canonical (the
+        // forward transform canonicalises). One lane per (polynomial, kept row, coefficient); component 1 notes the flag.
+        __global__ __launch_bounds__(kThreads) void ks_moddown_rescale_post_kernel(const KsRescaleDev *__restrict__ d,
+                                                                                   const PrimeDev *__restrict__ primes,
+                                                                                   const u64 *__restrict__ base,
+                                                                                   std::size_t base_stride,
+                                                                                   const u64 *__restrict__ acc,
+                                                                                   std::size_t acc_stride,
+                                                                                   const u64 *__restrict__ temp, u64 *__restrict__ out,
+                                                                                   std::size_t npolys, int logn,
+                                                                                   unsigned *__restrict__ tflags)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const int k = d->k, kk = k - 1;
+            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
+            const std::size_t c = i & (N - 1);
+            const std::size_t rr = i >> logn;
+            const int r = static_cast<int>(rr % kk);
+            const std::size_t poly = rr / kk;
+            if (poly >= npolys)
+                return;
+            const PrimeDev &Q = primes[r];
+            const std::size_t row = static_cast<std::size_t>(r) * N + c;
+            const u64 b = base[(poly >> 1) * base_stride + (poly & 1) * static_cast<std::size_t>(k) * N + row];
+            const u64 s = mul_add_mod(b, d->P_mod_q[r], acc[poly * acc_stride + row], Q.p, Q.cr0, Q.cr1);
+            const std::size_t o = poly * static_cast<std::size_t>(kk) * N + row;
+            const u64 w = mulmod_shoup(sub_mod(s, temp[o], Q.p), d->invD[r], d->invD_shoup[r], Q.p);
+            store_stream(out + o, w);
+            if (poly & 1)
+                note_nonzero(tflags, poly >> 1, w);
+        }
+
         inline unsigned blocks_for(std::size_t lanes)
         {
             return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
@@ -542,6 +669,57 @@ namespace sealhip
         ks_moddown_post_kernel<<<blocks_for(lanes), kThreads, 0, e.lane().stream>>>(
             d, e.d_primes, prod, prod_stride, temp, temp_stride, ct, ct_item_stride, npolys, e.logn, add_into_ct, c0_src, c0_stride,
             add_into_ct ? e.lane().tsink_arm : nullptr);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_ks_rescale_fold(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &, const u64 *base,
+                                      std::size_t base_stride, u64 *acc, std::size_t acc_stride, std::size_t npolys)
+    {
+        if (!npolys)
+            return hipSuccess;
+        ProfScope prof(e, "ks_rescale_fold", 0);
+        ks_rescale_fold_kernel<<<blocks_for(npolys << e.logn), kThreads, 0, e.lane().stream>>>(d, e.d_primes, base, base_stride, acc,
+                                                                                            acc_stride, npolys, e.logn);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_ks_moddown_rescale_pre(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &h, const u64 *acc,
+                                             std::size_t acc_stride, u64 *temp, std::size_t npolys)
+    {
+        if (!npolys)
+            return hipSuccess;
+        ProfScope prof(e, "ks_moddown_rescale_pre", 0);
+#define SEALHIP_RESCALE_PRE(ND1)                                                                                     \
+    ks_moddown_rescale_pre_kernel<ND1><<<blocks_for(npolys << e.logn), kThreads, 0, e.lane().stream>>>(                    \
+        d, e.d_primes, acc, acc_stride, temp, npolys, e.logn)
+        switch (h.nsp + 1)
+        {
+        case 2:
+            SEALHIP_RESCALE_PRE(2);
+            break;
+        case 3:
+            SEALHIP_RESCALE_PRE(3);
+            break;
+        case 4:
+            SEALHIP_RESCALE_PRE(4);
+            break;
+        default:
+            SEALHIP_RESCALE_PRE(0);
+        }
+#undef SEALHIP_RESCALE_PRE
+        return hipGetLastError();
+    }
+
+    hipError_t launch_ks_moddown_rescale_post(const Engine &e, const KsRescaleDev *d, const KsRescaleDev &h, const u64 *base,
+                                              std::size_t base_stride, const u64 *acc, std::size_t acc_stride, const u64 *temp,
+                                              u64 *out, std::size_t npolys)
+    {
+        if (!npolys)
+            return hipSuccess;
+        const std::size_t lanes = (npolys * static_cast<std::size_t>(h.k - 1)) << e.logn;
+        ProfScope prof(e, "ks_moddown_rescale_post", 0);
+        ks_moddown_rescale_post_kernel<<<blocks_for(lanes), kThreads, 0, e.lane().stream>>>(
+            d, e.d_primes, base, base_stride, acc, acc_stride, temp, out, npolys, e.logn, e.lane().tsink_arm);
         return hipGetLastError();
     }
 } // namespace sealhip

@@ -513,5 +513,21 @@ namespace sealhip
         static_assert(dot_group_admits(kDotGroupTerms, kDotAccOperandBits), "16 terms of 61-bit operands fit 128 bits");
         static_assert(dot_group_admits(31, kDotAccOperandBits) && !dot_group_admits(32, kDotAccOperandBits),
                       "this (conservative) count admits 31 terms at 61 bits: the group of 16 leaves almost a factor two");
+
+        // =====================================================================================================
+        // 9. The merged mod-down and rescale's conversion sum (keyswitch.hip ks_moddown_rescale_pre_kernel, DESIGN.md section
+        // 19): per kept prime, `dropped` products z_d * hat_d of canonical residues, the quotient v <= dropped times a
+        // canonical residue, and one canonical residue, accumulated with mac128 and reduced once. With every residue at most
+        // m = 2^bits - 1 the sum is at most dropped m^2 + (dropped + 1) m; it must stay below 2^128.
+        constexpr bool ks_rescale_sum_fits(int dropped, int bits)
+        {
+            if (dropped < 1 || bits < 1 || bits > 63)
+                return false;
+            const u128 m = (static_cast<u128>(1) << bits) - 1, max = ~static_cast<u128>(0);
+            const u128 tail = static_cast<u128>(dropped + 1) * m; // (below 2^71)
+            return static_cast<u128>(dropped) <= (max - tail) / (m * m);
+        }
+        static_assert(ks_rescale_sum_fits(64, kDotAccOperandBits) && !ks_rescale_sum_fits(65, kDotAccOperandBits),
+                      "the last prime and up to 63 special primes of 61 bits: 64 dropped primes fit, 65 would not");
     } // namespace bounds
 } // namespace sealhip

@@ -134,6 +134,19 @@ namespace sealhip
                 l.tsink_arm = nullptr;
             }
         };
+        // Restores the arena floor an operation raised over buffers at the front of the arena that must survive a nested
+        // operation's chunk loop (which resets the arena to the floor).
+        struct FloorRestore
+        {
+            Lane &l;
+            std::size_t floor;
+            explicit FloorRestore(Engine &e) : l(e.lane()), floor(l.ws_floor)
+            {}
+            ~FloorRestore()
+            {
+                l.ws_floor = floor;
+            }
+        };
     } // namespace
 
     namespace
@@ -383,6 +396,34 @@ namespace sealhip
                       "moddown_post");
             }
         }
+
+        // ks_finish merged with rescale_to_next (the words are those of tests/ks_rescale_ref.py):
+        // out[m][2][k-1][N] = floor((P * base + acc + half) / (P * q_{k-1})), CKKS only. base: m items of two polynomials of k
+        // rows (NTT form, canonical), base_stride words apart, read only. acc: the m x 2 reduced products, 2 (k + nsp) N
+        // words per item; their dropped rows are overwritten. temp: 2 (k - 1) N words per item. The nsp + 1 dropped rows go
+        // back to coefficient form in one launch, one kernel converts them to the k - 1 kept rows with the exact quotient,
+        // those go forward, one kernel finishes: 2 (nsp + k) row transforms, and the level-k result is never formed.
+        void ks_finish_rescale(Engine &e, LevelTools &lt, int k, const u64 *base, std::size_t base_stride, u64 *acc, u64 *temp,
+                               u64 *out, std::size_t m, unsigned *sink)
+        {
+            if (e.scheme != 2 || k < 2 || !lt.d_ksr)
+                throw std::logic_error("internal: merged rescale misused");
+            const KsRescaleDev &h = lt.h_ksr;
+            const std::size_t N = e.n;
+            const int rows = k + e.nsp;
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            check(launch_ks_rescale_fold(e, lt.d_ksr, h, base, base_stride, acc, ext_item, 2 * m), "rescale_fold");
+            // (the conversion adds half to canonical residues: the canonicalising inverse)
+            check(launch_ntt(e, acc, m * 2 * rows, skip_map(lt.map_key, k - 1, rows), true, kNttCanonical), "intt(dropped)");
+            check(launch_ks_moddown_rescale_pre(e, lt.d_ksr, h, acc, ext_item, temp, 2 * m), "moddown_rescale_pre");
+            // the exact transform in both modes (PARITY's uncorrected butterflies may wrap on 60- and 61-bit primes, SURVEY
+            // B.6, and there is no reference behaviour to reproduce for an operation the fork does not have); canonical,
+            // because the post kernel subtracts these words from canonical residues
+            check(launch_ntt(e, temp, m * 2 * (k - 1), e.level_host(k - 1).map_q, false, kNttCanonical | kNttStrict), "ntt(temp)");
+            SinkArm arm(e, sink);
+            check(launch_ks_moddown_rescale_post(e, lt.d_ksr, h, base, base_stride, acc, ext_item, temp, out, 2 * m),
+                  "moddown_rescale_post");
+        }
     } // namespace
 
     // ------------------------------------------------------------------------------------------
@@ -445,6 +486,52 @@ namespace sealhip
             if (partial)
                 return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
             ks_finish(e, lt, k, prod, temp, ctp, ct_stride, c0p, c0_stride, m, sink_at(e, off));
+        });
+    }
+
+    // bytes of arena one item of op_switch_key_rescale needs (shared with op_dot_product, which nests it)
+    static std::size_t switch_key_rescale_item_bytes(Engine &e, int k)
+    {
+        const std::size_t N = e.n, rows = static_cast<std::size_t>(k + e.nsp);
+        const std::size_t nd = static_cast<std::size_t>(e.level(k).h_ks.nd);
+        return (static_cast<std::size_t>(k) * N + nd * rows * N + 2 * rows * N + 2 * static_cast<std::size_t>(k - 1) * N) *
+               sizeof(u64);
+    }
+
+    // relinearize + rescale_to_next in one call: op_switch_key's front half, then the merged finish
+    void op_switch_key_rescale(Engine &e, int k, const u64 *base, std::size_t base_stride, const u64 *target,
+                               std::size_t target_stride, std::size_t count, const KSwitchKey &key, u64 *out)
+    {
+        if (e.scheme != 2)
+            throw std::invalid_argument("the merged rescale is a CKKS operation");
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        if (k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached"); // evaluator.cpp:1005-1008
+        LevelTools &lt = e.level_rescale(k);
+        const KsDev &h = lt.h_ks;
+        if (static_cast<int>(key.n_digits) < h.nd)
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const std::size_t N = e.n;
+        const int rows = k + e.nsp, nd = h.nd;
+        const std::size_t w_coeff = static_cast<std::size_t>(k) * N;
+        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
+        const std::size_t w_prod = 2ull * rows * N;
+        const std::size_t w_temp = 2ull * (k - 1) * N;
+        const std::size_t per_item = switch_key_rescale_item_bytes(e, k);
+        if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
+            throw std::logic_error("internal: arena accounting mismatch");
+        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = e.ws_alloc(w_coeff * m);
+            u64 *ext = e.ws_alloc(w_ext * m);
+            u64 *prod = e.ws_alloc(w_prod * m);
+            u64 *temp = e.ws_alloc(w_temp * m);
+            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
+            const KsRows in_bundle = ks_digits(e, lt, k, target + off * target_stride, target_stride, m, coeff, ext, 0, nd);
+            check(launch_ks_mac(e, lt.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m, key.d_data, prod,
+                                w_prod, m, 0, nd),
+                  "mac");
+            ks_finish_rescale(e, lt, k, base + off * base_stride, base_stride, prod, temp, out + off * w_temp, m, sink_at(e, off));
         });
     }
 
@@ -725,12 +812,18 @@ namespace sealhip
     // holds a group of terms in the arena, and sends the SUM through that path's tail once: one inverse transform of
     // 3 (k + |Bsk|) rows and three floors, whatever the number of terms. With a key the sum's c_2 stays in the arena and the
     // key switch adds its two polynomials into (c_0, c_1) in `out`.
+    // rescale (CKKS with a key): (c_0, c_1) of the sum stay in the arena next to c_2 and
+    // op_switch_key_rescale writes out[count][2][k-1][N].
     void op_dot_product(Engine &e, int k, const u64 *const *a, const u64 *const *b, std::size_t n_terms, std::size_t count,
-                        const KSwitchKey *key, u64 *out)
+                        const KSwitchKey *key, u64 *out, bool rescale)
     {
         if (k > e.k_first)
             throw std::invalid_argument("the inner product needs a ciphertext level");
         const bool ckks = e.scheme == 2;
+        if (rescale && (!ckks || !key))
+            throw std::invalid_argument("the merged rescale is a CKKS operation and needs relinearization keys");
+        if (rescale && k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached");
         if (!ckks && !e.mode_strict)
             // (as for the hoisted entries: the fork's BFV key switch does not decrypt, and there is no reference behaviour to
             //  reproduce for an operation the fork does not have)
@@ -742,8 +835,9 @@ namespace sealhip
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         const std::size_t N = e.n, poly_q = static_cast<std::size_t>(k) * N;
         const std::size_t out_item = (key ? 2 : 3) * poly_q;
-        const std::size_t ks_bytes = key ? switch_key_item_bytes(e, k) : 0;
+        const std::size_t ks_bytes = rescale ? switch_key_rescale_item_bytes(e, k) : key ? switch_key_item_bytes(e, k) : 0;
         const std::size_t w_c2 = key ? poly_q : 0;
+        const std::size_t w_c01 = rescale ? 2 * poly_q : 0; // (c_0, c_1) of the sum, when out is the level below
         // BFV: X holds a group of terms (4 polynomials of k + |Bsk| rows each), D the sum (3 polynomials)
         BfvMulPlan plan{};
         int kb = k;
@@ -775,8 +869,10 @@ namespace sealhip
         // c_2 must survive op_switch_key, which re-plans the arena: it is carved first and the floor raised over it; the
         // item's bytes cover the larger of this operation's temporaries and the key switch's, so the nested plan fits what
         // is reserved here and the arena cannot move while c_2 is live
-        for_chunks(e, count, w_c2 * sizeof(u64) + std::max(work_bytes, ks_bytes), 6, [&](std::size_t off, std::size_t m) {
+        for_chunks(e, count, (w_c2 + w_c01) * sizeof(u64) + std::max(work_bytes, ks_bytes), rescale ? 7 : 6,
+                   [&](std::size_t off, std::size_t m) {
             u64 *c2 = key ? e.ws_alloc(w_c2 * m) : nullptr;
+            u64 *c01 = rescale ? e.ws_alloc(w_c01 * m) : nullptr;
             struct FloorGuard
             {
                 Lane &l;
@@ -787,7 +883,7 @@ namespace sealhip
                     l.tsink_base = base;
                 }
             } guard{ e.lane(), e.lane().ws_floor, e.lane().tsink_base };
-            u64 *o = out + off * out_item;
+            u64 *o = rescale ? c01 : out + off * out_item;
             unsigned *const flags = sink_at(e, off);
             if (ckks)
             {
@@ -881,9 +977,12 @@ namespace sealhip
             if (key)
             {
                 // relinearize_internal (evaluator.cpp:811-815) of the sum: (c_0, c_1) += key switch of c_2
-                e.lane().ws_floor = guard.floor + pad256(w_c2 * m);
+                e.lane().ws_floor = guard.floor + pad256(w_c2 * m) + (rescale ? pad256(w_c01 * m) : 0);
                 e.lane().tsink_base = guard.base + off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
-                op_switch_key(e, k, o, 2 * poly_q, c2, poly_q, m, *key);
+                if (rescale)
+                    op_switch_key_rescale(e, k, c01, 2 * poly_q, c2, poly_q, m, *key, out + off * 2 * (poly_q - N));
+                else
+                    op_switch_key(e, k, o, 2 * poly_q, c2, poly_q, m, *key);
             }
         });
     }
@@ -894,7 +993,7 @@ namespace sealhip
     namespace
     {
         void mod_switch_polys(Engine &e, int k, const u64 *ct, std::size_t in_stride, u64 *out, std::size_t out_stride,
-                              std::size_t npolys);
+                              std::size_t npolys, bool exact = false);
     }
     // in_item_stride (words, 0 = the ciphertexts are back to back): distance between consecutive ciphertexts of `ct` when they
     // sit in a wider container -- the size-2 result of relinearize inside its size-3 product (the reference's objects are
@@ -918,11 +1017,13 @@ namespace sealhip
     // The CKKS division by the last prime of level k (rns.cpp:777-851) up to its forward transforms; lt = e.level(k).
     // rescale_temp: from the coefficient-form last rows of npolys polynomials (last_stride words apart) to their correction
     // over the k - 1 remaining primes in temp[npolys][k - 1][N], lazily transformed (rescale_post reduces).
-    void rescale_temp(Engine &e, LevelTools &lt, int k, u64 *last, std::size_t last_stride, std::size_t npolys, u64 *temp)
+    // ntt_flags: kNttStrict asks for the exact transform whatever the context's mode
+    void rescale_temp(Engine &e, LevelTools &lt, int k, u64 *last, std::size_t last_stride, std::size_t npolys, u64 *temp,
+                      int ntt_flags = 0)
     {
         check(launch_rescale_pre(e, lt.d_rns, lt.h_rns, last, last_stride, temp, static_cast<std::size_t>(k - 1) * e.n, npolys),
               "rescale_pre");
-        check(launch_ntt(e, temp, npolys * (k - 1), e.level_host(k - 1).map_q, false, 0), "ntt(temp)");
+        check(launch_ntt(e, temp, npolys * (k - 1), e.level_host(k - 1).map_q, false, ntt_flags), "ntt(temp)");
     }
     // divround_ntt_front: the same for polys[npolys][k][N] in NTT form, whose last rows go to coefficient form in place first
     void divround_ntt_front(Engine &e, LevelTools &lt, int k, u64 *polys, std::size_t npolys, u64 *temp)
@@ -931,8 +1032,10 @@ namespace sealhip
         rescale_temp(e, lt, k, polys + static_cast<std::size_t>(k - 1) * e.n, static_cast<std::size_t>(k) * e.n, npolys, temp);
     }
 
+    // exact (CKKS): the correction's forward transform is the exact one in both modes -- the merged finish without a
+    // key-switch term, whose words the restatement defines with the exact transform
     void mod_switch_polys(Engine &e, int k, const u64 *ct, std::size_t in_stride, u64 *out, std::size_t out_stride,
-                          std::size_t npolys)
+                          std::size_t npolys, bool exact)
     {
         LevelTools &lt = e.level(k);
         const std::size_t N = e.n;
@@ -954,7 +1057,7 @@ namespace sealhip
             one.rows = 1;
             one.prime[0] = static_cast<unsigned short>(k - 1);
             check(launch_ntt(e, last, m, one, true, kNttCanonical), "intt(last)");
-            rescale_temp(e, lt, k, last, N, m, temp);
+            rescale_temp(e, lt, k, last, N, m, temp, exact ? kNttStrict : 0);
             check(launch_rescale_post(e, lt.d_rns, lt.h_rns, ct + off * in_stride, in_stride, temp, temp_stride,
                                       out + off * out_stride, out_stride, m),
                   "rescale_post");
@@ -1137,14 +1240,18 @@ namespace sealhip
     // into base_s = (sum_i W (.) sigma_i(C_0), sum_{i identity} W (.) C_1), which the base kernel writes straight into out.
     void op_apply_galois_dot_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,
                                    const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
-                                   std::size_t n_sums, u64 *out)
+                                   std::size_t n_sums, u64 *out, bool rescale)
     {
         if (k > e.k_first)
             throw std::invalid_argument("key switching needs a ciphertext level");
         const bool ckks = e.scheme == 2;
+        if (rescale && !ckks)
+            throw std::invalid_argument("the merged rescale is a CKKS operation");
+        if (rescale && k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached");
         if (!ckks && !e.mode_strict)
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
-        LevelTools &ld = e.level(k);
+        LevelTools &ld = rescale ? e.level_rescale(k) : e.level(k);
         const KsDev &h = ld.h_ks;
         const int nd = h.nd, rows = k + e.nsp;
         std::size_t n_gal = 0;
@@ -1172,10 +1279,16 @@ namespace sealhip
         const std::size_t w_ext = n_gal ? static_cast<std::size_t>(nd) * rows * N : 0;
         const std::size_t w_cn = ckks ? 0 : 2 * poly; // (BFV: both components in NTT form)
         const std::size_t w_prod = n_gal ? 2ull * rows * N : 0;
-        const std::size_t w_temp = n_gal ? 2ull * poly : 0;
+        // rescale: out is the level below, out[n_sums][count][2][k-1][N], so base_s lives in the
+        // arena (at its front: without a Galois element the finish is the plain rescale of base_s, a nested chunk loop, and
+        // the floor is raised over base_s) and the merged finish writes out
+        const std::size_t poly_out = rescale ? poly - N : poly;
+        const std::size_t w_temp = n_gal ? 2ull * poly_out : 0;
+        const std::size_t w_base = rescale ? 2 * poly : 0, w_ms = rescale && !n_gal ? 2 * poly : 0;
         // arena of one item: the digits (and BFV's transformed components) once, per sum the accumulated products and the
         // mod-down's temporaries; base_s lives in out
-        const std::size_t base_bytes = (w_coeff + w_ext + w_cn) * sizeof(u64), sum_bytes = (w_prod + w_temp) * sizeof(u64);
+        const std::size_t base_bytes = (w_coeff + w_ext + w_cn) * sizeof(u64),
+                          sum_bytes = (w_prod + w_temp + w_base + w_ms) * sizeof(u64);
         // when not even one item fits with all its sums, the sum list is walked in passes and the digits stay live
         std::size_t pass = n_sums;
         const std::size_t budget = workspace_budget_bytes(e);
@@ -1186,12 +1299,14 @@ namespace sealhip
             log_chunk(e, n_sums, pass); // (the sum split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
         }
         unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext, in output order
-        for_chunks(e, count, base_bytes + pass * sum_bytes, 5, [&](std::size_t off, std::size_t m) {
+        for_chunks(e, count, base_bytes + pass * sum_bytes, rescale ? 8 : 5, [&](std::size_t off, std::size_t m) {
+            u64 *basebuf = rescale ? e.ws_alloc(w_base * m * pass) : nullptr;
             u64 *coeff = n_gal ? e.ws_alloc(w_coeff * m) : nullptr;
             u64 *ext = n_gal ? e.ws_alloc(w_ext * m) : nullptr;
             u64 *cntt = w_cn ? e.ws_alloc(w_cn * m) : nullptr;
             u64 *acc = n_gal ? e.ws_alloc(w_prod * m * pass) : nullptr;
             u64 *temp = n_gal ? e.ws_alloc(w_temp * m * pass) : nullptr;
+            FloorRestore restore(e);
             const u64 *c = ct + off * 2 * poly;
             const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
             KsRows in_bundle{ nullptr, 0 };
@@ -1208,10 +1323,12 @@ namespace sealhip
             {
                 const std::size_t ns = std::min(pass, n_sums - s0);
                 const u64 *w0 = plain_ntt + s0 * w_sum_stride;
-                u64 *o = out + (s0 * count + off) * 2 * poly; // sum s0 + s of this chunk: o + s * count * 2 * poly
+                // base of sum s0 + s of this chunk: o + s * o_sum
+                u64 *o = rescale ? basebuf : out + (s0 * count + off) * 2 * poly;
+                const std::size_t o_sum = rescale ? m * 2 * poly : count * 2 * poly;
                 HoistDotElts he{};
                 const auto flush_base = [&](bool add) {
-                    check(launch_hoist_dot_base(e, cn, he, w_sum_stride, o, count * 2 * poly, k, m, ns, add), "hoist_dot_base");
+                    check(launch_hoist_dot_base(e, cn, he, w_sum_stride, o, o_sum, k, m, ns, add), "hoist_dot_base");
                     he.n = 0;
                 };
                 bool launched = false;
@@ -1249,8 +1366,24 @@ namespace sealhip
                 const std::size_t run = m == count ? ns : 1;
                 for (std::size_t s = 0; s < ns; s += run)
                 {
-                    u64 *os = o + s * count * 2 * poly;
+                    u64 *os = o + s * o_sum;
                     const std::size_t first = (s0 + s) * count + off; // (output ciphertext, and its transparency flag)
+                    if (rescale)
+                    {
+                        u64 *od = out + first * 2 * poly_out;
+                        if (n_gal)
+                            ks_finish_rescale(e, ld, k, os, 2 * poly, acc + s * m * w_prod, temp + s * m * w_temp, od, run * m,
+                                              sink ? sink + first : nullptr);
+                        else
+                        {
+                            // acc = 0: the merged finish is rescale_to_next of base_s with the exact transform
+                            e.lane().ws_floor = restore.floor + pad256(w_base * m * pass);
+                            mod_switch_polys(e, k, os, poly, od, poly_out, run * m * 2, true);
+                            if (sink)
+                                check(launch_nonzero_tail(e, od, 2 * poly_out, poly_out, run * m, sink + first), "transparency");
+                        }
+                        continue;
+                    }
                     if (!ckks)
                         check(launch_ntt(e, os, run * m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
                     if (n_gal)
@@ -1272,14 +1405,19 @@ namespace sealhip
     // ONE ks_finish brings the whole product down.
     void op_apply_galois_bsgs_plain(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *baby_elts,
                                     const KSwitchKey *const *baby_keys, std::size_t n_baby, const std::uint32_t *giant_elts,
-                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out)
+                                    const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out,
+                                    bool rescale)
     {
         if (k > e.k_first)
             throw std::invalid_argument("key switching needs a ciphertext level");
         const bool ckks = e.scheme == 2;
+        if (rescale && !ckks)
+            throw std::invalid_argument("the merged rescale is a CKKS operation");
+        if (rescale && k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached");
         if (!ckks && !e.mode_strict)
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
-        LevelTools &ld = e.level(k);
+        LevelTools &ld = rescale ? e.level_rescale(k) : e.level(k);
         const KsDev &h = ld.h_ks;
         const int nd = h.nd, rows = k + e.nsp;
         const auto check_axis = [&](const std::uint32_t *elts, const KSwitchKey *const *keys, std::size_t n) {
@@ -1319,11 +1457,15 @@ namespace sealhip
         // temporaries and d_j's digits (identity giants leave theirs unused: one size for every giant keeps the plan simple).
         const std::size_t w_coeff = n_gb ? poly : 0, w_ext = n_gb ? w_digits : 0;
         const std::size_t w_cn = ckks ? 0 : 2 * poly;
-        const std::size_t w_acc = any_acc ? w_prod : 0, w_temp = any_acc ? 2 * poly : 0;
+        // rescale: out is the level below, so BASE lives at the front of the arena (the floor is raised
+        // over it when the finish is a plain rescale: no ACC term) and the ONE final finish is the merged one
+        const std::size_t poly_out = rescale ? poly - N : poly;
+        const std::size_t w_BASE = rescale ? 2 * poly : 0, w_ms = rescale && !any_acc ? 2 * poly : 0;
+        const std::size_t w_acc = any_acc ? w_prod : 0, w_temp = any_acc ? 2 * poly_out : 0;
         const std::size_t w_accj = n_gb ? w_prod : 0;
         const std::size_t w_d = n_gg ? poly : 0, w_temp1 = n_gg && n_gb ? poly : 0;
         const std::size_t w_coeff2 = n_gg ? poly : 0, w_ext2 = n_gg ? w_digits : 0;
-        const std::size_t base_bytes = (w_coeff + w_ext + w_cn + w_acc + w_temp) * sizeof(u64);
+        const std::size_t base_bytes = (w_coeff + w_ext + w_cn + w_acc + w_temp + w_BASE + w_ms) * sizeof(u64);
         const std::size_t giant_bytes = (2 * poly + w_accj + w_d + w_temp1 + w_coeff2 + w_ext2) * sizeof(u64);
         // when not even one item fits with all its giants, the giant list is walked in passes
         std::size_t pass = n_giant;
@@ -1335,7 +1477,9 @@ namespace sealhip
             log_chunk(e, n_giant, pass); // (the giant split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
         }
         unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext
-        for_chunks(e, count, base_bytes + pass * giant_bytes, 11, [&](std::size_t off, std::size_t m) {
+        for_chunks(e, count, base_bytes + pass * giant_bytes, rescale ? 14 : 11, [&](std::size_t off, std::size_t m) {
+            u64 *BASEbuf = rescale ? e.ws_alloc(w_BASE * m) : nullptr;
+            FloorRestore restore(e);
             u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
             u64 *ext = w_ext ? e.ws_alloc(w_ext * m) : nullptr;
             u64 *cntt = w_cn ? e.ws_alloc(w_cn * m) : nullptr;
@@ -1348,7 +1492,7 @@ namespace sealhip
             u64 *coeff2 = w_coeff2 ? e.ws_alloc(w_coeff2 * m * pass) : nullptr;
             u64 *ext2 = w_ext2 ? e.ws_alloc(w_ext2 * m * pass) : nullptr;
             const u64 *c = ct + off * 2 * poly;
-            u64 *o = out + off * 2 * poly; // BASE of this chunk, then the result
+            u64 *o = rescale ? BASEbuf : out + off * 2 * poly; // BASE of this chunk, then (without rescale) the result
             KsRows in_bundle{ nullptr, 0 };
             if (n_gb)
                 in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
@@ -1476,6 +1620,21 @@ namespace sealhip
             }
             if (!ckks)
                 check(launch_ntt(e, o, m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
+            if (rescale)
+            {
+                u64 *od = out + off * 2 * poly_out;
+                if (any_acc)
+                    ks_finish_rescale(e, ld, k, o, 2 * poly, ACC, temp, od, m, sink ? sink + off : nullptr);
+                else
+                {
+                    // acc = 0: the merged finish is rescale_to_next of BASE with the exact transform
+                    e.lane().ws_floor = restore.floor + pad256(w_BASE * m);
+                    mod_switch_polys(e, k, o, poly, od, poly_out, m * 2, true);
+                    if (sink)
+                        check(launch_nonzero_tail(e, od, 2 * poly_out, poly_out, m, sink + off), "transparency");
+                }
+                return;
+            }
             if (any_acc)
                 ks_finish(e, ld, k, ACC, temp, o, 2 * poly, nullptr, 0, m, sink ? sink + off : nullptr);
             else if (sink)

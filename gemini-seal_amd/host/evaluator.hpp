@@ -85,7 +85,8 @@ namespace sealhip_host
     {
     public:
         explicit Context(const sealhip_params &p)
-            : scheme_(p.scheme), n_(std::size_t(1) << p.log_n), t_(p.plain_modulus), n_key_(p.n_key_moduli)
+            : scheme_(p.scheme), n_(std::size_t(1) << p.log_n), t_(p.plain_modulus), n_key_(p.n_key_moduli),
+              key_moduli_(p.key_moduli ? p.key_moduli : nullptr, p.key_moduli ? p.key_moduli + p.n_key_moduli : nullptr)
         {
             throw_on(sealhip_context_create(&p, &ctx_));
         }
@@ -101,6 +102,7 @@ namespace sealhip_host
         std::size_t n() const { return n_; }
         std::uint64_t plain_modulus() const { return t_; }
         std::size_t n_key() const { return n_key_; } // the highest level the ABI names (key level)
+        std::uint64_t key_modulus(std::size_t i) const { return key_moduli_.at(i); } // q_i; the special primes come last
 
         // SEALContext's parms_id of level k (sealhip_context_set_parms_id), kept for DeviceCiphertext::save
         void set_parms_id(std::size_t k, const std::uint64_t parms_id[4])
@@ -213,6 +215,7 @@ namespace sealhip_host
         std::size_t n_;
         std::uint64_t t_;
         std::size_t n_key_;
+        std::vector<std::uint64_t> key_moduli_;
         mutable std::mutex mu_;
         std::map<std::size_t, std::array<std::uint64_t, 4>> parms_ids_;
         mutable std::map<std::pair<const void *, std::thread::id>, Ring> rings_;
@@ -840,7 +843,37 @@ namespace sealhip_host
                                     const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                     const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
         {
+            dot_plain_internal(encrypted, galois_elts, galois_keys, plains, destinations, false);
+        }
+        // ... followed by rescale_to_next, in one call and with one rounding (sealhip_evaluator_apply_galois_dot_plain_rescale,
+        // DESIGN.md section 19): CKKS only; the unmerged method's checks, and "end of modulus switching chain reached" at the
+        // last level. Each result is one level down with the scale encrypted.scale() * plain.scale / q_{k-1}.
+        template <class C, class P, IfCt<C> = 0>
+        void apply_galois_dot_plain_rescale(const C &encrypted, const std::vector<std::uint32_t> &galois_elts,
+                                            const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                            const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
+        {
+            dot_plain_internal(encrypted, galois_elts, galois_keys, plains, destinations, true);
+        }
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_vector_dot_plain_rescale(const C &encrypted, const std::vector<int> &steps,
+                                             const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                             const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            dot_plain_internal(encrypted, elts_of_steps(steps), galois_keys, plains, destinations, true);
+        }
+
+    private:
+        template <class C, class P>
+        void dot_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &galois_elts,
+                                const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                const std::vector<std::vector<P>> &plains, std::vector<C> &destinations, bool rescale)
+        {
             check_galois_operand(encrypted);
+            if (rescale)
+                check_rescale_operand(encrypted);
             std::vector<const sealhip_kswitch_key *> raw;
             for (std::uint32_t elt : galois_elts)
             {
@@ -852,21 +885,24 @@ namespace sealhip_host
             const std::size_t n_elts = galois_elts.size(), n_sums = plains.size();
             const double scale = check_dot_plains(plains, n_elts);
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
-            Dev c = dev_in(encrypted, words), o = dev_out((n_sums ? n_sums : 1) * words);
+            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
+            Dev c = dev_in(encrypted, words), o = dev_out((n_sums ? n_sums : 1) * out_words);
             Staged w(ctx_, n_sums * n_elts ? n_sums * n_elts * pw : 1);
             for (std::size_t s = 0; s < n_sums; s++)
                 for (std::size_t i = 0; i < n_elts; i++)
                     plain_to(plains[s][i], w.ptr() + (s * n_elts + i) * pw, pw);
             Check chk = checked(encrypted, n_sums ? n_sums : 1);
-            throw_on(sealhip_evaluator_apply_galois_dot_plain(ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(),
-                                                              raw.data(), std::uint32_t(n_elts), w.ptr(), std::uint32_t(n_sums),
-                                                              o.ptr()));
+            throw_on((rescale ? sealhip_evaluator_apply_galois_dot_plain_rescale : sealhip_evaluator_apply_galois_dot_plain)(
+                ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(), raw.data(), std::uint32_t(n_elts), w.ptr(),
+                std::uint32_t(n_sums), o.ptr()));
             chk.done();
-            scatter(encrypted, o, n_sums, words, destinations);
+            scatter(encrypted, o, n_sums, out_words, destinations, k_out);
             if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
                 for (C &d : destinations)
-                    d.scale() = encrypted.scale() * scale;
+                    d.scale() = encrypted.scale() * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
         }
+
+    public:
         // The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): CKKS rotate_vector's steps; step 0 is the
         // identity; no non-adjacent-form fallback
         template <class C, class P, IfCt<C> = 0>
@@ -902,7 +938,41 @@ namespace sealhip_host
                                      const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                      const std::vector<std::vector<P>> &plains, C &destination)
         {
+            bsgs_plain_internal(encrypted, baby_elts, giant_elts, galois_keys, plains, destination, false);
+        }
+        // ... followed by rescale_to_next, in one call and with one rounding (sealhip_evaluator_apply_galois_bsgs_plain_rescale,
+        // DESIGN.md section 19): CKKS only; the unmerged method's checks, and "end of modulus switching chain reached" at the
+        // last level. The result is one level down with the scale encrypted.scale() * plain.scale / q_{k-1}.
+        template <class C, class P, IfCt<C> = 0>
+        void apply_galois_bsgs_plain_rescale(const C &encrypted, const std::vector<std::uint32_t> &baby_elts,
+                                             const std::vector<std::uint32_t> &giant_elts,
+                                             const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                             const std::vector<std::vector<P>> &plains, C &destination)
+        {
+            bsgs_plain_internal(encrypted, baby_elts, giant_elts, galois_keys, plains, destination, true);
+        }
+        template <class C, class P, IfCt<C> = 0>
+        void rotate_vector_bsgs_plain_rescale(const C &encrypted, const std::vector<int> &baby_steps,
+                                              const std::vector<int> &giant_steps,
+                                              const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                              const std::vector<std::vector<P>> &plains, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            bsgs_plain_internal(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains, destination,
+                                true);
+        }
+
+    private:
+        template <class C, class P>
+        void bsgs_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &baby_elts,
+                                 const std::vector<std::uint32_t> &giant_elts,
+                                 const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                 const std::vector<std::vector<P>> &plains, C &destination, bool rescale)
+        {
             check_galois_operand(encrypted);
+            if (rescale)
+                check_rescale_operand(encrypted);
             const auto raw_keys = [&](const std::vector<std::uint32_t> &elts) {
                 std::vector<const sealhip_kswitch_key *> raw;
                 for (std::uint32_t elt : elts)
@@ -920,22 +990,26 @@ namespace sealhip_host
                 throw std::invalid_argument("plains must hold one row of plaintexts per giant element");
             const double scale = check_dot_plains(plains, n_baby);
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
-            Dev c = dev_in(encrypted, words), o = dev_out(words);
+            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
+            Dev c = dev_in(encrypted, words), o = dev_out(out_words);
             Staged w(ctx_, (n_giant && n_baby) ? n_giant * n_baby * pw : 1);
             for (std::size_t j = 0; j < n_giant; j++)
                 for (std::size_t i = 0; i < n_baby; i++)
                     plain_to(plains[j][i], w.ptr() + (j * n_baby + i) * pw, pw);
             Check chk = checked(encrypted, 1);
-            throw_on(sealhip_evaluator_apply_galois_bsgs_plain(ctx_.get(), std::uint32_t(k), c.ptr(), 1, baby_elts.data(), bk.data(),
-                                                               std::uint32_t(n_baby), giant_elts.data(), gk.data(),
-                                                               std::uint32_t(n_giant), w.ptr(), o.ptr()));
+            throw_on((rescale ? sealhip_evaluator_apply_galois_bsgs_plain_rescale : sealhip_evaluator_apply_galois_bsgs_plain)(
+                ctx_.get(), std::uint32_t(k), c.ptr(), 1, baby_elts.data(), bk.data(), std::uint32_t(n_baby), giant_elts.data(),
+                gk.data(), std::uint32_t(n_giant), w.ptr(), o.ptr()));
             chk.done();
+            const double in_scale = encrypted.scale(); // (the destination may be the operand)
             std::vector<C> one;
-            scatter(encrypted, o, 1, words, one);
+            scatter(encrypted, o, 1, out_words, one, k_out);
             destination = std::move(one[0]);
             if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
-                destination.scale() = encrypted.scale() * scale;
+                destination.scale() = in_scale * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
         }
+
+    public:
         // The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): CKKS rotate_vector's steps; step 0 is the
         // identity; no non-adjacent-form fallback
         template <class C, class P, IfCt<C> = 0>
@@ -1139,6 +1213,39 @@ namespace sealhip_host
                          C &destination)
         {
             dot_product_internal(encrypteds1, encrypteds2, &relin_key, destination);
+        }
+        // ... followed by rescale_to_next, in one call and with one rounding (sealhip_evaluator_dot_product_rescale, DESIGN.md
+        // section 19): CKKS only; dot_product's checks, and "end of modulus switching chain reached" at the last level. The
+        // result has size 2, one level down, with the scale encrypteds1[0].scale() * encrypteds2[0].scale() / q_{k-1}. With
+        // one term it is multiply + relinearize + rescale_to_next.
+        template <class C, IfCt<C> = 0>
+        void dot_product_rescale(const std::vector<C> &encrypteds1, const std::vector<C> &encrypteds2, const KSwitchKeys &relin_key,
+                                 C &destination)
+        {
+            dot_product_internal(encrypteds1, encrypteds2, &relin_key, destination, true);
+        }
+        // relinearize + rescale_to_next in one call and with one rounding (sealhip_evaluator_relinearize_rescale, DESIGN.md
+        // section 19): CKKS only, a size-3 operand in NTT form, relin_keys as relinearize_inplace takes them (index 0 is
+        // read); "end of modulus switching chain reached" at the last level. The result has size 2, one level down, with
+        // the scale encrypted.scale() / q_{k-1}.
+        template <class C, IfCt<C> = 0>
+        void relinearize_rescale(const C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
+        {
+            if (encrypted.size() != 3)
+                throw std::invalid_argument("encrypted size must be 3");
+            check_rescale_operand(encrypted);
+            if (relin_keys.empty() || !relin_keys[0])
+                throw std::invalid_argument("not enough relinearization keys"); // :793-796
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            const double scale = encrypted.scale() / double(ctx_.key_modulus(k - 1));
+            Dev c = dev_in(encrypted, 3 * k * n), o = dev_out(2 * (k - 1) * n);
+            const sealhip_kswitch_key *raw = relin_keys[0]->get();
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_relinearize_rescale(ctx_.get(), std::uint32_t(k), c.ptr(), 3, 3 * k * n, 1, &raw, 1, o.ptr()));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, k - 1);
+            destination.scale() = scale;
         }
 
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
@@ -1562,26 +1669,31 @@ namespace sealhip_host
         Check checked(const DeviceCiphertext &, std::size_t count = 1) { return Check(ctx_, this, count); }
 
         // the n results of a hoisted rotation, back to back in `o`, become the destinations (metadata of the operand)
-        void scatter(const CT &src, Dev &o, std::size_t n, std::size_t words, std::vector<CT> &dst)
+        // (k: the level of the results when it is not the operand's -- the *_rescale methods)
+        void scatter(const CT &src, Dev &o, std::size_t n, std::size_t words, std::vector<CT> &dst, std::size_t k = 0)
         {
             dst.assign(n, src);
+            for (std::size_t i = 0; k && i < n; i++)
+                dst[i].resize_raw(2, k);
             for (std::size_t i = 0; i < n; i++)
                 throw_on(sealhip_memcpy_d2h(ctx_.get(), dst[i].data(), o.ptr() + i * words, words * 8));
         }
-        void scatter(const DeviceCiphertext &src, Dev &o, std::size_t n, std::size_t words, std::vector<DeviceCiphertext> &dst)
+        void scatter(const DeviceCiphertext &src, Dev &o, std::size_t n, std::size_t words, std::vector<DeviceCiphertext> &dst,
+                     std::size_t k = 0)
         {
+            k = k ? k : src.coeff_modulus_size();
             std::vector<DeviceCiphertext> next;
             next.reserve(n);
             for (std::size_t i = 0; i < n; i++)
             {
                 next.emplace_back(ctx_);
                 if (n == 1)
-                    next[i].adopt(o.st->release(), o.st->words(), 2, src.coeff_modulus_size());
+                    next[i].adopt(o.st->release(), o.st->words(), 2, k);
                 else
                 {
                     Staged one(ctx_, words); // (each destination owns a pool block of its own)
                     throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), o.ptr() + i * words, words * 8));
-                    next[i].adopt(one.release(), words, 2, src.coeff_modulus_size());
+                    next[i].adopt(one.release(), words, 2, k);
                 }
                 next[i].copy_meta(src);
             }
@@ -1657,8 +1769,21 @@ namespace sealhip_host
                 throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
         }
 
+        // what every *_rescale method adds to the unmerged method's checks
         template <class C>
-        void dot_product_internal(const std::vector<C> &a, const std::vector<C> &b, const KSwitchKeys *relin_key, C &destination)
+        void check_rescale_operand(const C &encrypted) const
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme"); // (rescale_to_next: evaluator.cpp:1098-1101)
+            if (!encrypted.is_ntt_form())
+                throw std::invalid_argument("CKKS encrypted must be in NTT form");
+            if (encrypted.coeff_modulus_size() < 2)
+                throw std::invalid_argument("end of modulus switching chain reached"); // :1005-1008
+        }
+
+        template <class C>
+        void dot_product_internal(const std::vector<C> &a, const std::vector<C> &b, const KSwitchKeys *relin_key, C &destination,
+                                  bool rescale = false)
         {
             if (a.empty() || a.size() != b.size())
                 throw std::invalid_argument("encrypteds1 and encrypteds2 must hold the same, non-zero number of terms");
@@ -1672,8 +1797,11 @@ namespace sealhip_host
                 if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && (a[i].scale() != a[0].scale() || b[i].scale() != b[0].scale()))
                     throw std::invalid_argument("scale mismatch");
             }
+            if (rescale)
+                check_rescale_operand(a[0]);
             const std::size_t k = a[0].coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, size = relin_key ? 2 : 3;
-            const double scale = a[0].scale() * b[0].scale();
+            const std::size_t k_out = rescale ? k - 1 : k;
+            const double scale = a[0].scale() * b[0].scale() / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
             std::vector<Dev> staged;
             std::vector<const std::uint64_t *> pa, pb;
             staged.reserve(2 * a.size());
@@ -1684,14 +1812,15 @@ namespace sealhip_host
                 staged.push_back(dev_in(b[i], words));
                 pb.push_back(staged.back().ptr());
             }
-            Dev o = dev_out(size * k * n);
+            Dev o = dev_out(size * k_out * n);
             const sealhip_kswitch_key *raw = relin_key ? relin_key->get() : nullptr;
             Check chk = checked(a[0]);
-            throw_on(sealhip_evaluator_dot_product(ctx_.get(), std::uint32_t(k), pa.data(), pb.data(), std::uint32_t(a.size()), 1,
-                                                   relin_key ? &raw : nullptr, relin_key ? 1u : 0u, o.ptr()));
+            throw_on((rescale ? sealhip_evaluator_dot_product_rescale : sealhip_evaluator_dot_product)(
+                ctx_.get(), std::uint32_t(k), pa.data(), pb.data(), std::uint32_t(a.size()), 1, relin_key ? &raw : nullptr,
+                relin_key ? 1u : 0u, o.ptr()));
             chk.done();
             take_meta(destination, a[0]); // (every term is staged or enqueued by now: the destination may be one of them)
-            commit(destination, o, size, k);
+            commit(destination, o, size, k_out);
             if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
                 destination.scale() = scale;
         }

@@ -141,6 +141,16 @@ SYMBOLS = {
                                                    C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_dot_product_max_terms": [_vp, _u32, C.POINTER(C.c_uint64)],
     "sealhip_evaluator_dot_product": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_relinearize_rescale": [_vp, _u32, _vp, _u32, _sz, _sz, C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_dot_product_rescale": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_apply_galois_dot_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32,
+                                                         _vp],
+    "sealhip_evaluator_rotate_vector_dot_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32),
+                                                          C.POINTER(_vp), _u32, _vp, _u32, _vp],
+    "sealhip_evaluator_apply_galois_bsgs_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32,
+                                                          C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
+    "sealhip_evaluator_rotate_vector_bsgs_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_i32), _u32,
+                                                           C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -941,7 +951,8 @@ class Evaluator:
         _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts),
                                                           _ptr(out)))
 
-    def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out):
+    def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out,
+                               _entry="sealhip_evaluator_apply_galois_dot_plain"):
         """Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):
         out[s] = sum_i plains[s][i] * sigma_{elts[i]}(ct) with one decomposition of c_1 and one mod-down per sum. keys[i] is
         the KSwitchKeys of elts[i] and may be None for element 1. plains: n_sums x len(elts) x n_key x N words in key-level
@@ -949,10 +960,10 @@ class Evaluator:
         elts = [int(g) for g in elts]
         ea = (_u32 * max(1, len(elts)))(*elts)
         ka = (_vp * max(1, len(elts)))(*[key.handle if key is not None else None for key in keys])
-        _check(lib().sealhip_evaluator_apply_galois_dot_plain(self.ctx.handle, k, _ptr(ct), count, ea, ka, len(elts),
-                                                              _ptr(plains), n_sums, _ptr(out)))
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, ea, ka, len(elts), _ptr(plains), n_sums, _ptr(out)))
 
-    def rotate_vector_dot_plain(self, ct, k, count, steps, galois_keys, plains, n_sums, out):
+    def rotate_vector_dot_plain(self, ct, k, count, steps, galois_keys, plains, n_sums, out,
+                                _entry="sealhip_evaluator_rotate_vector_dot_plain"):
         """The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): step 0 is the identity and needs no key; a
         step without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
         steps = [int(st) for st in steps]
@@ -960,10 +971,11 @@ class Evaluator:
         sa = (_i32 * max(1, len(steps)))(*steps)
         ea = (_u32 * max(1, len(elts)))(*elts)
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(lib().sealhip_evaluator_rotate_vector_dot_plain(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka,
-                                                               len(elts), _ptr(plains), n_sums, _ptr(out)))
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts), _ptr(plains),
+                                      n_sums, _ptr(out)))
 
-    def apply_galois_bsgs_plain(self, ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out):
+    def apply_galois_bsgs_plain(self, ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out,
+                                _entry="sealhip_evaluator_apply_galois_bsgs_plain"):
         """Baby-step/giant-step matrix-vector product (sealhip_evaluator_apply_galois_bsgs_plain):
         out = sum_j sigma_{giant_elts[j]}( sum_i plains[j][i] * sigma_{baby_elts[i]}(ct) ), the giant steps accumulated in the
         extended basis and ONE full mod-down. A key may be None for element 1 on either axis. plains: len(giant_elts) x
@@ -973,10 +985,11 @@ class Evaluator:
         bk = (_vp * max(1, len(baby_elts)))(*[key.handle if key is not None else None for key in baby_keys])
         ga = (_u32 * max(1, len(giant_elts)))(*giant_elts)
         gk = (_vp * max(1, len(giant_elts)))(*[key.handle if key is not None else None for key in giant_keys])
-        _check(lib().sealhip_evaluator_apply_galois_bsgs_plain(self.ctx.handle, k, _ptr(ct), count, ba, bk, len(baby_elts), ga,
-                                                               gk, len(giant_elts), _ptr(plains), _ptr(out)))
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, ba, bk, len(baby_elts), ga, gk, len(giant_elts),
+                                      _ptr(plains), _ptr(out)))
 
-    def rotate_vector_bsgs_plain(self, ct, k, count, baby_steps, giant_steps, galois_keys, plains, out):
+    def rotate_vector_bsgs_plain(self, ct, k, count, baby_steps, giant_steps, galois_keys, plains, out,
+                                 _entry="sealhip_evaluator_rotate_vector_bsgs_plain"):
         """The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): step 0 is the identity and needs no key; a
         step of either axis without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
         baby_steps, giant_steps = [int(st) for st in baby_steps], [int(st) for st in giant_steps]
@@ -985,8 +998,8 @@ class Evaluator:
         gs = (_i32 * max(1, len(giant_steps)))(*giant_steps)
         ea = (_u32 * max(1, len(elts)))(*elts)
         ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(lib().sealhip_evaluator_rotate_vector_bsgs_plain(self.ctx.handle, k, _ptr(ct), count, bs, len(baby_steps), gs,
-                                                                len(giant_steps), ea, ka, len(elts), _ptr(plains), _ptr(out)))
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, bs, len(baby_steps), gs, len(giant_steps), ea, ka,
+                                      len(elts), _ptr(plains), _ptr(out)))
 
     def dot_product_max_terms(self, k):
         """Terms one dot_product call admits at level k (sealhip_evaluator_dot_product_max_terms): for BFV as many as keep the
@@ -995,7 +1008,7 @@ class Evaluator:
         _check(lib().sealhip_evaluator_dot_product_max_terms(self.ctx.handle, k, C.byref(n)))
         return int(n.value)
 
-    def dot_product(self, a_terms, b_terms, k, count, out, relin_keys=None):
+    def dot_product(self, a_terms, b_terms, k, count, out, relin_keys=None, _entry="sealhip_evaluator_dot_product"):
         """Ciphertext inner product (sealhip_evaluator_dot_product): out = sum_i a_terms[i] * b_terms[i]
         over device batches count x 2 x k x N of size-2 ciphertexts, the tensor products summed in NTT form, one floor (BFV
         STRICT) and, with relin_keys (a list of KSwitchKeys, index 0 is read), one relinearization. out: count x 3 x k x N
@@ -1007,8 +1020,42 @@ class Evaluator:
         keys = None
         if relin_keys is not None:
             keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
-        _check(lib().sealhip_evaluator_dot_product(self.ctx.handle, k, pa, pb, len(a_terms), count, keys,
-                                                   len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, pa, pb, len(a_terms), count, keys,
+                                      len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+
+    # ---- the key switch's mod-down merged with rescale_to_next: CKKS, operands at level k >= 2, every
+    # out at level k - 1; the words are those of tests/ks_rescale_ref.py, the error that of the unmerged method + rescale_to_next
+    def relinearize_rescale(self, ct, k, count, relin_keys, out, item_stride=0):
+        """relinearize + rescale_to_next in one call (sealhip_evaluator_relinearize_rescale): ct holds count size-3 ciphertexts
+        item_stride words apart (0 = back to back) and is not modified; out: count x 2 x (k-1) x N."""
+        keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        _check(lib().sealhip_evaluator_relinearize_rescale(self.ctx.handle, k, _ptr(ct), 3, item_stride or 3 * k * self.ctx.n,
+                                                           count, keys, len(relin_keys), _ptr(out)))
+
+    def dot_product_rescale(self, a_terms, b_terms, k, count, out, relin_keys):
+        """dot_product with keys + rescale_to_next in one call (sealhip_evaluator_dot_product_rescale); with one term
+        multiply + relinearize + rescale_to_next. out: count x 2 x (k-1) x N."""
+        self.dot_product(a_terms, b_terms, k, count, out, relin_keys, _entry="sealhip_evaluator_dot_product_rescale")
+
+    def apply_galois_dot_plain_rescale(self, ct, k, count, elts, keys, plains, n_sums, out):
+        """apply_galois_dot_plain + rescale_to_next in one call; out: n_sums x count x 2 x (k-1) x N."""
+        self.apply_galois_dot_plain(ct, k, count, elts, keys, plains, n_sums, out,
+                                    _entry="sealhip_evaluator_apply_galois_dot_plain_rescale")
+
+    def rotate_vector_dot_plain_rescale(self, ct, k, count, steps, galois_keys, plains, n_sums, out):
+        """rotate_vector_dot_plain + rescale_to_next in one call; out: n_sums x count x 2 x (k-1) x N."""
+        self.rotate_vector_dot_plain(ct, k, count, steps, galois_keys, plains, n_sums, out,
+                                     _entry="sealhip_evaluator_rotate_vector_dot_plain_rescale")
+
+    def apply_galois_bsgs_plain_rescale(self, ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out):
+        """apply_galois_bsgs_plain + rescale_to_next in one call (the final finish is merged); out: count x 2 x (k-1) x N."""
+        self.apply_galois_bsgs_plain(ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out,
+                                     _entry="sealhip_evaluator_apply_galois_bsgs_plain_rescale")
+
+    def rotate_vector_bsgs_plain_rescale(self, ct, k, count, baby_steps, giant_steps, galois_keys, plains, out):
+        """rotate_vector_bsgs_plain + rescale_to_next in one call; out: count x 2 x (k-1) x N."""
+        self.rotate_vector_bsgs_plain(ct, k, count, baby_steps, giant_steps, galois_keys, plains, out,
+                                      _entry="sealhip_evaluator_rotate_vector_bsgs_plain_rescale")
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

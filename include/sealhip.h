@@ -560,6 +560,58 @@ long sealhip_evaluator_dot_product(sealhip_context *ctx, uint32_t k, const uint6
                                    const uint64_t *const *b_terms, uint32_t n_terms, size_t count,
                                    const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out);
 
+/* The key switch's mod-down merged with rescale_to_next. CKKS only, both modes. Each *_rescale entry
+   is its unmerged sibling followed by sealhip_evaluator_rescale_to_next in ONE call and with ONE rounding: where the sibling
+   finishes with floor((acc + P/2) / P) added to base and the rescale divides that by q_{k-1}, the merged finish computes
+       out = floor( (P * base + acc + floor(D / 2)) / D ),   D = P * q_{k-1},
+   row by row over the k - 1 remaining primes, dropping {q_{k-1}, p_0 .. p_{nsp-1}} in one step with an exact integer
+   quotient: 2 (nsp + k) row transforms per ciphertext instead of 2 (nsp + 2 k), and the level-k result is never formed.
+   These are not the words of the composition (it rounds twice); what defines them is the restatement over the oracle in
+   tests/ks_rescale_ref.py (finish_rescale and the per-operation functions named below). They decrypt with the error of the
+   composition. When an operation forms no key-switch term (every Galois element is 1) the words are those of
+   rescale_to_next of the sibling's result.
+   k is the level of the operands, 2 <= k <= first level; every output is at level k - 1, compact, device memory, and must
+   overlap no input. The result's scale is the sibling's divided by q_{k-1}.
+   Checks, in this order: NULL pointers -> E_POINTER; then, also on host-only contexts, a BFV context ("CKKS only"), k < 2
+   or above the first level, (relinearize_rescale) size != 3 or ct_item_stride < 3 k N, the sibling's own argument errors,
+   out overlapping an input -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only context ->
+   COR_E_INVALIDOPERATION. Every entry runs on the calling thread's lane, stages nothing from the host, synchronises
+   nothing and is capturable under its sibling's conditions. With a transparency sink: one flag per output ciphertext, in
+   output order, written by the kernel that stores the result.
+
+   relinearize_rescale (ks_rescale_ref.relinearize_rescale): ct holds count size-3 ciphertexts, ct_item_stride >= 3 k N words
+   apart, and is not modified; relin_keys as for sealhip_evaluator_relinearize (required; only index 0 is read);
+   out is count x 2 x (k-1) x N.
+   dot_product_rescale (ks_rescale_ref.dot_product_rescale): the arguments of sealhip_evaluator_dot_product with relin_keys
+   required; out is count x 2 x (k-1) x N. With one term it is multiply + relinearize + rescale_to_next in one call.
+   apply_galois_dot_plain_rescale / rotate_vector_dot_plain_rescale (ks_rescale_ref.dot_plain_rescale): the arguments of the
+   unmerged entries; out is n_sums x count x 2 x (k-1) x N.
+   apply_galois_bsgs_plain_rescale / rotate_vector_bsgs_plain_rescale (ks_rescale_ref.bsgs_plain_rescale): the arguments of
+   the unmerged entries; only the final finish is merged, the giant steps' half mod-downs stay; out is count x 2 x (k-1) x N. */
+long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
+                                           size_t ct_item_stride, size_t count, const sealhip_kswitch_key *const *relin_keys,
+                                           uint32_t n_relin_keys, uint64_t *out);
+long sealhip_evaluator_dot_product_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *const *a_terms,
+                                           const uint64_t *const *b_terms, uint32_t n_terms, size_t count,
+                                           const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out);
+long sealhip_evaluator_apply_galois_dot_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                      const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                                      uint32_t n_elts, const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out);
+long sealhip_evaluator_rotate_vector_dot_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                       const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                                                       const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                       const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out);
+long sealhip_evaluator_apply_galois_bsgs_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                       const uint32_t *baby_elts, const sealhip_kswitch_key *const *baby_keys,
+                                                       uint32_t n_baby, const uint32_t *giant_elts,
+                                                       const sealhip_kswitch_key *const *giant_keys, uint32_t n_giant,
+                                                       const uint64_t *plain_ntt, uint64_t *out);
+long sealhip_evaluator_rotate_vector_bsgs_plain_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                                        const int32_t *baby_steps, uint32_t n_baby, const int32_t *giant_steps,
+                                                        uint32_t n_giant, const uint32_t *galois_elts,
+                                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                                        const uint64_t *plain_ntt, uint64_t *out);
+
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
    of the ciphertext (is_ntt_form). sk_powers_ntt = the Decryptor's secret_key_array_: (size-1) polynomials s, s^2, ...
