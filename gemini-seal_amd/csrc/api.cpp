@@ -2346,6 +2346,202 @@ long sealhip_evaluator_dot_product_rescale(sealhip_context *ctx, uint32_t k, con
     return dot_product_entry(ctx, k, a_terms, b_terms, n_terms, count, relin_keys, n_relin_keys, out, true);
 }
 
+/* ------------------------------------------------------------------ polynomial evaluation */
+namespace
+{
+    bool words_overlap(const u64 *a, std::size_t a_words, const u64 *b, std::size_t b_words)
+    {
+        return a < b + b_words && b < a + a_words;
+    }
+} // namespace
+
+long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, const uint64_t *const *terms, uint32_t n_terms,
+                                          uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
+                                          uint32_t n_sums, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(weights);
+    REQUIRE_PTR(out);
+    if (n_terms)
+    {
+        REQUIRE_PTR(terms);
+        for (uint32_t i = 0; i < n_terms; i++)
+            REQUIRE_PTR(terms[i]);
+    }
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (size < 2 || size > 16) // SEAL_CIPHERTEXT_SIZE_MIN / _MAX (util/defines.h:56-57), as multiply and relinearize check
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        if ((n_terms == 0 || n_sums == 0) && count > 0)
+            throw std::invalid_argument("the term list and the sums must not be empty");
+        const std::size_t item = static_cast<std::size_t>(size) * k * h.n;
+        const u64 *o = reinterpret_cast<const u64 *>(out), *w = reinterpret_cast<const u64 *>(weights),
+                  *kc = reinterpret_cast<const u64 *>(constant);
+        const std::size_t out_words = n_sums * count * item;
+        for (uint32_t i = 0; i < n_terms; i++)
+            if (words_overlap(o, out_words, reinterpret_cast<const u64 *>(terms[i]), count * item))
+                throw std::invalid_argument("out must not overlap a term");
+        if (words_overlap(o, out_words, w, static_cast<std::size_t>(n_sums) * n_terms * k))
+            throw std::invalid_argument("out must not overlap weights");
+        if (kc && words_overlap(o, out_words, kc, static_cast<std::size_t>(n_sums) * k))
+            throw std::invalid_argument("out must not overlap constant");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, static_cast<size_t>(n_sums) * count);
+        sink.begin();
+        op_linear_combination(e, static_cast<int>(k), reinterpret_cast<const u64 *const *>(terms), n_terms, static_cast<int>(size),
+                              count, w, kc, n_sums, reinterpret_cast<u64 *>(out));
+    });
+}
+
+/* Paterson-Stockmeyer over the two entries above: the power basis with multiply + relinearize (the launches of
+   do_multiply_many's products), every inner sum in ONE linear combination, the outer sum in ONE dot_product. Temporaries
+   are blocks of the context's pool, taken and released in stream order on the calling thread's lane: nothing here
+   synchronises. */
+long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                           const uint64_t *coeffs, uint32_t degree, uint32_t n_baby,
+                                           const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(coeffs);
+    REQUIRE_PTR(out);
+    if (relin_keys && n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (h.scheme != 1)
+            throw std::invalid_argument("polynomial evaluation is BFV only (CKKS: sealhip_evaluator_linear_combination)");
+        if (!h.mode_strict)
+            throw std::invalid_argument("polynomial evaluation of BFV ciphertexts needs a STRICT context");
+        for (std::size_t i = 0; i <= degree; i++)
+            if (coeffs[i] >= h.t)
+                throw std::invalid_argument("a coefficient is not below the plain modulus");
+        std::size_t d = degree;
+        while (d > 0 && coeffs[d] == 0)
+            d--;
+        if (d < 1)
+            throw std::invalid_argument("a constant polynomial is not an operation on a ciphertext");
+        if (n_baby == 1 || n_baby > d + 1)
+            throw std::invalid_argument("n_baby must be 0 (automatic) or between 2 and the degree plus one");
+        std::size_t m = n_baby;
+        if (m == 0)
+            for (m = 1; m * m < d + 1;)
+                m++; // ceil(sqrt(d + 1))
+        const std::size_t g = (d + m) / m; // ceil((d + 1) / m)
+        const std::size_t n_terms = std::min(m, d + 1) - 1, ms = n_terms + 1;
+        // inner sum j is identically zero when all of c_{jm} .. c_{jm + m - 1} are
+        std::vector<u64> padded(g * ms, 0);
+        std::vector<char> live(g, 0);
+        for (std::size_t c = 0; c <= d; c++)
+        {
+            padded[c] = coeffs[c];
+            if (coeffs[c])
+                live[c / ms] = 1;
+        }
+        std::vector<std::size_t> outer; // the giant steps j >= 1 whose inner sum survives
+        for (std::size_t j = 1; j < g; j++)
+            if (live[j])
+                outer.push_back(j);
+        if (outer.size() > dot_product_max_terms(h, static_cast<int>(k)))
+            throw std::invalid_argument("too many giant steps for one floor at this level (sealhip_evaluator_dot_product_max_terms)");
+        if (d >= 2)
+        {
+            if (!relin_keys || n_relin_keys == 0)
+                throw std::invalid_argument("not enough relinearization keys");
+            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+            if (relin_keys[0]->key.n_digits < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n, two_words = count * 2 * poly, two = two_words * sizeof(u64);
+        const u64 *x = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, two_words, x, two_words))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        // Temporaries are blocks of the context's pool (pool.cpp): taken and released in stream order on this lane, no
+        // synchronisation and, once the pool is warm, no allocator call. (Not hipMallocAsync: DESIGN.md section 11 -- in a
+        // sequence of calls its blocks gave wrong words here too, each call alone being right.)
+        std::vector<void *> owned;
+        struct Cleanup
+        {
+            Engine &e;
+            std::vector<void *> &v;
+            ~Cleanup()
+            {
+                for (void *p : v)
+                    pool_release(e, p);
+            }
+        } cleanup{ e, owned };
+        auto temp = [&](std::size_t bytes) {
+            void *p = pool_alloc(e, bytes);
+            owned.push_back(p);
+            return static_cast<u64 *>(p);
+        };
+        u64 *wide = nullptr; // the size-3 scratch of the products, reused in stream order
+        auto product = [&](const u64 *a, const u64 *b) {
+            if (!wide)
+                wide = temp(count * 3 * poly * sizeof(u64));
+            u64 *narrow = temp(two);
+            // (multiply(x, x) and square(x) give the same canonical residues, evaluator.cpp:1228-1235)
+            do_multiply(e, k, a, 2, b, 2, count, wide);
+            do_relinearize(e, k, wide, 3, count, relin_keys, n_relin_keys);
+            check(launch_copy_rows(e, wide, 3 * poly, narrow, 2 * poly, count, static_cast<int>(2 * k)), "resize");
+            return static_cast<const u64 *>(narrow);
+        };
+        // baby powers B_1 .. B_min(m, d): B_e = B_ceil(e/2) * B_floor(e/2)
+        const std::size_t n_powers = std::min(m, d);
+        std::vector<const u64 *> B(n_powers + 1, nullptr);
+        B[1] = x;
+        for (std::size_t p = 2; p <= n_powers; p++)
+            B[p] = product(B[(p + 1) / 2], B[p / 2]);
+        // giant powers G_1 = B_m, G_j = G_ceil(j/2) * G_floor(j/2): those a surviving term needs, and what they are built from
+        std::vector<const u64 *> G(g, nullptr);
+        std::vector<char> needed(g, 0);
+        for (std::size_t j : outer)
+            needed[j] = 1;
+        for (std::size_t j = g; j-- > 2;)
+            if (needed[j])
+                needed[(j + 1) / 2] = needed[j / 2] = 1;
+        if (g > 1)
+            G[1] = B[m];
+        for (std::size_t j = 2; j < g; j++)
+            if (needed[j])
+                G[j] = product(G[(j + 1) / 2], G[j / 2]);
+        // the tables of the inner sums and the inner sums themselves: I_0 goes straight to out when there is no outer sum
+        u64 *W = temp(g * n_terms * k * sizeof(u64)), *K = temp(g * k * sizeof(u64));
+        check(launch_poly_tables(e, static_cast<int>(k), padded.data(), padded.size(), ms, W, K), "poly_tables");
+        if (g == 1)
+        {
+            sink.begin();
+            op_linear_combination(e, static_cast<int>(k), B.data() + 1, n_terms, 2, count, W, K, 1, o);
+            return;
+        }
+        u64 *I = temp(g * two);
+        op_linear_combination(e, static_cast<int>(k), B.data() + 1, n_terms, 2, count, W, K, g, I);
+        // (g > 1 means d >= m: the inner sum that holds c_d is not zero, so there is an outer sum)
+        std::vector<const u64 *> ga, ib;
+        for (std::size_t j : outer)
+        {
+            ga.push_back(G[j]);
+            ib.push_back(I + j * two_words);
+        }
+        u64 *D = temp(two);
+        op_dot_product(e, static_cast<int>(k), ga.data(), ib.data(), outer.size(), count, &relin_keys[0]->key, D);
+        check(launch_ct_linear(e, CtLinearOp::Add, I, 2, D, 2, 0, o, count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)), "add");
+        sink.read_pass(o, 2, poly, count);
+    });
+}
+
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
 
 long sealhip_decryptor_dot_product_ct_sk(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

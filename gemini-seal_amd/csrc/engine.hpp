@@ -505,6 +505,28 @@ namespace sealhip
     hipError_t launch_tensor_dot(const Engine &e, const DotTerms &terms, std::size_t a_stride, std::size_t b_stride, u64 *out01,
                                  std::size_t out01_stride, u64 *out2, std::size_t out2_stride, std::size_t count,
                                  const RowMap &map, bool reduce_on_load, bool add_partial);
+    // Linear combinations of ciphertexts with per-prime scalar weights (poly.hip lincomb_kernel):
+    // out[s] = sum_t w[s][t] * x[t] (+ constant[s] on polynomial 0) for s < n_sums <= kLinTile over a group of up to kLinGroup
+    // terms. x[t]: items x_stride words apart, `size` polynomials of map.rows rows each. w points at the weight of (sum 0,
+    // term 0, row 0): rows are adjacent, terms map.rows words apart, sums w_sum_stride words apart. constant (or null):
+    // n_sums x map.rows words; const_mode 1 adds it at coefficient 0 (coefficient form), 2 at every coefficient (NTT form).
+    // out: sums out_sum_stride words apart, items x_stride words apart. add_partial: the canonical sums already in out are
+    // added in. The transparency sink, when armed, gets polynomials 1.. of (sum s, item c) at flag s * flag_sum_stride + c.
+    constexpr int kLinGroup = bounds::kLinGroupTerms, kLinTile = bounds::kLinTileSums;
+    struct LinTerms
+    {
+        const u64 *x[kLinGroup];
+        int n;
+    };
+    hipError_t launch_lincomb(const Engine &e, const LinTerms &terms, int size, std::size_t x_stride, const u64 *w,
+                              std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
+                              int n_sums, std::size_t count, const RowMap &map, bool add_partial, std::size_t flag_sum_stride);
+    // The weight and constant tables of a polynomial's inner sums (sealhip_evaluator_evaluate_polynomial): coefficient
+    // e = j * ms + i (j < n_sums, i < ms) of the zero-padded list becomes constant[j][r] = the word
+    // multiply_add_plain_with_scaling_variant adds at coefficient 0 for the one-coefficient plaintext c_e (i == 0), or
+    // w[j][i - 1][r] = (c_e - t [c_e >= (t + 1) / 2]) mod q_r (i >= 1). The coefficients travel in kernel arguments.
+    hipError_t launch_poly_tables(const Engine &e, int k, const u64 *coeffs, std::size_t n_coeffs, std::size_t ms, u64 *w,
+                                  u64 *constant);
     hipError_t launch_copy_rows(const Engine &e, const u64 *src, std::size_t src_poly_stride, u64 *dst,
                                 std::size_t dst_poly_stride, std::size_t npolys, int rows);
 
@@ -756,6 +778,11 @@ namespace sealhip
                         const KSwitchKey *key, u64 *out, bool rescale = false);
     // terms a level admits (BFV: while the floor's Shenoy-Kumaresan conversion stays exact; CKKS: 2^32 - 1); host constants only
     std::uint64_t dot_product_max_terms(Engine &e, int k);
+    // out[s][count][size][k][N] = sum_i weights[s][i][r] * terms[i] (+ constant[s][r] on polynomial 0: at coefficient 0 for BFV,
+    // at every coefficient for CKKS), DESIGN.md section 20. terms[i]: [count][size][k][N], only read; weights
+    // [n_sums][n_terms][k] and constant [n_sums][k] (or null) are device memory.
+    void op_linear_combination(Engine &e, int k, const u64 *const *terms, std::size_t n_terms, int size, std::size_t count,
+                               const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out);
     // Evaluator::square as its own path (evaluator.cpp:560-770): the operand is lifted / transformed once
     void op_bfv_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);
     void op_ckks_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);

@@ -513,6 +513,24 @@ namespace sealhip
         static_assert(dot_group_admits(kDotGroupTerms, kDotAccOperandBits), "16 terms of 61-bit operands fit 128 bits");
         static_assert(dot_group_admits(31, kDotAccOperandBits) && !dot_group_admits(32, kDotAccOperandBits),
                       "this (conservative) count admits 31 terms at 61 bits: the group of 16 leaves almost a factor two");
+        // The linear combination's sums (poly.hip lincomb_kernel): one launch accumulates a group of
+        // `terms` products weight * word, each below 2^(2 bits) for operands and weights below 2^bits, then adds the canonical
+        // partial sum of the groups before it and the constant (each below 2^bits), and reduces once. It must stay below 2^128.
+        constexpr bool lincomb_group_admits(int terms, int bits)
+        {
+            if (terms < 1 || bits < 1 || bits > 63)
+                return false;
+            // terms 2^(2 bits) + 2 2^bits <= 2^128 - 1  <=>  (terms 2^bits + 2) 2^bits < 2^128  <=>  terms 2^bits + 2 <= 2^shift
+            const int shift = 128 - bits;
+            if (shift <= bits)
+                return false;
+            return (static_cast<u128>(terms) << bits) + 2 <= (static_cast<u128>(1) << shift);
+        }
+        constexpr int kLinGroupTerms = 16; // terms per launch of lincomb_kernel
+        constexpr int kLinTileSums = 4;    // sums per launch (every sum has its own pair of 128-bit accumulators)
+        static_assert(lincomb_group_admits(kLinGroupTerms, kDotAccOperandBits), "16 products of 61-bit words fit 128 bits");
+        static_assert(lincomb_group_admits(63, kDotAccOperandBits) && !lincomb_group_admits(64, kDotAccOperandBits),
+                      "this (conservative) count admits 63 terms at 61 bits: the group of 16 leaves almost a factor four");
 
         // =====================================================================================================
         // 9. The merged mod-down and rescale's conversion sum (keyswitch.hip ks_moddown_rescale_pre_kernel, DESIGN.md section

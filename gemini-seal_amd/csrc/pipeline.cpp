@@ -988,6 +988,42 @@ namespace sealhip
     }
 
     // ------------------------------------------------------------------------------------------
+    // Linear combinations with scalar weights: out_s = sum_i W[s][i] * X_i (+ K[s] on c_0)
+    // ------------------------------------------------------------------------------------------
+    // lincomb_kernel reads the operands where they are and writes the sums where they belong: nothing comes from the arena.
+    // Sums go in tiles of kLinTile, terms in groups of kLinGroup; a later group adds the canonical partial sum in, and the
+    // last group adds the constant and notes the transparency flags (sum-major, as the output is).
+    void op_linear_combination(Engine &e, int k, const u64 *const *terms, std::size_t n_terms, int size, std::size_t count,
+                               const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("the linear combination needs a ciphertext level");
+        if (n_terms == 0 || n_sums == 0 || size < 2)
+            throw std::invalid_argument("an empty linear combination");
+        LevelTools &lt = e.level(k);
+        const std::size_t item = static_cast<std::size_t>(size) * k * e.n;
+        if (n_terms > static_cast<std::size_t>(kLinGroup))
+            log_chunk(e, n_terms, kLinGroup); // (the term split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        for_chunks(e, count, 0, 0, [&](std::size_t off, std::size_t m) {
+            for (std::size_t s0 = 0; s0 < n_sums; s0 += kLinTile)
+                for (std::size_t g0 = 0; g0 < n_terms; g0 += kLinGroup)
+                {
+                    LinTerms group{};
+                    group.n = static_cast<int>(std::min<std::size_t>(kLinGroup, n_terms - g0));
+                    for (int t = 0; t < group.n; t++)
+                        group.x[t] = terms[g0 + t] + off * item;
+                    const bool last = g0 + kLinGroup >= n_terms; // (only the last group's stores are the result's words)
+                    SinkArm arm(e, last ? sink_at(e, s0 * count + off) : nullptr);
+                    check(launch_lincomb(e, group, size, item, weights + (s0 * n_terms + g0) * k, n_terms * k,
+                                         last && constant ? constant + s0 * k : nullptr, e.scheme == 2 ? 2 : 1,
+                                         out + (s0 * count + off) * item, count * item,
+                                         static_cast<int>(std::min<std::size_t>(kLinTile, n_sums - s0)), m, lt.map_q, g0 > 0, count),
+                          "lincomb");
+                }
+        });
+    }
+
+    // ------------------------------------------------------------------------------------------
     // mod_switch_scale_to_next (evaluator.cpp:829-892): BFV mod_switch_to_next / CKKS rescale_to_next
     // ------------------------------------------------------------------------------------------
     namespace

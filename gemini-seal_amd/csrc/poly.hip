@@ -3,6 +3,8 @@
 // All of these are pure HBM streaming: 16-byte loads/stores, two coefficients per lane.
 #include "engine.hpp"
 
+#include <algorithm>
+
 namespace sealhip
 {
     namespace
@@ -228,6 +230,139 @@ namespace sealhip
                 *reinterpret_cast<ulonglong2 *>(po0 + poly_words) = c1;
                 *reinterpret_cast<ulonglong2 *>(po2) = c2;
                 note_nonzero(tflags, item, c1.x | c1.y | c2.x | c2.y);
+            }
+        }
+
+        // Linear combinations of ciphertexts: out_s = sum over the group's terms of w[s][t] * x_t for the
+        // S sums of a tile, one lane per coefficient pair of one row of one polynomial of one item. Each operand pair is loaded
+        // ONCE and accumulated into every sum as plain 128-bit integers (ntt_bounds.hpp lincomb_group_admits: a group of
+        // canonical operands and weights, the partial sum and the constant cannot wrap); every output word is reduced once,
+        // so it is the canonical residue of the composition of scalar products and modular additions. The next term's loads
+        // are issued before the current term is accumulated. The weights of a row are the same for every lane of a block that
+        // does not straddle rows: the kernel then derives the row from the block's first pair, which keeps the row, the prime's
+        // constants and the weights in scalar registers (lincomb_lane is instantiated once per case).
+        template <int S>
+        __device__ __forceinline__ void lincomb_lane(const LinTerms &terms, std::size_t xo, const u64 *__restrict__ wr, int k,
+                                                     std::size_t w_sum_stride, const u64 *__restrict__ kr, bool k_x, bool k_y,
+                                                     u64 p, u64 cr0, u64 cr1, u64 *po, std::size_t out_sum_stride, int add_partial,
+                                                     unsigned *tflags, std::size_t flag_sum_stride, std::size_t item)
+        {
+            u64 lo[S][2] = {}, hi[S][2] = {};
+            ulonglong2 next = *reinterpret_cast<const ulonglong2 *>(terms.x[0] + xo);
+            for (int t = 0; t < terms.n; t++)
+            {
+                const ulonglong2 v = next;
+                if (t + 1 < terms.n)
+                    next = *reinterpret_cast<const ulonglong2 *>(terms.x[t + 1] + xo);
+                const u64 *wt = wr + static_cast<std::size_t>(t) * k;
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                {
+                    const u64 ws = wt[s * w_sum_stride];
+                    mac128(lo[s][0], hi[s][0], v.x, ws);
+                    mac128(lo[s][1], hi[s][1], v.y, ws);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < S; s++)
+            {
+                u64 *ps = po + s * out_sum_stride;
+                if (add_partial)
+                {
+                    const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(ps);
+                    dot_add_word(lo[s][0], hi[s][0], q.x), dot_add_word(lo[s][1], hi[s][1], q.y);
+                }
+                if (kr != nullptr)
+                {
+                    const u64 kv = kr[static_cast<std::size_t>(s) * k];
+                    dot_add_word(lo[s][0], hi[s][0], k_x ? kv : 0), dot_add_word(lo[s][1], hi[s][1], k_y ? kv : 0);
+                }
+                ulonglong2 c;
+                c.x = barrett_reduce_128(lo[s][0], hi[s][0], p, cr0, cr1);
+                c.y = barrett_reduce_128(lo[s][1], hi[s][1], p, cr0, cr1);
+                *reinterpret_cast<ulonglong2 *>(ps) = c;
+                if (tflags != nullptr)
+                    note_nonzero(tflags + s * flag_sum_stride, item, c.x | c.y);
+            }
+        }
+        template <int S>
+        __global__ __launch_bounds__(kThreads) void lincomb_kernel(LinTerms terms, std::size_t x_stride, const u64 *__restrict__ w,
+                                                                   std::size_t w_sum_stride, const u64 *__restrict__ constant,
+                                                                   int const_mode, u64 *out, std::size_t out_sum_stride,
+                                                                   const PrimeDev *__restrict__ primes, RowMap map, int logn,
+                                                                   std::size_t npairs_per_item, std::size_t count,
+                                                                   unsigned *tflags, std::size_t flag_sum_stride, int add_partial)
+        {
+            const std::size_t total = npairs_per_item * count;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t nmask = (static_cast<std::size_t>(1) << logn) - 1;
+            const int k = map.rows;
+            // a row is 2^(logn - 1) pairs: from kThreads pairs per row on, a block covers pairs of ONE row of one item
+            const bool block_in_row = (static_cast<std::size_t>(1) << logn) >= 2 * static_cast<std::size_t>(kThreads);
+            for (std::size_t base = blockIdx.x * static_cast<std::size_t>(blockDim.x); base < total; base += stride)
+            {
+                const std::size_t i = base + threadIdx.x;
+                if (i >= total)
+                    continue;
+                if (block_in_row)
+                {
+                    const std::size_t item = base / npairs_per_item; // (uniform: what the block's first pair says)
+                    const std::size_t row = (2 * (base - item * npairs_per_item)) >> logn;
+                    const int r = static_cast<int>(row % k);
+                    const bool poly0 = row < static_cast<std::size_t>(k);
+                    const unsigned short pid = map.prime[r];
+                    if (pid == kSkipRow)
+                        continue;
+                    const std::size_t off = 2 * (i - item * npairs_per_item);
+                    const bool k_x = poly0 && (const_mode == 2 || (off & nmask) == 0), k_y = poly0 && const_mode == 2;
+                    lincomb_lane<S>(terms, item * x_stride + off, w + r, k, w_sum_stride,
+                                    constant != nullptr && poly0 ? constant + r : nullptr, k_x, k_y, primes[pid].p, primes[pid].cr0,
+                                    primes[pid].cr1, out + item * x_stride + off, out_sum_stride, add_partial,
+                                    poly0 ? nullptr : tflags, flag_sum_stride, item);
+                }
+                else
+                {
+                    const std::size_t item = i / npairs_per_item;
+                    const std::size_t off = 2 * (i - item * npairs_per_item);
+                    const std::size_t row = off >> logn;
+                    const int r = static_cast<int>(row % k);
+                    const bool poly0 = row < static_cast<std::size_t>(k);
+                    const unsigned short pid = map.prime[r];
+                    if (pid == kSkipRow)
+                        continue;
+                    const bool k_x = poly0 && (const_mode == 2 || (off & nmask) == 0), k_y = poly0 && const_mode == 2;
+                    lincomb_lane<S>(terms, item * x_stride + off, w + r, k, w_sum_stride,
+                                    constant != nullptr && poly0 ? constant + r : nullptr, k_x, k_y, primes[pid].p, primes[pid].cr0,
+                                    primes[pid].cr1, out + item * x_stride + off, out_sum_stride, add_partial,
+                                    poly0 ? nullptr : tflags, flag_sum_stride, item);
+                }
+            }
+        }
+
+        // The tables of a polynomial's inner sums from its coefficients mod t (launch_poly_tables). One lane per (coefficient,
+        // row): the weight is plain_lift_centered_kernel's word, the constant scaling_variant_kernel's at coefficient 0.
+        constexpr int kPolyCoeffChunk = 64;
+        struct PolyCoeffs
+        {
+            u64 c[kPolyCoeffChunk];
+        };
+        __global__ __launch_bounds__(kThreads) void poly_tables_kernel(PolyCoeffs cs, std::size_t first, int n, std::size_t ms,
+                                                                       ScalingArgs sc, const PrimeDev *__restrict__ primes,
+                                                                       u64 *__restrict__ w, u64 *__restrict__ constant)
+        {
+            const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+            if (i >= n * sc.k)
+                return;
+            const int r = i % sc.k;
+            const u64 c = cs.c[i / sc.k];
+            const std::size_t e = first + static_cast<std::size_t>(i / sc.k), j = e / ms, ii = e - j * ms;
+            const PrimeDev &P = primes[r];
+            if (ii == 0)
+                constant[j * sc.k + r] = mul_add_mod(sc.div[r], c, scaling_variant_fix(sc, c), P.p, P.cr0, P.cr1);
+            else
+            {
+                const u64 inc = P.p - barrett_reduce_63(sc.t, P.p, P.cr1);
+                w[(j * (ms - 1) + ii - 1) * sc.k + r] = barrett_reduce_63(c + (c >= sc.threshold ? inc : 0), P.p, P.cr1);
             }
         }
 
@@ -540,6 +675,69 @@ namespace sealhip
             tensor_dot_kernel<false><<<grid, kThreads, 0, e.lane().stream>>>(terms, a_stride, b_stride, out01, out01_stride, out2,
                                                                              out2_stride, e.d_primes, map, e.logn, pairs, count,
                                                                              e.lane().tsink_arm, add_partial ? 1 : 0);
+        return hipGetLastError();
+    }
+
+    namespace
+    {
+        template <int S>
+        void lincomb_launch(const Engine &e, unsigned grid, const LinTerms &terms, std::size_t x_stride, const u64 *w,
+                            std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
+                            const RowMap &map, std::size_t pairs, std::size_t count, bool add_partial, std::size_t flag_sum_stride)
+        {
+            lincomb_kernel<S><<<grid, kThreads, 0, e.lane().stream>>>(terms, x_stride, w, w_sum_stride, constant, const_mode, out,
+                                                                      out_sum_stride, e.d_primes, map, e.logn, pairs, count,
+                                                                      e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
+        }
+    } // namespace
+
+    hipError_t launch_lincomb(const Engine &e, const LinTerms &terms, int size, std::size_t x_stride, const u64 *w,
+                              std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
+                              int n_sums, std::size_t count, const RowMap &map, bool add_partial, std::size_t flag_sum_stride)
+    {
+        static_assert(bounds::lincomb_group_admits(kLinGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
+        static_assert(kLinTile == 4, "the dispatch below has one instance per tile size");
+        if (terms.n < 1 || terms.n > kLinGroup || n_sums < 1 || n_sums > kLinTile || size < 1 || map.rows < 1 ||
+            map.rows > kMaxRows || (constant && const_mode != 1 && const_mode != 2))
+            return hipErrorInvalidValue;
+        const std::size_t pairs = (static_cast<std::size_t>(size) * map.rows << e.logn) / 2;
+        if (pairs * count == 0)
+            return hipSuccess;
+        ProfScope prof(e, "lincomb", 0);
+        const unsigned grid = grid_for(pairs * count);
+#define SEALHIP_LINCOMB_CASE(S)                                                                                              \
+    case S:                                                                                                                  \
+        lincomb_launch<S>(e, grid, terms, x_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, map, pairs,   \
+                          count, add_partial, flag_sum_stride);                                                              \
+        break;
+        switch (n_sums)
+        {
+            SEALHIP_LINCOMB_CASE(1)
+            SEALHIP_LINCOMB_CASE(2)
+            SEALHIP_LINCOMB_CASE(3)
+            SEALHIP_LINCOMB_CASE(4)
+        }
+#undef SEALHIP_LINCOMB_CASE
+        return hipGetLastError();
+    }
+
+    hipError_t launch_poly_tables(const Engine &e, int k, const u64 *coeffs, std::size_t n_coeffs, std::size_t ms, u64 *w,
+                                  u64 *constant)
+    {
+        if (k < 1 || k > kMaxModuli || ms < 2)
+            return hipErrorInvalidValue;
+        ScalingArgs sc{};
+        fill_scaling_args(e, k, sc);
+        ProfScope prof(e, "poly_tables", 0);
+        for (std::size_t first = 0; first < n_coeffs; first += kPolyCoeffChunk)
+        {
+            PolyCoeffs cs{};
+            const int n = static_cast<int>(std::min<std::size_t>(kPolyCoeffChunk, n_coeffs - first));
+            for (int i = 0; i < n; i++)
+                cs.c[i] = coeffs[first + i];
+            poly_tables_kernel<<<grid_for(static_cast<std::size_t>(n) * k), kThreads, 0, e.lane().stream>>>(cs, first, n, ms, sc,
+                                                                                                            e.d_primes, w, constant);
+        }
         return hipGetLastError();
     }
 

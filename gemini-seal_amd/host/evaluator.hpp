@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -1224,6 +1225,96 @@ namespace sealhip_host
         {
             dot_product_internal(encrypteds1, encrypteds2, &relin_key, destination, true);
         }
+        // Linear combination with scalar weights (sealhip_evaluator_linear_combination): destination =
+        // sum_i weights[i] * terms[i], one streaming pass over the terms -- no transforms, no plaintext objects. Every term is
+        // checked like add's operands and against the first: same size (>= 2), same level, the scheme's form. An object may
+        // appear in several terms. The reference has no such method; the words are those of multiply_plain with a constant
+        // plaintext per term and add over the products.
+        // BFV: weights are scalars mod t (a weight >= t is refused); the product uses the residue multiply_plain uses for a
+        // one-coefficient plaintext, (c - t [c >= (t + 1) / 2]) mod q_r.
+        template <class C, IfCt<C> = 0>
+        void linear_combination(const std::vector<C> &terms, const std::vector<std::uint64_t> &weights, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
+                throw std::invalid_argument("integer weights are for BFV; CKKS takes doubles and a scale");
+            check_lincomb_terms(terms, weights.size());
+            const std::size_t k = terms[0].coeff_modulus_size();
+            const std::uint64_t t = ctx_.plain_modulus(), half = (t + 1) >> 1;
+            std::vector<std::uint64_t> w(weights.size() * k);
+            for (std::size_t i = 0; i < weights.size(); i++)
+            {
+                if (weights[i] >= t)
+                    throw std::invalid_argument("a weight is not below the plain modulus");
+                for (std::size_t r = 0; r < k; r++)
+                {
+                    const std::uint64_t q = ctx_.key_modulus(r);
+                    w[i * k + r] = weights[i] >= half ? (weights[i] % q + (q - t % q)) % q : weights[i] % q;
+                }
+            }
+            linear_combination_internal(terms, w, destination, terms[0].scale());
+        }
+        // CKKS: weights are doubles with ONE scale; the residues are those of encode(double value, scale)'s constant,
+        // round(weight * scale) reduced per prime (ckks.h:405-470), |weight * scale| >= 2^62 is refused. Terms are checked for
+        // one scale; the result's scale is terms[0].scale() * scale.
+        template <class C, IfCt<C> = 0>
+        void linear_combination(const std::vector<C> &terms, const std::vector<double> &weights, double scale, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::invalid_argument("weights with a scale are for CKKS; BFV takes scalars mod t");
+            check_lincomb_terms(terms, weights.size());
+            if (!(scale > 0))
+                throw std::invalid_argument("scale out of bounds"); // ckks.h:420-424
+            const std::size_t k = terms[0].coeff_modulus_size();
+            std::vector<std::uint64_t> w(weights.size() * k);
+            for (std::size_t i = 0; i < weights.size(); i++)
+            {
+                const double v = std::round(weights[i] * scale);
+                if (!(std::fabs(v) < 4611686018427387904.0)) // 2^62 (also refuses NaN)
+                    throw std::invalid_argument("encoded value is too large");
+                const std::uint64_t mag = static_cast<std::uint64_t>(std::fabs(v));
+                for (std::size_t r = 0; r < k; r++)
+                {
+                    const std::uint64_t q = ctx_.key_modulus(r), res = mag % q;
+                    w[i * k + r] = std::signbit(v) && res ? q - res : res;
+                }
+            }
+            linear_combination_internal(terms, w, destination, terms[0].scale() * scale);
+        }
+
+        // Evaluator-style polynomial evaluation (sealhip_evaluator_evaluate_polynomial): destination =
+        // sum_e coeffs[e] * encrypted^e by Paterson-Stockmeyer, BFV on STRICT contexts, a size-2 operand in coefficient form,
+        // coefficients below t (lowest degree first), relin_keys as relinearize_inplace takes them (index 0 is read; none is
+        // needed for degree one). The reference has no such method; the words are those of tests/poly_eval_ref.py.
+        template <class C, IfCt<C> = 0>
+        void evaluate_polynomial(const C &encrypted, const std::vector<std::uint64_t> &coeffs,
+                                 const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
+                throw std::logic_error("unsupported scheme");
+            if (encrypted.is_ntt_form())
+                throw std::invalid_argument("BFV encrypted cannot be in NTT form");
+            if (encrypted.size() != 2)
+                throw std::invalid_argument("encrypted size must be 2");
+            if (coeffs.empty())
+                throw std::invalid_argument("coeffs must not be empty");
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n;
+            Dev c = dev_in(encrypted, words), o = dev_out(words);
+            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_evaluate_polynomial(ctx_.get(), std::uint32_t(k), c.ptr(), 1, coeffs.data(),
+                                                           std::uint32_t(coeffs.size() - 1), 0, raw ? &raw : nullptr, raw ? 1u : 0u,
+                                                           o.ptr()));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, k);
+        }
+        template <class C, IfCt<C> = 0>
+        void evaluate_polynomial_inplace(C &encrypted, const std::vector<std::uint64_t> &coeffs,
+                                         const std::vector<const KSwitchKeys *> &relin_keys)
+        {
+            evaluate_polynomial(encrypted, coeffs, relin_keys, encrypted);
+        }
+
         // relinearize + rescale_to_next in one call and with one rounding (sealhip_evaluator_relinearize_rescale, DESIGN.md
         // section 19): CKKS only, a size-3 operand in NTT form, relin_keys as relinearize_inplace takes them (index 0 is
         // read); "end of modulus switching chain reached" at the last level. The result has size 2, one level down, with
@@ -1821,6 +1912,54 @@ namespace sealhip_host
             chk.done();
             take_meta(destination, a[0]); // (every term is staged or enqueued by now: the destination may be one of them)
             commit(destination, o, size, k_out);
+            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
+                destination.scale() = scale;
+        }
+
+        // linear_combination's checks on the term list: one size, one level, the scheme's form and, for CKKS, one scale
+        template <class C>
+        void check_lincomb_terms(const std::vector<C> &terms, std::size_t n_weights) const
+        {
+            if (terms.empty() || terms.size() != n_weights)
+                throw std::invalid_argument("terms and weights must hold the same, non-zero number of entries");
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            for (const C &c : terms)
+            {
+                if (bfv && c.is_ntt_form())
+                    throw std::invalid_argument("BFV encrypted cannot be in NTT form");
+                if (!bfv && !c.is_ntt_form())
+                    throw std::invalid_argument("CKKS encrypted must be in NTT form");
+                if (c.size() < 2 || c.size() != terms[0].size())
+                    throw std::invalid_argument("terms must have one size of at least 2");
+                if (c.coeff_modulus_size() != terms[0].coeff_modulus_size() || c.poly_modulus_degree() != ctx_.n())
+                    throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+                if (!bfv && c.scale() != terms[0].scale())
+                    throw std::invalid_argument("scale mismatch");
+            }
+        }
+        // w: terms.size() x k canonical residues (one sum, no constant)
+        template <class C>
+        void linear_combination_internal(const std::vector<C> &terms, const std::vector<std::uint64_t> &w, C &destination,
+                                         double scale)
+        {
+            const std::size_t size = terms[0].size(), k = terms[0].coeff_modulus_size(), words = size * k * ctx_.n();
+            std::vector<Dev> staged;
+            std::vector<const std::uint64_t *> ptrs;
+            staged.reserve(terms.size());
+            for (const C &c : terms)
+            {
+                staged.push_back(dev_in(c, words));
+                ptrs.push_back(staged.back().ptr());
+            }
+            Staged dw(ctx_, w.size());
+            dw.up(w.data(), w.size());
+            Dev o = dev_out(words);
+            Check chk = checked(terms[0]);
+            throw_on(sealhip_evaluator_linear_combination(ctx_.get(), std::uint32_t(k), ptrs.data(), std::uint32_t(ptrs.size()),
+                                                          std::uint32_t(size), 1, dw.ptr(), nullptr, 1, o.ptr()));
+            chk.done();
+            take_meta(destination, terms[0]); // (every term is staged or enqueued by now: the destination may be one of them)
+            commit(destination, o, size, k);
             if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
                 destination.scale() = scale;
         }

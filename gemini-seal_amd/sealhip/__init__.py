@@ -141,6 +141,8 @@ SYMBOLS = {
                                                    C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_dot_product_max_terms": [_vp, _u32, C.POINTER(C.c_uint64)],
     "sealhip_evaluator_dot_product": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_linear_combination": [_vp, _u32, C.POINTER(_vp), _u32, _u32, _sz, _vp, _vp, _u32, _vp],
+    "sealhip_evaluator_evaluate_polynomial": [_vp, _u32, _vp, _sz, C.POINTER(C.c_uint64), _u32, _u32, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_relinearize_rescale": [_vp, _u32, _vp, _u32, _sz, _sz, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_dot_product_rescale": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_apply_galois_dot_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32,
@@ -1022,6 +1024,30 @@ class Evaluator:
             keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
         _check(getattr(lib(), _entry)(self.ctx.handle, k, pa, pb, len(a_terms), count, keys,
                                       len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+
+    def linear_combination(self, terms, weights, k, count, out, size=2, n_sums=1, constant=None):
+        """Linear combinations with scalar weights (sealhip_evaluator_linear_combination):
+        out[s] = sum_i weights[s][i] * terms[i] (+ constant[s] on polynomial 0) over device batches count x size x k x N.
+        weights: device buffer n_sums x len(terms) x k of canonical residues; constant: device buffer n_sums x k or None;
+        out: n_sums x count x size x k x N. The operands are not modified; buffers may repeat."""
+        pt = (_vp * max(1, len(terms)))(*[_ptr(c) for c in terms])
+        _check(lib().sealhip_evaluator_linear_combination(self.ctx.handle, k, pt, len(terms), size, count, _ptr(weights),
+                                                          _ptr(constant) if constant is not None else None, n_sums, _ptr(out)))
+
+    def evaluate_polynomial(self, ct, coeffs, k, count, out, relin_keys=None, n_baby=0):
+        """p(ct) = sum_e coeffs[e] ct^e by Paterson-Stockmeyer (sealhip_evaluator_evaluate_polynomial):
+        BFV STRICT, ct and out device batches count x 2 x k x N, coeffs host integers below t (lowest degree first), n_baby
+        the number of baby steps (0: ceil(sqrt(d + 1))). relin_keys (a list of KSwitchKeys, index 0 is read) may be None for a
+        polynomial of degree one. The words are those of tests/poly_eval_ref.py."""
+        coeffs = [int(c) for c in coeffs]
+        if not coeffs:
+            raise ValueError("coeffs must not be empty")
+        ca = (C.c_uint64 * len(coeffs))(*coeffs)
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        _check(lib().sealhip_evaluator_evaluate_polynomial(self.ctx.handle, k, _ptr(ct), count, ca, len(coeffs) - 1, n_baby, keys,
+                                                           len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
 
     # ---- the key switch's mod-down merged with rescale_to_next (DESIGN.md section 19): CKKS, operands at level k >= 2, every
     # out at level k - 1; the words are those of tests/ks_rescale_ref.py, the error that of the unmerged method + rescale_to_next

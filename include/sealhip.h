@@ -612,6 +612,62 @@ long sealhip_evaluator_rotate_vector_bsgs_plain_rescale(sealhip_context *ctx, ui
                                                         const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
                                                         const uint64_t *plain_ntt, uint64_t *out);
 
+/* Linear combinations of ciphertexts with scalar weights, both schemes, both modes:
+       out_s = sum_{i < n_terms} W[s][i] * X_i  (+ K[s] on c_0)      for s < n_sums
+   formed by one streaming kernel that loads every operand word once per tile of 4 sums: no transforms, no lifted plaintexts,
+   no partial sums written and re-read.
+   terms: a host array of n_terms device pointers, as sealhip_evaluator_dot_product takes them; each points at a batch
+   count x size x k x N of ciphertexts at level k, all of the same size >= 2 (BFV in coefficient form, CKKS in NTT form).
+   Pointers may repeat; the operands are never modified. weights: DEVICE memory, n_sums x n_terms x k words, W[s][i][r] a
+   canonical residue modulo q_r. constant: DEVICE memory, n_sums x k words, or NULL; K[s][r] is added to polynomial 0 only --
+   BFV at coefficient 0 (a constant polynomial in coefficient form), CKKS at every coefficient (a constant polynomial in NTT
+   form). out: n_sums x count x size x k x N, sum-major as for sealhip_evaluator_apply_galois_dot_plain; it overlaps no term
+   and neither table. Weights and constants are shared across the batch; weights of zero are legal and contribute nothing.
+   Every output word is the canonical residue of the integer sum, so it is word for word the composition of
+   multiply_poly_scalar_coeffmod per term and row, add_poly_coeffmod left to right, the constant added last. Operand or
+   weight words at or above their prime give unspecified words.
+   Checks: NULL pointers (ctx, weights, out, terms and each of its entries) -> E_POINTER; then, also on host-only contexts,
+   k outside the ciphertext levels, size < 2 or > 16 (SEAL_CIPHERTEXT_SIZE_MIN / _MAX, util/defines.h:56-57, the bounds
+   sealhip_evaluator_multiply and _relinearize apply), n_terms == 0 or n_sums == 0 with count > 0, out overlapping a term or a
+   table -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION.
+   Runs on the calling thread's lane, takes nothing from the arena and synchronises nothing; the term pointers travel in
+   kernel arguments, so the call is capturable after one warm-up call. With a transparency sink: one flag per output
+   ciphertext (n_sums x count flags, in output order), written by the kernel that stores it. */
+long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, const uint64_t *const *terms, uint32_t n_terms,
+                                          uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
+                                          uint32_t n_sums, uint64_t *out);
+
+/* Polynomial evaluation on ciphertexts: out = p(ct) = sum_e coeffs[e] ct^e by Paterson-Stockmeyer
+   over the two entries above. BFV in STRICT mode. ct: count x 2 x k x N, coefficient form, not modified; out: count x 2 x k
+   x N, overlapping nothing; both device memory. coeffs: HOST memory, degree + 1 words below t, shared by the batch.
+   Trailing zero coefficients are trimmed first; with d what remains, m = n_baby, or ceil(sqrt(d + 1)) when n_baby is 0, and
+   g = ceil((d + 1) / m):
+     baby powers   B_1 = ct, B_e = relinearize(multiply(B_ceil(e/2), B_floor(e/2))) for 2 <= e <= min(m, d);
+     giant powers  G_1 = B_m, G_j = relinearize(multiply(G_ceil(j/2), G_floor(j/2))) for 2 <= j < g -- only those that a
+                   surviving term needs or that a needed one is built from;
+     inner sums    I_j = sum_{1 <= i < m} w(c_{jm+i}) B_i + K(c_{jm}) for j < g in ONE sealhip_evaluator_linear_combination,
+                   w(c)[r] = (c - t [c >= (t+1)/2]) mod q_r, the residue multiply_plain uses for a one-coefficient plaintext,
+                   K(c)[r] the word multiply_add_plain_with_scaling_variant adds at coefficient 0 for that plaintext;
+     outer sum     out = I_0 + sealhip_evaluator_dot_product({G_j}, {I_j}, j >= 1 with I_j not identically zero, relin_keys):
+                   one inverse transform, one floor and one relinearization for the whole sum; with g == 1, out = I_0
+                   (with g > 1 the inner sum that holds c_d is not zero, so there is such a j).
+   What defines the words is the restatement over the oracle in tests/poly_eval_ref.py.
+   relin_keys as for sealhip_evaluator_relinearize (only index 0 is read); with d == 1 no key is needed and it may be NULL.
+   Checks: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, a CKKS context
+   ("BFV only"), BFV in PARITY mode ("STRICT"), a coefficient >= t, d < 1 after trimming (a constant is not an operation on
+   a ciphertext), n_baby == 1 or n_baby > d + 1, more outer terms than sealhip_evaluator_dot_product_max_terms(k), with
+   d >= 2 missing keys or a key with fewer digits than the level, out overlapping ct -> E_INVALIDARG; then count == 0 ->
+   S_OK; then a host-only context -> COR_E_INVALIDOPERATION.
+   Temporaries -- (m - 1) + (g - 1) + g size-2 batches, the products' size-3 scratch and the two small tables -- are blocks
+   of the context's pool (sealhip_pool_*), taken and released in stream order on the calling lane, and the coefficients
+   travel in kernel arguments: nothing synchronises, but unlike sealhip_evaluator_linear_combination this entry allocates
+   (until the pool is warm) and is therefore NOT capturable. With a transparency sink: one flag per output ciphertext, from the kernel that stores out (g == 1) or a
+   read pass over it. CKKS polynomial evaluation needs per-power scale and level bookkeeping and is not offered;
+   sealhip_evaluator_linear_combination is its building block. */
+long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                           const uint64_t *coeffs, uint32_t degree, uint32_t n_baby,
+                                           const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out);
+
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
    of the ciphertext (is_ntt_form). sk_powers_ntt = the Decryptor's secret_key_array_: (size-1) polynomials s, s^2, ...
