@@ -15,6 +15,7 @@
 
 #include "blake2xb.hpp"
 #include "engine.hpp"
+#include "poly_plan.hpp"
 
 using namespace sealhip;
 
@@ -2398,6 +2399,62 @@ long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, cons
     });
 }
 
+/* The same sums over CKKS terms that keep their own level and size: lincomb_levels_kernel reads rows
+   r < k of every term at that term's row stride, so nothing is dropped to level k by a copy first. */
+long sealhip_evaluator_linear_combination_levels(sealhip_context *ctx, uint32_t k, const uint64_t *const *terms,
+                                                 const uint32_t *term_levels, const uint32_t *term_sizes, uint32_t n_terms,
+                                                 uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
+                                                 uint32_t n_sums, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(weights);
+    REQUIRE_PTR(out);
+    if (n_terms)
+    {
+        REQUIRE_PTR(terms);
+        for (uint32_t i = 0; i < n_terms; i++)
+            REQUIRE_PTR(terms[i]);
+        REQUIRE_PTR(term_levels);
+        REQUIRE_PTR(term_sizes);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (h.scheme != 2) // (a BFV mod_switch_to_next rounds every row: a higher level does not hold the lower one's words)
+            throw std::invalid_argument("terms at their own level are CKKS only");
+        for (uint32_t i = 0; i < n_terms; i++)
+            if (term_levels[i] < k || static_cast<int>(term_levels[i]) > h.k_first)
+                throw std::invalid_argument("a term's level is below k or out of range");
+        if (size < 2 || size > 16) // SEAL_CIPHERTEXT_SIZE_MIN / _MAX (util/defines.h:56-57)
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        for (uint32_t i = 0; i < n_terms; i++)
+            if (term_sizes[i] < 2 || term_sizes[i] > size)
+                throw std::invalid_argument("a term's size is below 2 or above the sum's");
+        if ((n_terms == 0 || n_sums == 0) && count > 0)
+            throw std::invalid_argument("the term list and the sums must not be empty");
+        const std::size_t item = static_cast<std::size_t>(size) * k * h.n;
+        const u64 *o = reinterpret_cast<const u64 *>(out), *w = reinterpret_cast<const u64 *>(weights),
+                  *kc = reinterpret_cast<const u64 *>(constant);
+        const std::size_t out_words = n_sums * count * item;
+        for (uint32_t i = 0; i < n_terms; i++)
+            if (words_overlap(o, out_words, reinterpret_cast<const u64 *>(terms[i]),
+                              count * term_sizes[i] * term_levels[i] * h.n))
+                throw std::invalid_argument("out must not overlap a term");
+        if (words_overlap(o, out_words, w, static_cast<std::size_t>(n_sums) * n_terms * k))
+            throw std::invalid_argument("out must not overlap weights");
+        if (kc && words_overlap(o, out_words, kc, static_cast<std::size_t>(n_sums) * k))
+            throw std::invalid_argument("out must not overlap constant");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, static_cast<size_t>(n_sums) * count);
+        sink.begin();
+        op_linear_combination_levels(e, static_cast<int>(k), reinterpret_cast<const u64 *const *>(terms), term_levels, term_sizes,
+                                     n_terms, static_cast<int>(size), count, w, kc, n_sums, reinterpret_cast<u64 *>(out));
+    });
+}
+
 /* Paterson-Stockmeyer over the two entries above: the power basis with multiply + relinearize (the launches of
    do_multiply_many's products), every inner sum in ONE linear combination, the outer sum in ONE dot_product. Temporaries
    are blocks of the context's pool, taken and released in stream order on the calling thread's lane: nothing here
@@ -2539,6 +2596,285 @@ long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, con
         op_dot_product(e, static_cast<int>(k), ga.data(), ib.data(), outer.size(), count, &relin_keys[0]->key, D);
         check(launch_ct_linear(e, CtLinearOp::Add, I, 2, D, 2, 0, o, count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)), "add");
         sink.read_pass(o, 2, poly, count);
+    });
+}
+
+/* ------------------------------------------------------------------ CKKS polynomial evaluation */
+extern "C++"
+{
+namespace
+{
+    // The checks both entries share, in the header's order, and the plan (poly_plan.hpp). tables: also the inner tables.
+    polyplan::Plan ckks_poly_plan(Engine &h, uint32_t k, double scale, const double *coeffs, uint32_t degree, uint32_t basis,
+                                  uint32_t n_baby, double scale_out, bool tables)
+    {
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+        if (h.scheme != 2)
+            throw std::invalid_argument("planned polynomial evaluation is CKKS only (BFV: sealhip_evaluator_evaluate_polynomial)");
+        return polyplan::make_plan(h.key_moduli.data(), static_cast<int>(k), scale, coeffs, degree, basis, n_baby, scale_out,
+                                   tables);
+    }
+
+    // Words per item of the pool blocks sealhip_evaluator_evaluate_polynomial_ckks takes, in the order it takes them (the
+    // entry counts what it takes and refuses to go on if the two ever disagree).
+    std::size_t ckks_poly_temp_words(const polyplan::Plan &p, std::size_t N)
+    {
+        const std::size_t k = static_cast<std::size_t>(p.k), nb = p.baby.size() - 1;
+        std::size_t words = 0;
+        bool drops = false;
+        for (std::size_t e = 2; e <= nb; e++)
+        {
+            drops = drops || p.baby[(e + 1) / 2].level != p.baby[e / 2].level;
+            words += 2 * static_cast<std::size_t>(p.baby[e].level) * N;
+        }
+        for (std::size_t j = 2; j < p.g; j++)
+            if (p.needed[j])
+            {
+                drops = drops || p.giant[(j + 1) / 2].level != p.giant[j / 2].level;
+                words += 2 * static_cast<std::size_t>(p.giant[j].level) * N;
+            }
+        if (drops)
+            words += 2 * k * N; // one shared drop buffer (only the operand at the higher level is copied)
+        if (p.basis == 1 && nb >= 2)
+            words += 2 * 3 * k * N; // the size-3 product and the size-3 combination of a Chebyshev step
+        const std::size_t nf = 1 + p.J.size();
+        words += nf * 2 * static_cast<std::size_t>(p.inner_level) * N; // the inner sums before their rescale
+        if (!p.J.empty())
+        {
+            words += nf * 2 * static_cast<std::size_t>(p.sums_level) * N;
+            for (std::size_t j : p.J)
+            {
+                if (p.giant[j].level != p.outer_level)
+                    words += 2 * static_cast<std::size_t>(p.outer_level) * N;
+                if (p.sums_level != p.outer_level)
+                    words += 2 * static_cast<std::size_t>(p.outer_level) * N;
+            }
+            words += 2 * static_cast<std::size_t>(p.out_level) * N; // the outer sum
+        }
+        return words;
+    }
+
+    void fill_plan(const polyplan::Plan &p, std::size_t N, sealhip_poly_plan *plan)
+    {
+        plan->d = static_cast<uint32_t>(p.d), plan->m = static_cast<uint32_t>(p.m), plan->g = static_cast<uint32_t>(p.g);
+        plan->inner_level = static_cast<uint32_t>(p.inner_level), plan->out_level = static_cast<uint32_t>(p.out_level);
+        plan->n_products = static_cast<uint32_t>(p.n_products);
+        plan->out_scale = p.scale_out;
+        plan->temp_bytes_per_item = ckks_poly_temp_words(p, N) * sizeof(u64);
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_evaluator_polynomial_plan_ckks(sealhip_context *ctx, uint32_t k, double scale, const double *coeffs, uint32_t degree,
+                                            uint32_t basis, uint32_t n_baby, double scale_out, sealhip_poly_plan *plan,
+                                            uint64_t *inner_weights, uint64_t *inner_constants)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(coeffs);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const bool tables = inner_weights || inner_constants;
+        const polyplan::Plan p = ckks_poly_plan(h, k, scale, coeffs, degree, basis, n_baby, scale_out, tables);
+        fill_plan(p, h.n, plan);
+        if (inner_weights)
+            std::copy(p.W.begin(), p.W.end(), inner_weights);
+        if (inner_constants)
+            std::copy(p.K.begin(), p.K.end(), inner_constants);
+    });
+}
+
+long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale,
+                                                const double *coeffs, uint32_t degree, uint32_t basis, uint32_t n_baby,
+                                                double scale_out, const sealhip_kswitch_key *const *relin_keys,
+                                                uint32_t n_relin_keys, uint64_t *out, uint32_t *out_level, double *out_scale)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(coeffs);
+    REQUIRE_PTR(out);
+    if (relin_keys && n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const polyplan::Plan p = ckks_poly_plan(h, k, scale, coeffs, degree, basis, n_baby, scale_out, true);
+        if (p.d >= 2)
+        {
+            if (!relin_keys || n_relin_keys == 0)
+                throw std::invalid_argument("not enough relinearization keys");
+            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+            if (relin_keys[0]->key.n_digits < nd)
+                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        }
+        const std::size_t N = h.n;
+        const u64 *x = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        const std::size_t out_poly = static_cast<std::size_t>(p.out_level) * N;
+        if (words_overlap(o, count * 2 * out_poly, x, count * 2 * k * N))
+            throw std::invalid_argument("out must not overlap ct");
+        if (out_level)
+            *out_level = static_cast<uint32_t>(p.out_level);
+        if (out_scale)
+            *out_scale = p.scale_out;
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        const KSwitchKey *key = p.d >= 2 ? &relin_keys[0]->key : nullptr;
+        // Temporaries are blocks of the context's pool, taken and released in stream order on this lane (see
+        // sealhip_evaluator_evaluate_polynomial).
+        std::vector<void *> owned;
+        struct Cleanup
+        {
+            Engine &e;
+            std::vector<void *> &v;
+            ~Cleanup()
+            {
+                for (void *q : v)
+                    pool_release(e, q);
+            }
+        } cleanup{ e, owned };
+        std::size_t taken = 0; // words per item
+        const auto temp = [&](std::size_t words_per_item) {
+            void *q = pool_alloc(e, count * words_per_item * sizeof(u64));
+            owned.push_back(q);
+            taken += words_per_item;
+            return static_cast<u64 *>(q);
+        };
+        const auto poly_words = [&](int level) { return static_cast<std::size_t>(level) * N; };
+
+        // ---- every table of the call, gathered on the host and sent through kernel arguments in one pass
+        const int Lin = p.inner_level;
+        const std::size_t nb = p.baby.size() - 1, nf = 1 + p.J.size(), mi = p.mi;
+        std::vector<u64> tab;
+        const u64 *q = h.key_moduli.data();
+        std::vector<std::size_t> cheb_at(nb + 1, 0); // Chebyshev step e: weights [2][L] (or [1][L]) then the constant [L]
+        if (p.basis == 1)
+            for (std::size_t el = 2; el <= nb; el++)
+            {
+                const int L = p.baby[(el + 1) / 2].level;
+                cheb_at[el] = tab.size();
+                for (int r = 0; r < L; r++)
+                    tab.push_back(2 % q[r]);
+                for (int r = 0; r < L; r++) // hi != lo: the weight of E_1; hi == lo: the constant
+                    tab.push_back(polyplan::rint_residue(-p.cheb_sub[el], q[r]));
+            }
+        std::vector<std::size_t> sums{ 0 }; // the sums that are formed, in order
+        sums.insert(sums.end(), p.J.begin(), p.J.end());
+        const std::size_t w_at = tab.size();
+        for (std::size_t j : sums)
+            tab.insert(tab.end(), p.W.begin() + j * mi * Lin, p.W.begin() + (j + 1) * mi * Lin);
+        const std::size_t k_at = tab.size();
+        for (std::size_t j : sums)
+            tab.insert(tab.end(), p.K.begin() + j * Lin, p.K.begin() + (j + 1) * Lin);
+        const std::size_t ones_at = tab.size();
+        tab.insert(tab.end(), 2 * static_cast<std::size_t>(p.out_level), 1);
+        u64 *T = static_cast<u64 *>(pool_alloc(e, tab.size() * sizeof(u64)));
+        owned.push_back(T);
+        check(launch_put_words(e, T, tab.data(), tab.size()), "put_words");
+
+        // ---- products: an operand above the product's level is dropped to it by a copy (tensor_dot reads one row stride)
+        u64 *drop_buf = nullptr;
+        const auto dropped = [&](const u64 *a, int la, int L) {
+            if (la == L)
+                return a;
+            if (!drop_buf)
+                drop_buf = temp(2 * poly_words(static_cast<int>(k)));
+            check(launch_copy_rows(e, a, poly_words(la), drop_buf, poly_words(L), count * 2, L), "drop");
+            return static_cast<const u64 *>(drop_buf);
+        };
+        const auto product_rescale = [&](const u64 *a, int la, const u64 *b, int lb, u64 *dst) {
+            const int L = std::min(la, lb);
+            const u64 *pa = dropped(a, la, L), *pb = dropped(b, lb, L);
+            op_dot_product(e, L, &pa, &pb, 1, count, key, dst, true);
+        };
+
+        // ---- baby elements
+        std::vector<const u64 *> E(nb + 1, nullptr);
+        E[1] = x;
+        u64 *wide_p = nullptr, *wide_r = nullptr;
+        for (std::size_t el = 2; el <= nb; el++)
+        {
+            const std::size_t hi = (el + 1) / 2, lo = el / 2;
+            const int L = p.baby[hi].level;
+            u64 *dst = temp(2 * poly_words(p.baby[el].level));
+            if (p.basis == 0)
+                product_rescale(E[hi], p.baby[hi].level, E[lo], p.baby[lo].level, dst);
+            else
+            {
+                if (!wide_p)
+                    wide_p = temp(3 * poly_words(static_cast<int>(k))), wide_r = temp(3 * poly_words(static_cast<int>(k)));
+                const u64 *pa = E[hi], *pb = dropped(E[lo], p.baby[lo].level, L);
+                op_dot_product(e, L, &pa, &pb, 1, count, nullptr, wide_p, false);
+                const u64 *terms[2] = { wide_p, x };
+                const uint32_t levels[2] = { static_cast<uint32_t>(L), k }, sizes[2] = { 3, 2 };
+                const u64 *W = T + cheb_at[el];
+                if (hi == lo) // 2 P - rint(sc(hi) sc(lo))
+                    op_linear_combination_levels(e, L, terms, levels, sizes, 1, 3, count, W, W + L, 1, wide_r);
+                else // 2 P - rint(sc(hi) sc(lo) / sc(1)) E_1
+                    op_linear_combination_levels(e, L, terms, levels, sizes, 2, 3, count, W, nullptr, 1, wide_r);
+                op_switch_key_rescale(e, L, wide_r, 3 * poly_words(L), wide_r + 2 * poly_words(L), 3 * poly_words(L), count, *key,
+                                      dst);
+            }
+            E[el] = dst;
+        }
+
+        // ---- giant powers: monomial powers of E_m in both bases
+        std::vector<const u64 *> Y(p.g, nullptr);
+        if (p.g > 1)
+            Y[1] = E[p.m];
+        for (std::size_t j = 2; j < p.g; j++)
+            if (p.needed[j])
+            {
+                u64 *dst = temp(2 * poly_words(p.giant[j].level));
+                product_rescale(Y[(j + 1) / 2], p.giant[(j + 1) / 2].level, Y[j / 2], p.giant[j / 2].level, dst);
+                Y[j] = dst;
+            }
+
+        // ---- the inner sums: ONE combination over E_1 .. E_mi, each read at its own level, ONE rescale of the batch
+        std::vector<uint32_t> levels(mi), sizes(mi, 2);
+        for (std::size_t i = 1; i <= mi; i++)
+            levels[i - 1] = static_cast<uint32_t>(p.baby[i].level);
+        u64 *S = temp(nf * 2 * poly_words(Lin));
+        op_linear_combination_levels(e, Lin, E.data() + 1, levels.data(), sizes.data(), mi, 2, count, T + w_at, T + k_at, nf, S);
+        if (p.J.empty())
+            op_mod_switch_scale(e, Lin, S, 2, count, o, 0);
+        else
+        {
+            const int LI = p.sums_level, Lo = p.outer_level;
+            u64 *I = temp(nf * 2 * poly_words(LI));
+            op_mod_switch_scale(e, Lin, S, 2, nf * count, I, 0);
+            std::vector<const u64 *> ya, ib;
+            for (std::size_t s = 1; s < nf; s++)
+            {
+                const std::size_t j = p.J[s - 1];
+                const u64 *yj = Y[j], *ij = I + s * count * 2 * poly_words(LI);
+                if (p.giant[j].level != Lo)
+                {
+                    u64 *c = temp(2 * poly_words(Lo));
+                    check(launch_copy_rows(e, yj, poly_words(p.giant[j].level), c, poly_words(Lo), count * 2, Lo), "drop");
+                    yj = c;
+                }
+                if (LI != Lo)
+                {
+                    u64 *c = temp(2 * poly_words(Lo));
+                    check(launch_copy_rows(e, ij, poly_words(LI), c, poly_words(Lo), count * 2, Lo), "drop");
+                    ij = c;
+                }
+                ya.push_back(yj);
+                ib.push_back(ij);
+            }
+            u64 *D = temp(2 * out_poly);
+            op_dot_product(e, Lo, ya.data(), ib.data(), ya.size(), count, key, D, true);
+            // out = D + I_0, I_0 read in place at the result's level
+            const u64 *terms[2] = { D, I };
+            const uint32_t lv[2] = { static_cast<uint32_t>(p.out_level), static_cast<uint32_t>(LI) }, sz[2] = { 2, 2 };
+            op_linear_combination_levels(e, p.out_level, terms, lv, sz, 2, 2, count, T + ones_at, nullptr, 1, o);
+        }
+        if (taken != ckks_poly_temp_words(p, N))
+            throw std::logic_error("evaluate_polynomial_ckks: the temporaries taken differ from the plan's count");
+        sink.read_pass(o, 2, out_poly, count);
     });
 }
 

@@ -521,12 +521,33 @@ namespace sealhip
     hipError_t launch_lincomb(const Engine &e, const LinTerms &terms, int size, std::size_t x_stride, const u64 *w,
                               std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
                               int n_sums, std::size_t count, const RowMap &map, bool add_partial, std::size_t flag_sum_stride);
+    // The same sums over terms that keep their own level and size (poly.hip lincomb_levels_kernel): a
+    // CKKS ciphertext at a higher level holds the rows of a lower one at its own row stride, so term t is read in place as
+    // items size[t] * rows[t] * N words apart, polynomials rows[t] * N words apart, rows r < map.rows of polynomials
+    // j < size[t]; polynomials j >= size[t] are zero. rows[t] >= map.rows and 1 <= size[t] <= size. Weights, constant, out,
+    // add_partial and the flags are those of launch_lincomb; out's items are out_stride = size * map.rows * N words apart.
+    constexpr int kLinLevelsTile = bounds::kLinLevelsTileSums;
+    struct LinLevelTerms
+    {
+        const u64 *x[kLinGroup];
+        unsigned char rows[kLinGroup]; // (kMaxModuli and the size bound 16 fit a byte)
+        unsigned char size[kLinGroup];
+        int n;
+    };
+    hipError_t launch_lincomb_levels(const Engine &e, const LinLevelTerms &terms, int size, std::size_t out_stride, const u64 *w,
+                                     std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out,
+                                     std::size_t out_sum_stride, int n_sums, std::size_t count, const RowMap &map,
+                                     bool add_partial, std::size_t flag_sum_stride);
     // The weight and constant tables of a polynomial's inner sums (sealhip_evaluator_evaluate_polynomial): coefficient
     // e = j * ms + i (j < n_sums, i < ms) of the zero-padded list becomes constant[j][r] = the word
     // multiply_add_plain_with_scaling_variant adds at coefficient 0 for the one-coefficient plaintext c_e (i == 0), or
     // w[j][i - 1][r] = (c_e - t [c_e >= (t + 1) / 2]) mod q_r (i >= 1). The coefficients travel in kernel arguments.
     hipError_t launch_poly_tables(const Engine &e, int k, const u64 *coeffs, std::size_t n_coeffs, std::size_t ms, u64 *w,
                                   u64 *constant);
+    // dst[0 .. n) = words (host memory), carried in kernel arguments kPutWords at a time: no staging buffer whose lifetime a
+    // stream would have to respect (the planned tables of sealhip_evaluator_evaluate_polynomial_ckks)
+    constexpr int kPutWords = 256;
+    hipError_t launch_put_words(const Engine &e, u64 *dst, const u64 *words, std::size_t n);
     hipError_t launch_copy_rows(const Engine &e, const u64 *src, std::size_t src_poly_stride, u64 *dst,
                                 std::size_t dst_poly_stride, std::size_t npolys, int rows);
 
@@ -783,6 +804,11 @@ namespace sealhip
     // [n_sums][n_terms][k] and constant [n_sums][k] (or null) are device memory.
     void op_linear_combination(Engine &e, int k, const u64 *const *terms, std::size_t n_terms, int size, std::size_t count,
                                const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out);
+    // the same over CKKS terms at their own level and size: terms[i] is [count][sizes[i]][levels[i]][N],
+    // levels[i] >= k, sizes[i] <= size; levels and sizes are host arrays
+    void op_linear_combination_levels(Engine &e, int k, const u64 *const *terms, const std::uint32_t *levels,
+                                      const std::uint32_t *sizes, std::size_t n_terms, int size, std::size_t count,
+                                      const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out);
     // Evaluator::square as its own path (evaluator.cpp:560-770): the operand is lifted / transformed once
     void op_bfv_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);
     void op_ckks_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);

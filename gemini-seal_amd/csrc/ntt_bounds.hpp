@@ -531,6 +531,12 @@ namespace sealhip
         static_assert(lincomb_group_admits(kLinGroupTerms, kDotAccOperandBits), "16 products of 61-bit words fit 128 bits");
         static_assert(lincomb_group_admits(63, kDotAccOperandBits) && !lincomb_group_admits(64, kDotAccOperandBits),
                       "this (conservative) count admits 63 terms at 61 bits: the group of 16 leaves almost a factor four");
+        // The sums over terms at their own level and size (poly.hip lincomb_levels_kernel): the same
+        // arithmetic per output word, so the same group and the same predicate. The tile is a constant of its own because the
+        // per-term strides add uniform state to a kernel family that must not spill (the register table of section 21).
+        constexpr int kLinLevelsTileSums = 4;
+        static_assert(kLinLevelsTileSums >= 1 && kLinLevelsTileSums <= kLinTileSums,
+                      "the levels kernel is instantiated for 1 .. kLinLevelsTileSums sums and never for more than lincomb_kernel");
 
         // =====================================================================================================
         // 9. The merged mod-down and rescale's conversion sum (keyswitch.hip ks_moddown_rescale_pre_kernel, DESIGN.md section

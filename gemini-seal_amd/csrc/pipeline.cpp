@@ -1023,6 +1023,50 @@ namespace sealhip
         });
     }
 
+    // The same over terms at their own level and size: CKKS, where a ciphertext at level levels[i] >= k
+    // holds the level-k ciphertext in its first k rows, and a term of sizes[i] <= size polynomials stands for the one padded
+    // with zero polynomials. lincomb_levels_kernel reads every term in place at its own strides: no row copy, no arena.
+    void op_linear_combination_levels(Engine &e, int k, const u64 *const *terms, const std::uint32_t *levels,
+                                      const std::uint32_t *sizes, std::size_t n_terms, int size, std::size_t count,
+                                      const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out)
+    {
+        if (e.scheme != 2)
+            throw std::invalid_argument("terms at their own level are CKKS only");
+        if (k > e.k_first)
+            throw std::invalid_argument("the linear combination needs a ciphertext level");
+        if (n_terms == 0 || n_sums == 0 || size < 2)
+            throw std::invalid_argument("an empty linear combination");
+        LevelTools &lt = e.level(k);
+        const std::size_t item = static_cast<std::size_t>(size) * k * e.n;
+        if (n_terms > static_cast<std::size_t>(kLinGroup))
+            log_chunk(e, n_terms, kLinGroup); // (the term split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        for_chunks(e, count, 0, 0, [&](std::size_t off, std::size_t m) {
+            for (std::size_t s0 = 0; s0 < n_sums; s0 += kLinLevelsTile)
+                for (std::size_t g0 = 0; g0 < n_terms; g0 += kLinGroup)
+                {
+                    LinLevelTerms group{};
+                    group.n = static_cast<int>(std::min<std::size_t>(kLinGroup, n_terms - g0));
+                    for (int t = 0; t < group.n; t++)
+                    {
+                        const std::size_t i = g0 + t;
+                        if (static_cast<int>(levels[i]) < k || static_cast<int>(levels[i]) > e.k_first || sizes[i] < 2 ||
+                            static_cast<int>(sizes[i]) > size)
+                            throw std::invalid_argument("a term's level or size does not admit the sum's");
+                        group.x[t] = terms[i] + off * sizes[i] * levels[i] * e.n;
+                        group.rows[t] = static_cast<unsigned char>(levels[i]);
+                        group.size[t] = static_cast<unsigned char>(sizes[i]);
+                    }
+                    const bool last = g0 + kLinGroup >= n_terms; // (only the last group's stores are the result's words)
+                    SinkArm arm(e, last ? sink_at(e, s0 * count + off) : nullptr);
+                    check(launch_lincomb_levels(e, group, size, item, weights + (s0 * n_terms + g0) * k, n_terms * k,
+                                                last && constant ? constant + s0 * k : nullptr, 2, out + (s0 * count + off) * item,
+                                                count * item, static_cast<int>(std::min<std::size_t>(kLinLevelsTile, n_sums - s0)),
+                                                m, lt.map_q, g0 > 0, count),
+                          "lincomb_levels");
+                }
+        });
+    }
+
     // ------------------------------------------------------------------------------------------
     // mod_switch_scale_to_next (evaluator.cpp:829-892): BFV mod_switch_to_next / CKKS rescale_to_next
     // ------------------------------------------------------------------------------------------

@@ -339,6 +339,129 @@ namespace sealhip
             }
         }
 
+        // The same sums over terms at their own level and size: a CKKS mod_switch_to_next only drops the
+        // last row, so a term at level rows[t] >= k holds the level-k ciphertext in place at its own row stride, and a term of
+        // size[t] polynomials is the size-`size` ciphertext whose further polynomials are zero. Term t's word for (item, j, r)
+        // is at ((item * size[t] + j) * rows[t] + r) * N; a term with size[t] <= j contributes nothing to polynomial j. The
+        // arithmetic per output word, the group, the partial sum and the flags are lincomb_lane's. Uniform (a block inside one
+        // row): item, j and r are the block's, so the term's base and whether it takes part are scalar and the block skips its
+        // load and its products together. Otherwise (N < 2 kThreads, a block straddles rows and polynomials) no lane branches:
+        // a term that takes no part is read at polynomial 0 and multiplied by zero.
+        template <int S, bool Uniform>
+        __device__ __forceinline__ void lincomb_levels_lane(const LinLevelTerms &terms, std::size_t item, int j, int r,
+                                                            std::size_t col, int logn, const u64 *__restrict__ wr, int k,
+                                                            std::size_t w_sum_stride, const u64 *__restrict__ kr, bool k_x,
+                                                            bool k_y, u64 p, u64 cr0, u64 cr1, u64 *po,
+                                                            std::size_t out_sum_stride, int add_partial, unsigned *tflags,
+                                                            std::size_t flag_sum_stride)
+        {
+            u64 lo[S][2] = {}, hi[S][2] = {};
+            const auto word = [&](int t, bool live) {
+                const std::size_t jt = Uniform || live ? static_cast<std::size_t>(j) : 0;
+                const std::size_t row = (item * terms.size[t] + jt) * terms.rows[t] + static_cast<std::size_t>(r);
+                return *reinterpret_cast<const ulonglong2 *>(terms.x[t] + (row << logn) + col);
+            };
+            bool live_next = j < static_cast<int>(terms.size[0]);
+            ulonglong2 next = {};
+            if (!Uniform || live_next)
+                next = word(0, live_next);
+            for (int t = 0; t < terms.n; t++)
+            {
+                const ulonglong2 v = next;
+                const bool live = live_next;
+                if (t + 1 < terms.n)
+                {
+                    live_next = j < static_cast<int>(terms.size[t + 1]);
+                    if (!Uniform || live_next)
+                        next = word(t + 1, live_next);
+                }
+                if (Uniform && !live)
+                    continue;
+                const u64 *wt = wr + static_cast<std::size_t>(t) * k;
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                {
+                    const u64 ws = Uniform || live ? wt[s * w_sum_stride] : 0;
+                    mac128(lo[s][0], hi[s][0], v.x, ws);
+                    mac128(lo[s][1], hi[s][1], v.y, ws);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < S; s++)
+            {
+                u64 *ps = po + s * out_sum_stride;
+                if (add_partial)
+                {
+                    const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(ps);
+                    dot_add_word(lo[s][0], hi[s][0], q.x), dot_add_word(lo[s][1], hi[s][1], q.y);
+                }
+                if (kr != nullptr)
+                {
+                    const u64 kv = kr[static_cast<std::size_t>(s) * k];
+                    dot_add_word(lo[s][0], hi[s][0], k_x ? kv : 0), dot_add_word(lo[s][1], hi[s][1], k_y ? kv : 0);
+                }
+                ulonglong2 c;
+                c.x = barrett_reduce_128(lo[s][0], hi[s][0], p, cr0, cr1);
+                c.y = barrett_reduce_128(lo[s][1], hi[s][1], p, cr0, cr1);
+                *reinterpret_cast<ulonglong2 *>(ps) = c;
+                if (tflags != nullptr)
+                    note_nonzero(tflags + s * flag_sum_stride, item, c.x | c.y);
+            }
+        }
+        template <int S>
+        __global__ __launch_bounds__(kThreads) void lincomb_levels_kernel(LinLevelTerms terms, std::size_t out_stride,
+                                                                          const u64 *__restrict__ w, std::size_t w_sum_stride,
+                                                                          const u64 *__restrict__ constant, int const_mode,
+                                                                          u64 *out, std::size_t out_sum_stride,
+                                                                          const PrimeDev *__restrict__ primes, RowMap map, int logn,
+                                                                          std::size_t npairs_per_item, std::size_t count,
+                                                                          unsigned *tflags, std::size_t flag_sum_stride,
+                                                                          int add_partial)
+        {
+            const std::size_t total = npairs_per_item * count;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t nmask = (static_cast<std::size_t>(1) << logn) - 1;
+            const int k = map.rows;
+            // a row is 2^(logn - 1) pairs: from kThreads pairs per row on, a block covers pairs of ONE row of one item
+            const bool block_in_row = (static_cast<std::size_t>(1) << logn) >= 2 * static_cast<std::size_t>(kThreads);
+            for (std::size_t base = blockIdx.x * static_cast<std::size_t>(blockDim.x); base < total; base += stride)
+            {
+                const std::size_t i = base + threadIdx.x;
+                if (i >= total)
+                    continue;
+                if (block_in_row)
+                {
+                    const std::size_t item = base / npairs_per_item; // (uniform: what the block's first pair says)
+                    const std::size_t row = (2 * (base - item * npairs_per_item)) >> logn;
+                    const int j = static_cast<int>(row / k), r = static_cast<int>(row % k);
+                    const unsigned short pid = map.prime[r];
+                    if (pid == kSkipRow)
+                        continue;
+                    const std::size_t off = 2 * (i - item * npairs_per_item);
+                    const bool k_x = j == 0 && (const_mode == 2 || (off & nmask) == 0), k_y = j == 0 && const_mode == 2;
+                    lincomb_levels_lane<S, true>(terms, item, j, r, off & nmask, logn, w + r, k, w_sum_stride,
+                                                 constant != nullptr && j == 0 ? constant + r : nullptr, k_x, k_y, primes[pid].p,
+                                                 primes[pid].cr0, primes[pid].cr1, out + item * out_stride + off, out_sum_stride,
+                                                 add_partial, j == 0 ? nullptr : tflags, flag_sum_stride);
+                }
+                else
+                {
+                    const std::size_t item = i / npairs_per_item;
+                    const std::size_t off = 2 * (i - item * npairs_per_item);
+                    const std::size_t row = off >> logn;
+                    const int j = static_cast<int>(row / k), r = static_cast<int>(row % k);
+                    const unsigned short pid = map.prime[r];
+                    if (pid == kSkipRow)
+                        continue;
+                    const bool k_x = j == 0 && (const_mode == 2 || (off & nmask) == 0), k_y = j == 0 && const_mode == 2;
+                    lincomb_levels_lane<S, false>(terms, item, j, r, off & nmask, logn, w + r, k, w_sum_stride,
+                                                  constant != nullptr && j == 0 ? constant + r : nullptr, k_x, k_y, primes[pid].p,
+                                                  primes[pid].cr0, primes[pid].cr1, out + item * out_stride + off, out_sum_stride,
+                                                  add_partial, j == 0 ? nullptr : tflags, flag_sum_stride);
+                }
+            }
+        }
+
         // The tables of a polynomial's inner sums from its coefficients mod t (launch_poly_tables). One lane per (coefficient,
         // row): the weight is plain_lift_centered_kernel's word, the constant scaling_variant_kernel's at coefficient 0.
         constexpr int kPolyCoeffChunk = 64;
@@ -721,6 +844,56 @@ namespace sealhip
         return hipGetLastError();
     }
 
+    namespace
+    {
+        template <int S>
+        void lincomb_levels_launch(const Engine &e, unsigned grid, const LinLevelTerms &terms, std::size_t out_stride, const u64 *w,
+                                   std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out,
+                                   std::size_t out_sum_stride, const RowMap &map, std::size_t pairs, std::size_t count,
+                                   bool add_partial, std::size_t flag_sum_stride)
+        {
+            if constexpr (S <= kLinLevelsTile) // (a smaller tile instantiates fewer kernels)
+                lincomb_levels_kernel<S><<<grid, kThreads, 0, e.lane().stream>>>(terms, out_stride, w, w_sum_stride, constant,
+                                                                                 const_mode, out, out_sum_stride, e.d_primes, map,
+                                                                                 e.logn, pairs, count, e.lane().tsink_arm,
+                                                                                 flag_sum_stride, add_partial ? 1 : 0);
+        }
+    } // namespace
+
+    hipError_t launch_lincomb_levels(const Engine &e, const LinLevelTerms &terms, int size, std::size_t out_stride, const u64 *w,
+                                     std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out,
+                                     std::size_t out_sum_stride, int n_sums, std::size_t count, const RowMap &map,
+                                     bool add_partial, std::size_t flag_sum_stride)
+    {
+        static_assert(bounds::lincomb_group_admits(kLinGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
+        static_assert(kLinLevelsTile <= 4, "the dispatch below has one instance per tile size");
+        if (terms.n < 1 || terms.n > kLinGroup || n_sums < 1 || n_sums > kLinLevelsTile || size < 1 || map.rows < 1 ||
+            map.rows > kMaxRows || (constant && const_mode != 1 && const_mode != 2))
+            return hipErrorInvalidValue;
+        for (int t = 0; t < terms.n; t++) // (what keeps every load inside its term)
+            if (terms.rows[t] < map.rows || terms.size[t] < 1 || terms.size[t] > size)
+                return hipErrorInvalidValue;
+        const std::size_t pairs = (static_cast<std::size_t>(size) * map.rows << e.logn) / 2;
+        if (pairs * count == 0)
+            return hipSuccess;
+        ProfScope prof(e, "lincomb_levels", 0);
+        const unsigned grid = grid_for(pairs * count);
+#define SEALHIP_LINCOMB_CASE(S)                                                                                              \
+    case S:                                                                                                                  \
+        lincomb_levels_launch<S>(e, grid, terms, out_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, map, \
+                                 pairs, count, add_partial, flag_sum_stride);                                                \
+        break;
+        switch (n_sums)
+        {
+            SEALHIP_LINCOMB_CASE(1)
+            SEALHIP_LINCOMB_CASE(2)
+            SEALHIP_LINCOMB_CASE(3)
+            SEALHIP_LINCOMB_CASE(4)
+        }
+#undef SEALHIP_LINCOMB_CASE
+        return hipGetLastError();
+    }
+
     hipError_t launch_poly_tables(const Engine &e, int k, const u64 *coeffs, std::size_t n_coeffs, std::size_t ms, u64 *w,
                                   u64 *constant)
     {
@@ -775,6 +948,34 @@ namespace sealhip
             rv.v[r] = row_values[r];
         ProfScope prof(e, "fill_rows", 0);
         fill_rows_kernel<<<grid_for(npairs), kThreads, 0, e.lane().stream>>>(dst, rv, rows, e.logn, npairs);
+        return hipGetLastError();
+    }
+
+    namespace
+    {
+        struct PutWords
+        {
+            u64 v[kPutWords];
+        };
+        __global__ __launch_bounds__(kThreads) void put_words_kernel(u64 *__restrict__ dst, PutWords words, int n)
+        {
+            const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+            if (i < n)
+                dst[i] = words.v[i];
+        }
+    } // namespace
+
+    hipError_t launch_put_words(const Engine &e, u64 *dst, const u64 *words, std::size_t n)
+    {
+        ProfScope prof(e, "put_words", 0);
+        for (std::size_t first = 0; first < n; first += kPutWords)
+        {
+            PutWords pw{};
+            const int m = static_cast<int>(std::min<std::size_t>(kPutWords, n - first));
+            for (int i = 0; i < m; i++)
+                pw.v[i] = words[first + i];
+            put_words_kernel<<<grid_for(static_cast<std::size_t>(m)), kThreads, 0, e.lane().stream>>>(dst + first, pw, m);
+        }
         return hipGetLastError();
     }
 

@@ -1315,6 +1315,49 @@ namespace sealhip_host
             evaluate_polynomial(encrypted, coeffs, relin_keys, encrypted);
         }
 
+        // CKKS: destination = p(encrypted) with planned levels and scales (sealhip_evaluator_evaluate_polynomial_ckks, DESIGN.md
+        // section 21). coeffs are doubles, lowest degree first, in the monomial basis (basis 0) or the Chebyshev basis of
+        // the first kind (basis 1, for messages in [-1, 1]); a size-2 operand in NTT form; relin_keys as above. The
+        // destination gets the plan's level (sealhip_evaluator_polynomial_plan_ckks: "end of modulus switching chain
+        // reached" when the operand's level is too low for the degree) and the scale scale_out, or the operand's scale when
+        // scale_out is 0 -- exactly, by construction. The words are those of tests/poly_eval_ckks_ref.py.
+        template <class C, IfCt<C> = 0>
+        void evaluate_polynomial(const C &encrypted, const std::vector<double> &coeffs,
+                                 const std::vector<const KSwitchKeys *> &relin_keys, C &destination, std::uint32_t basis = 0,
+                                 double scale_out = 0.0)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme");
+            if (!encrypted.is_ntt_form())
+                throw std::invalid_argument("CKKS encrypted must be in NTT form");
+            if (encrypted.size() != 2)
+                throw std::invalid_argument("encrypted size must be 2");
+            if (coeffs.empty())
+                throw std::invalid_argument("coeffs must not be empty");
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            sealhip_poly_plan plan{};
+            throw_on(sealhip_evaluator_polynomial_plan_ckks(ctx_.get(), std::uint32_t(k), encrypted.scale(), coeffs.data(),
+                                                            std::uint32_t(coeffs.size() - 1), basis, 0, scale_out, &plan, nullptr,
+                                                            nullptr));
+            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * std::size_t(plan.out_level) * n);
+            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_evaluate_polynomial_ckks(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(),
+                                                                coeffs.data(), std::uint32_t(coeffs.size() - 1), basis, 0, scale_out,
+                                                                raw ? &raw : nullptr, raw ? 1u : 0u, o.ptr(), nullptr, nullptr));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, plan.out_level);
+            destination.scale() = plan.out_scale;
+        }
+        template <class C, IfCt<C> = 0>
+        void evaluate_polynomial_inplace(C &encrypted, const std::vector<double> &coeffs,
+                                         const std::vector<const KSwitchKeys *> &relin_keys, std::uint32_t basis = 0,
+                                         double scale_out = 0.0)
+        {
+            evaluate_polynomial(encrypted, coeffs, relin_keys, encrypted, basis, scale_out);
+        }
+
         // relinearize + rescale_to_next in one call and with one rounding (sealhip_evaluator_relinearize_rescale, DESIGN.md
         // section 19): CKKS only, a size-3 operand in NTT form, relin_keys as relinearize_inplace takes them (index 0 is
         // read); "end of modulus switching chain reached" at the last level. The result has size 2, one level down, with

@@ -52,6 +52,14 @@ _lib = None
 
 # every symbol include/sealhip.h declares: name -> argtypes (restype is always long unless noted)
 _vp, _u32, _u64, _sz, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int32
+
+
+class PolyPlan(C.Structure):
+    """sealhip_poly_plan (include/sealhip.h)"""
+    _fields_ = [("d", _u32), ("m", _u32), ("g", _u32), ("inner_level", _u32), ("out_level", _u32), ("n_products", _u32),
+                ("out_scale", C.c_double), ("temp_bytes_per_item", _u64)]
+
+
 SYMBOLS = {
     "sealhip_last_error_string": None,
     "sealhip_num_devices": [C.POINTER(C.c_int32)],
@@ -142,6 +150,13 @@ SYMBOLS = {
     "sealhip_evaluator_dot_product_max_terms": [_vp, _u32, C.POINTER(C.c_uint64)],
     "sealhip_evaluator_dot_product": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_linear_combination": [_vp, _u32, C.POINTER(_vp), _u32, _u32, _sz, _vp, _vp, _u32, _vp],
+    "sealhip_evaluator_polynomial_plan_ckks": [_vp, _u32, C.c_double, C.POINTER(C.c_double), _u32, _u32, _u32, C.c_double, _vp,
+                                               C.POINTER(_u64), C.POINTER(_u64)],
+    "sealhip_evaluator_evaluate_polynomial_ckks": [_vp, _u32, _vp, _sz, C.c_double, C.POINTER(C.c_double), _u32, _u32, _u32,
+                                                   C.c_double, C.POINTER(_vp), _u32, _vp, C.POINTER(_u32),
+                                                   C.POINTER(C.c_double)],
+    "sealhip_evaluator_linear_combination_levels": [_vp, _u32, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _sz,
+                                                    _vp, _vp, _u32, _vp],
     "sealhip_evaluator_evaluate_polynomial": [_vp, _u32, _vp, _sz, C.POINTER(C.c_uint64), _u32, _u32, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_relinearize_rescale": [_vp, _u32, _vp, _u32, _sz, _sz, C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_dot_product_rescale": [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), _u32, _sz, C.POINTER(_vp), _u32, _vp],
@@ -1033,6 +1048,63 @@ class Evaluator:
         pt = (_vp * max(1, len(terms)))(*[_ptr(c) for c in terms])
         _check(lib().sealhip_evaluator_linear_combination(self.ctx.handle, k, pt, len(terms), size, count, _ptr(weights),
                                                           _ptr(constant) if constant is not None else None, n_sums, _ptr(out)))
+
+    def linear_combination_levels(self, terms, term_levels, term_sizes, weights, k, count, out, size=2, n_sums=1, constant=None):
+        """linear_combination over CKKS terms that keep their own level and size (sealhip_evaluator_linear_combination_levels,
+        DESIGN.md section 21): terms[i] is a device batch count x term_sizes[i] x term_levels[i] x N with term_levels[i] >= k
+        and term_sizes[i] <= size, read in place at its first k rows; a term of fewer polynomials contributes nothing to the
+        others. weights, constant and out are laid out at level k as for linear_combination. One term with weight 1 is
+        mod_switch_to level k in one pass."""
+        if not len(terms) == len(term_levels) == len(term_sizes):
+            raise ValueError("terms, term_levels and term_sizes differ in length")
+        n = max(1, len(terms))
+        pt = (_vp * n)(*[_ptr(c) for c in terms])
+        lv, sz = (_u32 * n)(*[int(v) for v in term_levels]), (_u32 * n)(*[int(v) for v in term_sizes])
+        _check(lib().sealhip_evaluator_linear_combination_levels(self.ctx.handle, k, pt, lv, sz, len(terms), size, count,
+                                                                 _ptr(weights), _ptr(constant) if constant is not None else None,
+                                                                 n_sums, _ptr(out)))
+
+    def polynomial_plan_ckks(self, k, scale, coeffs, basis=0, n_baby=0, scale_out=0.0, tables=True):
+        """The plan of evaluate_polynomial_ckks (sealhip_evaluator_polynomial_plan_ckks); works on a
+        host-only context. Returns a dict: d, m, g, inner_level, out_level, n_products, out_scale, temp_bytes_per_item and,
+        with tables, the inner sums' weights [g][m - 1][inner_level] and constants [g][inner_level] as uint64 arrays (rows of
+        sums that are not formed are zero)."""
+        coeffs = [float(c) for c in coeffs]
+        if not coeffs:
+            raise ValueError("coeffs must not be empty")
+        ca = (C.c_double * len(coeffs))(*coeffs)
+        plan = PolyPlan()
+        fn = lib().sealhip_evaluator_polynomial_plan_ckks
+        _check(fn(self.ctx.handle, k, scale, ca, len(coeffs) - 1, basis, n_baby, scale_out, C.addressof(plan), None, None))
+        out = {name: getattr(plan, name) for name, _ in PolyPlan._fields_}
+        if tables:
+            w = np.zeros((plan.g, plan.m - 1, plan.inner_level), dtype=np.uint64)
+            kc = np.zeros((plan.g, plan.inner_level), dtype=np.uint64)
+            _check(fn(self.ctx.handle, k, scale, ca, len(coeffs) - 1, basis, n_baby, scale_out, C.addressof(plan),
+                      w.ctypes.data_as(C.POINTER(_u64)), kc.ctypes.data_as(C.POINTER(_u64))))
+            out["weights"], out["constants"] = w, kc
+        return out
+
+    def evaluate_polynomial_ckks(self, ct, coeffs, k, count, scale, out, relin_keys=None, basis=0, n_baby=0, scale_out=0.0):
+        """p(ct) on CKKS ciphertexts with planned levels and scales (sealhip_evaluator_evaluate_polynomial_ckks, DESIGN.md
+        section 21): ct a device batch count x 2 x k x N at `scale`, coeffs host doubles (lowest degree first) in the monomial
+        (basis 0) or the Chebyshev basis (1, messages in [-1, 1]); out: count x 2 x out_level x N (polynomial_plan_ckks says
+        which level). relin_keys (a list of KSwitchKeys, index 0 is read) may be None for degree one. Returns (out_level,
+        out_scale); out_scale is scale_out, or the input scale when that is 0. The words are those of
+        tests/poly_eval_ckks_ref.py."""
+        coeffs = [float(c) for c in coeffs]
+        if not coeffs:
+            raise ValueError("coeffs must not be empty")
+        ca = (C.c_double * len(coeffs))(*coeffs)
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        level, result_scale = _u32(0), C.c_double(0.0)
+        _check(lib().sealhip_evaluator_evaluate_polynomial_ckks(self.ctx.handle, k, _ptr(ct), count, scale, ca, len(coeffs) - 1,
+                                                                basis, n_baby, scale_out, keys,
+                                                                len(relin_keys) if relin_keys is not None else 0, _ptr(out),
+                                                                C.byref(level), C.byref(result_scale)))
+        return level.value, result_scale.value
 
     def evaluate_polynomial(self, ct, coeffs, k, count, out, relin_keys=None, n_baby=0):
         """p(ct) = sum_e coeffs[e] ct^e by Paterson-Stockmeyer (sealhip_evaluator_evaluate_polynomial):

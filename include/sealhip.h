@@ -637,6 +637,29 @@ long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, cons
                                           uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
                                           uint32_t n_sums, uint64_t *out);
 
+/* The same sums over CKKS terms that keep their own level and size, both modes. A CKKS
+   mod_switch_to_next only drops the last row, so a ciphertext at level k_t >= k holds the level-k ciphertext in place: the
+   kernel reads rows r < k of every polynomial at the term's own row stride, and nothing is dropped to level k by a copy
+   first. term_levels, term_sizes: HOST arrays of n_terms entries; term i is a device batch count x term_sizes[i] x
+   term_levels[i] x N in NTT form, with k <= term_levels[i] <= the first level and 2 <= term_sizes[i] <= size; a term of fewer
+   polynomials than size contributes nothing to the others. weights, constant and out are laid out at level k exactly as for
+   sealhip_evaluator_linear_combination, and so are the capacity of a launch (16 terms, 4 sums) and the arithmetic per word.
+   The words are those of the composition: drop each term to its first k rows, pad it with zero polynomials to size, then
+   tests/poly_eval_ref.linear_combination; with every term at level k and size `size` they are those of
+   sealhip_evaluator_linear_combination. One term with weight 1 is a one-pass mod_switch_to any lower level.
+   Checks: NULL pointers (ctx, weights, out; with n_terms > 0 terms, each of its entries, term_levels, term_sizes) ->
+   E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, a BFV context ("CKKS only": a BFV
+   mod_switch_to_next is not a row drop), a term level below k or above the first level, size < 2 or > 16, a term size
+   < 2 or > size, n_terms == 0 or n_sums == 0 with count > 0, out overlapping a term or a table -> E_INVALIDARG; then
+   count == 0 -> S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION.
+   Runs on the calling thread's lane, takes nothing from the arena and synchronises nothing; pointers, levels and sizes
+   travel in kernel arguments, so the call is capturable after one warm-up call. Transparency flags as for
+   sealhip_evaluator_linear_combination. */
+long sealhip_evaluator_linear_combination_levels(sealhip_context *ctx, uint32_t k, const uint64_t *const *terms,
+                                                 const uint32_t *term_levels, const uint32_t *term_sizes, uint32_t n_terms,
+                                                 uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
+                                                 uint32_t n_sums, uint64_t *out);
+
 /* Polynomial evaluation on ciphertexts: out = p(ct) = sum_e coeffs[e] ct^e by Paterson-Stockmeyer
    over the two entries above. BFV in STRICT mode. ct: count x 2 x k x N, coefficient form, not modified; out: count x 2 x k
    x N, overlapping nothing; both device memory. coeffs: HOST memory, degree + 1 words below t, shared by the batch.
@@ -662,11 +685,64 @@ long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, cons
    of the context's pool (sealhip_pool_*), taken and released in stream order on the calling lane, and the coefficients
    travel in kernel arguments: nothing synchronises, but unlike sealhip_evaluator_linear_combination this entry allocates
    (until the pool is warm) and is therefore NOT capturable. With a transparency sink: one flag per output ciphertext, from the kernel that stores out (g == 1) or a
-   read pass over it. CKKS polynomial evaluation needs per-power scale and level bookkeeping and is not offered;
-   sealhip_evaluator_linear_combination is its building block. */
+   read pass over it. CKKS polynomial evaluation needs per-power scale and level bookkeeping: it is
+   sealhip_evaluator_evaluate_polynomial_ckks below. */
 long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
                                            const uint64_t *coeffs, uint32_t degree, uint32_t n_baby,
                                            const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out);
+
+/* Polynomial evaluation on CKKS ciphertexts with planned levels and scales, both modes:
+   out = p(ct), p = sum_e coeffs[e] x^e (basis 0) or sum_e coeffs[e] T_e(x) (basis 1: Chebyshev polynomials of the first kind,
+   for messages in [-1, 1]), by Paterson-Stockmeyer. The plan -- gemini-seal_amd/csrc/poly_plan.hpp, restated in
+   tests/poly_eval_ckks_ref.py, which also defines the words -- with d the degree after trimming trailing zeros, m = n_baby
+   or ceil(sqrt(d + 1)), g = ceil((d + 1) / m), delta(e) = ceil(log2 e), s the input scale and dbl(q) a prime as a double
+   (all scale arithmetic is IEEE double in the order written):
+     baby elements E_1 = ct, E_e from E_hi, E_lo (hi = ceil(e/2), lo = floor(e/2)) at level L = lev(hi), 2 <= e <= min(m, d):
+                   monomial   E_e = dot_product_rescale({E_hi}, {E_lo});
+                   Chebyshev  E_e = relinearize_rescale(2 E_hi E_lo - T_{hi-lo}), the subtraction BEFORE the rescale with the
+                              integer rint(sc(hi) sc(lo)) (a constant, hi == lo) or rint(sc(hi) sc(lo) / sc(1)) (the weight of
+                              E_1, read in place at level L) in one sealhip_evaluator_linear_combination_levels;
+                   lev(e) = k - delta(e), sc(e) = sc(hi) sc(lo) / dbl(q_{L-1});
+     chunks        monomial: c_{jm} .. c_{jm+m-1}; Chebyshev: the T_m-adic expansion p = sum_j r_j(x) T_m(x)^j by repeated
+                   division by T_m (the chunk coefficients grow by up to about 2^(g-1));
+     giant powers  Y_1 = E_m, Y_j = dot_product_rescale({Y_hi}, {Y_lo}) at level k - delta(m) - delta(j), only those needed;
+     inner sums    with mi = m - 1, L_in = k - delta(mi), J the j >= 1 whose chunk is not identically zero, L_out =
+                   min(L_in - 1, min_J lev(Y_j)), Sigma = scale_out dbl(q_{L_out-1}), tau_j = Sigma / sc(Y_j), tau_0 =
+                   scale_out: the weight of E_i in sum j is rint(chunk_j[i] (tau_j dbl(q_{L_in-1}) / sc(i))), its constant
+                   rint(chunk_j[0] (tau_j dbl(q_{L_in-1}))); all sums of {0} u J in ONE linear_combination_levels at level
+                   L_in over E_1 .. E_mi, each read at its own level, then ONE rescale_to_next of the whole batch;
+     result        I_0 (level L_in - 1) when J is empty, else dot_product_rescale({Y_j}, {I_j}, j in J) at level L_out plus
+                   I_0 at level L_out - 1. Its scale is scale_out exactly, by construction.
+   rint rounds half to even; the integer is reduced per prime exactly, whatever its size.
+   The plan query fills *plan and, when not NULL, the HOST tables inner_weights [g][m - 1][inner_level] and inner_constants
+   [g][inner_level] (rows of sums that are not formed stay zero); it works on host-only contexts. temp_bytes_per_item: the
+   pool blocks the evaluation takes per item of the batch (the small tables, a few KiB per call, are not counted).
+   coeffs: HOST doubles, degree + 1 of them. scale_out: 0 means the input scale. ct: count x 2 x k x N (NTT form, not
+   modified); out: count x 2 x out_level x N, overlapping nothing; *out_level and *out_scale (may be NULL) get the plan's.
+   Checks, in this order: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, a BFV
+   context ("CKKS only"), a non-finite or non-positive scale, a non-finite coefficient, basis > 1, d < 1, n_baby == 1 or
+   > d + 1, out_level < 1 ("end of modulus switching chain reached"), with d >= 2 missing keys or a key with fewer digits
+   than level k needs, out overlapping ct -> E_INVALIDARG; then count == 0 -> S_OK; then a host-only context ->
+   COR_E_INVALIDOPERATION. (The plan query has no keys, no buffers and no batch: its checks end with out_level.)
+   Temporaries are blocks of the context's pool, taken and released in stream order on the calling lane; the tables travel
+   in kernel arguments: nothing synchronises, but the entry may allocate and is NOT capturable. With a transparency sink: one
+   flag per output ciphertext from a read pass over out. */
+typedef struct sealhip_poly_plan
+{
+    uint32_t d, m, g;
+    uint32_t inner_level; /* L_in: the level the inner sums are formed at */
+    uint32_t out_level;
+    uint32_t n_products;  /* key-switched products: baby elements, giant powers, the outer sum */
+    double out_scale;
+    uint64_t temp_bytes_per_item;
+} sealhip_poly_plan;
+long sealhip_evaluator_polynomial_plan_ckks(sealhip_context *ctx, uint32_t k, double scale, const double *coeffs, uint32_t degree,
+                                            uint32_t basis, uint32_t n_baby, double scale_out, sealhip_poly_plan *plan,
+                                            uint64_t *inner_weights, uint64_t *inner_constants);
+long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale,
+                                                const double *coeffs, uint32_t degree, uint32_t basis, uint32_t n_baby,
+                                                double scale_out, const sealhip_kswitch_key *const *relin_keys,
+                                                uint32_t n_relin_keys, uint64_t *out, uint32_t *out_level, double *out_scale);
 
 /* ---------------------------------------------------------------- decrypt-side arithmetic */
 /* Decryptor::dot_product_ct_sk_array (decryptor.cpp:218-265): out[count][k][N] = c_0 + sum_{i>=1} c_i * s^i, in the form
