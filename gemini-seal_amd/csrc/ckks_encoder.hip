@@ -177,25 +177,27 @@ namespace sealhip
                 g[i] = tile[i];
         }
 
-        // ckks.h:484-607: scale, record the largest bit count, round to nearest (ties away from zero), reduce the exact
+        // ckks.h:484-607: scale, record the largest magnitude, round to nearest (ties away from zero), reduce the exact
         // integer modulo every prime and put the sign back. A rounded double is m * 2^e with a 53-bit m, so the
         // multi-precision decomposition of the slow path (:569-607) is m * (2^64)^(e/64) * 2^(e%64) mod q_j -- the same
         // canonical residue every one of the reference's three paths yields.
+        // The bit count of :498-499 is static_cast<int>(log2(d)) + 2 of the largest d = max(|x|, 1). The kernel hands back
+        // that d (max_abs holds its bit pattern, which orders like the value for positive doubles) and op_ckks_encode takes
+        // the logarithm with the host's libm, as the reference does: the exponent read here (ilogb) would be one less for
+        // a d a few ulps below a power of two, where log2 rounds up to the integer.
         __global__ __launch_bounds__(kThreads) void ckks_round_decompose_kernel(const double2 *__restrict__ cv, double n_inv,
                                                                                 u64 *__restrict__ out, int rows,
                                                                                 const PrimeDev *__restrict__ primes, int logn,
-                                                                                int *__restrict__ max_bits, std::size_t total)
+                                                                                unsigned long long *__restrict__ max_abs, std::size_t total)
         {
             const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
             const std::size_t n = std::size_t(1) << logn;
-            int local_max = 1;
+            double local_max = 1.0;
             for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
             {
                 const std::size_t item = i >> logn, c = i & (n - 1);
                 const double x = cv[i].x * n_inv;
-                const double d = fmax(fabs(x), 1.0);
-                const int bits = ilogb(d) + 2; // static_cast<int>(log2(d)) + 2, :498-499
-                local_max = bits > local_max ? bits : local_max;
+                local_max = fmax(local_max, fabs(x)); // max(|x|, 1) of :498; a NaN leaves it, as fmax does there
                 const double r = round(x);
                 const bool negative = signbit(r);
                 const double a = fabs(r);
@@ -227,8 +229,8 @@ namespace sealhip
                     dst[static_cast<std::size_t>(j) << logn] = negative ? neg_mod(v, P.p) : v;
                 }
             }
-            if (local_max > 1)
-                atomicMax(max_bits, local_max);
+            if (local_max > 1.0)
+                atomicMax(max_abs, static_cast<unsigned long long>(__double_as_longlong(local_max)));
         }
 
         // RNSBase::compose_array (rns.cpp:401-450) + ckks.h:681-720: CRT-compose a coefficient into K limbs, compare
@@ -378,7 +380,7 @@ namespace sealhip
 
     hipError_t launch_ckks_encode_front(const Engine &e, const double *values, std::size_t n_values, std::size_t count,
                                         double n_inv_scale, double *cv, u64 *out, int rows, const std::uint32_t *map,
-                                        const double *inv_roots, int *max_bits)
+                                        const double *inv_roots, unsigned long long *max_abs)
     {
         const std::size_t total = count << e.logn;
         if (!total)
@@ -391,7 +393,7 @@ namespace sealhip
         if (err != hipSuccess)
             return err;
         ckks_round_decompose_kernel<<<grid_for(total, kMaxBlocks), kThreads, 0, e.lane().stream>>>(c2, n_inv_scale, out, rows, e.d_primes, e.logn,
-                                                                                max_bits, total);
+                                                                                max_abs, total);
         return hipGetLastError();
     }
 

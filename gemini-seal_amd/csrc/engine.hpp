@@ -952,7 +952,7 @@ namespace sealhip
     // CKKSEncoder (ckks_encoder.hip)
     hipError_t launch_ckks_encode_front(const Engine &e, const double *values, std::size_t n_values, std::size_t count,
                                         double n_inv_scale, double *cv, u64 *out, int rows, const std::uint32_t *map,
-                                        const double *inv_roots, int *max_bits);
+                                        const double *inv_roots, unsigned long long *max_abs);
     hipError_t launch_ckks_decode_back(const Engine &e, const u64 *coeff, const CkksDecodeDev *d, int k, std::size_t count,
                                        double inv_scale, double *res, double *values, const std::uint32_t *map,
                                        const double *roots);

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace sealhip
@@ -2252,20 +2253,26 @@ namespace sealhip
         const std::size_t N = e.n;
         double n_inv = 1.0 / static_cast<double>(N); // :484-487
         n_inv *= scale;
-        int h_max = 1;
+        // :489-504: the bit count is static_cast<int>(log2(d)) + 2 of the largest d = max(|coefficient|, 1). The device finds
+        // d, the logarithm is the host's libm's (where the root tables come from too): a d a few ulps below 2^j has
+        // log2(d) == j there, and an exponent or a logarithm taken on the device need not agree with it in that last bit.
+        double h_max = 1.0;
         for_chunks(e, count, N * 2 * sizeof(double), 2, [&](std::size_t off, std::size_t m) {
-            int *d_max = reinterpret_cast<int *>(e.ws_alloc(1));
+            unsigned long long *d_max = reinterpret_cast<unsigned long long *>(e.ws_alloc(1));
             double *cv = reinterpret_cast<double *>(e.ws_alloc(2 * N * m));
-            SEALHIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(int), e.lane().stream));
+            SEALHIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(unsigned long long), e.lane().stream));
             check(launch_ckks_encode_front(e, values + off * n_values * 2, n_values, m, n_inv, cv,
                                            plain + off * static_cast<std::size_t>(k) * N, k, e.d_ckks_map, e.d_ckks_inv_roots, d_max),
                   "ckks encode");
-            int got = 0;
-            SEALHIP_CHECK(hipMemcpyAsync(&got, d_max, sizeof(int), hipMemcpyDeviceToHost, e.lane().stream));
+            unsigned long long got = 0;
+            SEALHIP_CHECK(hipMemcpyAsync(&got, d_max, sizeof(got), hipMemcpyDeviceToHost, e.lane().stream));
             SEALHIP_CHECK(hipStreamSynchronize(e.lane().stream));
-            h_max = std::max(h_max, got);
+            double d;
+            std::memcpy(&d, &got, sizeof(d)); // (0 when no coefficient exceeds 1)
+            h_max = std::max(h_max, d);
         });
-        if (h_max >= total_bits)
+        // (an infinite coefficient is too large whatever the cast of log2(inf) would give)
+        if (!std::isfinite(h_max) || static_cast<int>(std::log2(h_max)) + 2 >= total_bits)
             throw std::invalid_argument("encoded values are too large"); // :501-504
         check(launch_ntt(e, plain, count * k, map_q, false, kNttCanonical), "ntt(plain)"); // :609-613
     }
