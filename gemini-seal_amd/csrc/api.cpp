@@ -174,10 +174,61 @@ namespace
         return e;
     }
 
+    // The rules the entries share. A new entry calls these; it does not restate them.
+    // any level up to the key level (k data primes or all n_key key primes): the low-level entries
     void check_level(const Engine &e, uint32_t k)
     {
         if (k < 1 || static_cast<int>(k) > e.n_key)
             throw std::invalid_argument("level k out of range");
+    }
+
+    // a ciphertext level, 1 .. first data level: the Evaluator entries that check before they need a device
+    void check_data_level(const Engine &h, uint32_t k)
+    {
+        if (k < 1 || static_cast<int>(k) > h.k_first)
+            throw std::invalid_argument("level k out of range");
+    }
+
+    // the first checks of every *_rescale entry, ahead of the unmerged entry's own: CKKS only, 2 <= k <= first level
+    void check_rescale_level(const Engine &h, uint32_t k)
+    {
+        if (h.scheme != 2)
+            throw std::invalid_argument("the merged rescale is CKKS only");
+        check_data_level(h, k);
+        if (k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached"); // evaluator.cpp:1005-1008
+    }
+
+    uint32_t kswitch_digits(const Engine &h, uint32_t k)
+    {
+        return (k + h.nsp - 1) / h.nsp; // decomposition digits of a key switch at level k, keygenerator.cpp:334-336
+    }
+
+    void check_key_digits(const Engine &h, uint32_t k, const sealhip_kswitch_key *key)
+    {
+        if (key->key.n_digits < kswitch_digits(h, k))
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+    }
+
+    // the key of sk^2, checked; the caller asks only when it needs one (a null list may mean "leave the result at size 3")
+    const KSwitchKey *first_relin_key(const Engine &h, uint32_t k, const sealhip_kswitch_key *const *relin_keys,
+                                      uint32_t n_relin_keys)
+    {
+        if (!relin_keys || n_relin_keys == 0)
+            throw std::invalid_argument("not enough relinearization keys"); // evaluator.cpp:793-796
+        check_key_digits(h, k, relin_keys[0]);
+        return &relin_keys[0]->key;
+    }
+
+    void check_galois_elt(const Engine &h, uint32_t elt)
+    {
+        if (!(elt & 1) || elt >= 2 * h.n)
+            throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
+    }
+
+    bool words_overlap(const u64 *a, std::size_t a_words, const u64 *b, std::size_t b_words)
+    {
+        return a < b + b_words && b < a + a_words;
     }
 
     void ntt_entry(sealhip_context *ctx, uint64_t *data, size_t count, uint32_t k, uint32_t base, bool inverse,
@@ -218,6 +269,37 @@ namespace
         while (s--)
             elt = (elt * 5) & (m - 1);
         return static_cast<uint32_t>(elt);
+    }
+
+    // steps -> elements and their keys out of the caller's key list; step 0 gets `identity` (evaluator.cpp:1958-1962) and no key
+    void keys_for_steps(const Engine &h, const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
+                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint32_t identity,
+                        std::vector<uint32_t> &elts, std::vector<const sealhip_kswitch_key *> &keys)
+    {
+        elts.assign(n_steps, identity);
+        keys.assign(n_steps, nullptr);
+        for (uint32_t s = 0; s < n_steps; s++)
+        {
+            if (steps[s] == 0)
+                continue;
+            elts[s] = host_galois_elt_from_step(h.n, steps[s]);
+            for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
+                if (galois_elts[i] == elts[s])
+                    keys[s] = galois_keys[i];
+            if (!keys[s])
+                throw std::invalid_argument("Galois key not present");
+        }
+    }
+
+    // the pipelines' key list: null where the element is the identity
+    std::vector<const KSwitchKey *> run_keys(const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys,
+                                             uint32_t identity)
+    {
+        std::vector<const KSwitchKey *> r(elts.size(), nullptr);
+        for (size_t i = 0; i < elts.size(); i++)
+            if (elts[i] != identity)
+                r[i] = &keys[i]->key;
+        return r;
     }
 
     LevelTools &bfv_level(Engine &e, uint32_t k)
@@ -806,8 +888,7 @@ static long galois_entry(sealhip_context *ctx, const uint64_t *in, size_t count,
         check_level(e, k);
         if (in == out)
             throw std::invalid_argument("result cannot point to the same value as operand"); // galois.cpp:156-159
-        if (!(galois_elt & 1) || galois_elt >= 2 * e.n)
-            throw std::invalid_argument("Galois element is not valid");
+        check_galois_elt(e, galois_elt);
         const RowMap map = e.map_for(static_cast<int>(k), SEALHIP_BASE_Q);
         const uint32_t *table = ntt_form ? e.galois_table(galois_elt) : nullptr;
         check(launch_galois(e, reinterpret_cast<const u64 *>(in), reinterpret_cast<u64 *>(out), count * k, map,
@@ -836,8 +917,7 @@ long sealhip_kswitch_key_load(sealhip_context *ctx, const uint64_t *key, uint32_
     *out = nullptr;
     return guarded([&] {
         Engine &e = device_engine(ctx);
-        const uint32_t max_digits = static_cast<uint32_t>((e.k_first + e.nsp - 1) / e.nsp); // keygenerator.cpp:334-336
-        if (n_digits == 0 || n_digits > max_digits)
+        if (n_digits == 0 || n_digits > kswitch_digits(e, static_cast<uint32_t>(e.k_first)))
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         auto k = std::make_unique<sealhip_kswitch_key>();
         k->key.n_digits = n_digits;
@@ -958,61 +1038,12 @@ long sealhip_kswitch_digits(sealhip_context *ctx, uint32_t k, uint32_t *digits)
         check_level(e, k);
         if (static_cast<int>(k) > e.k_first)
             throw std::invalid_argument("key switching needs a ciphertext level");
-        *digits = static_cast<uint32_t>((static_cast<int>(k) + e.nsp - 1) / e.nsp); // keygenerator.cpp:334-336
+        *digits = kswitch_digits(e, k);
     });
 }
 
 namespace
 {
-    // Transparency as a flag output (sealhip_transparency_sink): an Evaluator entry clears the flags of its batch, then either
-    // lets the final kernel of the operation write them (fused: multiply, square, relinearize, apply_galois) or runs the
-    // read pass over its result (the remaining entries).
-    // Order of effects: the constructor VALIDATES the capacity and nothing else, so an entry can build its
-    // scope before its first launch and a call rejected for any reason leaves both the data and the caller's flags as they
-    // were. The flags are cleared where they start to be written: by begin() (fused entries call it after their argument
-    // checks, right before the operation), by arm() (relinearize: before its last key switch) or by read_pass().
-    struct SinkScope
-    {
-        Engine &e;
-        Lane &l;
-        bool on;
-        size_t count;
-        bool cleared = false;
-        SinkScope(Engine &eng, size_t n) : e(eng), l(eng.lane()), on(l.tsink != nullptr), count(n)
-        {
-            if (on && count > l.tsink_cap)
-                throw std::invalid_argument("the transparency sink is smaller than this batch");
-        }
-        void clear()
-        {
-            if (on && !cleared && count)
-                SEALHIP_CHECK(hipMemsetAsync(l.tsink, 0, count * sizeof(unsigned), l.stream));
-            cleared = true;
-            l.tsink_base = 0;
-        }
-        void begin() // fused entries (multiply, square, apply_galois): the operation's last kernel writes the flags
-        {
-            clear();
-            if (on)
-                l.tsink_cur = l.tsink;
-        }
-        void arm() // (relinearize: only its last key switch stores the final polynomial 1)
-        {
-            begin();
-        }
-        void read_pass(const u64 *result, uint32_t size, size_t poly_words, size_t n)
-        {
-            clear();
-            if (on && size >= 2 && n)
-                check(launch_nonzero_tail(e, result, poly_words * size, poly_words, n, l.tsink), "transparency");
-        }
-        ~SinkScope()
-        {
-            l.tsink_cur = l.tsink_arm = nullptr;
-            l.tsink_base = 0;
-        }
-    };
-
     // SEAL_CIPHERTEXT_SIZE_MIN/MAX (util/defines.h:56-57) and the aliasing rule of the raw-buffer form
     void check_multiply_args(Engine &e, uint32_t k, const u64 *a, uint32_t size_a, const u64 *b, uint32_t size_b, const u64 *out)
     {
@@ -1123,6 +1154,19 @@ namespace
     }
 } // namespace
 
+// engine.hpp: one relinearized product of multiply_many and evaluate_polynomial, the callers' buffers
+extern "C++" const u64 *sealhip::relin_product(Engine &e, uint32_t k, const u64 *a, const u64 *b, std::size_t count,
+                                               const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, u64 *wide,
+                                               u64 *narrow)
+{
+    const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+    // (multiply(x, x) and square(x) give the same canonical residues, evaluator.cpp:1228-1235)
+    do_multiply(e, k, a, 2, b, 2, count, wide);
+    do_relinearize(e, k, wide, 3, count, relin_keys, n_relin_keys);
+    check(launch_copy_rows(e, wide, 3 * poly, narrow, 2 * poly, count, static_cast<int>(2 * k)), "resize");
+    return narrow;
+}
+
 /* ---------------------------------------------------------------- Evaluator level */
 long sealhip_evaluator_multiply(sealhip_context *ctx, uint32_t k, const uint64_t *a, uint32_t size_a,
                                 const uint64_t *b, uint32_t size_b, size_t count, uint64_t *out)
@@ -1228,13 +1272,7 @@ namespace
             owned.push_back(wide);
             SEALHIP_CHECK(hipMallocAsync(&narrow, two, stream));
             owned.push_back(narrow);
-            // (multiply(x, x) and square(x) give the same canonical residues, :1228-1235)
-            do_multiply(e, k, a, 2, b, 2, count, static_cast<u64 *>(wide));
-            do_relinearize(e, k, static_cast<u64 *>(wide), 3, count, relin_keys, n_relin_keys);
-            check(launch_copy_rows(e, static_cast<u64 *>(wide), 3 * poly, static_cast<u64 *>(narrow), 2 * poly, count,
-                                   static_cast<int>(2 * k)),
-                  "resize");
-            return static_cast<const u64 *>(narrow);
+            return relin_product(e, k, a, b, count, relin_keys, n_relin_keys, static_cast<u64 *>(wide), static_cast<u64 *>(narrow));
         };
         std::vector<const u64 *> queue;
         for (std::size_t i = 0; i + 1 < n_enc; i += 2)
@@ -1759,17 +1797,13 @@ namespace
                               uint64_t *out)
     {
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
+        check_data_level(h, k);
         for (size_t i = 0; i < elts.size(); i++)
         {
             if (!elts[i])
                 continue;
-            if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
-                throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
-            if (keys[i]->key.n_digits < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+            check_galois_elt(h, elts[i]);
+            check_key_digits(h, k, keys[i]);
         }
         if (h.scheme == 1 && !h.mode_strict)
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
@@ -1779,21 +1813,21 @@ namespace
         const std::size_t item = 2 * static_cast<std::size_t>(k) * e.n;
         const u64 *in = reinterpret_cast<const u64 *>(ct);
         u64 *o = reinterpret_cast<u64 *>(out);
-        if (o < in + count * item && in < o + elts.size() * count * item)
+        if (words_overlap(o, elts.size() * count * item, in, count * item))
             throw std::invalid_argument("out must not overlap ct");
         SinkScope sink(e, elts.size() * count);
         sink.begin();
         // every non-zero element goes through ONE hoisted call, each into its own output slot; a zero is a copy
         std::vector<uint32_t> run_elts, run_slots;
-        std::vector<const KSwitchKey *> run_keys;
+        std::vector<const KSwitchKey *> slot_keys; // (compacted, so not run_keys()'s list)
         for (size_t i = 0; i < elts.size(); i++)
             if (elts[i])
             {
                 run_elts.push_back(elts[i]);
                 run_slots.push_back(static_cast<uint32_t>(i));
-                run_keys.push_back(&keys[i]->key);
+                slot_keys.push_back(&keys[i]->key);
             }
-        op_apply_galois_many(e, static_cast<int>(k), in, count, run_elts.data(), run_keys.data(), run_elts.size(), o,
+        op_apply_galois_many(e, static_cast<int>(k), in, count, run_elts.data(), slot_keys.data(), run_elts.size(), o,
                              run_slots.data());
         for (size_t i = 0; i < elts.size(); i++)
             if (!elts[i])
@@ -1847,40 +1881,15 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
     }
     return guarded([&] {
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        std::vector<uint32_t> elts(n_steps, 0);
-        std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
-        for (uint32_t s = 0; s < n_steps; s++)
-        {
-            if (steps[s] == 0)
-                continue; // evaluator.cpp:1958-1962
-            elts[s] = host_galois_elt_from_step(h.n, steps[s]);
-            for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
-                if (galois_elts[i] == elts[s])
-                    keys[s] = galois_keys[i];
-            if (!keys[s])
-                throw std::invalid_argument("Galois key not present");
-        }
+        check_data_level(h, k);
+        std::vector<uint32_t> elts;
+        std::vector<const sealhip_kswitch_key *> keys;
+        keys_for_steps(h, steps, n_steps, galois_elts, galois_keys, n_keys, 0, elts, keys);
         do_apply_galois_many(ctx, k, ct, count, elts, keys, out);
     });
 }
 
 /* ------------------------------------------------------------------ mod-down merged with the rescale */
-namespace
-{
-    // the first checks of every *_rescale entry, ahead of the unmerged entry's own: CKKS only, 2 <= k <= first level
-    void check_rescale_level(const Engine &h, uint32_t k)
-    {
-        if (h.scheme != 2)
-            throw std::invalid_argument("the merged rescale is CKKS only");
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        if (k < 2)
-            throw std::invalid_argument("end of modulus switching chain reached"); // evaluator.cpp:1005-1008
-    }
-} // namespace
-
 long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
                                            size_t ct_item_stride, size_t count, const sealhip_kswitch_key *const *relin_keys,
                                            uint32_t n_relin_keys, uint64_t *out)
@@ -1900,28 +1909,57 @@ long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, con
         const std::size_t poly = static_cast<std::size_t>(k) * h.n;
         if (ct_item_stride < 3 * poly)
             throw std::invalid_argument("item stride smaller than one ciphertext");
-        if (n_relin_keys == 0)
-            throw std::invalid_argument("not enough relinearization keys"); // evaluator.cpp:793-796
-        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-        if (relin_keys[0]->key.n_digits < nd)
-            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const KSwitchKey *key = first_relin_key(h, k, relin_keys, n_relin_keys);
         const u64 *in = reinterpret_cast<const u64 *>(ct);
         u64 *o = reinterpret_cast<u64 *>(out);
-        if (count && o < in + (count - 1) * ct_item_stride + 3 * poly && in < o + count * 2 * (poly - h.n))
+        if (count && words_overlap(o, count * 2 * (poly - h.n), in, (count - 1) * ct_item_stride + 3 * poly))
             throw std::invalid_argument("out must not overlap ct");
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
         sink.begin();
-        op_switch_key_rescale(e, static_cast<int>(k), in, ct_item_stride, in + 2 * poly, ct_item_stride, count, relin_keys[0]->key,
-                              o);
+        op_switch_key_rescale(e, static_cast<int>(k), in, ct_item_stride, in + 2 * poly, ct_item_stride, count, *key, o);
     });
 }
 
 /* ------------------------------------------------------------------ weighted sums of rotations */
 namespace
 {
+    // every element valid, every key but the identity's with the level's digits (the sums of rotations and both BSGS axes)
+    void check_elts_and_keys(const Engine &h, uint32_t k, const std::vector<uint32_t> &elts,
+                             const std::vector<const sealhip_kswitch_key *> &keys)
+    {
+        for (size_t i = 0; i < elts.size(); i++)
+        {
+            check_galois_elt(h, elts[i]);
+            if (elts[i] != 1)
+                check_key_digits(h, k, keys[i]);
+        }
+    }
+
+    // The end of the checks of the sums of rotations and of BSGS: out against ct and plain_ntt, the empty batch (null), the
+    // device. The overlap check runs before device_engine() in the merged form and after it otherwise: the merged entries
+    // report it on host-only contexts too, the unmerged ones keep the order they always had.
+    Engine *rotation_sum_device(sealhip_context *ctx, bool rescale, size_t count, const u64 *o, std::size_t out_words,
+                                const u64 *in, std::size_t in_words, const u64 *w, std::size_t w_words)
+    {
+        const auto check_overlap = [&] {
+            if (words_overlap(o, out_words, in, in_words))
+                throw std::invalid_argument("out must not overlap ct");
+            if (words_overlap(o, out_words, w, w_words))
+                throw std::invalid_argument("out must not overlap plain_ntt");
+        };
+        if (rescale)
+            check_overlap();
+        if (count == 0)
+            return nullptr;
+        Engine &e = device_engine(ctx);
+        if (!rescale)
+            check_overlap();
+        return &e;
+    }
+
     // elts: the elements (1 = the identity, which needs no key). The checks that need no device come first and run on
     // host-only contexts too (the order the header documents).
     void do_apply_galois_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
@@ -1929,18 +1967,8 @@ namespace
                                    const uint64_t *plain_ntt, uint32_t n_sums, uint64_t *out, bool rescale = false)
     {
         Engine &h = *ctx->engine;
-        if (rescale)
-            check_rescale_level(h, k);
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-        for (size_t i = 0; i < elts.size(); i++)
-        {
-            if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
-                throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
-            if (elts[i] != 1 && keys[i]->key.n_digits < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        }
+        rescale ? check_rescale_level(h, k) : check_data_level(h, k);
+        check_elts_and_keys(h, k, elts, keys);
         if (h.scheme == 1 && !h.mode_strict)
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
         if (count && (elts.empty() || !n_sums))
@@ -1948,29 +1976,14 @@ namespace
         const std::size_t item = 2 * static_cast<std::size_t>(k) * h.n;
         const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
         u64 *o = reinterpret_cast<u64 *>(out);
-        const auto check_overlap = [&] {
-            const std::size_t out_words = n_sums * count * (rescale ? item - 2 * h.n : item),
-                              w_words = n_sums * elts.size() * h.key_moduli.size() * h.n;
-            if (o < in + count * item && in < o + out_words)
-                throw std::invalid_argument("out must not overlap ct");
-            if (o < w + w_words && w < o + out_words)
-                throw std::invalid_argument("out must not overlap plain_ntt");
-        };
-        if (rescale)
-            check_overlap(); // (the merged entries report it on host-only contexts too)
-        if (count == 0)
+        Engine *dev = rotation_sum_device(ctx, rescale, count, o, n_sums * count * (rescale ? item - 2 * h.n : item), in,
+                                          count * item, w, n_sums * elts.size() * h.key_moduli.size() * h.n);
+        if (!dev)
             return;
-        Engine &e = device_engine(ctx);
-        if (!rescale)
-            check_overlap();
-        SinkScope sink(e, static_cast<size_t>(n_sums) * count);
+        SinkScope sink(*dev, static_cast<size_t>(n_sums) * count);
         sink.begin();
-        std::vector<const KSwitchKey *> run_keys(elts.size(), nullptr);
-        for (size_t i = 0; i < elts.size(); i++)
-            if (elts[i] != 1)
-                run_keys[i] = &keys[i]->key;
-        op_apply_galois_dot_plain(e, static_cast<int>(k), in, count, elts.data(), run_keys.data(), elts.size(), w, n_sums, o,
-                                  rescale);
+        op_apply_galois_dot_plain(*dev, static_cast<int>(k), in, count, elts.data(), run_keys(elts, keys, 1).data(), elts.size(), w,
+                                  n_sums, o, rescale);
     }
 
     long apply_galois_dot_plain_entry(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
@@ -2014,23 +2027,10 @@ namespace
         }
         return guarded([&] {
             Engine &h = *ctx->engine;
-            if (rescale)
-                check_rescale_level(h, k);
-            if (k < 1 || static_cast<int>(k) > h.k_first)
-                throw std::invalid_argument("level k out of range");
-            std::vector<uint32_t> elts(n_steps, 1);
-            std::vector<const sealhip_kswitch_key *> keys(n_steps, nullptr);
-            for (uint32_t s = 0; s < n_steps; s++)
-            {
-                if (steps[s] == 0)
-                    continue; // (element 1)
-                elts[s] = host_galois_elt_from_step(h.n, steps[s]);
-                for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
-                    if (galois_elts[i] == elts[s])
-                        keys[s] = galois_keys[i];
-                if (!keys[s])
-                    throw std::invalid_argument("Galois key not present");
-            }
+            rescale ? check_rescale_level(h, k) : check_data_level(h, k);
+            std::vector<uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> keys;
+            keys_for_steps(h, steps, n_steps, galois_elts, galois_keys, n_keys, 1, elts, keys);
             do_apply_galois_dot_plain(ctx, k, ct, count, elts, keys, plain_ntt, n_sums, out, rescale);
         });
     }
@@ -2078,22 +2078,9 @@ namespace
                                     const uint64_t *plain_ntt, uint64_t *out, bool rescale = false)
     {
         Engine &h = *ctx->engine;
-        if (rescale)
-            check_rescale_level(h, k);
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-        const auto check_axis = [&](const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys) {
-            for (size_t i = 0; i < elts.size(); i++)
-            {
-                if (!(elts[i] & 1) || elts[i] >= 2 * h.n)
-                    throw std::invalid_argument("Galois element is not valid"); // evaluator.cpp:1880-1883
-                if (elts[i] != 1 && keys[i]->key.n_digits < nd)
-                    throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-            }
-        };
-        check_axis(baby, bkeys);
-        check_axis(giant, gkeys);
+        rescale ? check_rescale_level(h, k) : check_data_level(h, k);
+        check_elts_and_keys(h, k, baby, bkeys);
+        check_elts_and_keys(h, k, giant, gkeys);
         if (h.scheme == 1 && !h.mode_strict)
             throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
         if (count && (baby.empty() || giant.empty()))
@@ -2101,33 +2088,15 @@ namespace
         const std::size_t item = 2 * static_cast<std::size_t>(k) * h.n;
         const u64 *in = reinterpret_cast<const u64 *>(ct), *w = reinterpret_cast<const u64 *>(plain_ntt);
         u64 *o = reinterpret_cast<u64 *>(out);
-        const auto check_overlap = [&] {
-            const std::size_t out_words = count * (rescale ? item - 2 * h.n : item),
-                              w_words = giant.size() * baby.size() * h.key_moduli.size() * h.n;
-            if (o < in + count * item && in < o + out_words)
-                throw std::invalid_argument("out must not overlap ct");
-            if (o < w + w_words && w < o + out_words)
-                throw std::invalid_argument("out must not overlap plain_ntt");
-        };
-        if (rescale)
-            check_overlap(); // (the merged entries report it on host-only contexts too)
-        if (count == 0)
+        Engine *dev = rotation_sum_device(ctx, rescale, count, o, count * (rescale ? item - 2 * h.n : item), in, count * item, w,
+                                          giant.size() * baby.size() * h.key_moduli.size() * h.n);
+        if (!dev)
             return;
-        Engine &e = device_engine(ctx);
-        if (!rescale)
-            check_overlap();
-        SinkScope sink(e, count);
+        SinkScope sink(*dev, count);
         sink.begin();
-        const auto run_keys = [](const std::vector<uint32_t> &elts, const std::vector<const sealhip_kswitch_key *> &keys) {
-            std::vector<const KSwitchKey *> r(elts.size(), nullptr);
-            for (size_t i = 0; i < elts.size(); i++)
-                if (elts[i] != 1)
-                    r[i] = &keys[i]->key;
-            return r;
-        };
-        const std::vector<const KSwitchKey *> bk = run_keys(baby, bkeys), gk = run_keys(giant, gkeys);
-        op_apply_galois_bsgs_plain(e, static_cast<int>(k), in, count, baby.data(), bk.data(), baby.size(), giant.data(), gk.data(),
-                                   giant.size(), w, o, rescale);
+        const std::vector<const KSwitchKey *> bk = run_keys(baby, bkeys, 1), gk = run_keys(giant, gkeys, 1);
+        op_apply_galois_bsgs_plain(*dev, static_cast<int>(k), in, count, baby.data(), bk.data(), baby.size(), giant.data(),
+                                   gk.data(), giant.size(), w, o, rescale);
     }
 
 long apply_galois_bsgs_plain_entry(sealhip_context *ctx, bool rescale, uint32_t k, const uint64_t *ct, size_t count,
@@ -2186,30 +2155,11 @@ long rotate_vector_bsgs_plain_entry(sealhip_context *ctx, bool rescale, uint32_t
     }
     return guarded([&] {
         Engine &h = *ctx->engine;
-        if (rescale)
-            check_rescale_level(h, k);
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
-        const auto axis = [&](const int32_t *steps, uint32_t n, std::vector<uint32_t> &elts,
-                              std::vector<const sealhip_kswitch_key *> &keys) {
-            elts.assign(n, 1);
-            keys.assign(n, nullptr);
-            for (uint32_t s = 0; s < n; s++)
-            {
-                if (steps[s] == 0)
-                    continue; // (element 1)
-                elts[s] = host_galois_elt_from_step(h.n, steps[s]);
-                for (uint32_t i = 0; i < n_keys && !keys[s]; i++)
-                    if (galois_elts[i] == elts[s])
-                        keys[s] = galois_keys[i];
-                if (!keys[s])
-                    throw std::invalid_argument("Galois key not present");
-            }
-        };
+        rescale ? check_rescale_level(h, k) : check_data_level(h, k);
         std::vector<uint32_t> baby, giant;
         std::vector<const sealhip_kswitch_key *> bkeys, gkeys;
-        axis(baby_steps, n_baby, baby, bkeys);
-        axis(giant_steps, n_giant, giant, gkeys);
+        keys_for_steps(h, baby_steps, n_baby, galois_elts, galois_keys, n_keys, 1, baby, bkeys);
+        keys_for_steps(h, giant_steps, n_giant, galois_elts, galois_keys, n_keys, 1, giant, gkeys);
         do_apply_galois_bsgs_plain(ctx, k, ct, count, baby, bkeys, giant, gkeys, plain_ntt, out, rescale);
     });
 }
@@ -2262,8 +2212,7 @@ long sealhip_evaluator_dot_product_max_terms(sealhip_context *ctx, uint32_t k, u
     REQUIRE_PTR(max_terms);
     return guarded([&] {
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        check_data_level(h, k);
         *max_terms = dot_product_max_terms(h, static_cast<int>(k));
     });
 }
@@ -2293,42 +2242,28 @@ long dot_product_entry(sealhip_context *ctx, uint32_t k, const uint64_t *const *
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
-        if (rescale)
-            check_rescale_level(h, k);
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        rescale ? check_rescale_level(h, k) : check_data_level(h, k);
         if (h.scheme == 1 && !h.mode_strict)
             throw std::invalid_argument("the inner product of BFV ciphertexts needs a STRICT context");
         if (n_terms == 0 && count > 0)
             throw std::invalid_argument("the term lists must not be empty");
         if (n_terms > dot_product_max_terms(h, static_cast<int>(k)))
             throw std::invalid_argument("too many terms for one floor at this level (sealhip_evaluator_dot_product_max_terms)");
-        if (relin_keys)
-        {
-            if (n_relin_keys == 0)
-                throw std::invalid_argument("not enough relinearization keys");
-            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-            if (relin_keys[0]->key.n_digits < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        }
+        const KSwitchKey *key = relin_keys ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr;
         const std::size_t poly = static_cast<std::size_t>(k) * h.n;
-        const u64 *o = reinterpret_cast<const u64 *>(out),
-                  *o_end = o + count * (rescale ? 2 * (poly - h.n) : (relin_keys ? 2 : 3) * poly);
+        const u64 *o = reinterpret_cast<const u64 *>(out);
+        const std::size_t out_words = count * (rescale ? 2 * (poly - h.n) : (key ? 2 : 3) * poly);
         for (uint32_t i = 0; i < n_terms; i++)
             for (const uint64_t *term : { a_terms[i], b_terms[i] })
-            {
-                const u64 *t = reinterpret_cast<const u64 *>(term);
-                if (o < t + count * 2 * poly && t < o_end)
+                if (words_overlap(o, out_words, reinterpret_cast<const u64 *>(term), count * 2 * poly))
                     throw std::invalid_argument("out must not overlap an operand");
-            }
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
         sink.begin();
         op_dot_product(e, static_cast<int>(k), reinterpret_cast<const u64 *const *>(a_terms),
-                       reinterpret_cast<const u64 *const *>(b_terms), n_terms, count, relin_keys ? &relin_keys[0]->key : nullptr,
-                       reinterpret_cast<u64 *>(out), rescale);
+                       reinterpret_cast<const u64 *const *>(b_terms), n_terms, count, key, reinterpret_cast<u64 *>(out), rescale);
     });
 }
 } // namespace
@@ -2348,14 +2283,6 @@ long sealhip_evaluator_dot_product_rescale(sealhip_context *ctx, uint32_t k, con
 }
 
 /* ------------------------------------------------------------------ polynomial evaluation */
-namespace
-{
-    bool words_overlap(const u64 *a, std::size_t a_words, const u64 *b, std::size_t b_words)
-    {
-        return a < b + b_words && b < a + a_words;
-    }
-} // namespace
-
 long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, const uint64_t *const *terms, uint32_t n_terms,
                                           uint32_t size, size_t count, const uint64_t *weights, const uint64_t *constant,
                                           uint32_t n_sums, uint64_t *out)
@@ -2372,8 +2299,7 @@ long sealhip_evaluator_linear_combination(sealhip_context *ctx, uint32_t k, cons
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        check_data_level(h, k);
         if (size < 2 || size > 16) // SEAL_CIPHERTEXT_SIZE_MIN / _MAX (util/defines.h:56-57), as multiply and relinearize check
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         if ((n_terms == 0 || n_sums == 0) && count > 0)
@@ -2419,8 +2345,7 @@ long sealhip_evaluator_linear_combination_levels(sealhip_context *ctx, uint32_t 
     }
     return guarded([&] {
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        check_data_level(h, k);
         if (h.scheme != 2) // (a BFV mod_switch_to_next rounds every row: a higher level does not hold the lower one's words)
             throw std::invalid_argument("terms at their own level are CKKS only");
         for (uint32_t i = 0; i < n_terms; i++)
@@ -2455,10 +2380,7 @@ long sealhip_evaluator_linear_combination_levels(sealhip_context *ctx, uint32_t 
     });
 }
 
-/* Paterson-Stockmeyer over the two entries above: the power basis with multiply + relinearize (the launches of
-   do_multiply_many's products), every inner sum in ONE linear combination, the outer sum in ONE dot_product. Temporaries
-   are blocks of the context's pool, taken and released in stream order on the calling thread's lane: nothing here
-   synchronises. */
+/* Paterson-Stockmeyer over the two entries above: the checks, then bfv_poly_plan and op_evaluate_polynomial (poly_eval.cpp). */
 long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
                                            const uint64_t *coeffs, uint32_t degree, uint32_t n_baby,
                                            const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out)
@@ -2471,52 +2393,14 @@ long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, con
         REQUIRE_PTR(relin_keys[0]);
     return guarded([&] {
         Engine &h = *ctx->engine;
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        check_data_level(h, k);
         if (h.scheme != 1)
             throw std::invalid_argument("polynomial evaluation is BFV only (CKKS: sealhip_evaluator_linear_combination)");
         if (!h.mode_strict)
             throw std::invalid_argument("polynomial evaluation of BFV ciphertexts needs a STRICT context");
-        for (std::size_t i = 0; i <= degree; i++)
-            if (coeffs[i] >= h.t)
-                throw std::invalid_argument("a coefficient is not below the plain modulus");
-        std::size_t d = degree;
-        while (d > 0 && coeffs[d] == 0)
-            d--;
-        if (d < 1)
-            throw std::invalid_argument("a constant polynomial is not an operation on a ciphertext");
-        if (n_baby == 1 || n_baby > d + 1)
-            throw std::invalid_argument("n_baby must be 0 (automatic) or between 2 and the degree plus one");
-        std::size_t m = n_baby;
-        if (m == 0)
-            for (m = 1; m * m < d + 1;)
-                m++; // ceil(sqrt(d + 1))
-        const std::size_t g = (d + m) / m; // ceil((d + 1) / m)
-        const std::size_t n_terms = std::min(m, d + 1) - 1, ms = n_terms + 1;
-        // inner sum j is identically zero when all of c_{jm} .. c_{jm + m - 1} are
-        std::vector<u64> padded(g * ms, 0);
-        std::vector<char> live(g, 0);
-        for (std::size_t c = 0; c <= d; c++)
-        {
-            padded[c] = coeffs[c];
-            if (coeffs[c])
-                live[c / ms] = 1;
-        }
-        std::vector<std::size_t> outer; // the giant steps j >= 1 whose inner sum survives
-        for (std::size_t j = 1; j < g; j++)
-            if (live[j])
-                outer.push_back(j);
-        if (outer.size() > dot_product_max_terms(h, static_cast<int>(k)))
-            throw std::invalid_argument("too many giant steps for one floor at this level (sealhip_evaluator_dot_product_max_terms)");
-        if (d >= 2)
-        {
-            if (!relin_keys || n_relin_keys == 0)
-                throw std::invalid_argument("not enough relinearization keys");
-            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-            if (relin_keys[0]->key.n_digits < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        }
-        const std::size_t poly = static_cast<std::size_t>(k) * h.n, two_words = count * 2 * poly, two = two_words * sizeof(u64);
+        const BfvPolyPlan plan = bfv_poly_plan(h, k, reinterpret_cast<const u64 *>(coeffs), degree, n_baby);
+        const KSwitchKey *key = plan.d >= 2 ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr; // (d = 1: no product)
+        const std::size_t two_words = count * 2 * k * h.n;
         const u64 *x = reinterpret_cast<const u64 *>(ct);
         u64 *o = reinterpret_cast<u64 *>(out);
         if (words_overlap(o, two_words, x, two_words))
@@ -2525,77 +2409,7 @@ long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, con
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
-        // Temporaries are blocks of the context's pool (pool.cpp): taken and released in stream order on this lane, no
-        // synchronisation and, once the pool is warm, no allocator call. (Not hipMallocAsync: DESIGN.md section 11 -- in a
-        // sequence of calls its blocks gave wrong words here too, each call alone being right.)
-        std::vector<void *> owned;
-        struct Cleanup
-        {
-            Engine &e;
-            std::vector<void *> &v;
-            ~Cleanup()
-            {
-                for (void *p : v)
-                    pool_release(e, p);
-            }
-        } cleanup{ e, owned };
-        auto temp = [&](std::size_t bytes) {
-            void *p = pool_alloc(e, bytes);
-            owned.push_back(p);
-            return static_cast<u64 *>(p);
-        };
-        u64 *wide = nullptr; // the size-3 scratch of the products, reused in stream order
-        auto product = [&](const u64 *a, const u64 *b) {
-            if (!wide)
-                wide = temp(count * 3 * poly * sizeof(u64));
-            u64 *narrow = temp(two);
-            // (multiply(x, x) and square(x) give the same canonical residues, evaluator.cpp:1228-1235)
-            do_multiply(e, k, a, 2, b, 2, count, wide);
-            do_relinearize(e, k, wide, 3, count, relin_keys, n_relin_keys);
-            check(launch_copy_rows(e, wide, 3 * poly, narrow, 2 * poly, count, static_cast<int>(2 * k)), "resize");
-            return static_cast<const u64 *>(narrow);
-        };
-        // baby powers B_1 .. B_min(m, d): B_e = B_ceil(e/2) * B_floor(e/2)
-        const std::size_t n_powers = std::min(m, d);
-        std::vector<const u64 *> B(n_powers + 1, nullptr);
-        B[1] = x;
-        for (std::size_t p = 2; p <= n_powers; p++)
-            B[p] = product(B[(p + 1) / 2], B[p / 2]);
-        // giant powers G_1 = B_m, G_j = G_ceil(j/2) * G_floor(j/2): those a surviving term needs, and what they are built from
-        std::vector<const u64 *> G(g, nullptr);
-        std::vector<char> needed(g, 0);
-        for (std::size_t j : outer)
-            needed[j] = 1;
-        for (std::size_t j = g; j-- > 2;)
-            if (needed[j])
-                needed[(j + 1) / 2] = needed[j / 2] = 1;
-        if (g > 1)
-            G[1] = B[m];
-        for (std::size_t j = 2; j < g; j++)
-            if (needed[j])
-                G[j] = product(G[(j + 1) / 2], G[j / 2]);
-        // the tables of the inner sums and the inner sums themselves: I_0 goes straight to out when there is no outer sum
-        u64 *W = temp(g * n_terms * k * sizeof(u64)), *K = temp(g * k * sizeof(u64));
-        check(launch_poly_tables(e, static_cast<int>(k), padded.data(), padded.size(), ms, W, K), "poly_tables");
-        if (g == 1)
-        {
-            sink.begin();
-            op_linear_combination(e, static_cast<int>(k), B.data() + 1, n_terms, 2, count, W, K, 1, o);
-            return;
-        }
-        u64 *I = temp(g * two);
-        op_linear_combination(e, static_cast<int>(k), B.data() + 1, n_terms, 2, count, W, K, g, I);
-        // (g > 1 means d >= m: the inner sum that holds c_d is not zero, so there is an outer sum)
-        std::vector<const u64 *> ga, ib;
-        for (std::size_t j : outer)
-        {
-            ga.push_back(G[j]);
-            ib.push_back(I + j * two_words);
-        }
-        u64 *D = temp(two);
-        op_dot_product(e, static_cast<int>(k), ga.data(), ib.data(), outer.size(), count, &relin_keys[0]->key, D);
-        check(launch_ct_linear(e, CtLinearOp::Add, I, 2, D, 2, 0, o, count, e.map_for(static_cast<int>(k), SEALHIP_BASE_Q)), "add");
-        sink.read_pass(o, 2, poly, count);
+        op_evaluate_polynomial(e, plan, k, x, count, key, relin_keys, n_relin_keys, o, sink);
     });
 }
 
@@ -2608,51 +2422,11 @@ namespace
     polyplan::Plan ckks_poly_plan(Engine &h, uint32_t k, double scale, const double *coeffs, uint32_t degree, uint32_t basis,
                                   uint32_t n_baby, double scale_out, bool tables)
     {
-        if (k < 1 || static_cast<int>(k) > h.k_first)
-            throw std::invalid_argument("level k out of range");
+        check_data_level(h, k);
         if (h.scheme != 2)
             throw std::invalid_argument("planned polynomial evaluation is CKKS only (BFV: sealhip_evaluator_evaluate_polynomial)");
         return polyplan::make_plan(h.key_moduli.data(), static_cast<int>(k), scale, coeffs, degree, basis, n_baby, scale_out,
                                    tables);
-    }
-
-    // Words per item of the pool blocks sealhip_evaluator_evaluate_polynomial_ckks takes, in the order it takes them (the
-    // entry counts what it takes and refuses to go on if the two ever disagree).
-    std::size_t ckks_poly_temp_words(const polyplan::Plan &p, std::size_t N)
-    {
-        const std::size_t k = static_cast<std::size_t>(p.k), nb = p.baby.size() - 1;
-        std::size_t words = 0;
-        bool drops = false;
-        for (std::size_t e = 2; e <= nb; e++)
-        {
-            drops = drops || p.baby[(e + 1) / 2].level != p.baby[e / 2].level;
-            words += 2 * static_cast<std::size_t>(p.baby[e].level) * N;
-        }
-        for (std::size_t j = 2; j < p.g; j++)
-            if (p.needed[j])
-            {
-                drops = drops || p.giant[(j + 1) / 2].level != p.giant[j / 2].level;
-                words += 2 * static_cast<std::size_t>(p.giant[j].level) * N;
-            }
-        if (drops)
-            words += 2 * k * N; // one shared drop buffer (only the operand at the higher level is copied)
-        if (p.basis == 1 && nb >= 2)
-            words += 2 * 3 * k * N; // the size-3 product and the size-3 combination of a Chebyshev step
-        const std::size_t nf = 1 + p.J.size();
-        words += nf * 2 * static_cast<std::size_t>(p.inner_level) * N; // the inner sums before their rescale
-        if (!p.J.empty())
-        {
-            words += nf * 2 * static_cast<std::size_t>(p.sums_level) * N;
-            for (std::size_t j : p.J)
-            {
-                if (p.giant[j].level != p.outer_level)
-                    words += 2 * static_cast<std::size_t>(p.outer_level) * N;
-                if (p.sums_level != p.outer_level)
-                    words += 2 * static_cast<std::size_t>(p.outer_level) * N;
-            }
-            words += 2 * static_cast<std::size_t>(p.out_level) * N; // the outer sum
-        }
-        return words;
     }
 
     void fill_plan(const polyplan::Plan &p, std::size_t N, sealhip_poly_plan *plan)
@@ -2699,19 +2473,10 @@ long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k
     return guarded([&] {
         Engine &h = *ctx->engine;
         const polyplan::Plan p = ckks_poly_plan(h, k, scale, coeffs, degree, basis, n_baby, scale_out, true);
-        if (p.d >= 2)
-        {
-            if (!relin_keys || n_relin_keys == 0)
-                throw std::invalid_argument("not enough relinearization keys");
-            const uint32_t nd = (k + h.nsp - 1) / h.nsp; // keygenerator.cpp:334-336
-            if (relin_keys[0]->key.n_digits < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        }
-        const std::size_t N = h.n;
+        const KSwitchKey *key = p.d >= 2 ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr; // (d = 1: no product)
         const u64 *x = reinterpret_cast<const u64 *>(ct);
         u64 *o = reinterpret_cast<u64 *>(out);
-        const std::size_t out_poly = static_cast<std::size_t>(p.out_level) * N;
-        if (words_overlap(o, count * 2 * out_poly, x, count * 2 * k * N))
+        if (words_overlap(o, count * 2 * p.out_level * h.n, x, count * 2 * k * h.n))
             throw std::invalid_argument("out must not overlap ct");
         if (out_level)
             *out_level = static_cast<uint32_t>(p.out_level);
@@ -2721,160 +2486,7 @@ long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
-        const KSwitchKey *key = p.d >= 2 ? &relin_keys[0]->key : nullptr;
-        // Temporaries are blocks of the context's pool, taken and released in stream order on this lane (see
-        // sealhip_evaluator_evaluate_polynomial).
-        std::vector<void *> owned;
-        struct Cleanup
-        {
-            Engine &e;
-            std::vector<void *> &v;
-            ~Cleanup()
-            {
-                for (void *q : v)
-                    pool_release(e, q);
-            }
-        } cleanup{ e, owned };
-        std::size_t taken = 0; // words per item
-        const auto temp = [&](std::size_t words_per_item) {
-            void *q = pool_alloc(e, count * words_per_item * sizeof(u64));
-            owned.push_back(q);
-            taken += words_per_item;
-            return static_cast<u64 *>(q);
-        };
-        const auto poly_words = [&](int level) { return static_cast<std::size_t>(level) * N; };
-
-        // ---- every table of the call, gathered on the host and sent through kernel arguments in one pass
-        const int Lin = p.inner_level;
-        const std::size_t nb = p.baby.size() - 1, nf = 1 + p.J.size(), mi = p.mi;
-        std::vector<u64> tab;
-        const u64 *q = h.key_moduli.data();
-        std::vector<std::size_t> cheb_at(nb + 1, 0); // Chebyshev step e: weights [2][L] (or [1][L]) then the constant [L]
-        if (p.basis == 1)
-            for (std::size_t el = 2; el <= nb; el++)
-            {
-                const int L = p.baby[(el + 1) / 2].level;
-                cheb_at[el] = tab.size();
-                for (int r = 0; r < L; r++)
-                    tab.push_back(2 % q[r]);
-                for (int r = 0; r < L; r++) // hi != lo: the weight of E_1; hi == lo: the constant
-                    tab.push_back(polyplan::rint_residue(-p.cheb_sub[el], q[r]));
-            }
-        std::vector<std::size_t> sums{ 0 }; // the sums that are formed, in order
-        sums.insert(sums.end(), p.J.begin(), p.J.end());
-        const std::size_t w_at = tab.size();
-        for (std::size_t j : sums)
-            tab.insert(tab.end(), p.W.begin() + j * mi * Lin, p.W.begin() + (j + 1) * mi * Lin);
-        const std::size_t k_at = tab.size();
-        for (std::size_t j : sums)
-            tab.insert(tab.end(), p.K.begin() + j * Lin, p.K.begin() + (j + 1) * Lin);
-        const std::size_t ones_at = tab.size();
-        tab.insert(tab.end(), 2 * static_cast<std::size_t>(p.out_level), 1);
-        u64 *T = static_cast<u64 *>(pool_alloc(e, tab.size() * sizeof(u64)));
-        owned.push_back(T);
-        check(launch_put_words(e, T, tab.data(), tab.size()), "put_words");
-
-        // ---- products: an operand above the product's level is dropped to it by a copy (tensor_dot reads one row stride)
-        u64 *drop_buf = nullptr;
-        const auto dropped = [&](const u64 *a, int la, int L) {
-            if (la == L)
-                return a;
-            if (!drop_buf)
-                drop_buf = temp(2 * poly_words(static_cast<int>(k)));
-            check(launch_copy_rows(e, a, poly_words(la), drop_buf, poly_words(L), count * 2, L), "drop");
-            return static_cast<const u64 *>(drop_buf);
-        };
-        const auto product_rescale = [&](const u64 *a, int la, const u64 *b, int lb, u64 *dst) {
-            const int L = std::min(la, lb);
-            const u64 *pa = dropped(a, la, L), *pb = dropped(b, lb, L);
-            op_dot_product(e, L, &pa, &pb, 1, count, key, dst, true);
-        };
-
-        // ---- baby elements
-        std::vector<const u64 *> E(nb + 1, nullptr);
-        E[1] = x;
-        u64 *wide_p = nullptr, *wide_r = nullptr;
-        for (std::size_t el = 2; el <= nb; el++)
-        {
-            const std::size_t hi = (el + 1) / 2, lo = el / 2;
-            const int L = p.baby[hi].level;
-            u64 *dst = temp(2 * poly_words(p.baby[el].level));
-            if (p.basis == 0)
-                product_rescale(E[hi], p.baby[hi].level, E[lo], p.baby[lo].level, dst);
-            else
-            {
-                if (!wide_p)
-                    wide_p = temp(3 * poly_words(static_cast<int>(k))), wide_r = temp(3 * poly_words(static_cast<int>(k)));
-                const u64 *pa = E[hi], *pb = dropped(E[lo], p.baby[lo].level, L);
-                op_dot_product(e, L, &pa, &pb, 1, count, nullptr, wide_p, false);
-                const u64 *terms[2] = { wide_p, x };
-                const uint32_t levels[2] = { static_cast<uint32_t>(L), k }, sizes[2] = { 3, 2 };
-                const u64 *W = T + cheb_at[el];
-                if (hi == lo) // 2 P - rint(sc(hi) sc(lo))
-                    op_linear_combination_levels(e, L, terms, levels, sizes, 1, 3, count, W, W + L, 1, wide_r);
-                else // 2 P - rint(sc(hi) sc(lo) / sc(1)) E_1
-                    op_linear_combination_levels(e, L, terms, levels, sizes, 2, 3, count, W, nullptr, 1, wide_r);
-                op_switch_key_rescale(e, L, wide_r, 3 * poly_words(L), wide_r + 2 * poly_words(L), 3 * poly_words(L), count, *key,
-                                      dst);
-            }
-            E[el] = dst;
-        }
-
-        // ---- giant powers: monomial powers of E_m in both bases
-        std::vector<const u64 *> Y(p.g, nullptr);
-        if (p.g > 1)
-            Y[1] = E[p.m];
-        for (std::size_t j = 2; j < p.g; j++)
-            if (p.needed[j])
-            {
-                u64 *dst = temp(2 * poly_words(p.giant[j].level));
-                product_rescale(Y[(j + 1) / 2], p.giant[(j + 1) / 2].level, Y[j / 2], p.giant[j / 2].level, dst);
-                Y[j] = dst;
-            }
-
-        // ---- the inner sums: ONE combination over E_1 .. E_mi, each read at its own level, ONE rescale of the batch
-        std::vector<uint32_t> levels(mi), sizes(mi, 2);
-        for (std::size_t i = 1; i <= mi; i++)
-            levels[i - 1] = static_cast<uint32_t>(p.baby[i].level);
-        u64 *S = temp(nf * 2 * poly_words(Lin));
-        op_linear_combination_levels(e, Lin, E.data() + 1, levels.data(), sizes.data(), mi, 2, count, T + w_at, T + k_at, nf, S);
-        if (p.J.empty())
-            op_mod_switch_scale(e, Lin, S, 2, count, o, 0);
-        else
-        {
-            const int LI = p.sums_level, Lo = p.outer_level;
-            u64 *I = temp(nf * 2 * poly_words(LI));
-            op_mod_switch_scale(e, Lin, S, 2, nf * count, I, 0);
-            std::vector<const u64 *> ya, ib;
-            for (std::size_t s = 1; s < nf; s++)
-            {
-                const std::size_t j = p.J[s - 1];
-                const u64 *yj = Y[j], *ij = I + s * count * 2 * poly_words(LI);
-                if (p.giant[j].level != Lo)
-                {
-                    u64 *c = temp(2 * poly_words(Lo));
-                    check(launch_copy_rows(e, yj, poly_words(p.giant[j].level), c, poly_words(Lo), count * 2, Lo), "drop");
-                    yj = c;
-                }
-                if (LI != Lo)
-                {
-                    u64 *c = temp(2 * poly_words(Lo));
-                    check(launch_copy_rows(e, ij, poly_words(LI), c, poly_words(Lo), count * 2, Lo), "drop");
-                    ij = c;
-                }
-                ya.push_back(yj);
-                ib.push_back(ij);
-            }
-            u64 *D = temp(2 * out_poly);
-            op_dot_product(e, Lo, ya.data(), ib.data(), ya.size(), count, key, D, true);
-            // out = D + I_0, I_0 read in place at the result's level
-            const u64 *terms[2] = { D, I };
-            const uint32_t lv[2] = { static_cast<uint32_t>(p.out_level), static_cast<uint32_t>(LI) }, sz[2] = { 2, 2 };
-            op_linear_combination_levels(e, p.out_level, terms, lv, sz, 2, 2, count, T + ones_at, nullptr, 1, o);
-        }
-        if (taken != ckks_poly_temp_words(p, N))
-            throw std::logic_error("evaluate_polynomial_ckks: the temporaries taken differ from the plan's count");
-        sink.read_pass(o, 2, out_poly, count);
+        op_evaluate_polynomial_ckks(e, p, k, x, count, key, o, sink);
     });
 }
 
@@ -3504,8 +3116,7 @@ long sealhip_expand_seed_host(sealhip_context *ctx, uint32_t rows, const uint64_
     REQUIRE_PTR(out_host);
     return guarded([&] {
         Engine &e = *ctx->engine; // host work: also on host-only contexts
-        if (rows < 1 || static_cast<int>(rows) > e.n_key)
-            throw std::invalid_argument("level k out of range");
+        check_level(e, rows);
         const std::vector<u64> c1 = wire_expand_seed(e, static_cast<int>(rows), reinterpret_cast<const unsigned char *>(seed));
         std::memcpy(out_host, c1.data(), c1.size() * sizeof(u64));
     });
@@ -3519,8 +3130,7 @@ long sealhip_expand_seed(sealhip_context *ctx, uint32_t rows, const uint64_t *se
     REQUIRE_PTR(out_device);
     return guarded([&] {
         Engine &e = device_engine(ctx);
-        if (rows < 1 || static_cast<int>(rows) > e.n_key)
-            throw std::invalid_argument("level k out of range");
+        check_level(e, rows);
         const std::size_t words = static_cast<std::size_t>(rows) * e.n;
         if (item_stride_words && item_stride_words < words)
             throw std::invalid_argument("item stride is below rows x N");
@@ -3585,8 +3195,7 @@ static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const ui
         {
             std::vector<uint32_t> seen(elts, elts + n_keys);
             for (uint32_t elt : seen)
-                if (!(elt & 1) || elt >= 2 * h.n)
-                    throw std::invalid_argument("Galois element is not valid"); // keygenerator.cpp:213-216
+                check_galois_elt(h, elt); // keygenerator.cpp:213-216
             std::sort(seen.begin(), seen.end());
             if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
                 throw std::invalid_argument("Galois elements must be distinct (one key per element)");
@@ -3601,7 +3210,7 @@ static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const ui
             return;
         if (e.lane().capturing)
             throw std::logic_error("key generation allocates and synchronises: it cannot be captured in a graph");
-        const uint32_t digits = static_cast<uint32_t>((e.k_first + e.nsp - 1) / e.nsp);
+        const uint32_t digits = kswitch_digits(e, static_cast<uint32_t>(e.k_first));
         const std::size_t words = static_cast<std::size_t>(digits) * 2 * e.n_key * e.n;
         std::vector<std::unique_ptr<sealhip_kswitch_key>> made(n_keys);
         std::vector<u64 *> data(n_keys, nullptr);

@@ -19,9 +19,12 @@
 #include "devmath.hpp"
 #include "ntt_bounds.hpp"
 #include "hostmath.hpp"
+#include "pool_scratch.hpp"
+struct sealhip_kswitch_key; // the C ABI's key handle (api.cpp)
 
 namespace sealhip
 {
+    namespace polyplan { struct Plan; } // poly_plan.hpp
     constexpr int kMaxRows = 136;          // rows of one "polynomial" a launch can describe
     constexpr int kMaxModuli = 64;         // SEAL_COEFF_MOD_COUNT_MAX (util/defines.h:48)
     constexpr unsigned short kSkipRow = 0xFFFF;
@@ -334,6 +337,7 @@ namespace sealhip
     void pool_release(const Engine &e, void *ptr);
     void pool_trim(const Engine &e);
     void pool_free_all(Engine &e);
+    using Scratch = PoolScratch<Engine>; // an operation's temporaries: pool_alloc / pool_release, scoped (pool_scratch.hpp)
 
     struct LanePool
     {
@@ -629,6 +633,54 @@ namespace sealhip
                                     std::size_t count, unsigned *flags);
     hipError_t launch_nonzero_tail(const Engine &e, const u64 *ct, std::size_t item_words, std::size_t skip_words,
                                    std::size_t count, unsigned *flags);
+    // Transparency as a flag output (sealhip_transparency_sink): an Evaluator entry clears the flags of its batch, then either
+    // lets the final kernel of the operation write them (fused: multiply, square, relinearize, apply_galois) or runs the
+    // read pass over its result (the remaining entries).
+    // Order of effects: the constructor VALIDATES the capacity and nothing else, so an entry can build its
+    // scope before its first launch and a call rejected for any reason leaves both the data and the caller's flags as they
+    // were. The flags are cleared where they start to be written: by begin() (fused entries call it after their argument
+    // checks, right before the operation), by arm() (relinearize: before its last key switch) or by read_pass().
+    struct SinkScope
+    {
+        Engine &e;
+        Lane &l;
+        bool on;
+        size_t count;
+        bool cleared = false;
+        SinkScope(Engine &eng, size_t n) : e(eng), l(eng.lane()), on(l.tsink != nullptr), count(n)
+        {
+            if (on && count > l.tsink_cap)
+                throw std::invalid_argument("the transparency sink is smaller than this batch");
+        }
+        void clear()
+        {
+            if (on && !cleared && count)
+                SEALHIP_CHECK(hipMemsetAsync(l.tsink, 0, count * sizeof(unsigned), l.stream));
+            cleared = true;
+            l.tsink_base = 0;
+        }
+        void begin() // fused entries (multiply, square, apply_galois): the operation's last kernel writes the flags
+        {
+            clear();
+            if (on)
+                l.tsink_cur = l.tsink;
+        }
+        void arm() // (relinearize: only its last key switch stores the final polynomial 1)
+        {
+            begin();
+        }
+        void read_pass(const u64 *result, uint32_t size, size_t poly_words, size_t n)
+        {
+            clear();
+            if (on && size >= 2 && n)
+                check(launch_nonzero_tail(e, result, poly_words * size, poly_words, n, l.tsink), "transparency");
+        }
+        ~SinkScope()
+        {
+            l.tsink_cur = l.tsink_arm = nullptr;
+            l.tsink_base = 0;
+        }
+    };
     hipError_t launch_out_of_range(const Engine &e, const u64 *ct, std::size_t item_words, std::size_t count,
                                    const RowMap &map, unsigned *flags);
     hipError_t launch_plain_lift(const Engine &e, const u64 *plain, std::size_t plain_stride, u64 *out, std::size_t nplains,
@@ -809,6 +861,26 @@ namespace sealhip
     void op_linear_combination_levels(Engine &e, int k, const u64 *const *terms, const std::uint32_t *levels,
                                       const std::uint32_t *sizes, std::size_t n_terms, int size, std::size_t count,
                                       const u64 *weights, const u64 *constant, std::size_t n_sums, u64 *out);
+    // ---- polynomial evaluation (poly_eval.cpp; DESIGN.md sections 20 and 21) ----
+    // a * b relinearized to size 2 (api.cpp: multiply, relinearize, copy): wide [count][3][k][N] is scratch, the result is narrow
+    const u64 *relin_product(Engine &e, std::uint32_t k, const u64 *a, const u64 *b, std::size_t count,
+                             const sealhip_kswitch_key *const *relin_keys, std::uint32_t n_relin_keys, u64 *wide, u64 *narrow);
+    // BFV: the host-only plan of sum_c coeffs[c] x^c (its refusals are E_INVALIDARG; polyplan::make_plan is the CKKS one)
+    struct BfvPolyPlan
+    {
+        std::size_t d, m, g, n_terms, ms; // degree (trailing zeros trimmed), baby and giant steps, an inner sum's terms (+ 1)
+        std::vector<u64> padded;        // [g][ms] coefficients
+        std::vector<std::size_t> outer; // the giant steps j >= 1 whose inner sum survives
+    };
+    BfvPolyPlan bfv_poly_plan(Engine &h, std::uint32_t k, const u64 *coeffs, std::size_t degree, std::size_t n_baby);
+    // out[count][2][k][N] = p(x) (CKKS: [p.out_level] rows, p made with its tables); key: relin_keys' first, null only when
+    // d = 1; sink: the entry's scope
+    void op_evaluate_polynomial(Engine &e, const BfvPolyPlan &plan, std::uint32_t k, const u64 *x, std::size_t count,
+                                const KSwitchKey *key, const sealhip_kswitch_key *const *relin_keys, std::uint32_t n_relin_keys,
+                                u64 *out, SinkScope &sink);
+    void op_evaluate_polynomial_ckks(Engine &e, const polyplan::Plan &p, std::uint32_t k, const u64 *x, std::size_t count,
+                                     const KSwitchKey *key, u64 *out, SinkScope &sink);
+    std::size_t ckks_poly_temp_words(const polyplan::Plan &p, std::size_t N); // per item, what that call takes from the pool
     // Evaluator::square as its own path (evaluator.cpp:560-770): the operand is lifted / transformed once
     void op_bfv_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);
     void op_ckks_square(Engine &e, int k, const u64 *a, int sa, std::size_t count, u64 *out);

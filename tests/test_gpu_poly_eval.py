@@ -384,6 +384,41 @@ def test_polynomial_work_done_once(S):
     assert launches(call, "bfv_floor_sk") == 3 * n_products + 3 and launches(call, "ks_mac") == n_products + 1
 
 
+def test_polynomial_temporaries_go_back_to_the_pool(S):
+    """both drivers hold their temporaries in a scoped scratch (csrc/pool_scratch.hpp): a call leaves the pool's bytes in use
+    where they were, and once the pool is warm an identical call makes no allocator call (no new miss). BFV d = 20, m = 4
+    (g = 6) at N = 2^12, k = 3, two items; CKKS d = 7 (m = 3, g = 3) on the CKKS file's session of the same ring degree. (The
+    release when an exception unwinds has no clean trigger here, every refusal coming before the first block is taken: it is
+    checked on the CPU over a stub pool, tests/pool_scratch_check.cpp.)"""
+    import test_gpu_poly_eval_ckks as PK
+
+    se = _session(S, S.SCHEME_BFV, 12, [40, 40, 40, 41], 1, S.MODE_STRICT, t=65537)
+    k, count = 3, 2
+    coeffs, n_baby, _ = SHAPES["d20 m4"]
+    host, dev = se.pool(k, 2, count, 1)
+    out = se.ctx.alloc(count * 2 * k * se.n)
+    bfv = lambda: se.ev.evaluate_polynomial(dev[0], coeffs, k, count, out, [se.key], n_baby=n_baby)
+    ck = PK._poly_session(S, 0)
+    ccoeffs, cbaby = PK.SHAPES["d7 auto"]
+    plan = ck.ev.polynomial_plan_ckks(ck.k, PK.DELTA, ccoeffs, 0, cbaby, 0.0, tables=False)
+    assert plan["g"] > 1
+    cout = ck.ctx.alloc(ck.count * 2 * plan["out_level"] * ck.n)
+    ckks = lambda: ck.ev.evaluate_polynomial_ckks(ck.dct, ccoeffs, ck.k, ck.count, PK.DELTA, cout, [ck.key], 0, cbaby, 0.0)
+    for ctx, call in ((se.ctx, bfv), (ck.ctx, ckks)):
+        call()  # (warm-up: arena, tables and the pool's blocks in place)
+        before = ctx.pool_stats()
+        call()
+        after = ctx.pool_stats()
+        call()
+        again = ctx.pool_stats()
+        print(before, after, again)
+        assert before["bytes_in_use"] == after["bytes_in_use"] == again["bytes_in_use"], (before, after, again)
+        assert before["misses"] == after["misses"] == again["misses"], (before, after, again)
+        assert before["hits"] < after["hits"] < again["hits"], (before, after, again)  # (the blocks do come from the pool)
+    out.free()
+    cout.free()
+
+
 def test_polynomial_end_to_end(S):
     """encrypt with the oracle's client, evaluate d = 7 on the device, decrypt on the device: p(m) mod (x^N + 1, t)"""
     logn, n, t = 12, 1 << 12, 65537
