@@ -3,6 +3,15 @@
 // (:829-957) and apply_galois (:1841-1943), batched over independent ciphertexts. Large batches are
 // processed in chunks sized to the workspace arena; every chunk is a fixed sequence of launches on
 // one stream, so temporaries are reused in stream order without host synchronisation.
+//
+// What the composite operations share (anonymous namespaces, each ahead of its first user):
+//   arena     plan_chunk / for_chunks (items per chunk), plan_pass (a list walked in passes next to one item), KsArena /
+//             switch_key_arena (a key switch's item, also for the operations that nest one), FloorRestore (scratch parked
+//             under a raised floor, and the sink's first item, around a nested chunk loop)
+//   key switch  ks_digits + ks_products (front half), ks_finish / ks_finish_rescale (back half)
+//   BFV in q u Bsk  split_q_bsk, bfv_lift_and_transform (steps 1-3), bfv_inverse_and_floors / bfv_floors (steps 5-8)
+//   Galois lists  check_galois_elt, check_axis + load_tables (GaloisAxis)
+//   weighted sums  check_weighted_form, components_ntt, hoist_dot_sums, finish_sum
 #include "engine.hpp"
 
 #include <cmath>
@@ -57,15 +66,32 @@ namespace sealhip
             log.emplace_back(length, per_pass);
         }
 
-        // how many items fit the arena, given the padded byte need of one item (sum over its buffers)
-        std::size_t plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers)
+        // how many items fit the arena, given the padded byte need of one item (sum over its buffers). log = false: an
+        // operation that parks scratch under a raised floor asks, before the scratch goes live, for what the nested
+        // operation's chunk loop will ask for -- the arena then cannot move while the scratch is live
+        std::size_t plan_chunk(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers, bool log = true)
         {
             const std::size_t budget = workspace_budget_bytes(e);
             std::size_t chunk = budget / (bytes_per_item ? bytes_per_item : 1);
             chunk = std::max<std::size_t>(1, std::min(chunk, count));
-            log_chunk(e, count, chunk);
+            if (log)
+                log_chunk(e, count, chunk);
             e.ws_reserve(e.lane().ws_floor + chunk * bytes_per_item + static_cast<std::size_t>(n_buffers) * 256);
             return chunk;
+        }
+
+        // "The list does not fit: walk it in passes". Next to fixed_bytes per item, how many of a list's n units of
+        // unit_bytes the arena takes at once: all of them, else what fits (at least one) -- and then the split is logged as
+        // (logged_n or n, pass), ahead of the operation's item chunks (sealhip_debug_chunk_log).
+        std::size_t plan_pass(Engine &e, std::size_t fixed_bytes, std::size_t unit_bytes, std::size_t n, std::size_t logged_n = 0)
+        {
+            const std::size_t budget = workspace_budget_bytes(e);
+            if (fixed_bytes + n * unit_bytes <= budget)
+                return n;
+            const std::size_t fit = budget > fixed_bytes ? (budget - fixed_bytes) / unit_bytes : 0;
+            const std::size_t pass = std::max<std::size_t>(1, std::min(fit, n));
+            log_chunk(e, logged_n ? logged_n : n, pass);
+            return pass;
         }
 
         RowMap skip_map(const RowMap &base, int keep_lo, int keep_hi)
@@ -75,6 +101,25 @@ namespace sealhip
                 if (r < keep_lo || r >= keep_hi)
                     m.prime[r] = kSkipRow;
             return m;
+        }
+
+        // Two maps over disjoint rows of `polys` polynomials in the extended base (qbsk = a level's map_qbsk, k of its
+        // rows the ciphertext primes): the q rows and the Bsk rows, for the launch pairs that treat them differently
+        struct QBskMaps
+        {
+            RowMap q, bsk;
+        };
+        QBskMaps split_q_bsk(const RowMap &qbsk, int k, int polys)
+        {
+            QBskMaps s{};
+            s.q.rows = s.bsk.rows = polys * qbsk.rows;
+            for (int p = 0; p < polys; p++)
+                for (int r = 0; r < qbsk.rows; r++)
+                {
+                    s.q.prime[p * qbsk.rows + r] = r < k ? qbsk.prime[r] : kSkipRow;
+                    s.bsk.prime[p * qbsk.rows + r] = r < k ? kSkipRow : qbsk.prime[r];
+                }
+            return s;
         }
     } // namespace
 
@@ -101,21 +146,30 @@ namespace sealhip
         return m;
     }
 
-    // bytes of arena one item of op_switch_key needs (shared with op_apply_galois, which must size the arena
-    // before it parks its own scratch at the front)
-    static std::size_t switch_key_item_bytes(Engine &e, int k)
-    {
-        LevelTools &lt = e.level(k);
-        const std::size_t N = e.n;
-        const std::size_t rows = static_cast<std::size_t>(k + e.nsp), nd = static_cast<std::size_t>(lt.h_ks.nd);
-        const bool ckks = e.scheme == 2;
-        const bool strict_bfv = e.mode_strict && !ckks;
-        const std::size_t w_coeff = (ckks || strict_bfv) ? static_cast<std::size_t>(k) * N : 0;
-        return (w_coeff + nd * rows * N + 2 * rows * N + 2 * static_cast<std::size_t>(k) * N) * sizeof(u64);
-    }
-
     namespace
     {
+        // The arena of one item of a key switch, in words: what its chunk loop plans with and carves, and what an
+        // operation that nests it (op_apply_galois, op_dot_product) sizes the arena by
+        struct KsArena
+        {
+            std::size_t w_coeff, w_ext, w_prod, w_temp;
+            static constexpr int n_buffers = 4; // (coeff counts whether or not an item has one: 256 bytes of slack)
+            std::size_t item_bytes() const
+            {
+                return (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64);
+            }
+        };
+        // op_switch_key: the target's k rows in the other form (CKKS, STRICT BFV), the digits, the products, the
+        // mod-down's temporaries. op_switch_key_rescale (rescale; CKKS): the temporaries are at the level below.
+        KsArena switch_key_arena(Engine &e, int k, bool rescale = false)
+        {
+            const std::size_t N = e.n, rows = static_cast<std::size_t>(k + e.nsp);
+            const std::size_t nd = static_cast<std::size_t>(e.level(k).h_ks.nd);
+            const bool has_coeff = e.scheme == 2 || e.mode_strict;
+            return KsArena{ has_coeff ? static_cast<std::size_t>(k) * N : 0, nd * rows * N, 2 * rows * N,
+                            2 * static_cast<std::size_t>(rescale ? k - 1 : k) * N };
+        }
+
         // Transparency sink (devmath.hpp note_nonzero): the sink of the operation in flight, shifted to a chunk's first
         // item, and the scope around the ONE launch that stores the result's polynomials 1..
         unsigned *sink_at(Engine &e, std::size_t off)
@@ -136,22 +190,29 @@ namespace sealhip
             }
         };
         // Restores the arena floor an operation raised over buffers at the front of the arena that must survive a nested
-        // operation's chunk loop (which resets the arena to the floor).
+        // operation's chunk loop (which resets the arena to the floor), and the sink's first item, which such an operation
+        // shifts to its own chunk for the nested loop (sink_at). Both go back to what they were, also after a throw.
         struct FloorRestore
         {
             Lane &l;
-            std::size_t floor;
-            explicit FloorRestore(Engine &e) : l(e.lane()), floor(l.ws_floor)
+            const std::size_t floor, base;
+            explicit FloorRestore(Engine &e) : l(e.lane()), floor(l.ws_floor), base(l.tsink_base)
             {}
             ~FloorRestore()
             {
                 l.ws_floor = floor;
+                l.tsink_base = base;
+            }
+            void raise(std::size_t bytes) // over the saved floor: what lies there is parked
+            {
+                l.ws_floor = floor + bytes;
+            }
+            void *parked() const // (ask after whatever may still move the arena)
+            {
+                return static_cast<char *>(l.ws) + floor;
             }
         };
-    } // namespace
 
-    namespace
-    {
         // The part of the key switch that does not depend on the key (evaluator.cpp:2302-2322): the digits [dj0, dj1) of m
         // targets, extended to every row outside their bundle and transformed, into ext (digit-major); returns the rows the
         // inner product reads inside a bundle (the targets themselves, or their transform in coeff for STRICT BFV).
@@ -276,6 +337,18 @@ namespace sealhip
                 inb_stride = static_cast<std::size_t>(k) * N;
             }
             return KsRows{ inb, inb_stride };
+        }
+
+        // The front half of a key switch: ks_digits, then Step 3b + 4 (:2326-2349), the 128-bit inner product of the digits
+        // [dj0, dj1) with the key, reduced, into prod[m][2][k + nsp][N]
+        void ks_products(Engine &e, LevelTools &lt, int k, const u64 *tg, std::size_t target_stride, std::size_t m, u64 *coeff,
+                         u64 *ext, const KSwitchKey &key, u64 *prod, int dj0, int dj1)
+        {
+            const std::size_t ext_item = static_cast<std::size_t>(k + e.nsp) * e.n;
+            const KsRows in_bundle = ks_digits(e, lt, k, tg, target_stride, m, coeff, ext, dj0, dj1);
+            check(launch_ks_mac(e, lt.d_ks, lt.h_ks, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m /* digit-major */,
+                                key.d_data, prod, 2 * ext_item, m, dj0, dj1),
+                  "mac");
         }
 
         // The part after the inner product (evaluator.cpp:2351-2366): the m x 2 reduced products go through
@@ -444,59 +517,31 @@ namespace sealhip
         const int dj0 = partial ? split->j0 : 0, dj1 = partial ? split->j1 : h.nd;
         if (dj0 < 0 || dj0 > dj1 || dj1 > h.nd)
             throw std::invalid_argument("digit range out of bounds");
-        const std::size_t N = e.n;
-        const int rows = k + e.nsp, nd = h.nd;
-        const bool ckks = e.scheme == 2;
-        const bool strict_bfv = e.mode_strict && !ckks;
-        // per item words
-        const std::size_t w_coeff = (ckks || strict_bfv) ? static_cast<std::size_t>(k) * N : 0;
-        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
-        const std::size_t w_prod = 2ull * rows * N;
-        const std::size_t w_temp = 2ull * k * N;
-        const std::size_t per_item = switch_key_item_bytes(e, k);
-        if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
-            throw std::logic_error("internal: arena accounting mismatch");
+        const int rows = k + e.nsp;
+        const KsArena ar = switch_key_arena(e, k);
         const RowMap map_rows = lt.map_key;
-        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
-            u64 *coeff = w_coeff ? e.ws_alloc(w_coeff * m) : nullptr;
-            u64 *ext = e.ws_alloc(w_ext * m);
-            u64 *prod = e.ws_alloc(w_prod * m);
-            u64 *temp = e.ws_alloc(w_temp * m);
+        for_chunks(e, count, ar.item_bytes(), KsArena::n_buffers, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = ar.w_coeff ? e.ws_alloc(ar.w_coeff * m) : nullptr;
+            u64 *ext = e.ws_alloc(ar.w_ext * m);
+            u64 *prod = e.ws_alloc(ar.w_prod * m);
+            u64 *temp = e.ws_alloc(ar.w_temp * m);
             if (partial)
-                prod = split->partial_out + off * w_prod;
+                prod = split->partial_out + off * ar.w_prod;
             if (finish)
-                prod = split->partial_sum + off * w_prod;
-            const u64 *tg = finish ? nullptr : target + off * target_stride;
+                prod = split->partial_sum + off * ar.w_prod;
             u64 *ctp = partial ? nullptr : ct + off * ct_stride;
             const u64 *c0p = c0_src ? c0_src + off * c0_stride : nullptr;
-            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
-            const std::size_t ext_digit = ext_item * m; // digit-major
 
             if (finish)
                 // the summed canonical partials (below ranks * p < 2^63) back to canonical residues: from here on every word
                 // is what the unsplit inner product (:2341-2349) leaves
                 check(launch_poly_op(e, PolyOp::Mod63, prod, nullptr, 0, prod, m * 2 * rows, map_rows), "mod(partial sum)");
-            if (!finish)
-            {
-                const KsRows in_bundle = ks_digits(e, lt, k, tg, target_stride, m, coeff, ext, dj0, dj1);
-                // Step 3b + 4 (:2326-2349): 128-bit inner product over the digits, reduced
-                check(launch_ks_mac(e, lt.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_digit, key.d_data, prod,
-                                    w_prod, m, dj0, dj1),
-                      "mac");
-            }
+            else
+                ks_products(e, lt, k, target + off * target_stride, target_stride, m, coeff, ext, key, prod, dj0, dj1);
             if (partial)
                 return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
             ks_finish(e, lt, k, prod, temp, ctp, ct_stride, c0p, c0_stride, m, sink_at(e, off));
         });
-    }
-
-    // bytes of arena one item of op_switch_key_rescale needs (shared with op_dot_product, which nests it)
-    static std::size_t switch_key_rescale_item_bytes(Engine &e, int k)
-    {
-        const std::size_t N = e.n, rows = static_cast<std::size_t>(k + e.nsp);
-        const std::size_t nd = static_cast<std::size_t>(e.level(k).h_ks.nd);
-        return (static_cast<std::size_t>(k) * N + nd * rows * N + 2 * rows * N + 2 * static_cast<std::size_t>(k - 1) * N) *
-               sizeof(u64);
     }
 
     // relinearize + rescale_to_next in one call: op_switch_key's front half, then the merged finish
@@ -513,26 +558,15 @@ namespace sealhip
         const KsDev &h = lt.h_ks;
         if (static_cast<int>(key.n_digits) < h.nd)
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        const std::size_t N = e.n;
-        const int rows = k + e.nsp, nd = h.nd;
-        const std::size_t w_coeff = static_cast<std::size_t>(k) * N;
-        const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
-        const std::size_t w_prod = 2ull * rows * N;
-        const std::size_t w_temp = 2ull * (k - 1) * N;
-        const std::size_t per_item = switch_key_rescale_item_bytes(e, k);
-        if (per_item != (w_coeff + w_ext + w_prod + w_temp) * sizeof(u64))
-            throw std::logic_error("internal: arena accounting mismatch");
-        for_chunks(e, count, per_item, 4, [&](std::size_t off, std::size_t m) {
-            u64 *coeff = e.ws_alloc(w_coeff * m);
-            u64 *ext = e.ws_alloc(w_ext * m);
-            u64 *prod = e.ws_alloc(w_prod * m);
-            u64 *temp = e.ws_alloc(w_temp * m);
-            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
-            const KsRows in_bundle = ks_digits(e, lt, k, target + off * target_stride, target_stride, m, coeff, ext, 0, nd);
-            check(launch_ks_mac(e, lt.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m, key.d_data, prod,
-                                w_prod, m, 0, nd),
-                  "mac");
-            ks_finish_rescale(e, lt, k, base + off * base_stride, base_stride, prod, temp, out + off * w_temp, m, sink_at(e, off));
+        const KsArena ar = switch_key_arena(e, k, true);
+        for_chunks(e, count, ar.item_bytes(), KsArena::n_buffers, [&](std::size_t off, std::size_t m) {
+            u64 *coeff = e.ws_alloc(ar.w_coeff * m);
+            u64 *ext = e.ws_alloc(ar.w_ext * m);
+            u64 *prod = e.ws_alloc(ar.w_prod * m);
+            u64 *temp = e.ws_alloc(ar.w_temp * m);
+            ks_products(e, lt, k, target + off * target_stride, target_stride, m, coeff, ext, key, prod, 0, h.nd);
+            ks_finish_rescale(e, lt, k, base + off * base_stride, base_stride, prod, temp, out + off * ar.w_temp, m,
+                              sink_at(e, off));
         });
     }
 
@@ -634,6 +668,107 @@ namespace sealhip
         return p;
     }
 
+    namespace
+    {
+        // bfv_multiply's steps (1)-(3) (:335-353) for m items: the sa polynomials of a, then the sb of b (null: none, the
+        // square), are lifted to Bsk (fastbconv_m_tilde + sm_mrq) and all rows go to NTT form (lazy), into
+        // X[m][sin][k + |Bsk|][N]. a, b: the first item's polynomials of k rows, items back to back.
+        void bfv_lift_and_transform(Engine &e, LevelTools &lt, const BfvMulPlan &plan, const u64 *a, int sa, const u64 *b, int sb,
+                                    u64 *X, std::size_t m)
+        {
+            const RnsDev &h = lt.h_rns;
+            const int k = plan.k, kb = k + plan.nB, sin = b ? sa + sb : sa;
+            const std::size_t poly_q = static_cast<std::size_t>(k) * e.n, poly_x = static_cast<std::size_t>(kb) * e.n;
+            const std::size_t w_x = sin * poly_x;
+            for (int s = 0; s < sin; s++)
+            {
+                const bool first = s < sa;
+                const u64 *src = first ? a + s * poly_q : b + (s - sa) * poly_q;
+                const std::size_t src_stride = (first ? sa : sb) * poly_q;
+                u64 *dst = X + s * poly_x;
+                if (!plan.gather)
+                    check(launch_copy_rows(e, src, src_stride, dst, w_x, m, k), "copy");
+                check(launch_bfv_lift(e, lt.d_rns, h, src, src_stride, dst + poly_q, w_x, m, plan), "bfv_lift");
+            }
+            if (!plan.gather)
+            {
+                // (the tensor product reduces whatever it reads, polyarithsmallmod.cpp:63-117; the 60-bit Bsk rows keep the
+                //  reference's wrapped words either way: launch_half / the pass kernels only use the freedom on small primes)
+                check(launch_ntt(e, X, m * sin * kb, lt.map_qbsk, false, kNttAnyRep), "ntt(X)");
+                return;
+            }
+            // one "polynomial" of the launch = all sin*(k+|Bsk|) rows of an item; the q rows are gathered from the operands
+            NttSource ns{};
+            ns.base[0] = a;
+            ns.base[1] = b;
+            ns.poly_stride[0] = sa * poly_q;
+            ns.poly_stride[1] = sb * poly_q;
+            for (int s = 0; s < sin; s++)
+                for (int r = 0; r < kb; r++)
+                {
+                    unsigned short code = kSkipRow; // Bsk rows: in place (written by bfv_lift)
+                    if (r < k)
+                        code = static_cast<unsigned short>((s < sa ? 0 : kSrcSecond) | ((s < sa ? s : s - sa) * k + r));
+                    ns.code[s * kb + r] = code;
+                }
+            // two launches over disjoint rows: the q rows only feed the tensor product, which reduces canonically, so
+            // their last layer may skip its Barrett step (kNttAnyRep); the 60-bit Bsk rows wrap in the reference (F2)
+            // and keep its exact sequence. (The fused tensor product multiplies the q rows without reducing them first
+            // and needs them below 5p: there the last layer keeps its Barrett step.) kNttApprox: the approximate Shoup
+            // quotient where every prime is below 2^58 (one multiplier instruction less per butterfly).
+            const QBskMaps maps = split_q_bsk(lt.map_qbsk, k, sin);
+            check(launch_ntt_gather(e, X, m * sin * kb, maps.q, ns,
+                                    plan.fused_tensor ? (plan.tensor_apx ? kNttApprox : 0) : (kNttAnyRep | kNttApprox)),
+                  "ntt(X, gathered q rows)");
+            // (fused tensor product: the wrapped Bsk words are brought below 2p as they are stored -- the residue class
+            //  is all the dyadic product depends on)
+            // (kNttAnyRep next to kNttReduceOut: "any representative below 2p will do". PARITY launches drop it on these
+            //  60-bit primes and keep the reference's words; STRICT launches take the dense lazy schedule with it, launch_half)
+            check(launch_ntt(e, X, m * sin * kb, maps.bsk, false,
+                             plan.fused_tensor ? (kNttReduceOut | kNttAnyRep | (plan.lift_top ? kNttTopDone : 0)) : 0),
+                  "ntt(X, Bsk rows)");
+        }
+
+        // where one polynomial of the product goes: items `stride` words apart, and its items' transparency flags (null:
+        // not a polynomial 1.. of the result)
+        struct BfvFloorDst
+        {
+            u64 *dst;
+            std::size_t stride;
+            unsigned *sink;
+        };
+        // steps (6)-(8) (:427-444): one floor per polynomial of D[m][dest][k + |Bsk|][N]
+        void bfv_floors(Engine &e, LevelTools &lt, const BfvMulPlan &plan, u64 *D, int dest, std::size_t m, const BfvFloorDst *to)
+        {
+            const std::size_t poly_x = static_cast<std::size_t>(plan.k + plan.nB) * e.n;
+            for (int I = 0; I < dest; I++)
+            {
+                SinkArm arm(e, to[I].sink);
+                check(launch_bfv_floor_sk(e, lt.d_rns, lt.h_rns, D + I * poly_x, dest * poly_x, to[I].dst, to[I].stride, m, plan),
+                      "floor_sk");
+            }
+        }
+        // the unfused path's step (5) (:423-424), then the floors; with the single-pass kernels the top inverse layer and
+        // the canonicalisation are applied by the consumer while it loads (saves one read+write pass over D)
+        void bfv_inverse_and_floors(Engine &e, LevelTools &lt, const BfvMulPlan &plan, u64 *D, int dest, std::size_t m,
+                                    const BfvFloorDst *to)
+        {
+            const int kb = plan.k + plan.nB;
+            if (plan.defer)
+            {
+                // two launches over disjoint rows: the q rows may store any representative (bfv_floor_sk canonicalises
+                // while it applies the deferred top layer), which lets the kernel drop most conditional subtractions
+                // (sparse lazy schedule); so may the 60-bit Bsk rows, which take the dense schedule (round 4)
+                const QBskMaps maps = split_q_bsk(lt.map_qbsk, plan.k, 1);
+                check(launch_ntt(e, D, m * dest * kb, maps.q, true, kNttDeferTop | kNttAnyRep), "intt(D, q rows)");
+                check(launch_ntt(e, D, m * dest * kb, maps.bsk, true, kNttDeferTop | kNttAnyRep), "intt(D, Bsk rows)");
+            }
+            else
+                check(launch_ntt(e, D, m * dest * kb, lt.map_qbsk, true, kNttCanonical), "intt(D)");
+            bfv_floors(e, lt, plan, D, dest, m, to);
+        }
+    } // namespace
+
     void op_bfv_multiply(Engine &e, int k, const u64 *a, int sa, const u64 *b, int sb, std::size_t count, u64 *out)
     {
         LevelTools &lt = e.level(k);
@@ -645,124 +780,37 @@ namespace sealhip
         const BfvMulPlan plan = plan_bfv_multiply(e, k, sa, sb, sq);
         if (plan.nB != h.nB || plan.redc_small != (h.redc_small != 0))
             throw std::logic_error("op_bfv_multiply: the plan and the level's device constants disagree");
-        const bool gather = plan.gather, defer = plan.defer, fused_tensor = plan.fused_tensor, tensor_apx = plan.tensor_apx,
-                   lift_top = plan.lift_top;
         const int nB = h.nB, kb = k + nB, sin = sq ? sa : sa + sb, dest = sa + sb - 1;
         const std::size_t w_x = static_cast<std::size_t>(sin) * kb * N;
         const std::size_t w_d = static_cast<std::size_t>(dest) * kb * N;
         const std::size_t poly_q = static_cast<std::size_t>(k) * N, poly_x = static_cast<std::size_t>(kb) * N;
+        std::vector<BfvFloorDst> to(dest);
         for_chunks(e, count, (w_x + w_d) * sizeof(u64), 2, [&](std::size_t off, std::size_t m) {
             u64 *X = e.ws_alloc(w_x * m);
             u64 *D = e.ws_alloc(w_d * m);
-            // steps (1)-(3) (:335-353): lift to Bsk (fastbconv_m_tilde + sm_mrq) and one lazy NTT over all rows
-            for (int s = 0; s < sin; s++)
-            {
-                const bool first = s < sa;
-                const u64 *src = first ? a + off * sa * poly_q + s * poly_q : b + off * sb * poly_q + (s - sa) * poly_q;
-                const std::size_t src_stride = (first ? sa : sb) * poly_q;
-                u64 *dst = X + s * poly_x;
-                if (!gather)
-                    check(launch_copy_rows(e, src, src_stride, dst, w_x, m, k), "copy");
-                check(launch_bfv_lift(e, lt.d_rns, h, src, src_stride, dst + poly_q, w_x, m, plan), "bfv_lift");
-            }
-            if (gather)
-            {
-                // one "polynomial" of the launch = all sin*(k+|Bsk|) rows of an item
-                RowMap big{};
-                NttSource ns{};
-                big.rows = sin * kb;
-                ns.base[0] = a + off * sa * poly_q;
-                ns.base[1] = sq ? nullptr : b + off * sb * poly_q;
-                ns.poly_stride[0] = sa * poly_q;
-                ns.poly_stride[1] = sb * poly_q;
-                for (int s = 0; s < sin; s++)
-                    for (int r = 0; r < kb; r++)
-                    {
-                        big.prime[s * kb + r] = lt.map_qbsk.prime[r];
-                        unsigned short code = kSkipRow; // Bsk rows: in place (written by bfv_lift)
-                        if (r < k)
-                            code = static_cast<unsigned short>((s < sa ? 0 : kSrcSecond) | ((s < sa ? s : s - sa) * k + r));
-                        ns.code[s * kb + r] = code;
-                    }
-                // two launches over disjoint rows: the q rows only feed the tensor product, which reduces canonically, so
-                // their last layer may skip its Barrett step (kNttAnyRep); the 60-bit Bsk rows wrap in the reference (F2)
-                // and keep its exact sequence. (The fused tensor product multiplies the q rows without reducing them first
-                // and needs them below 5p: there the last layer keeps its Barrett step.) kNttApprox: the approximate Shoup
-                // quotient where every prime is below 2^58 (one multiplier instruction less per butterfly).
-                RowMap mq = big, mb = big;
-                for (int s = 0; s < sin; s++)
-                    for (int r = 0; r < kb; r++)
-                        (r < k ? mb : mq).prime[s * kb + r] = kSkipRow;
-                check(launch_ntt_gather(e, X, m * sin * kb, mq, ns,
-                                        fused_tensor ? (tensor_apx ? kNttApprox : 0) : (kNttAnyRep | kNttApprox)),
-                      "ntt(X, gathered q rows)");
-                // (fused tensor product: the wrapped Bsk words are brought below 2p as they are stored -- the residue class
-                //  is all the dyadic product depends on)
-                // (kNttAnyRep next to kNttReduceOut: "any representative below 2p will do". PARITY launches drop it on these
-                //  60-bit primes and keep the reference's words; STRICT launches take the dense lazy schedule with it, launch_half)
-                check(launch_ntt(e, X, m * sin * kb, mb, false,
-                                 fused_tensor ? (kNttReduceOut | kNttAnyRep | (lift_top ? kNttTopDone : 0)) : 0),
-                      "ntt(X, Bsk rows)");
-            }
-            else
-                // (the tensor product reduces whatever it reads, polyarithsmallmod.cpp:63-117; the 60-bit Bsk rows keep the
-                //  reference's wrapped words either way: launch_half / the pass kernels only use the freedom on small primes)
-                check(launch_ntt(e, X, m * sin * kb, lt.map_qbsk, false, kNttAnyRep), "ntt(X)");
-            if (fused_tensor)
+            bfv_lift_and_transform(e, lt, plan, a + off * sa * poly_q, sa, sq ? nullptr : b + off * sb * poly_q, sb, X, m);
+            for (int I = 0; I < dest; I++) // (the sink: polynomials 1.. of the product)
+                to[I] = BfvFloorDst{ out + off * dest * poly_q + I * poly_q, dest * poly_q, I >= 1 ? sink_at(e, off) : nullptr };
+            if (plan.fused_tensor)
             {
                 // steps (4) + (5) (:376-424): D[I] = inverse NTT of sum_{i1+i2=I} X[i1] (.) X[2+i2], top layer deferred, every
                 // word with the Montgomery factor 2^-64 that bfv_floor_sk's constants undo. q rows: lazy sums (any
                 // representative, sparse schedule); Bsk rows: operands reduced on load, the dense lazy schedule
-                RowMap mq{}, mb{};
-                mq.rows = mb.rows = dest * kb;
-                for (int I = 0; I < dest; I++)
-                    for (int r = 0; r < kb; r++)
-                    {
-                        mq.prime[I * kb + r] = r < k ? lt.map_qbsk.prime[r] : kSkipRow;
-                        mb.prime[I * kb + r] = r < k ? kSkipRow : lt.map_qbsk.prime[r];
-                    }
-                check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, mq, kNttDeferTop | kNttAnyRep, sq),
+                const QBskMaps maps = split_q_bsk(lt.map_qbsk, k, dest);
+                check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, maps.q, kNttDeferTop | kNttAnyRep, sq),
                       "intt(tensor, q rows)");
                 // (round 4: the Bsk rows may store any representative below 2p as well -- bfv_floor_sk2 takes u, v below 2p and
                 //  canonicalises; the launcher then runs the DENSE lazy schedule on the 60-bit primes, ntt_bounds.hpp section 1)
-                check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, mb, kNttDeferTop | kNttAnyRep, sq),
+                check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, maps.bsk, kNttDeferTop | kNttAnyRep, sq),
                       "intt(tensor, Bsk rows)");
-                for (int I = 0; I < dest; I++)
-                {
-                    SinkArm arm(e, I >= 1 ? sink_at(e, off) : nullptr); // polynomials 1.. of the product
-                    check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, out + off * dest * poly_q + I * poly_q,
-                                              dest * poly_q, m, plan),
-                          "floor_sk");
-                }
+                bfv_floors(e, lt, plan, D, dest, m, to.data());
                 return;
             }
             // step (4) (:376-420)
             // (square: both operands are the same two transformed polynomials; the kernel then forms x_0 x_1 once and adds it
             //  to itself, :650-651)
             check(launch_tensor_product(e, X, sa, w_x, sq ? X : X + sa * poly_x, sb, w_x, D, w_d, m, lt.map_qbsk, sq), "tensor");
-            // step (5) (:423-424); with the single-pass kernels the top inverse layer and the canonicalisation are
-            // applied by the consumer while it loads (saves one read+write pass over D)
-            if (defer)
-            {
-                // two launches over disjoint rows: the q rows may store any representative (bfv_floor_sk canonicalises
-                // while it applies the deferred top layer), which lets the kernel drop most conditional subtractions
-                // (sparse lazy schedule); so may the 60-bit Bsk rows, which take the dense schedule (round 4)
-                RowMap mq = lt.map_qbsk, mb = lt.map_qbsk;
-                for (int r = 0; r < kb; r++)
-                    (r < k ? mb : mq).prime[r] = kSkipRow;
-                check(launch_ntt(e, D, m * dest * kb, mq, true, kNttDeferTop | kNttAnyRep), "intt(D, q rows)");
-                check(launch_ntt(e, D, m * dest * kb, mb, true, kNttDeferTop | kNttAnyRep), "intt(D, Bsk rows)");
-            }
-            else
-                check(launch_ntt(e, D, m * dest * kb, lt.map_qbsk, true, kNttCanonical), "intt(D)");
-            // steps (6)-(8) (:427-444)
-            for (int I = 0; I < dest; I++)
-            {
-                SinkArm arm(e, I >= 1 ? sink_at(e, off) : nullptr);
-                check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, out + off * dest * poly_q + I * poly_q,
-                                          dest * poly_q, m, plan),
-                      "floor_sk");
-            }
+            bfv_inverse_and_floors(e, lt, plan, D, dest, m, to.data());
         });
     }
 
@@ -836,7 +884,7 @@ namespace sealhip
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         const std::size_t N = e.n, poly_q = static_cast<std::size_t>(k) * N;
         const std::size_t out_item = (key ? 2 : 3) * poly_q;
-        const std::size_t ks_bytes = rescale ? switch_key_rescale_item_bytes(e, k) : key ? switch_key_item_bytes(e, k) : 0;
+        const std::size_t ks_bytes = key ? switch_key_arena(e, k, rescale).item_bytes() : 0;
         const std::size_t w_c2 = key ? poly_q : 0;
         const std::size_t w_c01 = rescale ? 2 * poly_q : 0; // (c_0, c_1) of the sum, when out is the level below
         // BFV: X holds a group of terms (4 polynomials of k + |Bsk| rows each), D the sum (3 polynomials)
@@ -857,15 +905,7 @@ namespace sealhip
         // sum from one group to the next, so a pass over fewer terms is simply a smaller group
         std::size_t group = std::min<std::size_t>(kDotGroup, n_terms);
         if (!ckks)
-        {
-            const std::size_t budget = workspace_budget_bytes(e), fixed = (w_c2 + w_d) * sizeof(u64);
-            if (fixed + group * w_x * sizeof(u64) > budget)
-            {
-                const std::size_t fit = budget > fixed ? (budget - fixed) / (w_x * sizeof(u64)) : 0;
-                group = std::max<std::size_t>(1, std::min(fit, group));
-                log_chunk(e, n_terms, group); // (the term split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
-            }
-        }
+            group = plan_pass(e, (w_c2 + w_d) * sizeof(u64), w_x * sizeof(u64), group, n_terms); // (logs the term split)
         const std::size_t work_bytes = (group * w_x + w_d) * sizeof(u64);
         // c_2 must survive op_switch_key, which re-plans the arena: it is carved first and the floor raised over it; the
         // item's bytes cover the larger of this operation's temporaries and the key switch's, so the nested plan fits what
@@ -874,16 +914,7 @@ namespace sealhip
                    [&](std::size_t off, std::size_t m) {
             u64 *c2 = key ? e.ws_alloc(w_c2 * m) : nullptr;
             u64 *c01 = rescale ? e.ws_alloc(w_c01 * m) : nullptr;
-            struct FloorGuard
-            {
-                Lane &l;
-                std::size_t floor, base;
-                ~FloorGuard()
-                {
-                    l.ws_floor = floor;
-                    l.tsink_base = base;
-                }
-            } guard{ e.lane(), e.lane().ws_floor, e.lane().tsink_base };
+            FloorRestore guard(e);
             u64 *o = rescale ? c01 : out + off * out_item;
             unsigned *const flags = sink_at(e, off);
             if (ckks)
@@ -906,7 +937,6 @@ namespace sealhip
             }
             else
             {
-                const RnsDev &h = lt.h_rns;
                 u64 *X = e.ws_alloc(group * w_x * m);
                 u64 *D = e.ws_alloc(w_d * m);
                 for (std::size_t g0 = 0; g0 < n_terms; g0 += group)
@@ -915,39 +945,9 @@ namespace sealhip
                     terms.n = static_cast<int>(std::min(group, n_terms - g0));
                     for (int t = 0; t < terms.n; t++)
                     {
-                        // steps (1)-(3) of op_bfv_multiply's unfused path for term g0 + t
+                        // steps (1)-(3) for term g0 + t (tensor_dot_kernel reduces what it loads: the plan's unfused flags)
                         u64 *Xt = X + static_cast<std::size_t>(t) * w_x * m;
-                        const u64 *pa = a[g0 + t] + off * 2 * poly_q, *pb = b[g0 + t] + off * 2 * poly_q;
-                        for (int s = 0; s < 4; s++)
-                        {
-                            const u64 *src = (s < 2 ? pa : pb) + (s & 1) * poly_q;
-                            u64 *dst = Xt + s * poly_x;
-                            if (!plan.gather)
-                                check(launch_copy_rows(e, src, 2 * poly_q, dst, w_x, m, k), "copy");
-                            check(launch_bfv_lift(e, lt.d_rns, h, src, 2 * poly_q, dst + poly_q, w_x, m, plan), "bfv_lift");
-                        }
-                        if (plan.gather)
-                        {
-                            RowMap mq{}, mb{};
-                            NttSource ns{};
-                            mq.rows = mb.rows = 4 * kb;
-                            ns.base[0] = pa;
-                            ns.base[1] = pb;
-                            ns.poly_stride[0] = ns.poly_stride[1] = 2 * poly_q;
-                            for (int s = 0; s < 4; s++)
-                                for (int r = 0; r < kb; r++)
-                                {
-                                    mq.prime[s * kb + r] = r < k ? lt.map_qbsk.prime[r] : kSkipRow;
-                                    mb.prime[s * kb + r] = r < k ? kSkipRow : lt.map_qbsk.prime[r];
-                                    ns.code[s * kb + r] =
-                                        r < k ? static_cast<unsigned short>((s < 2 ? 0 : kSrcSecond) | ((s & 1) * k + r)) : kSkipRow;
-                                }
-                            // (tensor_dot_kernel reduces what it loads: any representative will do, on both row sets)
-                            check(launch_ntt_gather(e, Xt, m * 4 * kb, mq, ns, kNttAnyRep | kNttApprox), "ntt(X, gathered q rows)");
-                            check(launch_ntt(e, Xt, m * 4 * kb, mb, false, 0), "ntt(X, Bsk rows)");
-                        }
-                        else
-                            check(launch_ntt(e, Xt, m * 4 * kb, lt.map_qbsk, false, kNttAnyRep), "ntt(X)");
+                        bfv_lift_and_transform(e, lt, plan, a[g0 + t] + off * 2 * poly_q, 2, b[g0 + t] + off * 2 * poly_q, 2, Xt, m);
                         terms.a[t] = Xt;
                         terms.b[t] = Xt + 2 * poly_x;
                     }
@@ -955,30 +955,17 @@ namespace sealhip
                     check(launch_tensor_dot(e, terms, w_x, w_x, D, w_d, D + 2 * poly_x, w_d, m, lt.map_qbsk, true, g0 > 0),
                           "tensor_dot");
                 }
-                // step (5), ONCE for the sum
-                if (plan.defer)
-                {
-                    RowMap mq = lt.map_qbsk, mb = lt.map_qbsk;
-                    for (int r = 0; r < kb; r++)
-                        (r < k ? mb : mq).prime[r] = kSkipRow;
-                    check(launch_ntt(e, D, m * 3 * kb, mq, true, kNttDeferTop | kNttAnyRep), "intt(D, q rows)");
-                    check(launch_ntt(e, D, m * 3 * kb, mb, true, kNttDeferTop | kNttAnyRep), "intt(D, Bsk rows)");
-                }
-                else
-                    check(launch_ntt(e, D, m * 3 * kb, lt.map_qbsk, true, kNttCanonical), "intt(D)");
-                // steps (6)-(8): three floors
-                for (int I = 0; I < 3; I++)
-                {
-                    SinkArm arm(e, !key && I >= 1 ? flags : nullptr);
-                    u64 *dst = key && I == 2 ? c2 : o + I * poly_q;
-                    check(launch_bfv_floor_sk(e, lt.d_rns, h, D + I * poly_x, w_d, dst, key && I == 2 ? poly_q : out_item, m, plan),
-                          "floor_sk");
-                }
+                // step (5) ONCE for the sum, and three floors: with a key c_2 goes to the arena and nothing is flagged here
+                unsigned *const f = key ? nullptr : flags;
+                const BfvFloorDst to[3] = { { o, out_item, nullptr },
+                                            { o + poly_q, out_item, f },
+                                            { key ? c2 : o + 2 * poly_q, key ? poly_q : out_item, f } };
+                bfv_inverse_and_floors(e, lt, plan, D, 3, m, to);
             }
             if (key)
             {
                 // relinearize_internal (evaluator.cpp:811-815) of the sum: (c_0, c_1) += key switch of c_2
-                e.lane().ws_floor = guard.floor + pad256(w_c2 * m) + (rescale ? pad256(w_c01 * m) : 0);
+                guard.raise(pad256(w_c2 * m) + (rescale ? pad256(w_c01 * m) : 0));
                 e.lane().tsink_base = guard.base + off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
                 if (rescale)
                     op_switch_key_rescale(e, k, c01, 2 * poly_q, c2, poly_q, m, *key, out + off * 2 * (poly_q - N));
@@ -1165,11 +1152,53 @@ namespace sealhip
     // ------------------------------------------------------------------------------------------
     // apply_galois_inplace (evaluator.cpp:1841-1943)
     // ------------------------------------------------------------------------------------------
+    namespace
+    {
+        void check_galois_elt(const Engine &e, std::uint32_t elt)
+        {
+            if (!(elt & 1) || elt >= static_cast<std::uint64_t>(e.n) * 2)
+                throw std::invalid_argument("Galois element is not valid"); // :1880-1883
+        }
+
+        // One list of Galois elements with their keys, as the hoisted entries take it; tables: T_g, null for a free identity
+        struct GaloisAxis
+        {
+            const std::uint32_t *elts;
+            const KSwitchKey *const *keys;
+            std::size_t n, n_gal; // elements, and those that need a key switch
+            bool identity_free;   // the identity needs no key (NULL allowed) and no table
+            std::vector<const std::uint32_t *> tables;
+        };
+        // Validates, element by element, the element and -- where it needs a key switch -- its key's digit count against the
+        // level's nd. identity_free: the weighted forms; otherwise (op_apply_galois_many) every element is key-switched.
+        GaloisAxis check_axis(const Engine &e, int nd, const std::uint32_t *elts, const KSwitchKey *const *keys, std::size_t n,
+                              bool identity_free)
+        {
+            GaloisAxis ax{ elts, keys, n, 0, identity_free, {} };
+            for (std::size_t i = 0; i < n; i++)
+            {
+                check_galois_elt(e, elts[i]);
+                if (identity_free && elts[i] == 1)
+                    continue;
+                if (!keys[i] || static_cast<int>(keys[i]->n_digits) < nd)
+                    throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+                ax.n_gal++;
+            }
+            return ax;
+        }
+        // ... and, once the call is known to do work, the tables (resident after the first call: the condition for a capture)
+        void load_tables(Engine &e, GaloisAxis &ax)
+        {
+            ax.tables.assign(ax.n, nullptr);
+            for (std::size_t i = 0; i < ax.n; i++)
+                if (!ax.identity_free || ax.elts[i] != 1)
+                    ax.tables[i] = e.galois_table(ax.elts[i]);
+        }
+    } // namespace
+
     void op_apply_galois(Engine &e, int k, u64 *ct, std::size_t count, std::uint32_t elt, const KSwitchKey &key)
     {
-        const std::uint64_t m2 = static_cast<std::uint64_t>(e.n) * 2;
-        if (!(elt & 1) || elt >= m2)
-            throw std::invalid_argument("Galois element is not valid"); // :1880-1883
+        check_galois_elt(e, elt);
         LevelTools &lt = e.level(k);
         const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
         const std::uint32_t *table = e.scheme == 2 ? e.galois_table(elt) : nullptr;
@@ -1180,43 +1209,21 @@ namespace sealhip
         const std::size_t scratch_bytes = (items * per_item + 255) & ~static_cast<std::size_t>(255);
         // the arena must hold the scratch plus at least one item of the key switch; growing it may move it
         e.ws_reserve(scratch_bytes + 256);
-        struct FloorGuard
-        {
-            Engine &e;
-            std::size_t saved;
-            ~FloorGuard()
-            {
-                e.lane().ws_floor = saved;
-            }
-        } guard{ e, e.lane().ws_floor };
-        e.lane().ws_floor = guard.saved + scratch_bytes;
+        FloorRestore guard(e);
+        guard.raise(scratch_bytes);
         for (std::size_t off = 0; off < count; off += items)
         {
             const std::size_t m = std::min(items, count - off);
             u64 *c = ct + off * 2 * poly;
-            // (re-derive the pointer every iteration: a nested ws_reserve may have re-allocated the arena, but only
-            //  while no scratch contents are live, i.e. before the first launch of this iteration)
-            {
-                // size the arena now exactly as the nested op_switch_key will ask for, so that it cannot move
-                // while the scratch is live
-                const std::size_t ks_item = switch_key_item_bytes(e, k);
-                const std::size_t ks_chunk = std::max<std::size_t>(1, std::min(workspace_budget_bytes(e) / ks_item, m));
-                e.ws_reserve(e.lane().ws_floor + ks_chunk * ks_item + 4 * 256);
-            }
-            u64 *scratch = reinterpret_cast<u64 *>(static_cast<char *>(e.lane().ws) + guard.saved);
+            // size the arena now exactly as the nested op_switch_key will ask for, so that it cannot move while the scratch
+            // is live, and re-derive the pointer after it (no scratch contents are live before this iteration's first launch)
+            plan_chunk(e, m, switch_key_arena(e, k).item_bytes(), KsArena::n_buffers, false);
+            u64 *scratch = static_cast<u64 *>(guard.parked());
             check(launch_galois(e, c, scratch, m * 2 * k, lt.map_q, elt, table), "galois");
             // The reference copies galois(c0) back (:1903 / :1917), zeroes c1 (:1928) and lets the key switch add its two
             // polynomials into that ciphertext (:1934-1935). Here the key switch's last kernel writes (galois(c0) + r0, r1)
             // directly: same sums, no copy pass and no fill pass over the ciphertext.
-            e.lane().tsink_base = off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
-            struct BaseReset
-            {
-                Lane &l;
-                ~BaseReset()
-                {
-                    l.tsink_base = 0;
-                }
-            } base_reset{ e.lane() };
+            e.lane().tsink_base = guard.base + off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
             op_switch_key(e, k, c, 2 * poly, scratch + poly, 2 * poly, m, key, scratch, 2 * poly);
         }
     }
@@ -1241,18 +1248,10 @@ namespace sealhip
         LevelTools &ld = e.level(k);
         const KsDev &h = ld.h_ks;
         const int nd = h.nd, rows = k + e.nsp;
-        for (std::size_t i = 0; i < n_elts; i++)
-        {
-            if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
-                throw std::invalid_argument("Galois element is not valid"); // :1880-1883
-            if (static_cast<int>(keys[i]->n_digits) < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-        }
+        GaloisAxis ax = check_axis(e, nd, elts, keys, n_elts, false);
         if (!n_elts || !count)
             return;
-        std::vector<const std::uint32_t *> tables(n_elts);
-        for (std::size_t i = 0; i < n_elts; i++)
-            tables[i] = e.galois_table(elts[i]); // (resident after the first call: the condition for a capture)
+        load_tables(e, ax);
         const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
         const std::size_t w_coeff = poly; // (CKKS: c_1 in coefficient form; STRICT BFV: c_1 in NTT form)
         const std::size_t w_ext = static_cast<std::size_t>(nd) * rows * N;
@@ -1261,14 +1260,7 @@ namespace sealhip
         // arena of one item: the digits once, and per element the products, the mod-down's temporaries and sigma_g(c_0)
         const std::size_t base_bytes = (w_coeff + w_ext) * sizeof(u64), elt_bytes = (w_prod + w_temp + poly) * sizeof(u64);
         // when not even one item fits with all its elements, the element list is walked in passes and the digits stay live
-        std::size_t pass = n_elts;
-        const std::size_t budget = workspace_budget_bytes(e);
-        if (base_bytes + pass * elt_bytes > budget)
-        {
-            pass = budget > base_bytes ? (budget - base_bytes) / elt_bytes : 0;
-            pass = std::max<std::size_t>(1, std::min(pass, n_elts));
-            log_chunk(e, n_elts, pass); // (the element split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
-        }
+        const std::size_t pass = plan_pass(e, base_bytes, elt_bytes, n_elts);
         unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext, in output order
         for_chunks(e, count, base_bytes + pass * elt_bytes, 5, [&](std::size_t off, std::size_t m) {
             u64 *coeff = e.ws_alloc(w_coeff * m);
@@ -1289,7 +1281,7 @@ namespace sealhip
                     for (int i = 0; i < he.n; i++)
                     {
                         he.elt[i] = elts[e0 + l0 + i];
-                        he.table[i] = tables[e0 + l0 + i];
+                        he.table[i] = ax.tables[e0 + l0 + i];
                         he.key[i] = keys[e0 + l0 + i]->d_data;
                     }
                     check(launch_hoist_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m, he,
@@ -1316,6 +1308,108 @@ namespace sealhip
     // Plaintext-weighted sum of rotations: out_s = sum_i W[s][i] * sigma_{g_i}(ct), one decomposition
     // of c_1 per ciphertext and one mod-down per sum
     // ------------------------------------------------------------------------------------------
+    namespace
+    {
+        // BFV: both components of the chunk's m ciphertexts go to NTT form in cntt; CKKS (cntt null) reads them in place
+        const u64 *components_ntt(Engine &e, LevelTools &ld, int k, const u64 *c, u64 *cntt, std::size_t m)
+        {
+            if (!cntt)
+                return c;
+            const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+            SEALHIP_CHECK(hipMemcpyAsync(cntt, c, m * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream));
+            check(launch_ntt(e, cntt, m * 2 * k, ld.map_q, false, kNttCanonical), "ntt(ct)");
+            return cntt;
+        }
+
+        // Section 16's inner sums for ns sums of a chunk of m items: base_s (sums base_sum_stride words apart) from every
+        // element of the axis, acc_s (acc[ns][m][2][k + nsp][N]) from those that need a key switch, both in launches of up
+        // to kHoistMaxElts elements, the later ones adding in. w0: the plaintext of (first sum, element 0); cn: the
+        // components in NTT form; in_bundle, ext: the digits of c_1 (ks_digits).
+        void hoist_dot_sums(Engine &e, LevelTools &ld, int k, const GaloisAxis &ax, const u64 *cn, const KsRows &in_bundle,
+                            const u64 *ext, std::size_t m, const u64 *w0, u64 *base, std::size_t base_sum_stride, u64 *acc,
+                            std::size_t ns)
+        {
+            const KsDev &h = ld.h_ks;
+            const std::size_t ext_item = static_cast<std::size_t>(k + e.nsp) * e.n;
+            const std::size_t w_plain = static_cast<std::size_t>(h.n_total) * e.n, w_sum_stride = ax.n * w_plain;
+            HoistDotElts he{};
+            bool launched = false;
+            for (std::size_t i = 0; i < ax.n; i++)
+            {
+                he.table[he.n] = ax.tables[i];
+                he.key[he.n] = nullptr;
+                he.w[he.n++] = w0 + i * w_plain;
+                if (he.n == kHoistMaxElts || i + 1 == ax.n)
+                {
+                    check(launch_hoist_dot_base(e, cn, he, w_sum_stride, base, base_sum_stride, k, m, ns, launched),
+                          "hoist_dot_base");
+                    he.n = 0;
+                    launched = true;
+                }
+            }
+            launched = false;
+            for (std::size_t i = 0, seen = 0; i < ax.n; i++)
+            {
+                if (ax.elts[i] == 1)
+                    continue;
+                he.table[he.n] = ax.tables[i];
+                he.key[he.n] = ax.keys[i]->d_data;
+                he.w[he.n++] = w0 + i * w_plain;
+                seen++;
+                if (he.n == kHoistMaxElts || seen == ax.n_gal)
+                {
+                    check(launch_hoist_dot_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m, he,
+                                               w_sum_stride, acc, 2 * ext_item, m, ns, launched),
+                          "hoist_dot_mac");
+                    he.n = 0;
+                    launched = true;
+                }
+            }
+        }
+
+        // The end of a weighted sum, for n ciphertexts: base (in NTT form, two polynomials of k rows each) goes back to
+        // coefficient form for BFV, and the accumulated products (acc, with the mod-down's temp; null: no key-switch term)
+        // come down into it -- ks_finish, the result replaces base. rescale (CKKS): the result goes to
+        // dst at the level below instead, through the merged finish or, with acc = 0, rescale_to_next of base with the exact
+        // transform: a nested chunk loop, for which the guard's floor is raised over the parked_bytes that hold base.
+        // sink: the flags of these n ciphertexts (null: none); where no finish notes them, a pass over the result does.
+        void finish_sum(Engine &e, LevelTools &ld, int k, u64 *base, u64 *acc, u64 *temp, u64 *dst, std::size_t n,
+                        unsigned *sink, bool rescale, FloorRestore &guard, std::size_t parked_bytes)
+        {
+            const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+            if (e.scheme != 2)
+                check(launch_ntt(e, base, n * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
+            if (rescale && acc)
+                ks_finish_rescale(e, ld, k, base, 2 * poly, acc, temp, dst, n, sink);
+            else if (rescale)
+            {
+                guard.raise(parked_bytes);
+                mod_switch_polys(e, k, base, poly, dst, poly - N, n * 2, true);
+                if (sink)
+                    check(launch_nonzero_tail(e, dst, 2 * (poly - N), poly - N, n, sink), "transparency");
+            }
+            else if (acc)
+                ks_finish(e, ld, k, acc, temp, base, 2 * poly, nullptr, 0, n, sink);
+            else if (sink)
+                check(launch_nonzero_tail(e, base, 2 * poly, poly, n, sink), "transparency");
+        }
+
+        // the checks the two weighted forms share, in the order they fire; returns the level's tools
+        LevelTools &check_weighted_form(Engine &e, int k, bool rescale)
+        {
+            if (k > e.k_first)
+                throw std::invalid_argument("key switching needs a ciphertext level");
+            const bool ckks = e.scheme == 2;
+            if (rescale && !ckks)
+                throw std::invalid_argument("the merged rescale is a CKKS operation");
+            if (rescale && k < 2)
+                throw std::invalid_argument("end of modulus switching chain reached");
+            if (!ckks && !e.mode_strict)
+                throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context");
+            return rescale ? e.level_rescale(k) : e.level(k);
+        }
+    } // namespace
+
     // The plaintexts (key-level NTT form) multiply the key-switch inner products while these are still in the extended basis
     // (hoist.hip, hoist_dot_mac); the weighted products are summed there and ks_finish brings each sum down once, adding it
     // into base_s = (sum_i W (.) sigma_i(C_0), sum_{i identity} W (.) C_1), which the base kernel writes straight into out.
@@ -1323,37 +1417,17 @@ namespace sealhip
                                    const KSwitchKey *const *keys, std::size_t n_elts, const u64 *plain_ntt,
                                    std::size_t n_sums, u64 *out, bool rescale)
     {
-        if (k > e.k_first)
-            throw std::invalid_argument("key switching needs a ciphertext level");
+        LevelTools &ld = check_weighted_form(e, k, rescale);
         const bool ckks = e.scheme == 2;
-        if (rescale && !ckks)
-            throw std::invalid_argument("the merged rescale is a CKKS operation");
-        if (rescale && k < 2)
-            throw std::invalid_argument("end of modulus switching chain reached");
-        if (!ckks && !e.mode_strict)
-            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
-        LevelTools &ld = rescale ? e.level_rescale(k) : e.level(k);
         const KsDev &h = ld.h_ks;
         const int nd = h.nd, rows = k + e.nsp;
-        std::size_t n_gal = 0;
-        for (std::size_t i = 0; i < n_elts; i++)
-        {
-            if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
-                throw std::invalid_argument("Galois element is not valid"); // :1880-1883
-            if (elts[i] == 1)
-                continue;
-            if (!keys[i] || static_cast<int>(keys[i]->n_digits) < nd)
-                throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-            n_gal++;
-        }
+        GaloisAxis ax = check_axis(e, nd, elts, keys, n_elts, true);
+        const std::size_t n_gal = ax.n_gal;
         if (!count)
             return;
         if (!n_elts || !n_sums)
             throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
-        std::vector<const std::uint32_t *> tables(n_elts, nullptr);
-        for (std::size_t i = 0; i < n_elts; i++)
-            if (elts[i] != 1)
-                tables[i] = e.galois_table(elts[i]); // (resident after the first call: the condition for a capture)
+        load_tables(e, ax);
         const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
         const std::size_t w_plain = static_cast<std::size_t>(h.n_total) * N, w_sum_stride = n_elts * w_plain;
         const std::size_t w_coeff = n_gal ? poly : 0;
@@ -1371,14 +1445,7 @@ namespace sealhip
         const std::size_t base_bytes = (w_coeff + w_ext + w_cn) * sizeof(u64),
                           sum_bytes = (w_prod + w_temp + w_base + w_ms) * sizeof(u64);
         // when not even one item fits with all its sums, the sum list is walked in passes and the digits stay live
-        std::size_t pass = n_sums;
-        const std::size_t budget = workspace_budget_bytes(e);
-        if (base_bytes + pass * sum_bytes > budget)
-        {
-            pass = budget > base_bytes ? (budget - base_bytes) / sum_bytes : 0;
-            pass = std::max<std::size_t>(1, std::min(pass, n_sums));
-            log_chunk(e, n_sums, pass); // (the sum split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
-        }
+        const std::size_t pass = plan_pass(e, base_bytes, sum_bytes, n_sums);
         unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext, in output order
         for_chunks(e, count, base_bytes + pass * sum_bytes, rescale ? 8 : 5, [&](std::size_t off, std::size_t m) {
             u64 *basebuf = rescale ? e.ws_alloc(w_base * m * pass) : nullptr;
@@ -1389,89 +1456,26 @@ namespace sealhip
             u64 *temp = n_gal ? e.ws_alloc(w_temp * m * pass) : nullptr;
             FloorRestore restore(e);
             const u64 *c = ct + off * 2 * poly;
-            const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
             KsRows in_bundle{ nullptr, 0 };
             if (n_gal)
                 in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
-            const u64 *cn = c;
-            if (cntt)
-            {
-                SEALHIP_CHECK(hipMemcpyAsync(cntt, c, m * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream));
-                check(launch_ntt(e, cntt, m * 2 * k, ld.map_q, false, kNttCanonical), "ntt(ct)");
-                cn = cntt;
-            }
+            const u64 *cn = components_ntt(e, ld, k, c, cntt, m);
             for (std::size_t s0 = 0; s0 < n_sums; s0 += pass)
             {
                 const std::size_t ns = std::min(pass, n_sums - s0);
-                const u64 *w0 = plain_ntt + s0 * w_sum_stride;
                 // base of sum s0 + s of this chunk: o + s * o_sum
                 u64 *o = rescale ? basebuf : out + (s0 * count + off) * 2 * poly;
                 const std::size_t o_sum = rescale ? m * 2 * poly : count * 2 * poly;
-                HoistDotElts he{};
-                const auto flush_base = [&](bool add) {
-                    check(launch_hoist_dot_base(e, cn, he, w_sum_stride, o, o_sum, k, m, ns, add), "hoist_dot_base");
-                    he.n = 0;
-                };
-                bool launched = false;
-                for (std::size_t i = 0; i < n_elts; i++)
-                {
-                    he.table[he.n] = tables[i];
-                    he.key[he.n] = nullptr;
-                    he.w[he.n++] = w0 + i * w_plain;
-                    if (he.n == kHoistMaxElts || i + 1 == n_elts)
-                    {
-                        flush_base(launched);
-                        launched = true;
-                    }
-                }
-                launched = false;
-                for (std::size_t i = 0, seen = 0; i < n_elts; i++)
-                {
-                    if (elts[i] == 1)
-                        continue;
-                    he.table[he.n] = tables[i];
-                    he.key[he.n] = keys[i]->d_data;
-                    he.w[he.n++] = w0 + i * w_plain;
-                    seen++;
-                    if (he.n == kHoistMaxElts || seen == n_gal)
-                    {
-                        check(launch_hoist_dot_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m,
-                                                   he, w_sum_stride, acc, w_prod, m, ns, launched),
-                              "hoist_dot_mac");
-                        he.n = 0;
-                        launched = true;
-                    }
-                }
+                hoist_dot_sums(e, ld, k, ax, cn, in_bundle, ext, m, plain_ntt + s0 * w_sum_stride, o, o_sum, acc, ns);
                 // the back half once per sum: when the chunk is the whole batch the sums of this pass are one contiguous
                 // batch of ns * m ciphertexts, else one batch per sum
                 const std::size_t run = m == count ? ns : 1;
                 for (std::size_t s = 0; s < ns; s += run)
                 {
-                    u64 *os = o + s * o_sum;
                     const std::size_t first = (s0 + s) * count + off; // (output ciphertext, and its transparency flag)
-                    if (rescale)
-                    {
-                        u64 *od = out + first * 2 * poly_out;
-                        if (n_gal)
-                            ks_finish_rescale(e, ld, k, os, 2 * poly, acc + s * m * w_prod, temp + s * m * w_temp, od, run * m,
-                                              sink ? sink + first : nullptr);
-                        else
-                        {
-                            // acc = 0: the merged finish is rescale_to_next of base_s with the exact transform
-                            e.lane().ws_floor = restore.floor + pad256(w_base * m * pass);
-                            mod_switch_polys(e, k, os, poly, od, poly_out, run * m * 2, true);
-                            if (sink)
-                                check(launch_nonzero_tail(e, od, 2 * poly_out, poly_out, run * m, sink + first), "transparency");
-                        }
-                        continue;
-                    }
-                    if (!ckks)
-                        check(launch_ntt(e, os, run * m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
-                    if (n_gal)
-                        ks_finish(e, ld, k, acc + s * m * w_prod, temp + s * m * w_temp, os, 2 * poly, nullptr, 0, run * m,
-                                  sink ? sink + first : nullptr);
-                    else if (sink)
-                        check(launch_nonzero_tail(e, os, 2 * poly, poly, run * m, sink + first), "transparency");
+                    finish_sum(e, ld, k, o + s * o_sum, n_gal ? acc + s * m * w_prod : nullptr, temp + s * m * w_temp,
+                               out + first * 2 * poly_out, run * m, sink ? sink + first : nullptr, rescale, restore,
+                               pad256(w_base * m * pass));
                 }
             }
         });
@@ -1489,44 +1493,20 @@ namespace sealhip
                                     const KSwitchKey *const *giant_keys, std::size_t n_giant, const u64 *plain_ntt, u64 *out,
                                     bool rescale)
     {
-        if (k > e.k_first)
-            throw std::invalid_argument("key switching needs a ciphertext level");
+        LevelTools &ld = check_weighted_form(e, k, rescale);
         const bool ckks = e.scheme == 2;
-        if (rescale && !ckks)
-            throw std::invalid_argument("the merged rescale is a CKKS operation");
-        if (rescale && k < 2)
-            throw std::invalid_argument("end of modulus switching chain reached");
-        if (!ckks && !e.mode_strict)
-            throw std::invalid_argument("hoisted rotation of BFV ciphertexts needs a STRICT context"); // (as op_apply_galois_many)
-        LevelTools &ld = rescale ? e.level_rescale(k) : e.level(k);
         const KsDev &h = ld.h_ks;
         const int nd = h.nd, rows = k + e.nsp;
-        const auto check_axis = [&](const std::uint32_t *elts, const KSwitchKey *const *keys, std::size_t n) {
-            std::size_t n_gal = 0;
-            for (std::size_t i = 0; i < n; i++)
-            {
-                if (!(elts[i] & 1) || elts[i] >= static_cast<std::uint64_t>(e.n) * 2)
-                    throw std::invalid_argument("Galois element is not valid"); // :1880-1883
-                if (elts[i] == 1)
-                    continue;
-                if (!keys[i] || static_cast<int>(keys[i]->n_digits) < nd)
-                    throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
-                n_gal++;
-            }
-            return n_gal;
-        };
-        const std::size_t n_gb = check_axis(baby_elts, baby_keys, n_baby), n_gg = check_axis(giant_elts, giant_keys, n_giant);
+        GaloisAxis baby = check_axis(e, nd, baby_elts, baby_keys, n_baby, true);
+        GaloisAxis giant = check_axis(e, nd, giant_elts, giant_keys, n_giant, true);
+        const std::size_t n_gb = baby.n_gal, n_gg = giant.n_gal;
         if (!count)
             return;
         if (!n_baby || !n_giant)
             throw std::invalid_argument("an empty sum of rotations is a transparent ciphertext");
-        std::vector<const std::uint32_t *> btab(n_baby, nullptr), gtab(n_giant, nullptr);
-        for (std::size_t i = 0; i < n_baby; i++)
-            if (baby_elts[i] != 1)
-                btab[i] = e.galois_table(baby_elts[i]); // (resident after the first call: the condition for a capture)
-        for (std::size_t j = 0; j < n_giant; j++)
-            if (giant_elts[j] != 1)
-                gtab[j] = e.galois_table(giant_elts[j]);
+        load_tables(e, baby);
+        load_tables(e, giant);
+        const std::vector<const std::uint32_t *> &gtab = giant.tables;
         const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
         const std::size_t w_plain = static_cast<std::size_t>(h.n_total) * N, w_sum_stride = n_baby * w_plain;
         const std::size_t ext_item = static_cast<std::size_t>(rows) * N;
@@ -1549,14 +1529,7 @@ namespace sealhip
         const std::size_t base_bytes = (w_coeff + w_ext + w_cn + w_acc + w_temp + w_BASE + w_ms) * sizeof(u64);
         const std::size_t giant_bytes = (2 * poly + w_accj + w_d + w_temp1 + w_coeff2 + w_ext2) * sizeof(u64);
         // when not even one item fits with all its giants, the giant list is walked in passes
-        std::size_t pass = n_giant;
-        const std::size_t budget = workspace_budget_bytes(e);
-        if (base_bytes + pass * giant_bytes > budget)
-        {
-            pass = budget > base_bytes ? (budget - base_bytes) / giant_bytes : 0;
-            pass = std::max<std::size_t>(1, std::min(pass, n_giant));
-            log_chunk(e, n_giant, pass); // (the giant split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
-        }
+        const std::size_t pass = plan_pass(e, base_bytes, giant_bytes, n_giant);
         unsigned *const sink = e.lane().tsink_cur; // one flag per output ciphertext
         for_chunks(e, count, base_bytes + pass * giant_bytes, rescale ? 14 : 11, [&](std::size_t off, std::size_t m) {
             u64 *BASEbuf = rescale ? e.ws_alloc(w_BASE * m) : nullptr;
@@ -1577,52 +1550,13 @@ namespace sealhip
             KsRows in_bundle{ nullptr, 0 };
             if (n_gb)
                 in_bundle = ks_digits(e, ld, k, c + poly, 2 * poly, m, coeff, ext, 0, nd);
-            const u64 *cn = c;
-            if (cntt)
-            {
-                SEALHIP_CHECK(hipMemcpyAsync(cntt, c, m * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream));
-                check(launch_ntt(e, cntt, m * 2 * k, ld.map_q, false, kNttCanonical), "ntt(ct)");
-                cn = cntt;
-            }
+            const u64 *cn = components_ntt(e, ld, k, c, cntt, m);
             bool acc_started = false, base_started = false;
             for (std::size_t g0 = 0; g0 < n_giant; g0 += pass)
             {
                 const std::size_t ng = std::min(pass, n_giant - g0);
-                const u64 *w0 = plain_ntt + g0 * w_sum_stride;
                 // base_j and acc_j of the pass's inner sums: section 16's launches, into workspace
-                HoistDotElts he{};
-                bool launched = false;
-                for (std::size_t i = 0; i < n_baby; i++)
-                {
-                    he.table[he.n] = btab[i];
-                    he.key[he.n] = nullptr;
-                    he.w[he.n++] = w0 + i * w_plain;
-                    if (he.n == kHoistMaxElts || i + 1 == n_baby)
-                    {
-                        check(launch_hoist_dot_base(e, cn, he, w_sum_stride, bw, m * 2 * poly, k, m, ng, launched),
-                              "hoist_dot_base");
-                        he.n = 0;
-                        launched = true;
-                    }
-                }
-                launched = false;
-                for (std::size_t i = 0, seen = 0; i < n_baby; i++)
-                {
-                    if (baby_elts[i] == 1)
-                        continue;
-                    he.table[he.n] = btab[i];
-                    he.key[he.n] = baby_keys[i]->d_data;
-                    he.w[he.n++] = w0 + i * w_plain;
-                    seen++;
-                    if (he.n == kHoistMaxElts || seen == n_gb)
-                    {
-                        check(launch_hoist_dot_mac(e, ld.d_ks, h, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m,
-                                                   he, w_sum_stride, accj, w_prod, m, ng, launched),
-                              "hoist_dot_mac");
-                        he.n = 0;
-                        launched = true;
-                    }
-                }
+                hoist_dot_sums(e, ld, k, baby, cn, in_bundle, ext, m, plain_ntt + g0 * w_sum_stride, bw, m * 2 * poly, accj, ng);
                 // d_j of the pass's non-identity giants, back to back in dbuf (target t = slot * m + item): base_j[1], for
                 // BFV in coefficient form, plus the mod-down of acc_j[1] -- one batch per run of consecutive such giants
                 std::vector<std::size_t> slot(ng, 0);
@@ -1699,27 +1633,9 @@ namespace sealhip
                     }
                 }
             }
-            if (!ckks)
-                check(launch_ntt(e, o, m * 2 * k, ld.map_q, true, kNttCanonical), "intt(base)");
-            if (rescale)
-            {
-                u64 *od = out + off * 2 * poly_out;
-                if (any_acc)
-                    ks_finish_rescale(e, ld, k, o, 2 * poly, ACC, temp, od, m, sink ? sink + off : nullptr);
-                else
-                {
-                    // acc = 0: the merged finish is rescale_to_next of BASE with the exact transform
-                    e.lane().ws_floor = restore.floor + pad256(w_BASE * m);
-                    mod_switch_polys(e, k, o, poly, od, poly_out, m * 2, true);
-                    if (sink)
-                        check(launch_nonzero_tail(e, od, 2 * poly_out, poly_out, m, sink + off), "transparency");
-                }
-                return;
-            }
-            if (any_acc)
-                ks_finish(e, ld, k, ACC, temp, o, 2 * poly, nullptr, 0, m, sink ? sink + off : nullptr);
-            else if (sink)
-                check(launch_nonzero_tail(e, o, 2 * poly, poly, m, sink + off), "transparency");
+            // ONE finish brings the whole product down (ACC is null when no term was formed)
+            finish_sum(e, ld, k, o, ACC, temp, out + off * 2 * poly_out, m, sink ? sink + off : nullptr, rescale, restore,
+                       pad256(w_BASE * m));
         });
     }
     // multiply_plain_normal (evaluator.cpp:1475-1603) for parameters with fast plain lift (every q_i > t): lift the
@@ -1818,21 +1734,13 @@ namespace sealhip
         const std::size_t item = static_cast<std::size_t>(size) * k * e.n;
         // one bit count per item, at the FRONT of the arena (ws_floor) for the whole batch; the chunks use the rest
         const std::size_t flag_bytes = (count * sizeof(int) + 255) & ~static_cast<std::size_t>(255);
-        struct FloorGuard
-        {
-            Engine &e;
-            std::size_t saved;
-            ~FloorGuard()
-            {
-                e.lane().ws_floor = saved;
-            }
-        } guard{ e, e.lane().ws_floor };
-        e.lane().ws_floor = guard.saved + flag_bytes;
+        FloorRestore guard(e);
+        guard.raise(flag_bytes);
         int *bits = nullptr;
         for_chunks(e, count, item * sizeof(u64), 2, [&](std::size_t off, std::size_t m) {
             if (off == 0) // (sizing the chunks may have moved the arena: the flags are addressed, and cleared, after it)
             {
-                bits = reinterpret_cast<int *>(static_cast<char *>(e.lane().ws) + guard.saved);
+                bits = static_cast<int *>(guard.parked());
                 check(hipMemsetAsync(bits, 0, count * sizeof(int), e.lane().stream), "memset(bits)");
             }
             const u64 *v = dot_product_coeff_chunk(e, k, map_q, ct + off * item, size, m, sk_powers);

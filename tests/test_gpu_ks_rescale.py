@@ -9,6 +9,7 @@ Seventeen ciphertexts reach the grouped inner-product kernel and more than one b
 launch group of the tensor sum."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -365,3 +366,131 @@ def test_cpp_adapter(S, tmp_path):
         for side in ("host", "device"):
             line = "%s %s digest %016x meta 1" % (side, name, O.fnv(words_))
             assert line in run.stdout, (line, run.stdout)
+
+
+# ---------------------------------------------------------------- arena chunks (a child process with the smallest arena)
+LOGN, N = 13, 1 << 13
+ARENA_MB = "64"
+
+
+def _child():
+    """N = 2^13, 8 + 1 primes, k = 8, CKKS, rows of N words = 64 KiB: the merged-rescale forms of the weighted sums under the
+    arena rule of DESIGN.md section 19. base_s and BASE live at the front of the arena; the temporaries are 2 (k - 1) rows.
+
+    dot_plain: per item once the digits, (8 + 72) rows = 5 MiB; per sum products + temporaries + base_s = (18 + 14 + 16) rows
+    = 3 MiB. Two sums: 11 MiB per item, 5 items in 64 MiB, so 7 items go 5 + 2. Twenty sums: 65 MiB for one item, so the
+    sum list is split 19 + 1 and the chunk is a single item.
+    bsgs: per item once digits + ACC + temporaries + BASE = (8 + 72 + 18 + 14 + 16) rows = 8 MiB, per giant 8.125 MiB (as
+    without rescale). Two giants: 24.25 MiB per item, 2 items per chunk, so 3 items go 2 + 1. Seven giants: 64.875 MiB for
+    one item, so the giant list is split 6 + 1.
+    Identity elements only: no key-switch term, and the finish is rescale_to_next of base_s / BASE -- a nested chunk loop
+    over 2 m polynomials of (1 + 7) rows under a floor raised over them, for which every item carries 16 more rows. Two
+    sums or giants: 4 MiB per item, 16 items per chunk, so 17 items need a second chunk; the nested loops log their pairs."""
+    import sealhip as S
+
+    assert os.environ.get("SEALHIP_WORKSPACE_MB") == ARENA_MB
+    mods = O.coeff_modulus_create(N, [50] * 8 + [60])
+    ctx = S.Context(S.SCHEME_CKKS, LOGN, mods, 1, 0)
+    ref = O.RefContext(2, LOGN, mods, nsp=1)
+    ev = S.Evaluator(ctx)
+    rng = np.random.default_rng(64)
+    k = 8
+    budget = int(ARENA_MB) << 20
+    row = N * 8
+    digits, prod, temp, base2 = (k + k * (k + 1)) * row, 2 * (k + 1) * row, 2 * (k - 1) * row, 2 * k * row
+    nested = budget // ((1 + k - 1) * row)  # polynomials per chunk of the plain rescale
+    made = {}
+
+    def key(g):
+        if g != 1 and g not in made:
+            host = _rows(rng, mods, N, (8, 2))
+            made[g] = (host, S.KSwitchKeys(ctx, host))
+        return made.get(g, (None, None))
+
+    def dot_plain(count, elts, n_sums, items, sums):
+        keys = [key(g) for g in elts]
+        ct = _rows(rng, mods[:k], N, (count, 2))
+        plains = _rows(rng, mods, N, (n_sums, len(elts)))
+        d, dp = ctx.upload(ct), ctx.upload(plains)
+        out = ctx.alloc(n_sums * count * 2 * (k - 1) * N)
+        ctx.chunk_log()
+        ev.apply_galois_dot_plain_rescale(d, k, count, elts, [kk[1] for kk in keys], dp, n_sums, out)
+        log = ctx.chunk_log()
+        got = out.download((n_sums, count, 2, k - 1, N))
+        want = R.dot_plain_rescale(ref, k, ct[list(items)], elts, [kk[0] for kk in keys], plains[list(sums)])
+        for j, s in enumerate(sums):
+            for i, c in enumerate(items):
+                assert np.array_equal(got[s, c], want[j, i]), ("dot_plain", elts, n_sums, s, c)
+        for b in (d, dp, out):
+            b.free()
+        return log
+
+    def bsgs(count, baby, giant, items):
+        bk, gk = [key(g) for g in baby], [key(g) for g in giant]
+        ct = _rows(rng, mods[:k], N, (count, 2))
+        plains = _rows(rng, mods, N, (len(giant), len(baby)))
+        d, dp = ctx.upload(ct), ctx.upload(plains)
+        out = ctx.alloc(count * 2 * (k - 1) * N)
+        ctx.chunk_log()
+        ev.apply_galois_bsgs_plain_rescale(d, k, count, baby, [kk[1] for kk in bk], giant, [kk[1] for kk in gk], dp, out)
+        log = ctx.chunk_log()
+        got = out.download((count, 2, k - 1, N))
+        want = R.bsgs_plain_rescale(ref, k, ct[list(items)], baby, [kk[0] for kk in bk], giant, [kk[0] for kk in gk], plains)
+        for i, c in enumerate(items):
+            assert np.array_equal(got[c], want[i]), ("bsgs", baby, giant, c)
+        for b in (d, dp, out):
+            b.free()
+        return log
+
+    # ---- apply_galois_dot_plain_rescale
+    once, per_sum = digits, prod + temp + base2
+    per_chunk = budget // (once + 2 * per_sum)
+    assert per_chunk == 5
+    log = dot_plain(7, [3, 1, 5], 2, (0, 6), (0, 1))
+    assert log == [(7, per_chunk)], log                   # a second, ragged item chunk; the sum list whole
+    n_sums = 20
+    assert once + n_sums * per_sum > budget
+    per_pass = (budget - once) // per_sum
+    assert per_pass == n_sums - 1
+    log = dot_plain(2, [3], n_sums, (0, 1), (0, n_sums - 1))
+    assert log == [(n_sums, per_pass), (2, 1)], log       # the sum list split 19 + 1, one item per chunk
+    per_chunk = budget // (2 * (base2 + base2))
+    assert per_chunk == 16 and 2 * per_chunk <= nested
+    log = dot_plain(17, [1, 1], 2, (0, 16), (0, 1))
+    # one plain rescale per sum and chunk (a chunk is not the whole batch), each over the 2 m polynomials of its m items
+    assert log == [(17, per_chunk)] + [(32, 32)] * 2 + [(2, 2)] * 2, log
+
+    # ---- apply_galois_bsgs_plain_rescale
+    once, per_giant = digits + prod + temp + base2, (2 * k + 2 * (k + 1) + 3 * k + k * (k + 1)) * row
+    per_chunk = budget // (once + 2 * per_giant)
+    assert per_chunk == 2
+    log = bsgs(3, [3, 1], [5, 1], (0, 2))
+    assert log == [(3, per_chunk)], log                   # a second, ragged item chunk; the giant list whole
+    giants = [5, 7, 1, 9, 11, 5, 13]
+    assert once + len(giants) * per_giant > budget
+    per_pass = (budget - once) // per_giant
+    assert per_pass == len(giants) - 1
+    log = bsgs(2, [3, 1], giants, (0, 1))
+    assert log == [(len(giants), per_pass), (2, 1)], log  # the giant list split 6 + 1, one item per chunk
+    per_chunk = budget // (base2 + base2 + 2 * base2)
+    assert per_chunk == 16
+    log = bsgs(17, [1, 1], [1, 1], (0, 16))
+    assert log == [(17, per_chunk), (32, 32), (2, 2)], log  # one plain rescale of BASE per chunk
+    print("KS_RESCALE_CHUNKS_OK")
+
+
+def test_chunked_items_and_split_lists():
+    """apply_galois_dot_plain_rescale and apply_galois_bsgs_plain_rescale under the smallest arena: ragged item chunks, a
+    sum / giant list one longer than what fits next to one item, and the identity-only calls, whose plain rescale nests a
+    chunk loop under the raised floor. Chunk logs against the rule; first and last item (and sum) against the restatement."""
+    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode == 0 and "KS_RESCALE_CHUNKS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+
+
+if __name__ == "__main__" and "--child" in sys.argv:
+    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    _child()
