@@ -3281,6 +3281,107 @@ long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitc
     });
 }
 
+/* ---------------------------------------------------------------- RLWE samples from seeds */
+// the argument rules sealhip_sample_polys and its host form share; returns the item stride
+static std::size_t check_sample_args(const Engine &h, uint32_t n_ternary, uint32_t n_noise, size_t item_stride_words)
+{
+    const uint64_t polys = static_cast<uint64_t>(n_ternary) + n_noise;
+    if (polys == 0 || polys > kSampleMaxPolys)
+        throw std::invalid_argument("n_ternary + n_noise must be 1 .. 16");
+    const std::size_t words = static_cast<std::size_t>(polys) * h.n;
+    if (item_stride_words && item_stride_words < words)
+        throw std::invalid_argument("item stride is below (n_ternary + n_noise) x N");
+    return item_stride_words ? item_stride_words : words;
+}
+
+long sealhip_sample_polys(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary, uint32_t n_noise,
+                          int32_t *out_device, size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(out_device);
+    return guarded([&] {
+        const std::size_t stride = check_sample_args(*ctx->engine, n_ternary, n_noise, item_stride_words);
+        if ((stride & 3) || (reinterpret_cast<std::uintptr_t>(out_device) & 15))
+            throw std::invalid_argument("out_device must be 16-byte aligned and the item stride a multiple of 4");
+        Engine &e = device_engine(ctx);
+        op_sample_polys(e, seeds_host, count, n_ternary, n_noise, out_device, stride,
+                        out_device + static_cast<std::size_t>(n_ternary) * e.n, stride);
+    });
+}
+
+long sealhip_sample_polys_split(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary,
+                                uint32_t n_noise, int32_t *ternary_device, int32_t *noise_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    if (n_ternary)
+        REQUIRE_PTR(ternary_device);
+    if (n_noise)
+        REQUIRE_PTR(noise_device);
+    return guarded([&] {
+        (void)check_sample_args(*ctx->engine, n_ternary, n_noise, 0);
+        if ((reinterpret_cast<std::uintptr_t>(ternary_device) | reinterpret_cast<std::uintptr_t>(noise_device)) & 15)
+            throw std::invalid_argument("ternary_device and noise_device must be 16-byte aligned");
+        Engine &e = device_engine(ctx);
+        op_sample_polys(e, seeds_host, count, n_ternary, n_noise, ternary_device, static_cast<std::size_t>(n_ternary) * e.n,
+                        noise_device, static_cast<std::size_t>(n_noise) * e.n);
+    });
+}
+
+long sealhip_sample_polys_host(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary,
+                               uint32_t n_noise, int32_t *out_host, size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(out_host);
+    return guarded([&] {
+        Engine &e = *ctx->engine; // host work: also on host-only contexts
+        const std::size_t stride = check_sample_args(e, n_ternary, n_noise, item_stride_words);
+        for (size_t i = 0; i < count; i++)
+        {
+            uint64_t seed[8];
+            std::memcpy(seed, seeds_host + 8 * i, sizeof(seed));
+            sample_polys_host(seed, e.n, n_ternary, n_noise, out_host + i * stride);
+        }
+    });
+}
+
+long sealhip_debug_sample_map(sealhip_context *ctx, const uint64_t *words_device, size_t n, int32_t kind, int32_t *out_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(words_device);
+    REQUIRE_PTR(out_device);
+    return guarded([&] {
+        if (kind != 0 && kind != 1)
+            throw std::invalid_argument("kind must be 0 (ternary) or 1 (noise)");
+        Engine &e = device_engine(ctx);
+        op_debug_sample_map(e, reinterpret_cast<const u64 *>(words_device), n, kind == 1, out_device);
+    });
+}
+
+long sealhip_generate_secret_key(sealhip_context *ctx, const uint64_t seed_host[8], uint64_t *sk_ntt_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seed_host);
+    REQUIRE_PTR(sk_ntt_device);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        op_generate_secret_key(e, seed_host, reinterpret_cast<u64 *>(sk_ntt_device));
+    });
+}
+
+long sealhip_memset_zero(sealhip_context *ctx, void *dptr, size_t bytes)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(dptr);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (bytes)
+            SEALHIP_CHECK(hipMemsetAsync(dptr, 0, bytes, e.lane().stream));
+    });
+}
+
 long sealhip_is_data_valid_for(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,
                                uint8_t *valid)
 {

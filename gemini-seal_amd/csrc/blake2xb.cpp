@@ -4,6 +4,7 @@
 // H0 = BLAKE2b(64 bytes, XOF length = l) and output block i = BLAKE2b(H0; digest length min(64, rest), fanout 0, depth 0,
 // leaf length 64, node offset i, XOF length l, inner length 64).
 #include "blake2xb.hpp"
+#include "sample_map.hpp"
 
 #include <cstring>
 
@@ -206,6 +207,26 @@ namespace sealhip
                 } while (r >= max_multiple);
                 dst[j * n + i] = r % q;
             }
+        }
+    }
+    void sample_polys_host(const std::uint64_t (&seed)[8], std::size_t n, unsigned n_ternary, unsigned n_noise, std::int32_t *out)
+    {
+        unsigned char key[64], buffer[4096];
+        for (int i = 0; i < 8; i++)
+            for (int b = 0; b < 8; b++)
+                key[8 * i + b] = static_cast<unsigned char>(seed[i] >> (8 * b));
+        const std::size_t total = static_cast<std::size_t>(n_ternary + n_noise) * n;
+        for (std::size_t m = 0; m < total; m++) // stream word m: word m & 511 of buffer m >> 9
+        {
+            if ((m & 511) == 0)
+            {
+                unsigned char ctr[8];
+                for (int i = 0; i < 8; i++)
+                    ctr[i] = static_cast<unsigned char>((m >> 9) >> (8 * i));
+                (void)blake2xb(buffer, sizeof(buffer), ctr, sizeof(ctr), key, sizeof(key));
+            }
+            const std::uint64_t w = load64(buffer + 8 * (m & 511));
+            out[m] = m / n < n_ternary ? sample_ternary(w) : sample_noise(w);
         }
     }
 } // namespace sealhip

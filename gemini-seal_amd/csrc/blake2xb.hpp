@@ -26,4 +26,8 @@ namespace sealhip
 
     // sample_poly_uniform (util/rlwe.cpp:101-129): rows x n words, row j uniform modulo moduli[j] by rejection from 63 bits
     void sample_poly_uniform(BlakePrng &prng, const std::uint64_t *moduli, std::size_t rows, std::size_t n, std::uint64_t *dst);
+
+    // The library's RLWE sampling rule on the host (sample_map.hpp): out[p][n] for the n_ternary ternary
+    // and then n_noise noise polynomials of one item; coefficient j of polynomial p comes from word pn + j of BlakePRNG(seed)
+    void sample_polys_host(const std::uint64_t (&seed)[8], std::size_t n, unsigned n_ternary, unsigned n_noise, std::int32_t *out);
 } // namespace sealhip

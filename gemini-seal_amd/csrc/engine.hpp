@@ -1057,6 +1057,21 @@ namespace sealhip
     };
     void op_expand_seeds(Engine &e, int rows, const SeedJob *jobs, std::size_t count);
 
+    // ---- RLWE samples from seeds (seed_expand.hip, sample_map.hpp) ----
+    constexpr unsigned kSampleMaxPolys = 16; // polynomials per item
+    // Item i: n_ternary ternary polynomials at out + i * item_stride, n_noise noise polynomials at out_noise + i *
+    // noise_stride (int32, N values each), from the BlakePRNG stream of seed i (seeds_host: count x 8 words): word pN + j of
+    // the stream gives coefficient j of polynomial p, ternary ones first. One array out[i][p][N] is out_noise = out +
+    // n_ternary N with equal strides. Pointers are 16-byte aligned and strides multiples of 4. Stream-ordered on the calling
+    // thread's lane; the seeds are staged (not capturable), and the roots derived from them are erased from the arena.
+    void op_sample_polys(Engine &e, const std::uint64_t *seeds_host, std::size_t count, unsigned n_ternary, unsigned n_noise,
+                         std::int32_t *out, std::size_t item_stride, std::int32_t *out_noise, std::size_t noise_stride);
+    // the kernels' map functions on n caller-supplied words (device)
+    void op_debug_sample_map(Engine &e, const u64 *words, std::size_t n, bool noise, std::int32_t *out);
+    // KeyGenerator::generate_sk (keygenerator.cpp:66-103): one ternary polynomial from the seed, lifted over the n_key key
+    // primes and transformed; sk_ntt = n_key x N words. The coefficient-form scratch is erased.
+    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, u64 *sk_ntt);
+
     // ---- KeyGenerator::generate_one_kswitch_key for a batch of keys (keygen.hip, composition in pipeline.cpp) ----
     constexpr int kKeygenMaxKeys = 32; // keys per assemble launch (kernel-argument table)
     struct KeygenArgs

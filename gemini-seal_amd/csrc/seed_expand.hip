@@ -9,7 +9,11 @@
 // Phase A generates a provisioned number of candidates per seed fully in parallel (one lane per key block, per buffer root,
 // per leaf); phase B walks each seed's rows in one workgroup (flag, block scan, place) and generates in-kernel whatever it
 // needs beyond the provision, so the result is exact for every seed, not only for those whose rejections fit the slack.
+// The same PRNG also feeds the RLWE samplers (DESIGN.md "RLWE samples on the device from seeds"): phases A.0 and A.1, then
+// sample_leaf_kernel maps every raw stream word to one ternary or noise sample (sample_map.hpp) -- fixed consumption, so
+// there is no candidate arena and no phase B.
 #include "engine.hpp"
+#include "sample_map.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -124,8 +128,9 @@ namespace sealhip
             b2_compress<true>(h, m, 136);
         }
 
-        // leaf `leaf` of a buffer (64 bytes, t = 64, last), and its 8 words as candidates r
-        __host__ __device__ __forceinline__ void leaf_candidates(const u64 (&h0)[8], unsigned leaf, u64 (&r)[8])
+        // leaf `leaf` of a buffer (64 bytes, t = 64, last): its 8 output words, the stream words 8 leaf .. 8 leaf + 7 of the
+        // buffer
+        __host__ __device__ __forceinline__ void leaf_words(const u64 (&h0)[8], unsigned leaf, u64 (&r)[8])
         {
 #pragma unroll
             for (int i = 0; i < 8; i++)
@@ -134,6 +139,12 @@ namespace sealhip
             r[1] ^= kLeafP1 | leaf;
             r[2] ^= kLeafP2;
             b2_compress<true>(r, h0, 64);
+        }
+
+        // the same leaf's 8 words as sample_poly_uniform's candidates r
+        __host__ __device__ __forceinline__ void leaf_candidates(const u64 (&h0)[8], unsigned leaf, u64 (&r)[8])
+        {
+            leaf_words(h0, leaf, r);
             // generate() hands out low32(w) first (hi), then high32(w) (lo), and r = (hi << 31) | (lo >> 1) (util/rlwe.cpp:124):
             // the word rotated left by 31 with bit 63 (bit 32 of w) cleared
 #pragma unroll
@@ -301,6 +312,84 @@ namespace sealhip
             }
         }
 
+        // ---------------------------------------------------------------- RLWE samples
+        // An item's stream words [pN, (p+1)N) become polynomial p: ternary for p < n_ternary, noise after. `leaves` =
+        // (n_ternary + n_noise) N / 8 leaves in `nbuf` buffers per item, the last one partial when N < 512.
+        struct SampleArgs
+        {
+            unsigned logn, n_ternary, leaves, nbuf;
+            // item s: its ternary polynomials at out + s * stride, its noise polynomials at out_noise + s * stride_noise
+            // (16-byte aligned, strides multiples of 4); one array out[i][p][N] has out_noise = out + n_ternary N
+            std::int32_t *out, *out_noise;
+            std::size_t stride, stride_noise;
+        };
+
+        // One lane per leaf, one wave per buffer (so H0 is a scalar load): the leaf's 8 words mapped by the kind of its
+        // polynomial (N >= 8: a leaf lies in one polynomial) and written with two 16-byte stores. Lanes past the item's
+        // last leaf write nothing.
+        __global__ __launch_bounds__(kGenThreads) void sample_leaf_kernel(const u64 *__restrict__ h0, const SampleArgs a,
+                                                                         unsigned total_bufs)
+        {
+            const std::size_t g = static_cast<std::size_t>(blockIdx.x) * kGenThreads + threadIdx.x;
+            const unsigned bi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(g >> 6));
+            if (bi >= total_bufs)
+                return;
+            const unsigned s = bi / a.nbuf, lane = static_cast<unsigned>(g & 63), leaf = (bi - s * a.nbuf) * 64 + lane;
+            if (leaf >= a.leaves)
+                return;
+            u64 h[8], w[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                h[i] = h0[static_cast<std::size_t>(bi) * 8 + i];
+            leaf_words(h, lane, w);
+            std::int32_t v[8];
+            int4 *dst;
+            const unsigned ternary_leaves = a.n_ternary << (a.logn - 3);
+            if (leaf >= ternary_leaves) // the kind is public: only the words are secret
+            {
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    v[i] = sample_noise(w[i]);
+                dst = reinterpret_cast<int4 *>(a.out_noise + static_cast<std::size_t>(s) * a.stride_noise +
+                                               static_cast<std::size_t>(leaf - ternary_leaves) * 8);
+            }
+            else
+            {
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    v[i] = sample_ternary(w[i]);
+                dst = reinterpret_cast<int4 *>(a.out + static_cast<std::size_t>(s) * a.stride + static_cast<std::size_t>(leaf) * 8);
+            }
+            dst[0] = make_int4(v[0], v[1], v[2], v[3]);
+            dst[1] = make_int4(v[4], v[5], v[6], v[7]);
+        }
+
+        // the kernel's own map functions on caller-supplied words (sealhip_debug_sample_map)
+        __global__ __launch_bounds__(kGenThreads) void sample_map_kernel(const u64 *__restrict__ words, std::size_t n, bool noise,
+                                                                        std::int32_t *__restrict__ out)
+        {
+            const std::size_t i = static_cast<std::size_t>(blockIdx.x) * kGenThreads + threadIdx.x;
+            if (i < n)
+                out[i] = noise ? sample_noise(words[i]) : sample_ternary(words[i]);
+        }
+
+        // KeyGenerator::generate_sk's lift (keygenerator.cpp:78-84): row j of the key is the ternary polynomial mod q_j
+        struct LiftArgs
+        {
+            int rows, logn;
+            u64 q[kMaxModuli];
+        };
+        __global__ __launch_bounds__(kGenThreads) void ternary_lift_kernel(const std::int32_t *__restrict__ t, u64 *__restrict__ out,
+                                                                          const LiftArgs a)
+        {
+            const std::size_t i = static_cast<std::size_t>(blockIdx.x) * kGenThreads + threadIdx.x;
+            if (i >= (static_cast<std::size_t>(a.rows) << a.logn))
+                return;
+            const std::int32_t v = t[i & ((std::size_t(1) << a.logn) - 1)];
+            const u64 q = a.q[i >> a.logn];
+            out[i] = v < 0 ? q - static_cast<u64>(-v) : static_cast<u64>(v);
+        }
+
         // candidates a seed needs, as a function of the rows' rejection rates: row j rejects a fraction
         // f_j = (((2^63 - 1) mod q_j) + 2) / 2^63; its rejections before N acceptances are negative-binomial with mean
         // N f/(1-f) and variance N f/(1-f)^2. Slack = mean + 8 standard deviations + 64.
@@ -315,6 +404,94 @@ namespace sealhip
                 var += static_cast<double>(e.n) * f / ((1 - f) * (1 - f));
             }
             return static_cast<u64>(std::ceil(mean + 8 * std::sqrt(var))) + 64;
+        }
+        // The lane's pinned staging for `count` records of 9 words (seed, destination), once its previous copy has left
+        // it. The caller fills l.seed_pin, enqueues its copies and records l.seed_pin_done after the last one.
+        void stage_records(Lane &l, std::size_t count)
+        {
+            const std::size_t rec_words = count * 9;
+            if (l.seed_pin_done)
+                SEALHIP_CHECK(hipEventSynchronize(l.seed_pin_done));
+            else
+                SEALHIP_CHECK(hipEventCreateWithFlags(&l.seed_pin_done, hipEventDisableTiming));
+            if (rec_words > l.seed_pin_words)
+            {
+                if (l.seed_pin)
+                    SEALHIP_CHECK(hipHostFree(l.seed_pin));
+                l.seed_pin = nullptr;
+                l.seed_pin_words = 0;
+                SEALHIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&l.seed_pin), rec_words * 8, hipHostMallocDefault));
+                l.seed_pin_words = rec_words;
+            }
+        }
+
+        // phases A.0 and A.1 for the m staged records from `off`: records to the device, key states, buffer roots
+        void roots_of_chunk(Engine &e, std::size_t off, std::size_t m, std::size_t nbuf, u64 *rec, u64 *ks, u64 *h0)
+        {
+            Lane &l = e.lane();
+            SEALHIP_CHECK(hipMemcpyAsync(rec, l.seed_pin + off * 9, m * 9 * 8, hipMemcpyHostToDevice, l.stream));
+            {
+                ProfScope prof(e, "seed_key_state", static_cast<double>(m));
+                seed_key_state_kernel<<<static_cast<unsigned>((m + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
+                    rec, ks, static_cast<unsigned>(m));
+                check(hipGetLastError(), "seed_key_state");
+            }
+            const std::size_t nroots = m * nbuf;
+            {
+                ProfScope prof(e, "seed_buffer_root", static_cast<double>(nroots));
+                seed_buffer_root_kernel<<<static_cast<unsigned>((nroots + kGenThreads - 1) / kGenThreads), kGenThreads, 0,
+                                          l.stream>>>(ks, h0, static_cast<unsigned>(nbuf), static_cast<unsigned>(nroots));
+                check(hipGetLastError(), "seed_buffer_root");
+            }
+        }
+
+        // The sampling steps of one chunk inside a for_chunks body: roots of the m staged seeds from `off`, then every leaf
+        // an item needs, mapped. The roots are erased afterwards: a noise seed's roots give its whole stream.
+        void sample_chunk(Engine &e, std::size_t off, std::size_t m, SampleArgs a)
+        {
+            Lane &l = e.lane();
+            const std::size_t nroots = m * a.nbuf;
+            u64 *h0 = e.ws_alloc(nroots * 8);
+            u64 *ks = e.ws_alloc(m * 8);
+            u64 *rec = e.ws_alloc(m * 9);
+            roots_of_chunk(e, off, m, a.nbuf, rec, ks, h0);
+            {
+                ProfScope prof(e, "sample_leaf", static_cast<double>(m) * a.leaves);
+                sample_leaf_kernel<<<static_cast<unsigned>((nroots * 64 + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
+                    h0, a, static_cast<unsigned>(nroots));
+                check(hipGetLastError(), "sample_leaf");
+            }
+            SEALHIP_CHECK(hipMemsetAsync(h0, 0, nroots * 64, l.stream));
+            SEALHIP_CHECK(hipMemsetAsync(ks, 0, m * 64, l.stream));
+            SEALHIP_CHECK(hipMemsetAsync(rec, 0, m * 72, l.stream));
+        }
+        // bytes of sample_chunk's three temporaries per item
+        std::size_t sample_item_bytes(const SampleArgs &a)
+        {
+            return (static_cast<std::size_t>(a.nbuf) * 8 + 8 + 9) * 8;
+        }
+
+        SampleArgs sample_args(const Engine &e, unsigned n_ternary, unsigned n_noise)
+        {
+            if (n_ternary + n_noise == 0 || n_ternary + n_noise > kSampleMaxPolys)
+                throw std::invalid_argument("n_ternary + n_noise must be 1 .. 16");
+            SampleArgs a{};
+            a.logn = static_cast<unsigned>(e.logn);
+            a.n_ternary = n_ternary;
+            a.leaves = static_cast<unsigned>((static_cast<std::size_t>(n_ternary + n_noise) * e.n) >> 3);
+            a.nbuf = (a.leaves + 63) / 64;
+            return a;
+        }
+
+        // seeds (count x 8 words, host) into the staging; the caller has checked that the lane is not capturing
+        void stage_seeds(Lane &l, const std::uint64_t *seeds_host, std::size_t count)
+        {
+            stage_records(l, count);
+            for (std::size_t i = 0; i < count; i++)
+            {
+                std::memcpy(l.seed_pin + i * 9, seeds_host + i * 8, 64);
+                l.seed_pin[i * 9 + 8] = 0;
+            }
         }
     } // namespace
 
@@ -347,21 +524,7 @@ namespace sealhip
             pa.cr1[j] = static_cast<u64>((static_cast<unsigned __int128>(1) << 64) / q); // floor(2^64 / q): barrett_reduce_63
         }
 
-        // stage the records (seed, destination) in the lane's pinned buffer once its previous copy has left it
-        const std::size_t rec_words = count * 9;
-        if (l.seed_pin_done)
-            SEALHIP_CHECK(hipEventSynchronize(l.seed_pin_done));
-        else
-            SEALHIP_CHECK(hipEventCreateWithFlags(&l.seed_pin_done, hipEventDisableTiming));
-        if (rec_words > l.seed_pin_words)
-        {
-            if (l.seed_pin)
-                SEALHIP_CHECK(hipHostFree(l.seed_pin));
-            l.seed_pin = nullptr;
-            l.seed_pin_words = 0;
-            SEALHIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&l.seed_pin), rec_words * 8, hipHostMallocDefault));
-            l.seed_pin_words = rec_words;
-        }
+        stage_records(l, count);
         for (std::size_t i = 0; i < count; i++)
         {
             std::memcpy(l.seed_pin + i * 9, jobs[i].seed, 64);
@@ -375,20 +538,8 @@ namespace sealhip
             u64 *h0 = e.ws_alloc(m * nbuf * 8);
             u64 *ks = e.ws_alloc(m * 8);
             u64 *rec = e.ws_alloc(m * 9);
-            SEALHIP_CHECK(hipMemcpyAsync(rec, l.seed_pin + off * 9, m * 9 * 8, hipMemcpyHostToDevice, l.stream));
-            {
-                ProfScope prof(e, "seed_key_state", static_cast<double>(m));
-                seed_key_state_kernel<<<static_cast<unsigned>((m + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
-                    rec, ks, static_cast<unsigned>(m));
-                check(hipGetLastError(), "seed_key_state");
-            }
+            roots_of_chunk(e, off, m, nbuf, rec, ks, h0);
             const std::size_t nroots = m * nbuf;
-            {
-                ProfScope prof(e, "seed_buffer_root", static_cast<double>(nroots));
-                seed_buffer_root_kernel<<<static_cast<unsigned>((nroots + kGenThreads - 1) / kGenThreads), kGenThreads, 0,
-                                          l.stream>>>(ks, h0, static_cast<unsigned>(nbuf), static_cast<unsigned>(nroots));
-                check(hipGetLastError(), "seed_buffer_root");
-            }
             const std::size_t leaves = nroots * 64;
             {
                 ProfScope prof(e, "seed_leaf", static_cast<double>(leaves));
@@ -404,5 +555,62 @@ namespace sealhip
         });
         // every record copy has been enqueued before this: once the event completes, the staging may be rewritten
         SEALHIP_CHECK(hipEventRecord(l.seed_pin_done, l.stream));
+    }
+    void op_sample_polys(Engine &e, const std::uint64_t *seeds_host, std::size_t count, unsigned n_ternary, unsigned n_noise,
+                         std::int32_t *out, std::size_t item_stride, std::int32_t *out_noise, std::size_t noise_stride)
+    {
+        SampleArgs a = sample_args(e, n_ternary, n_noise);
+        if (count == 0)
+            return;
+        if (count > 0xFFFFFFFFull / 64 / a.nbuf)
+            throw std::invalid_argument("sampling: too many leaves in one call");
+        Lane &l = e.lane();
+        if (l.capturing)
+            throw std::logic_error("sampling stages its seeds on the host: it cannot be captured in a graph");
+        stage_seeds(l, seeds_host, count);
+        for_chunks(e, count, sample_item_bytes(a), 3, [&](std::size_t off, std::size_t m) {
+            a.out = out + off * item_stride;
+            a.stride = item_stride;
+            a.out_noise = out_noise + off * noise_stride;
+            a.stride_noise = noise_stride;
+            sample_chunk(e, off, m, a);
+        });
+        SEALHIP_CHECK(hipEventRecord(l.seed_pin_done, l.stream));
+    }
+
+    void op_debug_sample_map(Engine &e, const u64 *words, std::size_t n, bool noise, std::int32_t *out)
+    {
+        if (n == 0)
+            return;
+        sample_map_kernel<<<static_cast<unsigned>((n + kGenThreads - 1) / kGenThreads), kGenThreads, 0, e.lane().stream>>>(
+            words, n, noise, out);
+        check(hipGetLastError(), "sample_map");
+    }
+
+    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, u64 *sk_ntt)
+    {
+        SampleArgs a = sample_args(e, 1, 0);
+        Lane &l = e.lane();
+        if (l.capturing)
+            throw std::logic_error("sampling stages its seeds on the host: it cannot be captured in a graph");
+        LiftArgs la{};
+        la.rows = e.n_key;
+        la.logn = e.logn;
+        for (int j = 0; j < e.n_key; j++)
+            la.q[j] = e.key_moduli[j];
+        stage_seeds(l, seed_host, 1);
+        const std::size_t t_words = (e.n + 1) / 2, total = static_cast<std::size_t>(e.n_key) * e.n;
+        for_chunks(e, 1, sample_item_bytes(a) + t_words * 8, 4, [&](std::size_t off, std::size_t m) {
+            std::int32_t *t = reinterpret_cast<std::int32_t *>(e.ws_alloc(t_words));
+            a.out = a.out_noise = t;
+            a.stride = a.stride_noise = 0;
+            sample_chunk(e, off, m, a);
+            ternary_lift_kernel<<<static_cast<unsigned>((total + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
+                t, sk_ntt, la);
+            check(hipGetLastError(), "ternary_lift");
+            SEALHIP_CHECK(hipMemsetAsync(t, 0, t_words * 8, l.stream));
+        });
+        SEALHIP_CHECK(hipEventRecord(l.seed_pin_done, l.stream));
+        check(launch_ntt(e, sk_ntt, static_cast<std::size_t>(e.n_key), ct_row_map(e.n_key, 1, -1), false, kNttCanonical), "ntt(sk)");
     }
 } // namespace sealhip

@@ -255,8 +255,33 @@ namespace sealhip_host
         std::size_t words_;
     };
 
+    // Staging that held secret samples (u, the noise, a secret key in coefficient form): erased in stream order before the
+    // block goes back to the pool, as the reference's clear_on_destruction pool does (util/rlwe.cpp:141)
+    class ZeroedStaged : public Staged
+    {
+    public:
+        ZeroedStaged(const Context &c, std::size_t words) : Staged(c, words), ctx_(c) {}
+        ~ZeroedStaged() { sealhip_memset_zero(ctx_.get(), ptr(), (words() ? words() : 1) * 8); }
+
+    private:
+        const Context &ctx_;
+    };
+
+    // Where the random samples come from when they are drawn on the device (sealhip_sample_polys): the
+    // source is asked for one 64-byte seed at a time (a CSPRNG's output; never reuse one). Only seeds cross from the host.
+    using SeedSource = std::function<void(std::uint64_t *seed8)>;
+
     namespace detail
     {
+        // two seeds from the source, in order; the second (a noise seed, secret) must not be the first (c_1's, public)
+        inline void draw_seed_pair(const SeedSource &source, std::uint64_t *public_seed, std::uint64_t *noise_seed)
+        {
+            source(public_seed);
+            source(noise_seed);
+            if (std::equal(public_seed, public_seed + 8, noise_seed))
+                throw std::logic_error("the seed source returned the same seed twice");
+        }
+
         // HostCiphertext needs its N before resize_raw; seal::Ciphertext gets it from its parms_id
         template <class C>
         auto prepare_host(C &c, std::size_t n) -> decltype(c.n_ = n, void())
@@ -2312,7 +2337,8 @@ namespace sealhip_host
     // BlakePRNGFactory().create() seed of c_1 and the N values of e. Ciphertexts are made on the device
     // (sealhip_encryptor_encrypt, sealhip_encryptor_encrypt_symmetric); the batch overloads make one call per run of equal
     // level. The seeded forms return the Serializable<Ciphertext> stream (the level's parms_id must be registered with
-    // sealhip_context_set_parms_id).
+    // sealhip_context_set_parms_id). Built with a SeedSource instead of the samplers, it draws u and the noise on the device
+    // from seeds: the library's own streams, the reference's noise law.
     template <class CT>
     class Encryptor
     {
@@ -2333,6 +2359,20 @@ namespace sealhip_host
             throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
             k_first_ = k_first;
         }
+        // The samples drawn on the device: a public-key encryption asks `seeds` for one seed and samples (1, 2) = u, e_0,
+        // e_1 from it; a secret-key encryption asks for two, c_1's seed and then a separate noise seed sampled as (0, 1) --
+        // c_1's seed is public in a seeded stream, the noise seed never leaves this call. The scratch that held the samples
+        // is erased before it goes back to the pool.
+        Encryptor(const Context &context, const std::uint64_t *public_key, const std::uint64_t *secret_key_ntt, SeedSource seeds)
+            : Encryptor(context, public_key, secret_key_ntt, AsymSampler(), SymSampler())
+        {
+            if (!seeds)
+                throw std::invalid_argument("seed source is empty");
+            seeds_ = std::move(seeds);
+        }
+        // where the samples of the last seed-source encryption lay on the device (pointer, bytes), for tests: the blocks
+        // are back in the pool, erased
+        const std::vector<std::pair<const void *, std::size_t>> &last_sample_scratch() const { return scratch_; }
         void set_public_key(const std::uint64_t *public_key)
         {
             pk_.assign(public_key, public_key + 2 * ctx_.n_key() * ctx_.n());
@@ -2499,7 +2539,40 @@ namespace sealhip_host
                 if (dp)
                     dp->up(host_plain.data(), host_plain.size());
                 Staged ct(ctx_, count * words);
-                if (asymmetric)
+                if (seeds_)
+                {
+                    std::vector<std::uint64_t> seeds(count * 8), noise_seeds(asymmetric ? 0 : count * 8);
+                    for (std::size_t i = 0; i < count; i++)
+                    {
+                        if (asymmetric)
+                            seeds_(seeds.data() + 8 * i);
+                        else
+                            detail::draw_seed_pair(seeds_, seeds.data() + 8 * i, noise_seeds.data() + 8 * i);
+                    }
+                    ZeroedStaged du(ctx_, asymmetric ? (count * n + 1) / 2 : 0), de(ctx_, (count * (asymmetric ? 2 : 1) * n + 1) / 2);
+                    auto *u32 = reinterpret_cast<std::int32_t *>(du.ptr()), *e32 = reinterpret_cast<std::int32_t *>(de.ptr());
+                    scratch_.assign({ { de.ptr(), de.words() * 8 } });
+                    if (asymmetric)
+                        scratch_.push_back({ du.ptr(), du.words() * 8 });
+                    if (asymmetric)
+                    {
+                        throw_on(sealhip_sample_polys_split(ctx_.get(), seeds.data(), count, 1, 2, u32, e32));
+                        throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key, dp ? dp->ptr() : nullptr, pw, u32,
+                                                           e32, count, ct.ptr()));
+                        std::fill(seeds.begin(), seeds.end(), 0); // (u and the noise follow from them)
+                    }
+                    else
+                    {
+                        throw_on(sealhip_sample_polys(ctx_.get(), noise_seeds.data(), count, 0, 1, e32, 0));
+                        throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key,
+                                                                     dp ? dp->ptr() : nullptr, pw, seeds.data(), e32,
+                                                                     save_seed ? 1 : 0, count, ct.ptr()));
+                        std::fill(noise_seeds.begin(), noise_seeds.end(), 0);
+                        if (seeds_out) // c_1's seeds only: the noise seeds stay here
+                            seeds_out->insert(seeds_out->end(), seeds.begin(), seeds.end());
+                    }
+                }
+                else if (asymmetric)
                 {
                     std::vector<std::int32_t> u(count * n), e(count * 2 * n);
                     for (std::size_t i = 0; i < count; i++)
@@ -2579,6 +2652,8 @@ namespace sealhip_host
         std::unique_ptr<Staged> dpk_, dsk_; // the keys on the device (device_key)
         AsymSampler asym_;
         SymSampler sym_;
+        SeedSource seeds_; // set: the samples are drawn on the device
+        std::vector<std::pair<const void *, std::size_t>> scratch_;
         std::size_t k_first_ = 0;
     };
 
@@ -2586,6 +2661,7 @@ namespace sealhip_host
     // host). Sampling stays with the caller: `sampler(seed, noise)` is asked once per encrypt_zero_symmetric, in the
     // reference's order (key by key, digit by digit), for the 8-word BlakePRNGFactory().create() seed of c_1 and the N
     // signed values of sample_poly_normal. The keys are made on the device (sealhip_generate_*_keys).
+    // Built with a SeedSource instead of the sampler, it draws the noise on the device from seeds.
     class KeyGenerator
     {
     public:
@@ -2596,6 +2672,29 @@ namespace sealhip_host
         KeyGenerator(const Context &context, const std::uint64_t *secret_key_ntt, Sampler sampler)
             : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n()), sampler_(std::move(sampler))
         {}
+        // The noise drawn on the device: every encrypt_zero_symmetric (a key digit, the public key) asks `seeds` for two
+        // seeds, c_1's and then a separate noise seed sampled as (0, 1). save_seed keeps c_1's seeds only.
+        KeyGenerator(const Context &context, const std::uint64_t *secret_key_ntt, SeedSource seeds)
+            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n()), seeds_(std::move(seeds))
+        {
+            if (!seeds_)
+                throw std::invalid_argument("seed source is empty");
+        }
+
+        // generate_sk (keygenerator.cpp:66-103) on the device from one seed of `seeds` (sealhip_generate_secret_key): the
+        // n_key x N words of the secret key in NTT form
+        static std::vector<std::uint64_t> generate_secret_key(const Context &context, const SeedSource &seeds)
+        {
+            std::uint64_t seed[8];
+            seeds(seed);
+            const std::size_t words = context.n_key() * context.n();
+            ZeroedStaged sk(context, words);
+            throw_on(sealhip_generate_secret_key(context.get(), seed, sk.ptr()));
+            std::fill(seed, seed + 8, 0);
+            std::vector<std::uint64_t> out(words);
+            sk.down(out.data(), words);
+            return out;
+        }
 
         // relin_keys(count, save_seed) (:146-175): keys[i] is the key of sk^(i+2) (RelinKeys::get_index(i + 2) = i)
         Keys relin_keys(std::size_t count, bool save_seed = false)
@@ -2648,11 +2747,11 @@ namespace sealhip_host
         {
             const std::size_t n = ctx_.n(), nk = ctx_.n_key();
             std::uint64_t seed[8];
-            std::vector<std::int32_t> noise(n);
-            sampler_(seed, noise.data());
-            Staged sk(ctx_, nk * n), a(ctx_, nk * n), e(ctx_, (n + 1) / 2), ct(ctx_, 2 * nk * n);
+            Drawn drawn = draw(seed, 1);
+            Staged sk(ctx_, nk * n), a(ctx_, nk * n), ct(ctx_, 2 * nk * n);
+            ZeroedStaged e(ctx_, (n + 1) / 2);
             sk.up(sk_.data(), nk * n);
-            throw_on(sealhip_memcpy_h2d(ctx_.get(), e.ptr(), noise.data(), n * sizeof(std::int32_t)));
+            to_device(drawn, 1, e);
             throw_on(sealhip_expand_seed(ctx_.get(), std::uint32_t(nk), seed, 1, a.ptr(), 0));
             throw_on(sealhip_encrypt_zero_symmetric(ctx_.get(), std::uint32_t(nk), 1, a.ptr(),
                                                     reinterpret_cast<const std::int32_t *>(e.ptr()), sk.ptr(), 1, ct.ptr()));
@@ -2689,12 +2788,11 @@ namespace sealhip_host
             throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
             const std::size_t n = ctx_.n(), nk = ctx_.n_key(), d = digits, items = n_keys * d;
             std::vector<std::uint64_t> seeds(items * 8);
-            std::vector<std::int32_t> noise(items * n);
-            for (std::size_t i = 0; i < items; i++)
-                sampler_(seeds.data() + 8 * i, noise.data() + n * i);
-            Staged sk(ctx_, nk * n), e(ctx_, (items * n + 1) / 2);
+            Drawn drawn = draw(seeds.data(), items);
+            Staged sk(ctx_, nk * n);
+            ZeroedStaged e(ctx_, (items * n + 1) / 2);
             sk.up(sk_.data(), nk * n);
-            throw_on(sealhip_memcpy_h2d(ctx_.get(), e.ptr(), noise.data(), noise.size() * sizeof(std::int32_t)));
+            to_device(drawn, items, e);
             std::vector<sealhip_kswitch_key *> raw(n_keys, nullptr);
             const auto *en = reinterpret_cast<const std::int32_t *>(e.ptr());
             if (elts)
@@ -2708,8 +2806,45 @@ namespace sealhip_host
             return out;
         }
 
+        // What `items` encrypt_zero_symmetric calls draw on the host, item by item in the reference's order, before any
+        // device work: c_1's seed (into seeds, 8 words per item) and either the N noise values from the sampler, or a second
+        // seed from the seed source, from which to_device samples them as (0, 1) and which is dropped there
+        struct Drawn
+        {
+            std::vector<std::int32_t> noise;
+            std::vector<std::uint64_t> noise_seeds;
+        };
+        Drawn draw(std::uint64_t *seeds, std::size_t items)
+        {
+            Drawn d;
+            const std::size_t n = ctx_.n();
+            if (seeds_)
+            {
+                d.noise_seeds.resize(items * 8);
+                for (std::size_t i = 0; i < items; i++)
+                    detail::draw_seed_pair(seeds_, seeds + 8 * i, d.noise_seeds.data() + 8 * i);
+                return d;
+            }
+            d.noise.resize(items * n);
+            for (std::size_t i = 0; i < items; i++)
+                sampler_(seeds + 8 * i, d.noise.data() + n * i);
+            return d;
+        }
+        void to_device(Drawn &d, std::size_t items, Staged &e)
+        {
+            auto *e32 = reinterpret_cast<std::int32_t *>(e.ptr());
+            if (seeds_)
+            {
+                throw_on(sealhip_sample_polys(ctx_.get(), d.noise_seeds.data(), items, 0, 1, e32, 0));
+                std::fill(d.noise_seeds.begin(), d.noise_seeds.end(), 0);
+            }
+            else
+                throw_on(sealhip_memcpy_h2d(ctx_.get(), e32, d.noise.data(), d.noise.size() * sizeof(std::int32_t)));
+        }
+
         const Context &ctx_;
         std::vector<std::uint64_t> sk_;
         Sampler sampler_;
+        SeedSource seeds_; // set: the noise is drawn on the device
     };
 } // namespace sealhip_host

@@ -195,6 +195,12 @@ SYMBOLS = {
     "sealhip_expand_seed_host": [_vp, _u32, _vp, _vp],
     "sealhip_expand_seed": [_vp, _u32, _vp, _sz, _vp, _sz],
     "sealhip_debug_seed_slack": [_vp, C.c_int64],
+    "sealhip_sample_polys": [_vp, _vp, _sz, _u32, _u32, _vp, _sz],
+    "sealhip_sample_polys_host": [_vp, _vp, _sz, _u32, _u32, _vp, _sz],
+    "sealhip_sample_polys_split": [_vp, _vp, _sz, _u32, _u32, _vp, _vp],
+    "sealhip_debug_sample_map": [_vp, _vp, _sz, _i32, _vp],
+    "sealhip_generate_secret_key": [_vp, _vp, _vp],
+    "sealhip_memset_zero": [_vp, _vp, _sz],
     "sealhip_ciphertext_load_many": [_vp, _vp, _vp, _sz, _vp, _vp, _sz],
     "sealhip_host_register": [_vp, _vp, _sz],
     "sealhip_host_unregister": [_vp, _vp],
@@ -754,6 +760,50 @@ class Context:
                                                   seeds.ctypes.data if seeds.size else None,
                                                   _ptr(noise) if noise is not None else None, 1 if keep_seeds else 0, out))
         return [KSwitchKeys._adopt(self, out[i]) for i in range(elts.size)]
+
+    # ---- RLWE samples from seeds
+    def sample_polys(self, seeds, n_ternary, n_noise, out, item_stride=0):
+        """sealhip_sample_polys: seeds = count x 8 words (host); out + i * item_stride int32 words (0: (n_ternary + n_noise)
+        x N) receives item i's n_ternary ternary and then n_noise noise polynomials of N int32 values (device)"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        _check(lib().sealhip_sample_polys(self.handle, seeds.ctypes.data, seeds.shape[0], n_ternary, n_noise, _ptr(out),
+                                          item_stride))
+
+    def sample_polys_split(self, seeds, n_ternary, n_noise, ternary, noise):
+        """sealhip_sample_polys_split: the same samples as ternary[count][n_ternary][N] and noise[count][n_noise][N]"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        _check(lib().sealhip_sample_polys_split(self.handle, seeds.ctypes.data, seeds.shape[0], n_ternary, n_noise,
+                                                _ptr(ternary) if ternary is not None else None,
+                                                _ptr(noise) if noise is not None else None))
+
+    def sample_polys_host(self, seeds, n_ternary, n_noise, item_stride=0):
+        """sealhip_sample_polys_host: the same words computed on the host; returns int32 [count][item_stride or polys x N]"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        width = item_stride if item_stride else (n_ternary + n_noise) * self.n
+        out = np.zeros((seeds.shape[0], width), dtype=np.int32)
+        _check(lib().sealhip_sample_polys_host(self.handle, seeds.ctypes.data, seeds.shape[0], n_ternary, n_noise,
+                                               out.ctypes.data, item_stride))
+        return out
+
+    def debug_sample_map(self, words, kind):
+        """sealhip_debug_sample_map: the kernels' map (kind 0 ternary, 1 noise) of the given 64-bit words; returns int32"""
+        words = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).reshape(-1))
+        n = words.size
+        src = self.upload(words if n else np.zeros(1, dtype=np.uint64))
+        dst = self.alloc((n + 1) // 2 + 1)
+        _check(lib().sealhip_debug_sample_map(self.handle, _ptr(src), n, kind, _ptr(dst)))
+        return dst.download().view(np.int32)[:n].copy()
+
+    def generate_secret_key(self, seed, out=None):
+        """sealhip_generate_secret_key: the n_key x N words (NTT form, device) of the secret key drawn from `seed` (8 words)"""
+        seed = np.ascontiguousarray(np.asarray(seed, dtype=np.uint64).reshape(8))
+        out = self.alloc(self.n_key * self.n) if out is None else out
+        _check(lib().sealhip_generate_secret_key(self.handle, seed.ctypes.data, _ptr(out)))
+        return out
+
+    def memset_zero(self, buf, nbytes):
+        """stream-ordered zero fill of device memory (sealhip_memset_zero)"""
+        _check(lib().sealhip_memset_zero(self.handle, _ptr(buf), nbytes))
 
     def debug_seed_slack(self, extra):
         """candidates provisioned per seed beyond rows x N on this thread's lane (< 0: the default; sealhip_debug_seed_slack)"""

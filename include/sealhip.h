@@ -982,6 +982,47 @@ long sealhip_generate_galois_keys(sealhip_context *ctx, const uint64_t *sk_ntt, 
    expands the seeds on the device. */
 long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots,
                                       void *bytes, size_t capacity, size_t *written);
+/* ---------------------------------------------------------------- RLWE samples from seeds */
+/* The ternary polynomials (u, the secret key) and the noise polynomials (e, e_0, e_1) of encryption and key generation,
+   drawn on the device from 64-byte seeds, so that only seeds cross from the host. The rule is the library's own (the
+   streams are NOT the reference's sample_poly_ternary / sample_poly_normal streams); the noise LAW is the reference's.
+     stream word m of seed S = the little-endian 64-bit word at byte 8m of BlakePRNG(S) (the words under
+       sealhip_expand_seed, before its rotate-and-mask);
+     item i draws n_ternary ternary polynomials, then n_noise noise polynomials; coefficient j of polynomial p comes from
+       word pN + j alone (fixed consumption: no rejection);
+     ternary: mulhi64(w, 3) - 1; noise: with r = w >> 1, magnitude = #{m in 0..18 : r >= T_m}, negative when w & 1, where
+       T_m are the 19 constants of csrc/sample_map.hpp: trunc(X), X ~ N(0, 3.2^2) conditioned on |X| <= 19.2
+       (util/rlwe.cpp:57-99), to within 2^-40 in statistical distance.
+   sealhip_sample_polys: out_device + i * item_stride_words (int32 words) receives out[i][p][N] for seed i (seeds_host: count
+   x 8 words). item_stride_words 0 means (n_ternary + n_noise) x N. Checks: null pointers -> E_POINTER; then, also on
+   host-only contexts, n_ternary + n_noise outside 1..16, a nonzero stride below (n_ternary + n_noise) x N, a stride that
+   is no multiple of 4 or an out_device that is not 16-byte aligned (the kernel stores 16 bytes at a time) -> E_INVALIDARG;
+   then a host-only context -> COR_E_INVALIDOPERATION; count 0 -> S_OK, nothing launched. Runs on the calling thread's lane
+   in stream order; the seeds are staged before it returns (not capturable). The PRNG roots it derives are erased from the
+   arena in stream order; out_device is the caller's to erase (sealhip_memset_zero).
+   sealhip_sample_polys_host: the same words into host memory, computed on the host (works on host-only contexts; no
+   alignment rule).
+   sealhip_debug_sample_map: the kernel's own map functions on n caller-supplied words (device): kind 0 ternary, 1 noise;
+   other kinds -> E_INVALIDARG. The only way to reach the high thresholds: streams exceed magnitude 15 once in 10^7 draws. */
+long sealhip_sample_polys(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary, uint32_t n_noise,
+                          int32_t *out_device, size_t item_stride_words);
+long sealhip_sample_polys_host(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary,
+                               uint32_t n_noise, int32_t *out_host, size_t item_stride_words);
+/* sealhip_sample_polys with the two kinds in two arrays, the layouts sealhip_encryptor_encrypt takes its samples in:
+   ternary_device[count][n_ternary][N] and noise_device[count][n_noise][N] (the same samples: polynomial p of item i still
+   comes from words [pN, (p+1)N) of seed i, ternary ones first). An array whose count is 0 may be NULL. Checks as
+   sealhip_sample_polys (both pointers 16-byte aligned). */
+long sealhip_sample_polys_split(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t n_ternary,
+                                uint32_t n_noise, int32_t *ternary_device, int32_t *noise_device);
+long sealhip_debug_sample_map(sealhip_context *ctx, const uint64_t *words_device, size_t n, int32_t kind, int32_t *out_device);
+/* KeyGenerator::generate_sk (keygenerator.cpp:66-103) from a seed: sk_ntt_device (n_key x N words) receives the ternary
+   polynomial sealhip_sample_polys(seed, 1, 0) lifted over the n_key key primes (-1 -> q_j - 1) in NTT form. The
+   coefficient-form scratch is erased in stream order. null pointers -> E_POINTER; a host-only context ->
+   COR_E_INVALIDOPERATION. Stream-ordered on the calling thread's lane; not capturable. */
+long sealhip_generate_secret_key(sealhip_context *ctx, const uint64_t seed_host[8], uint64_t *sk_ntt_device);
+/* stream-ordered hipMemsetAsync(dptr, 0, bytes) on the calling thread's lane: erases scratch that held secret samples
+   before it goes back to a pool (the reference's clear_on_destruction pool, util/rlwe.cpp:141). Does not synchronise. */
+long sealhip_memset_zero(sealhip_context *ctx, void *dptr, size_t bytes);
 /* is_data_valid_for (valcheck.cpp:284-317) on device-resident ciphertexts: valid[i] = 1 iff every coefficient of
    ciphertext i is below its row's prime (what an ingesting service checks before evaluating untrusted input). */
 long sealhip_is_data_valid_for(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,

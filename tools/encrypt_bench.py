@@ -11,7 +11,15 @@ synchronise after one warm-up call, medians over --reps windows:
             secret key  expand_seed, encrypt_zero_symmetric, then the plaintext step;
   the two are alternated in the same process, window by window;
   oracle:   the oracle's composition on one CPU thread for --oracle-items items, scaled to C.
-Per-kernel times come from a separate rocprofv3 --kernel-trace --stats run of this tool."""
+Per-kernel times come from a separate rocprofv3 --kernel-trace --stats run of this tool.
+With --sampling it measures instead, per C items:
+  sample:        sealhip_sample_polys (1, 2) and (0, 1) alone;
+  device:        each encrypt path with its samples drawn on the device (sample_polys_split + encrypt; sample_polys (0, 1)
+                 + encrypt_symmetric), next to the same path with the samples handed in (the figure above);
+  host:          sealhip_sample_polys_host (1, 2) on one thread and on 16, for --host-items items scaled to C, and the
+                 host-to-device copy of C items' samples: what a caller's own sampler costs at best;
+  reference-style: samples per second of tests/sample_law_check.cpp (normal_distribution, redraw, truncate) on one thread;
+  leaf:          the engine's event timing (sealhip_profile) of seed_leaf and sample_leaf in this run, per leaf."""
 import argparse
 import ctypes as C
 import json
@@ -87,12 +95,108 @@ def oracle_time(scheme, logn, mods, t, items, asym, u, e, seeds, es, plains, k):
     return (time.perf_counter() - t0) / items
 
 
+def law_check_rate():
+    """samples per second of tests/sample_law_check.cpp on one thread (None without a compiler)"""
+    import subprocess
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "sample_law_check")
+        try:
+            subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(ROOT, "tests", "sample_law_check.cpp")])
+            out = subprocess.run([exe, "22"], capture_output=True, text=True, timeout=120).stdout
+        except (OSError, subprocess.SubprocessError):
+            return None
+    for line in out.splitlines():
+        if line.startswith("samples_per_second"):
+            return float(line.split()[1])
+    return None
+
+
+def sampling(a, name, scheme, logn, mods, t, rng):
+    from concurrent.futures import ThreadPoolExecutor
+
+    n, n_key = 1 << logn, len(mods)
+    k, count = n_key - 1, a.count
+    ctx = S.Context(scheme, logn, mods, 1, t)
+    sk = ctx.upload(np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in mods]))
+    pk = ctx.upload(np.stack([np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in mods]) for _ in range(2)]))
+    seeds = rng.integers(0, 2**64, size=(count, 8), dtype=np.uint64)
+    seeds2 = rng.integers(0, 2**64, size=(count, 8), dtype=np.uint64)
+    if scheme == 1:
+        pl = ctx.upload(rng.integers(0, t, size=(count, n), dtype=np.uint64))
+    else:
+        pl = ctx.upload(np.stack([rng.integers(0, q, size=(count, n), dtype=np.uint64) for q in mods[:k]], axis=1))
+    pstride = n if scheme == 1 else k * n
+    ct = ctx.alloc(count * 2 * k * n)
+    all3, u, e, es = ctx.alloc(count * 3 * n // 2), ctx.alloc(count * n // 2), ctx.alloc(count * n), ctx.alloc(count * n // 2)
+
+    def median(fn):
+        timed(ctx, fn)
+        return float(np.median([timed(ctx, fn) for _ in range(a.reps)]))
+
+    def emit(what, seconds, **more):
+        print(json.dumps(dict({"config": name, "what": what, "count": count, "k": k, "ms": seconds * 1e3}, **more)), flush=True)
+
+    def asym_device():
+        ctx.sample_polys_split(seeds, 1, 2, u, e)
+        ctx.encrypt(k, pk, pl, u, e, count, ct, plain_item_stride=pstride)
+
+    def sym_device():
+        ctx.sample_polys(seeds2, 0, 1, es)
+        ctx.encrypt_symmetric(k, sk, pl, seeds, es, count, ct, plain_item_stride=pstride)
+
+    t12 = median(lambda: ctx.sample_polys(seeds, 1, 2, all3))
+    t01 = median(lambda: ctx.sample_polys(seeds, 0, 1, es))
+    emit("sample_polys_1_2", t12)
+    emit("sample_polys_0_1", t01)
+    ta_dev = median(asym_device)
+    ta_in = median(lambda: ctx.encrypt(k, pk, pl, u, e, count, ct, plain_item_stride=pstride))
+    emit("asym_device_samples", ta_dev, samples_handed_in_ms=ta_in * 1e3, sampling_over_call=t12 / ta_dev)
+    ts_dev = median(sym_device)
+    ts_in = median(lambda: ctx.encrypt_symmetric(k, sk, pl, seeds, es, count, ct, plain_item_stride=pstride))
+    emit("sym_device_samples", ts_dev, samples_handed_in_ms=ts_in * 1e3, sampling_over_call=t01 / ts_dev)
+    # the engine's own event timing of the two leaf kernels, per leaf (units = leaves)
+    ctx.profile_enable(True)
+    for _ in range(a.reps):
+        ctx.sample_polys(seeds, 1, 2, all3)
+        ctx.expand_seeds(k, seeds, ct)
+    prof = ctx.profile_fetch()
+    ctx.profile_enable(False)
+    per_leaf = {tag: prof[tag]["ms"] * 1e6 / prof[tag]["units"] for tag in ("seed_leaf", "sample_leaf") if tag in prof}
+    if len(per_leaf) == 2:
+        print(json.dumps({"config": name, "what": "leaf", "seed_leaf_ns_per_leaf": per_leaf["seed_leaf"],
+                          "sample_leaf_ns_per_leaf": per_leaf["sample_leaf"],
+                          "sample_over_seed": per_leaf["sample_leaf"] / per_leaf["seed_leaf"],
+                          "sample_leaf_ms_per_call": prof["sample_leaf"]["ms"] / a.reps,
+                          "seed_leaf_ms_per_call": prof["seed_leaf"]["ms"] / a.reps}), flush=True)
+    # a caller's sampler at best: the same rule on the host, then the copy
+    items = min(count, a.host_items)
+    host = S.Context(scheme, logn, mods, 1, t, device=-1)
+    t0 = time.perf_counter()
+    one = host.sample_polys_host(seeds[:items], 1, 2)
+    t1 = (time.perf_counter() - t0) / items * count
+    with ThreadPoolExecutor(16) as pool:
+        t0 = time.perf_counter()
+        list(pool.map(lambda i: host.sample_polys_host(seeds[i : i + 1], 1, 2), range(16 * items)))
+        t16 = (time.perf_counter() - t0) / (16 * items) * count
+    block = np.ascontiguousarray(np.tile(one, (count // items + 1, 1))[:count])
+    th2d = median(lambda: all3.upload(block.view(np.uint64)))
+    emit("host_sampler_1_2", t1, threads=1, scaled_from_items=items)
+    emit("host_sampler_1_2", t16, threads=16, scaled_from_items=16 * items, h2d_copy_ms=th2d * 1e3)
+    rate = law_check_rate()
+    if rate:
+        emit("reference_style_sampler_1_2", count * 3 * n / rate, threads=1, samples_per_second=rate)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--count", type=int, default=1024)
     ap.add_argument("--oracle-items", type=int, default=2)
     ap.add_argument("--only", default="cfg3,cfg4,cfg5")
+    ap.add_argument("--sampling", action="store_true", help="measure the device sampler and the paths fed by it instead")
+    ap.add_argument("--host-items", type=int, default=4, help="--sampling: items the host sampler runs (scaled to --count)")
     a = ap.parse_args()
     assert S.num_devices() >= 1, "no HIP device: nothing to measure"
     cfgs = {
@@ -103,6 +207,9 @@ def main():
     rng = np.random.default_rng(1)
     for name in a.only.split(","):
         scheme, logn, mods, t = cfgs[name]
+        if a.sampling:
+            sampling(a, name, scheme, logn, mods, t, rng)
+            continue
         n, n_key = 1 << logn, len(mods)
         k, R, count = n_key - 1, n_key, a.count
         ctx = S.Context(scheme, logn, mods, 1, t)
