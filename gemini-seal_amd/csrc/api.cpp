@@ -15,6 +15,7 @@
 
 #include "blake2xb.hpp"
 #include "engine.hpp"
+#include "homdft_plan.hpp"
 #include "poly_plan.hpp"
 
 using namespace sealhip;
@@ -2203,6 +2204,292 @@ long sealhip_evaluator_rotate_vector_bsgs_plain_rescale(sealhip_context *ctx, ui
 {
     return rotate_vector_bsgs_plain_entry(ctx, true, k, ct, count, baby_steps, n_baby, giant_steps, n_giant, galois_elts,
                                           galois_keys, n_keys, plain_ntt, out);
+}
+
+/* ------------------------------------------------------------------ homomorphic DFT */
+extern "C++" {
+struct sealhip_dft_tables
+{
+    DftTables *tables = nullptr;
+};
+
+namespace
+{
+    dftplan::Plan dft_make_plan(const Engine &h, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                                const uint32_t *n_baby)
+    {
+        dftplan::Ring ring;
+        ring.scheme = h.scheme;
+        ring.logn = static_cast<uint32_t>(h.logn);
+        ring.n_key = static_cast<uint32_t>(h.n_key);
+        ring.k_first = static_cast<uint32_t>(h.k_first);
+        ring.key_moduli = h.key_moduli.data();
+        if (n_stages > SEALHIP_DFT_MAX_STAGES)
+            throw std::invalid_argument("the stages' layer counts must sum to log2(N/2)");
+        return dftplan::make_plan(ring, direction, k, stages, n_stages, n_baby);
+    }
+
+    void dft_plan_to_abi(const dftplan::Plan &p, sealhip_dft_plan *out)
+    {
+        std::memset(out, 0, sizeof(*out));
+        out->direction = p.direction;
+        out->n_stages = static_cast<uint32_t>(p.stages.size());
+        out->in_level = p.in_level;
+        out->out_level = p.out_level;
+        out->needs_conjugation = p.needs_conjugation ? 1 : 0;
+        out->n_key_steps = static_cast<uint32_t>(p.key_steps.size());
+        out->table_words = p.table_words;
+        out->temp_bytes_per_item = p.temp_bytes_per_item;
+        for (size_t t = 0; t < p.stages.size(); t++)
+        {
+            const dftplan::Stage &s = p.stages[t];
+            sealhip_dft_stage &o = out->stages[t];
+            o.s0 = s.s0;
+            o.r = s.r;
+            o.h0 = s.h0;
+            o.level = s.level;
+            o.n_baby = s.n_baby;
+            o.n_giant = s.n_giant;
+            o.folded = s.folded ? 1 : 0;
+            o.scale = s.scale;
+        }
+    }
+
+    // the tables' context is the caller's: another ring's tables would be read with the wrong strides
+    void check_dft_tables(const sealhip_context *ctx, const sealhip_dft_tables *tables)
+    {
+        if (dft_tables_engine(*tables->tables) != ctx->engine.get())
+            throw std::invalid_argument("the DFT tables were made on another context");
+    }
+
+    // what the split and merge kernels load and store 16 bytes at a time
+    void check_dft_aligned(const void *p, const char *name)
+    {
+        if (reinterpret_cast<std::uintptr_t>(p) & 15)
+            throw std::invalid_argument(std::string(name) + " must be 16-byte aligned");
+    }
+
+    void check_dft_gain(double gain)
+    {
+        if (!std::isfinite(gain) || gain == 0)
+            throw std::invalid_argument("gain must be finite and non-zero");
+    }
+
+    // every stage's elements and keys out of the caller's key list, checked against the stage's level
+    std::vector<DftStageKeys> dft_stage_keys(const Engine &h, const dftplan::Plan &p, const uint32_t *galois_elts,
+                                             const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys)
+    {
+        std::vector<DftStageKeys> all;
+        for (const dftplan::Stage &s : p.stages)
+        {
+            DftStageKeys sk;
+            std::vector<const sealhip_kswitch_key *> bk, gk;
+            keys_for_steps(h, s.baby.data(), s.n_baby, galois_elts, galois_keys, n_keys, 1, sk.baby, bk);
+            keys_for_steps(h, s.giant.data(), s.n_giant, galois_elts, galois_keys, n_keys, 1, sk.giant, gk);
+            check_elts_and_keys(h, s.level, sk.baby, bk);
+            check_elts_and_keys(h, s.level, sk.giant, gk);
+            sk.baby_keys = run_keys(sk.baby, bk, 1);
+            sk.giant_keys = run_keys(sk.giant, gk, 1);
+            all.push_back(std::move(sk));
+        }
+        return all;
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_evaluator_dft_plan(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                      const uint32_t *n_baby, sealhip_dft_plan *plan, uint32_t *key_steps, uint32_t key_steps_capacity)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
+        if (key_steps && key_steps_capacity < p.key_steps.size())
+            throw std::invalid_argument("key_steps is too small");
+        dft_plan_to_abi(p, plan);
+        if (key_steps)
+            std::copy(p.key_steps.begin(), p.key_steps.end(), key_steps);
+    });
+}
+
+long sealhip_dft_stage_steps(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages,
+                             uint32_t n_stages, const uint32_t *n_baby, uint32_t stage, int32_t *baby_steps,
+                             int32_t *giant_steps)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(baby_steps);
+    REQUIRE_PTR(giant_steps);
+    return guarded([&] {
+        const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
+        if (stage >= p.stages.size())
+            throw std::invalid_argument("stage out of range");
+        std::copy(p.stages[stage].baby.begin(), p.stages[stage].baby.end(), baby_steps);
+        std::copy(p.stages[stage].giant.begin(), p.stages[stage].giant.end(), giant_steps);
+    });
+}
+
+long sealhip_dft_stage_values(sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                              const uint32_t *n_baby, double gain, uint32_t stage, double *values)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(values);
+    return guarded([&] {
+        const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
+        if (stage >= p.stages.size())
+            throw std::invalid_argument("stage out of range");
+        check_dft_gain(gain);
+        Engine &e = device_engine(ctx);
+        op_dft_stage_values(e, p, stage, gain, values);
+    });
+}
+
+long sealhip_dft_stage_values_host(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages,
+                                   uint32_t n_stages, const uint32_t *n_baby, double gain, uint32_t stage, double *values)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(values);
+    return guarded([&] {
+        const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
+        if (stage >= p.stages.size())
+            throw std::invalid_argument("stage out of range");
+        check_dft_gain(gain);
+        dft_stage_values_host(*ctx->engine, p, stage, gain, values);
+    });
+}
+
+long sealhip_dft_tables_create(sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                               const uint32_t *n_baby, double gain, sealhip_dft_tables **tables)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
+        check_dft_gain(gain);
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("sealhip_dft_tables_create synchronises: it cannot be captured");
+        std::unique_ptr<sealhip_dft_tables> t(new sealhip_dft_tables);
+        t->tables = dft_tables_create(e, p, gain);
+        *tables = t.release();
+    });
+}
+
+long sealhip_dft_tables_destroy(sealhip_dft_tables *tables)
+{
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        dft_tables_destroy(tables->tables); // (throws, and leaves the tables alone, during a graph capture)
+        delete tables;
+    });
+}
+
+long sealhip_dft_tables_plan(const sealhip_dft_tables *tables, sealhip_dft_plan *plan)
+{
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(plan);
+    return guarded([&] { dft_plan_to_abi(dft_tables_plan(*tables->tables), plan); });
+}
+
+long sealhip_dft_tables_stage(const sealhip_dft_tables *tables, uint32_t stage, const uint64_t **plain_ntt)
+{
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(plain_ntt);
+    return guarded([&] {
+        if (stage >= dft_tables_plan(*tables->tables).stages.size())
+            throw std::invalid_argument("stage out of range");
+        *plain_ntt = reinterpret_cast<const uint64_t *>(dft_tables_stage(*tables->tables, stage));
+    });
+}
+
+long sealhip_evaluator_coeffs_to_slots(sealhip_context *ctx, const sealhip_dft_tables *tables, const uint64_t *ct, size_t count,
+                                       const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                       uint32_t n_keys, uint64_t *out_re, uint64_t *out_im)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out_re);
+    REQUIRE_PTR(out_im);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+        for (uint32_t i = 0; i < n_keys; i++)
+            REQUIRE_PTR(galois_keys[i]);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const dftplan::Plan &p = dft_tables_plan(*tables->tables);
+        check_dft_tables(ctx, tables);
+        check_dft_aligned(out_re, "out_re");
+        check_dft_aligned(out_im, "out_im");
+        if (p.direction != dftplan::kCoeffsToSlots)
+            throw std::invalid_argument("the tables were made for slots_to_coeffs");
+        const std::vector<DftStageKeys> keys = dft_stage_keys(h, p, galois_elts, galois_keys, n_keys);
+        const uint32_t conj_elt = static_cast<uint32_t>(2 * h.n - 1);
+        const sealhip_kswitch_key *conj = nullptr;
+        for (uint32_t i = 0; i < n_keys && !conj; i++)
+            if (galois_elts[i] == conj_elt)
+                conj = galois_keys[i];
+        if (!conj)
+            throw std::invalid_argument("Galois key not present");
+        check_key_digits(h, p.out_level, conj);
+        const std::size_t in_words = count * 2 * p.in_level * h.n, out_words = count * 2 * p.out_level * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *re = reinterpret_cast<u64 *>(out_re), *im = reinterpret_cast<u64 *>(out_im);
+        if (words_overlap(re, out_words, in, in_words) || words_overlap(im, out_words, in, in_words))
+            throw std::invalid_argument("out must not overlap ct");
+        if (words_overlap(re, out_words, im, out_words))
+            throw std::invalid_argument("out_re must not overlap out_im");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, 2 * count);
+        op_coeffs_to_slots(e, *tables->tables, in, count, keys, conj->key, re, im);
+        const std::size_t poly = static_cast<std::size_t>(p.out_level) * h.n;
+        sink.read_pass(re, 2, poly, count);
+        if (sink.on)
+            check(launch_nonzero_tail(e, im, 2 * poly, poly, count, e.lane().tsink + count), "transparency");
+    });
+}
+
+long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_tables *tables, const uint64_t *ct_re,
+                                       const uint64_t *ct_im, size_t count, const uint32_t *galois_elts,
+                                       const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(ct_re);
+    REQUIRE_PTR(ct_im);
+    REQUIRE_PTR(out);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+        for (uint32_t i = 0; i < n_keys; i++)
+            REQUIRE_PTR(galois_keys[i]);
+    }
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const dftplan::Plan &p = dft_tables_plan(*tables->tables);
+        check_dft_tables(ctx, tables);
+        check_dft_aligned(ct_re, "ct_re");
+        check_dft_aligned(ct_im, "ct_im");
+        if (p.direction != dftplan::kSlotsToCoeffs)
+            throw std::invalid_argument("the tables were made for coeffs_to_slots");
+        const std::vector<DftStageKeys> keys = dft_stage_keys(h, p, galois_elts, galois_keys, n_keys);
+        const std::size_t in_words = count * 2 * p.in_level * h.n, out_words = count * 2 * p.out_level * h.n;
+        const u64 *re = reinterpret_cast<const u64 *>(ct_re), *im = reinterpret_cast<const u64 *>(ct_im);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, out_words, re, in_words) || words_overlap(o, out_words, im, in_words))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op_slots_to_coeffs(e, *tables->tables, re, im, count, keys, o);
+        sink.read_pass(o, 2, static_cast<std::size_t>(p.out_level) * h.n, count);
+    });
 }
 
 /* ------------------------------------------------------------------ ciphertext inner product */

@@ -1034,6 +1034,42 @@ namespace sealhip
     // values out: count x N/2 complex doubles
     void op_ckks_decode(Engine &e, int k, const u64 *plain, std::size_t count, double scale, double *values);
 
+    // ---- homomorphic DFT: CoeffToSlot / SlotToCoeff (homdft.hip, homdft.cpp, homdft_plan.hpp) ----
+    namespace dftplan
+    {
+        struct Plan;
+    }
+    // values[n_giant][n_baby][N/2] complex doubles (device): gain * the stage's diagonals, pre-rotated for BSGS; the encoder's
+    // tables must be resident (Engine::ckks_tables)
+    hipError_t launch_dft_stage_values(const Engine &e, int s0, int r, bool inverse, bool folded, std::uint32_t n_baby,
+                                       std::uint32_t n_giant, double gain, double *values);
+    // a, b = count x 2 x map.rows x N in NTT form: re = a + b, im = -i (a - b) / out = re + i im
+    hipError_t launch_dft_conj_split(const Engine &e, const u64 *a, const u64 *b, u64 *re, u64 *im, std::size_t count,
+                                     const RowMap &map);
+    hipError_t launch_dft_merge(const Engine &e, const u64 *re, const u64 *im, u64 *out, std::size_t count, const RowMap &map);
+    // the real factor of a stage's values: `gain` on the last CoeffToSlot / first SlotToCoeff stage, 1/2 more on the last
+    // CoeffToSlot stage (the split adds a value to its conjugate), 2^-r on every CoeffToSlot stage (inverse layers)
+    double dft_stage_gain(const dftplan::Plan &p, std::size_t stage, double gain);
+    void dft_stage_values_host(const Engine &h, const dftplan::Plan &p, std::size_t stage, double gain, double *values);
+    void op_dft_stage_values(Engine &e, const dftplan::Plan &p, std::size_t stage, double gain, double *values);
+    struct DftTables; // the plan and, per stage, plain_ntt[n_giant][n_baby][n_key][N] in device memory
+    DftTables *dft_tables_create(Engine &e, const dftplan::Plan &p, double gain);
+    void dft_tables_destroy(DftTables *t);
+    const dftplan::Plan &dft_tables_plan(const DftTables &t);
+    const Engine *dft_tables_engine(const DftTables &t); // the context they were made on
+    const u64 *dft_tables_stage(const DftTables &t, std::size_t stage);
+    struct DftStageKeys // a stage's Galois elements (1 = the identity) and keys (null there), as op_apply_galois_bsgs_plain takes them
+    {
+        std::vector<std::uint32_t> baby, giant;
+        std::vector<const KSwitchKey *> baby_keys, giant_keys;
+    };
+    // ct[count][2][k][N] -> out_re, out_im[count][2][k - n_stages][N]; conj_key: the key of element 2N - 1
+    void op_coeffs_to_slots(Engine &e, const DftTables &t, const u64 *ct, std::size_t count, const std::vector<DftStageKeys> &keys,
+                            const KSwitchKey &conj_key, u64 *out_re, u64 *out_im);
+    // ct_re, ct_im[count][2][k][N] -> out[count][2][k - n_stages][N]
+    void op_slots_to_coeffs(Engine &e, const DftTables &t, const u64 *ct_re, const u64 *ct_im, std::size_t count,
+                            const std::vector<DftStageKeys> &keys, u64 *out);
+
     // ---- Decryptor (decrypt.hip, pipeline.cpp) ----
     // bits_out[i] = max(bits_out[i], bits of the largest centred |t v| of item i), v = count x k x N dot products
     hipError_t launch_noise_bits(const Engine &e, const NoiseBudgetDev *d, int k, const u64 *v, std::size_t count,

@@ -610,6 +610,48 @@ namespace sealhip_host
         sealhip_kswitch_key *key_ = nullptr;
     };
 
+    // The plan and the device tables of one homomorphic DFT (sealhip_dft_tables_create): CoeffToSlot
+    // (SEALHIP_DFT_COEFFS_TO_SLOTS) or SlotToCoeff (SEALHIP_DFT_SLOTS_TO_COEFFS) for ciphertexts at level k, as the stages
+    // `stages` (layer counts in application order, summing to log2(N/2)). Evaluator::coeffs_to_slots / slots_to_coeffs take
+    // it; the result is n_stages levels lower at the same scale. key_steps(): the rotation steps whose Galois keys the
+    // client must make (CoeffToSlot also needs the key of element 2N - 1).
+    class HomomorphicDFT
+    {
+    public:
+        HomomorphicDFT(const Context &c, std::uint32_t direction, std::size_t k, const std::vector<std::uint32_t> &stages,
+                       const std::vector<std::uint32_t> &n_baby = {}, double gain = 1.0)
+        {
+            if (!n_baby.empty() && n_baby.size() != stages.size())
+                throw std::invalid_argument("n_baby and stages differ in length");
+            const std::uint32_t *nb = n_baby.empty() ? nullptr : n_baby.data();
+            const std::uint32_t n_stages = std::uint32_t(stages.size());
+            // (the plan first: its refusals need no device)
+            throw_on(sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, &plan_, nullptr, 0));
+            key_steps_.resize(plan_.n_key_steps);
+            throw_on(sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, &plan_,
+                                                key_steps_.data(), plan_.n_key_steps));
+            throw_on(sealhip_dft_tables_create(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, gain, &tables_));
+        }
+        ~HomomorphicDFT()
+        {
+            if (tables_)
+                sealhip_dft_tables_destroy(tables_);
+        }
+        HomomorphicDFT(const HomomorphicDFT &) = delete;
+        HomomorphicDFT &operator=(const HomomorphicDFT &) = delete;
+        const sealhip_dft_tables *get() const { return tables_; }
+        const sealhip_dft_plan &plan() const { return plan_; }
+        std::uint32_t direction() const { return plan_.direction; }
+        std::size_t in_level() const { return plan_.in_level; }
+        std::size_t out_level() const { return plan_.out_level; }
+        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
+
+    private:
+        sealhip_dft_tables *tables_ = nullptr;
+        sealhip_dft_plan plan_{};
+        std::vector<std::uint32_t> key_steps_;
+    };
+
     template <class CT>
     class Evaluator
     {
@@ -1033,6 +1075,77 @@ namespace sealhip_host
             destination = std::move(one[0]);
             if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
                 destination.scale() = in_scale * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
+        }
+
+    public:
+        // CoeffToSlot in one call (sealhip_evaluator_coeffs_to_slots): slot j of destination_re /
+        // destination_im holds coefficient bitrev(j) / bitrev(j) + N/2 of the operand's message over its scale. The results
+        // are dft.out_level() primes long at the operand's scale. galois_keys: element -> key, with the keys of
+        // dft.key_steps() and of element 2N - 1.
+        template <class C, IfCt<C> = 0>
+        void coeffs_to_slots(const C &encrypted, const HomomorphicDFT &dft,
+                             const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination_re,
+                             C &destination_im)
+        {
+            check_dft_operand(encrypted, dft, SEALHIP_DFT_COEFFS_TO_SLOTS);
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            dft_keys(galois_keys, elts, raw);
+            const std::size_t n = ctx_.n(), words = 2 * dft.in_level() * n, out_words = 2 * dft.out_level() * n;
+            Dev c = dev_in(encrypted, words), o = dev_out(2 * out_words);
+            Check chk = checked(encrypted, 2);
+            throw_on(sealhip_evaluator_coeffs_to_slots(ctx_.get(), dft.get(), c.ptr(), 1, elts.data(), raw.data(),
+                                                       std::uint32_t(elts.size()), o.ptr(), o.ptr() + out_words));
+            chk.done();
+            std::vector<C> two;
+            scatter(encrypted, o, 2, out_words, two, dft.out_level());
+            destination_re = std::move(two[0]);
+            destination_im = std::move(two[1]);
+        }
+        // SlotToCoeff in one call (sealhip_evaluator_slots_to_coeffs): the inverse of coeffs_to_slots, from its slot order
+        template <class C, IfCt<C> = 0>
+        void slots_to_coeffs(const C &encrypted_re, const C &encrypted_im, const HomomorphicDFT &dft,
+                             const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination)
+        {
+            check_dft_operand(encrypted_re, dft, SEALHIP_DFT_SLOTS_TO_COEFFS);
+            check_dft_operand(encrypted_im, dft, SEALHIP_DFT_SLOTS_TO_COEFFS);
+            if (encrypted_re.scale() != encrypted_im.scale())
+                throw std::invalid_argument("scale mismatch");
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            dft_keys(galois_keys, elts, raw);
+            const std::size_t n = ctx_.n(), words = 2 * dft.in_level() * n, out_words = 2 * dft.out_level() * n;
+            Dev a = dev_in(encrypted_re, words), b = dev_in(encrypted_im, words), o = dev_out(out_words);
+            Check chk = checked(encrypted_re, 1);
+            throw_on(sealhip_evaluator_slots_to_coeffs(ctx_.get(), dft.get(), a.ptr(), b.ptr(), 1, elts.data(), raw.data(),
+                                                       std::uint32_t(elts.size()), o.ptr()));
+            chk.done();
+            std::vector<C> one;
+            scatter(encrypted_re, o, 1, out_words, one, dft.out_level());
+            destination = std::move(one[0]);
+        }
+
+    private:
+        template <class C>
+        void check_dft_operand(const C &encrypted, const HomomorphicDFT &dft, std::uint32_t direction) const
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme");
+            check_galois_operand(encrypted);
+            if (dft.direction() != direction)
+                throw std::invalid_argument("the DFT tables were made for the other direction");
+            if (encrypted.coeff_modulus_size() != dft.in_level())
+                throw std::invalid_argument("encrypted is not at the level of the DFT tables");
+        }
+        static void dft_keys(const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<std::uint32_t> &elts,
+                             std::vector<const sealhip_kswitch_key *> &raw)
+        {
+            for (const auto &kv : galois_keys)
+                if (kv.second)
+                {
+                    elts.push_back(kv.first);
+                    raw.push_back(kv.second->get());
+                }
         }
 
     public:

@@ -60,6 +60,20 @@ class PolyPlan(C.Structure):
                 ("out_scale", C.c_double), ("temp_bytes_per_item", _u64)]
 
 
+class DftStage(C.Structure):
+    """sealhip_dft_stage (include/sealhip.h)"""
+    _fields_ = [("s0", _u32), ("r", _u32), ("h0", _u32), ("level", _u32), ("n_baby", _u32), ("n_giant", _u32), ("folded", _u32),
+                ("reserved", _u32), ("scale", C.c_double)]
+
+
+class DftPlan(C.Structure):
+    """sealhip_dft_plan (include/sealhip.h)"""
+    _fields_ = [("direction", _u32), ("n_stages", _u32), ("in_level", _u32), ("out_level", _u32), ("needs_conjugation", _u32),
+                ("n_key_steps", _u32), ("table_words", _u64), ("temp_bytes_per_item", _u64), ("stages", DftStage * 16)]
+
+
+DFT_COEFFS_TO_SLOTS, DFT_SLOTS_TO_COEFFS = 0, 1
+
 SYMBOLS = {
     "sealhip_last_error_string": None,
     "sealhip_num_devices": [C.POINTER(C.c_int32)],
@@ -168,6 +182,16 @@ SYMBOLS = {
                                                           C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_rotate_vector_bsgs_plain_rescale": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_i32), _u32,
                                                            C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
+    "sealhip_evaluator_dft_plan": [_vp, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), _vp, C.POINTER(_u32), _u32],
+    "sealhip_dft_stage_steps": [_vp, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), _u32, C.POINTER(_i32), C.POINTER(_i32)],
+    "sealhip_dft_stage_values": [_vp, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), C.c_double, _u32, _vp],
+    "sealhip_dft_stage_values_host": [_vp, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), C.c_double, _u32, _vp],
+    "sealhip_dft_tables_create": [_vp, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), C.c_double, C.POINTER(_vp)],
+    "sealhip_dft_tables_destroy": [_vp],
+    "sealhip_dft_tables_plan": [_vp, _vp],
+    "sealhip_dft_tables_stage": [_vp, _u32, C.POINTER(_vp)],
+    "sealhip_evaluator_coeffs_to_slots": [_vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
+    "sealhip_evaluator_slots_to_coeffs": [_vp, _vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -1205,6 +1229,62 @@ class Evaluator:
         self.rotate_vector_bsgs_plain(ct, k, count, baby_steps, giant_steps, galois_keys, plains, out,
                                       _entry="sealhip_evaluator_rotate_vector_bsgs_plain_rescale")
 
+    # ---- homomorphic DFT: CoeffToSlot / SlotToCoeff
+    def dft_plan(self, direction, k, stages, n_baby=None):
+        """The plan of a homomorphic DFT (sealhip_evaluator_dft_plan); works on a host-only context. direction:
+        DFT_COEFFS_TO_SLOTS or DFT_SLOTS_TO_COEFFS; stages: layer counts in application order, summing to log2(N/2); n_baby:
+        per stage or None. Returns a dict: in_level, out_level, needs_conjugation, table_words, temp_bytes_per_item, key_steps
+        (the sorted distinct non-zero rotation steps: the Galois keys to make) and stages, a list of dicts s0, r, h0, level,
+        n_baby, n_giant, folded, scale, baby_steps, giant_steps."""
+        args = _dft_args(direction, k, stages, n_baby)
+        plan = DftPlan()
+        fn = lib().sealhip_evaluator_dft_plan
+        _check(fn(self.ctx.handle, *args, C.addressof(plan), None, 0))
+        steps = (_u32 * max(1, plan.n_key_steps))()
+        _check(fn(self.ctx.handle, *args, C.addressof(plan), steps, plan.n_key_steps))
+        out = _dft_plan_dict(plan)
+        out["key_steps"] = [int(v) for v in steps[:plan.n_key_steps]]
+        for t, st in enumerate(out["stages"]):
+            bs, gs = (_i32 * st["n_baby"])(), (_i32 * st["n_giant"])()
+            _check(lib().sealhip_dft_stage_steps(self.ctx.handle, *args, t, bs, gs))
+            st["baby_steps"], st["giant_steps"] = [int(v) for v in bs], [int(v) for v in gs]
+        return out
+
+    def dft_stage_values(self, direction, k, stages, stage, n_baby=None, gain=1.0, host=False):
+        """One stage's pre-rotated diagonals as a complex array [n_giant][n_baby][N/2] (sealhip_dft_stage_values: the
+        generator kernel, downloaded; host=True: sealhip_dft_stage_values_host, also on a host-only context)."""
+        args = _dft_args(direction, k, stages, n_baby)
+        plan = DftPlan()
+        _check(lib().sealhip_evaluator_dft_plan(self.ctx.handle, *args, C.addressof(plan), None, 0))
+        st = plan.stages[stage]
+        out = np.zeros((st.n_giant, st.n_baby, self.ctx.n // 2), dtype=np.complex128)
+        if host:
+            _check(lib().sealhip_dft_stage_values_host(self.ctx.handle, *args, gain, stage, out.ctypes.data))
+            return out
+        dev = self.ctx.alloc(out.size * 2)
+        _check(lib().sealhip_dft_stage_values(self.ctx.handle, *args, gain, stage, dev.ptr))
+        return dev.download(out.size * 2).view(np.complex128).reshape(out.shape)
+
+    def coeffs_to_slots(self, tables, ct, count, galois_keys, out_re, out_im):
+        """CoeffToSlot in one call (sealhip_evaluator_coeffs_to_slots): ct a device batch count x 2 x k x N at the tables'
+        level; out_re, out_im: count x 2 x tables.out_level x N, slot j of them m_(bitrev j) and m_(bitrev j + N/2) over the
+        scale, which is unchanged. galois_keys: dict galois_elt -> KSwitchKeys with the plan's key_steps and element 2N - 1;
+        a missing one raises ValueError."""
+        elts = list(galois_keys.keys())
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        _check(lib().sealhip_evaluator_coeffs_to_slots(self.ctx.handle, tables.handle, _ptr(ct), count, ea, ka, len(elts),
+                                                       _ptr(out_re), _ptr(out_im)))
+
+    def slots_to_coeffs(self, tables, ct_re, ct_im, count, galois_keys, out):
+        """SlotToCoeff in one call (sealhip_evaluator_slots_to_coeffs): ct_re, ct_im device batches count x 2 x k x N in
+        coeffs_to_slots' bit-reversed slot order; out: count x 2 x tables.out_level x N; the scale is unchanged."""
+        elts = list(galois_keys.keys())
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        _check(lib().sealhip_evaluator_slots_to_coeffs(self.ctx.handle, tables.handle, _ptr(ct_re), _ptr(ct_im), count, ea, ka,
+                                                       len(elts), _ptr(out)))
+
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod
     def _host_ptrs(arrays):
@@ -1350,6 +1430,59 @@ class Evaluator:
 
     def transform_from_ntt_inplace(self, ct, size, k, count):
         _check(lib().sealhip_evaluator_transform_from_ntt(self.ctx.handle, k, _ptr(ct), size, count))
+
+
+def _dft_args(direction, k, stages, n_baby):
+    stages = [int(v) for v in stages]
+    sa = (_u32 * max(1, len(stages)))(*stages)
+    if n_baby is not None and len(n_baby) != len(stages):
+        raise ValueError("n_baby and stages differ in length")
+    na = (_u32 * max(1, len(stages)))(*[int(v) for v in n_baby]) if n_baby is not None else None
+    return int(direction), int(k), sa, len(stages), na
+
+
+def _dft_plan_dict(plan):
+    out = {name: int(getattr(plan, name)) for name in ("direction", "in_level", "out_level", "needs_conjugation", "table_words",
+                                                        "temp_bytes_per_item")}
+    out["stages"] = []
+    for t in range(plan.n_stages):
+        st = plan.stages[t]
+        d = {name: int(getattr(st, name)) for name in ("s0", "r", "h0", "level", "n_baby", "n_giant", "folded")}
+        d["scale"] = float(st.scale)
+        out["stages"].append(d)
+    return out
+
+
+class DftTables:
+    """The device tables of one homomorphic DFT (sealhip_dft_tables_create): every stage's diagonals,
+    generated on the device and encoded at the key level. plan: Evaluator.dft_plan's dict without the step lists;
+    stage_ptr(t): the device address of stage t's n_giant x n_baby x n_key x N words."""
+
+    def __init__(self, ctx, direction, k, stages, n_baby=None, gain=1.0):
+        self.ctx, self.handle = ctx, None
+        h = _vp()
+        _check(lib().sealhip_dft_tables_create(ctx.handle, *_dft_args(direction, k, stages, n_baby), gain, C.byref(h)))
+        self.handle = h
+        plan = DftPlan()
+        _check(lib().sealhip_dft_tables_plan(self.handle, C.addressof(plan)))
+        self.plan = _dft_plan_dict(plan)
+        self.in_level, self.out_level = self.plan["in_level"], self.plan["out_level"]
+
+    def stage_ptr(self, stage):
+        p = _vp()
+        _check(lib().sealhip_dft_tables_stage(self.handle, stage, C.byref(p)))
+        return p.value
+
+    def free(self):
+        if self.handle is not None and lib is not None:
+            lib().sealhip_dft_tables_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _naf(value):

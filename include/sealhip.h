@@ -612,6 +612,99 @@ long sealhip_evaluator_rotate_vector_bsgs_plain_rescale(sealhip_context *ctx, ui
                                                         const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
                                                         const uint64_t *plain_ntt, uint64_t *out);
 
+/* Homomorphic DFT of CKKS bootstrapping: CoeffToSlot and SlotToCoeff, each one call over
+   sealhip_evaluator_rotate_vector_bsgs_plain_rescale's pipeline, with the diagonals generated on the device. CKKS only, both
+   modes. The fork has no such method; the plan and the values are restated from the layer matrices in tests/homdft_ref.py.
+   Notation: n = N/2 slots, L = log2 n, zeta = exp(i pi / N); slot j of m(X) is z_j = m(zeta^(5^j mod 2N)); w_t = m_t + i m_(t+n).
+   z = U w with U = F_L ... F_1 R, R the bit reversal on L bits and F_s the butterfly layer of span 2^s with twiddles
+   omega_(s,j) = exp(2 pi i (5^j mod 4 2^s) / (4 2^s)) (csrc/homdft_plan.hpp). The bit reversal is dropped:
+     CoeffToSlot  applies G = F_1^-1 ... F_L^-1, (G z)_j = w_(bitrev j), then splits real and imaginary parts:
+                  slot j of out_re holds m_(bitrev j) / scale, slot j of out_im holds m_(bitrev j + n) / scale;
+     SlotToCoeff  merges re + i im and applies F_L ... F_1 to a vector in that bit-reversed order.
+   `stages` lists layer counts in application order, summing to L: a stage is that many consecutive layers as ONE
+   baby-step/giant-step product (CoeffToSlot starts with the top layers, SlotToCoeff with the bottom ones). n_baby: per stage,
+   a power of two at most 2^r, or NULL / 0 for 2^ceil((r+1)/2). The stage at level k_s encodes its diagonals at scale
+   (double) q_(k_s - 1), the prime its merged rescale drops, so the ciphertext's scale is exactly unchanged; a transform of
+   n_stages stages takes level k to k - n_stages.
+   sealhip_evaluator_dft_plan: works on host-only contexts. key_steps == NULL: plan alone (n_key_steps says how many); else the sorted
+   distinct non-zero rotation steps of all stages (the Galois keys the client must make; CoeffToSlot needs element 2N - 1
+   too: needs_conjugation), key_steps_capacity < n_key_steps -> E_INVALIDARG. sealhip_dft_stage_steps: one stage's steps,
+   n_baby and n_giant values in [0, n), 0 the identity.
+   E_INVALIDARG: a BFV context, layer counts not summing to L, a zero count, n_stages >= k (more stages than levels below
+   k), k outside the ciphertext levels, an n_baby that is no power of two or exceeds 2^r. */
+#define SEALHIP_DFT_COEFFS_TO_SLOTS 0u
+#define SEALHIP_DFT_SLOTS_TO_COEFFS 1u
+#define SEALHIP_DFT_MAX_STAGES 16
+typedef struct sealhip_dft_stage
+{
+    uint32_t s0, r, h0;       /* layers s0 .. s0 + r - 1, h0 = 2^(s0 - 1) */
+    uint32_t level;           /* of the stage's input */
+    uint32_t n_baby, n_giant; /* the table is n_giant x n_baby x n_key x N words */
+    uint32_t folded;          /* 1: the stage holds the top layer, 2^r diagonals and no empty cell */
+    uint32_t reserved;
+    double scale;             /* of its plaintexts */
+} sealhip_dft_stage;
+typedef struct sealhip_dft_plan
+{
+    uint32_t direction, n_stages, in_level, out_level;
+    uint32_t needs_conjugation, n_key_steps;
+    uint64_t table_words;         /* device words of all stages' tables */
+    uint64_t temp_bytes_per_item; /* a transform's workspace per ciphertext of the batch: a pool block the tables hold */
+    sealhip_dft_stage stages[SEALHIP_DFT_MAX_STAGES];
+} sealhip_dft_plan;
+typedef struct sealhip_dft_tables sealhip_dft_tables;
+long sealhip_evaluator_dft_plan(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                      const uint32_t *n_baby, sealhip_dft_plan *plan, uint32_t *key_steps, uint32_t key_steps_capacity);
+long sealhip_dft_stage_steps(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages,
+                             uint32_t n_stages, const uint32_t *n_baby, uint32_t stage, int32_t *baby_steps,
+                             int32_t *giant_steps);
+/* The generator alone: values = n_giant x n_baby x n complex doubles {re, im} of stage `stage`, cell [g][b] the diagonal
+   c = c_g n_baby + b rotated by minus its giant step: values[g][b][p] = f M[i][i + c h0], i = (p - giant step) mod n, zero
+   outside the stage's blocks. f is real: 1/2 on the last CoeffToSlot stage (the split adds a value to its conjugate), times
+   `gain` on the last CoeffToSlot or the first SlotToCoeff stage. sealhip_dft_stage_values writes DEVICE memory (stream-ordered,
+   one gather kernel over the encoder's resident root table); _host writes HOST memory with the same function over the same
+   tables, also on host-only contexts, and gives the same bits. */
+long sealhip_dft_stage_values(sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                              const uint32_t *n_baby, double gain, uint32_t stage, double *values);
+long sealhip_dft_stage_values_host(const sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages,
+                                   uint32_t n_stages, const uint32_t *n_baby, double gain, uint32_t stage, double *values);
+/* The tables of one transform: every stage's values through sealhip_ckks_encode at k = n_key and the stage's scale, kept in
+   device memory (plan.table_words words; the values are a temporary). Synchronises; not capturable. gain must be finite and
+   non-zero. _stage: the device pointer of a stage's n_giant x n_baby x n_key x N words, the plain_ntt argument of
+   sealhip_evaluator_rotate_vector_bsgs_plain_rescale; _plan: the plan they were made for. Destroy the tables before their
+   context, not while a call that reads them is in flight, and not during a graph capture (COR_E_INVALIDOPERATION, the
+   tables stay): _destroy gives the transforms' workspace blocks back to the context's pool. */
+long sealhip_dft_tables_create(sealhip_context *ctx, uint32_t direction, uint32_t k, const uint32_t *stages, uint32_t n_stages,
+                               const uint32_t *n_baby, double gain, sealhip_dft_tables **tables);
+long sealhip_dft_tables_destroy(sealhip_dft_tables *tables);
+long sealhip_dft_tables_plan(const sealhip_dft_tables *tables, sealhip_dft_plan *plan);
+long sealhip_dft_tables_stage(const sealhip_dft_tables *tables, uint32_t stage, const uint64_t **plain_ntt);
+/* coeffs_to_slots: ct: count x 2 x k x N at the tables' level k, not modified; stage by stage the BSGS product with the merged
+   rescale, then sigma_(2N-1) of the result and ONE streaming kernel for both outputs:
+       re = c' + sigma(c'),   im = -i (c' - sigma(c'))      (the last stage's values carry the 1/2),
+   multiplication by i being the dyadic product with NTT(X^(N/2)). out_re, out_im: count x 2 x (k - n_stages) x N each.
+   slots_to_coeffs: ct_re, ct_im: count x 2 x k x N; c = re + i im in one streaming kernel, then the stages;
+   out: count x 2 x (k - n_stages) x N. The words are those of the same stages issued one by one through
+   sealhip_evaluator_rotate_vector_bsgs_plain_rescale with the tables, composed with sealhip_evaluator_apply_galois, add, sub
+   and the dyadic product. galois_elts[i] is the Galois element of galois_keys[i] (n_keys of them), as for
+   sealhip_evaluator_rotate_vector_bsgs_plain.
+   ct_re, ct_im, out_re and out_im must be 16-byte aligned: the split and the merge load and store two words at a time.
+   Checks: NULL pointers -> E_POINTER; then, also on host-only contexts, tables made on another context, one of those four
+   pointers not 16-byte aligned, tables of the other direction, a step (or, for
+   coeffs_to_slots, element 2N - 1) whose key is absent ("Galois key not present"), a key with fewer digits than its stage's
+   level, an output overlapping an input or the other output -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then
+   a host-only context -> COR_E_INVALIDOPERATION. With a transparency sink: one flag per output ciphertext, written by a
+   read pass over the result -- coeffs_to_slots: count flags for out_re, then count for out_im. Nothing synchronises. The
+   temporaries (count x plan.temp_bytes_per_item bytes) are a block of the context's pool (sealhip_pool_stats counts it as
+   in use) that the tables hold per calling thread, replaced by a larger one on demand and released by
+   sealhip_dft_tables_destroy: capturable after one call with the same tables at a batch at least as large. */
+long sealhip_evaluator_coeffs_to_slots(sealhip_context *ctx, const sealhip_dft_tables *tables, const uint64_t *ct, size_t count,
+                                       const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                       uint32_t n_keys, uint64_t *out_re, uint64_t *out_im);
+long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_tables *tables, const uint64_t *ct_re,
+                                       const uint64_t *ct_im, size_t count, const uint32_t *galois_elts,
+                                       const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
+
 /* Linear combinations of ciphertexts with scalar weights, both schemes, both modes:
        out_s = sum_{i < n_terms} W[s][i] * X_i  (+ K[s] on c_0)      for s < n_sums
    formed by one streaming kernel that loads every operand word once per tile of 4 sums: no transforms, no lifted plaintexts,
