@@ -15,6 +15,7 @@
 
 #include "blake2xb.hpp"
 #include "engine.hpp"
+#include "evalmod_plan.hpp"
 #include "homdft_plan.hpp"
 #include "poly_plan.hpp"
 
@@ -2492,6 +2493,75 @@ long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_t
     });
 }
 
+/* ------------------------------------------------------------------ ModRaise and the double-angle step */
+long sealhip_evaluator_mod_raise(sealhip_context *ctx, uint32_t k_in, const uint64_t *ct, size_t count, uint32_t k_out,
+                                 uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        if (h.scheme != 2)
+            throw std::invalid_argument("ModRaise is CKKS only");
+        check_data_level(h, k_in);
+        check_data_level(h, k_out);
+        if (k_out < 2)
+            throw std::invalid_argument("k_out must be at least 2");
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * k_out * h.n, in, count * 2 * k_in * h.n))
+            throw std::invalid_argument("out must not overlap ct");
+        check_dft_aligned(ct, "ct");
+        check_dft_aligned(out, "out");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op_mod_raise(e, static_cast<int>(k_in), in, count, static_cast<int>(k_out), o);
+        sink.read_pass(o, 2, static_cast<std::size_t>(k_out) * h.n, count);
+    });
+}
+
+long sealhip_evaluator_double_angle(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale,
+                                    const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out,
+                                    double *out_scale)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    REQUIRE_PTR(out_scale);
+    REQUIRE_PTR(relin_keys);
+    if (n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        check_rescale_level(h, k);
+        const double square = scale * scale;
+        if (!std::isfinite(scale) || scale <= 0 || !std::isfinite(square))
+            throw std::invalid_argument("scale out of bounds");
+        const KSwitchKey *key = first_relin_key(h, k, relin_keys, n_relin_keys);
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * (poly - h.n), in, count * 2 * poly))
+            throw std::invalid_argument("out must not overlap an operand");
+        check_dft_aligned(ct, "ct"); // (square_affine_kernel loads it two words at a time)
+        std::vector<u64> constant(k);
+        for (uint32_t r = 0; r < k; r++)
+            constant[r] = polyplan::rint_residue(-std::nearbyint(square), h.key_moduli[r]);
+        *out_scale = square / static_cast<double>(h.key_moduli[k - 1]);
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        sink.begin();
+        op_double_angle(e, static_cast<int>(k), in, count, constant.data(), *key, o);
+    });
+}
+
 /* ------------------------------------------------------------------ ciphertext inner product */
 long sealhip_evaluator_dot_product_max_terms(sealhip_context *ctx, uint32_t k, uint64_t *max_terms)
 {
@@ -2774,6 +2844,248 @@ long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
         op_evaluate_polynomial_ckks(e, p, k, x, count, key, o, sink);
+    });
+}
+
+/* ------------------------------------------------------------------ EvalMod */
+extern "C++"
+{
+namespace
+{
+    evalmod::Plan evalmod_make_plan(Engine &h, uint32_t k, double scale, uint32_t K, uint32_t r, uint32_t degree, uint32_t n_baby,
+                                    double scale_out, bool tables)
+    {
+        check_data_level(h, k);
+        if (h.scheme != 2)
+            throw std::invalid_argument("EvalMod is CKKS only");
+        return evalmod::make_plan(h.key_moduli.data(), static_cast<int>(k), scale, K, r, degree, n_baby, scale_out, tables);
+    }
+
+    void evalmod_plan_to_abi(const evalmod::Plan &p, std::size_t N, sealhip_evalmod_plan *plan)
+    {
+        std::memset(plan, 0, sizeof(*plan));
+        plan->K = p.K, plan->r = p.r, plan->degree = p.d, plan->n_baby = static_cast<uint32_t>(p.poly.m);
+        plan->poly_level = static_cast<uint32_t>(p.poly_level), plan->out_level = static_cast<uint32_t>(p.out_level);
+        plan->n_products = static_cast<uint32_t>(p.n_products);
+        plan->poly_scale_out = p.t0;
+        std::copy(p.scales.begin(), p.scales.end(), plan->scales);
+        plan->temp_bytes_per_item = evalmod_temp_words(p, N) * sizeof(u64);
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_evalmod_coeffs(uint32_t K, uint32_t r, uint32_t degree, double *coeffs)
+{
+    REQUIRE_PTR(coeffs);
+    return guarded([&] {
+        const std::vector<double> c = evalmod::coeffs(K, r, degree);
+        std::copy(c.begin(), c.end(), coeffs);
+    });
+}
+
+long sealhip_evaluator_evalmod_plan(const sealhip_context *ctx, uint32_t k, double scale, uint32_t K, uint32_t r, uint32_t degree,
+                                    uint32_t n_baby, double scale_out, sealhip_evalmod_plan *plan)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const evalmod::Plan p = evalmod_make_plan(h, k, scale, K, r, degree, n_baby, scale_out, false);
+        evalmod_plan_to_abi(p, h.n, plan);
+    });
+}
+
+long sealhip_evaluator_eval_mod(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale, uint32_t K,
+                                uint32_t r, uint32_t degree, uint32_t n_baby, double scale_out,
+                                const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out,
+                                uint32_t *out_level, double *out_scale)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    if (relin_keys && n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const evalmod::Plan p = evalmod_make_plan(h, k, scale, K, r, degree, n_baby, scale_out, true);
+        const KSwitchKey *key = (p.poly.d >= 2 || r > 0) ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr;
+        const u64 *x = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * p.out_level * h.n, x, count * 2 * k * h.n))
+            throw std::invalid_argument("out must not overlap ct");
+        if (out_level)
+            *out_level = static_cast<uint32_t>(p.out_level);
+        if (out_scale)
+            *out_scale = p.scales.back();
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op_eval_mod(e, p, k, x, count, key, o, sink);
+    });
+}
+
+/* ------------------------------------------------------------------ the bootstrap */
+extern "C++"
+{
+struct sealhip_bootstrap_tables
+{
+    BootstrapTables *tables = nullptr;
+    sealhip_bootstrap_plan plan{};
+};
+
+namespace
+{
+    struct BootPlan
+    {
+        dftplan::Plan c2s, s2c;
+        evalmod::Plan em;
+        double raise_scale = 0, s2c_gain = 0;
+        std::vector<uint32_t> key_steps;
+    };
+
+    BootPlan boot_make_plan(Engine &h, uint32_t k_top, const uint32_t *c2s_stages, uint32_t n_c2s, const uint32_t *c2s_n_baby,
+                            const uint32_t *s2c_stages, uint32_t n_s2c, const uint32_t *s2c_n_baby, uint32_t K, uint32_t r,
+                            uint32_t degree, uint32_t n_baby, bool tables)
+    {
+        BootPlan b;
+        b.c2s = dft_make_plan(h, dftplan::kCoeffsToSlots, k_top, c2s_stages, n_c2s, c2s_n_baby);
+        if (K < 1)
+            throw std::invalid_argument("K must be at least 1");
+        b.raise_scale = static_cast<double>(h.key_moduli[0]) * static_cast<double>(K);
+        b.em = evalmod_make_plan(h, b.c2s.out_level, b.raise_scale, K, r, degree, n_baby, 0.0, tables);
+        if (b.em.out_level < 2)
+            throw std::invalid_argument("end of modulus switching chain reached");
+        b.s2c = dft_make_plan(h, dftplan::kSlotsToCoeffs, static_cast<uint32_t>(b.em.out_level), s2c_stages, n_s2c, s2c_n_baby);
+        const double two_pi_s = 6.283185307179586476925286766559 * b.em.scales.back();
+        b.s2c_gain = static_cast<double>(h.key_moduli[0]) / two_pi_s;
+        b.key_steps = b.c2s.key_steps;
+        b.key_steps.insert(b.key_steps.end(), b.s2c.key_steps.begin(), b.s2c.key_steps.end());
+        std::sort(b.key_steps.begin(), b.key_steps.end());
+        b.key_steps.erase(std::unique(b.key_steps.begin(), b.key_steps.end()), b.key_steps.end());
+        return b;
+    }
+
+    void boot_plan_to_abi(const Engine &h, const BootPlan &b, sealhip_bootstrap_plan *out)
+    {
+        std::memset(out, 0, sizeof(*out));
+        out->k_top = b.c2s.in_level, out->c2s_out_level = b.c2s.out_level;
+        out->evalmod_out_level = static_cast<uint32_t>(b.em.out_level), out->out_level = b.s2c.out_level;
+        out->needs_conjugation = 1;
+        out->n_key_steps = static_cast<uint32_t>(b.key_steps.size());
+        out->raise_scale = b.raise_scale, out->s2c_gain = b.s2c_gain;
+        out->table_words = b.c2s.table_words + b.s2c.table_words;
+        out->temp_bytes_per_item = bootstrap_temp_words(b.c2s.in_level, b.c2s, b.em, h.n) * sizeof(u64);
+        evalmod_plan_to_abi(b.em, h.n, &out->evalmod);
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_evaluator_bootstrap_plan(const sealhip_context *ctx, uint32_t k_top, const uint32_t *c2s_stages, uint32_t n_c2s,
+                                      const uint32_t *c2s_n_baby, const uint32_t *s2c_stages, uint32_t n_s2c,
+                                      const uint32_t *s2c_n_baby, uint32_t K, uint32_t r, uint32_t degree, uint32_t n_baby,
+                                      sealhip_bootstrap_plan *plan, uint32_t *key_steps, uint32_t key_steps_capacity)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const BootPlan b = boot_make_plan(h, k_top, c2s_stages, n_c2s, c2s_n_baby, s2c_stages, n_s2c, s2c_n_baby, K, r, degree,
+                                          n_baby, false);
+        if (key_steps && key_steps_capacity < b.key_steps.size())
+            throw std::invalid_argument("key_steps is too small");
+        boot_plan_to_abi(h, b, plan);
+        if (key_steps)
+            std::copy(b.key_steps.begin(), b.key_steps.end(), key_steps);
+    });
+}
+
+long sealhip_bootstrap_tables_create(sealhip_context *ctx, uint32_t k_top, const uint32_t *c2s_stages, uint32_t n_c2s,
+                                     const uint32_t *c2s_n_baby, const uint32_t *s2c_stages, uint32_t n_s2c,
+                                     const uint32_t *s2c_n_baby, uint32_t K, uint32_t r, uint32_t degree, uint32_t n_baby,
+                                     sealhip_bootstrap_tables **tables)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const BootPlan b = boot_make_plan(h, k_top, c2s_stages, n_c2s, c2s_n_baby, s2c_stages, n_s2c, s2c_n_baby, K, r, degree,
+                                          n_baby, true);
+        check_dft_gain(b.s2c_gain);
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("sealhip_bootstrap_tables_create synchronises: it cannot be captured");
+        std::unique_ptr<sealhip_bootstrap_tables> t(new sealhip_bootstrap_tables);
+        boot_plan_to_abi(h, b, &t->plan);
+        t->tables = bootstrap_tables_create(e, k_top, b.c2s, b.em, b.s2c, b.s2c_gain);
+        *tables = t.release();
+    });
+}
+
+long sealhip_bootstrap_tables_destroy(sealhip_bootstrap_tables *tables)
+{
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        bootstrap_tables_destroy(tables->tables); // (throws, and leaves the tables alone, during a graph capture)
+        delete tables;
+    });
+}
+
+long sealhip_bootstrap_tables_plan(const sealhip_bootstrap_tables *tables, sealhip_bootstrap_plan *plan)
+{
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(plan);
+    return guarded([&] { *plan = tables->plan; });
+}
+
+long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in, const uint64_t *ct,
+                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                 uint32_t n_keys, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                                 uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    if (n_keys)
+    {
+        REQUIRE_PTR(galois_elts);
+        REQUIRE_PTR(galois_keys);
+        for (uint32_t i = 0; i < n_keys; i++)
+            REQUIRE_PTR(galois_keys[i]);
+    }
+    if (relin_keys && n_relin_keys)
+        REQUIRE_PTR(relin_keys[0]);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        const BootstrapTables &t = *tables->tables;
+        if (bootstrap_tables_engine(t) != ctx->engine.get())
+            throw std::invalid_argument("the bootstrap tables were made on another context");
+        check_data_level(h, k_in);
+        check_dft_aligned(ct, "ct");
+        check_dft_aligned(out, "out");
+        const dftplan::Plan &c2s = dft_tables_plan(bootstrap_tables_c2s(t)), &s2c = dft_tables_plan(bootstrap_tables_s2c(t));
+        const std::vector<DftStageKeys> c2s_keys = dft_stage_keys(h, c2s, galois_elts, galois_keys, n_keys);
+        const std::vector<DftStageKeys> s2c_keys = dft_stage_keys(h, s2c, galois_elts, galois_keys, n_keys);
+        const uint32_t conj_elt = static_cast<uint32_t>(2 * h.n - 1);
+        const sealhip_kswitch_key *conj = nullptr;
+        for (uint32_t i = 0; i < n_keys && !conj; i++)
+            if (galois_elts[i] == conj_elt)
+                conj = galois_keys[i];
+        if (!conj)
+            throw std::invalid_argument("Galois key not present");
+        check_key_digits(h, c2s.out_level, conj);
+        const KSwitchKey *relin = first_relin_key(h, c2s.out_level, relin_keys, n_relin_keys);
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * s2c.out_level * h.n, in, count * 2 * k_in * h.n))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op_bootstrap(e, t, static_cast<int>(k_in), in, count, c2s_keys, conj->key, s2c_keys, *relin, o);
+        sink.read_pass(o, 2, static_cast<std::size_t>(s2c.out_level) * h.n, count);
     });
 }
 

@@ -1,0 +1,130 @@
+// bootstrap.cpp -- CKKS bootstrapping as one call: ModRaise, CoeffToSlot, EvalMod over both halves at
+// once, SlotToCoeff. The plans are homdft_plan.hpp's and evalmod_plan.hpp's; the argument checks are the ABI entries'
+// (api.cpp). The intermediates are one block of the context's pool per lane that the tables hold, under the rule of the
+// DFT tables (homdft.cpp): a larger batch takes a larger block, the earlier ones stay held, destroy releases all of them.
+#include "../../include/sealhip.h"
+
+#include <map>
+#include <mutex>
+
+#include "engine.hpp"
+#include "evalmod_plan.hpp"
+#include "homdft_plan.hpp"
+
+namespace sealhip
+{
+    struct BootstrapTables
+    {
+        const Engine *engine = nullptr;
+        int device = -1;
+        std::uint32_t k_top = 0;
+        evalmod::Plan evalmod;
+        DftTables *c2s = nullptr, *s2c = nullptr;
+        struct Block
+        {
+            void *p;
+            std::size_t bytes;
+        };
+        mutable std::mutex mu;
+        mutable std::map<const Lane *, std::vector<Block>> blocks;
+        char *workspace(const Engine &e, std::size_t bytes) const
+        {
+            Lane &l = e.lane();
+            std::lock_guard<std::mutex> lock(mu);
+            std::vector<Block> &v = blocks[&l];
+            if (!v.empty() && v.back().bytes >= bytes)
+                return static_cast<char *>(v.back().p);
+            if (l.capturing)
+                throw std::logic_error("the bootstrap's workspace would be allocated during a graph capture");
+            void *p = pool_alloc(e, bytes);
+            v.push_back(Block{ p, bytes });
+            return static_cast<char *>(p);
+        }
+    };
+
+    // per ciphertext: the raised input at k_top, CoeffToSlot's two outputs, EvalMod's two outputs
+    std::size_t bootstrap_temp_words(std::uint32_t k_top, const dftplan::Plan &c2s, const evalmod::Plan &em, std::size_t N)
+    {
+        return 2 * N * (static_cast<std::size_t>(k_top) + 2 * static_cast<std::size_t>(c2s.out_level) +
+                        2 * static_cast<std::size_t>(em.out_level));
+    }
+
+    BootstrapTables *bootstrap_tables_create(Engine &e, std::uint32_t k_top, const dftplan::Plan &c2s, const evalmod::Plan &em,
+                                             const dftplan::Plan &s2c, double s2c_gain)
+    {
+        std::unique_ptr<BootstrapTables> t(new BootstrapTables);
+        t->engine = &e;
+        t->device = e.device;
+        t->k_top = k_top;
+        t->evalmod = em;
+        t->c2s = dft_tables_create(e, c2s, 1.0);
+        try
+        {
+            t->s2c = dft_tables_create(e, s2c, s2c_gain);
+        }
+        catch (...)
+        {
+            dft_tables_destroy(t->c2s);
+            throw;
+        }
+        return t.release();
+    }
+
+    void bootstrap_tables_destroy(BootstrapTables *t)
+    {
+        if (!t)
+            return;
+        const Engine &e = *t->engine;
+        if (e.lane().capturing)
+            throw std::logic_error("bootstrap tables cannot be destroyed during a graph capture");
+        int current = -1;
+        (void)hipGetDevice(&current);
+        SEALHIP_CHECK(hipSetDevice(t->device));
+        for (auto &lane : t->blocks)
+            for (BootstrapTables::Block &b : lane.second)
+                pool_release(e, b.p);
+        t->blocks.clear();
+        dft_tables_destroy(t->c2s);
+        dft_tables_destroy(t->s2c);
+        delete t;
+        if (current >= 0 && current != e.device)
+            (void)hipSetDevice(current);
+    }
+
+    const Engine *bootstrap_tables_engine(const BootstrapTables &t)
+    {
+        return t.engine;
+    }
+    const DftTables &bootstrap_tables_c2s(const BootstrapTables &t)
+    {
+        return *t.c2s;
+    }
+    const DftTables &bootstrap_tables_s2c(const BootstrapTables &t)
+    {
+        return *t.s2c;
+    }
+
+    void op_bootstrap(Engine &e, const BootstrapTables &t, int k_in, const u64 *ct, std::size_t count,
+                      const std::vector<DftStageKeys> &c2s_keys, const KSwitchKey &conj_key,
+                      const std::vector<DftStageKeys> &s2c_keys, const KSwitchKey &relin_key, u64 *out)
+    {
+        const dftplan::Plan &c2s = dft_tables_plan(*t.c2s);
+        const evalmod::Plan &em = t.evalmod;
+        const std::size_t N = e.n;
+        const std::size_t w_top = count * 2 * t.k_top * N, w_slots = count * 2 * c2s.out_level * N,
+                          w_sine = count * 2 * static_cast<std::size_t>(em.out_level) * N;
+        char *ws = t.workspace(e, (w_top + 2 * w_slots + 2 * w_sine) * sizeof(u64) + 3 * 256);
+        const auto pad = [](std::size_t words) { return (words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255); };
+        u64 *raised = reinterpret_cast<u64 *>(ws);
+        u64 *slots = reinterpret_cast<u64 *>(ws + pad(w_top));                   // re, then im: ONE batch of 2 count items
+        u64 *sine = reinterpret_cast<u64 *>(ws + pad(w_top) + pad(2 * w_slots)); // likewise
+        op_mod_raise(e, k_in, ct, count, static_cast<int>(t.k_top), raised);
+        op_coeffs_to_slots(e, *t.c2s, raised, count, c2s_keys, conj_key, slots, slots + w_slots);
+        {
+            SinkScope quiet(e, 0); // (an intermediate: the caller's flags describe `out` alone)
+            quiet.on = false;
+            op_eval_mod(e, em, c2s.out_level, slots, 2 * count, &relin_key, sine, quiet);
+        }
+        op_slots_to_coeffs(e, *t.s2c, sine, sine + w_sine, count, s2c_keys, out);
+    }
+} // namespace sealhip

@@ -25,6 +25,7 @@ struct sealhip_kswitch_key; // the C ABI's key handle (api.cpp)
 namespace sealhip
 {
     namespace polyplan { struct Plan; } // poly_plan.hpp
+    namespace evalmod { struct Plan; }  // evalmod_plan.hpp
     constexpr int kMaxRows = 136;          // rows of one "polynomial" a launch can describe
     constexpr int kMaxModuli = 64;         // SEAL_COEFF_MOD_COUNT_MAX (util/defines.h:48)
     constexpr unsigned short kSkipRow = 0xFFFF;
@@ -1069,6 +1070,41 @@ namespace sealhip
     // ct_re, ct_im[count][2][k][N] -> out[count][2][k - n_stages][N]
     void op_slots_to_coeffs(Engine &e, const DftTables &t, const u64 *ct_re, const u64 *ct_im, std::size_t count,
                             const std::vector<DftStageKeys> &keys, u64 *out);
+
+    // ---- towards CKKS bootstrapping: ModRaise and the double-angle step (bootstrap.hip, poly.hip) ----
+    // coef[npolys][N] (coefficient form, canonical modulo q_0) -> rows 1 .. k_out-1 of out[npolys][k_out][N]: the centred
+    // coefficients modulo each row's prime, canonical, in coefficient form. Row 0 is left alone.
+    hipError_t launch_mod_raise_lift(const Engine &e, const u64 *coef, u64 *out, std::size_t npolys, int k_out);
+    // ct[count][2][k_in][N] -> out[count][2][k_out][N] (CKKS, NTT form): row 0 is the input's, row i >= 1 the forward
+    // transform of centre(INTT_0(row 0)) mod q_i. Only the q_0 rows of ct are read.
+    void op_mod_raise(Engine &e, int k_in, const u64 *ct, std::size_t count, int k_out, u64 *out);
+    // out[count][3][map.rows][N] = (2 a_0^2 + constant[r], 4 a_0 a_1, 2 a_1^2) of a[count][2][map.rows][N], canonical;
+    // constant: map.rows words of host memory (they travel in the kernel's arguments)
+    hipError_t launch_square_affine(const Engine &e, const u64 *a, u64 *out, std::size_t count, const RowMap &map,
+                                    const u64 *constant);
+    // CKKS: out[count][2][k-1][N] = the merged key switch and rescale of 2 ct^2 + constant (host, k words)
+    void op_double_angle(Engine &e, int k, const u64 *ct, std::size_t count, const u64 *constant, const KSwitchKey &key,
+                         u64 *out);
+    // EvalMod (poly_eval.cpp over evalmod_plan.hpp): out[count][2][p.out_level][N] = the planned Chebyshev polynomial of x
+    // followed by p.r double-angle steps; key: relin_keys' first; sink: the entry's scope. Temporaries are pool blocks.
+    void op_eval_mod(Engine &e, const evalmod::Plan &p, std::uint32_t k, const u64 *x, std::size_t count, const KSwitchKey *key,
+                     u64 *out, SinkScope &sink);
+    std::size_t evalmod_temp_words(const evalmod::Plan &p, std::size_t N); // per item, what that call takes from the pool
+    // The bootstrap (bootstrap.cpp): two DFT tables (CoeffToSlot with gain 1, SlotToCoeff with the plan's gain), the EvalMod
+    // plan, and one pool block per lane for the intermediates
+    struct BootstrapTables;
+    BootstrapTables *bootstrap_tables_create(Engine &e, std::uint32_t k_top, const dftplan::Plan &c2s, const evalmod::Plan &em,
+                                             const dftplan::Plan &s2c, double s2c_gain);
+    void bootstrap_tables_destroy(BootstrapTables *t);
+    const Engine *bootstrap_tables_engine(const BootstrapTables &t);
+    const DftTables &bootstrap_tables_c2s(const BootstrapTables &t);
+    const DftTables &bootstrap_tables_s2c(const BootstrapTables &t);
+    std::size_t bootstrap_temp_words(std::uint32_t k_top, const dftplan::Plan &c2s, const evalmod::Plan &em, std::size_t N);
+    // ct[count][2][k_in][N] -> out[count][2][s2c out level][N]: mod_raise to k_top, coeffs_to_slots, eval_mod ONCE over the
+    // 2 count real and imaginary halves, slots_to_coeffs
+    void op_bootstrap(Engine &e, const BootstrapTables &t, int k_in, const u64 *ct, std::size_t count,
+                      const std::vector<DftStageKeys> &c2s_keys, const KSwitchKey &conj_key,
+                      const std::vector<DftStageKeys> &s2c_keys, const KSwitchKey &relin_key, u64 *out);
 
     // ---- Decryptor (decrypt.hip, pipeline.cpp) ----
     // bits_out[i] = max(bits_out[i], bits of the largest centred |t v| of item i), v = count x k x N dot products

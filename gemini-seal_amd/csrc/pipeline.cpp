@@ -570,6 +570,58 @@ namespace sealhip
         });
     }
 
+    // The double-angle step 2 x^2 - 1 of EvalMod: square_affine_kernel writes the size-3 ciphertext
+    // 2 ct^2 + constant into the arena in one pass, and the merged key switch and rescale brings it to level k - 1. The wide
+    // ciphertext is parked under a raised floor while the nested chunk loop runs, as op_dot_product parks its sum.
+    void op_double_angle(Engine &e, int k, const u64 *ct, std::size_t count, const u64 *constant, const KSwitchKey &key, u64 *out)
+    {
+        if (e.scheme != 2)
+            throw std::invalid_argument("the merged rescale is a CKKS operation");
+        if (k > e.k_first)
+            throw std::invalid_argument("key switching needs a ciphertext level");
+        if (k < 2)
+            throw std::invalid_argument("end of modulus switching chain reached"); // evaluator.cpp:1005-1008
+        LevelTools &lt = e.level_rescale(k);
+        if (static_cast<int>(key.n_digits) < lt.h_ks.nd)
+            throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        const std::size_t N = e.n, poly_q = static_cast<std::size_t>(k) * N, w_wide = 3 * poly_q;
+        const std::size_t ks_bytes = switch_key_arena(e, k, true).item_bytes();
+        for_chunks(e, count, w_wide * sizeof(u64) + ks_bytes, 2 + KsArena::n_buffers, [&](std::size_t off, std::size_t m) {
+            u64 *wide = e.ws_alloc(w_wide * m);
+            FloorRestore guard(e);
+            check(launch_square_affine(e, ct + off * 2 * poly_q, wide, m, lt.map_q, constant), "square_affine");
+            guard.raise(pad256(w_wide * m));
+            e.lane().tsink_base = guard.base + off; // (the nested chunk loop counts its items from this chunk's first ciphertext)
+            op_switch_key_rescale(e, k, wide, w_wide, wide + 2 * poly_q, w_wide, m, key, out + off * 2 * (poly_q - N));
+        });
+    }
+
+    // ModRaise: the q_0 rows of the batch go to coefficient form in the arena, the lift re-reads their
+    // centred coefficients modulo q_1 .. q_(k_out-1) into the output's rows, which are then transformed in place; row 0 of
+    // the output is the input's row 0, copied.
+    void op_mod_raise(Engine &e, int k_in, const u64 *ct, std::size_t count, int k_out, u64 *out)
+    {
+        if (e.scheme != 2)
+            throw std::invalid_argument("ModRaise is a CKKS operation");
+        if (k_in < 1 || k_in > e.k_first || k_out < 2 || k_out > e.k_first)
+            throw std::invalid_argument("level k out of range");
+        const std::size_t N = e.n, in_poly = static_cast<std::size_t>(k_in) * N, out_poly = static_cast<std::size_t>(k_out) * N;
+        RowMap first{};
+        first.rows = 1;
+        first.prime[0] = 0;
+        const RowMap raised = skip_map(e.level_host(k_out).map_q, 1, k_out);
+        for_chunks(e, count, 2 * N * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
+            u64 *coef = e.ws_alloc(2 * N * m);
+            const u64 *in = ct + off * 2 * in_poly;
+            u64 *o = out + off * 2 * out_poly;
+            check(launch_copy_rows(e, in, in_poly, coef, N, 2 * m, 1), "copy(q_0 rows)");
+            check(launch_ntt(e, coef, 2 * m, first, true, kNttCanonical), "intt(q_0 rows)");
+            check(launch_mod_raise_lift(e, coef, o, 2 * m, k_out), "mod_raise_lift");
+            check(launch_ntt(e, o, 2 * m * k_out, raised, false, kNttCanonical), "ntt(raised rows)");
+            check(launch_copy_rows(e, in, in_poly, o, out_poly, 2 * m, 1), "copy(row 0)");
+        });
+    }
+
     // modup_rns as a standalone operation (multi_special_primes.cpp:151-185)
     void op_modup(Engine &e, int k, int bundle, u64 *ext, std::size_t count)
     {

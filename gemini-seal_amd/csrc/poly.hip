@@ -803,6 +803,76 @@ namespace sealhip
 
     namespace
     {
+        // The double-angle step's front: out = 2 a^2 + C as a size-3 ciphertext,
+        //     o_0 = 2 a_0^2 + C_r,   o_1 = 4 a_0 a_1,   o_2 = 2 a_1^2      (mod the row's prime),
+        // in ONE pass: 2 words read and 3 written per coefficient, where tensor_dot_kernel followed by lincomb_levels_kernel
+        // moves 11. The operands are canonical and the primes at most 61 bits, so 4 a_0 a_1 < 2^124 and 2 a_0^2 + C_r < 2^124:
+        // each output is one 128-bit integer reduced ONCE, hence the canonical residue -- the very word the two passes leave.
+        // a[count][2][rows][N], out[count][3][rows][N]; one lane per coefficient pair; the constants travel in the arguments.
+        struct SquareAffineConsts
+        {
+            u64 c[kMaxModuli];
+        };
+        __device__ __forceinline__ u64 square_affine_word(u64 x, u64 y, int shift, u64 c, u64 p, u64 cr0, u64 cr1)
+        {
+            u64 lo = x * y, hi = mulhi(x, y);
+            hi = (hi << shift) | (lo >> (64 - shift));
+            lo <<= shift;
+            dot_add_word(lo, hi, c);
+            return barrett_reduce_128(lo, hi, p, cr0, cr1);
+        }
+        __global__ __launch_bounds__(kThreads) void square_affine_kernel(const u64 *__restrict__ a, u64 *__restrict__ out,
+                                                                         SquareAffineConsts consts,
+                                                                         const PrimeDev *__restrict__ primes, RowMap map, int logn,
+                                                                         std::size_t npairs_per_item, std::size_t count)
+        {
+            const std::size_t total = npairs_per_item * count;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t poly_words = static_cast<std::size_t>(map.rows) << logn;
+            for (std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; i < total; i += stride)
+            {
+                const std::size_t item = i / npairs_per_item;
+                const std::size_t off = 2 * (i - item * npairs_per_item); // word offset inside one polynomial
+                const int row = static_cast<int>(off >> logn);
+                const unsigned short pid = map.prime[row];
+                const u64 p = primes[pid].p, cr0 = primes[pid].cr0, cr1 = primes[pid].cr1, c = consts.c[row];
+                const u64 *pa = a + item * 2 * poly_words + off;
+                const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(pa);
+                const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(pa + poly_words);
+                u64 *po = out + item * 3 * poly_words + off;
+                store_stream2(po, square_affine_word(a0.x, a0.x, 1, c, p, cr0, cr1),
+                              square_affine_word(a0.y, a0.y, 1, c, p, cr0, cr1));
+                store_stream2(po + poly_words, square_affine_word(a0.x, a1.x, 2, 0, p, cr0, cr1),
+                              square_affine_word(a0.y, a1.y, 2, 0, p, cr0, cr1));
+                store_stream2(po + 2 * poly_words, square_affine_word(a1.x, a1.x, 1, 0, p, cr0, cr1),
+                              square_affine_word(a1.y, a1.y, 1, 0, p, cr0, cr1));
+            }
+        }
+    } // namespace
+
+    hipError_t launch_square_affine(const Engine &e, const u64 *a, u64 *out, std::size_t count, const RowMap &map,
+                                    const u64 *constant)
+    {
+        if (map.rows < 1 || map.rows > kMaxModuli)
+            return hipErrorInvalidValue;
+        const std::size_t pairs = (static_cast<std::size_t>(map.rows) << e.logn) / 2;
+        if (pairs * count == 0)
+            return hipSuccess;
+        SquareAffineConsts consts{};
+        for (int r = 0; r < map.rows; r++)
+        {
+            if (map.prime[r] == kSkipRow)
+                return hipErrorInvalidValue;
+            consts.c[r] = constant[r];
+        }
+        ProfScope prof(e, "square_affine", 0);
+        square_affine_kernel<<<grid_for(pairs * count), kThreads, 0, e.lane().stream>>>(a, out, consts, e.d_primes, map, e.logn,
+                                                                                       pairs, count);
+        return hipGetLastError();
+    }
+
+    namespace
+    {
         template <int S>
         void lincomb_launch(const Engine &e, unsigned grid, const LinTerms &terms, std::size_t x_stride, const u64 *w,
                             std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,

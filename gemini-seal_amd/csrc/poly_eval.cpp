@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "engine.hpp"
+#include "evalmod_plan.hpp"
 #include "poly_plan.hpp"
 
 namespace sealhip
@@ -279,5 +280,49 @@ namespace sealhip
         if (taken != ckks_poly_temp_words(p, N))
             throw std::logic_error("evaluate_polynomial_ckks: the temporaries taken differ from the plan's count");
         sink.read_pass(o, 2, out_poly, count);
+    }
+
+    // ---- EvalMod: the planned polynomial, then r double-angle steps between two pool blocks
+    std::size_t evalmod_temp_words(const evalmod::Plan &p, std::size_t N)
+    {
+        std::size_t words = ckks_poly_temp_words(p.poly, N);
+        if (p.r >= 1)
+            words += 2 * static_cast<std::size_t>(p.poly_level) * N;
+        if (p.r >= 2)
+            words += 2 * static_cast<std::size_t>(p.poly_level - 1) * N;
+        return words;
+    }
+
+    void op_eval_mod(Engine &e, const evalmod::Plan &p, std::uint32_t k, const u64 *x, std::size_t count, const KSwitchKey *key,
+                     u64 *o, SinkScope &sink)
+    {
+        if (p.r == 0)
+            return op_evaluate_polynomial_ckks(e, p.poly, k, x, count, key, o, sink);
+        if (!key)
+            throw std::invalid_argument("not enough relinearization keys");
+        const std::size_t N = e.n;
+        Scratch scratch(e);
+        u64 *a = scratch.take(count * 2 * static_cast<std::size_t>(p.poly_level) * N * sizeof(u64));
+        u64 *b = p.r >= 2 ? scratch.take(count * 2 * static_cast<std::size_t>(p.poly_level - 1) * N * sizeof(u64)) : nullptr;
+        {
+            SinkScope quiet(e, 0); // (the polynomial's result is an intermediate: its read pass must not touch the flags)
+            quiet.on = false;
+            op_evaluate_polynomial_ckks(e, p.poly, k, x, count, key, a, quiet);
+        }
+        const u64 *cur = a;
+        std::vector<u64> constant;
+        for (unsigned i = 1; i <= p.r; i++)
+        {
+            const int level = p.poly_level - static_cast<int>(i) + 1;
+            const double s = p.scales[i - 1];
+            constant.assign(level, 0);
+            for (int r = 0; r < level; r++)
+                constant[r] = polyplan::rint_residue(-std::nearbyint(s * s), e.key_moduli[r]);
+            u64 *dst = i == p.r ? o : (cur == a ? b : a);
+            if (i == p.r)
+                sink.begin(); // the last step's key switch stores the result and notes the flags
+            op_double_angle(e, level, cur, count, constant.data(), *key, dst);
+            cur = dst;
+        }
     }
 } // namespace sealhip

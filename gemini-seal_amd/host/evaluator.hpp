@@ -652,6 +652,48 @@ namespace sealhip_host
         std::vector<std::uint32_t> key_steps_;
     };
 
+    // The plan and the device tables of one bootstrap shape (sealhip_bootstrap_tables_create):
+    // ModRaise to level k_top, CoeffToSlot as `c2s_stages`, EvalMod (K, r, degree, n_baby), SlotToCoeff as `s2c_stages`.
+    // K bounds ModRaise's integer polynomial, K >= max|I| + 1: it grows with the secret's Hamming weight, and the library
+    // does not sample sparse secrets. Evaluator::bootstrap takes it; the result is at out_level() with the operand's scale,
+    // its precision bounded by |m| / q_0 (the sine step's relative error is (2 pi m / q_0)^2 / 6). key_steps(): the rotation
+    // steps whose Galois keys the client must make, next to the key of element 2N - 1.
+    class Bootstrapper
+    {
+    public:
+        Bootstrapper(const Context &c, std::size_t k_top, const std::vector<std::uint32_t> &c2s_stages,
+                     const std::vector<std::uint32_t> &s2c_stages, std::uint32_t K, std::uint32_t r, std::uint32_t degree,
+                     std::uint32_t n_baby = 0)
+        {
+            const std::uint32_t n1 = std::uint32_t(c2s_stages.size()), n2 = std::uint32_t(s2c_stages.size());
+            // (the plan first: its refusals need no device)
+            throw_on(sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
+                                                      s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &plan_, nullptr, 0));
+            key_steps_.resize(plan_.n_key_steps);
+            throw_on(sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
+                                                      s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &plan_,
+                                                      key_steps_.data(), plan_.n_key_steps));
+            throw_on(sealhip_bootstrap_tables_create(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
+                                                     s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &tables_));
+        }
+        ~Bootstrapper()
+        {
+            if (tables_)
+                sealhip_bootstrap_tables_destroy(tables_);
+        }
+        Bootstrapper(const Bootstrapper &) = delete;
+        Bootstrapper &operator=(const Bootstrapper &) = delete;
+        const sealhip_bootstrap_tables *get() const { return tables_; }
+        const sealhip_bootstrap_plan &plan() const { return plan_; }
+        std::size_t out_level() const { return plan_.out_level; }
+        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
+
+    private:
+        sealhip_bootstrap_tables *tables_ = nullptr;
+        sealhip_bootstrap_plan plan_{};
+        std::vector<std::uint32_t> key_steps_;
+    };
+
     template <class CT>
     class Evaluator
     {
@@ -1137,6 +1179,13 @@ namespace sealhip_host
             if (encrypted.coeff_modulus_size() != dft.in_level())
                 throw std::invalid_argument("encrypted is not at the level of the DFT tables");
         }
+        template <class C>
+        void check_bootstrap_operand(const C &encrypted) const
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme");
+            check_galois_operand(encrypted);
+        }
         static void dft_keys(const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<std::uint32_t> &elts,
                              std::vector<const sealhip_kswitch_key *> &raw)
         {
@@ -1518,6 +1567,90 @@ namespace sealhip_host
             take_meta(destination, encrypted);
             commit(destination, o, 2, k - 1);
             destination.scale() = scale;
+        }
+
+        // ---- CKKS bootstrapping and its parts; size-2 operands in NTT form
+        // ModRaise (sealhip_evaluator_mod_raise): the centred coefficients of the operand modulo q_0 re-read modulo the
+        // first k_out primes. Only the operand's q_0 rows are read; the destination decrypts to m + q_0 I and keeps the
+        // operand's scale (the caller re-declares it, e.g. as q_0 K ahead of coeffs_to_slots).
+        template <class C, IfCt<C> = 0>
+        void mod_raise(const C &encrypted, std::size_t k_out, C &destination)
+        {
+            check_bootstrap_operand(encrypted);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            if (k_out < 2)
+                throw std::invalid_argument("k_out must be at least 2");
+            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * k_out * n);
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_mod_raise(ctx_.get(), std::uint32_t(k), c.ptr(), 1, std::uint32_t(k_out), o.ptr()));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, k_out);
+        }
+        // destination = 2 encrypted^2 - 1, one level down, at the scale scale^2 / q_(k-1) (sealhip_evaluator_double_angle)
+        template <class C, IfCt<C> = 0>
+        void double_angle(const C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
+        {
+            check_bootstrap_operand(encrypted);
+            if (relin_keys.empty() || !relin_keys[0])
+                throw std::invalid_argument("not enough relinearization keys"); // :793-796
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            if (k < 2)
+                throw std::invalid_argument("end of modulus switching chain reached");
+            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * (k - 1) * n);
+            const sealhip_kswitch_key *raw = relin_keys[0]->get();
+            double scale = 0.0;
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_double_angle(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(), &raw, 1, o.ptr(),
+                                                    &scale));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, k - 1);
+            destination.scale() = scale;
+        }
+        // EvalMod (sealhip_evaluator_eval_mod): slots x = c / (q_0 K) in [-1, 1] become sin(2 pi K x); the destination gets
+        // the plan's level and scale (sealhip_evaluator_evalmod_plan), scale_out or the operand's scale up to rounding
+        template <class C, IfCt<C> = 0>
+        void eval_mod(const C &encrypted, std::uint32_t K, std::uint32_t r, std::uint32_t degree,
+                      const std::vector<const KSwitchKeys *> &relin_keys, C &destination, std::uint32_t n_baby = 0,
+                      double scale_out = 0.0)
+        {
+            check_bootstrap_operand(encrypted);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            sealhip_evalmod_plan plan{};
+            throw_on(sealhip_evaluator_evalmod_plan(ctx_.get(), std::uint32_t(k), encrypted.scale(), K, r, degree, n_baby, scale_out,
+                                                    &plan));
+            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * std::size_t(plan.out_level) * n);
+            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_eval_mod(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(), K, r, degree, n_baby,
+                                                scale_out, raw ? &raw : nullptr, raw ? 1u : 0u, o.ptr(), nullptr, nullptr));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, plan.out_level);
+            destination.scale() = plan.scales[plan.r];
+        }
+        // The bootstrap in one call (sealhip_evaluator_bootstrap): the destination is at boot.out_level() with the operand's
+        // scale. galois_keys: element -> key, with the keys of boot.key_steps() and of element 2N - 1.
+        template <class C, IfCt<C> = 0>
+        void bootstrap(const C &encrypted, const Bootstrapper &boot, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                       const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
+        {
+            check_bootstrap_operand(encrypted);
+            if (relin_keys.empty() || !relin_keys[0])
+                throw std::invalid_argument("not enough relinearization keys"); // :793-796
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            dft_keys(galois_keys, elts, raw);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * boot.out_level() * n);
+            const sealhip_kswitch_key *relin = relin_keys[0]->get();
+            Check chk = checked(encrypted);
+            throw_on(sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c.ptr(), 1, elts.data(), raw.data(),
+                                                 std::uint32_t(elts.size()), &relin, 1, o.ptr()));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, boot.out_level());
         }
 
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step

@@ -72,6 +72,20 @@ class DftPlan(C.Structure):
                 ("n_key_steps", _u32), ("table_words", _u64), ("temp_bytes_per_item", _u64), ("stages", DftStage * 16)]
 
 
+class EvalModPlan(C.Structure):
+    """sealhip_evalmod_plan (include/sealhip.h)"""
+    _fields_ = [("K", _u32), ("r", _u32), ("degree", _u32), ("n_baby", _u32), ("poly_level", _u32), ("out_level", _u32),
+                ("n_products", _u32), ("reserved", _u32), ("poly_scale_out", C.c_double), ("scales", C.c_double * 9),
+                ("temp_bytes_per_item", _u64)]
+
+
+class BootstrapPlan(C.Structure):
+    """sealhip_bootstrap_plan (include/sealhip.h)"""
+    _fields_ = [("k_top", _u32), ("c2s_out_level", _u32), ("evalmod_out_level", _u32), ("out_level", _u32),
+                ("needs_conjugation", _u32), ("n_key_steps", _u32), ("raise_scale", C.c_double), ("s2c_gain", C.c_double),
+                ("table_words", _u64), ("temp_bytes_per_item", _u64), ("evalmod", EvalModPlan)]
+
+
 DFT_COEFFS_TO_SLOTS, DFT_SLOTS_TO_COEFFS = 0, 1
 
 SYMBOLS = {
@@ -192,6 +206,17 @@ SYMBOLS = {
     "sealhip_dft_tables_stage": [_vp, _u32, C.POINTER(_vp)],
     "sealhip_evaluator_coeffs_to_slots": [_vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_slots_to_coeffs": [_vp, _vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
+    "sealhip_evaluator_mod_raise": [_vp, _u32, _vp, _sz, _u32, _vp],
+    "sealhip_evaluator_double_angle": [_vp, _u32, _vp, _sz, C.c_double, C.POINTER(_vp), _u32, _vp, C.POINTER(C.c_double)],
+    "sealhip_evalmod_coeffs": [_u32, _u32, _u32, C.POINTER(C.c_double)],
+    "sealhip_evaluator_evalmod_plan": [_vp, _u32, C.c_double, _u32, _u32, _u32, _u32, C.c_double, _vp],
+    "sealhip_evaluator_eval_mod": [_vp, _u32, _vp, _sz, C.c_double, _u32, _u32, _u32, _u32, C.c_double, C.POINTER(_vp), _u32, _vp,
+                                   C.POINTER(_u32), C.POINTER(C.c_double)],
+    "sealhip_evaluator_bootstrap_plan": [_vp, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, C.POINTER(_u32), _u32, _u32, _u32, _u32, _vp, C.POINTER(_u32), _u32],
+    "sealhip_bootstrap_tables_create": [_vp, _u32, C.POINTER(_u32), _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, C.POINTER(_u32), _u32, _u32, _u32, _u32, C.POINTER(_vp)],
+    "sealhip_bootstrap_tables_destroy": [_vp],
+    "sealhip_bootstrap_tables_plan": [_vp, _vp],
+    "sealhip_evaluator_bootstrap": [_vp, _vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, C.POINTER(_vp), _u32, _vp],
     "sealhip_decryptor_dot_product_ct_sk": [_vp, _u32, _vp, _u32, _sz, _vp, _i32, _vp],
     "sealhip_decrypt_scale_and_round": [_vp, _u32, _vp, _sz, _vp],
     "sealhip_decryptor_invariant_noise_budget": [_vp, _u32, _vp, _u32, _sz, _vp, _vp],
@@ -1285,6 +1310,80 @@ class Evaluator:
         _check(lib().sealhip_evaluator_slots_to_coeffs(self.ctx.handle, tables.handle, _ptr(ct_re), _ptr(ct_im), count, ea, ka,
                                                        len(elts), _ptr(out)))
 
+    # ---- towards CKKS bootstrapping: ModRaise and the double-angle step
+    def mod_raise(self, ct, k_in, count, k_out, out):
+        """ModRaise (sealhip_evaluator_mod_raise): ct a device batch count x 2 x k_in x N in NTT form, of which only the q_0
+        rows are read; out: count x 2 x k_out x N, the centred coefficients modulo q_0 re-read modulo q_0 .. q_(k_out-1). The
+        result decrypts to m + q_0 I. Both buffers must be 16-byte aligned."""
+        _check(lib().sealhip_evaluator_mod_raise(self.ctx.handle, k_in, _ptr(ct), count, k_out, _ptr(out)))
+
+    def double_angle(self, ct, k, count, scale, relin_keys, out):
+        """out = 2 ct^2 - 1 from level k to k - 1 in one call (sealhip_evaluator_double_angle): ct a device batch
+        count x 2 x k x N at `scale`, 16-byte aligned, out: count x 2 x (k-1) x N. Returns the result's scale, scale * scale / q_(k-1). The words
+        are those of dot_product without keys, linear_combination_levels and relinearize_rescale issued one by one."""
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        out_scale = C.c_double(0.0)
+        _check(lib().sealhip_evaluator_double_angle(self.ctx.handle, k, _ptr(ct), count, scale, keys,
+                                                    len(relin_keys) if relin_keys is not None else 0, _ptr(out),
+                                                    C.byref(out_scale)))
+        return out_scale.value
+
+    def evalmod_plan(self, k, scale, K, r, degree, n_baby=0, scale_out=0.0):
+        """The plan of eval_mod (sealhip_evaluator_evalmod_plan); works on a host-only context. Returns a dict: K, r, degree,
+        n_baby, poly_level, out_level, n_products, poly_scale_out (t_0), scales [s_0 .. s_r], out_scale (s_r),
+        temp_bytes_per_item and coeffs, the Chebyshev coefficients (sealhip_evalmod_coeffs)."""
+        plan = EvalModPlan()
+        _check(lib().sealhip_evaluator_evalmod_plan(self.ctx.handle, k, scale, K, r, degree, n_baby, scale_out,
+                                                    C.addressof(plan)))
+        out = {name: getattr(plan, name) for name, _ in EvalModPlan._fields_ if name not in ("scales", "reserved")}
+        out["scales"] = [float(v) for v in plan.scales[:r + 1]]
+        out["out_scale"] = out["scales"][-1]
+        out["coeffs"] = evalmod_coeffs(K, r, degree)
+        return out
+
+    def eval_mod(self, ct, k, count, scale, K, r, degree, relin_keys, out, n_baby=0, scale_out=0.0):
+        """EvalMod in one call (sealhip_evaluator_eval_mod): ct a device batch count x 2 x k x N whose slots hold
+        x = c / (q_0 K) in [-1, 1] at `scale`; out: count x 2 x out_level x N, slots sin(2 pi K x) (evalmod_plan says which
+        level). Returns (out_level, out_scale)."""
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        level, result_scale = _u32(0), C.c_double(0.0)
+        _check(lib().sealhip_evaluator_eval_mod(self.ctx.handle, k, _ptr(ct), count, scale, K, r, degree, n_baby, scale_out, keys,
+                                                len(relin_keys) if relin_keys is not None else 0, _ptr(out), C.byref(level),
+                                                C.byref(result_scale)))
+        return level.value, result_scale.value
+
+    def bootstrap_plan(self, k_top, c2s_stages, s2c_stages, K, r, degree, n_baby=0, c2s_n_baby=None, s2c_n_baby=None):
+        """The plan of a bootstrap (sealhip_evaluator_bootstrap_plan); works on a host-only context. Returns a dict: k_top,
+        c2s_out_level, evalmod_out_level, out_level, needs_conjugation, raise_scale S = q_0 K, s2c_gain, table_words,
+        temp_bytes_per_item, key_steps (the sorted distinct rotation steps of both transforms: the Galois keys to make, next
+        to element 2N - 1) and evalmod, the dict of evalmod_plan."""
+        args = _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby)
+        plan = BootstrapPlan()
+        fn = lib().sealhip_evaluator_bootstrap_plan
+        _check(fn(self.ctx.handle, *args, C.addressof(plan), None, 0))
+        steps = (_u32 * max(1, plan.n_key_steps))()
+        _check(fn(self.ctx.handle, *args, C.addressof(plan), steps, plan.n_key_steps))
+        out = _bootstrap_plan_dict(plan)
+        out["key_steps"] = [int(v) for v in steps[:plan.n_key_steps]]
+        return out
+
+    def bootstrap(self, tables, ct, k_in, count, galois_keys, relin_keys, out):
+        """Bootstrap in one call (sealhip_evaluator_bootstrap): ct a device batch count x 2 x k_in x N (only the q_0 rows are
+        read); out: count x 2 x tables.plan["out_level"] x N at the input's scale. galois_keys: dict galois_elt ->
+        KSwitchKeys with the plan's key_steps and element 2N - 1; relin_keys: a list of KSwitchKeys (index 0 is read)."""
+        elts = list(galois_keys.keys())
+        ea = (_u32 * max(1, len(elts)))(*elts)
+        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        keys = None
+        if relin_keys is not None:
+            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        _check(lib().sealhip_evaluator_bootstrap(self.ctx.handle, tables.handle, k_in, _ptr(ct), count, ea, ka, len(elts), keys,
+                                                 len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod
     def _host_ptrs(arrays):
@@ -1430,6 +1529,60 @@ class Evaluator:
 
     def transform_from_ntt_inplace(self, ct, size, k, count):
         _check(lib().sealhip_evaluator_transform_from_ntt(self.ctx.handle, k, _ptr(ct), size, count))
+
+
+def evalmod_coeffs(K, r, degree):
+    """The Chebyshev coefficients of cos((2 pi K x - pi / 2) / 2^r) by interpolation at degree + 1 nodes
+    (sealhip_evalmod_coeffs), lowest degree first"""
+    out = (C.c_double * (max(0, int(degree)) + 1))()
+    _check(lib().sealhip_evalmod_coeffs(K, r, degree, out))
+    return [float(v) for v in out]
+
+
+def _u32_list(values):
+    return (_u32 * max(1, len(values)))(*[int(v) for v in values]) if values is not None else None
+
+
+def _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby):
+    for stages, nb in ((c2s_stages, c2s_n_baby), (s2c_stages, s2c_n_baby)):
+        if nb is not None and len(nb) != len(stages):
+            raise ValueError("n_baby and stages differ in length")
+    return (k_top, _u32_list(c2s_stages), len(c2s_stages), _u32_list(c2s_n_baby), _u32_list(s2c_stages), len(s2c_stages),
+            _u32_list(s2c_n_baby), K, r, degree, n_baby)
+
+
+def _bootstrap_plan_dict(plan):
+    out = {name: getattr(plan, name) for name, _ in BootstrapPlan._fields_ if name not in ("evalmod", "n_key_steps")}
+    em = plan.evalmod
+    out["evalmod"] = {name: getattr(em, name) for name, _ in EvalModPlan._fields_ if name not in ("scales", "reserved")}
+    out["evalmod"]["scales"] = [float(v) for v in em.scales[:em.r + 1]]
+    out["evalmod"]["out_scale"] = out["evalmod"]["scales"][-1]
+    return out
+
+
+class BootstrapTables:
+    """sealhip_bootstrap_tables: both transforms' tables, the EvalMod coefficients and the intermediates' pool blocks of
+    one bootstrap shape"""
+
+    def __init__(self, ctx, k_top, c2s_stages, s2c_stages, K, r, degree, n_baby=0, c2s_n_baby=None, s2c_n_baby=None):
+        self.ctx = ctx
+        self.handle = _vp()
+        args = _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby)
+        _check(lib().sealhip_bootstrap_tables_create(ctx.handle, *args, C.byref(self.handle)))
+        plan = BootstrapPlan()
+        _check(lib().sealhip_bootstrap_tables_plan(self.handle, C.addressof(plan)))
+        self.plan = _bootstrap_plan_dict(plan)
+
+    def free(self):
+        if self.handle:
+            _check(lib().sealhip_bootstrap_tables_destroy(self.handle))
+            self.handle = _vp()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _dft_args(direction, k, stages, n_baby):

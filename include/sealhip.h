@@ -705,6 +705,136 @@ long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_t
                                        const uint64_t *ct_im, size_t count, const uint32_t *galois_elts,
                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
 
+/* Towards CKKS bootstrapping: ModRaise and the double-angle step of EvalMod. CKKS only, both modes.
+   The fork has neither; tests/bootstrap_ref.py restates ModRaise over the oracle's transforms.
+
+   mod_raise: a level-1 ciphertext decrypts under s to m(X) modulo q_0. With centre(x) = x for x <= (q_0 - 1) / 2 and
+   x - q_0 otherwise, the centred coefficients of c_0, c_1 mod q_0 are re-read modulo q_0 .. q_(k_out-1); the result decrypts
+   to m + q_0 I for an integer polynomial I with |I_j| <= (h + 1) / 2 when the secret has Hamming weight h.
+   ct: count x 2 x k_in x N in NTT form, not modified. Only the q_0 rows are read (dropping rows is CKKS's mod_switch_to),
+   so any k_in >= 1 is accepted. out: count x 2 x k_out x N, 2 <= k_out <= first level: row 0 of every polynomial is the
+   input's row 0, row i >= 1 is NTT_i(centre(INTT_0(row 0)) mod q_i), canonical. ct and out must be 16-byte aligned.
+   Checks, in this order: NULL pointers -> E_POINTER; then, also on host-only contexts, a BFV context, k_in or k_out outside
+   the ciphertext levels, k_out < 2, out overlapping ct, an operand not 16-byte aligned -> E_INVALIDARG; then count == 0 ->
+   S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION. The 2 N words per ciphertext of temporaries
+   come from the lane's arena, in chunks when the batch exceeds it; nothing synchronises; capturable after one warm-up call
+   at a batch at least as large. With a transparency sink: one flag per output ciphertext, by a read pass over out.
+
+   double_angle: out = 2 ct^2 - 1 for ct at scale `scale`, from level k to k - 1, in one call:
+       (2 c_0^2 - rint(scale^2), 4 c_0 c_1, 2 c_1^2), relinearized with the rescale merged into the key switch's mod-down.
+   *out_scale = scale * scale / (double) q_(k-1), formed in that order in doubles. The words are those of
+   sealhip_evaluator_dot_product({ct}, {ct}) without keys, sealhip_evaluator_linear_combination_levels with weight 2 and the
+   constant rint(-rint(scale * scale)) mod q_r, and sealhip_evaluator_relinearize_rescale, issued one by one; one streaming
+   kernel replaces the first two (2 words read and 3 written per coefficient where they move 11).
+   ct: count x 2 x k x N, not modified; out: count x 2 x (k-1) x N; relin_keys as for sealhip_evaluator_relinearize (required;
+   only index 0 is read). Checks and order are those of sealhip_evaluator_dot_product_rescale, with a scale that is not
+   finite and positive, or whose square is not finite, -> E_INVALIDARG next to the level's, and a ct that is not 16-byte
+   aligned -> E_INVALIDARG after the overlap check (the kernel loads it two words at a time); out_scale is written once the
+   checks have passed, also for an empty batch. Capturable under dot_product_rescale's conditions; with a transparency
+   sink: one flag per output ciphertext, written by the kernel that stores the result. */
+long sealhip_evaluator_mod_raise(sealhip_context *ctx, uint32_t k_in, const uint64_t *ct, size_t count, uint32_t k_out,
+                                 uint64_t *out);
+long sealhip_evaluator_double_angle(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale,
+                                    const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out,
+                                    double *out_scale);
+
+/* EvalMod, the scaled sine of CKKS bootstrapping (csrc/evalmod_plan.hpp). CKKS only, both modes.
+   After ModRaise a coefficient is c = m + q_0 I. K is the caller's bound on I: K >= max|I| + 1, where |I_j| <= (h + 1) / 2
+   for a secret of Hamming weight h (the library does not sample sparse secrets: with its own ternary secrets h is about
+   2 N / 3 and K must be chosen accordingly). For slots holding x = c / (q_0 K) in [-1, 1] at scale `scale`, eval_mod evaluates
+   the degree-`degree` Chebyshev interpolant of cos((2 pi K x - pi / 2) / 2^r) with sealhip_evaluator_evaluate_polynomial_ckks'
+   pipeline and applies sealhip_evaluator_double_angle r times (0 <= r <= 8): the slots then hold sin(2 pi c / q_0) =
+   sin(2 pi m / q_0), which is 2 pi m / q_0 up to the relative error (2 pi m / q_0)^2 / 6 -- |m| / q_0 sets the precision
+   floor of a bootstrapping, whatever the degree.
+   sealhip_evalmod_coeffs: the degree + 1 coefficients (lowest degree first), by interpolation at the Chebyshev nodes with
+   the sums formed in long double; needs no context.
+   sealhip_evaluator_evalmod_plan: works on host-only contexts. With L_0 the polynomial plan's out level for (k, degree,
+   n_baby) -- n_baby as for the polynomial evaluator, 0 its default --, step i = 1 .. r runs at level L_0 - i + 1. The scales
+   are planned backwards, t_r = scale_out (0: scale), t_(i-1) = sqrt(t_i * (double) q_(L_0 - i)); the polynomial is evaluated
+   with scale_out = t_0 (poly_scale_out); scales[0 .. r] are the forward values s_0 = t_0, s_i = s_(i-1) * s_(i-1) /
+   (double) q_(L_0 - i), and scales[r] is the result's scale: scale_out up to |s_r / scale_out - 1| <= 2^(r+3) 2^-53.
+   E_INVALIDARG: a BFV context, k outside the ciphertext levels, K < 1, r > 8, degree < 1 or above 1023, the polynomial
+   plan's refusals, an out level L_0 - r below 1 ("end of modulus switching chain reached"), or a scale s_i or an element's
+   scale of the polynomial plan that is not finite, positive and below 2^62 ("scale out of bounds"): the primes at the EvalMod
+   levels are then too far from `scale` -- they should be near it.
+   sealhip_evaluator_eval_mod: ct: count x 2 x k x N, not modified; out: count x 2 x plan.out_level x N; *out_level and
+   *out_scale (either may be NULL) receive plan.out_level and scales[r]. The words are those of
+   sealhip_evaluator_evaluate_polynomial_ckks with basis 1, the library's coefficients and scale_out = poly_scale_out, followed
+   by r calls of sealhip_evaluator_double_angle at scales[0 .. r-1]. Checks: NULL pointers -> E_POINTER; then, also on
+   host-only contexts, the plan's refusals, missing or short relinearization keys, out overlapping ct -> E_INVALIDARG; then
+   count == 0 -> S_OK; then a host-only context -> COR_E_INVALIDOPERATION. Temporaries (count x plan.temp_bytes_per_item
+   bytes at most) are blocks of the context's pool; NOT capturable, because the polynomial evaluator is not. ct and out need
+   no more than their 8-byte alignment: the double-angle steps read pool blocks. With a transparency sink: one flag per
+   output ciphertext. */
+#define SEALHIP_EVALMOD_MAX_DOUBLINGS 8
+typedef struct sealhip_evalmod_plan
+{
+    uint32_t K, r, degree, n_baby;   /* n_baby: the polynomial plan's baby steps m */
+    uint32_t poly_level, out_level;  /* L_0 and L_0 - r */
+    uint32_t n_products, reserved;   /* key-switched products: the polynomial's and the r steps */
+    double poly_scale_out;           /* t_0 */
+    double scales[SEALHIP_EVALMOD_MAX_DOUBLINGS + 1]; /* s_0 .. s_r, the rest 0 */
+    uint64_t temp_bytes_per_item;
+} sealhip_evalmod_plan;
+long sealhip_evalmod_coeffs(uint32_t K, uint32_t r, uint32_t degree, double *coeffs);
+long sealhip_evaluator_evalmod_plan(const sealhip_context *ctx, uint32_t k, double scale, uint32_t K, uint32_t r, uint32_t degree,
+                                    uint32_t n_baby, double scale_out, sealhip_evalmod_plan *plan);
+long sealhip_evaluator_eval_mod(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, double scale, uint32_t K,
+                                uint32_t r, uint32_t degree, uint32_t n_baby, double scale_out,
+                                const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out,
+                                uint32_t *out_level, double *out_scale);
+
+/* CKKS bootstrapping in one call: bootstrap(ct) takes a ciphertext that has run out of levels and
+   returns one at a usable level with the same scale. Full packing only (sparse packing stays out). The chain is
+       mod_raise to k_top (the raised ciphertext is DECLARED to have scale S = (double) q_0 * K)
+       -> coeffs_to_slots with gain 1: the slots hold x = c / (q_0 K) in [-1, 1]
+       -> eval_mod (K, r, degree, n_baby) ONCE over the 2 count real and imaginary halves, scale_out = S
+       -> slots_to_coeffs with gain (double) q_0 / (2 pi s_r), s_r the scale EvalMod ends at.
+   The output coefficients are m again, so the result has the caller's scale whatever it was: the bootstrap takes no scale
+   argument. K is the caller's bound on the integer polynomial I of ModRaise, K >= max|I| + 1 (see EvalMod above: the library
+   does not sample sparse secrets, and K grows with the secret's Hamming weight). The relative error of the sine step is
+   (2 pi m / q_0)^2 / 6: |m| / q_0 sets the precision floor of the result, next to the CKKS noise of the chain.
+   sealhip_evaluator_bootstrap_plan: works on host-only contexts. c2s_stages / s2c_stages and their optional n_baby lists are
+   sealhip_evaluator_dft_plan's. key_steps as for sealhip_evaluator_dft_plan: the union of both transforms' sorted distinct
+   rotation steps; element 2N - 1 is needed too (needs_conjugation). E_INVALIDARG: either transform's or EvalMod's refusals,
+   an out level below 1.
+   sealhip_bootstrap_tables_create: two sealhip_dft_tables with those gains, the coefficient vector, and (on first use) one
+   block of the context's pool per calling thread for the intermediates -- count x plan.temp_bytes_per_item bytes, CoeffToSlot's
+   out_re and out_im contiguous in it; a larger batch takes a larger block, _destroy releases all of them. Synchronises; not
+   capturable; destroy the tables before their context and not during a graph capture (COR_E_INVALIDOPERATION).
+   sealhip_evaluator_bootstrap: ct: count x 2 x k_in x N in NTT form (only its q_0 rows are read), out: count x 2 x
+   plan.out_level x N, both 16-byte aligned. galois_elts / galois_keys as for sealhip_evaluator_coeffs_to_slots; relin_keys
+   as for sealhip_evaluator_relinearize. Checks: NULL pointers -> E_POINTER; then, also on host-only contexts (where the
+   first always applies, tables being made on a device), tables made on another context, k_in outside the ciphertext levels, a pointer not 16-byte aligned, a step or element 2N - 1 whose key is
+   absent ("Galois key not present"), a key with fewer digits than its level needs, missing relinearization keys, out
+   overlapping ct -> E_INVALIDARG; then count == 0 -> S_OK; then a host-only context -> COR_E_INVALIDOPERATION. NOT
+   capturable (EvalMod is not). With a transparency sink: one flag per output ciphertext, by a read pass over out. */
+typedef struct sealhip_bootstrap_plan
+{
+    uint32_t k_top, c2s_out_level, evalmod_out_level, out_level; /* the level after each part */
+    uint32_t needs_conjugation, n_key_steps;
+    double raise_scale;           /* S = (double) q_0 * K */
+    double s2c_gain;              /* (double) q_0 / (2 pi s_r) */
+    uint64_t table_words;         /* device words of both transforms' tables */
+    uint64_t temp_bytes_per_item; /* the intermediates the tables hold, per ciphertext (the parts' own workspaces come on top) */
+    sealhip_evalmod_plan evalmod;
+} sealhip_bootstrap_plan;
+typedef struct sealhip_bootstrap_tables sealhip_bootstrap_tables;
+long sealhip_evaluator_bootstrap_plan(const sealhip_context *ctx, uint32_t k_top, const uint32_t *c2s_stages, uint32_t n_c2s,
+                                      const uint32_t *c2s_n_baby, const uint32_t *s2c_stages, uint32_t n_s2c,
+                                      const uint32_t *s2c_n_baby, uint32_t K, uint32_t r, uint32_t degree, uint32_t n_baby,
+                                      sealhip_bootstrap_plan *plan, uint32_t *key_steps, uint32_t key_steps_capacity);
+long sealhip_bootstrap_tables_create(sealhip_context *ctx, uint32_t k_top, const uint32_t *c2s_stages, uint32_t n_c2s,
+                                     const uint32_t *c2s_n_baby, const uint32_t *s2c_stages, uint32_t n_s2c,
+                                     const uint32_t *s2c_n_baby, uint32_t K, uint32_t r, uint32_t degree, uint32_t n_baby,
+                                     sealhip_bootstrap_tables **tables);
+long sealhip_bootstrap_tables_destroy(sealhip_bootstrap_tables *tables);
+long sealhip_bootstrap_tables_plan(const sealhip_bootstrap_tables *tables, sealhip_bootstrap_plan *plan);
+long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in, const uint64_t *ct,
+                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                 uint32_t n_keys, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                                 uint64_t *out);
+
 /* Linear combinations of ciphertexts with scalar weights, both schemes, both modes:
        out_s = sum_{i < n_terms} W[s][i] * X_i  (+ K[s] on c_0)      for s < n_sums
    formed by one streaming kernel that loads every operand word once per tile of 4 sums: no transforms, no lifted plaintexts,
