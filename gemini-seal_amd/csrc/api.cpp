@@ -165,6 +165,41 @@ namespace
             return fail(SEALHIP_E_POINTER, #p " is null");         \
     } while (0)
 
+// The pointer checks of the key lists, by the parameter names every entry uses. A Galois list of n entries (an empty one
+// may be null): the two arrays alone (the rotate_vector entries look keys up by step); every key as well; every key but
+// those of element 1, the identity, which needs none. The relinearization list: required, or optional (null = no key).
+#define REQUIRE_GALOIS_LIST(n)        \
+    do                                \
+    {                                 \
+        if (n)                        \
+        {                             \
+            REQUIRE_PTR(galois_elts); \
+            REQUIRE_PTR(galois_keys); \
+        }                             \
+    } while (0)
+#define REQUIRE_GALOIS_KEYS_WHERE(n, needed)  \
+    do                                       \
+    {                                        \
+        REQUIRE_GALOIS_LIST(n);              \
+        for (uint32_t i = 0; i < (n); i++)   \
+            if (needed)                      \
+                REQUIRE_PTR(galois_keys[i]); \
+    } while (0)
+#define REQUIRE_GALOIS_KEYS(n) REQUIRE_GALOIS_KEYS_WHERE(n, true)
+#define REQUIRE_GALOIS_KEYS_BUT_IDENTITY(n) REQUIRE_GALOIS_KEYS_WHERE(n, galois_elts[i] != 1)
+#define REQUIRE_RELIN_KEYS_IF_ANY()         \
+    do                                      \
+    {                                       \
+        if (relin_keys && n_relin_keys)     \
+            REQUIRE_PTR(relin_keys[0]);     \
+    } while (0)
+#define REQUIRE_RELIN_KEYS()         \
+    do                               \
+    {                                \
+        REQUIRE_PTR(relin_keys);     \
+        REQUIRE_RELIN_KEYS_IF_ANY(); \
+    } while (0)
+
     Engine &device_engine(sealhip_context *ctx)
     {
         Engine &e = *ctx->engine;
@@ -1392,11 +1427,7 @@ long sealhip_evaluator_rotate_vector_host(sealhip_context *ctx, uint32_t k, uint
     REQUIRE_PTR(ctx);
     if (count)
         REQUIRE_PTR(ct);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-    }
+    REQUIRE_GALOIS_LIST(n_keys);
     return guarded([&] {
         Engine &e = device_engine(ctx);
         check_level(e, k);
@@ -1775,11 +1806,7 @@ long sealhip_evaluator_rotate_vector(sealhip_context *ctx, uint32_t k, uint64_t 
 {
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(ct);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-    }
+    REQUIRE_GALOIS_LIST(n_keys);
     return guarded([&] {
         Engine &e = device_engine(ctx);
         // (the NAF fallback applies several automorphisms: the flags are read off the final ciphertext)
@@ -1850,13 +1877,7 @@ long sealhip_evaluator_apply_galois_many(sealhip_context *ctx, uint32_t k, const
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out);
-    if (n_elts)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-        for (uint32_t i = 0; i < n_elts; i++)
-            REQUIRE_PTR(galois_keys[i]);
-    }
+    REQUIRE_GALOIS_KEYS(n_elts);
     return guarded([&] {
         const std::vector<uint32_t> elts(galois_elts, galois_elts + n_elts);
         for (uint32_t elt : elts)
@@ -1876,11 +1897,7 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
     REQUIRE_PTR(out);
     if (n_steps)
         REQUIRE_PTR(steps);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-    }
+    REQUIRE_GALOIS_LIST(n_keys);
     return guarded([&] {
         Engine &h = *ctx->engine;
         check_data_level(h, k);
@@ -1899,9 +1916,7 @@ long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, con
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out);
-    REQUIRE_PTR(relin_keys);
-    if (n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS();
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
@@ -1996,14 +2011,7 @@ namespace
         REQUIRE_PTR(ct);
         REQUIRE_PTR(plain_ntt);
         REQUIRE_PTR(out);
-        if (n_elts)
-        {
-            REQUIRE_PTR(galois_elts);
-            REQUIRE_PTR(galois_keys);
-            for (uint32_t i = 0; i < n_elts; i++)
-                if (galois_elts[i] != 1)
-                    REQUIRE_PTR(galois_keys[i]);
-        }
+        REQUIRE_GALOIS_KEYS_BUT_IDENTITY(n_elts);
         return guarded([&] {
             do_apply_galois_dot_plain(ctx, k, ct, count, std::vector<uint32_t>(galois_elts, galois_elts + n_elts),
                                       std::vector<const sealhip_kswitch_key *>(galois_keys, galois_keys + n_elts), plain_ntt,
@@ -2022,11 +2030,7 @@ namespace
         REQUIRE_PTR(out);
         if (n_steps)
             REQUIRE_PTR(steps);
-        if (n_keys)
-        {
-            REQUIRE_PTR(galois_elts);
-            REQUIRE_PTR(galois_keys);
-        }
+        REQUIRE_GALOIS_LIST(n_keys);
         return guarded([&] {
             Engine &h = *ctx->engine;
             rescale ? check_rescale_level(h, k) : check_data_level(h, k);
@@ -2150,11 +2154,7 @@ long rotate_vector_bsgs_plain_entry(sealhip_context *ctx, bool rescale, uint32_t
         REQUIRE_PTR(baby_steps);
     if (n_giant)
         REQUIRE_PTR(giant_steps);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-    }
+    REQUIRE_GALOIS_LIST(n_keys);
     return guarded([&] {
         Engine &h = *ctx->engine;
         rescale ? check_rescale_level(h, k) : check_data_level(h, k);
@@ -2256,15 +2256,38 @@ namespace
         }
     }
 
-    // the tables' context is the caller's: another ring's tables would be read with the wrong strides
-    void check_dft_tables(const sealhip_context *ctx, const sealhip_dft_tables *tables)
+    // the tables' context is the caller's: another ring's tables would be read with the wrong strides. kind: "DFT", "bootstrap"
+    void check_tables_context(const sealhip_context *ctx, const Engine *made_on, const char *kind)
     {
-        if (dft_tables_engine(*tables->tables) != ctx->engine.get())
-            throw std::invalid_argument("the DFT tables were made on another context");
+        if (made_on != ctx->engine.get())
+            throw std::invalid_argument(std::string("the ") + kind + " tables were made on another context");
     }
 
-    // what the split and merge kernels load and store 16 bytes at a time
-    void check_dft_aligned(const void *p, const char *name)
+    // "<entry> synchronises": refused during a graph capture; else a handle that `fill` completes, freed if it throws
+    template <class Handle, class Fill>
+    Handle *create_tables_outside_capture(Engine &e, const char *entry, Fill fill)
+    {
+        if (e.lane().capturing)
+            throw std::logic_error(std::string(entry) + " synchronises: it cannot be captured");
+        std::unique_ptr<Handle> t(new Handle);
+        fill(*t);
+        return t.release();
+    }
+
+    // a plan entry's two calls: key_steps null = the plan alone, which says how many steps there are; else the steps too
+    template <class WritePlan>
+    void plan_with_key_steps(const std::vector<uint32_t> &steps, uint32_t *key_steps, uint32_t key_steps_capacity,
+                             WritePlan write_plan)
+    {
+        if (key_steps && key_steps_capacity < steps.size())
+            throw std::invalid_argument("key_steps is too small");
+        write_plan();
+        if (key_steps)
+            std::copy(steps.begin(), steps.end(), key_steps);
+    }
+
+    // what a kernel loads or stores 16 bytes at a time (the DFT's split and merge, ModRaise, the double angle's square)
+    void check_aligned16(const void *p, const char *name)
     {
         if (reinterpret_cast<std::uintptr_t>(p) & 15)
             throw std::invalid_argument(std::string(name) + " must be 16-byte aligned");
@@ -2295,6 +2318,21 @@ namespace
         }
         return all;
     }
+
+    // the key of element 2N - 1 out of the caller's key list, checked for a key switch at `level`
+    const KSwitchKey &conjugation_key(const Engine &h, uint32_t level, const uint32_t *galois_elts,
+                                      const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys)
+    {
+        const uint32_t conj_elt = static_cast<uint32_t>(2 * h.n - 1);
+        const sealhip_kswitch_key *conj = nullptr;
+        for (uint32_t i = 0; i < n_keys && !conj; i++)
+            if (galois_elts[i] == conj_elt)
+                conj = galois_keys[i];
+        if (!conj)
+            throw std::invalid_argument("Galois key not present");
+        check_key_digits(h, level, conj);
+        return conj->key;
+    }
 } // namespace
 } // extern "C++"
 
@@ -2305,11 +2343,7 @@ long sealhip_evaluator_dft_plan(const sealhip_context *ctx, uint32_t direction, 
     REQUIRE_PTR(plan);
     return guarded([&] {
         const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
-        if (key_steps && key_steps_capacity < p.key_steps.size())
-            throw std::invalid_argument("key_steps is too small");
-        dft_plan_to_abi(p, plan);
-        if (key_steps)
-            std::copy(p.key_steps.begin(), p.key_steps.end(), key_steps);
+        plan_with_key_steps(p.key_steps, key_steps, key_steps_capacity, [&] { dft_plan_to_abi(p, plan); });
     });
 }
 
@@ -2367,11 +2401,8 @@ long sealhip_dft_tables_create(sealhip_context *ctx, uint32_t direction, uint32_
         const dftplan::Plan p = dft_make_plan(*ctx->engine, direction, k, stages, n_stages, n_baby);
         check_dft_gain(gain);
         Engine &e = device_engine(ctx);
-        if (e.lane().capturing)
-            throw std::logic_error("sealhip_dft_tables_create synchronises: it cannot be captured");
-        std::unique_ptr<sealhip_dft_tables> t(new sealhip_dft_tables);
-        t->tables = dft_tables_create(e, p, gain);
-        *tables = t.release();
+        *tables = create_tables_outside_capture<sealhip_dft_tables>(
+            e, "sealhip_dft_tables_create", [&](sealhip_dft_tables &t) { t.tables = dft_tables_create(e, p, gain); });
     });
 }
 
@@ -2411,30 +2442,17 @@ long sealhip_evaluator_coeffs_to_slots(sealhip_context *ctx, const sealhip_dft_t
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out_re);
     REQUIRE_PTR(out_im);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-        for (uint32_t i = 0; i < n_keys; i++)
-            REQUIRE_PTR(galois_keys[i]);
-    }
+    REQUIRE_GALOIS_KEYS(n_keys);
     return guarded([&] {
         Engine &h = *ctx->engine;
         const dftplan::Plan &p = dft_tables_plan(*tables->tables);
-        check_dft_tables(ctx, tables);
-        check_dft_aligned(out_re, "out_re");
-        check_dft_aligned(out_im, "out_im");
+        check_tables_context(ctx, dft_tables_engine(*tables->tables), "DFT");
+        check_aligned16(out_re, "out_re");
+        check_aligned16(out_im, "out_im");
         if (p.direction != dftplan::kCoeffsToSlots)
             throw std::invalid_argument("the tables were made for slots_to_coeffs");
         const std::vector<DftStageKeys> keys = dft_stage_keys(h, p, galois_elts, galois_keys, n_keys);
-        const uint32_t conj_elt = static_cast<uint32_t>(2 * h.n - 1);
-        const sealhip_kswitch_key *conj = nullptr;
-        for (uint32_t i = 0; i < n_keys && !conj; i++)
-            if (galois_elts[i] == conj_elt)
-                conj = galois_keys[i];
-        if (!conj)
-            throw std::invalid_argument("Galois key not present");
-        check_key_digits(h, p.out_level, conj);
+        const KSwitchKey &conj = conjugation_key(h, p.out_level, galois_elts, galois_keys, n_keys);
         const std::size_t in_words = count * 2 * p.in_level * h.n, out_words = count * 2 * p.out_level * h.n;
         const u64 *in = reinterpret_cast<const u64 *>(ct);
         u64 *re = reinterpret_cast<u64 *>(out_re), *im = reinterpret_cast<u64 *>(out_im);
@@ -2446,7 +2464,7 @@ long sealhip_evaluator_coeffs_to_slots(sealhip_context *ctx, const sealhip_dft_t
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, 2 * count);
-        op_coeffs_to_slots(e, *tables->tables, in, count, keys, conj->key, re, im);
+        op_coeffs_to_slots(e, *tables->tables, in, count, keys, conj, re, im);
         const std::size_t poly = static_cast<std::size_t>(p.out_level) * h.n;
         sink.read_pass(re, 2, poly, count);
         if (sink.on)
@@ -2463,19 +2481,13 @@ long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_t
     REQUIRE_PTR(ct_re);
     REQUIRE_PTR(ct_im);
     REQUIRE_PTR(out);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-        for (uint32_t i = 0; i < n_keys; i++)
-            REQUIRE_PTR(galois_keys[i]);
-    }
+    REQUIRE_GALOIS_KEYS(n_keys);
     return guarded([&] {
         Engine &h = *ctx->engine;
         const dftplan::Plan &p = dft_tables_plan(*tables->tables);
-        check_dft_tables(ctx, tables);
-        check_dft_aligned(ct_re, "ct_re");
-        check_dft_aligned(ct_im, "ct_im");
+        check_tables_context(ctx, dft_tables_engine(*tables->tables), "DFT");
+        check_aligned16(ct_re, "ct_re");
+        check_aligned16(ct_im, "ct_im");
         if (p.direction != dftplan::kSlotsToCoeffs)
             throw std::invalid_argument("the tables were made for coeffs_to_slots");
         const std::vector<DftStageKeys> keys = dft_stage_keys(h, p, galois_elts, galois_keys, n_keys);
@@ -2513,8 +2525,8 @@ long sealhip_evaluator_mod_raise(sealhip_context *ctx, uint32_t k_in, const uint
         u64 *o = reinterpret_cast<u64 *>(out);
         if (words_overlap(o, count * 2 * k_out * h.n, in, count * 2 * k_in * h.n))
             throw std::invalid_argument("out must not overlap ct");
-        check_dft_aligned(ct, "ct");
-        check_dft_aligned(out, "out");
+        check_aligned16(ct, "ct");
+        check_aligned16(out, "out");
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
@@ -2532,9 +2544,7 @@ long sealhip_evaluator_double_angle(sealhip_context *ctx, uint32_t k, const uint
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out);
     REQUIRE_PTR(out_scale);
-    REQUIRE_PTR(relin_keys);
-    if (n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS();
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
@@ -2548,7 +2558,7 @@ long sealhip_evaluator_double_angle(sealhip_context *ctx, uint32_t k, const uint
         u64 *o = reinterpret_cast<u64 *>(out);
         if (words_overlap(o, count * 2 * (poly - h.n), in, count * 2 * poly))
             throw std::invalid_argument("out must not overlap an operand");
-        check_dft_aligned(ct, "ct"); // (square_affine_kernel loads it two words at a time)
+        check_aligned16(ct, "ct"); // (square_affine_kernel loads it two words at a time)
         std::vector<u64> constant(k);
         for (uint32_t r = 0; r < k; r++)
             constant[r] = polyplan::rint_residue(-std::nearbyint(square), h.key_moduli[r]);
@@ -2594,8 +2604,7 @@ long dot_product_entry(sealhip_context *ctx, uint32_t k, const uint64_t *const *
             REQUIRE_PTR(b_terms[i]);
         }
     }
-    if (relin_keys && n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS_IF_ANY();
     return guarded([&] {
         // The checks that need no device come first and run on host-only contexts too (the order the header documents).
         Engine &h = *ctx->engine;
@@ -2746,8 +2755,7 @@ long sealhip_evaluator_evaluate_polynomial(sealhip_context *ctx, uint32_t k, con
     REQUIRE_PTR(ct);
     REQUIRE_PTR(coeffs);
     REQUIRE_PTR(out);
-    if (relin_keys && n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS_IF_ANY();
     return guarded([&] {
         Engine &h = *ctx->engine;
         check_data_level(h, k);
@@ -2794,6 +2802,30 @@ namespace
         plan->out_scale = p.scale_out;
         plan->temp_bytes_per_item = ckks_poly_temp_words(p, N) * sizeof(u64);
     }
+
+    // What evaluate_polynomial_ckks and eval_mod do once they have their plan: the relinearization key if the plan has a
+    // product, `out` at the plan's level against `ct` at k, the plan's level and scale reported, and op(e, x, key, o, sink).
+    template <class Op>
+    void planned_ckks_run(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, bool needs_key,
+                          const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys, uint64_t *out,
+                          uint32_t plan_level, double plan_scale, uint32_t *out_level, double *out_scale, Op op)
+    {
+        Engine &h = *ctx->engine;
+        const KSwitchKey *key = needs_key ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr;
+        const u64 *x = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * plan_level * h.n, x, count * 2 * k * h.n))
+            throw std::invalid_argument("out must not overlap ct");
+        if (out_level)
+            *out_level = plan_level;
+        if (out_scale)
+            *out_scale = plan_scale;
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op(e, x, key, o, sink);
+    }
 } // namespace
 } // extern "C++"
 
@@ -2825,25 +2857,15 @@ long sealhip_evaluator_evaluate_polynomial_ckks(sealhip_context *ctx, uint32_t k
     REQUIRE_PTR(ct);
     REQUIRE_PTR(coeffs);
     REQUIRE_PTR(out);
-    if (relin_keys && n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS_IF_ANY();
     return guarded([&] {
         Engine &h = *ctx->engine;
         const polyplan::Plan p = ckks_poly_plan(h, k, scale, coeffs, degree, basis, n_baby, scale_out, true);
-        const KSwitchKey *key = p.d >= 2 ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr; // (d = 1: no product)
-        const u64 *x = reinterpret_cast<const u64 *>(ct);
-        u64 *o = reinterpret_cast<u64 *>(out);
-        if (words_overlap(o, count * 2 * p.out_level * h.n, x, count * 2 * k * h.n))
-            throw std::invalid_argument("out must not overlap ct");
-        if (out_level)
-            *out_level = static_cast<uint32_t>(p.out_level);
-        if (out_scale)
-            *out_scale = p.scale_out;
-        if (count == 0)
-            return;
-        Engine &e = device_engine(ctx);
-        SinkScope sink(e, count);
-        op_evaluate_polynomial_ckks(e, p, k, x, count, key, o, sink);
+        planned_ckks_run(ctx, k, ct, count, p.d >= 2 /* (d = 1: no product) */, relin_keys, n_relin_keys, out,
+                         static_cast<uint32_t>(p.out_level), p.scale_out, out_level, out_scale,
+                         [&](Engine &e, const u64 *x, const KSwitchKey *key, u64 *o, SinkScope &sink) {
+                             op_evaluate_polynomial_ckks(e, p, k, x, count, key, o, sink);
+                         });
     });
 }
 
@@ -2903,25 +2925,15 @@ long sealhip_evaluator_eval_mod(sealhip_context *ctx, uint32_t k, const uint64_t
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out);
-    if (relin_keys && n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_RELIN_KEYS_IF_ANY();
     return guarded([&] {
         Engine &h = *ctx->engine;
         const evalmod::Plan p = evalmod_make_plan(h, k, scale, K, r, degree, n_baby, scale_out, true);
-        const KSwitchKey *key = (p.poly.d >= 2 || r > 0) ? first_relin_key(h, k, relin_keys, n_relin_keys) : nullptr;
-        const u64 *x = reinterpret_cast<const u64 *>(ct);
-        u64 *o = reinterpret_cast<u64 *>(out);
-        if (words_overlap(o, count * 2 * p.out_level * h.n, x, count * 2 * k * h.n))
-            throw std::invalid_argument("out must not overlap ct");
-        if (out_level)
-            *out_level = static_cast<uint32_t>(p.out_level);
-        if (out_scale)
-            *out_scale = p.scales.back();
-        if (count == 0)
-            return;
-        Engine &e = device_engine(ctx);
-        SinkScope sink(e, count);
-        op_eval_mod(e, p, k, x, count, key, o, sink);
+        planned_ckks_run(ctx, k, ct, count, p.poly.d >= 2 || r > 0, relin_keys, n_relin_keys, out,
+                         static_cast<uint32_t>(p.out_level), p.scales.back(), out_level, out_scale,
+                         [&](Engine &e, const u64 *x, const KSwitchKey *key, u64 *o, SinkScope &sink) {
+                             op_eval_mod(e, p, k, x, count, key, o, sink);
+                         });
     });
 }
 
@@ -2992,11 +3004,7 @@ long sealhip_evaluator_bootstrap_plan(const sealhip_context *ctx, uint32_t k_top
         Engine &h = *ctx->engine;
         const BootPlan b = boot_make_plan(h, k_top, c2s_stages, n_c2s, c2s_n_baby, s2c_stages, n_s2c, s2c_n_baby, K, r, degree,
                                           n_baby, false);
-        if (key_steps && key_steps_capacity < b.key_steps.size())
-            throw std::invalid_argument("key_steps is too small");
-        boot_plan_to_abi(h, b, plan);
-        if (key_steps)
-            std::copy(b.key_steps.begin(), b.key_steps.end(), key_steps);
+        plan_with_key_steps(b.key_steps, key_steps, key_steps_capacity, [&] { boot_plan_to_abi(h, b, plan); });
     });
 }
 
@@ -3013,12 +3021,11 @@ long sealhip_bootstrap_tables_create(sealhip_context *ctx, uint32_t k_top, const
                                           n_baby, true);
         check_dft_gain(b.s2c_gain);
         Engine &e = device_engine(ctx);
-        if (e.lane().capturing)
-            throw std::logic_error("sealhip_bootstrap_tables_create synchronises: it cannot be captured");
-        std::unique_ptr<sealhip_bootstrap_tables> t(new sealhip_bootstrap_tables);
-        boot_plan_to_abi(h, b, &t->plan);
-        t->tables = bootstrap_tables_create(e, k_top, b.c2s, b.em, b.s2c, b.s2c_gain);
-        *tables = t.release();
+        *tables = create_tables_outside_capture<sealhip_bootstrap_tables>(
+            e, "sealhip_bootstrap_tables_create", [&](sealhip_bootstrap_tables &t) {
+                boot_plan_to_abi(h, b, &t.plan);
+                t.tables = bootstrap_tables_create(e, k_top, b.c2s, b.em, b.s2c, b.s2c_gain);
+            });
     });
 }
 
@@ -3047,34 +3054,19 @@ long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_t
     REQUIRE_PTR(tables);
     REQUIRE_PTR(ct);
     REQUIRE_PTR(out);
-    if (n_keys)
-    {
-        REQUIRE_PTR(galois_elts);
-        REQUIRE_PTR(galois_keys);
-        for (uint32_t i = 0; i < n_keys; i++)
-            REQUIRE_PTR(galois_keys[i]);
-    }
-    if (relin_keys && n_relin_keys)
-        REQUIRE_PTR(relin_keys[0]);
+    REQUIRE_GALOIS_KEYS(n_keys);
+    REQUIRE_RELIN_KEYS_IF_ANY();
     return guarded([&] {
         Engine &h = *ctx->engine;
         const BootstrapTables &t = *tables->tables;
-        if (bootstrap_tables_engine(t) != ctx->engine.get())
-            throw std::invalid_argument("the bootstrap tables were made on another context");
+        check_tables_context(ctx, bootstrap_tables_engine(t), "bootstrap");
         check_data_level(h, k_in);
-        check_dft_aligned(ct, "ct");
-        check_dft_aligned(out, "out");
+        check_aligned16(ct, "ct");
+        check_aligned16(out, "out");
         const dftplan::Plan &c2s = dft_tables_plan(bootstrap_tables_c2s(t)), &s2c = dft_tables_plan(bootstrap_tables_s2c(t));
         const std::vector<DftStageKeys> c2s_keys = dft_stage_keys(h, c2s, galois_elts, galois_keys, n_keys);
         const std::vector<DftStageKeys> s2c_keys = dft_stage_keys(h, s2c, galois_elts, galois_keys, n_keys);
-        const uint32_t conj_elt = static_cast<uint32_t>(2 * h.n - 1);
-        const sealhip_kswitch_key *conj = nullptr;
-        for (uint32_t i = 0; i < n_keys && !conj; i++)
-            if (galois_elts[i] == conj_elt)
-                conj = galois_keys[i];
-        if (!conj)
-            throw std::invalid_argument("Galois key not present");
-        check_key_digits(h, c2s.out_level, conj);
+        const KSwitchKey &conj = conjugation_key(h, c2s.out_level, galois_elts, galois_keys, n_keys);
         const KSwitchKey *relin = first_relin_key(h, c2s.out_level, relin_keys, n_relin_keys);
         const u64 *in = reinterpret_cast<const u64 *>(ct);
         u64 *o = reinterpret_cast<u64 *>(out);
@@ -3084,7 +3076,7 @@ long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_t
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
-        op_bootstrap(e, t, static_cast<int>(k_in), in, count, c2s_keys, conj->key, s2c_keys, *relin, o);
+        op_bootstrap(e, t, static_cast<int>(k_in), in, count, c2s_keys, conj, s2c_keys, *relin, o);
         sink.read_pass(o, 2, static_cast<std::size_t>(s2c.out_level) * h.n, count);
     });
 }

@@ -1,11 +1,8 @@
 // bootstrap.cpp -- CKKS bootstrapping as one call: ModRaise, CoeffToSlot, EvalMod over both halves at
 // once, SlotToCoeff. The plans are homdft_plan.hpp's and evalmod_plan.hpp's; the argument checks are the ABI entries'
-// (api.cpp). The intermediates are one block of the context's pool per lane that the tables hold, under the rule of the
-// DFT tables (homdft.cpp): a larger batch takes a larger block, the earlier ones stay held, destroy releases all of them.
+// (api.cpp). The intermediates are one block of the context's pool per lane that the tables hold, under the rule of
+// held_workspace.hpp: a larger batch takes a larger block, the earlier ones stay held, destroy releases all of them.
 #include "../../include/sealhip.h"
-
-#include <map>
-#include <mutex>
 
 #include "engine.hpp"
 #include "evalmod_plan.hpp"
@@ -20,26 +17,7 @@ namespace sealhip
         std::uint32_t k_top = 0;
         evalmod::Plan evalmod;
         DftTables *c2s = nullptr, *s2c = nullptr;
-        struct Block
-        {
-            void *p;
-            std::size_t bytes;
-        };
-        mutable std::mutex mu;
-        mutable std::map<const Lane *, std::vector<Block>> blocks;
-        char *workspace(const Engine &e, std::size_t bytes) const
-        {
-            Lane &l = e.lane();
-            std::lock_guard<std::mutex> lock(mu);
-            std::vector<Block> &v = blocks[&l];
-            if (!v.empty() && v.back().bytes >= bytes)
-                return static_cast<char *>(v.back().p);
-            if (l.capturing)
-                throw std::logic_error("the bootstrap's workspace would be allocated during a graph capture");
-            void *p = pool_alloc(e, bytes);
-            v.push_back(Block{ p, bytes });
-            return static_cast<char *>(p);
-        }
+        mutable HeldWorkspace<Engine> held;
     };
 
     // per ciphertext: the raised input at k_top, CoeffToSlot's two outputs, EvalMod's two outputs
@@ -72,23 +50,12 @@ namespace sealhip
 
     void bootstrap_tables_destroy(BootstrapTables *t)
     {
-        if (!t)
-            return;
-        const Engine &e = *t->engine;
-        if (e.lane().capturing)
-            throw std::logic_error("bootstrap tables cannot be destroyed during a graph capture");
-        int current = -1;
-        (void)hipGetDevice(&current);
-        SEALHIP_CHECK(hipSetDevice(t->device));
-        for (auto &lane : t->blocks)
-            for (BootstrapTables::Block &b : lane.second)
-                pool_release(e, b.p);
-        t->blocks.clear();
-        dft_tables_destroy(t->c2s);
-        dft_tables_destroy(t->s2c);
-        delete t;
-        if (current >= 0 && current != e.device)
-            (void)hipSetDevice(current);
+        if (t)
+            destroy_held_tables(t, "bootstrap tables cannot be destroyed during a graph capture", [t] {
+                dft_tables_destroy(t->c2s);
+                dft_tables_destroy(t->s2c);
+                delete t;
+            });
     }
 
     const Engine *bootstrap_tables_engine(const BootstrapTables &t)
@@ -113,11 +80,12 @@ namespace sealhip
         const std::size_t N = e.n;
         const std::size_t w_top = count * 2 * t.k_top * N, w_slots = count * 2 * c2s.out_level * N,
                           w_sine = count * 2 * static_cast<std::size_t>(em.out_level) * N;
-        char *ws = t.workspace(e, (w_top + 2 * w_slots + 2 * w_sine) * sizeof(u64) + 3 * 256);
-        const auto pad = [](std::size_t words) { return (words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255); };
-        u64 *raised = reinterpret_cast<u64 *>(ws);
-        u64 *slots = reinterpret_cast<u64 *>(ws + pad(w_top));                   // re, then im: ONE batch of 2 count items
-        u64 *sine = reinterpret_cast<u64 *>(ws + pad(w_top) + pad(2 * w_slots)); // likewise
+        Lane &l = e.lane();
+        Carver ws{ t.held.get(e, &l, l.capturing, (w_top + 2 * w_slots + 2 * w_sine) * sizeof(u64) + 3 * 256,
+                              "the bootstrap's workspace would be allocated during a graph capture") };
+        u64 *raised = ws.take(w_top);
+        u64 *slots = ws.take(2 * w_slots); // re, then im: ONE batch of 2 count items
+        u64 *sine = ws.take(2 * w_sine);   // likewise
         op_mod_raise(e, k_in, ct, count, static_cast<int>(t.k_top), raised);
         op_coeffs_to_slots(e, *t.c2s, raised, count, c2s_keys, conj_key, slots, slots + w_slots);
         {

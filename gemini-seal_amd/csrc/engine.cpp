@@ -1049,7 +1049,7 @@ namespace sealhip
     u64 *Engine::ws_alloc(std::size_t words) const
     {
         Lane &l = lane();
-        const std::size_t bytes = (words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255);
+        const std::size_t bytes = pad256(words);
         if (l.ws_used + bytes > l.ws_bytes)
             throw std::logic_error("internal: workspace overflow");
         u64 *p = reinterpret_cast<u64 *>(static_cast<char *>(l.ws) + l.ws_used);

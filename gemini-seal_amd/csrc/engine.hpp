@@ -20,6 +20,7 @@
 #include "ntt_bounds.hpp"
 #include "hostmath.hpp"
 #include "pool_scratch.hpp"
+#include "held_workspace.hpp"
 struct sealhip_kswitch_key; // the C ABI's key handle (api.cpp)
 
 namespace sealhip
@@ -443,6 +444,24 @@ namespace sealhip
         if (err != hipSuccess)
             throw HipError(err, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
     }
+
+    // `words` u64 words in a workspace: their bytes, up to the next 256-byte boundary
+    inline std::size_t pad256(std::size_t words)
+    {
+        return (words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255);
+    }
+    // a block cut into buffers that each start at a 256-byte step
+    struct Carver
+    {
+        char *base;
+        std::size_t at = 0;
+        u64 *take(std::size_t words)
+        {
+            u64 *p = reinterpret_cast<u64 *>(base + at);
+            at += pad256(words);
+            return p;
+        }
+    };
 
     // Launch shape of the elementwise kernels: kThreads lanes per block, one block per kThreads work items up to
     // max_blocks; the kernels grid-stride the rest.
@@ -1053,6 +1072,23 @@ namespace sealhip
     double dft_stage_gain(const dftplan::Plan &p, std::size_t stage, double gain);
     void dft_stage_values_host(const Engine &h, const dftplan::Plan &p, std::size_t stage, double gain, double *values);
     void op_dft_stage_values(Engine &e, const dftplan::Plan &p, std::size_t stage, double gain, double *values);
+    // The end of tables that hold a workspace (held_workspace.hpp) next to `engine` and `device`: refused during a graph
+    // capture with the owner's text; else the blocks go back to the pool on the calling thread's lane, `rest` frees what
+    // else the tables own and the tables themselves, and the caller's current device is left as it was.
+    template <class Tables, class Rest>
+    void destroy_held_tables(Tables *t, const char *refusal, Rest rest)
+    {
+        const Engine &e = *t->engine;
+        if (e.lane().capturing)
+            throw std::logic_error(refusal);
+        int current = -1;
+        (void)hipGetDevice(&current);
+        SEALHIP_CHECK(hipSetDevice(t->device));
+        t->held.release_all(e);
+        rest();
+        if (current >= 0 && current != e.device)
+            (void)hipSetDevice(current);
+    }
     struct DftTables; // the plan and, per stage, plain_ntt[n_giant][n_baby][n_key][N] in device memory
     DftTables *dft_tables_create(Engine &e, const dftplan::Plan &p, double gain);
     void dft_tables_destroy(DftTables *t);

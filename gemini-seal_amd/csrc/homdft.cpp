@@ -2,16 +2,13 @@
 // restatement, the tables (values -> op_ckks_encode at the key level), and CoeffToSlot / SlotToCoeff as chains of
 // op_apply_galois_bsgs_plain with the merged rescale around the split and merge kernels. The plan is homdft_plan.hpp's; the
 // argument checks are the ABI entries' (api.cpp). A transform's temporaries are blocks of the context's pool (pool.cpp) that
-// the tables hold, one current block per lane, grown on demand and given back when the tables are destroyed: after one call
-// at a batch size the next makes no allocator call and can be captured, and a captured graph stays valid when a larger
-// batch takes a larger block later, because the earlier one stays held. (Not a Scratch per call: a pool block cannot be
-// released during a capture. Not the lane arena under ws_floor: see DESIGN.md section 23.)
+// the tables hold under the rule of held_workspace.hpp: one current block per lane, grown on demand, the earlier ones held
+// until the tables are destroyed. (Not a Scratch per call: a pool block cannot be released during a capture. Not the lane
+// arena under ws_floor: see DESIGN.md section 23.)
 #include "../../include/sealhip.h"
 
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "engine.hpp"
 #include "homdft_entry.hpp"
@@ -25,30 +22,16 @@ namespace sealhip
         int device = -1;
         std::vector<u64 *> stage; // device, [n_giant][n_baby][n_key][N] each
         const Engine *engine = nullptr; // the context the tables were made on: its ring, its pool, its lanes
-        // per lane, the pool blocks a transform's temporaries were given: the last is current, the earlier ones stay held
-        // until the tables go (graphs captured on them may still be replayed). A context's lanes live as long as the
-        // context (LanePool owns them and hands the lane of a thread that exited to the next one), and the tables are
-        // destroyed before it, so the key cannot dangle.
-        struct Block
-        {
-            void *p;
-            std::size_t bytes;
-        };
-        mutable std::mutex mu;
-        mutable std::map<const Lane *, std::vector<Block>> blocks;
-        char *workspace(const Engine &e, std::size_t bytes) const
+        // a transform's temporaries, keyed by the lane. A context's lanes live as long as the context (LanePool owns them and
+        // hands the lane of a thread that exited to the next one), and the tables are destroyed before it, so the key
+        // cannot dangle.
+        mutable HeldWorkspace<Engine> held;
+        Carver workspace(const Engine &e, std::size_t bytes) const
         {
             Lane &l = e.lane();
-            std::lock_guard<std::mutex> lock(mu);
-            std::vector<Block> &v = blocks[&l];
-            if (!v.empty() && v.back().bytes >= bytes)
-                return static_cast<char *>(v.back().p);
-            if (l.capturing)
-                throw std::logic_error("the transform's workspace would be allocated during a graph capture: run the call once "
-                                       "before capturing");
-            void *p = pool_alloc(e, bytes);
-            v.push_back(Block{ p, bytes });
-            return static_cast<char *>(p);
+            return Carver{ held.get(e, &l, l.capturing, bytes,
+                                    "the transform's workspace would be allocated during a graph capture: run the call once "
+                                    "before capturing") };
         }
         ~DftTables()
         {
@@ -150,21 +133,8 @@ namespace sealhip
     // caller's current device is left as it was
     void dft_tables_destroy(DftTables *t)
     {
-        if (!t)
-            return;
-        const Engine &e = *t->engine;
-        if (e.lane().capturing)
-            throw std::logic_error("DFT tables cannot be destroyed during a graph capture");
-        int current = -1;
-        (void)hipGetDevice(&current);
-        SEALHIP_CHECK(hipSetDevice(t->device));
-        for (auto &lane : t->blocks)
-            for (DftTables::Block &b : lane.second)
-                pool_release(e, b.p);
-        t->blocks.clear();
-        delete t;
-        if (current >= 0 && current != e.device)
-            (void)hipSetDevice(current);
+        if (t)
+            destroy_held_tables(t, "DFT tables cannot be destroyed during a graph capture", [t] { delete t; });
     }
 
     const Engine *dft_tables_engine(const DftTables &t)
@@ -184,14 +154,6 @@ namespace sealhip
 
     namespace
     {
-        // `words` u64 words at a 256-byte boundary of the workspace; `at` moves past them
-        u64 *carve(char *base, std::size_t &at, std::size_t words)
-        {
-            u64 *p = reinterpret_cast<u64 *>(base + at);
-            at += (words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255);
-            return p;
-        }
-
         // stage st of the chain: in at the stage's level -> out one level below
         void run_stage(Engine &e, const DftTables &t, std::size_t st, const DftStageKeys &k, const u64 *in, std::size_t count,
                        u64 *out)
@@ -208,10 +170,9 @@ namespace sealhip
         const dftplan::Plan &p = t.plan;
         const std::size_t n_stages = p.stages.size(), N = e.n;
         const std::size_t wide = count * 2 * (p.in_level - 1) * N, low = count * 2 * p.out_level * N;
-        char *ws = t.workspace(e, (wide * sizeof(u64) + 256) * (n_stages >= 2 ? 2 : 1) + low * sizeof(u64) + 256);
-        std::size_t at = 0;
-        u64 *buf[2] = { carve(ws, at, wide), n_stages >= 2 ? carve(ws, at, wide) : nullptr };
-        u64 *conj = carve(ws, at, low);
+        Carver ws = t.workspace(e, (wide * sizeof(u64) + 256) * (n_stages >= 2 ? 2 : 1) + low * sizeof(u64) + 256);
+        u64 *buf[2] = { ws.take(wide), n_stages >= 2 ? ws.take(wide) : nullptr };
+        u64 *conj = ws.take(low);
         const u64 *cur = ct;
         for (std::size_t st = 0; st < n_stages; st++)
         {
@@ -231,10 +192,9 @@ namespace sealhip
         const std::size_t n_stages = p.stages.size(), N = e.n;
         const std::size_t wide = count * 2 * (p.in_level - 1) * N, top = count * 2 * p.in_level * N;
         const std::size_t n_wide = n_stages >= 3 ? 2 : n_stages - 1;
-        char *ws = t.workspace(e, top * sizeof(u64) + 256 + (wide * sizeof(u64) + 256) * n_wide);
-        std::size_t at = 0;
-        u64 *merged = carve(ws, at, top);
-        u64 *buf[2] = { n_stages >= 2 ? carve(ws, at, wide) : nullptr, n_stages >= 3 ? carve(ws, at, wide) : nullptr };
+        Carver ws = t.workspace(e, top * sizeof(u64) + 256 + (wide * sizeof(u64) + 256) * n_wide);
+        u64 *merged = ws.take(top);
+        u64 *buf[2] = { n_stages >= 2 ? ws.take(wide) : nullptr, n_stages >= 3 ? ws.take(wide) : nullptr };
         check(launch_dft_merge(e, ct_re, ct_im, merged, count, e.map_for(static_cast<int>(p.in_level), SEALHIP_BASE_Q)), "dft merge");
         const u64 *cur = merged;
         for (std::size_t st = 0; st < n_stages; st++)

@@ -52,11 +52,6 @@ namespace sealhip
             return l.ws_budget = std::min(hi, std::max(lo, (free_b + l.ws_bytes) / 6));
         }
 
-        std::size_t pad256(std::size_t words)
-        {
-            return ((words * sizeof(u64) + 255) & ~static_cast<std::size_t>(255));
-        }
-
         // one (length, entries per pass) pair of Lane::chunk_log, the oldest of 64 dropped
         void log_chunk(Engine &e, std::size_t length, std::size_t per_pass)
         {

@@ -610,12 +610,47 @@ namespace sealhip_host
         sealhip_kswitch_key *key_ = nullptr;
     };
 
+    // What HomomorphicDFT and Bootstrapper share: the tables' handle (destroyed with the object, not copyable), the plan and
+    // its key steps. plan_entry(plan, key_steps, capacity) is the ABI's plan entry over the owner's arguments, called
+    // twice (the plan says how many steps there are); create(tables) its create entry. The plan comes first: its
+    // refusals need no device.
+    template <class Tables, class Plan, long (*Destroy)(Tables *)>
+    class PlannedTables
+    {
+    public:
+        ~PlannedTables()
+        {
+            if (tables_)
+                Destroy(tables_);
+        }
+        PlannedTables(const PlannedTables &) = delete;
+        PlannedTables &operator=(const PlannedTables &) = delete;
+        const Tables *get() const { return tables_; }
+        const Plan &plan() const { return plan_; }
+        std::size_t out_level() const { return plan_.out_level; }
+        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
+
+    protected:
+        PlannedTables() = default;
+        template <class PlanEntry, class Create>
+        void make(PlanEntry plan_entry, Create create)
+        {
+            throw_on(plan_entry(&plan_, nullptr, 0));
+            key_steps_.resize(plan_.n_key_steps);
+            throw_on(plan_entry(&plan_, key_steps_.data(), plan_.n_key_steps));
+            throw_on(create(&tables_));
+        }
+        Tables *tables_ = nullptr;
+        Plan plan_{};
+        std::vector<std::uint32_t> key_steps_;
+    };
+
     // The plan and the device tables of one homomorphic DFT (sealhip_dft_tables_create): CoeffToSlot
     // (SEALHIP_DFT_COEFFS_TO_SLOTS) or SlotToCoeff (SEALHIP_DFT_SLOTS_TO_COEFFS) for ciphertexts at level k, as the stages
     // `stages` (layer counts in application order, summing to log2(N/2)). Evaluator::coeffs_to_slots / slots_to_coeffs take
     // it; the result is n_stages levels lower at the same scale. key_steps(): the rotation steps whose Galois keys the
     // client must make (CoeffToSlot also needs the key of element 2N - 1).
-    class HomomorphicDFT
+    class HomomorphicDFT : public PlannedTables<sealhip_dft_tables, sealhip_dft_plan, sealhip_dft_tables_destroy>
     {
     public:
         HomomorphicDFT(const Context &c, std::uint32_t direction, std::size_t k, const std::vector<std::uint32_t> &stages,
@@ -625,31 +660,15 @@ namespace sealhip_host
                 throw std::invalid_argument("n_baby and stages differ in length");
             const std::uint32_t *nb = n_baby.empty() ? nullptr : n_baby.data();
             const std::uint32_t n_stages = std::uint32_t(stages.size());
-            // (the plan first: its refusals need no device)
-            throw_on(sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, &plan_, nullptr, 0));
-            key_steps_.resize(plan_.n_key_steps);
-            throw_on(sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, &plan_,
-                                                key_steps_.data(), plan_.n_key_steps));
-            throw_on(sealhip_dft_tables_create(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, gain, &tables_));
+            const auto plan_entry = [&](sealhip_dft_plan *p, std::uint32_t *steps, std::uint32_t capacity) {
+                return sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, p, steps, capacity);
+            };
+            make(plan_entry, [&](sealhip_dft_tables **t) {
+                return sealhip_dft_tables_create(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, gain, t);
+            });
         }
-        ~HomomorphicDFT()
-        {
-            if (tables_)
-                sealhip_dft_tables_destroy(tables_);
-        }
-        HomomorphicDFT(const HomomorphicDFT &) = delete;
-        HomomorphicDFT &operator=(const HomomorphicDFT &) = delete;
-        const sealhip_dft_tables *get() const { return tables_; }
-        const sealhip_dft_plan &plan() const { return plan_; }
         std::uint32_t direction() const { return plan_.direction; }
         std::size_t in_level() const { return plan_.in_level; }
-        std::size_t out_level() const { return plan_.out_level; }
-        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
-
-    private:
-        sealhip_dft_tables *tables_ = nullptr;
-        sealhip_dft_plan plan_{};
-        std::vector<std::uint32_t> key_steps_;
     };
 
     // The plan and the device tables of one bootstrap shape (sealhip_bootstrap_tables_create):
@@ -658,7 +677,7 @@ namespace sealhip_host
     // does not sample sparse secrets. Evaluator::bootstrap takes it; the result is at out_level() with the operand's scale,
     // its precision bounded by |m| / q_0 (the sine step's relative error is (2 pi m / q_0)^2 / 6). key_steps(): the rotation
     // steps whose Galois keys the client must make, next to the key of element 2N - 1.
-    class Bootstrapper
+    class Bootstrapper : public PlannedTables<sealhip_bootstrap_tables, sealhip_bootstrap_plan, sealhip_bootstrap_tables_destroy>
     {
     public:
         Bootstrapper(const Context &c, std::size_t k_top, const std::vector<std::uint32_t> &c2s_stages,
@@ -666,32 +685,15 @@ namespace sealhip_host
                      std::uint32_t n_baby = 0)
         {
             const std::uint32_t n1 = std::uint32_t(c2s_stages.size()), n2 = std::uint32_t(s2c_stages.size());
-            // (the plan first: its refusals need no device)
-            throw_on(sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
-                                                      s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &plan_, nullptr, 0));
-            key_steps_.resize(plan_.n_key_steps);
-            throw_on(sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
-                                                      s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &plan_,
-                                                      key_steps_.data(), plan_.n_key_steps));
-            throw_on(sealhip_bootstrap_tables_create(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
-                                                     s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, &tables_));
+            const auto plan_entry = [&](sealhip_bootstrap_plan *p, std::uint32_t *steps, std::uint32_t capacity) {
+                return sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
+                                                        s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, p, steps, capacity);
+            };
+            make(plan_entry, [&](sealhip_bootstrap_tables **t) {
+                return sealhip_bootstrap_tables_create(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
+                                                       s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, t);
+            });
         }
-        ~Bootstrapper()
-        {
-            if (tables_)
-                sealhip_bootstrap_tables_destroy(tables_);
-        }
-        Bootstrapper(const Bootstrapper &) = delete;
-        Bootstrapper &operator=(const Bootstrapper &) = delete;
-        const sealhip_bootstrap_tables *get() const { return tables_; }
-        const sealhip_bootstrap_plan &plan() const { return plan_; }
-        std::size_t out_level() const { return plan_.out_level; }
-        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
-
-    private:
-        sealhip_bootstrap_tables *tables_ = nullptr;
-        sealhip_bootstrap_plan plan_{};
-        std::vector<std::uint32_t> key_steps_;
     };
 
     template <class CT>
@@ -1484,16 +1486,12 @@ namespace sealhip_host
                 throw std::invalid_argument("encrypted size must be 2");
             if (coeffs.empty())
                 throw std::invalid_argument("coeffs must not be empty");
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n;
-            Dev c = dev_in(encrypted, words), o = dev_out(words);
-            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_evaluate_polynomial(ctx_.get(), std::uint32_t(k), c.ptr(), 1, coeffs.data(),
-                                                           std::uint32_t(coeffs.size() - 1), 0, raw ? &raw : nullptr, raw ? 1u : 0u,
-                                                           o.ptr()));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, k);
+            const std::size_t k = encrypted.coeff_modulus_size();
+            const sealhip_kswitch_key *raw = first_relin_key_or_null(relin_keys);
+            to_size2(encrypted, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_evaluate_polynomial(ctx_.get(), std::uint32_t(k), c, 1, coeffs.data(),
+                                                             std::uint32_t(coeffs.size() - 1), 0, raw ? &raw : nullptr, raw ? 1u : 0u, o);
+            });
         }
         template <class C, IfCt<C> = 0>
         void evaluate_polynomial_inplace(C &encrypted, const std::vector<std::uint64_t> &coeffs,
@@ -1521,21 +1519,17 @@ namespace sealhip_host
                 throw std::invalid_argument("encrypted size must be 2");
             if (coeffs.empty())
                 throw std::invalid_argument("coeffs must not be empty");
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            const std::size_t k = encrypted.coeff_modulus_size();
             sealhip_poly_plan plan{};
             throw_on(sealhip_evaluator_polynomial_plan_ckks(ctx_.get(), std::uint32_t(k), encrypted.scale(), coeffs.data(),
                                                             std::uint32_t(coeffs.size() - 1), basis, 0, scale_out, &plan, nullptr,
                                                             nullptr));
-            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * std::size_t(plan.out_level) * n);
-            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_evaluate_polynomial_ckks(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(),
-                                                                coeffs.data(), std::uint32_t(coeffs.size() - 1), basis, 0, scale_out,
-                                                                raw ? &raw : nullptr, raw ? 1u : 0u, o.ptr(), nullptr, nullptr));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, plan.out_level);
-            destination.scale() = plan.out_scale;
+            const sealhip_kswitch_key *raw = first_relin_key_or_null(relin_keys);
+            to_size2(encrypted, 2, plan.out_level, destination, &plan.out_scale, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_evaluate_polynomial_ckks(ctx_.get(), std::uint32_t(k), c, 1, encrypted.scale(), coeffs.data(),
+                                                                  std::uint32_t(coeffs.size() - 1), basis, 0, scale_out,
+                                                                  raw ? &raw : nullptr, raw ? 1u : 0u, o, nullptr, nullptr);
+            });
         }
         template <class C, IfCt<C> = 0>
         void evaluate_polynomial_inplace(C &encrypted, const std::vector<double> &coeffs,
@@ -1555,18 +1549,12 @@ namespace sealhip_host
             if (encrypted.size() != 3)
                 throw std::invalid_argument("encrypted size must be 3");
             check_rescale_operand(encrypted);
-            if (relin_keys.empty() || !relin_keys[0])
-                throw std::invalid_argument("not enough relinearization keys"); // :793-796
+            const sealhip_kswitch_key *raw = first_relin_key(relin_keys);
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
             const double scale = encrypted.scale() / double(ctx_.key_modulus(k - 1));
-            Dev c = dev_in(encrypted, 3 * k * n), o = dev_out(2 * (k - 1) * n);
-            const sealhip_kswitch_key *raw = relin_keys[0]->get();
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_relinearize_rescale(ctx_.get(), std::uint32_t(k), c.ptr(), 3, 3 * k * n, 1, &raw, 1, o.ptr()));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, k - 1);
-            destination.scale() = scale;
+            to_size2(encrypted, 3, k - 1, destination, &scale, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_relinearize_rescale(ctx_.get(), std::uint32_t(k), c, 3, 3 * k * n, 1, &raw, 1, o);
+            });
         }
 
         // ---- CKKS bootstrapping and its parts; size-2 operands in NTT form
@@ -1577,36 +1565,26 @@ namespace sealhip_host
         void mod_raise(const C &encrypted, std::size_t k_out, C &destination)
         {
             check_bootstrap_operand(encrypted);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            const std::size_t k = encrypted.coeff_modulus_size();
             if (k_out < 2)
                 throw std::invalid_argument("k_out must be at least 2");
-            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * k_out * n);
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_mod_raise(ctx_.get(), std::uint32_t(k), c.ptr(), 1, std::uint32_t(k_out), o.ptr()));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, k_out);
+            to_size2(encrypted, 2, k_out, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_mod_raise(ctx_.get(), std::uint32_t(k), c, 1, std::uint32_t(k_out), o);
+            });
         }
         // destination = 2 encrypted^2 - 1, one level down, at the scale scale^2 / q_(k-1) (sealhip_evaluator_double_angle)
         template <class C, IfCt<C> = 0>
         void double_angle(const C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
             check_bootstrap_operand(encrypted);
-            if (relin_keys.empty() || !relin_keys[0])
-                throw std::invalid_argument("not enough relinearization keys"); // :793-796
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            const sealhip_kswitch_key *raw = first_relin_key(relin_keys);
+            const std::size_t k = encrypted.coeff_modulus_size();
             if (k < 2)
                 throw std::invalid_argument("end of modulus switching chain reached");
-            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * (k - 1) * n);
-            const sealhip_kswitch_key *raw = relin_keys[0]->get();
-            double scale = 0.0;
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_double_angle(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(), &raw, 1, o.ptr(),
-                                                    &scale));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, k - 1);
-            destination.scale() = scale;
+            double scale = 0.0; // (the entry reports it)
+            to_size2(encrypted, 2, k - 1, destination, &scale, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_double_angle(ctx_.get(), std::uint32_t(k), c, 1, encrypted.scale(), &raw, 1, o, &scale);
+            });
         }
         // EvalMod (sealhip_evaluator_eval_mod): slots x = c / (q_0 K) in [-1, 1] become sin(2 pi K x); the destination gets
         // the plan's level and scale (sealhip_evaluator_evalmod_plan), scale_out or the operand's scale up to rounding
@@ -1616,19 +1594,15 @@ namespace sealhip_host
                       double scale_out = 0.0)
         {
             check_bootstrap_operand(encrypted);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
+            const std::size_t k = encrypted.coeff_modulus_size();
             sealhip_evalmod_plan plan{};
             throw_on(sealhip_evaluator_evalmod_plan(ctx_.get(), std::uint32_t(k), encrypted.scale(), K, r, degree, n_baby, scale_out,
                                                     &plan));
-            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * std::size_t(plan.out_level) * n);
-            const sealhip_kswitch_key *raw = !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_eval_mod(ctx_.get(), std::uint32_t(k), c.ptr(), 1, encrypted.scale(), K, r, degree, n_baby,
-                                                scale_out, raw ? &raw : nullptr, raw ? 1u : 0u, o.ptr(), nullptr, nullptr));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, plan.out_level);
-            destination.scale() = plan.scales[plan.r];
+            const sealhip_kswitch_key *raw = first_relin_key_or_null(relin_keys);
+            to_size2(encrypted, 2, plan.out_level, destination, &plan.scales[plan.r], [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_eval_mod(ctx_.get(), std::uint32_t(k), c, 1, encrypted.scale(), K, r, degree, n_baby,
+                                                  scale_out, raw ? &raw : nullptr, raw ? 1u : 0u, o, nullptr, nullptr);
+            });
         }
         // The bootstrap in one call (sealhip_evaluator_bootstrap): the destination is at boot.out_level() with the operand's
         // scale. galois_keys: element -> key, with the keys of boot.key_steps() and of element 2N - 1.
@@ -1637,20 +1611,15 @@ namespace sealhip_host
                        const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
             check_bootstrap_operand(encrypted);
-            if (relin_keys.empty() || !relin_keys[0])
-                throw std::invalid_argument("not enough relinearization keys"); // :793-796
+            const sealhip_kswitch_key *relin = first_relin_key(relin_keys);
             std::vector<std::uint32_t> elts;
             std::vector<const sealhip_kswitch_key *> raw;
             dft_keys(galois_keys, elts, raw);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n();
-            Dev c = dev_in(encrypted, 2 * k * n), o = dev_out(2 * boot.out_level() * n);
-            const sealhip_kswitch_key *relin = relin_keys[0]->get();
-            Check chk = checked(encrypted);
-            throw_on(sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c.ptr(), 1, elts.data(), raw.data(),
-                                                 std::uint32_t(elts.size()), &relin, 1, o.ptr()));
-            chk.done();
-            take_meta(destination, encrypted);
-            commit(destination, o, 2, boot.out_level());
+            const std::size_t k = encrypted.coeff_modulus_size();
+            to_size2(encrypted, 2, boot.out_level(), destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(), raw.data(),
+                                                   std::uint32_t(elts.size()), &relin, 1, o);
+            });
         }
 
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
@@ -2072,6 +2041,35 @@ namespace sealhip_host
         };
         Check checked(const CT &, std::size_t = 1) { return Check(); }
         Check checked(const DeviceCiphertext &, std::size_t count = 1) { return Check(ctx_, this, count); }
+
+        // One operand of in_size polynomials in, one size-2 result at level k_out out: call(in, out) is the ABI entry over
+        // the two device blocks. The destination (which may be the operand) takes the operand's metadata, the result's
+        // words and, where `scale` is not null, that scale, read after the call.
+        template <class C, class Call>
+        void to_size2(const C &encrypted, std::size_t in_size, std::size_t k_out, C &destination, const double *scale, Call call)
+        {
+            const std::size_t n = ctx_.n();
+            Dev c = dev_in(encrypted, in_size * encrypted.coeff_modulus_size() * n), o = dev_out(2 * k_out * n);
+            Check chk = checked(encrypted);
+            throw_on(call(c.ptr(), o.ptr()));
+            chk.done();
+            take_meta(destination, encrypted);
+            commit(destination, o, 2, k_out);
+            if (scale)
+                destination.scale() = *scale;
+        }
+
+        // relin_keys as relinearize_inplace takes them, of which index 0 is read: required (:793-796), or null without one
+        static const sealhip_kswitch_key *first_relin_key(const std::vector<const KSwitchKeys *> &relin_keys)
+        {
+            if (relin_keys.empty() || !relin_keys[0])
+                throw std::invalid_argument("not enough relinearization keys");
+            return relin_keys[0]->get();
+        }
+        static const sealhip_kswitch_key *first_relin_key_or_null(const std::vector<const KSwitchKeys *> &relin_keys)
+        {
+            return !relin_keys.empty() && relin_keys[0] ? relin_keys[0]->get() : nullptr;
+        }
 
         // the n results of a hoisted rotation, back to back in `o`, become the destinations (metadata of the operand)
         // (k: the level of the results when it is not the operand's -- the *_rescale methods)

@@ -1042,10 +1042,8 @@ class Evaluator:
 
     def rotate_vector_native(self, ct, k, count, steps, galois_keys):
         """The same rotate_internal logic behind the C ABI (sealhip_evaluator_rotate_vector)."""
-        elts = list(galois_keys.keys())
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(lib().sealhip_evaluator_rotate_vector(self.ctx.handle, k, _ptr(ct), count, steps, ea, ka, len(elts)))
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_rotate_vector(self.ctx.handle, k, _ptr(ct), count, steps, ea, ka, n_keys))
 
     def apply_galois_many(self, ct, k, count, elts, keys, out):
         """Hoisted rotation (sealhip_evaluator_apply_galois_many): `count` size-2 ciphertexts under every Galois element of
@@ -1060,11 +1058,9 @@ class Evaluator:
         """The same by rotation steps (sealhip_evaluator_rotate_vector_many): out: len(steps) x count x 2 x k x N; step 0
         copies the input, a step without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
         steps = [int(st) for st in steps]
-        elts = list(galois_keys.keys())
         sa = (_i32 * max(1, len(steps)))(*steps)
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts),
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, n_keys,
                                                           _ptr(out)))
 
     def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out,
@@ -1083,11 +1079,9 @@ class Evaluator:
         """The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): step 0 is the identity and needs no key; a
         step without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
         steps = [int(st) for st in steps]
-        elts = list(galois_keys.keys())
         sa = (_i32 * max(1, len(steps)))(*steps)
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, len(elts), _ptr(plains),
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, n_keys, _ptr(plains),
                                       n_sums, _ptr(out)))
 
     def apply_galois_bsgs_plain(self, ct, k, count, baby_elts, baby_keys, giant_elts, giant_keys, plains, out,
@@ -1109,13 +1103,11 @@ class Evaluator:
         """The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): step 0 is the identity and needs no key; a
         step of either axis without its key in galois_keys (dict galois_elt -> KSwitchKeys) raises ValueError."""
         baby_steps, giant_steps = [int(st) for st in baby_steps], [int(st) for st in giant_steps]
-        elts = list(galois_keys.keys())
         bs = (_i32 * max(1, len(baby_steps)))(*baby_steps)
         gs = (_i32 * max(1, len(giant_steps)))(*giant_steps)
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(getattr(lib(), _entry)(self.ctx.handle, k, _ptr(ct), count, bs, len(baby_steps), gs, len(giant_steps), ea, ka,
-                                      len(elts), _ptr(plains), _ptr(out)))
+                                      n_keys, _ptr(plains), _ptr(out)))
 
     def dot_product_max_terms(self, k):
         """Terms one dot_product call admits at level k (sealhip_evaluator_dot_product_max_terms): for BFV as many as keep the
@@ -1133,11 +1125,9 @@ class Evaluator:
             raise ValueError("a_terms and b_terms differ in length")
         pa = (_vp * max(1, len(a_terms)))(*[_ptr(c) for c in a_terms])
         pb = (_vp * max(1, len(b_terms)))(*[_ptr(c) for c in b_terms])
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        keys, n_relin = _relin_array(relin_keys)
         _check(getattr(lib(), _entry)(self.ctx.handle, k, pa, pb, len(a_terms), count, keys,
-                                      len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+                                      n_relin, _ptr(out)))
 
     def linear_combination(self, terms, weights, k, count, out, size=2, n_sums=1, constant=None):
         """Linear combinations with scalar weights (sealhip_evaluator_linear_combination):
@@ -1195,13 +1185,11 @@ class Evaluator:
         if not coeffs:
             raise ValueError("coeffs must not be empty")
         ca = (C.c_double * len(coeffs))(*coeffs)
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        keys, n_relin = _relin_array(relin_keys)
         level, result_scale = _u32(0), C.c_double(0.0)
         _check(lib().sealhip_evaluator_evaluate_polynomial_ckks(self.ctx.handle, k, _ptr(ct), count, scale, ca, len(coeffs) - 1,
                                                                 basis, n_baby, scale_out, keys,
-                                                                len(relin_keys) if relin_keys is not None else 0, _ptr(out),
+                                                                n_relin, _ptr(out),
                                                                 C.byref(level), C.byref(result_scale)))
         return level.value, result_scale.value
 
@@ -1214,11 +1202,9 @@ class Evaluator:
         if not coeffs:
             raise ValueError("coeffs must not be empty")
         ca = (C.c_uint64 * len(coeffs))(*coeffs)
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        keys, n_relin = _relin_array(relin_keys)
         _check(lib().sealhip_evaluator_evaluate_polynomial(self.ctx.handle, k, _ptr(ct), count, ca, len(coeffs) - 1, n_baby, keys,
-                                                           len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+                                                           n_relin, _ptr(out)))
 
     # ---- the key switch's mod-down merged with rescale_to_next: CKKS, operands at level k >= 2, every
     # out at level k - 1; the words are those of tests/ks_rescale_ref.py, the error that of the unmerged method + rescale_to_next
@@ -1262,13 +1248,9 @@ class Evaluator:
         (the sorted distinct non-zero rotation steps: the Galois keys to make) and stages, a list of dicts s0, r, h0, level,
         n_baby, n_giant, folded, scale, baby_steps, giant_steps."""
         args = _dft_args(direction, k, stages, n_baby)
-        plan = DftPlan()
-        fn = lib().sealhip_evaluator_dft_plan
-        _check(fn(self.ctx.handle, *args, C.addressof(plan), None, 0))
-        steps = (_u32 * max(1, plan.n_key_steps))()
-        _check(fn(self.ctx.handle, *args, C.addressof(plan), steps, plan.n_key_steps))
+        plan, key_steps = _plan_with_key_steps(lib().sealhip_evaluator_dft_plan, DftPlan, self.ctx.handle, *args)
         out = _dft_plan_dict(plan)
-        out["key_steps"] = [int(v) for v in steps[:plan.n_key_steps]]
+        out["key_steps"] = key_steps
         for t, st in enumerate(out["stages"]):
             bs, gs = (_i32 * st["n_baby"])(), (_i32 * st["n_giant"])()
             _check(lib().sealhip_dft_stage_steps(self.ctx.handle, *args, t, bs, gs))
@@ -1295,20 +1277,16 @@ class Evaluator:
         level; out_re, out_im: count x 2 x tables.out_level x N, slot j of them m_(bitrev j) and m_(bitrev j + N/2) over the
         scale, which is unchanged. galois_keys: dict galois_elt -> KSwitchKeys with the plan's key_steps and element 2N - 1;
         a missing one raises ValueError."""
-        elts = list(galois_keys.keys())
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        _check(lib().sealhip_evaluator_coeffs_to_slots(self.ctx.handle, tables.handle, _ptr(ct), count, ea, ka, len(elts),
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_coeffs_to_slots(self.ctx.handle, tables.handle, _ptr(ct), count, ea, ka, n_keys,
                                                        _ptr(out_re), _ptr(out_im)))
 
     def slots_to_coeffs(self, tables, ct_re, ct_im, count, galois_keys, out):
         """SlotToCoeff in one call (sealhip_evaluator_slots_to_coeffs): ct_re, ct_im device batches count x 2 x k x N in
         coeffs_to_slots' bit-reversed slot order; out: count x 2 x tables.out_level x N; the scale is unchanged."""
-        elts = list(galois_keys.keys())
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(lib().sealhip_evaluator_slots_to_coeffs(self.ctx.handle, tables.handle, _ptr(ct_re), _ptr(ct_im), count, ea, ka,
-                                                       len(elts), _ptr(out)))
+                                                       n_keys, _ptr(out)))
 
     # ---- towards CKKS bootstrapping: ModRaise and the double-angle step (DESIGN.md section 24)
     def mod_raise(self, ct, k_in, count, k_out, out):
@@ -1321,12 +1299,10 @@ class Evaluator:
         """out = 2 ct^2 - 1 from level k to k - 1 in one call (sealhip_evaluator_double_angle): ct a device batch
         count x 2 x k x N at `scale`, 16-byte aligned, out: count x 2 x (k-1) x N. Returns the result's scale, scale * scale / q_(k-1). The words
         are those of dot_product without keys, linear_combination_levels and relinearize_rescale issued one by one."""
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        keys, n_relin = _relin_array(relin_keys)
         out_scale = C.c_double(0.0)
         _check(lib().sealhip_evaluator_double_angle(self.ctx.handle, k, _ptr(ct), count, scale, keys,
-                                                    len(relin_keys) if relin_keys is not None else 0, _ptr(out),
+                                                    n_relin, _ptr(out),
                                                     C.byref(out_scale)))
         return out_scale.value
 
@@ -1337,9 +1313,7 @@ class Evaluator:
         plan = EvalModPlan()
         _check(lib().sealhip_evaluator_evalmod_plan(self.ctx.handle, k, scale, K, r, degree, n_baby, scale_out,
                                                     C.addressof(plan)))
-        out = {name: getattr(plan, name) for name, _ in EvalModPlan._fields_ if name not in ("scales", "reserved")}
-        out["scales"] = [float(v) for v in plan.scales[:r + 1]]
-        out["out_scale"] = out["scales"][-1]
+        out = _evalmod_plan_dict(plan)
         out["coeffs"] = evalmod_coeffs(K, r, degree)
         return out
 
@@ -1347,12 +1321,10 @@ class Evaluator:
         """EvalMod in one call (sealhip_evaluator_eval_mod): ct a device batch count x 2 x k x N whose slots hold
         x = c / (q_0 K) in [-1, 1] at `scale`; out: count x 2 x out_level x N, slots sin(2 pi K x) (evalmod_plan says which
         level). Returns (out_level, out_scale)."""
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
+        keys, n_relin = _relin_array(relin_keys)
         level, result_scale = _u32(0), C.c_double(0.0)
         _check(lib().sealhip_evaluator_eval_mod(self.ctx.handle, k, _ptr(ct), count, scale, K, r, degree, n_baby, scale_out, keys,
-                                                len(relin_keys) if relin_keys is not None else 0, _ptr(out), C.byref(level),
+                                                n_relin, _ptr(out), C.byref(level),
                                                 C.byref(result_scale)))
         return level.value, result_scale.value
 
@@ -1362,27 +1334,19 @@ class Evaluator:
         temp_bytes_per_item, key_steps (the sorted distinct rotation steps of both transforms: the Galois keys to make, next
         to element 2N - 1) and evalmod, the dict of evalmod_plan."""
         args = _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby)
-        plan = BootstrapPlan()
-        fn = lib().sealhip_evaluator_bootstrap_plan
-        _check(fn(self.ctx.handle, *args, C.addressof(plan), None, 0))
-        steps = (_u32 * max(1, plan.n_key_steps))()
-        _check(fn(self.ctx.handle, *args, C.addressof(plan), steps, plan.n_key_steps))
+        plan, key_steps = _plan_with_key_steps(lib().sealhip_evaluator_bootstrap_plan, BootstrapPlan, self.ctx.handle, *args)
         out = _bootstrap_plan_dict(plan)
-        out["key_steps"] = [int(v) for v in steps[:plan.n_key_steps]]
+        out["key_steps"] = key_steps
         return out
 
     def bootstrap(self, tables, ct, k_in, count, galois_keys, relin_keys, out):
         """Bootstrap in one call (sealhip_evaluator_bootstrap): ct a device batch count x 2 x k_in x N (only the q_0 rows are
         read); out: count x 2 x tables.plan["out_level"] x N at the input's scale. galois_keys: dict galois_elt ->
         KSwitchKeys with the plan's key_steps and element 2N - 1; relin_keys: a list of KSwitchKeys (index 0 is read)."""
-        elts = list(galois_keys.keys())
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
-        keys = None
-        if relin_keys is not None:
-            keys = (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys])
-        _check(lib().sealhip_evaluator_bootstrap(self.ctx.handle, tables.handle, k_in, _ptr(ct), count, ea, ka, len(elts), keys,
-                                                 len(relin_keys) if relin_keys is not None else 0, _ptr(out)))
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        keys, n_relin = _relin_array(relin_keys)
+        _check(lib().sealhip_evaluator_bootstrap(self.ctx.handle, tables.handle, k_in, _ptr(ct), count, ea, ka, n_keys, keys,
+                                                 n_relin, _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod
@@ -1411,11 +1375,9 @@ class Evaluator:
                                                         len(relin_keys)))
 
     def rotate_vector_host(self, cts, k, steps, galois_keys):
-        elts = list(galois_keys.keys())
-        ea = (_u32 * max(1, len(elts)))(*elts)
-        ka = (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts])
+        ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(lib().sealhip_evaluator_rotate_vector_host(self.ctx.handle, k, self._host_ptrs(cts), len(cts), steps, ea, ka,
-                                                          len(elts)))
+                                                          n_keys))
 
     def mod_switch_to_next_host(self, cts, size, k, out, rescale=False):
         fn = lib().sealhip_evaluator_rescale_to_next_host if rescale else lib().sealhip_evaluator_mod_switch_to_next_host
@@ -1539,43 +1501,50 @@ def evalmod_coeffs(K, r, degree):
     return [float(v) for v in out]
 
 
-def _u32_list(values):
+def _u32_array(values):
     return (_u32 * max(1, len(values)))(*[int(v) for v in values]) if values is not None else None
 
 
-def _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby):
-    for stages, nb in ((c2s_stages, c2s_n_baby), (s2c_stages, s2c_n_baby)):
-        if nb is not None and len(nb) != len(stages):
-            raise ValueError("n_baby and stages differ in length")
-    return (k_top, _u32_list(c2s_stages), len(c2s_stages), _u32_list(c2s_n_baby), _u32_list(s2c_stages), len(s2c_stages),
-            _u32_list(s2c_n_baby), K, r, degree, n_baby)
+def _relin_array(relin_keys):
+    """(the handles of a list of KSwitchKeys or None, their number): the ABI's relin_keys, n_relin_keys"""
+    if relin_keys is None:
+        return None, 0
+    return (_vp * max(1, len(relin_keys)))(*[rk.handle for rk in relin_keys]), len(relin_keys)
 
 
-def _bootstrap_plan_dict(plan):
-    out = {name: getattr(plan, name) for name, _ in BootstrapPlan._fields_ if name not in ("evalmod", "n_key_steps")}
-    em = plan.evalmod
-    out["evalmod"] = {name: getattr(em, name) for name, _ in EvalModPlan._fields_ if name not in ("scales", "reserved")}
-    out["evalmod"]["scales"] = [float(v) for v in em.scales[:em.r + 1]]
-    out["evalmod"]["out_scale"] = out["evalmod"]["scales"][-1]
+def _galois_arrays(galois_keys):
+    """(elements, key handles, their number) of a dict galois_elt -> KSwitchKeys: the ABI's galois_elts, galois_keys, n_keys"""
+    elts = list(galois_keys.keys())
+    return (_u32 * max(1, len(elts)))(*elts), (_vp * max(1, len(elts)))(*[galois_keys[g].handle for g in elts]), len(elts)
+
+
+def _plan_with_key_steps(fn, plan_type, *args):
+    """The ABI's two calls of a plan entry: the plan, which says how many key steps there are, then the steps"""
+    plan = plan_type()
+    _check(fn(*args, C.addressof(plan), None, 0))
+    steps = (_u32 * max(1, plan.n_key_steps))()
+    _check(fn(*args, C.addressof(plan), steps, plan.n_key_steps))
+    return plan, [int(v) for v in steps[:plan.n_key_steps]]
+
+
+def _evalmod_plan_dict(plan):
+    out = {name: getattr(plan, name) for name, _ in EvalModPlan._fields_ if name not in ("scales", "reserved")}
+    out["scales"] = [float(v) for v in plan.scales[:plan.r + 1]]
+    out["out_scale"] = out["scales"][-1]
     return out
 
 
-class BootstrapTables:
-    """sealhip_bootstrap_tables: both transforms' tables, the EvalMod coefficients and the intermediates' pool blocks of
-    one bootstrap shape"""
+class _Tables:
+    """A handle of device tables and its end: free() destroys them once and raises when the library refuses (during a graph
+    capture), in which case the handle is kept"""
+    _destroy = None  # the ABI's destroy entry, by name
 
-    def __init__(self, ctx, k_top, c2s_stages, s2c_stages, K, r, degree, n_baby=0, c2s_n_baby=None, s2c_n_baby=None):
-        self.ctx = ctx
-        self.handle = _vp()
-        args = _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby)
-        _check(lib().sealhip_bootstrap_tables_create(ctx.handle, *args, C.byref(self.handle)))
-        plan = BootstrapPlan()
-        _check(lib().sealhip_bootstrap_tables_plan(self.handle, C.addressof(plan)))
-        self.plan = _bootstrap_plan_dict(plan)
+    def __init__(self, ctx):
+        self.ctx, self.handle = ctx, _vp()
 
     def free(self):
-        if self.handle:
-            _check(lib().sealhip_bootstrap_tables_destroy(self.handle))
+        if self.handle and lib is not None:
+            _check(getattr(lib(), self._destroy)(self.handle))
             self.handle = _vp()
 
     def __del__(self):
@@ -1585,13 +1554,39 @@ class BootstrapTables:
             pass
 
 
+def _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby):
+    for stages, nb in ((c2s_stages, c2s_n_baby), (s2c_stages, s2c_n_baby)):
+        if nb is not None and len(nb) != len(stages):
+            raise ValueError("n_baby and stages differ in length")
+    return (k_top, _u32_array(c2s_stages), len(c2s_stages), _u32_array(c2s_n_baby), _u32_array(s2c_stages), len(s2c_stages),
+            _u32_array(s2c_n_baby), K, r, degree, n_baby)
+
+
+def _bootstrap_plan_dict(plan):
+    out = {name: getattr(plan, name) for name, _ in BootstrapPlan._fields_ if name not in ("evalmod", "n_key_steps")}
+    out["evalmod"] = _evalmod_plan_dict(plan.evalmod)
+    return out
+
+
+class BootstrapTables(_Tables):
+    """sealhip_bootstrap_tables: both transforms' tables, the EvalMod coefficients and the intermediates' pool blocks of
+    one bootstrap shape"""
+    _destroy = "sealhip_bootstrap_tables_destroy"
+
+    def __init__(self, ctx, k_top, c2s_stages, s2c_stages, K, r, degree, n_baby=0, c2s_n_baby=None, s2c_n_baby=None):
+        super().__init__(ctx)
+        args = _bootstrap_args(k_top, c2s_stages, c2s_n_baby, s2c_stages, s2c_n_baby, K, r, degree, n_baby)
+        _check(lib().sealhip_bootstrap_tables_create(ctx.handle, *args, C.byref(self.handle)))
+        plan = BootstrapPlan()
+        _check(lib().sealhip_bootstrap_tables_plan(self.handle, C.addressof(plan)))
+        self.plan = _bootstrap_plan_dict(plan)
+
+
 def _dft_args(direction, k, stages, n_baby):
-    stages = [int(v) for v in stages]
-    sa = (_u32 * max(1, len(stages)))(*stages)
+    sa = _u32_array(stages)
     if n_baby is not None and len(n_baby) != len(stages):
         raise ValueError("n_baby and stages differ in length")
-    na = (_u32 * max(1, len(stages)))(*[int(v) for v in n_baby]) if n_baby is not None else None
-    return int(direction), int(k), sa, len(stages), na
+    return int(direction), int(k), sa, len(stages), _u32_array(n_baby)
 
 
 def _dft_plan_dict(plan):
@@ -1606,16 +1601,17 @@ def _dft_plan_dict(plan):
     return out
 
 
-class DftTables:
+class DftTables(_Tables):
     """The device tables of one homomorphic DFT (sealhip_dft_tables_create): every stage's diagonals,
     generated on the device and encoded at the key level. plan: Evaluator.dft_plan's dict without the step lists;
     stage_ptr(t): the device address of stage t's n_giant x n_baby x n_key x N words."""
 
+    _destroy = "sealhip_dft_tables_destroy"
+
     def __init__(self, ctx, direction, k, stages, n_baby=None, gain=1.0):
-        self.ctx, self.handle = ctx, None
-        h = _vp()
-        _check(lib().sealhip_dft_tables_create(ctx.handle, *_dft_args(direction, k, stages, n_baby), gain, C.byref(h)))
-        self.handle = h
+        super().__init__(ctx)
+        _check(lib().sealhip_dft_tables_create(ctx.handle, *_dft_args(direction, k, stages, n_baby), gain,
+                                               C.byref(self.handle)))
         plan = DftPlan()
         _check(lib().sealhip_dft_tables_plan(self.handle, C.addressof(plan)))
         self.plan = _dft_plan_dict(plan)
@@ -1626,16 +1622,6 @@ class DftTables:
         _check(lib().sealhip_dft_tables_stage(self.handle, stage, C.byref(p)))
         return p.value
 
-    def free(self):
-        if self.handle is not None and lib is not None:
-            lib().sealhip_dft_tables_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def _naf(value):
