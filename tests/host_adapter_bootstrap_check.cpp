@@ -8,48 +8,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    return c;
-}
 
 static int host_checks()
 {
@@ -91,8 +52,7 @@ int main(int argc, char **argv)
             return 2;
         const int device = std::atoi(argv[1]);
         std::uint64_t mods[11];
-        for (int i = 0; i < 11; i++)
-            mods[i] = std::strtoull(argv[2 + i], nullptr, 10);
+        parse_moduli(argv, 2, 11, mods);
         const std::size_t n = 256, k_top = 10, nk = 11, nd = 10;
         sealhip_params p{ SEALHIP_SCHEME_CKKS, 8, 11, 1, mods, 0ULL, SEALHIP_MODE_PARITY, device };
         Context ctx(p);
@@ -107,17 +67,11 @@ int main(int argc, char **argv)
         auto random_ct = [&](std::size_t k, double scale) {
             HostCiphertext c = host_ct(2, k, n, true);
             c.scale_ = scale;
-            for (std::size_t row = 0; row < 2 * k; row++)
-                for (std::size_t i = 0; i < n; i++)
-                    c.words[row * n + i] = splitmix(state) % mods[row % k];
+            fill_rows(c.words.data(), 2 * k, n, mods, k, state);
             return c;
         };
         auto random_key = [&] {
-            std::vector<std::uint64_t> w(nd * 2 * nk * n);
-            for (std::size_t row = 0; row < nd * 2 * nk; row++)
-                for (std::size_t i = 0; i < n; i++)
-                    w[row * n + i] = splitmix(state) % mods[row % nk];
-            return std::unique_ptr<KSwitchKeys>(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            return seeded_key(ctx, nd, nk, n, mods, state);
         };
         std::vector<std::uint32_t> elts{ std::uint32_t(2 * n - 1) };
         for (std::uint32_t step : boot.key_steps())

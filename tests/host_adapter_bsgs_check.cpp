@@ -10,69 +10,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
-{
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    return c;
-}
-
-static HostPlaintext host_plain(std::size_t k, std::size_t n, bool ntt, double scale)
-{
-    HostPlaintext p;
-    p.words.assign(k * n, 1);
-    p.k = k;
-    p.ntt_form = ntt;
-    p.scale = scale;
-    return p;
-}
 
 using Plains = std::vector<std::vector<HostPlaintext>>;
 
@@ -151,8 +91,7 @@ int main(int argc, char **argv)
         const int device = std::atoi(argv[1]);
         const bool bfv = std::strcmp(argv[2], "bfv") == 0;
         std::uint64_t mods[4];
-        for (int i = 0; i < 4; i++)
-            mods[i] = std::strtoull(argv[3 + i], nullptr, 10);
+        parse_moduli(argv, 3, 4, mods);
         const std::size_t n = 4096, k = 3, nk = 4, nd = 3, n_giant = 3, n_baby = 2;
         sealhip_params p{ bfv ? SEALHIP_SCHEME_BFV : SEALHIP_SCHEME_CKKS, 12, 4, 1, mods, bfv ? 65537ULL : 0ULL,
                           bfv ? SEALHIP_MODE_STRICT : SEALHIP_MODE_PARITY, device };
@@ -160,9 +99,7 @@ int main(int argc, char **argv)
         std::uint64_t state = 0x4017;
         HostCiphertext ct = host_ct(2, k, n, !bfv);
         ct.scale_ = bfv ? 1.0 : 1048576.0;
-        for (std::size_t r = 0; r < 2 * k; r++)
-            for (std::size_t i = 0; i < n; i++)
-                ct.words[r * n + i] = splitmix(state) % mods[r % k];
+        fill_rows(ct.words.data(), 2 * k, n, mods, k, state);
         const int steps[3] = { 1, -2, 4 };
         std::uint32_t elts[3];
         std::vector<std::unique_ptr<KSwitchKeys>> keys;
@@ -170,11 +107,7 @@ int main(int argc, char **argv)
         for (int e = 0; e < 3; e++)
         {
             throw_on(sealhip_galois_elt_from_step(ctx.get(), steps[e], &elts[e]));
-            std::vector<std::uint64_t> w(nd * 2 * nk * n);
-            for (std::size_t r = 0; r < nd * 2 * nk; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    w[r * n + i] = splitmix(state) % mods[r % nk];
-            keys.emplace_back(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            keys.push_back(seeded_key(ctx, nd, nk, n, mods, state));
             gk[elts[e]] = keys.back().get();
         }
         const double pscale = bfv ? 1.0 : 1024.0;
@@ -188,9 +121,7 @@ int main(int argc, char **argv)
                 w.k = nk;
                 w.ntt_form = true;
                 w.scale = pscale;
-                for (std::size_t r = 0; r < nk; r++)
-                    for (std::size_t i = 0; i < n; i++)
-                        w.words[r * n + i] = splitmix(state) % mods[r];
+                fill_rows(w.words.data(), nk, n, mods, nk, state);
                 dplains[s].emplace_back(ctx);
                 dplains[s].back().upload(w.words, true);
                 dplains[s].back().scale() = pscale;
@@ -200,10 +131,10 @@ int main(int argc, char **argv)
         const std::vector<std::uint32_t> baby{ elts[0], 1 }, giant{ 1, elts[1], elts[2] };
         const std::vector<int> baby_steps{ 1, 0 }, giant_steps{ 0, -2, 4 };
         auto report = [&](const char *what, const HostCiphertext &c) {
-            const std::uint64_t h = digest(0xcbf29ce484222325ULL, c.data(), c.words.size());
+            const std::uint64_t h = digest(c.words);
             const bool meta = c.size() == 2 && c.coeff_modulus_size() == k && c.is_ntt_form() == !bfv &&
                               (bfv || c.scale() == ct.scale() * pscale);
-            std::printf("%s digest %016llx meta %d\n", what, static_cast<unsigned long long>(h), int(meta));
+            print_digest(what, h, meta);
         };
         HostCiphertext out;
         ev.apply_galois_bsgs_plain(ct, baby, giant, gk, plains, out);

@@ -4,16 +4,9 @@
 #include <cstdlib>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
 
 int main(int argc, char **argv)
 {
@@ -32,34 +25,19 @@ int main(int argc, char **argv)
         std::uint64_t state = 0xC0FFEE + 1;
         // same fill order as the survey generator (keys first), SURVEY Appendix B.2
         std::vector<std::uint64_t> key(2 * 2 * 3 * n);
-        for (std::size_t d = 0; d < 2; d++)
-            for (std::size_t l = 0; l < 2; l++)
-                for (std::size_t r = 0; r < 3; r++)
-                    for (std::size_t c = 0; c < n; c++)
-                        key[((d * 2 + l) * 3 + r) * n + c] = splitmix(state) % mods[r];
+        fill_rows(key.data(), 2 * 2 * 3, n, mods, 3, state);
         HostCiphertext a, b;
         for (HostCiphertext *ct : { &a, &b })
         {
-            ct->n_ = n;
-            ct->resize_raw(2, k);
-            for (std::size_t s = 0; s < 2; s++)
-                for (std::size_t r = 0; r < k; r++)
-                    for (std::size_t c = 0; c < n; c++)
-                        ct->words[(s * k + r) * n + c] = splitmix(state) % mods[r];
+            *ct = host_ct(2, k, n, false);
+            fill_rows(ct->words.data(), 2 * k, n, mods, k, state);
         }
         Evaluator<HostCiphertext> ev(ctx);
         KSwitchKeys rk(ctx, key.data(), 2);
         ev.multiply_inplace(a, b);
         ev.relinearize_inplace(a, { &rk });
         ev.mod_switch_to_next_inplace(a);
-        std::uint64_t h = 0xcbf29ce484222325ULL;
-        for (std::uint64_t w : a.words)
-            for (int i = 0; i < 8; i++)
-            {
-                h ^= (w >> (8 * i)) & 0xff;
-                h *= 0x100000001b3ULL;
-            }
-        std::printf("modswitch digest %016llx\n", (unsigned long long)h);
+        std::printf("modswitch digest %016llx\n", (unsigned long long)digest(a.words));
         // SURVEY 8(f1) methods: algebraic identities through the adapter
         HostCiphertext c = b, d = b;
         ev.add_inplace(c, b);
@@ -84,12 +62,8 @@ int main(int argc, char **argv)
             HostCiphertext a0, b0;
             for (HostCiphertext *ct : { &a0, &b0 })
             {
-                ct->n_ = n;
-                ct->resize_raw(2, k);
-                for (std::size_t s = 0; s < 2; s++)
-                    for (std::size_t r = 0; r < k; r++)
-                        for (std::size_t c2 = 0; c2 < n; c2++)
-                            ct->words[(s * k + r) * n + c2] = splitmix(st2) % mods[r];
+                *ct = host_ct(2, k, n, false);
+                fill_rows(ct->words.data(), 2 * k, n, mods, k, st2);
             }
             HostCiphertext one_by_one = a0;
             ev.multiply_inplace(one_by_one, b0);
@@ -175,16 +149,7 @@ int main(int argc, char **argv)
         // the key buffer above standing in for the Galois keys of both elements; digests compared by the Python test with
         // the oracle's apply_galois on the same words. Destination-taking variants, add_many, mod_switch_to.
         {
-            const auto digest = [](const HostCiphertext &ct) {
-                std::uint64_t hh = 0xcbf29ce484222325ULL;
-                for (std::uint64_t w : ct.words)
-                    for (int i = 0; i < 8; i++)
-                    {
-                        hh ^= (w >> (8 * i)) & 0xff;
-                        hh *= 0x100000001b3ULL;
-                    }
-                return (unsigned long long)hh;
-            };
+            const auto digest = [](const HostCiphertext &ct) { return (unsigned long long)adapter_check::digest(ct.words); };
             std::uint32_t e1 = 0, ec = 0;
             throw_on(sealhip_galois_elt_from_step(ctx.get(), 1, &e1));
             throw_on(sealhip_galois_elt_from_step(ctx.get(), 0, &ec));
@@ -262,16 +227,7 @@ int main(int argc, char **argv)
             cev.rotate_vector(x, 1, gks, rv);
             cev.rescale_to_next(x, rs);
             cev.rescale_to(x, 1, rs2);
-            const auto digest = [](const HostCiphertext &ct) {
-                std::uint64_t hh = 0xcbf29ce484222325ULL;
-                for (std::uint64_t w : ct.words)
-                    for (int i = 0; i < 8; i++)
-                    {
-                        hh ^= (w >> (8 * i)) & 0xff;
-                        hh *= 0x100000001b3ULL;
-                    }
-                return (unsigned long long)hh;
-            };
+            const auto digest = [](const HostCiphertext &ct) { return (unsigned long long)adapter_check::digest(ct.words); };
             std::printf("complex_conjugate digest %016llx\n", digest(cj));
             std::printf("rotate_vector digest %016llx\n", digest(rv));
             int logic = 0;

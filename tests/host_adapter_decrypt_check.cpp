@@ -10,54 +10,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t digest(const std::vector<std::uint64_t> &w)
-{
-    std::uint64_t h = 0xcbf29ce484222325ULL;
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w.data());
-    for (std::size_t i = 0; i < w.size() * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strncmp(e.what(), msg, std::strlen(msg)) == 0)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext make_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext ct;
-    ct.n_ = n;
-    ct.size_ = size;
-    ct.k_ = k;
-    ct.ntt_form_ = ntt;
-    ct.words.assign(size * k * n, 0);
-    return ct;
-}
 
 static int host_checks()
 {
@@ -70,26 +25,26 @@ static int host_checks()
     Decryptor<HostCiphertext> db(bfv, sk.data()), dc(ckks, sk.data());
     const char *invalid = "encrypted is not valid for encryption parameters";
     bool ok = true;
-    HostCiphertext one = make_ct(1, 2, n, false), wide = make_ct(17, 2, n, false), deep = make_ct(2, 5, n, false);
-    HostCiphertext ring = make_ct(2, 2, n / 2, false), coeff = make_ct(2, 2, n, false), ntt = make_ct(2, 2, n, true);
+    HostCiphertext one = host_ct(1, 2, n, false), wide = host_ct(17, 2, n, false), deep = host_ct(2, 5, n, false);
+    HostCiphertext ring = host_ct(2, 2, n / 2, false), coeff = host_ct(2, 2, n, false), ntt = host_ct(2, 2, n, true);
     for (const HostCiphertext *bad : { &one, &wide, &deep, &ring })
     {
-        ok &= throws<std::invalid_argument>([&] { db.decrypt(*bad, plain); }, invalid);
-        ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(*bad); }, invalid);
-        ok &= throws<std::invalid_argument>([&] { dc.invariant_noise_budget(*bad); }, invalid);
+        ok &= throws_prefix<std::invalid_argument>([&] { db.decrypt(*bad, plain); }, invalid);
+        ok &= throws_prefix<std::invalid_argument>([&] { db.invariant_noise_budget(*bad); }, invalid);
+        ok &= throws_prefix<std::invalid_argument>([&] { dc.invariant_noise_budget(*bad); }, invalid);
     }
-    ok &= throws<std::invalid_argument>([&] { db.decrypt(ntt, plain); }, "encrypted cannot be in NTT form");
-    ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(ntt); }, "encrypted cannot be in NTT form");
-    ok &= throws<std::invalid_argument>([&] { dc.decrypt(coeff, plain); }, "encrypted must be in NTT form");
-    ok &= throws<std::logic_error>([&] { dc.invariant_noise_budget(ntt); }, "unsupported scheme");
-    ok &= throws<std::logic_error>([&] { dc.invariant_noise_budget(coeff); }, "unsupported scheme");
+    ok &= throws_prefix<std::invalid_argument>([&] { db.decrypt(ntt, plain); }, "encrypted cannot be in NTT form");
+    ok &= throws_prefix<std::invalid_argument>([&] { db.invariant_noise_budget(ntt); }, "encrypted cannot be in NTT form");
+    ok &= throws_prefix<std::invalid_argument>([&] { dc.decrypt(coeff, plain); }, "encrypted must be in NTT form");
+    ok &= throws_prefix<std::logic_error>([&] { dc.invariant_noise_budget(ntt); }, "unsupported scheme");
+    ok &= throws_prefix<std::logic_error>([&] { dc.invariant_noise_budget(coeff); }, "unsupported scheme");
     // a batch is checked whole before any device work
-    ok &= throws<std::invalid_argument>([&] { db.invariant_noise_budget(std::vector<const HostCiphertext *>{ &coeff, &ntt }); },
+    ok &= throws_prefix<std::invalid_argument>([&] { db.invariant_noise_budget(std::vector<const HostCiphertext *>{ &coeff, &ntt }); },
                                         "encrypted cannot be in NTT form");
     // valid arguments reach the device: a host-only context refuses them
-    ok &= throws<std::logic_error>([&] { db.decrypt(coeff, plain); }, "host-only");
-    ok &= throws<std::logic_error>([&] { db.invariant_noise_budget(coeff); }, "host-only");
-    ok &= throws<std::logic_error>([&] { dc.decrypt(ntt, plain); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { db.decrypt(coeff, plain); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { db.invariant_noise_budget(coeff); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { dc.decrypt(ntt, plain); }, "host-only");
     if (!ok)
         return 1;
     std::printf("host-only decrypt checks ok\n");
@@ -127,7 +82,7 @@ int main(int argc, char **argv)
         std::vector<HostCiphertext> cts;
         for (std::size_t i = 0; i < count; i++)
         {
-            cts.push_back(make_ct(size, k, n, scheme == SEALHIP_SCHEME_CKKS));
+            cts.push_back(host_ct(size, k, n, scheme == SEALHIP_SCHEME_CKKS));
             std::memcpy(cts.back().words.data(), in.data() + at, size * k * n * 8);
             at += size * k * n;
         }

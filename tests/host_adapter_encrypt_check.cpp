@@ -13,44 +13,11 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
 
-static std::uint64_t digest(const std::uint64_t *w, std::size_t words)
-{
-    std::uint64_t h = 0xcbf29ce484222325ULL;
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strncmp(e.what(), msg, std::strlen(msg)) == 0)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
+// (not host_ct: no polynomials at all, the state a destination has before its first use)
 static HostCiphertext empty_ct(std::size_t n)
 {
     HostCiphertext ct;
@@ -89,28 +56,28 @@ static int host_checks()
     const char *invalid = "plain is not valid for encryption parameters";
     const std::uint64_t pid[4] = { 1, 2, 3, 4 };
     bool ok = true;
-    ok &= throws<std::logic_error>([&] { none.encrypt(ok_plain, ct); }, "public key is not set");
-    ok &= throws<std::logic_error>([&] { none.encrypt_zero(ct); }, "public key is not set");
-    ok &= throws<std::logic_error>([&] { none.encrypt_symmetric(ok_plain, ct); }, "secret key is not set");
-    ok &= throws<std::logic_error>([&] { none.encrypt_zero_symmetric(ct); }, "secret key is not set");
-    ok &= throws<std::logic_error>([&] { none.encrypt_symmetric_seeded(ok_plain, pid); }, "secret key is not set");
-    ok &= throws<std::invalid_argument>([&] { eb.encrypt(ntt_plain, ct); }, "plain cannot be in NTT form");
-    ok &= throws<std::invalid_argument>([&] { eb.encrypt(long_plain, ct); }, invalid);
-    ok &= throws<std::invalid_argument>([&] { eb.encrypt_symmetric(big_plain, ct); }, invalid);
-    ok &= throws<std::invalid_argument>([&] { ec.encrypt(ckks_coeff, ct); }, "plain must be in NTT form");
-    ok &= throws<std::invalid_argument>([&] { ec.encrypt(ckks_key, ct); }, invalid);
-    ok &= throws<std::invalid_argument>([&] { ec.encrypt_symmetric(ckks_short, ct); }, invalid);
+    ok &= throws_prefix<std::logic_error>([&] { none.encrypt(ok_plain, ct); }, "public key is not set");
+    ok &= throws_prefix<std::logic_error>([&] { none.encrypt_zero(ct); }, "public key is not set");
+    ok &= throws_prefix<std::logic_error>([&] { none.encrypt_symmetric(ok_plain, ct); }, "secret key is not set");
+    ok &= throws_prefix<std::logic_error>([&] { none.encrypt_zero_symmetric(ct); }, "secret key is not set");
+    ok &= throws_prefix<std::logic_error>([&] { none.encrypt_symmetric_seeded(ok_plain, pid); }, "secret key is not set");
+    ok &= throws_prefix<std::invalid_argument>([&] { eb.encrypt(ntt_plain, ct); }, "plain cannot be in NTT form");
+    ok &= throws_prefix<std::invalid_argument>([&] { eb.encrypt(long_plain, ct); }, invalid);
+    ok &= throws_prefix<std::invalid_argument>([&] { eb.encrypt_symmetric(big_plain, ct); }, invalid);
+    ok &= throws_prefix<std::invalid_argument>([&] { ec.encrypt(ckks_coeff, ct); }, "plain must be in NTT form");
+    ok &= throws_prefix<std::invalid_argument>([&] { ec.encrypt(ckks_key, ct); }, invalid);
+    ok &= throws_prefix<std::invalid_argument>([&] { ec.encrypt_symmetric(ckks_short, ct); }, invalid);
     for (std::size_t bad : { std::size_t(0), std::size_t(5) })
     {
-        ok &= throws<std::invalid_argument>([&] { eb.encrypt_zero(bad, ct); }, "parms_id is not valid for encryption parameters");
-        ok &= throws<std::invalid_argument>([&] { ec.encrypt_zero_symmetric(bad, ct); },
+        ok &= throws_prefix<std::invalid_argument>([&] { eb.encrypt_zero(bad, ct); }, "parms_id is not valid for encryption parameters");
+        ok &= throws_prefix<std::invalid_argument>([&] { ec.encrypt_zero_symmetric(bad, ct); },
                                             "parms_id is not valid for encryption parameters");
     }
     // valid arguments reach the device: a host-only context refuses them
-    ok &= throws<std::logic_error>([&] { eb.encrypt(ok_plain, ct); }, "host-only");
-    ok &= throws<std::logic_error>([&] { eb.encrypt_zero(4, ct); }, "host-only");
-    ok &= throws<std::logic_error>([&] { ec.encrypt(ckks_ok, ct); }, "host-only");
-    ok &= throws<std::logic_error>([&] { ec.encrypt_symmetric(ckks_ok, ct); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { eb.encrypt(ok_plain, ct); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { eb.encrypt_zero(4, ct); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { ec.encrypt(ckks_ok, ct); }, "host-only");
+    ok &= throws_prefix<std::logic_error>([&] { ec.encrypt_symmetric(ckks_ok, ct); }, "host-only");
     if (!ok)
         return 1;
     std::printf("host-only encrypt checks ok\n");

@@ -10,69 +10,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
-{
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    return c;
-}
-
-static HostPlaintext host_plain(std::size_t k, std::size_t n, bool ntt, double scale)
-{
-    HostPlaintext p;
-    p.words.assign(k * n, 1);
-    p.k = k;
-    p.ntt_form = ntt;
-    p.scale = scale;
-    return p;
-}
 
 using Plains = std::vector<std::vector<HostPlaintext>>;
 
@@ -144,17 +84,14 @@ int main(int argc, char **argv)
             return 2;
         const int device = std::atoi(argv[1]);
         std::uint64_t mods[4];
-        for (int i = 0; i < 4; i++)
-            mods[i] = std::strtoull(argv[2 + i], nullptr, 10);
+        parse_moduli(argv, 2, 4, mods);
         const std::size_t n = 4096, k = 3, nk = 4, nd = 3, n_sums = 2, n_elts = 3;
         sealhip_params p{ SEALHIP_SCHEME_CKKS, 12, 4, 1, mods, 0, SEALHIP_MODE_PARITY, device };
         Context ctx(p);
         std::uint64_t state = 0x4016;
         HostCiphertext ct = host_ct(2, k, n, true);
         ct.scale_ = 1048576.0;
-        for (std::size_t r = 0; r < 2 * k; r++)
-            for (std::size_t i = 0; i < n; i++)
-                ct.words[r * n + i] = splitmix(state) % mods[r % k];
+        fill_rows(ct.words.data(), 2 * k, n, mods, k, state);
         std::uint32_t elts[2];
         throw_on(sealhip_galois_elt_from_step(ctx.get(), 1, &elts[0]));
         throw_on(sealhip_galois_elt_from_step(ctx.get(), -2, &elts[1]));
@@ -162,11 +99,7 @@ int main(int argc, char **argv)
         std::map<std::uint32_t, const KSwitchKeys *> gk;
         for (int e = 0; e < 2; e++)
         {
-            std::vector<std::uint64_t> w(nd * 2 * nk * n);
-            for (std::size_t r = 0; r < nd * 2 * nk; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    w[r * n + i] = splitmix(state) % mods[r % nk];
-            keys.emplace_back(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            keys.push_back(seeded_key(ctx, nd, nk, n, mods, state));
             gk[elts[e]] = keys.back().get();
         }
         const double pscale = 1024.0;
@@ -180,9 +113,7 @@ int main(int argc, char **argv)
                 w.k = nk;
                 w.ntt_form = true;
                 w.scale = pscale;
-                for (std::size_t r = 0; r < nk; r++)
-                    for (std::size_t i = 0; i < n; i++)
-                        w.words[r * n + i] = splitmix(state) % mods[r];
+                fill_rows(w.words.data(), nk, n, mods, nk, state);
                 dplains[s].emplace_back(ctx);
                 dplains[s].back().upload(w.words, true);
                 dplains[s].back().scale() = pscale;
@@ -191,7 +122,7 @@ int main(int argc, char **argv)
         const std::vector<std::uint32_t> ge{ elts[0], 1, elts[1] };
         const std::vector<int> steps{ 1, 0, -2 };
         auto report = [&](const char *what, const std::vector<HostCiphertext> &out) {
-            std::uint64_t h = 0xcbf29ce484222325ULL;
+            std::uint64_t h = kFnvBasis;
             bool meta = true;
             for (auto &c : out)
             {

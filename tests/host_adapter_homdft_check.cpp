@@ -8,48 +8,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    return c;
-}
 
 static int host_checks()
 {
@@ -88,8 +49,7 @@ int main(int argc, char **argv)
             return 2;
         const int device = std::atoi(argv[1]);
         std::uint64_t mods[5];
-        for (int i = 0; i < 5; i++)
-            mods[i] = std::strtoull(argv[2 + i], nullptr, 10);
+        parse_moduli(argv, 2, 5, mods);
         const std::size_t n = 256, k = 4, nk = 5, nd = 4;
         sealhip_params p{ SEALHIP_SCHEME_CKKS, 8, 5, 1, mods, 0ULL, SEALHIP_MODE_PARITY, device };
         Context ctx(p);
@@ -101,9 +61,7 @@ int main(int argc, char **argv)
         auto random_ct = [&] {
             HostCiphertext c = host_ct(2, k, n, true);
             c.scale_ = 1048576.0;
-            for (std::size_t r = 0; r < 2 * k; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    c.words[r * n + i] = splitmix(state) % mods[r % k];
+            fill_rows(c.words.data(), 2 * k, n, mods, k, state);
             return c;
         };
         const HostCiphertext ct = random_ct(), ct2 = random_ct();
@@ -121,11 +79,7 @@ int main(int argc, char **argv)
         std::vector<const sealhip_kswitch_key *> raw;
         for (std::uint32_t elt : elts)
         {
-            std::vector<std::uint64_t> w(nd * 2 * nk * n);
-            for (std::size_t r = 0; r < nd * 2 * nk; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    w[r * n + i] = splitmix(state) % mods[r % nk];
-            keys.emplace_back(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            keys.push_back(seeded_key(ctx, nd, nk, n, mods, state));
             gk[elt] = keys.back().get();
             raw.push_back(keys.back()->get());
         }

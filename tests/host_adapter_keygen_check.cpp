@@ -7,50 +7,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(const unsigned char *p, std::size_t len)
-{
-    std::uint64_t h = 0xcbf29ce484222325ULL;
-    for (std::size_t i = 0; i < len; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strcmp(e.what(), msg) == 0)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
 
 static std::uint64_t save_digest(const Context &ctx, const std::vector<const sealhip_kswitch_key *> &keys)
 {
@@ -73,9 +32,7 @@ int main(int argc, char **argv)
         Context ctx(p);
         std::vector<std::uint64_t> sk(4 * n);
         std::uint64_t state = 0x5EC2E7;
-        for (std::size_t r = 0; r < 4; r++)
-            for (std::size_t i = 0; i < n; i++)
-                sk[r * n + i] = splitmix(state) % mods[r];
+        fill_rows(sk.data(), 4, n, mods, 4, state);
         std::uint64_t sample_state = 0xCAFE;
         std::size_t asked = 0;
         KeyGenerator kg(ctx, sk.data(), [&](std::uint64_t *seed, std::int32_t *noise) {
@@ -88,19 +45,19 @@ int main(int argc, char **argv)
         if (device < 0)
         {
             bool ok = true;
-            ok &= throws<std::invalid_argument>([&] { kg.relin_keys(0); }, "invalid count");
-            ok &= throws<std::invalid_argument>([&] { kg.relin_keys(15); }, "invalid count");
-            ok &= throws<std::invalid_argument>([&] { kg.galois_keys(std::vector<std::uint32_t>{ 3, 4 }); },
+            ok &= throws_exact<std::invalid_argument>([&] { kg.relin_keys(0); }, "invalid count");
+            ok &= throws_exact<std::invalid_argument>([&] { kg.relin_keys(15); }, "invalid count");
+            ok &= throws_exact<std::invalid_argument>([&] { kg.galois_keys(std::vector<std::uint32_t>{ 3, 4 }); },
                                                 "Galois element is not valid");
-            ok &= throws<std::invalid_argument>([&] { kg.galois_keys(std::vector<std::uint32_t>{ 3, 2 * n + 1 }); },
+            ok &= throws_exact<std::invalid_argument>([&] { kg.galois_keys(std::vector<std::uint32_t>{ 3, 2 * n + 1 }); },
                                                 "Galois element is not valid");
-            ok &= throws<std::invalid_argument>([&] { kg.galois_keys(std::vector<int>{ 1, int(n / 2) }); }, "step count too large");
+            ok &= throws_exact<std::invalid_argument>([&] { kg.galois_keys(std::vector<int>{ 1, int(n / 2) }); }, "step count too large");
             ok &= asked == 0; // nothing sampled for rejected arguments
             sealhip_params nb = p;
             nb.plain_modulus = 65539; // prime, not 1 mod 2N
             Context ctx_nb(nb);
             KeyGenerator kg_nb(ctx_nb, sk.data(), [](std::uint64_t *, std::int32_t *) {});
-            ok &= throws<std::logic_error>([&] { kg_nb.galois_keys(std::vector<std::uint32_t>{ 3 }); },
+            ok &= throws_exact<std::logic_error>([&] { kg_nb.galois_keys(std::vector<std::uint32_t>{ 3 }); },
                                            "encryption parameters do not support batching");
             // get_elts_all: 2N - 1 first, 2 (log N - 1) + 1 entries, 5^(N/4) twice
             const std::vector<std::uint32_t> all = kg.elts_all();

@@ -11,69 +11,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
-{
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    return c;
-}
-
-static HostPlaintext host_plain(std::size_t k, std::size_t n, bool ntt, double scale)
-{
-    HostPlaintext p;
-    p.words.assign(k * n, 1);
-    p.k = k;
-    p.ntt_form = ntt;
-    p.scale = scale;
-    return p;
-}
 
 using Plains = std::vector<std::vector<HostPlaintext>>;
 
@@ -164,8 +104,7 @@ int main(int argc, char **argv)
             return 2;
         const int device = std::atoi(argv[1]);
         std::uint64_t mods[4];
-        for (int i = 0; i < 4; i++)
-            mods[i] = std::strtoull(argv[2 + i], nullptr, 10);
+        parse_moduli(argv, 2, 4, mods);
         const std::size_t n = 256, k = 3, nk = 4, nd = 3;
         sealhip_params p{ SEALHIP_SCHEME_CKKS, 8, 4, 1, mods, 0ULL, SEALHIP_MODE_PARITY, device };
         Context ctx(p);
@@ -174,17 +113,11 @@ int main(int argc, char **argv)
         auto fill_ct = [&](std::size_t size) {
             HostCiphertext c = host_ct(size, k, n, true);
             c.scale_ = scale;
-            for (std::size_t r = 0; r < size * k; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    c.words[r * n + i] = splitmix(state) % mods[r % k];
+            fill_rows(c.words.data(), size * k, n, mods, k, state);
             return c;
         };
         auto fill_key = [&] {
-            std::vector<std::uint64_t> w(nd * 2 * nk * n);
-            for (std::size_t r = 0; r < nd * 2 * nk; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    w[r * n + i] = splitmix(state) % mods[r % nk];
-            return std::unique_ptr<KSwitchKeys>(new KSwitchKeys(ctx, w.data(), std::uint32_t(nd)));
+            return seeded_key(ctx, nd, nk, n, mods, state);
         };
         // (the order of the Python test's draws: a, b, the size-3 ciphertext, the relinearization key, the keys of steps 1
         //  and 2, the 2 x 2 plaintexts)
@@ -205,9 +138,7 @@ int main(int argc, char **argv)
                 w.k = nk;
                 w.ntt_form = true;
                 w.scale = pscale;
-                for (std::size_t r = 0; r < nk; r++)
-                    for (std::size_t i = 0; i < n; i++)
-                        w.words[r * n + i] = splitmix(state) % mods[r];
+                fill_rows(w.words.data(), nk, n, mods, nk, state);
                 dplains[s].emplace_back(ctx);
                 dplains[s].back().upload(w.words, true);
                 dplains[s].back().scale() = pscale;
@@ -215,7 +146,7 @@ int main(int argc, char **argv)
         Evaluator<HostCiphertext> ev(ctx);
         const double q_last = double(mods[k - 1]);
         auto report = [&](const char *side, const char *what, const std::vector<HostCiphertext> &cs, double want_scale) {
-            std::uint64_t h = 0xcbf29ce484222325ULL;
+            std::uint64_t h = kFnvBasis;
             bool meta = true;
             for (const HostCiphertext &c : cs)
             {

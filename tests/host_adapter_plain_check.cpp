@@ -7,54 +7,13 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
 
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(const std::vector<std::uint64_t> &words)
-{
-    std::uint64_t h = 0xcbf29ce484222325ULL;
-    for (std::uint64_t w : words)
-        for (int i = 0; i < 8; i++)
-        {
-            h ^= (w >> (8 * i)) & 0xff;
-            h *= 0x100000001b3ULL;
-        }
-    return h;
-}
-
-template <class F>
-static bool throws_invalid(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const std::invalid_argument &e)
-    {
-        if (std::strcmp(e.what(), msg) == 0)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want invalid_argument '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
 int main(int argc, char **argv)
 {
+    const auto throws_invalid = [](auto &&f, const char *msg) { return throws_exact<std::invalid_argument>(f, msg); };
     // cfg1 of BASELINE.json: BFV N=4096, {36,36,37}, t = 786433
     const std::uint64_t mods[3] = { 68719230977ULL, 68719403009ULL, 137438822401ULL };
     const std::uint64_t t = 786433;

@@ -11,60 +11,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
-{
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt, double scale = 1.0)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    c.scale_ = scale;
-    return c;
-}
 
 using Terms = std::vector<HostCiphertext>;
 using Scalars = std::vector<std::uint64_t>;
@@ -151,8 +100,7 @@ int main(int argc, char **argv)
         const int device = std::atoi(argv[1]);
         const bool bfv = std::strcmp(argv[2], "bfv") == 0;
         std::uint64_t mods[4];
-        for (int i = 0; i < 4; i++)
-            mods[i] = std::strtoull(argv[3 + i], nullptr, 10);
+        parse_moduli(argv, 3, 4, mods);
         const std::size_t n = 4096, k = 3, nk = 4, nd = 3, n_terms = 3;
         sealhip_params p{ bfv ? SEALHIP_SCHEME_BFV : SEALHIP_SCHEME_CKKS, 12, 4, 1, mods, bfv ? 65537ULL : 0ULL,
                           bfv ? SEALHIP_MODE_STRICT : SEALHIP_MODE_PARITY, device };
@@ -163,25 +111,20 @@ int main(int argc, char **argv)
         for (std::size_t t = 0; t < n_terms; t++)
         {
             HostCiphertext ct = host_ct(2, k, n, !bfv, ct_scale);
-            for (std::size_t r = 0; r < 2 * k; r++)
-                for (std::size_t i = 0; i < n; i++)
-                    ct.words[r * n + i] = splitmix(state) % mods[r % k];
+            fill_rows(ct.words.data(), 2 * k, n, mods, k, state);
             terms.push_back(ct);
         }
-        std::vector<std::uint64_t> w(nd * 2 * nk * n);
-        for (std::size_t r = 0; r < nd * 2 * nk; r++)
-            for (std::size_t i = 0; i < n; i++)
-                w[r * n + i] = splitmix(state) % mods[r % nk];
-        KSwitchKeys key(ctx, w.data(), std::uint32_t(nd));
+        const std::unique_ptr<KSwitchKeys> seeded = seeded_key(ctx, nd, nk, n, mods, state);
+        const KSwitchKeys &key = *seeded;
         const Keys keys{ &key };
         const Scalars scalars{ 3, 65536, 40000 }, coeffs{ 7, 0, 65530, 5, 9 };
         const Doubles values{ 1.5, -2.25, 0.0078125 };
         Evaluator<HostCiphertext> ev(ctx);
         auto report = [&](const char *what, const HostCiphertext &c, double scale) {
-            const std::uint64_t h = digest(0xcbf29ce484222325ULL, c.data(), c.words.size());
+            const std::uint64_t h = digest(c.words);
             const bool meta = c.size() == 2 && c.coeff_modulus_size() == k && c.is_ntt_form() == !bfv &&
                               c.words.size() == 2 * k * n && (bfv || c.scale() == scale);
-            std::printf("%s digest %016llx meta %d\n", what, static_cast<unsigned long long>(h), int(meta));
+            print_digest(what, h, meta);
         };
         HostCiphertext out;
         if (bfv)

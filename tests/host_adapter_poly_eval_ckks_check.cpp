@@ -10,60 +10,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t splitmix(std::uint64_t &s)
-{
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-static std::uint64_t digest(std::uint64_t h, const std::uint64_t *w, std::size_t words)
-{
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
-
-template <class E, class F>
-static bool throws(F &&f, const char *msg)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &e)
-    {
-        if (std::strstr(e.what(), msg) != nullptr)
-            return true;
-        std::printf("wrong message: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s' (want '%s')\n", e.what(), msg);
-        return false;
-    }
-    std::printf("no exception (want '%s')\n", msg);
-    return false;
-}
-
-static HostCiphertext host_ct(std::size_t size, std::size_t k, std::size_t n, bool ntt, double scale = 1.0)
-{
-    HostCiphertext c;
-    c.n_ = n;
-    c.resize_raw(size, k);
-    c.ntt_form_ = ntt;
-    c.scale_ = scale;
-    return c;
-}
 
 using Doubles = std::vector<double>;
 using Keys = std::vector<const KSwitchKeys *>;
@@ -113,21 +62,15 @@ int main(int argc, char **argv)
         const int device = std::atoi(argv[1]);
         const std::size_t n = 4096, k = 8, nk = 9, nd = 8;
         std::uint64_t mods[nk];
-        for (std::size_t i = 0; i < nk; i++)
-            mods[i] = std::strtoull(argv[2 + i], nullptr, 10);
+        parse_moduli(argv, 2, int(nk), mods);
         sealhip_params p{ SEALHIP_SCHEME_CKKS, 12, std::uint32_t(nk), 1, mods, 0ULL, SEALHIP_MODE_PARITY, device };
         Context ctx(p);
         std::uint64_t state = 0x4021;
         const double scale = 1099511627776.0, scale_out = 274877906944.0; // 2^40, 2^38
         HostCiphertext ct = host_ct(2, k, n, true, scale);
-        for (std::size_t r = 0; r < 2 * k; r++)
-            for (std::size_t i = 0; i < n; i++)
-                ct.words[r * n + i] = splitmix(state) % mods[r % k];
-        std::vector<std::uint64_t> w(nd * 2 * nk * n);
-        for (std::size_t r = 0; r < nd * 2 * nk; r++)
-            for (std::size_t i = 0; i < n; i++)
-                w[r * n + i] = splitmix(state) % mods[r % nk];
-        KSwitchKeys key(ctx, w.data(), std::uint32_t(nd));
+        fill_rows(ct.words.data(), 2 * k, n, mods, k, state);
+        const std::unique_ptr<KSwitchKeys> seeded = seeded_key(ctx, nd, nk, n, mods, state);
+        const KSwitchKeys &key = *seeded;
         const Keys keys{ &key };
         const Doubles coeffs{ 0.5, -0.25, 0.125, 0.75, -0.5, 0.0625, 0.3125, -0.875 };
         sealhip_poly_plan plan{};
@@ -136,10 +79,10 @@ int main(int argc, char **argv)
             return 3;
         Evaluator<HostCiphertext> ev(ctx);
         auto report = [&](const char *what, const HostCiphertext &c, double want_scale) {
-            const std::uint64_t h = digest(0xcbf29ce484222325ULL, c.data(), c.words.size());
+            const std::uint64_t h = digest(c.words);
             const bool meta = c.size() == 2 && c.coeff_modulus_size() == plan.out_level && c.is_ntt_form() &&
                               c.words.size() == 2 * plan.out_level * n && c.scale() == want_scale;
-            std::printf("%s digest %016llx meta %d\n", what, static_cast<unsigned long long>(h), int(meta));
+            print_digest(what, h, meta);
         };
         HostCiphertext out;
         ev.evaluate_polynomial(ct, coeffs, keys, out);

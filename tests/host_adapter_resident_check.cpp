@@ -7,29 +7,15 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
 
 namespace
 {
-    std::uint64_t splitmix(std::uint64_t &s)
-    {
-        std::uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-        return z ^ (z >> 31);
-    }
-
     unsigned long long digest(const HostCiphertext &ct)
     {
-        std::uint64_t h = 0xcbf29ce484222325ULL;
-        for (std::uint64_t w : ct.words)
-            for (int i = 0; i < 8; i++)
-            {
-                h ^= (w >> (8 * i)) & 0xff;
-                h *= 0x100000001b3ULL;
-            }
-        return (unsigned long long)h;
+        return (unsigned long long)adapter_check::digest(ct.words);
     }
 
     HostCiphertext down(const DeviceCiphertext &d)
@@ -63,14 +49,8 @@ namespace
     // the words of a random size-2 ciphertext at level k
     HostCiphertext random_ct(std::uint64_t &state, const std::uint64_t *mods, std::size_t n, std::size_t k, bool ntt)
     {
-        HostCiphertext ct;
-        ct.n_ = n;
-        ct.resize_raw(2, k);
-        for (std::size_t s = 0; s < 2; s++)
-            for (std::size_t r = 0; r < k; r++)
-                for (std::size_t c = 0; c < n; c++)
-                    ct.words[(s * k + r) * n + c] = splitmix(state) % mods[r];
-        ct.is_ntt_form() = ntt;
+        HostCiphertext ct = host_ct(2, k, n, ntt);
+        fill_rows(ct.words.data(), 2 * k, n, mods, k, state);
         return ct;
     }
 
@@ -436,11 +416,7 @@ int main(int argc, char **argv)
         std::uint64_t state = 0xC0FFEE + 1;
         // the survey generator's fill order (keys first), as tests/host_adapter_check.cpp
         std::vector<std::uint64_t> key(2 * 2 * 3 * n);
-        for (std::size_t d = 0; d < 2; d++)
-            for (std::size_t l = 0; l < 2; l++)
-                for (std::size_t r = 0; r < 3; r++)
-                    for (std::size_t c = 0; c < n; c++)
-                        key[((d * 2 + l) * 3 + r) * n + c] = splitmix(state) % mods[r];
+        fill_rows(key.data(), 2 * 2 * 3, n, mods, 3, state);
         const HostCiphertext a = random_ct(state, mods, n, k, false), b = random_ct(state, mods, n, k, false);
         Evaluator<HostCiphertext> ev(ctx);
         KSwitchKeys rk(ctx, key.data(), 2);

@@ -15,20 +15,9 @@
 #include <cstring>
 
 #include "../gemini-seal_amd/host/evaluator.hpp"
+#include "adapter_check.hpp"
 
 using namespace sealhip_host;
-
-static std::uint64_t digest(const std::uint64_t *w, std::size_t words)
-{
-    std::uint64_t h = 0xcbf29ce484222325ULL;
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(w);
-    for (std::size_t i = 0; i < words * 8; i++)
-    {
-        h ^= p[i];
-        h *= 0x100000001b3ULL;
-    }
-    return h;
-}
 
 static const std::uint64_t kBase = 0x5EED000000000000ULL, kStep = 0x9E3779B97F4A7C15ULL;
 
@@ -47,25 +36,6 @@ static void seed_number(std::size_t i, std::uint64_t *seed)
             return 1;                                          \
         }                                                      \
     } while (0)
-
-template <class E, class F>
-static bool throws(F &&f)
-{
-    try
-    {
-        f();
-    }
-    catch (const E &)
-    {
-        return true;
-    }
-    catch (const std::exception &e)
-    {
-        std::printf("wrong exception: '%s'\n", e.what());
-        return false;
-    }
-    return false;
-}
 
 static int host_checks()
 {

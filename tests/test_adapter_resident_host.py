@@ -3,13 +3,10 @@ Python mirrors; their argument checks on a host-only context (E_POINTER first, t
 COR_E_INVALIDOPERATION); and the resident check program compiled and linked against the header
 (on a host-only context it only checks that the pool refuses resident work)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
+from support import compile_cpp, run_exe
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NEW = ("sealhip_pool_alloc", "sealhip_pool_release", "sealhip_pool_trim", "sealhip_pool_stats", "sealhip_memcpy_d2d",
        "sealhip_transparency_note")
 MODS = [1073738753, 1099511603713, 1152921504606830593]
@@ -66,9 +63,5 @@ def test_pool_entries_on_host_only_context():
 
 
 def test_cpp_resident_check_builds_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_resident_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(HERE, "host_adapter_resident_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only resident checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_resident_check.cpp", link_sealhip=True, opt="-O1")
+    assert "host-only resident checks ok" in run_exe(exe, timeout=120)

@@ -5,7 +5,6 @@ the sanitizers as a stand-alone program (tests/evalmod_plan_check.cpp); the argu
 eval_mod on host-only contexts in the header's order."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from numpy.polynomial import chebyshev as NC
 import bootstrap_ref as B
 import oracle_lib as O
 import poly_eval_ckks_ref as PC
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -146,12 +146,8 @@ def test_plan_refusals_on_host_only_context(host):
 
 
 def test_plan_header_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "evalmod_plan_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "gemini-seal_amd", "csrc"), "-o", exe,
-                           os.path.join(HERE, "evalmod_plan_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "evalmod_plan_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "evalmod_plan_check.cpp", sanitize=True)
+    assert "evalmod_plan_check: OK" in run_exe(exe, timeout=300)
 
 
 # ------------------------------------------------------------------ the calls' checks on host-only contexts
@@ -245,12 +241,8 @@ def test_double_angle_and_eval_mod_checks_on_host_only_context(host):
 def test_cpp_adapter_on_host_only_context(tmp_path):
     """tests/host_adapter_bootstrap_check.cpp "host": the plans' refusals and the operand checks arrive before the missing
     device does"""
-    exe = str(tmp_path / "host_adapter_bootstrap_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_bootstrap_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only bootstrap checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_bootstrap_check.cpp", link_sealhip=True)
+    assert "host-only bootstrap checks ok" in run_exe(exe, "host", timeout=120)
 
 
 def test_bootstrap_plan_on_host_only_context(host):

@@ -3,17 +3,14 @@ without a GPU. The exports and their Python mirrors; the restatement of invarian
 planted budgets and, on oracle-only ciphertexts, against the semantics the reference promises; the C++ Decryptor's host
 checks; and the argument checks of both entries on host-only contexts."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import noise_ref as R
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NEW = ("sealhip_decryptor_invariant_noise_budget", "sealhip_decryptor_decrypt")
 
 
@@ -116,12 +113,8 @@ def test_semantics_size_three():
 
 
 def test_cpp_decryptor_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_decrypt_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_decrypt_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only decrypt checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_decrypt_check.cpp", link_sealhip=True)
+    assert "host-only decrypt checks ok" in run_exe(exe, timeout=120)
 
 
 def test_entries_on_host_only_context():

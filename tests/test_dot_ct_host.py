@@ -4,7 +4,6 @@ of terms against its Python-integer form; the 128-bit capacity of the kernel's s
 restatement (tests/dot_ct_ref.py) itself: one term is ref_bfv_multiply, 17 terms decrypt to sum m_a m_b."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import dot_ct_ref as D
 import noise_ref as R
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -242,16 +242,10 @@ def test_ckks_restatement_is_linear_in_the_terms():
 
 def test_sum_capacity_bounds_program(tmp_path):
     """ntt_bounds.hpp section 8 (dot_group_admits) and the kernel's accumulation against exact arithmetic"""
-    exe = str(tmp_path / "dot_ct_bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "dot_ct_bounds_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "dot_ct_bounds_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "dot_ct_bounds_check.cpp")
+    assert "dot_ct_bounds_check: OK" in run_exe(exe, timeout=120)
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_dot_ct_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_dot_ct_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only dot_ct checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_dot_ct_check.cpp", link_sealhip=True)
+    assert "host-only dot_ct checks ok" in run_exe(exe, "host", timeout=120)

@@ -4,16 +4,13 @@ contexts; the C++ Encryptor's host checks; and, on the oracle alone, the level r
 (encryptor.cpp:141-176): with nsp special primes the zero encryption runs over the k_first + 1 primes of the previous level,
 not over the n_key key primes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NEW = ("sealhip_encryptor_encrypt", "sealhip_encryptor_encrypt_symmetric", "sealhip_ciphertext_save_seeded")
 MODS = [1073738753, 1099511603713, 1152921504606830593, 1152921504606844417]
 
@@ -105,12 +102,8 @@ def test_seeded_save_on_host_only_context():
 
 
 def test_cpp_encryptor_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_encrypt_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(HERE, "host_adapter_encrypt_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only encrypt checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_encrypt_check.cpp", link_sealhip=True, opt="-O1")
+    assert "host-only encrypt checks ok" in run_exe(exe, timeout=120)
 
 
 def _compose(ref, cl, pk, rows, k, u, e, plain):

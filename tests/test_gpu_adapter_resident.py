@@ -7,28 +7,19 @@ Python: same-lane reuse, cross-lane ordering, bad releases, a miss or a release 
 the size classes."""
 import json
 import os
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import S, compile_cpp, run_exe
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 DIG = json.load(open(os.path.join(HERE, "golden", "survey_digests.json")))
 MODS = [68719230977, 68719403009, 137438822401]  # cfg1: N = 4096, {36, 36, 37}
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def ctx_of(S):
@@ -36,24 +27,20 @@ def ctx_of(S):
 
 
 def test_cpp_resident_adapter(S, tmp_path):
-    exe = str(tmp_path / "host_adapter_resident_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_resident_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
+    exe = compile_cpp(tmp_path, "host_adapter_resident_check.cpp", link_sealhip=True)
     cfg3 = [r for r in DIG["end_to_end"] if r["cfg"] == 3][0]
     mods3 = O.coeff_modulus_create(1 << 15, cfg3["bits"])
-    out = subprocess.run([exe, "0"] + [str(q) for q in mods3], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
+    stdout = run_exe(exe, "0", *mods3, timeout=600)
     # Encryptor / Decryptor resident overloads equal the host ones and round-trip; DevicePlaintext operations equal the host
     # plaintext forms; the cfg3 encrypt -> ... -> decrypt chain makes no allocator call on its second pass
     for tag in ("cfg1", "cfg3"):
         for what in ("client", "device plaintext", "warm chain"):
-            assert "%s %s ok" % (what, tag) in out.stdout, out.stdout
+            assert "%s %s ok" % (what, tag) in stdout, stdout
     want = [r for r in DIG["end_to_end"] if r["cfg"] == 1][0]["digests"]["modswitch"]
-    assert "resident modswitch digest " + want in out.stdout, out.stdout
+    assert "resident modswitch digest " + want in stdout, stdout
     for line in ("resident equals host ok", "wire ok"):
-        assert line in out.stdout, out.stdout
-    assert "warm pool ok" in out.stdout and "transparency ok" in out.stdout, out.stdout
+        assert line in stdout, stdout
+    assert "warm pool ok" in stdout and "transparency ok" in stdout, stdout
     # the automorphism of the resident path (equal to the host one inside the check) against the oracle's apply_galois on
     # the same words: the check's BFV operand at k = 2 (splitmix64 from seed 13), the survey's cfg1 key
     import ctypes as C
@@ -75,10 +62,7 @@ def test_cpp_resident_adapter(S, tmp_path):
     L = O.lib()
     elt = L.ref_galois_elt_from_step(n, 1, None)
     assert L.ref_apply_galois_inplace(C.byref(ref.c), k, O.ptr(x), elt, O.ptr(inp["rk"])) == 0
-    fnv = 0xcbf29ce484222325
-    for byte in x.tobytes():
-        fnv = ((fnv ^ byte) * 0x100000001b3) & mask
-    assert "apply_galois 1 digest %016x" % fnv in out.stdout, out.stdout
+    assert "apply_galois 1 digest %016x" % O.fnv(x) in stdout, stdout
 
 
 def test_same_lane_reuse_is_a_hit(S):

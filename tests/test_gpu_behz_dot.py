@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import S as sealhip
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +24,6 @@ TOP, ALT, ZERO, RANDOM = 0, 1, 2, 3
 # (a, b) per item: multiply sees every pattern in both operands over the two triples; square reads a only
 ITEMS = (((TOP, TOP), (ALT, RANDOM), (RANDOM, ZERO)), ((TOP, ALT), (ZERO, TOP), (RANDOM, RANDOM)))
 SQUARE_ITEMS = ((TOP, TOP), (ALT, ALT), (RANDOM, RANDOM)), ((ZERO, ZERO), (ALT, ALT), (TOP, TOP))
-
-
-@pytest.fixture(scope="module")
-def sealhip():
-    import sealhip as S
-
-    assert S.num_devices() >= 1, "no HIP device visible: the engine has no CPU fallback"
-    return S
 
 
 @pytest.fixture(scope="module")

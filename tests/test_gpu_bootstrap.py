@@ -8,8 +8,6 @@ _bootstrap.
 2. The double-angle step, word for word against the three entries it merges, issued one by one; EvalMod against the
    polynomial evaluator followed by double_angle calls; the bootstrap end to end with real keys and a sparse secret.
 3. Boundary behaviour: the header's refusals, the empty batch, host-only contexts, transparency flags, graph capture."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,26 +17,9 @@ import hoist_ref as H
 import homdft_ref as R
 import oracle_lib as O
 import poly_eval_ckks_ref as PC
+from support import S, compile_cpp, rows, run_exe
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
 
 
 # ------------------------------------------------------------------ 1. ModRaise
@@ -66,7 +47,7 @@ def _raise_case(logn, primes, k_in, k_out, count):
         mods = _prime_set(primes, logn)
         ref = O.RefContext(2, logn, mods, nsp=1, t=0, mode=0)
         rng = np.random.default_rng(1000 * logn + 10 * k_in + count)
-        ct = _rows(rng, mods[:k_in], n, (count, 2))
+        ct = rows(rng, mods[:k_in], n, (count, 2))
         # the q_0 row of component 0 of the last item: the centring's edges in coefficient form, then transformed
         q0 = mods[0]
         coef = rng.integers(0, q0, size=n, dtype=np.uint64)
@@ -152,10 +133,10 @@ def test_double_angle_words(S, logn, bits, nsp, k, mode):
     k_first = len(mods) - nsp
     nd = (k_first + nsp - 1) // nsp
     rng = np.random.default_rng(17 * logn + k + nsp)
-    rk = [S.KSwitchKeys(ctx, _rows(rng, mods, n, (nd, 2)))]
+    rk = [S.KSwitchKeys(ctx, rows(rng, mods, n, (nd, 2)))]
     for count in (1, 5):
         for scale in (2.0 ** 40, 2.0 ** 53.6):  # the second one's square exceeds 2^64
-            ct = _rows(rng, mods[:k], n, (count, 2))
+            ct = rows(rng, mods[:k], n, (count, 2))
             d_ct, d_out = ctx.upload(ct), ctx.alloc(count * 2 * (k - 1) * n)
             out_scale = ev.double_angle(d_ct, k, count, scale, rk, d_out)
             assert out_scale == scale * scale / float(mods[k - 1])
@@ -172,12 +153,12 @@ def test_eval_mod_words(S, K, r, d, n_baby, k):
     ctx = S.Context(S.SCHEME_CKKS, logn, mods, 2, 0)
     ev = S.Evaluator(ctx)
     rng = np.random.default_rng(100 * K + d)
-    rk = [S.KSwitchKeys(ctx, _rows(rng, mods, n, ((k + 1) // 2, 2)))]
+    rk = [S.KSwitchKeys(ctx, rows(rng, mods, n, ((k + 1) // 2, 2)))]
     s_x = 2.0 ** 50
     plan = ev.evalmod_plan(k, s_x, K, r, d, n_baby=n_baby)
     assert plan["out_level"] == plan["poly_level"] - r >= 1
     for count in (1, 2):
-        d_ct = ctx.upload(_rows(rng, mods[:k], n, (count, 2)))
+        d_ct = ctx.upload(rows(rng, mods[:k], n, (count, 2)))
         out = ctx.alloc(count * 2 * plan["out_level"] * n)
         level, scale = ev.eval_mod(d_ct, k, count, s_x, K, r, d, rk, out, n_baby=n_baby)
         assert (level, scale) == (plan["out_level"], plan["out_scale"])
@@ -318,8 +299,8 @@ def test_checks_flags_capture(S):
     ev = S.Evaluator(ctx)
     rng = np.random.default_rng(3)
     count = 3
-    rk = [S.KSwitchKeys(ctx, _rows(rng, mods, n, (4, 2)))]
-    ct = _rows(rng, mods[:k], n, (count, 2))
+    rk = [S.KSwitchKeys(ctx, rows(rng, mods, n, (4, 2)))]
+    ct = rows(rng, mods[:k], n, (count, 2))
     d_ct = ctx.upload(ct)
     up, down = ctx.alloc(count * 2 * 4 * n), ctx.alloc(count * 2 * (k - 1) * n)
     # ---- mod_raise: levels, overlap, alignment, the scheme
@@ -354,7 +335,7 @@ def test_checks_flags_capture(S):
         ev.double_angle(d_ct, k, count, 2.0 ** 30, [], down)
     with pytest.raises(TypeError):
         ev.double_angle(d_ct, k, count, 2.0 ** 30, None, down)
-    short = [S.KSwitchKeys(ctx, _rows(rng, mods, n, (3, 2)))]
+    short = [S.KSwitchKeys(ctx, rows(rng, mods, n, (3, 2)))]
     with pytest.raises(ValueError, match="not valid for encryption parameters"):
         ev.double_angle(d_ct, k, count, 2.0 ** 30, short, down)
     with pytest.raises(ValueError, match="overlap"):
@@ -381,7 +362,7 @@ def test_checks_flags_capture(S):
     ev.double_angle(d_z, k, count, 2.0 ** 30, rk, down)
     assert list(flags.download().view(np.uint32)[:count] != 0) == [True, False, True]
     with pytest.raises(ValueError, match="transparency sink"):
-        ev.mod_raise(ctx.upload(_rows(rng, mods[:1], n, (9, 2))), 1, 9, 2, ctx.alloc(9 * 2 * 2 * n))
+        ev.mod_raise(ctx.upload(rows(rng, mods[:1], n, (9, 2))), 1, 9, 2, ctx.alloc(9 * 2 * 2 * n))
     ctx.transparency_sink(None, 0)
     # ---- graph capture after one warm-up: a replay gives the eager words
     ev.mod_raise(d_ct, k, count, 4, up)
@@ -403,11 +384,7 @@ def test_cpp_adapter(tmp_path):
     """tests/host_adapter_bootstrap_check.cpp: the host-ciphertext and the DeviceCiphertext forms of mod_raise, double_angle,
     eval_mod and bootstrap give the C ABI's words on the same seeded inputs, at the plans' levels and scales; the operand
     checks and their messages"""
-    exe = str(tmp_path / "host_adapter_bootstrap_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_bootstrap_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
+    exe = compile_cpp(tmp_path, "host_adapter_bootstrap_check.cpp", link_sealhip=True)
     q0 = O.get_primes(256, 40, 1)[0]
     mods = [q0] + _primes_next_to(2 * q0, 8, 9) + O.get_primes(256, 59, 1)
-    out = subprocess.run([exe, "0"] + [str(p) for p in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "bootstrap adapter checks ok" in out.stdout, out.stdout + out.stderr
+    assert "bootstrap adapter checks ok" in run_exe(exe, "0", *mods, timeout=120)

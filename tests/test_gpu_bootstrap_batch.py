@@ -15,7 +15,8 @@ import pytest
 
 import hoist_ref as H
 import oracle_lib as O
-from test_gpu_bootstrap import _primes_next_to, _rows, _three_entry_chain
+from test_gpu_bootstrap import _primes_next_to, _three_entry_chain
+from support import S, rows
 
 pytestmark = pytest.mark.gpu
 
@@ -24,17 +25,10 @@ K_TOP, STAGES, K, R, D = 11, [4, 3], 2, 2, 7
 SENTINEL = 0xA5A5A5A5
 
 
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
 class _Session:
     """q_0 of 40 bits, ten primes next to 2 q_0, one 59-bit special prime: ModRaise to level 11, CoeffToSlot [4,3] to 9,
-    EvalMod (K 2, r 2, degree 7) to 3, SlotToCoeff [4,3] to 1. Random keys for the plan's steps."""
+    EvalMod (K 2, r 2, degree 7) to 3, SlotToCoeff [4,3] to 1. Random keys for the plan's steps. (Not a BaseSession: the
+    primes are picked one by one and there is no oracle side.)"""
 
     def __init__(self, S):
         q0 = O.get_primes(N, 40, 1)[0]
@@ -52,7 +46,7 @@ class _Session:
     def key(self, ctx, digits=None):
         import sealhip
 
-        return sealhip.KSwitchKeys(ctx, _rows(self.rng, self.mods, N, (digits or self.nd, 2)))
+        return sealhip.KSwitchKeys(ctx, rows(self.rng, self.mods, N, (digits or self.nd, 2)))
 
 
 @pytest.fixture(scope="module")
@@ -74,7 +68,7 @@ def test_bootstrap_batch_words_flags_pool(S, se):
     ctx, ev, per_item = se.ctx, se.ev, se.plan["temp_bytes_per_item"]
     assert ctx.pool_stats()["bytes_in_use"] == 0
     count, k_in = 3, 2
-    ct = _rows(se.rng, se.mods[:k_in], N, (count, 2))
+    ct = rows(se.rng, se.mods[:k_in], N, (count, 2))
     ct[1] = 0  # a transparent item: it stays one through every part
     tables = S.BootstrapTables(ctx, K_TOP, STAGES, STAGES, K, R, D)
     assert ctx.pool_stats()["bytes_in_use"] == 0, "the block is taken on first use"
@@ -95,7 +89,7 @@ def test_bootstrap_batch_words_flags_pool(S, se):
         got = out.download((count, 2, 1, N))
         assert _flags(flags, count) == [True, False, True]
         with pytest.raises(ValueError, match="transparency sink"):
-            ev.bootstrap(tables, ctx.upload(_rows(se.rng, se.mods[:1], N, (4, 2))), 1, 4, se.gk, se.rk, ctx.alloc(4 * 2 * N))
+            ev.bootstrap(tables, ctx.upload(rows(se.rng, se.mods[:1], N, (4, 2))), 1, 4, se.gk, se.rk, ctx.alloc(4 * 2 * N))
     finally:
         ctx.transparency_sink(None, 0)
     held_3 = ctx.pool_stats()["bytes_in_use"]
@@ -110,7 +104,7 @@ def test_bootstrap_batch_words_flags_pool(S, se):
 
 def test_eval_mod_flags(S, se):
     ctx, ev, k, count = se.ctx, se.ev, 9, 3
-    ct = _rows(se.rng, se.mods[:k], N, (count, 2))
+    ct = rows(se.rng, se.mods[:k], N, (count, 2))
     ct[1] = 0
     plan = ev.evalmod_plan(k, se.plan["raise_scale"], K, R, D)
     assert plan["out_level"] == 3
@@ -121,7 +115,7 @@ def test_eval_mod_flags(S, se):
         ev.eval_mod(ctx.upload(ct), k, count, se.plan["raise_scale"], K, R, D, se.rk, out)
         assert _flags(flags, count) == [True, False, True]
         with pytest.raises(ValueError, match="transparency sink"):
-            ev.eval_mod(ctx.upload(_rows(se.rng, se.mods[:k], N, (4, 2))), k, 4, se.plan["raise_scale"], K, R, D, se.rk,
+            ev.eval_mod(ctx.upload(rows(se.rng, se.mods[:k], N, (4, 2))), k, 4, se.plan["raise_scale"], K, R, D, se.rk,
                         ctx.alloc(4 * 2 * 3 * N))
     finally:
         ctx.transparency_sink(None, 0)
@@ -131,7 +125,7 @@ def test_eval_mod_flags(S, se):
 def test_bootstrap_refusals(S, se):
     ctx, ev, gk, rk = se.ctx, se.ev, se.gk, se.rk
     count, k_in = 2, 2
-    ct = _rows(se.rng, se.mods[:k_in], N, (count, 2))
+    ct = rows(se.rng, se.mods[:k_in], N, (count, 2))
     d_ct, out = ctx.upload(ct), ctx.alloc(count * 2 * N)
     tables = S.BootstrapTables(ctx, K_TOP, STAGES, STAGES, K, R, D)
     # ---- NULL pointers
@@ -192,7 +186,7 @@ def test_bootstrap_refusals(S, se):
 def test_eval_mod_refusals(S, se):
     ctx, ev, rk, k, count = se.ctx, se.ev, se.rk, 9, 2
     s_x = se.plan["raise_scale"]
-    d_ct, out = ctx.upload(_rows(se.rng, se.mods[:k], N, (count, 2))), ctx.alloc(count * 2 * 3 * N)
+    d_ct, out = ctx.upload(rows(se.rng, se.mods[:k], N, (count, 2))), ctx.alloc(count * 2 * 3 * N)
     with pytest.raises(TypeError):
         ev.eval_mod(None, k, count, s_x, K, R, D, rk, out)
     with pytest.raises(TypeError):
@@ -237,7 +231,7 @@ def test_eval_mod_refusals(S, se):
 def test_double_angle_alignment(S, se):
     """square_affine_kernel loads ct two words at a time: the entry refuses a ct that is not 16-byte aligned"""
     ctx, ev, k = se.ctx, se.ev, 3
-    d_ct, out = ctx.upload(_rows(se.rng, se.mods[:k], N, (2, 2))), ctx.alloc(2 * 2 * N)
+    d_ct, out = ctx.upload(rows(se.rng, se.mods[:k], N, (2, 2))), ctx.alloc(2 * 2 * N)
     with pytest.raises(ValueError, match="ct must be 16-byte aligned"):
         ev.double_angle(d_ct.ptr + 8, k, 1, 2.0 ** 40, se.rk, out)
     with pytest.raises(ValueError, match="ct must be 16-byte aligned"):
@@ -256,9 +250,9 @@ def test_double_angle_words_61_bit_primes(S, mode):
     ctx = S.Context(S.SCHEME_CKKS, logn, mods, 1, 0, mode=mode)
     ev = S.Evaluator(ctx)
     rng = np.random.default_rng(61)
-    rk = [S.KSwitchKeys(ctx, _rows(rng, mods, n, (3, 2)))]
+    rk = [S.KSwitchKeys(ctx, rows(rng, mods, n, (3, 2)))]
     for count in (1, 5):
-        ct = _rows(rng, mods[:k], n, (count, 2))
+        ct = rows(rng, mods[:k], n, (count, 2))
         ct[0, :, :, :4] = np.array([p - 1 for p in data], dtype=np.uint64)[None, :, None]  # the largest residues
         for scale in (2.0 ** 40, 2.0 ** 53.6):
             d_ct, d_out = ctx.upload(ct), ctx.alloc(count * 2 * (k - 1) * n)

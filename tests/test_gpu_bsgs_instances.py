@@ -13,6 +13,7 @@ import pytest
 import hoist_bsgs_ref as HB
 import hoist_ref as H
 import oracle_lib as O
+from support import top
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,6 @@ LOGN, N = 10, 1 << 10
 BITS = [61] * 17
 COUNT, ITEMS = 5, (0, 4)
 LEVELS = {"1_4": range(1, 5), "5_8": range(5, 9), "9_12": range(9, 13), "13_16": range(13, 17)}
-
-
-def _top(mods, n, lead):
-    """every word p - 1"""
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = p - 1
-    return out
 
 
 def giants(n):
@@ -49,7 +42,7 @@ def session():
     mods = O.coeff_modulus_create(N, BITS)
     ctx = S.Context(S.SCHEME_CKKS, LOGN, mods, 1, 0)
     ref = O.RefContext(2, LOGN, mods, nsp=1)
-    key = _top(mods, N, (16, 2))
+    key = top(mods, N, (16, 2))
     # every row of the key is constant, so sigma_{g^-1} of it (H.hoisted_key) is the key itself
     assert np.array_equal(H.hoisted_key(ref, key, 3), key)
     return S, mods, ctx, ref, S.Evaluator(ctx), key, S.KSwitchKeys(ctx, key)
@@ -60,10 +53,10 @@ def test_sixteen_giants_in_one_launch_at_every_instance(session, levels):
     S, mods, ctx, ref, ev, key, dkey = session
     giant = giants(N)
     baby = [giant[2], 1]
-    plains = _top(mods, N, (len(giant), len(baby)))
+    plains = top(mods, N, (len(giant), len(baby)))
     dp = ctx.upload(plains)
     for k in LEVELS[levels]:
-        ct = _top(mods[:k], N, (COUNT, 2))
+        ct = top(mods[:k], N, (COUNT, 2))
         d = ctx.upload(ct)
         out = ctx.alloc(COUNT * 2 * k * N)
         ctx.profile_enable(True)

@@ -9,7 +9,6 @@ Shapes: N = 2^13, 8 ciphertext primes and 1 special prime. An operation's chunk 
 batch is just over 64 MiB of temporaries whatever the level; the counts below are one or two items past a whole chunk."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,21 +16,11 @@ import pytest
 
 import noise_ref as R
 import oracle_lib as O
+from support import ARENA_MB, child_main, rows, run_arena_child
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 LOGN, N, T = 13, 1 << 13, 786433
-ARENA_MB = "64"
-
-
-def _rows(rng, mods, count):
-    """count x len(mods) x N canonical residues"""
-    out = np.empty((count, len(mods), N), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[:, r] = rng.integers(0, int(p), size=(count, N), dtype=np.uint64)
-    return out
 
 
 def _item(S, ctx, buf, index, words):
@@ -63,7 +52,7 @@ def _child():
 
     # ---- Evaluator::rescale_to_next (CKKS): the log counts polynomials
     k, count = kf, 65
-    x = _rows(rng, mods[:k], count * 2).reshape(count, 2, k, N)
+    x = rows(rng, mods[:k], N, (count * 2,)).reshape(count, 2, k, N)
     out = ckks.alloc(count * 2 * (k - 1) * N)
     ckks.chunk_log()
     S.Evaluator(ckks).rescale_to_next(ckks.upload(x), 2, k, count, out)
@@ -76,7 +65,7 @@ def _child():
 
     # ---- divide_and_round_q_last_ntt_inplace
     k, count = kf, 147
-    x = _rows(rng, mods[:k], count)
+    x = rows(rng, mods[:k], N, (count,))
     d = ckks.upload(x)
     ckks.chunk_log()
     ckks.divide_and_round_q_last_ntt_inplace(k, d, count)
@@ -90,7 +79,7 @@ def _child():
 
     # ---- rescale_special_rns_inplace (BFV: the q rows go back to coefficient form)
     k, count = kf, 129
-    x = _rows(rng, mods, count)
+    x = rows(rng, mods, N, (count,))
     d = bfv.upload(x)
     bfv.chunk_log()
     bfv.rescale_special_rns_inplace(k, d, count)
@@ -106,7 +95,7 @@ def _child():
     k, size, count = 5, 3, 103
     pw = R.random_sk_powers(mods, LOGN, size - 1, rng)
     dpw = bfv.upload(pw)
-    x = _rows(rng, mods[:k], count * size).reshape(count, size, k, N)
+    x = rows(rng, mods[:k], N, (count * size,)).reshape(count, size, k, N)
     out = bfv.alloc(count * k * N)
     d = bfv.upload(x)
     bfv.chunk_log()
@@ -153,18 +142,18 @@ def _child():
     done += ["invariant_noise_budget", "decrypt"]
 
     # ---- util::encrypt_zero_asymmetric, both forms of the result
-    rows, count = kf, 129
-    pk = _rows(rng, mods[:rows], 2)
+    n_rows, count = kf, 129
+    pk = rows(rng, mods[:n_rows], N, (2,))
     u = rng.integers(-1, 2, size=(count, N)).astype(np.int32)
     e = rng.integers(-19, 20, size=(count, 2, N)).astype(np.int32)
     dpk, du, de = bfv.upload(pk), bfv.upload_i32(u), bfv.upload_i32(e)
-    out = bfv.alloc(count * 2 * rows * N)
+    out = bfv.alloc(count * 2 * n_rows * N)
     for ntt_form in (False, True):
         bfv.chunk_log()
-        bfv.encrypt_zero_asymmetric(rows, ntt_form, dpk, du, de, count, out)
+        bfv.encrypt_zero_asymmetric(n_rows, ntt_form, dpk, du, de, count, out)
         for i in _boundary(bfv, count):
-            exp = np.zeros((2, rows, N), dtype=np.uint64)
-            L.ref_encrypt_zero_asymmetric_given(C.byref(rbfv.c), rows, O.ptr(pk), 1 if ntt_form else 0, O.ptr(u[i]),
+            exp = np.zeros((2, n_rows, N), dtype=np.uint64)
+            L.ref_encrypt_zero_asymmetric_given(C.byref(rbfv.c), n_rows, O.ptr(pk), 1 if ntt_form else 0, O.ptr(u[i]),
                                                 O.ptr(e[i]), O.ptr(exp))
             assert np.array_equal(_item(S, bfv, out, i, exp.size), exp.reshape(-1)), ("encrypt_zero_asymmetric", ntt_form, i)
     out.free()
@@ -197,7 +186,7 @@ def _child():
     plain.free()
     done.append("ckks_encode")
     count = 257
-    x = _rows(rng, mods[:k], count)
+    x = rows(rng, mods[:k], N, (count,))
     d = ckks.upload(x)
     ckks.chunk_log()
     dec = ckks.ckks_decode(d, k, count, scale)
@@ -209,8 +198,8 @@ def _child():
 
 
 def test_ops_span_arena_chunks():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    code = "import sys; sys.path[:0] = %r; import test_gpu_chunked_ops as T; T._child()" % (
-        [HERE, ROOT, os.path.join(ROOT, "gemini-seal_amd")],)
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHUNKED_OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    run_arena_child(__file__, "CHUNKED_OK", timeout=600)
+
+
+if __name__ == "__main__" and "--child" in sys.argv:
+    child_main(_child)

@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import S as sealhip
 
 pytestmark = pytest.mark.gpu
 
@@ -208,14 +209,6 @@ class Side:
         assert -2 in rc and set(rc) <= {0, -2}, (what, "the oracle does not refuse it", rc)
         with pytest.raises(ValueError, match="encoded values are too large"):
             self.ctx.ckks_encode(values, k, scale)
-
-
-@pytest.fixture(scope="module")
-def sealhip():
-    import sealhip as S
-
-    assert S.num_devices() >= 1, "no HIP device visible: the engine has no CPU fallback"
-    return S
 
 
 @pytest.fixture(scope="module")

@@ -4,28 +4,17 @@ tests/noise_ref.py (rings 2^12..2^16, every limb instance of the kernel and both
 sealhip_decryptor_decrypt bit-exact against the oracle (BFV and CKKS), the error codes, an end-to-end STRICT chain, and the
 C++ Decryptor on the device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import noise_ref as R
 import oracle_lib as O
+from support import S, compile_cpp, run_exe
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 T = 786433
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def planted_items(n, q, rng):
@@ -252,13 +241,6 @@ def _dot(cl, ct):
     return dot
 
 
-def _fnv(words):
-    h = 0xCBF29CE484222325
-    for b in np.ascontiguousarray(words, dtype=np.uint64).tobytes():
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
 @pytest.mark.parametrize("scheme", [1, 2])
 def test_cpp_decryptor_on_device(S, tmp_path, scheme):
     """the adapter's budgets and plaintext digests (batch and one by one) equal the C ABI's for the same inputs"""
@@ -286,16 +268,13 @@ def test_cpp_decryptor_on_device(S, tmp_path, scheme):
                            ct.reshape(-1)])
     path = str(tmp_path / "in.bin")
     blob.astype(np.uint64).tofile(path)
-    exe = str(tmp_path / "host_adapter_decrypt_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_decrypt_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0", path], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "device decrypt ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_decrypt_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", path, timeout=300)
+    assert "device decrypt ok" in stdout, stdout
     ctx = S.Context(scheme, logn, mods, 1, t)
     pw = ctx.upload(cl.sk_powers(size - 1))
     dct = ctx.upload(ct)
-    lines = out.stdout.split("\n")
+    lines = stdout.split("\n")
     if scheme == 1:
         budgets = ctx.invariant_noise_budget(dct, size, k, count, pw)
         assert [f"budget {i} {int(b)}" for i, b in enumerate(budgets)] == [x for x in lines if x.startswith("budget")]
@@ -311,5 +290,5 @@ def test_cpp_decryptor_on_device(S, tmp_path, scheme):
         plain = ctx.alloc(count * k * n)
         ctx.decrypt(dct, size, k, count, pw, True, plain)
         trimmed = list(plain.download((count, k * n)))
-    assert [f"plain {i} {len(w)} {_fnv(w)}" for i, w in enumerate(trimmed)] == [x for x in lines if x.startswith("plain")]
+    assert [f"plain {i} {len(w)} {O.fnv(w)}" for i, w in enumerate(trimmed)] == [x for x in lines if x.startswith("plain")]
     ctx.close()

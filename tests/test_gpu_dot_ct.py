@@ -8,7 +8,6 @@ and 5 terms are one group, 17 a full group and a group of one that adds the part
 not group items; three items with an odd row count give a last block that is not full."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,40 +15,17 @@ import pytest
 
 import dot_ct_ref as D
 import oracle_lib as O
+from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe, session_memo
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
-
-
-class Session:
+class Session(BaseSession):
     """contexts on both sides and a random key: the word-for-word comparison needs no valid key"""
 
     def __init__(self, S, scheme, logn, bits, nsp, mode, t=0, seed=0):
-        self.S, self.n, self.nsp = S, 1 << logn, nsp
-        self.mods = O.coeff_modulus_create(self.n, bits)
-        self.ctx = S.Context(scheme, logn, self.mods, nsp, t, mode=mode)
-        self.ref = O.RefContext(scheme, logn, self.mods, nsp=nsp, t=t, mode=mode)
-        self.rng = np.random.default_rng(seed + logn + len(bits))
-        self.nd = (len(self.mods) - nsp + nsp - 1) // nsp
-        self.ev = S.Evaluator(self.ctx)
-        self.key_host = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+        super().__init__(S, scheme, logn, bits, nsp, mode, t, seed + logn + len(bits))
+        self.key_host = rows(self.rng, self.mods, self.n, (self.nd, 2))
         self.key = S.KSwitchKeys(self.ctx, self.key_host)
 
     def run(self, k, count, a_idx, b_idx, pool, keys):
@@ -68,7 +44,7 @@ class Session:
 
     def compare(self, k, count, n_terms, keys, tag, items=None, a_idx=None, b_idx=None):
         pool_size = 2 * n_terms if a_idx is None else 1 + max(a_idx + b_idx)
-        pool = [_rows(self.rng, self.mods[:k], self.n, (count, 2)) for _ in range(pool_size)]
+        pool = [rows(self.rng, self.mods[:k], self.n, (count, 2)) for _ in range(pool_size)]
         a_idx = list(range(n_terms)) if a_idx is None else a_idx
         b_idx = list(range(n_terms, 2 * n_terms)) if b_idx is None else b_idx
         got = self.run(k, count, a_idx, b_idx, pool, keys)
@@ -79,14 +55,7 @@ class Session:
         return pool, got
 
 
-_SESSIONS = {}
-
-
-def _session(S, *args, **kw):
-    key = repr((args, sorted(kw.items())))
-    if key not in _SESSIONS:
-        _SESSIONS[key] = Session(S, *args, **kw)
-    return _SESSIONS[key]
+_session = session_memo(Session)
 
 
 @pytest.mark.parametrize("keys", [False, True])
@@ -171,8 +140,8 @@ def test_refusals_that_need_a_device(S):
     """a key with fewer digits than the level; too small a sink; each leaves the output untouched"""
     se = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0)
     ctx, ev, n, k = se.ctx, se.ev, se.n, 3
-    short = S.KSwitchKeys(ctx, _rows(se.rng, se.mods, n, (2, 2)))
-    a, b = ctx.upload(_rows(se.rng, se.mods[:k], n, (1, 2))), ctx.upload(_rows(se.rng, se.mods[:k], n, (1, 2)))
+    short = S.KSwitchKeys(ctx, rows(se.rng, se.mods, n, (2, 2)))
+    a, b = ctx.upload(rows(se.rng, se.mods[:k], n, (1, 2))), ctx.upload(rows(se.rng, se.mods[:k], n, (1, 2)))
     sentinel = np.full(2 * k * n, 0x5A5A5A5A, dtype=np.uint64)
     out = ctx.upload(sentinel)
     with pytest.raises(ValueError, match="kswitch_keys is not valid"):
@@ -200,7 +169,7 @@ def test_transparency_flags(S, scheme):
     else:
         se, k = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0), 3
     ctx, ev, n, count, n_terms = se.ctx, se.ev, se.n, 3, 17
-    pool = [_rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(2 * n_terms)]
+    pool = [rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(2 * n_terms)]
     for p in pool:
         p[1, 1] = 0
     dev = [ctx.upload(p) for p in pool]
@@ -242,7 +211,7 @@ def test_work_done_once(S, logn):
     se = _session(S, S.SCHEME_BFV, logn, bits, 1, S.MODE_STRICT, t=65537)
     ctx, ev, n, count, n_terms = se.ctx, se.ev, se.n, 2, 5
     kb = k + len(D.bsk_primes(n, se.mods[:k], 65537))
-    dev = [ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(2 * n_terms)]
+    dev = [ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(2 * n_terms)]
     out2, out3 = ctx.alloc(count * 2 * k * n), ctx.alloc(count * 3 * k * n)
     dot = _profile(ctx, lambda: ev.dot_product(dev[:n_terms], dev[n_terms:], k, count, out2, [se.key]))
     plain = _profile(ctx, lambda: ev.dot_product(dev[:n_terms], dev[n_terms:], k, count, out3))
@@ -267,13 +236,13 @@ def test_graph_capture(S):
     """one CKKS call with three terms and keys, captured after a warm-up and replayed on new inputs"""
     se = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0)
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 2
-    dev = [ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(6)]
+    dev = [ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(6)]
     out = ctx.alloc(count * 2 * k * n)
     run = lambda: ev.dot_product(dev[:3], dev[3:], k, count, out, [se.key])
     run()
     g = ctx.capture(run)
     for _ in range(2):
-        pool = [_rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(6)]
+        pool = [rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(6)]
         for d, p in zip(dev, pool):
             d.upload(p)
         g.launch()
@@ -292,12 +261,8 @@ def test_cpp_adapter(S, tmp_path, scheme):
     ABI's words on the same seeded inputs, with the operands' level and form and, for CKKS, the product of the scales"""
     logn, n, k = 12, 1 << 12, 3
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_dot_ct_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_dot_ct_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0", scheme] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_dot_ct_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", scheme, *mods, timeout=120)
     sm = O.SplitMix(0x4018)
     terms = [sm.fill(2 * k, n, mods[:k] * 2).reshape(1, 2, k, n) for _ in range(6)]
     key = sm.fill(3 * 2 * 4, n, mods * 6).reshape(3, 2, 4, n)
@@ -314,13 +279,12 @@ def test_cpp_adapter(S, tmp_path, scheme):
     for name, buf in (("size3", out3), ("relin", out2)):
         for side in ("host", "device"):
             line = "%s %s digest %016x meta 1" % (side, name, O.fnv(buf.download()))
-            assert line in out.stdout, (line, out.stdout)
+            assert line in stdout, (line, stdout)
 
 
 # ---------------------------------------------------------------- the term list walked in passes (a child process with the
 # smallest arena)
 LOGN, N, T = 15, 1 << 15, 65537
-ARENA_MB = "64"
 
 
 def _child():
@@ -338,9 +302,9 @@ def _child():
     k, n_terms = 3, 9
     kb = k + len(D.bsk_primes(N, mods[:k], T))
     budget, row = int(ARENA_MB) << 20, N * 8
-    key_host = _rows(rng, mods, N, (3, 2))
+    key_host = rows(rng, mods, N, (3, 2))
     key = S.KSwitchKeys(ctx, key_host)
-    pool = [_rows(rng, mods[:k], N, (1, 2)) for _ in range(2 * n_terms)]
+    pool = [rows(rng, mods[:k], N, (1, 2)) for _ in range(2 * n_terms)]
     dev = [ctx.upload(p) for p in pool]
     for keys in (False, True):
         fixed = (3 * kb + (k if keys else 0)) * row
@@ -359,14 +323,8 @@ def _child():
 
 
 def test_term_list_walked_in_passes():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "DOT_CT_PASSES_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "DOT_CT_PASSES_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import S, compile_cpp, run_exe
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +26,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PID = (0x5151, 0x6262, 0x7373, 0x8484)
 T = 786433  # prime, = 1 mod 2^18
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def wire():
@@ -43,7 +36,8 @@ def wire():
 
 
 class Setup:
-    """a context on both sides, a secret key, and the key-level public key (2 x n_key x N, NTT form)"""
+    """a context on both sides, a secret key, and the key-level public key (2 x n_key x N, NTT form); not a BaseSession:
+    the oracle side and its client come first, the moduli may be given, there is no evaluator"""
 
     def __init__(self, S, scheme, logn, bits, nsp, mods=None):
         self.S, self.scheme = S, scheme
@@ -404,6 +398,7 @@ def _batch_child():
 
 
 def test_batch_spans_arena_chunks():
+    # (not run_arena_child: a 512 MB arena, and the child imports this module instead of running it)
     env = dict(os.environ, SEALHIP_WORKSPACE_MB="512")
     code = "import sys; sys.path[:0] = %r; import test_gpu_encryptor as T; T._batch_child()" % (
         [HERE, ROOT, os.path.join(ROOT, "gemini-seal_amd")],)
@@ -477,22 +472,18 @@ def test_cpp_encryptor_on_device(S, tmp_path):
                            pl.reshape(-1), asym_words.reshape(-1), sym_words.reshape(-1), np.array(pid, np.uint64)])
     path, stream_path = str(tmp_path / "in.bin"), str(tmp_path / "seeded.bin")
     blob.astype(np.uint64).tofile(path)
-    exe = str(tmp_path / "host_adapter_encrypt_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_encrypt_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0", path, stream_path], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = out.stdout.split("\n")
+    exe = compile_cpp(tmp_path, "host_adapter_encrypt_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", path, stream_path, timeout=300)
+    lines = stdout.split("\n")
     for key in ("decrypt_asym=ok", "decrypt_sym=ok", "decrypt_seeded=ok", "meta=ok"):
-        assert key in lines, out.stdout
+        assert key in lines, stdout
     for i in range(count):
         want = st.expected_asym(k, u[i], e[i], pl[i])
-        assert "asym %d %d" % (i, O.fnv(want)) in lines, (i, out.stdout)
+        assert "asym %d %d" % (i, O.fnv(want)) in lines, (i, stdout)
         want = st.expected_sym(k, seeds[i], es[i], pl[i], False)
-        assert "sym %d %d" % (i, O.fnv(want)) in lines, (i, out.stdout)
+        assert "sym %d %d" % (i, O.fnv(want)) in lines, (i, stdout)
     want = st.expected_sym(k, seeds[count], es[count], pl[1], True)
-    assert "seeded %d" % O.fnv(want) in lines, out.stdout
+    assert "seeded %d" % O.fnv(want) in lines, stdout
     with open(stream_path, "rb") as f:
         raw = f.read()
     assert raw == W.save_ciphertext(pid, False, 2, n, k, 1.0, want[0].reshape(-1), seed=seeds[count].tobytes())

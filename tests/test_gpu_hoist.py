@@ -10,7 +10,6 @@ is a single digit; the element list has conjugation (2N - 1) and a non-rotation 
 Seventeen digits take the inner product's loop kernel; 22 elements in one pass (the chunking case) take two launches of 16 + 6."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,26 +17,9 @@ import pytest
 
 import hoist_ref as H
 import oracle_lib as O
+from support import ARENA_MB, S, child_main, compile_cpp, rows, run_arena_child, run_exe
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
 
 
 def _elts(n):
@@ -45,7 +27,8 @@ def _elts(n):
 
 
 def _session(S, scheme, logn, bits, nsp, mode, t=0, n_keys=4, seed=0):
-    """contexts on both sides and random keys: the word-for-word comparison needs no valid keys"""
+    """contexts on both sides and random keys: the word-for-word comparison needs no valid keys (not a BaseSession: no
+    evaluator is kept, and the keys are drawn here)"""
     n = 1 << logn
     mods = O.coeff_modulus_create(n, bits)
     ctx = S.Context(scheme, logn, mods, nsp, t, mode=mode)
@@ -53,14 +36,14 @@ def _session(S, scheme, logn, bits, nsp, mode, t=0, n_keys=4, seed=0):
     rng = np.random.default_rng(seed + logn + len(bits))
     kf = len(mods) - nsp
     nd = (kf + nsp - 1) // nsp
-    keys = [_rows(rng, mods, n, (nd, 2)) for _ in range(n_keys)]
+    keys = [rows(rng, mods, n, (nd, 2)) for _ in range(n_keys)]
     dkeys = [S.KSwitchKeys(ctx, key) for key in keys]
     return ctx, ref, mods, rng, keys, dkeys
 
 
 def _compare(S, ctx, ref, mods, rng, keys, dkeys, k, count, elts, tag):
     n = ref.n
-    ct = _rows(rng, mods[:k], n, (count, 2))
+    ct = rows(rng, mods[:k], n, (count, 2))
     d = ctx.upload(ct)
     out = ctx.alloc(len(elts) * count * 2 * k * n)
     S.Evaluator(ctx).apply_galois_many(d, k, count, elts, dkeys, out)
@@ -160,12 +143,12 @@ def test_refusals(S):
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
     rng = np.random.default_rng(1)
     k, count = 3, 1
-    key = _rows(rng, mods, n, (3, 2))
+    key = rows(rng, mods, n, (3, 2))
     for scheme, mode, t in ((S.SCHEME_BFV, S.MODE_PARITY, 65537), (S.SCHEME_CKKS, S.MODE_PARITY, 0)):
         ctx = S.Context(scheme, logn, mods, 1, t, mode=mode)
         ev = S.Evaluator(ctx)
         dkey, short = S.KSwitchKeys(ctx, key), S.KSwitchKeys(ctx, key[:2])
-        ct = _rows(rng, mods[:k], n, (count, 2))
+        ct = rows(rng, mods[:k], n, (count, 2))
         d = ctx.upload(ct)
         out = ctx.alloc(2 * count * 2 * k * n)
         sentinel = np.full(out.words, 7, dtype=np.uint64)
@@ -198,7 +181,7 @@ def test_rotate_vector_many(S):
     ev = S.Evaluator(ctx)
     e1, e2 = H.elt_from_step(n, 1), H.elt_from_step(n, -2)
     gk = {e1: dkeys[0], e2: dkeys[1]}
-    ct = _rows(rng, mods[:k], n, (count, 2))
+    ct = rows(rng, mods[:k], n, (count, 2))
     d = ctx.upload(ct)
     out = ctx.alloc(3 * count * 2 * k * n)
     ctx.profile_enable(True)
@@ -225,7 +208,7 @@ def test_transparency_flags_in_output_order(S):
     ctx, ref, mods, rng, keys, dkeys = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 41], 1, S.MODE_PARITY, n_keys=2)
     n, k, count = ref.n, 3, 3
     ev = S.Evaluator(ctx)
-    ct = _rows(rng, mods[:k], n, (count, 2))
+    ct = rows(rng, mods[:k], n, (count, 2))
     ct[1, 1] = 0
     d = ctx.upload(ct)
     e1, e2 = H.elt_from_step(n, 1), H.elt_from_step(n, -2)
@@ -256,11 +239,11 @@ def test_graph_capture(S):
     n, k, count = ref.n, 3, 2
     ev = S.Evaluator(ctx)
     elts = _elts(n)[:2]
-    d = ctx.upload(_rows(rng, mods[:k], n, (count, 2)))
+    d = ctx.upload(rows(rng, mods[:k], n, (count, 2)))
     out = ctx.alloc(2 * count * 2 * k * n)
     g = ctx.capture(lambda: ev.apply_galois_many(d, k, count, elts, dkeys, out))
     for _ in range(2):
-        ct = _rows(rng, mods[:k], n, (count, 2))
+        ct = rows(rng, mods[:k], n, (count, 2))
         d.upload(ct)
         g.launch()
         got = out.download((2, count, 2, k, n))
@@ -272,12 +255,8 @@ def test_cpp_adapter(S, tmp_path):
     same seeded inputs, with the operand's metadata; the deferred transparency exception arrives"""
     logn, n, k = 12, 1 << 12, 3
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_hoist_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_hoist_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0"] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_hoist_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", *mods, timeout=120)
     sm = O.SplitMix(0x4015)
     ct = sm.fill(2 * k, n, mods[:k] * 2).reshape(1, 2, k, n)
     keys = [sm.fill(3 * 2 * 4, n, mods * 6).reshape(3, 2, 4, n) for _ in range(2)]
@@ -293,13 +272,12 @@ def test_cpp_adapter(S, tmp_path):
     for name, buf, count in (("apply_galois_many", many, 2), ("rotate_vector_many", rot, 3)):
         for side in ("host", "device"):
             line = "%s %s digest %016x count %d meta 1" % (side, name, O.fnv(buf.download()), count)
-            assert line in out.stdout, (line, out.stdout)
-    assert "deferred transparency ok" in out.stdout, out.stdout
+            assert line in stdout, (line, stdout)
+    assert "deferred transparency ok" in stdout, stdout
 
 
 # ---------------------------------------------------------------- arena chunks (a child process with the smallest arena)
 LOGN, N = 13, 1 << 13
-ARENA_MB = "64"
 
 
 def _child():
@@ -318,11 +296,11 @@ def _child():
     rng = np.random.default_rng(64)
     k = 8
     elts = [2 * i + 3 for i in range(23)]
-    keys = [_rows(rng, mods, N, (8, 2)) for _ in elts]
+    keys = [rows(rng, mods, N, (8, 2)) for _ in elts]
     dkeys = [S.KSwitchKeys(ctx, key) for key in keys]
 
     def run(count, n_elts, items, which):
-        ct = _rows(rng, mods[:k], N, (count, 2))
+        ct = rows(rng, mods[:k], N, (count, 2))
         d = ctx.upload(ct)
         out = ctx.alloc(n_elts * count * 2 * k * N)
         ctx.chunk_log()
@@ -345,14 +323,8 @@ def _child():
 
 
 def test_chunked_items_and_split_element_list():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "HOIST_CHUNKS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "HOIST_CHUNKS_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

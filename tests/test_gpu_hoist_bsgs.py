@@ -10,7 +10,6 @@ workgroup take the loop kernel; seventeen giants take two launches of the giant 
 adding into what the first left."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -20,26 +19,9 @@ import hoist_bsgs_ref as HB
 import hoist_ref as H
 import noise_ref as NR
 import oracle_lib as O
+from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
 
 
 def _baby(n):
@@ -52,31 +34,25 @@ def _giant(n):
     return [H.elt_from_step(n, 4), 2 * n - 1, 1, H.elt_from_step(n, 4)]
 
 
-class Session:
+class Session(BaseSession):
     """contexts on both sides and random keys: the word-for-word comparison needs no valid keys"""
 
     def __init__(self, S, scheme, logn, bits, nsp, mode, t=0, seed=0):
-        self.S, self.n = S, 1 << logn
-        self.mods = O.coeff_modulus_create(self.n, bits)
-        self.ctx = S.Context(scheme, logn, self.mods, nsp, t, mode=mode)
-        self.ref = O.RefContext(scheme, logn, self.mods, nsp=nsp, t=t, mode=mode)
-        self.rng = np.random.default_rng(seed + logn + len(bits))
-        self.nd = (len(self.mods) - nsp + nsp - 1) // nsp
-        self.ev = S.Evaluator(self.ctx)
+        super().__init__(S, scheme, logn, bits, nsp, mode, t, seed + logn + len(bits))
         self.keys = {}
 
     def key(self, g):
         if g == 1:
             return None, None
         if g not in self.keys:
-            host = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+            host = rows(self.rng, self.mods, self.n, (self.nd, 2))
             self.keys[g] = (host, self.S.KSwitchKeys(self.ctx, host))
         return self.keys[g]
 
     def compare(self, k, count, baby, giant, tag, items=None):
         n = self.n
-        ct = _rows(self.rng, self.mods[:k], n, (count, 2))
-        plains = _rows(self.rng, self.mods, n, (len(giant), len(baby)))
+        ct = rows(self.rng, self.mods[:k], n, (count, 2))
+        plains = rows(self.rng, self.mods, n, (len(giant), len(baby)))
         d, dp = self.ctx.upload(ct), self.ctx.upload(plains)
         out = self.ctx.alloc(count * 2 * k * n)
         bk, gk = [self.key(g) for g in baby], [self.key(g) for g in giant]
@@ -172,8 +148,8 @@ def test_degenerate_shapes(S, scheme):
     se.compare(k, count, [1, 1], _giant(n), (scheme, "babies 1"))
     se.compare(k, count, _baby(n), [1, 1, 1], (scheme, "giants 1"))
     se.compare(k, count, [1, 1], [1, 1], (scheme, "all 1"))
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
-    d, dp = ctx.upload(ct), ctx.upload(_rows(se.rng, se.mods, n, (2, 2)))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
+    d, dp = ctx.upload(ct), ctx.upload(rows(se.rng, se.mods, n, (2, 2)))
     out = ctx.alloc(count * 2 * k * n)
 
     def tags(baby, giant):
@@ -211,8 +187,8 @@ def test_launch_counts(S):
     baby = [1, 3, 5, 7]
     giant = [1, 9, 11, 13]
     bk, gk = [se.key(g)[1] for g in baby], [se.key(g)[1] for g in giant]
-    d = ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2)))
-    dp = ctx.upload(_rows(se.rng, se.mods, n, (4, 4)))
+    d = ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2)))
+    dp = ctx.upload(rows(se.rng, se.mods, n, (4, 4)))
     out = ctx.alloc(3 * count * 2 * k * n)
     ev.apply_galois_bsgs_plain(d, k, count, baby, bk, giant, gk, dp, out)  # (tables resident)
 
@@ -251,13 +227,13 @@ def test_refusals(S):
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
     rng = np.random.default_rng(1)
     k, count = 3, 1
-    key = _rows(rng, mods, n, (3, 2))
+    key = rows(rng, mods, n, (3, 2))
     for scheme, mode, t in ((S.SCHEME_BFV, S.MODE_PARITY, 65537), (S.SCHEME_CKKS, S.MODE_PARITY, 0)):
         ctx = S.Context(scheme, logn, mods, 1, t, mode=mode)
         ev = S.Evaluator(ctx)
         dkey, short = S.KSwitchKeys(ctx, key), S.KSwitchKeys(ctx, key[:2])
-        ct = _rows(rng, mods[:k], n, (count, 2))
-        plains = _rows(rng, mods, n, (2, 2))
+        ct = rows(rng, mods[:k], n, (count, 2))
+        plains = rows(rng, mods, n, (2, 2))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(count * 2 * k * n)
         sentinel = np.full(out.words, 7, dtype=np.uint64)
@@ -311,12 +287,12 @@ def test_transparency_flags(S):
     by the storing kernel of the mod-down and by the read pass of the all-identity call; a sink that is too small is refused"""
     se = Session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 41], 1, S.MODE_PARITY)
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 3
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
     ct[1, 1] = 0
     d = ctx.upload(ct)
     e1, e2 = H.elt_from_step(n, 1), H.elt_from_step(n, -2)
     dkeys = [se.key(e1)[1], se.key(e2)[1]]
-    dp = ctx.upload(_rows(se.rng, se.mods, n, (2, 2)))
+    dp = ctx.upload(rows(se.rng, se.mods, n, (2, 2)))
     flags = ctx.alloc(8)  # 16 uint32 words
     ctx.transparency_sink(flags, 16)
     try:
@@ -345,15 +321,15 @@ def test_graph_capture(S):
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 2
     baby, giant = _baby(n)[:3], _giant(n)[1:]
     bk, gk = [se.key(g) for g in baby], [se.key(g) for g in giant]
-    d = ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2)))
-    dp = ctx.upload(_rows(se.rng, se.mods, n, (3, 3)))
+    d = ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2)))
+    dp = ctx.upload(rows(se.rng, se.mods, n, (3, 3)))
     out = ctx.alloc(count * 2 * k * n)
     run = lambda: ev.apply_galois_bsgs_plain(d, k, count, baby, [kk[1] for kk in bk], giant, [kk[1] for kk in gk], dp, out)
     run()
     g = ctx.capture(run)
     for _ in range(2):
-        ct = _rows(se.rng, se.mods[:k], n, (count, 2))
-        plains = _rows(se.rng, se.mods, n, (3, 3))
+        ct = rows(se.rng, se.mods[:k], n, (count, 2))
+        plains = rows(se.rng, se.mods, n, (3, 3))
         d.upload(ct)
         dp.upload(plains)
         g.launch()
@@ -449,12 +425,8 @@ def test_cpp_adapter(S, tmp_path, scheme):
     inputs, with the operand's level and form and, for CKKS, the product of the scales"""
     logn, n, k = 12, 1 << 12, 3
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_bsgs_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_bsgs_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0", scheme] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_bsgs_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", scheme, *mods, timeout=120)
     sm = O.SplitMix(0x4017)
     ct = sm.fill(2 * k, n, mods[:k] * 2).reshape(1, 2, k, n)
     keys = [sm.fill(3 * 2 * 4, n, mods * 6).reshape(3, 2, 4, n) for _ in range(3)]
@@ -476,12 +448,11 @@ def test_cpp_adapter(S, tmp_path, scheme):
     for name, buf in (("apply_galois_bsgs_plain", by_elt), ("steps", by_step)):
         for side in ("host", "device"):
             line = "%s %s digest %016x meta 1" % (side, name, O.fnv(buf.download()))
-            assert line in out.stdout, (line, out.stdout)
+            assert line in stdout, (line, stdout)
 
 
 # ---------------------------------------------------------------- arena chunks (a child process with the smallest arena)
 LOGN, N = 13, 1 << 13
-ARENA_MB = "64"
 
 
 def _child():
@@ -506,14 +477,14 @@ def _child():
 
     def key(g):
         if g != 1 and g not in made:
-            host = _rows(rng, mods, N, (8, 2))
+            host = rows(rng, mods, N, (8, 2))
             made[g] = (host, S.KSwitchKeys(ctx, host))
         return made.get(g, (None, None))
 
     def run(count, baby, giant, items):
         bk, gk = [key(g) for g in baby], [key(g) for g in giant]
-        ct = _rows(rng, mods[:k], N, (count, 2))
-        plains = _rows(rng, mods, N, (len(giant), len(baby)))
+        ct = rows(rng, mods[:k], N, (count, 2))
+        plains = rows(rng, mods, N, (len(giant), len(baby)))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(count * 2 * k * N)
         ctx.chunk_log()
@@ -539,14 +510,8 @@ def _child():
 
 
 def test_chunked_items_and_split_giant_list():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "HOIST_BSGS_CHUNKS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "HOIST_BSGS_CHUNKS_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

@@ -9,7 +9,6 @@ eleven ciphertexts give a short last group at one sum and at two, and five sums 
 the loop kernel; 22 elements with the identity at position 18 take two launches of the base kernel (16 + 6) and of the inner
 product (16 + 5), the second adding into what the first left."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,57 +17,34 @@ import pytest
 import hoist_dot_ref as HD
 import hoist_ref as H
 import oracle_lib as O
+from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
 
 
 def _elts(n):
     return [H.elt_from_step(n, 1), 1, H.elt_from_step(n, -3), 2 * n - 1, 3]
 
 
-class Session:
+class Session(BaseSession):
     """contexts on both sides and random keys: the word-for-word comparison needs no valid keys"""
 
     def __init__(self, S, scheme, logn, bits, nsp, mode, t=0, seed=0):
-        self.S, self.n = S, 1 << logn
-        self.mods = O.coeff_modulus_create(self.n, bits)
-        self.ctx = S.Context(scheme, logn, self.mods, nsp, t, mode=mode)
-        self.ref = O.RefContext(scheme, logn, self.mods, nsp=nsp, t=t, mode=mode)
-        self.rng = np.random.default_rng(seed + logn + len(bits))
-        self.nd = (len(self.mods) - nsp + nsp - 1) // nsp
-        self.ev = S.Evaluator(self.ctx)
+        super().__init__(S, scheme, logn, bits, nsp, mode, t, seed + logn + len(bits))
         self.keys = {}
 
     def key(self, g):
         if g == 1:
             return None, None
         if g not in self.keys:
-            host = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+            host = rows(self.rng, self.mods, self.n, (self.nd, 2))
             self.keys[g] = (host, self.S.KSwitchKeys(self.ctx, host))
         return self.keys[g]
 
     def compare(self, k, count, elts, n_sums, tag, items=None):
         n = self.n
-        ct = _rows(self.rng, self.mods[:k], n, (count, 2))
-        plains = _rows(self.rng, self.mods, n, (n_sums, len(elts)))
+        ct = rows(self.rng, self.mods[:k], n, (count, 2))
+        plains = rows(self.rng, self.mods, n, (n_sums, len(elts)))
         d, dp = self.ctx.upload(ct), self.ctx.upload(plains)
         out = self.ctx.alloc(n_sums * count * 2 * k * n)
         keys = [self.key(g) for g in elts]
@@ -147,8 +123,8 @@ def test_only_identity_elements(S):
     se = Session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 41], 1, S.MODE_PARITY)
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 2
     se.compare(k, count, [1, 1, 1], 2, "identities")
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
-    plain = _rows(se.rng, se.mods, n, (1, 1))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
+    plain = rows(se.rng, se.mods, n, (1, 1))
     d, dp = ctx.upload(ct), ctx.upload(plain)
     out = ctx.alloc(count * 2 * k * n)
     ctx.profile_enable(True)
@@ -170,8 +146,8 @@ def test_one_decomposition_and_one_mod_down_per_sum(S):
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 3
     elts = _elts(n)[2:] + [5] + [7, 9, 11, 13]
     keys = [se.key(g)[1] for g in elts]
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
-    plains = _rows(se.rng, se.mods, n, (2, 4))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
+    plains = rows(se.rng, se.mods, n, (2, 4))
     d, dp = ctx.upload(ct), ctx.upload(plains)
     out = ctx.alloc(8 * count * 2 * k * n)
     ev.apply_galois_many(d, k, count, elts, keys, out)  # (tables resident)
@@ -206,13 +182,13 @@ def test_refusals(S):
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
     rng = np.random.default_rng(1)
     k, count = 3, 1
-    key = _rows(rng, mods, n, (3, 2))
+    key = rows(rng, mods, n, (3, 2))
     for scheme, mode, t in ((S.SCHEME_BFV, S.MODE_PARITY, 65537), (S.SCHEME_CKKS, S.MODE_PARITY, 0)):
         ctx = S.Context(scheme, logn, mods, 1, t, mode=mode)
         ev = S.Evaluator(ctx)
         dkey, short = S.KSwitchKeys(ctx, key), S.KSwitchKeys(ctx, key[:2])
-        ct = _rows(rng, mods[:k], n, (count, 2))
-        plains = _rows(rng, mods, n, (2, 2))
+        ct = rows(rng, mods[:k], n, (count, 2))
+        plains = rows(rng, mods, n, (2, 2))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(2 * count * 2 * k * n)
         sentinel = np.full(out.words, 7, dtype=np.uint64)
@@ -252,12 +228,12 @@ def test_transparency_flags_in_output_order(S):
     sink that is too small is refused"""
     se = Session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 41], 1, S.MODE_PARITY)
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 3
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
     ct[1, 1] = 0
     d = ctx.upload(ct)
     e1, e2 = H.elt_from_step(n, 1), H.elt_from_step(n, -2)
     dkeys = [se.key(e1)[1], se.key(e2)[1]]
-    dp = ctx.upload(_rows(se.rng, se.mods, n, (2, 2)))
+    dp = ctx.upload(rows(se.rng, se.mods, n, (2, 2)))
     flags = ctx.alloc(8)  # 16 uint32 words
     ctx.transparency_sink(flags, 16)
     try:
@@ -284,13 +260,13 @@ def test_graph_capture(S):
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 2
     elts = _elts(n)[:3]
     keys = [se.key(g) for g in elts]
-    d = ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2)))
-    dp = ctx.upload(_rows(se.rng, se.mods, n, (2, 3)))
+    d = ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2)))
+    dp = ctx.upload(rows(se.rng, se.mods, n, (2, 3)))
     out = ctx.alloc(2 * count * 2 * k * n)
     g = ctx.capture(lambda: ev.apply_galois_dot_plain(d, k, count, elts, [kk[1] for kk in keys], dp, 2, out))
     for _ in range(2):
-        ct = _rows(se.rng, se.mods[:k], n, (count, 2))
-        plains = _rows(se.rng, se.mods, n, (2, 3))
+        ct = rows(se.rng, se.mods[:k], n, (count, 2))
+        plains = rows(se.rng, se.mods, n, (2, 3))
         d.upload(ct)
         dp.upload(plains)
         g.launch()
@@ -393,7 +369,7 @@ def test_ckks_key_level_encoding_agrees_with_the_level_encoding(S):
     at_key = ctx.ckks_encode(values, n_key, 2.0 ** 30)
     at_k = ctx.ckks_encode(values, k, 2.0 ** 30)
     assert np.array_equal(at_key.download((n_key, n))[:k], at_k.download((k, n)))
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
     d = ctx.upload(ct)
     out = ctx.alloc(count * 2 * k * n)
     ev.apply_galois_dot_plain(d, k, count, [1], [None], at_key, 1, out)
@@ -407,12 +383,8 @@ def test_cpp_adapter(S, tmp_path):
     takes every block from the pool; the deferred transparency exception arrives"""
     logn, n, k, n_sums = 12, 1 << 12, 3, 2
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_hoist_dot_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_hoist_dot_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0"] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_hoist_dot_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", *mods, timeout=120)
     sm = O.SplitMix(0x4016)
     ct = sm.fill(2 * k, n, mods[:k] * 2).reshape(1, 2, k, n)
     keys = [sm.fill(3 * 2 * 4, n, mods * 6).reshape(3, 2, 4, n) for _ in range(2)]
@@ -429,14 +401,13 @@ def test_cpp_adapter(S, tmp_path):
     for name, buf in (("apply_galois_dot_plain", by_elt), ("rotate_vector_dot_plain", by_step)):
         for side in ("host", "device"):
             line = "%s %s digest %016x count %d meta 1" % (side, name, O.fnv(buf.download()), n_sums)
-            assert line in out.stdout, (line, out.stdout)
-    assert "warm call pool mallocs 0 frees 0" in out.stdout, out.stdout
-    assert "deferred transparency ok" in out.stdout, out.stdout
+            assert line in stdout, (line, stdout)
+    assert "warm call pool mallocs 0 frees 0" in stdout, stdout
+    assert "deferred transparency ok" in stdout, stdout
 
 
 # ---------------------------------------------------------------- arena chunks (a child process with the smallest arena)
 LOGN, N = 13, 1 << 13
-ARENA_MB = "64"
 
 
 def _child():
@@ -457,10 +428,10 @@ def _child():
     base, per_sum = (k + k * (k + 1)) * N * 8, (2 * (k + 1) + 2 * k) * N * 8
 
     def run(count, elts, n_sums, items, sums):
-        keys = [None if g == 1 else _rows(rng, mods, N, (8, 2)) for g in elts]
+        keys = [None if g == 1 else rows(rng, mods, N, (8, 2)) for g in elts]
         dkeys = [None if key is None else S.KSwitchKeys(ctx, key) for key in keys]
-        ct = _rows(rng, mods[:k], N, (count, 2))
-        plains = _rows(rng, mods, N, (n_sums, len(elts)))
+        ct = rows(rng, mods[:k], N, (count, 2))
+        plains = rows(rng, mods, N, (n_sums, len(elts)))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(n_sums * count * 2 * k * N)
         ctx.chunk_log()
@@ -487,14 +458,8 @@ def _child():
 
 
 def test_chunked_items_and_split_sum_list():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "HOIST_DOT_CHUNKS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "HOIST_DOT_CHUNKS_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

@@ -11,8 +11,6 @@ section 23).
    error against the same chain over numpy-made, oracle-encoded diagonals.
 5. Boundary behaviour."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,32 +19,15 @@ import hoist_ref as H
 import homdft_ref as R
 import ks_rescale_ref as KR
 import oracle_lib as O
+from support import BaseSession, S, compile_cpp, rows, run_exe, session_memo
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def _download(S, ctx, ptr, shape):
     out = np.empty(shape, dtype=np.uint64)
     ctx.synchronize()
     S._check(S.lib().sealhip_memcpy_d2h(ctx.handle, out.ctypes.data, ptr, out.nbytes))
-    return out
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
     return out
 
 
@@ -66,26 +47,19 @@ def _numpy_values(n_ring, direction, counts, t, gain):
     return _grid(n_ring, direction, s0, r)[0] * R.stage_gain(direction, t, len(counts), gain)
 
 
-class Session:
+class Session(BaseSession):
     """contexts on both sides; keys are random words unless a client makes real ones"""
 
     def __init__(self, S, logn, bits, nsp, mode=0, seed=0):
-        self.S, self.logn, self.n, self.nsp = S, logn, 1 << logn, nsp
-        self.mods = O.coeff_modulus_create(self.n, bits)
+        super().__init__(S, S.SCHEME_CKKS, logn, bits, nsp, mode, 0, seed + 31 * logn + nsp)
         self.n_key = len(self.mods)
-        self.ctx = S.Context(S.SCHEME_CKKS, logn, self.mods, nsp, 0, mode=mode)
-        self.ref = O.RefContext(2, logn, self.mods, nsp=nsp, t=0, mode=mode)
-        self.ev = S.Evaluator(self.ctx)
-        self.k_first = self.n_key - nsp
-        self.nd = (self.k_first + nsp - 1) // nsp
-        self.rng = np.random.default_rng(seed + 31 * logn + nsp)
         self.host_keys, self.dev_keys = {}, {}
 
     def random_keys(self, steps, conj):
         elts = [H.elt_from_step(self.n, s) for s in steps] + ([2 * self.n - 1] if conj else [])
         for g in elts:
             if g not in self.host_keys:
-                self.host_keys[g] = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+                self.host_keys[g] = rows(self.rng, self.mods, self.n, (self.nd, 2))
                 self.dev_keys[g] = self.S.KSwitchKeys(self.ctx, self.host_keys[g])
         return {g: self.dev_keys[g] for g in elts}
 
@@ -141,14 +115,11 @@ class Session:
         return cur
 
 
-_SESSIONS = {}
+_made = session_memo(Session)
 
 
 def _session(S, logn, bits, nsp, mode=0):
-    key = (logn, tuple(bits), nsp, mode)
-    if key not in _SESSIONS:
-        _SESSIONS[key] = Session(S, logn, bits, nsp, mode)
-    return _SESSIONS[key]
+    return _made(S, logn, list(bits), nsp, mode)
 
 
 # ------------------------------------------------------------------ 1. the generator
@@ -200,7 +171,7 @@ def test_tables_are_the_encoding_of_the_device_values(S, logn, counts, direction
 # ------------------------------------------------------------------ 3. the words
 def _check_words(S, se, counts, k, count, cpu_chain=False):
     n = se.n
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
     d_ct = se.ctx.upload(ct)
     # CoeffToSlot
     plan = se.ev.dft_plan(R.C2S, k, counts)
@@ -231,7 +202,7 @@ def _check_words(S, se, counts, k, count, cpu_chain=False):
     plan = se.ev.dft_plan(R.S2C, k, counts)
     gk = se.random_keys(plan["key_steps"], conj=False)
     tables = S.DftTables(se.ctx, R.S2C, k, counts)
-    a, b = _rows(se.rng, se.mods[:k], n, (count, 2)), _rows(se.rng, se.mods[:k], n, (count, 2))
+    a, b = rows(se.rng, se.mods[:k], n, (count, 2)), rows(se.rng, se.mods[:k], n, (count, 2))
     d_a, d_b = se.ctx.upload(a), se.ctx.upload(b)
     out = se.ctx.alloc(count * 2 * ko * n)
     se.ev.slots_to_coeffs(tables, d_a, d_b, count, gk, out)
@@ -366,7 +337,7 @@ def test_checks_flags_capture(S):
     c2s, s2c = S.DftTables(ctx, R.C2S, k, counts), S.DftTables(ctx, R.S2C, k, counts)
     gk2 = se.random_keys(ev.dft_plan(R.S2C, k, counts)["key_steps"], conj=False)
     ko = plan["out_level"]
-    ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+    ct = rows(se.rng, se.mods[:k], n, (count, 2))
     d_ct = ctx.upload(ct)
     re, im, out = (ctx.alloc(count * 2 * ko * n) for _ in range(3))
     # a missing key: a step's, and the conjugation's
@@ -421,7 +392,7 @@ def test_checks_flags_capture(S):
     f = flags.download().view(np.uint32)[:count]
     assert list(f != 0) == [True, False, True], f
     with pytest.raises(ValueError, match="transparency sink"):
-        ev.coeffs_to_slots(c2s, ctx.upload(_rows(se.rng, se.mods[:k], n, (5, 2))), 5, gk, ctx.alloc(5 * 2 * ko * n),
+        ev.coeffs_to_slots(c2s, ctx.upload(rows(se.rng, se.mods[:k], n, (5, 2))), 5, gk, ctx.alloc(5 * 2 * ko * n),
                            ctx.alloc(5 * 2 * ko * n))
     ctx.transparency_sink(None, 0)
     # graph capture: a replay gives the eager words; the workspace is pool memory the tables hold
@@ -448,10 +419,6 @@ def test_checks_flags_capture(S):
 def test_cpp_adapter(tmp_path):
     """tests/host_adapter_homdft_check.cpp: the host-ciphertext and the DeviceCiphertext forms give the C ABI's words on the
     same seeded inputs, at the plan's level and the operand's scale; the operand checks and their messages"""
-    exe = str(tmp_path / "host_adapter_homdft_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_homdft_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
+    exe = compile_cpp(tmp_path, "host_adapter_homdft_check.cpp", link_sealhip=True)
     mods = O.coeff_modulus_create(256, [40] * 5)
-    out = subprocess.run([exe, "0"] + [str(p) for p in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "homdft adapter checks ok" in out.stdout, out.stdout + out.stderr
+    assert "homdft adapter checks ok" in run_exe(exe, "0", *mods, timeout=120)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import S, run_exe
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +20,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PID = (0x1111, 0x2222, 0x3333, 0x4444)
 T = 786433  # prime, = 1 mod 2^18: batching at every ring up to 2^16
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def wire():
@@ -37,6 +30,8 @@ def wire():
 
 
 class Setup:
+    """(not a BaseSession: the oracle side and its client come first, the context gets parms_ids, there is no evaluator)"""
+
     def __init__(self, S, scheme, logn, bits, nsp, mode=0):
         self.n = n = 1 << logn
         self.logn, self.nsp = logn, nsp
@@ -318,6 +313,7 @@ def splitmix(state):
 
 
 def fnv(raw):
+    """(not oracle_lib.fnv: over a byte stream whose length need not be whole words)"""
     h = 0xCBF29CE484222325
     for b in raw:
         h = ((h ^ b) * 0x100000001B3) & (2**64 - 1)
@@ -331,9 +327,8 @@ def test_cpp_keygenerator_on_device(S, tmp_path):
 
     import subprocess
 
-    out = subprocess.run([build_keygen_adapter(tmp_path), "0"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = dict(l.split(" digest ") for l in out.stdout.splitlines() if " digest " in l)
+    stdout = run_exe(build_keygen_adapter(tmp_path), "0", timeout=300)
+    lines = dict(l.split(" digest ") for l in stdout.splitlines() if " digest " in l)
     mods = [1073738753, 1099511603713, 1152921504606830593, 1152921504606844417]
     n = 256
     ctx = S.Context(1, 8, mods, 2, T)
@@ -365,4 +360,4 @@ def test_cpp_keygenerator_on_device(S, tmp_path):
     pk = ctx.alloc(2 * 4 * n)
     ctx.encrypt_zero_symmetric(4, True, a, ctx.upload_i32(noise), dsk, 1, pk)
     assert int(lines["public_key"], 16) == fnv(pk.download().astype("<u8").tobytes())
-    assert "samples asked 5" in out.stdout
+    assert "samples asked 5" in stdout

@@ -44,6 +44,7 @@ import pytest
 import hoist_dot_ref as HD
 import hoist_ref as H
 import oracle_lib as O
+from support import BaseSession, rows, top
 
 pytestmark = pytest.mark.gpu
 
@@ -136,54 +137,34 @@ def compared_items(call):
     return tuple(sorted(edges))
 
 
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
-
-
-def _top(mods, n, lead):
-    """every word p - 1"""
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = p - 1
-    return out
-
-
-class Session:
+class Session(BaseSession):
     """the contexts of both sides, one key per element and one for relinearize, built once per module"""
 
     def __init__(self, S, name):
         c = CONTEXTS[name]
-        self.S, self.name, self.n, self.nsp = S, name, 1 << c.logn, c.nsp
-        self.mods = O.coeff_modulus_create(self.n, c.bits)
-        self.ctx = S.Context(c.scheme, c.logn, self.mods, c.nsp, c.t, mode=c.mode)
-        self.ref = O.RefContext(c.scheme, c.logn, self.mods, nsp=c.nsp, t=c.t, mode=c.mode)
-        self.ev = S.Evaluator(self.ctx)
-        self.rng = np.random.default_rng(sum(name.encode()))
+        super().__init__(S, c.scheme, c.logn, c.bits, c.nsp, c.mode, c.t, sum(name.encode()))
+        self.name = name
         self.elts = elements(self.n)
-        self.nd = -(-(len(self.mods) - c.nsp) // c.nsp)
         self.keys, self.top_key = {}, None
 
     def key(self, which, extreme=False):
         """(host words, device handle) of element `which` (None: the relinearization key); the extremes share one key"""
         if extreme:
             if self.top_key is None:
-                host = _top(self.mods, self.n, (self.nd, 2))
+                host = top(self.mods, self.n, (self.nd, 2))
                 self.top_key = (host, self.S.KSwitchKeys(self.ctx, host))
             return self.top_key
         if which not in self.keys:
-            host = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+            host = rows(self.rng, self.mods, self.n, (self.nd, 2))
             self.keys[which] = (host, self.S.KSwitchKeys(self.ctx, host))
         return self.keys[which]
 
     def ciphertexts(self, k, count, size, extreme):
-        ct = _rows(self.rng, self.mods[:k], self.n, (count, size))
+        ct = rows(self.rng, self.mods[:k], self.n, (count, size))
         if extreme:  # all p - 1, alternating 0 / p - 1, random, and so on through the batch
-            top = _top(self.mods[:k], self.n, (size,))
-            ct[0::3] = top
-            ct[1::3] = top
+            hi = top(self.mods[:k], self.n, (size,))
+            ct[0::3] = hi
+            ct[1::3] = hi
             ct[1::3, :, :, 0::2] = 0
         return ct
 
@@ -239,7 +220,7 @@ class Session:
         keys = [(None, None) if g == 1 else self.key(g, call.extreme) for g in elts]
         ct = self.ciphertexts(k, count, 2, call.extreme)
         lead = (n_sums, len(elts))
-        plains = _top(self.mods, n, lead) if call.extreme else _rows(self.rng, self.mods, n, lead)
+        plains = top(self.mods, n, lead) if call.extreme else rows(self.rng, self.mods, n, lead)
         d, dp = self.ctx.upload(ct), self.ctx.upload(plains)
         out = self.ctx.alloc(n_sums * count * 2 * k * n)
         self.ctx.chunk_log()

@@ -8,7 +8,6 @@ loop form of the conversion kernel; N = 2^6 is a ring smaller than a workgroup; 
 Seventeen ciphertexts reach the grouped inner-product kernel and more than one block per row; seventeen terms the second
 launch group of the tensor sum."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,11 +16,10 @@ import pytest
 import hoist_ref as H
 import ks_rescale_ref as R
 import oracle_lib as O
+from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe, session_memo, top
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 # logn, prime bits, special primes, levels
 SETS = {
@@ -33,46 +31,16 @@ SETS = {
 }
 
 
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
-
-
-def _top(mods, n, lead):
-    """every word p - 1"""
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = int(p) - 1
-    return out
-
-
-class Session:
-    """contexts on both sides and random keys: the word-for-word comparison needs no valid keys. fill: _rows or _top."""
+class Session(BaseSession):
+    """contexts on both sides and random keys: the word-for-word comparison needs no valid keys. fill: rows or top."""
 
     def __init__(self, S, logn, bits, nsp, mode=0, seed=0, top=False):
-        self.S, self.n, self.nsp = S, 1 << logn, nsp
-        self.mods = O.coeff_modulus_create(self.n, bits)
-        self.ctx = S.Context(S.SCHEME_CKKS, logn, self.mods, nsp, 0, mode=mode)
-        self.ref = O.RefContext(2, logn, self.mods, nsp=nsp, t=0, mode=mode)
-        self.rng = np.random.default_rng(seed + logn + len(bits))
-        self.k_first = len(self.mods) - nsp
-        self.nd = (self.k_first + nsp - 1) // nsp
-        self.ev = S.Evaluator(self.ctx)
+        super().__init__(S, S.SCHEME_CKKS, logn, bits, nsp, mode, 0, seed + logn + len(bits))
         self.top = top
         self.keys = {}
 
     def rows(self, mods, lead):
-        return _top(mods, self.n, lead) if self.top else _rows(self.rng, mods, self.n, lead)
+        return top(mods, self.n, lead) if self.top else rows(self.rng, mods, self.n, lead)
 
     def key(self, g):
         """(host words, device handle) of the key of element g; "relin" names the relinearization key; 1 has none"""
@@ -152,14 +120,12 @@ class Session:
         return ct, plains, got
 
 
-_SESSIONS = {}
+_made = session_memo(Session)
 
 
 def _session(S, name, mode=0):
-    if (name, mode) not in _SESSIONS:
-        logn, bits, nsp, _ = SETS[name]
-        _SESSIONS[(name, mode)] = Session(S, logn, bits, nsp, mode)
-    return _SESSIONS[(name, mode)]
+    logn, bits, nsp, _ = SETS[name]
+    return _made(S, logn, bits, nsp, mode)
 
 
 def _few(se, count):
@@ -249,19 +215,19 @@ def test_transparency_flags(S):
         def arm():
             flags.upload(np.full(8, 0x0000000500000005, dtype=np.uint64))
 
-        ct3 = _rows(se.rng, se.mods[:k], n, (count, 3))
+        ct3 = rows(se.rng, se.mods[:k], n, (count, 3))
         ct3[1, 1:] = 0
         d3 = ctx.upload(ct3)
         out = ctx.alloc(2 * count * 2 * (k - 1) * n)
         arm()
         ev.relinearize_rescale(d3, k, count, [kd], out)
         check([True, False, True], "relinearize")
-        ct = _rows(se.rng, se.mods[:k], n, (count, 2))
+        ct = rows(se.rng, se.mods[:k], n, (count, 2))
         ct[1, 1] = 0
         d = ctx.upload(ct)
         g = H.elt_from_step(n, 1)
         gk = se.key(g)[1]
-        dp = ctx.upload(_rows(se.rng, se.mods, n, (2, 2)))
+        dp = ctx.upload(rows(se.rng, se.mods, n, (2, 2)))
         for elts, keys in (([g, 1], [gk, None]), ([1, 1], [None, None])):
             arm()
             ev.apply_galois_dot_plain_rescale(d, k, count, elts, keys, dp, 2, out)
@@ -281,13 +247,13 @@ def test_graph_capture(S):
     se = _session(S, "n10_nsp1")
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 4, 2
     kh, kd = se.key("relin")
-    d = ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 3)))
+    d = ctx.upload(rows(se.rng, se.mods[:k], n, (count, 3)))
     out = ctx.alloc(count * 2 * (k - 1) * n)
     run = lambda: ev.relinearize_rescale(d, k, count, [kd], out)
     run()
     g = ctx.capture(run)
     for _ in range(2):
-        ct = _rows(se.rng, se.mods[:k], n, (count, 3))
+        ct = rows(se.rng, se.mods[:k], n, (count, 3))
         d.upload(ct)
         g.launch()
         got = out.download((count, 2, k - 1, n)).copy()
@@ -304,8 +270,8 @@ def test_refusals(S):
     se = _session(S, "n8_nsp3")
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 7, 2
     kd = se.key("relin")[1]
-    short = S.KSwitchKeys(ctx, _rows(se.rng, se.mods, n, (2, 2)))
-    ct3 = _rows(se.rng, se.mods[:k], n, (count, 3))
+    short = S.KSwitchKeys(ctx, rows(se.rng, se.mods, n, (2, 2)))
+    ct3 = rows(se.rng, se.mods[:k], n, (count, 3))
     d = ctx.upload(ct3)
     out = ctx.alloc(count * 2 * (k - 1) * n)
     sentinel = np.full(out.words, 7, dtype=np.uint64)
@@ -334,12 +300,8 @@ def test_cpp_adapter(S, tmp_path):
     adapter method give the ABI's words on the same seeded inputs, one level down, with the scale divided by q_{k-1}"""
     logn, n, k = 8, 1 << 8, 3
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_ks_rescale_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_ks_rescale_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    run = subprocess.run([exe, "0"] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_ks_rescale_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", *mods, timeout=120)
     ctx = S.Context(S.SCHEME_CKKS, logn, mods, 1, 0)
     ev = S.Evaluator(ctx)
     sm = O.SplitMix(0x4019)
@@ -365,12 +327,11 @@ def test_cpp_adapter(S, tmp_path):
     for name, words_ in results.items():
         for side in ("host", "device"):
             line = "%s %s digest %016x meta 1" % (side, name, O.fnv(words_))
-            assert line in run.stdout, (line, run.stdout)
+            assert line in stdout, (line, stdout)
 
 
 # ---------------------------------------------------------------- arena chunks (a child process with the smallest arena)
 LOGN, N = 13, 1 << 13
-ARENA_MB = "64"
 
 
 def _child():
@@ -403,14 +364,14 @@ def _child():
 
     def key(g):
         if g != 1 and g not in made:
-            host = _rows(rng, mods, N, (8, 2))
+            host = rows(rng, mods, N, (8, 2))
             made[g] = (host, S.KSwitchKeys(ctx, host))
         return made.get(g, (None, None))
 
     def dot_plain(count, elts, n_sums, items, sums):
         keys = [key(g) for g in elts]
-        ct = _rows(rng, mods[:k], N, (count, 2))
-        plains = _rows(rng, mods, N, (n_sums, len(elts)))
+        ct = rows(rng, mods[:k], N, (count, 2))
+        plains = rows(rng, mods, N, (n_sums, len(elts)))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(n_sums * count * 2 * (k - 1) * N)
         ctx.chunk_log()
@@ -427,8 +388,8 @@ def _child():
 
     def bsgs(count, baby, giant, items):
         bk, gk = [key(g) for g in baby], [key(g) for g in giant]
-        ct = _rows(rng, mods[:k], N, (count, 2))
-        plains = _rows(rng, mods, N, (len(giant), len(baby)))
+        ct = rows(rng, mods[:k], N, (count, 2))
+        plains = rows(rng, mods, N, (len(giant), len(baby)))
         d, dp = ctx.upload(ct), ctx.upload(plains)
         out = ctx.alloc(count * 2 * (k - 1) * N)
         ctx.chunk_log()
@@ -483,14 +444,8 @@ def test_chunked_items_and_split_lists():
     """apply_galois_dot_plain_rescale and apply_galois_bsgs_plain_rescale under the smallest arena: ragged item chunks, a
     sum / giant list one longer than what fits next to one item, and the identity-only calls, whose plain rescale nests a
     chunk loop under the raised floor. Chunk logs against the rule; first and last item (and sum) against the restatement."""
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "KS_RESCALE_CHUNKS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "KS_RESCALE_CHUNKS_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

@@ -10,6 +10,7 @@ import pytest
 
 import oracle_lib as O
 import synth
+from support import S as sealhip
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,6 @@ L = O.lib()
 
 def h(a):
     return "%016x" % O.fnv(a)
-
-
-@pytest.fixture(scope="module")
-def sealhip():
-    import sealhip as S
-
-    assert S.num_devices() >= 1, "no HIP device visible: the engine has no CPU fallback"
-    return S
 
 
 def rand_rows(rng, moduli, n, full_range=False):

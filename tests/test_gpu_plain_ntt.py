@@ -5,13 +5,13 @@ decryption on parameters without fast plain lift, where no other plaintext produ
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 from test_plain_ntt_host import build_plain_adapter
+from support import S, run_exe
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +19,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CLASSES = json.load(open(os.path.join(HERE, "golden", "ntt_instance_classes.json")))
 T40 = (1 << 40) - 87  # odd, coprime to every NTT prime used here
 T_VALUES = (2, 1 << 16, 786433, T40)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def lift(plain, t, q):
@@ -279,17 +271,9 @@ def _splitmix(state):
     return state, z ^ (z >> 31)
 
 
-def _fnv(words):
-    h = 0xcbf29ce484222325
-    for b in np.ascontiguousarray(words, dtype="<u8").tobytes():
-        h = ((h ^ b) * 0x100000001b3) & (2**64 - 1)
-    return "%016x" % h
-
-
 def test_cpp_adapter_plain_methods_match_the_abi(S, tmp_path):
     """tests/host_adapter_plain_check.cpp on the device: its digests equal those of the ABI's outputs on the same inputs"""
-    out = subprocess.run([build_plain_adapter(tmp_path), "0"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
+    stdout = run_exe(build_plain_adapter(tmp_path), "0", timeout=300)
     mods = [68719230977, 68719403009, 137438822401]
     t, n, cc = 786433, 4096, 3000
     state, plain = 0x9A17 + 5, []
@@ -300,10 +284,10 @@ def test_cpp_adapter_plain_methods_match_the_abi(S, tmp_path):
     ctx = S.Context(S.SCHEME_BFV, 12, mods, 1, t, device=0)
     res = {k: run_transform(S, ctx, [plain], cc, k, 1, 0)[0] for k in (1, 2, 3)}
     for k in (1, 2, 3):
-        assert "transform_to_ntt k=%d digest %s" % (k, _fnv(res[k])) in out.stdout, out.stdout
-    assert "transform_to_ntt_inplace k=3 digest %s words %d ntt 1" % (_fnv(res[3]), 3 * n) in out.stdout, out.stdout
-    assert "mod_switch_to_next digest %s words %d" % (_fnv(res[2]), 2 * n) in out.stdout, out.stdout
-    assert "mod_switch_to k=1 digest %s words %d" % (_fnv(res[1]), n) in out.stdout, out.stdout
-    assert "in-place switches agree" in out.stdout
+        assert "transform_to_ntt k=%d digest %016x" % (k, O.fnv(res[k])) in stdout, stdout
+    assert "transform_to_ntt_inplace k=3 digest %016x words %d ntt 1" % (O.fnv(res[3]), 3 * n) in stdout, stdout
+    assert "mod_switch_to_next digest %016x words %d" % (O.fnv(res[2]), 2 * n) in stdout, stdout
+    assert "mod_switch_to k=1 digest %016x words %d" % (O.fnv(res[1]), n) in stdout, stdout
+    assert "in-place switches agree" in stdout
     # and the oracle agrees with the ABI
     assert np.array_equal(res[3][None], expected([plain], cc, t, mods, 12, False))

@@ -11,7 +11,6 @@ copy + lift front inside dot_product, N = 2^14 the gathered forward transform an
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,49 +18,19 @@ import pytest
 
 import oracle_lib as O
 import poly_eval_ref as P
+from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe, session_memo, weights
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 TILE, GROUP = 4, 16
 
 
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
-
-
-def _weights(rng, mods, lead):
-    """canonical residues [lead..][k]"""
-    out = np.empty(tuple(lead) + (len(mods),), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r] = rng.integers(0, int(p), size=tuple(lead), dtype=np.uint64)
-    return out
-
-
-class Session:
+class Session(BaseSession):
     """contexts on both sides and a random key: the word-for-word comparison needs no valid key"""
 
     def __init__(self, S, scheme, logn, bits, nsp, mode, t=0, seed=0):
-        self.S, self.n, self.nsp, self.t = S, 1 << logn, nsp, t
-        self.mods = O.coeff_modulus_create(self.n, bits)
-        self.ctx = S.Context(scheme, logn, self.mods, nsp, t, mode=mode)
-        self.ref = O.RefContext(scheme, logn, self.mods, nsp=nsp, t=t, mode=mode)
-        self.rng = np.random.default_rng(seed + logn + len(bits))
-        self.nd = (len(self.mods) - nsp + nsp - 1) // nsp
-        self.ev = S.Evaluator(self.ctx)
-        self.key_host = _rows(self.rng, self.mods, self.n, (self.nd, 2))
+        super().__init__(S, scheme, logn, bits, nsp, mode, t, seed + logn + len(bits))
+        self.key_host = rows(self.rng, self.mods, self.n, (self.nd, 2))
         self.key = S.KSwitchKeys(self.ctx, self.key_host)
         self.pools = {}
 
@@ -70,7 +39,7 @@ class Session:
         key = (k, size, count)
         host, dev = self.pools.setdefault(key, ([], []))
         while len(host) < n_terms:
-            host.append(_rows(self.rng, self.mods[:k], self.n, (count, size)))
+            host.append(rows(self.rng, self.mods[:k], self.n, (count, size)))
             dev.append(self.ctx.upload(host[-1]))
         return host[:n_terms], dev[:n_terms]
 
@@ -90,8 +59,8 @@ class Session:
 
     def compare_lincomb(self, k, size, count, n_terms, n_sums, const, tag, items=None, idx=None, w=None):
         idx = list(range(n_terms)) if idx is None else idx
-        w = _weights(self.rng, self.mods[:k], (n_sums, len(idx))) if w is None else w
-        kc = _weights(self.rng, self.mods[:k], (n_sums,)) if const else None
+        w = weights(self.rng, self.mods[:k], (n_sums, len(idx))) if w is None else w
+        kc = weights(self.rng, self.mods[:k], (n_sums,)) if const else None
         host, got = self.lincomb(k, size, count, idx, w, kc)
         for c in (range(count) if items is None else items):
             want = P.linear_combination(self.ref, k, [host[i][c] for i in idx], w, kc)
@@ -104,14 +73,7 @@ class Session:
                 assert np.array_equal(d.download(h.shape), h), "an operand was modified"
 
 
-_SESSIONS = {}
-
-
-def _session(S, *args, **kw):
-    key = repr((args, sorted(kw.items())))
-    if key not in _SESSIONS:
-        _SESSIONS[key] = Session(S, *args, **kw)
-    return _SESSIONS[key]
+_session = session_memo(Session)
 
 
 # ---------------------------------------------------------------- linear_combination
@@ -142,7 +104,7 @@ def test_lincomb_bfv_words(S, size):
     se.check_pools_unchanged()
     # the constant alone: zero weights leave K at coefficient 0 of polynomial 0 and zeros everywhere else
     w = np.zeros((2, 3, 3), dtype=np.uint64)
-    kc = _weights(se.rng, se.mods[:3], (2,))
+    kc = weights(se.rng, se.mods[:3], (2,))
     _, got = se.lincomb(3, size, 3, [0, 1, 2], w, kc)
     want = np.zeros_like(got)
     want[:, :, 0, :, 0] = kc[:, None, :]
@@ -183,7 +145,7 @@ def test_lincomb_repeated_pointers_and_zero_weights(S, scheme):
     else:
         se, k = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0), 3
     idx = [0, 1, 0, 2, 2]
-    w = _weights(se.rng, se.mods[:k], (3, len(idx)))
+    w = weights(se.rng, se.mods[:k], (3, len(idx)))
     w[:, 1] = 0      # a term nobody uses
     w[1] = 0         # a sum of nothing
     w[2, 3, 1] = 0   # one row of one weight
@@ -201,13 +163,13 @@ def test_lincomb_transparency_flags(S, scheme):
     else:
         se, k = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0), 3
     ctx, ev, n, count, n_terms, n_sums = se.ctx, se.ev, se.n, 3, 17, 5
-    pool = [_rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(n_terms)]
+    pool = [rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(n_terms)]
     for p in pool:
         p[1, 1] = 0
     dev = [ctx.upload(p) for p in pool]
-    w = _weights(se.rng, se.mods[:k], (n_sums, n_terms))
+    w = weights(se.rng, se.mods[:k], (n_sums, n_terms))
     w[3] = 0
-    dw, dk = ctx.upload(w), ctx.upload(_weights(se.rng, se.mods[:k], (n_sums,)))
+    dw, dk = ctx.upload(w), ctx.upload(weights(se.rng, se.mods[:k], (n_sums,)))
     out = ctx.alloc(n_sums * count * 2 * k * n)
     flags = ctx.alloc(8)  # 16 uint32 words
     ctx.transparency_sink(flags, 16)
@@ -230,15 +192,15 @@ def test_lincomb_graph_capture(S):
     """capturable after one warm-up call: three groups and three tiles, replayed on new inputs and new weights"""
     se = _session(S, S.SCHEME_CKKS, 12, [40, 40, 40, 40], 1, 0)
     ctx, ev, n, k, count, n_terms, n_sums = se.ctx, se.ev, se.n, 3, 2, 33, 9
-    dev = [ctx.upload(_rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(n_terms)]
-    dw = ctx.upload(_weights(se.rng, se.mods[:k], (n_sums, n_terms)))
-    dk = ctx.upload(_weights(se.rng, se.mods[:k], (n_sums,)))
+    dev = [ctx.upload(rows(se.rng, se.mods[:k], n, (count, 2))) for _ in range(n_terms)]
+    dw = ctx.upload(weights(se.rng, se.mods[:k], (n_sums, n_terms)))
+    dk = ctx.upload(weights(se.rng, se.mods[:k], (n_sums,)))
     out = ctx.alloc(n_sums * count * 2 * k * n)
     run = lambda: ev.linear_combination(dev, dw, k, count, out, n_sums=n_sums, constant=dk)
     run()
     g = ctx.capture(run)
-    pool = [_rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(n_terms)]
-    w, kc = _weights(se.rng, se.mods[:k], (n_sums, n_terms)), _weights(se.rng, se.mods[:k], (n_sums,))
+    pool = [rows(se.rng, se.mods[:k], n, (count, 2)) for _ in range(n_terms)]
+    w, kc = weights(se.rng, se.mods[:k], (n_sums, n_terms)), weights(se.rng, se.mods[:k], (n_sums,))
     for d, p in zip(dev, pool):
         d.upload(p)
     dw.upload(w)
@@ -307,7 +269,7 @@ def test_polynomial_refusals_that_need_a_device(S):
     """a key with fewer digits than the level; too small a sink; each leaves the output untouched"""
     se = _session(S, S.SCHEME_BFV, 12, [40, 40, 40, 41], 1, S.MODE_STRICT, t=65537)
     ctx, ev, n, k = se.ctx, se.ev, se.n, 3
-    short = S.KSwitchKeys(ctx, _rows(se.rng, se.mods, n, (2, 2)))
+    short = S.KSwitchKeys(ctx, rows(se.rng, se.mods, n, (2, 2)))
     host, dev = se.pool(k, 2, 2, 1)
     sentinel = np.full(2 * 2 * k * n, 0x5A5A5A5A, dtype=np.uint64)
     out = ctx.upload(sentinel)
@@ -330,7 +292,7 @@ def test_polynomial_transparency_flags(S, name):
     se = _session(S, S.SCHEME_BFV, 12, [40, 40, 40, 41], 1, S.MODE_STRICT, t=65537)
     ctx, ev, n, k, count = se.ctx, se.ev, se.n, 3, 3
     coeffs, n_baby, keys = SHAPES[name]
-    x =_rows(se.rng, se.mods[:k], n, (count, 2))
+    x =rows(se.rng, se.mods[:k], n, (count, 2))
     x[1, 1] = 0
     dx, out = ctx.upload(x), ctx.alloc(count * 2 * k * n)
     flags = ctx.alloc(8)
@@ -458,12 +420,8 @@ def test_cpp_adapter(S, tmp_path, scheme):
     encode(value, scale): ref_ckks_encode_value + ref_multiply_plain_ntt + add), and evaluate_polynomial"""
     logn, n, k = 12, 1 << 12, 3
     mods = O.coeff_modulus_create(n, [40, 40, 40, 41])
-    exe = str(tmp_path / "host_adapter_poly_eval_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_poly_eval_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0", scheme] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_poly_eval_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", scheme, *mods, timeout=120)
     sm = O.SplitMix(0x4020)
     terms = [sm.fill(2 * k, n, mods[:k] * 2).reshape(2, k, n) for _ in range(3)]
     key = sm.fill(3 * 2 * 4, n, mods * 6).reshape(3, 2, 4, n)
@@ -492,12 +450,11 @@ def test_cpp_adapter(S, tmp_path, scheme):
         lines = ["%s lincomb digest %016x meta 1" % (side, O.fnv(lin)) for side in ("host", "device")]
         lines += ["%s poly digest %016x meta 1" % (side, O.fnv(poly)) for side in ("host", "device")]
     for line in lines:
-        assert line in out.stdout, (line, out.stdout)
+        assert line in stdout, (line, stdout)
 
 
 # ---------------------------------------------------------------- the smallest arena (a child process)
 LOGN, N = 15, 1 << 15
-ARENA_MB = "64"
 
 
 def _child():
@@ -513,9 +470,9 @@ def _child():
     ev = S.Evaluator(ctx)
     rng = np.random.default_rng(64)
     k, n_terms, n_sums, count = 3, 17, 9, 4
-    pool = [_rows(rng, mods[:k], N, (count, 2)) for _ in range(n_terms)]
+    pool = [rows(rng, mods[:k], N, (count, 2)) for _ in range(n_terms)]
     dev = [ctx.upload(p) for p in pool]
-    w, kc = _weights(rng, mods[:k], (n_sums, n_terms)), _weights(rng, mods[:k], (n_sums,))
+    w, kc = weights(rng, mods[:k], (n_sums, n_terms)), weights(rng, mods[:k], (n_sums,))
     out = ctx.alloc(n_sums * count * 2 * k * N)
     ctx.chunk_log()
     ev.linear_combination(dev, ctx.upload(w), k, count, out, n_sums=n_sums, constant=ctx.upload(kc))
@@ -531,14 +488,8 @@ def _child():
 
 
 def test_lincomb_needs_no_arena():
-    env = dict(os.environ, SEALHIP_WORKSPACE_MB=ARENA_MB)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, env=env,
-                         timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "LINCOMB_ARENA_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_arena_child(__file__, "LINCOMB_ARENA_OK", timeout=300)
 
 
 if __name__ == "__main__" and "--child" in sys.argv:
-    for p in (ROOT, HERE, os.path.join(ROOT, "gemini-seal_amd")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    _child()
+    child_main(_child)

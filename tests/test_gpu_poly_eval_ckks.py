@@ -14,8 +14,6 @@ one. At N = 2^8 a block of 256 pairs straddles two rows (and, at the row 2 k - 1
 variant), and three items of 3 x 2 rows leave the last block half full; at N = 2^12 a block lies inside one row (the uniform
 variant)."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,9 +21,8 @@ import pytest
 import oracle_lib as O
 import poly_eval_ckks_ref as PC
 import poly_eval_ref as P
+from support import BaseSession, S, compile_cpp, rows, run_exe, session_memo, weights
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,28 +32,6 @@ TILE, GROUP = 4, 16
 LEVELS, SIZES = (2, 3, 5), (2, 3)
 
 
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
-
-
-def _rows(rng, mods, n, lead):
-    out = np.empty(tuple(lead) + (len(mods), n), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r, :] = rng.integers(0, int(p), size=tuple(lead) + (n,), dtype=np.uint64)
-    return out
-
-
-def _weights(rng, mods, lead):
-    out = np.empty(tuple(lead) + (len(mods),), dtype=np.uint64)
-    for r, p in enumerate(mods):
-        out[..., r] = rng.integers(0, int(p), size=tuple(lead), dtype=np.uint64)
-    return out
-
-
 def _dropped(x, k, size):
     """[size_t][k_t][N] -> [size][k][N]: the first k rows, zero polynomials up to size"""
     out = np.zeros((size, k, x.shape[-1]), dtype=np.uint64)
@@ -64,21 +39,17 @@ def _dropped(x, k, size):
     return out
 
 
-class Session:
+class Session(BaseSession):
     def __init__(self, S, logn, mode, count=3):
-        self.S, self.n, self.count = S, 1 << logn, count
-        self.mods = O.coeff_modulus_create(self.n, BITS)
-        self.ctx = S.Context(S.SCHEME_CKKS, logn, self.mods, 1, 0, mode=mode)
-        self.ref = O.RefContext(S.SCHEME_CKKS, logn, self.mods, nsp=1, t=0, mode=mode)
-        self.ev = S.Evaluator(self.ctx)
-        self.rng = np.random.default_rng(100 * logn + mode)
+        super().__init__(S, S.SCHEME_CKKS, logn, BITS, 1, mode, 0, 100 * logn + mode)
+        self.count = count
         self.pools = {}
 
     def term(self, level, size, i):
         """the i-th operand batch count x size x level x N, host and device, made once and never modified"""
         host, dev = self.pools.setdefault((level, size), ([], []))
         while len(host) <= i:
-            host.append(_rows(self.rng, self.mods[:level], self.n, (self.count, size)))
+            host.append(rows(self.rng, self.mods[:level], self.n, (self.count, size)))
             dev.append(self.ctx.upload(host[-1]))
         return host[i], dev[i]
 
@@ -113,8 +84,8 @@ class Session:
         return hosts, got
 
     def compare(self, k, size, levels, sizes, n_sums, const, tag, items=None):
-        w = _weights(self.rng, self.mods[:k], (n_sums, len(levels)))
-        kc = _weights(self.rng, self.mods[:k], (n_sums,)) if const else None
+        w = weights(self.rng, self.mods[:k], (n_sums, len(levels)))
+        kc = weights(self.rng, self.mods[:k], (n_sums,)) if const else None
         hosts, got = self.call(k, size, levels, sizes, w, kc)
         for c in (range(self.count) if items is None else items):
             want = P.linear_combination(self.ref, k, [_dropped(h[c], k, size) for h in hosts], w, kc)
@@ -127,13 +98,7 @@ class Session:
                 assert np.array_equal(d.download(h.shape), h), "an operand was modified"
 
 
-_SESSIONS = {}
-
-
-def _session(S, logn, mode):
-    if (logn, mode) not in _SESSIONS:
-        _SESSIONS[(logn, mode)] = Session(S, logn, mode)
-    return _SESSIONS[(logn, mode)]
+_session = session_memo(Session)
 
 
 def test_export_and_method(S):
@@ -174,8 +139,8 @@ def test_levels_other_output_levels_and_sizes(S, logn):
 def test_equal_levels_and_sizes_give_the_existing_entrys_words(S, logn):
     se = _session(S, logn, 0)
     for k, size, n_terms, n_sums in ((5, 2, 5, 1), (5, 3, 17, TILE + 1), (3, 3, 5, 2)):
-        w = _weights(se.rng, se.mods[:k], (n_sums, n_terms))
-        kc = _weights(se.rng, se.mods[:k], (n_sums,))
+        w = weights(se.rng, se.mods[:k], (n_sums, n_terms))
+        kc = weights(se.rng, se.mods[:k], (n_sums,))
         _, a = se.call(k, size, [k] * n_terms, [size] * n_terms, w, kc)
         _, b = se.call(k, size, [k] * n_terms, [size] * n_terms, w, kc, entry="plain")
         assert np.array_equal(a, b), (k, size, n_terms, n_sums)
@@ -196,13 +161,13 @@ def test_levels_transparency_flags(S):
     se = _session(S, 12, 0)
     ctx, ev, n, k, count, n_sums = se.ctx, se.ev, se.n, 2, 3, TILE + 1
     levels, sizes = se.shapes(17)
-    pool = [_rows(se.rng, se.mods[:lv], n, (count, sz)) for lv, sz in zip(levels, sizes)]
+    pool = [rows(se.rng, se.mods[:lv], n, (count, sz)) for lv, sz in zip(levels, sizes)]
     for p in pool:
         p[1, 1:] = 0
     dev = [ctx.upload(p) for p in pool]
-    w = _weights(se.rng, se.mods[:k], (n_sums, 17))
+    w = weights(se.rng, se.mods[:k], (n_sums, 17))
     w[3] = 0
-    dw, dk = ctx.upload(w), ctx.upload(_weights(se.rng, se.mods[:k], (n_sums,)))
+    dw, dk = ctx.upload(w), ctx.upload(weights(se.rng, se.mods[:k], (n_sums,)))
     out = ctx.alloc(n_sums * count * 3 * k * n)
     flags = ctx.alloc(8)  # 16 uint32 words
     ctx.transparency_sink(flags, 16)
@@ -226,16 +191,16 @@ def test_levels_graph_capture(S):
     se = _session(S, 12, 0)
     ctx, ev, n, k, count, n_sums = se.ctx, se.ev, se.n, 2, 2, TILE + 1
     levels, sizes = se.shapes(17)
-    fresh = lambda: [_rows(se.rng, se.mods[:lv], n, (count, sz)) for lv, sz in zip(levels, sizes)]
+    fresh = lambda: [rows(se.rng, se.mods[:lv], n, (count, sz)) for lv, sz in zip(levels, sizes)]
     dev = [ctx.upload(p) for p in fresh()]
-    dw = ctx.upload(_weights(se.rng, se.mods[:k], (n_sums, 17)))
-    dk = ctx.upload(_weights(se.rng, se.mods[:k], (n_sums,)))
+    dw = ctx.upload(weights(se.rng, se.mods[:k], (n_sums, 17)))
+    dk = ctx.upload(weights(se.rng, se.mods[:k], (n_sums,)))
     out = ctx.alloc(n_sums * count * 3 * k * n)
     run = lambda: ev.linear_combination_levels(dev, levels, sizes, dw, k, count, out, size=3, n_sums=n_sums, constant=dk)
     run()
     g = ctx.capture(run)
     pool = fresh()
-    w, kc = _weights(se.rng, se.mods[:k], (n_sums, 17)), _weights(se.rng, se.mods[:k], (n_sums,))
+    w, kc = weights(se.rng, se.mods[:k], (n_sums, 17)), weights(se.rng, se.mods[:k], (n_sums,))
     for d, p in zip(dev, pool):
         d.upload(p)
     dw.upload(w)
@@ -255,7 +220,7 @@ def test_levels_chunk_log_and_refusals_on_a_device(S):
     se = _session(S, 12, 0)
     levels, sizes = se.shapes(17)
     devs = [d for _, d in se.terms(levels, sizes)]
-    dw = se.ctx.upload(_weights(se.rng, se.mods[:2], (1, 17)))
+    dw = se.ctx.upload(weights(se.rng, se.mods[:2], (1, 17)))
     out = se.ctx.alloc(se.count * 3 * 2 * se.n)
     se.ctx.chunk_log()
     se.ev.linear_combination_levels(devs, levels, sizes, dw, 2, se.count, out, size=3)
@@ -301,9 +266,9 @@ class PolySession:
         self.ref = O.RefContext(S.SCHEME_CKKS, 12, self.mods, nsp=1, t=0, mode=mode)
         self.ev = S.Evaluator(self.ctx)
         rng = np.random.default_rng(77 + mode)
-        self.key_host = _rows(rng, self.mods, self.n, (self.k, 2))
+        self.key_host = rows(rng, self.mods, self.n, (self.k, 2))
         self.key = S.KSwitchKeys(self.ctx, self.key_host)
-        self.ct = _rows(rng, self.mods[:self.k], self.n, (self.count, 2))
+        self.ct = rows(rng, self.mods[:self.k], self.n, (self.count, 2))
         self.dct = self.ctx.upload(self.ct)
 
     def run(self, coeffs, basis, n_baby, scale_out=0.0, k=None, keys=True):
@@ -419,7 +384,7 @@ def test_polynomial_transparency_flags(S):
     key, and a random key would make every result opaque)"""
     se = _poly_session(S, 0)
     ctx, n, k, count = se.ctx, se.n, se.k, 3
-    x = _rows(np.random.default_rng(9), se.mods[:k], n, (count, 2))
+    x = rows(np.random.default_rng(9), se.mods[:k], n, (count, 2))
     x[1, 1] = 0
     out = ctx.alloc(count * 2 * (k - 1) * n)
     flags = ctx.alloc(8)
@@ -496,12 +461,8 @@ def test_cpp_adapter(S, tmp_path):
     words on the same seeded inputs, at the plan's level and with the requested scale"""
     logn, n, k = 12, 1 << 12, 8
     mods = O.coeff_modulus_create(n, EBITS)
-    exe = str(tmp_path / "host_adapter_poly_eval_ckks_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_poly_eval_ckks_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "0"] + [str(q) for q in mods], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_poly_eval_ckks_check.cpp", link_sealhip=True)
+    stdout = run_exe(exe, "0", *mods, timeout=120)
     sm = O.SplitMix(0x4021)
     ct = sm.fill(2 * k, n, mods[:k] * 2).reshape(2, k, n)
     key = sm.fill(8 * 2 * 9, n, mods * 16).reshape(8, 2, 9, n)
@@ -512,4 +473,4 @@ def test_cpp_adapter(S, tmp_path):
     for side in ("host", "device"):
         for name, words in (("monomial", mono), ("chebyshev", cheb)):
             line = "%s %s digest %016x meta 1" % (side, name, O.fnv(words))
-            assert line in out.stdout, (line, out.stdout)
+            assert line in stdout, (line, stdout)

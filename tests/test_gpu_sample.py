@@ -6,8 +6,6 @@ keys, encryptions -- made from seeds alone equals the existing entries fed the r
 evaluates."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,23 +13,14 @@ import pytest
 import oracle_lib as O
 import noise_ref as NR
 import sample_ref as R
+from support import S, compile_cpp, run_exe
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 T = 786433  # prime, = 1 mod 2^18
 KINDS = [(1, 0), (0, 1), (1, 2), (0, 3), (2, 2)]
 MAX_POLYS = 4
 SENTINEL = -1234567
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 @functools.lru_cache(maxsize=None)
@@ -316,24 +305,13 @@ def test_session_from_seeds_alone(S, scheme):
 # ---------------------------------------------------------------- through the C++ adapter
 @pytest.fixture(scope="module")
 def adapter_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("sample_adapter") / "host_adapter_sample_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(HERE, "host_adapter_sample_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    return exe
+    return compile_cpp(tmp_path_factory.mktemp("sample_adapter"), "host_adapter_sample_check.cpp", link_sealhip=True, opt="-O1")
 
 
 def seed_number(i):
     """seed number i of the check program's seed source"""
     mask = (1 << 64) - 1
     return np.array([((0x5EED000000000000 + i + j) * 0x9E3779B97F4A7C15) & mask for j in range(8)], dtype=np.uint64)
-
-
-def fnv(data):
-    h = 0xCBF29CE484222325
-    for b in bytes(data):
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return "%016x" % h
 
 
 @pytest.mark.parametrize("scheme", [1, 2])
@@ -356,32 +334,31 @@ def test_cpp_adapter_with_a_seed_source(S, adapter_exe, tmp_path, scheme):
     path = str(tmp_path / "input.bin")
     np.concatenate([np.array([scheme, logn, n_key, nsp, t] + mods + list(pid), dtype=np.uint64),
                     plain_host.reshape(-1)]).astype("<u8").tofile(path)
-    out = subprocess.run([adapter_exe, "0", path], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
+    stdout = run_exe(adapter_exe, "0", path, timeout=300)
     for line in ("seeded save ok", "scratch zero ok", "sample adapter ok"):
-        assert line in out.stdout, out.stdout
+        assert line in stdout, stdout
     ctx = S.Context(scheme, logn, mods, nsp, t)
     ctx.set_parms_id(n_key, pid)
     d = ctx.kswitch_digits(k)
-    assert "seeds drawn %d" % (3 + 2 * d + 3) in out.stdout, out.stdout
+    assert "seeds drawn %d" % (3 + 2 * d + 3) in stdout, stdout
     host = lambda seeds, nt, nn: R.sample_polys(S, seeds, n, nt, nn)
     d_sk = ctx.generate_secret_key(seed_number(0))
-    assert "sk digest " + fnv(d_sk.download()) in out.stdout, out.stdout
+    assert "sk digest %016x" % O.fnv(d_sk.download()) in stdout, stdout
     a, pk = ctx.alloc(n_key * n), ctx.alloc(2 * n_key * n)
     ctx.expand_seeds(n_key, seed_number(1), a)
     ctx.encrypt_zero_symmetric(n_key, True, a, ctx.upload_i32(host(seed_number(2), 0, 1)), d_sk, 1, pk)
-    assert "pk digest " + fnv(pk.download()) in out.stdout, out.stdout
+    assert "pk digest %016x" % O.fnv(pk.download()) in stdout, stdout
     c1 = np.stack([seed_number(3 + 2 * j) for j in range(d)])
     noise = np.stack([seed_number(4 + 2 * j) for j in range(d)])
     rk = ctx.generate_relin_keys(d_sk, 1, c1, ctx.upload_i32(host(noise, 0, 1)))
     stream = S.save_kswitch_keys(ctx, rk)
-    assert "rk digest " + fnv(stream[: len(stream) // 8 * 8]) in out.stdout, out.stdout
+    assert "rk digest %016x" % O.fnv(np.frombuffer(stream[: len(stream) // 8 * 8], dtype=np.uint64)) in stdout, stdout
     first = 3 + 2 * d
     plain = ctx.upload(plain_host)
     fed = host(seed_number(first), 1, 2)
     ct = ctx.alloc(2 * k * n)
     ctx.encrypt(k, pk, plain, ctx.upload_i32(fed[:, 0]), ctx.upload_i32(fed[:, 1:]), 1, ct)
-    assert "asym digest " + fnv(ct.download()) in out.stdout, out.stdout
+    assert "asym digest %016x" % O.fnv(ct.download()) in stdout, stdout
     ctx.encrypt_symmetric(k, d_sk, plain, seed_number(first + 1), ctx.upload_i32(host(seed_number(first + 2), 0, 1)), 1, ct)
-    assert "sym digest " + fnv(ct.download()) in out.stdout, out.stdout
+    assert "sym digest %016x" % O.fnv(ct.download()) in stdout, stdout
     ctx.close()

@@ -16,19 +16,12 @@ import pytest
 
 import oracle_lib as O
 from test_seed_expand_host import reject_chain, restated_expand
+from support import S
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import sealhip
-
-    assert sealhip.num_devices() >= 1
-    return sealhip
 
 
 def wire():
@@ -176,6 +169,7 @@ print(json.dumps({{"log": log, "bad": bad}}))
 
 
 def test_chunked_batch_in_a_small_arena(S):
+    # (not run_arena_child: the child is the source above and answers in JSON)
     env = dict(os.environ, SEALHIP_WORKSPACE_MB="64")
     code = CHUNK_CHILD.format(root=ROOT, tests=HERE, pkg=os.path.join(ROOT, "gemini-seal_amd"))
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)

@@ -5,7 +5,6 @@ sum_j sigma_{h_j}( sum_i w_ji * sigma_{g_i}(m) ) (BFV STRICT), within the error 
 degenerate shapes are, word for word, what they reduce to."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import hoist_bsgs_ref as HB
 import hoist_dot_ref as HD
 import hoist_ref as H
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -264,9 +264,5 @@ def test_degenerate_shapes_are_what_they_reduce_to(scheme):
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_bsgs_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_bsgs_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only bsgs checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_bsgs_check.cpp", link_sealhip=True)
+    assert "host-only bsgs checks ok" in run_exe(exe, "host", timeout=120)

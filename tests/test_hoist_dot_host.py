@@ -4,7 +4,6 @@ header's order; and the CPU restatement (tests/hoist_dot_ref.py) itself: it decr
 (BFV STRICT) and within the error of the composition it replaces (CKKS), with other words than the composition."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import hoist_dot_ref as HD
 import hoist_ref as H
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -215,9 +215,5 @@ def test_restatement_ckks_error_of_the_composition(bits, nsp, mode):
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_hoist_dot_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_hoist_dot_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only hoist dot checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_hoist_dot_check.cpp", link_sealhip=True)
+    assert "host-only hoist dot checks ok" in run_exe(exe, "host", timeout=120)

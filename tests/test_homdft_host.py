@@ -5,13 +5,13 @@ matrices, the BSGS grid against M v, and the host restatement of the generator (
 the layer products. Then the refusals on host-only contexts, and the planner header under the sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import homdft_ref as R
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -208,12 +208,8 @@ def test_refusals_on_host_only_contexts():
 
 def test_planner_program_under_sanitizers(tmp_path):
     """gemini-seal_amd/csrc/homdft_plan.hpp compiled for the host with AddressSanitizer and UBSan into a program of its own"""
-    exe = str(tmp_path / "homdft_plan_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "gemini-seal_amd", "csrc"), "-o", exe,
-                           os.path.join(HERE, "homdft_plan_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "homdft_plan_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "homdft_plan_check.cpp", sanitize=True)
+    assert "homdft_plan_check: OK" in run_exe(exe, timeout=300)
 
 
 def test_reference_chain_decrypts_on_the_cpu():
@@ -290,9 +286,5 @@ def test_reference_chain_decrypts_on_the_cpu():
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_homdft_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_homdft_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only homdft checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_homdft_check.cpp", link_sealhip=True)
+    assert "host-only homdft checks ok" in run_exe(exe, "host", timeout=120)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -339,11 +340,7 @@ def test_bench_dump_outputs_stub(tmp_path):
 def _build_adapter(tmp_path):
     import subprocess
 
-    exe = str(tmp_path / "host_adapter_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(ROOT, "tests", "host_adapter_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    return exe
+    return compile_cpp(tmp_path, "host_adapter_check.cpp", link_sealhip=True)
 
 
 def test_cpp_host_adapter_compiles_and_links(tmp_path):
@@ -363,11 +360,8 @@ def test_shortcut_bounds_are_proved_not_sampled(tmp_path):
     Invariant: native/src/seal/util/defines.h:52-53, butterflies util/ntt.cpp:245-281."""
     import subprocess
 
-    exe = str(tmp_path / "bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "bounds_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "bounds_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "bounds_check.cpp", extra=("-ffp-contract=off",))
+    assert "bounds_check: OK" in run_exe(exe, timeout=300)
 
 
 def test_ntt_instance_classes_fixture_follows_the_predicates(tmp_path):
@@ -379,14 +373,11 @@ def test_ntt_instance_classes_fixture_follows_the_predicates(tmp_path):
     import json
     import subprocess
 
-    exe = str(tmp_path / "bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "bounds_check.cpp")])
-    out = subprocess.run([exe, "--classes"], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "bounds_check.cpp", extra=("-ffp-contract=off",))
+    stdout = run_exe(exe, "--classes", timeout=60)
     with open(os.path.join(ROOT, "tests", "golden", "ntt_instance_classes.json")) as f:
         committed = f.read()
-    assert out.stdout == committed
+    assert stdout == committed
     classes = json.loads(committed)
     assert sorted(classes) == ["14", "15", "16"]
     for logn, c in classes.items():
@@ -497,10 +488,7 @@ def test_f3_seed_expansion_blake2xb_known_answers_and_oracle():
 def _behz_bounds_exe(tmp_path):
     import subprocess
 
-    exe = str(tmp_path / "bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe,
-                           os.path.join(ROOT, "tests", "bounds_check.cpp")])
-    return exe
+    return compile_cpp(tmp_path, "bounds_check.cpp", extra=("-ffp-contract=off",))
 
 
 def test_behz_instance_classes_fixture_follows_the_predicate(tmp_path):
@@ -510,11 +498,10 @@ def test_behz_instance_classes_fixture_follows_the_predicate(tmp_path):
     import json
     import subprocess
 
-    out = subprocess.run([_behz_bounds_exe(tmp_path), "--behz-classes"], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
+    stdout = run_exe(_behz_bounds_exe(tmp_path), "--behz-classes", timeout=60)
     with open(os.path.join(ROOT, "tests", "golden", "behz_instance_classes.json")) as f:
         committed = f.read()
-    assert out.stdout == committed
+    assert stdout == committed
     classes = json.loads(committed)
     assert sorted(map(int, classes)) == list(range(3, 17))
     for logn, c in classes.items():

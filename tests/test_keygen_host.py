@@ -3,16 +3,13 @@ what can be checked without a GPU. The argument checks of the new entries on a h
 E_INVALIDARG, COR_E_INVALIDOPERATION; the Python mirrors; and the C++ KeyGenerator's host checks with the reference's
 messages (keygenerator.cpp:146-240)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NEW = ("sealhip_generate_relin_keys", "sealhip_generate_galois_keys", "sealhip_kswitch_keys_save_seeded")
 
 
@@ -101,16 +98,11 @@ def test_no_context_without_key_switching():
 
 # ------------------------------------------------------------------ the C++ adapter
 def build_keygen_adapter(tmp_path):
-    exe = str(tmp_path / "host_adapter_keygen_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_keygen_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    return exe
+    return compile_cpp(tmp_path, "host_adapter_keygen_check.cpp", link_sealhip=True)
 
 
 def test_cpp_keygenerator_checks_on_host_only_context(tmp_path):
     """relin_keys: "invalid count"; galois_keys: "Galois element is not valid", "step count too large" (invalid_argument) and
     "encryption parameters do not support batching" (logic_error) before any sample is drawn; get_elts_all's list; duplicate
     elements draw no samples; a valid call is refused by the host-only context"""
-    out = subprocess.run([build_keygen_adapter(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only keygen checks ok" in out.stdout, out.stdout + out.stderr
+    assert "host-only keygen checks ok" in run_exe(build_keygen_adapter(tmp_path), timeout=120)

@@ -5,7 +5,6 @@ its exact quotient agrees with Python's big integers, and it decrypts within the
 kernels' arithmetic executed on the CPU (tests/ks_rescale_bounds_check.cpp); the C++ adapter's checks."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import hoist_dot_ref as HD
 import hoist_ref as H
 import ks_rescale_ref as R
 import oracle_lib as O
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -377,16 +377,10 @@ def test_bsgs_plain_rescale_decrypts(mode):
 
 
 def test_kernel_arithmetic_on_the_cpu(tmp_path):
-    exe = str(tmp_path / "ks_rescale_bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "ks_rescale_bounds_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ks_rescale_bounds_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "ks_rescale_bounds_check.cpp")
+    assert "ks_rescale_bounds_check: OK" in run_exe(exe, timeout=300)
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_ks_rescale_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_ks_rescale_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only ks rescale checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_ks_rescale_check.cpp", link_sealhip=True)
+    assert "host-only ks rescale checks ok" in run_exe(exe, "host", timeout=120)

@@ -2,16 +2,11 @@
 what can be checked without a GPU. The lift formula of the device path (poly.hip plain_lift_centered_kernel) against a
 literal restatement of the reference's two branches (evaluator.cpp:1682-1737) in Python integers; the new entries on a
 host-only context; and the C++ adapter's host checks with the reference's messages."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from support import compile_cpp, run_exe
 
 
 # ------------------------------------------------------------------ the reference's two branches, restated literally
@@ -199,16 +194,11 @@ def test_mod_switch_plain_to_on_host_only_context():
 
 # ------------------------------------------------------------------ the C++ adapter
 def build_plain_adapter(tmp_path):
-    exe = str(tmp_path / "host_adapter_plain_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_plain_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    return exe
+    return compile_cpp(tmp_path, "host_adapter_plain_check.cpp", link_sealhip=True)
 
 
 def test_cpp_adapter_plain_checks_on_host_only_context(tmp_path):
     """transform_to_ntt(_inplace) / mod_switch_to(_next)(_inplace) of plaintexts: is_valid_for (valcheck.cpp:236-281), "plain
     is already in NTT form", "plain is not in NTT form", "cannot switch to higher level modulus", "end of modulus switching
     chain reached" as std::invalid_argument; a valid call is refused by the host-only context"""
-    out = subprocess.run([build_plain_adapter(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only plain checks ok" in out.stdout, out.stdout + out.stderr
+    assert "host-only plain checks ok" in run_exe(build_plain_adapter(tmp_path), timeout=120)

@@ -6,13 +6,13 @@ Python restatement (tests/poly_eval_ckks_ref.py) bit for bit; the planner header
 -- treating a prime as Delta anywhere is then an error of order 1 -- the result decrypts to p(message)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import poly_eval_ckks_ref as PC
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -304,21 +304,13 @@ def test_chebyshev_chunks_reproduce_chebval():
 
 def test_planner_program_under_sanitizers(tmp_path):
     """gemini-seal_amd/csrc/poly_plan.hpp compiled for the host with AddressSanitizer and UBSan into a program of its own"""
-    exe = str(tmp_path / "poly_plan_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "gemini-seal_amd", "csrc"), "-o", exe,
-                           os.path.join(HERE, "poly_plan_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "poly_plan_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "poly_plan_check.cpp", sanitize=True)
+    assert "poly_plan_check: OK" in run_exe(exe, timeout=120)
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_poly_eval_ckks_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_poly_eval_ckks_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only poly_eval_ckks checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_poly_eval_ckks_check.cpp", link_sealhip=True)
+    assert "host-only poly_eval_ckks checks ok" in run_exe(exe, "host", timeout=120)
 
 
 # ---------------------------------------------------------------- decryption

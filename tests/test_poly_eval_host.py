@@ -5,7 +5,6 @@ restatement (tests/poly_eval_ref.py) itself: degree one is multiply_plain plus t
 power-basis sum, and a degree-7 polynomial decrypts to p(m) with noise budget to spare."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 import noise_ref as R
 import oracle_lib as O
 import poly_eval_ref as P
+from support import compile_cpp, run_exe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -190,19 +190,13 @@ def test_too_many_outer_terms():
 
 def test_sum_capacity_bounds_program(tmp_path):
     """ntt_bounds.hpp lincomb_group_admits and the kernel's accumulation against exact arithmetic"""
-    exe = str(tmp_path / "lincomb_bounds_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "lincomb_bounds_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "lincomb_bounds_check: OK" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "lincomb_bounds_check.cpp")
+    assert "lincomb_bounds_check: OK" in run_exe(exe, timeout=120)
 
 
 def test_cpp_adapter_checks_on_host_only_context(tmp_path):
-    exe = str(tmp_path / "host_adapter_poly_eval_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HERE, "host_adapter_poly_eval_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only poly_eval checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_poly_eval_check.cpp", link_sealhip=True)
+    assert "host-only poly_eval checks ok" in run_exe(exe, "host", timeout=120)
 
 
 # ---------------------------------------------------------------- the restatement itself

@@ -5,13 +5,13 @@ sampler word for word; the committed thresholds are the formula's; and the sampl
 (tests/sample_law_check.cpp draws it the reference's way)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import sample_ref as R
+from support import compile_cpp, run_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = [(1, 0), (0, 1), (1, 2), (0, 3), (2, 2)]
@@ -162,12 +162,10 @@ def test_samples_follow_the_law():
 def test_table_is_the_reference_law(tmp_path):
     """normal_distribution(0, 3.2), redraw beyond 19.2, truncate (tests/sample_law_check.cpp): its histogram of 2^20 samples
     against the table, same cells and bound"""
-    exe = str(tmp_path / "sample_law_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(ROOT, "tests", "sample_law_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "sample_law_check.cpp")
+    stdout = run_exe(exe, timeout=120)
     hist = {}
-    for line in out.stdout.splitlines():
+    for line in stdout.splitlines():
         a, b = line.split()
         if a != "samples_per_second":
             hist[int(a)] = int(b)
@@ -182,9 +180,5 @@ def test_cpp_seed_source_checks_on_host_only_context(tmp_path):
     seed first and a repeated seed is refused, generate_secret_key draws one seed and has no host fallback. (With a device
     the same program counts the draws of every operation and searches the seeded save for noise seeds:
     tests/test_gpu_sample.py.)"""
-    exe = str(tmp_path / "host_adapter_sample_check")
-    libdir = os.path.join(ROOT, "gemini-seal_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "host_adapter_sample_check.cpp"),
-                           "-L" + libdir, "-lsealhip", "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "host-only sample checks ok" in out.stdout, out.stdout + out.stderr
+    exe = compile_cpp(tmp_path, "host_adapter_sample_check.cpp", link_sealhip=True, opt="-O1")
+    assert "host-only sample checks ok" in run_exe(exe, timeout=120)
