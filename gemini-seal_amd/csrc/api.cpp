@@ -751,6 +751,27 @@ long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t 
     });
 }
 
+long sealhip_debug_behz_dot_split(sealhip_context *ctx, uint32_t k, int32_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        Engine &e = *ctx->engine;
+        check_level(e, k);
+        if (e.scheme != 1)
+            throw std::invalid_argument("BFV contexts only");
+        // with a device: what the level's tables were packed with; host-only contexts: what they would be packed with
+        if (e.device >= 0)
+        {
+            *out = e.level(static_cast<int>(k)).h_rns.dot_split;
+            return;
+        }
+        const HostRnsTool &r = *e.level_host(static_cast<int>(k)).host_rns;
+        const u64 max_q = *std::max_element(r.q.begin(), r.q.end()), max_b = *std::max_element(r.Bsk.begin(), r.Bsk.end());
+        *out = bounds::behz_select_split(static_cast<int>(k), max_q, max_b);
+    });
+}
+
 /* ---------------------------------------------------------------- NTT */
 long sealhip_ntt_negacyclic_harvey_lazy(sealhip_context *ctx, uint64_t *data, size_t count, uint32_t k, uint32_t base)
 {

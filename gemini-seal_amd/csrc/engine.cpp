@@ -579,25 +579,30 @@ namespace sealhip
             rd.lift_L1m = upload<u64>(*this, lt.owned, L1m.data(), L1m.size());
             rd.floor_G2m = upload<u64>(*this, lt.owned, G2m.data(), G2m.size());
             rd.B_to_qm = upload<u64>(*this, lt.owned, BQm.data(), BQm.size());
-            // the exact-k instances read every dot product's constants as one contiguous row, pre-split for DotAcc31
-            // (dotacc.hpp dot31_pack), with the row's prime and -p^-1 mod 2^64 behind them
+            // the exact-k instances read every dot product's constants as one contiguous row, pre-split at the level's
+            // split position (dotacc.hpp dot_pack), with the row's prime and -p^-1 mod 2^64 behind them. The split is 30
+            // where the level's primes leave room for it (one accumulator per part up to 8 primes), 31 otherwise
+            // (ntt_bounds.hpp section 5; 31 above the exact-k instances, which alone read the packed tables)
+            rd.dot_split = bounds::behz_select_split(k, max_q, max_b);
             {
+                const int split = rd.dot_split;
+                const auto pack = [split](u64 c) { return dot_pack(split, c); };
                 const std::size_t ls = static_cast<std::size_t>(k) + 3, qs = static_cast<std::size_t>(B) + 4;
                 std::vector<u64> lrows(nB * ls), frows(5 * nB * ls), qrows(k * qs), first(5 * static_cast<std::size_t>(k) * 3);
                 for (int j = 0; j < nB; j++)
                 {
                     u64 *lr = &lrows[j * ls];
-                    lr[0] = dot31_pack(rd.lift_L2m[j]);
+                    lr[0] = pack(rd.lift_L2m[j]);
                     for (int i = 0; i < k; i++)
-                        lr[1 + i] = dot31_pack(L1m[static_cast<std::size_t>(j) * k + i]);
+                        lr[1 + i] = pack(L1m[static_cast<std::size_t>(j) * k + i]);
                     lr[k + 1] = rd.b_p[j];
                     lr[k + 2] = rd.b_ninv[j];
                     for (int sel = 0; sel < 5; sel++)
                     {
                         u64 *fr = &frows[(static_cast<std::size_t>(sel) * nB + j) * ls];
-                        fr[0] = dot31_pack(sel < 4 ? rd.floor_G1m_top[sel][j] : rd.floor_G1m[j]);
+                        fr[0] = pack(sel < 4 ? rd.floor_G1m_top[sel][j] : rd.floor_G1m[j]);
                         for (int i = 0; i < k; i++)
-                            fr[1 + i] = dot31_pack(G2m[static_cast<std::size_t>(j) * k + i]);
+                            fr[1 + i] = pack(G2m[static_cast<std::size_t>(j) * k + i]);
                         fr[k + 1] = rd.b_p[j];
                         fr[k + 2] = rd.b_ninv[j];
                     }
@@ -605,10 +610,10 @@ namespace sealhip
                 for (int i = 0; i < k; i++)
                 {
                     u64 *qr = &qrows[i * qs];
-                    qr[0] = dot31_pack(rd.pBm[i]);
-                    qr[1] = dot31_pack(rd.nBm[i]);
+                    qr[0] = pack(rd.pBm[i]);
+                    qr[1] = pack(rd.nBm[i]);
                     for (int j = 0; j < B; j++)
-                        qr[2 + j] = dot31_pack(BQm[static_cast<std::size_t>(i) * B + j]);
+                        qr[2 + j] = pack(BQm[static_cast<std::size_t>(i) * B + j]);
                     qr[B + 2] = rd.q_p[i];
                     qr[B + 3] = rd.q_ninv[i];
                     for (int sel = 0; sel < 5; sel++)
@@ -620,7 +625,7 @@ namespace sealhip
                     }
                 }
                 for (int j = 0; j < B; j++)
-                    rd.B_to_mskp[j] = dot31_pack(rd.B_to_mskm[j]);
+                    rd.B_to_mskp[j] = pack(rd.B_to_mskm[j]);
                 rd.lift_rows = upload<u64>(*this, lt.owned, lrows.data(), lrows.size());
                 rd.floor_rows = upload<u64>(*this, lt.owned, frows.data(), frows.size());
                 rd.q_rows = upload<u64>(*this, lt.owned, qrows.data(), qrows.size());

@@ -167,7 +167,7 @@ namespace sealhip
         u64 inv_prod_B_mod_msk_s;
         u64 pBm[kMaxModuli], nBm[kMaxModuli]; // prod_B_mod_q * 2^64, (q - prod_B_mod_q) * 2^64  (mod q_i)
         // the same constants as the exact-k instances read them: one contiguous row per dot product, every constant split
-        // for DotAcc31 (dotacc.hpp dot31_pack), followed by the row's prime p and -p^-1 mod 2^64 (not packed)
+        // at dot_split (dotacc.hpp dot_pack), followed by the row's prime p and -p^-1 mod 2^64 (not packed)
         const u64 *lift_rows;   // [nB][k + 3]     {lift_L2m[j], lift_L1m[j][0..k-1], p, ninv}
         const u64 *floor_rows;  // [5][nB][k + 3]  {G1[j], floor_G2m[j][0..k-1], p, ninv}; G1 = floor_G1m_top[sel] (sel < 4), floor_G1m (4)
         const u64 *q_rows;      // [k][B + 4]      {pBm[i], nBm[i], B_to_qm[i][0..B-1], p, ninv}
@@ -179,6 +179,7 @@ namespace sealhip
         u64 dsr_neg_inv_q_t, dsr_neg_inv_q_g, dsr_inv_gamma_t, dsr_gamma;
         unsigned gamma_prime; // PrimeDev id of gamma
         int redc_small;                        // every REDC of the fused kernels provably lands below 2p
+        int dot_split;                         // 30 or 31: the split the packed rows above carry (bounds::behz_select_split)
         // (32-bit: there are no sub-dword scalar loads; a 16-bit id became a VECTOR load with a vmcnt(0) wait in the middle
         //  of every row loop)
         unsigned q_prime[kMaxModuli];       // prime ids of q rows

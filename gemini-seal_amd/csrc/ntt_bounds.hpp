@@ -444,6 +444,170 @@ namespace sealhip
                     return false;
             return true;
         }
+        // The same form with the split position S as a parameter (dotacc.hpp DotAccSplit<S, ...>): t = t1 2^S + t0 and
+        // c = c1 2^S + c0. A dot product is described by the widths of its operand classes: the per-lane factor of term 0
+        // (below 2^first_bits), the per-lane factors of the other terms (below 2^lane_bits) and the wave-uniform constants
+        // (below 2^const_bits). An operand below 2^w has a low part of at most 2^min(w, S) - 1 and a high part of at most
+        // 2^(w - S) - 1, both reached by 2^w - 1. The products are dealt as DotAccSplit::add deals them: t0 c0 of term i to
+        // L[i % NL], t0 c1 to M[2i % NM], t1 c0 to M[(2i + 1) % NM], t1 c1 to H[i % NH].
+        struct DotShape
+        {
+            int nterms, first_bits, lane_bits, const_bits;
+        };
+        constexpr u128 split_lo_max(int bits, int s) { return (static_cast<u128>(1) << (bits < s ? bits : s)) - 1; }
+        constexpr u128 split_hi_max(int bits, int s) { return bits > s ? (static_cast<u128>(1) << (bits - s)) - 1 : 0; }
+        constexpr bool dotsplit_shape_ok(int s, const DotShape &d)
+        {
+            // both halves of every operand are 32-bit words (one v_mad_u64_u32 per product)
+            return s >= 1 && s <= 32 && d.nterms >= 1 && d.nterms <= 64 && d.first_bits >= 1 && d.lane_bits >= 1 &&
+                   d.const_bits >= 1 && d.first_bits - s <= 32 && d.lane_bits - s <= 32 && d.const_bits - s <= 32;
+        }
+        // part 0, 1, 2 = L, M, H: the worst-case sum of every one of the part's `count` accumulators stays below 2^64
+        constexpr bool dotsplit_part_fits(int s, const DotShape &d, int part, int count)
+        {
+            if (!dotsplit_shape_ok(s, d) || count < 1 || count > 2 * d.nterms)
+                return false;
+            const u128 c0 = split_lo_max(d.const_bits, s), c1 = split_hi_max(d.const_bits, s);
+            for (int a = 0; a < count; a++)
+            {
+                u128 sum = 0;
+                for (int i = 0; i < d.nterms; i++)
+                {
+                    const int w = i == 0 ? d.first_bits : d.lane_bits;
+                    const u128 t0 = split_lo_max(w, s), t1 = split_hi_max(w, s);
+                    if (part == 0 && i % count == a)
+                        sum += t0 * c0;
+                    if (part == 1 && (2 * i) % count == a)
+                        sum += t0 * c1;
+                    if (part == 1 && (2 * i + 1) % count == a)
+                        sum += t1 * c0;
+                    if (part == 2 && i % count == a)
+                        sum += t1 * c1;
+                }
+                if (sum > kWord - 1)
+                    return false;
+            }
+            return true;
+        }
+        // the fewest accumulators of a part that fit (0: the shape is not admitted at all)
+        constexpr int dotsplit_count(int s, const DotShape &d, int part)
+        {
+            for (int n = 1; n <= 2 * d.nterms; n++)
+                if (dotsplit_part_fits(s, d, part, n))
+                    return n;
+            return 0;
+        }
+        // the assembled sum: nterms products of the operands themselves, below 2^128
+        constexpr bool dotsplit_total_fits(const DotShape &d)
+        {
+            if (d.first_bits + d.const_bits > 126 || d.lane_bits + d.const_bits > 126)
+                return false;
+            const u128 c = (static_cast<u128>(1) << d.const_bits) - 1;
+            const u128 first = ((static_cast<u128>(1) << d.first_bits) - 1) * c;
+            const u128 other = ((static_cast<u128>(1) << d.lane_bits) - 1) * c;
+            u128 sum = first;
+            for (int i = 1; i < d.nterms; i++)
+            {
+                if (other > ~static_cast<u128>(0) - sum)
+                    return false;
+                sum += other;
+            }
+            return true;
+        }
+        // THE predicate: a dot product of shape d, accumulated at split s in (nl, nm, nh) accumulators, never wraps
+        constexpr bool dotsplit_ok(int s, const DotShape &d, int nl, int nm, int nh)
+        {
+            return dotsplit_part_fits(s, d, 0, nl) && dotsplit_part_fits(s, d, 1, nm) && dotsplit_part_fits(s, d, 2, nh) &&
+                   dotsplit_total_fits(d);
+        }
+        // split at 31 on 61-bit operands throughout is DotAcc31: the derived counts are the closed forms above
+        constexpr bool dotsplit31_matches(int max_terms)
+        {
+            for (int t = 1; t <= max_terms; t++)
+            {
+                const DotShape d{ t, kDotAccOperandBits, kDotAccOperandBits, kDotAccOperandBits };
+                if (dotsplit_count(31, d, 0) != dotacc31_nl(t) || dotsplit_count(31, d, 1) != dotacc31_nm(t) ||
+                    dotsplit_count(31, d, 2) != dotacc31_nh(t) || !dotsplit_total_fits(d))
+                    return false;
+            }
+            return true;
+        }
+        static_assert(dotsplit31_matches(34), "DotAccSplit<31> on 61-bit operands has DotAcc31's accumulators");
+        // The dot products of the exact-k BEHZ instances (rns.hip) and their operand classes, for ciphertext primes below
+        // 2^qb and auxiliary primes (the base Bsk) below 2^bb:
+        //   t[i]   lift and floor: a canonical Shoup product modulo q_i                                  below 2^qb
+        //   temp   lift, term 0: the centred r_m_tilde, below 2^31 or 2^32 - r below b_j (bb >= 32)       below 2^bb
+        //   x      floor Bsk rows, term 0: before_top<true> leaves it below 2 b_j, NOT canonical          below 2^(bb + 1)
+        //   tb[j]  floor: a canonical REDC modulo b_j                                                     below 2^bb
+        //   a2     floor q rows, term 0: min(alpha, m_sk - alpha), at most m_sk / 2                       below 2^bb
+        //   constants: host-folded Montgomery forms, canonical modulo the row's prime: below 2^bb on the Bsk rows and in
+        //              conv_sk (modulo m_sk), below 2^qb on the q rows
+        // kind 0: lift row {temp, t[0..k-1]} x b_j;  1: floor Bsk row {x, t[0..k-1]} x b_j;  2: conv_sk {tb[0..k]} x m_sk (an
+        // instance holds k + 1 terms; a level with |B| = k adds k of them);  3: floor q row {a2, tb[0..k]} x q_i
+        constexpr int kBehzDotKinds = 4;
+        constexpr DotShape behz_dot_shape(int kind, int k, int qb, int bb)
+        {
+            return kind == 0   ? DotShape{ k + 1, bb, qb, bb }
+                   : kind == 1 ? DotShape{ k + 1, bb + 1, qb, bb }
+                   : kind == 2 ? DotShape{ k + 1, bb, bb, bb }
+                               : DotShape{ k + 2, bb, bb, qb };
+        }
+        // The widths the S = 30 instances are built for: auxiliary primes are 60-bit (engine.cpp get_primes(n, 60, ...)),
+        // ciphertext primes below 2^59, the widest the fused tensor path takes (pipeline.cpp plan_bfv_multiply). Up to k = 8
+        // and from k = 12 on the accumulators are the ones 58-bit primes would get; k = 9, 10, 11 pay one more cross
+        // accumulator for the last bit. At S = 31 the instances keep 61 bits throughout.
+        constexpr int kSplit30QBits = 59, kSplit30BBits = 60;
+        constexpr DotShape behz_built_shape(int s, int kind, int k)
+        {
+            return s == 30 ? behz_dot_shape(kind, k, kSplit30QBits, kSplit30BBits)
+                           : DotShape{ kind == 3 ? k + 2 : k + 1, kDotAccOperandBits, kDotAccOperandBits, kDotAccOperandBits };
+        }
+        constexpr int bit_width(u64 v)
+        {
+            int b = 0;
+            while (v)
+            {
+                b++;
+                v >>= 1;
+            }
+            return b;
+        }
+        // Selection (engine.cpp, per level): the instances of split s, with the accumulators they were built with, admit
+        // a level whose largest ciphertext prime is max_q and whose largest auxiliary prime is max_b
+        constexpr bool behz_split_admits(int s, int k, u64 max_q, u64 max_b)
+        {
+            const int qb = bit_width(max_q), bb = bit_width(max_b);
+            if (k < 1 || k > 15 || bb < 32) // (temp's class; kBehzExactMaxK, section 7)
+                return false;
+            for (int kind = 0; kind < kBehzDotKinds; kind++)
+            {
+                const DotShape built = behz_built_shape(s, kind, k), have = behz_dot_shape(kind, k, qb, bb);
+                if (!dotsplit_ok(s, have, dotsplit_count(s, built, 0), dotsplit_count(s, built, 1), dotsplit_count(s, built, 2)))
+                    return false;
+            }
+            return true;
+        }
+        constexpr int behz_select_split(int k, u64 max_q, u64 max_b) { return behz_split_admits(30, k, max_q, max_b) ? 30 : 31; }
+        constexpr bool behz_split_all_ok(int s, u64 max_q, u64 max_b)
+        {
+            for (int k = 1; k <= 15; k++)
+                if (!behz_split_admits(s, k, max_q, max_b))
+                    return false;
+            return true;
+        }
+        static_assert(behz_split_all_ok(30, (u64(1) << kSplit30QBits) - 1, (u64(1) << kSplit30BBits) - 1),
+                      "S = 30: every dot product of every exact-k instance (term counts up to k + 2 = 17) at the widths it is built for");
+        static_assert(behz_split_all_ok(31, (u64(1) << 60) - 1, (u64(1) << 60) - 1),
+                      "S = 31 serves every level the context admits: x below 2^61, everything else below 2^60");
+        // one accumulator per part is what the split at 30 buys at the headline level (k = 7 and 8, |B| = k + 1 at most)
+        static_assert(dotsplit_count(30, behz_built_shape(30, 1, 7), 0) == 1 && dotsplit_count(30, behz_built_shape(30, 1, 7), 1) == 1 &&
+                          dotsplit_count(30, behz_built_shape(30, 1, 7), 2) == 1 && dotsplit_count(30, behz_built_shape(30, 3, 7), 1) == 1,
+                      "k = 7 at S = 30: single accumulators");
+        // 60-bit ciphertext primes put 2 (k + 1) + 1 cross products of 2^60 into the floor rows' one M accumulator: refused
+        // from k = 7 on, where S = 31 is selected
+        static_assert(!behz_split_admits(30, 7, (u64(1) << 60) - 1, (u64(1) << 60) - 1) &&
+                          behz_split_admits(30, 7, (u64(1) << 59) - 1, (u64(1) << 60) - 1),
+                      "the edge of S = 30 at k = 7 lies between 59- and 60-bit ciphertext primes");
 
         // =====================================================================================================
         // 6. Small quotients estimated in single precision (devmath.hpp reduce_small_quot): for a word x below M p the

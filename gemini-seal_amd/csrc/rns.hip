@@ -185,7 +185,9 @@ namespace sealhip
         // phase would run on these two words) and stores the results. The transform that follows is launched with
         // kNttTopDone: its workgroups then read their own half only, and the layer's products are computed once per pair
         // instead of once per workgroup.
-        template <int KMAX, bool TOP = false>
+        // S (exact-K instances): the split position of the carry-free dot products (dotacc.hpp), selected per level by the
+        // host (RnsDev::dot_split); the row tables are packed with it
+        template <int KMAX, bool TOP = false, int S = 31>
         __global__ __launch_bounds__(kThreads) void bfv_lift2_kernel(const RnsDev *__restrict__ d_,
                                                                      const PrimeDev *__restrict__ primes_,
                                                                      const u64 *__restrict__ in, std::size_t in_stride,
@@ -226,19 +228,19 @@ namespace sealhip
             // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
             // a compile-time fact there, so the row loops carry no branch
             const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            Split31 ts[NC][KA];
+            Split<S> ts[NC][KA];
             if constexpr (KMAX < 0)
                 static_for<KA>([&](auto I) {
 #pragma unroll
                     for (int h = 0; h < NC; h++)
-                        ts[h][I.value] = Split31(t[h][I.value]);
+                        ts[h][I.value] = Split<S>(t[h][I.value]);
                 });
             const auto *L1m = kc(d->lift_L1m);
             const auto *L2m = kc(d->lift_L2m);
             const auto *Lrows = kc(d->lift_rows);
             const auto row_out = [&](int j) {
                 // constants carry the factor 2^64: REDC removes it. Exact K: the row {L2, L1[0..K-1], p, -p^-1}, split for
-                // DotAcc31, is one contiguous run of scalar loads
+                // the dot product, is one contiguous run of scalar loads
                 auto *row = KMAX < 0 ? Lrows + j * (KA + 3) : L1m + j * k;
                 if constexpr (KMAX < 0)
                     row = row_window(row);
@@ -254,8 +256,8 @@ namespace sealhip
                     u64 lo, hi;
                     if constexpr (KMAX < 0)
                     {
-                        DotAcc31<KA + 1> acc2; // carry-free accumulation (dotacc.hpp), same integer sum
-                        acc2.template add<0>(Split31(temp), row[0]);
+                        BehzDot<S, 0, KA> acc2; // carry-free accumulation (dotacc.hpp), same integer sum
+                        acc2.template add<0>(Split<S>(temp), row[0]);
                         static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[h][I.value], row[I.value + 1]); });
                         acc2.finish(lo, hi);
                     }
@@ -326,7 +328,7 @@ namespace sealhip
                 r = r >= two_p ? r - two_p : r;
             return r;
         }
-        template <int KMAX, bool DEFER>
+        template <int KMAX, bool DEFER, int S = 31>
         __global__ __launch_bounds__(kThreads) void bfv_floor_sk2_kernel(const RnsDev *__restrict__ d_,
                                                                          const PrimeDev *__restrict__ primes_,
                                                                          const u64 *__restrict__ in,
@@ -424,12 +426,12 @@ namespace sealhip
             // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
             // a compile-time fact there, so the row loops carry no branch
             const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            Split31 ts[KA], tbs[KA + 1];
+            Split<S> ts[KA], tbs[KA + 1];
             if constexpr (KMAX < 0)
-                static_for<KA>([&](auto I) { ts[I.value] = Split31(t[I.value]); });
+                static_for<KA>([&](auto I) { ts[I.value] = Split<S>(t[I.value]); });
             const auto *G1m = DEFER ? kc(d->floor_G1m_top[top_sel]) : kc(d->floor_G1m);
             const auto *G2m = kc(d->floor_G2m);
-            // Exact K: the row {G1, G2[0..K-1], p, -p^-1} of this launch's table, split for DotAcc31, in one run of scalar loads
+            // Exact K: the row {G1, G2[0..K-1], p, -p^-1} of this launch's table, split at S, in one run of scalar loads
             const auto *Frows = kc(d->floor_rows) + (DEFER ? top_sel : 4) * (d->nB * (KA + 3));
             const auto bsk_row = [&](int j) {
                 if (le_B(j))
@@ -443,8 +445,8 @@ namespace sealhip
                     u64 lo, hi;
                     if constexpr (KMAX < 0)
                     {
-                        DotAcc31<KA + 1> acc2;
-                        acc2.template add<0>(Split31(x), row[0]);
+                        BehzDot<S, 1, KA> acc2;
+                        acc2.template add<0>(Split<S>(x), row[0]);
                         static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[I.value], row[I.value + 1]); });
                         acc2.finish(lo, hi);
                     }
@@ -487,9 +489,9 @@ namespace sealhip
             {
                 static_for<KA + 1>([&](auto J) {
                     if (lt_B(J.value))
-                        tbs[J.value] = Split31(tb[J.value]);
+                        tbs[J.value] = Split<S>(tb[J.value]);
                 });
-                DotAcc31<KA + 1> acc2;
+                BehzDot<S, 2, KA> acc2;
                 static_for<KA + 1>([&](auto J) {
                     if (lt_B(J.value))
                         acc2.template add<J.value>(tbs[J.value], BtoMsk[J.value]);
@@ -508,11 +510,11 @@ namespace sealhip
             const u64 alpha = mulmod_shoup(conv_sk + (mp - fl_sk), d->inv_prod_B_mod_msk, d->inv_prod_B_mod_msk_s, mp);
             const bool neg = alpha > (mp >> 1); // rns.cpp:909
             const u64 a2 = neg ? mp - alpha : alpha;
-            const Split31 a2s(a2);
+            const Split<S> a2s(a2);
             const auto *pBm = kc(d->pBm);
             const auto *nBm = kc(d->nBm);
             const auto *BtoQ = kc(d->B_to_qm);
-            const auto *Qrows = kc(d->q_rows); // exact K: rows {pB, nB, B_to_q[i][0..B-1], p, -p^-1}, split for DotAcc31
+            const auto *Qrows = kc(d->q_rows); // exact K: rows {pB, nB, B_to_q[i][0..B-1], p, -p^-1}, split at S
             u64 nz = 0;                        // OR of the words this column stores (transparency sink)
             const auto q_row = [&](int i) {
                 const auto *qrow = Qrows + i * (B + 4);
@@ -521,7 +523,7 @@ namespace sealhip
                 u64 l2, h2;
                 if constexpr (KMAX < 0)
                 {
-                    DotAcc31<KA + 2> acc2;
+                    BehzDot<S, 3, KA> acc2;
                     acc2.template add<0>(a2s, c);
                     static_for<KA + 1>([&](auto J) {
                         if (lt_B(J.value))
@@ -872,7 +874,7 @@ namespace sealhip
 
     namespace
     {
-        template <int KM>
+        template <int KM, int S = 31>
         void lift2_launch(const Engine &e, const RnsDev *d, const u64 *in, std::size_t in_stride, u64 *out, std::size_t out_stride,
                           std::size_t count, unsigned grid, bool top_layer)
         {
@@ -880,12 +882,23 @@ namespace sealhip
             {
                 if (top_layer)
                 {
-                    bfv_lift2_kernel<KM, true><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride,
-                                                                                       count, e.logn);
+                    bfv_lift2_kernel<KM, true, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
+                                                                                          out_stride, count, e.logn);
                     return;
                 }
             }
-            bfv_lift2_kernel<KM><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+            bfv_lift2_kernel<KM, false, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride,
+                                                                                   count, e.logn);
+        }
+        // the exact-k instance of the split the level's tables are packed with (RnsDev::dot_split)
+        template <int KM>
+        void lift2_launch_split(int split, const Engine &e, const RnsDev *d, const u64 *in, std::size_t in_stride, u64 *out,
+                                std::size_t out_stride, std::size_t count, unsigned grid, bool top_layer)
+        {
+            if (split == 30)
+                lift2_launch<KM, 30>(e, d, in, in_stride, out, out_stride, count, grid, top_layer);
+            else
+                lift2_launch<KM, 31>(e, d, in, in_stride, out, out_stride, count, grid, top_layer);
         }
     } // namespace
 
@@ -905,7 +918,7 @@ namespace sealhip
             return h.k > 32;
         if (code == kBehzGeneric)
             return h.k <= 32;
-        return code == h.k && h.redc_small && h.k <= bounds::kBehzExactMaxK;
+        return code == h.k && h.redc_small && h.k <= bounds::kBehzExactMaxK && (h.dot_split == 30 || h.dot_split == 31);
     }
 
     hipError_t launch_bfv_lift(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in, std::size_t in_stride,
@@ -920,7 +933,8 @@ namespace sealhip
         ProfScope prof(e, "bfv_lift", 0);
         if (plan.lift_kernel != kBehzStepwise)
         {
-#define SEALHIP_LIFT2(KM) lift2_launch<KM>(e, d, in, in_stride, out, out_stride, count, grid, top_layer)
+#define SEALHIP_LIFT2(KM) lift2_launch_split<KM>(h.dot_split, e, d, in, in_stride, out, out_stride, count, grid, top_layer)
+#define SEALHIP_LIFT2G(KM) lift2_launch<KM>(e, d, in, in_stride, out, out_stride, count, grid, top_layer)
             switch (plan.lift_kernel)
             {
             case 1: SEALHIP_LIFT2(-1); break;
@@ -938,9 +952,10 @@ namespace sealhip
             case 13: SEALHIP_LIFT2(-13); break;
             case 14: SEALHIP_LIFT2(-14); break;
             case 15: SEALHIP_LIFT2(-15); break;
-            default: SEALHIP_LIFT2(32); break;
+            default: SEALHIP_LIFT2G(32); break;
             }
 #undef SEALHIP_LIFT2
+#undef SEALHIP_LIFT2G
             return hipGetLastError();
         }
         SEALHIP_DISPATCH_K(h.k, bfv_lift_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
@@ -986,16 +1001,25 @@ namespace sealhip
         ProfScope prof(e, "bfv_floor_sk", 0);
         if (plan.floor_kernel != kBehzStepwise)
         {
-#define SEALHIP_FLOOR2(KM)                                                                                          \
+#define SEALHIP_FLOOR2S(KM, S)                                                                                      \
     do                                                                                                               \
     {                                                                                                                \
         if (deferred_top)                                                                                            \
-            bfv_floor_sk2_kernel<KM, true><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,       \
-                                                                           out_stride, count, e.logn,               \
-                                                                           deferred_top == 2 ? 1 : 0, tflags);      \
+            bfv_floor_sk2_kernel<KM, true, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,    \
+                                                                              out_stride, count, e.logn,            \
+                                                                              deferred_top == 2 ? 1 : 0, tflags);   \
         else                                                                                                         \
-            bfv_floor_sk2_kernel<KM, false><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,      \
-                                                                            out_stride, count, e.logn, 0, tflags);  \
+            bfv_floor_sk2_kernel<KM, false, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,   \
+                                                                               out_stride, count, e.logn, 0, tflags); \
+    } while (0)
+// the exact-k instance of the split the level's tables are packed with (RnsDev::dot_split)
+#define SEALHIP_FLOOR2(KM)                                                                                          \
+    do                                                                                                               \
+    {                                                                                                                \
+        if (h.dot_split == 30)                                                                                       \
+            SEALHIP_FLOOR2S(KM, 30);                                                                                 \
+        else                                                                                                         \
+            SEALHIP_FLOOR2S(KM, 31);                                                                                 \
     } while (0)
             switch (plan.floor_kernel)
             {
@@ -1014,9 +1038,10 @@ namespace sealhip
             case 13: SEALHIP_FLOOR2(-13); break;
             case 14: SEALHIP_FLOOR2(-14); break;
             case 15: SEALHIP_FLOOR2(-15); break;
-            default: SEALHIP_FLOOR2(32); break;
+            default: SEALHIP_FLOOR2S(32, 31); break;
             }
 #undef SEALHIP_FLOOR2
+#undef SEALHIP_FLOOR2S
             return hipGetLastError();
         }
         if (deferred_top)

@@ -109,6 +109,7 @@ SYMBOLS = {
     "sealhip_debug_ntt_table": [_vp, _u32, _u32, _vp, _sz],
     "sealhip_debug_rns_constants": [_vp, _u32, _u32, _vp, _sz, C.POINTER(_sz)],
     "sealhip_debug_bfv_multiply_plan": [_vp, _u32, _u32, _u32, _i32, _vp],
+    "sealhip_debug_behz_dot_split": [_vp, _u32, C.POINTER(C.c_int32)],
     "sealhip_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_ntt_negacyclic_harvey": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_inverse_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
@@ -600,6 +601,12 @@ class Context:
         out = np.zeros(len(self.BFV_PLAN_FIELDS), dtype=np.int32)
         _check(lib().sealhip_debug_bfv_multiply_plan(self.handle, k, size_a, size_b, 1 if square else 0, out.ctypes.data))
         return dict(zip(self.BFV_PLAN_FIELDS, (int(x) for x in out)))
+
+    def debug_behz_dot_split(self, k):
+        """30 or 31: the split position of the exact-k BEHZ kernels' dot products at level k (sealhip_debug_behz_dot_split)"""
+        v = C.c_int32()
+        _check(lib().sealhip_debug_behz_dot_split(self.handle, k, C.byref(v)))
+        return v.value
 
     def galois_elt_from_step(self, step):
         v = C.c_uint32()

@@ -184,6 +184,9 @@ long sealhip_debug_rns_constants(sealhip_context *ctx, uint32_t k, uint32_t whic
    kernel, 64 the step-by-step kernels. */
 long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t size_a, uint32_t size_b, int32_t square,
                                      int32_t *out);
+/* The split position (30 or 31) of the carry-free dot products of the exact-k BEHZ kernels at level k of a BFV context:
+   what the level's constant tables are packed with (host-only contexts: would be packed with). 31 at k above 15. */
+long sealhip_debug_behz_dot_split(sealhip_context *ctx, uint32_t k, int32_t *out);
 
 /* ---------------------------------------------------------------- L2: NTT (util/ntt.h:189-368)
    data: count polynomials x rows x N, in place. `base` selects the primes of the `rows` rows of one
