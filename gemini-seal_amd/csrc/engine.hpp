@@ -18,6 +18,7 @@
 
 #include "devmath.hpp"
 #include "ntt_bounds.hpp"
+#include "ntt_select.hpp"
 #include "hostmath.hpp"
 #include "pool_scratch.hpp"
 #include "held_workspace.hpp"
@@ -47,15 +48,16 @@ namespace sealhip
         const u64 *base[2];
         std::size_t poly_stride[2];
         unsigned short code[kMaxRows];
-        // launch-wide treatment of the loaded words (single-prime mod-up, multi_special_primes.cpp:99-108): 0 none,
-        // 1 barrett_reduce_63 w.r.t. the row's prime, 2 one conditional subtraction (every source prime is below twice
-        // every destination prime, so the canonical residue is x or x - p). Both are no-ops on rows whose source prime
-        // does not exceed their own. 4: the CKKS mod-down with one special prime (multi_special_primes.cpp:262-273): the
+        // launch-wide treatment of the loaded words (ntt_select.hpp; single-prime mod-up, multi_special_primes.cpp:99-108):
+        // kTreatNone, kTreatBarrett: barrett_reduce_63 w.r.t. the row's prime, kTreatCondSub: one conditional subtraction
+        // (every source prime is below twice every destination prime, so the canonical residue is x or x - p). Both are
+        // no-ops on rows whose source prime does not exceed their own. kTreatNegSpecial: the CKKS mod-down with one special
+        // prime (multi_special_primes.cpp:262-273): the
         // word becomes -(x mod aux_p) as the integer aux_p - (x mod aux_p) (0 stays 0), aux_p = the special prime.
-        // 5: the same, on a source row whose inverse transform left its top layer to the consumer (kNttDeferTop): the
+        // kTreatNegSpecialTop: the same, on a source row whose inverse transform left its top layer to the consumer (kNttDeferTop): the
         // transform reads the pairs (c, c + N/2) anyway and applies BackwardLazyLast (ntt.cpp:274-281) to them first;
         // aux_top = the special prime's {n^-1, its Shoup quotient, w n^-1, its Shoup quotient}.
-        // 7: mode 5 plus the rest of the CKKS mod-down as the transform's store phase (multi_special_primes.cpp:291-302 and the
+        // kTreatModDownStore: that plus the rest of the CKKS mod-down as the transform's store phase (multi_special_primes.cpp:291-302 and the
         // final add, evaluator.cpp:2363-2366): the transformed word t of row (polynomial pl, prime q) is not stored; instead
         // v = (prod[pl][q] + t) * P^-1 mod q goes into the ciphertext -- added to what is there, or, with c0_src set,
         // written as (c0_src + v, v) for components (0, 1). Floating-point instance at log n >= 15 only (ntt_can_fuse_moddown).
@@ -78,28 +80,13 @@ namespace sealhip
 
     // Environment variables the library reads: the resource knobs SEALHIP_WORKSPACE_MB / SEALHIP_HOST_CHUNK /
     // SEALHIP_HOST_THREADS and the switches that run the REFERENCE'S OWN operation sequences instead of the proved shortcuts:
-    // SEALHIP_NTT_EXACT_FWD, SEALHIP_NTT_EXACT_INV, SEALHIP_NTT_CANON_EXACT, SEALHIP_NTT_NO_FP64. Nothing else: no variable
+    // SEALHIP_NTT_EXACT_FWD, SEALHIP_NTT_EXACT_INV, SEALHIP_NTT_CANON_EXACT, SEALHIP_NTT_NO_FP64 -- all four read once, by
+    // ntt_switches() (ntt.hip), into an NttSwitches (ntt_select.hpp). Nothing else: no variable
     // can re-open a race or switch a proved path off. (The A/B knobs of earlier rounds are gone with their
     // measurement-only build; what they measured is recorded in DESIGN.md and profiles/.)
 
-    constexpr int kNttCanonical = 1; // fuse the canonicalising wrapper (ntt.h:236-245 / :328-333)
-    constexpr int kNttStrict = 2;    // Harvey-corrected forward butterflies
-    constexpr int kNttAnyRep = 8;    // inverse: the consumer canonicalises, any representative below 2p may be stored
-    constexpr int kNttReduceOut = 0x10; // forward, single-pass kernel: one more conditional subtraction, outputs in [0, 2p)
-    constexpr int kNttApprox = 0x20;   // forward, with kNttAnyRep or a consumer that takes outputs below (2 + g) p: approximate quotient (ntt_bounds.hpp section 2)
-    constexpr int kNttPolyMajor = 0x4000;        // forward half kernel: live positions grouped item by item (ntt_half.hpp half_block_map; group size in bits 16-23)
-    constexpr int kNttSmallQuot = 0x1000000;     // (launcher-internal) canonical approximate-quotient launch: single-precision quotient estimate in the store
-    constexpr int kNttDebugNoSignal = 0x40; // forward half kernel: never send the hand-off signal (tests of the time-out path)
-    // forward, single-pass kernel, with kNttReduceOut, in place: the producer of the rows has already applied the top layer
-    // (gap N/2) -- bfv_lift2 does for the Bsk rows it writes. Each workgroup then loads its own half only: no second read of
-    // the row, no duplicated products (both workgroups of a row compute the top layer's products otherwise), no hand-off.
-    constexpr int kNttTopDone = 0x80;
-    constexpr int kNttDeferTop = 4;  // inverse, single-pass kernels only: leave the top layer (gap N/2) to the consumer
-    // Primes below this bound have double-precision twiddle tables: the single-pass kernels then run their butterflies
-    // on the FP64 pipe (exact, devmath.hpp) whenever the launch promises nothing about representatives that only the
-    // integer sequence would deliver (canonical outputs, or kNttAnyRep). SEALHIP_NTT_NO_FP64=1 switches it off.
-    // (the bound is what the schedules' worst-case recurrences in ntt_bounds.hpp admit: 50 bits)
-    constexpr u64 kFpPrimeBound = u64(1) << bounds::kFpPrimeBits;
+    // The NTT launch flags (kNttCanonical .. kNttDeferTop), kFpPrimeBound and the names of the single-pass kernels' instance
+    // codes: ntt_select.hpp.
 
     struct NttRound
     {

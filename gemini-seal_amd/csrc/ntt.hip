@@ -293,15 +293,20 @@ namespace sealhip
         }
     } // namespace
 
+    const NttSwitches &ntt_switches()
+    {
+        static const NttSwitches sw = { std::getenv("SEALHIP_NTT_NO_FP64") != nullptr, std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr,
+                                        std::getenv("SEALHIP_NTT_EXACT_INV") != nullptr,
+                                        std::getenv("SEALHIP_NTT_CANON_EXACT") != nullptr };
+        return sw;
+    }
     bool fp64_enabled()
     {
-        static const bool off = std::getenv("SEALHIP_NTT_NO_FP64") != nullptr;
-        return !off;
+        return !ntt_switches().no_fp64;
     }
     bool exact_fwd()
     {
-        static const bool on = std::getenv("SEALHIP_NTT_EXACT_FWD") != nullptr;
-        return on;
+        return ntt_switches().exact_fwd;
     }
 
     NttPlan plan_ntt(int logn, bool inverse, int flags)
@@ -553,7 +558,7 @@ namespace sealhip
     }
 
     // STRICT mode: may a producer apply the forward transform's top layer to rows on these primes (kNttTopDone)? Only the
-    // dense lazy schedule has an instance that starts below it (launch_half)
+    // dense lazy schedule has an instance that starts below it (ntt_select.hpp select_fwd_half)
     bool ntt_strict_top_done_ok(const Engine &e, const RowMap &map)
     {
         if (!e.use_half_kernel || e.logn < 14 || e.logn > 16 || exact_fwd())

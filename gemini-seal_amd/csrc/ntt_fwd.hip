@@ -1,6 +1,6 @@
 // ntt_fwd.hip -- single-pass forward NTT for N = 2^14 .. 2^16 (the half-row kernel, ntt_half.hpp) and its launcher.
 #include <cstring>
-#include <cstdlib>
+#include <utility>
 
 #include "ntt_half.hpp"
 
@@ -8,11 +8,11 @@ namespace sealhip
 {
     namespace
     {
-        // STRICT == 2 (approximate Shoup quotient): which form (ntt_bounds.hpp section 2: bounds::kFwdApxLevel) -- 1: round 2's
+        // STRICT == kSchedApprox (approximate Shoup quotient): which form (ntt_bounds.hpp section 2: bounds::kFwdApxLevel) -- 1: round 2's
         // (hi32(y0*s0) dropped, product below 3p); 2: round 4's carry-free quotient (devmath.hpp mulhi_apx2, below 4p).
         // The butterfly's second output is u - v + (that bound), so the bound is what the layers add.
         template <int STRICT>
-        constexpr int kApx = STRICT == 2 ? bounds::kFwdApxLevel : 0;
+        constexpr int kApx = STRICT == kSchedApprox ? bounds::kFwdApxLevel : 0;
         // The final round at N = 2^15 runs at the register cap (two stages of prefetched twiddles, 48 registers): four more for
         // zero-high pairs spill two coefficients. Its 32 butterflies (of 272) keep the level-1 quotient there -- a product
         // below 3p under a schedule that allows 4p, so the bounds of level 2 cover it (ntt_bounds.hpp section 2).
@@ -22,7 +22,7 @@ namespace sealhip
         template <int STRICT>
         __device__ __forceinline__ u64 fwd_addend(u64 two_p, u64 neg_p)
         {
-            if constexpr (STRICT != 2)
+            if constexpr (STRICT != kSchedApprox)
                 return two_p;
             u64 a = two_p << 1; // 4p (level 2), opaque: left visible the compiler rewrites (u << 1) + (2p << 1) as (u + 2p) << 1,
             asm("" : "+s"(a));  // two 64-bit instructions where v_lshl_add_u64 does it in one
@@ -52,11 +52,11 @@ namespace sealhip
         // l5 of lane (h, r), so instruction h writes the 128 consecutive coefficients of half-wave h: one dword move per
         // dword, no LDS, no barrier. For f = 3 a v_permlane16_swap step (rows of 16 lanes) transposes the second bit.
         // Every f >= 2 instance takes the swap but mode 7, which keeps the trip: its store phase reads the product rows at
-        // the same addresses (mode 7 has a floating-point instance only, launch_half).
+        // the same addresses (mode 7 has a floating-point instance only, ntt_select.hpp kFwdInstances).
         template <int T, int REDUCE>
-        constexpr bool kStoreSwap = (T - 12) >= 2 && REDUCE != 7;
+        constexpr bool kStoreSwap = (T - 12) >= 2 && REDUCE != kTreatModDownStore;
         template <int T, int REDUCE>
-        constexpr bool kStoreExchange = (T - 12) >= 2 && REDUCE == 7;
+        constexpr bool kStoreExchange = fwd_store_exchange(T, REDUCE); // (ntt_select.hpp: the instance table states where it exists)
 
         __device__ __forceinline__ void swap_half_waves(u64 &a, u64 &b) // lanes 32-63 of a <-> lanes 0-31 of b
         {
@@ -130,14 +130,14 @@ namespace sealhip
                     if (e & bit)
                         continue;
                     const int s = (G << f) | e;
-                    if constexpr (STRICT == 3)
+                    if constexpr (STRICT == kSchedFp64)
                     {
                         fp_butterfly_fwd(x[s], x[s | bit], ((twd_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)], fp_of(two_p),
                                          fp_of(neg_p));
                         continue;
                     }
                     const u64x2 Wv = ((tw_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
-                    if (STRICT == 1)
+                    if (STRICT == kSchedHarvey)
                         x[s] = x[s] >= two_p ? x[s] - two_p : x[s];
                     else if (gb == 0 && !(fin & 2)) // fin & 2: the consumer takes any representative and nothing can wrap
                         x[s] = barrett_lazy_hs(x[s], rdp, neg_p);
@@ -154,7 +154,7 @@ namespace sealhip
                 ulonglong2 v;
                 v.x = x[s];
                 v.y = x[s + 1];
-                if constexpr (STRICT == 3)
+                if constexpr (STRICT == kSchedFp64)
                 {
                     // canonical residues always: they serve kNttCanonical and every any-representative consumer alike
                     v.x = fp_to_u64(fp_canonical(fp_of(v.x), fp_of(two_p), fp_of(neg_p)));
@@ -162,7 +162,7 @@ namespace sealhip
                 }
                 else if (fin & 1)
                 {
-                    if constexpr (STRICT == 2)
+                    if constexpr (STRICT == kSchedApprox)
                     {
                         // canonical output of the approximate-quotient schedule (values below (2 + g log n) p <= 66p,
                         // ntt_bounds.hpp section 2): one step to [0, 2p), one conditional subtraction. fin & 4: the step is
@@ -187,7 +187,7 @@ namespace sealhip
                     v.x = v.x >= p ? v.x - p : v.x;
                     v.y = v.y >= p ? v.y - p : v.y;
                 }
-                else if constexpr (ROUT && STRICT == 4)
+                else if constexpr (ROUT && STRICT == kSchedDense)
                 {
                     // dense lazy schedule: words below 16p -> [0, 2p) (rdp carries the bits of the quotient constant)
                     const float cq = __uint_as_float(static_cast<unsigned>(rdp));
@@ -272,12 +272,12 @@ namespace sealhip
                         continue;
                     const int s = (G << f) | e;
                     const u64x2 Wv = tg[(1 << (f - 1 - W)) - 1 + (e >> (W + 1))];
-                    if constexpr (STRICT == 3)
+                    if constexpr (STRICT == kSchedFp64)
                     {
                         fp_butterfly_fwd(x[s], x[s | bit], Wv.x, fp_of(two_p), fp_of(neg_p));
                         continue;
                     }
-                    if (STRICT == 1)
+                    if (STRICT == kSchedHarvey)
                         x[s] = x[s] >= two_p ? x[s] - two_p : x[s];
                     else if (gb == 0 && !(fin & 2)) // fin & 2: the consumer takes any representative and nothing can wrap
                         x[s] = barrett_lazy_hs(x[s], rdp, neg_p);
@@ -294,7 +294,7 @@ namespace sealhip
                 ulonglong2 v;
                 v.x = x[s];
                 v.y = x[s + 1];
-                if constexpr (STRICT == 3)
+                if constexpr (STRICT == kSchedFp64)
                 {
                     // canonical residues always: they serve kNttCanonical and every any-representative consumer alike
                     v.x = fp_to_u64(fp_canonical(fp_of(v.x), fp_of(two_p), fp_of(neg_p)));
@@ -302,7 +302,7 @@ namespace sealhip
                 }
                 else if (fin & 1)
                 {
-                    if constexpr (STRICT == 2)
+                    if constexpr (STRICT == kSchedApprox)
                     {
                         // canonical output of the approximate-quotient schedule (values below (2 + g log n) p <= 66p,
                         // ntt_bounds.hpp section 2): one step to [0, 2p), one conditional subtraction. fin & 4: the step is
@@ -327,7 +327,7 @@ namespace sealhip
                     v.x = v.x >= p ? v.x - p : v.x;
                     v.y = v.y >= p ? v.y - p : v.y;
                 }
-                else if constexpr (ROUT && STRICT == 4)
+                else if constexpr (ROUT && STRICT == kSchedDense)
                 {
                     // dense lazy schedule: words below 16p -> [0, 2p) (rdp carries the bits of the quotient constant)
                     const float cq = __uint_as_float(static_cast<unsigned>(rdp));
@@ -385,7 +385,7 @@ namespace sealhip
             {
                 u64x2 next[FinalStage<T>::SG * FinalStage<T>::NTW];
                 if constexpr (ST + 1 < FinalStage<T>::NS)
-                    StageTw<T, ST + 1, 0, STRICT == 3>::load(next, tw, jb, N);
+                    StageTw<T, ST + 1, 0, STRICT == kSchedFp64>::load(next, tw, jb, N);
                 __builtin_amdgcn_sched_barrier(0);
                 StageRun<T, STRICT, ROUT, SX, ST>::run(x, cur, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
                 __builtin_amdgcn_sched_barrier(0);
@@ -416,7 +416,7 @@ namespace sealhip
                 for (int j = 0; j < kIL; j++)
                 {
                     u64x2 Wv;
-                    if constexpr (STRICT == 3)
+                    if constexpr (STRICT == kSchedFp64)
                     {
                         Wv.x = UNIFORM ? ((twd_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)]
                                        : ((twd_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
@@ -433,7 +433,7 @@ namespace sealhip
             __device__ static __forceinline__ void run(u64 (&x)[32], const u64 (&w)[kIL], const u64 (&ws)[kIL], u64 two_p,
                                                        u64 neg_p, ZeroPairs &zp)
             {
-                if constexpr (STRICT == 3)
+                if constexpr (STRICT == kSchedFp64)
                 {
 #pragma unroll
                     for (int j = 0; j < kIL; j++)
@@ -446,7 +446,7 @@ namespace sealhip
                 {
                     u[j] = x[slot(j)];
                     y[j] = x[slot(j) | bit];
-                    if (STRICT == 1)
+                    if (STRICT == kSchedHarvey)
                         u[j] = u[j] >= two_p ? u[j] - two_p : u[j];
                 }
                 if constexpr (kApx<STRICT> == 2)
@@ -476,10 +476,10 @@ namespace sealhip
                     RoundStage<T, R, STRICT, UNIFORM, K + 1>::load(wn, wsn, tw, jb, N);
                 __builtin_amdgcn_sched_barrier(0);
                 // (before on-chip layers 5 and 10 -- after round 2's first and round 3's second layer: see fp_reduce_all)
-                if constexpr (STRICT == 3 && K % (16 / kIL) == 0 && bounds::fp_fwd_reduce_before_layer(4 * (R - 1) + K / (16 / kIL)))
+                if constexpr (STRICT == kSchedFp64 && K % (16 / kIL) == 0 && bounds::fp_fwd_reduce_before_layer(4 * (R - 1) + K / (16 / kIL)))
                     fp_reduce_all(x, two_p, neg_p);
-                // dense lazy schedule (STRICT == 4, ntt_bounds.hpp section 2b): every word back below 2p before rounds 2 and 3
-                if constexpr (STRICT == 4 && K == 0 && bounds::fwd_dense_reduce_before_round(R))
+                // dense lazy schedule (STRICT == kSchedDense, ntt_bounds.hpp section 2b): every word back below 2p before rounds 2 and 3
+                if constexpr (STRICT == kSchedDense && K == 0 && bounds::fwd_dense_reduce_before_round(R))
                 {
                     const float cq = small_quot_const(0 - neg_p);
 #pragma unroll
@@ -503,7 +503,7 @@ namespace sealhip
             if constexpr (kApx<STRICT> == 2)
                 zp.init();
             u64x2 W1;
-            if constexpr (STRICT == 3)
+            if constexpr (STRICT == kSchedFp64)
                 W1.x = ((twd_const_t)tw)[1];
             else
                 W1 = ((tw_const_t)tw)[1];
@@ -519,7 +519,7 @@ namespace sealhip
                     lo[i] = *reinterpret_cast<const ulonglong2 *>(rowp + idx);
                     hi[i] = *reinterpret_cast<const ulonglong2 *>(rowp + (1 << T) + idx);
                 }
-                if constexpr (REDUCE == 5 || REDUCE == 7)
+                if constexpr (REDUCE == kTreatNegSpecialTop || REDUCE == kTreatModDownStore)
                 {
                     // mode 4 on a source row whose top inverse layer was left to us: the pair (lo, hi) = (c, c + N/2) first
                     // goes through BackwardLazyLast w.r.t. the special prime P (inputs below 2P), then -(. mod P)
@@ -527,7 +527,7 @@ namespace sealhip
                     for (int i = 0; i < kLoadBatch; i++)
                     {
                         const auto top = [&](u64 &u, u64 &v) {
-                            if constexpr (STRICT == 3)
+                            if constexpr (STRICT == kSchedFp64)
                             {
                                 // aux_p / aux_cr1: P and 1/P as doubles; aux_top[0], [2]: n^-1 and w n^-1 as doubles
                                 const double P = fp_of(aux_p), Pinv = fp_of(aux_cr1), ud = fp_from_u64(u), vd = fp_from_u64(v);
@@ -553,7 +553,7 @@ namespace sealhip
                         top(lo[i].y, hi[i].y);
                     }
                 }
-                if constexpr (REDUCE == 4)
+                if constexpr (REDUCE == kTreatNegSpecial)
                 {
                     // CKKS mod-down with one special prime P (multi_special_primes.cpp:262-273): the word is a lazy value of
                     // the special row; the row being transformed holds (-(s mod P)) mod q. -(s mod P) is formed here as the
@@ -563,7 +563,7 @@ namespace sealhip
                     for (int i = 0; i < kLoadBatch; i++)
                     {
                         const auto red = [&](u64 v) {
-                            if constexpr (STRICT == 3)
+                            if constexpr (STRICT == kSchedFp64)
                             {
                                 // floating-point instance: aux_p / aux_cr1 carry P and 1/P as doubles, v < 2^52; the word
                                 // stays a double (the top layer below does not convert it again)
@@ -579,11 +579,11 @@ namespace sealhip
                         hi[i].y = red(hi[i].y);
                     }
                 }
-                if constexpr (REDUCE == 1 || REDUCE == 2) // gathered single-prime mod-up (multi_special_primes.cpp:103-107)
+                if constexpr (REDUCE == kTreatBarrett || REDUCE == kTreatCondSub) // gathered single-prime mod-up (multi_special_primes.cpp:103-107)
                 {
-                    const u64 p = STRICT == 3 ? static_cast<u64>(fp_of(two_p)) : 0 - neg_p;
+                    const u64 p = STRICT == kSchedFp64 ? static_cast<u64>(fp_of(two_p)) : 0 - neg_p;
                     const auto red = [&](u64 v) {
-                        if constexpr (REDUCE == 2)
+                        if constexpr (REDUCE == kTreatCondSub)
                             return v >= p ? v - p : v; // source prime < 2p: the canonical residue is v or v - p
                         else
                             return barrett_reduce_63(v, p, cr1);
@@ -605,13 +605,13 @@ namespace sealhip
                     const int s = (batch * kLoadBatch + i) * 2;
                     u64 u[4] = {lo[i].x, lo[i].y, lo[i + 1].x, lo[i + 1].y};
                     u64 y[4] = {hi[i].x, hi[i].y, hi[i + 1].x, hi[i + 1].y};
-                    if constexpr (STRICT == 3)
+                    if constexpr (STRICT == kSchedFp64)
                     {
-                        // inputs below 2^52 (launch_half: residues, lazy gathered values, or the treatments above)
+                        // inputs below 2^52 (select_fwd_half: residues, lazy gathered values, or the treatments above)
 #pragma unroll
                         for (int j = 0; j < 4; j++)
                         {
-                            if constexpr (REDUCE != 4 && REDUCE != 5 && REDUCE != 7)
+                            if constexpr (REDUCE != kTreatNegSpecial && REDUCE != kTreatNegSpecialTop && REDUCE != kTreatModDownStore)
                             {
                                 u[j] = fp_bits(fp_from_u64(u[j]));
                                 y[j] = fp_bits(fp_from_u64(y[j]));
@@ -622,7 +622,7 @@ namespace sealhip
                         continue;
                     }
                     const u64 w[4] = {W1.x, W1.x, W1.x, W1.x}, ws[4] = {W1.y, W1.y, W1.y, W1.y};
-                    if (STRICT == 1)
+                    if (STRICT == kSchedHarvey)
                     {
 #pragma unroll
                         for (int j = 0; j < 4; j++)
@@ -712,7 +712,7 @@ namespace sealhip
             const std::size_t row = poly * map.rows + live.slot[position];
             const unsigned short pid = map.prime[row % map.rows];
             const PrimeDev P = primes[pid];
-            constexpr bool FP = STRICT == 3; // butterflies on the FP64 pipe (primes below 2^50, see fp_reduce_all)
+            constexpr bool FP = STRICT == kSchedFp64; // butterflies on the FP64 pipe (primes below 2^50, see fp_reduce_all)
             const u64 p = P.p, two_p = FP ? fp_bits(P.p_d) : P.two_p, rdp = P.rdp;
             const u64 *tw = FP ? reinterpret_cast<const u64 *>(P.fwd_d) : P.fwd;
             u64 *rowp = data + (row << LOGN);
@@ -731,7 +731,7 @@ namespace sealhip
                            (static_cast<std::size_t>(code & 0x3FFF) << LOGN);
                 }
             }
-            if constexpr (REDUCE == 6)
+            if constexpr (REDUCE == kTreatReduceOutTopDone)
             {
                 // kNttTopDone: the producer applied the top layer; this workgroup's half, arrangement 1, nothing else
                 const int jb1 = Arr<T, 1>::tid_index(fresh_tid(wave_base));
@@ -786,7 +786,7 @@ namespace sealhip
             u64x2 tg0[FinalStage<T>::SG * FinalStage<T>::NTW];
             if constexpr (FinalStage<T>::PIPE)
             {
-                StageTw<T, 0, 0, STRICT == 3>::load(tg0, tw, jb4, N); // lands while the last exchange runs
+                StageTw<T, 0, 0, STRICT == kSchedFp64>::load(tg0, tw, jb4, N); // lands while the last exchange runs
                 __builtin_amdgcn_sched_barrier(0);
             }
             h_exchange<T, 3, 4>(x, lds, fresh_tid(wave_base));
@@ -819,13 +819,13 @@ namespace sealhip
                 wait_for_sibling(); // the final round stores as it goes
             // ---- final round + store, group by group (arrangement 4: runs of 2^f consecutive coefficients per lane)
             // bit 0: canonicalising wrapper; bit 1: leave the last layer's first operand unreduced (kNttAnyRep)
-            // bit 2 (approximate-quotient canonical launches on primes of at least 45 bits, launch_half): the canonicalising
+            // bit 2 (approximate-quotient canonical launches on primes of at least 45 bits, select_fwd_half): the canonicalising
             // step estimates its small quotient in single precision (devmath.hpp reduce_small_quot)
-            // (STRICT == 4, the dense lazy schedule: the last layer leaves its first operand as it is, the store reduces)
-            const int fin = ((flags & kNttCanonical) ? 1 : 0) | (((flags & kNttAnyRep) || STRICT == 4) ? 2 : 0) | ((flags & kNttSmallQuot) ? 4 : 0);
+            // (STRICT == kSchedDense, the dense lazy schedule: the last layer leaves its first operand as it is, the store reduces)
+            const int fin = ((flags & kNttCanonical) ? 1 : 0) | (((flags & kNttAnyRep) || STRICT == kSchedDense) ? 2 : 0) | ((flags & kNttSmallQuot) ? 4 : 0);
             const u64 rdp_fin =
-                ((STRICT == 2 && (flags & kNttSmallQuot)) || STRICT == 4) ? static_cast<u64>(__float_as_uint(small_quot_const(p))) : rdp;
-            constexpr bool ROUT = REDUCE == 3 || REDUCE == 6; // kNttReduceOut launches (never gathered: no load treatment to combine with)
+                ((STRICT == kSchedApprox && (flags & kNttSmallQuot)) || STRICT == kSchedDense) ? static_cast<u64>(__float_as_uint(small_quot_const(p))) : rdp;
+            constexpr bool ROUT = REDUCE == kTreatReduceOut || REDUCE == kTreatReduceOutTopDone; // kNttReduceOut launches (never gathered: no load treatment to combine with)
             if constexpr (kFinalApx<T, STRICT> == 2)
                 zp.init();
             if constexpr (FinalStage<T>::PIPE)
@@ -836,7 +836,7 @@ namespace sealhip
             {
                 h_exchange<T, 4, 1>(x, lds, fresh_tid(wave_base));
                 wait_for_sibling();
-                if constexpr (REDUCE == 7)
+                if constexpr (REDUCE == kTreatModDownStore)
                 {
                     // row = (polynomial pl of the launch, prime slot q): products at prod[pl][q], ciphertext component pl & 1
                     const std::size_t pl = row / map.rows, q = row % map.rows;
@@ -854,6 +854,32 @@ namespace sealhip
             }
         }
 
+        // The instances of a ring of 2^LOGN, in the order of kFwdInstances (ntt_select.hpp; null where the table says the
+        // instance does not exist at this ring size): launch_half launches from this table and init_half registers from it.
+        using FwdKernel = void (*)(u64 *, const PrimeDev *, RowMap, std::size_t, int, unsigned *, unsigned *, unsigned, NttSource,
+                                   std::size_t, LiveSlots);
+        template <int LOGN, int I>
+        FwdKernel fwd_kernel()
+        {
+            if constexpr (fwd_instance_at(LOGN, kFwdInstances[I]))
+                return &ntt_fwd_half_kernel<LOGN, kFwdInstances[I].sched, kFwdInstances[I].treatment>;
+            else
+                return nullptr;
+        }
+        template <int LOGN, int... I>
+        const FwdKernel *fwd_kernels(std::integer_sequence<int, I...>)
+        {
+            static const FwdKernel table[] = { fwd_kernel<LOGN, I>()... };
+            return table;
+        }
+        template <int LOGN>
+        const FwdKernel *fwd_kernels()
+        {
+            return fwd_kernels<LOGN>(std::make_integer_sequence<int, kFwdInstanceCount>{});
+        }
+
+        // Which instance runs, and with which flags, is select_fwd_half's decision (ntt_select.hpp; the instances and who
+        // launches them: DESIGN.md section 6). Here: the facts it decides on, the hand-off tickets, the launch.
         template <int LOGN>
         hipError_t launch_half(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags,
                                const NttSource &src)
@@ -878,241 +904,67 @@ namespace sealhip
             const std::size_t blocks = chunk * 16;
             if (blocks > 0x7fffffffull)
                 return hipErrorInvalidValue;
-            // STRICT mode means "no wrap-around": Harvey's corrected butterflies (one conditional subtraction each)
-            // guarantee it for any prime. Where the consumer takes any representative (kNttAnyRep, kNttApprox) or the
-            // canonical residue is what is returned (kNttCanonical), and every live prime leaves the head-room that the cheaper
-            // schedules are proved on (ntt_bounds.hpp section 2: nothing can wrap there either), the residues are the same and
-            // the flag is dropped for the launch (round 4). The `_lazy` entries and the 60-bit rows keep the corrected sequence.
-            if ((flags & kNttStrict) != 0 && (flags & (kNttAnyRep | kNttCanonical | kNttApprox)) != 0 && (flags & kNttReduceOut) == 0)
+            u64 live_p[kMaxRows];
+            FwdFacts f{};
+            f.logn = LOGN;
+            f.flags = flags;
+            f.live = live_p;
+            f.live_n = live.n;
+            f.gathers = src.base[0] != nullptr;
+            f.all_gathered = f.same_source = f.key_moduli_fp = true;
+            for (int i = 0; i < live.n; i++)
             {
-                bool ok = !exact_fwd();
-                for (int i = 0; ok && i < live.n; i++)
-                    ok = bounds::fwd_canon_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
-                if (ok)
-                    flags &= ~kNttStrict;
+                live_p[i] = e.tables[map.prime[live.slot[i]]].p;
+                if (f.gathers)
+                {
+                    f.all_gathered = f.all_gathered && src.code[live.slot[i]] != kSkipRow;
+                    f.same_source = f.same_source && ((src.code[live.slot[i]] ^ src.code[live.slot[0]]) & ~kSrcReduce) == 0;
+                }
             }
-            // STRICT launches on primes without the head-room of the rule above (the 60-bit Bsk rows of a BFV multiply) whose
-            // consumer takes any representative below 2p (kNttReduceOut | kNttAnyRep): the dense lazy schedule of
-            // ntt_bounds.hpp section 2b instead of a conditional subtraction per butterfly -- the reference's own butterfly,
-            // every word brought back below 2p before rounds 2 and 3 and in the store. Same residues, nothing wraps.
-            bool dense = (flags & kNttStrict) != 0 && (flags & kNttReduceOut) != 0 && (flags & kNttAnyRep) != 0 &&
-                         (flags & kNttCanonical) == 0 && !src.base[0] && !exact_fwd();
-            for (int i = 0; dense && i < live.n; i++)
-                dense = bounds::fwd_dense_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
-            // (kNttTopDone: no workgroup reads the other's half, nothing to hand off)
-            const bool top_done = (flags & kNttTopDone) != 0;
-            // (a STRICT launch may start below the top layer only on the dense schedule: Harvey's sequence has no such instance)
-            if (top_done && (((flags & (kNttReduceOut | kNttStrict | kNttCanonical)) != kNttReduceOut && !dense) || src.base[0]))
+            for (std::size_t i = 0; f.gathers && f.key_moduli_fp && i < e.key_moduli.size(); i++)
+                f.key_moduli_fp = e.key_moduli[i] < bounds::kFpInputBound;
+            f.treatment = src.reduce_mode;
+            f.aux_p = src.aux_p;
+            f.sw = ntt_switches();
+            f.suppress_signal = e.ntt_suppress_signal;
+            const FwdChoice c = select_fwd_half(f);
+            if (!c.valid)
                 return hipErrorInvalidValue;
-            // a launch whose live rows are all gathered from another buffer writes no row that anybody reads: nothing to
-            // hand off either
-            bool all_gathered = src.base[0] != nullptr;
-            for (int i = 0; all_gathered && i < live.n; i++)
-                all_gathered = src.code[live.slot[i]] != kSkipRow;
-            const bool no_handoff = top_done || all_gathered;
-            unsigned *tickets = no_handoff ? nullptr : e.ntt_tickets(nrows); // zeroed for this launch, stream-ordered
-            if (e.ntt_suppress_signal)
-                flags |= kNttDebugNoSignal; // sealhip_debug_ntt_handoff: drive the time-out path
-            // (see half_block_map)
-            bool one_source = all_gathered && src.reduce_mode <= 2 && live.n > 1;
-            for (int i = 1; one_source && i < live.n; i++) // every live row gathers the same source row (a key-switch digit)
-                one_source = ((src.code[live.slot[i]] ^ src.code[live.slot[0]]) & ~kSrcReduce) == 0;
-            if (!tickets && !no_handoff)
+            // The transform is in place and both workgroups of a row read both halves: a ticket per row (zeroed for this
+            // launch, stream-ordered) tells each when the other has finished loading -- unless the choice says that nothing
+            // is handed off
+            unsigned *tickets = c.tickets ? e.ntt_tickets(nrows) : nullptr;
+            if (c.tickets && !tickets)
                 return hipErrorOutOfMemory;
-            // Floating-point instance (devmath.hpp): every live prime below 2^50, inputs below 2^52 (residues, or gathered
-            // words of another key prime, or the output of a load treatment), and a launch that does not ask for the
-            // integer sequence's own representatives (canonical output, or a consumer that reduces whatever it reads).
-            // The result is the canonical residue, so the integer instances' flags play no further role.
-            bool fp = fp64_enabled() && (flags & (kNttAnyRep | kNttCanonical)) != 0 && (flags & kNttReduceOut) == 0;
-            for (int i = 0; fp && i < live.n; i++)
-                fp = e.tables[map.prime[live.slot[i]]].p < kFpPrimeBound;
-            if (fp && src.base[0])
+            NttSource ksrc = src;
+            if (c.aux_as_doubles)
             {
-                if (src.reduce_mode == 4 || src.reduce_mode == 5 || src.reduce_mode == 7)
-                    fp = src.aux_p < (src.reduce_mode == 4 ? bounds::kFpInputBound : kFpPrimeBound); // (5, 7: sums of two words below 2P)
-                else
-                    for (std::size_t i = 0; fp && i < e.key_moduli.size(); i++)
-                        fp = e.key_moduli[i] < bounds::kFpInputBound;
-            }
-            if (one_source && !fp) // (the integer digit launches)
-            {
-                const int g = 4 < live.n ? 4 : live.n;
-                flags |= kNttPolyMajor | (g << 16);
-            }
-            if (flags & kNttAnyRep)
-            {
-                // the last layer may keep its first operand unreduced only if the grown values cannot wrap
-                // (below (2 log n + 3) p < 2^64 for p < 2^58) and nothing expects the [0, 4p) output range
-                bool ok = !exact_fwd() && (flags & (kNttCanonical | kNttStrict)) == 0;
-                for (int i = 0; ok && i < live.n; i++)
-                    ok = bounds::fwd_lazy_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
-                if (!ok)
-                    flags &= ~kNttAnyRep;
-            }
-            ProfScope prof(e, "ntt_fwd_half", transformed_rows(nrows, map));
-#define SEALHIP_FWD_HALF(STRICT_, RED_)                                                                              \
-    ntt_fwd_half_kernel<LOGN, STRICT_, RED_><<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>( \
-        data, e.d_primes, map, nrows, flags, tickets, e.lane().d_fault, e.ntt_spin_limit, src, chunk, live)
-            int red = src.base[0] ? src.reduce_mode : 0;
-            if (flags & kNttReduceOut)
-            {
-                if (red != 0 || (flags & kNttCanonical))
-                    return hipErrorInvalidValue; // an in-place, non-canonical launch option
-                red = top_done ? 6 : 3;
-            }
-            // butterfly mode 2 (approximate Shoup quotient, one multiplier instruction less per butterfly): the product then
-            // lies in [0, 3p), every layer adds 3p instead of 2p and the outputs are below 50p (kNttAnyRep) or 5p. Only where
-            // the consumer reduces whatever representative it reads, nothing expects the [0, 4p) range (no canonicalising
-            // wrapper, no kNttReduceOut) and 50p cannot wrap: every live prime below 2^58.
-            const bool no_apx = exact_fwd();
-            bool apx = !no_apx && (flags & kNttApprox) != 0 && (flags & (kNttStrict | kNttCanonical | kNttReduceOut)) == 0 &&
-                       red != 4 && red != 5 && red != 7;
-            for (int i = 0; apx && i < live.n; i++)
-                apx = bounds::fwd_lazy_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
-            // The canonicalising wrapper (ntt.h:225-246) on primes with head-room: the canonical residue does not depend on
-            // the representatives the layers pass on, so an in-place canonical transform runs the cheapest exact schedule --
-            // approximate quotient, no Barrett step in the last layer, values below (4 + g log n) p for inputs below 4p
-            // (ntt_bounds.hpp section 2: fwd_canon_admits) -- and canonicalises with one reduction as it stores.
-            // SEALHIP_NTT_CANON_EXACT=1: the reference's sequence.
-            static const bool canon_exact = std::getenv("SEALHIP_NTT_CANON_EXACT") != nullptr;
-            bool capx = !no_apx && !canon_exact && !fp && red == 0 && (flags & kNttCanonical) != 0 &&
-                        (flags & (kNttStrict | kNttReduceOut)) == 0;
-            for (int i = 0; capx && i < live.n; i++) // (inputs below 4p, the range include/sealhip.h documents)
-                capx = bounds::fwd_canon_admits(e.tables[map.prime[live.slot[i]]].p, LOGN);
-            if (capx)
-            {
-                apx = true;
-                flags |= kNttAnyRep;
-                bool sq = true; // (else the Barrett step, as in round 3)
-                for (int i = 0; sq && i < live.n; i++)
-                    sq = bounds::small_quot_admits(e.tables[map.prime[live.slot[i]]].p, bounds::fwd_canon_output_mult(LOGN));
-                if (sq)
-                    flags |= kNttSmallQuot;
-            }
-            if (red == 7 && (!fp || !kStoreExchange<T, 7>))
-                return hipErrorInvalidValue; // ntt_can_fuse_moddown said no: the caller runs moddown_post itself
-            if (fp && (red == 4 || red == 5 || red == 7))
-            {
-                NttSource fsrc = src; // the special prime's constants as doubles (h_load_top)
                 const double P = static_cast<double>(src.aux_p), Pinv = 1.0 / P;
                 const double c0 = static_cast<double>(src.aux_top[0]), c2 = static_cast<double>(src.aux_top[2]);
-                std::memcpy(&fsrc.aux_p, &P, 8);
-                std::memcpy(&fsrc.aux_cr1, &Pinv, 8);
-                std::memcpy(&fsrc.aux_top[0], &c0, 8);
-                std::memcpy(&fsrc.aux_top[2], &c2, 8);
-                if (red == 7)
-                {
-                    if constexpr (kStoreExchange<T, 7>)
-                        ntt_fwd_half_kernel<LOGN, 3, 7><<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
-                            data, e.d_primes, map, nrows, flags, tickets, e.lane().d_fault, e.ntt_spin_limit, fsrc, chunk, live);
-                }
-                else if (red == 5)
-                    ntt_fwd_half_kernel<LOGN, 3, 5><<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
-                        data, e.d_primes, map, nrows, flags, tickets, e.lane().d_fault, e.ntt_spin_limit, fsrc, chunk, live);
-                else
-                    ntt_fwd_half_kernel<LOGN, 3, 4><<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
-                        data, e.d_primes, map, nrows, flags, tickets, e.lane().d_fault, e.ntt_spin_limit, fsrc, chunk, live);
+                std::memcpy(&ksrc.aux_p, &P, 8);
+                std::memcpy(&ksrc.aux_cr1, &Pinv, 8);
+                std::memcpy(&ksrc.aux_top[0], &c0, 8);
+                std::memcpy(&ksrc.aux_top[2], &c2, 8);
             }
-            else if (fp)
-            {
-                if (red == 2)
-                    SEALHIP_FWD_HALF(3, 2);
-                else if (red == 1)
-                    SEALHIP_FWD_HALF(3, 1);
-                else
-                    SEALHIP_FWD_HALF(3, 0);
-            }
-            else if (apx)
-            {
-                if (red == 2)
-                    SEALHIP_FWD_HALF(2, 2);
-                else if (red == 1)
-                    SEALHIP_FWD_HALF(2, 1);
-                else
-                    SEALHIP_FWD_HALF(2, 0);
-            }
-            else if (dense && top_done)
-                SEALHIP_FWD_HALF(4, 6);
-            else if (dense)
-                SEALHIP_FWD_HALF(4, 3);
-            else if (flags & kNttStrict)
-            {
-                if (red == 5)
-                    SEALHIP_FWD_HALF(1, 5);
-                else if (red == 4)
-                    SEALHIP_FWD_HALF(1, 4);
-                else if (red == 3)
-                    SEALHIP_FWD_HALF(1, 3);
-                else if (red == 2)
-                    SEALHIP_FWD_HALF(1, 2);
-                else if (red == 1)
-                    SEALHIP_FWD_HALF(1, 1);
-                else
-                    SEALHIP_FWD_HALF(1, 0);
-            }
-            else
-            {
-                if (red == 6)
-                    SEALHIP_FWD_HALF(0, 6);
-                else if (red == 5)
-                    SEALHIP_FWD_HALF(0, 5);
-                else if (red == 4)
-                    SEALHIP_FWD_HALF(0, 4);
-                else if (red == 3)
-                    SEALHIP_FWD_HALF(0, 3);
-                else if (red == 2)
-                    SEALHIP_FWD_HALF(0, 2);
-                else if (red == 1)
-                    SEALHIP_FWD_HALF(0, 1);
-                else
-                    SEALHIP_FWD_HALF(0, 0);
-            }
-#undef SEALHIP_FWD_HALF
+            ProfScope prof(e, "ntt_fwd_half", transformed_rows(nrows, map));
+            fwd_kernels<LOGN>()[c.instance]<<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
+                data, e.d_primes, map, nrows, c.flags, tickets, e.lane().d_fault, e.ntt_spin_limit, ksrc, chunk, live);
             return hipGetLastError();
         }
 
+        // the dynamic LDS limit of every instance of the ring (the default suffices at 2^14 only)
         template <int LOGN>
         hipError_t init_half()
         {
             const int lds_bytes = hpad(1 << (LOGN - 2)) * 8;
-            hipError_t err = hipSuccess;
-            const void *fwd[23] = { reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 4, 3>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 4, 6>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 6>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 5>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 5>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 5>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 0>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 1>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 2>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 4>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 4>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 4>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 3>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 3>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 0>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 1>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 0, 2>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 0>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 1>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 1, 2>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 2, 0>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 2, 1>),
-                                    reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 2, 2>) };
-            for (const void *f : fwd)
-            {
-                err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (err != hipSuccess)
-                    return err;
-            }
-            if constexpr (kStoreExchange<LOGN - 1, 7>)
-            {
-                err = hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_fwd_half_kernel<LOGN, 3, 7>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (err != hipSuccess)
-                    return err;
-            }
-            return err;
+            for (int i = 0; i < kFwdInstanceCount; i++)
+                if (const FwdKernel k = fwd_kernels<LOGN>()[i])
+                {
+                    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+                    if (err != hipSuccess)
+                        return err;
+                }
+            return hipSuccess;
         }
     } // namespace
 

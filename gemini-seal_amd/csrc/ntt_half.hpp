@@ -8,9 +8,11 @@
 
 namespace sealhip
 {
-    // Read once per process (getenv), defined in ntt.hip: SEALHIP_NTT_NO_FP64 switches the floating-point instances off;
-    // SEALHIP_NTT_EXACT_FWD switches the forward transform's shortcuts off (the reference's own sequence). The
-    // STRICT-drop rule, the dense schedule and ntt_strict_top_done_ok must agree about the latter within a process.
+    // The environment switches (ntt_select.hpp NttSwitches), read once per process, defined in ntt.hip: the only getenv of
+    // the NTT. SEALHIP_NTT_NO_FP64 switches the floating-point instances off; SEALHIP_NTT_EXACT_FWD switches the forward
+    // transform's shortcuts off (the reference's own sequence). The STRICT-drop rule, the dense schedule and
+    // ntt_strict_top_done_ok must agree about the latter within a process: all three read this one copy.
+    SEALHIP_INTERNAL const NttSwitches &ntt_switches();
     SEALHIP_INTERNAL bool fp64_enabled();
     SEALHIP_INTERNAL bool exact_fwd();
 
@@ -172,7 +174,7 @@ namespace sealhip
         // the floating-point variant's tables hold one double per twiddle (PrimeDev::fwd_d / inv_d), moved as 64-bit words
         typedef const __attribute__((address_space(1))) u64 *twd_global_t;
         typedef const __attribute__((address_space(4))) u64 *twd_const_t;
-        // In the floating-point instances (STRICT == 3 forward, MODE == 2 inverse) the registers x[] hold the bit patterns
+        // In the floating-point instances (STRICT == kSchedFp64 forward, LZ == kInvFp64 inverse) the registers x[] hold the bit patterns
         // of doubles, the parameters named two_p / neg_p carry the bits of p and 1/p as doubles, and tw points to the
         // double table. Reduction schedule of the forward transform (ntt_bounds.hpp section 4 holds the derivation and the
         // recurrence the CPU test runs). With U = 2^50 >= p and B a bound on the magnitudes, a layer gives
@@ -237,7 +239,7 @@ namespace sealhip
         // transforms 17.34 ms per 1024 pairs at g = 1, 17.18 / 17.10 / 16.98 at g = 2 / 3 / 4, 17.13 at g = 7 (the tables start
         // to thrash the 4 MB L2); step 44.98 -> 44.51 ms at g = 4. Config 4 (FP64, eleven readers): the transforms gain 2.5 % at
         // g = 11 but the inner product, which reads what they wrote in the old order, loses as much: off there.
-        // launch_half: g = 4, integer launches only.
+        // select_fwd_half (ntt_select.hpp): g = 4, integer launches only.
         __device__ __forceinline__ bool half_block_map(unsigned bid, std::size_t npolys, int n_live, std::size_t chunk,
                                                        std::size_t &poly, int &position, int &half, int poly_major = 0)
         {

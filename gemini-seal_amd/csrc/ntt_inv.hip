@@ -1,6 +1,6 @@
 // ntt_inv.hip -- single-pass inverse NTT for N = 2^14 .. 2^16 (the half-row kernel and its whole-row and quarter-row
 // forms, ntt_half.hpp), the streaming top-layer passes, and their launcher.
-#include <cstdlib>
+#include <utility>
 
 #include "ntt_half.hpp"
 
@@ -17,23 +17,23 @@ namespace sealhip
         // pass (or, inside the pipelines, by the consumer kernel).
         // ---- inverse rounds as stage pipelines (mirror of ntt_fwd.hip RoundStage / RoundPipe; layers ascend W = 1, 2, 3, 4)
         // Lazy-sum schedule of the inverse (only when the caller accepts any representative of the stored values and every
-        // prime of the launch is small enough, launch_half_inv): the conditional subtraction of the sum output is dropped
+        // prime of the launch is small enough, select_inv_half): the conditional subtraction of the sum output is dropped
         // on all but two of the T on-chip layers; those two (the middle one and the last) reduce with barrett_lazy
         // instead. Values entering layer l are below 2^shift(l) * p; the difference operand gets that bound added.
         // (the schedule, its worst-case recurrence and the admission predicate live in ntt_bounds.hpp)
         // Round 4: the MODE 1 layers of the lazy schedule (all but two) take the level-2 quotient (devmath.hpp mulhi_apx2,
         // butterflies_inv_apx2): their products land below 4p, which is what the unreduced sum of such a layer is bounded by
         // anyway, so shift(), mode() and the admission predicate are what they were (ntt_bounds.hpp section 1).
-        // LZ 1: the sparse schedule (two reducing layers; primes with head-room), LZ 3 (round 4): the DENSE schedule for primes
+        // kInvLazySum: the sparse schedule (two reducing layers; primes with head-room), kInvDense (round 4): the DENSE schedule for primes
         // up to 2^60 -- every third layer and the last reduce their sums with the single-precision quotient estimate, values
         // never pass 16p (ntt_bounds.hpp section 1): the 60-bit Bsk rows of a BFV multiply and ciphertext primes of 56-60 bits
         // no longer pay a conditional subtraction in every butterfly.
         template <int LZ>
-        constexpr bool kLazy = LZ == 1 || LZ == 3;
-        template <int T, int LZ = 1>
+        constexpr bool kLazy = LZ == kInvLazySum || LZ == kInvDense;
+        template <int T, int LZ = kInvLazySum>
         struct InvLazy
         {
-            static constexpr int sched = LZ == 3 ? 1 : 0;
+            static constexpr int sched = LZ == kInvDense ? 1 : 0;
             static constexpr int mode(int l)
             {
                 return bounds::inv_lazy_mode(T, l, sched);
@@ -43,13 +43,9 @@ namespace sealhip
                 return bounds::inv_lazy_shift(T, l, sched);
             }
             // what butterflies_inv_hs gets for a reducing layer: Barrett (sparse) or the quotient estimate (dense)
-            static constexpr int reduce_mode = LZ == 3 ? 3 : 2;
+            static constexpr int reduce_mode = LZ == kInvDense ? 3 : 2;
         };
-        // on-chip layers of the inverse kernel instance ntt_inv_half_kernel<KLOGN, ...> (half-row form of a ring of 2^KLOGN,
-        // or whole-row form of a ring of 2^(KLOGN-1)): what the launchers hand to bounds::inv_lazy_admits
-        template <int KLOGN>
-        constexpr int kInvLayers = KLOGN - 1;
-        // Floating-point schedule of the inverse (LZ == 2, primes below 2^50, inputs below 2p): sums double the bound per
+        // Floating-point schedule of the inverse (LZ == kInvFp64, primes below 2^50, inputs below 2p): sums double the bound per
         // layer, so both outputs of layers 1, 5, 9, 13 are brought back to [-p/2, p/2]: 2p -> 4p -> 8p | 0.5p -> p -> 2p ->
         // 4p -> 8p | ...; a difference is at most 8p too, its product below (0.5 + 8p 2^-52) p <= 2.5p. Every magnitude stays
         // at or below 8p < 2^53: exact (devmath.hpp). The last layer's outputs are canonicalised by the store instead.
@@ -68,7 +64,7 @@ namespace sealhip
         {
             return bounds::fp_inv_reduce_after_layer(T, layer);
         }
-        template <int T, int R, bool UNIFORM, int K, int LZ = 0>
+        template <int T, int R, bool UNIFORM, int K, int LZ = kInvExact>
         struct RoundStageInv
         {
             static constexpr int PER = 16 / kIL;
@@ -87,7 +83,7 @@ namespace sealhip
                 for (int j = 0; j < kIL; j++)
                 {
                     u64x2 Wv;
-                    if constexpr (LZ == 2)
+                    if constexpr (LZ == kInvFp64)
                     {
                         Wv.x = UNIFORM ? ((twd_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)]
                                        : ((twd_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
@@ -105,7 +101,7 @@ namespace sealhip
             __device__ static __forceinline__ void run(u64 (&x)[32], const u64 (&w)[kIL], const u64 (&ws)[kIL], u64 two_p,
                                                        u64 neg_p, u64 rdp, ZeroPairs &zp)
             {
-                if constexpr (LZ == 2)
+                if constexpr (LZ == kInvFp64)
                 {
                     const double pd = fp_of(two_p), pinv = fp_of(neg_p);
 #pragma unroll
@@ -189,7 +185,7 @@ namespace sealhip
         __device__ __forceinline__ void h_first_group_regs(u64 (&x)[32], const u64x2 *tg, u64 neg_p, u64 two_p, u64 rdp, ZeroPairs &zp)
         {
             constexpr int f = T - 12;
-            static_assert(LZ != 1 || f - 1 < bounds::inv_lazy_r1(T), "sparse schedule: the first layers are never the reducing ones");
+            static_assert(LZ != kInvLazySum || f - 1 < bounds::inv_lazy_r1(T), "sparse schedule: the first layers are never the reducing ones");
             int base = 0;
 #pragma unroll
             for (int W = 0; W < f; W++)
@@ -203,7 +199,7 @@ namespace sealhip
                         continue;
                     const int s = (G << f) | e;
                     const u64x2 Wv = tg[base + (e >> (W + 1))];
-                    if constexpr (LZ == 2)
+                    if constexpr (LZ == kInvFp64)
                     {
                         const double pd = fp_of(two_p), pinv = fp_of(neg_p);
                         fp_butterfly_inv(x[s], x[s | bit], Wv.x, pd, pinv);
@@ -224,7 +220,7 @@ namespace sealhip
                     // (W is a constant after unrolling: the branch folds)
                     // (level-2 quotient in the non-reducing layers of the first round too -- sparse schedule only: the dense
                     //  plain instances spill four dwords with the pairs live here)
-                    if (LZ == 1 && InvLazy<T, 1>::mode(W) == 1)
+                    if (LZ == kInvLazySum && InvLazy<T, kInvLazySum>::mode(W) == 1)
                         x[s | bit] = mulmod_lazy_apx2<false>(u - v + addend, Wv.x, Wv.y, neg_p, zp.z[(e >> (W + 1)) & 1]);
                     else
                         x[s | bit] = mulmod_lazy_hs<false>(u - v + addend, Wv.x, Wv.y, neg_p);
@@ -237,7 +233,7 @@ namespace sealhip
         {
             __device__ static __forceinline__ void load(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
             {
-                h_first_tw<T, ST * FinalStage<T>::SG + I, LZ == 2>(tg + I * FinalStage<T>::NTW, tw, jb, N);
+                h_first_tw<T, ST * FinalStage<T>::SG + I, LZ == kInvFp64>(tg + I * FinalStage<T>::NTW, tw, jb, N);
                 if constexpr (I + 1 < FinalStage<T>::SG)
                     FirstStage<T, ST, LZ, I + 1>::load(tg, tw, jb, N);
             }
@@ -498,7 +494,7 @@ namespace sealhip
             const std::size_t row = poly * map.rows + live.slot[position];
             const unsigned short pid = map.prime[row % map.rows];
             const PrimeDev P = primes[pid];
-            constexpr bool FP = LZ == 2; // two_p / neg_p then carry the bits of p and 1/p as doubles (see fp_reduce_all)
+            constexpr bool FP = LZ == kInvFp64; // two_p / neg_p then carry the bits of p and 1/p as doubles (see fp_reduce_all)
             static_assert(!FP || !DY, "the floating-point instance serves plain half transforms only");
             const u64 p = P.p, two_p = FP ? fp_bits(P.p_d) : P.two_p;
             const u64 *tw = FP ? reinterpret_cast<const u64 *>(P.inv_d) : P.inv;
@@ -510,7 +506,7 @@ namespace sealhip
             const u64 neg_p = FP ? fp_bits(P.pinv_d) : 0 - p;
             // what the reducing layers of the lazy schedules read: floor(2^64 / p) (sparse: Barrett) or the bits of the
             // single-precision quotient constant (dense)
-            const u64 rdp = LZ == 1 ? P.rdp : (LZ == 3 ? static_cast<u64>(__float_as_uint(small_quot_const(p))) : 0);
+            const u64 rdp = LZ == kInvLazySum ? P.rdp : (LZ == kInvDense ? static_cast<u64>(__float_as_uint(small_quot_const(p))) : 0);
             {
                 // every coefficient of the half row first (16 x 16 bytes per lane in flight at once), the twiddles of
                 // the first stage with them
@@ -553,9 +549,9 @@ namespace sealhip
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 ZeroPairs zp1; // (devmath.hpp mulhi_apx2: the first round's own pairs, written here, dead after it)
-                if constexpr (LZ == 1)
+                if constexpr (LZ == kInvLazySum)
                     zp1.init();
-                FirstPipe<T, 0, LZ, FinalStage<T>::PIPE && !(DY && kLazy<LZ>) && !(WHOLE && LZ == 0)>::run(x, tg0, tw, gbase + jloc, N, neg_p,
+                FirstPipe<T, 0, LZ, FinalStage<T>::PIPE && !(DY && kLazy<LZ>) && !(WHOLE && LZ == kInvExact)>::run(x, tg0, tw, gbase + jloc, N, neg_p,
                                                                                                          two_p, rdp, zp1);
             }
             const int jb3 = gbase + Arr<T, 3>::tid_index(fresh_tid(wave_base));
@@ -605,7 +601,7 @@ namespace sealhip
                     {
                         const u64 u = x[s2], v = x[s2 | 16];
                         u64 tt = u + v;
-                        if (LZ == 0)
+                        if (LZ == kInvExact)
                             tt = tt >= two_p ? tt - two_p : tt;
                         u64 a0 = mulmod_lazy_hs<true>(tt, P.inv_n, P.inv_n_shoup, neg_p);
                         u64 a1 = mulmod_lazy_hs<true>(u - v + addend, P.inv_n_w, P.inv_n_w_shoup, neg_p);
@@ -732,12 +728,49 @@ namespace sealhip
             }
         }
 
+        // The instances that serve a ring of 2^LOGN, in the order of kInvInstances (ntt_select.hpp; null where the table says
+        // the instance does not serve this ring size): launch_half_inv launches from this table and init_half_inv registers
+        // from it. The whole-row form of a ring is the half-row kernel of the ring twice as large, the quarter-row form
+        // that of the ring half as large (inv_kernel_logn).
+        using InvKernel = void (*)(u64 *, const PrimeDev *, RowMap, std::size_t, std::size_t, const u64 *, std::size_t, LiveSlots,
+                                   DyadicSrc, int);
+        template <int LOGN, int I>
+        InvKernel inv_kernel()
+        {
+            constexpr InvInstance inst = kInvInstances[I];
+            if constexpr (inv_instance_at(LOGN, inst))
+                return &ntt_inv_half_kernel<inv_kernel_logn(inst.shape, LOGN), inst.sched, inst.tensor_load(), inst.shape == kShapeWhole,
+                                            inst.shape == kShapeQuarter>;
+            else
+                return nullptr;
+        }
+        template <int LOGN, int... I>
+        const InvKernel *inv_kernels(std::integer_sequence<int, I...>)
+        {
+            static const InvKernel table[] = { inv_kernel<LOGN, I>()... };
+            return table;
+        }
+        template <int LOGN>
+        const InvKernel *inv_kernels()
+        {
+            return inv_kernels<LOGN>(std::make_integer_sequence<int, kInvInstanceCount>{});
+        }
+        // a shape's exchange buffer: half of the 2^(KLOGN - 1) coefficients a workgroup of ntt_inv_half_kernel<KLOGN, ..> holds
+        constexpr int inv_lds_bytes(int shape, int logn)
+        {
+            return hpad(1 << (inv_kernel_logn(shape, logn) - 2)) * 8;
+        }
+
+        // Which shape and schedule run, and which top pass follows, is select_inv_half's decision (ntt_select.hpp; the
+        // instances and who launches them: DESIGN.md section 6). Here: the facts it decides on and the launches.
+        // (A one-launch standalone inverse by sibling hand-off -- the second finisher of a row applying the top layer to
+        //  both halves -- was measured in round 2 and brought nothing; its cross-workgroup publish
+        //  rested on workgroup-scope fences, so the path was removed rather than kept as an unsupported option.)
         template <int LOGN>
         hipError_t launch_half_inv(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags,
                                    const u64 *src = nullptr, std::size_t src_poly_stride = 0,
                                    const DyadicSrc *dyadic = nullptr)
         {
-            constexpr int T = LOGN - 1;
             if (fp64_enabled() && (flags & (kNttAnyRep | kNttCanonical)) != 0 && !dyadic)
             {
                 RowMap a, b;
@@ -747,202 +780,58 @@ namespace sealhip
                     return err != hipSuccess ? err : launch_half_inv<LOGN>(e, data, nrows, b, flags, src, src_poly_stride);
                 }
             }
-            const std::size_t lds_bytes = static_cast<std::size_t>(hpad(1 << (T - 1))) * 8;
             if (nrows % map.rows != 0)
                 return hipErrorInvalidValue;
             const LiveSlots live = live_slots(map);
             if (live.n == 0)
                 return hipSuccess;
-            const std::size_t chunk = ((nrows / map.rows) * live.n + 7) / 8; // live rows per XCD
-            const std::size_t blocks = chunk * 16;
-            if (blocks > 0x7fffffffull)
+            u64 live_p[kMaxRows];
+            for (int i = 0; i < live.n; i++)
+                live_p[i] = e.tables[map.prime[live.slot[i]]].p;
+            const InvChoice c = select_inv_half(InvFacts{ LOGN, flags, live_p, live.n, dyadic != nullptr, ntt_switches() });
+            if (!c.valid)
                 return hipErrorInvalidValue;
-            bool did_quarter = false;
+            const std::size_t chunk = ((nrows / map.rows) * live.n + 7) / 8; // live rows per XCD
+            const std::size_t blocks = chunk * 8 * inv_blocks_per_row(c.shape); // (eight XCDs)
+            if (chunk * 16 > 0x7fffffffull || blocks > 0x7fffffffull)
+                return hipErrorInvalidValue;
             {
                 ProfScope prof(e, "ntt_inv_half", transformed_rows(nrows, map));
-                // lazy-sum schedule (InvLazy): the stored values keep their residue class and stay below 2p, but not the
-                // reference's representative -- only where the caller says so (kNttAnyRep: its inputs are below 2p and
-                // the consuming kernel canonicalises) and no live prime can wrap
-                // (the canonicalising wrapper, ntt.h:328-333, erases the representative too: its inputs are what the reference
-                //  itself requires of an inverse transform, values below 2p)
-                static const bool exact_only = std::getenv("SEALHIP_NTT_EXACT_INV") != nullptr;
-                bool lazy = (flags & (kNttAnyRep | kNttCanonical)) != 0 && !exact_only;
-                bool dense = lazy; // (round 4) the dense schedule where the sparse one has no head-room: primes of 2^45 .. 2^60
-                for (int i = 0; dense && i < live.n; i++)
-                    dense = bounds::inv_dense_admits(kInvLayers<LOGN>, e.tables[map.prime[live.slot[i]]].p);
-                for (int i = 0; lazy && i < live.n; i++)
-                    lazy = bounds::inv_lazy_admits(kInvLayers<LOGN>, e.tables[map.prime[live.slot[i]]].p);
-                dense = dense && !lazy;
-                // floating-point instance: same contract (inputs below 2p, any representative out), every live prime below 2^50
-                bool fp = (flags & (kNttAnyRep | kNttCanonical)) != 0 && fp64_enabled() && !dyadic;
-                for (int i = 0; fp && i < live.n; i++)
-                    fp = e.tables[map.prime[live.slot[i]]].p < kFpPrimeBound;
-                const DyadicSrc dy = dyadic ? *dyadic : DyadicSrc{};
-                // (A one-launch standalone inverse by sibling hand-off -- the second finisher of a row applying the top layer to
-                //  both halves -- was measured in round 2 and brought nothing; its cross-workgroup publish
-                //  rested on workgroup-scope fences, so the path was removed rather than kept as an unsupported option.)
-                if constexpr (LOGN <= 15)
-                {
-                    // whole-row form (see the kernel): standalone transforms (the top layer is not left to a consumer)
-                    if (!dyadic && !(flags & kNttDeferTop))
-                    {
-                        const std::size_t wlds = static_cast<std::size_t>(hpad(1 << (LOGN - 1))) * 8;
-                        const int canon = (flags & kNttCanonical) ? 1 : 0;
-#define SEALHIP_INV_WHOLE(LZ_)                                                                                          \
-    ntt_inv_half_kernel<LOGN + 1, LZ_, false, true>                                                                      \
-        <<<static_cast<unsigned>(chunk * 8), 1 << (LOGN - 5), wlds, e.lane().stream>>>(                                  \
-            data, e.d_primes, map, nrows, chunk, src, src_poly_stride, live, dy, canon)
-                        // (the lazy-sum schedule of the larger shape has one more layer: its own bound on the primes -- the
-                        //  predicate takes the layer count of the instance that is launched, ntt_inv_half_kernel<LOGN + 1, ..>)
-                        bool lazy_w = lazy, dense_w = (lazy || dense);
-                        for (int i = 0; lazy_w && i < live.n; i++)
-                            lazy_w = bounds::inv_lazy_admits(kInvLayers<LOGN + 1>, e.tables[map.prime[live.slot[i]]].p);
-                        for (int i = 0; dense_w && i < live.n; i++)
-                            dense_w = bounds::inv_dense_admits(kInvLayers<LOGN + 1>, e.tables[map.prime[live.slot[i]]].p);
-                        if (fp)
-                            SEALHIP_INV_WHOLE(2);
-                        else if (lazy_w)
-                            SEALHIP_INV_WHOLE(1);
-                        else if (dense_w)
-                            SEALHIP_INV_WHOLE(3);
-                        else
-                            SEALHIP_INV_WHOLE(0);
-#undef SEALHIP_INV_WHOLE
-                        return hipGetLastError();
-                    }
-                }
-                if constexpr (LOGN == 16)
-                {
-                    // (round 4) standalone transforms at N = 2^16: quarter-row workgroups of the N = 2^15 shape (two per CU) and one
-                    // streaming radix-4 pass for the two top layers, instead of the 1024-lane half-row kernel (one per CU) and
-                    // the streaming top-layer pass (profiles/r04/n65536_quarter_row_inverse.txt)
-                    if (!dyadic && !(flags & kNttDeferTop))
-                    {
-                        constexpr int QL = LOGN - 1; // the shape: ntt_inv_half_kernel<15, ..>, 14 on-chip layers
-                        const std::size_t qlds = static_cast<std::size_t>(hpad(1 << (QL - 2))) * 8;
-                        const std::size_t qblocks = chunk * 32; // four workgroups per live row, eight XCDs
-                        if (qblocks > 0x7fffffffull)
-                            return hipErrorInvalidValue;
-                        bool lazy_q = (flags & (kNttAnyRep | kNttCanonical)) != 0 && !exact_only, dense_q = lazy_q;
-                        for (int i = 0; lazy_q && i < live.n; i++)
-                            lazy_q = bounds::inv_lazy_admits(kInvLayers<QL>, e.tables[map.prime[live.slot[i]]].p);
-                        for (int i = 0; dense_q && i < live.n; i++)
-                            dense_q = bounds::inv_dense_admits(kInvLayers<QL>, e.tables[map.prime[live.slot[i]]].p);
-#define SEALHIP_INV_QUARTER(LZ_)                                                                                          \
-    ntt_inv_half_kernel<QL, LZ_, false, false, true>                                                                        \
-        <<<static_cast<unsigned>(qblocks), 1 << (QL - 6), qlds, e.lane().stream>>>(data, e.d_primes, map, nrows, chunk, src, \
-                                                                                    src_poly_stride, live, dy)
-                        if (fp)
-                            SEALHIP_INV_QUARTER(2);
-                        else if (lazy_q)
-                            SEALHIP_INV_QUARTER(1);
-                        else if (dense_q)
-                            SEALHIP_INV_QUARTER(3);
-                        else
-                            SEALHIP_INV_QUARTER(0);
-#undef SEALHIP_INV_QUARTER
-                        hipError_t qerr = hipGetLastError();
-                        if (qerr != hipSuccess)
-                            return qerr;
-                        did_quarter = true;
-                    }
-                }
-                if (!did_quarter)
-                {
-#define SEALHIP_INV_HALF(LZ_, DY_)                                                                                    \
-    ntt_inv_half_kernel<LOGN, LZ_, DY_><<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>( \
-        data, e.d_primes, map, nrows, chunk, src, src_poly_stride, live, dy)
-                if (dyadic)
-                {
-                    if (lazy)
-                        SEALHIP_INV_HALF(1, true);
-                    else if (dense)
-                        SEALHIP_INV_HALF(3, true);
-                    else
-                        SEALHIP_INV_HALF(0, true);
-                }
-                else if (fp)
-                    SEALHIP_INV_HALF(2, false);
-                else if (lazy)
-                    SEALHIP_INV_HALF(1, false);
-                else if (dense)
-                    SEALHIP_INV_HALF(3, false);
-                else
-                    SEALHIP_INV_HALF(0, false);
-#undef SEALHIP_INV_HALF
-                hipError_t err = hipGetLastError();
-                if (err != hipSuccess)
+                inv_kernels<LOGN>()[c.instance]<<<static_cast<unsigned>(blocks), 1 << (inv_kernel_logn(c.shape, LOGN) - 6),
+                                                  inv_lds_bytes(c.shape, LOGN), e.lane().stream>>>(
+                    data, e.d_primes, map, nrows, chunk, src, src_poly_stride, live, dyadic ? *dyadic : DyadicSrc{}, c.canon);
+                const hipError_t err = hipGetLastError();
+                if (err != hipSuccess || c.top == kTopNone)
                     return err;
-                }
             }
-            if (did_quarter)
-            {
-                const std::size_t nitems = nrows << (LOGN - 3);
-                std::size_t grid = (nitems + 255) / 256;
-                if (grid > 256u * 32u)
-                    grid = 256u * 32u;
-                ProfScope prof(e, "ntt_inv_top", 0);
-                ntt_inv_top2_kernel<<<static_cast<unsigned>(grid), 256, 0, e.lane().stream>>>(data, e.d_primes, map, LOGN, nitems, flags);
-                return hipGetLastError();
-            }
-            if (flags & kNttDeferTop)
-                return hipSuccess; // the consumer applies the top layer (and the canonicalisation) on load
-            const std::size_t npairs = nrows << (LOGN - 2);
-            std::size_t grid = (npairs + 255) / 256;
+            // the streaming pass for what the kernel left: one lane per 16-byte pair of the first half (top layer) or of
+            // the first quarter (radix-4 pass) of every row
+            const bool radix4 = c.top == kTopRadix4;
+            const std::size_t nitems = nrows << (LOGN - (radix4 ? 3 : 2));
+            std::size_t grid = (nitems + 255) / 256;
             if (grid > 256u * 32u)
                 grid = 256u * 32u;
-            ProfScope prof(e, "ntt_inv_top", transformed_rows(nrows, map));
-            ntt_inv_top_kernel<<<static_cast<unsigned>(grid), 256, 0, e.lane().stream>>>(data, e.d_primes, map, LOGN, npairs,
-                                                                               flags);
+            ProfScope prof(e, "ntt_inv_top", radix4 ? 0 : transformed_rows(nrows, map));
+            if (radix4)
+                ntt_inv_top2_kernel<<<static_cast<unsigned>(grid), 256, 0, e.lane().stream>>>(data, e.d_primes, map, LOGN, nitems, flags);
+            else
+                ntt_inv_top_kernel<<<static_cast<unsigned>(grid), 256, 0, e.lane().stream>>>(data, e.d_primes, map, LOGN, nitems, flags);
             return hipGetLastError();
         }
 
+        // the dynamic LDS limit of every instance that serves the ring
         template <int LOGN>
         hipError_t init_half_inv()
         {
-            const int lds_bytes = hpad(1 << (LOGN - 2)) * 8;
-            hipError_t err = hipSuccess;
-            const void *inv[7] = { reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 2, false>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 1, false>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 0, false>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 3, false>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 1, true>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 3, true>),
-                                   reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 0, true>) };
-            for (const void *f : inv)
-            {
-                err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (err != hipSuccess)
-                    return err;
-            }
-            if constexpr (LOGN == 15)
-            {
-                // the quarter-row instances that serve rings of 2^16 (same shape, same LDS)
-                const void *quarter[4] = { reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 2, false, false, true>),
-                                           reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 1, false, false, true>),
-                                           reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 3, false, false, true>),
-                                           reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN, 0, false, false, true>) };
-                for (const void *f : quarter)
+            for (int i = 0; i < kInvInstanceCount; i++)
+                if (const InvKernel k = inv_kernels<LOGN>()[i])
                 {
-                    err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+                    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                               inv_lds_bytes(kInvInstances[i].shape, LOGN));
                     if (err != hipSuccess)
                         return err;
                 }
-            }
-            if constexpr (LOGN <= 15)
-            {
-                const void *whole[4] = { reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN + 1, 2, false, true>),
-                                         reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN + 1, 1, false, true>),
-                                         reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN + 1, 3, false, true>),
-                                         reinterpret_cast<const void *>(&ntt_inv_half_kernel<LOGN + 1, 0, false, true>) };
-                for (const void *f : whole)
-                {
-                    err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, hpad(1 << (LOGN - 1)) * 8);
-                    if (err != hipSuccess)
-                        return err;
-                }
-            }
-            return err;
+            return hipSuccess;
         }
     } // namespace
 

@@ -260,8 +260,8 @@ namespace sealhip
                     need_any = need_any || (a != b && ps > pd);
                     need_barrett = need_barrett || (a != b && ps >= 2 * pd);
                 }
-            int modup_mode = need_barrett ? 1 : (need_any ? 2 : 0);
-            if (modup_mode == 2)
+            int modup_mode = need_barrett ? kTreatBarrett : (need_any ? kTreatCondSub : kTreatNone);
+            if (modup_mode == kTreatCondSub)
             {
                 // A gathered word is then below 2p of its destination prime. The lazy forward transform takes such an input
                 // as it is (the first operand of a butterfly is never reduced before the last layer, the second goes through
@@ -273,7 +273,7 @@ namespace sealhip
                 for (int r = 0; r < rows; r++)
                     pmax = std::max(pmax, e.key_moduli[h.row_prime[r]]);
                 if (bounds::fwd_lazy_admits(pmax, e.logn)) // (inputs below 2p: the case the recurrence in ntt_bounds.hpp walks)
-                    modup_mode = 0;
+                    modup_mode = kTreatNone;
             }
             if (!gather)
                 check(launch_ks_modup(e, lt.d_ks, h, src, src_stride, ext, ext_item, ext_digit, m, -1), "modup");
@@ -405,7 +405,7 @@ namespace sealhip
             const bool fold_pre = fold_ok;
             // the gathered transform below reads the special row as pairs (c, c + N/2): it can apply the top inverse layer
             const bool fold_top = fold_pre && ntt_can_defer_top(e, k);
-            // ... and, in its floating-point form, finish the mod-down as it stores (reduce mode 7): temp is never written
+            // ... and, in its floating-point form, finish the mod-down as it stores (kTreatModDownStore): temp is never written
             const bool fold_store = fold_top && ntt_can_fuse_moddown(e, k, p_special);
             // (:2351-2355) special rows back to coefficient form (lazy)
             // (the mod-down reduces the special rows with barrett_reduce_63 / a Shoup product: canonical either way)
@@ -415,13 +415,13 @@ namespace sealhip
             // Step 5 (:2361): rescale_special_rns_inplace, then add into the ciphertext (:2363-2366)
             // Step 5 for CKKS with one special prime P: temp_i = (-(special mod P)) mod q_i, then its forward transform
             // (multi_special_primes.cpp:262-289). With the single-pass kernel the transform gathers the special row and forms
-            // temp_i while it loads (reduce mode 4): no pass that writes the k rows of temp, none that reads them back.
+            // temp_i while it loads (kTreatNegSpecial): no pass that writes the k rows of temp, none that reads them back.
             if (fold_pre)
             {
                 NttSource ns{};
                 ns.base[0] = prod;
                 ns.poly_stride[0] = prod_stride;
-                ns.reduce_mode = fold_store ? 7 : (fold_top ? 5 : 4);
+                ns.reduce_mode = fold_store ? kTreatModDownStore : (fold_top ? kTreatNegSpecialTop : kTreatNegSpecial);
                 if (fold_store)
                 {
                     ns.md.inv_p = lt.d_ks->invP; // (addresses inside the device copy of KsDev; not dereferenced here)
