@@ -243,7 +243,8 @@ namespace
 
     void check_key_digits(const Engine &h, uint32_t k, const sealhip_kswitch_key *key)
     {
-        if (key->key.n_digits < kswitch_digits(h, k))
+        // (a switching key made for levels <= key.level has zero rows above it)
+        if (key->key.n_digits < kswitch_digits(h, k) || (key->key.level && k > key->key.level))
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
     }
 
@@ -3066,10 +3067,12 @@ long sealhip_bootstrap_tables_plan(const sealhip_bootstrap_tables *tables, sealh
     return guarded([&] { *plan = tables->plan; });
 }
 
-long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in, const uint64_t *ct,
-                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
-                                 uint32_t n_keys, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
-                                 uint64_t *out)
+// sealhip_evaluator_bootstrap (to_sparse = to_dense = NULL) and sealhip_evaluator_bootstrap_encapsulated: the same checks, then
+// the two keys' (to_sparse serves level 1, to_dense level k_top)
+static long bootstrap_entry(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in, const uint64_t *ct,
+                            size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                            uint32_t n_keys, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                            const sealhip_kswitch_key *to_sparse, const sealhip_kswitch_key *to_dense, uint64_t *out)
 {
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(tables);
@@ -3093,13 +3096,67 @@ long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_t
         u64 *o = reinterpret_cast<u64 *>(out);
         if (words_overlap(o, count * 2 * s2c.out_level * h.n, in, count * 2 * k_in * h.n))
             throw std::invalid_argument("out must not overlap ct");
+        if (to_sparse)
+        {
+            check_key_digits(h, 1, to_sparse);
+            check_key_digits(h, c2s.in_level, to_dense);
+        }
         if (count == 0)
             return;
         Engine &e = device_engine(ctx);
         SinkScope sink(e, count);
-        op_bootstrap(e, t, static_cast<int>(k_in), in, count, c2s_keys, conj, s2c_keys, *relin, o);
+        op_bootstrap(e, t, static_cast<int>(k_in), in, count, c2s_keys, conj, s2c_keys, *relin, o,
+                     to_sparse ? &to_sparse->key : nullptr, to_dense ? &to_dense->key : nullptr);
         sink.read_pass(o, 2, static_cast<std::size_t>(s2c.out_level) * h.n, count);
     });
+}
+
+long sealhip_evaluator_bootstrap(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in, const uint64_t *ct,
+                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                 uint32_t n_keys, const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                                 uint64_t *out)
+{
+    return bootstrap_entry(ctx, tables, k_in, ct, count, galois_elts, galois_keys, n_keys, relin_keys, n_relin_keys, nullptr,
+                           nullptr, out);
+}
+
+/* ------------------------------------------------------------------ sparse-secret encapsulation */
+long sealhip_evaluator_switch_secret(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                     const sealhip_kswitch_key *key, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(key);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        check_key_digits(h, k, key);
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * poly, in, count * 2 * poly))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        sink.begin(); // (fused, as apply_galois: the key switch's last kernel writes the flags)
+        op_switch_secret(e, static_cast<int>(k), in, in + poly, 2 * poly, count, key->key, o);
+    });
+}
+
+long sealhip_evaluator_bootstrap_encapsulated(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in,
+                                              const uint64_t *ct, size_t count, const uint32_t *galois_elts,
+                                              const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                              const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                                              const sealhip_kswitch_key *to_sparse, const sealhip_kswitch_key *to_dense,
+                                              uint64_t *out)
+{
+    REQUIRE_PTR(to_sparse);
+    REQUIRE_PTR(to_dense);
+    return bootstrap_entry(ctx, tables, k_in, ct, count, galois_elts, galois_keys, n_keys, relin_keys, n_relin_keys, to_sparse,
+                           to_dense, out);
 }
 
 /* ------------------------------------------------------------------ decrypt-side arithmetic */
@@ -3786,12 +3843,16 @@ long sealhip_kswitch_keys_save(sealhip_context *ctx, const sealhip_kswitch_key *
 
 /* ---------------------------------------------------------------- KeyGenerator (keygenerator.cpp:146-240, :325-369) */
 // elts == nullptr: relin keys sk^2 .. sk^(n_keys+1); otherwise the Galois keys of elts. Every check runs on the host before
-// any device work (so host-only contexts report them too); on any failure every keys[i] stays NULL.
+// any device work (so host-only contexts report them too); on any failure every keys[i] stays NULL. switching: the new keys
+// are handed in (s_from: n_keys x n_key x N) and `level` limits what the keys publish (sealhip_generate_switching_keys).
 static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const uint32_t *elts, bool galois, size_t n_keys,
-                          const uint64_t *seeds_host, const int32_t *noise, int32_t keep_seeds, sealhip_kswitch_key **keys)
+                          const uint64_t *seeds_host, const int32_t *noise, int32_t keep_seeds, sealhip_kswitch_key **keys,
+                          bool switching = false, const uint64_t *s_from = nullptr, uint32_t level = 0)
 {
     REQUIRE_PTR(ctx);
     REQUIRE_PTR(sk_ntt);
+    if (switching && n_keys)
+        REQUIRE_PTR(s_from);
     if (n_keys)
     {
         if (galois)
@@ -3816,6 +3877,12 @@ static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const ui
         }
         else if (n_keys > 14) // SEAL_CIPHERTEXT_SIZE_MAX - 2, :152-155
             throw std::invalid_argument("invalid count");
+        if (switching)
+        {
+            check_data_level(h, level);
+            if (keep_seeds && static_cast<int>(level) < h.k_first)
+                throw std::invalid_argument("a key limited to a level keeps no seeds: a seed gives back the rows it leaves out");
+        }
         // (using_keyswitching, :327-330, holds for every context: sealhip_context_create refuses a single prime)
         Engine &e = device_engine(ctx);
         if (n_keys == 0)
@@ -3838,6 +3905,7 @@ static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const ui
                 made[i] = std::make_unique<sealhip_kswitch_key>();
                 made[i]->key.n_digits = digits;
                 made[i]->key.words = words;
+                made[i]->key.level = switching && static_cast<int>(level) < e.k_first ? level : 0;
                 SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&made[i]->key.d_data), words * sizeof(u64)));
                 data[i] = made[i]->key.d_data;
                 // (save_seed is dropped below n_key x N = 9 words, rlwe.cpp:225-230: every context has at least 2 x 8)
@@ -3845,7 +3913,7 @@ static long generate_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const ui
                     made[i]->key.seeds.assign(seeds_host + i * digits * 8, seeds_host + (i + 1) * digits * 8);
             }
             op_generate_kswitch_keys(e, reinterpret_cast<const u64 *>(sk_ntt), galois ? elts : nullptr, n_keys, seeds_host,
-                                     noise, data.data());
+                                     noise, data.data(), reinterpret_cast<const u64 *>(s_from), static_cast<int>(level));
             e.sync_and_check();
         }
         catch (...)
@@ -3870,6 +3938,13 @@ long sealhip_generate_galois_keys(sealhip_context *ctx, const uint64_t *sk_ntt, 
                                   sealhip_kswitch_key **keys)
 {
     return generate_keys(ctx, sk_ntt, galois_elts, true, n_elts, seeds_host, noise, keep_seeds, keys);
+}
+
+long sealhip_generate_switching_keys(sealhip_context *ctx, const uint64_t *sk_to_ntt, const uint64_t *sk_from_ntt,
+                                     uint32_t n_keys, uint32_t level, const uint64_t *seeds_host, const int32_t *noise,
+                                     int32_t keep_seeds, sealhip_kswitch_key **keys)
+{
+    return generate_keys(ctx, sk_to_ntt, nullptr, false, n_keys, seeds_host, noise, keep_seeds, keys, true, sk_from_ntt, level);
 }
 
 long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots,
@@ -3979,7 +4054,76 @@ long sealhip_generate_secret_key(sealhip_context *ctx, const uint64_t seed_host[
     REQUIRE_PTR(sk_ntt_device);
     return guarded([&] {
         Engine &e = device_engine(ctx);
-        op_generate_secret_key(e, seed_host, reinterpret_cast<u64 *>(sk_ntt_device));
+        op_generate_secret_key(e, seed_host, 0, reinterpret_cast<u64 *>(sk_ntt_device));
+    });
+}
+
+/* ---------------------------------------------------------------- fixed-weight secrets */
+// the argument rules the fixed-weight entries share; returns the item stride
+static std::size_t check_fixed_weight_args(const Engine &h, uint32_t weight, size_t item_stride_words)
+{
+    if (weight < 1 || weight > h.n)
+        throw std::invalid_argument("h must be 1 .. N");
+    return check_sample_args(h, 1, 0, item_stride_words);
+}
+
+long sealhip_sample_fixed_weight(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t h, int32_t *out_device,
+                                 size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(out_device);
+    return guarded([&] {
+        const std::size_t stride = check_fixed_weight_args(*ctx->engine, h, item_stride_words);
+        if ((stride & 3) || (reinterpret_cast<std::uintptr_t>(out_device) & 15))
+            throw std::invalid_argument("out_device must be 16-byte aligned and the item stride a multiple of 4");
+        Engine &e = device_engine(ctx);
+        op_sample_fixed_weight(e, seeds_host, count, h, out_device, stride);
+    });
+}
+
+long sealhip_sample_fixed_weight_host(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t h,
+                                      int32_t *out_host, size_t item_stride_words)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seeds_host);
+    REQUIRE_PTR(out_host);
+    return guarded([&] {
+        Engine &e = *ctx->engine; // host work: also on host-only contexts
+        const std::size_t stride = check_fixed_weight_args(e, h, item_stride_words);
+        for (size_t i = 0; i < count; i++)
+        {
+            uint64_t seed[8];
+            std::memcpy(seed, seeds_host + 8 * i, sizeof(seed));
+            sample_fixed_weight_host(seed, e.n, h, out_host + i * stride);
+        }
+    });
+}
+
+long sealhip_debug_fixed_weight_map(sealhip_context *ctx, const uint64_t *words_device, size_t n_polys, uint32_t h,
+                                    int32_t *out_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(words_device);
+    REQUIRE_PTR(out_device);
+    return guarded([&] {
+        (void)check_fixed_weight_args(*ctx->engine, h, 0);
+        if ((reinterpret_cast<std::uintptr_t>(words_device) | reinterpret_cast<std::uintptr_t>(out_device)) & 15)
+            throw std::invalid_argument("words_device and out_device must be 16-byte aligned");
+        Engine &e = device_engine(ctx);
+        op_debug_fixed_weight_map(e, reinterpret_cast<const u64 *>(words_device), n_polys, h, out_device);
+    });
+}
+
+long sealhip_generate_sparse_secret_key(sealhip_context *ctx, const uint64_t seed_host[8], uint32_t h, uint64_t *sk_ntt_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(seed_host);
+    REQUIRE_PTR(sk_ntt_device);
+    return guarded([&] {
+        (void)check_fixed_weight_args(*ctx->engine, h, 0);
+        Engine &e = device_engine(ctx);
+        op_generate_secret_key(e, seed_host, h, reinterpret_cast<u64 *>(sk_ntt_device));
     });
 }
 

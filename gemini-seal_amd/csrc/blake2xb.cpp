@@ -6,7 +6,10 @@
 #include "blake2xb.hpp"
 #include "sample_map.hpp"
 
+#include <algorithm>
 #include <cstring>
+#include <numeric>
+#include <vector>
 
 namespace sealhip
 {
@@ -209,24 +212,46 @@ namespace sealhip
             }
         }
     }
+    namespace
+    {
+        // f(m, w) for the stream words m < total of BlakePRNG(seed): word m & 511 of buffer m >> 9
+        template <class F>
+        void for_stream_words(const std::uint64_t (&seed)[8], std::size_t total, F f)
+        {
+            unsigned char key[64], buffer[4096];
+            for (int i = 0; i < 8; i++)
+                for (int b = 0; b < 8; b++)
+                    key[8 * i + b] = static_cast<unsigned char>(seed[i] >> (8 * b));
+            for (std::size_t m = 0; m < total; m++)
+            {
+                if ((m & 511) == 0)
+                {
+                    unsigned char ctr[8];
+                    for (int i = 0; i < 8; i++)
+                        ctr[i] = static_cast<unsigned char>((m >> 9) >> (8 * i));
+                    (void)blake2xb(buffer, sizeof(buffer), ctr, sizeof(ctr), key, sizeof(key));
+                }
+                f(m, load64(buffer + 8 * (m & 511)));
+            }
+        }
+    } // namespace
+
     void sample_polys_host(const std::uint64_t (&seed)[8], std::size_t n, unsigned n_ternary, unsigned n_noise, std::int32_t *out)
     {
-        unsigned char key[64], buffer[4096];
-        for (int i = 0; i < 8; i++)
-            for (int b = 0; b < 8; b++)
-                key[8 * i + b] = static_cast<unsigned char>(seed[i] >> (8 * b));
-        const std::size_t total = static_cast<std::size_t>(n_ternary + n_noise) * n;
-        for (std::size_t m = 0; m < total; m++) // stream word m: word m & 511 of buffer m >> 9
-        {
-            if ((m & 511) == 0)
-            {
-                unsigned char ctr[8];
-                for (int i = 0; i < 8; i++)
-                    ctr[i] = static_cast<unsigned char>((m >> 9) >> (8 * i));
-                (void)blake2xb(buffer, sizeof(buffer), ctr, sizeof(ctr), key, sizeof(key));
-            }
-            const std::uint64_t w = load64(buffer + 8 * (m & 511));
+        for_stream_words(seed, static_cast<std::size_t>(n_ternary + n_noise) * n, [&](std::size_t m, std::uint64_t w) {
             out[m] = m / n < n_ternary ? sample_ternary(w) : sample_noise(w);
-        }
+        });
+    }
+
+    void sample_fixed_weight_host(const std::uint64_t (&seed)[8], std::size_t n, std::size_t h, std::int32_t *out)
+    {
+        std::vector<std::uint64_t> w(n);
+        for_stream_words(seed, n, [&](std::size_t m, std::uint64_t v) { w[m] = v; });
+        std::vector<std::uint32_t> order(n);
+        std::iota(order.begin(), order.end(), 0u);
+        std::stable_sort(order.begin(), order.end(), [&](std::uint32_t a, std::uint32_t b) { return w[a] < w[b]; });
+        std::fill(out, out + n, 0);
+        for (std::size_t r = 0; r < h && r < n; r++) // order[r] has rank r
+            out[order[r]] = (w[order[r]] & 1) ? -1 : 1;
     }
 } // namespace sealhip

@@ -30,4 +30,9 @@ namespace sealhip
     // The library's RLWE sampling rule on the host (sample_map.hpp): out[p][n] for the n_ternary ternary
     // and then n_noise noise polynomials of one item; coefficient j of polynomial p comes from word pn + j of BlakePRNG(seed)
     void sample_polys_host(const std::uint64_t (&seed)[8], std::size_t n, unsigned n_ternary, unsigned n_noise, std::int32_t *out);
+
+    // The fixed-weight rule on the host: out[n] of weight h (1 .. n) from words [0, n) of
+    // BlakePRNG(seed): rank_i = #{ j : w_j < w_i, or w_j == w_i and j < i }; coefficient i is 0 when rank_i >= h, else -1 when
+    // w_i & 1, else +1. A stable sort here (the device counts ranks in constant time; this restatement does not try to).
+    void sample_fixed_weight_host(const std::uint64_t (&seed)[8], std::size_t n, std::size_t h, std::int32_t *out);
 } // namespace sealhip

@@ -244,6 +244,9 @@ namespace sealhip
         // keys made with save_seed (sealhip_generate_*_keys): the seed of c_1 of every digit, 8 words each (host memory);
         // empty otherwise. What the seeded save writes in place of c_1 (ciphertext.cpp:189-208).
         std::vector<std::uint64_t> seeds;
+        // sealhip_generate_switching_keys with level < n_ct: the data-prime rows r >= level of every digit and the digits
+        // j >= ceil(level / nsp) are zero, so the key serves key switches at levels <= level only. 0: a full key.
+        std::uint32_t level = 0;
     };
 
     // Optional per-launch timing with HIP events on the launch stream (bench.py's roofline line).
@@ -1125,10 +1128,18 @@ namespace sealhip
     const DftTables &bootstrap_tables_s2c(const BootstrapTables &t);
     std::size_t bootstrap_temp_words(std::uint32_t k_top, const dftplan::Plan &c2s, const evalmod::Plan &em, std::size_t N);
     // ct[count][2][k_in][N] -> out[count][2][s2c out level][N]: mod_raise to k_top, coeffs_to_slots, eval_mod ONCE over the
-    // 2 count real and imaginary halves, slots_to_coeffs
+    // 2 count real and imaginary halves, slots_to_coeffs. With to_sparse and to_dense (both or neither; DESIGN.md section
+    // 25) only the raise runs under the sparse secret: the q_0 rows are switched with to_sparse at level 1, raised, and
+    // switched back with to_dense at k_top; the rest is the same code.
     void op_bootstrap(Engine &e, const BootstrapTables &t, int k_in, const u64 *ct, std::size_t count,
                       const std::vector<DftStageKeys> &c2s_keys, const KSwitchKey &conj_key,
-                      const std::vector<DftStageKeys> &s2c_keys, const KSwitchKey &relin_key, u64 *out);
+                      const std::vector<DftStageKeys> &s2c_keys, const KSwitchKey &relin_key, u64 *out,
+                      const KSwitchKey *to_sparse = nullptr, const KSwitchKey *to_dense = nullptr);
+    // out[count][2][k][N] = (c_0, 0) + switch_key(c_1): a ciphertext under the key's source secret becomes one under its
+    // target secret. c0 and c1 are k rows each (NTT form for CKKS, coefficient form for BFV, as op_switch_key's target),
+    // `stride` words from one item to the next; out must not overlap them.
+    void op_switch_secret(Engine &e, int k, const u64 *c0, const u64 *c1, std::size_t stride, std::size_t count,
+                          const KSwitchKey &key, u64 *out);
 
     // ---- Decryptor (decrypt.hip, pipeline.cpp) ----
     // bits_out[i] = max(bits_out[i], bits of the largest centred |t v| of item i), v = count x k x N dot products
@@ -1165,8 +1176,16 @@ namespace sealhip
     // the kernels' map functions on n caller-supplied words (device)
     void op_debug_sample_map(Engine &e, const u64 *words, std::size_t n, bool noise, std::int32_t *out);
     // KeyGenerator::generate_sk (keygenerator.cpp:66-103): one ternary polynomial from the seed, lifted over the n_key key
-    // primes and transformed; sk_ntt = n_key x N words. The coefficient-form scratch is erased.
-    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, u64 *sk_ntt);
+    // primes and transformed; sk_ntt = n_key x N words. The coefficient-form scratch is erased. h > 0: the fixed-weight
+    // polynomial of weight h in place of the ternary one.
+    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, unsigned h, u64 *sk_ntt);
+    // Fixed-weight polynomials: out + i * item_stride receives the N int32 coefficients of weight
+    // h (1 .. N) for seed i, from the first N stream words of BlakePRNG(seed i) -- the h smallest words are the support, bit 0
+    // the sign. Pointer and stride rules, staging and erasure as op_sample_polys; the raw-word scratch is erased too.
+    void op_sample_fixed_weight(Engine &e, const std::uint64_t *seeds_host, std::size_t count, unsigned h, std::int32_t *out,
+                                std::size_t item_stride);
+    // the rank kernel itself on caller-supplied words[n_polys][N] (device) -> out[n_polys][N]
+    void op_debug_fixed_weight_map(Engine &e, const u64 *words, std::size_t n_polys, unsigned h, std::int32_t *out);
 
     // ---- KeyGenerator::generate_one_kswitch_key for a batch of keys (keygen.hip, composition in pipeline.cpp) ----
     constexpr int kKeygenMaxKeys = 32; // keys per assemble launch (kernel-argument table)
@@ -1183,8 +1202,12 @@ namespace sealhip
     // Key i (key_data[i]: digits x 2 x n_key x N words of device memory) for the new key apply_galois_ntt(sk, elts[i]), or,
     // with elts == nullptr, sk^(i+2) (relin_keys, keygenerator.cpp:146-175). seeds_host: n_keys x digits x 8 words (the
     // seeds of c_1), noise: n_keys x digits x N small signed samples (device). Stream-ordered on the calling thread's lane.
+    // s_from (n_keys x n_key x N, NTT form, with elts == nullptr): the new key of key i handed in -- a switching key from
+    // that secret to sk_ntt's; then `level` < n_ct zero-fills, in both components, the data-prime rows r >= level of every
+    // digit and every digit j >= ceil(level / nsp) once the keys are assembled.
     void op_generate_kswitch_keys(Engine &e, const u64 *sk_ntt, const std::uint32_t *elts, std::size_t n_keys,
-                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data);
+                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data,
+                                  const u64 *s_from = nullptr, int level = 0);
     // The chunk loop of every operation that needs arena temporaries per item (pipeline.cpp): as many items per chunk as
     // the lane's arena holds at `bytes_per_item` (the padded sum over the item's `n_buffers` temporaries), one
     // (count, chunk) entry in Lane::chunk_log, then body(off, m) for the m items from item `off` with the arena reset.

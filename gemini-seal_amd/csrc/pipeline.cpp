@@ -507,7 +507,7 @@ namespace sealhip
         const KsDev &h = lt.h_ks;
         const bool finish = split && split->partial_sum;   // latency mode, after the all-reduce
         const bool partial = split && split->partial_out;  // latency mode, before it
-        if (!finish && static_cast<int>(key.n_digits) < h.nd)
+        if (!finish && (static_cast<int>(key.n_digits) < h.nd || (key.level && k > static_cast<int>(key.level))))
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         const int dj0 = partial ? split->j0 : 0, dj1 = partial ? split->j1 : h.nd;
         if (dj0 < 0 || dj0 > dj1 || dj1 > h.nd)
@@ -537,6 +537,14 @@ namespace sealhip
                 return; // the reduced partial products leave here (all-reduce, then op_switch_key with partial_sum)
             ks_finish(e, lt, k, prod, temp, ctp, ct_stride, c0p, c0_stride, m, sink_at(e, off));
         });
+    }
+
+    // The plain re-encryption under another secret: as op_apply_galois without the automorphism, the
+    // key switch's last kernel writes (c_0 + r_0, r_1) straight into `out`.
+    void op_switch_secret(Engine &e, int k, const u64 *c0, const u64 *c1, std::size_t stride, std::size_t count,
+                          const KSwitchKey &key, u64 *out)
+    {
+        op_switch_key(e, k, out, 2 * static_cast<std::size_t>(k) * e.n, c1, stride, count, key, c0, stride);
     }
 
     // relinearize + rescale_to_next in one call: op_switch_key's front half, then the merged finish
@@ -1916,7 +1924,8 @@ namespace sealhip
     // The new key is read through the Galois permutation inside the kernel (no rotated secret key is stored); the relin
     // keys' powers sk^2.. are built once by dyadic products (compute_secret_key_array, :262-323).
     void op_generate_kswitch_keys(Engine &e, const u64 *sk_ntt, const std::uint32_t *elts, std::size_t n_keys,
-                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data)
+                                  const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *const *key_data,
+                                  const u64 *s_from, int level)
     {
         if (n_keys == 0)
             return;
@@ -1935,7 +1944,7 @@ namespace sealhip
 
         hipError_t err = hipSuccess;
         u64 *powers = nullptr; // relin keys: sk^2 .. sk^(n_keys+1), in the lane's arena (free again once expansion is enqueued)
-        if (!elts)
+        if (!elts && !s_from)
         {
             e.ws_reset();
             e.ws_reserve(e.lane().ws_floor + n_keys * poly * sizeof(u64) + 256);
@@ -1964,12 +1973,28 @@ namespace sealhip
             for (int i = 0; i < g.n_keys; i++)
             {
                 g.key[i] = key_data[off + i];
-                g.s_new[i] = elts ? sk_ntt : powers + (off + i) * poly;
+                g.s_new[i] = elts ? sk_ntt : (s_from ? s_from : powers) + (off + i) * poly;
                 g.elt[i] = elts ? elts[off + i] : 1u;
             }
             err = launch_keygen_assemble(e, g);
         }
         check(err, "kswitch_keygen_assemble");
+        if (s_from && level > 0 && level < e.k_first)
+        {
+            // what a key for levels <= level never shows: rows level .. n_ct-1 of both components of the digits it keeps,
+            // and the digits past ceil(level / nsp) whole
+            const int kept = (level + e.nsp - 1) / e.nsp;
+            hipStream_t stream = e.lane().stream;
+            for (std::size_t i = 0; i < n_keys; i++)
+            {
+                for (int c = 0; c < 2 * kept; c++)
+                    SEALHIP_CHECK(hipMemsetAsync(key_data[i] + (static_cast<std::size_t>(c) * nk + level) * N, 0,
+                                                 static_cast<std::size_t>(e.k_first - level) * N * sizeof(u64), stream));
+                if (kept < digits)
+                    SEALHIP_CHECK(hipMemsetAsync(key_data[i] + kept * digit_words, 0, (digits - kept) * digit_words * sizeof(u64),
+                                                 stream));
+            }
+        }
     }
 
     void op_encrypt_zero_asymmetric(Engine &e, int rows, bool is_ntt_form, const u64 *pk, const std::int32_t *u,

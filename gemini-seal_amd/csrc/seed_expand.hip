@@ -11,7 +11,8 @@
 // needs beyond the provision, so the result is exact for every seed, not only for those whose rejections fit the slack.
 // The same PRNG also feeds the RLWE samplers (DESIGN.md "RLWE samples on the device from seeds"): phases A.0 and A.1, then
 // sample_leaf_kernel maps every raw stream word to one ternary or noise sample (sample_map.hpp) -- fixed consumption, so
-// there is no candidate arena and no phase B.
+// there is no candidate arena and no phase B. The fixed-weight sampler takes the same leaves raw and
+// ranks an item's N words against each other (fixed_weight_rank_kernel): the h smallest are the support.
 #include "engine.hpp"
 #include "sample_map.hpp"
 
@@ -322,11 +323,14 @@ namespace sealhip
             // (16-byte aligned, strides multiples of 4); one array out[i][p][N] has out_noise = out + n_ternary N
             std::int32_t *out, *out_noise;
             std::size_t stride, stride_noise;
+            u64 *raw; // the raw variant: item s's stream words themselves at raw + s N (16-byte aligned)
         };
 
         // One lane per leaf, one wave per buffer (so H0 is a scalar load): the leaf's 8 words mapped by the kind of its
         // polynomial (N >= 8: a leaf lies in one polynomial) and written with two 16-byte stores. Lanes past the item's
-        // last leaf write nothing.
+        // last leaf write nothing. kRaw: the words themselves, unmapped, with four 16-byte stores (the fixed-weight sampler
+        // ranks them).
+        template <bool kRaw>
         __global__ __launch_bounds__(kGenThreads) void sample_leaf_kernel(const u64 *__restrict__ h0, const SampleArgs a,
                                                                          unsigned total_bufs)
         {
@@ -342,6 +346,15 @@ namespace sealhip
             for (int i = 0; i < 8; i++)
                 h[i] = h0[static_cast<std::size_t>(bi) * 8 + i];
             leaf_words(h, lane, w);
+            if (kRaw)
+            {
+                ulonglong2 *raw = reinterpret_cast<ulonglong2 *>(a.raw + (static_cast<std::size_t>(s) << a.logn) +
+                                                                 static_cast<std::size_t>(leaf) * 8);
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    raw[i] = make_ulonglong2(w[2 * i], w[2 * i + 1]);
+                return;
+            }
             std::int32_t v[8];
             int4 *dst;
             const unsigned ternary_leaves = a.n_ternary << (a.logn - 3);
@@ -372,6 +385,88 @@ namespace sealhip
             if (i < n)
                 out[i] = noise ? sample_noise(words[i]) : sample_ternary(words[i]);
         }
+
+        // ---------------------------------------------------------------- fixed-weight polynomials
+        // rank_i = #{ j : w_j < w_i, or w_j == w_i and j < i } over a polynomial's N words; coefficient i is 0 when
+        // rank_i >= h, else -1 when w_i & 1, else +1. A workgroup owns kRankTile consecutive words, a lane kRankOwn
+        // consecutive ones in registers, and walks all N words tile by tile through LDS: every lane reads the same LDS
+        // address per step (a broadcast: no bank conflict), and one read feeds kRankOwn 64-bit compares. Constant time in
+        // sample_map.hpp's sense: every loop bound, branch, address and LDS index is a function of N, h and the lane's
+        // position; a word only ever enters compares whose results are added, and the select at the end is a mask.
+        constexpr int kRankThreads = 256, kRankOwn = 4;
+        constexpr unsigned kRankTile = kRankThreads * kRankOwn; // words per workgroup = words per LDS tile (8 KiB)
+
+        // kTie: 0 the tile lies before the workgroup's own words (every j < i: count w_j <= w_i), 1 it is the own tile
+        // (the full rule), 2 it lies after (every j > i: count w_j < w_i). The tile's position is public.
+        template <int kTie>
+        __device__ __forceinline__ void rank_tile(const u64 *tile, unsigned len, unsigned j0, unsigned i0, const u64 (&w)[kRankOwn],
+                                                  unsigned (&rank)[kRankOwn])
+        {
+#pragma unroll 8
+            for (unsigned jj = 0; jj < len; jj++) // len is a multiple of 8
+            {
+                const u64 x = tile[jj];
+#pragma unroll
+                for (int r = 0; r < kRankOwn; r++)
+                {
+                    if (kTie == 0)
+                        rank[r] += static_cast<unsigned>(x <= w[r]);
+                    else if (kTie == 2)
+                        rank[r] += static_cast<unsigned>(x < w[r]);
+                    else
+                        rank[r] += static_cast<unsigned>(x < w[r]) |
+                                   (static_cast<unsigned>(x == w[r]) & static_cast<unsigned>(j0 + jj < i0 + r));
+                }
+            }
+        }
+
+        // grid (ceil(N / kRankTile), polynomials); words[p][N] -> out + p * stride, N int32 each (16-byte stores). N is a
+        // power of two >= 8, so a lane's kRankOwn words lie inside the polynomial or all outside it; lanes outside still
+        // stage and synchronise, with zeros for own words, and store nothing.
+        __global__ __launch_bounds__(kRankThreads) void fixed_weight_rank_kernel(const u64 *__restrict__ words, unsigned logn,
+                                                                                unsigned h, std::int32_t *__restrict__ out,
+                                                                                std::size_t stride)
+        {
+            __shared__ __attribute__((aligned(16))) u64 s_tile[kRankTile];
+            const unsigned N = 1u << logn, tid = threadIdx.x, n_tiles = (N + kRankTile - 1) / kRankTile;
+            const u64 *poly = words + (static_cast<std::size_t>(blockIdx.y) << logn);
+            const unsigned i0 = blockIdx.x * kRankTile + tid * kRankOwn;
+            const bool mine = i0 < N;
+            u64 w[kRankOwn] = {};
+            unsigned rank[kRankOwn] = {};
+            if (mine)
+            {
+                const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(poly + i0),
+                                 b = *reinterpret_cast<const ulonglong2 *>(poly + i0 + 2);
+                w[0] = a.x, w[1] = a.y, w[2] = b.x, w[3] = b.y;
+            }
+            for (unsigned t = 0; t < n_tiles; t++)
+            {
+                const unsigned j0 = t * kRankTile, len = N - j0 < kRankTile ? N - j0 : kRankTile, mj = tid * kRankOwn;
+                if (mj < len)
+                {
+                    *reinterpret_cast<ulonglong2 *>(s_tile + mj) = *reinterpret_cast<const ulonglong2 *>(poly + j0 + mj);
+                    *reinterpret_cast<ulonglong2 *>(s_tile + mj + 2) = *reinterpret_cast<const ulonglong2 *>(poly + j0 + mj + 2);
+                }
+                __syncthreads();
+                if (t < blockIdx.x)
+                    rank_tile<0>(s_tile, len, j0, i0, w, rank);
+                else if (t == blockIdx.x)
+                    rank_tile<1>(s_tile, len, j0, i0, w, rank);
+                else
+                    rank_tile<2>(s_tile, len, j0, i0, w, rank);
+                __syncthreads(); // the next tile overwrites s_tile
+            }
+            if (mine)
+            {
+                std::int32_t v[kRankOwn];
+#pragma unroll
+                for (int r = 0; r < kRankOwn; r++) // +1 or -1 by bit 0, masked to 0 outside the support
+                    v[r] = (1 - 2 * static_cast<std::int32_t>(w[r] & 1)) & -static_cast<std::int32_t>(rank[r] < h);
+                *reinterpret_cast<int4 *>(out + static_cast<std::size_t>(blockIdx.y) * stride + i0) = make_int4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        static_assert(kRankOwn == 4, "a lane loads its words as two 16-byte pairs and stores one int4");
 
         // KeyGenerator::generate_sk's lift (keygenerator.cpp:78-84): row j of the key is the ternary polynomial mod q_j
         struct LiftArgs
@@ -457,8 +552,11 @@ namespace sealhip
             roots_of_chunk(e, off, m, a.nbuf, rec, ks, h0);
             {
                 ProfScope prof(e, "sample_leaf", static_cast<double>(m) * a.leaves);
-                sample_leaf_kernel<<<static_cast<unsigned>((nroots * 64 + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
-                    h0, a, static_cast<unsigned>(nroots));
+                const unsigned grid = static_cast<unsigned>((nroots * 64 + kGenThreads - 1) / kGenThreads);
+                if (a.raw)
+                    sample_leaf_kernel<true><<<grid, kGenThreads, 0, l.stream>>>(h0, a, static_cast<unsigned>(nroots));
+                else
+                    sample_leaf_kernel<false><<<grid, kGenThreads, 0, l.stream>>>(h0, a, static_cast<unsigned>(nroots));
                 check(hipGetLastError(), "sample_leaf");
             }
             SEALHIP_CHECK(hipMemsetAsync(h0, 0, nroots * 64, l.stream));
@@ -469,6 +567,39 @@ namespace sealhip
         std::size_t sample_item_bytes(const SampleArgs &a)
         {
             return (static_cast<std::size_t>(a.nbuf) * 8 + 8 + 9) * 8;
+        }
+
+        hipError_t launch_fixed_weight_rank(const Engine &e, const u64 *words, std::size_t n_polys, unsigned h, std::int32_t *out,
+                                            std::size_t stride)
+        {
+            // N^2 compares per polynomial
+            ProfScope prof(e, "fixed_weight_rank", static_cast<double>(n_polys) * static_cast<double>(e.n) * static_cast<double>(e.n));
+            constexpr std::size_t max_polys = 65535; // grid.y
+            for (std::size_t p = 0; p < n_polys; p += max_polys)
+            {
+                const dim3 grid(static_cast<unsigned>((e.n + kRankTile - 1) / kRankTile),
+                                static_cast<unsigned>(std::min(max_polys, n_polys - p)));
+                fixed_weight_rank_kernel<<<grid, kRankThreads, 0, e.lane().stream>>>(words + p * e.n, static_cast<unsigned>(e.logn),
+                                                                                    h, out + p * stride, stride);
+            }
+            return hipGetLastError();
+        }
+
+        // One chunk of fixed-weight polynomials inside a for_chunks body: the m staged seeds' first N stream words raw into
+        // arena scratch (sample_chunk's steps with the raw leaf kernel), ranked into out + i * stride; the scratch is erased
+        // like the roots. `a` = sample_args(e, 1, 0): the words ternary polynomial 0 would consume.
+        void fixed_weight_chunk(Engine &e, std::size_t off, std::size_t m, SampleArgs a, unsigned h, std::int32_t *out,
+                                std::size_t stride)
+        {
+            u64 *words = e.ws_alloc(m * e.n);
+            a.raw = words;
+            sample_chunk(e, off, m, a);
+            check(launch_fixed_weight_rank(e, words, m, h, out, stride), "fixed_weight_rank");
+            SEALHIP_CHECK(hipMemsetAsync(words, 0, m * e.n * sizeof(u64), e.lane().stream));
+        }
+        std::size_t fixed_weight_item_bytes(const Engine &e, const SampleArgs &a)
+        {
+            return sample_item_bytes(a) + e.n * sizeof(u64);
         }
 
         SampleArgs sample_args(const Engine &e, unsigned n_ternary, unsigned n_noise)
@@ -587,7 +718,32 @@ namespace sealhip
         check(hipGetLastError(), "sample_map");
     }
 
-    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, u64 *sk_ntt)
+    void op_sample_fixed_weight(Engine &e, const std::uint64_t *seeds_host, std::size_t count, unsigned h, std::int32_t *out,
+                                std::size_t item_stride)
+    {
+        const SampleArgs a = sample_args(e, 1, 0);
+        if (count == 0)
+            return;
+        if (count > 0xFFFFFFFFull / 64 / a.nbuf)
+            throw std::invalid_argument("sampling: too many leaves in one call");
+        Lane &l = e.lane();
+        if (l.capturing)
+            throw std::logic_error("sampling stages its seeds on the host: it cannot be captured in a graph");
+        stage_seeds(l, seeds_host, count);
+        for_chunks(e, count, fixed_weight_item_bytes(e, a), 4, [&](std::size_t off, std::size_t m) {
+            fixed_weight_chunk(e, off, m, a, h, out + off * item_stride, item_stride);
+        });
+        SEALHIP_CHECK(hipEventRecord(l.seed_pin_done, l.stream));
+    }
+
+    void op_debug_fixed_weight_map(Engine &e, const u64 *words, std::size_t n_polys, unsigned h, std::int32_t *out)
+    {
+        if (n_polys == 0)
+            return;
+        check(launch_fixed_weight_rank(e, words, n_polys, h, out, e.n), "fixed_weight_rank");
+    }
+
+    void op_generate_secret_key(Engine &e, const std::uint64_t *seed_host, unsigned h, u64 *sk_ntt)
     {
         SampleArgs a = sample_args(e, 1, 0);
         Lane &l = e.lane();
@@ -600,11 +756,15 @@ namespace sealhip
             la.q[j] = e.key_moduli[j];
         stage_seeds(l, seed_host, 1);
         const std::size_t t_words = (e.n + 1) / 2, total = static_cast<std::size_t>(e.n_key) * e.n;
-        for_chunks(e, 1, sample_item_bytes(a) + t_words * 8, 4, [&](std::size_t off, std::size_t m) {
+        for_chunks(e, 1, (h ? fixed_weight_item_bytes(e, a) : sample_item_bytes(a)) + t_words * 8, h ? 5 : 4,
+                   [&](std::size_t off, std::size_t m) {
             std::int32_t *t = reinterpret_cast<std::int32_t *>(e.ws_alloc(t_words));
             a.out = a.out_noise = t;
             a.stride = a.stride_noise = 0;
-            sample_chunk(e, off, m, a);
+            if (h)
+                fixed_weight_chunk(e, off, m, a, h, t, 0);
+            else
+                sample_chunk(e, off, m, a);
             ternary_lift_kernel<<<static_cast<unsigned>((total + kGenThreads - 1) / kGenThreads), kGenThreads, 0, l.stream>>>(
                 t, sk_ntt, la);
             check(hipGetLastError(), "ternary_lift");

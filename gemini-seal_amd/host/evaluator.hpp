@@ -1610,15 +1610,28 @@ namespace sealhip_host
         void bootstrap(const C &encrypted, const Bootstrapper &boot, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                        const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
-            check_bootstrap_operand(encrypted);
-            const sealhip_kswitch_key *relin = first_relin_key(relin_keys);
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            dft_keys(galois_keys, elts, raw);
+            bootstrap_internal(encrypted, boot, galois_keys, relin_keys, nullptr, nullptr, destination);
+        }
+        // The same with ModRaise alone under a sparse secret (sealhip_evaluator_bootstrap_encapsulated):
+        // to_sparse = KeyGenerator(sparse secret).switching_keys(dense secret, 1, 1)[0], to_dense =
+        // KeyGenerator(dense secret).switching_keys(sparse secret, 1)[0]; the operand, the destination and every other key
+        // are under the dense secret
+        template <class C, IfCt<C> = 0>
+        void bootstrap(const C &encrypted, const Bootstrapper &boot, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                       const std::vector<const KSwitchKeys *> &relin_keys, const KSwitchKeys &to_sparse, const KSwitchKeys &to_dense,
+                       C &destination)
+        {
+            bootstrap_internal(encrypted, boot, galois_keys, relin_keys, to_sparse.get(), to_dense.get(), destination);
+        }
+        // Re-encryption under another secret (sealhip_evaluator_switch_secret): destination = (c_0, 0) + switch_key(c_1), the
+        // operand under the key's source secret, the destination under its target secret (KeyGenerator::switching_keys)
+        template <class C, IfCt<C> = 0>
+        void switch_secret(const C &encrypted, const KSwitchKeys &key, C &destination)
+        {
+            check_galois_operand(encrypted);
             const std::size_t k = encrypted.coeff_modulus_size();
-            to_size2(encrypted, 2, boot.out_level(), destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
-                return sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(), raw.data(),
-                                                   std::uint32_t(elts.size()), &relin, 1, o);
+            to_size2(encrypted, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_switch_secret(ctx_.get(), std::uint32_t(k), c, 1, key.get(), o);
             });
         }
 
@@ -2057,6 +2070,28 @@ namespace sealhip_host
             commit(destination, o, 2, k_out);
             if (scale)
                 destination.scale() = *scale;
+        }
+
+        template <class C>
+        void bootstrap_internal(const C &encrypted, const Bootstrapper &boot,
+                                const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                                const std::vector<const KSwitchKeys *> &relin_keys, const sealhip_kswitch_key *to_sparse,
+                                const sealhip_kswitch_key *to_dense, C &destination)
+        {
+            check_bootstrap_operand(encrypted);
+            const sealhip_kswitch_key *relin = first_relin_key(relin_keys);
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            dft_keys(galois_keys, elts, raw);
+            const std::size_t k = encrypted.coeff_modulus_size();
+            to_size2(encrypted, 2, boot.out_level(), destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                if (to_sparse)
+                    return sealhip_evaluator_bootstrap_encapsulated(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(),
+                                                                    raw.data(), std::uint32_t(elts.size()), &relin, 1, to_sparse,
+                                                                    to_dense, o);
+                return sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(), raw.data(),
+                                                   std::uint32_t(elts.size()), &relin, 1, o);
+            });
         }
 
         // relin_keys as relinearize_inplace takes them, of which index 0 is read: required (:793-796), or null without one
@@ -2929,17 +2964,53 @@ namespace sealhip_host
         // n_key x N words of the secret key in NTT form
         static std::vector<std::uint64_t> generate_secret_key(const Context &context, const SeedSource &seeds)
         {
+            return secret_key(context, seeds, 0);
+        }
+        // the same with the fixed-weight polynomial of Hamming weight h, 1 .. N, in place of the ternary one
+        // (sealhip_generate_sparse_secret_key)
+        static std::vector<std::uint64_t> generate_sparse_secret_key(const Context &context, const SeedSource &seeds, std::uint32_t h)
+        {
+            if (h < 1 || h > context.n())
+                throw std::invalid_argument("h must be 1 .. N");
+            return secret_key(context, seeds, h);
+        }
+
+        // Key-switch keys from OTHER secrets to this generator's (sealhip_generate_switching_keys): keys[i] switches what is
+        // encrypted under from_secret_keys_ntt[i] (count x n_key x N words, NTT form) to the secret key this generator was
+        // built with. level 0 or n_ct: the full key; a smaller level: a key for key switches at levels <= level only, which
+        // publishes nothing above it and cannot keep its seeds (encapsulation's dense -> sparse key takes level 1). Samples
+        // are drawn as for relin_keys, key by key, digit by digit.
+        Keys switching_keys(const std::uint64_t *from_secret_keys_ntt, std::size_t count, std::size_t level = 0,
+                            bool save_seed = false)
+        {
+            if (!count || count > 14)
+                throw std::invalid_argument("invalid count");
+            if (!from_secret_keys_ntt)
+                throw std::invalid_argument("from_secret_keys_ntt is null");
+            std::uint32_t k_first = 0;
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            if (level > k_first)
+                throw std::invalid_argument("level k out of range");
+            return generate(nullptr, count, save_seed, from_secret_keys_ntt, level ? level : k_first);
+        }
+
+    private:
+        // h = 0: the ternary polynomial
+        static std::vector<std::uint64_t> secret_key(const Context &context, const SeedSource &seeds, std::uint32_t h)
+        {
             std::uint64_t seed[8];
             seeds(seed);
             const std::size_t words = context.n_key() * context.n();
             ZeroedStaged sk(context, words);
-            throw_on(sealhip_generate_secret_key(context.get(), seed, sk.ptr()));
+            throw_on(h ? sealhip_generate_sparse_secret_key(context.get(), seed, h, sk.ptr())
+                       : sealhip_generate_secret_key(context.get(), seed, sk.ptr()));
             std::fill(seed, seed + 8, 0);
             std::vector<std::uint64_t> out(words);
             sk.down(out.data(), words);
             return out;
         }
 
+    public:
         // relin_keys(count, save_seed) (:146-175): keys[i] is the key of sk^(i+2) (RelinKeys::get_index(i + 2) = i)
         Keys relin_keys(std::size_t count, bool save_seed = false)
         {
@@ -3022,7 +3093,9 @@ namespace sealhip_host
         }
 
     private:
-        Keys generate(const std::uint32_t *elts, std::size_t n_keys, bool save_seed)
+        // from (n_keys x n_key x N, with elts == nullptr): switching keys from those secrets at `level`
+        Keys generate(const std::uint32_t *elts, std::size_t n_keys, bool save_seed, const std::uint64_t *from = nullptr,
+                      std::size_t level = 0)
         {
             Keys out;
             if (!n_keys)
@@ -3039,7 +3112,14 @@ namespace sealhip_host
             to_device(drawn, items, e);
             std::vector<sealhip_kswitch_key *> raw(n_keys, nullptr);
             const auto *en = reinterpret_cast<const std::int32_t *>(e.ptr());
-            if (elts)
+            if (from)
+            {
+                ZeroedStaged other(ctx_, n_keys * nk * n);
+                other.up(from, n_keys * nk * n);
+                throw_on(sealhip_generate_switching_keys(ctx_.get(), sk.ptr(), other.ptr(), std::uint32_t(n_keys),
+                                                         std::uint32_t(level), seeds.data(), en, save_seed ? 1 : 0, raw.data()));
+            }
+            else if (elts)
                 throw_on(sealhip_generate_galois_keys(ctx_.get(), sk.ptr(), elts, std::uint32_t(n_keys), seeds.data(), en,
                                                       save_seed ? 1 : 0, raw.data()));
             else

@@ -250,6 +250,13 @@ SYMBOLS = {
     "sealhip_sample_polys_split": [_vp, _vp, _sz, _u32, _u32, _vp, _vp],
     "sealhip_debug_sample_map": [_vp, _vp, _sz, _i32, _vp],
     "sealhip_generate_secret_key": [_vp, _vp, _vp],
+    "sealhip_sample_fixed_weight": [_vp, _vp, _sz, _u32, _vp, _sz],
+    "sealhip_sample_fixed_weight_host": [_vp, _vp, _sz, _u32, _vp, _sz],
+    "sealhip_debug_fixed_weight_map": [_vp, _vp, _sz, _u32, _vp],
+    "sealhip_generate_sparse_secret_key": [_vp, _vp, _u32, _vp],
+    "sealhip_generate_switching_keys": [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _i32, C.POINTER(_vp)],
+    "sealhip_evaluator_switch_secret": [_vp, _u32, _vp, _sz, _vp, _vp],
+    "sealhip_evaluator_bootstrap_encapsulated": [_vp, _vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, C.POINTER(_vp), _u32, _vp, _vp, _vp],
     "sealhip_memset_zero": [_vp, _vp, _sz],
     "sealhip_ciphertext_load_many": [_vp, _vp, _vp, _sz, _vp, _vp, _sz],
     "sealhip_host_register": [_vp, _vp, _sz],
@@ -857,6 +864,49 @@ class Context:
         _check(lib().sealhip_generate_secret_key(self.handle, seed.ctypes.data, _ptr(out)))
         return out
 
+    # ---- fixed-weight secrets
+    def sample_fixed_weight(self, seeds, h, out, item_stride=0):
+        """sealhip_sample_fixed_weight: seeds = count x 8 words (host); out + i * item_stride int32 words (0: N) receives the
+        N coefficients of weight exactly h for seed i (device): the h smallest of the seed's first N stream words are the
+        support, bit 0 of a word the sign"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        _check(lib().sealhip_sample_fixed_weight(self.handle, seeds.ctypes.data, seeds.shape[0], h, _ptr(out), item_stride))
+
+    def sample_fixed_weight_host(self, seeds, h, item_stride=0):
+        """sealhip_sample_fixed_weight_host: the same words computed on the host; returns int32 [count][item_stride or N]"""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1, 8))
+        out = np.zeros((seeds.shape[0], item_stride if item_stride else self.n), dtype=np.int32)
+        _check(lib().sealhip_sample_fixed_weight_host(self.handle, seeds.ctypes.data, seeds.shape[0], h, out.ctypes.data,
+                                                      item_stride))
+        return out
+
+    def debug_fixed_weight_map(self, words, h):
+        """sealhip_debug_fixed_weight_map: the rank kernel on the given 64-bit words [n_polys][N]; returns int32 of that shape"""
+        words = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).reshape(-1, self.n))
+        src = self.upload(words)
+        dst = self.alloc((words.size + 1) // 2)
+        _check(lib().sealhip_debug_fixed_weight_map(self.handle, _ptr(src), words.shape[0], h, _ptr(dst)))
+        return dst.download().view(np.int32)[: words.size].reshape(words.shape).copy()
+
+    def generate_sparse_secret_key(self, seed, h, out=None):
+        """sealhip_generate_sparse_secret_key: generate_secret_key with the fixed-weight polynomial of weight h"""
+        seed = np.ascontiguousarray(np.asarray(seed, dtype=np.uint64).reshape(8))
+        out = self.alloc(self.n_key * self.n) if out is None else out
+        _check(lib().sealhip_generate_sparse_secret_key(self.handle, seed.ctypes.data, h, _ptr(out)))
+        return out
+
+    def generate_switching_keys(self, sk_to_ntt, sk_from_ntt, n_keys, level, seeds, noise, keep_seeds=False):
+        """sealhip_generate_switching_keys: key i switches what is encrypted under sk_from_ntt[i] (n_keys x n_key x N,
+        device) to sk_to_ntt. level = n_ct: the full key; a smaller level: a key for key switches at levels <= level only
+        (encapsulation's dense -> sparse key takes level 1). Layouts as generate_relin_keys. Returns n_keys KSwitchKeys."""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        out = (C.c_void_p * max(1, n_keys))()
+        _check(lib().sealhip_generate_switching_keys(self.handle, _ptr(sk_to_ntt),
+                                                     _ptr(sk_from_ntt) if sk_from_ntt is not None else None, n_keys, level,
+                                                     seeds.ctypes.data if seeds.size else None,
+                                                     _ptr(noise) if noise is not None else None, 1 if keep_seeds else 0, out))
+        return [KSwitchKeys._adopt(self, out[i]) for i in range(n_keys)]
+
     def memset_zero(self, buf, nbytes):
         """stream-ordered zero fill of device memory (sealhip_memset_zero)"""
         _check(lib().sealhip_memset_zero(self.handle, _ptr(buf), nbytes))
@@ -1354,6 +1404,23 @@ class Evaluator:
         keys, n_relin = _relin_array(relin_keys)
         _check(lib().sealhip_evaluator_bootstrap(self.ctx.handle, tables.handle, k_in, _ptr(ct), count, ea, ka, n_keys, keys,
                                                  n_relin, _ptr(out)))
+
+    # ---- sparse-secret encapsulation
+    def switch_secret(self, ct, k, count, key, out):
+        """Re-encryption under another secret (sealhip_evaluator_switch_secret): out = (c_0, 0) + switch_key(c_1) of the
+        device batch ct count x 2 x k x N; key: a KSwitchKeys of Context.generate_switching_keys."""
+        _check(lib().sealhip_evaluator_switch_secret(self.ctx.handle, k, _ptr(ct), count, key.handle if key is not None else None,
+                                                     _ptr(out)))
+
+    def bootstrap_encapsulated(self, tables, ct, k_in, count, galois_keys, relin_keys, to_sparse, to_dense, out):
+        """bootstrap with ModRaise alone under a sparse secret (sealhip_evaluator_bootstrap_encapsulated): to_sparse the
+        dense -> sparse switching key made with level 1, to_dense the sparse -> dense one at the full level; everything else
+        as bootstrap, under the dense secret."""
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        keys, n_relin = _relin_array(relin_keys)
+        _check(lib().sealhip_evaluator_bootstrap_encapsulated(
+            self.ctx.handle, tables.handle, k_in, _ptr(ct), count, ea, ka, n_keys, keys, n_relin,
+            to_sparse.handle if to_sparse is not None else None, to_dense.handle if to_dense is not None else None, _ptr(out)))
 
     # ---- batches of separately allocated HOST ciphertexts (lists of numpy arrays: what a vector<Ciphertext> is)
     @staticmethod

@@ -743,8 +743,9 @@ long sealhip_evaluator_double_angle(sealhip_context *ctx, uint32_t k, const uint
 
 /* EvalMod, the scaled sine of CKKS bootstrapping (csrc/evalmod_plan.hpp). CKKS only, both modes.
    After ModRaise a coefficient is c = m + q_0 I. K is the caller's bound on I: K >= max|I| + 1, where |I_j| <= (h + 1) / 2
-   for a secret of Hamming weight h (the library does not sample sparse secrets: with its own ternary secrets h is about
-   2 N / 3 and K must be chosen accordingly). For slots holding x = c / (q_0 K) in [-1, 1] at scale `scale`, eval_mod evaluates
+   for a secret of Hamming weight h (sealhip_generate_secret_key does not sample sparse secrets: with its ternary secrets h
+   is about 2 N / 3 and no practical K covers I; sealhip_generate_sparse_secret_key makes a secret of a chosen weight, and
+   sealhip_evaluator_bootstrap_encapsulated runs ModRaise alone under it). For slots holding x = c / (q_0 K) in [-1, 1] at scale `scale`, eval_mod evaluates
    the degree-`degree` Chebyshev interpolant of cos((2 pi K x - pi / 2) / 2^r) with sealhip_evaluator_evaluate_polynomial_ckks'
    pipeline and applies sealhip_evaluator_double_angle r times (0 <= r <= 8): the slots then hold sin(2 pi c / q_0) =
    sin(2 pi m / q_0), which is 2 pi m / q_0 up to the relative error (2 pi m / q_0)^2 / 6 -- |m| / q_0 sets the precision
@@ -794,8 +795,9 @@ long sealhip_evaluator_eval_mod(sealhip_context *ctx, uint32_t k, const uint64_t
        -> eval_mod (K, r, degree, n_baby) ONCE over the 2 count real and imaginary halves, scale_out = S
        -> slots_to_coeffs with gain (double) q_0 / (2 pi s_r), s_r the scale EvalMod ends at.
    The output coefficients are m again, so the result has the caller's scale whatever it was: the bootstrap takes no scale
-   argument. K is the caller's bound on the integer polynomial I of ModRaise, K >= max|I| + 1 (see EvalMod above: the library
-   does not sample sparse secrets, and K grows with the secret's Hamming weight). The relative error of the sine step is
+   argument. K is the caller's bound on the integer polynomial I of ModRaise, K >= max|I| + 1 (see EvalMod above: K grows with
+   the Hamming weight of the secret the raise runs under, which sealhip_evaluator_bootstrap_encapsulated below makes a sparse
+   one of the caller's choice while the working key stays dense). The relative error of the sine step is
    (2 pi m / q_0)^2 / 6: |m| / q_0 sets the precision floor of the result, next to the CKKS noise of the chain.
    sealhip_evaluator_bootstrap_plan: works on host-only contexts. c2s_stages / s2c_stages and their optional n_baby lists are
    sealhip_evaluator_dft_plan's. key_steps as for sealhip_evaluator_dft_plan: the union of both transforms' sorted distinct
@@ -1246,6 +1248,64 @@ long sealhip_debug_sample_map(sealhip_context *ctx, const uint64_t *words_device
    coefficient-form scratch is erased in stream order. null pointers -> E_POINTER; a host-only context ->
    COR_E_INVALIDOPERATION. Stream-ordered on the calling thread's lane; not capturable. */
 long sealhip_generate_secret_key(sealhip_context *ctx, const uint64_t seed_host[8], uint64_t *sk_ntt_device);
+/* ---------------------------------------------------------------- fixed-weight secrets and encapsulation */
+/* The fixed-weight rule (the library's own): the polynomial of weight h, 1 <= h <= N, of seed S is
+     w_i, i < N = stream words [0, N) of BlakePRNG(S), the words sealhip_sample_polys' ternary polynomial 0 would consume;
+     rank_i = #{ j : w_j < w_i, or w_j == w_i and j < i }, a permutation of 0 .. N-1;
+     coefficient i = 0 when rank_i >= h, else -1 when w_i & 1, else +1.
+   The weight is exactly h; consumption is fixed at N words (no rejection, no continuation). The support is the set of the h
+   smallest words: uniform over h-subsets for i.i.d. uniform words, and bit 0 is an independent fair sign unless two words
+   agree in their upper 63 bits, so the statistical distance from (uniform subset x uniform signs) is at most N^2 / 2^64
+   (2^-32 at N = 2^16). The device counts ranks in constant time (every lane compares its words with all N; no branch, loop
+   bound, address or LDS index depends on a word; h and N are public).
+   sealhip_sample_fixed_weight: out_device + i * item_stride_words receives out[i][N] (int32) for seed i. Checks, alignment
+   and stride rules, lane, staging, erasure (the raw-word scratch included), host-only and empty-batch behaviour are
+   sealhip_sample_polys' with one polynomial; h outside 1..N -> E_INVALIDARG.
+   sealhip_sample_fixed_weight_host: the same words computed on the host (works on host-only contexts).
+   sealhip_debug_fixed_weight_map: the rank kernel itself on caller-supplied words_device[n_polys][N] -> out_device[n_polys][N]
+   (both 16-byte aligned), as sealhip_debug_sample_map: the only way to reach ties and the extreme words.
+   sealhip_generate_sparse_secret_key: sealhip_generate_secret_key with the fixed-weight polynomial of weight h in place of the
+   ternary one: the same lift (-1 -> q_j - 1), transform and erasure of the coefficient-form scratch; both schemes. */
+long sealhip_sample_fixed_weight(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t h, int32_t *out_device,
+                                 size_t item_stride_words);
+long sealhip_sample_fixed_weight_host(sealhip_context *ctx, const uint64_t *seeds_host, size_t count, uint32_t h,
+                                      int32_t *out_host, size_t item_stride_words);
+long sealhip_debug_fixed_weight_map(sealhip_context *ctx, const uint64_t *words_device, size_t n_polys, uint32_t h,
+                                    int32_t *out_device);
+long sealhip_generate_sparse_secret_key(sealhip_context *ctx, const uint64_t seed_host[8], uint32_t h, uint64_t *sk_ntt_device);
+/* Key-switch keys from one secret to ANOTHER: generate_one_kswitch_key with the new key handed in. keys[i] switches what is
+   encrypted under sk_from_ntt[i] (n_keys x n_key x N, NTT form, device) to sk_to_ntt; no Galois element, no power of sk.
+   seeds_host, noise, keep_seeds, the checks, errors, lane and synchronisation are sealhip_generate_relin_keys'; the handles are
+   ordinary key-switch keys. level, 1 <= level <= n_ct (else E_INVALIDARG): n_ct gives the full key; a smaller level
+   zero-fills, in both components, the data-prime rows r >= level of every digit and every digit j >= ceil(level / nsp). The
+   key then serves key switches at levels <= level only (above it every entry answers E_INVALIDARG, "kswitch_keys is not
+   valid for encryption parameters"), and cannot keep seeds (keep_seeds -> E_INVALIDARG: a seed gives back the c_1 rows
+   left out). Encapsulation makes its dense -> sparse key with level = 1: an encryption under the sparse secret is then
+   published modulo q_0 times the special primes only, not modulo the whole key modulus, where a sparse secret has the
+   least margin. */
+long sealhip_generate_switching_keys(sealhip_context *ctx, const uint64_t *sk_to_ntt, const uint64_t *sk_from_ntt,
+                                     uint32_t n_keys, uint32_t level, const uint64_t *seeds_host, const int32_t *noise,
+                                     int32_t keep_seeds, sealhip_kswitch_key **keys);
+/* Re-encryption under another secret: out[count][2][k][N] = (c_0, 0) + switch_key(c_1) of ct[count][2][k][N] -- the words of
+   sealhip_switch_key_inplace on a copy of ct whose c_1 is zeroed, with target c_1. A size-2 ciphertext under the key's
+   source secret becomes one under its target secret. Both schemes (CKKS in NTT form, BFV in coefficient form), both modes.
+   Checks before any device work: null pointers -> E_POINTER; k outside 1..n_ct, a key that does not serve level k (fewer
+   digits than it needs, or made for a lower level), out overlapping ct -> E_INVALIDARG; then a host-only context ->
+   COR_E_INVALIDOPERATION; count 0 -> S_OK. Transparency flag as sealhip_evaluator_apply_galois. */
+long sealhip_evaluator_switch_secret(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                     const sealhip_kswitch_key *key, uint64_t *out);
+/* sealhip_evaluator_bootstrap with ModRaise alone under a sparse secret: the q_0 rows of ct -> switch_secret at level 1 with
+   to_sparse -> mod_raise to k_top -> switch_secret at k_top with to_dense -> the same CoeffToSlot / EvalMod / SlotToCoeff.
+   The input, the output and every other key are under the working (dense) secret; K bounds the I of the SPARSE secret:
+   |I_j| <= (h + 1) / 2. to_sparse: dense -> sparse, made with level = 1; to_dense: sparse -> dense at the full level. Checks
+   are sealhip_evaluator_bootstrap's, then the two keys' (null -> E_POINTER; one that does not serve its level ->
+   E_INVALIDARG). Not capturable; the intermediates are the tables' block and the lane arena. */
+long sealhip_evaluator_bootstrap_encapsulated(sealhip_context *ctx, const sealhip_bootstrap_tables *tables, uint32_t k_in,
+                                              const uint64_t *ct, size_t count, const uint32_t *galois_elts,
+                                              const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                                              const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
+                                              const sealhip_kswitch_key *to_sparse, const sealhip_kswitch_key *to_dense,
+                                              uint64_t *out);
 /* stream-ordered hipMemsetAsync(dptr, 0, bytes) on the calling thread's lane: erases scratch that held secret samples
    before it goes back to a pool (the reference's clear_on_destruction pool, util/rlwe.cpp:141). Does not synchronise. */
 long sealhip_memset_zero(sealhip_context *ctx, void *dptr, size_t bytes);

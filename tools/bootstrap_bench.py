@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """CKKS bootstrapping on one MI355X: prints one JSON line per measurement.
-    python tools/bootstrap_bench.py [--counts 1,16] [--min-seconds 0.5]
+    python tools/bootstrap_bench.py [--counts 1,16] [--min-seconds 0.5] [--encapsulated]
 Its own context: N = 2^16, q_0 of 54 bits, fifteen primes next to 12 q_0 (57.6 bits), two 59-bit special primes. ModRaise to
 level 16, CoeffToSlot [5,5,5], EvalMod (K 12, r 3, degree 31, eight baby steps), SlotToCoeff [5,5,5]: out level 1. Keys are
 random words (timing does not depend on them).
@@ -10,6 +10,9 @@ random words (timing does not depend on them).
   double_angle  sealhip_evaluator_double_angle against the three entries it merges (dot_product without keys,
                 linear_combination_levels, relinearize_rescale), alternating in the same process: the ratio of the medians
                 with the spread of both.
+  encapsulated  (--encapsulated) sealhip_evaluator_bootstrap_encapsulated against
+                sealhip_evaluator_bootstrap, alternating in the same process, next to the two switch_secret calls it adds (level
+                1 and level k_top) alone: the difference of the medians should be those two key switches.
 There is no bar: nothing like this existed to compare against."""
 import argparse
 import json
@@ -26,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--counts", default="1,16")
     ap.add_argument("--min-seconds", type=float, default=0.5)
+    ap.add_argument("--encapsulated", action="store_true")
     a = ap.parse_args()
     import torch
 
@@ -102,6 +106,27 @@ def main():
                           "parts_ms": {name: round(v, 3) for name, v in part_ms.items()},
                           "parts_share": {name: round(v / total, 3) for name, v in part_ms.items()}}), flush=True)
         for b in (low, top, slots, sine, raised, re_im, sin_out, out):
+            b.free()
+
+    # ---- the encapsulated bootstrap against the plain one, alternating
+    for count in [int(v) for v in a.counts.split(",")] if a.encapsulated else []:
+        to_sparse, to_dense = random_key(), random_key()
+        low, top, out = rows(1, count), rows(k_top, count), ctx.alloc(count * 2 * lo * n)
+        low_out, top_out = ctx.alloc(count * 2 * n), ctx.alloc(count * 2 * k_top * n)
+        plain, enc = [], []
+        for _ in range(5):
+            plain.append(timed(lambda: ev.bootstrap(tables, low, 1, count, gk, rk, out))[0])
+            enc.append(timed(lambda: ev.bootstrap_encapsulated(tables, low, 1, count, gk, rk, to_sparse, to_dense, out))[0])
+        s1 = timed(lambda: ev.switch_secret(low, 1, count, to_sparse, low_out))[0]
+        s2 = timed(lambda: ev.switch_secret(top, k_top, count, to_dense, top_out))[0]
+        print(json.dumps({"what": "encapsulated", "count": count, "plain_ms": [round(v, 3) for v in plain],
+                          "encapsulated_ms": [round(v, 3) for v in enc],
+                          "difference_ms": round(float(np.median(enc) - np.median(plain)), 3),
+                          "switch_secret_level_1_ms": round(s1, 3), "switch_secret_level_k_top_ms": round(s2, 3),
+                          "ratio": round(float(np.median(enc) / np.median(plain)), 4),
+                          "spread_plain": round((max(plain) - min(plain)) / float(np.median(plain)), 4),
+                          "spread_encapsulated": round((max(enc) - min(enc)) / float(np.median(enc)), 4)}), flush=True)
+        for b in (low, top, out, low_out, top_out):
             b.free()
 
     # ---- double_angle against the three entries it merges, alternating
