@@ -209,7 +209,11 @@ long sealhip_inverse_ntt_negacyclic_harvey(sealhip_context *ctx, uint64_t *data,
                                            uint32_t base);
 
 /* ---------------------------------------------------------------- L2: coefficient-wise (util/polyarithsmallmod.{h,cpp})
-   operands: count polynomials x rows x N of the given base/level; result may alias an operand. */
+   operands: count polynomials x rows x N of the given base/level; result may alias an operand.
+   Operand ranges (p = the row's prime; results are canonical, below p; tests/test_gpu_linear_layer.py covers exactly these):
+     dyadic_product: a any 64-bit word (lazy NTT outputs), b below p;
+     multiply_poly_scalar: a and scalar any 64-bit word (the reference reduces the 128-bit product, polyarithsmallmod.cpp:35-60);
+     add, sub, negate: operands below p (one conditional correction, polyarithsmallmod.h:176-205, :261-299, :366-404). */
 long sealhip_dyadic_product_coeffmod(sealhip_context *ctx, const uint64_t *a, const uint64_t *b, size_t count,
                                      uint32_t k, uint32_t base, uint64_t *result);
 long sealhip_multiply_poly_scalar_coeffmod(sealhip_context *ctx, const uint64_t *a, size_t count, uint32_t k,
@@ -234,7 +238,9 @@ long sealhip_divide_and_round_q_last_ntt_inplace(sealhip_context *ctx, uint32_t 
 
 /* ---------------------------------------------------------------- L2: Galois (util/galois.cpp) */
 long sealhip_galois_elt_from_step(const sealhip_context *ctx, int32_t step, uint32_t *galois_elt);
-/* coefficient form (galois.cpp:144-186) / NTT form (:188-214); in and out must not alias */
+/* coefficient form (galois.cpp:144-186) / NTT form (:188-214); in and out must not alias. galois_elt: any odd element of
+   [1, 2N), the identity 1 included; anything else is E_INVALIDARG. Coefficient form: words below the row's prime (the sign
+   flip is p - v, and 0 stays 0); NTT form: a permutation of whatever words it is given. */
 long sealhip_apply_galois(sealhip_context *ctx, const uint64_t *in, size_t count, uint32_t k, uint32_t galois_elt,
                           uint64_t *out);
 long sealhip_apply_galois_ntt(sealhip_context *ctx, const uint64_t *in, size_t count, uint32_t k,
@@ -362,7 +368,8 @@ long sealhip_host_register(sealhip_context *ctx, void *ptr, size_t bytes);
 long sealhip_host_unregister(sealhip_context *ctx, void *ptr);
 
 /* ---------------------------------------------------------------- Evaluator surface beyond the hot path */
-/* Ciphertext batches [count][size][k][N]. Evaluator::negate_inplace (evaluator.cpp:65-88); out may alias ct. */
+/* Ciphertext batches [count][size][k][N], words below their row's prime; sizes from 1 on, 0 is E_INVALIDARG.
+   Evaluator::negate_inplace (evaluator.cpp:65-88); out may alias ct. */
 long sealhip_evaluator_negate(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size, size_t count,
                               uint64_t *out);
 /* Evaluator::add_inplace (evaluator.cpp:90-151) / sub_inplace (:174-233): out has max(size_a, size_b) polynomials per
@@ -374,7 +381,7 @@ long sealhip_evaluator_sub(sealhip_context *ctx, uint32_t k, const uint64_t *a, 
                            uint32_t size_b, size_t count, uint64_t *out);
 /* Evaluator::multiply_plain_ntt (evaluator.cpp:1605-1646): every polynomial of every ciphertext times a plaintext in
    NTT form (k x N), in place. plain_stride = words between the plaintexts of consecutive ciphertexts, 0 = one
-   plaintext for the whole batch. */
+   plaintext for the whole batch. Ciphertext and plaintext words below their row's prime. */
 long sealhip_evaluator_multiply_plain_ntt(sealhip_context *ctx, uint32_t k, uint64_t *ct, uint32_t size, size_t count,
                                           const uint64_t *plain_ntt, size_t plain_stride);
 /* Evaluator::multiply_plain_normal (evaluator.cpp:1475-1603), BFV, coefficient form, in place. plain = N coefficients
