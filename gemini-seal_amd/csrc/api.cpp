@@ -752,6 +752,41 @@ long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t 
     });
 }
 
+long sealhip_debug_ks_split_last(sealhip_context *ctx, uint32_t k, size_t count, int32_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        check_level(e, k);
+        *out = ks_split_last_plan(e, static_cast<int>(k), count) ? 1 : 0;
+    });
+}
+
+long sealhip_debug_ntt_split_last(sealhip_context *ctx, uint32_t prime_index, uint32_t treatment, int32_t exact,
+                                  const uint64_t *src_device, uint64_t *dst_device)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(src_device);
+    REQUIRE_PTR(dst_device);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (prime_index >= e.key_moduli.size() || treatment > 2 || src_device == dst_device)
+            throw std::invalid_argument("ntt_split_last: a key prime, treatment 0..2, distinct buffers");
+        RowMap map{};
+        map.rows = 1;
+        map.prime[0] = static_cast<unsigned short>(prime_index);
+        NttSource ns{};
+        ns.base[0] = reinterpret_cast<const u64 *>(src_device);
+        ns.code[0] = 0;
+        ns.reduce_mode = static_cast<int>(treatment);
+        const int flags = exact ? 0 : (kNttAnyRep | kNttApprox);
+        if (!ntt_can_split_last(e, map, ns, flags, 1))
+            throw std::invalid_argument("ntt_split_last: no instance of this form for the ring and prime");
+        SEALHIP_CHECK(launch_ntt_gather(e, reinterpret_cast<u64 *>(dst_device), 1, map, ns, flags | kNttSplitLast));
+    });
+}
+
 long sealhip_debug_behz_dot_split(sealhip_context *ctx, uint32_t k, int32_t *out)
 {
     REQUIRE_PTR(ctx);

@@ -488,6 +488,8 @@ namespace sealhip
     bool ntt_strict_top_done_ok(const Engine &e, const RowMap &map); // STRICT: kNttTopDone needs the dense forward schedule
     hipError_t launch_ntt_gather(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, const NttSource &src,
                                  int flags);
+    // may this gathered launch leave the transform's last layer to an inner product of nd digits (kNttSplitLast)?
+    bool ntt_can_split_last(const Engine &e, const RowMap &map, const NttSource &src, int flags, int nd);
 
     enum class PolyOp
     {
@@ -591,6 +593,7 @@ namespace sealhip
         int deferred_top;   // floor input: 0 canonical, 1 top layer deferred, 2 and Montgomery-scaled (fused tensor)
     };
     BfvMulPlan plan_bfv_multiply(Engine &e, int k, int sa, int sb, bool square);
+    bool ks_split_last_plan(Engine &e, int k, std::size_t count); // (sealhip_debug_ks_split_last)
 
     // fused fastbconv_m_tilde + sm_mrq: in k rows -> out |Bsk| rows, instance plan.lift_kernel
     // plan.lift_top: also apply the forward NTT's top layer to the rows written (exact-k instances only; the caller then
@@ -710,7 +713,9 @@ namespace sealhip
     hipError_t launch_ks_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
                              std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
                              std::size_t ext_digit_stride, const u64 *key, u64 *prod, std::size_t prod_stride,
-                             std::size_t count, int j0 = 0, int j1 = -1); // digits [j0, j1) (default: all of the level)
+                             std::size_t count, int j0 = 0, int j1 = -1, // digits [j0, j1) (default: all of the level)
+                             bool pair = false); // the digit rows lack their last layer (kNttSplitLast): the pair form
+    bool ks_mac_has_pair_form(const Engine &e, const KsDev &h, std::size_t count, int j0, int j1);
     hipError_t launch_ks_moddown_pre(const Engine &e, const KsDev *d, const KsDev &h, const u64 *prod,
                                      std::size_t prod_stride, u64 *temp, std::size_t temp_stride, std::size_t npolys);
     // BFV only: steps 1-4 of the rescale + the add into the ciphertext in one kernel; top_deferred = the rows of prod

@@ -214,6 +214,144 @@ namespace sealhip
             }
         }
 
+        // The pair form of ks_mac_items_kernel, for digit rows whose forward transform stopped before its last layer
+        // (kNttSplitLast): row r of ext[j][item] holds E[0..N/2) | O[0..N/2), the transforms of the even- and
+        // the odd-indexed coefficients as rings of N/2. One lane per pair index c < N/2 finishes the transform,
+        //   X[2c] = E[c] + T,  X[2c+1] = E[c] - T + 2p,  T = O[c] * psi^brev(N/2 + c) as an exact lazy Shoup product (below 2p),
+        // with the twiddle pair from the second half of PrimeDev::fwd loaded once and kept across the group like the key words,
+        // and accumulates both words into the two components' sums with the key words at 2c, 2c + 1 (16-byte loads; the two
+        // canonical residues of a component leave as one 16-byte store). The in-bundle row is the target's whole transform: its
+        // pair 2c, 2c + 1 is taken as it is. The words are below 2^64 and nd p < 2^64 (bounds::fwd_split_admits): the 128-bit
+        // sums cannot wrap. Workgroups never straddle a row (N/2 >= 2^13 lanes per row): the row's facts are scalars.
+        // PF: request the next ciphertext's words before the current one is accumulated (dropped where it would spill).
+        // (lo, hi) += a * b as one 128-bit multiply-add: the compiler forms the product from four 32 x 32 multiply-adds and
+        // adds it with one carry chain, where mac128's separate low and high products repeat partial products
+        __device__ __forceinline__ void mac128_wide(u64 &lo, u64 &hi, u64 a, u64 b)
+        {
+            const unsigned __int128 acc = ((static_cast<unsigned __int128>(hi) << 64) | lo) + static_cast<unsigned __int128>(a) * b;
+            lo = static_cast<u64>(acc);
+            hi = static_cast<u64>(acc >> 64);
+        }
+
+        template <int ND, bool PF>
+        __global__ __launch_bounds__(kThreads) void ks_mac_pair_kernel(const KsDev *__restrict__ d,
+                                                                       const PrimeDev *__restrict__ primes,
+                                                                       const u64 *__restrict__ target,
+                                                                       std::size_t target_stride,
+                                                                       const u64 *__restrict__ ext, std::size_t ext_stride,
+                                                                       std::size_t ext_digit_stride,
+                                                                       const u64 *__restrict__ key,
+                                                                       u64 *__restrict__ prod, std::size_t prod_stride,
+                                                                       std::size_t count, int logn, std::size_t group)
+        {
+            const std::size_t N = static_cast<std::size_t>(1) << logn, H = N >> 1;
+            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            const std::size_t lane0 = blockIdx.x * static_cast<std::size_t>(kThreads); // (uniform: H is a multiple of kThreads)
+            const std::size_t c0 = lane0 & (H - 1); // the workgroup's first pair; the lane's is c0 + threadIdx.x
+            const std::size_t rr = lane0 >> (logn - 1);
+            const int r = static_cast<int>(rr % rows);
+            const std::size_t item0 = (rr / rows) * group;
+            if (item0 >= count)
+                return;
+            const std::size_t item1 = item0 + group < count ? item0 + group : count;
+            const int rns_idx = d->row_prime[r];
+            const int my_digit = r < k ? r / nsp : -1;
+            const std::size_t row_off = static_cast<std::size_t>(r) * N;
+            const PrimeDev &P = primes[rns_idx];
+            const u64 p = P.p, two_p = P.two_p, cr0 = P.cr0, cr1 = P.cr1;
+            // every address is a uniform base (scalar registers) plus the lane's 32-bit byte offset: one offset register for
+            // the 8-byte words and one for the 16-byte pairs instead of a 64-bit address per load
+            const unsigned off8 = threadIdx.x * 8u, off16 = threadIdx.x * 16u;
+            const auto word = [](const u64 *base, unsigned off) {
+                return *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(base) + off);
+            };
+            const auto pair = [](const u64 *base, unsigned off) {
+                return *reinterpret_cast<const ulonglong2 *>(reinterpret_cast<const char *>(base) + off);
+            };
+            const u64 *key_row = key + static_cast<std::size_t>(rns_idx) * N + 2 * c0;
+            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const ulonglong2 w = pair(P.fwd + 2 * (H + c0), off16); // (twiddle, its Shoup quotient) of pair c
+            ulonglong2 k0[ND], k1[ND];
+#pragma unroll
+            for (int j = 0; j < ND; j++)
+            {
+                k0[j] = pair(key_row + (2 * static_cast<std::size_t>(j)) * key_comp, off16);
+                k1[j] = pair(key_row + (2 * static_cast<std::size_t>(j) + 1) * key_comp, off16);
+            }
+            // where the next ciphertext's words of digit j start for this workgroup (uniform; advanced by every load_x) -- in
+            // the bundle: words 2c, 2c + 1 of the target row; else E[c], O[c] of the digit row
+            const u64 *src[ND];
+#pragma unroll
+            for (int j = 0; j < ND; j++)
+                src[j] = j == my_digit ? target + item0 * target_stride + row_off + 2 * c0
+                                       : ext + item0 * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + row_off + c0;
+            const unsigned off8_o = off8 + (static_cast<unsigned>(H) << 3), off16_o = off16 + 8u;
+            const auto load_x = [&](u64(&e)[ND], u64(&o)[ND]) {
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                {
+                    const bool inb = j == my_digit;
+                    e[j] = word(src[j], inb ? off16 : off8);
+                    o[j] = word(src[j], inb ? off16_o : off8_o);
+                    src[j] += inb ? target_stride : ext_stride;
+                }
+            };
+            // one ciphertext: the pair butterflies, the four sums, the two stores
+            const auto accumulate = [&](const u64(&e)[ND], const u64(&o)[ND], std::size_t item) {
+                u64 lo00 = 0, hi00 = 0, lo01 = 0, hi01 = 0, lo10 = 0, hi10 = 0, lo11 = 0, hi11 = 0;
+#pragma unroll
+                for (int j = 0; j < ND; j++)
+                {
+                    u64 x0 = e[j], x1 = o[j];
+                    if (j != my_digit)
+                    {
+                        const u64 t = mulmod_lazy(x1, w.x, w.y, p);
+                        x1 = x0 - t + two_p;
+                        x0 = x0 + t;
+                    }
+                    mac128_wide(lo00, hi00, x0, k0[j].x);
+                    mac128_wide(lo01, hi01, x1, k0[j].y);
+                    mac128_wide(lo10, hi10, x0, k1[j].x);
+                    mac128_wide(lo11, hi11, x1, k1[j].y);
+                }
+                u64 *pp = reinterpret_cast<u64 *>(reinterpret_cast<char *>(prod + item * prod_stride + row_off + 2 * c0) + off16);
+                store_stream2(pp, barrett_reduce_128(lo00, hi00, p, cr0, cr1), barrett_reduce_128(lo01, hi01, p, cr0, cr1));
+                store_stream2(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo10, hi10, p, cr0, cr1),
+                              barrett_reduce_128(lo11, hi11, p, cr0, cr1));
+            };
+            u64 xe[ND], xo[ND];
+            load_x(xe, xo);
+            if constexpr (PF)
+            {
+                // two ciphertexts per trip, the buffers changing roles: the next one's words are requested before the current
+                // one is accumulated, and nothing is copied
+                u64 ne[ND], no[ND];
+                for (std::size_t item = item0; item < item1; item += 2)
+                {
+                    if (item + 1 < item1)
+                        load_x(ne, no);
+                    accumulate(xe, xo, item);
+                    if (item + 1 >= item1)
+                        break;
+                    if (item + 2 < item1)
+                        load_x(xe, xo);
+                    accumulate(ne, no, item + 1);
+                }
+            }
+            else
+                for (std::size_t item = item0; item < item1; item++)
+                {
+                    accumulate(xe, xo, item);
+                    if (item + 1 < item1)
+                        load_x(xe, xo);
+                }
+        }
+
+        // digits up to which the pair form keeps the next ciphertext's words in flight (194 registers at nd = 7; without it 138 and the
+        // same time within the spread, profiles/r18/ks_split_last_ab.txt; 24 registers more per digit: from nd = 10 on the prefetch
+        // would leave one wave per SIMD. Measured at nd = 7 only.)
+        constexpr int kKsPairPrefetchDigits = 8;
+
         // rescale_special_rns_inplace, steps 1-2 (multi_special_primes.cpp:253-282): from the (coefficient
         // form) special rows of one polynomial compute temp_i for every ciphertext prime i.
         __global__ __launch_bounds__(kThreads) void ks_moddown_pre_kernel(const KsDev *__restrict__ d,
@@ -559,10 +697,16 @@ namespace sealhip
         return hipGetLastError();
     }
 
+    // the pair form exists where the items kernel does: all digits in one call, batches of at least 16, up to 16 digits
+    bool ks_mac_has_pair_form(const Engine &e, const KsDev &h, std::size_t count, int j0, int j1)
+    {
+        return e.logn >= 14 && count >= 16 && j0 == 0 && j1 == h.nd && h.nd >= 1 && h.nd <= 16;
+    }
+
     hipError_t launch_ks_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
                              std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
                              std::size_t ext_digit_stride, const u64 *key, u64 *prod, std::size_t prod_stride,
-                             std::size_t count, int j0, int j1)
+                             std::size_t count, int j0, int j1, bool pair)
     {
         if (!count)
             return hipSuccess;
@@ -571,6 +715,8 @@ namespace sealhip
         if (j0 < 0 || j0 > j1 || j1 > h.nd)
             return hipErrorInvalidValue;
         const bool all_digits = j0 == 0 && j1 == h.nd;
+        if (pair && !ks_mac_has_pair_form(e, h, count, j0, j1)) // (digit rows without their last layer: no other kernel reads them)
+            return hipErrorInvalidValue;
         const u64 *tg = target;
         const std::size_t lanes = (count * static_cast<std::size_t>(h.k + h.nsp)) << e.logn;
         ProfScope prof(e, "ks_mac", 0);
@@ -590,6 +736,38 @@ namespace sealhip
             }
         const std::size_t groups = (count + mac_group - 1) / mac_group;
         const std::size_t glanes = (groups * static_cast<std::size_t>(h.k + h.nsp)) << e.logn;
+        if (pair)
+        {
+            // one lane per pair of coefficients: half the lanes, the items kernel's group size (mac_group stays as it is)
+            const std::size_t planes = (groups * static_cast<std::size_t>(h.k + h.nsp)) << (e.logn - 1);
+#define SEALHIP_KS_MAC_PAIR(ND)                                                                                                          \
+    case ND:                                                                                                                             \
+        ks_mac_pair_kernel<ND, (ND <= kKsPairPrefetchDigits)><<<blocks_for(planes), kThreads, 0, e.lane().stream>>>(                    \
+            d, e.d_primes, tg, target_stride, ext, ext_stride, ext_digit_stride, key, prod, prod_stride, count, e.logn, mac_group); \
+        break;
+            switch (h.nd)
+            {
+                SEALHIP_KS_MAC_PAIR(1)
+                SEALHIP_KS_MAC_PAIR(2)
+                SEALHIP_KS_MAC_PAIR(3)
+                SEALHIP_KS_MAC_PAIR(4)
+                SEALHIP_KS_MAC_PAIR(5)
+                SEALHIP_KS_MAC_PAIR(6)
+                SEALHIP_KS_MAC_PAIR(7)
+                SEALHIP_KS_MAC_PAIR(8)
+                SEALHIP_KS_MAC_PAIR(9)
+                SEALHIP_KS_MAC_PAIR(10)
+                SEALHIP_KS_MAC_PAIR(11)
+                SEALHIP_KS_MAC_PAIR(12)
+                SEALHIP_KS_MAC_PAIR(13)
+                SEALHIP_KS_MAC_PAIR(14)
+                SEALHIP_KS_MAC_PAIR(15)
+                SEALHIP_KS_MAC_PAIR(16)
+            default: return hipErrorInvalidValue;
+            }
+#undef SEALHIP_KS_MAC_PAIR
+            return hipGetLastError();
+        }
 #define SEALHIP_KS_MAC(ND)                                                                                          \
     case ND:                                                                                                        \
         ks_mac_items_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(                                     \

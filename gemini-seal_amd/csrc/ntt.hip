@@ -574,6 +574,19 @@ namespace sealhip
         return e.use_half_kernel && e.logn >= 14 && e.logn <= 16;
     }
 
+    // May a key switch's digit launch (map, src, flags as launch_ntt_gather will get them) leave its last layer to an inner
+    // product of nd digits (kNttSplitLast)? The launch must select an integer instance of that form and
+    // every live prime must lie in bounds::fwd_split_admits with nd terms.
+    bool ntt_can_split_last(const Engine &e, const RowMap &map, const NttSource &src, int flags, int nd)
+    {
+        if (!ntt_can_gather(e))
+            return false;
+        for (int r = 0; r < map.rows; r++)
+            if (map.prime[r] != kSkipRow && !bounds::fwd_split_admits(e.tables[map.prime[r]].p, e.logn, nd))
+                return false;
+        return ntt_fwd_half_splits(e, map, flags | (e.mode_strict ? kNttStrict : 0), src);
+    }
+
     hipError_t launch_ntt_gather(const Engine &e, u64 *data, size_t nrows, const RowMap &map, const NttSource &src,
                                  int flags)
     {

@@ -252,6 +252,37 @@ namespace sealhip
         static_assert(fwd_dense_peak_mult(14) == 14 && fwd_dense_peak_mult(15) == 14 && fwd_dense_peak_mult(16) == 16,
                       "dense forward schedule: 14p after round 1, at most 16p after the final round at N = 2^16");
 
+        // ---- 2c. Forward transform without its last layer (kNttSplitLast): each half-row workgroup
+        // runs the log n - 1 layers of a ring of N/2 on one parity class of the gathered row (inputs below 2p, as above), so
+        // E[j], O[j] are below fwd_split_output_mult(log n) p = (2 + g (log n - 1)) p with the approximate quotient (the exact
+        // instance grows by 2p per layer and lies below that). The consumer (ks_mac_pair_kernel) finishes the pair:
+        // T = the exact lazy Shoup product of O[j] (any 64-bit word) by psi^brev(N/2 + j), below 2p; X0 = E + T and
+        // X1 = E - T + 2p, both below (fwd_split_output_mult + 2) p, which must stay below 2^64 -- and the 128-bit sums of nd
+        // products of such words with key words below p must stay below 2^128: nd p < 2^64.
+        constexpr int fwd_split_output_mult(int logn)
+        {
+            return 2 + kFwdApxGrowth * (logn - 1);
+        }
+        constexpr u128 fwd_split_peak(int logn, u64 p) // the largest word the split form makes, pair butterfly included
+        {
+            return fwd_int_peak(logn - 1, p, 2, true, true) + static_cast<u128>(2) * p;
+        }
+        constexpr int fwd_split_prime_bits(int logn)
+        {
+            int bits = 0;
+            for (int b = 1; b <= kMaxPrimeBits; b++)
+                if (fwd_split_peak(logn, max_prime_of_bits(b)) < kWord)
+                    bits = b;
+            return bits;
+        }
+        static_assert(kFwdApxLevel != 2 || (fwd_split_prime_bits(14) == 58 && fwd_split_prime_bits(15) == 58 && fwd_split_prime_bits(16) == 58),
+                      "split form at level 2: 56p / 60p / 64p at log n = 14 / 15 / 16, below 2^64 for primes below 2^58");
+        constexpr bool fwd_split_admits(u64 p, int logn, int nd)
+        {
+            return logn >= kMinHalfLogn && logn <= kMaxHalfLogn && nd >= 1 && p <= max_prime_of_bits(fwd_split_prime_bits(logn)) &&
+                   static_cast<u128>(nd) * p < kWord;
+        }
+
         // =====================================================================================================
         // 3. Tensor product formed by the inverse transform's load (dyadic_redc in ntt.hip): t = (sum of NP products) *
         // 2^-64 mod p as ONE Montgomery reduction, t < sum / 2^64 + p. Carry-free accumulation needs operands below 2^61

@@ -643,6 +643,48 @@ namespace sealhip
             }
         }
 
+        // kNttSplitLast: the parity class HALF of the gathered row, src[2 i + HALF] for i < 2^T, in arrangement 1 -- no layer
+        // is applied here. A slot pair (i, i + 1) lies in two neighbouring 16-byte pieces of the row, of which this workgroup
+        // keeps one word each: as many 16-byte loads per lane as h_load_top issues (32), every line of the row read once by
+        // each of the row's two workgroups.
+        template <int T, int HALF, int REDUCE>
+        __device__ __forceinline__ void h_load_split(u64 (&x)[32], const u64 *__restrict__ rowp, int tid, u64 p, u64 cr1)
+        {
+            static_assert(REDUCE == kTreatNone || REDUCE == kTreatBarrett || REDUCE == kTreatCondSub, "mod-up treatments only");
+            const int jb = Arr<T, 1>::tid_index(tid);
+#pragma unroll
+            for (int batch = 0; batch < 16 / kLoadBatch; batch++)
+            {
+                ulonglong2 a[kLoadBatch], b[kLoadBatch];
+#pragma unroll
+                for (int i = 0; i < kLoadBatch; i++)
+                {
+                    const int idx = jb + Arr<T, 1>::slot_index((batch * kLoadBatch + i) * 2);
+                    a[i] = *reinterpret_cast<const ulonglong2 *>(rowp + 2 * idx);
+                    b[i] = *reinterpret_cast<const ulonglong2 *>(rowp + 2 * idx + 2);
+                }
+#pragma unroll
+                for (int i = 0; i < kLoadBatch; i++)
+                {
+                    const int s = (batch * kLoadBatch + i) * 2;
+                    u64 v0 = HALF ? a[i].y : a[i].x, v1 = HALF ? b[i].y : b[i].x;
+                    if constexpr (REDUCE == kTreatCondSub)
+                    {
+                        v0 = v0 >= p ? v0 - p : v0; // source prime < 2p: the canonical residue is v or v - p
+                        v1 = v1 >= p ? v1 - p : v1;
+                    }
+                    else if constexpr (REDUCE == kTreatBarrett)
+                    {
+                        v0 = barrett_reduce_63(v0, p, cr1);
+                        v1 = barrett_reduce_63(v1, p, cr1);
+                    }
+                    x[s] = v0;
+                    x[s + 1] = v1;
+                }
+                __builtin_amdgcn_sched_barrier(0); // (as in h_load_top: loaded values are not held across batches)
+            }
+        }
+
         // arrangement 1 -> memory: pairs, consecutive lanes 16 bytes apart
         template <int T>
         __device__ __forceinline__ void h_store_rows(const u64 (&x)[32], u64 *__restrict__ halfp, int tid)
@@ -694,14 +736,18 @@ namespace sealhip
             note_nonzero(tflag, 0, nz);
         }
 
-        template <int LOGN, int STRICT, int REDUCE>
+        // SPLIT (kNttSplitLast): the workgroup transforms one parity class of the gathered row as a ring of
+        // N/2 -- h_load_split instead of the top layer, the rounds' twiddle addressing of a ring of N/2 (tables: the first half
+        // of PrimeDev::fwd), the store phase as it is, into the workgroup's half of the row. The consumer applies the last layer.
+        template <int LOGN, int STRICT, int REDUCE, bool SPLIT = false>
         __global__ __launch_bounds__(1 << (LOGN - 6), 4) void ntt_fwd_half_kernel(
             u64 *__restrict__ data, const PrimeDev *__restrict__ primes, RowMap map, std::size_t nrows, int flags,
             unsigned *__restrict__ tickets, unsigned *__restrict__ timeout_flag, unsigned spin_limit, NttSource src,
             std::size_t chunk, LiveSlots live)
         {
             constexpr int T = LOGN - 1;
-            constexpr int N = 1 << LOGN;
+            constexpr int N = SPLIT ? 1 << (LOGN - 1) : 1 << LOGN; // the ring whose twiddles the rounds address
+            static_assert(!SPLIT || ((STRICT == kSchedLazy || STRICT == kSchedApprox) && REDUCE <= kTreatCondSub), "kFwdSplitInstances");
             extern __shared__ u64 lds[];
             const int wave_base = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) & ~63); // (see fresh_tid)
             int half, position;
@@ -716,6 +762,8 @@ namespace sealhip
             const u64 p = P.p, two_p = FP ? fp_bits(P.p_d) : P.two_p, rdp = P.rdp;
             const u64 *tw = FP ? reinterpret_cast<const u64 *>(P.fwd_d) : P.fwd;
             u64 *rowp = data + (row << LOGN);
+            if constexpr (SPLIT)
+                rowp += half << T; // (the rounds below run with gbase = 0: indices of the workgroup's own ring)
             u64 x[32];
 
             // ---- load both halves, top layer on the fly, arrangement 1 (block-uniform branch on the half)
@@ -743,6 +791,13 @@ namespace sealhip
                     x[s + 1] = v.y;
                 }
             }
+            else if constexpr (SPLIT)
+            {
+                if (half)
+                    h_load_split<T, 1, REDUCE>(x, srcp, fresh_tid(wave_base), p, P.cr1);
+                else
+                    h_load_split<T, 0, REDUCE>(x, srcp, fresh_tid(wave_base), p, P.cr1);
+            }
             else if (half)
                 h_load_top<T, STRICT, 1, REDUCE>(x, srcp, tw, fresh_tid(wave_base), two_p, neg_p, P.cr1, src.aux_p, src.aux_cr1, src.aux_top);
             else
@@ -756,7 +811,7 @@ namespace sealhip
             // the workgroup has consumed all of its loaded values in round 1, so no extra wait or barrier is needed.
             // (Sharing the top layer between the two workgroups instead -- each publishing the other's outputs -- measured
             //  slower: profiles/r04/sibling_top_exchange_ab.txt.)
-            const int gbase = half << T;
+            const int gbase = SPLIT ? 0 : half << T;
             // round 1: every lane index bit lies below the processed bits -> block-uniform twiddles
             u64 w0[kIL], ws0[kIL];
             RoundStage<T, 1, STRICT, true, 0>::load(w0, ws0, tw, gbase, N);
@@ -822,7 +877,8 @@ namespace sealhip
             // bit 2 (approximate-quotient canonical launches on primes of at least 45 bits, select_fwd_half): the canonicalising
             // step estimates its small quotient in single precision (devmath.hpp reduce_small_quot)
             // (STRICT == kSchedDense, the dense lazy schedule: the last layer leaves its first operand as it is, the store reduces)
-            const int fin = ((flags & kNttCanonical) ? 1 : 0) | (((flags & kNttAnyRep) || STRICT == kSchedDense) ? 2 : 0) | ((flags & kNttSmallQuot) ? 4 : 0);
+            // (SPLIT: the half ring's last layer is not the row's; the consumer reduces, select_fwd_half admitted the primes)
+            const int fin = ((flags & kNttCanonical) ? 1 : 0) | (((flags & kNttAnyRep) || STRICT == kSchedDense || SPLIT) ? 2 : 0) | ((flags & kNttSmallQuot) ? 4 : 0);
             const u64 rdp_fin =
                 ((STRICT == kSchedApprox && (flags & kNttSmallQuot)) || STRICT == kSchedDense) ? static_cast<u64>(__float_as_uint(small_quot_const(p))) : rdp;
             constexpr bool ROUT = REDUCE == kTreatReduceOut || REDUCE == kTreatReduceOutTopDone; // kNttReduceOut launches (never gathered: no load treatment to combine with)
@@ -877,6 +933,47 @@ namespace sealhip
         {
             return fwd_kernels<LOGN>(std::make_integer_sequence<int, kFwdInstanceCount>{});
         }
+        // ... and those of kFwdSplitInstances
+        template <int LOGN, int... I>
+        const FwdKernel *fwd_split_kernels(std::integer_sequence<int, I...>)
+        {
+            static const FwdKernel table[] = { &ntt_fwd_half_kernel<LOGN, kFwdSplitInstances[I].sched, kFwdSplitInstances[I].treatment, true>... };
+            return table;
+        }
+        template <int LOGN>
+        const FwdKernel *fwd_split_kernels()
+        {
+            return fwd_split_kernels<LOGN>(std::make_integer_sequence<int, kFwdSplitInstanceCount>{});
+        }
+
+        // the facts select_fwd_half decides on, and its decision, for a launch on ring e.logn
+        FwdChoice choose_fwd(const Engine &e, const RowMap &map, int flags, const NttSource &src, const LiveSlots &live)
+        {
+            u64 live_p[kMaxRows];
+            FwdFacts f{};
+            f.logn = e.logn;
+            f.flags = flags;
+            f.live = live_p;
+            f.live_n = live.n;
+            f.gathers = src.base[0] != nullptr;
+            f.all_gathered = f.same_source = f.key_moduli_fp = true;
+            for (int i = 0; i < live.n; i++)
+            {
+                live_p[i] = e.tables[map.prime[live.slot[i]]].p;
+                if (f.gathers)
+                {
+                    f.all_gathered = f.all_gathered && src.code[live.slot[i]] != kSkipRow;
+                    f.same_source = f.same_source && ((src.code[live.slot[i]] ^ src.code[live.slot[0]]) & ~kSrcReduce) == 0;
+                }
+            }
+            for (std::size_t i = 0; f.gathers && f.key_moduli_fp && i < e.key_moduli.size(); i++)
+                f.key_moduli_fp = e.key_moduli[i] < bounds::kFpInputBound;
+            f.treatment = src.reduce_mode;
+            f.aux_p = src.aux_p;
+            f.sw = ntt_switches();
+            f.suppress_signal = e.ntt_suppress_signal;
+            return select_fwd_half(f);
+        }
 
         // Which instance runs, and with which flags, is select_fwd_half's decision (ntt_select.hpp; the instances and who
         // launches them: DESIGN.md section 6). Here: the facts it decides on, the hand-off tickets, the launch.
@@ -904,30 +1001,7 @@ namespace sealhip
             const std::size_t blocks = chunk * 16;
             if (blocks > 0x7fffffffull)
                 return hipErrorInvalidValue;
-            u64 live_p[kMaxRows];
-            FwdFacts f{};
-            f.logn = LOGN;
-            f.flags = flags;
-            f.live = live_p;
-            f.live_n = live.n;
-            f.gathers = src.base[0] != nullptr;
-            f.all_gathered = f.same_source = f.key_moduli_fp = true;
-            for (int i = 0; i < live.n; i++)
-            {
-                live_p[i] = e.tables[map.prime[live.slot[i]]].p;
-                if (f.gathers)
-                {
-                    f.all_gathered = f.all_gathered && src.code[live.slot[i]] != kSkipRow;
-                    f.same_source = f.same_source && ((src.code[live.slot[i]] ^ src.code[live.slot[0]]) & ~kSrcReduce) == 0;
-                }
-            }
-            for (std::size_t i = 0; f.gathers && f.key_moduli_fp && i < e.key_moduli.size(); i++)
-                f.key_moduli_fp = e.key_moduli[i] < bounds::kFpInputBound;
-            f.treatment = src.reduce_mode;
-            f.aux_p = src.aux_p;
-            f.sw = ntt_switches();
-            f.suppress_signal = e.ntt_suppress_signal;
-            const FwdChoice c = select_fwd_half(f);
+            const FwdChoice c = choose_fwd(e, map, flags, src, live);
             if (!c.valid)
                 return hipErrorInvalidValue;
             // The transform is in place and both workgroups of a row read both halves: a ticket per row (zeroed for this
@@ -947,7 +1021,7 @@ namespace sealhip
                 std::memcpy(&ksrc.aux_top[2], &c2, 8);
             }
             ProfScope prof(e, "ntt_fwd_half", transformed_rows(nrows, map));
-            fwd_kernels<LOGN>()[c.instance]<<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
+            (c.split ? fwd_split_kernels<LOGN>() : fwd_kernels<LOGN>())[c.instance]<<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
                 data, e.d_primes, map, nrows, c.flags, tickets, e.lane().d_fault, e.ntt_spin_limit, ksrc, chunk, live);
             return hipGetLastError();
         }
@@ -964,6 +1038,12 @@ namespace sealhip
                     if (err != hipSuccess)
                         return err;
                 }
+            for (int i = 0; i < kFwdSplitInstanceCount; i++)
+            {
+                const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_split_kernels<LOGN>()[i]), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+                if (err != hipSuccess)
+                    return err;
+            }
             return hipSuccess;
         }
     } // namespace
@@ -977,6 +1057,15 @@ namespace sealhip
         case 16: return launch_half<16>(e, data, nrows, map, flags, src);
         default: return hipErrorInvalidValue;
         }
+    }
+
+    bool ntt_fwd_half_splits(const Engine &e, const RowMap &map, int flags, const NttSource &src)
+    {
+        const LiveSlots live = live_slots(map);
+        if (e.logn < 14 || e.logn > 16 || live.n == 0)
+            return false;
+        const FwdChoice c = choose_fwd(e, map, flags | kNttSplitLast, src, live);
+        return c.valid && c.split;
     }
 
     hipError_t ntt_fwd_half_init()

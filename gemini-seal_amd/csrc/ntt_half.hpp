@@ -21,6 +21,8 @@ namespace sealhip
                                              const NttSource &src);
     SEALHIP_INTERNAL hipError_t ntt_inv_half(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags,
                                              const u64 *src = nullptr, std::size_t src_poly_stride = 0);
+    // would this gathered launch, with kNttSplitLast added, select an instance of kFwdSplitInstances (else it is refused)
+    SEALHIP_INTERNAL bool ntt_fwd_half_splits(const Engine &e, const RowMap &map, int flags, const NttSource &src);
     // inverse of the ciphertext tensor product formed on load (ntt_inv.hip DyadicSrc, launch_intt_tensor)
     SEALHIP_INTERNAL hipError_t ntt_inv_tensor(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags,
                                                const u64 *x, std::size_t item_stride, std::size_t poly_stride, int kb,

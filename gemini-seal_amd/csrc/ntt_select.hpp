@@ -25,6 +25,11 @@ namespace sealhip
     // the row, no duplicated products (both workgroups of a row compute the top layer's products otherwise), no hand-off.
     constexpr int kNttTopDone = 0x80;
     constexpr int kNttDeferTop = 4;  // inverse, single-pass kernels only: leave the top layer (gap N/2) to the consumer
+    // forward, single-pass kernel, gathered out-of-place launches whose consumer applies the transform's LAST layer (DESIGN.md
+    // section 6b): workgroup `half` of a row transforms the parity class src[2i + half] as a ring of N/2 and stores it to
+    // words [half N/2, (half + 1) N/2) of the row. No top layer, no duplicated products, no hand-off. Integer instances
+    // of kFwdSplitInstances only, live primes in bounds::fwd_split_admits: anything else is refused.
+    constexpr int kNttSplitLast = 0x100;
     // Primes below this bound have double-precision twiddle tables: the single-pass kernels then run their butterflies
     // on the FP64 pipe (exact, devmath.hpp) whenever the launch promises nothing about representatives that only the
     // integer sequence would deliver (canonical outputs, or kNttAnyRep). SEALHIP_NTT_NO_FP64=1 switches it off.
@@ -104,6 +109,21 @@ namespace sealhip
         return -1;
     }
 
+    // ---- forward instances without the last layer (kNttSplitLast): ntt_fwd_half_kernel<LOGN, sched, treatment, true>, a
+    // table of its own (FwdChoice::split says which table FwdChoice::instance indexes). They exist at every ring size.
+    constexpr FwdInstance kFwdSplitInstances[] = {
+        { kSchedLazy, kTreatNone },   { kSchedLazy, kTreatBarrett },   { kSchedLazy, kTreatCondSub },
+        { kSchedApprox, kTreatNone }, { kSchedApprox, kTreatBarrett }, { kSchedApprox, kTreatCondSub },
+    };
+    constexpr int kFwdSplitInstanceCount = static_cast<int>(sizeof(kFwdSplitInstances) / sizeof(kFwdSplitInstances[0]));
+    constexpr int fwd_split_instance_index(int sched, int treatment)
+    {
+        for (int i = 0; i < kFwdSplitInstanceCount; i++)
+            if (kFwdSplitInstances[i].sched == sched && kFwdSplitInstances[i].treatment == treatment)
+                return i;
+        return -1;
+    }
+
     // ---- inverse instances: ntt_inv_half_kernel<inv_kernel_logn(shape, logn), sched, DY, WHOLE, QUARTER>
     struct InvInstance
     {
@@ -175,6 +195,7 @@ namespace sealhip
                              // kNttPolyMajor with its group size, kNttDebugNoSignal
         bool tickets;        // the two workgroups of a row hand off through a ticket: the launch needs Engine::ntt_tickets
         bool aux_as_doubles; // the special prime's constants go in as doubles (h_load_top's floating-point treatments)
+        bool split;          // kNttSplitLast: `instance` indexes kFwdSplitInstances
     };
 
     // (The ring size is a template argument so that the predicates get it as a constant: they are worst-case recurrences,
@@ -215,6 +236,10 @@ namespace sealhip
         // a launch whose live rows are all gathered from another buffer writes no row that anybody reads: nothing to
         // hand off either
         const bool all_gathered = f.gathers && f.all_gathered;
+        // kNttSplitLast: out of place by definition (every live row gathered), no in-place option beside it
+        const bool split = (flags & kNttSplitLast) != 0;
+        if (split && (!all_gathered || (flags & (kNttCanonical | kNttReduceOut | kNttTopDone)) != 0))
+            return c;
         c.tickets = !(top_done || all_gathered);
         if (f.suppress_signal)
             flags |= kNttDebugNoSignal;
@@ -284,6 +309,17 @@ namespace sealhip
         c.treatment = red;
         c.flags = flags;
         c.aux_as_doubles = fp && f.gathers && special;
+        if (split)
+        {
+            // the consumer forms the last layer from words that must not have wrapped (its 128-bit sums: the launcher's
+            // caller checks nd, here one digit); no floating-point, Harvey or special-prime instance of this form exists
+            if (fp || !every_live([&](bounds::u64 p) { return bounds::fwd_split_admits(p, LOGN, 1); }))
+                return c;
+            c.split = true;
+            c.instance = fwd_split_instance_index(c.sched, c.treatment);
+            c.valid = c.instance >= 0;
+            return c;
+        }
         c.instance = fwd_instance_index(LOGN, c.sched, c.treatment); // (kTreatModDownStore at 2^14: none)
         c.valid = c.instance >= 0;
         return c;

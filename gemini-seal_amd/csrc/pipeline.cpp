@@ -211,13 +211,17 @@ namespace sealhip
         // The part of the key switch that does not depend on the key (evaluator.cpp:2302-2322): the digits [dj0, dj1) of m
         // targets, extended to every row outside their bundle and transformed, into ext (digit-major); returns the rows the
         // inner product reads inside a bundle (the targets themselves, or their transform in coeff for STRICT BFV).
+        // split_last (only ks_products asks for it, the other consumers need whole rows): the digit rows
+        // are stored without the transform's last layer, as E | O, where every digit launch can take that form and the inner
+        // product has its pair form for the batch -- KsRows::split_last says whether they were.
         struct KsRows
         {
             const u64 *inb;
             std::size_t inb_stride;
+            bool split_last;
         };
         KsRows ks_digits(Engine &e, LevelTools &lt, int k, const u64 *tg, std::size_t target_stride, std::size_t m, u64 *coeff,
-                         u64 *ext, int dj0, int dj1)
+                         u64 *ext, int dj0, int dj1, bool split_last = false, bool plan_only = false)
         {
             const KsDev &h = lt.h_ks;
             const std::size_t N = e.n;
@@ -231,7 +235,7 @@ namespace sealhip
             // Step 1 (:2302-2307): CKKS bundles go back to coefficient form (canonical inverse NTT)
             const u64 *src = tg;
             std::size_t src_stride = target_stride;
-            if (ckks)
+            if (ckks && !plan_only) // (plan_only: no launch, only KsRows::split_last is computed; no pointer is followed)
             {
                 // (valid ciphertext rows are below p and the canonicalising top kernel follows: any representative will do)
                 if (ntt_can_gather(e)) // the inverse kernel reads the target rows where they are
@@ -275,34 +279,47 @@ namespace sealhip
                 if (bounds::fwd_lazy_admits(pmax, e.logn)) // (inputs below 2p: the case the recurrence in ntt_bounds.hpp walks)
                     modup_mode = kTreatNone;
             }
-            if (!gather)
+            if (!gather && !plan_only)
                 check(launch_ks_modup(e, lt.d_ks, h, src, src_stride, ext, ext_item, ext_digit, m, -1), "modup");
-            for (int j = dj0; j < dj1; j++)
-            {
+            // digit j's launch: every row but the bundle's, each gathered from the bundle's single row
+            const auto digit_map = [&](int j) {
                 RowMap mj = map_rows;
                 const int r0 = j * e.nsp, r1 = std::min(r0 + e.nsp, k);
                 for (int r = r0; r < r1; r++)
                     mj.prime[r] = kSkipRow;
-                if (gather)
+                return mj;
+            };
+            const auto digit_source = [&](int j) {
+                NttSource ns{};
+                ns.base[0] = src;
+                ns.poly_stride[0] = src_stride;
+                ns.reduce_mode = modup_mode;
+                const u64 p_src = e.key_moduli[h.row_prime[j]];
+                for (int r = 0; r < rows; r++)
                 {
-                    NttSource ns{};
-                    ns.base[0] = src;
-                    ns.poly_stride[0] = src_stride;
-                    ns.reduce_mode = modup_mode;
-                    const u64 p_src = e.key_moduli[h.row_prime[j]];
-                    for (int r = 0; r < rows; r++)
+                    if (r == j)
                     {
-                        if (r == j)
-                        {
-                            ns.code[r] = kSkipRow;
-                            continue;
-                        }
-                        const u64 p_dst = e.key_moduli[h.row_prime[r]];
-                        ns.code[r] = static_cast<unsigned short>(j | (p_src <= p_dst ? 0 : kSrcReduce));
+                        ns.code[r] = kSkipRow;
+                        continue;
                     }
-                    // (the inner product reduces canonically: any representative of the transformed rows will do)
-                    check(launch_ntt_gather(e, ext + j * ext_digit, m * rows, mj, ns, kNttAnyRep | kNttApprox), "ntt(ext, gathered)");
+                    const u64 p_dst = e.key_moduli[h.row_prime[r]];
+                    ns.code[r] = static_cast<unsigned short>(j | (p_src <= p_dst ? 0 : kSrcReduce));
                 }
+                return ns;
+            };
+            // (the inner product reduces canonically: any representative of the transformed rows will do)
+            const int digit_flags = kNttAnyRep | kNttApprox;
+            split_last = split_last && gather && ks_mac_has_pair_form(e, h, m, dj0, dj1);
+            for (int j = dj0; split_last && j < dj1; j++)
+                split_last = ntt_can_split_last(e, digit_map(j), digit_source(j), digit_flags, h.nd);
+            if (plan_only)
+                return KsRows{ nullptr, 0, split_last };
+            for (int j = dj0; j < dj1; j++)
+            {
+                const RowMap mj = digit_map(j);
+                if (gather)
+                    check(launch_ntt_gather(e, ext + j * ext_digit, m * rows, mj, digit_source(j), digit_flags | (split_last ? kNttSplitLast : 0)),
+                          "ntt(ext, gathered)");
                 else
                     check(launch_ntt(e, ext + j * ext_digit, m * rows, mj, false, kNttAnyRep), "ntt(ext)"); // (as above)
             }
@@ -331,7 +348,7 @@ namespace sealhip
                 inb = coeff;
                 inb_stride = static_cast<std::size_t>(k) * N;
             }
-            return KsRows{ inb, inb_stride };
+            return KsRows{ inb, inb_stride, split_last };
         }
 
         // The front half of a key switch: ks_digits, then Step 3b + 4 (:2326-2349), the 128-bit inner product of the digits
@@ -340,9 +357,9 @@ namespace sealhip
                          u64 *ext, const KSwitchKey &key, u64 *prod, int dj0, int dj1)
         {
             const std::size_t ext_item = static_cast<std::size_t>(k + e.nsp) * e.n;
-            const KsRows in_bundle = ks_digits(e, lt, k, tg, target_stride, m, coeff, ext, dj0, dj1);
+            const KsRows in_bundle = ks_digits(e, lt, k, tg, target_stride, m, coeff, ext, dj0, dj1, true);
             check(launch_ks_mac(e, lt.d_ks, lt.h_ks, in_bundle.inb, in_bundle.inb_stride, ext, ext_item, ext_item * m /* digit-major */,
-                                key.d_data, prod, 2 * ext_item, m, dj0, dj1),
+                                key.d_data, prod, 2 * ext_item, m, dj0, dj1, in_bundle.split_last),
                   "mac");
         }
 
@@ -494,6 +511,15 @@ namespace sealhip
                   "moddown_rescale_post");
         }
     } // namespace
+
+    // sealhip_debug_ks_split_last: would ks_products store the digit rows of a chunk of `count` items at level k without the
+    // transform's last layer? The decision ks_digits makes, with no launch.
+    bool ks_split_last_plan(Engine &e, int k, std::size_t count)
+    {
+        LevelTools &lt = e.level(k);
+        const u64 *const rows_not_read = reinterpret_cast<const u64 *>(&lt); // (a source is "gathered" by being non-null)
+        return ks_digits(e, lt, k, rows_not_read, 0, count, const_cast<u64 *>(rows_not_read), nullptr, 0, lt.h_ks.nd, true, true).split_last;
+    }
 
     // ------------------------------------------------------------------------------------------
     // switch_key_inplace (evaluator.cpp:2259-2368)

@@ -110,6 +110,8 @@ SYMBOLS = {
     "sealhip_debug_rns_constants": [_vp, _u32, _u32, _vp, _sz, C.POINTER(_sz)],
     "sealhip_debug_bfv_multiply_plan": [_vp, _u32, _u32, _u32, _i32, _vp],
     "sealhip_debug_behz_dot_split": [_vp, _u32, C.POINTER(C.c_int32)],
+    "sealhip_debug_ks_split_last": [_vp, _u32, _sz, C.POINTER(C.c_int32)],
+    "sealhip_debug_ntt_split_last": [_vp, _u32, _u32, _i32, _vp, _vp],
     "sealhip_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_ntt_negacyclic_harvey": [_vp, _vp, _sz, _u32, _u32],
     "sealhip_inverse_ntt_negacyclic_harvey_lazy": [_vp, _vp, _sz, _u32, _u32],
@@ -614,6 +616,18 @@ class Context:
         v = C.c_int32()
         _check(lib().sealhip_debug_behz_dot_split(self.handle, k, C.byref(v)))
         return v.value
+
+    def debug_ks_split_last(self, k, count):
+        """True where a key switch of a chunk of `count` items at level k stores its digit rows without the forward transform's
+        last layer and the inner product's pair form applies it (sealhip_debug_ks_split_last)"""
+        v = C.c_int32()
+        _check(lib().sealhip_debug_ks_split_last(self.handle, k, count, C.byref(v)))
+        return bool(v.value)
+
+    def debug_ntt_split_last(self, prime_index, src, dst, treatment=0, exact=False):
+        """one forward transform without its last layer of the N words of `src` on key prime prime_index, into `dst` as E | O
+        (sealhip_debug_ntt_split_last)"""
+        _check(lib().sealhip_debug_ntt_split_last(self.handle, prime_index, treatment, 1 if exact else 0, _ptr(src), _ptr(dst)))
 
     def galois_elt_from_step(self, step):
         v = C.c_uint32()

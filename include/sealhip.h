@@ -187,6 +187,18 @@ long sealhip_debug_bfv_multiply_plan(sealhip_context *ctx, uint32_t k, uint32_t 
 /* The split position (30 or 31) of the carry-free dot products of the exact-k BEHZ kernels at level k of a BFV context:
    what the level's constant tables are packed with (host-only contexts: would be packed with). 31 at k above 15. */
 long sealhip_debug_behz_dot_split(sealhip_context *ctx, uint32_t k, int32_t *out);
+/* Does a key switch whose inner product consumes the digit rows directly (relinearize, apply_galois, switch_key) store the
+   digit rows of a chunk of `count` items at level k without the forward transform's last layer, which the inner product's
+   pair form then applies? *out = 1 or 0. Device contexts. */
+long sealhip_debug_ks_split_last(sealhip_context *ctx, uint32_t k, size_t count, int32_t *out);
+/* One forward transform without its last layer, as the key switch launches it: the N words at src_device, taken as a row
+   on key prime `prime_index` (load treatment 0 none, 1 Barrett-63, 2 one conditional subtraction; exact != 0: the exact
+   Shoup quotient instead of the approximate one), go to dst_device (another buffer of N words) as E[0..N/2) | O[0..N/2): the
+   transforms, as rings of N/2, of the even- and the odd-indexed words, any representative below
+   (2 + 4 (log2 N - 1)) p. E_INVALIDARG where the form does not exist (rings other than 2^14..2^16, a prime outside its bound
+   or one that the floating-point instances take). */
+long sealhip_debug_ntt_split_last(sealhip_context *ctx, uint32_t prime_index, uint32_t treatment, int32_t exact,
+                                  const uint64_t *src_device, uint64_t *dst_device);
 
 /* ---------------------------------------------------------------- L2: NTT (util/ntt.h:189-368)
    data: count polynomials x rows x N, in place. `base` selects the primes of the `rows` rows of one
