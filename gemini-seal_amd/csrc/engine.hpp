@@ -19,6 +19,7 @@
 #include "devmath.hpp"
 #include "ntt_bounds.hpp"
 #include "ntt_select.hpp"
+#include "mac_select.hpp"
 #include "hostmath.hpp"
 #include "pool_scratch.hpp"
 #include "held_workspace.hpp"
@@ -455,8 +456,8 @@ namespace sealhip
     };
 
     // Launch shape of the elementwise kernels: kThreads lanes per block, one block per kThreads work items up to
-    // max_blocks; the kernels grid-stride the rest.
-    constexpr int kThreads = 256;
+    // max_blocks; the kernels grid-stride the rest. (kThreads, and blocks_for -- one lane per work item, no cap -- stand in
+    // mac_select.hpp, which a host compiler builds too.)
     inline unsigned grid_for(std::size_t work_items, std::size_t max_blocks = 256u * 16u)
     {
         const std::size_t blocks = (work_items + kThreads - 1) / kThreads;
@@ -715,7 +716,10 @@ namespace sealhip
                              std::size_t ext_digit_stride, const u64 *key, u64 *prod, std::size_t prod_stride,
                              std::size_t count, int j0 = 0, int j1 = -1, // digits [j0, j1) (default: all of the level)
                              bool pair = false); // the digit rows lack their last layer (kNttSplitLast): the pair form
-    bool ks_mac_has_pair_form(const Engine &e, const KsDev &h, std::size_t count, int j0, int j1);
+    inline bool ks_mac_has_pair_form(const Engine &e, const KsDev &h, std::size_t count, int j0, int j1) // (mac_select.hpp)
+    {
+        return ks_mac_has_pair_form(e.logn, h.nd, count, j0, j1);
+    }
     hipError_t launch_ks_moddown_pre(const Engine &e, const KsDev *d, const KsDev &h, const u64 *prod,
                                      std::size_t prod_stride, u64 *temp, std::size_t temp_stride, std::size_t npolys);
     // BFV only: steps 1-4 of the rescale + the add into the ciphertext in one kernel; top_deferred = the rows of prod
@@ -743,7 +747,7 @@ namespace sealhip
 
     // hoisted rotation (hoist.hip): the Galois elements of one launch, by value in the kernel arguments (nothing to upload,
     // so the launch is capturable): the NTT-form table T_g (Engine::galois_table), the key K_g, the element itself
-    constexpr int kHoistMaxElts = 16;
+    // (at most kHoistMaxElts of them: mac_select.hpp)
     struct HoistElts
     {
         int n;

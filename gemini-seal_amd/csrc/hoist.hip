@@ -7,6 +7,7 @@
 // the high bits of the index together), so the 64 words a wave gathers lie in the same four 128-byte lines a straight
 // read of one aligned 64-word block would touch: no traffic amplification, no LDS staging.
 #include "engine.hpp"
+#include "instance_dispatch.hpp"
 
 namespace sealhip
 {
@@ -590,11 +591,6 @@ namespace sealhip
                 o[poly] = v1;
             }
         }
-
-        inline unsigned blocks_for(std::size_t lanes)
-        {
-            return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
-        }
     } // namespace
 
     hipError_t launch_hoist_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
@@ -604,52 +600,18 @@ namespace sealhip
     {
         if (!count || !elts.n)
             return hipSuccess;
-        if (elts.n < 0 || elts.n > kHoistMaxElts)
+        const MacChoice c = select_hoist_mac(e.logn, h.nd, static_cast<std::size_t>(h.k + h.nsp), elts.n, count);
+        if (c.family == kMacRefused)
             return hipErrorInvalidValue;
-        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
-        // ciphertexts per key load, as launch_ks_mac picks it: 8, or 16 / 64 when that still leaves 4096 workgroups
-        const std::size_t key_bytes = (2ull * h.nd * rows * elts.n) << (e.logn + 3);
-        const std::size_t cap = key_bytes > (std::size_t(48) << 20) ? 64 : 16;
-        std::size_t group = count < 8 ? count : 8;
-        for (std::size_t g = cap; g > 8; g >>= 1)
-            if ((((count + g - 1) / g * rows * elts.n) << e.logn) / kThreads >= 4096)
-            {
-                group = g;
-                break;
-            }
-        const std::size_t n_groups = (count + group - 1) / group;
-        const std::size_t glanes = (n_groups * rows * elts.n) << e.logn;
         ProfScope prof(e, "hoist_mac", 0);
-#define SEALHIP_HOIST_MAC(ND)                                                                                       \
-    case ND:                                                                                                        \
-        hoist_mac_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(                                  \
-            d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, prod, prod_stride, count, \
-            e.logn, group, n_groups);                                                                \
-        break;
-        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
-        {
-            SEALHIP_HOIST_MAC(1)
-            SEALHIP_HOIST_MAC(2)
-            SEALHIP_HOIST_MAC(3)
-            SEALHIP_HOIST_MAC(4)
-            SEALHIP_HOIST_MAC(5)
-            SEALHIP_HOIST_MAC(6)
-            SEALHIP_HOIST_MAC(7)
-            SEALHIP_HOIST_MAC(8)
-            SEALHIP_HOIST_MAC(9)
-            SEALHIP_HOIST_MAC(10)
-            SEALHIP_HOIST_MAC(11)
-            SEALHIP_HOIST_MAC(12)
-            SEALHIP_HOIST_MAC(13)
-            SEALHIP_HOIST_MAC(14)
-            SEALHIP_HOIST_MAC(15)
-            SEALHIP_HOIST_MAC(16)
-        default: // more than 16 digits, or a ring smaller than a workgroup
-            hoist_mac_loop_kernel<<<blocks_for((count * rows * elts.n) << e.logn), kThreads, 0, e.lane().stream>>>(
-                d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, prod, prod_stride, count, e.logn,
-                h.nd);
-        }
-#undef SEALHIP_HOIST_MAC
+        const hipStream_t stream = e.lane().stream;
+        if (!dispatch_mac_digits(c.nd, [&](auto nd) {
+                hoist_mac_kernel<decltype(nd)::value><<<c.blocks, kThreads, 0, stream>>>(
+                    d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, prod, prod_stride, count, e.logn,
+                    c.group, c.n_groups);
+            })) // more than 16 digits, or a ring smaller than a workgroup
+            hoist_mac_loop_kernel<<<c.blocks, kThreads, 0, stream>>>(d, e.d_primes, target, target_stride, ext, ext_stride,
+                                                                    ext_digit_stride, elts, prod, prod_stride, count, e.logn, h.nd);
         return hipGetLastError();
     }
 
@@ -672,53 +634,21 @@ namespace sealhip
     {
         if (!count || !elts.n || !n_sums)
             return hipSuccess;
-        if (elts.n < 0 || elts.n > kHoistMaxElts)
+        const MacChoice c = select_hoist_dot_mac(e.logn, h.nd, static_cast<std::size_t>(h.k + h.nsp), elts.n, count, n_sums);
+        if (c.family == kMacRefused)
             return hipErrorInvalidValue;
-        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
-        // the four slots of a lane: as many sums as the call has (1, 2 or 4), the rest ciphertexts
-        const int S = n_sums >= 3 ? 4 : static_cast<int>(n_sums);
-        const std::size_t groups = ((n_sums + S - 1) / S) * ((count + 4 / S - 1) / (4 / S));
-        const std::size_t glanes = (groups * rows) << e.logn;
         ProfScope prof(e, "hoist_dot_mac", 0);
-#define SEALHIP_HOIST_DOT_ARGS                                                                                             \
-    d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, w_sum_stride, acc, acc_stride, count, \
-        n_sums, e.logn
-#define SEALHIP_HOIST_DOT(ND)                                                                                              \
-    case ND:                                                                                                               \
-        if (S == 1)                                                                                                        \
-            hoist_dot_mac_kernel<ND, 1><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
-                                                                                              add ? 1 : 0);                \
-        else if (S == 2)                                                                                                   \
-            hoist_dot_mac_kernel<ND, 2><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
-                                                                                              add ? 1 : 0);                \
-        else                                                                                                               \
-            hoist_dot_mac_kernel<ND, 4><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_DOT_ARGS,      \
-                                                                                              add ? 1 : 0);                \
-        break;
-        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
-        {
-            SEALHIP_HOIST_DOT(1)
-            SEALHIP_HOIST_DOT(2)
-            SEALHIP_HOIST_DOT(3)
-            SEALHIP_HOIST_DOT(4)
-            SEALHIP_HOIST_DOT(5)
-            SEALHIP_HOIST_DOT(6)
-            SEALHIP_HOIST_DOT(7)
-            SEALHIP_HOIST_DOT(8)
-            SEALHIP_HOIST_DOT(9)
-            SEALHIP_HOIST_DOT(10)
-            SEALHIP_HOIST_DOT(11)
-            SEALHIP_HOIST_DOT(12)
-            SEALHIP_HOIST_DOT(13)
-            SEALHIP_HOIST_DOT(14)
-            SEALHIP_HOIST_DOT(15)
-            SEALHIP_HOIST_DOT(16)
-        default: // more than 16 digits, or a ring smaller than a workgroup
-            hoist_dot_mac_loop_kernel<<<blocks_for((n_sums * count * rows) << e.logn), kThreads, 0, e.lane().stream>>>(
-                SEALHIP_HOIST_DOT_ARGS, h.nd, add ? 1 : 0);
-        }
-#undef SEALHIP_HOIST_DOT
-#undef SEALHIP_HOIST_DOT_ARGS
+        const hipStream_t stream = e.lane().stream;
+        if (!dispatch_mac_digits(c.nd, [&](auto nd) {
+                dispatch_among<1, 2, 4>(c.slots, [&](auto slots) {
+                    hoist_dot_mac_kernel<decltype(nd)::value, decltype(slots)::value><<<c.blocks, kThreads, 0, stream>>>(
+                        d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, elts, w_sum_stride, acc, acc_stride,
+                        count, n_sums, e.logn, add ? 1 : 0);
+                });
+            })) // more than 16 digits, or a ring smaller than a workgroup
+            hoist_dot_mac_loop_kernel<<<c.blocks, kThreads, 0, stream>>>(d, e.d_primes, target, target_stride, ext, ext_stride,
+                                                                        ext_digit_stride, elts, w_sum_stride, acc, acc_stride, count,
+                                                                        n_sums, e.logn, h.nd, add ? 1 : 0);
         return hipGetLastError();
     }
 
@@ -744,42 +674,19 @@ namespace sealhip
     {
         if (!count || !elts.n)
             return hipSuccess;
-        if (elts.n < 0 || elts.n > kHoistMaxElts)
+        const MacChoice c = select_hoist_giant_mac(e.logn, h.nd, static_cast<std::size_t>(h.k + h.nsp), elts.n, count);
+        if (c.family == kMacRefused)
             return hipErrorInvalidValue;
-        const std::size_t rows = static_cast<std::size_t>(h.k + h.nsp);
-        const std::size_t glanes = (((count + 3) / 4) * rows) << e.logn; // four ciphertexts per lane
         ProfScope prof(e, "hoist_giant_mac", 0);
-#define SEALHIP_HOIST_GIANT_ARGS \
-    d, e.d_primes, elts, inb_stride, ext_stride, ext_digit_stride, accj_stride, acc, acc_stride, count, e.logn
-#define SEALHIP_HOIST_GIANT(ND)                                                                                          \
-    case ND:                                                                                                             \
-        hoist_giant_mac_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(SEALHIP_HOIST_GIANT_ARGS,       \
-                                                                                         add ? 1 : 0);                   \
-        break;
-        switch (e.n >= static_cast<std::size_t>(kThreads) ? h.nd : 0) // (rings below a workgroup: the per-lane kernel)
-        {
-            SEALHIP_HOIST_GIANT(1)
-            SEALHIP_HOIST_GIANT(2)
-            SEALHIP_HOIST_GIANT(3)
-            SEALHIP_HOIST_GIANT(4)
-            SEALHIP_HOIST_GIANT(5)
-            SEALHIP_HOIST_GIANT(6)
-            SEALHIP_HOIST_GIANT(7)
-            SEALHIP_HOIST_GIANT(8)
-            SEALHIP_HOIST_GIANT(9)
-            SEALHIP_HOIST_GIANT(10)
-            SEALHIP_HOIST_GIANT(11)
-            SEALHIP_HOIST_GIANT(12)
-            SEALHIP_HOIST_GIANT(13)
-            SEALHIP_HOIST_GIANT(14)
-            SEALHIP_HOIST_GIANT(15)
-            SEALHIP_HOIST_GIANT(16)
-        default: // more than 16 digits, or a ring smaller than a workgroup
-            hoist_giant_mac_loop_kernel<<<blocks_for((count * rows) << e.logn), kThreads, 0, e.lane().stream>>>(
-                SEALHIP_HOIST_GIANT_ARGS, h.nd, add ? 1 : 0);
-        }
-#undef SEALHIP_HOIST_GIANT
-#undef SEALHIP_HOIST_GIANT_ARGS
+        const hipStream_t stream = e.lane().stream;
+        if (!dispatch_mac_digits(c.nd, [&](auto nd) {
+                hoist_giant_mac_kernel<decltype(nd)::value><<<c.blocks, kThreads, 0, stream>>>(
+                    d, e.d_primes, elts, inb_stride, ext_stride, ext_digit_stride, accj_stride, acc, acc_stride, count, e.logn,
+                    add ? 1 : 0);
+            })) // more than 16 digits, or a ring smaller than a workgroup
+            hoist_giant_mac_loop_kernel<<<c.blocks, kThreads, 0, stream>>>(d, e.d_primes, elts, inb_stride, ext_stride,
+                                                                          ext_digit_stride, accj_stride, acc, acc_stride, count, e.logn,
+                                                                          h.nd, add ? 1 : 0);
         return hipGetLastError();
     }
 

@@ -10,6 +10,7 @@
 // all digits, streaming the key slices.
 #include <cstdlib>
 #include "engine.hpp"
+#include "instance_dispatch.hpp"
 
 namespace sealhip
 {
@@ -347,11 +348,6 @@ namespace sealhip
                 }
         }
 
-        // digits up to which the pair form keeps the next ciphertext's words in flight (194 registers at nd = 7; without it 138 and the
-        // same time within the spread, profiles/r18/ks_split_last_ab.txt; 24 registers more per digit: from nd = 10 on the prefetch
-        // would leave one wave per SIMD. Measured at nd = 7 only.)
-        constexpr int kKsPairPrefetchDigits = 8;
-
         // rescale_special_rns_inplace, steps 1-2 (multi_special_primes.cpp:253-282): from the (coefficient
         // form) special rows of one polynomial compute temp_i for every ciphertext prime i.
         __global__ __launch_bounds__(kThreads) void ks_moddown_pre_kernel(const KsDev *__restrict__ d,
@@ -678,11 +674,6 @@ namespace sealhip
             if (poly & 1)
                 note_nonzero(tflags, poly >> 1, w);
         }
-
-        inline unsigned blocks_for(std::size_t lanes)
-        {
-            return static_cast<unsigned>((lanes + kThreads - 1) / kThreads);
-        }
     } // namespace
 
     hipError_t launch_ks_modup(const Engine &e, const KsDev *d, const KsDev &, const u64 *coeff,
@@ -697,12 +688,6 @@ namespace sealhip
         return hipGetLastError();
     }
 
-    // the pair form exists where the items kernel does: all digits in one call, batches of at least 16, up to 16 digits
-    bool ks_mac_has_pair_form(const Engine &e, const KsDev &h, std::size_t count, int j0, int j1)
-    {
-        return e.logn >= 14 && count >= 16 && j0 == 0 && j1 == h.nd && h.nd >= 1 && h.nd <= 16;
-    }
-
     hipError_t launch_ks_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *target,
                              std::size_t target_stride, const u64 *ext, std::size_t ext_stride,
                              std::size_t ext_digit_stride, const u64 *key, u64 *prod, std::size_t prod_stride,
@@ -712,93 +697,29 @@ namespace sealhip
             return hipSuccess;
         if (j1 < 0)
             j1 = h.nd;
-        if (j0 < 0 || j0 > j1 || j1 > h.nd)
+        const MacChoice c = select_ks_mac(e.logn, h.nd, static_cast<std::size_t>(h.k + h.nsp), count, j0, j1, pair);
+        if (c.family == kMacRefused)
             return hipErrorInvalidValue;
-        const bool all_digits = j0 == 0 && j1 == h.nd;
-        if (pair && !ks_mac_has_pair_form(e, h, count, j0, j1)) // (digit rows without their last layer: no other kernel reads them)
-            return hipErrorInvalidValue;
-        const u64 *tg = target;
-        const std::size_t lanes = (count * static_cast<std::size_t>(h.k + h.nsp)) << e.logn;
         ProfScope prof(e, "ks_mac", 0);
-        // ciphertexts per key load: 8 for small batches (enough workgroups to fill the chip), else 16 -- or 64 when the key
-        // slices this kernel reads (2 * nd * rows rows) are too large to stay in the memory-side cache between groups
-        // (profiles/r02/ks_mac_group.txt: config 4, 69 MB of key: 9.15 -> 7.96 ms per step; config 5, 251 MB: 9.38 -> 7.66;
-        // config 3, 29 MB: 3.68 -> 3.60 at 16, but 3.9-4.1 at 32)
-        const std::size_t key_bytes = (2ull * h.nd * (h.k + h.nsp)) << (e.logn + 3);
-        // (the largest candidate that still leaves 4096 workgroups -- two full rounds of the chip's resident set)
-        const std::size_t cap = key_bytes > (std::size_t(48) << 20) ? 64 : 16;
-        std::size_t mac_group = 8;
-        for (std::size_t g = cap; g > 8; g >>= 1)
-            if ((((count + g - 1) / g * static_cast<std::size_t>(h.k + h.nsp)) << e.logn) / kThreads >= 4096)
-            {
-                mac_group = g;
-                break;
-            }
-        const std::size_t groups = (count + mac_group - 1) / mac_group;
-        const std::size_t glanes = (groups * static_cast<std::size_t>(h.k + h.nsp)) << e.logn;
-        if (pair)
-        {
-            // one lane per pair of coefficients: half the lanes, the items kernel's group size (mac_group stays as it is)
-            const std::size_t planes = (groups * static_cast<std::size_t>(h.k + h.nsp)) << (e.logn - 1);
-#define SEALHIP_KS_MAC_PAIR(ND)                                                                                                          \
-    case ND:                                                                                                                             \
-        ks_mac_pair_kernel<ND, (ND <= kKsPairPrefetchDigits)><<<blocks_for(planes), kThreads, 0, e.lane().stream>>>(                    \
-            d, e.d_primes, tg, target_stride, ext, ext_stride, ext_digit_stride, key, prod, prod_stride, count, e.logn, mac_group); \
-        break;
-            switch (h.nd)
-            {
-                SEALHIP_KS_MAC_PAIR(1)
-                SEALHIP_KS_MAC_PAIR(2)
-                SEALHIP_KS_MAC_PAIR(3)
-                SEALHIP_KS_MAC_PAIR(4)
-                SEALHIP_KS_MAC_PAIR(5)
-                SEALHIP_KS_MAC_PAIR(6)
-                SEALHIP_KS_MAC_PAIR(7)
-                SEALHIP_KS_MAC_PAIR(8)
-                SEALHIP_KS_MAC_PAIR(9)
-                SEALHIP_KS_MAC_PAIR(10)
-                SEALHIP_KS_MAC_PAIR(11)
-                SEALHIP_KS_MAC_PAIR(12)
-                SEALHIP_KS_MAC_PAIR(13)
-                SEALHIP_KS_MAC_PAIR(14)
-                SEALHIP_KS_MAC_PAIR(15)
-                SEALHIP_KS_MAC_PAIR(16)
-            default: return hipErrorInvalidValue;
-            }
-#undef SEALHIP_KS_MAC_PAIR
-            return hipGetLastError();
-        }
-#define SEALHIP_KS_MAC(ND)                                                                                          \
-    case ND:                                                                                                        \
-        ks_mac_items_kernel<ND><<<blocks_for(glanes), kThreads, 0, e.lane().stream>>>(                                     \
-            d, e.d_primes, tg, target_stride, ext, ext_stride, ext_digit_stride, key, prod, prod_stride, count,    \
-            e.logn, mac_group);                                                                                     \
-        break;
-        switch (count >= 16 && all_digits ? h.nd : 0)
-        {
-            SEALHIP_KS_MAC(1)
-            SEALHIP_KS_MAC(2)
-            SEALHIP_KS_MAC(3)
-            SEALHIP_KS_MAC(4)
-            SEALHIP_KS_MAC(5)
-            SEALHIP_KS_MAC(6)
-            SEALHIP_KS_MAC(7)
-            SEALHIP_KS_MAC(8)
-            SEALHIP_KS_MAC(9)
-            SEALHIP_KS_MAC(10)
-            SEALHIP_KS_MAC(11)
-            SEALHIP_KS_MAC(12)
-            SEALHIP_KS_MAC(13)
-            SEALHIP_KS_MAC(14)
-            SEALHIP_KS_MAC(15)
-            SEALHIP_KS_MAC(16)
-        default: // small batches or more than 16 digits: one lane per (ciphertext, row, coefficient)
-            ks_mac_kernel<<<blocks_for(lanes), kThreads, 0, e.lane().stream>>>(d, e.d_primes, tg, target_stride, ext, ext_stride,
-                                                                        ext_digit_stride, key, prod, prod_stride, count,
-                                                                        e.logn, j0, j1);
-        }
-#undef SEALHIP_KS_MAC
-        return hipGetLastError();
+        const hipStream_t stream = e.lane().stream;
+        bool launched = true;
+        if (c.family == kMacPair)
+            launched = dispatch_mac_digits(c.nd, [&](auto nd) {
+                constexpr int ND = decltype(nd)::value;
+                ks_mac_pair_kernel<ND, (ND <= kKsPairPrefetchDigits)><<<c.blocks, kThreads, 0, stream>>>(
+                    d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, key, prod, prod_stride, count, e.logn,
+                    c.group);
+            });
+        else if (c.family == kMacItems)
+            launched = dispatch_mac_digits(c.nd, [&](auto nd) {
+                ks_mac_items_kernel<decltype(nd)::value><<<c.blocks, kThreads, 0, stream>>>(
+                    d, e.d_primes, target, target_stride, ext, ext_stride, ext_digit_stride, key, prod, prod_stride, count, e.logn,
+                    c.group);
+            });
+        else // small batches, a digit range or more than 16 digits: one lane per (ciphertext, row, coefficient)
+            ks_mac_kernel<<<c.blocks, kThreads, 0, stream>>>(d, e.d_primes, target, target_stride, ext, ext_stride,
+                                                            ext_digit_stride, key, prod, prod_stride, count, e.logn, j0, j1);
+        return launched ? hipGetLastError() : hipErrorInvalidValue; // (the selector names no instance outside the range)
     }
 
     hipError_t launch_ks_moddown_pre(const Engine &e, const KsDev *d, const KsDev &, const u64 *prod,
@@ -820,18 +741,13 @@ namespace sealhip
             return hipSuccess;
         const std::size_t lanes = npolys << (e.logn - 1); // one lane per (polynomial, coefficient pair)
         ProfScope prof(e, "ks_moddown_bfv", 0);
-#define SEALHIP_MODDOWN_BFV(DEFER_, ONE_)                                                                            \
-    ks_moddown_bfv_kernel<DEFER_, ONE_><<<blocks_for(lanes), kThreads, 0, e.lane().stream>>>(                              \
-        d, e.d_primes, prod, prod_stride, ct, ct_item_stride, npolys, e.logn, c0_src, c0_stride, e.lane().tsink_arm)
-        if (top_deferred && h.nsp == 1)
-            SEALHIP_MODDOWN_BFV(true, true);
-        else if (top_deferred)
-            SEALHIP_MODDOWN_BFV(true, false);
-        else if (h.nsp == 1)
-            SEALHIP_MODDOWN_BFV(false, true);
-        else
-            SEALHIP_MODDOWN_BFV(false, false);
-#undef SEALHIP_MODDOWN_BFV
+        dispatch_bool(top_deferred, [&](auto defer) {
+            dispatch_bool(h.nsp == 1, [&](auto one) {
+                ks_moddown_bfv_kernel<decltype(defer)::value, decltype(one)::value>
+                    <<<blocks_for(lanes), kThreads, 0, e.lane().stream>>>(d, e.d_primes, prod, prod_stride, ct, ct_item_stride,
+                                                                          npolys, e.logn, c0_src, c0_stride, e.lane().tsink_arm);
+            });
+        });
         return hipGetLastError();
     }
 
@@ -867,24 +783,12 @@ namespace sealhip
         if (!npolys)
             return hipSuccess;
         ProfScope prof(e, "ks_moddown_rescale_pre", 0);
-#define SEALHIP_RESCALE_PRE(ND1)                                                                                     \
-    ks_moddown_rescale_pre_kernel<ND1><<<blocks_for(npolys << e.logn), kThreads, 0, e.lane().stream>>>(                    \
-        d, e.d_primes, acc, acc_stride, temp, npolys, e.logn)
-        switch (h.nsp + 1)
-        {
-        case 2:
-            SEALHIP_RESCALE_PRE(2);
-            break;
-        case 3:
-            SEALHIP_RESCALE_PRE(3);
-            break;
-        case 4:
-            SEALHIP_RESCALE_PRE(4);
-            break;
-        default:
-            SEALHIP_RESCALE_PRE(0);
-        }
-#undef SEALHIP_RESCALE_PRE
+        const auto launch = [&](auto nd1) {
+            ks_moddown_rescale_pre_kernel<decltype(nd1)::value><<<blocks_for(npolys << e.logn), kThreads, 0, e.lane().stream>>>(
+                d, e.d_primes, acc, acc_stride, temp, npolys, e.logn);
+        };
+        if (!dispatch_int<2, 4>(h.nsp + 1, launch)) // (larger sets: the loop form)
+            launch(std::integral_constant<int, 0>{});
         return hipGetLastError();
     }
 

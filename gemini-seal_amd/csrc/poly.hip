@@ -2,6 +2,7 @@
 // Galois automorphisms (native/src/seal/util/galois.cpp) over batches of RNS rows.
 // All of these are pure HBM streaming: 16-byte loads/stores, two coefficients per lane.
 #include "engine.hpp"
+#include "instance_dispatch.hpp"
 
 #include <algorithm>
 
@@ -871,25 +872,11 @@ namespace sealhip
         return hipGetLastError();
     }
 
-    namespace
-    {
-        template <int S>
-        void lincomb_launch(const Engine &e, unsigned grid, const LinTerms &terms, std::size_t x_stride, const u64 *w,
-                            std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
-                            const RowMap &map, std::size_t pairs, std::size_t count, bool add_partial, std::size_t flag_sum_stride)
-        {
-            lincomb_kernel<S><<<grid, kThreads, 0, e.lane().stream>>>(terms, x_stride, w, w_sum_stride, constant, const_mode, out,
-                                                                      out_sum_stride, e.d_primes, map, e.logn, pairs, count,
-                                                                      e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
-        }
-    } // namespace
-
     hipError_t launch_lincomb(const Engine &e, const LinTerms &terms, int size, std::size_t x_stride, const u64 *w,
                               std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
                               int n_sums, std::size_t count, const RowMap &map, bool add_partial, std::size_t flag_sum_stride)
     {
         static_assert(bounds::lincomb_group_admits(kLinGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
-        static_assert(kLinTile == 4, "the dispatch below has one instance per tile size");
         if (terms.n < 1 || terms.n > kLinGroup || n_sums < 1 || n_sums > kLinTile || size < 1 || map.rows < 1 ||
             map.rows > kMaxRows || (constant && const_mode != 1 && const_mode != 2))
             return hipErrorInvalidValue;
@@ -898,37 +885,14 @@ namespace sealhip
             return hipSuccess;
         ProfScope prof(e, "lincomb", 0);
         const unsigned grid = grid_for(pairs * count);
-#define SEALHIP_LINCOMB_CASE(S)                                                                                              \
-    case S:                                                                                                                  \
-        lincomb_launch<S>(e, grid, terms, x_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, map, pairs,   \
-                          count, add_partial, flag_sum_stride);                                                              \
-        break;
-        switch (n_sums)
-        {
-            SEALHIP_LINCOMB_CASE(1)
-            SEALHIP_LINCOMB_CASE(2)
-            SEALHIP_LINCOMB_CASE(3)
-            SEALHIP_LINCOMB_CASE(4)
-        }
-#undef SEALHIP_LINCOMB_CASE
+        // (one instance per number of sums in a tile: n_sums was checked against the range above)
+        dispatch_int<1, kLinTile>(n_sums, [&](auto s) {
+            lincomb_kernel<decltype(s)::value><<<grid, kThreads, 0, e.lane().stream>>>(
+                terms, x_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, e.d_primes, map, e.logn, pairs, count,
+                e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
+        });
         return hipGetLastError();
     }
-
-    namespace
-    {
-        template <int S>
-        void lincomb_levels_launch(const Engine &e, unsigned grid, const LinLevelTerms &terms, std::size_t out_stride, const u64 *w,
-                                   std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out,
-                                   std::size_t out_sum_stride, const RowMap &map, std::size_t pairs, std::size_t count,
-                                   bool add_partial, std::size_t flag_sum_stride)
-        {
-            if constexpr (S <= kLinLevelsTile) // (a smaller tile instantiates fewer kernels)
-                lincomb_levels_kernel<S><<<grid, kThreads, 0, e.lane().stream>>>(terms, out_stride, w, w_sum_stride, constant,
-                                                                                 const_mode, out, out_sum_stride, e.d_primes, map,
-                                                                                 e.logn, pairs, count, e.lane().tsink_arm,
-                                                                                 flag_sum_stride, add_partial ? 1 : 0);
-        }
-    } // namespace
 
     hipError_t launch_lincomb_levels(const Engine &e, const LinLevelTerms &terms, int size, std::size_t out_stride, const u64 *w,
                                      std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out,
@@ -936,7 +900,6 @@ namespace sealhip
                                      bool add_partial, std::size_t flag_sum_stride)
     {
         static_assert(bounds::lincomb_group_admits(kLinGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
-        static_assert(kLinLevelsTile <= 4, "the dispatch below has one instance per tile size");
         if (terms.n < 1 || terms.n > kLinGroup || n_sums < 1 || n_sums > kLinLevelsTile || size < 1 || map.rows < 1 ||
             map.rows > kMaxRows || (constant && const_mode != 1 && const_mode != 2))
             return hipErrorInvalidValue;
@@ -948,19 +911,12 @@ namespace sealhip
             return hipSuccess;
         ProfScope prof(e, "lincomb_levels", 0);
         const unsigned grid = grid_for(pairs * count);
-#define SEALHIP_LINCOMB_CASE(S)                                                                                              \
-    case S:                                                                                                                  \
-        lincomb_levels_launch<S>(e, grid, terms, out_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, map, \
-                                 pairs, count, add_partial, flag_sum_stride);                                                \
-        break;
-        switch (n_sums)
-        {
-            SEALHIP_LINCOMB_CASE(1)
-            SEALHIP_LINCOMB_CASE(2)
-            SEALHIP_LINCOMB_CASE(3)
-            SEALHIP_LINCOMB_CASE(4)
-        }
-#undef SEALHIP_LINCOMB_CASE
+        // (a smaller tile instantiates fewer kernels: the range is the tile)
+        dispatch_int<1, kLinLevelsTile>(n_sums, [&](auto s) {
+            lincomb_levels_kernel<decltype(s)::value><<<grid, kThreads, 0, e.lane().stream>>>(
+                terms, out_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, e.d_primes, map, e.logn, pairs, count,
+                e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
+        });
         return hipGetLastError();
     }
 

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "engine.hpp"
+#include "instance_dispatch.hpp"
 
 namespace sealhip
 {
@@ -835,20 +836,17 @@ namespace sealhip
         }
     } // namespace
 
-#define SEALHIP_DISPATCH_K(kval, KERNEL, ...)                                             \
-    do                                                                                    \
-    {                                                                                     \
-        if ((kval) <= 4)                                                                  \
-            KERNEL<4><<<grid, kThreads, 0, e.lane().stream>>>(__VA_ARGS__);                      \
-        else if ((kval) <= 8)                                                             \
-            KERNEL<8><<<grid, kThreads, 0, e.lane().stream>>>(__VA_ARGS__);                      \
-        else if ((kval) <= 16)                                                            \
-            KERNEL<16><<<grid, kThreads, 0, e.lane().stream>>>(__VA_ARGS__);                     \
-        else if ((kval) <= 32)                                                            \
-            KERNEL<32><<<grid, kThreads, 0, e.lane().stream>>>(__VA_ARGS__);                     \
-        else                                                                              \
-            KERNEL<64><<<grid, kThreads, 0, e.lane().stream>>>(__VA_ARGS__);                     \
-    } while (0)
+    namespace
+    {
+        // The step-by-step kernels are instantiated for row counts rounded up to 4, 8, 16, 32 and 64 (kMaxModuli):
+        // f(integral_constant<int, KM>) for the smallest of them that holds k.
+        template <class F>
+        void dispatch_k_bucket(int k, F &&f)
+        {
+            static_assert(kMaxModuli == 64, "the largest bucket holds every level");
+            dispatch_among<4, 8, 16, 32, 64>(k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64))), f);
+        }
+    } // namespace
 
     hipError_t launch_fastbconv_m_tilde(const Engine &e, const RnsDev *d, const RnsDev &h, const u64 *in,
                                         std::size_t in_stride, u64 *out, std::size_t out_stride, std::size_t count)
@@ -857,7 +855,10 @@ namespace sealhip
             return hipSuccess;
         const unsigned grid = blocks_for(count, e.logn);
         ProfScope prof(e, "fastbconv_m_tilde", 0);
-        SEALHIP_DISPATCH_K(h.k, fastbconv_m_tilde_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+        dispatch_k_bucket(h.k, [&](auto km) {
+            fastbconv_m_tilde_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
+                                                                                                  out_stride, count, e.logn);
+        });
         return hipGetLastError();
     }
 
@@ -874,31 +875,18 @@ namespace sealhip
 
     namespace
     {
-        template <int KM, int S = 31>
-        void lift2_launch(const Engine &e, const RnsDev *d, const u64 *in, std::size_t in_stride, u64 *out, std::size_t out_stride,
-                          std::size_t count, unsigned grid, bool top_layer)
+        // The fused BEHZ kernels' exact-k instances: f(KM = -k, S) for the plan's code k = 1 .. 15, S the split the level's
+        // tables are packed with (RnsDev::dot_split: 30, else 31). false: the code names the generic instance (KM = 32).
+        constexpr int kBehzDefaultSplit = 31;
+        template <class F>
+        bool dispatch_behz_exact(int code, int dot_split, F &&f)
         {
-            if constexpr (KM < 0)
-            {
-                if (top_layer)
-                {
-                    bfv_lift2_kernel<KM, true, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
-                                                                                          out_stride, count, e.logn);
-                    return;
-                }
-            }
-            bfv_lift2_kernel<KM, false, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride,
-                                                                                   count, e.logn);
-        }
-        // the exact-k instance of the split the level's tables are packed with (RnsDev::dot_split)
-        template <int KM>
-        void lift2_launch_split(int split, const Engine &e, const RnsDev *d, const u64 *in, std::size_t in_stride, u64 *out,
-                                std::size_t out_stride, std::size_t count, unsigned grid, bool top_layer)
-        {
-            if (split == 30)
-                lift2_launch<KM, 30>(e, d, in, in_stride, out, out_stride, count, grid, top_layer);
-            else
-                lift2_launch<KM, 31>(e, d, in, in_stride, out, out_stride, count, grid, top_layer);
+            return dispatch_int<1, bounds::kBehzExactMaxK>(code, [&](auto k) {
+                dispatch_bool(dot_split == 30, [&](auto s30) {
+                    f(std::integral_constant<int, -decltype(k)::value>{},
+                      std::integral_constant<int, decltype(s30)::value ? 30 : kBehzDefaultSplit>{});
+                });
+            });
         }
     } // namespace
 
@@ -933,32 +921,21 @@ namespace sealhip
         ProfScope prof(e, "bfv_lift", 0);
         if (plan.lift_kernel != kBehzStepwise)
         {
-#define SEALHIP_LIFT2(KM) lift2_launch_split<KM>(h.dot_split, e, d, in, in_stride, out, out_stride, count, grid, top_layer)
-#define SEALHIP_LIFT2G(KM) lift2_launch<KM>(e, d, in, in_stride, out, out_stride, count, grid, top_layer)
-            switch (plan.lift_kernel)
-            {
-            case 1: SEALHIP_LIFT2(-1); break;
-            case 2: SEALHIP_LIFT2(-2); break;
-            case 3: SEALHIP_LIFT2(-3); break;
-            case 4: SEALHIP_LIFT2(-4); break;
-            case 5: SEALHIP_LIFT2(-5); break;
-            case 6: SEALHIP_LIFT2(-6); break;
-            case 7: SEALHIP_LIFT2(-7); break;
-            case 8: SEALHIP_LIFT2(-8); break;
-            case 9: SEALHIP_LIFT2(-9); break;
-            case 10: SEALHIP_LIFT2(-10); break;
-            case 11: SEALHIP_LIFT2(-11); break;
-            case 12: SEALHIP_LIFT2(-12); break;
-            case 13: SEALHIP_LIFT2(-13); break;
-            case 14: SEALHIP_LIFT2(-14); break;
-            case 15: SEALHIP_LIFT2(-15); break;
-            default: SEALHIP_LIFT2G(32); break;
-            }
-#undef SEALHIP_LIFT2
-#undef SEALHIP_LIFT2G
+            const auto launch = [&](auto km, auto top, auto split) {
+                bfv_lift2_kernel<decltype(km)::value, decltype(top)::value, decltype(split)::value>
+                    <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+            };
+            // (only the exact-k instances apply the top layer)
+            if (!dispatch_behz_exact(plan.lift_kernel, h.dot_split,
+                                     [&](auto km, auto split) { dispatch_bool(top_layer, [&](auto top) { launch(km, top, split); }); }))
+                launch(std::integral_constant<int, kBehzGeneric>{}, std::false_type{},
+                       std::integral_constant<int, kBehzDefaultSplit>{});
             return hipGetLastError();
         }
-        SEALHIP_DISPATCH_K(h.k, bfv_lift_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+        dispatch_k_bucket(h.k, [&](auto km) {
+            bfv_lift_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride,
+                                                                                         count, e.logn);
+        });
         return hipGetLastError();
     }
 
@@ -969,8 +946,10 @@ namespace sealhip
             return hipSuccess;
         const unsigned grid = blocks_for(count, e.logn);
         ProfScope prof(e, "fast_floor", 0);
-        SEALHIP_DISPATCH_K(h.k, fast_floor_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn,
-                           mul_t);
+        dispatch_k_bucket(h.k, [&](auto km) {
+            fast_floor_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
+                                                                                           out_stride, count, e.logn, mul_t);
+        });
         return hipGetLastError();
     }
 
@@ -981,7 +960,10 @@ namespace sealhip
             return hipSuccess;
         const unsigned grid = blocks_for(count, e.logn);
         ProfScope prof(e, "fastbconv_sk", 0);
-        SEALHIP_DISPATCH_K(h.k, fastbconv_sk_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+        dispatch_k_bucket(h.k, [&](auto km) {
+            fastbconv_sk_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
+                                                                                             out_stride, count, e.logn);
+        });
         return hipGetLastError();
     }
 
@@ -1001,52 +983,24 @@ namespace sealhip
         ProfScope prof(e, "bfv_floor_sk", 0);
         if (plan.floor_kernel != kBehzStepwise)
         {
-#define SEALHIP_FLOOR2S(KM, S)                                                                                      \
-    do                                                                                                               \
-    {                                                                                                                \
-        if (deferred_top)                                                                                            \
-            bfv_floor_sk2_kernel<KM, true, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,    \
-                                                                              out_stride, count, e.logn,            \
-                                                                              deferred_top == 2 ? 1 : 0, tflags);   \
-        else                                                                                                         \
-            bfv_floor_sk2_kernel<KM, false, S><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,   \
-                                                                               out_stride, count, e.logn, 0, tflags); \
-    } while (0)
-// the exact-k instance of the split the level's tables are packed with (RnsDev::dot_split)
-#define SEALHIP_FLOOR2(KM)                                                                                          \
-    do                                                                                                               \
-    {                                                                                                                \
-        if (h.dot_split == 30)                                                                                       \
-            SEALHIP_FLOOR2S(KM, 30);                                                                                 \
-        else                                                                                                         \
-            SEALHIP_FLOOR2S(KM, 31);                                                                                 \
-    } while (0)
-            switch (plan.floor_kernel)
-            {
-            case 1: SEALHIP_FLOOR2(-1); break;
-            case 2: SEALHIP_FLOOR2(-2); break;
-            case 3: SEALHIP_FLOOR2(-3); break;
-            case 4: SEALHIP_FLOOR2(-4); break;
-            case 5: SEALHIP_FLOOR2(-5); break;
-            case 6: SEALHIP_FLOOR2(-6); break;
-            case 7: SEALHIP_FLOOR2(-7); break;
-            case 8: SEALHIP_FLOOR2(-8); break;
-            case 9: SEALHIP_FLOOR2(-9); break;
-            case 10: SEALHIP_FLOOR2(-10); break;
-            case 11: SEALHIP_FLOOR2(-11); break;
-            case 12: SEALHIP_FLOOR2(-12); break;
-            case 13: SEALHIP_FLOOR2(-13); break;
-            case 14: SEALHIP_FLOOR2(-14); break;
-            case 15: SEALHIP_FLOOR2(-15); break;
-            default: SEALHIP_FLOOR2S(32, 31); break;
-            }
-#undef SEALHIP_FLOOR2
-#undef SEALHIP_FLOOR2S
+            // (every instance, the generic one included, has the form that applies the deferred top layer)
+            const auto launch = [&](auto km, auto split) {
+                dispatch_bool(deferred_top != 0, [&](auto top) {
+                    bfv_floor_sk2_kernel<decltype(km)::value, decltype(top)::value, decltype(split)::value>
+                        <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn,
+                                                                 deferred_top == 2 ? 1 : 0, tflags);
+                });
+            };
+            if (!dispatch_behz_exact(plan.floor_kernel, h.dot_split, launch))
+                launch(std::integral_constant<int, kBehzGeneric>{}, std::integral_constant<int, kBehzDefaultSplit>{});
             return hipGetLastError();
         }
         if (deferred_top)
             return hipErrorInvalidValue;
-        SEALHIP_DISPATCH_K(h.k, bfv_floor_sk_kernel, d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+        dispatch_k_bucket(h.k, [&](auto km) {
+            bfv_floor_sk_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
+                                                                                             out_stride, count, e.logn);
+        });
         hipError_t err = hipGetLastError();
         if (err == hipSuccess && tflags)
             err = launch_nonzero_words(e, out, out_stride, static_cast<std::size_t>(h.k) << e.logn, count, tflags);

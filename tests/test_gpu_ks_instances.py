@@ -3,8 +3,8 @@
 launch_ks_mac (keyswitch.hip), launch_hoist_mac and launch_hoist_dot_mac (hoist.hip) pick a template instance from the level's
 digit count nd = ceil(k / nsp): ks_mac_items_kernel<1..16>, hoist_mac_kernel<1..16>, hoist_dot_mac_kernel<1..16, {1, 2, 4}>, and
 three loop kernels for everything else. Every device call of this file is a `Call` in CASES, which names its context, level
-and batch; tests/test_ks_instances_host.py restates the launchers' rules over CASES and asserts, without a device, that the
-calls reach the whole table. References: ref_apply_galois_inplace / ref_relinearize for the plain key switch,
+and batch; tests/test_ks_instances_host.py evaluates the launchers' rules (csrc/mac_select.hpp, and its own statement of them)
+over CASES and asserts, without a device, that the calls reach the whole table. References: ref_apply_galois_inplace / ref_relinearize for the plain key switch,
 hoist_ref.hoisted_rotation for apply_galois_many, hoist_dot_ref.dot_plain for apply_galois_dot_plain. Keys are random rows (the
 comparison needs no valid keys); no tolerance is involved anywhere.
 
