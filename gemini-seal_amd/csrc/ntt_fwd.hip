@@ -29,9 +29,6 @@ namespace sealhip
             return a;
         }
 
-        // final round, one group at a time: the low f index bits of the 2^f registers that share the filler
-        // slot bits G are finished (layers f-1 .. 0) and stored right away, which bounds the live twiddles
-
         // Final-round stores. A lane finishes runs of 2^f consecutive coefficients; for f >= 2 storing them from there
         // means 16-byte pieces at a 2^f * 8-byte stride per instruction -- every 128-byte line is written by 2^(f-1)
         // different instructions, and a kernel that does nothing but these stores reaches 2.0 TB/s at f = 2 (3.0 at
@@ -111,155 +108,105 @@ namespace sealhip
                 store_nt(dst + i * 128, x[s + 2 * i], x[s + 2 * i + 1]);
         }
 
-        // SX: what happens to the finished words -- 0 stored from arrangement 4 as they are, 1 kept for the LDS trip
-        // (kStoreExchange), 2 transposed in registers and stored group by group (kStoreSwap)
-        template <int T, int STRICT, int G, bool ROUT, int SX>
-        __device__ __forceinline__ void h_final_group(u64 (&x)[32], const u64 *__restrict__ tw, u64 *__restrict__ rowp,
-                                                      int jb, int N, u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
+        // Where the final round's twiddles come from: get(W, e) is the twiddle of layer W's butterfly on element e of the group.
+        // TwRegs: the group's prefetched registers (GroupTw, FinalPipe: f <= 2). TwMemory: loaded where they are used
+        // (FinalGroups: f = 3, where two stages of 28 twiddle registers do not fit).
+        template <int T>
+        struct TwRegs
         {
-            constexpr int f = T - 12;
-#pragma unroll
-            for (int W = f - 1; W >= 0; W--)
+            static constexpr bool from_memory = false;
+            const u64x2 *tg;
+            __device__ __forceinline__ u64x2 get(int W, int e) const
             {
-                const int gb = Arr<T, 4>::slot_bit(W);
-                const int tb = (N + jb) >> (gb + 1);
-                const int bit = 1 << W;
-#pragma unroll
-                for (int e = 0; e < (1 << f); e++)
-                {
-                    if (e & bit)
-                        continue;
-                    const int s = (G << f) | e;
-                    if constexpr (STRICT == kSchedFp64)
-                    {
-                        fp_butterfly_fwd(x[s], x[s | bit], ((twd_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)], fp_of(two_p),
-                                         fp_of(neg_p));
-                        continue;
-                    }
-                    const u64x2 Wv = ((tw_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
-                    if (STRICT == kSchedHarvey)
-                        x[s] = x[s] >= two_p ? x[s] - two_p : x[s];
-                    else if (gb == 0 && !(fin & 2)) // fin & 2: the consumer takes any representative and nothing can wrap
-                        x[s] = barrett_lazy_hs(x[s], rdp, neg_p);
-                    if constexpr (kFinalApx<T, STRICT> == 2)
-                        butterfly_fwd_apx2<false>(x[s], x[s | bit], Wv.x, Wv.y, neg_p, fwd_addend<STRICT>(two_p, neg_p), zp.z[(((e >> (W + 1)) << W) | (e & (bit - 1))) & (kFinalZeroPairs - 1)]);
-                    else
-                        butterfly_fwd_hs<false, kFinalApx<T, STRICT>>(x[s], x[s | bit], Wv.x, Wv.y, neg_p, fwd_addend<STRICT>(two_p, neg_p));
-                }
+                return tg[GroupTw<T, true>::at(W, e)];
             }
-#pragma unroll
-            for (int e = 0; e < (1 << f); e += 2)
+        };
+        template <int T, int G, bool FP>
+        struct TwMemory
+        {
+            static constexpr bool from_memory = true;
+            const u64 *__restrict__ tw;
+            int jb, N;
+            __device__ __forceinline__ u64x2 get(int W, int e) const
             {
-                const int s = (G << f) | e;
-                ulonglong2 v;
-                v.x = x[s];
-                v.y = x[s + 1];
-                if constexpr (STRICT == kSchedFp64)
+                const int i = ((N + jb) >> (Arr<T, 4>::slot_bit(W) + 1)) + Arr<T, 4>::tw_offset((G << (T - 12)) | e, W);
+                u64x2 Wv;
+                if constexpr (FP)
                 {
-                    // canonical residues always: they serve kNttCanonical and every any-representative consumer alike
-                    v.x = fp_to_u64(fp_canonical(fp_of(v.x), fp_of(two_p), fp_of(neg_p)));
-                    v.y = fp_to_u64(fp_canonical(fp_of(v.y), fp_of(two_p), fp_of(neg_p)));
-                }
-                else if (fin & 1)
-                {
-                    if constexpr (STRICT == kSchedApprox)
-                    {
-                        // canonical output of the approximate-quotient schedule (values below (2 + g log n) p <= 66p,
-                        // ntt_bounds.hpp section 2): one step to [0, 2p), one conditional subtraction. fin & 4: the step is
-                        // the single-precision quotient estimate (rdp then carries the bits of its constant), else Barrett
-                        if (fin & 4)
-                        {
-                            const float cq = __uint_as_float(static_cast<unsigned>(rdp));
-                            v.x = reduce_small_quot(v.x, cq, neg_p);
-                            v.y = reduce_small_quot(v.y, cq, neg_p);
-                        }
-                        else
-                        {
-                            v.x = barrett_lazy_hs(v.x, rdp, neg_p);
-                            v.y = barrett_lazy_hs(v.y, rdp, neg_p);
-                        }
-                    }
-                    else
-                    {
-                        v.x = v.x >= two_p ? v.x - two_p : v.x;
-                        v.y = v.y >= two_p ? v.y - two_p : v.y;
-                    }
-                    v.x = v.x >= p ? v.x - p : v.x;
-                    v.y = v.y >= p ? v.y - p : v.y;
-                }
-                else if constexpr (ROUT && STRICT == kSchedDense)
-                {
-                    // dense lazy schedule: words below 16p -> [0, 2p) (rdp carries the bits of the quotient constant)
-                    const float cq = __uint_as_float(static_cast<unsigned>(rdp));
-                    v.x = reduce_small_quot(v.x, cq, neg_p);
-                    v.y = reduce_small_quot(v.y, cq, neg_p);
-                }
-                else if constexpr (ROUT)
-                {
-                    // kNttReduceOut: [0, 4p) -> [0, 2p), same residue. (The last layer reduces its first operand and its
-                    // product below 2p before it adds them -- ForwardLazyLast, ntt.cpp:254-261 -- so even on the 60-bit rows,
-                    // where earlier layers wrap, what it outputs is below 4p.)
-                    v.x = v.x >= two_p ? v.x - two_p : v.x;
-                    v.y = v.y >= two_p ? v.y - two_p : v.y;
-                }
-                if constexpr (SX != 0)
-                {
-                    x[s] = v.x; // stored by h_store_rows after the trip back to arrangement 1, or transposed below
-                    x[s + 1] = v.y;
+                    Wv.x = ((twd_global_t)tw)[i];
+                    Wv.y = 0;
                 }
                 else
-                    // (plain store: a lane's 64-byte run is written by four instructions and the L2 has to merge them;
-                    //  streaming stores cost 12 % there)
-                    *reinterpret_cast<ulonglong2 *>(rowp + (jb & ((1 << T) | ((1 << T) - 1))) + Arr<T, 4>::slot_index(s)) = v;
-            }
-            if constexpr (SX == 2)
-                h_store_group_swapped<T, G>(x, rowp, jb);
-        }
-
-        template <int T, int STRICT, int G, int NG, bool ROUT, int SX>
-        struct FinalGroups
-        {
-            __device__ static __forceinline__ void run(u64 (&x)[32], const u64 *__restrict__ tw, u64 *__restrict__ rowp,
-                                                       int jb, int N, u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
-            {
-                h_final_group<T, STRICT, G, ROUT, SX>(x, tw, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
-                if ((G & 1) == 1)
-                    __builtin_amdgcn_sched_barrier(0); // keep the compiler from hoisting every group's twiddle loads
-                FinalGroups<T, STRICT, G + 1, NG, ROUT, SX>::run(x, tw, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
+                    Wv = ((tw_global_t)tw)[i];
+                return Wv;
             }
         };
-        template <int T, int STRICT, int NG, bool ROUT, int SX>
-        struct FinalGroups<T, STRICT, NG, NG, ROUT, SX>
-        {
-            __device__ static __forceinline__ void run(u64 (&)[32], const u64 *, u64 *, int, int, u64, u64, u64, u64, int, ZeroPairs &)
-            {}
-        };
 
-        template <int T, int G, bool FP = false>
-        __device__ __forceinline__ void h_final_tw(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
+        // a finished pair of words of the final round -> the words that are stored (fin, rdp: see ntt_fwd_half_kernel)
+        template <int STRICT, bool ROUT>
+        __device__ __forceinline__ void h_finish_pair(u64 &a, u64 &b, u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin)
         {
-            constexpr int f = T - 12;
-#pragma unroll
-            for (int W = f - 1; W >= 0; W--)
+            if constexpr (STRICT == kSchedFp64)
             {
-                const int tb = (N + jb) >> (Arr<T, 4>::slot_bit(W) + 1);
-#pragma unroll
-                for (int o = 0; o < (1 << (f - 1 - W)); o++)
+                // canonical residues always: they serve kNttCanonical and every any-representative consumer alike
+                a = fp_to_u64(fp_canonical(fp_of(a), fp_of(two_p), fp_of(neg_p)));
+                b = fp_to_u64(fp_canonical(fp_of(b), fp_of(two_p), fp_of(neg_p)));
+            }
+            else if (fin & 1)
+            {
+                if constexpr (STRICT == kSchedApprox)
                 {
-                    const int s = (G << f) | (o << (W + 1));
-                    if constexpr (FP)
-                        tg[(1 << (f - 1 - W)) - 1 + o].x = ((twd_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
+                    // canonical output of the approximate-quotient schedule (values below (2 + g log n) p <= 66p,
+                    // ntt_bounds.hpp section 2): one step to [0, 2p), one conditional subtraction. fin & 4: the step is
+                    // the single-precision quotient estimate (rdp then carries the bits of its constant), else Barrett
+                    if (fin & 4)
+                    {
+                        const float cq = __uint_as_float(static_cast<unsigned>(rdp));
+                        a = reduce_small_quot(a, cq, neg_p);
+                        b = reduce_small_quot(b, cq, neg_p);
+                    }
                     else
-                        tg[(1 << (f - 1 - W)) - 1 + o] = ((tw_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
+                    {
+                        a = barrett_lazy_hs(a, rdp, neg_p);
+                        b = barrett_lazy_hs(b, rdp, neg_p);
+                    }
                 }
+                else
+                {
+                    a = a >= two_p ? a - two_p : a;
+                    b = b >= two_p ? b - two_p : b;
+                }
+                a = a >= p ? a - p : a;
+                b = b >= p ? b - p : b;
+            }
+            else if constexpr (ROUT && STRICT == kSchedDense)
+            {
+                // dense lazy schedule: words below 16p -> [0, 2p) (rdp carries the bits of the quotient constant)
+                const float cq = __uint_as_float(static_cast<unsigned>(rdp));
+                a = reduce_small_quot(a, cq, neg_p);
+                b = reduce_small_quot(b, cq, neg_p);
+            }
+            else if constexpr (ROUT)
+            {
+                // kNttReduceOut: [0, 4p) -> [0, 2p), same residue. (The last layer reduces its first operand and its
+                // product below 2p before it adds them -- ForwardLazyLast, ntt.cpp:254-261 -- so even on the 60-bit rows,
+                // where earlier layers wrap, what it outputs is below 4p.)
+                a = a >= two_p ? a - two_p : a;
+                b = b >= two_p ? b - two_p : b;
             }
         }
 
-        template <int T, int STRICT, int G, bool ROUT, int SX>
-        __device__ __forceinline__ void h_final_group_regs(u64 (&x)[32], const u64x2 *tg, u64 *__restrict__ rowp, int jb,
-                                                           int N, u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
+        // final round, one group at a time: the low f index bits of the 2^f registers that share the filler
+        // slot bits G are finished (layers f-1 .. 0) and stored right away, which bounds the live twiddles
+        // SX: what happens to the finished words -- 0 stored from arrangement 4 as they are, 1 kept for the LDS trip
+        // (kStoreExchange), 2 transposed in registers and stored group by group (kStoreSwap)
+        template <int T, int STRICT, int G, bool ROUT, int SX, class TwSource>
+        __device__ __forceinline__ void h_final_group(u64 (&x)[32], const TwSource &twiddles, u64 *__restrict__ rowp, int jb,
+                                                      u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
         {
             constexpr int f = T - 12;
+            // (twiddles from memory: f = 3, where kStoreSwap or kStoreExchange always holds)
+            static_assert(SX != 0 || !TwSource::from_memory, "the store from arrangement 4 exists in the prefetched form only");
 #pragma unroll
             for (int W = f - 1; W >= 0; W--)
             {
@@ -271,7 +218,7 @@ namespace sealhip
                     if (e & bit)
                         continue;
                     const int s = (G << f) | e;
-                    const u64x2 Wv = tg[(1 << (f - 1 - W)) - 1 + (e >> (W + 1))];
+                    const u64x2 Wv = twiddles.get(W, e);
                     if constexpr (STRICT == kSchedFp64)
                     {
                         fp_butterfly_fwd(x[s], x[s | bit], Wv.x, fp_of(two_p), fp_of(neg_p));
@@ -294,54 +241,7 @@ namespace sealhip
                 ulonglong2 v;
                 v.x = x[s];
                 v.y = x[s + 1];
-                if constexpr (STRICT == kSchedFp64)
-                {
-                    // canonical residues always: they serve kNttCanonical and every any-representative consumer alike
-                    v.x = fp_to_u64(fp_canonical(fp_of(v.x), fp_of(two_p), fp_of(neg_p)));
-                    v.y = fp_to_u64(fp_canonical(fp_of(v.y), fp_of(two_p), fp_of(neg_p)));
-                }
-                else if (fin & 1)
-                {
-                    if constexpr (STRICT == kSchedApprox)
-                    {
-                        // canonical output of the approximate-quotient schedule (values below (2 + g log n) p <= 66p,
-                        // ntt_bounds.hpp section 2): one step to [0, 2p), one conditional subtraction. fin & 4: the step is
-                        // the single-precision quotient estimate (rdp then carries the bits of its constant), else Barrett
-                        if (fin & 4)
-                        {
-                            const float cq = __uint_as_float(static_cast<unsigned>(rdp));
-                            v.x = reduce_small_quot(v.x, cq, neg_p);
-                            v.y = reduce_small_quot(v.y, cq, neg_p);
-                        }
-                        else
-                        {
-                            v.x = barrett_lazy_hs(v.x, rdp, neg_p);
-                            v.y = barrett_lazy_hs(v.y, rdp, neg_p);
-                        }
-                    }
-                    else
-                    {
-                        v.x = v.x >= two_p ? v.x - two_p : v.x;
-                        v.y = v.y >= two_p ? v.y - two_p : v.y;
-                    }
-                    v.x = v.x >= p ? v.x - p : v.x;
-                    v.y = v.y >= p ? v.y - p : v.y;
-                }
-                else if constexpr (ROUT && STRICT == kSchedDense)
-                {
-                    // dense lazy schedule: words below 16p -> [0, 2p) (rdp carries the bits of the quotient constant)
-                    const float cq = __uint_as_float(static_cast<unsigned>(rdp));
-                    v.x = reduce_small_quot(v.x, cq, neg_p);
-                    v.y = reduce_small_quot(v.y, cq, neg_p);
-                }
-                else if constexpr (ROUT)
-                {
-                    // kNttReduceOut: [0, 4p) -> [0, 2p), same residue. (The last layer reduces its first operand and its
-                    // product below 2p before it adds them -- ForwardLazyLast, ntt.cpp:254-261 -- so even on the 60-bit rows,
-                    // where earlier layers wrap, what it outputs is below 4p.)
-                    v.x = v.x >= two_p ? v.x - two_p : v.x;
-                    v.y = v.y >= two_p ? v.y - two_p : v.y;
-                }
+                h_finish_pair<STRICT, ROUT>(v.x, v.y, p, two_p, neg_p, rdp, fin);
                 if constexpr (SX != 0)
                 {
                     x[s] = v.x; // stored by h_store_rows after the trip back to arrangement 1, or transposed below
@@ -354,26 +254,36 @@ namespace sealhip
                 h_store_group_swapped<T, G>(x, rowp, jb);
         }
 
-        template <int T, int ST, int I = 0, bool FP = false>
-        struct StageTw // twiddle loads of stage ST
+        template <int T, int STRICT, int G, int NG, bool ROUT, int SX>
+        struct FinalGroups
         {
-            __device__ static __forceinline__ void load(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
+            __device__ static __forceinline__ void run(u64 (&x)[32], const u64 *__restrict__ tw, u64 *__restrict__ rowp,
+                                                       int jb, int N, u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
             {
-                h_final_tw<T, ST * FinalStage<T>::SG + I, FP>(tg + I * FinalStage<T>::NTW, tw, jb, N);
-                if constexpr (I + 1 < FinalStage<T>::SG)
-                    StageTw<T, ST, I + 1, FP>::load(tg, tw, jb, N);
+                h_final_group<T, STRICT, G, ROUT, SX>(x, TwMemory<T, G, STRICT == kSchedFp64>{ tw, jb, N }, rowp, jb, p, two_p, neg_p,
+                                                      rdp, fin, zp);
+                if ((G & 1) == 1)
+                    __builtin_amdgcn_sched_barrier(0); // keep the compiler from hoisting every group's twiddle loads
+                FinalGroups<T, STRICT, G + 1, NG, ROUT, SX>::run(x, tw, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
             }
         };
+        template <int T, int STRICT, int NG, bool ROUT, int SX>
+        struct FinalGroups<T, STRICT, NG, NG, ROUT, SX>
+        {
+            __device__ static __forceinline__ void run(u64 (&)[32], const u64 *, u64 *, int, int, u64, u64, u64, u64, int, ZeroPairs &)
+            {}
+        };
+
         template <int T, int STRICT, bool ROUT, int SX, int ST, int I = 0>
         struct StageRun
         {
-            __device__ static __forceinline__ void run(u64 (&x)[32], const u64x2 *tg, u64 *__restrict__ rowp, int jb, int N,
+            __device__ static __forceinline__ void run(u64 (&x)[32], const u64x2 *tg, u64 *__restrict__ rowp, int jb,
                                                        u64 p, u64 two_p, u64 neg_p, u64 rdp, int fin, ZeroPairs &zp)
             {
-                h_final_group_regs<T, STRICT, ST * FinalStage<T>::SG + I, ROUT, SX>(x, tg + I * FinalStage<T>::NTW, rowp, jb, N, p,
-                                                                               two_p, neg_p, rdp, fin, zp);
+                h_final_group<T, STRICT, ST * FinalStage<T>::SG + I, ROUT, SX>(x, TwRegs<T>{ tg + I * FinalStage<T>::NTW }, rowp, jb, p,
+                                                                          two_p, neg_p, rdp, fin, zp);
                 if constexpr (I + 1 < FinalStage<T>::SG)
-                    StageRun<T, STRICT, ROUT, SX, ST, I + 1>::run(x, tg, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
+                    StageRun<T, STRICT, ROUT, SX, ST, I + 1>::run(x, tg, rowp, jb, p, two_p, neg_p, rdp, fin, zp);
             }
         };
         template <int T, int STRICT, bool ROUT, int SX, int ST>
@@ -385,9 +295,9 @@ namespace sealhip
             {
                 u64x2 next[FinalStage<T>::SG * FinalStage<T>::NTW];
                 if constexpr (ST + 1 < FinalStage<T>::NS)
-                    StageTw<T, ST + 1, 0, STRICT == kSchedFp64>::load(next, tw, jb, N);
+                    StageTw<T, ST + 1, true, STRICT == kSchedFp64>::load(next, tw, jb, N);
                 __builtin_amdgcn_sched_barrier(0);
-                StageRun<T, STRICT, ROUT, SX, ST>::run(x, cur, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
+                StageRun<T, STRICT, ROUT, SX, ST>::run(x, cur, rowp, jb, p, two_p, neg_p, rdp, fin, zp);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (ST + 1 < FinalStage<T>::NS)
                     FinalPipe<T, STRICT, ROUT, SX, ST + 1>::run(x, next, tw, rowp, jb, N, p, two_p, neg_p, rdp, fin, zp);
@@ -398,38 +308,11 @@ namespace sealhip
         // 16 / kIL stages each). The twiddles of stage K+1 are requested before stage K is computed (pinned with
         // sched_barrier), the first stage's before the preceding LDS exchange: no twiddle latency is exposed.
         template <int T, int R, int STRICT, bool UNIFORM, int K>
-        struct RoundStage
+        struct RoundStage : Stage<T, R, 4 - K / kStagesPerLayer, (K % kStagesPerLayer) * kIL, UNIFORM, STRICT == kSchedFp64>
         {
-            static constexpr int PER = 16 / kIL;
-            static constexpr int W = 4 - K / PER;
-            static constexpr int C = (K % PER) * kIL;
-            static constexpr int bit = 1 << W;
-            static constexpr int slot(int j)
-            {
-                return (((C + j) >> W) << (W + 1)) | ((C + j) & (bit - 1)); // the (C+j)-th slot with bit W clear
-            }
-            __device__ static __forceinline__ void load(u64 (&w)[kIL], u64 (&ws)[kIL], const u64 *__restrict__ tw, int jb,
-                                                        int N)
-            {
-                const int tb = (N + jb) >> (Arr<T, R>::slot_bit(W) + 1);
-#pragma unroll
-                for (int j = 0; j < kIL; j++)
-                {
-                    u64x2 Wv;
-                    if constexpr (STRICT == kSchedFp64)
-                    {
-                        Wv.x = UNIFORM ? ((twd_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)]
-                                       : ((twd_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
-                        Wv.y = 0;
-                    }
-                    else if (UNIFORM)
-                        Wv = ((tw_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)];
-                    else
-                        Wv = ((tw_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
-                    w[j] = Wv.x;
-                    ws[j] = Wv.y;
-                }
-            }
+            using S = Stage<T, R, 4 - K / kStagesPerLayer, (K % kStagesPerLayer) * kIL, UNIFORM, STRICT == kSchedFp64>;
+            using S::bit;
+            using S::slot;
             __device__ static __forceinline__ void run(u64 (&x)[32], const u64 (&w)[kIL], const u64 (&ws)[kIL], u64 two_p,
                                                        u64 neg_p, ZeroPairs &zp)
             {
@@ -752,7 +635,7 @@ namespace sealhip
             const int wave_base = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) & ~63); // (see fresh_tid)
             int half, position;
             std::size_t poly;
-            if (!half_block_map(blockIdx.x, nrows / map.rows, live.n, chunk, poly, position, half,
+            if (!block_place<1>(blockIdx.x, nrows / map.rows, live.n, chunk, poly, position, half,
                                 (flags & kNttPolyMajor) ? ((flags >> 16) & 0xFF) : 0))
                 return;
             const std::size_t row = poly * map.rows + live.slot[position];
@@ -841,7 +724,7 @@ namespace sealhip
             u64x2 tg0[FinalStage<T>::SG * FinalStage<T>::NTW];
             if constexpr (FinalStage<T>::PIPE)
             {
-                StageTw<T, 0, 0, STRICT == kSchedFp64>::load(tg0, tw, jb4, N); // lands while the last exchange runs
+                StageTw<T, 0, true, STRICT == kSchedFp64>::load(tg0, tw, jb4, N); // lands while the last exchange runs
                 __builtin_amdgcn_sched_barrier(0);
             }
             h_exchange<T, 3, 4>(x, lds, fresh_tid(wave_base));
@@ -911,40 +794,33 @@ namespace sealhip
         }
 
         // The instances of a ring of 2^LOGN, in the order of kFwdInstances (ntt_select.hpp; null where the table says the
-        // instance does not exist at this ring size): launch_half launches from this table and init_half registers from it.
+        // instance does not exist at this ring size), for kernel_table (ntt_half.hpp): launch_half launches from that table and
+        // ntt_fwd_half_init registers from it.
         using FwdKernel = void (*)(u64 *, const PrimeDev *, RowMap, std::size_t, int, unsigned *, unsigned *, unsigned, NttSource,
                                    std::size_t, LiveSlots);
-        template <int LOGN, int I>
-        FwdKernel fwd_kernel()
+        struct FwdTable
         {
-            if constexpr (fwd_instance_at(LOGN, kFwdInstances[I]))
-                return &ntt_fwd_half_kernel<LOGN, kFwdInstances[I].sched, kFwdInstances[I].treatment>;
-            else
-                return nullptr;
-        }
-        template <int LOGN, int... I>
-        const FwdKernel *fwd_kernels(std::integer_sequence<int, I...>)
+            using Kernel = FwdKernel;
+            static constexpr int count = kFwdInstanceCount;
+            template <int LOGN, int I>
+            static Kernel at()
+            {
+                if constexpr (fwd_instance_at(LOGN, kFwdInstances[I]))
+                    return &ntt_fwd_half_kernel<LOGN, kFwdInstances[I].sched, kFwdInstances[I].treatment>;
+                else
+                    return nullptr;
+            }
+        };
+        struct FwdSplitTable // ... and those of kFwdSplitInstances
         {
-            static const FwdKernel table[] = { fwd_kernel<LOGN, I>()... };
-            return table;
-        }
-        template <int LOGN>
-        const FwdKernel *fwd_kernels()
-        {
-            return fwd_kernels<LOGN>(std::make_integer_sequence<int, kFwdInstanceCount>{});
-        }
-        // ... and those of kFwdSplitInstances
-        template <int LOGN, int... I>
-        const FwdKernel *fwd_split_kernels(std::integer_sequence<int, I...>)
-        {
-            static const FwdKernel table[] = { &ntt_fwd_half_kernel<LOGN, kFwdSplitInstances[I].sched, kFwdSplitInstances[I].treatment, true>... };
-            return table;
-        }
-        template <int LOGN>
-        const FwdKernel *fwd_split_kernels()
-        {
-            return fwd_split_kernels<LOGN>(std::make_integer_sequence<int, kFwdSplitInstanceCount>{});
-        }
+            using Kernel = FwdKernel;
+            static constexpr int count = kFwdSplitInstanceCount;
+            template <int LOGN, int I>
+            static Kernel at()
+            {
+                return &ntt_fwd_half_kernel<LOGN, kFwdSplitInstances[I].sched, kFwdSplitInstances[I].treatment, true>;
+            }
+        };
 
         // the facts select_fwd_half decides on, and its decision, for a launch on ring e.logn
         FwdChoice choose_fwd(const Engine &e, const RowMap &map, int flags, const NttSource &src, const LiveSlots &live)
@@ -1021,42 +897,16 @@ namespace sealhip
                 std::memcpy(&ksrc.aux_top[2], &c2, 8);
             }
             ProfScope prof(e, "ntt_fwd_half", transformed_rows(nrows, map));
-            (c.split ? fwd_split_kernels<LOGN>() : fwd_kernels<LOGN>())[c.instance]<<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
+            (c.split ? kernel_table<FwdSplitTable, LOGN>() : kernel_table<FwdTable, LOGN>())[c.instance]<<<static_cast<unsigned>(blocks), 1 << (LOGN - 6), lds_bytes, e.lane().stream>>>(
                 data, e.d_primes, map, nrows, c.flags, tickets, e.lane().d_fault, e.ntt_spin_limit, ksrc, chunk, live);
             return hipGetLastError();
         }
 
-        // the dynamic LDS limit of every instance of the ring (the default suffices at 2^14 only)
-        template <int LOGN>
-        hipError_t init_half()
-        {
-            const int lds_bytes = hpad(1 << (LOGN - 2)) * 8;
-            for (int i = 0; i < kFwdInstanceCount; i++)
-                if (const FwdKernel k = fwd_kernels<LOGN>()[i])
-                {
-                    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                    if (err != hipSuccess)
-                        return err;
-                }
-            for (int i = 0; i < kFwdSplitInstanceCount; i++)
-            {
-                const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_split_kernels<LOGN>()[i]), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (err != hipSuccess)
-                    return err;
-            }
-            return hipSuccess;
-        }
     } // namespace
 
     hipError_t ntt_fwd_half(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags, const NttSource &src)
     {
-        switch (e.logn)
-        {
-        case 14: return launch_half<14>(e, data, nrows, map, flags, src);
-        case 15: return launch_half<15>(e, data, nrows, map, flags, src);
-        case 16: return launch_half<16>(e, data, nrows, map, flags, src);
-        default: return hipErrorInvalidValue;
-        }
+        return at_ring_size(e.logn, [&](auto logn) { return launch_half<decltype(logn)::value>(e, data, nrows, map, flags, src); });
     }
 
     bool ntt_fwd_half_splits(const Engine &e, const RowMap &map, int flags, const NttSource &src)
@@ -1070,11 +920,11 @@ namespace sealhip
 
     hipError_t ntt_fwd_half_init()
     {
-        hipError_t err = init_half<14>();
-        if (err == hipSuccess)
-            err = init_half<15>();
-        if (err == hipSuccess)
-            err = init_half<16>();
-        return err;
+        return at_every_ring_size([](auto logn) {
+            constexpr int LOGN = decltype(logn)::value;
+            const auto bytes = [](int) { return hpad(1 << (LOGN - 2)) * 8; };
+            const hipError_t err = set_dynamic_lds(kernel_table<FwdTable, LOGN>(), FwdTable::count, bytes);
+            return err != hipSuccess ? err : set_dynamic_lds(kernel_table<FwdSplitTable, LOGN>(), FwdSplitTable::count, bytes);
+        });
     }
 } // namespace sealhip

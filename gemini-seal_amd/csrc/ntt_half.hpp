@@ -1,7 +1,10 @@
 // ntt_half.hpp -- what the single-pass NTT kernels for N = 2^14 .. 2^16 of both directions share (ntt_fwd.hip,
 // ntt_inv.hip), and the entry points through which ntt.hip reaches them. Internal to the library.
 #pragma once
+#include <utility>
+
 #include "engine.hpp"
+#include "instance_dispatch.hpp"
 
 // (library-internal: not exported from libsealhip.so)
 #define SEALHIP_INTERNAL __attribute__((visibility("hidden")))
@@ -211,7 +214,88 @@ namespace sealhip
             static constexpr bool PIPE = f <= 2; // f = 3: two stages of 28 twiddle registers do not fit
         };
 
-        // XCD-aware block -> (row, half) map (speed only; any placement gives the same result). Blocks are dealt
+        // The twiddles of one group of 2^f registers (those that share the filler slot bits G), held in tg[] in the order the
+        // direction uses its layers: DESC (forward) W = f-1 (1 entry), f-2 (2), ..., 0; else (inverse) W = 0 (2^(f-1) entries),
+        // 1, ..., f-1 (1 entry). Entry o of layer W serves the butterflies of the elements e with e >> (W + 1) == o.
+        template <int T, bool DESC>
+        struct GroupTw
+        {
+            static constexpr int f = T - 12;
+            static constexpr int at(int W, int e) // place in tg[] of the twiddle of layer W's butterfly on element e
+            {
+                return (DESC ? (1 << (f - 1 - W)) - 1 : (1 << f) - (1 << (f - W))) + (e >> (W + 1));
+            }
+            // loads issued in the order of tg[]
+            template <int G, bool FP>
+            __device__ static __forceinline__ void load(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
+            {
+#pragma unroll
+                for (int k = 0; k < f; k++)
+                {
+                    const int W = DESC ? f - 1 - k : k;
+                    const int tb = (N + jb) >> (Arr<T, 4>::slot_bit(W) + 1);
+#pragma unroll
+                    for (int o = 0; o < (1 << (f - 1 - W)); o++)
+                    {
+                        const int e = o << (W + 1), s = (G << f) | e;
+                        if constexpr (FP)
+                            tg[at(W, e)].x = ((twd_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
+                        else
+                            tg[at(W, e)] = ((tw_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
+                    }
+                }
+            }
+        };
+        template <int T, int ST, bool DESC, bool FP, int I = 0>
+        struct StageTw // twiddle loads of stage ST (FinalStage<T>::SG groups)
+        {
+            __device__ static __forceinline__ void load(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
+            {
+                GroupTw<T, DESC>::template load<ST * FinalStage<T>::SG + I, FP>(tg + I * FinalStage<T>::NTW, tw, jb, N);
+                if constexpr (I + 1 < FinalStage<T>::SG)
+                    StageTw<T, ST, DESC, FP, I + 1>::load(tg, tw, jb, N);
+            }
+        };
+
+        // A stage of a compute round in arrangement R: kIL butterflies of layer W (slot bit W), the C-th .. (C+kIL-1)-th of its
+        // 16. Its slots, and the loads of its twiddles: doubles moved as 64-bit words (FP) or (w, w') pairs; through the
+        // scalar cache where the index is wave-uniform (UNIFORM), else global loads.
+        template <int T, int R, int W, int C, bool UNIFORM, bool FP>
+        struct Stage
+        {
+            static constexpr int bit = 1 << W;
+            static constexpr int slot(int j)
+            {
+                return (((C + j) >> W) << (W + 1)) | ((C + j) & (bit - 1)); // the (C+j)-th slot with bit W clear
+            }
+            __device__ static __forceinline__ void load(u64 (&w)[kIL], u64 (&ws)[kIL], const u64 *__restrict__ tw, int jb,
+                                                        int N)
+            {
+                const int tb = (N + jb) >> (Arr<T, R>::slot_bit(W) + 1);
+#pragma unroll
+                for (int j = 0; j < kIL; j++)
+                {
+                    u64x2 Wv;
+                    if constexpr (FP)
+                    {
+                        Wv.x = UNIFORM ? ((twd_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)]
+                                       : ((twd_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
+                        Wv.y = 0;
+                    }
+                    else if (UNIFORM)
+                        Wv = ((tw_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)];
+                    else
+                        Wv = ((tw_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
+                    w[j] = Wv.x;
+                    ws[j] = Wv.y;
+                }
+            }
+        };
+        constexpr int kStagesPerLayer = 16 / kIL;
+
+        // XCD-aware block -> (row, part) map (speed only; any placement gives the same result). A row is transformed by
+        // 2^PARTS_LOG2 workgroups: its two halves (the forward kernel, the half-row inverse), one (the whole-row inverse) or
+        // four quarters (the quarter-row inverse). Blocks are dealt
         // round-robin over the 8 XCDs, each with its own 4 MB L2. Rows are enumerated prime-major
         // (v = position * npolys + poly, positions = the LIVE slots of a polynomial in slot order) and XCD x gets the
         // contiguous range [x*chunk, (x+1)*chunk): it then touches at most two primes, so their twiddle tables (512 KB
@@ -219,7 +303,8 @@ namespace sealhip
         // 583 -> 377 KB per row at N=2^15). Slots mapped to kSkipRow are left out of the enumeration: counting them
         // left the XCD that owned a skipped slot idle (the key-switch launches skip one slot in k+1, and the CKKS
         // special-row launches transform one slot in k+1: one XCD did all the work).
-        // The two halves of a row are consecutive blocks of one XCD.
+        // The parts of a row are consecutive blocks of one XCD. (The tensor-load inverse enumerates in an order of its own:
+        // ntt_inv.hip.)
         struct LiveSlots
         {
             int n;
@@ -233,8 +318,9 @@ namespace sealhip
                     ls.slot[ls.n++] = static_cast<unsigned short>(r);
             return ls;
         }
-        // -> false when the block has nothing to do; else the polynomial index and the position among the live slots
-        // poly_major = g > 0 (the key switch's digit launches, whose live rows all gather ONE source row): groups of g live
+        // -> false when the block has nothing to do; else the polynomial index and the position among the live slots, and which half or quarter of
+        // that row (`part`)
+        // poly_major = g > 0 (two parts per row only: the key switch's digit launches, whose live rows all gather ONE source row): groups of g live
         // positions interleaved item by item, so that g readers of a source row run next to each other on one XCD and the row is
         // fetched from HBM n_live / g times instead of n_live times -- at the price of an XCD touching up to 2g twiddle tables
         // instead of two. Round 3, config 3 (integer instances, seven readers per source row, 512 KB per table): forward
@@ -242,36 +328,39 @@ namespace sealhip
         // to thrash the 4 MB L2); step 44.98 -> 44.51 ms at g = 4. Config 4 (FP64, eleven readers): the transforms gain 2.5 % at
         // g = 11 but the inner product, which reads what they wrote in the old order, loses as much: off there.
         // select_fwd_half (ntt_select.hpp): g = 4, integer launches only.
-        __device__ __forceinline__ bool half_block_map(unsigned bid, std::size_t npolys, int n_live, std::size_t chunk,
-                                                       std::size_t &poly, int &position, int &half, int poly_major = 0)
+        template <int PARTS_LOG2>
+        __device__ __forceinline__ bool block_place(unsigned bid, std::size_t npolys, int n_live, std::size_t chunk,
+                                                    std::size_t &poly, int &position, int &part, int poly_major = 0)
         {
+            static_assert(PARTS_LOG2 >= 0 && PARTS_LOG2 <= 2, "one, two or four workgroups per row");
             const unsigned xcd = bid & 7u;
             const std::size_t slot = bid >> 3;
-            half = static_cast<int>(slot & 1);
-            const std::size_t v = static_cast<std::size_t>(xcd) * chunk + (slot >> 1);
-            if ((slot >> 1) >= chunk || v >= npolys * static_cast<std::size_t>(n_live))
+            part = static_cast<int>(slot & ((1u << PARTS_LOG2) - 1));
+            const std::size_t v = static_cast<std::size_t>(xcd) * chunk + (slot >> PARTS_LOG2);
+            if ((slot >> PARTS_LOG2) >= chunk || v >= npolys * static_cast<std::size_t>(n_live))
                 return false;
-            if (poly_major)
-            {
-                // groups of g consecutive live positions interleaved item by item: v = (group * npolys + poly) * g + b
-                // (g = n_live: item-major; the last group may be shorter)
-                const int g = poly_major;
-                const std::size_t full = static_cast<std::size_t>(n_live / g) * npolys * g; // rows in complete groups
-                if (v < full)
+            if constexpr (PARTS_LOG2 == 1)
+                if (poly_major)
                 {
-                    const std::size_t gp = v / g;
-                    position = static_cast<int>(gp / npolys) * g + static_cast<int>(v - gp * g);
-                    poly = gp % npolys;
+                    // groups of g consecutive live positions interleaved item by item: v = (group * npolys + poly) * g + b
+                    // (g = n_live: item-major; the last group may be shorter)
+                    const int g = poly_major;
+                    const std::size_t full = static_cast<std::size_t>(n_live / g) * npolys * g; // rows in complete groups
+                    if (v < full)
+                    {
+                        const std::size_t gp = v / g;
+                        position = static_cast<int>(gp / npolys) * g + static_cast<int>(v - gp * g);
+                        poly = gp % npolys;
+                    }
+                    else
+                    {
+                        const int rem = n_live % g; // > 0 here
+                        const std::size_t u = v - full, gp = u / rem;
+                        position = (n_live / g) * g + static_cast<int>(u - gp * rem);
+                        poly = gp;
+                    }
+                    return true;
                 }
-                else
-                {
-                    const int rem = n_live % g; // > 0 here
-                    const std::size_t u = v - full, gp = u / rem;
-                    position = (n_live / g) * g + static_cast<int>(u - gp * rem);
-                    poly = gp;
-                }
-                return true;
-            }
             poly = v % npolys;
             position = static_cast<int>(v / npolys);
             return true;
@@ -323,6 +412,51 @@ namespace sealhip
                 }
             }
             return n_fp > 0 && n_rest > 0;
+        }
+
+        // The kernels of a ring of 2^LOGN in the order of an instance table of ntt_select.hpp. Of names the table:
+        // Of::Kernel, Of::count, and Of::at<LOGN, I>(), the kernel of instance I at that ring size or null where the table says
+        // there is none. The launchers launch from this table and register from it.
+        template <class Of, int LOGN, int... I>
+        const typename Of::Kernel *kernel_table(std::integer_sequence<int, I...>)
+        {
+            static const typename Of::Kernel table[] = { Of::template at<LOGN, I>()... };
+            return table;
+        }
+        template <class Of, int LOGN>
+        const typename Of::Kernel *kernel_table()
+        {
+            return kernel_table<Of, LOGN>(std::make_integer_sequence<int, Of::count>{});
+        }
+        // the dynamic LDS limit of every kernel of a table (the default suffices for the 2^13-coefficient shape only)
+        template <class Kernel, class Bytes>
+        hipError_t set_dynamic_lds(const Kernel *table, int count, Bytes bytes_of)
+        {
+            for (int i = 0; i < count; i++)
+                if (table[i])
+                {
+                    const hipError_t err =
+                        hipFuncSetAttribute(reinterpret_cast<const void *>(table[i]), hipFuncAttributeMaxDynamicSharedMemorySize, bytes_of(i));
+                    if (err != hipSuccess)
+                        return err;
+                }
+            return hipSuccess;
+        }
+        // f(std::integral_constant<int, LOGN>{}) -> hipError_t at the ring size logn; at every ring size, until one fails
+        template <class F>
+        hipError_t at_ring_size(int logn, F &&f)
+        {
+            hipError_t err = hipErrorInvalidValue; // (no single-pass kernel for this ring)
+            dispatch_among<14, 15, 16>(logn, [&](auto n) { err = f(n); });
+            return err;
+        }
+        template <class F>
+        hipError_t at_every_ring_size(F &&f)
+        {
+            hipError_t err = hipSuccess;
+            for (int logn = 14; logn <= 16 && err == hipSuccess; logn++)
+                err = at_ring_size(logn, f);
+            return err;
         }
     } // namespace
 } // namespace sealhip

@@ -15,7 +15,7 @@ namespace sealhip
         // ascending bits) and stores lazy values in [0, 2p). The top layer (gap N/2, with n^{-1} folded
         // in, ntt.cpp:393-402) needs both halves and is applied by ntt_inv_top_kernel, a pure streaming
         // pass (or, inside the pipelines, by the consumer kernel).
-        // ---- inverse rounds as stage pipelines (mirror of ntt_fwd.hip RoundStage / RoundPipe; layers ascend W = 1, 2, 3, 4)
+        // ---- inverse rounds as stage pipelines (ntt_half.hpp Stage, as ntt_fwd.hip RoundStage / RoundPipe; layers ascend W = 1, 2, 3, 4)
         // Lazy-sum schedule of the inverse (only when the caller accepts any representative of the stored values and every
         // prime of the launch is small enough, select_inv_half): the conditional subtraction of the sum output is dropped
         // on all but two of the T on-chip layers; those two (the middle one and the last) reduce with barrett_lazy
@@ -65,38 +65,12 @@ namespace sealhip
             return bounds::fp_inv_reduce_after_layer(T, layer);
         }
         template <int T, int R, bool UNIFORM, int K, int LZ = kInvExact>
-        struct RoundStageInv
+        struct RoundStageInv : Stage<T, R, 1 + K / kStagesPerLayer, (K % kStagesPerLayer) * kIL, UNIFORM, LZ == kInvFp64>
         {
-            static constexpr int PER = 16 / kIL;
-            static constexpr int W = 1 + K / PER;
-            static constexpr int C = (K % PER) * kIL;
-            static constexpr int bit = 1 << W;
-            static constexpr int slot(int j)
-            {
-                return (((C + j) >> W) << (W + 1)) | ((C + j) & (bit - 1));
-            }
-            __device__ static __forceinline__ void load(u64 (&w)[kIL], u64 (&ws)[kIL], const u64 *__restrict__ tw, int jb,
-                                                        int N)
-            {
-                const int tb = (N + jb) >> (Arr<T, R>::slot_bit(W) + 1);
-#pragma unroll
-                for (int j = 0; j < kIL; j++)
-                {
-                    u64x2 Wv;
-                    if constexpr (LZ == kInvFp64)
-                    {
-                        Wv.x = UNIFORM ? ((twd_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)]
-                                       : ((twd_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
-                        Wv.y = 0;
-                    }
-                    else if (UNIFORM)
-                        Wv = ((tw_const_t)tw)[__builtin_amdgcn_readfirstlane(tb) + Arr<T, R>::tw_offset(slot(j), W)];
-                    else
-                        Wv = ((tw_global_t)tw)[tb + Arr<T, R>::tw_offset(slot(j), W)];
-                    w[j] = Wv.x;
-                    ws[j] = Wv.y;
-                }
-            }
+            static constexpr int W = 1 + K / kStagesPerLayer;
+            using S = Stage<T, R, W, (K % kStagesPerLayer) * kIL, UNIFORM, LZ == kInvFp64>;
+            using S::bit;
+            using S::slot;
             static constexpr int layer = (T - 12) + 4 * (3 - R) + (W - 1); // 0-based on-chip layer index
             __device__ static __forceinline__ void run(u64 (&x)[32], const u64 (&w)[kIL], const u64 (&ws)[kIL], u64 two_p,
                                                        u64 neg_p, u64 rdp, ZeroPairs &zp)
@@ -158,29 +132,8 @@ namespace sealhip
 
         // first phase of the inverse: the 2^f consecutive coefficients that share the filler slot bits G run their low
         // layers (index bits 0 .. f-1, ascending); group twiddles in the order used: layer W = 0 (2^(f-1) entries),
-        // W = 1, ..., W = f-1 (1 entry). All coefficients are loaded before (one exposed latency), twiddles are
-        // requested one stage (FinalStage<T>::SG groups) ahead.
-        template <int T, int G, bool FP = false>
-        __device__ __forceinline__ void h_first_tw(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
-        {
-            constexpr int f = T - 12;
-            int base = 0;
-#pragma unroll
-            for (int W = 0; W < f; W++)
-            {
-                const int tb = (N + jb) >> (Arr<T, 4>::slot_bit(W) + 1);
-#pragma unroll
-                for (int o = 0; o < (1 << (f - 1 - W)); o++)
-                {
-                    const int s = (G << f) | (o << (W + 1));
-                    if constexpr (FP)
-                        tg[base + o].x = ((twd_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
-                    else
-                        tg[base + o] = ((tw_global_t)tw)[tb + Arr<T, 4>::tw_offset(s, W)];
-                }
-                base += 1 << (f - 1 - W);
-            }
-        }
+        // W = 1, ..., W = f-1 (1 entry): ntt_half.hpp GroupTw. All coefficients are loaded before (one exposed latency),
+        // twiddles are requested one stage (FinalStage<T>::SG groups) ahead.
         template <int T, int G, int LZ>
         __device__ __forceinline__ void h_first_group_regs(u64 (&x)[32], const u64x2 *tg, u64 neg_p, u64 two_p, u64 rdp, ZeroPairs &zp)
         {
@@ -231,12 +184,6 @@ namespace sealhip
         template <int T, int ST, int LZ, int I = 0>
         struct FirstStage
         {
-            __device__ static __forceinline__ void load(u64x2 *tg, const u64 *__restrict__ tw, int jb, int N)
-            {
-                h_first_tw<T, ST * FinalStage<T>::SG + I, LZ == kInvFp64>(tg + I * FinalStage<T>::NTW, tw, jb, N);
-                if constexpr (I + 1 < FinalStage<T>::SG)
-                    FirstStage<T, ST, LZ, I + 1>::load(tg, tw, jb, N);
-            }
             __device__ static __forceinline__ void run(u64 (&x)[32], const u64x2 *tg, u64 neg_p, u64 two_p, u64 rdp, ZeroPairs &zp)
             {
                 h_first_group_regs<T, ST * FinalStage<T>::SG + I, LZ>(x, tg + I * FinalStage<T>::NTW, neg_p, two_p, rdp, zp);
@@ -256,12 +203,12 @@ namespace sealhip
             {
                 u64x2 next[FinalStage<T>::SG * FinalStage<T>::NTW];
                 if constexpr (ST + 1 < FinalStage<T>::NS && AHEAD)
-                    FirstStage<T, ST + 1, LZ>::load(next, tw, jb, N);
+                    StageTw<T, ST + 1, false, LZ == kInvFp64>::load(next, tw, jb, N);
                 __builtin_amdgcn_sched_barrier(0);
                 FirstStage<T, ST, LZ>::run(x, cur, neg_p, two_p, rdp, zp);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (ST + 1 < FinalStage<T>::NS && !AHEAD)
-                    FirstStage<T, ST + 1, LZ>::load(next, tw, jb, N);
+                    StageTw<T, ST + 1, false, LZ == kInvFp64>::load(next, tw, jb, N);
                 if constexpr (ST + 1 < FinalStage<T>::NS)
                     FirstPipe<T, ST + 1, LZ, AHEAD>::run(x, next, tw, jb, N, neg_p, two_p, rdp, zp);
             }
@@ -450,17 +397,7 @@ namespace sealhip
             const int wave_base = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) & ~63); // (see fresh_tid)
             int half = 0, position;
             std::size_t poly;
-            if constexpr (WHOLE)
-            {
-                // same XCD-aware enumeration as half_block_map, one workgroup per live row
-                const std::size_t slot = blockIdx.x >> 3, npolys = nrows / map.rows;
-                const std::size_t v = static_cast<std::size_t>(blockIdx.x & 7u) * chunk + slot;
-                if (slot >= chunk || v >= npolys * static_cast<std::size_t>(live.n))
-                    return;
-                poly = v % npolys;
-                position = static_cast<int>(v / npolys);
-            }
-            else if constexpr (DY)
+            if constexpr (DY)
             {
                 // The three output polynomials of one (item, prime) read the same four input rows (c_0: a_0 b_0, c_1: all
                 // four, c_2: a_1 b_1): enumerate them next to each other -- v = (prime position, item, output) -- so that the six
@@ -478,18 +415,8 @@ namespace sealhip
                 position = static_cast<int>(v - pr * 3) * nr + static_cast<int>(pr / npolys);
                 poly = pr % npolys;
             }
-            else if constexpr (QUARTER)
-            {
-                // four workgroups per live row, next to each other on one XCD; `half` counts quarters here (gbase = half << T)
-                const std::size_t slot = blockIdx.x >> 3, npolys = nrows / map.rows;
-                half = static_cast<int>(slot & 3);
-                const std::size_t v = static_cast<std::size_t>(blockIdx.x & 7u) * chunk + (slot >> 2);
-                if ((slot >> 2) >= chunk || v >= npolys * static_cast<std::size_t>(live.n))
-                    return;
-                poly = v % npolys;
-                position = static_cast<int>(v / npolys);
-            }
-            else if (!half_block_map(blockIdx.x, nrows / map.rows, live.n, chunk, poly, position, half))
+            // one, two or four workgroups per live row; `half` counts quarters in the quarter-row form (gbase = half << T)
+            else if (!block_place<WHOLE ? 0 : (QUARTER ? 2 : 1)>(blockIdx.x, nrows / map.rows, live.n, chunk, poly, position, half))
                 return;
             const std::size_t row = poly * map.rows + live.slot[position];
             const unsigned short pid = map.prime[row % map.rows];
@@ -514,7 +441,7 @@ namespace sealhip
                 const int jloc = Arr<T, 4>::tid_index(fresh_tid(wave_base)), jl = Arr<T, 4>::tid_index(fresh_tid(wave_base));
                 u64x2 tg0[FinalStage<T>::SG * FinalStage<T>::NTW];
                 if constexpr (!DY)
-                    FirstStage<T, 0, LZ>::load(tg0, tw, gbase + jloc, N);
+                    StageTw<T, 0, false, LZ == kInvFp64>::load(tg0, tw, gbase + jloc, N);
                 if constexpr (DY)
                 {
                     // map.rows = 3 * kb: slot = I * kb + r selects the output polynomial I and the prime row r
@@ -535,7 +462,7 @@ namespace sealhip
                     else
                         h_load_dyadic2<T>(x, xr + ps, xr + 3 * ps, jl, p, P.ninv);
                     // (the first stage's twiddles only now: held across the products they cost 24 registers of scratch)
-                    FirstStage<T, 0, LZ>::load(tg0, tw, gbase + jloc, N);
+                    StageTw<T, 0, false, LZ == kInvFp64>::load(tg0, tw, gbase + jloc, N);
                 }
                 else
                 {
@@ -729,32 +656,26 @@ namespace sealhip
         }
 
         // The instances that serve a ring of 2^LOGN, in the order of kInvInstances (ntt_select.hpp; null where the table says
-        // the instance does not serve this ring size): launch_half_inv launches from this table and init_half_inv registers
-        // from it. The whole-row form of a ring is the half-row kernel of the ring twice as large, the quarter-row form
-        // that of the ring half as large (inv_kernel_logn).
+        // the instance does not serve this ring size), for kernel_table (ntt_half.hpp): launch_half_inv launches from that table
+        // and ntt_inv_half_init registers from it. The whole-row form of a ring is the half-row kernel of the ring twice as
+        // large, the quarter-row form that of the ring half as large (inv_kernel_logn).
         using InvKernel = void (*)(u64 *, const PrimeDev *, RowMap, std::size_t, std::size_t, const u64 *, std::size_t, LiveSlots,
                                    DyadicSrc, int);
-        template <int LOGN, int I>
-        InvKernel inv_kernel()
+        struct InvTable
         {
-            constexpr InvInstance inst = kInvInstances[I];
-            if constexpr (inv_instance_at(LOGN, inst))
-                return &ntt_inv_half_kernel<inv_kernel_logn(inst.shape, LOGN), inst.sched, inst.tensor_load(), inst.shape == kShapeWhole,
-                                            inst.shape == kShapeQuarter>;
-            else
-                return nullptr;
-        }
-        template <int LOGN, int... I>
-        const InvKernel *inv_kernels(std::integer_sequence<int, I...>)
-        {
-            static const InvKernel table[] = { inv_kernel<LOGN, I>()... };
-            return table;
-        }
-        template <int LOGN>
-        const InvKernel *inv_kernels()
-        {
-            return inv_kernels<LOGN>(std::make_integer_sequence<int, kInvInstanceCount>{});
-        }
+            using Kernel = InvKernel;
+            static constexpr int count = kInvInstanceCount;
+            template <int LOGN, int I>
+            static Kernel at()
+            {
+                constexpr InvInstance inst = kInvInstances[I];
+                if constexpr (inv_instance_at(LOGN, inst))
+                    return &ntt_inv_half_kernel<inv_kernel_logn(inst.shape, LOGN), inst.sched, inst.tensor_load(), inst.shape == kShapeWhole,
+                                                inst.shape == kShapeQuarter>;
+                else
+                    return nullptr;
+            }
+        };
         // a shape's exchange buffer: half of the 2^(KLOGN - 1) coefficients a workgroup of ntt_inv_half_kernel<KLOGN, ..> holds
         constexpr int inv_lds_bytes(int shape, int logn)
         {
@@ -797,7 +718,7 @@ namespace sealhip
                 return hipErrorInvalidValue;
             {
                 ProfScope prof(e, "ntt_inv_half", transformed_rows(nrows, map));
-                inv_kernels<LOGN>()[c.instance]<<<static_cast<unsigned>(blocks), 1 << (inv_kernel_logn(c.shape, LOGN) - 6),
+                kernel_table<InvTable, LOGN>()[c.instance]<<<static_cast<unsigned>(blocks), 1 << (inv_kernel_logn(c.shape, LOGN) - 6),
                                                   inv_lds_bytes(c.shape, LOGN), e.lane().stream>>>(
                     data, e.d_primes, map, nrows, chunk, src, src_poly_stride, live, dyadic ? *dyadic : DyadicSrc{}, c.canon);
                 const hipError_t err = hipGetLastError();
@@ -818,55 +739,32 @@ namespace sealhip
                 ntt_inv_top_kernel<<<static_cast<unsigned>(grid), 256, 0, e.lane().stream>>>(data, e.d_primes, map, LOGN, nitems, flags);
             return hipGetLastError();
         }
-
-        // the dynamic LDS limit of every instance that serves the ring
-        template <int LOGN>
-        hipError_t init_half_inv()
-        {
-            for (int i = 0; i < kInvInstanceCount; i++)
-                if (const InvKernel k = inv_kernels<LOGN>()[i])
-                {
-                    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                               inv_lds_bytes(kInvInstances[i].shape, LOGN));
-                    if (err != hipSuccess)
-                        return err;
-                }
-            return hipSuccess;
-        }
     } // namespace
 
     hipError_t ntt_inv_half(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags, const u64 *src,
                             std::size_t src_poly_stride)
     {
-        switch (e.logn)
-        {
-        case 14: return launch_half_inv<14>(e, data, nrows, map, flags, src, src_poly_stride);
-        case 15: return launch_half_inv<15>(e, data, nrows, map, flags, src, src_poly_stride);
-        case 16: return launch_half_inv<16>(e, data, nrows, map, flags, src, src_poly_stride);
-        default: return hipErrorInvalidValue;
-        }
+        return at_ring_size(e.logn, [&](auto logn) {
+            return launch_half_inv<decltype(logn)::value>(e, data, nrows, map, flags, src, src_poly_stride);
+        });
     }
 
     hipError_t ntt_inv_tensor(const Engine &e, u64 *data, std::size_t nrows, const RowMap &map, int flags, const u64 *x,
                               std::size_t item_stride, std::size_t poly_stride, int kb, bool square)
     {
         const DyadicSrc dy{ x, item_stride, poly_stride, kb, square ? 1 : 0 };
-        switch (e.logn)
-        {
-        case 14: return launch_half_inv<14>(e, data, nrows, map, flags, nullptr, 0, &dy);
-        case 15: return launch_half_inv<15>(e, data, nrows, map, flags, nullptr, 0, &dy);
-        case 16: return launch_half_inv<16>(e, data, nrows, map, flags, nullptr, 0, &dy);
-        default: return hipErrorInvalidValue;
-        }
+        return at_ring_size(e.logn, [&](auto logn) {
+            return launch_half_inv<decltype(logn)::value>(e, data, nrows, map, flags, nullptr, 0, &dy);
+        });
     }
 
     hipError_t ntt_inv_half_init()
     {
-        hipError_t err = init_half_inv<14>();
-        if (err == hipSuccess)
-            err = init_half_inv<15>();
-        if (err == hipSuccess)
-            err = init_half_inv<16>();
-        return err;
+        // the dynamic LDS limit of every instance that serves the ring
+        return at_every_ring_size([](auto logn) {
+            constexpr int LOGN = decltype(logn)::value;
+            return set_dynamic_lds(kernel_table<InvTable, LOGN>(), InvTable::count,
+                                   [](int i) { return inv_lds_bytes(kInvInstances[i].shape, LOGN); });
+        });
     }
 } // namespace sealhip

@@ -17,7 +17,7 @@ namespace sealhip
     constexpr int kNttAnyRep = 8;    // inverse: the consumer canonicalises, any representative below 2p may be stored
     constexpr int kNttReduceOut = 0x10; // forward, single-pass kernel: one more conditional subtraction, outputs in [0, 2p)
     constexpr int kNttApprox = 0x20;   // forward, with kNttAnyRep or a consumer that takes outputs below (2 + g) p: approximate quotient (ntt_bounds.hpp section 2)
-    constexpr int kNttPolyMajor = 0x4000;        // forward half kernel: live positions grouped item by item (ntt_half.hpp half_block_map; group size in bits 16-23)
+    constexpr int kNttPolyMajor = 0x4000;        // forward half kernel: live positions grouped item by item (ntt_half.hpp block_place; group size in bits 16-23)
     constexpr int kNttSmallQuot = 0x1000000;     // (launcher-internal) canonical approximate-quotient launch: single-precision quotient estimate in the store
     constexpr int kNttDebugNoSignal = 0x40; // forward half kernel: never send the hand-off signal (tests of the time-out path)
     // forward, single-pass kernel, with kNttReduceOut, in place: the producer of the rows has already applied the top layer
@@ -243,7 +243,7 @@ namespace sealhip
         c.tickets = !(top_done || all_gathered);
         if (f.suppress_signal)
             flags |= kNttDebugNoSignal;
-        // (see half_block_map)
+        // (see ntt_half.hpp block_place)
         const bool one_source = all_gathered && f.treatment <= kTreatCondSub && f.live_n > 1 && f.same_source;
         // Floating-point instance (devmath.hpp): every live prime below 2^50, inputs below 2^52 (residues, or gathered
         // words of another key prime, or the output of a load treatment), and a launch that does not ask for the
