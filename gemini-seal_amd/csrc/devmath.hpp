@@ -211,6 +211,14 @@ namespace sealhip
         hi += ph + (nl < lo);
         lo = nl;
     }
+    // (lo, hi) += a * b as one 128-bit multiply-add: the compiler forms the product from four 32 x 32 multiply-adds and
+    // adds it with one carry chain, where mac128's separate low and high products repeat partial products
+    __device__ __forceinline__ void mac128_wide(u64 &lo, u64 &hi, u64 a, u64 b)
+    {
+        const unsigned __int128 acc = ((static_cast<unsigned __int128>(hi) << 64) | lo) + static_cast<unsigned __int128>(a) * b;
+        lo = static_cast<u64>(acc);
+        hi = static_cast<u64>(acc >> 64);
+    }
 
     __device__ __forceinline__ u64 add_mod(u64 a, u64 b, u64 p) // polyarithsmallmod.h:261-299
     {

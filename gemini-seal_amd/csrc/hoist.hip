@@ -8,6 +8,7 @@
 // read of one aligned 64-word block would touch: no traffic amplification, no LDS staging.
 #include "engine.hpp"
 #include "instance_dispatch.hpp"
+#include "ks_inner.hpp"
 
 namespace sealhip
 {
@@ -32,42 +33,36 @@ namespace sealhip
                                                                      std::size_t n_groups)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            // a workgroup lies inside one row (N >= kThreads, the launcher sees to it): element, row and item group come from
-            // the block index alone, so they, the row's prime and every base address are wave-uniform (scalar registers)
-            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
-            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
-            unsigned q = blockIdx.x / blocks_per_row;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = block_lane(N); // (element, row and item group, so every base address, are wave-uniform)
+            const std::size_t c = lane.c;
+            unsigned q = static_cast<unsigned>(lane.q);
             const int el = static_cast<int>(q % elts.n);
             q /= elts.n;
-            const int r = static_cast<int>(q % rows);
-            const std::size_t grp = q / rows;
+            const int r = static_cast<int>(q % dim.rows);
+            const std::size_t grp = q / dim.rows;
             if (grp >= n_groups)
                 return;
             const std::size_t item0 = grp * group;
             const std::size_t item1 = item0 + group < count ? item0 + group : count;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N;
-            const std::size_t src_off = row_off + elts.table[el][c];
-            const u64 *pkey = elts.key[el] + static_cast<std::size_t>(rns_idx) * N + c;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t src_off = m.row_off() + elts.table[el][c];
+            const u64 *pkey = elts.key[el] + m.prime_row() + c;
             u64 k0[ND], k1[ND], x[ND], xn[ND];
 #pragma unroll
             for (int j = 0; j < ND; j++)
             {
-                k0[j] = pkey[(2 * static_cast<std::size_t>(j)) * key_comp];
-                k1[j] = pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp];
+                k0[j] = pkey[m.key_slice(j, 0)];
+                k1[j] = pkey[m.key_slice(j, 1)];
             }
             auto load_x = [&](u64(&dst)[ND], std::size_t item) {
 #pragma unroll
                 for (int j = 0; j < ND; j++)
-                    dst[j] = j == my_digit ? target[item * target_stride + src_off]
-                                           : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
+                    dst[j] = j == m.my_digit ? target[item * target_stride + src_off]
+                                             : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
             };
             load_x(x, item0);
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacMod mod = mac_mod(primes, m);
             for (std::size_t item = item0; item < item1; item++)
             {
                 if (item + 1 < item1)
@@ -75,13 +70,10 @@ namespace sealhip
                 u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
 #pragma unroll
                 for (int j = 0; j < ND; j++)
-                {
-                    mac128(lo0, hi0, x[j], k0[j]);
-                    mac128(lo1, hi1, x[j], k1[j]);
-                }
-                u64 *pp = prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + row_off + c;
-                store_stream(pp, barrett_reduce_128(lo0, hi0, p, cr0, cr1));
-                store_stream(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo1, hi1, p, cr0, cr1));
+                    mac2(x[j], k0[j], k1[j], lo0, hi0, lo1, hi1);
+                u64 *pp = prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + m.row_off() + c;
+                store_stream(pp, mod.reduce(lo0, hi0));
+                store_stream(pp + m.comp(), mod.reduce(lo1, hi1));
 #pragma unroll
                 for (int j = 0; j < ND; j++)
                     x[j] = xn[j];
@@ -100,34 +92,26 @@ namespace sealhip
                                                                           std::size_t count, int logn, int nd)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
-            const std::size_t c = i & (N - 1);
-            std::size_t q = i >> logn;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = flat_lane(logn);
+            const std::size_t c = lane.c;
+            std::size_t q = lane.q;
             const int el = static_cast<int>(q % elts.n);
             q /= elts.n;
-            const int r = static_cast<int>(q % rows);
-            const std::size_t item = q / rows;
+            const int r = static_cast<int>(q % dim.rows);
+            const std::size_t item = q / dim.rows;
             if (item >= count)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N;
-            const std::size_t src_off = row_off + elts.table[el][c];
-            const u64 *pkey = elts.key[el] + static_cast<std::size_t>(rns_idx) * N + c;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t src_off = m.row_off() + elts.table[el][c];
+            const u64 *pkey = elts.key[el] + m.prime_row() + c;
             u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
             for (int j = 0; j < nd; j++)
-            {
-                const u64 x = j == my_digit ? target[item * target_stride + src_off]
-                                            : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
-                mac128(lo0, hi0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
-                mac128(lo1, hi1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
-            }
-            const PrimeDev &P = primes[rns_idx];
-            u64 *pp = prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + row_off + c;
-            store_stream(pp, barrett_reduce_128(lo0, hi0, P.p, P.cr0, P.cr1));
-            store_stream(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo1, hi1, P.p, P.cr0, P.cr1));
+                digit_mac(m, j, ext + item * ext_stride + src_off, ext_digit_stride, pkey, target + item * target_stride + src_off, lo0, hi0,
+                          lo1, hi1);
+            const MacMod mod = mac_mod(primes, m);
+            store2(prod + (static_cast<std::size_t>(el) * count + item) * prod_stride + m.row_off() + c, m.comp(), mod.reduce(lo0, hi0),
+                   mod.reduce(lo1, hi1));
         }
 
         // sigma_g(c_0) of every (element, item) in one pass: out[element][item][k][N] from component 0 of ct[item]
@@ -188,25 +172,20 @@ namespace sealhip
         {
             constexpr int G = 4 / S;
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            // (a workgroup lies inside one row, as in hoist_mac_kernel: row, item group and sum group are wave-uniform)
-            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
-            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
-            unsigned q = blockIdx.x / blocks_per_row;
-            const int r = static_cast<int>(q % rows);
-            q /= rows;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = block_lane(N); // (row, item group and sum group are wave-uniform)
+            const std::size_t c = lane.c;
+            unsigned q = static_cast<unsigned>(lane.q);
+            const int r = static_cast<int>(q % dim.rows);
+            q /= dim.rows;
             const std::size_t sum_groups = (n_sums + S - 1) / S;
             const std::size_t sum0 = static_cast<std::size_t>(q % sum_groups) * S;
             const std::size_t item0 = static_cast<std::size_t>(q / sum_groups) * G;
             if (item0 >= count)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
-            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t row_off = m.row_off(), key_comp = m.key_comp(), prime_off = m.prime_row() + c;
+            const MacMod mod = mac_mod(primes, m);
             u64 lo[G][S][2], hi[G][S][2];
 #pragma unroll
             for (int g = 0; g < G; g++)
@@ -241,18 +220,11 @@ namespace sealhip
                     const u64 *px = pe;
 #pragma unroll
                     for (int j = 0; j < ND; j++, px += ext_digit_stride)
-                    {
-                        const u64 x = j == my_digit ? *pt : *px;
-                        mac128(l0, h0, x, k0[j]);
-                        mac128(l1, h1, x, k1[j]);
-                    }
-                    const u64 p0 = barrett_reduce_128(l0, h0, p, cr0, cr1), p1 = barrett_reduce_128(l1, h1, p, cr0, cr1);
+                        mac2(j == m.my_digit ? *pt : *px, k0[j], k1[j], l0, h0, l1, h1);
+                    const u64 p0 = mod.reduce(l0, h0), p1 = mod.reduce(l1, h1);
 #pragma unroll
                     for (int s = 0; s < S; s++)
-                    {
-                        mac128(lo[g][s][0], hi[g][s][0], w[s], p0);
-                        mac128(lo[g][s][1], hi[g][s][1], w[s], p1);
-                    }
+                        mac2(w[s], p0, p1, lo[g][s][0], hi[g][s][0], lo[g][s][1], hi[g][s][1]);
                 }
             }
 #pragma unroll
@@ -263,15 +235,13 @@ namespace sealhip
                     if (item0 + g >= count || sum0 + s >= n_sums)
                         continue;
                     u64 *pa = acc + ((sum0 + s) * count + item0 + g) * acc_stride + row_off + c;
-                    u64 v0 = barrett_reduce_128(lo[g][s][0], hi[g][s][0], p, cr0, cr1);
-                    u64 v1 = barrett_reduce_128(lo[g][s][1], hi[g][s][1], p, cr0, cr1);
-                    if (add)
+                    u64 v0 = mod.reduce(lo[g][s][0], hi[g][s][0]), v1 = mod.reduce(lo[g][s][1], hi[g][s][1]);
+                    if (add) // (inline: as add_store2 every instance is scheduled differently, profiles/r21/device_code.txt)
                     {
-                        v0 = add_mod(v0, pa[0], p);
-                        v1 = add_mod(v1, pa[static_cast<std::size_t>(rows) * N], p);
+                        v0 = add_mod(v0, pa[0], mod.p);
+                        v1 = add_mod(v1, pa[m.comp()], mod.p);
                     }
-                    store_stream(pa, v0);
-                    store_stream(pa + static_cast<std::size_t>(rows) * N, v1);
+                    store2(pa, m.comp(), v0, v1);
                 }
         }
 
@@ -284,22 +254,18 @@ namespace sealhip
             std::size_t n_sums, int logn, int nd, int add)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
-            const std::size_t c = i & (N - 1);
-            std::size_t q = i >> logn;
-            const int r = static_cast<int>(q % rows);
-            q /= rows;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = flat_lane(logn);
+            const std::size_t c = lane.c;
+            std::size_t q = lane.q;
+            const int r = static_cast<int>(q % dim.rows);
+            q /= dim.rows;
             const std::size_t item = q % count, sum = q / count;
             if (sum >= n_sums)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
-            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t row_off = m.row_off(), prime_off = m.prime_row() + c;
+            const MacMod mod = mac_mod(primes, m);
             u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
             for (int el = 0; el < elts.n; el++)
             {
@@ -307,26 +273,14 @@ namespace sealhip
                 const std::size_t src_off = row_off + elts.table[el][c];
                 u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
                 for (int j = 0; j < nd; j++)
-                {
-                    const u64 x = j == my_digit
-                                      ? target[item * target_stride + src_off]
-                                      : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + src_off];
-                    mac128(l0, h0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
-                    mac128(l1, h1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
-                }
+                    digit_mac(m, j, ext + item * ext_stride + src_off, ext_digit_stride, pkey, target + item * target_stride + src_off, l0, h0,
+                              l1, h1);
                 const u64 w = elts.w[el][sum * w_sum_stride + prime_off];
-                mac128(lo0, hi0, w, barrett_reduce_128(l0, h0, p, cr0, cr1));
-                mac128(lo1, hi1, w, barrett_reduce_128(l1, h1, p, cr0, cr1));
+                mac128(lo0, hi0, w, mod.reduce(l0, h0));
+                mac128(lo1, hi1, w, mod.reduce(l1, h1));
             }
             u64 *pa = acc + (sum * count + item) * acc_stride + row_off + c;
-            u64 v0 = barrett_reduce_128(lo0, hi0, p, cr0, cr1), v1 = barrett_reduce_128(lo1, hi1, p, cr0, cr1);
-            if (add)
-            {
-                v0 = add_mod(v0, pa[0], p);
-                v1 = add_mod(v1, pa[static_cast<std::size_t>(rows) * N], p);
-            }
-            store_stream(pa, v0);
-            store_stream(pa + static_cast<std::size_t>(rows) * N, v1);
+            add_store2(pa, m.comp(), mod.reduce(lo0, hi0), mod.reduce(lo1, hi1), add, mod.p);
         }
 
         // base_s of section 16: out[sum][item][0][r][c] = sum_i W[s][i][r][c] * C[item][0][r][T_i[c]] over every element of
@@ -403,22 +357,17 @@ namespace sealhip
         {
             constexpr int G = 4;
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            // (a workgroup lies inside one row, as in hoist_mac_kernel: row and item group are wave-uniform)
-            const unsigned blocks_per_row = static_cast<unsigned>(N / kThreads);
-            const std::size_t c = static_cast<std::size_t>(blockIdx.x % blocks_per_row) * kThreads + threadIdx.x;
-            const unsigned q = blockIdx.x / blocks_per_row;
-            const int r = static_cast<int>(q % rows);
-            const std::size_t item0 = static_cast<std::size_t>(q / rows) * G;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = block_lane(N); // (row and item group are wave-uniform)
+            const std::size_t c = lane.c;
+            const unsigned q = static_cast<unsigned>(lane.q);
+            const int r = static_cast<int>(q % dim.rows);
+            const std::size_t item0 = static_cast<std::size_t>(q / dim.rows) * G;
             if (item0 >= count)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N, comp = static_cast<std::size_t>(rows) * N;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
-            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t row_off = m.row_off(), comp = m.comp(), key_comp = m.key_comp(), prime_off = m.prime_row() + c;
+            const MacMod mod = mac_mod(primes, m);
             u64 s[G][2];
 #pragma unroll
             for (int g = 0; g < G; g++)
@@ -435,8 +384,8 @@ namespace sealhip
                     {
                         if (item0 + g >= count)
                             break;
-                        s[g][0] = add_mod(s[g][0], pa[0], p);
-                        s[g][1] = add_mod(s[g][1], pa[comp], p);
+                        s[g][0] = add_mod(s[g][0], pa[0], mod.p);
+                        s[g][1] = add_mod(s[g][1], pa[comp], mod.p);
                     }
                     continue;
                 }
@@ -463,16 +412,12 @@ namespace sealhip
                     const u64 *px = pe;
 #pragma unroll
                     for (int j = 0; j < ND; j++, px += ext_digit_stride)
-                    {
-                        const u64 x = j == my_digit ? *pt : *px;
-                        mac128(l0, h0, x, k0[j]);
-                        mac128(l1, h1, x, k1[j]);
-                    }
-                    s[g][0] = add_mod(s[g][0], barrett_reduce_128(l0, h0, p, cr0, cr1), p);
-                    s[g][1] = add_mod(s[g][1], barrett_reduce_128(l1, h1, p, cr0, cr1), p);
+                        mac2(j == m.my_digit ? *pt : *px, k0[j], k1[j], l0, h0, l1, h1);
+                    s[g][0] = add_mod(s[g][0], mod.reduce(l0, h0), mod.p);
+                    s[g][1] = add_mod(s[g][1], mod.reduce(l1, h1), mod.p);
                     if (pa)
                     {
-                        s[g][0] = add_mod(s[g][0], *pa, p);
+                        s[g][0] = add_mod(s[g][0], *pa, mod.p);
                         pa += accj_stride;
                     }
                 }
@@ -483,14 +428,7 @@ namespace sealhip
                 if (item0 + g >= count)
                     continue;
                 u64 *po = acc + (item0 + g) * acc_stride + row_off + c;
-                u64 v0 = s[g][0], v1 = s[g][1];
-                if (add)
-                {
-                    v0 = add_mod(v0, po[0], p);
-                    v1 = add_mod(v1, po[comp], p);
-                }
-                store_stream(po, v0);
-                store_stream(po + comp, v1);
+                add_store2(po, comp, s[g][0], s[g][1], add, mod.p);
             }
         }
 
@@ -502,21 +440,16 @@ namespace sealhip
             std::size_t acc_stride, std::size_t count, int logn, int nd, int add)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
-            const std::size_t c = i & (N - 1);
-            const std::size_t q = i >> logn;
-            const int r = static_cast<int>(q % rows);
-            const std::size_t item = q / rows;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = flat_lane(logn);
+            const std::size_t c = lane.c;
+            const int r = static_cast<int>(lane.q % dim.rows);
+            const std::size_t item = lane.q / dim.rows;
             if (item >= count)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N, comp = static_cast<std::size_t>(rows) * N;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
-            const std::size_t prime_off = static_cast<std::size_t>(rns_idx) * N + c;
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t row_off = m.row_off(), comp = m.comp(), prime_off = m.prime_row() + c;
+            const MacMod mod = mac_mod(primes, m);
             u64 s0 = 0, s1 = 0;
             for (int el = 0; el < elts.n; el++)
             {
@@ -524,34 +457,22 @@ namespace sealhip
                 const u64 *pa = elts.accj[el];
                 if (!tab)
                 {
-                    s0 = add_mod(s0, pa[item * accj_stride + row_off + c], p);
-                    s1 = add_mod(s1, pa[item * accj_stride + comp + row_off + c], p);
+                    s0 = add_mod(s0, pa[item * accj_stride + row_off + c], mod.p);
+                    s1 = add_mod(s1, pa[item * accj_stride + comp + row_off + c], mod.p);
                     continue;
                 }
                 const u64 *pkey = elts.key[el] + prime_off;
                 const std::size_t src_off = row_off + tab[c];
                 u64 l0 = 0, h0 = 0, l1 = 0, h1 = 0;
                 for (int j = 0; j < nd; j++)
-                {
-                    const u64 x = j == my_digit ? elts.inb[el][item * inb_stride + src_off]
-                                                : elts.ext[el][item * ext_stride +
-                                                               static_cast<std::size_t>(j) * ext_digit_stride + src_off];
-                    mac128(l0, h0, x, pkey[(2 * static_cast<std::size_t>(j)) * key_comp]);
-                    mac128(l1, h1, x, pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp]);
-                }
-                s0 = add_mod(s0, barrett_reduce_128(l0, h0, p, cr0, cr1), p);
-                s1 = add_mod(s1, barrett_reduce_128(l1, h1, p, cr0, cr1), p);
+                    digit_mac(m, j, elts.ext[el] + item * ext_stride + src_off, ext_digit_stride, pkey,
+                              elts.inb[el] + item * inb_stride + src_off, l0, h0, l1, h1);
+                s0 = add_mod(s0, mod.reduce(l0, h0), mod.p);
+                s1 = add_mod(s1, mod.reduce(l1, h1), mod.p);
                 if (pa)
-                    s0 = add_mod(s0, pa[item * accj_stride + src_off], p);
+                    s0 = add_mod(s0, pa[item * accj_stride + src_off], mod.p);
             }
-            u64 *po = acc + item * acc_stride + row_off + c;
-            if (add)
-            {
-                s0 = add_mod(s0, po[0], p);
-                s1 = add_mod(s1, po[comp], p);
-            }
-            store_stream(po, s0);
-            store_stream(po + comp, s1);
+            add_store2(acc + item * acc_stride + row_off + c, comp, s0, s1, add, mod.p);
         }
 
         // BASE of section 17, on the k ciphertext rows: out[item][0][r][c] = sum over the giants of the launch of

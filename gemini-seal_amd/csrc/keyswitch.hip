@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include "engine.hpp"
 #include "instance_dispatch.hpp"
+#include "ks_inner.hpp"
 
 namespace sealhip
 {
@@ -117,33 +118,22 @@ namespace sealhip
                                                                   std::size_t count, int logn, int j0, int j1)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
-            const std::size_t c = i & (N - 1);
-            const std::size_t rr = i >> logn;
-            const int r = static_cast<int>(rr % rows);
-            const std::size_t item = rr / rows;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = flat_lane(logn);
+            const int r = static_cast<int>(lane.q % dim.rows);
+            const std::size_t item = lane.q / dim.rows;
             if (item >= count)
                 return;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const u64 *pext = ext + item * ext_stride + static_cast<std::size_t>(r) * N + c;
-            const u64 *pkey = key + static_cast<std::size_t>(rns_idx) * N + c;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const MacRow m = mac_row(dim, d, r, N);
             u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+            const u64 *pext = ext + item * ext_stride + m.row_off() + lane.c, *pkey = key + m.prime_row() + lane.c;
+            const u64 *own = target + m.row_off() + lane.c + item * target_stride;
             for (int j = j0; j < j1; j++) // (all digits of the level, or one device's share of them: latency mode)
-            {
-                const u64 x = j == my_digit ? target[item * target_stride + static_cast<std::size_t>(r) * N + c]
-                                            : pext[static_cast<std::size_t>(j) * ext_digit_stride];
-                const u64 k0 = pkey[(2 * static_cast<std::size_t>(j)) * key_comp];
-                const u64 k1 = pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp];
-                mac128(lo0, hi0, x, k0);
-                mac128(lo1, hi1, x, k1);
-            }
-            const PrimeDev &P = primes[rns_idx];
-            u64 *pp = prod + item * prod_stride + static_cast<std::size_t>(r) * N + c;
-            pp[0] = barrett_reduce_128(lo0, hi0, P.p, P.cr0, P.cr1);
-            pp[static_cast<std::size_t>(rows) * N] = barrett_reduce_128(lo1, hi1, P.p, P.cr0, P.cr1);
+                digit_mac(m, j, pext, ext_digit_stride, pkey, own, lo0, hi0, lo1, hi1);
+            u64 *pp = prod + item * prod_stride + m.row_off() + lane.c;
+            const MacMod mod = mac_mod(primes, m);
+            pp[0] = barrett_reduce_128(lo0, hi0, mod.p, mod.cr0, mod.cr1); // (not mod.reduce: it reschedules this kernel; plain stores as ever)
+            pp[m.comp()] = barrett_reduce_128(lo1, hi1, mod.p, mod.cr0, mod.cr1);
         }
 
         // The same inner product with the key words of a lane's (row, coefficient) kept in registers across
@@ -165,50 +155,45 @@ namespace sealhip
                                                                         std::size_t count, int logn, std::size_t group)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
-            const std::size_t i = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x;
-            const std::size_t c = i & (N - 1);
-            const std::size_t rr = i >> logn;
-            const int r = static_cast<int>(rr % rows);
-            const std::size_t item0 = (rr / rows) * group;
+            const MacDims dim = mac_dims(d);
+            const MacLane lane = flat_lane(logn);
+            const int r = static_cast<int>(lane.q % dim.rows);
+            const std::size_t item0 = (lane.q / dim.rows) * group;
             if (item0 >= count)
                 return;
             const std::size_t item1 = item0 + group < count ? item0 + group : count;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N + c;
-            const u64 *pkey = key + static_cast<std::size_t>(rns_idx) * N + c;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
+            const MacRow m = mac_row(dim, d, r, N);
+            const std::size_t off = m.row_off() + lane.c;
+            const u64 *pkey = key + m.prime_row() + lane.c;
             u64 k0[ND], k1[ND], x[ND], xn[ND];
 #pragma unroll
             for (int j = 0; j < ND; j++)
             {
-                k0[j] = pkey[(2 * static_cast<std::size_t>(j)) * key_comp];
-                k1[j] = pkey[(2 * static_cast<std::size_t>(j) + 1) * key_comp];
+                k0[j] = pkey[m.key_slice(j, 0)];
+                k1[j] = pkey[m.key_slice(j, 1)];
             }
             auto load_x = [&](u64(&dst)[ND], std::size_t item) {
 #pragma unroll
                 for (int j = 0; j < ND; j++)
-                    dst[j] = j == my_digit ? target[item * target_stride + row_off]
-                                           : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + row_off];
+                    dst[j] = j == m.my_digit ? target[item * target_stride + off]
+                                             : ext[item * ext_stride + static_cast<std::size_t>(j) * ext_digit_stride + off];
             };
             load_x(x, item0);
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacMod mod = mac_mod(primes, m);
             for (std::size_t item = item0; item < item1; item++)
             {
                 if (item + 1 < item1)
                     load_x(xn, item + 1);
                 u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
 #pragma unroll
-                for (int j = 0; j < ND; j++)
+                for (int j = 0; j < ND; j++) // (not mac2: instance 4 would be scheduled differently)
                 {
                     mac128(lo0, hi0, x[j], k0[j]);
                     mac128(lo1, hi1, x[j], k1[j]);
                 }
-                u64 *pp = prod + item * prod_stride + row_off;
-                store_stream(pp, barrett_reduce_128(lo0, hi0, p, cr0, cr1));
-                store_stream(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo1, hi1, p, cr0, cr1));
+                u64 *pp = prod + item * prod_stride + off;
+                store_stream(pp, mod.reduce(lo0, hi0));
+                store_stream(pp + m.comp(), mod.reduce(lo1, hi1));
 #pragma unroll
                 for (int j = 0; j < ND; j++)
                     x[j] = xn[j];
@@ -225,15 +210,7 @@ namespace sealhip
         // pair 2c, 2c + 1 is taken as it is. The words are below 2^64 and nd p < 2^64 (bounds::fwd_split_admits): the 128-bit
         // sums cannot wrap. Workgroups never straddle a row (N/2 >= 2^13 lanes per row): the row's facts are scalars.
         // PF: request the next ciphertext's words before the current one is accumulated (dropped where it would spill).
-        // (lo, hi) += a * b as one 128-bit multiply-add: the compiler forms the product from four 32 x 32 multiply-adds and
-        // adds it with one carry chain, where mac128's separate low and high products repeat partial products
-        __device__ __forceinline__ void mac128_wide(u64 &lo, u64 &hi, u64 a, u64 b)
-        {
-            const unsigned __int128 acc = ((static_cast<unsigned __int128>(hi) << 64) | lo) + static_cast<unsigned __int128>(a) * b;
-            lo = static_cast<u64>(acc);
-            hi = static_cast<u64>(acc >> 64);
-        }
-
+        // The sums use mac128_wide (devmath.hpp).
         template <int ND, bool PF>
         __global__ __launch_bounds__(kThreads) void ks_mac_pair_kernel(const KsDev *__restrict__ d,
                                                                        const PrimeDev *__restrict__ primes,
@@ -246,20 +223,20 @@ namespace sealhip
                                                                        std::size_t count, int logn, std::size_t group)
         {
             const std::size_t N = static_cast<std::size_t>(1) << logn, H = N >> 1;
-            const int k = d->k, nsp = d->nsp, rows = k + nsp, n_total = d->n_total;
+            const MacDims dim = mac_dims(d);
             const std::size_t lane0 = blockIdx.x * static_cast<std::size_t>(kThreads); // (uniform: H is a multiple of kThreads)
             const std::size_t c0 = lane0 & (H - 1); // the workgroup's first pair; the lane's is c0 + threadIdx.x
             const std::size_t rr = lane0 >> (logn - 1);
-            const int r = static_cast<int>(rr % rows);
-            const std::size_t item0 = (rr / rows) * group;
+            const int r = static_cast<int>(rr % dim.rows);
+            const std::size_t item0 = (rr / dim.rows) * group;
             if (item0 >= count)
                 return;
             const std::size_t item1 = item0 + group < count ? item0 + group : count;
-            const int rns_idx = d->row_prime[r];
-            const int my_digit = r < k ? r / nsp : -1;
-            const std::size_t row_off = static_cast<std::size_t>(r) * N;
-            const PrimeDev &P = primes[rns_idx];
-            const u64 p = P.p, two_p = P.two_p, cr0 = P.cr0, cr1 = P.cr1;
+            const MacRow m = mac_row(dim, d, r, N);
+            const int my_digit = m.my_digit;
+            const std::size_t row_off = m.row_off();
+            const MacMod mod = mac_mod(primes, m);
+            const u64 p = mod.p, two_p = mod.two_p, cr0 = mod.cr0, cr1 = mod.cr1;
             // every address is a uniform base (scalar registers) plus the lane's 32-bit byte offset: one offset register for
             // the 8-byte words and one for the 16-byte pairs instead of a 64-bit address per load
             const unsigned off8 = threadIdx.x * 8u, off16 = threadIdx.x * 16u;
@@ -269,9 +246,9 @@ namespace sealhip
             const auto pair = [](const u64 *base, unsigned off) {
                 return *reinterpret_cast<const ulonglong2 *>(reinterpret_cast<const char *>(base) + off);
             };
-            const u64 *key_row = key + static_cast<std::size_t>(rns_idx) * N + 2 * c0;
-            const std::size_t key_comp = static_cast<std::size_t>(n_total) * N;
-            const ulonglong2 w = pair(P.fwd + 2 * (H + c0), off16); // (twiddle, its Shoup quotient) of pair c
+            const u64 *key_row = key + m.prime_row() + 2 * c0;
+            const std::size_t key_comp = m.key_comp();
+            const ulonglong2 w = pair(primes[m.rns_idx].fwd + 2 * (H + c0), off16); // (twiddle, its Shoup quotient) of pair c
             ulonglong2 k0[ND], k1[ND];
 #pragma unroll
             for (int j = 0; j < ND; j++)
@@ -317,7 +294,7 @@ namespace sealhip
                 }
                 u64 *pp = reinterpret_cast<u64 *>(reinterpret_cast<char *>(prod + item * prod_stride + row_off + 2 * c0) + off16);
                 store_stream2(pp, barrett_reduce_128(lo00, hi00, p, cr0, cr1), barrett_reduce_128(lo01, hi01, p, cr0, cr1));
-                store_stream2(pp + static_cast<std::size_t>(rows) * N, barrett_reduce_128(lo10, hi10, p, cr0, cr1),
+                store_stream2(pp + m.comp(), barrett_reduce_128(lo10, hi10, p, cr0, cr1),
                               barrett_reduce_128(lo11, hi11, p, cr0, cr1));
             };
             u64 xe[ND], xo[ND];

@@ -125,6 +125,12 @@ def test_ring_smaller_than_a_workgroup(S):
         se.compare(k, 3, _baby(se.n), _giant(se.n), ("ring 6", k))
 
 
+def test_loop_kernel_second_launch_adds(S):
+    """N = 2^7 and 17 distinct giants: the second launch of the per-lane loop kernel adds into ACC"""
+    se = Session(S, S.SCHEME_CKKS, 7, [50] * 3 + [51], 1, S.MODE_PARITY)
+    se.compare(3, 2, _baby(se.n)[:2], [2 * i + 3 for i in range(17)], "ring 7, 17 giants")
+
+
 def test_more_giants_and_babies_than_one_launch(S):
     """17 giants (the identity 12th, one repeated): the second launch of the giant kernel and of the BASE update adds; 17
     babies: the second launch of section 16's kernels adds into workspace"""

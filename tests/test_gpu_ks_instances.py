@@ -105,7 +105,9 @@ CASES["sweep_bfv_strict_dot"] = dot_calls("sweep_bfv_strict", BFV_LEVELS)
 CASES["digits_nsp3"] = all_ops("nsp3", range(1, 13), (17, 2), 2)
 CASES["digits_nsp9"] = all_ops("nsp9", (10, 9, 1), (17, 2), 2)
 CASES["rings"] = (all_ops("ring6", (3, 1), (17, 2), 3) + all_ops("ring7", (3, 1), (17, 2), 3)
-                  + all_ops("ring8", (3, 1), (17, 2), 3) + all_ops("ring8_17", (17,), (17, 2), 3))
+                  + all_ops("ring8", (3, 1), (17, 2), 3) + all_ops("ring8_17", (17,), (17, 2), 3)
+                  # 17 distinct elements: the second launch of hoist_dot_mac_loop_kernel adds into acc
+                  + [Call("ring7", "dot", 3, 2, tuple(range(17)), 2)])
 CASES["extremes_switch_many"] = [Call("extreme", "switch", 16, 17, extreme=True),
                                  Call("extreme", "switch", 16, 3, extreme=True),
                                  Call("extreme", "many", 16, 9, PAIR, extreme=True)]
