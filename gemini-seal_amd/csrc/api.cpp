@@ -17,6 +17,7 @@
 #include "engine.hpp"
 #include "evalmod_plan.hpp"
 #include "homdft_plan.hpp"
+#include "lintrans_plan.hpp"
 #include "poly_plan.hpp"
 
 using namespace sealhip;
@@ -2560,6 +2561,192 @@ long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_t
         op_slots_to_coeffs(e, *tables->tables, re, im, count, keys, o);
         sink.read_pass(o, 2, static_cast<std::size_t>(p.out_level) * h.n, count);
     });
+}
+
+/* ------------------------------------------------------------------ matrix-vector products from a caller's matrix */
+extern "C++" {
+struct sealhip_linear_transform
+{
+    LinearTransform *tables = nullptr;
+};
+
+namespace
+{
+    // The checks that need no device, in the order the header documents; mask null = every diagonal
+    ltplan::Plan lintrans_make_plan(const Engine &h, uint32_t d, const uint8_t *mask, uint32_t n1)
+    {
+        if (h.scheme != 2)
+            throw std::invalid_argument("linear transforms are CKKS only");
+        return ltplan::make_plan(static_cast<uint32_t>(h.logn - 1), d, mask, n1);
+    }
+
+    // d alone, for the entries that have no mask yet
+    void check_lintrans_size(const Engine &h, uint32_t d)
+    {
+        if (h.scheme != 2)
+            throw std::invalid_argument("linear transforms are CKKS only");
+        if (!ltplan::is_pow2(d) || d > h.n / 2)
+            throw std::invalid_argument("d must be a power of two between 1 and N/2");
+    }
+
+    void lintrans_plan_to_abi(const Engine &h, const ltplan::Plan &p, sealhip_lintrans_plan *out)
+    {
+        std::memset(out, 0, sizeof(*out));
+        out->d = p.d;
+        out->n_diagonals = p.n_diagonals;
+        out->n1 = p.n1;
+        out->n_baby = static_cast<uint32_t>(p.baby.size());
+        out->n_giant = static_cast<uint32_t>(p.giant.size());
+        out->n_key_steps = static_cast<uint32_t>(p.key_steps.size());
+        out->table_words = static_cast<uint64_t>(p.cells()) * h.key_moduli.size() * h.n;
+        out->temp_bytes_per_item = 0;
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_linear_transform_plan(const sealhip_context *ctx, uint32_t d, const uint8_t *diag_mask_host, uint32_t n1,
+                                   sealhip_lintrans_plan *plan, int32_t *baby_steps, int32_t *giant_steps, uint32_t *key_steps,
+                                   uint32_t capacity)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        const Engine &h = *ctx->engine;
+        const ltplan::Plan p = lintrans_make_plan(h, d, diag_mask_host, n1);
+        if ((baby_steps && capacity < p.baby.size()) || (giant_steps && capacity < p.giant.size()) ||
+            (key_steps && capacity < p.key_steps.size()))
+            throw std::invalid_argument("capacity is too small");
+        lintrans_plan_to_abi(h, p, plan);
+        if (baby_steps)
+            std::copy(p.baby.begin(), p.baby.end(), baby_steps);
+        if (giant_steps)
+            std::copy(p.giant.begin(), p.giant.end(), giant_steps);
+        if (key_steps)
+            std::copy(p.key_steps.begin(), p.key_steps.end(), key_steps);
+    });
+}
+
+long sealhip_linear_transform_diagonals(sealhip_context *ctx, const double *matrix_dev, uint32_t d, uint8_t *diag_mask_host)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(matrix_dev);
+    REQUIRE_PTR(diag_mask_host);
+    return guarded([&] {
+        check_lintrans_size(*ctx->engine, d);
+        check_aligned16(matrix_dev, "matrix_dev");
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("sealhip_linear_transform_diagonals synchronises: it cannot be captured");
+        if (!op_lintrans_occupancy(e, matrix_dev, d, diag_mask_host))
+            throw std::invalid_argument("the matrix has an entry that is not finite");
+    });
+}
+
+long sealhip_linear_transform_values(sealhip_context *ctx, const double *matrix_dev, uint32_t d, const uint8_t *diag_mask_host,
+                                     uint32_t n1, double gain, double *values_dev)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(matrix_dev);
+    REQUIRE_PTR(values_dev);
+    return guarded([&] {
+        const ltplan::Plan p = lintrans_make_plan(*ctx->engine, d, diag_mask_host, n1);
+        check_dft_gain(gain);
+        check_aligned16(matrix_dev, "matrix_dev");
+        check_aligned16(values_dev, "values_dev");
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("sealhip_linear_transform_values synchronises: it cannot be captured");
+        op_lintrans_values(e, p, matrix_dev, gain, values_dev);
+    });
+}
+
+long sealhip_linear_transform_values_host(const sealhip_context *ctx, const double *matrix_host, uint32_t d,
+                                          const uint8_t *diag_mask_host, uint32_t n1, double gain, double *values_host)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(matrix_host);
+    REQUIRE_PTR(values_host);
+    return guarded([&] {
+        const ltplan::Plan p = lintrans_make_plan(*ctx->engine, d, diag_mask_host, n1);
+        check_dft_gain(gain);
+        ltplan::values_host(p, matrix_host, gain, values_host);
+    });
+}
+
+long sealhip_linear_transform_create(sealhip_context *ctx, const double *matrix_dev, uint32_t d, uint32_t n1, double scale,
+                                     double gain, sealhip_linear_transform **tables)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(matrix_dev);
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        (void)lintrans_make_plan(*ctx->engine, d, nullptr, n1); // (d and n1, before the device is needed)
+        check_dft_gain(gain);
+        check_aligned16(matrix_dev, "matrix_dev");
+        Engine &e = device_engine(ctx);
+        *tables = create_tables_outside_capture<sealhip_linear_transform>(
+            e, "sealhip_linear_transform_create",
+            [&](sealhip_linear_transform &t) { t.tables = lintrans_create(e, matrix_dev, d, n1, scale, gain); });
+    });
+}
+
+long sealhip_linear_transform_destroy(sealhip_linear_transform *tables)
+{
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        lintrans_destroy(tables->tables); // (throws, and leaves the tables alone, during a graph capture)
+        delete tables;
+    });
+}
+
+long sealhip_linear_transform_tables_plan(const sealhip_linear_transform *tables, sealhip_lintrans_plan *plan, double *scale)
+{
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(plan);
+    return guarded([&] {
+        lintrans_plan_to_abi(*lintrans_engine(*tables->tables), lintrans_plan(*tables->tables), plan);
+        if (scale)
+            *scale = lintrans_scale(*tables->tables);
+    });
+}
+
+long sealhip_linear_transform_tables_steps(const sealhip_linear_transform *tables, int32_t *baby_steps, int32_t *giant_steps)
+{
+    REQUIRE_PTR(tables);
+    return guarded([&] {
+        const ltplan::Plan &p = lintrans_plan(*tables->tables);
+        if (baby_steps)
+            std::copy(p.baby.begin(), p.baby.end(), baby_steps);
+        if (giant_steps)
+            std::copy(p.giant.begin(), p.giant.end(), giant_steps);
+    });
+}
+
+long sealhip_linear_transform_tables_plain(const sealhip_linear_transform *tables, const uint64_t **plain_ntt)
+{
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(plain_ntt);
+    return guarded([&] { *plain_ntt = reinterpret_cast<const uint64_t *>(lintrans_plain(*tables->tables)); });
+}
+
+long sealhip_evaluator_linear_transform(sealhip_context *ctx, const sealhip_linear_transform *tables, uint32_t k,
+                                        const uint64_t *ct, size_t count, const uint32_t *galois_elts,
+                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, int32_t rescale,
+                                        uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tables);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    REQUIRE_GALOIS_LIST(n_keys);
+    const long same = guarded([&] { check_tables_context(ctx, lintrans_engine(*tables->tables), "linear-transform"); });
+    if (same != SEALHIP_S_OK)
+        return same;
+    // the BSGS entry with the tables' steps and plaintexts: its checks, its pipeline, its transparency flags
+    const ltplan::Plan &p = lintrans_plan(*tables->tables);
+    return rotate_vector_bsgs_plain_entry(ctx, rescale != 0, k, ct, count, p.baby.data(), static_cast<uint32_t>(p.baby.size()),
+                                          p.giant.data(), static_cast<uint32_t>(p.giant.size()), galois_elts, galois_keys, n_keys,
+                                          reinterpret_cast<const uint64_t *>(lintrans_plain(*tables->tables)), out);
 }
 
 /* ------------------------------------------------------------------ ModRaise and the double-angle step */

@@ -1222,8 +1222,35 @@ namespace sealhip
     // (count, chunk) entry in Lane::chunk_log, then body(off, m) for the m items from item `off` with the arena reset.
     void for_chunks(Engine &e, std::size_t count, std::size_t bytes_per_item, int n_buffers,
                     const std::function<void(std::size_t off, std::size_t m)> &body);
+    // The same division for an operation that walks its items itself: how many of `count` items the lane's arena cap holds
+    // at `bytes_per_item` (at least one), logged as (count, chunk) in Lane::chunk_log. Reserves nothing.
+    std::size_t arena_chunk_items(Engine &e, std::size_t count, std::size_t bytes_per_item);
     // rows 0..rows-1 of the key primes for each of `polys` polynomials of an item; `only` >= 0 keeps that polynomial
     RowMap ct_row_map(int rows, int polys, int only);
+
+    // ---- matrix-vector products from a caller's matrix (lintrans.hip, lintrans.cpp, lintrans_plan.hpp) ----
+    namespace ltplan
+    {
+        struct Plan;
+    }
+    // flags[c], c < d (device): bit 0 = diagonal c of the d x d complex matrix has a non-zero entry, bit 1 = a non-finite one
+    hipError_t launch_lintrans_occupancy(const Engine &e, const double *matrix, std::uint32_t d, std::uint8_t *flags);
+    // values: `cells` cells of N/2 complex doubles (device), the grid's cells cell0 .. cell0 + cells - 1 in [gi][bi] order;
+    // mask (d bytes), baby and giant (the plan's steps) in device memory
+    hipError_t launch_lintrans_values(const Engine &e, const double *matrix, std::uint32_t d, const std::uint8_t *mask,
+                                      const std::int32_t *baby, std::uint32_t n_baby, const std::int32_t *giant, std::size_t cell0,
+                                      std::size_t cells, double gain, double *values);
+    // occupied: d bytes on the host, 0 or 1; returns whether every entry is finite. Synchronises.
+    bool op_lintrans_occupancy(Engine &e, const double *matrix, std::uint32_t d, std::uint8_t *occupied);
+    // the whole grid, n_giant x n_baby x N/2 complex doubles (device). Stages the plan's steps from the host and synchronises.
+    void op_lintrans_values(Engine &e, const ltplan::Plan &p, const double *matrix, double gain, double *values);
+    struct LinearTransform; // the plan and plain_ntt[n_giant][n_baby][n_key][N] in device memory
+    LinearTransform *lintrans_create(Engine &e, const double *matrix, std::uint32_t d, std::uint32_t n1, double scale, double gain);
+    void lintrans_destroy(LinearTransform *t);
+    const Engine *lintrans_engine(const LinearTransform &t); // the context they were made on
+    const ltplan::Plan &lintrans_plan(const LinearTransform &t);
+    const u64 *lintrans_plain(const LinearTransform &t);
+    double lintrans_scale(const LinearTransform &t);
 
     std::unique_ptr<Engine> make_engine(int scheme, int logn, const u64 *key_moduli, int n_key, int nsp, u64 t,
                                         bool strict, int device);

@@ -129,6 +129,14 @@ namespace sealhip
         }
     }
 
+    std::size_t arena_chunk_items(Engine &e, std::size_t count, std::size_t bytes_per_item)
+    {
+        const std::size_t fit = workspace_budget_bytes(e) / (bytes_per_item ? bytes_per_item : 1);
+        const std::size_t chunk = std::max<std::size_t>(1, std::min(fit, count));
+        log_chunk(e, count, chunk);
+        return chunk;
+    }
+
     RowMap ct_row_map(int rows, int polys, int only)
     {
         if (rows * polys > kMaxRows)

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <complex>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -696,6 +697,78 @@ namespace sealhip_host
         }
     };
 
+    // The device tables of one d x d complex matrix (sealhip_linear_transform_create): the diagonals
+    // that hold a non-zero entry, found, pre-rotated and encoded at the key level on the device, at `scale`. The matrix is
+    // row-major, d a power of two <= N/2; it is read from device memory (16-byte aligned: a torch tensor's data_ptr()), or
+    // from a host vector that is staged through the pool for the making. Evaluator::linear_transform takes the object at
+    // any level; for a ciphertext whose slots are z the result's slots are
+    //     out[p] = sum_c u_c[p] z[(p + c) mod n],  u_c[p] = M[p mod d][(p + c) mod d]
+    // -- M z, tiled, when z is a d-vector tiled N/2d times. n1: the baby stride (0: the default); key_steps(): the rotation
+    // steps whose Galois keys the client must make.
+    class LinearTransform
+    {
+    public:
+        LinearTransform(const Context &c, const double *matrix_dev, std::size_t d, double scale, std::uint32_t n1 = 0,
+                        double gain = 1.0)
+        {
+            make(c, matrix_dev, d, scale, n1, gain);
+        }
+        LinearTransform(const Context &c, const std::vector<std::complex<double>> &matrix, std::size_t d, double scale,
+                        std::uint32_t n1 = 0, double gain = 1.0)
+        {
+            if (matrix.size() != d * d)
+                throw std::invalid_argument("matrix must hold d x d entries");
+            sealhip_lintrans_plan dense; // (d and n1 are refused before the staging needs a device)
+            throw_on(sealhip_linear_transform_plan(c.get(), std::uint32_t(d), nullptr, n1, &dense, nullptr, nullptr, nullptr, 0));
+            Staged m(c, 2 * d * d);
+            m.up(reinterpret_cast<const std::uint64_t *>(matrix.data()), 2 * d * d);
+            make(c, reinterpret_cast<const double *>(m.ptr()), d, scale, n1, gain);
+        }
+        ~LinearTransform()
+        {
+            if (tables_)
+                sealhip_linear_transform_destroy(tables_);
+        }
+        LinearTransform(const LinearTransform &) = delete;
+        LinearTransform &operator=(const LinearTransform &) = delete;
+        const sealhip_linear_transform *get() const { return tables_; }
+        const sealhip_lintrans_plan &plan() const { return plan_; }
+        double scale() const { return scale_; }
+        const std::vector<int> &baby_steps() const { return baby_; }
+        const std::vector<int> &giant_steps() const { return giant_; }
+        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
+        const std::uint64_t *plain_ntt() const // device: n_giant x n_baby x n_key x N words
+        {
+            const std::uint64_t *p = nullptr;
+            throw_on(sealhip_linear_transform_tables_plain(tables_, &p));
+            return p;
+        }
+
+    private:
+        void make(const Context &c, const double *matrix_dev, std::size_t d, double scale, std::uint32_t n1, double gain)
+        {
+            throw_on(sealhip_linear_transform_create(c.get(), matrix_dev, std::uint32_t(d), n1, scale, gain, &tables_));
+            throw_on(sealhip_linear_transform_tables_plan(tables_, &plan_, &scale_));
+            std::vector<std::int32_t> b(plan_.n_baby), g(plan_.n_giant);
+            throw_on(sealhip_linear_transform_tables_steps(tables_, b.data(), g.data()));
+            baby_.assign(b.begin(), b.end());
+            giant_.assign(g.begin(), g.end());
+            for (int s : baby_)
+                if (s)
+                    key_steps_.push_back(std::uint32_t(s));
+            for (int s : giant_)
+                if (s)
+                    key_steps_.push_back(std::uint32_t(s));
+            std::sort(key_steps_.begin(), key_steps_.end());
+            key_steps_.erase(std::unique(key_steps_.begin(), key_steps_.end()), key_steps_.end());
+        }
+        sealhip_linear_transform *tables_ = nullptr;
+        sealhip_lintrans_plan plan_{};
+        double scale_ = 0;
+        std::vector<int> baby_, giant_;
+        std::vector<std::uint32_t> key_steps_;
+    };
+
     template <class CT>
     class Evaluator
     {
@@ -1167,6 +1240,36 @@ namespace sealhip_host
             std::vector<C> one;
             scatter(encrypted_re, o, 1, out_words, one, dft.out_level());
             destination = std::move(one[0]);
+        }
+
+        // The matrix of `lt` applied to the slots of `encrypted` (sealhip_evaluator_linear_transform),
+        // at the operand's level; with rescale the result is one level down. The result's scale is encrypted.scale() *
+        // lt.scale(), divided by q_{k-1} with rescale. galois_keys: element -> key, with the keys of lt.key_steps(); a step
+        // whose key is absent throws std::invalid_argument("Galois key not present").
+        template <class C, IfCt<C> = 0>
+        void linear_transform(const C &encrypted, const LinearTransform &lt,
+                              const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination, bool rescale = false)
+        {
+            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
+                throw std::logic_error("unsupported scheme");
+            check_galois_operand(encrypted);
+            if (rescale)
+                check_rescale_operand(encrypted);
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            dft_keys(galois_keys, elts, raw);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n;
+            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
+            Dev c = dev_in(encrypted, words), o = dev_out(out_words);
+            Check chk = checked(encrypted, 1);
+            throw_on(sealhip_evaluator_linear_transform(ctx_.get(), lt.get(), std::uint32_t(k), c.ptr(), 1, elts.data(), raw.data(),
+                                                        std::uint32_t(elts.size()), rescale ? 1 : 0, o.ptr()));
+            chk.done();
+            const double in_scale = encrypted.scale(); // (the destination may be the operand)
+            std::vector<C> one;
+            scatter(encrypted, o, 1, out_words, one, k_out);
+            destination = std::move(one[0]);
+            destination.scale() = in_scale * lt.scale() / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
         }
 
     private:

@@ -86,6 +86,12 @@ class BootstrapPlan(C.Structure):
                 ("table_words", _u64), ("temp_bytes_per_item", _u64), ("evalmod", EvalModPlan)]
 
 
+class LintransPlan(C.Structure):
+    """sealhip_lintrans_plan (include/sealhip.h)"""
+    _fields_ = [("d", _u32), ("n_diagonals", _u32), ("n1", _u32), ("n_baby", _u32), ("n_giant", _u32), ("n_key_steps", _u32),
+                ("table_words", _u64), ("temp_bytes_per_item", _u64)]
+
+
 DFT_COEFFS_TO_SLOTS, DFT_SLOTS_TO_COEFFS = 0, 1
 
 SYMBOLS = {
@@ -209,6 +215,16 @@ SYMBOLS = {
     "sealhip_dft_tables_stage": [_vp, _u32, C.POINTER(_vp)],
     "sealhip_evaluator_coeffs_to_slots": [_vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _vp],
     "sealhip_evaluator_slots_to_coeffs": [_vp, _vp, _vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
+    "sealhip_linear_transform_plan": [_vp, _u32, _vp, _u32, _vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_u32), _u32],
+    "sealhip_linear_transform_diagonals": [_vp, _vp, _u32, _vp],
+    "sealhip_linear_transform_values": [_vp, _vp, _u32, _vp, _u32, C.c_double, _vp],
+    "sealhip_linear_transform_values_host": [_vp, _vp, _u32, _vp, _u32, C.c_double, _vp],
+    "sealhip_linear_transform_create": [_vp, _vp, _u32, _u32, C.c_double, C.c_double, C.POINTER(_vp)],
+    "sealhip_linear_transform_destroy": [_vp],
+    "sealhip_linear_transform_tables_plan": [_vp, _vp, C.POINTER(C.c_double)],
+    "sealhip_linear_transform_tables_steps": [_vp, C.POINTER(_i32), C.POINTER(_i32)],
+    "sealhip_linear_transform_tables_plain": [_vp, C.POINTER(_vp)],
+    "sealhip_evaluator_linear_transform": [_vp, _vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _i32, _vp],
     "sealhip_evaluator_mod_raise": [_vp, _u32, _vp, _sz, _u32, _vp],
     "sealhip_evaluator_double_angle": [_vp, _u32, _vp, _sz, C.c_double, C.POINTER(_vp), _u32, _vp, C.POINTER(C.c_double)],
     "sealhip_evalmod_coeffs": [_u32, _u32, _u32, C.POINTER(C.c_double)],
@@ -1343,6 +1359,58 @@ class Evaluator:
         _check(lib().sealhip_dft_stage_values(self.ctx.handle, *args, gain, stage, dev.ptr))
         return dev.download(out.size * 2).view(np.complex128).reshape(out.shape)
 
+    # ---- matrix-vector products from a caller's matrix
+    def linear_transform_plan(self, d, mask=None, n1=0):
+        """The plan of a d x d matrix-vector product (sealhip_linear_transform_plan); works on a host-only context. mask: d
+        flags, the diagonals in use, or None for all; n1: the baby stride, 0 for the default. Returns a dict: d,
+        n_diagonals, n1, n_baby, n_giant, table_words, temp_bytes_per_item, baby_steps, giant_steps and key_steps (the
+        sorted distinct non-zero rotation steps: the Galois keys to make)."""
+        m = _mask_bytes(mask, d)
+        plan = LintransPlan()
+        fn = lib().sealhip_linear_transform_plan
+        _check(fn(self.ctx.handle, d, _np_ptr(m), n1, C.addressof(plan), None, None, None, 0))
+        cap = max(1, plan.n_baby, plan.n_giant, plan.n_key_steps)
+        bs, gs, ks = (_i32 * cap)(), (_i32 * cap)(), (_u32 * cap)()
+        _check(fn(self.ctx.handle, d, _np_ptr(m), n1, C.addressof(plan), bs, gs, ks, cap))
+        out = _lintrans_plan_dict(plan)
+        out["baby_steps"], out["giant_steps"] = [int(v) for v in bs[:plan.n_baby]], [int(v) for v in gs[:plan.n_giant]]
+        out["key_steps"] = [int(v) for v in ks[:plan.n_key_steps]]
+        return out
+
+    def linear_transform_diagonals(self, matrix, d):
+        """The diagonals of a device matrix that hold a non-zero entry, as d flags (sealhip_linear_transform_diagonals: the
+        occupancy kernel); a non-finite entry raises ValueError. matrix: d x d complex doubles in device memory."""
+        out = np.zeros(d, dtype=np.uint8)
+        _check(lib().sealhip_linear_transform_diagonals(self.ctx.handle, _ptr(matrix), d, out.ctypes.data))
+        return out
+
+    def linear_transform_values(self, matrix, d, mask=None, n1=0, gain=1.0, host=False):
+        """The pre-rotated diagonals as a complex array [n_giant][n_baby][N/2] (sealhip_linear_transform_values: the gather
+        kernel over a device matrix, downloaded; host=True: matrix is a numpy array and sealhip_linear_transform_values_host
+        does the same on the host, also on a host-only context)."""
+        plan = self.linear_transform_plan(d, mask, n1)
+        m = _mask_bytes(mask, d)
+        out = np.zeros((plan["n_giant"], plan["n_baby"], self.ctx.n // 2), dtype=np.complex128)
+        if host:
+            mat = np.ascontiguousarray(matrix, dtype=np.complex128)
+            if mat.size != d * d:
+                raise ValueError("matrix is not d x d")
+            _check(lib().sealhip_linear_transform_values_host(self.ctx.handle, mat.ctypes.data, d, _np_ptr(m), n1, gain,
+                                                              out.ctypes.data))
+            return out
+        dev = self.ctx.alloc(out.size * 2)
+        _check(lib().sealhip_linear_transform_values(self.ctx.handle, _ptr(matrix), d, _np_ptr(m), n1, gain, dev.ptr))
+        return dev.download(out.size * 2).view(np.complex128).reshape(out.shape)
+
+    def linear_transform(self, tables, ct, k, count, galois_keys, out, rescale=False):
+        """out = the tables' matrix applied to the slots of ct (sealhip_evaluator_linear_transform): ct a device batch
+        count x 2 x k x N; out: count x 2 x k x N, or count x 2 x (k-1) x N with rescale. galois_keys: dict galois_elt ->
+        KSwitchKeys with the plan's key_steps; a missing one raises ValueError. The scale is multiplied by tables.scale
+        (and divided by q_(k-1) with rescale)."""
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_linear_transform(self.ctx.handle, tables.handle, k, _ptr(ct), count, ea, ka, n_keys,
+                                                        1 if rescale else 0, _ptr(out)))
+
     def coeffs_to_slots(self, tables, ct, count, galois_keys, out_re, out_im):
         """CoeffToSlot in one call (sealhip_evaluator_coeffs_to_slots): ct a device batch count x 2 x k x N at the tables'
         level; out_re, out_im: count x 2 x tables.out_level x N, slot j of them m_(bitrev j) and m_(bitrev j + N/2) over the
@@ -1710,6 +1778,49 @@ class DftTables(_Tables):
         _check(lib().sealhip_dft_tables_stage(self.handle, stage, C.byref(p)))
         return p.value
 
+
+def _mask_bytes(mask, d):
+    """the ABI's diag_mask_host: d bytes, or None for every diagonal"""
+    if mask is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.size != d:
+        raise ValueError("mask must have d entries")
+    return m
+
+
+def _np_ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def _lintrans_plan_dict(plan):
+    return {name: int(getattr(plan, name)) for name, _ in LintransPlan._fields_ if name != "n_key_steps"}
+
+
+class LinearTransform(_Tables):
+    """The device tables of one d x d matrix (sealhip_linear_transform_create): the diagonals that
+    hold a non-zero entry, found, pre-rotated and encoded at the key level on the device. matrix: d x d complex doubles in
+    device memory (a DeviceBuffer, a torch tensor or an address). plan: Evaluator.linear_transform_plan's dict for the
+    diagonals found; scale: of the plaintexts; plain_ptr(): the device address of the n_giant x n_baby x n_key x N words."""
+
+    _destroy = "sealhip_linear_transform_destroy"
+
+    def __init__(self, ctx, matrix, d, scale, n1=0, gain=1.0):
+        super().__init__(ctx)
+        _check(lib().sealhip_linear_transform_create(ctx.handle, _ptr(matrix), d, n1, scale, gain, C.byref(self.handle)))
+        plan, sc = LintransPlan(), C.c_double(0.0)
+        _check(lib().sealhip_linear_transform_tables_plan(self.handle, C.addressof(plan), C.byref(sc)))
+        self.plan, self.scale = _lintrans_plan_dict(plan), sc.value
+        bs, gs = (_i32 * max(1, plan.n_baby))(), (_i32 * max(1, plan.n_giant))()
+        _check(lib().sealhip_linear_transform_tables_steps(self.handle, bs, gs))
+        self.plan["baby_steps"] = [int(v) for v in bs[:plan.n_baby]]
+        self.plan["giant_steps"] = [int(v) for v in gs[:plan.n_giant]]
+        self.plan["key_steps"] = sorted({s for s in self.plan["baby_steps"] + self.plan["giant_steps"] if s})
+
+    def plain_ptr(self):
+        p = _vp()
+        _check(lib().sealhip_linear_transform_tables_plain(self.handle, C.byref(p)))
+        return p.value
 
 
 def _naf(value):

@@ -727,6 +727,86 @@ long sealhip_evaluator_slots_to_coeffs(sealhip_context *ctx, const sealhip_dft_t
                                        const uint64_t *ct_im, size_t count, const uint32_t *galois_elts,
                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
 
+/* Encrypted matrix-vector products from a caller's matrix: the diagonals found, pre-rotated, encoded
+   and laid out on the device for sealhip_evaluator_rotate_vector_bsgs_plain[_rescale]. CKKS only, both modes. The fork has no
+   such method; tests/lintrans_ref.py restates the scan, the plan and the values.
+   Notation: n = N/2 slots; d a power of two, 1 <= d <= n. M is a d x d complex matrix, row-major, M[i][j] at doubles
+   2 (i d + j) (re) and 2 (i d + j) + 1 (im), 16-byte aligned. Diagonal c in [0, d) is the slot vector
+       u_c[p] = M[p mod d][(p + c) mod d],   p < n,
+   and for a ciphertext whose slots are z the result's slots are
+       out[p] = sum_{c in D} u_c[p] * z[(p + c) mod n],
+   D the diagonals in use (for the tables: those holding a non-zero entry). The formula is the definition; for a d-periodic
+   z (a vector of d values tiled n/d times) it is M z, tiled.
+   The plan, given the baby stride n1 (a power of two <= d; 0 = the default): c = g + b with b = c mod n1, g = c - b; the baby
+   steps are the distinct b over D and the giant steps the distinct g, both ascending; cell [gi][bi] of the grid holds
+       values[gi][bi][p] = gain * u_(g+b)[(p - g) mod n],
+   zero when g + b is not in D. Step 0 on either axis is the identity and needs no key. The default n1 is the power of two
+   that minimises nb + 2 ng over the NON-ZERO baby and giant steps, ties to the larger n1 (dense d = 2^r, r >= 1:
+   2^ceil((r+1)/2), the homomorphic DFT's default).
+   diag_mask_host: d bytes on the host, non-zero = the diagonal is in D; NULL = every diagonal.
+   Checks of every entry, in this order: NULL pointers -> E_POINTER; then, also on host-only contexts, a BFV context, a d that
+   is no power of two in [1, n], an n1 that is neither 0 nor a power of two <= d, a mask without a diagonal, a gain that is
+   not finite or is zero, a matrix or values pointer that is not 16-byte aligned -> E_INVALIDARG; then a host-only context
+   -> COR_E_INVALIDOPERATION where the entry needs the device.
+
+   sealhip_linear_transform_plan: works on host-only contexts. baby_steps, giant_steps, key_steps may each be NULL (the plan
+   alone: n_baby, n_giant and n_key_steps say how many there are); what is given holds `capacity` entries, fewer than the
+   list needs -> E_INVALIDARG. key_steps: the sorted distinct non-zero steps of both axes, the Galois keys the client makes. */
+typedef struct sealhip_lintrans_plan
+{
+    uint32_t d, n_diagonals;      /* |D| */
+    uint32_t n1, n_baby, n_giant; /* the table is n_giant x n_baby x n_key x N words */
+    uint32_t n_key_steps;
+    uint64_t table_words;
+    uint64_t temp_bytes_per_item; /* pool bytes the tables hold per ciphertext of a transform: 0, its temporaries are the
+                                     BSGS pipeline's, in the calling thread's arena */
+} sealhip_lintrans_plan;
+typedef struct sealhip_linear_transform sealhip_linear_transform;
+long sealhip_linear_transform_plan(const sealhip_context *ctx, uint32_t d, const uint8_t *diag_mask_host, uint32_t n1,
+                                   sealhip_lintrans_plan *plan, int32_t *baby_steps, int32_t *giant_steps, uint32_t *key_steps,
+                                   uint32_t capacity);
+/* The occupancy scan alone: diag_mask_host[c] = 1 if diagonal c of the DEVICE matrix holds a non-zero entry, re or im
+   (-0.0 is zero), else 0; an entry that is not finite -> E_INVALIDARG (the mask is then unspecified). One kernel, one
+   workgroup per diagonal, then one copy of d bytes. Synchronises; not capturable. */
+long sealhip_linear_transform_diagonals(sealhip_context *ctx, const double *matrix_dev, uint32_t d, uint8_t *diag_mask_host);
+/* The generator alone: values = n_giant x n_baby x n complex doubles {re, im}, the grid above for the diagonals of
+   diag_mask_host; the products are re * gain and im * gain, two IEEE multiplies. sealhip_linear_transform_values reads a
+   DEVICE matrix and writes DEVICE memory with one gather kernel; it stages the plan's steps from the host and synchronises
+   (not capturable). _values_host reads and writes HOST memory with the same function, also on host-only contexts, and gives
+   the same bits. */
+long sealhip_linear_transform_values(sealhip_context *ctx, const double *matrix_dev, uint32_t d, const uint8_t *diag_mask_host,
+                                     uint32_t n1, double gain, double *values_dev);
+long sealhip_linear_transform_values_host(const sealhip_context *ctx, const double *matrix_host, uint32_t d,
+                                          const uint8_t *diag_mask_host, uint32_t n1, double gain, double *values_host);
+/* The tables of one matrix: the occupancy scan (a non-finite entry, or a matrix without a non-zero entry -- an empty sum
+   would be a transparent ciphertext -- -> E_INVALIDARG), the plan over the diagonals found, then the grid chunk by chunk:
+   as many cells as the calling thread's arena cap holds go values -> sealhip_ckks_encode at k = n_key and `scale`, into
+   plan.table_words words of device memory (out of memory -> E_OUTOFMEMORY, nothing is kept). The encoder's refusals pass
+   through ("scale out of bounds", "encoded values are too large"). Synchronises; not capturable. The plaintexts are at the
+   key level, so one object serves every ciphertext level. _tables_steps: n_baby and n_giant steps (either may be NULL);
+   _tables_plain: the device pointer that is valid as plain_ntt of sealhip_evaluator_rotate_vector_bsgs_plain[_rescale] with
+   those steps. Destroy the tables before their context, not while a call that reads them is in flight, and not during a
+   graph capture (COR_E_INVALIDOPERATION, the tables stay). */
+long sealhip_linear_transform_create(sealhip_context *ctx, const double *matrix_dev, uint32_t d, uint32_t n1, double scale,
+                                     double gain, sealhip_linear_transform **tables);
+long sealhip_linear_transform_destroy(sealhip_linear_transform *tables);
+long sealhip_linear_transform_tables_plan(const sealhip_linear_transform *tables, sealhip_lintrans_plan *plan, double *scale);
+long sealhip_linear_transform_tables_steps(const sealhip_linear_transform *tables, int32_t *baby_steps, int32_t *giant_steps);
+long sealhip_linear_transform_tables_plain(const sealhip_linear_transform *tables, const uint64_t **plain_ntt);
+/* The transform: ct is count x 2 x k x N in NTT form, not modified. rescale == 0: the words of
+   sealhip_evaluator_rotate_vector_bsgs_plain with the tables' steps and plaintexts, out: count x 2 x k x N; the result's
+   scale is the ciphertext's times the tables'. rescale != 0: the words of sealhip_evaluator_rotate_vector_bsgs_plain_rescale,
+   2 <= k, out: count x 2 x (k-1) x N, the scale divided by q_(k-1). galois_elts[i] is the Galois element of galois_keys[i].
+   Checks: NULL pointers -> E_POINTER; then, also on host-only contexts, tables made on another context, the BSGS entry's own
+   argument errors (k outside its levels, a step whose key is absent -- "Galois key not present" --, a key with fewer digits
+   than the level, out overlapping ct) -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only context
+   -> COR_E_INVALIDOPERATION. Nothing synchronises; capturable under the BSGS entry's conditions (after one call with the
+   same keys); transparency sink as the BSGS entry: one flag per output ciphertext. */
+long sealhip_evaluator_linear_transform(sealhip_context *ctx, const sealhip_linear_transform *tables, uint32_t k,
+                                        const uint64_t *ct, size_t count, const uint32_t *galois_elts,
+                                        const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, int32_t rescale,
+                                        uint64_t *out);
+
 /* Towards CKKS bootstrapping: ModRaise and the double-angle step of EvalMod. CKKS only, both modes.
    The fork has neither; tests/bootstrap_ref.py restates ModRaise over the oracle's transforms.
 
