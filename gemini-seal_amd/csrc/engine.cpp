@@ -116,13 +116,7 @@ namespace sealhip
             d.inv_n_shoup = tb.inv_n_shoup;
             d.inv_n_w = tb.inv_n_w;
             d.inv_n_w_shoup = tb.inv_n_w_shoup;
-            {
-                // -p^{-1} mod 2^64 by Newton iteration (p odd; the even "modulus" 2^32 never uses REDC)
-                u64 inv = tb.p;
-                for (int it = 0; it < 6; it++)
-                    inv *= 2 - tb.p * inv;
-                d.ninv = 0 - inv;
-            }
+            d.ninv = neg_inv_pow64(tb.p); // (p odd; the even "modulus" 2^32 never uses REDC)
             d.fwd = tb.fwd.empty() ? nullptr : upload<u64>(*e, e->owned, tb.fwd.data(), tb.fwd.size());
             d.inv = tb.inv.empty() ? nullptr : upload<u64>(*e, e->owned, tb.inv.data(), tb.inv.size());
             d.fwd_d = d.inv_d = nullptr;
@@ -483,8 +477,8 @@ namespace sealhip
             }
             rd.B_to_q = upload<u64>(*this, lt.owned, hr.B_to_q.matrix.data(), hr.B_to_q.matrix.size());
             rd.inv_prod_B_mod_msk = hr.inv_prod_B_mod_m_sk;
-            // folded constants of the fused kernels
-            std::vector<u64> L1(static_cast<std::size_t>(nB) * k), G2(static_cast<std::size_t>(nB) * k);
+            // folded constants of the fused kernels (RnsDev): L1, L2, G1, G2 stay here, the device gets their Montgomery forms
+            std::vector<u64> L1(static_cast<std::size_t>(nB) * k), G2(static_cast<std::size_t>(nB) * k), L2(nB), G1(nB);
             for (int j = 0; j < nB; j++)
             {
                 const u64 b = hr.Bsk[j];
@@ -492,8 +486,8 @@ namespace sealhip
                 u64 g = hr.inv_prod_q_mod_Bsk[j];
                 if (j < B)
                     g = mulmod(g, hr.B_to_q.inv_punct[j], b);
-                rd.lift_L2[j] = mulmod(hr.prod_q_mod_Bsk[j], inv_mt, b);
-                rd.floor_G1[j] = mulmod(t % b, g, b);
+                L2[j] = mulmod(hr.prod_q_mod_Bsk[j], inv_mt, b);
+                G1[j] = mulmod(t % b, g, b);
                 for (int i = 0; i < k; i++)
                 {
                     const u64 m = hr.q_to_Bsk.matrix[static_cast<std::size_t>(j) * k + i];
@@ -504,8 +498,6 @@ namespace sealhip
             }
             for (int i = 0; i < k; i++)
                 rd.floor_F0[i] = mulmod(t % hr.q[i], hr.q_to_Bsk.inv_punct[i], hr.q[i]);
-            rd.lift_L1 = upload<u64>(*this, lt.owned, L1.data(), L1.size());
-            rd.floor_G2 = upload<u64>(*this, lt.owned, G2.data(), G2.size());
             // Montgomery (x 2^64 mod prime) and Shoup companions
             auto mont = [](u64 c, u64 p) { return static_cast<u64>((static_cast<u128>(c) << 64) % p); };
             std::vector<u64> L1m(L1.size()), G2m(G2.size()), BQm(hr.B_to_q.matrix.size());
@@ -516,8 +508,8 @@ namespace sealhip
             {
                 const u64 b = hr.Bsk[j];
                 max_b = std::max(max_b, b);
-                rd.lift_L2m[j] = mont(rd.lift_L2[j], b);
-                rd.floor_G1m[j] = mont(rd.floor_G1[j], b);
+                rd.lift_L2m[j] = mont(L2[j], b);
+                rd.floor_G1m[j] = mont(G1[j], b);
                 for (int i = 0; i < k; i++)
                 {
                     L1m[static_cast<std::size_t>(j) * k + i] = mont(L1[static_cast<std::size_t>(j) * k + i], b);
@@ -531,20 +523,15 @@ namespace sealhip
                 const HostNttTables &tb = tables[n_key + (j < B ? 2 + j : 0)];
                 if (tb.p != b)
                     throw std::logic_error("internal: Bsk prime order");
-                rd.floor_G1m_top[0][j] = mont(mulmod(rd.floor_G1[j], tb.inv_n, b), b);
-                rd.floor_G1m_top[1][j] = mont(mulmod(rd.floor_G1[j], tb.inv_n_w, b), b);
+                rd.floor_G1m_top[0][j] = mont(mulmod(G1[j], tb.inv_n, b), b);
+                rd.floor_G1m_top[1][j] = mont(mulmod(G1[j], tb.inv_n_w, b), b);
                 rd.floor_G1m_top[2][j] = mont(rd.floor_G1m_top[0][j], b);
                 rd.floor_G1m_top[3][j] = mont(rd.floor_G1m_top[1][j], b);
                 rd.b_p[j] = b;
                 rd.b_w1[j] = tb.fwd.size() >= 4 ? tb.fwd[2] : 0; // pair 1 of the forward table: the top layer's twiddle
                 rd.b_w1s[j] = tb.fwd.size() >= 4 ? tb.fwd[3] : 0;
                 rd.b_rdp[j] = tb.rdp ? tb.rdp : shoup(1, b);
-                {
-                    u64 inv = b;
-                    for (int it = 0; it < 6; it++)
-                        inv *= 2 - b * inv;
-                    rd.b_ninv[j] = 0 - inv;
-                }
+                rd.b_ninv[j] = neg_inv_pow64(b);
             }
             for (int i = 0; i < k; i++)
             {
@@ -560,12 +547,7 @@ namespace sealhip
                 }
                 rd.q_p[i] = qi;
                 rd.q_rdp[i] = tables[i].rdp ? tables[i].rdp : shoup(1, qi);
-                {
-                    u64 inv = qi;
-                    for (int it = 0; it < 6; it++)
-                        inv *= 2 - qi * inv;
-                    rd.q_ninv[i] = 0 - inv;
-                }
+                rd.q_ninv[i] = neg_inv_pow64(qi);
                 rd.q_mt_inv_s[i] = shoup(rd.q_mt_inv[i], qi);
                 rd.floor_F0_s[i] = shoup(rd.floor_F0[i], qi);
                 rd.pBm[i] = mont(hr.prod_B_mod_q[i], qi);
@@ -586,36 +568,28 @@ namespace sealhip
             rd.dot_split = bounds::behz_select_split(k, max_q, max_b);
             {
                 const int split = rd.dot_split;
-                const auto pack = [split](u64 c) { return dot_pack(split, c); };
+                // one packed row {head.., body[0..n-1], p, ninv}: the heads and the body split, the prime's two words plain
+                const auto fill_row = [split](u64 *row, std::initializer_list<u64> head, const u64 *body, int n, u64 p, u64 ninv) {
+                    for (const u64 h : head)
+                        *row++ = dot_pack(split, h);
+                    for (int i = 0; i < n; i++)
+                        *row++ = dot_pack(split, body[i]);
+                    row[0] = p;
+                    row[1] = ninv;
+                };
                 const std::size_t ls = static_cast<std::size_t>(k) + 3, qs = static_cast<std::size_t>(B) + 4;
                 std::vector<u64> lrows(nB * ls), frows(5 * nB * ls), qrows(k * qs), first(5 * static_cast<std::size_t>(k) * 3);
                 for (int j = 0; j < nB; j++)
                 {
-                    u64 *lr = &lrows[j * ls];
-                    lr[0] = pack(rd.lift_L2m[j]);
-                    for (int i = 0; i < k; i++)
-                        lr[1 + i] = pack(L1m[static_cast<std::size_t>(j) * k + i]);
-                    lr[k + 1] = rd.b_p[j];
-                    lr[k + 2] = rd.b_ninv[j];
+                    fill_row(&lrows[j * ls], { rd.lift_L2m[j] }, &L1m[static_cast<std::size_t>(j) * k], k, rd.b_p[j], rd.b_ninv[j]);
                     for (int sel = 0; sel < 5; sel++)
-                    {
-                        u64 *fr = &frows[(static_cast<std::size_t>(sel) * nB + j) * ls];
-                        fr[0] = pack(sel < 4 ? rd.floor_G1m_top[sel][j] : rd.floor_G1m[j]);
-                        for (int i = 0; i < k; i++)
-                            fr[1 + i] = pack(G2m[static_cast<std::size_t>(j) * k + i]);
-                        fr[k + 1] = rd.b_p[j];
-                        fr[k + 2] = rd.b_ninv[j];
-                    }
+                        fill_row(&frows[(static_cast<std::size_t>(sel) * nB + j) * ls],
+                                 { sel < 4 ? rd.floor_G1m_top[sel][j] : rd.floor_G1m[j] }, &G2m[static_cast<std::size_t>(j) * k], k,
+                                 rd.b_p[j], rd.b_ninv[j]);
                 }
                 for (int i = 0; i < k; i++)
                 {
-                    u64 *qr = &qrows[i * qs];
-                    qr[0] = pack(rd.pBm[i]);
-                    qr[1] = pack(rd.nBm[i]);
-                    for (int j = 0; j < B; j++)
-                        qr[2 + j] = pack(BQm[static_cast<std::size_t>(i) * B + j]);
-                    qr[B + 2] = rd.q_p[i];
-                    qr[B + 3] = rd.q_ninv[i];
+                    fill_row(&qrows[i * qs], { rd.pBm[i], rd.nBm[i] }, &BQm[static_cast<std::size_t>(i) * B], B, rd.q_p[i], rd.q_ninv[i]);
                     for (int sel = 0; sel < 5; sel++)
                     {
                         u64 *f = &first[(static_cast<std::size_t>(sel) * k + i) * 3];
@@ -625,7 +599,7 @@ namespace sealhip
                     }
                 }
                 for (int j = 0; j < B; j++)
-                    rd.B_to_mskp[j] = pack(rd.B_to_mskm[j]);
+                    rd.B_to_mskp[j] = dot_pack(split, rd.B_to_mskm[j]);
                 rd.lift_rows = upload<u64>(*this, lt.owned, lrows.data(), lrows.size());
                 rd.floor_rows = upload<u64>(*this, lt.owned, frows.data(), frows.size());
                 rd.q_rows = upload<u64>(*this, lt.owned, qrows.data(), qrows.size());

@@ -111,6 +111,8 @@ namespace sealhip
     {
         int k, nB, B;               // |q|, |Bsk|, |B|
         u64 t;                      // plain modulus
+        // ---- read by the unit and k > 32 kernels: the reference's constants as they are (the fused lift of both families
+        // below reads q_mt_inv, q_to_mt and inv_prod_q_mod_mt too, their sign step inv_prod_B_mod_msk) ----
         // q -> Bsk U {m_tilde}
         u64 q_mt_inv[kMaxModuli];   // m_tilde * (q^_i)^{-1} mod q_i   (fused multiply_poly_scalar + inv_punctured)
         u64 q_inv[kMaxModuli];      // (q^_i)^{-1} mod q_i
@@ -126,13 +128,14 @@ namespace sealhip
         u64 inv_prod_B_mod_msk;
         u64 prod_B_mod_q[kMaxModuli];
         u64 inv_q_last_mod_q[kMaxModuli];
-        // constant-folded forms used by the fused BFV kernels (canonical results are unchanged):
-        //   lift : out_j = ( sum_i t_i*lift_L1[j][i] + temp_j*lift_L2[j] ) mod b_j
-        //   floor: tb_j  = ( in_j*floor_G1[j] + sum_i t_i*floor_G2[j][i] ) mod b_j,  t_i = in_i*floor_F0[i] mod q_i
-        const u64 *lift_L1;  // [nB][k]  M_ji * m_tilde^{-1} mod b_j
-        const u64 *floor_G2; // [nB][k]  -(M_ji * (prod q)^{-1} [* B^_j^{-1} for j < B]) mod b_j
-        u64 lift_L2[kMaxModuli + 2];  // prod_q * m_tilde^{-1} mod b_j
-        u64 floor_G1[kMaxModuli + 2]; // t * (prod q)^{-1} [* B^_j^{-1} for j < B] mod b_j
+        // ---- read by the run-time-k instance (k <= 32). Of these the exact-k instances read q_p, q_mt_inv_s, b_w1(s),
+        // inv_prod_B_mod_msk_s and the m_sk entries b_p[B], b_ninv[B]; everything else reaches them through the rows below ----
+        // constant-folded forms of the fused BFV kernels (canonical results are unchanged):
+        //   lift : out_j = ( sum_i t_i*L1[j][i] + temp_j*L2[j] ) mod b_j
+        //   floor: tb_j  = ( in_j*G1[j] + sum_i t_i*G2[j][i] ) mod b_j,  t_i = in_i*floor_F0[i] mod q_i
+        //   L1[j][i] = M_ji * m_tilde^{-1},  L2[j] = prod_q * m_tilde^{-1},  G1[j] = t * g_j,  G2[j][i] = -(M_ji * g_j)  (mod b_j)
+        //   with g_j = (prod q)^{-1} [* B^_j^{-1} for j < B]. Engine::level forms them; the device holds their
+        //   Montgomery forms only (suffix m: times 2^64 mod the row's prime; s: the Shoup quotient)
         u64 floor_F0[kMaxModuli];     // t * (q^_i)^{-1} mod q_i
         // the same constants with the deferred top inverse-NTT layer's factor folded in (index 0: lower half of a row,
         // n^{-1}; index 1: upper half, w * n^{-1}; ntt.cpp:393-402), so the fused floor kernel multiplies once, not twice
@@ -147,21 +150,21 @@ namespace sealhip
         u64 q_p[kMaxModuli], q_ninv[kMaxModuli], q_rdp[kMaxModuli];
         u64 b_p[kMaxModuli + 2], b_ninv[kMaxModuli + 2], b_rdp[kMaxModuli + 2];
         u64 b_w1[kMaxModuli + 2], b_w1s[kMaxModuli + 2]; // top-layer forward twiddle of the Bsk rows and its Shoup quotient
-        // Montgomery/Shoup companions of the folded constants (suffix m: times 2^64 mod the row's prime; s: Shoup)
+        // Montgomery/Shoup companions of the folded constants and of the B -> q, B -> m_sk constants above
         const u64 *lift_L1m, *floor_G2m, *B_to_qm; // [nB][k], [nB][k], [k][B]
         u64 lift_L2m[kMaxModuli + 2], floor_G1m[kMaxModuli + 2];
         u64 q_mt_inv_s[kMaxModuli], floor_F0_s[kMaxModuli];
         u64 B_to_mskm[kMaxModuli + 1];
         u64 inv_prod_B_mod_msk_s;
         u64 pBm[kMaxModuli], nBm[kMaxModuli]; // prod_B_mod_q * 2^64, (q - prod_B_mod_q) * 2^64  (mod q_i)
-        // the same constants as the exact-k instances read them: one contiguous row per dot product, every constant split
-        // at dot_split (dotacc.hpp dot_pack), followed by the row's prime p and -p^-1 mod 2^64 (not packed)
+        // ---- read by the exact-k instances: the same constants, one contiguous row per dot product, every constant split
+        // at dot_split (dotacc.hpp dot_pack), followed by the row's prime p and -p^-1 mod 2^64 (not packed) ----
         const u64 *lift_rows;   // [nB][k + 3]     {lift_L2m[j], lift_L1m[j][0..k-1], p, ninv}
         const u64 *floor_rows;  // [5][nB][k + 3]  {G1[j], floor_G2m[j][0..k-1], p, ninv}; G1 = floor_G1m_top[sel] (sel < 4), floor_G1m (4)
         const u64 *q_rows;      // [k][B + 4]      {pBm[i], nBm[i], B_to_qm[i][0..B-1], p, ninv}
         const u64 *floor_first; // [5][k][3]       {F0, its Shoup quotient, q_i}: floor_F0_top(_s)[sel] (sel < 4), floor_F0(_s) (4); plain
         u64 B_to_mskp[kMaxModuli + 1];
-        // decrypt_scale_and_round (rns.cpp:1070-1126), constants folded where the results are canonical anyway:
+        // ---- read by decrypt_scale_and_round (rns.cpp:1070-1126) ---- constants folded where the results are canonical anyway:
         //   y_i = in_i * dsr_scale[i] mod q_i  (|gamma t|_qi times (q^_i)^{-1});  {t, gamma} part = sum_i y_i * dsr_to_t/g[i]
         u64 dsr_scale[kMaxModuli], dsr_scale_s[kMaxModuli], dsr_to_t[kMaxModuli], dsr_to_g[kMaxModuli];
         u64 dsr_neg_inv_q_t, dsr_neg_inv_q_g, dsr_inv_gamma_t, dsr_gamma;

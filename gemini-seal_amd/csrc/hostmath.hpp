@@ -36,6 +36,14 @@ namespace sealhip
     {
         return static_cast<u64>((static_cast<u128>(x) << 64) / p);
     }
+    // -p^{-1} mod 2^64 by Newton iteration, p odd (the constant of the Montgomery reductions)
+    inline u64 neg_inv_pow64(u64 p)
+    {
+        u64 inv = p;
+        for (int it = 0; it < 6; it++)
+            inv *= 2 - p * inv;
+        return 0 - inv;
+    }
     bool is_prime_u64(u64 n);
     // largest-first primes = 1 (mod 2*ntt_size) below 2^bit_size (numth.cpp:277-323)
     std::vector<u64> get_primes(std::size_t ntt_size, int bit_size, std::size_t count);

@@ -21,7 +21,7 @@ namespace sealhip
     constexpr int kNttSmallQuot = 0x1000000;     // (launcher-internal) canonical approximate-quotient launch: single-precision quotient estimate in the store
     constexpr int kNttDebugNoSignal = 0x40; // forward half kernel: never send the hand-off signal (tests of the time-out path)
     // forward, single-pass kernel, with kNttReduceOut, in place: the producer of the rows has already applied the top layer
-    // (gap N/2) -- bfv_lift2 does for the Bsk rows it writes. Each workgroup then loads its own half only: no second read of
+    // (gap N/2) -- bfv_lift_exact does for the Bsk rows it writes. Each workgroup then loads its own half only: no second read of
     // the row, no duplicated products (both workgroups of a row compute the top layer's products otherwise), no hand-off.
     constexpr int kNttTopDone = 0x80;
     constexpr int kNttDeferTop = 4;  // inverse, single-pass kernels only: leave the top layer (gap N/2) to the consumer

@@ -888,7 +888,7 @@ namespace sealhip
                 const QBskMaps maps = split_q_bsk(lt.map_qbsk, k, dest);
                 check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, maps.q, kNttDeferTop | kNttAnyRep, sq),
                       "intt(tensor, q rows)");
-                // (round 4: the Bsk rows may store any representative below 2p as well -- bfv_floor_sk2 takes u, v below 2p and
+                // (round 4: the Bsk rows may store any representative below 2p as well -- the fused floor (bfv_floor_sk_exact / _guarded) takes u, v below 2p and
                 //  canonicalises; the launcher then runs the DENSE lazy schedule on the 60-bit primes, ntt_bounds.hpp section 1)
                 check(launch_intt_tensor(e, D, X, w_x, poly_x, kb, m * dest * kb, maps.bsk, kNttDeferTop | kNttAnyRep, sq),
                       "intt(tensor, Bsk rows)");

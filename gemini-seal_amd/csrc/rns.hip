@@ -106,10 +106,18 @@ namespace sealhip
             pout[nB * N] = acc & 0xFFFFFFFFull;
         }
 
+        // centred reduction of r_m_tilde modulo the row's prime p (rns.cpp:969-973)
+        __device__ __forceinline__ u64 centred_r_m_tilde(u64 r_mt, u64 p)
+        {
+            u64 temp = r_mt;
+            if (temp >= (1ull << 31))
+                temp += p - (1ull << 32);
+            return temp;
+        }
         // sm_mrq (rns.cpp:925-981)
         __device__ __forceinline__ u64 sm_mrq_one(u64 in_b, u64 r_mt, const RnsDev *d, int j, const PrimeDev &Bp)
         {
-            u64 temp = r_mt;
+            u64 temp = r_mt; // (centred_r_m_tilde: the unit kernel keeps the statement, which the compiler lays out otherwise)
             if (temp >= (1ull << 31))
                 temp += Bp.p - (1ull << 32);
             return mul_mod(mul_add_mod(d->prod_q_mod_Bsk[j], temp, in_b, Bp.p, Bp.cr0, Bp.cr1), d->inv_mt_mod_Bsk[j],
@@ -140,8 +148,7 @@ namespace sealhip
                 pout[j * N] = sm_mrq_one(pin[j * N], r_mt, d, j, primes[d->bsk_prime[j]]);
         }
 
-        // fused fastbconv_m_tilde + sm_mrq (evaluator.cpp:345-348): k rows -> |Bsk| rows
-        template <int KMAX>
+        // fused fastbconv_m_tilde + sm_mrq (evaluator.cpp:345-348): k rows -> |Bsk| rows. The step-by-step form, for k > 32
         __global__ __launch_bounds__(kThreads) void bfv_lift_kernel(const RnsDev *__restrict__ d,
                                                                     const PrimeDev *__restrict__ primes,
                                                                     const u64 *__restrict__ in, std::size_t in_stride,
@@ -155,10 +162,10 @@ namespace sealhip
             const std::size_t N = static_cast<std::size_t>(1) << logn;
             const u64 *pin = in + cc.item * in_stride + cc.c;
             u64 *pout = out + cc.item * out_stride + cc.c;
-            u64 t[KMAX];
+            u64 t[kMaxModuli];
             u64 acc = 0;
 #pragma unroll
-            for (int i = 0; i < KMAX; i++)
+            for (int i = 0; i < kMaxModuli; i++)
                 if (i < k)
                 {
                     const PrimeDev &Q = primes[d->q_prime[i]];
@@ -169,7 +176,7 @@ namespace sealhip
             for (int j = 0; j < nB; j++)
             {
                 const PrimeDev &Bp = primes[d->bsk_prime[j]];
-                const u64 conv = dot_mod<KMAX>(t, k, d->q_to_Bsk + j * k, Bp);
+                const u64 conv = dot_mod<kMaxModuli>(t, k, d->q_to_Bsk + j * k, Bp);
                 pout[j * N] = sm_mrq_one(conv, r_mt, d, j, Bp);
             }
         }
@@ -178,103 +185,114 @@ namespace sealhip
         //   conv_j = sum_i t_i M_ji mod b;  u = (prod_q*temp + conv_j) mod b;  out = u * m_tilde^{-1} mod b
         // (rns.cpp:1062-1067 + :960-980) is a composition of exact modular operations, so it equals
         //   out = ( sum_i t_i*(M_ji*m_tilde^{-1}) + temp*(prod_q*m_tilde^{-1}) ) mod b
-        // with ONE 128-bit accumulation and ONE Barrett reduction per output instead of three.
-        // KMAX < 0 means "exactly K = -KMAX primes, known at compile time" (no per-iteration guards, constants
-        // fetched with wide scalar loads); KMAX > 0 is the guarded form for any k <= KMAX
-        // TOP (exact-K instances): one lane per column PAIR (c, c + N/2); after a row's two outputs are formed the lane
+        // with ONE 128-bit accumulation and ONE reduction per output instead of three. The constants carry the factor 2^64,
+        // which the Montgomery reduction removes. Two families of kernels compute it (and the fused floor below):
+        //   exact k     K = 1 .. bounds::kBehzExactMaxK primes, known at compile time, launched only where the host proved
+        //               that every REDC lands below 2p (RnsDev::redc_small): no guards and no branches in the row loops, the
+        //               constants of a dot product are one packed row (wide scalar loads), the dot products are carry-free
+        //               (dotacc.hpp) at the split S the host selected for the level (RnsDev::dot_split)
+        //   run-time k  any k <= kBehzGeneric: guarded loops, the constants in separate arrays, 128-bit multiply-accumulate
+
+        // Exact k, the floor's three dot products (the lift's row writes the same steps out, see there):
+        // (head * chead +) sum_i v[i] * c[i] mod p, canonical. c is packed (dot_pack<S>); `last` says whether the
+        // last of K + 1 values takes part (the optional extra prime of B); K values all do. KIND names the dot product's
+        // operand classes (bounds::behz_dot_shape); kind 2, the m_sk row, has no head term.
+        // The values' constants start at c[C0]. p and ninv (and rdp below) come as pointers, read after the products: a
+        // caller that has the word passes its local's address, one that has not passes the table's.
+        template <int KIND, int K, int C0, int S, int NV, class CP, class PP, class NP>
+        __device__ __forceinline__ u64 dot_redc_exact(const Split<S> &head, u64 chead, const Split<S> (&v)[NV], bool last,
+                                                      CP c, PP p, NP ninv)
+        {
+            constexpr int H = KIND == 2 ? 0 : 1;
+            u64 lo, hi;
+            BehzDot<S, KIND, K> acc; // carry-free accumulation (dotacc.hpp), same integer sum
+            if constexpr (H != 0)
+                acc.template add<0>(head, chead);
+            static_for<NV>([&](auto I) {
+                if (I.value < K || last)
+                    acc.template add<I.value + H>(v[I.value], c[I.value + C0]);
+            });
+            acc.finish(lo, hi);
+            const u64 pv = *p;
+            return redc_canonical_hs(lo, hi, pv, *ninv);
+        }
+        // Run-time k: head * chead + sum_{i < n} v[i] * row[i] mod p, canonical (`small`: the REDC lands below 2p)
+        template <int NV, class CP, class PP, class NP, class RP>
+        __device__ __forceinline__ u64 dot_redc_guarded(u64 head, u64 chead, const u64 (&v)[NV], CP row, int n, PP p,
+                                                        NP ninv, RP rdp, bool small)
+        {
+            u64 lo = head * chead, hi = mulhi(head, chead);
+#pragma unroll
+            for (int i = 0; i < NV; i++)
+                if (i < n)
+                    mac128(lo, hi, v[i], row[i]);
+            const u64 pv = *p;
+            return redc_finish(redc128(lo, hi, pv, *ninv), pv, *rdp, small);
+        }
+
+        // The lift at an exact K.
+        // TOP: one lane per column PAIR (c, c + N/2); after a row's two outputs are formed the lane
         // applies the forward NTT's top layer to them (ForwardLazy, ntt.cpp:245-252, the very function the NTT kernel's load
         // phase would run on these two words) and stores the results. The transform that follows is launched with
         // kNttTopDone: its workgroups then read their own half only, and the layer's products are computed once per pair
         // instead of once per workgroup.
-        // S (exact-K instances): the split position of the carry-free dot products (dotacc.hpp), selected per level by the
-        // host (RnsDev::dot_split); the row tables are packed with it
-        template <int KMAX, bool TOP = false, int S = 31>
-        __global__ __launch_bounds__(kThreads) void bfv_lift2_kernel(const RnsDev *__restrict__ d_,
-                                                                     const PrimeDev *__restrict__ primes_,
-                                                                     const u64 *__restrict__ in, std::size_t in_stride,
-                                                                     u64 *__restrict__ out, std::size_t out_stride,
-                                                                     std::size_t count, int logn)
+        template <int K, bool TOP, int S>
+        __global__ __launch_bounds__(kThreads) void bfv_lift_exact_kernel(const RnsDev *__restrict__ d_,
+                                                                          const PrimeDev *__restrict__, // (RnsDev has the rows' primes)
+                                                                          const u64 *__restrict__ in, std::size_t in_stride,
+                                                                          u64 *__restrict__ out, std::size_t out_stride,
+                                                                          std::size_t count, int logn)
         {
-            static_assert(!TOP || KMAX < 0, "the paired-column form exists for the exact-K instances");
             Cols cc;
             if (!column(count, TOP ? logn - 1 : logn, cc))
                 return;
-            constexpr int KA = KMAX < 0 ? -KMAX : KMAX; // array extent
-            constexpr int NC = TOP ? 2 : 1;             // columns per lane
-            const auto *d = kc(d_);           // read-only for the lifetime of the context: constant address space
-            const auto *primes = kc(primes_); // (scalar loads the compiler may merge and hoist)
-            const int k = KMAX < 0 ? KA : d->k, nB = d->nB;
+            constexpr int NC = TOP ? 2 : 1; // columns per lane
+            const auto *d = kc(d_);         // read-only for the lifetime of the context: constant address space
+            const int nB = d->nB;
             const std::size_t N = static_cast<std::size_t>(1) << logn;
             const u64 *pin = in + cc.item * in_stride + cc.c;
             u64 *pout = out + cc.item * out_stride + cc.c;
-            u64 t[NC][KA];
+            u64 t[NC][K];
             u64 acc[NC] = {};
-            (void)primes;
 #pragma unroll
-            for (int i = 0; i < KA; i++)
-                if (KMAX < 0 || i < k)
+            for (int i = 0; i < K; i++)
+            {
+                const u64 qp = d->q_p[i];
+#pragma unroll
+                for (int h = 0; h < NC; h++)
                 {
-                    const u64 qp = d->q_p[i];
-#pragma unroll
-                    for (int h = 0; h < NC; h++)
-                    {
-                        t[h][i] = mulmod_shoup_hs(pin[i * N + h * (N >> 1)], d->q_mt_inv[i], d->q_mt_inv_s[i], qp); // exact canonical product
-                        acc[h] += t[h][i] * d->q_to_mt[i];
-                    }
+                    t[h][i] = mulmod_shoup_hs(pin[i * N + h * (N >> 1)], d->q_mt_inv[i], d->q_mt_inv_s[i], qp); // exact canonical product
+                    acc[h] += t[h][i] * d->q_to_mt[i];
                 }
+            }
             u64 r_mt[NC];
 #pragma unroll
             for (int h = 0; h < NC; h++)
                 r_mt[h] = r_m_tilde(acc[h] & 0xFFFFFFFFull, d);
-            // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
-            // a compile-time fact there, so the row loops carry no branch
-            const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            Split<S> ts[NC][KA];
-            if constexpr (KMAX < 0)
-                static_for<KA>([&](auto I) {
+            Split<S> ts[NC][K];
+            static_for<K>([&](auto I) {
 #pragma unroll
-                    for (int h = 0; h < NC; h++)
-                        ts[h][I.value] = Split<S>(t[h][I.value]);
-                });
-            const auto *L1m = kc(d->lift_L1m);
-            const auto *L2m = kc(d->lift_L2m);
+                for (int h = 0; h < NC; h++)
+                    ts[h][I.value] = Split<S>(t[h][I.value]);
+            });
             const auto *Lrows = kc(d->lift_rows);
             const auto row_out = [&](int j) {
-                // constants carry the factor 2^64: REDC removes it. Exact K: the row {L2, L1[0..K-1], p, -p^-1}, split for
-                // the dot product, is one contiguous run of scalar loads
-                auto *row = KMAX < 0 ? Lrows + j * (KA + 3) : L1m + j * k;
-                if constexpr (KMAX < 0)
-                    row = row_window(row);
-                const u64 bp = KMAX < 0 ? row[KA + 1] : d->b_p[j];
-                const u64 ninv = KMAX < 0 ? row[KA + 2] : d->b_ninv[j];
+                // the row {L2, L1[0..K-1], p, -p^-1}, split for the dot product, is one contiguous run of scalar loads
+                const auto *row = row_window(Lrows + j * (K + 3));
+                const u64 bp = row[K + 1];
+                const u64 ninv = row[K + 2];
                 u64 v[NC];
 #pragma unroll
                 for (int h = 0; h < NC; h++)
                 {
-                    u64 temp = r_mt[h];
-                    if (temp >= (1ull << 31))
-                        temp += bp - (1ull << 32); // centred reduction of r_m_tilde, rns.cpp:969-973
+                    // (dot_redc_exact<0, K, 1> written out: inside this column loop the call leaves the one-column instances
+                    //  another schedule, with scalar registers spilled to vector lanes at K = 15)
                     u64 lo, hi;
-                    if constexpr (KMAX < 0)
-                    {
-                        BehzDot<S, 0, KA> acc2; // carry-free accumulation (dotacc.hpp), same integer sum
-                        acc2.template add<0>(Split<S>(temp), row[0]);
-                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[h][I.value], row[I.value + 1]); });
-                        acc2.finish(lo, hi);
-                    }
-                    else
-                    {
-                        lo = temp * L2m[j];
-                        hi = mulhi(temp, L2m[j]);
-#pragma unroll
-                        for (int i = 0; i < KA; i++)
-                            if (i < k)
-                                mac128(lo, hi, t[h][i], row[i]);
-                    }
-                    if constexpr (KMAX < 0)
-                        v[h] = redc_canonical_hs(lo, hi, bp, ninv);
-                    else
-                        v[h] = redc_finish(redc128(lo, hi, bp, ninv), bp, d->b_rdp[j], small);
+                    BehzDot<S, 0, K> acc2; // carry-free accumulation (dotacc.hpp), same integer sum
+                    acc2.template add<0>(Split<S>(centred_r_m_tilde(r_mt[h], bp)), row[0]);
+                    static_for<K>([&](auto I) { acc2.template add<I.value + 1>(ts[h][I.value], row[I.value + 1]); });
+                    acc2.finish(lo, hi);
+                    v[h] = redc_canonical_hs(lo, hi, bp, ninv);
                 }
                 if constexpr (TOP)
                 {
@@ -283,41 +301,55 @@ namespace sealhip
                 }
                 pout[j * N] = v[0];
             };
-            if constexpr (KMAX < 0)
+            // |Bsk| is k + 1 or k + 2 (rns.cpp:568-573): with an exact K only the last row is a run-time question, the
+            // others are straight-line code whose scalar loads overlap the neighbouring rows' arithmetic
+            static_for<K + 1>([&](auto J) { row_out(J.value); });
+            if (nB == K + 2)
+                row_out(K + 1);
+        }
+
+        // The lift at a run-time k <= kBehzGeneric
+        __global__ __launch_bounds__(kThreads) void bfv_lift_guarded_kernel(const RnsDev *__restrict__ d_,
+                                                                            const PrimeDev *__restrict__, // (RnsDev has the rows' primes)
+                                                                            const u64 *__restrict__ in, std::size_t in_stride,
+                                                                            u64 *__restrict__ out, std::size_t out_stride,
+                                                                            std::size_t count, int logn)
+        {
+            Cols cc;
+            if (!column(count, logn, cc))
+                return;
+            const auto *d = kc(d_); // read-only for the lifetime of the context: constant address space
+            const int k = d->k, nB = d->nB;
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const u64 *pin = in + cc.item * in_stride + cc.c;
+            u64 *pout = out + cc.item * out_stride + cc.c;
+            u64 t[kBehzGeneric];
+            u64 acc = 0;
+#pragma unroll
+            for (int i = 0; i < kBehzGeneric; i++)
+                if (i < k)
+                {
+                    t[i] = mulmod_shoup_hs(pin[i * N], d->q_mt_inv[i], d->q_mt_inv_s[i], d->q_p[i]); // exact canonical product
+                    acc += t[i] * d->q_to_mt[i];
+                }
+            const u64 r_mt = r_m_tilde(acc & 0xFFFFFFFFull, d);
+            const bool small = d->redc_small != 0;
+            const auto *L1m = kc(d->lift_L1m);
+            const auto *L2m = kc(d->lift_L2m);
+            for (int j = 0; j < nB; j++)
             {
-                // |Bsk| is k + 1 or k + 2 (rns.cpp:568-573): with an exact K only the last row is a run-time question, the
-                // others are straight-line code whose scalar loads overlap the neighbouring rows' arithmetic
-                static_for<KA + 1>([&](auto J) { row_out(J.value); });
-                if (nB == KA + 2)
-                    row_out(KA + 1);
+                const u64 bp = d->b_p[j];
+                const u64 ninv = d->b_ninv[j];
+                pout[j * N] = dot_redc_guarded(centred_r_m_tilde(r_mt, bp), L2m[j], t, L1m + j * k, k, &bp, &ninv, &d->b_rdp[j], small);
             }
-            else
-                for (int j = 0; j < nB; j++)
-                    row_out(j);
         }
 
         // Constant-folded variant of bfv_floor_sk_kernel (k <= 32); see RnsDev for the folded constants.
         // Every output is the same canonical residue as the step-by-step version: only exact modular
         // identities are used ((b - c)*g == -c*g, (x*t)*g == x*(t*g), mul_add_mod(a,b,c) == a*b + c (mod q)).
-        // One coefficient of an inverse-NTT output whose top layer was deferred (kNttDeferTop): apply
-        // BackwardLazyLast (ntt.cpp:274-281) to the pair (c mod N/2, c mod N/2 + N/2) and the canonicalising
-        // subtraction of ntt.h:328-333, keeping only this lane's side of the butterfly.
-        template <class PP>
-        __device__ __forceinline__ u64 after_top(u64 u, u64 v, bool is_hi, PP P)
-        {
-            const u64 p = P->p, two_p = P->two_p, neg_p = 0 - p;
-            u64 r;
-            if (is_hi)
-                r = mulmod_lazy_hs<true>(u - v + two_p, P->inv_n_w, P->inv_n_w_shoup, neg_p);
-            else
-            {
-                u64 tt = u + v;
-                tt = tt >= two_p ? tt - two_p : tt;
-                r = mulmod_lazy_hs<true>(tt, P->inv_n, P->inv_n_shoup, neg_p);
-            }
-            return r >= p ? r - p : r;
-        }
-        // The same pair without the multiplication: its constant (n^{-1} or w * n^{-1}) is folded into the constant the
+        // One coefficient of an inverse-NTT output whose top layer was deferred (kNttDeferTop): BackwardLazyLast
+        // (ntt.cpp:274-281) on the pair (c mod N/2, c mod N/2 + N/2), this lane's side of the butterfly only, without the
+        // multiplication: its constant (n^{-1} or w * n^{-1}) is folded into the constant the
         // value is multiplied with next (RnsDev::floor_F0_top / floor_G1m_top). REDUCE brings the value below 2p (operands
         // of the carry-free dot products must stay below 2^61); a Shoup product takes it as it is.
         template <bool REDUCE>
@@ -329,45 +361,169 @@ namespace sealhip
                 r = r >= two_p ? r - two_p : r;
             return r;
         }
-        template <int KMAX, bool DEFER, int S = 31>
-        __global__ __launch_bounds__(kThreads) void bfv_floor_sk2_kernel(const RnsDev *__restrict__ d_,
-                                                                         const PrimeDev *__restrict__ primes_,
-                                                                         const u64 *__restrict__ in,
-                                                                         std::size_t in_stride, u64 *__restrict__ out,
-                                                                         std::size_t out_stride, std::size_t count,
-                                                                         int logn, int mont, unsigned *__restrict__ tflags)
+        // The column of this lane where the inverse NTT's top layer was deferred; is_hi: it lies in the upper half of its row.
+        // The lanes of columns c and c + N/2 read the same 2(k + |Bsk| + 1) words. Blocks
+        // are dealt round-robin over the 8 XCDs (one L2 each): physical blocks b and b + 8 run on the same XCD at
+        // about the same time, so they are given the lower and the upper half of the same 256 columns and the second
+        // read comes from L2 instead of HBM (the halves used to be half a grid apart: 37 row passes instead of 22).
+        // logn >= 14 here: the blocks of an item are a multiple of 16. Everything is derived from the block index, so
+        // the compiler knows is_hi is uniform and reads the tables selected by it with scalar loads.
+        __device__ __forceinline__ bool deferred_column(std::size_t count, std::size_t N, Cols &cc, bool &is_hi)
         {
-            constexpr int KA = KMAX < 0 ? -KMAX : KMAX;
+            const std::size_t per_item = N / kThreads, bid = blockIdx.x;
+            cc.item = bid / per_item;
+            if (cc.item >= count)
+                return false;
+            const unsigned pl = static_cast<unsigned>(bid - cc.item * per_item), r = pl & 15u;
+            is_hi = (r >> 3) != 0;
+            cc.c = (is_hi ? N >> 1 : 0) + static_cast<std::size_t>(((pl >> 4) << 3) | (r & 7u)) * kThreads + threadIdx.x;
+            return true;
+        }
+        // The Shenoy-Kumaresan correction's sign and magnitude (rns.cpp:898-909) from the two m_sk words
+        struct SkAlpha
+        {
+            bool neg;
+            u64 a2;
+        };
+        template <class DP>
+        __device__ __forceinline__ SkAlpha sk_alpha(u64 diff, u64 mp, DP d) // diff = conv_sk - fl_sk, kept positive
+        {
+            const u64 alpha = mulmod_shoup(diff, d->inv_prod_B_mod_msk, d->inv_prod_B_mod_msk_s, mp);
+            const bool neg = alpha > (mp >> 1); // rns.cpp:909
+            return { neg, neg ? mp - alpha : alpha };
+        }
+
+        // The floor at an exact K
+        template <int K, bool DEFER, int S>
+        __global__ __launch_bounds__(kThreads) void bfv_floor_sk_exact_kernel(const RnsDev *__restrict__ d_,
+                                                                              const PrimeDev *__restrict__, // (RnsDev has the rows' primes)
+                                                                              const u64 *__restrict__ in,
+                                                                              std::size_t in_stride, u64 *__restrict__ out,
+                                                                              std::size_t out_stride, std::size_t count,
+                                                                              int logn, int mont, unsigned *__restrict__ tflags)
+        {
             const std::size_t N = static_cast<std::size_t>(1) << logn;
             const std::size_t half = N >> 1;
             Cols cc;
             bool is_hi = false;
-            if constexpr (DEFER)
-            {
-                // With the deferred top layer the lanes of columns c and c + N/2 read the same 2(k + |Bsk| + 1) words. Blocks
-                // are dealt round-robin over the 8 XCDs (one L2 each): physical blocks b and b + 8 run on the same XCD at
-                // about the same time, so they are given the lower and the upper half of the same 256 columns and the second
-                // read comes from L2 instead of HBM (the halves used to be half a grid apart: 37 row passes instead of 22).
-                // logn >= 14 here: the blocks of an item are a multiple of 16. Everything is derived from the block index, so
-                // the compiler knows is_hi is uniform and reads the tables selected by it with scalar loads.
-                const std::size_t per_item = N / kThreads, bid = blockIdx.x;
-                cc.item = bid / per_item;
-                if (cc.item >= count)
-                    return;
-                const unsigned pl = static_cast<unsigned>(bid - cc.item * per_item), r = pl & 15u;
-                is_hi = (r >> 3) != 0;
-                cc.c = (is_hi ? half : 0) + static_cast<std::size_t>(((pl >> 4) << 3) | (r & 7u)) * kThreads + threadIdx.x;
-            }
-            else if (!column(count, logn, cc))
+            if (DEFER ? !deferred_column(count, N, cc, is_hi) : !column(count, logn, cc))
                 return;
-            const auto *d = kc(d_);           // read-only for the lifetime of the context: constant address space
-            const auto *primes = kc(primes_); // (scalar loads the compiler may merge and hoist)
-            const int k = KMAX < 0 ? KA : d->k, B = d->B; // B is k or k + 1
-            // with an exact K every test against B is a compile-time fact except for the one optional extra prime of B
-            // (index K): no branches inside the row loops, so scalar loads and arithmetic of neighbouring rows overlap
-            const bool extraB = B > KA;
-            auto lt_B = [&](int j) { return KMAX < 0 ? (j < KA || (j == KA && extraB)) : j < B; };
-            auto le_B = [&](int j) { return KMAX < 0 ? (j <= KA || (j == KA + 1 && extraB)) : j <= B; };
+            const auto *d = kc(d_); // read-only for the lifetime of the context: constant address space
+            const int B = d->B;     // K or K + 1
+            // every test against B is a compile-time fact except for the one optional extra prime of B (index K): no
+            // branches inside the row loops, so scalar loads and arithmetic of neighbouring rows overlap
+            const bool extraB = B > K;
+            const auto lt_B = [&](int j) { return j < K || (j == K && extraB); };
+            const auto le_B = [&](int j) { return j <= K || (j == K + 1 && extraB); };
+            const u64 *pin = in + cc.item * in_stride + cc.c;
+            const u64 *pitem = in + cc.item * in_stride;
+            const std::size_t c_lo = cc.c & (half - 1);
+            u64 *pout = out + cc.item * out_stride + cc.c;
+            // every input word of this column is requested before any arithmetic: one exposed memory latency per
+            // thread instead of one per output row (the loads used to sit in the row loops)
+            u64 ru[2 * K + 2], rv[2 * K + 2];
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                ru[i] = DEFER ? pitem[i * N + c_lo] : pin[i * N];
+                rv[i] = DEFER ? pitem[i * N + c_lo + half] : 0;
+            }
+            static_for<K + 2>([&](auto J) {
+                constexpr int j = J.value;
+                if (le_B(j))
+                {
+                    ru[K + j] = DEFER ? pitem[(K + j) * N + c_lo] : pin[(K + j) * N];
+                    rv[K + j] = DEFER ? pitem[(K + j) * N + c_lo + half] : 0;
+                }
+            });
+            __builtin_amdgcn_sched_barrier(0);
+            u64 t[K];
+            // mont (kernel-uniform): the input words carry the Montgomery factor 2^-64 of the tensor product formed inside
+            // the inverse NTT; the constants of the first product of every input then carry 2^64 on top
+            const int top_sel = (mont ? 2 : 0) + (is_hi ? 1 : 0); // scalar: selects a table by address arithmetic
+            // {F0, its Shoup quotient, q_i} sit next to each other, one short scalar load per input row, requested
+            // as the loop goes (a batch of all 3K constants up front held 6K scalar registers through the first rows and
+            // pushed the row constants to scratch)
+            const auto *first = kc(d->floor_first) + (DEFER ? top_sel : 4) * (K * 3);
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                const u64 cF0 = first[3 * i], cF0s = first[3 * i + 1];
+                const u64 qp = first[3 * i + 2];
+                if (DEFER) // (u +- v) * (n^{-1} or w n^{-1}) * F0 with ONE canonical Shoup product
+                    t[i] = mulmod_shoup_hs(before_top<false>(ru[i], rv[i], is_hi, qp << 1), cF0, cF0s, qp);
+                else
+                    t[i] = mulmod_shoup_hs(ru[i], cF0, cF0s, qp);
+            }
+            u64 tb[K + 1];
+            u64 fl_sk = 0;
+            Split<S> ts[K], tbs[K + 1];
+            static_for<K>([&](auto I) { ts[I.value] = Split<S>(t[I.value]); });
+            // the row {G1, G2[0..K-1], p, -p^-1} of this launch's table, split at S, in one run of scalar loads
+            const auto *Frows = kc(d->floor_rows) + (DEFER ? top_sel : 4) * (d->nB * (K + 3));
+            // (compile-time row indices: a `#pragma unroll` gives up on these loops from K = 15 on and leaves
+            //  run-time indexed register arrays, i.e. scratch)
+            static_for<K + 2>([&](auto J) {
+                constexpr int j = J.value;
+                if (le_B(j))
+                {
+                    const auto *row = row_window(Frows + j * (K + 3));
+                    const u64 bp = row[K + 1];
+                    const u64 ninv = row[K + 2];
+                    const u64 x = DEFER ? before_top<true>(ru[K + j], rv[K + j], is_hi, bp << 1) : ru[K + j];
+                    u64 v = dot_redc_exact<1, K, 1>(Split<S>(x), row[0], ts, false, row, &bp, &ninv);
+                    row_done(v);
+                    if (lt_B(j))
+                        tb[j < K + 1 ? j : 0] = v;
+                    else
+                        fl_sk = v;
+                    // one row's constants at a time: left alone the scheduler requests the constants of every row up front
+                    // and spills scalar registers to scratch
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+            const u64 mp = d->b_p[B];
+            const auto *BtoMsk = kc(d->B_to_mskp);
+            static_for<K + 1>([&](auto J) {
+                if (lt_B(J.value))
+                    tbs[J.value] = Split<S>(tb[J.value]);
+            });
+            const u64 conv_sk = dot_redc_exact<2, K, 0>(Split<S>(), 0, tbs, extraB, BtoMsk, &mp, &d->b_ninv[B]);
+            const SkAlpha al = sk_alpha(conv_sk + (mp - fl_sk), mp, d);
+            const bool neg = al.neg;
+            const Split<S> a2s(al.a2);
+            const auto *Qrows = kc(d->q_rows); // rows {pB, nB, B_to_q[i][0..B-1], p, -p^-1}, split at S
+            u64 nz = 0;                        // OR of the words this column stores (transparency sink)
+            const auto q_row = [&](int i) {
+                const auto *qrow = Qrows + i * (B + 4);
+                const u64 c = neg ? qrow[0] : qrow[1];
+                const u64 w = dot_redc_exact<3, K, 2>(a2s, c, tbs, extraB, qrow, qrow + (B + 2), qrow + (B + 3));
+                pout[i * N] = w;
+                nz |= w;
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            static_for<K>([&](auto I) { q_row(I.value); });
+            note_nonzero(tflags, cc.item, nz); // (the launcher passes the sink for polynomials 1.. of the product only)
+        }
+
+        // The floor at a run-time k <= kBehzGeneric
+        template <bool DEFER>
+        __global__ __launch_bounds__(kThreads) void bfv_floor_sk_guarded_kernel(const RnsDev *__restrict__ d_,
+                                                                                const PrimeDev *__restrict__, // (RnsDev has the rows' primes)
+                                                                                const u64 *__restrict__ in,
+                                                                                std::size_t in_stride, u64 *__restrict__ out,
+                                                                                std::size_t out_stride, std::size_t count,
+                                                                                int logn, int mont, unsigned *__restrict__ tflags)
+        {
+            constexpr int KA = kBehzGeneric; // array extent
+            const std::size_t N = static_cast<std::size_t>(1) << logn;
+            const std::size_t half = N >> 1;
+            Cols cc;
+            bool is_hi = false;
+            if (DEFER ? !deferred_column(count, N, cc, is_hi) : !column(count, logn, cc))
+                return;
+            const auto *d = kc(d_); // read-only for the lifetime of the context: constant address space
+            const int k = d->k, B = d->B; // B is k or k + 1
             const u64 *pin = in + cc.item * in_stride + cc.c;
             const u64 *pitem = in + cc.item * in_stride;
             const std::size_t c_lo = cc.c & (half - 1);
@@ -377,46 +533,33 @@ namespace sealhip
             u64 ru[2 * KA + 2], rv[2 * KA + 2];
 #pragma unroll
             for (int i = 0; i < KA; i++)
-                if (KMAX < 0 || i < k)
+                if (i < k)
                 {
                     ru[i] = DEFER ? pitem[i * N + c_lo] : pin[i * N];
                     rv[i] = DEFER ? pitem[i * N + c_lo + half] : 0;
                 }
-            const auto load_bsk = [&](int j) {
-                if (le_B(j))
+#pragma unroll
+            for (int j = 0; j < KA + 2; j++)
+                if (j <= B)
                 {
                     ru[KA + j] = DEFER ? pitem[(k + j) * N + c_lo] : pin[(k + j) * N];
                     rv[KA + j] = DEFER ? pitem[(k + j) * N + c_lo + half] : 0;
                 }
-            };
-            if constexpr (KMAX < 0)
-                static_for<KA + 2>([&](auto J) { load_bsk(J.value); });
-            else
-            {
-#pragma unroll
-                for (int j = 0; j < KA + 2; j++)
-                    load_bsk(j);
-            }
             __builtin_amdgcn_sched_barrier(0);
             u64 t[KA];
             // mont (kernel-uniform): the input words carry the Montgomery factor 2^-64 of the tensor product formed inside
             // the inverse NTT; the constants of the first product of every input then carry 2^64 on top
             const int top_sel = (mont ? 2 : 0) + (is_hi ? 1 : 0); // scalar: selects a table by address arithmetic
-            const auto *F0t = DEFER ? kc(d->floor_F0_top[top_sel]) : kc(d->floor_F0);
-            const auto *F0ts = DEFER ? kc(d->floor_F0_top_s[top_sel]) : kc(d->floor_F0_s);
-            (void)primes;
             // the constants of the first loop, requested as one batch of scalar loads while the vector loads are in flight
             // (inside the loop every iteration waited for its own three)
-            // Exact K: {F0, its Shoup quotient, q_i} sit next to each other, one short scalar load per input row, requested
-            // as the loop goes (a batch of all 3K constants up front held 6K scalar registers through the first rows and
-            // pushed the row constants to scratch)
-            const auto *first = kc(d->floor_first) + (DEFER ? top_sel : 4) * (KA * 3);
+            const auto *F0t = DEFER ? kc(d->floor_F0_top[top_sel]) : kc(d->floor_F0);
+            const auto *F0ts = DEFER ? kc(d->floor_F0_top_s[top_sel]) : kc(d->floor_F0_s);
 #pragma unroll
             for (int i = 0; i < KA; i++)
-                if (KMAX < 0 || i < k)
+                if (i < k)
                 {
-                    const u64 cF0 = KMAX < 0 ? first[3 * i] : F0t[i], cF0s = KMAX < 0 ? first[3 * i + 1] : F0ts[i];
-                    const u64 qp = KMAX < 0 ? first[3 * i + 2] : d->q_p[i];
+                    const u64 cF0 = F0t[i], cF0s = F0ts[i];
+                    const u64 qp = d->q_p[i];
                     if (DEFER) // (u +- v) * (n^{-1} or w n^{-1}) * F0 with ONE canonical Shoup product
                         t[i] = mulmod_shoup_hs(before_top<false>(ru[i], rv[i], is_hi, qp << 1), cF0, cF0s, qp);
                     else
@@ -424,50 +567,17 @@ namespace sealhip
                 }
             u64 tb[KA + 1];
             u64 fl_sk = 0;
-            // exact-K instances are only launched when the host proved every REDC lands below 2p (RnsDev::redc_small):
-            // a compile-time fact there, so the row loops carry no branch
-            const bool small = KMAX < 0 ? true : d->redc_small != 0;
-            Split<S> ts[KA], tbs[KA + 1];
-            if constexpr (KMAX < 0)
-                static_for<KA>([&](auto I) { ts[I.value] = Split<S>(t[I.value]); });
+            const bool small = d->redc_small != 0;
             const auto *G1m = DEFER ? kc(d->floor_G1m_top[top_sel]) : kc(d->floor_G1m);
             const auto *G2m = kc(d->floor_G2m);
-            // Exact K: the row {G1, G2[0..K-1], p, -p^-1} of this launch's table, split at S, in one run of scalar loads
-            const auto *Frows = kc(d->floor_rows) + (DEFER ? top_sel : 4) * (d->nB * (KA + 3));
-            const auto bsk_row = [&](int j) {
-                if (le_B(j))
+            for (int j = 0; j < KA + 2; j++)
+                if (j <= B)
                 {
-                    auto *row = KMAX < 0 ? Frows + j * (KA + 3) : G2m + j * k;
-                    if constexpr (KMAX < 0)
-                        row = row_window(row);
-                    const u64 bp = KMAX < 0 ? row[KA + 1] : d->b_p[j];
-                    const u64 ninv = KMAX < 0 ? row[KA + 2] : d->b_ninv[j];
+                    const u64 bp = d->b_p[j];
+                    const u64 ninv = d->b_ninv[j];
                     const u64 x = DEFER ? before_top<true>(ru[KA + j], rv[KA + j], is_hi, bp << 1) : ru[KA + j];
-                    u64 lo, hi;
-                    if constexpr (KMAX < 0)
-                    {
-                        BehzDot<S, 1, KA> acc2;
-                        acc2.template add<0>(Split<S>(x), row[0]);
-                        static_for<KA>([&](auto I) { acc2.template add<I.value + 1>(ts[I.value], row[I.value + 1]); });
-                        acc2.finish(lo, hi);
-                    }
-                    else
-                    {
-                        lo = x * G1m[j];
-                        hi = mulhi(x, G1m[j]);
-#pragma unroll
-                        for (int i = 0; i < KA; i++)
-                            if (i < k)
-                                mac128(lo, hi, t[i], row[i]);
-                    }
-                    u64 v;
-                    if constexpr (KMAX < 0)
-                        v = redc_canonical_hs(lo, hi, bp, ninv);
-                    else
-                        v = redc_finish(redc128(lo, hi, bp, ninv), bp, d->b_rdp[j], small);
-                    if constexpr (KMAX < 0)
-                        row_done(v);
-                    if (lt_B(j))
+                    const u64 v = dot_redc_guarded(x, G1m[j], t, G2m + j * k, k, &bp, &ninv, &d->b_rdp[j], small);
+                    if (j < B)
                         tb[j < KA + 1 ? j : 0] = v;
                     else
                         fl_sk = v;
@@ -475,87 +585,20 @@ namespace sealhip
                     // and spills scalar registers to scratch
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            };
-            // (compile-time row indices for an exact K: a `#pragma unroll` gives up on these loops from K = 15 on and leaves
-            //  run-time indexed register arrays, i.e. scratch)
-            if constexpr (KMAX < 0)
-                static_for<KA + 2>([&](auto J) { bsk_row(J.value); });
-            else
-                for (int j = 0; j < KA + 2; j++)
-                    bsk_row(j);
             const u64 mp = d->b_p[B];
-            const auto *BtoMsk = KMAX < 0 ? kc(d->B_to_mskp) : kc(d->B_to_mskm);
-            u64 lo = 0, hi = 0;
-            if constexpr (KMAX < 0)
-            {
-                static_for<KA + 1>([&](auto J) {
-                    if (lt_B(J.value))
-                        tbs[J.value] = Split<S>(tb[J.value]);
-                });
-                BehzDot<S, 2, KA> acc2;
-                static_for<KA + 1>([&](auto J) {
-                    if (lt_B(J.value))
-                        acc2.template add<J.value>(tbs[J.value], BtoMsk[J.value]);
-                });
-                acc2.finish(lo, hi);
-            }
-            else
-            {
-#pragma unroll
-                for (int j = 0; j < KA + 1; j++)
-                    if (lt_B(j))
-                        mac128(lo, hi, tb[j], BtoMsk[j]);
-            }
-            const u64 conv_sk = KMAX < 0 ? redc_canonical_hs(lo, hi, mp, d->b_ninv[B])
-                                         : redc_finish(redc128(lo, hi, mp, d->b_ninv[B]), mp, d->b_rdp[B], small);
-            const u64 alpha = mulmod_shoup(conv_sk + (mp - fl_sk), d->inv_prod_B_mod_msk, d->inv_prod_B_mod_msk_s, mp);
-            const bool neg = alpha > (mp >> 1); // rns.cpp:909
-            const u64 a2 = neg ? mp - alpha : alpha;
-            const Split<S> a2s(a2);
+            const u64 conv_sk = dot_redc_guarded(0, 0, tb, kc(d->B_to_mskm), B, &mp, &d->b_ninv[B], &d->b_rdp[B], small);
+            const SkAlpha al = sk_alpha(conv_sk + (mp - fl_sk), mp, d);
             const auto *pBm = kc(d->pBm);
             const auto *nBm = kc(d->nBm);
             const auto *BtoQ = kc(d->B_to_qm);
-            const auto *Qrows = kc(d->q_rows); // exact K: rows {pB, nB, B_to_q[i][0..B-1], p, -p^-1}, split at S
-            u64 nz = 0;                        // OR of the words this column stores (transparency sink)
-            const auto q_row = [&](int i) {
-                const auto *qrow = Qrows + i * (B + 4);
-                const u64 c = KMAX < 0 ? (neg ? qrow[0] : qrow[1]) : (neg ? pBm[i] : nBm[i]);
-                const auto *mrow = KMAX < 0 ? qrow + 2 : BtoQ + i * B;
-                u64 l2, h2;
-                if constexpr (KMAX < 0)
-                {
-                    BehzDot<S, 3, KA> acc2;
-                    acc2.template add<0>(a2s, c);
-                    static_for<KA + 1>([&](auto J) {
-                        if (lt_B(J.value))
-                            acc2.template add<J.value + 1>(tbs[J.value], mrow[J.value]);
-                    });
-                    acc2.finish(l2, h2);
-                }
-                else
-                {
-                    l2 = a2 * c;
-                    h2 = mulhi(a2, c);
-#pragma unroll
-                    for (int j = 0; j < KA + 1; j++)
-                        if (lt_B(j))
-                            mac128(l2, h2, tb[j], mrow[j]);
-                }
-                const u64 qp = KMAX < 0 ? qrow[B + 2] : d->q_p[i];
-                u64 w;
-                if constexpr (KMAX < 0)
-                    w = redc_canonical_hs(l2, h2, qp, qrow[B + 3]);
-                else
-                    w = redc_finish(redc128(l2, h2, qp, d->q_ninv[i]), qp, d->q_rdp[i], small);
+            u64 nz = 0; // OR of the words this column stores (transparency sink)
+            for (int i = 0; i < k; i++)
+            {
+                const u64 w = dot_redc_guarded(al.a2, al.neg ? pBm[i] : nBm[i], tb, BtoQ + i * B, B, &d->q_p[i], &d->q_ninv[i], &d->q_rdp[i], small);
                 pout[i * N] = w;
                 nz |= w;
                 __builtin_amdgcn_sched_barrier(0);
-            };
-            if constexpr (KMAX < 0)
-                static_for<KA>([&](auto I) { q_row(I.value); });
-            else
-                for (int i = 0; i < k; i++)
-                    q_row(i);
+            }
             note_nonzero(tflags, cc.item, nz); // (the launcher passes the sink for polynomials 1.. of the product only)
         }
 
@@ -654,8 +697,7 @@ namespace sealhip
             sk_finish<KMAX>(d, primes, tb, pin[B * N], out + cc.item * out_stride + cc.c, N);
         }
 
-        // fused BEHZ steps (6)-(8) of evaluator.cpp:427-444: (k+|Bsk|) rows -> k rows
-        template <int KMAX>
+        // fused BEHZ steps (6)-(8) of evaluator.cpp:427-444: (k+|Bsk|) rows -> k rows. The step-by-step form, for k > 32
         __global__ __launch_bounds__(kThreads) void bfv_floor_sk_kernel(const RnsDev *__restrict__ d,
                                                                         const PrimeDev *__restrict__ primes,
                                                                         const u64 *__restrict__ in,
@@ -669,34 +711,34 @@ namespace sealhip
             const int k = d->k, B = d->B;
             const std::size_t N = static_cast<std::size_t>(1) << logn;
             const u64 *pin = in + cc.item * in_stride + cc.c;
-            u64 t[KMAX];
+            u64 t[kMaxModuli];
 #pragma unroll
-            for (int i = 0; i < KMAX; i++)
+            for (int i = 0; i < kMaxModuli; i++)
                 if (i < k)
                 {
                     const PrimeDev &Q = primes[d->q_prime[i]];
                     const u64 x = mul_mod(pin[i * N], d->t, Q.p, Q.cr0, Q.cr1);
                     t[i] = mul_mod(x, d->q_inv[i], Q.p, Q.cr0, Q.cr1);
                 }
-            u64 tb[KMAX + 1];
+            u64 tb[kMaxModuli + 1];
             u64 in_sk = 0;
 #pragma unroll
-            for (int j = 0; j < KMAX + 2; j++)
+            for (int j = 0; j < kMaxModuli + 2; j++)
                 if (j <= B)
                 {
                     const PrimeDev &Bp = primes[d->bsk_prime[j]];
-                    const u64 conv = dot_mod<KMAX>(t, k, d->q_to_Bsk + j * k, Bp);
+                    const u64 conv = dot_mod<kMaxModuli>(t, k, d->q_to_Bsk + j * k, Bp);
                     const u64 x = mul_mod(pin[(k + j) * N], d->t, Bp.p, Bp.cr0, Bp.cr1);
                     const u64 fl = mul_mod(x + (Bp.p - conv), d->inv_prod_q_mod_Bsk[j], Bp.p, Bp.cr0, Bp.cr1);
                     if (j < B)
                     {
-                        if (j < KMAX + 1)
-                            tb[j < KMAX + 1 ? j : 0] = mul_mod(fl, d->B_inv[j], Bp.p, Bp.cr0, Bp.cr1);
+                        if (j < kMaxModuli + 1)
+                            tb[j < kMaxModuli + 1 ? j : 0] = mul_mod(fl, d->B_inv[j], Bp.p, Bp.cr0, Bp.cr1);
                     }
                     else
                         in_sk = fl;
                 }
-            sk_finish<KMAX>(d, primes, tb, in_sk, out + cc.item * out_stride + cc.c, N);
+            sk_finish<kMaxModuli>(d, primes, tb, in_sk, out + cc.item * out_stride + cc.c, N);
         }
 
         // divide_and_round_q_last_inplace (rns.cpp:731-775); writes out_rows rows (k-1, or k to mirror the
@@ -838,8 +880,9 @@ namespace sealhip
 
     namespace
     {
-        // The step-by-step kernels are instantiated for row counts rounded up to 4, 8, 16, 32 and 64 (kMaxModuli):
-        // f(integral_constant<int, KM>) for the smallest of them that holds k.
+        // The unit kernels are instantiated for row counts rounded up to 4, 8, 16, 32 and 64 (kMaxModuli):
+        // f(integral_constant<int, KM>) for the smallest of them that holds k. (The two fused step-by-step kernels run
+        // for k > 32 only and have the one extent kMaxModuli.)
         template <class F>
         void dispatch_k_bucket(int k, F &&f)
         {
@@ -875,17 +918,14 @@ namespace sealhip
 
     namespace
     {
-        // The fused BEHZ kernels' exact-k instances: f(KM = -k, S) for the plan's code k = 1 .. 15, S the split the level's
-        // tables are packed with (RnsDev::dot_split: 30, else 31). false: the code names the generic instance (KM = 32).
-        constexpr int kBehzDefaultSplit = 31;
+        // The fused BEHZ kernels' exact-k instances: f(K, S) for the plan's code K = 1 .. 15, S the split the level's
+        // tables are packed with (RnsDev::dot_split: 30, else 31). false: the code names the run-time-k kernel.
         template <class F>
         bool dispatch_behz_exact(int code, int dot_split, F &&f)
         {
             return dispatch_int<1, bounds::kBehzExactMaxK>(code, [&](auto k) {
-                dispatch_bool(dot_split == 30, [&](auto s30) {
-                    f(std::integral_constant<int, -decltype(k)::value>{},
-                      std::integral_constant<int, decltype(s30)::value ? 30 : kBehzDefaultSplit>{});
-                });
+                dispatch_bool(dot_split == 30,
+                              [&](auto s30) { f(k, std::integral_constant<int, decltype(s30)::value ? 30 : 31>{}); });
             });
         }
     } // namespace
@@ -919,23 +959,16 @@ namespace sealhip
             return hipErrorInvalidValue;
         const unsigned grid = blocks_for(count, top_layer ? e.logn - 1 : e.logn);
         ProfScope prof(e, "bfv_lift", 0);
-        if (plan.lift_kernel != kBehzStepwise)
-        {
-            const auto launch = [&](auto km, auto top, auto split) {
-                bfv_lift2_kernel<decltype(km)::value, decltype(top)::value, decltype(split)::value>
-                    <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
-            };
-            // (only the exact-k instances apply the top layer)
-            if (!dispatch_behz_exact(plan.lift_kernel, h.dot_split,
-                                     [&](auto km, auto split) { dispatch_bool(top_layer, [&](auto top) { launch(km, top, split); }); }))
-                launch(std::integral_constant<int, kBehzGeneric>{}, std::false_type{},
-                       std::integral_constant<int, kBehzDefaultSplit>{});
-            return hipGetLastError();
-        }
-        dispatch_k_bucket(h.k, [&](auto km) {
-            bfv_lift_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride,
-                                                                                         count, e.logn);
-        });
+        if (plan.lift_kernel == kBehzStepwise)
+            bfv_lift_kernel<<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+        else if (!dispatch_behz_exact(plan.lift_kernel, h.dot_split, [&](auto k, auto split) {
+                     dispatch_bool(top_layer, [&](auto top) { // (only the exact-k instances apply the top layer)
+                         bfv_lift_exact_kernel<decltype(k)::value, decltype(top)::value, decltype(split)::value>
+                             <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
+                     });
+                 }))
+            bfv_lift_guarded_kernel<<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count,
+                                                                            e.logn);
         return hipGetLastError();
     }
 
@@ -983,24 +1016,22 @@ namespace sealhip
         ProfScope prof(e, "bfv_floor_sk", 0);
         if (plan.floor_kernel != kBehzStepwise)
         {
-            // (every instance, the generic one included, has the form that applies the deferred top layer)
-            const auto launch = [&](auto km, auto split) {
-                dispatch_bool(deferred_top != 0, [&](auto top) {
-                    bfv_floor_sk2_kernel<decltype(km)::value, decltype(top)::value, decltype(split)::value>
-                        <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn,
-                                                                 deferred_top == 2 ? 1 : 0, tflags);
-                });
-            };
-            if (!dispatch_behz_exact(plan.floor_kernel, h.dot_split, launch))
-                launch(std::integral_constant<int, kBehzGeneric>{}, std::integral_constant<int, kBehzDefaultSplit>{});
+            // (both families have the form that applies the deferred top layer)
+            const int mont = deferred_top == 2 ? 1 : 0;
+            dispatch_bool(deferred_top != 0, [&](auto top) {
+                if (!dispatch_behz_exact(plan.floor_kernel, h.dot_split, [&](auto k, auto split) {
+                        bfv_floor_sk_exact_kernel<decltype(k)::value, decltype(top)::value, decltype(split)::value>
+                            <<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn,
+                                                                     mont, tflags);
+                    }))
+                    bfv_floor_sk_guarded_kernel<decltype(top)::value><<<grid, kThreads, 0, e.lane().stream>>>(
+                        d, e.d_primes, in, in_stride, out, out_stride, count, e.logn, mont, tflags);
+            });
             return hipGetLastError();
         }
         if (deferred_top)
             return hipErrorInvalidValue;
-        dispatch_k_bucket(h.k, [&](auto km) {
-            bfv_floor_sk_kernel<decltype(km)::value><<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out,
-                                                                                             out_stride, count, e.logn);
-        });
+        bfv_floor_sk_kernel<<<grid, kThreads, 0, e.lane().stream>>>(d, e.d_primes, in, in_stride, out, out_stride, count, e.logn);
         hipError_t err = hipGetLastError();
         if (err == hipSuccess && tflags)
             err = launch_nonzero_words(e, out, out_stride, static_cast<std::size_t>(h.k) << e.logn, count, tflags);

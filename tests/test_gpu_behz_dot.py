@@ -1,4 +1,4 @@
-"""BFV multiply and square through the exact-k BEHZ kernels (bfv_lift2_kernel / bfv_floor_sk2_kernel, rns.hip) with the
+"""BFV multiply and square through the exact-k BEHZ kernels (bfv_lift_exact_kernel / bfv_floor_sk_exact_kernel, rns.hip) with the
 operands highest in the dot products' accumulators (dotacc.hpp DotAcc31), word for word against the CPU oracle.
 
 Ring N = 2^14, the smallest with the fused kernels; 58-bit ciphertext primes, the widest the fused tensor product admits;

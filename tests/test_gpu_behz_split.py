@@ -1,4 +1,4 @@
-"""BFV multiply and square through the exact-k BEHZ kernels (bfv_lift2_kernel / bfv_floor_sk2_kernel, rns.hip) at both
+"""BFV multiply and square through the exact-k BEHZ kernels (bfv_lift_exact_kernel / bfv_floor_sk_exact_kernel, rns.hip) at both
 split positions of their carry-free dot products (dotacc.hpp DotAccSplit<S, ...>), word for word against the CPU oracle.
 
 Ring N = 2^14, the smallest with the fused kernels; 3 items per call; PARITY and STRICT; levels k = 1, 7, 8, 15 and two

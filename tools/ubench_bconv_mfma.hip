@@ -1,7 +1,7 @@
 // ubench_bconv_mfma.hip -- round 4, VERDICT r03 item 5: the byte-limb int8-MFMA form of a BEHZ base conversion TIMED
 // against the carry-free vector-ALU form the engine ships (devmath.hpp DotAcc), instead of estimated.
 //
-// One instance, the one the verdict names: config 3's q -> Bsk conversion inside bfv_lift2 / bfv_floor_sk2
+// One instance, the one the verdict names: config 3's q -> Bsk conversion inside bfv_lift_exact / bfv_floor_sk_exact
 // (BaseConverter::fast_convert_array, native/src/seal/util/rns.cpp:469-496): per coefficient column 7 words t_i < 2^56 in,
 // 8 words out,  r_j = (sum_i t_i * M_ji) mod p_j  with M a constant 8 x 7 matrix of residues of 60-bit primes p_j.
 // Both kernels compute that canonical residue from the exact integer sum (so they agree bit for bit, and with the
@@ -59,7 +59,7 @@ __constant__ Consts g_c;
 
 // ---------------------------------------------------------------- the shipped form
 // REPS > 1: the conversion is repeated on the loaded words (each repetition on t + rep, results xor-ed) so that the kernels are
-// bound by their arithmetic, as the fused BEHZ kernels are (bfv_floor_sk2 forms ~170 products per column from 30 loaded words;
+// bound by their arithmetic, as the fused BEHZ kernels are (bfv_floor_sk_exact forms ~170 products per column from 30 loaded words;
 // one conversion alone -- 56 products from 7 words -- is bound by its memory traffic in either form)
 template <int REPS>
 __global__ __launch_bounds__(256) void bconv_valu(const u64 *__restrict__ in, u64 *__restrict__ out, std::size_t ncols)
