@@ -1966,6 +1966,120 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
     });
 }
 
+/* ------------------------------------------------------------------ ring packing */
+namespace
+{
+    // n = 2^l samples, 0 <= l <= log N: l, or the refusal
+    int pack_log_n(const Engine &h, size_t n)
+    {
+        if (n < 1 || n > h.n || (n & (n - 1)))
+            throw std::invalid_argument("n must be a power of two between 1 and N");
+        int l = 0;
+        while ((static_cast<size_t>(1) << l) < n)
+            l++;
+        return l;
+    }
+} // namespace
+
+long sealhip_pack_lwes_galois_elts(sealhip_context *ctx, size_t n, int32_t trace, uint32_t *elts, uint32_t capacity,
+                                   uint32_t *n_elts)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(n_elts);
+    return guarded([&] {
+        const Engine &h = *ctx->engine;
+        const int l = pack_log_n(h, n), last = trace ? h.logn : l; // the steps t = 1 .. last run
+        *n_elts = static_cast<uint32_t>(last);
+        if (!elts)
+            return;
+        if (capacity < static_cast<uint32_t>(last))
+            throw std::invalid_argument("capacity is smaller than the number of Galois elements");
+        for (int t = 1; t <= last; t++)
+            elts[t - 1] = (1u << t) + 1;
+    });
+}
+
+long sealhip_evaluator_extract_lwe(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                   const uint32_t *indices_host, size_t n_idx, uint64_t *lwe_a, uint64_t *lwe_b)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(lwe_a);
+    REQUIRE_PTR(lwe_b);
+    if (n_idx)
+        REQUIRE_PTR(indices_host);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        for (size_t i = 0; i < n_idx; i++)
+            if (indices_host[i] >= h.n)
+                throw std::invalid_argument("coefficient index out of range");
+        if (reinterpret_cast<uintptr_t>(lwe_a) % 16)
+            throw std::invalid_argument("lwe_a must be 16-byte aligned");
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        const u64 *a = reinterpret_cast<const u64 *>(lwe_a), *b = reinterpret_cast<const u64 *>(lwe_b);
+        const std::size_t a_words = count * n_idx * poly, b_words = count * n_idx * k;
+        if (words_overlap(a, a_words, in, count * 2 * poly) || words_overlap(b, b_words, in, count * 2 * poly) ||
+            words_overlap(a, a_words, b, b_words))
+            throw std::invalid_argument("lwe_a and lwe_b must not overlap ct or each other");
+        if (count == 0 || n_idx == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("extract_lwe stages its indices: it cannot be captured");
+        Scratch scratch(e);
+        std::uint32_t *idx = reinterpret_cast<std::uint32_t *>(scratch.take(n_idx * sizeof(std::uint32_t)));
+        SEALHIP_CHECK(hipMemcpyAsync(idx, indices_host, n_idx * sizeof(std::uint32_t), hipMemcpyHostToDevice, e.lane().stream));
+        op_extract_lwe(e, static_cast<int>(k), in, count, idx, n_idx, reinterpret_cast<u64 *>(lwe_a), reinterpret_cast<u64 *>(lwe_b));
+    });
+}
+
+long sealhip_evaluator_pack_lwes(sealhip_context *ctx, uint32_t k, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t n,
+                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                 uint32_t n_keys, int32_t trace, int32_t normalize, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(lwe_a);
+    REQUIRE_PTR(lwe_b);
+    REQUIRE_PTR(out);
+    REQUIRE_GALOIS_KEYS(n_keys);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        const int l = pack_log_n(h, n), last = trace ? h.logn : l;
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("ring packing of BFV ciphertexts needs a STRICT context");
+        for (uint32_t i = 0; i < n_keys; i++)
+            check_galois_elt(h, galois_elts[i]);
+        std::vector<const KSwitchKey *> keys(static_cast<size_t>(h.logn) + 1, nullptr);
+        for (int t = 1; t <= last; t++)
+        {
+            const uint32_t g = (1u << t) + 1;
+            for (uint32_t i = 0; i < n_keys && !keys[t]; i++)
+                if (galois_elts[i] == g)
+                {
+                    check_key_digits(h, k, galois_keys[i]);
+                    keys[t] = &galois_keys[i]->key;
+                }
+            if (!keys[t])
+                throw std::invalid_argument("Galois key not present");
+        }
+        if (reinterpret_cast<uintptr_t>(lwe_a) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+            throw std::invalid_argument("lwe_a and out must be 16-byte aligned");
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *a = reinterpret_cast<const u64 *>(lwe_a), *b = reinterpret_cast<const u64 *>(lwe_b);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * 2 * poly, a, count * n * poly) || words_overlap(o, count * 2 * poly, b, count * n * k))
+            throw std::invalid_argument("out must not overlap lwe_a or lwe_b");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count);
+        op_pack_lwes(e, static_cast<int>(k), a, b, l, count, keys.data(), trace != 0, normalize != 0, o, sink);
+    });
+}
+
 /* ------------------------------------------------------------------ mod-down merged with the rescale */
 long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
                                            size_t ct_item_stride, size_t count, const sealhip_kswitch_key *const *relin_keys,

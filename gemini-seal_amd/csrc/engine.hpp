@@ -393,6 +393,10 @@ namespace sealhip
         int plain_prime = -1;                  // prime id of the plain modulus when batching is possible (context.cpp:262-275)
         std::uint32_t *d_batch_map = nullptr;  // BatchEncoder::matrix_reps_index_map_ (batchencoder.cpp:70-94)
         const std::uint32_t *batch_map();
+        // ring packing: NTT_r(X^(N / 2^t)) for t = 1 .. logn and every ciphertext prime r, as
+        // {word, Shoup companion} pairs: [t - 1][k_first][N][2]
+        u64 *d_pack_mono = nullptr;
+        const u64 *pack_monomials();
         mutable std::mutex mu; // lazily built shared tables (levels, Galois tables, encoder tables, parms_ids)
         // profiler (per lane)
         void prof_begin(const char *tag, double units) const;
@@ -709,6 +713,24 @@ namespace sealhip
     hipError_t launch_galois(const Engine &e, const u64 *in, u64 *out, std::size_t nrows, const RowMap &map,
                              std::uint32_t elt, const std::uint32_t *table /* null: coefficient form */);
 
+    // ring packing (ringpack.hip). map_q: the level's k ciphertext rows.
+    // lwe_a[count][n_idx][k][N], lwe_b[count][n_idx][k] = the LWE samples of the coefficients idx[.] (device, each < N) of
+    // the coefficient-form size-2 ciphertexts ct (ct_stride words per item)
+    hipError_t launch_lwe_extract(const Engine &e, const u64 *ct, std::size_t ct_stride, std::size_t count,
+                                  const std::uint32_t *idx, std::size_t n_idx, u64 *lwe_a, u64 *lwe_b, const RowMap &map_q);
+    // out[jj][item][2][k][N], jj < n_out = the embedding of sample (item, j) of lwe_a[items][n][k][N] times w[r] (w_shoup: its
+    // Shoup companions; host arrays of k words); c_1 in coefficient form, c_0 in coefficient form or (ntt_c0) as its
+    // transform. n_out = c: j = j0 + jj. n_out = 2 c: then also j = n / 2 + j0 + (jj - c), the other operands of c merges.
+    hipError_t launch_lwe_embed(const Engine &e, const u64 *lwe_a, const u64 *lwe_b, std::size_t n, std::size_t items,
+                                std::size_t j0, std::size_t c, std::size_t n_out, u64 *out, const RowMap &map_q, const u64 *w,
+                                const u64 *w_shoup, bool ntt_c0);
+    // out[x] = ((E_0 + O_0) + sigma_g(E_0 - O_0), E_1 + O_1), target[x] = sigma_g(E_1 - O_1) for ncts ciphertexts, O = X^shift B
+    // (B null: O absent, the trace step). table null: coefficient form with ginv = g^{-1} mod 2N; else NTT form with
+    // table = T_g and mono = the step's rows of Engine::pack_monomials. out and target overlap neither E nor B.
+    hipError_t launch_pack_merge(const Engine &e, const u64 *E, const u64 *B, u64 *out, u64 *target, std::size_t ncts,
+                                 const RowMap &map_q, std::uint32_t shift, std::uint32_t ginv, const std::uint32_t *table,
+                                 const u64 *mono);
+
     // key switch
     // ext is digit-major: ext + j*ext_digit_stride + item*ext_stride + r*N
     hipError_t launch_ks_modup(const Engine &e, const KsDev *d, const KsDev &h, const u64 *coeff,
@@ -912,6 +934,13 @@ namespace sealhip
     void op_divround_ntt_inplace(Engine &e, int k, u64 *data, std::size_t count);
     void op_rescale_special_inplace(Engine &e, int k, u64 *poly, std::size_t count);
     void op_apply_galois(Engine &e, int k, u64 *ct, std::size_t count, std::uint32_t elt, const KSwitchKey &key);
+    // Ring packing. extract: the samples of the coefficients idx (device) of ct[count][2][k][N] in the
+    // scheme's form; ct is only read. pack: out[count][2][k][N] = the pack of the n = 2^l samples of every item, then (trace)
+    // the field trace (n is passed as l); keys[t] is the key of 2^t + 1 for the steps t that run (1 .. l, and l + 1 .. logn with trace).
+    void op_extract_lwe(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *idx, std::size_t n_idx,
+                        u64 *lwe_a, u64 *lwe_b);
+    void op_pack_lwes(Engine &e, int k, const u64 *lwe_a, const u64 *lwe_b, int l, std::size_t count,
+                      const KSwitchKey *const *keys, bool trace, bool normalize, u64 *out, SinkScope &sink);
     // One decomposition of c_1, n_elts rotations: out[n_elts][count][2][k][N], ct is only read.
     // Not the words of n_elts calls of op_apply_galois (the automorphism does not commute with the mod-up).
     void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,

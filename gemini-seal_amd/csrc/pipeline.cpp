@@ -32,6 +32,8 @@ namespace sealhip
             // where larger chunks mean larger launches (bench: +3 % from 8 to 48 GiB). Fixed per lane (an operation that
             // parks scratch at the front of the arena relies on the nested operation seeing the same cap); a lane created
             // later sees what the earlier ones left, so the caps of all threads' lanes cannot add up to more than the device.
+            // An operation that parks scratch plans the nested one with the whole cap: the arena then exceeds it by the
+            // parked bytes (op_apply_galois: at most 1 GiB; op_pack_lwes: at most half of the cap, 1.5 times in all).
             Lane &l = e.lane();
             if (l.ws_budget)
                 return l.ws_budget;
@@ -1316,6 +1318,173 @@ namespace sealhip
             op_switch_key(e, k, c, 2 * poly, scratch + poly, 2 * poly, m, key, scratch, 2 * poly);
         }
     }
+    // ------------------------------------------------------------------------------------------
+    // Ring packing: LWE samples out of a ciphertext, and n = 2^l of them packed into one
+    // ------------------------------------------------------------------------------------------
+    void op_extract_lwe(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *idx, std::size_t n_idx,
+                        u64 *lwe_a, u64 *lwe_b)
+    {
+        LevelTools &lt = e.level(k);
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N;
+        const std::size_t a_item = n_idx * poly, b_item = n_idx * static_cast<std::size_t>(k);
+        if (e.scheme != 2) // BFV ciphertexts are in coefficient form already
+        {
+            check(launch_lwe_extract(e, ct, 2 * poly, count, idx, n_idx, lwe_a, lwe_b, lt.map_q), "lwe_extract");
+            return;
+        }
+        // CKKS: a temporary copy goes back to coefficient form; the caller's ciphertext is not modified
+        for_chunks(e, count, 2 * poly * sizeof(u64), 1, [&](std::size_t off, std::size_t m) {
+            u64 *tmp = e.ws_alloc(2 * poly * m);
+            check(launch_copy_rows(e, ct + off * 2 * poly, poly, tmp, poly, 2 * m, k), "copy");
+            check(launch_ntt(e, tmp, 2 * m * k, lt.map_q, true, kNttCanonical), "intt(ct)");
+            check(launch_lwe_extract(e, tmp, 2 * poly, m, idx, n_idx, lwe_a + off * a_item, lwe_b + off * b_item, lt.map_q),
+                  "lwe_extract");
+        });
+    }
+
+    // The pack keeps its working set sample-major, W[j][item]: step t merges W[j] and W[j + half] for j < half, so both
+    // operands, the result and the key switch's batch are contiguous runs of half * items ciphertexts. A step is one merge
+    // launch, which leaves (E + O) + (sigma_g(E_0 - O_0), 0) in the destination and sigma_g(E_1 - O_1) in `target`, and one
+    // key switch of `target` that adds into the destination: the sums of (E + O) + apply_galois(E - O, g), reordered.
+    // The working set is parked at the front of the arena under a raised floor, as op_apply_galois parks its scratch, and
+    // takes at most half of the arena's cap; the nested key switch plans with the whole cap as always, so the arena may
+    // reach 1.5 times the cap while a pack runs. Three buffers: A for the embeddings and then every even step's
+    // result; B for every odd step's, the first one's n / 2 ciphertexts above all; the targets. The last step
+    // writes to `out`. When A cannot hold all embeddings of a chunk of items, the batch is walked item by item; when not
+    // even those of one item, the first step walks the item's merges in groups of c: embed {j, j + n/2} for c values of
+    // j, merge them into B, continue -- A then holds 2 c ciphertexts. Modular sums do not depend on the grouping, so the
+    // words are the same. What must always fit is the first step's result and the second step's: 0.875 n ciphertexts.
+    void op_pack_lwes(Engine &e, int k, const u64 *lwe_a, const u64 *lwe_b, int l, std::size_t count,
+                      const KSwitchKey *const *keys, bool trace, bool normalize, u64 *out, SinkScope &sink)
+    {
+        LevelTools &lt = e.level(k);
+        const bool ckks = e.scheme == 2;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N, n = static_cast<std::size_t>(1) << l;
+        const int steps = trace ? e.logn : l;
+        // w_r: the inverse of what the steps multiply the phase by (n, or N with the trace), else 1
+        u64 w[kMaxModuli], w_shoup[kMaxModuli];
+        for (int r = 0; r < k; r++)
+        {
+            const u64 q = e.key_moduli[static_cast<std::size_t>(r)];
+            w[r] = 1;
+            if (normalize && !invmod((trace ? N : n) % q, q, w[r]))
+                throw std::logic_error("pack: the normalisation has no inverse");
+            w_shoup[r] = shoup(w[r], q);
+        }
+        const u64 *mono = ckks && l ? e.pack_monomials() : nullptr;
+        std::vector<const std::uint32_t *> tables(static_cast<std::size_t>(e.logn) + 1, nullptr);
+        std::vector<std::uint32_t> ginv(static_cast<std::size_t>(e.logn) + 1, 1); // (2^t + 1)^{-1} mod 2N
+        for (int t = 1; t <= steps; t++)
+        {
+            const std::uint32_t g = (1u << t) + 1;
+            if (ckks)
+                tables[static_cast<std::size_t>(t)] = e.galois_table(g);
+            std::uint32_t &inv = ginv[static_cast<std::size_t>(t)];
+            for (int it = 0; it < 5; it++) // every Newton step doubles the correct low bits, from one to 32
+                inv *= 2 - g * inv;
+            inv &= static_cast<std::uint32_t>(2 * N - 1);
+        }
+
+        // one item's buffers in words when the first step merges c values of j at a time (l = 0: one embedding, no merge)
+        const std::size_t half0 = std::max<std::size_t>(1, n / 2);
+        struct Words
+        {
+            std::size_t a, b, t;
+            std::size_t bytes() const
+            {
+                return (a + b + t) * sizeof(u64);
+            }
+        };
+        auto words_for = [&](std::size_t c) {
+            const std::size_t emb = l ? 2 * c : 1;
+            return Words{ steps ? std::max(emb, n / 4) * 2 * poly : 0, steps >= 2 ? half0 * 2 * poly : 0,
+                          steps ? std::max(l ? c : 1, n / 4) * poly : 0 };
+        };
+        const std::size_t cap = workspace_budget_bytes(e) / 2 - 3 * 256;
+        std::size_t c = half0, items = count;
+        Words ww = words_for(c);
+        if (ww.bytes() > cap) // one item at a time, its first step in groups
+        {
+            items = 1;
+            do
+                ww = words_for(c /= 2);
+            while (c && ww.bytes() > cap);
+            if (!c)
+                throw HipError(hipErrorOutOfMemory,
+                               ("pack: the smallest working set of one item (" + std::to_string(words_for(1).bytes()) +
+                                " bytes) does not fit half of the workspace arena (" + std::to_string(cap) +
+                                " bytes): raise SEALHIP_WORKSPACE_MB or pack fewer samples per call")
+                                   .c_str());
+        }
+        else if (ww.bytes())
+            items = std::max<std::size_t>(1, std::min(count, cap / ww.bytes()));
+        const std::size_t scratch_bytes = pad256(ww.a * items) + pad256(ww.b * items) + pad256(ww.t * items);
+        Lane &lane = e.lane();
+        e.ws_reserve(lane.ws_floor + scratch_bytes + 256);
+        FloorRestore guard(e);
+        guard.raise(scratch_bytes);
+        const RowMap map_c1 = ct_row_map(k, 2, 1);
+        for (std::size_t off = 0; off < count; off += items)
+        {
+            const std::size_t m = std::min(items, count - off);
+            u64 *dst_out = out + off * 2 * poly;
+            const u64 *a_in = lwe_a + off * n * poly, *b_in = lwe_b + off * n * static_cast<std::size_t>(k);
+            // size the arena now as the largest nested key switch will ask for, so that it cannot move while the working set
+            // is live, and derive the pointers after it
+            if (steps)
+                plan_chunk(e, m * std::max(l ? c : 1, n / 4), switch_key_arena(e, k).item_bytes(), KsArena::n_buffers, false);
+            Carver carve{ static_cast<char *>(guard.parked()) };
+            u64 *bufs[2] = { carve.take(ww.a * items), nullptr };
+            bufs[1] = carve.take(ww.b * items);
+            u64 *target = carve.take(ww.t * items);
+            // n_out embeddings (c_1 alone transformed for CKKS: an embedded c_0 is a constant, written in NTT form directly)
+            auto embed = [&](std::size_t j0, std::size_t cj, std::size_t n_out, u64 *emb) {
+                check(launch_lwe_embed(e, a_in, b_in, n, m, j0, cj, n_out, emb, lt.map_q, w, w_shoup, ckks), "lwe_embed");
+                if (ckks)
+                    check(launch_ntt(e, emb, n_out * m * 2 * k, map_c1, false, kNttCanonical), "ntt(embedded c1)");
+            };
+            // one launch and one key switch: ncts results of step t from src (and, merging, the ncts ciphertexts behind them)
+            auto step = [&](int t, const u64 *src, std::size_t ncts, u64 *dst) {
+                check(launch_pack_merge(e, src, t <= l ? src + ncts * 2 * poly : nullptr, dst, target, ncts, lt.map_q,
+                                        static_cast<std::uint32_t>(N >> t), ginv[static_cast<std::size_t>(t)],
+                                        tables[static_cast<std::size_t>(t)],
+                                        mono ? mono + static_cast<std::size_t>(t - 1) * e.k_first * N * 2 : nullptr),
+                      "pack_merge");
+                if (t == steps) // one flag per output ciphertext, from the last key switch
+                {
+                    sink.arm();
+                    lane.tsink_base = guard.base + off;
+                }
+                op_switch_key(e, k, dst, 2 * poly, target, poly, ncts, *keys[t]);
+                lane.tsink_cur = nullptr;
+            };
+            if (!l)
+                embed(0, 1, 1, steps ? bufs[0] : dst_out);
+            else
+                for (std::size_t j0 = 0; j0 < half0; j0 += c) // step 1, by groups (one group: c = n / 2)
+                {
+                    embed(j0, c, 2 * c, bufs[0]);
+                    step(1, bufs[0], c * m, (steps == 1 ? dst_out : bufs[1]) + j0 * m * 2 * poly);
+                }
+            std::size_t cur = l ? half0 : 1; // ciphertexts per item
+            for (int t = l ? 2 : 1; t <= steps; t++)
+            {
+                const std::size_t left = t <= l ? cur / 2 : cur;
+                // (odd steps read A and write B, even steps the reverse: step 1 leaves its result in B, and a trace without
+                // any merge starts from the embedding in A)
+                const int from = (t & 1) ^ 1;
+                step(t, bufs[from], left * m, t == steps ? dst_out : bufs[from ^ 1]);
+                cur = left;
+            }
+        }
+        if (!steps)
+            sink.read_pass(out, 2, poly, count);
+        // (after the key switches' own entries: the last pairs of sealhip_debug_chunk_log)
+        if (c < half0)
+            log_chunk(e, half0, c);
+        log_chunk(e, count, items);
+    }
+
     // ------------------------------------------------------------------------------------------
     // Hoisted rotation: n_elts automorphisms of the same ciphertexts with one decomposition of c_1
     // ------------------------------------------------------------------------------------------

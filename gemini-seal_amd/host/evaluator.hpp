@@ -769,6 +769,39 @@ namespace sealhip_host
         std::vector<std::uint32_t> key_steps_;
     };
 
+    // LWE samples of coefficients of one resident ciphertext (Evaluator::extract_lwe / pack_lwes): a is
+    // n x k x N words and b is n x k words, in two blocks of the context's pool, with the level and the scale of the
+    // ciphertext they came from. Move-only.
+    class LweSamples
+    {
+    public:
+        explicit LweSamples(const Context &context) : ctx_(&context) {}
+        LweSamples(LweSamples &&) = default;
+        LweSamples &operator=(LweSamples &&) = default;
+        std::size_t size() const { return n_; } // samples
+        std::size_t coeff_modulus_size() const { return k_; }
+        double &scale() { return scale_; }
+        double scale() const { return scale_; }
+        const std::uint64_t *a() const { return a_ ? a_->ptr() : nullptr; } // DEVICE pointers
+        const std::uint64_t *b() const { return b_ ? b_->ptr() : nullptr; }
+        // (Evaluator) fresh blocks for n samples at level k
+        void reset(std::size_t n, std::size_t k)
+        {
+            a_.reset(new Staged(*ctx_, n * k * ctx_->n()));
+            b_.reset(new Staged(*ctx_, n * k));
+            n_ = n;
+            k_ = k;
+        }
+        std::uint64_t *a_out() { return a_->ptr(); }
+        std::uint64_t *b_out() { return b_->ptr(); }
+
+    private:
+        const Context *ctx_;
+        std::unique_ptr<Staged> a_, b_;
+        std::size_t n_ = 0, k_ = 0;
+        double scale_ = 1.0;
+    };
+
     template <class CT>
     class Evaluator
     {
@@ -1010,6 +1043,49 @@ namespace sealhip_host
                                                           elts.data(), raw.data(), std::uint32_t(elts.size()), o.ptr()));
             chk.done();
             scatter(encrypted, o, count, words, destinations);
+        }
+
+        // Ring packing (sealhip_evaluator_extract_lwe / _pack_lwes), on resident ciphertexts. The
+        // reference has no such methods. extract_lwe: the LWE samples of the coefficients `indices` (each below N, any
+        // order, repeats allowed) of a size-2 ciphertext, which is not modified. pack_lwes: n = 2^l samples into one
+        // ciphertext, sample j at coefficient (N / n) j, times n -- times N with `trace`, which also clears every other
+        // coefficient, times 1 with `normalize`; galois_keys holds the elements of sealhip_pack_lwes_galois_elts (an absent
+        // one -> std::invalid_argument("Galois key not present")); the destination gets the samples' level and scale and
+        // the scheme's form, and one deferred transparency slot. BFV needs a STRICT context.
+        void extract_lwe(const DeviceCiphertext &encrypted, const std::vector<std::uint32_t> &indices, LweSamples &destination)
+        {
+            if (encrypted.size() != 2)
+                throw std::invalid_argument("encrypted size must be 2");
+            const std::size_t k = encrypted.coeff_modulus_size();
+            LweSamples next(ctx_);
+            next.reset(indices.size(), k);
+            throw_on(sealhip_evaluator_extract_lwe(ctx_.get(), std::uint32_t(k), encrypted.data(), 1, indices.data(), indices.size(),
+                                                   next.a_out(), next.b_out()));
+            next.scale() = encrypted.scale();
+            destination = std::move(next);
+        }
+        void pack_lwes(const LweSamples &samples, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                       DeviceCiphertext &destination, bool trace = false, bool normalize = false)
+        {
+            if (!samples.a())
+                throw std::invalid_argument("samples are empty");
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (auto &kv : galois_keys)
+                if (kv.second)
+                {
+                    elts.push_back(kv.first);
+                    raw.push_back(kv.second->get());
+                }
+            const std::size_t k = samples.coeff_modulus_size(), words = 2 * k * ctx_.n();
+            Dev o = dev_out(words);
+            Check chk = checked(destination);
+            throw_on(sealhip_evaluator_pack_lwes(ctx_.get(), std::uint32_t(k), samples.a(), samples.b(), samples.size(), 1, elts.data(),
+                                                 raw.data(), std::uint32_t(elts.size()), trace ? 1 : 0, normalize ? 1 : 0, o.ptr()));
+            chk.done();
+            destination.adopt(o.st->release(), words, 2, k);
+            destination.is_ntt_form() = ctx_.scheme() == SEALHIP_SCHEME_CKKS;
+            destination.scale() = samples.scale();
         }
 
         // Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):

@@ -177,6 +177,9 @@ SYMBOLS = {
     "sealhip_evaluator_apply_galois_many": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp],
     "sealhip_evaluator_rotate_vector_many": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp), _u32,
                                              _vp],
+    "sealhip_pack_lwes_galois_elts": [_vp, _sz, _i32, C.POINTER(_u32), _u32, C.POINTER(_u32)],
+    "sealhip_evaluator_extract_lwe": [_vp, _u32, _vp, _sz, C.POINTER(_u32), _sz, _vp, _vp],
+    "sealhip_evaluator_pack_lwes": [_vp, _u32, _vp, _vp, _sz, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _i32, _i32, _vp],
     "sealhip_evaluator_apply_galois_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32, _vp],
     "sealhip_evaluator_rotate_vector_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp),
                                                   _u32, _vp, _u32, _vp],
@@ -651,6 +654,14 @@ class Context:
         return v.value
 
     # -- L2 functions (names of native/src/seal/util/*.h)
+    def pack_lwes_galois_elts(self, n, trace=False):
+        """the Galois elements 2^t + 1 that Evaluator.pack_lwes of n samples needs, ascending (works on host-only contexts)"""
+        count = _u32(0)
+        _check(lib().sealhip_pack_lwes_galois_elts(self.handle, n, 1 if trace else 0, None, 0, C.byref(count)))
+        elts = (_u32 * max(1, count.value))()
+        _check(lib().sealhip_pack_lwes_galois_elts(self.handle, n, 1 if trace else 0, elts, count.value, C.byref(count)))
+        return [int(elts[i]) for i in range(count.value)]
+
     def ntt_negacyclic_harvey_lazy(self, data, count, k, base=BASE_Q):
         _check(lib().sealhip_ntt_negacyclic_harvey_lazy(self.handle, _ptr(data), count, k, base))
 
@@ -1149,6 +1160,22 @@ class Evaluator:
         ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(lib().sealhip_evaluator_rotate_vector_many(self.ctx.handle, k, _ptr(ct), count, sa, len(steps), ea, ka, n_keys,
                                                           _ptr(out)))
+
+    def extract_lwe(self, ct, k, count, indices, lwe_a, lwe_b):
+        """Ring packing (sealhip_evaluator_extract_lwe): the LWE samples of the coefficients `indices`
+        (host integers below N, any order, repeats allowed) of `count` size-2 ciphertexts in the scheme's form.
+        lwe_a: count x len(indices) x k x N, lwe_b: count x len(indices) x k; ct is not modified."""
+        idx = [int(i) for i in indices]
+        _check(lib().sealhip_evaluator_extract_lwe(self.ctx.handle, k, _ptr(ct), count, _u32_array(idx), len(idx), _ptr(lwe_a),
+                                                   _ptr(lwe_b)))
+
+    def pack_lwes(self, lwe_a, lwe_b, k, n, count, galois_keys, out, trace=False, normalize=False):
+        """sealhip_evaluator_pack_lwes: the n = 2^l samples of every item packed into one ciphertext, sample j at coefficient
+        (N / n) j, times n (N with `trace`, which also clears every other coefficient; 1 with `normalize`). galois_keys: dict
+        galois_elt -> KSwitchKeys with the elements of Context.pack_lwes_galois_elts(n, trace). out: count x 2 x k x N."""
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_pack_lwes(self.ctx.handle, k, _ptr(lwe_a), _ptr(lwe_b), n, count, ea, ka, n_keys,
+                                                 1 if trace else 0, 1 if normalize else 0, _ptr(out)))
 
     def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out,
                                _entry="sealhip_evaluator_apply_galois_dot_plain"):

@@ -472,6 +472,61 @@ long sealhip_evaluator_rotate_vector_many(sealhip_context *ctx, uint32_t k, cons
                                           const int32_t *steps, uint32_t n_steps, const uint32_t *galois_elts,
                                           const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys, uint64_t *out);
 
+/* Ring packing: one coefficient of a ciphertext as an LWE sample, and n = 2^l such samples packed into
+   one ciphertext -- PackLWEs and the field trace of Chen, Dai, Kim, Song, "Efficient Homomorphic Conversion Between (Ring)
+   LWE Ciphertexts" (Alg. 2 and 3) in iterative, batched order. The fork has no such method: what defines the words is the
+   restatement over the oracle in tests/ring_pack_ref.py. Every word in and out is a canonical residue; -v is q_r - v, -0 = 0.
+     sample of coefficient j of (c_0, c_1) in coefficient form:  b = c_0[j];  a[i] = c_1[j - i] for i <= j, -c_1[N + j - i]
+       for i > j;  then b + <a, s> = (c_0 + c_1 s)[j] modulo every q_r.  lwe_a[count][n][k][N], lwe_b[count][n][k].
+     embedding of a sample, scaled by w_r:  c_0 = w_r b at coefficient 0;  c_1[0] = w_r a[0], c_1[N - i] = -w_r a[i].
+     pack of n = 2^l samples, W the n embeddings:  for t = 1 .. l, half = 2^(l - t), g = 2^t + 1, and for j < half:
+       E = W[j], O = X^(N / 2^t) W[j + half], W'[j] = (E + O) + apply_galois(E - O, g) (sealhip_evaluator_apply_galois).
+       Coefficient (N / n) j of the result's phase is n w phase_j.
+     trace (optional):  for t = l + 1 .. log N:  W = W + apply_galois(W, 2^t + 1). Then coefficient (N / n) j holds
+       N w phase_j and every other coefficient of the phase is the key switches' noise alone.
+     normalize (optional):  w_r = n^{-1} mod q_r, or N^{-1} mod q_r with the trace; otherwise w_r = 1.
+   Every step is ONE streaming kernel, which forms (E + O) + (sigma_g(E_0 - O_0), 0) and the key switch's target
+   sigma_g(E_1 - O_1) in one pass over the operands, and ONE key switch batched over count * half ciphertexts: n - 1 key
+   switches per item, plus log N - l with the trace. The sums are exact and only reordered: the words are those of the
+   composition above. BFV works in coefficient form and needs a STRICT context (BFV in PARITY mode is E_INVALIDARG, as for
+   apply_galois_many); CKKS works in NTT form: extract transforms a temporary copy back (ct is not modified), pack transforms
+   the embedded c_1 rows forward and merges in NTT form.
+
+   sealhip_pack_lwes_galois_elts: the elements 2^t + 1 the pack of n samples needs, ascending (t = 1 .. l, or 1 .. log N with
+   trace), for sealhip_generate_galois_keys. *n_elts gets their number; elts (HOST, may be NULL to ask for the number alone)
+   gets them when capacity suffices. Works on host-only contexts. Checks: NULL ctx or n_elts -> E_POINTER; n not a power of
+   two in [1, N], elts given with capacity < *n_elts -> E_INVALIDARG.
+
+   sealhip_evaluator_extract_lwe: ct: count x 2 x k x N in the scheme's form, not modified; indices_host: n_idx HOST words,
+   each < N, in any order, repeats allowed; every item yields n_idx samples. Checks, in this order: NULL pointers
+   (indices_host only when n_idx > 0) -> E_POINTER; then, also on host-only contexts, k outside the ciphertext levels, an
+   index >= N, lwe_a not 16-byte aligned, lwe_a or lwe_b overlapping ct or each other -> E_INVALIDARG; then count == 0 or
+   n_idx == 0 -> S_OK, nothing launched; then a host-only context -> COR_E_INVALIDOPERATION. The indices are staged into a
+   pool block: the entry may allocate and is NOT capturable. No transparency flags (the outputs are not ciphertexts).
+
+   sealhip_evaluator_pack_lwes: lwe_a: count x n x k x N, lwe_b: count x n x k, only read; out: count x 2 x k x N in the
+   scheme's form. galois_elts[i] is the element of galois_keys[i] (n_keys of them; keys the pack does not need are ignored).
+   Checks, in this order: NULL pointers (every key of the list) -> E_POINTER; then, also on host-only contexts, k outside the
+   ciphertext levels, n not a power of two in [1, N], BFV in PARITY mode, an even listed element or one >= 2N, a needed
+   element without its key ("Galois key not present"), a needed key with fewer digits than the level, lwe_a or out not
+   16-byte aligned, out overlapping lwe_a or lwe_b -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a
+   host-only context -> COR_E_INVALIDOPERATION. The working set (1.5 n + n / 4 ciphertexts per item) is parked in the lane's
+   arena next to the key switch's and takes at most half of the arena's cap (the key switch plans with the whole cap, so
+   the arena can reach 1.5 times the cap during a pack). A batch that does not fit is walked in chunks of items; one item
+   that does not fit is walked over its samples (the first step embeds and merges {j, j + n/2} for a group of j at a
+   time: the same words); sealhip_debug_chunk_log shows both. When even the first two steps' results of one item
+   (0.875 n ciphertexts) do not fit -> E_OUTOFMEMORY with a message that names both sizes (raise SEALHIP_WORKSPACE_MB or
+   pack fewer samples). With a transparency sink: one flag per output ciphertext, from the last key switch, or from a read pass over
+   out when there is none (n == 1 without trace, the embedding alone). Nothing synchronises; capturable once the Galois
+   tables and the monomial rows are resident (after one call of the same shape). */
+long sealhip_pack_lwes_galois_elts(sealhip_context *ctx, size_t n, int32_t trace, uint32_t *elts, uint32_t capacity,
+                                   uint32_t *n_elts);
+long sealhip_evaluator_extract_lwe(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                   const uint32_t *indices_host, size_t n_idx, uint64_t *lwe_a, uint64_t *lwe_b);
+long sealhip_evaluator_pack_lwes(sealhip_context *ctx, uint32_t k, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t n,
+                                 size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
+                                 uint32_t n_keys, int32_t trace, int32_t normalize, uint64_t *out);
+
 /* Plaintext-weighted sums of rotations ("double hoisting", Bossuat et al.):
        out_s = sum_i W[s][i] * sigma_{g_i}(ct)   for s < n_sums,
    with ONE decomposition of c_1 per ciphertext and ONE mod-down per sum -- what a baby-step/giant-step matrix-vector product
