@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from encrypt_edge_ref import divround_restated
 from support import S, compile_cpp, run_exe
 
 pytestmark = pytest.mark.gpu
@@ -101,35 +102,13 @@ class Setup:
             tool = L.ref_context_rns_tool(C.byref(c), R)
             for j in range(2):
                 if not tool:  # the oracle builds no RNSTool where the level's Bsk base cannot be formed (60-bit primes)
-                    self.divround_restated(big[j], R, ntt)
+                    divround_restated(big[j], self.mods, R, ntt, c)
                 elif ntt:
                     L.ref_divide_and_round_q_last_ntt_inplace(tool, O.ptr(big[j]), c.key_tables, 0)
                 else:
                     L.ref_divide_and_round_q_last_inplace(tool, O.ptr(big[j]))
         ct = np.ascontiguousarray(big[:, :k])
         return self.add_plain(k, ct, plain)
-
-    def divround_restated(self, x, R, ntt):
-        """divide_and_round_q_last_inplace (rns.cpp:731-775) / _ntt_inplace (:777-851) of one R-row polynomial in place,
-        restated line by line from oracle/sealref.c with Python integers and the oracle's transforms"""
-        L, c, n = O.lib(), self.ref.c, self.n
-        q = self.mods
-        ql = q[R - 1]
-        half = ql >> 1
-        last_row = x[R - 1].copy()
-        if ntt:
-            L.ref_ntt_inverse(O.ptr(last_row), C.byref(c.key_tables[R - 1]))
-        last = [(int(v) + half) % ql for v in last_row]
-        for i in range(R - 1):
-            qi = q[i]
-            inv = pow(ql, -1, qi)
-            if not ntt:
-                out = [((int(xv) - ((lv % qi) - half % qi) % qi) % qi) * inv % qi for xv, lv in zip(x[i], last)]
-            else:
-                temp = np.array([(lv % qi if qi < ql else lv) + qi - half % qi for lv in last], dtype=np.uint64)
-                L.ref_ntt_forward_lazy(O.ptr(temp), C.byref(c.key_tables[i]), 0)
-                out = [((int(xv) + 4 * qi - int(tv)) % (1 << 64)) * inv % qi for xv, tv in zip(x[i], temp)]
-            x[i] = np.array(out, dtype=np.uint64)
 
     def expected_sym(self, k, seed, e, plain, save_seed):
         L, c = O.lib(), self.ref.c
