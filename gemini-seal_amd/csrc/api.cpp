@@ -2080,6 +2080,102 @@ long sealhip_evaluator_pack_lwes(sealhip_context *ctx, uint32_t k, const uint64_
     });
 }
 
+/* ------------------------------------------------------------------ oblivious expansion */
+long sealhip_expand_galois_elts(sealhip_context *ctx, size_t n, uint32_t *elts, uint32_t capacity, uint32_t *n_elts)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(n_elts);
+    return guarded([&] {
+        const Engine &h = *ctx->engine;
+        const int l = pack_log_n(h, n); // the steps t = 1 .. l run, with the elements N / 2^(t-1) + 1
+        *n_elts = static_cast<uint32_t>(l);
+        if (!elts)
+            return;
+        if (capacity < static_cast<uint32_t>(l))
+            throw std::invalid_argument("capacity is smaller than the number of Galois elements");
+        for (int t = l; t >= 1; t--) // ascending
+            elts[l - t] = static_cast<uint32_t>(h.n >> (t - 1)) + 1;
+    });
+}
+
+long sealhip_evaluator_expand(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, size_t n,
+                              const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                              int32_t normalize, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(out);
+    REQUIRE_GALOIS_KEYS(n_keys);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        const int l = pack_log_n(h, n);
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument("oblivious expansion of BFV ciphertexts needs a STRICT context");
+        for (uint32_t i = 0; i < n_keys; i++)
+            check_galois_elt(h, galois_elts[i]);
+        std::vector<const KSwitchKey *> keys(static_cast<size_t>(h.logn) + 1, nullptr);
+        for (int t = 1; t <= l; t++)
+        {
+            const uint32_t g = static_cast<uint32_t>(h.n >> (t - 1)) + 1;
+            for (uint32_t i = 0; i < n_keys && !keys[t]; i++)
+                if (galois_elts[i] == g)
+                {
+                    check_key_digits(h, k, galois_keys[i]);
+                    keys[t] = &galois_keys[i]->key;
+                }
+            if (!keys[t])
+                throw std::invalid_argument("Galois key not present");
+        }
+        if (reinterpret_cast<uintptr_t>(ct) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+            throw std::invalid_argument("ct and out must be 16-byte aligned");
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n;
+        const u64 *in = reinterpret_cast<const u64 *>(ct);
+        u64 *o = reinterpret_cast<u64 *>(out);
+        if (words_overlap(o, count * n * 2 * poly, in, count * 2 * poly))
+            throw std::invalid_argument("out must not overlap ct");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, count * n);
+        op_expand(e, static_cast<int>(k), in, l, count, keys.data(), normalize != 0, o, sink);
+    });
+}
+
+long sealhip_evaluator_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *cts, uint32_t n_terms, uint32_t size,
+                                 size_t count, const uint64_t *plain, uint32_t n_sums, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(cts);
+    REQUIRE_PTR(plain);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        // The checks that need no device come first and run on host-only contexts too (the order the header documents).
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        if (size < 2 || size > 16) // SEAL_CIPHERTEXT_SIZE_MIN / _MAX (util/defines.h:56-57), as linear_combination checks
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        if ((n_terms == 0 || n_sums == 0) && count > 0)
+            throw std::invalid_argument("the term list and the sums must not be empty");
+        if (reinterpret_cast<uintptr_t>(cts) % 16 || reinterpret_cast<uintptr_t>(plain) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+            throw std::invalid_argument("cts, plain and out must be 16-byte aligned");
+        const std::size_t poly = static_cast<std::size_t>(k) * h.n, item = static_cast<std::size_t>(size) * poly;
+        const u64 *o = reinterpret_cast<const u64 *>(out), *x = reinterpret_cast<const u64 *>(cts),
+                  *p = reinterpret_cast<const u64 *>(plain);
+        const std::size_t out_words = n_sums * count * item;
+        if (words_overlap(o, out_words, x, count * n_terms * item))
+            throw std::invalid_argument("out must not overlap cts");
+        if (words_overlap(o, out_words, p, static_cast<std::size_t>(n_sums) * n_terms * poly))
+            throw std::invalid_argument("out must not overlap plain");
+        if (count == 0)
+            return;
+        Engine &e = device_engine(ctx);
+        SinkScope sink(e, static_cast<size_t>(n_sums) * count);
+        sink.begin();
+        op_dot_plain(e, static_cast<int>(k), x, n_terms, static_cast<int>(size), count, p, n_sums, reinterpret_cast<u64 *>(out));
+    });
+}
+
 /* ------------------------------------------------------------------ mod-down merged with the rescale */
 long sealhip_evaluator_relinearize_rescale(sealhip_context *ctx, uint32_t k, const uint64_t *ct, uint32_t size,
                                            size_t ct_item_stride, size_t count, const sealhip_kswitch_key *const *relin_keys,

@@ -879,6 +879,38 @@ namespace sealhip
         return d_pack_mono = upload<u64>(*this, owned, pairs.data(), pairs.size());
     }
 
+    const u64 *Engine::expand_monomials()
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (d_expand_mono)
+            return d_expand_mono;
+        if (lane().capturing)
+            throw std::logic_error("the monomial rows of the expansion are not built yet: run the sequence once before capturing");
+        // one-hot rows X^(-2^u) = -X^(N - 2^u), u < logn, one per ciphertext prime, through the forward transform itself, as
+        // pack_monomials builds its rows; then every word gets its Shoup companion on the host
+        const std::size_t kf = static_cast<std::size_t>(k_first), nrows = static_cast<std::size_t>(logn) * kf;
+        std::vector<u64> rows(nrows * n, 0);
+        for (int u = 0; u < logn; u++)
+            for (std::size_t r = 0; r < kf; r++)
+                rows[(u * kf + r) * n + (n - (static_cast<std::size_t>(1) << u))] = key_moduli[r] - 1;
+        SEALHIP_CHECK(hipSetDevice(device));
+        u64 *tmp = nullptr;
+        SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&tmp), sizeof(u64) * rows.size()));
+        std::unique_ptr<u64, void (*)(u64 *)> guard(tmp, [](u64 *p) { (void)hipFree(p); });
+        Lane &l = lane();
+        SEALHIP_CHECK(hipMemcpyAsync(tmp, rows.data(), sizeof(u64) * rows.size(), hipMemcpyHostToDevice, l.stream));
+        check(launch_ntt(*this, tmp, nrows, ct_row_map(k_first, 1, -1), false, kNttCanonical), "ntt(monomials)");
+        SEALHIP_CHECK(hipMemcpyAsync(rows.data(), tmp, sizeof(u64) * rows.size(), hipMemcpyDeviceToHost, l.stream));
+        SEALHIP_CHECK(hipStreamSynchronize(l.stream));
+        std::vector<u64> pairs(2 * rows.size());
+        for (std::size_t i = 0; i < rows.size(); i++)
+        {
+            pairs[2 * i] = rows[i];
+            pairs[2 * i + 1] = shoup(rows[i], key_moduli[(i / n) % kf]);
+        }
+        return d_expand_mono = upload<u64>(*this, owned, pairs.data(), pairs.size());
+    }
+
     void Engine::ckks_tables()
     {
         std::lock_guard<std::mutex> lock(mu);

@@ -397,6 +397,9 @@ namespace sealhip
         // {word, Shoup companion} pairs: [t - 1][k_first][N][2]
         u64 *d_pack_mono = nullptr;
         const u64 *pack_monomials();
+        // oblivious expansion: NTT_r(X^(-2^u)) for u < logn, the same layout: [u][k_first][N][2]
+        u64 *d_expand_mono = nullptr;
+        const u64 *expand_monomials();
         mutable std::mutex mu; // lazily built shared tables (levels, Galois tables, encoder tables, parms_ids)
         // profiler (per lane)
         void prof_begin(const char *tag, double units) const;
@@ -546,6 +549,14 @@ namespace sealhip
     hipError_t launch_lincomb(const Engine &e, const LinTerms &terms, int size, std::size_t x_stride, const u64 *w,
                               std::size_t w_sum_stride, const u64 *constant, int const_mode, u64 *out, std::size_t out_sum_stride,
                               int n_sums, std::size_t count, const RowMap &map, bool add_partial, std::size_t flag_sum_stride);
+    // Sums of ciphertexts against rows of plaintexts, all in NTT form (poly.hip dot_plain_kernel):
+    // out[s] = sum_t x[t] (.) plain[s][t] for s < n_sums <= kLinTile over a group of n_terms <= kLinGroup terms. x points at
+    // term 0 of item 0: terms are size * map.rows * N words apart, items item_stride words. plain points at plaintext (sum 0,
+    // term 0): terms map.rows * N words apart, sums plain_sum_stride words. out, add_partial and the flags are those of
+    // launch_lincomb, out's items size * map.rows * N words apart.
+    hipError_t launch_dot_plain(const Engine &e, const u64 *x, int size, std::size_t item_stride, int n_terms, const u64 *plain,
+                                std::size_t plain_sum_stride, u64 *out, std::size_t out_sum_stride, int n_sums, std::size_t count,
+                                const RowMap &map, bool add_partial, std::size_t flag_sum_stride);
     // The same sums over terms that keep their own level and size (poly.hip lincomb_levels_kernel): a
     // CKKS ciphertext at a higher level holds the rows of a lower one at its own row stride, so term t is read in place as
     // items size[t] * rows[t] * N words apart, polynomials rows[t] * N words apart, rows r < map.rows of polynomials
@@ -730,6 +741,17 @@ namespace sealhip
     hipError_t launch_pack_merge(const Engine &e, const u64 *E, const u64 *B, u64 *out, u64 *target, std::size_t ncts,
                                  const RowMap &map_q, std::uint32_t shift, std::uint32_t ginv, const std::uint32_t *table,
                                  const u64 *mono);
+
+    // One step of the oblivious expansion without its key switch (ringpack.hip): for nsrc sources E
+    // (src_stride words apart) and O = X^(-shift) E: out_even = (E_0 + sigma_g(E_0), E_1), target_even = sigma_g(E_1) and
+    // the same of O. Source x = item * 2^log_grp + j: its even result is ciphertext item * out_item + j of out, its odd one
+    // out_odd ciphertexts behind; the targets likewise with tgt_item and tgt_odd. table null: coefficient form with
+    // ginv = g^{-1} mod 2N; else NTT form with table = T_g and mono = the step's rows of Engine::expand_monomials. w (or null)
+    // and w_shoup: host arrays of map_q.rows words, the factor every loaded word gets. out and target do not overlap E.
+    hipError_t launch_expand_step(const Engine &e, const u64 *E, std::size_t src_stride, std::size_t nsrc, int log_grp, u64 *out,
+                                  std::size_t out_item, std::size_t out_odd, u64 *target, std::size_t tgt_item, std::size_t tgt_odd,
+                                  const RowMap &map_q, std::uint32_t shift, std::uint32_t ginv, const std::uint32_t *table,
+                                  const u64 *mono, const u64 *w, const u64 *w_shoup);
 
     // key switch
     // ext is digit-major: ext + j*ext_digit_stride + item*ext_stride + r*N
@@ -941,6 +963,14 @@ namespace sealhip
                         u64 *lwe_a, u64 *lwe_b);
     void op_pack_lwes(Engine &e, int k, const u64 *lwe_a, const u64 *lwe_b, int l, std::size_t count,
                       const KSwitchKey *const *keys, bool trace, bool normalize, u64 *out, SinkScope &sink);
+    // Oblivious expansion: out[count][n][2][k][N], n = 2^l, from ct[count][2][k][N] (only read) in the
+    // scheme's form; keys[t] is the key of N / 2^(t-1) + 1 for the steps t = 1 .. l. sink: count * n flags.
+    void op_expand(Engine &e, int k, const u64 *ct, int l, std::size_t count, const KSwitchKey *const *keys, bool normalize,
+                   u64 *out, SinkScope &sink);
+    // Sums against plaintext rows: out[n_sums][count][size][k][N] = sum_i cts[count][n_terms][size][k][N]
+    // (.) plain[n_sums][n_terms][k][N], everything in NTT form
+    void op_dot_plain(Engine &e, int k, const u64 *cts, std::size_t n_terms, int size, std::size_t count, const u64 *plain,
+                      std::size_t n_sums, u64 *out);
     // One decomposition of c_1, n_elts rotations: out[n_elts][count][2][k][N], ct is only read.
     // Not the words of n_elts calls of op_apply_galois (the automorphism does not commute with the mod-up).
     void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,

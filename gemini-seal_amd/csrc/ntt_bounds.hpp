@@ -726,6 +726,11 @@ namespace sealhip
         static_assert(lincomb_group_admits(kLinGroupTerms, kDotAccOperandBits), "16 products of 61-bit words fit 128 bits");
         static_assert(lincomb_group_admits(63, kDotAccOperandBits) && !lincomb_group_admits(64, kDotAccOperandBits),
                       "this (conservative) count admits 63 terms at 61 bits: the group of 16 leaves almost a factor four");
+        // The sums against plaintext rows (poly.hip dot_plain_kernel): a group of `terms` products
+        // ciphertext word * plaintext word of canonical residues, then the canonical partial sum, and no constant -- at most
+        // terms 2^(2 bits) + 2^bits, below what lincomb_group_admits bounds. The kernel uses the same group and tile; its
+        // launcher asserts the predicate, and tests/dot_plain_bounds_check.cpp runs the sum on the CPU.
+        static_assert(lincomb_group_admits(kLinGroupTerms, kDotAccOperandBits), "dot_plain_kernel's group of 61-bit words fits 128 bits");
         // The sums over terms at their own level and size (poly.hip lincomb_levels_kernel): the same
         // arithmetic per output word, so the same group and the same predicate. The tile is a constant of its own because the
         // per-term strides add uniform state to a kernel family that must not spill (the register table of section 21).

@@ -33,7 +33,7 @@ namespace sealhip
             // parks scratch at the front of the arena relies on the nested operation seeing the same cap); a lane created
             // later sees what the earlier ones left, so the caps of all threads' lanes cannot add up to more than the device.
             // An operation that parks scratch plans the nested one with the whole cap: the arena then exceeds it by the
-            // parked bytes (op_apply_galois: at most 1 GiB; op_pack_lwes: at most half of the cap, 1.5 times in all).
+            // parked bytes (op_apply_galois: at most 1 GiB; op_pack_lwes and op_expand: at most half of the cap, 1.5 times in all).
             Lane &l = e.lane();
             if (l.ws_budget)
                 return l.ws_budget;
@@ -1483,6 +1483,184 @@ namespace sealhip
         if (c < half0)
             log_chunk(e, half0, c);
         log_chunk(e, count, items);
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Oblivious expansion: one ciphertext into n = 2^l, one per coefficient of the phase
+    // ------------------------------------------------------------------------------------------
+    // The working set is item-major, W_t[item][i], i < 2^t: step t reads the m 2^(t-1) ciphertexts of W_(t-1) as one run,
+    // writes source (item, j)'s even result to (item, j) and its odd one to (item, j + 2^(t-1)) of W_t, the key switch's
+    // targets at the same places, and one key switch of all m 2^t targets adds into W_t: E + apply_galois(E, g) and
+    // O + apply_galois(O, g), the exact sums reordered. Step 1 reads the caller's ciphertexts, step l writes the caller's
+    // out. W_1 .. W_(l-1) alternate between two buffers parked at the front of the arena under a raised floor, as
+    // op_pack_lwes parks its own, next to the targets: n / 2 + n / 4 ciphertexts and n target polynomials per item,
+    // at most half of the arena's cap. A batch that does not fit is walked in chunks of items. One item that does not fit
+    // has its LAST step walked in groups of c sources, which needs 2 c target polynomials instead of n (subtrees are
+    // independent: the same words); a group's even and odd results are two runs of out, so it takes two key switches of
+    // c. What must always fit is W_(l-1), W_(l-2) and the targets of step l - 1: n ciphertexts.
+    void op_expand(Engine &e, int k, const u64 *ct, int l, std::size_t count, const KSwitchKey *const *keys, bool normalize,
+                   u64 *out, SinkScope &sink)
+    {
+        LevelTools &lt = e.level(k);
+        const bool ckks = e.scheme == 2;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(k) * N, n = static_cast<std::size_t>(1) << l;
+        if (!l) // a copy (n^{-1} = 1)
+        {
+            check(launch_copy_rows(e, ct, poly, out, poly, 2 * count, k), "copy");
+            sink.read_pass(out, 2, poly, count);
+            log_chunk(e, count, count);
+            return;
+        }
+        // w_r = n^{-1}: the inverse of what the l steps multiply the phase by
+        u64 w[kMaxModuli], w_shoup[kMaxModuli];
+        for (int r = 0; r < k && normalize; r++)
+        {
+            const u64 q = e.key_moduli[static_cast<std::size_t>(r)];
+            if (!invmod(n % q, q, w[r]))
+                throw std::logic_error("expand: the normalisation has no inverse");
+            w_shoup[r] = shoup(w[r], q);
+        }
+        const u64 *mono = ckks ? e.expand_monomials() : nullptr;
+        std::vector<const std::uint32_t *> tables(static_cast<std::size_t>(l) + 1, nullptr);
+        std::vector<std::uint32_t> ginv(static_cast<std::size_t>(l) + 1, 1); // (N / 2^(t-1) + 1)^{-1} mod 2N
+        for (int t = 1; t <= l; t++)
+        {
+            const std::uint32_t g = static_cast<std::uint32_t>(N >> (t - 1)) + 1;
+            if (ckks)
+                tables[static_cast<std::size_t>(t)] = e.galois_table(g);
+            std::uint32_t &inv = ginv[static_cast<std::size_t>(t)];
+            for (int it = 0; it < 5; it++) // every Newton step doubles the correct low bits, from one to 32
+                inv *= 2 - g * inv;
+            inv &= static_cast<std::uint32_t>(2 * N - 1);
+        }
+
+        // one item's buffers in words when the last step takes c sources at a time (c = n / 2: all of them)
+        struct Words
+        {
+            std::size_t big, small, t;
+            std::size_t bytes() const
+            {
+                return (big + small + t) * sizeof(u64);
+            }
+        };
+        const std::size_t half = n / 2;
+        auto words_for = [&](std::size_t c) {
+            return Words{ l >= 2 ? half * 2 * poly : 0, l >= 3 ? (n / 4) * 2 * poly : 0, std::max(l >= 2 ? half : 0, 2 * c) * poly };
+        };
+        const std::size_t cap = workspace_budget_bytes(e) / 2 - 3 * 256;
+        std::size_t c = half, items = count;
+        Words ww = words_for(c);
+        if (ww.bytes() > cap) // one item at a time, its last step in groups
+        {
+            items = 1;
+            do
+                ww = words_for(c /= 2);
+            while (c && ww.bytes() > cap);
+            if (!c)
+                throw HipError(hipErrorOutOfMemory,
+                               ("expand: the smallest working set of one item (" +
+                                std::to_string(words_for(1).bytes()) +
+                                " bytes) does not fit half of the workspace arena (" + std::to_string(cap) +
+                                " bytes): raise SEALHIP_WORKSPACE_MB or expand into fewer ciphertexts per call")
+                                   .c_str());
+        }
+        else
+            items = std::max<std::size_t>(1, std::min(count, cap / ww.bytes()));
+        int log_c = 0;
+        while ((static_cast<std::size_t>(1) << log_c) < c)
+            log_c++;
+        const std::size_t scratch_bytes = pad256(ww.big * items) + pad256(ww.small * items) + pad256(ww.t * items);
+        Lane &lane = e.lane();
+        e.ws_reserve(lane.ws_floor + scratch_bytes + 256);
+        FloorRestore guard(e);
+        guard.raise(scratch_bytes);
+        for (std::size_t off = 0; off < count; off += items)
+        {
+            const std::size_t m = std::min(items, count - off);
+            // size the arena now as the largest nested key switch will ask for, so that it cannot move while the working set
+            // is live, and derive the pointers after it
+            plan_chunk(e, m * std::max(l >= 2 ? half : 0, c < half ? c : n), switch_key_arena(e, k).item_bytes(), KsArena::n_buffers,
+                       false);
+            Carver carve{ static_cast<char *>(guard.parked()) };
+            u64 *bufs[2];
+            bufs[(l - 1) & 1] = carve.take(ww.big * items); // W_(l-1), and every W_t of its parity
+            bufs[l & 1] = carve.take(ww.small * items);
+            u64 *target = carve.take(ww.t * items);
+            u64 *dst_out = out + off * n * 2 * poly;
+            for (int t = 1; t <= l; t++)
+            {
+                const std::size_t cur = static_cast<std::size_t>(1) << (t - 1);
+                const u64 *src = t == 1 ? ct + off * 2 * poly : bufs[(t - 1) & 1];
+                u64 *dst = t == l ? dst_out : bufs[t & 1];
+                const std::size_t ts = static_cast<std::size_t>(t);
+                const u64 *rows = mono ? mono + static_cast<std::size_t>(t - 1) * e.k_first * N * 2 : nullptr;
+                const bool scaled = normalize && t == 1;
+                const KSwitchKey &key = *keys[t];
+                // the key switch of ncts results from `at` on; the last step's carries the flags, one per output ciphertext
+                auto key_switch = [&](std::size_t at, const u64 *tg, std::size_t ncts) {
+                    if (t == l)
+                    {
+                        sink.arm();
+                        lane.tsink_base = guard.base + off * n + at;
+                    }
+                    op_switch_key(e, k, dst + at * 2 * poly, 2 * poly, tg, poly, ncts, key);
+                    lane.tsink_cur = nullptr;
+                };
+                if (t == l && c < half) // (one item) by groups of c sources
+                    for (std::size_t j0 = 0; j0 < half; j0 += c)
+                    {
+                        check(launch_expand_step(e, src + j0 * 2 * poly, 2 * poly, c, log_c, dst + j0 * 2 * poly, n, half, target, 2 * c,
+                                                 c, lt.map_q, static_cast<std::uint32_t>(cur), ginv[ts], tables[ts], rows,
+                                                 scaled ? w : nullptr, scaled ? w_shoup : nullptr),
+                              "expand_step");
+                        key_switch(j0, target, c);
+                        key_switch(half + j0, target + c * poly, c);
+                    }
+                else
+                {
+                    check(launch_expand_step(e, src, 2 * poly, m * cur, t - 1, dst, 2 * cur, cur, target, 2 * cur, cur, lt.map_q,
+                                             static_cast<std::uint32_t>(cur), ginv[ts], tables[ts], rows, scaled ? w : nullptr,
+                                             scaled ? w_shoup : nullptr),
+                          "expand_step");
+                    key_switch(0, target, m * 2 * cur);
+                }
+            }
+        }
+        // (after the key switches' own entries: the last pairs of sealhip_debug_chunk_log)
+        if (c < half)
+            log_chunk(e, half, c);
+        log_chunk(e, count, items);
+    }
+
+    // Sums against plaintext rows. dot_plain_kernel reads the ciphertexts and the plaintexts where they
+    // are and writes the sums where they belong: nothing comes from the arena. Sums go in tiles of kLinTile, terms in groups
+    // of kLinGroup; a later group adds the canonical partial sum in, and the last group notes the transparency flags
+    // (sum-major, as the output is).
+    void op_dot_plain(Engine &e, int k, const u64 *cts, std::size_t n_terms, int size, std::size_t count, const u64 *plain,
+                      std::size_t n_sums, u64 *out)
+    {
+        if (k > e.k_first)
+            throw std::invalid_argument("the sum against plaintexts needs a ciphertext level");
+        if (n_terms == 0 || n_sums == 0 || size < 2)
+            throw std::invalid_argument("an empty sum against plaintexts");
+        LevelTools &lt = e.level(k);
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n, item = static_cast<std::size_t>(size) * poly;
+        if (n_terms > static_cast<std::size_t>(kLinGroup))
+            log_chunk(e, n_terms, kLinGroup); // (the term split, ahead of the operation's item chunks: sealhip_debug_chunk_log)
+        for_chunks(e, count, 0, 0, [&](std::size_t off, std::size_t m) {
+            for (std::size_t s0 = 0; s0 < n_sums; s0 += kLinTile)
+                for (std::size_t g0 = 0; g0 < n_terms; g0 += kLinGroup)
+                {
+                    const bool last = g0 + kLinGroup >= n_terms; // (only the last group's stores are the result's words)
+                    SinkArm arm(e, last ? sink_at(e, s0 * count + off) : nullptr);
+                    check(launch_dot_plain(e, cts + (off * n_terms + g0) * item, size, n_terms * item,
+                                           static_cast<int>(std::min<std::size_t>(kLinGroup, n_terms - g0)),
+                                           plain + (s0 * n_terms + g0) * poly, n_terms * poly, out + (s0 * count + off) * item,
+                                           count * item, static_cast<int>(std::min<std::size_t>(kLinTile, n_sums - s0)), m,
+                                           lt.map_q, g0 > 0, count),
+                          "dot_plain");
+                }
+        });
     }
 
     // ------------------------------------------------------------------------------------------

@@ -340,6 +340,86 @@ namespace sealhip
             }
         }
 
+        // Sums of ciphertexts against rows of plaintexts: out_s = sum over the group's terms of
+        // x_t (.) P[s][t] for the S sums of a tile, everything in NTT form, so the weight of a word is the plaintext's word at
+        // the same row and slot. The shape is lincomb_lane's: each operand pair is loaded ONCE per tile and accumulated into
+        // every sum as plain 128-bit integers (lincomb_group_admits covers it: the same products and the partial sum, no
+        // constant), one reduction per output word, the next term's operand load issued before the current term is
+        // accumulated. Term t of item c is at x + c * item_stride + t * term_stride, plaintext (s, t) at
+        // pl + s * plain_sum_stride + t * plain_words.
+        template <int S>
+        __device__ __forceinline__ void dot_plain_lane(const u64 *__restrict__ x, std::size_t term_stride, int n,
+                                                       const u64 *__restrict__ pl, std::size_t plain_words,
+                                                       std::size_t plain_sum_stride, u64 p, u64 cr0, u64 cr1, u64 *po,
+                                                       std::size_t out_sum_stride, int add_partial, unsigned *tflags,
+                                                       std::size_t flag_sum_stride, std::size_t item)
+        {
+            u64 lo[S][2] = {}, hi[S][2] = {};
+            ulonglong2 next = *reinterpret_cast<const ulonglong2 *>(x);
+            for (int t = 0; t < n; t++)
+            {
+                const ulonglong2 v = next;
+                if (t + 1 < n)
+                    next = *reinterpret_cast<const ulonglong2 *>(x + static_cast<std::size_t>(t + 1) * term_stride);
+                const u64 *pt = pl + static_cast<std::size_t>(t) * plain_words;
+#pragma unroll
+                for (int s = 0; s < S; s++)
+                {
+                    const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(pt + s * plain_sum_stride);
+                    mac128(lo[s][0], hi[s][0], v.x, w.x);
+                    mac128(lo[s][1], hi[s][1], v.y, w.y);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < S; s++)
+            {
+                u64 *ps = po + s * out_sum_stride;
+                if (add_partial)
+                {
+                    const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(ps);
+                    dot_add_word(lo[s][0], hi[s][0], q.x), dot_add_word(lo[s][1], hi[s][1], q.y);
+                }
+                ulonglong2 c;
+                c.x = barrett_reduce_128(lo[s][0], hi[s][0], p, cr0, cr1);
+                c.y = barrett_reduce_128(lo[s][1], hi[s][1], p, cr0, cr1);
+                *reinterpret_cast<ulonglong2 *>(ps) = c;
+                if (tflags != nullptr)
+                    note_nonzero(tflags + s * flag_sum_stride, item, c.x | c.y);
+            }
+        }
+        // One lane per coefficient pair of one row of one polynomial of one item; as in lincomb_kernel, a block that cannot
+        // straddle rows (N >= 2 kThreads) derives the row from its first pair, which keeps the prime's constants scalar.
+        template <int S>
+        __global__ __launch_bounds__(kThreads) void dot_plain_kernel(const u64 *__restrict__ x, std::size_t term_stride,
+                                                                     std::size_t item_stride, int n, const u64 *__restrict__ plain,
+                                                                     std::size_t plain_sum_stride, u64 *out,
+                                                                     std::size_t out_sum_stride, const PrimeDev *__restrict__ primes,
+                                                                     RowMap map, int logn, std::size_t npairs_per_item,
+                                                                     std::size_t count, unsigned *tflags,
+                                                                     std::size_t flag_sum_stride, int add_partial)
+        {
+            const std::size_t total = npairs_per_item * count;
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t nmask = (static_cast<std::size_t>(1) << logn) - 1;
+            const std::size_t k = static_cast<std::size_t>(map.rows);
+            const bool block_in_row = (static_cast<std::size_t>(1) << logn) >= 2 * static_cast<std::size_t>(kThreads);
+            for (std::size_t base = blockIdx.x * static_cast<std::size_t>(blockDim.x); base < total; base += stride)
+            {
+                const std::size_t i = base + threadIdx.x;
+                if (i >= total)
+                    continue;
+                // (uniform where the block lies in one row: what the block's first pair says)
+                const std::size_t item = (block_in_row ? base : i) / npairs_per_item;
+                const std::size_t row = (2 * ((block_in_row ? base : i) - item * npairs_per_item)) >> logn;
+                const std::size_t r = row % k;
+                const unsigned short pid = map.prime[r];
+                const std::size_t off = 2 * (i - item * npairs_per_item); // word offset inside the ciphertext
+                dot_plain_lane<S>(x + item * item_stride + off, term_stride, n, plain + (r << logn) + (off & nmask), k << logn,
+                                  plain_sum_stride, primes[pid].p, primes[pid].cr0, primes[pid].cr1, out + item * term_stride + off,
+                                  out_sum_stride, add_partial, row < k ? nullptr : tflags, flag_sum_stride, item);
+            }
+        }
+
         // The same sums over terms at their own level and size: a CKKS mod_switch_to_next only drops the
         // last row, so a term at level rows[t] >= k holds the level-k ciphertext in place at its own row stride, and a term of
         // size[t] polynomials is the size-`size` ciphertext whose further polynomials are zero. Term t's word for (item, j, r)
@@ -890,6 +970,32 @@ namespace sealhip
             lincomb_kernel<decltype(s)::value><<<grid, kThreads, 0, e.lane().stream>>>(
                 terms, x_stride, w, w_sum_stride, constant, const_mode, out, out_sum_stride, e.d_primes, map, e.logn, pairs, count,
                 e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
+        });
+        return hipGetLastError();
+    }
+
+    hipError_t launch_dot_plain(const Engine &e, const u64 *x, int size, std::size_t item_stride, int n_terms, const u64 *plain,
+                                std::size_t plain_sum_stride, u64 *out, std::size_t out_sum_stride, int n_sums, std::size_t count,
+                                const RowMap &map, bool add_partial, std::size_t flag_sum_stride)
+    {
+        // the products and the partial sum of lincomb_kernel, without its constant: the same predicate admits the group
+        static_assert(bounds::lincomb_group_admits(kLinGroup, bounds::kDotAccOperandBits), "a group's sums fit 128 bits");
+        if (n_terms < 1 || n_terms > kLinGroup || n_sums < 1 || n_sums > kLinTile || size < 1 || map.rows < 1 ||
+            map.rows > kMaxRows)
+            return hipErrorInvalidValue;
+        for (int r = 0; r < map.rows; r++)
+            if (map.prime[r] == kSkipRow)
+                return hipErrorInvalidValue;
+        const std::size_t term_stride = static_cast<std::size_t>(size) * map.rows << e.logn;
+        const std::size_t pairs = term_stride / 2;
+        if (pairs * count == 0)
+            return hipSuccess;
+        ProfScope prof(e, "dot_plain", 0);
+        const unsigned grid = grid_for(pairs * count);
+        dispatch_int<1, kLinTile>(n_sums, [&](auto s) {
+            dot_plain_kernel<decltype(s)::value><<<grid, kThreads, 0, e.lane().stream>>>(
+                x, term_stride, item_stride, n_terms, plain, plain_sum_stride, out, out_sum_stride, e.d_primes, map, e.logn, pairs,
+                count, e.lane().tsink_arm, flag_sum_stride, add_partial ? 1 : 0);
         });
         return hipGetLastError();
     }

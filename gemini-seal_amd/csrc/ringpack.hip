@@ -1,6 +1,8 @@
 // ringpack.hip -- ring packing: the LWE sample of one coefficient of a ciphertext, its embedding
 // back into the ring, and the merge step of PackLWEs / the field trace (Chen, Dai, Kim, Song, "Efficient Homomorphic
-// Conversion Between (Ring) LWE Ciphertexts", Alg. 2 and 3) fused around the key switch. The fork has no such method.
+// Conversion Between (Ring) LWE Ciphertexts", Alg. 2 and 3) fused around the key switch; and the other direction, the step
+// of the oblivious expansion of one ciphertext into n (the Expand of Angel, Chen, Laine, Setty, "PIR
+// with compressed queries and amortized query processing", Fig. 3), fused the same way. The fork has no such method.
 // All of these are HBM streaming in the style of poly.hip: two coefficients per lane, every store 16 bytes wide and
 // coalesced, every permutation (the reversed read of a sample, the monomial shift, the automorphism) on the load side.
 #include "engine.hpp"
@@ -255,6 +257,158 @@ namespace sealhip
                 pack_merge_kernel<decltype(ntt)::value ? 1 : 0, decltype(odd)::value>
                     <<<grid_for(npairs), kThreads, 0, e.lane().stream>>>(E, B, out, target, e.d_primes, map_q, e.logn, npairs, shift,
                                                                          ginv, table, reinterpret_cast<const ulonglong2 *>(mono));
+            });
+        });
+        return hipGetLastError();
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Oblivious expansion: one step of the tree, fused around the key switch
+    // ------------------------------------------------------------------------------------------
+    namespace
+    {
+        struct NoWeights // what an unscaled step carries for the normalisation: nothing
+        {
+        };
+        // a loaded word, times w_r where the step normalises (SCALED: step 1 alone)
+        template <bool SCALED, class W>
+        __device__ __forceinline__ u64 expand_word(u64 v, const W &wt, std::size_t r, u64 p)
+        {
+            if constexpr (SCALED)
+                return mulmod_shoup(v, wt.w[r], wt.ws[r], p);
+            else
+                return v;
+        }
+
+        // (X^(-s) E)[x] in coefficient form: E[x + s], with the sign of the wrap
+        __device__ __forceinline__ u64 shifted_down(const u64 *__restrict__ e, std::size_t x, std::size_t s, std::size_t N, u64 p)
+        {
+            return neg_if(x + s >= N, e[(x + s) & (N - 1)], p);
+        }
+
+        // One step of the expansion without its key switch: with O = X^(-s) E,
+        //     out_even = (E_0 + sigma_g(E_0), E_1),  target_even = sigma_g(E_1),
+        //     out_odd  = (O_0 + sigma_g(O_0), O_1),  target_odd  = sigma_g(O_1),
+        // so that out + key_switch(target) is E + apply_galois(E, g) and O + apply_galois(O, g). Source x is [2][k][N] at
+        // x * src_stride words; with x = item * 2^log_grp + j its even result is ciphertext item * out_item + j of out and
+        // its odd one out_odd ciphertexts behind it; the targets ([k][N] each) likewise with tgt_item and tgt_odd. One lane
+        // per pair of output coefficients of one row of one source; every permutation is on the load side.
+        // FORM 0, coefficient form: coefficient c of sigma_g(D) is +-D[c g^{-1} mod 2N] (ginv = g^{-1} mod 2N).
+        // FORM 1, NTT form: O = M (.) E with M = NTT(X^(-s)) as {word, Shoup companion} pairs, sigma_g(D)[c] = D[T[c]].
+        // SCALED: every loaded word of E is multiplied by w_r first (the normalisation, which step 1 applies).
+        template <int FORM, bool SCALED>
+        __global__ __launch_bounds__(kThreads) void expand_step_kernel(
+            const u64 *__restrict__ E, std::size_t src_stride, u64 *__restrict__ out, u64 *__restrict__ target,
+            const PrimeDev *__restrict__ primes, RowMap map, int logn, std::size_t npairs, int log_grp, std::size_t out_item,
+            std::size_t out_odd, std::size_t tgt_item, std::size_t tgt_odd, std::uint32_t shift, std::uint32_t ginv,
+            const std::uint32_t *__restrict__ table, const ulonglong2 *__restrict__ mono,
+            std::conditional_t<SCALED, PackWeights, NoWeights> wt)
+        {
+            const std::size_t stride = static_cast<std::size_t>(gridDim.x) * blockDim.x;
+            const std::size_t N = static_cast<std::size_t>(1) << logn, nmask = N - 1;
+            const std::size_t k = static_cast<std::size_t>(map.rows);
+            const std::size_t poly = k << logn;
+            for (std::size_t t = blockIdx.x * static_cast<std::size_t>(blockDim.x) + threadIdx.x; t < npairs; t += stride)
+            {
+                const std::size_t word = 2 * t;
+                const std::size_t c = word & nmask;
+                const std::size_t row = word >> logn; // x * k + r; below 2^32 (the launcher): a 32-bit division
+                const unsigned row32 = static_cast<unsigned>(row), x32 = row32 / static_cast<unsigned>(k);
+                const std::size_t x = x32, r = row32 - x32 * static_cast<unsigned>(k);
+                const std::size_t item = x >> log_grp, j = x - (item << log_grp);
+                const unsigned short pid = map.prime[r];
+                const u64 p = primes[pid].p;
+                const u64 *e0 = E + x * src_stride + (r << logn), *e1 = e0 + poly;
+                const ulonglong2 ve0 = *reinterpret_cast<const ulonglong2 *>(e0 + c);
+                const ulonglong2 ve1 = *reinterpret_cast<const ulonglong2 *>(e1 + c);
+                const u64 s0[2] = { expand_word<SCALED>(ve0.x, wt, r, p), expand_word<SCALED>(ve0.y, wt, r, p) };
+                const u64 s1[2] = { expand_word<SCALED>(ve1.x, wt, r, p), expand_word<SCALED>(ve1.y, wt, r, p) };
+                u64 ev0[2], ev1[2], evt[2], od0[2], od1[2], odt[2];
+                if (FORM == 0)
+                {
+#pragma unroll
+                    for (int h = 0; h < 2; h++)
+                    {
+                        const std::size_t cc = c + h;
+                        const std::size_t u = (cc * ginv) & (2 * N - 1), i = u & nmask;
+                        const bool neg = u >= N;
+                        const u64 d0 = expand_word<SCALED>(e0[i], wt, r, p), d1 = expand_word<SCALED>(e1[i], wt, r, p);
+                        ev0[h] = add_mod(s0[h], neg_if(neg, d0, p), p);
+                        ev1[h] = s1[h];
+                        evt[h] = neg_if(neg, d1, p);
+                        const u64 q0 = expand_word<SCALED>(shifted_down(e0, cc, shift, N, p), wt, r, p);
+                        const u64 q1 = expand_word<SCALED>(shifted_down(e1, cc, shift, N, p), wt, r, p);
+                        const u64 g0 = expand_word<SCALED>(shifted_down(e0, i, shift, N, p), wt, r, p);
+                        const u64 g1 = expand_word<SCALED>(shifted_down(e1, i, shift, N, p), wt, r, p);
+                        od0[h] = add_mod(q0, neg_if(neg, g0, p), p);
+                        od1[h] = q1;
+                        odt[h] = neg_if(neg, g1, p);
+                    }
+                }
+                else
+                {
+                    const uint2 tt = *reinterpret_cast<const uint2 *>(table + c);
+                    const std::size_t ti[2] = { tt.x, tt.y };
+                    const ulonglong2 *m = mono + (static_cast<std::size_t>(pid) << logn);
+#pragma unroll
+                    for (int h = 0; h < 2; h++)
+                    {
+                        const std::size_t i = ti[h];
+                        const ulonglong2 mc = m[c + h], mi = m[i];
+                        const u64 d0 = expand_word<SCALED>(e0[i], wt, r, p), d1 = expand_word<SCALED>(e1[i], wt, r, p);
+                        ev0[h] = add_mod(s0[h], d0, p);
+                        ev1[h] = s1[h];
+                        evt[h] = d1;
+                        od0[h] = add_mod(mulmod_shoup(s0[h], mc.x, mc.y, p), mulmod_shoup(d0, mi.x, mi.y, p), p);
+                        od1[h] = mulmod_shoup(s1[h], mc.x, mc.y, p);
+                        odt[h] = mulmod_shoup(d1, mi.x, mi.y, p);
+                    }
+                }
+                const std::size_t at = (r << logn) + c;
+                u64 *po = out + (item * out_item + j) * 2 * poly + at;
+                store_stream2(po, ev0[0], ev0[1]);
+                store_stream2(po + poly, ev1[0], ev1[1]);
+                store_stream2(po + out_odd * 2 * poly, od0[0], od0[1]);
+                store_stream2(po + out_odd * 2 * poly + poly, od1[0], od1[1]);
+                u64 *pt = target + (item * tgt_item + j) * poly + at;
+                store_stream2(pt, evt[0], evt[1]);
+                store_stream2(pt + tgt_odd * poly, odt[0], odt[1]);
+            }
+        }
+    } // namespace
+
+    hipError_t launch_expand_step(const Engine &e, const u64 *E, std::size_t src_stride, std::size_t nsrc, int log_grp, u64 *out,
+                                  std::size_t out_item, std::size_t out_odd, u64 *target, std::size_t tgt_item, std::size_t tgt_odd,
+                                  const RowMap &map_q, std::uint32_t shift, std::uint32_t ginv, const std::uint32_t *table,
+                                  const u64 *mono, const u64 *w, const u64 *w_shoup)
+    {
+        if (map_q.rows < 1 || map_q.rows > kMaxModuli)
+            return hipErrorInvalidValue;
+        const std::size_t npairs = (nsrc * static_cast<std::size_t>(map_q.rows) << e.logn) / 2;
+        if (!npairs)
+            return hipSuccess;
+        // (a group's results must not reach into the odd half or the next item; the NTT form needs its rows)
+        const std::size_t grp = static_cast<std::size_t>(1) << log_grp;
+        if (rows_exceed_32_bits(e, npairs) || log_grp < 0 || shift < 1 || shift >= e.n || out_odd < grp || tgt_odd < grp ||
+            (nsrc > grp && (out_item < out_odd + grp || tgt_item < tgt_odd + grp)) || (table != nullptr) != (mono != nullptr) ||
+            (w != nullptr) != (w_shoup != nullptr))
+            return hipErrorInvalidValue;
+        ProfScope prof(e, "expand_step", 0);
+        const unsigned grid = grid_for(npairs);
+        dispatch_bool(table != nullptr, [&](auto ntt) {
+            dispatch_bool(w != nullptr, [&](auto scaled) {
+                constexpr int form = decltype(ntt)::value ? 1 : 0;
+                constexpr bool sc = decltype(scaled)::value;
+                std::conditional_t<sc, PackWeights, NoWeights> wt{};
+                if constexpr (sc)
+                    for (int r = 0; r < map_q.rows; r++)
+                    {
+                        wt.w[r] = w[r];
+                        wt.ws[r] = w_shoup[r];
+                    }
+                expand_step_kernel<form, sc><<<grid, kThreads, 0, e.lane().stream>>>(
+                    E, src_stride, out, target, e.d_primes, map_q, e.logn, npairs, log_grp, out_item, out_odd, tgt_item, tgt_odd,
+                    shift, ginv, table, reinterpret_cast<const ulonglong2 *>(mono), wt);
             });
         });
         return hipGetLastError();

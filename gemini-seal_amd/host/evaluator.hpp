@@ -1088,6 +1088,99 @@ namespace sealhip_host
             destination.scale() = samples.scale();
         }
 
+        // Oblivious expansion (sealhip_evaluator_expand): `encrypted`, whose phase carries n = 2^l values
+        // in its first n coefficients, into n ciphertexts; destinations[i] holds n times coefficient i of the phase as its
+        // constant coefficient (1 times with `normalize`), with the operand's level, scale and form (and, for a host type,
+        // its parms_id). galois_keys holds the elements of sealhip_expand_galois_elts (an absent one ->
+        // std::invalid_argument("Galois key not present")). The reference has no such method. BFV needs a STRICT context.
+        // One block from the ABI, then one pool block and one deferred transparency slot per result, as apply_galois_many's:
+        // a resident call takes at most 256 results (std::invalid_argument("too many results for one checked operation")).
+        template <class C, IfCt<C> = 0>
+        void expand(const C &encrypted, std::size_t n, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
+                    std::vector<C> &destinations, bool normalize = false)
+        {
+            check_galois_operand(encrypted);
+            if (n == 0)
+                throw std::invalid_argument("n must be a power of two between 1 and N");
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (auto &kv : galois_keys)
+                if (kv.second)
+                {
+                    elts.push_back(kv.first);
+                    raw.push_back(kv.second->get());
+                }
+            const std::size_t k = encrypted.coeff_modulus_size(), words = 2 * k * ctx_.n();
+            Dev c = dev_in(encrypted, words), o = dev_out(n * words);
+            Check chk = checked(encrypted, n);
+            throw_on(sealhip_evaluator_expand(ctx_.get(), std::uint32_t(k), c.ptr(), 1, n, elts.data(), raw.data(),
+                                              std::uint32_t(elts.size()), normalize ? 1 : 0, o.ptr()));
+            chk.done();
+            scatter(encrypted, o, n, words, destinations);
+        }
+
+        // Sums against plaintext rows (sealhip_evaluator_dot_plain) on resident operands:
+        // destinations[s] = sum_i terms[i] (.) plains[s][i], everything in NTT form at one level: the ciphertexts of one size
+        // and (CKKS) one scale, the plaintexts k x N words in NTT form and (CKKS) of one scale. Each result has the terms'
+        // size, level and form and, for CKKS, the scale terms[0].scale() * plains[0][0].scale(). The ABI reads the terms and
+        // the plaintexts from one block each: they are gathered on the device (stream-ordered copies). One pool block and
+        // one deferred transparency slot per sum. std::invalid_argument: no terms or no sums, terms that differ in size,
+        // level or scale or are not in NTT form, a ragged plaintext matrix, a plaintext of another level, form or scale.
+        void dot_plain(const std::vector<DeviceCiphertext> &terms, const std::vector<std::vector<const DevicePlaintext *>> &plains,
+                       std::vector<DeviceCiphertext> &destinations)
+        {
+            if (terms.empty() || plains.empty())
+                throw std::invalid_argument("the term list and the sums must not be empty");
+            const bool ckks = ctx_.scheme() == SEALHIP_SCHEME_CKKS;
+            const std::size_t size = terms[0].size(), k = terms[0].coeff_modulus_size(), n = ctx_.n();
+            const std::size_t pw = k * n, words = size * pw, n_terms = terms.size(), n_sums = plains.size();
+            for (const DeviceCiphertext &t : terms)
+            {
+                if (!t.is_ntt_form())
+                    throw std::invalid_argument("encrypted must be in NTT form");
+                if (t.size() != size || t.coeff_modulus_size() != k || t.size() < 2)
+                    throw std::invalid_argument("encrypted parameter mismatch");
+                if (ckks && t.scale() != terms[0].scale())
+                    throw std::invalid_argument("scale mismatch");
+            }
+            for (const auto &row : plains)
+            {
+                if (row.size() != n_terms)
+                    throw std::invalid_argument("plains must hold one plaintext per term in every sum");
+                for (const DevicePlaintext *p : row)
+                {
+                    if (!p || !p->is_ntt_form() || p->coeff_modulus_size() != k || p->words() != pw)
+                        throw std::invalid_argument("plain must be in NTT form at the terms' level");
+                    if (ckks && p->scale() != plains[0][0]->scale())
+                        throw std::invalid_argument("scale mismatch");
+                }
+            }
+            Staged x(ctx_, n_terms * words), w(ctx_, n_sums * n_terms * pw);
+            for (std::size_t i = 0; i < n_terms; i++)
+                throw_on(sealhip_memcpy_d2d(ctx_.get(), x.ptr() + i * words, terms[i].data(), words * 8));
+            for (std::size_t s = 0; s < n_sums; s++)
+                for (std::size_t i = 0; i < n_terms; i++)
+                    plain_to(*plains[s][i], w.ptr() + (s * n_terms + i) * pw, pw);
+            Dev o = dev_out(n_sums * words);
+            Check chk = checked(terms[0], n_sums);
+            throw_on(sealhip_evaluator_dot_plain(ctx_.get(), std::uint32_t(k), x.ptr(), std::uint32_t(n_terms), std::uint32_t(size), 1,
+                                                 w.ptr(), std::uint32_t(n_sums), o.ptr()));
+            chk.done();
+            std::vector<DeviceCiphertext> next;
+            next.reserve(n_sums);
+            for (std::size_t s = 0; s < n_sums; s++)
+            {
+                next.emplace_back(ctx_);
+                Staged one(ctx_, words); // (each destination owns a pool block of its own)
+                throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), o.ptr() + s * words, words * 8));
+                next[s].adopt(one.release(), words, size, k);
+                next[s].copy_meta(terms[0]);
+                if (ckks)
+                    next[s].scale() = terms[0].scale() * plains[0][0]->scale();
+            }
+            destinations.swap(next);
+        }
+
         // Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):
         // destinations[s] = sum_i plains[s][i] * sigma_{galois_elts[i]}(encrypted), with one decomposition of the operand's
         // second polynomial and one mod-down per sum. plains[s][i] is a plaintext in KEY-LEVEL NTT form (n_key x N words:

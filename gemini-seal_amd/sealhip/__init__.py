@@ -180,6 +180,9 @@ SYMBOLS = {
     "sealhip_pack_lwes_galois_elts": [_vp, _sz, _i32, C.POINTER(_u32), _u32, C.POINTER(_u32)],
     "sealhip_evaluator_extract_lwe": [_vp, _u32, _vp, _sz, C.POINTER(_u32), _sz, _vp, _vp],
     "sealhip_evaluator_pack_lwes": [_vp, _u32, _vp, _vp, _sz, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _i32, _i32, _vp],
+    "sealhip_expand_galois_elts": [_vp, _sz, C.POINTER(_u32), _u32, C.POINTER(_u32)],
+    "sealhip_evaluator_expand": [_vp, _u32, _vp, _sz, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _i32, _vp],
+    "sealhip_evaluator_dot_plain": [_vp, _u32, _vp, _u32, _u32, _sz, _vp, _u32, _vp],
     "sealhip_evaluator_apply_galois_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, _vp, _u32, _vp],
     "sealhip_evaluator_rotate_vector_dot_plain": [_vp, _u32, _vp, _sz, C.POINTER(_i32), _u32, C.POINTER(_u32), C.POINTER(_vp),
                                                   _u32, _vp, _u32, _vp],
@@ -660,6 +663,15 @@ class Context:
         _check(lib().sealhip_pack_lwes_galois_elts(self.handle, n, 1 if trace else 0, None, 0, C.byref(count)))
         elts = (_u32 * max(1, count.value))()
         _check(lib().sealhip_pack_lwes_galois_elts(self.handle, n, 1 if trace else 0, elts, count.value, C.byref(count)))
+        return [int(elts[i]) for i in range(count.value)]
+
+    def expand_galois_elts(self, n):
+        """the Galois elements N / 2^(t-1) + 1 that Evaluator.expand into n ciphertexts needs, ascending (works on host-only
+        contexts)"""
+        count = _u32(0)
+        _check(lib().sealhip_expand_galois_elts(self.handle, n, None, 0, C.byref(count)))
+        elts = (_u32 * max(1, count.value))()
+        _check(lib().sealhip_expand_galois_elts(self.handle, n, elts, count.value, C.byref(count)))
         return [int(elts[i]) for i in range(count.value)]
 
     def ntt_negacyclic_harvey_lazy(self, data, count, k, base=BASE_Q):
@@ -1176,6 +1188,22 @@ class Evaluator:
         ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(lib().sealhip_evaluator_pack_lwes(self.ctx.handle, k, _ptr(lwe_a), _ptr(lwe_b), n, count, ea, ka, n_keys,
                                                  1 if trace else 0, 1 if normalize else 0, _ptr(out)))
+
+    def expand(self, ct, k, count, n, galois_keys, out, normalize=False):
+        """Oblivious expansion (sealhip_evaluator_expand): every one of `count` size-2 ciphertexts in the
+        scheme's form into n = 2^l, output i holding n times coefficient i of the phase (1 times with `normalize`).
+        galois_keys: dict galois_elt -> KSwitchKeys with the elements of Context.expand_galois_elts(n). out: count x n x 2 x
+        k x N; ct is not modified."""
+        ea, ka, n_keys = _galois_arrays(galois_keys)
+        _check(lib().sealhip_evaluator_expand(self.ctx.handle, k, _ptr(ct), count, n, ea, ka, n_keys, 1 if normalize else 0,
+                                              _ptr(out)))
+
+    def dot_plain(self, cts, plain, k, count, n_terms, n_sums, out, size=2):
+        """Sums against plaintext rows (sealhip_evaluator_dot_plain): out[s] = sum_i ct_i (.) P[s][i],
+        everything in NTT form. cts: count x n_terms x size x k x N (the layout expand writes); plain: n_sums x n_terms x k x
+        N; out: n_sums x count x size x k x N."""
+        _check(lib().sealhip_evaluator_dot_plain(self.ctx.handle, k, _ptr(cts), n_terms, size, count, _ptr(plain), n_sums,
+                                                 _ptr(out)))
 
     def apply_galois_dot_plain(self, ct, k, count, elts, keys, plains, n_sums, out,
                                _entry="sealhip_evaluator_apply_galois_dot_plain"):

@@ -527,6 +527,68 @@ long sealhip_evaluator_pack_lwes(sealhip_context *ctx, uint32_t k, const uint64_
                                  size_t count, const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys,
                                  uint32_t n_keys, int32_t trace, int32_t normalize, uint64_t *out);
 
+/* Oblivious expansion: one ciphertext whose phase carries n = 2^l values in its first n coefficients
+   into n ciphertexts, one per coefficient -- the Expand of Angel, Chen, Laine, Setty, "PIR with compressed queries and
+   amortized query processing" (Fig. 3), which is the coefficient extraction tree of Chen, Dai, Kim, Song; the other
+   direction of the ring packing above. The fork has no such method: what defines the words is the restatement over the
+   oracle in tests/expand_ref.py. The ring is Z_q[X]/(X^N + 1), rows are the level's primes q_r, r < k; every word in and
+   out is a canonical residue; -v is q_r - v, -0 = 0.
+     W_0[0] = the input (a size-2 ciphertext), times w_r.  For t = 1 .. l with cur = 2^(t-1), s = cur and
+     g = N / 2^(t-1) + 1 (the elements N + 1, N / 2 + 1, ...), and for j < cur, E = W[j], O = X^(-s) E:
+       W'[j]       = E + apply_galois(E, g)          (sealhip_evaluator_apply_galois)
+       W'[j + cur] = O + apply_galois(O, g).
+     After l steps the phase of output i is n w sum_u m[i + n u] X^(n u), m the input's phase: when the phase lives in the
+     coefficients below n, output i holds the constant n w m[i]. Outputs are in natural order.
+     normalize:  w_r = n^{-1} mod q_r (multiply_poly_scalar_coeffmod on both input polynomials), so that the factor n cancels
+       exactly modulo q, the input's noise is not amplified and BFV decrypts to m[i] itself; otherwise w_r = 1. n = 1 is a copy.
+   Key-switch noise of step t is multiplied by at most n / 2^t by the steps after it. Every step is ONE streaming kernel,
+   which for every source E writes (E_0 + sigma_g(E_0), E_1), (O_0 + sigma_g(O_0), O_1) and the key switch's targets
+   sigma_g(E_1), sigma_g(O_1) in one pass, and ONE key switch batched over all count * 2^t results: the sums are exact and
+   only reordered, so the words are those of the composition above. BFV works in coefficient form and needs a STRICT
+   context; CKKS works in NTT form in both modes (X^(-s) . is a dyadic product with NTT_r(X^(-s)), rows built once per
+   context).
+
+   sealhip_expand_galois_elts: the elements the expansion into n needs, ascending (N / 2^(l-1) + 1 .. N + 1), for
+   sealhip_generate_galois_keys. *n_elts gets their number; elts (HOST, may be NULL to ask for the number alone) gets them
+   when capacity suffices. Works on host-only contexts. Checks: NULL ctx or n_elts -> E_POINTER; n not a power of two in
+   [1, N], elts given with capacity < *n_elts -> E_INVALIDARG.
+
+   sealhip_evaluator_expand: ct: count x 2 x k x N in the scheme's form, only read; out: count x n x 2 x k x N.
+   galois_elts[i] is the element of galois_keys[i] (n_keys of them; keys the expansion does not need are ignored). Checks,
+   in this order: NULL pointers (every key of the list) -> E_POINTER; then, also on host-only contexts, k outside the
+   ciphertext levels, n not a power of two in [1, N], BFV in PARITY mode, an even listed element or one >= 2N, a needed
+   element without its key ("Galois key not present"), a needed key with fewer digits than the level, ct or out not 16-byte
+   aligned, out overlapping ct -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only context ->
+   COR_E_INVALIDOPERATION. The working set (3 n / 4 ciphertexts and n target polynomials per item) is parked in the lane's
+   arena next to the key switch's and takes at most half of the arena's cap, as the pack's does. A batch that does not fit
+   is walked in chunks of items; one item that does not fit has its last step walked in groups of c sources, c the largest
+   power of two that fits (subtrees are independent: the same words); sealhip_debug_chunk_log ends with (count, items per
+   chunk), preceded by (n / 2, c) when the last step was walked. When the results of the two steps before the last and the
+   targets of the step before the last (n ciphertexts in all) do not fit -> E_OUTOFMEMORY with a message that names both
+   sizes. With a transparency sink: one flag per output ciphertext, count * n in output order, from the last key switch, or
+   from a read pass over out when there is none (n == 1). Nothing synchronises; capturable once the Galois tables and the
+   monomial rows are resident (after one call of the same shape).
+
+   sealhip_evaluator_dot_plain: what follows an expansion -- sums of ciphertexts against rows of plaintexts,
+       out[s] = sum_{i < n_terms} ct_i (.) P[s][i]        s < n_sums,
+   everything in NTT form at level k (CKKS: the ciphertexts' form; BFV callers bracket the call with transform_to_ntt and
+   transform_from_ntt). cts: count x n_terms x size x k x N in DEVICE memory (the layout the expansion writes); plain:
+   n_sums x n_terms x k x N in DEVICE memory, shared across the batch; out: n_sums x count x size x k x N, sum-major as for
+   sealhip_evaluator_linear_combination. One streaming kernel in the shape of the linear combination's: every operand word
+   is loaded once per tile of up to 4 sums, accumulated in plain 128-bit integers and reduced once; terms go in groups of 16
+   per launch. Every output word is the canonical residue of the integer sum: word for word multiply_plain_ntt per term and
+   add left to right. Checks, in this order: NULL pointers -> E_POINTER; then, also on host-only contexts, k outside the
+   ciphertext levels, size outside [2, 16], n_terms == 0 or n_sums == 0 with count > 0, cts, plain or out not 16-byte
+   aligned, out overlapping cts or plain -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched; then a host-only
+   context -> COR_E_INVALIDOPERATION. Nothing comes from the arena; nothing synchronises; capturable. With a transparency
+   sink: n_sums * count flags, sum-major, from the kernel that stores the result. */
+long sealhip_expand_galois_elts(sealhip_context *ctx, size_t n, uint32_t *elts, uint32_t capacity, uint32_t *n_elts);
+long sealhip_evaluator_expand(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count, size_t n,
+                              const uint32_t *galois_elts, const sealhip_kswitch_key *const *galois_keys, uint32_t n_keys,
+                              int32_t normalize, uint64_t *out);
+long sealhip_evaluator_dot_plain(sealhip_context *ctx, uint32_t k, const uint64_t *cts, uint32_t n_terms, uint32_t size,
+                                 size_t count, const uint64_t *plain, uint32_t n_sums, uint64_t *out);
+
 /* Plaintext-weighted sums of rotations ("double hoisting", Bossuat et al.):
        out_s = sum_i W[s][i] * sigma_{g_i}(ct)   for s < n_sums,
    with ONE decomposition of c_1 per ciphertext and ONE mod-down per sum -- what a baby-step/giant-step matrix-vector product
