@@ -52,6 +52,10 @@ struct sealhip_kswitch_key
 {
     KSwitchKey key;
 };
+struct sealhip_rgsw
+{
+    RgswKey key;
+};
 struct sealhip_graph
 {
     hipGraph_t graph = nullptr;
@@ -4377,6 +4381,287 @@ long sealhip_generate_switching_keys(sealhip_context *ctx, const uint64_t *sk_to
                                      int32_t keep_seeds, sealhip_kswitch_key **keys)
 {
     return generate_keys(ctx, sk_to_ntt, nullptr, false, n_keys, seeds_host, noise, keep_seeds, keys, true, sk_from_ntt, level);
+}
+
+/* ---------------------------------------------------------------- RGSW */
+extern "C++" {
+namespace
+{
+    // an empty block for a context's digit count; the caller fills it on its lane and synchronises before it hands it out
+    std::unique_ptr<sealhip_rgsw> rgsw_alloc(const Engine &e, uint32_t n_digits, uint32_t level)
+    {
+        auto g = std::make_unique<sealhip_rgsw>();
+        g->key.n_digits = n_digits;
+        g->key.half_words = static_cast<std::size_t>(n_digits) * 2 * e.n_key * e.n;
+        g->key.level = level;
+        SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&g->key.d_data), 2 * g->key.half_words * sizeof(u64)));
+        return g;
+    }
+    // a stream-ordered device copy that is complete (or has thrown) on return
+    void copy_words_sync(Engine &e, u64 *dst, const u64 *src, std::size_t words)
+    {
+        hipError_t err = hipMemcpyAsync(dst, src, words * sizeof(u64), hipMemcpyDeviceToDevice, e.lane().stream);
+        if (err == hipSuccess)
+            err = hipStreamSynchronize(e.lane().stream);
+        if (err != hipSuccess)
+            throw HipError(err, hipGetErrorString(err));
+    }
+
+    // The checks the three evaluator entries share, in the header's order, up to the handle. ins: the operands the result
+    // must not overlap, each of in_words words (NULL entries are skipped). Returns the engine once a device is known.
+    Engine &rgsw_entry_checks(sealhip_context *ctx, uint32_t k, const char *what, std::initializer_list<const uint64_t *> ins,
+                              std::size_t in_words, const uint64_t *out, std::size_t out_words)
+    {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument(std::string(what) + " of BFV ciphertexts needs a STRICT context");
+        for (const uint64_t *p : ins)
+            if (reinterpret_cast<uintptr_t>(p) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+                throw std::invalid_argument("the operands and out must be 16-byte aligned");
+        for (const uint64_t *p : ins)
+            if (p && words_overlap(reinterpret_cast<const u64 *>(out), out_words, reinterpret_cast<const u64 *>(p), in_words))
+                throw std::invalid_argument("out must not overlap an operand");
+        return device_engine(ctx);
+    }
+    void check_rgsw_level(const Engine &e, uint32_t k, const sealhip_rgsw *g)
+    {
+        if (g->key.n_digits < kswitch_digits(e, k) || (g->key.level && k > g->key.level))
+            throw std::invalid_argument("rgsw is not valid for encryption parameters");
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_generate_rgsw(sealhip_context *ctx, const uint64_t *sk_ntt, const int32_t *m_coeff, uint32_t n, uint32_t level,
+                           const uint64_t *seeds_host, const int32_t *noise, sealhip_rgsw **out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(sk_ntt);
+    if (n)
+    {
+        REQUIRE_PTR(m_coeff);
+        REQUIRE_PTR(seeds_host);
+        REQUIRE_PTR(noise);
+        REQUIRE_PTR(out);
+        std::fill(out, out + n, nullptr);
+    }
+    return guarded([&] {
+        check_data_level(*ctx->engine, level);
+        Engine &e = device_engine(ctx);
+        if (n == 0)
+            return;
+        if (e.lane().capturing)
+            throw std::logic_error("key generation allocates and synchronises: it cannot be captured in a graph");
+        const uint32_t digits = kswitch_digits(e, static_cast<uint32_t>(e.k_first));
+        std::vector<std::unique_ptr<sealhip_rgsw>> made(n);
+        std::vector<u64 *> data(n, nullptr);
+        u64 *scratch = nullptr;
+        const std::size_t scratch_bytes = static_cast<std::size_t>(n) * 2 * e.n_key * e.n * sizeof(u64);
+        auto release = [&] {
+            (void)hipStreamSynchronize(e.lane().stream); // nothing may still write into a buffer that is freed
+            for (auto &g : made)
+                if (g && g->key.d_data)
+                    (void)hipFree(g->key.d_data);
+            if (scratch) // (it may hold the lifted m and m s: erased before it goes back to the allocator, as on success)
+            {
+                (void)hipMemsetAsync(scratch, 0, scratch_bytes, e.lane().stream);
+                (void)hipStreamSynchronize(e.lane().stream);
+                (void)hipFree(scratch);
+            }
+        };
+        try
+        {
+            for (uint32_t i = 0; i < n; i++)
+            {
+                made[i] = rgsw_alloc(e, digits, static_cast<int>(level) < e.k_first ? level : 0);
+                data[i] = made[i]->key.d_data;
+            }
+            SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&scratch), scratch_bytes));
+            op_generate_rgsw(e, reinterpret_cast<const u64 *>(sk_ntt), m_coeff, n, static_cast<int>(level), seeds_host, noise,
+                             scratch, data.data());
+            e.sync_and_check();
+        }
+        catch (...)
+        {
+            release();
+            throw;
+        }
+        SEALHIP_CHECK(hipFree(scratch)); // (erased in stream order, and the lane is idle)
+        for (uint32_t i = 0; i < n; i++)
+            out[i] = made[i].release();
+    });
+}
+
+long sealhip_rgsw_create(sealhip_context *ctx, const sealhip_kswitch_key *key_b, const sealhip_kswitch_key *key_a,
+                         sealhip_rgsw **out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(key_b);
+    REQUIRE_PTR(key_a);
+    REQUIRE_PTR(out);
+    *out = nullptr;
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (key_b->key.n_digits != key_a->key.n_digits || key_b->key.level != key_a->key.level)
+            throw std::invalid_argument("the two halves of an rgsw must have the same digit count and level");
+        if (e.lane().capturing)
+            throw std::logic_error("rgsw_create allocates and synchronises: it cannot be captured in a graph");
+        auto g = rgsw_alloc(e, key_b->key.n_digits, key_b->key.level);
+        try
+        {
+            SEALHIP_CHECK(hipMemcpyAsync(g->key.d_data, key_b->key.d_data, g->key.half_words * sizeof(u64), hipMemcpyDeviceToDevice,
+                                         e.lane().stream));
+            copy_words_sync(e, g->key.d_data + g->key.half_words, key_a->key.d_data, g->key.half_words);
+        }
+        catch (...)
+        {
+            (void)hipStreamSynchronize(e.lane().stream);
+            (void)hipFree(g->key.d_data);
+            throw;
+        }
+        *out = g.release();
+    });
+}
+
+long sealhip_rgsw_export(sealhip_context *ctx, const sealhip_rgsw *rgsw, sealhip_kswitch_key **keys)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(rgsw);
+    REQUIRE_PTR(keys);
+    keys[0] = keys[1] = nullptr;
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        if (e.lane().capturing)
+            throw std::logic_error("rgsw_export allocates and synchronises: it cannot be captured in a graph");
+        std::unique_ptr<sealhip_kswitch_key> made[2];
+        try
+        {
+            for (int h = 0; h < 2; h++)
+            {
+                made[h] = std::make_unique<sealhip_kswitch_key>();
+                made[h]->key.n_digits = rgsw->key.n_digits;
+                made[h]->key.words = rgsw->key.half_words;
+                made[h]->key.level = rgsw->key.level;
+                SEALHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&made[h]->key.d_data), rgsw->key.half_words * sizeof(u64)));
+                copy_words_sync(e, made[h]->key.d_data, rgsw->key.half(h), rgsw->key.half_words);
+            }
+        }
+        catch (...)
+        {
+            (void)hipStreamSynchronize(e.lane().stream);
+            for (auto &k : made)
+                if (k && k->key.d_data)
+                    (void)hipFree(k->key.d_data);
+            throw;
+        }
+        keys[0] = made[0].release();
+        keys[1] = made[1].release();
+    });
+}
+
+long sealhip_rgsw_destroy(sealhip_context *ctx, sealhip_rgsw *rgsw)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(rgsw);
+    return guarded([&] {
+        Engine &e = device_engine(ctx);
+        e.sync_and_check(true); // any thread's lane may still be reading the block
+        e.key_generation++;     // graphs captured earlier may embed its address: they are stale now
+        SEALHIP_CHECK(hipFree(rgsw->key.d_data));
+        delete rgsw;
+    });
+}
+
+long sealhip_evaluator_external_product(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                        const sealhip_rgsw *rgsw, const uint64_t *base, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(rgsw);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        const std::size_t poly = static_cast<std::size_t>(k) * ctx->engine->n, words = count * 2 * poly;
+        Engine &e = rgsw_entry_checks(ctx, k, "the external product", { ct, base }, words, out, words);
+        check_rgsw_level(e, k, rgsw);
+        if (count == 0)
+            return;
+        u64 *o = reinterpret_cast<u64 *>(out);
+        SinkScope sink(e, count);
+        sink.begin();
+        if (base)
+            check(launch_copy_rows(e, reinterpret_cast<const u64 *>(base), poly, o, poly, 2 * count, static_cast<int>(k)), "copy(base)");
+        else
+            SEALHIP_CHECK(hipMemsetAsync(o, 0, words * sizeof(u64), e.lane().stream));
+        op_external_product(e, static_cast<int>(k), reinterpret_cast<const u64 *>(ct), 2 * poly, count, rgsw->key, o);
+    });
+}
+
+long sealhip_evaluator_cmux(sealhip_context *ctx, uint32_t k, const uint64_t *ct0, const uint64_t *ct1, size_t count,
+                            const sealhip_rgsw *rgsw, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct0);
+    REQUIRE_PTR(ct1);
+    REQUIRE_PTR(rgsw);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        const std::size_t poly = static_cast<std::size_t>(k) * ctx->engine->n, words = count * 2 * poly;
+        Engine &e = rgsw_entry_checks(ctx, k, "CMux", { ct0, ct1 }, words, out, words);
+        check_rgsw_level(e, k, rgsw);
+        if (count == 0)
+            return;
+        SinkScope sink(e, count);
+        sink.begin();
+        op_cmux(e, static_cast<int>(k), reinterpret_cast<const u64 *>(ct0), 2 * poly, reinterpret_cast<const u64 *>(ct1), 2 * poly,
+                count, rgsw->key, reinterpret_cast<u64 *>(out));
+    });
+}
+
+long sealhip_evaluator_select(sealhip_context *ctx, uint32_t k, const uint64_t *cts, size_t count, uint32_t l,
+                              const sealhip_rgsw *const *rgsw_bits, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(cts);
+    REQUIRE_PTR(out);
+    if (l)
+    {
+        REQUIRE_PTR(rgsw_bits);
+        for (uint32_t t = 0; t < l && l <= 16; t++) // (a longer list is refused below, unread)
+            REQUIRE_PTR(rgsw_bits[t]);
+    }
+    return guarded([&] {
+        check_data_level(*ctx->engine, k);
+        if (l > 16)
+            throw std::invalid_argument("l out of range: a selection among at most 2^16 ciphertexts");
+        const std::size_t poly = static_cast<std::size_t>(k) * ctx->engine->n, words = count * 2 * poly;
+        Engine &e = rgsw_entry_checks(ctx, k, "selection", { cts }, words << l, out, words);
+        std::vector<const RgswKey *> bits(l);
+        for (uint32_t t = 0; t < l; t++)
+        {
+            check_rgsw_level(e, k, rgsw_bits[t]);
+            bits[t] = &rgsw_bits[t]->key;
+        }
+        if (count == 0)
+            return;
+        SinkScope sink(e, count);
+        op_select(e, static_cast<int>(k), reinterpret_cast<const u64 *>(cts), count, static_cast<int>(l), bits.data(),
+                  reinterpret_cast<u64 *>(out), sink);
+    });
+}
+
+long sealhip_debug_ext_mac_plan(sealhip_context *ctx, uint32_t k, size_t count, int32_t out[4])
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        check_data_level(*ctx->engine, k);
+        Engine &e = device_engine(ctx);
+        const ExtMacPlan plan = ext_mac_plan(e, e.level(static_cast<int>(k)).h_ks, count);
+        out[0] = plan.choice.family == kMacItems ? 2 : (plan.choice.family == kMacLoop ? 1 : 0);
+        out[1] = plan.choice.nd;
+        out[2] = plan.split ? 1 : 0;
+        out[3] = static_cast<int32_t>(plan.choice.group);
+    });
 }
 
 long sealhip_kswitch_keys_save_seeded(sealhip_context *ctx, const sealhip_kswitch_key *const *keys, uint32_t n_slots,

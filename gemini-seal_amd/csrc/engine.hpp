@@ -971,6 +971,43 @@ namespace sealhip
     // (.) plain[n_sums][n_terms][k][N], everything in NTT form
     void op_dot_plain(Engine &e, int k, const u64 *cts, std::size_t n_terms, int size, std::size_t count, const u64 *plain,
                       std::size_t n_sums, u64 *out);
+    // RGSW. An RGSW encryption of a small m is two key-switch keys in one block,
+    // [half][digit][component][n_key][N]: half 0 (K_b) made with new_key = m, half 1 (K_a) with new_key = m s.
+    struct RgswKey
+    {
+        u64 *d_data = nullptr;
+        std::uint32_t n_digits = 0;
+        std::size_t half_words = 0; // n_digits * 2 * n_key * N
+        std::uint32_t level = 0;    // as KSwitchKey::level
+        const u64 *half(int h) const { return d_data + static_cast<std::size_t>(h) * half_words; }
+    };
+    // what launch_ext_mac would run for a chunk of `count` items at level k, with no launch (sealhip_debug_ext_mac_plan)
+    struct ExtMacPlan
+    {
+        MacChoice choice;
+        bool split; // the sum is reduced between its halves (bounds::ext_mac_sum_fits fails for 2 nd terms)
+    };
+    ExtMacPlan ext_mac_plan(const Engine &e, const KsDev &h, std::size_t count);
+    // prod[item][l][r][c] = ( sum_j D0_j K_b[j][l] + sum_j D1_j K_a[j][l] ) mod p_r: ext holds the 2 nd digits digit-major
+    // (those of c_0 first), own0 / own1 the rows the sum reads inside a bundle, own_stride words from item to item
+    hipError_t launch_ext_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *own0, const u64 *own1,
+                              std::size_t own_stride, const u64 *ext, std::size_t ext_stride, std::size_t ext_digit_stride,
+                              const u64 *key_b, const u64 *key_a, u64 *prod, std::size_t prod_stride, std::size_t count);
+    // diff[i] = ct1[i] - ct0[i] (2 k N words per item, back to back) and base[i] = ct0[i], for npairs ciphertext pairs whose
+    // operands lie stride0 / stride1 words apart; everything 16-byte aligned
+    hipError_t launch_cmux_prepare(const Engine &e, int k, const u64 *ct0, std::size_t stride0, const u64 *ct1,
+                                   std::size_t stride1, u64 *diff, u64 *base, std::size_t base_stride, std::size_t npairs);
+    // n blocks (rgsw[i]: 2 x digits x 2 x n_key x N words) from m_coeff[n][N]; seeds_host n x 2 x digits x 8, noise n x 2 x digits x N
+    void op_generate_rgsw(Engine &e, const u64 *sk_ntt, const std::int32_t *m_coeff, std::size_t n, int level,
+                          const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *scratch, u64 *const *rgsw);
+    // out[count][2][k][N] += ct (x) rgsw: out holds the base on entry (ct_stride words between the items of ct)
+    void op_external_product(Engine &e, int k, const u64 *ct, std::size_t ct_stride, std::size_t count, const RgswKey &g, u64 *out);
+    // out = ct0 + (ct1 - ct0) (x) rgsw
+    void op_cmux(Engine &e, int k, const u64 *ct0, std::size_t stride0, const u64 *ct1, std::size_t stride1, std::size_t count,
+                 const RgswKey &g, u64 *out);
+    // out[count] = cts[count][index], the index's bit t encrypted in bits[t] (least significant first): l levels of CMux
+    void op_select(Engine &e, int k, const u64 *cts, std::size_t count, int l, const RgswKey *const *bits, u64 *out,
+                   SinkScope &sink);
     // One decomposition of c_1, n_elts rotations: out[n_elts][count][2][k][N], ct is only read.
     // Not the words of n_elts calls of op_apply_galois (the automorphism does not commute with the mod-up).
     void op_apply_galois_many(Engine &e, int k, const u64 *ct, std::size_t count, const std::uint32_t *elts,

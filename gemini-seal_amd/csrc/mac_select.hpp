@@ -1,5 +1,6 @@
 // mac_select.hpp -- which kernel the key switch's inner-product launchers run and with what launch shape: launch_ks_mac
-// (keyswitch.hip), launch_hoist_mac, launch_hoist_dot_mac and launch_hoist_giant_mac (hoist.hip), as pure functions of plain
+// (keyswitch.hip), launch_hoist_mac, launch_hoist_dot_mac and launch_hoist_giant_mac (hoist.hip), launch_ext_mac (rgsw.hip;
+// its check program is tests/ext_select_check.cpp, its second statement in tests/test_rgsw_host.py), as pure functions of plain
 // numbers. No Engine, no HIP: tests/mac_select_check.cpp compiles this header with a host compiler, checks the rule's
 // invariants over a grid and prints the choice for any call; tests/test_ks_instances_host.py holds the second statement of
 // the rule and requires the two to agree call by call. The launchers gather the numbers, call the selector and dispatch
@@ -113,6 +114,34 @@ namespace sealhip
             return c;
         }
         // small batches, a digit range or more than 16 digits
+        c.family = kMacLoop;
+        c.blocks = blocks_for((count * rows) << logn);
+        return c;
+    }
+
+    // launch_ext_mac (rgsw.hip): the 2 nd digits of a ciphertext's two components against the two
+    // halves of one RGSW block. The items family is instantiated for even ND2 = 2 nd up to kMacMaxDigits and tiles a row
+    // with whole workgroups; its key words are twice a key switch's, which is what mac_item_group is told. The batch
+    // threshold and the group constants are the key switch's, not tuned for this kernel (section 29, "Open").
+    constexpr bool ext_mac_has_instance(int logn, int nd)
+    {
+        return nd >= 1 && (std::size_t(1) << logn) >= static_cast<std::size_t>(kThreads) && mac_has_instance(2 * nd);
+    }
+    constexpr MacChoice select_ext_mac(int logn, int nd, std::size_t rows, std::size_t count)
+    {
+        MacChoice c{};
+        if (nd < 1)
+            return c;
+        if (count >= 16 && ext_mac_has_instance(logn, nd))
+        {
+            c.family = kMacItems;
+            c.nd = 2 * nd;
+            c.group = mac_item_group(logn, 2 * nd, rows, 1, count);
+            c.n_groups = mac_ceil_div(count, c.group);
+            c.blocks = blocks_for((c.n_groups * rows) << logn);
+            return c;
+        }
+        // small batches, rings below one workgroup per row, 2 nd > kMacMaxDigits
         c.family = kMacLoop;
         c.blocks = blocks_for((count * rows) << logn);
         return c;

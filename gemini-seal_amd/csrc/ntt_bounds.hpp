@@ -753,5 +753,26 @@ namespace sealhip
         }
         static_assert(ks_rescale_sum_fits(64, kDotAccOperandBits) && !ks_rescale_sum_fits(65, kDotAccOperandBits),
                       "the last prime and up to 63 special primes of 61 bits: 64 dropped primes fit, 65 would not");
+
+        // =====================================================================================================
+        // 10. The external product's inner product (rgsw.hip ext_mac_kernel / ext_mac_items_kernel):
+        // `terms` products digit word * key word accumulated with mac128 and reduced once. A key word is a canonical
+        // residue (at most pmax - 1); a digit word is whatever representative ks_digits stored, below 2^rep_bits. The split
+        // form reduces after the first half and carries that canonical residue into the second, so one more word of at
+        // most pmax - 1 is counted -- for the unsplit sum it is slack. The sum must stay below 2^128.
+        // The key switch's own argument ("words below 2^64 and nd p < 2^64") is this predicate at terms = nd and
+        // rep_bits = 64; the external product has 2 nd terms, where it fails first for 61-bit primes: 2 nd > 8.
+        constexpr int kKsDigitRepBits = 64; // ks_digits transforms the digit rows with kNttAnyRep: any 64-bit word
+        constexpr bool ext_mac_sum_fits(int terms, u64 pmax, int rep_bits)
+        {
+            if (terms < 1 || pmax < 2 || rep_bits < 1 || rep_bits > 64)
+                return false;
+            const u128 x = max_prime_of_bits(rep_bits), k = pmax - 1, max = ~static_cast<u128>(0);
+            return static_cast<u128>(terms) <= (max - k) / (x * k); // terms x k + k <= 2^128 - 1
+        }
+        static_assert(ext_mac_sum_fits(8, max_prime_of_bits(61), kKsDigitRepBits) && !ext_mac_sum_fits(9, max_prime_of_bits(61), kKsDigitRepBits),
+                      "61-bit primes: eight terms in one sum (nd <= 4 unsplit, nd <= 8 in two halves)");
+        static_assert(ext_mac_sum_fits(16, max_prime_of_bits(60), kKsDigitRepBits) && !ext_mac_sum_fits(17, max_prime_of_bits(60), kKsDigitRepBits),
+                      "60-bit primes: sixteen terms, every instance of the items family unsplit");
     } // namespace bounds
 } // namespace sealhip

@@ -33,7 +33,8 @@ namespace sealhip
             // parks scratch at the front of the arena relies on the nested operation seeing the same cap); a lane created
             // later sees what the earlier ones left, so the caps of all threads' lanes cannot add up to more than the device.
             // An operation that parks scratch plans the nested one with the whole cap: the arena then exceeds it by the
-            // parked bytes (op_apply_galois: at most 1 GiB; op_pack_lwes and op_expand: at most half of the cap, 1.5 times in all).
+            // parked bytes (op_apply_galois: at most 1 GiB; op_pack_lwes, op_expand and op_select: at most half of the cap, 1.5 times
+            // in all).
             Lane &l = e.lane();
             if (l.ws_budget)
                 return l.ws_budget;
@@ -1664,6 +1665,145 @@ namespace sealhip
     }
 
     // ------------------------------------------------------------------------------------------
+    // RGSW: the external product, CMux and the CMux tree
+    // ------------------------------------------------------------------------------------------
+    namespace
+    {
+        // a key switch's item with the digits of both components (and both components in the other form, where there is one)
+        constexpr int kExtProductBuffers = 6;
+        KsArena ext_product_arena(Engine &e, int k)
+        {
+            KsArena ar = switch_key_arena(e, k);
+            ar.w_coeff *= 2;
+            ar.w_ext *= 2;
+            return ar;
+        }
+        LevelTools &ext_product_level(Engine &e, int k, const RgswKey &g)
+        {
+            if (k > e.k_first)
+                throw std::invalid_argument("key switching needs a ciphertext level");
+            if (e.scheme != 2 && !e.mode_strict)
+                throw std::invalid_argument("the external product of BFV ciphertexts needs a STRICT context");
+            LevelTools &lt = e.level(k);
+            if (static_cast<int>(g.n_digits) < lt.h_ks.nd || (g.level && k > static_cast<int>(g.level)))
+                throw std::invalid_argument("rgsw is not valid for encryption parameters");
+            return lt;
+        }
+        // One chunk: outp[m][2][k][N] += c (x) g. The digits of c_0 and of c_1 go into one digit-major ext of 2 nd digits,
+        // one launch forms the 2 nd-term inner product, one ks_finish brings it down and adds it in.
+        void ext_product_chunk(Engine &e, LevelTools &lt, int k, const KsArena &ar, const u64 *c, std::size_t stride, std::size_t m,
+                               const RgswKey &g, u64 *outp, unsigned *sink)
+        {
+            const std::size_t poly = static_cast<std::size_t>(k) * e.n, ext_item = static_cast<std::size_t>(k + e.nsp) * e.n;
+            const int nd = lt.h_ks.nd;
+            u64 *coeff0 = ar.w_coeff ? e.ws_alloc(ar.w_coeff / 2 * m) : nullptr;
+            u64 *coeff1 = ar.w_coeff ? e.ws_alloc(ar.w_coeff / 2 * m) : nullptr;
+            u64 *ext = e.ws_alloc(ar.w_ext * m);
+            u64 *prod = e.ws_alloc(ar.w_prod * m);
+            u64 *temp = e.ws_alloc(ar.w_temp * m);
+            const KsRows in0 = ks_digits(e, lt, k, c, stride, m, coeff0, ext, 0, nd);
+            const KsRows in1 = ks_digits(e, lt, k, c + poly, stride, m, coeff1, ext + nd * ext_item * m, 0, nd);
+            check(launch_ext_mac(e, lt.d_ks, lt.h_ks, in0.inb, in1.inb, in0.inb_stride, ext, ext_item, ext_item * m, g.half(0), g.half(1),
+                                 prod, 2 * ext_item, m),
+                  "ext_mac");
+            ks_finish(e, lt, k, prod, temp, outp, 2 * poly, nullptr, 0, m, sink);
+        }
+    } // namespace
+
+    void op_external_product(Engine &e, int k, const u64 *ct, std::size_t ct_stride, std::size_t count, const RgswKey &g, u64 *out)
+    {
+        LevelTools &lt = ext_product_level(e, k, g);
+        const KsArena ar = ext_product_arena(e, k);
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+        for_chunks(e, count, ar.item_bytes(), kExtProductBuffers, [&](std::size_t off, std::size_t m) {
+            ext_product_chunk(e, lt, k, ar, ct + off * ct_stride, ct_stride, m, g, out + off * 2 * poly, sink_at(e, off));
+        });
+    }
+
+    // cmux_prepare_kernel reads both operands once: the difference goes to the arena, the copy of ct0 to out, and the chunk
+    // goes on as an external product's
+    void op_cmux(Engine &e, int k, const u64 *ct0, std::size_t stride0, const u64 *ct1, std::size_t stride1, std::size_t count,
+                 const RgswKey &g, u64 *out)
+    {
+        LevelTools &lt = ext_product_level(e, k, g);
+        const KsArena ar = ext_product_arena(e, k);
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+        for_chunks(e, count, ar.item_bytes() + 2 * poly * sizeof(u64), kExtProductBuffers + 1, [&](std::size_t off, std::size_t m) {
+            u64 *diff = e.ws_alloc(2 * poly * m);
+            u64 *outp = out + off * 2 * poly;
+            check(launch_cmux_prepare(e, k, ct0 + off * stride0, stride0, ct1 + off * stride1, stride1, diff, outp, 2 * poly, m),
+                  "cmux_prepare");
+            ext_product_chunk(e, lt, k, ar, diff, 2 * poly, m, g, outp, sink_at(e, off));
+        });
+    }
+
+    // The CMux tree. The working set is item-major and flat: level t reads the pairs (W[2i], W[2i+1]) of the m 2^(l-t)
+    // ciphertexts before it as one run and writes m 2^(l-t-1). Level 0 reads the caller's ciphertexts, level l - 1 writes the
+    // caller's out; the sets between alternate between two buffers parked at the front of the arena under a raised floor,
+    // next to the differences: 2^(l-1) + 2^(l-2) + 2^(l-1) ciphertexts per item, at most half of the arena's cap. Each level
+    // is one prepare launch and one external product of all its pairs, chunked by its own loop. A batch that does not fit
+    // is walked in chunks of items.
+    void op_select(Engine &e, int k, const u64 *cts, std::size_t count, int l, const RgswKey *const *bits, u64 *out, SinkScope &sink)
+    {
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n, ct_words = 2 * poly;
+        if (!l) // a copy
+        {
+            if (k > e.k_first)
+                throw std::invalid_argument("key switching needs a ciphertext level");
+            check(launch_copy_rows(e, cts, poly, out, poly, 2 * count, k), "copy");
+            sink.read_pass(out, 2, poly, count);
+            log_chunk(e, count, count);
+            return;
+        }
+        for (int t = 0; t < l; t++)
+            (void)ext_product_level(e, k, *bits[t]);
+        const std::size_t half = static_cast<std::size_t>(1) << (l - 1);
+        const std::size_t w_big = l >= 2 ? half * ct_words : 0, w_small = l >= 3 ? (half / 2) * ct_words : 0, w_diff = half * ct_words;
+        const std::size_t item_bytes = (w_big + w_small + w_diff) * sizeof(u64);
+        const std::size_t cap = workspace_budget_bytes(e) / 2 - 3 * 256;
+        if (item_bytes > cap)
+            throw HipError(hipErrorOutOfMemory, ("select: the first level of one item (" + std::to_string(item_bytes) +
+                                                 " bytes) does not fit half of the workspace arena (" + std::to_string(cap) +
+                                                 " bytes): raise SEALHIP_WORKSPACE_MB or select among fewer ciphertexts per call")
+                                                    .c_str());
+        const std::size_t items = std::max<std::size_t>(1, std::min(count, cap / item_bytes));
+        const std::size_t scratch_bytes = pad256(w_big * items) + pad256(w_small * items) + pad256(w_diff * items);
+        const KsArena ar = ext_product_arena(e, k);
+        Lane &lane = e.lane();
+        e.ws_reserve(lane.ws_floor + scratch_bytes + 256);
+        FloorRestore guard(e);
+        guard.raise(scratch_bytes);
+        for (std::size_t off = 0; off < count; off += items)
+        {
+            const std::size_t m = std::min(items, count - off);
+            // size the arena now as the largest nested external product will ask for, so that it cannot move while the
+            // working set is live, and derive the pointers after it
+            plan_chunk(e, m * half, ar.item_bytes(), kExtProductBuffers, false);
+            Carver carve{ static_cast<char *>(guard.parked()) };
+            u64 *bufs[2];
+            bufs[0] = carve.take(w_big * items);
+            bufs[1] = carve.take(w_small * items);
+            u64 *diff = carve.take(w_diff * items);
+            for (int t = 0; t < l; t++)
+            {
+                const std::size_t pairs = m << (l - t - 1);
+                const u64 *src = t == 0 ? cts + (off << l) * ct_words : bufs[(t - 1) & 1];
+                u64 *dst = t == l - 1 ? out + off * ct_words : bufs[t & 1];
+                check(launch_cmux_prepare(e, k, src, 2 * ct_words, src + ct_words, 2 * ct_words, diff, dst, ct_words, pairs),
+                      "cmux_prepare");
+                if (t == l - 1) // the last level's mod-down carries the flags, one per output ciphertext
+                {
+                    sink.arm();
+                    lane.tsink_base = guard.base + off;
+                }
+                op_external_product(e, k, diff, ct_words, pairs, *bits[t], dst);
+                lane.tsink_cur = nullptr;
+            }
+        }
+        log_chunk(e, count, items); // (after the external products' own entries: the last pair of sealhip_debug_chunk_log)
+    }
+
+    // ------------------------------------------------------------------------------------------
     // Hoisted rotation: n_elts automorphisms of the same ciphertexts with one decomposition of c_1
     // ------------------------------------------------------------------------------------------
     // out_g = finish( (sigma_g(c_0), 0), sum_j sigma_g(D_j) (.) K_g ), D_j the digits op_switch_key forms for the target c_1.
@@ -2376,6 +2516,32 @@ namespace sealhip
                                                  stream));
             }
         }
+    }
+
+    // RGSW(m_i): m_i is lifted over the key primes as a secret key is and transformed, m_i s is a
+    // dyadic product, and the 2 n halves are the switching keys op_generate_kswitch_keys makes for the new keys
+    // {NTT(m_i), NTT(m_i) (.) s}, half h of message i with the seeds and the noise [i][h]. scratch: n x 2 x n_key x N words,
+    // erased in stream order once the halves are assembled.
+    void op_generate_rgsw(Engine &e, const u64 *sk_ntt, const std::int32_t *m_coeff, std::size_t n, int level,
+                          const std::uint64_t *seeds_host, const std::int32_t *noise, u64 *scratch, u64 *const *rgsw)
+    {
+        if (n == 0)
+            return;
+        const int nk = e.n_key;
+        const std::size_t N = e.n, poly = static_cast<std::size_t>(nk) * N;
+        const std::size_t half_words = static_cast<std::size_t>((e.k_first + e.nsp - 1) / e.nsp) * 2 * poly;
+        lift_to_ntt(e, rlwe_args(scratch, 2 * poly, nk, m_coeff, N), n, ct_row_map(nk, 2, 0), "lift(m)", "ntt(m)");
+        const RowMap rows = ct_row_map(nk, 1, -1);
+        std::vector<u64 *> halves(2 * n);
+        for (std::size_t i = 0; i < n; i++)
+        {
+            check(launch_poly_op(e, PolyOp::Dyadic, scratch + 2 * i * poly, sk_ntt, 0, scratch + (2 * i + 1) * poly, nk, rows),
+                  "m (.) s");
+            halves[2 * i] = rgsw[i];
+            halves[2 * i + 1] = rgsw[i] + half_words;
+        }
+        op_generate_kswitch_keys(e, sk_ntt, nullptr, 2 * n, seeds_host, noise, halves.data(), scratch, level);
+        SEALHIP_CHECK(hipMemsetAsync(scratch, 0, 2 * n * poly * sizeof(u64), e.lane().stream));
     }
 
     void op_encrypt_zero_asymmetric(Engine &e, int rows, bool is_ntt_form, const u64 *pk, const std::int32_t *u,

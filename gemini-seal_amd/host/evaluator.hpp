@@ -611,6 +611,39 @@ namespace sealhip_host
         sealhip_kswitch_key *key_ = nullptr;
     };
 
+    // One RGSW ciphertext, resident on the device: the key-switch keys K_b (new key m) and K_a (new
+    // key m s) of a small polynomial m in one block. Made by KeyGenerator::rgsw, or from two key-switch keys (for example
+    // loaded from a stream; a device copy -- digit counts or levels that differ -> std::invalid_argument).
+    // Evaluator::external_product / cmux / select take it.
+    class RgswCiphertext
+    {
+    public:
+        RgswCiphertext(const Context &c, const KSwitchKeys &key_b, const KSwitchKeys &key_a) : c_(c)
+        {
+            throw_on(sealhip_rgsw_create(c.get(), key_b.get(), key_a.get(), &g_));
+        }
+        RgswCiphertext(const Context &c, sealhip_rgsw *adopt) : c_(c), g_(adopt) {} // a handle the ABI made
+        ~RgswCiphertext()
+        {
+            if (g_)
+                sealhip_rgsw_destroy(c_.get(), g_);
+        }
+        RgswCiphertext(const RgswCiphertext &) = delete;
+        RgswCiphertext &operator=(const RgswCiphertext &) = delete;
+        const sealhip_rgsw *get() const { return g_; }
+        // (K_b, K_a) as two owned key-switch keys holding copies of the halves (sealhip_rgsw_export)
+        std::pair<std::unique_ptr<KSwitchKeys>, std::unique_ptr<KSwitchKeys>> export_keys() const
+        {
+            sealhip_kswitch_key *raw[2] = { nullptr, nullptr };
+            throw_on(sealhip_rgsw_export(c_.get(), g_, raw));
+            return { std::make_unique<KSwitchKeys>(c_, raw[0]), std::make_unique<KSwitchKeys>(c_, raw[1]) };
+        }
+
+    private:
+        const Context &c_;
+        sealhip_rgsw *g_ = nullptr;
+    };
+
     // What HomomorphicDFT and Bootstrapper share: the tables' handle (destroyed with the object, not copyable), the plan and
     // its key steps. plan_entry(plan, key_steps, capacity) is the ABI's plan entry over the owner's arguments, called
     // twice (the plan says how many steps there are); create(tables) its create entry. The plan comes first: its
@@ -1907,6 +1940,71 @@ namespace sealhip_host
             });
         }
 
+        // The external product (sealhip_evaluator_external_product): destination = base + encrypted (x)
+        // rgsw, the phase of `encrypted` times the small polynomial the RGSW encrypts, with additive noise; base (optional)
+        // has the operand's size, level and form. The destination (which may be an operand) takes the metadata of
+        // `encrypted`. The reference has no such method. CKKS in NTT form; BFV in coefficient form on a STRICT context.
+        template <class C, IfCt<C> = 0>
+        void external_product(const C &encrypted, const RgswCiphertext &rgsw, C &destination, const C *base = nullptr)
+        {
+            check_galois_operand(encrypted);
+            const std::size_t k = encrypted.coeff_modulus_size(), words = 2 * k * ctx_.n();
+            Dev b;
+            if (base)
+            {
+                check_rgsw_pair(encrypted, *base);
+                b = dev_in(*base, words);
+            }
+            to_size2(encrypted, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_external_product(ctx_.get(), std::uint32_t(k), c, 1, rgsw.get(), b.ptr(), o);
+            });
+        }
+        // CMux (sealhip_evaluator_cmux): destination = encrypted0 + (encrypted1 - encrypted0) (x) rgsw, i.e. encrypted1 where
+        // the RGSW encrypts 1 and encrypted0 where it encrypts 0; the metadata is encrypted0's
+        template <class C, IfCt<C> = 0>
+        void cmux(const C &encrypted0, const C &encrypted1, const RgswCiphertext &rgsw, C &destination)
+        {
+            check_galois_operand(encrypted0);
+            check_rgsw_pair(encrypted0, encrypted1);
+            const std::size_t k = encrypted0.coeff_modulus_size(), words = 2 * k * ctx_.n();
+            Dev c1 = dev_in(encrypted1, words);
+            to_size2(encrypted0, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_cmux(ctx_.get(), std::uint32_t(k), c, c1.ptr(), 1, rgsw.get(), o);
+            });
+        }
+        // Selection (sealhip_evaluator_select): destination = encrypteds[index] for the index whose bit t (least significant
+        // first) rgsw_bits[t] encrypts: a CMux tree over 2^l ciphertexts of one size, level and form, l = rgsw_bits.size()
+        // (another count -> std::invalid_argument). The metadata is encrypteds[0]'s. The operands are gathered into one
+        // block for the call.
+        template <class C, IfCt<C> = 0>
+        void select(const std::vector<C> &encrypteds, const std::vector<const RgswCiphertext *> &rgsw_bits, C &destination)
+        {
+            if (rgsw_bits.size() > 16 || encrypteds.size() != (std::size_t(1) << rgsw_bits.size()))
+                throw std::invalid_argument("select needs 2^l ciphertexts for l RGSW bits");
+            check_galois_operand(encrypteds[0]);
+            const std::size_t k = encrypteds[0].coeff_modulus_size(), words = 2 * k * ctx_.n();
+            std::vector<const sealhip_rgsw *> raw;
+            for (const RgswCiphertext *g : rgsw_bits)
+            {
+                if (!g)
+                    throw std::invalid_argument("rgsw_bits holds a null entry");
+                raw.push_back(g->get());
+            }
+            Dev all = dev_out(encrypteds.size() * words), o = dev_out(words);
+            for (std::size_t i = 0; i < encrypteds.size(); i++)
+            {
+                check_rgsw_pair(encrypteds[0], encrypteds[i]);
+                gather_words(encrypteds[i], all.ptr() + i * words, words);
+            }
+            Check chk = checked(encrypteds[0]);
+            throw_on(sealhip_evaluator_select(ctx_.get(), std::uint32_t(k), all.ptr(), 1, std::uint32_t(raw.size()),
+                                              raw.empty() ? nullptr : raw.data(), o.ptr()));
+            chk.done();
+            const C first = meta_of(encrypteds[0]); // (the destination may be one of the operands)
+            take_meta(destination, first);
+            commit(destination, o, 2, k);
+        }
+
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
         template <class C, IfCt<C> = 0>
         void multiply_many(const std::vector<C> &encrypteds, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
@@ -2326,6 +2424,32 @@ namespace sealhip_host
         };
         Check checked(const CT &, std::size_t = 1) { return Check(); }
         Check checked(const DeviceCiphertext &, std::size_t count = 1) { return Check(ctx_, this, count); }
+
+        // the second operand of an RGSW operation: the first one's size, level and form
+        template <class C>
+        void check_rgsw_pair(const C &first, const C &other) const
+        {
+            if (other.size() != 2 || other.coeff_modulus_size() != first.coeff_modulus_size() ||
+                other.is_ntt_form() != first.is_ntt_form())
+                throw std::invalid_argument("encrypted operands differ in size, level or form");
+        }
+        // an operand's words into a block that gathers several
+        void gather_words(const CT &c, std::uint64_t *dst, std::size_t words)
+        {
+            throw_on(sealhip_memcpy_h2d(ctx_.get(), dst, c.data(), words * 8));
+        }
+        void gather_words(const DeviceCiphertext &c, std::uint64_t *dst, std::size_t words)
+        {
+            throw_on(sealhip_memcpy_d2d(ctx_.get(), dst, c.data(), words * 8));
+        }
+        // an operand's metadata, detached from its words (a host ciphertext is its own metadata)
+        CT meta_of(const CT &c) { return c; }
+        DeviceCiphertext meta_of(const DeviceCiphertext &c)
+        {
+            DeviceCiphertext m(ctx_);
+            m.copy_meta(c);
+            return m;
+        }
 
         // One operand of in_size polynomials in, one size-2 result at level k_out out: call(in, out) is the ABI entry over
         // the two device blocks. The destination (which may be the operand) takes the operand's metadata, the result's
@@ -3264,6 +3388,42 @@ namespace sealhip_host
             if (level > k_first)
                 throw std::invalid_argument("level k out of range");
             return generate(nullptr, count, save_seed, from_secret_keys_ntt, level ? level : k_first);
+        }
+
+        // RGSW encryptions of small polynomials under this generator's secret key (sealhip_generate_rgsw, DESIGN.md section
+        // 29): messages[i] holds the N signed coefficients of m_i. level as switching_keys. Samples are drawn as for
+        // relin_keys: message by message, K_b's digits before K_a's.
+        std::vector<std::unique_ptr<RgswCiphertext>> rgsw(const std::vector<std::vector<std::int32_t>> &messages, std::size_t level = 0)
+        {
+            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), count = messages.size();
+            if (!count)
+                throw std::invalid_argument("invalid count");
+            for (const auto &m : messages)
+                if (m.size() != n)
+                    throw std::invalid_argument("an rgsw message has N coefficients");
+            std::uint32_t k_first = 0, digits = 0;
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            if (level > k_first)
+                throw std::invalid_argument("level k out of range");
+            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
+            const std::size_t items = count * 2 * digits;
+            std::vector<std::uint64_t> seeds(items * 8);
+            Drawn drawn = draw(seeds.data(), items);
+            Staged sk(ctx_, nk * n);
+            ZeroedStaged e(ctx_, (items * n + 1) / 2), mm(ctx_, (count * n + 1) / 2);
+            sk.up(sk_.data(), nk * n);
+            to_device(drawn, items, e);
+            for (std::size_t i = 0; i < count; i++)
+                throw_on(sealhip_memcpy_h2d(ctx_.get(), reinterpret_cast<std::int32_t *>(mm.ptr()) + i * n, messages[i].data(),
+                                            n * sizeof(std::int32_t)));
+            std::vector<sealhip_rgsw *> raw(count, nullptr);
+            throw_on(sealhip_generate_rgsw(ctx_.get(), sk.ptr(), reinterpret_cast<const std::int32_t *>(mm.ptr()), std::uint32_t(count),
+                                           std::uint32_t(level ? level : k_first), seeds.data(),
+                                           reinterpret_cast<const std::int32_t *>(e.ptr()), raw.data()));
+            std::vector<std::unique_ptr<RgswCiphertext>> out;
+            for (auto *h : raw)
+                out.push_back(std::make_unique<RgswCiphertext>(ctx_, h));
+            return out;
         }
 
     private:

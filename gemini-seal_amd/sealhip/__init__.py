@@ -280,6 +280,14 @@ SYMBOLS = {
     "sealhip_generate_sparse_secret_key": [_vp, _vp, _u32, _vp],
     "sealhip_generate_switching_keys": [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _i32, C.POINTER(_vp)],
     "sealhip_evaluator_switch_secret": [_vp, _u32, _vp, _sz, _vp, _vp],
+    "sealhip_generate_rgsw": [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_vp)],
+    "sealhip_rgsw_create": [_vp, _vp, _vp, C.POINTER(_vp)],
+    "sealhip_rgsw_export": [_vp, _vp, C.POINTER(_vp)],
+    "sealhip_rgsw_destroy": [_vp, _vp],
+    "sealhip_evaluator_external_product": [_vp, _u32, _vp, _sz, _vp, _vp, _vp],
+    "sealhip_evaluator_cmux": [_vp, _u32, _vp, _vp, _sz, _vp, _vp],
+    "sealhip_evaluator_select": [_vp, _u32, _vp, _sz, _u32, C.POINTER(_vp), _vp],
+    "sealhip_debug_ext_mac_plan": [_vp, _u32, _sz, C.POINTER(_i32)],
     "sealhip_evaluator_bootstrap_encapsulated": [_vp, _vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, C.POINTER(_vp), _u32, _vp, _vp, _vp],
     "sealhip_memset_zero": [_vp, _vp, _sz],
     "sealhip_ciphertext_load_many": [_vp, _vp, _vp, _sz, _vp, _vp, _sz],
@@ -468,6 +476,25 @@ class KSwitchKeys:
         try:
             if self.handle:
                 lib().sealhip_kswitch_key_destroy(self.ctx.handle, self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class Rgsw:
+    """One RGSW ciphertext: the key-switch keys K_b (new key m) and K_a (new key m s) in one device
+    block. Made by Context.generate_rgsw or Context.rgsw_create."""
+
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        self = cls.__new__(cls)
+        self.ctx, self.handle = ctx, handle
+        return self
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().sealhip_rgsw_destroy(self.ctx.handle, self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -960,6 +987,36 @@ class Context:
                                                      _ptr(noise) if noise is not None else None, 1 if keep_seeds else 0, out))
         return [KSwitchKeys._adopt(self, out[i]) for i in range(n_keys)]
 
+    def generate_rgsw(self, sk_ntt, m_coeff, n, level, seeds, noise):
+        """sealhip_generate_rgsw: n Rgsw objects from m_coeff (n x N int32, device, small signed coefficients). seeds: n x 2
+        x digits x 8 words (host), noise: n x 2 x digits x N int32 (device); half h of message i uses [i][h]. level as
+        generate_switching_keys."""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        out = (C.c_void_p * max(1, n))()
+        _check(lib().sealhip_generate_rgsw(self.handle, _ptr(sk_ntt), _ptr(m_coeff) if m_coeff is not None else None, n, level,
+                                           seeds.ctypes.data if seeds.size else None,
+                                           _ptr(noise) if noise is not None else None, out))
+        return [Rgsw._adopt(self, out[i]) for i in range(n)]
+
+    def rgsw_create(self, key_b, key_a):
+        """sealhip_rgsw_create: the Rgsw whose halves are copies of two KSwitchKeys (K_b: new key m, K_a: new key m s)"""
+        h = C.c_void_p()
+        _check(lib().sealhip_rgsw_create(self.handle, key_b.handle, key_a.handle, C.byref(h)))
+        return Rgsw._adopt(self, h.value)
+
+    def rgsw_export(self, rgsw):
+        """sealhip_rgsw_export: (K_b, K_a) as two owned KSwitchKeys holding copies of the halves"""
+        out = (C.c_void_p * 2)()
+        _check(lib().sealhip_rgsw_export(self.handle, rgsw.handle, out))
+        return KSwitchKeys._adopt(self, out[0]), KSwitchKeys._adopt(self, out[1])
+
+    def debug_ext_mac_plan(self, k, count):
+        """what the external product's inner product would run for a chunk of `count` items at level k
+        (sealhip_debug_ext_mac_plan): dict(family "loop" | "items", nd2, split, group)"""
+        out = (_i32 * 4)()
+        _check(lib().sealhip_debug_ext_mac_plan(self.handle, k, count, out))
+        return dict(family={1: "loop", 2: "items"}.get(out[0], "refused"), nd2=out[1], split=bool(out[2]), group=out[3])
+
     def memset_zero(self, buf, nbytes):
         """stream-ordered zero fill of device memory (sealhip_memset_zero)"""
         _check(lib().sealhip_memset_zero(self.handle, _ptr(buf), nbytes))
@@ -1197,6 +1254,23 @@ class Evaluator:
         ea, ka, n_keys = _galois_arrays(galois_keys)
         _check(lib().sealhip_evaluator_expand(self.ctx.handle, k, _ptr(ct), count, n, ea, ka, n_keys, 1 if normalize else 0,
                                               _ptr(out)))
+
+    def external_product(self, ct, k, count, rgsw, out, base=None):
+        """out = base + ct (x) rgsw (sealhip_evaluator_external_product): count size-2 ciphertexts in the
+        scheme's form against one Rgsw; base (count x 2 x k x N) None means zero. The phase is multiplied by the Rgsw's m."""
+        _check(lib().sealhip_evaluator_external_product(self.ctx.handle, k, _ptr(ct), count, rgsw.handle,
+                                                        _ptr(base) if base is not None else None, _ptr(out)))
+
+    def cmux(self, ct0, ct1, k, count, rgsw, out):
+        """out = ct0 + (ct1 - ct0) (x) rgsw (sealhip_evaluator_cmux): ct1 where the Rgsw encrypts 1, ct0 where it encrypts 0"""
+        _check(lib().sealhip_evaluator_cmux(self.ctx.handle, k, _ptr(ct0), _ptr(ct1), count, rgsw.handle, _ptr(out)))
+
+    def select(self, cts, k, count, rgsw_bits, out):
+        """out[i] = cts[i][index] (sealhip_evaluator_select): cts count x 2^l x 2 x k x N, rgsw_bits the l Rgsw encryptions of
+        the index's bits, least significant first; a CMux tree of l levels"""
+        l = len(rgsw_bits)
+        handles = (C.c_void_p * max(1, l))(*[g.handle for g in rgsw_bits])
+        _check(lib().sealhip_evaluator_select(self.ctx.handle, k, _ptr(cts), count, l, handles if l else None, _ptr(out)))
 
     def dot_plain(self, cts, plain, k, count, n_terms, n_sums, out, size=2):
         """Sums against plaintext rows (sealhip_evaluator_dot_plain): out[s] = sum_i ct_i (.) P[s][i],

@@ -1522,6 +1522,75 @@ long sealhip_evaluator_bootstrap_encapsulated(sealhip_context *ctx, const sealhi
                                               const sealhip_kswitch_key *const *relin_keys, uint32_t n_relin_keys,
                                               const sealhip_kswitch_key *to_sparse, const sealhip_kswitch_key *to_dense,
                                               uint64_t *out);
+/* RGSW ciphertexts and the external product: the RLWE x RGSW product of Chillotti, Gama, Georgieva,
+   Izabachene ("TFHE", J. Cryptology 2020) in this library's hybrid gadget, whose noise growth is additive. An RGSW
+   encryption of a small polynomial m is two ordinary key-switch keys: K_b made with new_key = m and K_a made with
+   new_key = m s. For a size-2 ciphertext (c_0, c_1) with phase c_0 + c_1 s,
+       ct (x) rgsw = KS(c_0; K_b) + KS(c_1; K_a)
+   has phase m (c_0 + c_1 s) + e_ks, e_ks ONE key switch's error (2 nd digit terms, one mod-down). The fork has no such
+   method: what defines the words is the composition from entries this header already has -- sealhip_switch_key_partial
+   on c_0 with K_b and on c_1 with K_a over all digits, the word-wise sum, sealhip_switch_key_finish with n_partials = 2 into
+   a copy of the base -- restated over the oracle in tests/rgsw_ref.py. The fused entries decompose both components into
+   one set of 2 nd digits, form ONE inner product with one reduction per word and run ONE mod-down; modular sums are
+   associative, so the words are the composition's.
+
+   sealhip_rgsw owns one device block [half][digit][component][n_key][N], half 0 = K_b, half 1 = K_a, each half in the
+   layout of sealhip_kswitch_key_load.
+   sealhip_generate_rgsw: n objects from m_coeff (n x N int32, DEVICE, coefficient form, small signed values). m is lifted
+     over the key primes as a secret key is (-v -> q_j - v) and transformed, m s is a dyadic product with sk_ntt, and half h
+     of message i is generated by the code behind sealhip_generate_switching_keys from seeds_host[i][h] (n x 2 x digits x 8
+     words, HOST) and noise[i][h] (n x 2 x digits x N int32, DEVICE): every word is what that entry gives for
+     sk_from = {NTT(m_i), NTT(m_i) (.) sk} with the same samples. level as there (1 .. n_ct). The lifted m and m s live in
+     scratch that is erased in stream order. Checks: NULL ctx or sk_ntt, and with n > 0 NULL m_coeff, seeds_host, noise or
+     out -> E_POINTER (every out[i] is NULL after any failure); then, also on host-only contexts, level outside 1 .. n_ct ->
+     E_INVALIDARG; then a host-only context -> COR_E_INVALIDOPERATION; n == 0 -> S_OK; during a graph capture ->
+     COR_E_INVALIDOPERATION. Allocates, and synchronises the calling thread's lane before it returns.
+     Unlike sealhip_generate_switching_keys (at most 14 keys) there is no limit on n: the 2 n halves are assembled in
+     batches. The scratch is erased before it is freed on the failure paths too.
+   sealhip_rgsw_create: the object from two ordinary key handles (for example loaded from a stream), a device copy; refuses
+     digit counts or levels that differ (E_INVALIDARG). sealhip_rgsw_export: keys[0] = K_b, keys[1] = K_a as two ordinary,
+     owned key handles holding copies of the halves (the saves and the partial / finish entries work on them); both NULL
+     after a failure. sealhip_rgsw_destroy: as sealhip_kswitch_key_destroy -- it waits for every lane, and graphs captured
+     earlier are stale afterwards.
+
+   The evaluator entries work on `count` size-2 ciphertexts at level k (count x 2 x k x N, DEVICE; CKKS in NTT form in both
+   modes; BFV in coefficient form on a STRICT context -- PARITY BFV's in-bundle rows are the fork's quirk and do not
+   decrypt) with ONE rgsw shared by the batch.
+   sealhip_evaluator_external_product: out = base + ct (x) rgsw; base (count x 2 x k x N) may be NULL, meaning zero.
+   sealhip_evaluator_cmux: out = ct0 + (ct1 - ct0) (x) rgsw, i.e. ct1 where rgsw encrypts 1 and ct0 where it encrypts 0; one
+     streaming kernel reads both operands once and writes the difference and the copy of ct0 the mod-down adds into. The
+     words are sealhip_evaluator_external_product(sub(ct1, ct0), base = ct0)'s.
+   sealhip_evaluator_select: cts: count x 2^l x 2 x k x N; out: count x 2 x k x N = cts[.][index] for the index whose bit t
+     (least significant first) rgsw_bits[t] encrypts. Level t = 0 .. l - 1 computes W'[i] = cmux(rgsw_bits[t]; W[2i],
+     W[2i+1]): one prepare launch and one external product batched over count * 2^(l-t-1) pairs. l == 0 is a copy. The
+     working sets between the levels (2^(l-1) + 2^(l-2) ciphertexts per item) and the differences (2^(l-1)) are parked in the
+     lane's arena under a raised floor and take at most half of its cap; a batch that does not fit is walked in chunks of
+     items and sealhip_debug_chunk_log ends with (count, items per chunk); when one item does not fit -> E_OUTOFMEMORY with
+     a message that names both sizes.
+   Checks, in this order: NULL ctx, ciphertext operands, out, rgsw (select: with l > 0 the list and every entry) ->
+   E_POINTER; then, also on host-only contexts: k outside the ciphertext levels, (select) l > 16, BFV in PARITY mode, an
+   operand, base or out not 16-byte aligned, out overlapping an operand or base -> E_INVALIDARG; then a host-only context
+   -> COR_E_INVALIDOPERATION; then an rgsw that does not serve level k (fewer digits than the level needs, or made for a
+   lower level: "rgsw is not valid for encryption parameters") -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched.
+   With a transparency sink: one flag per output ciphertext, from the (last) mod-down, or from a read pass for l == 0.
+   Nothing synchronises; capturable once the arena has its size (after one call of the same shape).
+   sealhip_debug_ext_mac_plan: what the inner product's launcher would run for a chunk of `count` items at level k, with no
+     launch: out[0] = 1 (the loop kernel) or 2 (the items family), out[1] = the instance's ND2 (0 for the loop kernel),
+     out[2] = 1 when the 2 nd-term sum does not fit 128 bits and is reduced between its halves, out[3] = the item group. */
+typedef struct sealhip_rgsw sealhip_rgsw;
+long sealhip_generate_rgsw(sealhip_context *ctx, const uint64_t *sk_ntt, const int32_t *m_coeff, uint32_t n, uint32_t level,
+                           const uint64_t *seeds_host, const int32_t *noise, sealhip_rgsw **out);
+long sealhip_rgsw_create(sealhip_context *ctx, const sealhip_kswitch_key *key_b, const sealhip_kswitch_key *key_a,
+                         sealhip_rgsw **out);
+long sealhip_rgsw_export(sealhip_context *ctx, const sealhip_rgsw *rgsw, sealhip_kswitch_key **keys);
+long sealhip_rgsw_destroy(sealhip_context *ctx, sealhip_rgsw *rgsw);
+long sealhip_evaluator_external_product(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t count,
+                                        const sealhip_rgsw *rgsw, const uint64_t *base, uint64_t *out);
+long sealhip_evaluator_cmux(sealhip_context *ctx, uint32_t k, const uint64_t *ct0, const uint64_t *ct1, size_t count,
+                            const sealhip_rgsw *rgsw, uint64_t *out);
+long sealhip_evaluator_select(sealhip_context *ctx, uint32_t k, const uint64_t *cts, size_t count, uint32_t l,
+                              const sealhip_rgsw *const *rgsw_bits, uint64_t *out);
+long sealhip_debug_ext_mac_plan(sealhip_context *ctx, uint32_t k, size_t count, int32_t out[4]);
 /* stream-ordered hipMemsetAsync(dptr, 0, bytes) on the calling thread's lane: erases scratch that held secret samples
    before it goes back to a pool (the reference's clear_on_destruction pool, util/rlwe.cpp:141). Does not synchronise. */
 long sealhip_memset_zero(sealhip_context *ctx, void *dptr, size_t bytes);
