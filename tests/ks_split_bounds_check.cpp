@@ -13,7 +13,9 @@
 //    that has no such instance is refused: a row that is not gathered, a Harvey, floating-point or special-prime choice, a
 //    canonical launch, a prime outside the bound. Without the flag nothing is split (tests/ntt_select_check.cpp pins that domain).
 // 3. Just above the bound (one bit more, the same adversarial words): the recurrence says 2^64 is passed, and the predicate refuses.
+// `ks_split_bounds_check --bits` only prints the admitted prime sizes (tests/test_ks_instances_host.py holds them against its own).
 #include <cstdio>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -201,8 +203,20 @@ static void selection()
     }
 }
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && !std::strcmp(argv[1], "--bits"))
+    {
+        // what tests/test_ks_instances_host.py restates: per ring the prime sizes the split form and the lazy schedule admit,
+        // then the size below which a launch takes the floating-point schedule and the size of its raw inputs
+        for (int logn = kMinHalfLogn; logn <= kMaxHalfLogn; logn++)
+            std::printf("ring %d split %d lazy %d\n", logn, fwd_split_prime_bits(logn), fwd_lazy_prime_bits(logn));
+        int input_bits = 0;
+        while ((u64(1) << input_bits) < kFpInputBound)
+            input_bits++;
+        std::printf("fp %d input %d\n", kFpPrimeBits, input_bits);
+        return 0;
+    }
     predicate();
     selection();
     for (int logn = kMinHalfLogn; logn <= kMaxHalfLogn; logn++)

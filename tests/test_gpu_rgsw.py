@@ -5,9 +5,13 @@ that existed before (rgsw_export, two switch_key_partial, an add, switch_key_fin
 Shapes: the smallest that reach every path. Rings of 2^3 and 2^4 (less than a workgroup per row: the loop kernel at every
 batch), 2^8 and 2^9 (the first rings with the items family) and 2^12 (several workgroups per row); batches of 1, 15, 16, 17
 and 33 (the items threshold and a ragged last group); the first level and level 1; one, two and three special primes with a
-short last digit; nine digits (2 nd = 18: no instance); six 61-bit primes (2 nd = 10 terms do not fit 128 bits: the sum is
+short last digit; nine digits (2 nd = 18: no instance); seven digits at levels 7 and 6 (2 nd = 14 and 12, the two instances
+no other chain reaches); six 61-bit primes (2 nd = 10 terms do not fit 128 bits: the sum is
 reduced between its halves, in both kernels); the 61/20/45/61 chain; CKKS in both modes and BFV in STRICT. Word comparisons
-need no valid keys: the RGSW block is two random keys. The semantic runs use keys the library generated."""
+need no valid keys: the RGSW block is two random keys. The semantic runs use keys the library generated.
+COMPARED lists every (chain, log N, level, batch) that `compare` is given; tests/test_rgsw_host.py evaluates the selector's rule
+over it and asserts, without a device, that the runs reach every instance of the items family and the loop kernel for each of
+its reasons."""
 import os
 import sys
 
@@ -17,7 +21,7 @@ import pytest
 import oracle_lib as O
 import rgsw_ref as G
 from support import ARENA_MB, BaseSession, S, child_main, compile_cpp, rows, run_arena_child, run_exe, session_memo, top
-from test_rgsw_host import select_ext_mac
+from test_rgsw_host import select_ext_mac, sum_is_split
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0x5E5E5E5E5E5E5E5E
@@ -29,10 +33,33 @@ CHAINS = {
     "bfv nsp2": (1, [30, 35, 40, 45, 50, 55, 60], 2, 65537, 1),  # five ciphertext primes: digits of 2, 2 and 1
     "ckks nsp3": (2, [40] * 4 + [41] * 3, 3, 0, 1),               # four: digits of 3 and 1
     "nd9": (2, [30] * 9 + [31], 1, 0, 1),                        # 2 nd = 18: the loop kernel at every batch
+    "nd7": (2, [40] * 7 + [41], 1, 0, 1),                        # 2 nd = 14, and 12 one level down
     "61": (2, [61] * 6, 1, 0, 1),                                # nd = 5: ten terms of 61-bit primes, the split sum
     "bfv 61": (1, [61] * 6, 1, 65537, 1),
     "mixed": (2, [61, 20, 45, 61], 1, 0, 1),
 }
+
+
+def first_level(chain):
+    return len(CHAINS[chain][1]) - CHAINS[chain][2]
+
+
+THRESHOLD_CHAINS = ("ckks nsp1", "ckks parity", "bfv nsp2", "ckks nsp3", "mixed")
+SEVEN_DIGITS = (("nd7", 8, 7, 17), ("nd7", 8, 6, 17), ("nd7", 8, 7, 1))  # ND2 = 14, ND2 = 12, the loop kernel below 16 items
+# every (chain, log N, level, batch) a test below hands to Session.compare (which refuses anything else)
+COMPARED = set(SEVEN_DIGITS)
+for _chain in ("ckks nsp1", "bfv nsp2", "ckks nsp3"):
+    for _logn in (3, 4):
+        COMPARED |= {(_chain, _logn, first_level(_chain), 1), (_chain, _logn, first_level(_chain), 17), (_chain, _logn, 1, 3)}
+for _chain in THRESHOLD_CHAINS:
+    for _logn in (8, 9):
+        COMPARED |= {(_chain, _logn, first_level(_chain), _count) for _count in (1, 15, 16, 17, 33)} | {(_chain, _logn, 1, 17)}
+for _chain in ("ckks nsp1", "bfv nsp2"):
+    COMPARED |= {(_chain, 12, first_level(_chain), 1), (_chain, 12, first_level(_chain), 33), (_chain, 12, 1, 16)}
+COMPARED |= {("nd9", 8, 9, 1), ("nd9", 8, 9, 17), ("nd9", 8, 8, 17)}
+for _chain in ("61", "bfv 61"):
+    COMPARED |= {(_chain, 8, 5, 1), (_chain, 8, 5, 17), (_chain, 8, 4, 17)}
+COMPARED |= {(_chain, 8, first_level(_chain), 17) for _chain in ("ckks nsp1", "bfv nsp2", "mixed")}
 
 
 class Session(BaseSession):
@@ -52,6 +79,7 @@ class Session(BaseSession):
         nd = -(-k // self.nsp)
         want = select_ext_mac(self.logn, nd, k + self.nsp, count)
         assert (got["family"], got["nd2"], got["group"]) == want[:3], (self.chain, k, count, got, want)
+        assert got["split"] == sum_is_split(nd, max(self.mods[:k] + self.mods[self.kf:])), (self.chain, k, count, got)
         return got
 
     def run(self, fn, inputs, count, k, flags_for=None):
@@ -101,6 +129,7 @@ class Session(BaseSession):
         return acc.download((count, 2, k, self.n))
 
     def compare(self, k, count, with_base=True, ct=None, tag=""):
+        assert (self.chain, self.logn, k, count) in COMPARED, "a comparison the host test's table does not list"
         self.plan(k, count)
         if ct is None:
             ct = rows(self.rng, self.mods[:k], self.n, (count, 2))
@@ -169,7 +198,7 @@ def test_external_product_small_rings(S, chain, logn):
     s.compare(1, 3, with_base=False)
 
 
-@pytest.mark.parametrize("chain", ["ckks nsp1", "ckks parity", "bfv nsp2", "ckks nsp3", "mixed"])
+@pytest.mark.parametrize("chain", THRESHOLD_CHAINS)
 @pytest.mark.parametrize("logn", [8, 9])
 def test_external_product_items_threshold(S, chain, logn):
     """either side of 16 items and the group edges, on the first rings with one workgroup (2^8) and two (2^9) per row"""
@@ -197,6 +226,17 @@ def test_external_product_nine_digits(S):
         s.compare(s.kf, count)
     assert s.plan(8, 17)["family"] == "items" and s.plan(8, 17)["nd2"] == 16  # (one level down the family's last instance)
     s.compare(8, 17)
+
+
+def test_external_product_seven_digits(S):
+    """seven ciphertext primes and one special prime: ext_mac_items_kernel<14> at the first level and <12> one below, the two
+    instances between the five-digit chains and nd9's level 8; one item at the first level takes the loop kernel with the
+    same fourteen terms"""
+    for chain, logn, k, count in SEVEN_DIGITS:
+        s = session(S, chain, logn)
+        plan = s.plan(k, count)
+        assert (plan["family"], plan["nd2"]) == (("items", 2 * k) if count >= 16 else ("loop", 0)) and not plan["split"]
+        s.compare(k, count)
 
 
 @pytest.mark.parametrize("chain", ["61", "bfv 61"])

@@ -366,6 +366,45 @@ def select_ext_mac(logn, nd, rows, count):
     return ("loop", 0, 0, 0, blocks_for((count * rows) << logn))
 
 
+def sum_is_split(nd, pmax):
+    """ext_mac_plan's other decision (rgsw.hip; bounds::ext_mac_sum_fits): 2 nd products of a digit word (any 64-bit word) by
+    a key word (at most pmax - 1), and one more such word, do not fit 128 bits -- the sum is reduced between its halves"""
+    return 2 * nd > ((1 << 128) - 1 - (pmax - 1)) // (((1 << 64) - 1) * (pmax - 1))
+
+
+def test_the_gpu_comparisons_reach_every_instance():
+    """the (chain, log N, level, batch) tuples tests/test_gpu_rgsw.py compares word for word -- its COMPARED, which its
+    Session.compare enforces -- through the rule above: every even ND2 = 2..16 of the items family, the loop kernel for each
+    of its three reasons, and the split sum in both families"""
+    import test_gpu_rgsw as R  # (it imports this module: resolved at the call)
+
+    items, loop_reasons, split = set(), set(), set()
+    for chain, logn, k, count in R.COMPARED:
+        _, bits, nsp, _, _ = R.CHAINS[chain]
+        assert 1 <= k <= len(bits) - nsp, (chain, k)
+        nd = -(-k // nsp)
+        mods = [int(p) for p in O.coeff_modulus_create(1 << logn, bits)]
+        family, nd2 = select_ext_mac(logn, nd, k + nsp, count)[:2]
+        if family == "items":
+            assert nd2 == 2 * nd
+            items.add(nd2)
+        else:
+            assert family == "loop"
+            # (the first reason that applies, in the selector's order)
+            loop_reasons.add("small batch" if count < 16 else ("ring below a workgroup" if 1 << logn < K_THREADS else "no instance"))
+            assert count < 16 or 1 << logn < K_THREADS or 2 * nd > INSTANCES
+        if sum_is_split(nd, max(mods[:k] + mods[len(bits) - nsp:])):
+            split.add(family)
+    assert items == set(range(2, INSTANCES + 1, 2)), sorted(items)
+    assert loop_reasons == {"small batch", "ring below a workgroup", "no instance"}
+    assert split == {"items", "loop"}
+    # each reason alone: a full batch on a small ring, a full batch on a full ring at nine digits
+    assert any(count >= 16 and logn < 8 for _, logn, _, count in R.COMPARED)
+    assert ("nd9", 8, 9, 17) in R.COMPARED and select_ext_mac(8, 9, 10, 17)[0] == "loop"
+    assert {t[2:] for t in R.SEVEN_DIGITS} == {(7, 17), (6, 17), (7, 1)} <= {t[2:] for t in R.COMPARED if t[0] == "nd7"}
+    assert not sum_is_split(8, (1 << 60) - 1) and sum_is_split(5, (1 << 61) - 1) and not sum_is_split(4, (1 << 61) - 1)
+
+
 def test_the_selector_and_the_rule_here_agree_call_by_call(tmp_path):
     exe = compile_cpp(tmp_path, "ext_select_check.cpp", extra=("-I", CSRC))
     assert "ext_select_check: OK" in run_exe(exe, timeout=120)
