@@ -4429,6 +4429,8 @@ namespace
         if (g->key.n_digits < kswitch_digits(e, k) || (g->key.level && k > g->key.level))
             throw std::invalid_argument("rgsw is not valid for encryption parameters");
     }
+    void make_rgsw_objects(Engine &e, const uint64_t *sk_ntt, const int32_t *m_coeff, uint32_t n, uint32_t level,
+                           const uint64_t *seeds_host, const int32_t *noise, sealhip_rgsw **out);
 } // namespace
 } // extern "C++"
 
@@ -4450,6 +4452,18 @@ long sealhip_generate_rgsw(sealhip_context *ctx, const uint64_t *sk_ntt, const i
         Engine &e = device_engine(ctx);
         if (n == 0)
             return;
+        make_rgsw_objects(e, sk_ntt, m_coeff, n, level, seeds_host, noise, out);
+    });
+}
+
+extern "C++" {
+namespace
+{
+    // n owned objects from m_coeff (device) on a device context, n > 0: the body of sealhip_generate_rgsw, which
+    // sealhip_generate_blind_rotation_keys shares. out is filled only on success.
+    void make_rgsw_objects(Engine &e, const uint64_t *sk_ntt, const int32_t *m_coeff, uint32_t n, uint32_t level,
+                           const uint64_t *seeds_host, const int32_t *noise, sealhip_rgsw **out)
+    {
         if (e.lane().capturing)
             throw std::logic_error("key generation allocates and synchronises: it cannot be captured in a graph");
         const uint32_t digits = kswitch_digits(e, static_cast<uint32_t>(e.k_first));
@@ -4489,8 +4503,9 @@ long sealhip_generate_rgsw(sealhip_context *ctx, const uint64_t *sk_ntt, const i
         SEALHIP_CHECK(hipFree(scratch)); // (erased in stream order, and the lane is idle)
         for (uint32_t i = 0; i < n; i++)
             out[i] = made[i].release();
-    });
-}
+    }
+} // namespace
+} // extern "C++"
 
 long sealhip_rgsw_create(sealhip_context *ctx, const sealhip_kswitch_key *key_b, const sealhip_kswitch_key *key_a,
                          sealhip_rgsw **out)
@@ -4661,6 +4676,161 @@ long sealhip_debug_ext_mac_plan(sealhip_context *ctx, uint32_t k, size_t count, 
         out[1] = plan.choice.nd;
         out[2] = plan.split ? 1 : 0;
         out[3] = static_cast<int32_t>(plan.choice.group);
+    });
+}
+
+/* ---------------------------------------------------------------- blind rotation */
+extern "C++" {
+namespace
+{
+    bool bytes_overlap(const void *a, std::size_t a_bytes, const void *b, std::size_t b_bytes)
+    {
+        const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
+        return x < y + b_bytes && y < x + a_bytes;
+    }
+    // The checks multiply_monomial and blind_rotate share, in the header's order, up to the device. ct: n_ct size-2
+    // ciphertexts; exps: count rows of exps_stride words, of which exps_row are read.
+    Engine &monomial_entry_checks(sealhip_context *ctx, uint32_t k, const char *what, const uint64_t *ct, size_t n_ct, size_t count,
+                                  const uint32_t *exps, size_t exps_stride, size_t exps_row, const uint64_t *out)
+    {
+        Engine &h = *ctx->engine;
+        check_data_level(h, k);
+        if (n_ct != 1 && n_ct != count)
+            throw std::invalid_argument("n_ct must be 1 (one operand shared by the batch) or count");
+        if (h.scheme == 1 && !h.mode_strict)
+            throw std::invalid_argument(std::string(what) + " of BFV ciphertexts needs a STRICT context");
+        if (reinterpret_cast<uintptr_t>(ct) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+            throw std::invalid_argument("the operands and out must be 16-byte aligned");
+        if (reinterpret_cast<uintptr_t>(exps) % 4)
+            throw std::invalid_argument("exps must be 4-byte aligned");
+        const std::size_t ct_bytes = 2 * static_cast<std::size_t>(k) * h.n * sizeof(u64);
+        const std::size_t exps_bytes = count ? ((count - 1) * exps_stride + exps_row) * sizeof(uint32_t) : 0;
+        if (bytes_overlap(out, count * ct_bytes, ct, n_ct * ct_bytes) || bytes_overlap(out, count * ct_bytes, exps, exps_bytes))
+            throw std::invalid_argument("out must not overlap an operand or exps");
+        return device_engine(ctx);
+    }
+} // namespace
+} // extern "C++"
+
+long sealhip_evaluator_multiply_monomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t n_ct, size_t count,
+                                         const uint32_t *exps_dev, size_t exps_stride, int32_t minus_one, uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(ct);
+    REQUIRE_PTR(exps_dev);
+    REQUIRE_PTR(out);
+    return guarded([&] {
+        Engine &e = monomial_entry_checks(ctx, k, "the monomial product", ct, n_ct, count, exps_dev, exps_stride, 1, out);
+        if (count == 0)
+            return;
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+        SinkScope sink(e, count);
+        op_multiply_monomial(e, static_cast<int>(k), reinterpret_cast<const u64 *>(ct), n_ct == count ? 2 * poly : 0, count, exps_dev,
+                             exps_stride, minus_one != 0, reinterpret_cast<u64 *>(out));
+        sink.read_pass(reinterpret_cast<const u64 *>(out), 2, poly, count);
+    });
+}
+
+long sealhip_lwe_mod_switch(sealhip_context *ctx, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t n_samples,
+                            int32_t ternary, uint32_t b_offset, uint32_t *exps_out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(lwe_a);
+    REQUIRE_PTR(lwe_b);
+    REQUIRE_PTR(exps_out);
+    return guarded([&] {
+        Engine &h = *ctx->engine;
+        check_data_level(h, 1);
+        if (reinterpret_cast<uintptr_t>(lwe_a) % 16 || reinterpret_cast<uintptr_t>(lwe_b) % 8)
+            throw std::invalid_argument("lwe_a must be 16-byte aligned and lwe_b 8-byte aligned");
+        if (reinterpret_cast<uintptr_t>(exps_out) % 4)
+            throw std::invalid_argument("exps_out must be 4-byte aligned");
+        const std::size_t out_bytes = n_samples * (1 + (ternary ? 2 : 1) * h.n) * sizeof(uint32_t);
+        if (bytes_overlap(exps_out, out_bytes, lwe_a, n_samples * h.n * sizeof(u64)) ||
+            bytes_overlap(exps_out, out_bytes, lwe_b, n_samples * sizeof(u64)))
+            throw std::invalid_argument("exps_out must not overlap lwe_a or lwe_b");
+        Engine &e = device_engine(ctx);
+        if (n_samples == 0)
+            return;
+        op_lwe_mod_switch(e, reinterpret_cast<const u64 *>(lwe_a), reinterpret_cast<const u64 *>(lwe_b), n_samples, ternary != 0,
+                          b_offset, exps_out);
+    });
+}
+
+long sealhip_generate_blind_rotation_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const int32_t *lwe_secret_dev,
+                                          uint32_t n_lwe, int32_t ternary, uint32_t level, const uint64_t *seeds_host,
+                                          const int32_t *noise, sealhip_rgsw **out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(sk_ntt);
+    const uint32_t per = ternary ? 2 : 1;
+    if (n_lwe)
+    {
+        REQUIRE_PTR(lwe_secret_dev);
+        REQUIRE_PTR(seeds_host);
+        REQUIRE_PTR(noise);
+        REQUIRE_PTR(out);
+        if (n_lwe <= UINT32_MAX / per)
+            std::fill(out, out + static_cast<std::size_t>(n_lwe) * per, nullptr);
+    }
+    return guarded([&] {
+        check_data_level(*ctx->engine, level);
+        if (n_lwe > UINT32_MAX / per)
+            throw std::invalid_argument("n_lwe out of range");
+        Engine &e = device_engine(ctx);
+        if (n_lwe == 0)
+            return;
+        if (e.lane().capturing)
+            throw std::logic_error("key generation allocates and synchronises: it cannot be captured in a graph");
+        const uint32_t n = n_lwe * per;
+        const std::size_t m_bytes = static_cast<std::size_t>(n) * e.n * sizeof(int32_t);
+        Scratch scratch(e);
+        int32_t *m_coeff = reinterpret_cast<int32_t *>(scratch.take(m_bytes));
+        // the indicators tell the secret: erased in stream order before the block goes back, on the failure paths too
+        struct Erase
+        {
+            Engine &e;
+            void *p;
+            std::size_t bytes;
+            ~Erase()
+            {
+                (void)hipMemsetAsync(p, 0, bytes, e.lane().stream);
+            }
+        } erase{ e, m_coeff, m_bytes };
+        check(launch_lwe_indicators(e, lwe_secret_dev, n_lwe, ternary != 0, m_coeff), "lwe_indicators");
+        make_rgsw_objects(e, sk_ntt, m_coeff, n, level, seeds_host, noise, out);
+    });
+}
+
+long sealhip_evaluator_blind_rotate(sealhip_context *ctx, uint32_t k, const uint64_t *tv, size_t n_tv, size_t count,
+                                    const uint32_t *exps_dev, uint32_t n_steps, const sealhip_rgsw *const *rgsw_list,
+                                    uint64_t *out)
+{
+    REQUIRE_PTR(ctx);
+    REQUIRE_PTR(tv);
+    REQUIRE_PTR(exps_dev);
+    REQUIRE_PTR(out);
+    if (n_steps)
+    {
+        REQUIRE_PTR(rgsw_list);
+        for (uint32_t t = 0; t < n_steps; t++)
+            REQUIRE_PTR(rgsw_list[t]);
+    }
+    return guarded([&] {
+        const std::size_t row = static_cast<std::size_t>(n_steps) + 1;
+        Engine &e = monomial_entry_checks(ctx, k, "blind rotation", tv, n_tv, count, exps_dev, row, row, out);
+        std::vector<const RgswKey *> keys(n_steps);
+        for (uint32_t t = 0; t < n_steps; t++)
+        {
+            check_rgsw_level(e, k, rgsw_list[t]);
+            keys[t] = &rgsw_list[t]->key;
+        }
+        if (count == 0)
+            return;
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+        SinkScope sink(e, count);
+        op_blind_rotate(e, static_cast<int>(k), reinterpret_cast<const u64 *>(tv), n_tv == count ? 2 * poly : 0, count, exps_dev,
+                        n_steps, keys.data(), reinterpret_cast<u64 *>(out), sink);
     });
 }
 

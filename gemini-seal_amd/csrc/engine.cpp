@@ -911,6 +911,31 @@ namespace sealhip
         return d_expand_mono = upload<u64>(*this, owned, pairs.data(), pairs.size());
     }
 
+    const u64 *Engine::psi_powers()
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (d_psi_pow)
+            return d_psi_pow;
+        if (lane().capturing)
+            throw std::logic_error("the table of root powers is not built yet: run the sequence once before capturing");
+        // psi_r^j, j < N, by repeated multiplication on the host, each with its Shoup companion
+        const std::size_t kf = static_cast<std::size_t>(k_first);
+        std::vector<u64> pairs(2 * kf * n);
+        for (std::size_t r = 0; r < kf; r++)
+        {
+            const u64 p = key_moduli[r], psi = tables[r].psi;
+            u64 w = 1;
+            for (std::size_t j = 0; j < n; j++)
+            {
+                pairs[2 * (r * n + j)] = w;
+                pairs[2 * (r * n + j) + 1] = shoup(w, p);
+                w = mulmod(w, psi, p);
+            }
+        }
+        SEALHIP_CHECK(hipSetDevice(device));
+        return d_psi_pow = upload<u64>(*this, owned, pairs.data(), pairs.size());
+    }
+
     void Engine::ckks_tables()
     {
         std::lock_guard<std::mutex> lock(mu);

@@ -400,6 +400,10 @@ namespace sealhip
         // oblivious expansion: NTT_r(X^(-2^u)) for u < logn, the same layout: [u][k_first][N][2]
         u64 *d_expand_mono = nullptr;
         const u64 *expand_monomials();
+        // blind rotation: psi_r^j for j < N in natural order and every ciphertext prime r, as
+        // {word, Shoup companion} pairs: [k_first][N][2]; psi^(N + j) = -psi^j, so the kernel keeps the sign apart
+        u64 *d_psi_pow = nullptr;
+        const u64 *psi_powers();
         mutable std::mutex mu; // lazily built shared tables (levels, Galois tables, encoder tables, parms_ids)
         // profiler (per lane)
         void prof_begin(const char *tag, double units) const;
@@ -993,6 +997,27 @@ namespace sealhip
     hipError_t launch_ext_mac(const Engine &e, const KsDev *d, const KsDev &h, const u64 *own0, const u64 *own1,
                               std::size_t own_stride, const u64 *ext, std::size_t ext_stride, std::size_t ext_digit_stride,
                               const u64 *key_b, const u64 *key_a, u64 *prod, std::size_t prod_stride, std::size_t count);
+    // blind rotation (blindrot.hip).
+    // dst[i] = X^(e_i) src[i] - minus_one * src[i] for count size-2 ciphertexts at level k, e_i = exps[i * exps_stride + step]
+    // mod 2N (device); src_stride 0 shares one operand. ntt_form: psi_pow = Engine::psi_powers. dst does not overlap src.
+    hipError_t launch_monomial_prepare(const Engine &e, int k, bool ntt_form, bool minus_one, const u64 *src, std::size_t src_stride,
+                                       u64 *dst, std::size_t dst_stride, const std::uint32_t *exps, std::size_t exps_stride,
+                                       std::size_t step, const u64 *psi_pow, std::size_t count);
+    // exps[n_samples][1 + (ternary ? 2N : N)] from the level-1 samples lwe_a[n_samples][N], lwe_b[n_samples]
+    hipError_t launch_lwe_mod_switch(const Engine &e, const u64 *lwe_a, const u64 *lwe_b, std::size_t n_samples, bool ternary,
+                                     std::uint32_t b_offset, std::uint32_t *exps);
+    // m_coeff[n_lwe * (ternary ? 2 : 1)][N]: the constant polynomials [s_j = 1] (and [s_j = -1]) of secret[n_lwe] (device)
+    hipError_t launch_lwe_indicators(const Engine &e, const std::int32_t *secret, std::size_t n_lwe, bool ternary,
+                                     std::int32_t *m_coeff);
+    // out[i] = X^(e_i) ct[i] - minus_one * ct[i], e_i = exps[i * exps_stride] (ct_stride 0: one ct shared by the batch)
+    void op_multiply_monomial(Engine &e, int k, const u64 *ct, std::size_t ct_stride, std::size_t count, const std::uint32_t *exps,
+                              std::size_t exps_stride, bool minus_one, u64 *out);
+    // acc_0 = X^(exps[i][0]) tv[i]; acc_t = acc_(t-1) + ((X^(exps[i][t]) - 1) acc_(t-1)) (x) rgsw[t-1]; out = acc_(n_steps).
+    // exps: count x (1 + n_steps) words (device). The accumulator lives in out from step 0 on.
+    void op_blind_rotate(Engine &e, int k, const u64 *tv, std::size_t tv_stride, std::size_t count, const std::uint32_t *exps,
+                         std::size_t n_steps, const RgswKey *const *rgsw, u64 *out, SinkScope &sink);
+    void op_lwe_mod_switch(Engine &e, const u64 *lwe_a, const u64 *lwe_b, std::size_t n_samples, bool ternary,
+                           std::uint32_t b_offset, std::uint32_t *exps);
     // diff[i] = ct1[i] - ct0[i] (2 k N words per item, back to back) and base[i] = ct0[i], for npairs ciphertext pairs whose
     // operands lie stride0 / stride1 words apart; everything 16-byte aligned
     hipError_t launch_cmux_prepare(const Engine &e, int k, const u64 *ct0, std::size_t stride0, const u64 *ct1,

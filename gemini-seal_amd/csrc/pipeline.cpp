@@ -1804,6 +1804,82 @@ namespace sealhip
     }
 
     // ------------------------------------------------------------------------------------------
+    // Blind rotation: the monomial product with an exponent per item, and the accumulator loop
+    // ------------------------------------------------------------------------------------------
+    namespace
+    {
+        // the form the scheme's ciphertexts are in, with the checks both entries share; the table where the form needs it
+        const u64 *monomial_form(Engine &e, int k, bool &ntt_form)
+        {
+            if (k > e.k_first)
+                throw std::invalid_argument("level k out of range");
+            if (e.scheme != 2 && !e.mode_strict)
+                throw std::invalid_argument("the monomial product of BFV ciphertexts needs a STRICT context");
+            ntt_form = e.scheme == 2;
+            return ntt_form ? e.psi_powers() : nullptr;
+        }
+    } // namespace
+
+    void op_multiply_monomial(Engine &e, int k, const u64 *ct, std::size_t ct_stride, std::size_t count, const std::uint32_t *exps,
+                              std::size_t exps_stride, bool minus_one, u64 *out)
+    {
+        bool ntt_form;
+        const u64 *psi = monomial_form(e, k, ntt_form);
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n;
+        check(launch_monomial_prepare(e, k, ntt_form, minus_one, ct, ct_stride, out, 2 * poly, exps, exps_stride, 0, psi, count),
+              "monomial_prepare");
+    }
+
+    // The whole step loop runs inside a chunk of items. Step 0 writes X^(e_0) tv into the caller's out, which is the
+    // accumulator from then on; step t reads it once and writes only the target (X^(e_t) - 1) acc into the arena, and the
+    // external product's mod-down adds into the accumulator in place: 4 polynomials moved per step around the key switch.
+    // The arena is one target of 2 k N words per item beside the external product's own buffers, which every step carves
+    // anew from the same mark. Nothing is read back or synchronised between the steps.
+    void op_blind_rotate(Engine &e, int k, const u64 *tv, std::size_t tv_stride, std::size_t count, const std::uint32_t *exps,
+                         std::size_t n_steps, const RgswKey *const *rgsw, u64 *out, SinkScope &sink)
+    {
+        bool ntt_form;
+        const u64 *psi = monomial_form(e, k, ntt_form);
+        for (std::size_t t = 0; t < n_steps; t++)
+            (void)ext_product_level(e, k, *rgsw[t]);
+        const std::size_t poly = static_cast<std::size_t>(k) * e.n, ct_words = 2 * poly, row = 1 + n_steps;
+        if (!n_steps)
+        {
+            check(launch_monomial_prepare(e, k, ntt_form, false, tv, tv_stride, out, ct_words, exps, row, 0, psi, count),
+                  "monomial_prepare");
+            sink.read_pass(out, 2, poly, count);
+            log_chunk(e, count, count);
+            return;
+        }
+        LevelTools &lt = e.level(k);
+        const KsArena ar = ext_product_arena(e, k);
+        sink.begin();
+        Lane &lane = e.lane();
+        for_chunks(e, count, ar.item_bytes() + ct_words * sizeof(u64), kExtProductBuffers + 1, [&](std::size_t off, std::size_t m) {
+            u64 *acc = out + off * ct_words;
+            const std::uint32_t *ex = exps + off * row;
+            u64 *target = e.ws_alloc(ct_words * m);
+            const std::size_t mark = lane.ws_used;
+            check(launch_monomial_prepare(e, k, ntt_form, false, tv + off * tv_stride, tv_stride, acc, ct_words, ex, row, 0, psi, m),
+                  "monomial_prepare");
+            for (std::size_t t = 1; t <= n_steps; t++)
+            {
+                lane.ws_used = mark;
+                check(launch_monomial_prepare(e, k, ntt_form, true, acc, ct_words, target, ct_words, ex, row, t, psi, m),
+                      "monomial_prepare");
+                // (the last step's mod-down carries the flags, one per output ciphertext)
+                ext_product_chunk(e, lt, k, ar, target, ct_words, m, *rgsw[t - 1], acc, t == n_steps ? sink_at(e, off) : nullptr);
+            }
+        });
+    }
+
+    void op_lwe_mod_switch(Engine &e, const u64 *lwe_a, const u64 *lwe_b, std::size_t n_samples, bool ternary,
+                           std::uint32_t b_offset, std::uint32_t *exps)
+    {
+        check(launch_lwe_mod_switch(e, lwe_a, lwe_b, n_samples, ternary, b_offset, exps), "lwe_mod_switch");
+    }
+
+    // ------------------------------------------------------------------------------------------
     // Hoisted rotation: n_elts automorphisms of the same ciphertexts with one decomposition of c_1
     // ------------------------------------------------------------------------------------------
     // out_g = finish( (sigma_g(c_0), 0), sum_j sigma_g(D_j) (.) K_g ), D_j the digits op_switch_key forms for the target c_1.

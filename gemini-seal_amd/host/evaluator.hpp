@@ -22,6 +22,7 @@
 #include <cmath>
 #include <complex>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <memory>
@@ -643,6 +644,39 @@ namespace sealhip_host
         const Context &c_;
         sealhip_rgsw *g_ = nullptr;
     };
+
+    // The keys of a blind rotation, resident on the device: the RGSW encryptions of the indicators
+    // [s_j = 1] (and, for a ternary secret, [s_j = -1] behind each) of an LWE secret, in step order. Made by
+    // KeyGenerator::blind_rotation_keys; Evaluator::blind_rotate takes them.
+    class BlindRotationKeys
+    {
+    public:
+        BlindRotationKeys(std::vector<std::unique_ptr<RgswCiphertext>> keys, bool ternary) : keys_(std::move(keys)), ternary_(ternary)
+        {
+            for (const auto &g : keys_)
+                raw_.push_back(g->get());
+        }
+        std::size_t n_steps() const { return keys_.size(); }
+        bool ternary() const { return ternary_; }
+        const sealhip_rgsw *const *get() const { return raw_.empty() ? nullptr : raw_.data(); }
+
+    private:
+        std::vector<std::unique_ptr<RgswCiphertext>> keys_;
+        std::vector<const sealhip_rgsw *> raw_;
+        bool ternary_;
+    };
+
+    // The test vector of a lookup table for Evaluator::blind_rotate: the plaintext coefficients tv[j] = f(floor(j t / 2N)),
+    // j < N. Messages are restricted to [0, t/2); with b_offset = N / t in sealhip_lwe_mod_switch the windows are centred
+    // and the constant coefficient of the rotation's result is f(m).
+    inline std::vector<std::uint64_t> lut_test_vector(const std::function<std::uint64_t(std::uint64_t)> &f, std::uint64_t t,
+                                                      std::size_t n)
+    {
+        std::vector<std::uint64_t> tv(n);
+        for (std::size_t j = 0; j < n; j++)
+            tv[j] = f((j * t) / (2 * n));
+        return tv;
+    }
 
     // What HomomorphicDFT and Bootstrapper share: the tables' handle (destroyed with the object, not copyable), the plan and
     // its key steps. plan_entry(plan, key_steps, capacity) is the ABI's plan entry over the owner's arguments, called
@@ -2003,6 +2037,45 @@ namespace sealhip_host
             const C first = meta_of(encrypteds[0]); // (the destination may be one of the operands)
             take_meta(destination, first);
             commit(destination, o, 2, k);
+        }
+
+        // The monomial product (sealhip_evaluator_multiply_monomial): destination = X^exponent encrypted,
+        // or (X^exponent - 1) encrypted with minus_one; the exponent is taken modulo 2N with X^N = -1. The destination (which
+        // may be the operand) takes the operand's metadata. CKKS in NTT form; BFV in coefficient form on a STRICT context.
+        template <class C, IfCt<C> = 0>
+        void multiply_monomial(const C &encrypted, std::uint32_t exponent, C &destination, bool minus_one = false)
+        {
+            check_galois_operand(encrypted);
+            const std::size_t k = encrypted.coeff_modulus_size();
+            Staged e(ctx_, 1);
+            const std::uint64_t word = exponent;
+            e.up(&word, 1);
+            to_size2(encrypted, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_multiply_monomial(ctx_.get(), std::uint32_t(k), c, 1, 1,
+                                                           reinterpret_cast<const std::uint32_t *>(e.ptr()), 1, minus_one ? 1 : 0, o);
+            });
+        }
+        // Blind rotation (sealhip_evaluator_blind_rotate): destination = X^(exponents[0]) test_vector, then for every step t
+        // the accumulator plus ((X^(exponents[t]) - 1) accumulator) (x) keys[t - 1]. exponents holds 1 + keys.n_steps() words,
+        // one row of what sealhip_lwe_mod_switch writes (another count -> std::invalid_argument). The metadata is the test
+        // vector's.
+        template <class C, IfCt<C> = 0>
+        void blind_rotate(const C &test_vector, const std::vector<std::uint32_t> &exponents, const BlindRotationKeys &keys,
+                          C &destination)
+        {
+            if (exponents.size() != 1 + keys.n_steps())
+                throw std::invalid_argument("blind_rotate needs one exponent and one more per key");
+            check_galois_operand(test_vector);
+            const std::size_t k = test_vector.coeff_modulus_size();
+            std::vector<std::uint64_t> packed((exponents.size() + 1) / 2, 0);
+            std::memcpy(packed.data(), exponents.data(), exponents.size() * sizeof(std::uint32_t));
+            Staged e(ctx_, packed.size());
+            e.up(packed.data(), packed.size());
+            to_size2(test_vector, 2, k, destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_blind_rotate(ctx_.get(), std::uint32_t(k), c, 1, 1,
+                                                      reinterpret_cast<const std::uint32_t *>(e.ptr()),
+                                                      std::uint32_t(keys.n_steps()), keys.get(), o);
+            });
         }
 
         // Evaluator::multiply_many (evaluator.cpp:1180-1255): destination = product of all, relinearized after every step
@@ -3424,6 +3497,42 @@ namespace sealhip_host
             for (auto *h : raw)
                 out.push_back(std::make_unique<RgswCiphertext>(ctx_, h));
             return out;
+        }
+
+        // The keys of a blind rotation under this generator's secret key (sealhip_generate_blind_rotation_keys, DESIGN.md
+        // section 30) for an LWE secret with coefficients in {-1, 0, 1} (binary: {0, 1}): n_steps = lwe_secret.size(), or twice
+        // that with `ternary`. level as switching_keys. Samples are drawn as for rgsw: step by step, K_b's digits before
+        // K_a's. The staged secret is erased in stream order.
+        std::unique_ptr<BlindRotationKeys> blind_rotation_keys(const std::vector<std::int32_t> &lwe_secret, bool ternary,
+                                                               std::size_t level = 0)
+        {
+            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), n_lwe = lwe_secret.size(), count = n_lwe * (ternary ? 2 : 1);
+            if (!n_lwe)
+                throw std::invalid_argument("invalid count");
+            for (std::int32_t s : lwe_secret)
+                if (s > 1 || s < (ternary ? -1 : 0))
+                    throw std::invalid_argument("an LWE secret has coefficients in {-1, 0, 1} (binary: {0, 1})");
+            std::uint32_t k_first = 0, digits = 0;
+            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
+            if (level > k_first)
+                throw std::invalid_argument("level k out of range");
+            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
+            const std::size_t items = count * 2 * digits;
+            std::vector<std::uint64_t> seeds(items * 8);
+            Drawn drawn = draw(seeds.data(), items);
+            Staged sk(ctx_, nk * n);
+            ZeroedStaged e(ctx_, (items * n + 1) / 2), ss(ctx_, (n_lwe + 1) / 2);
+            sk.up(sk_.data(), nk * n);
+            to_device(drawn, items, e);
+            throw_on(sealhip_memcpy_h2d(ctx_.get(), ss.ptr(), lwe_secret.data(), n_lwe * sizeof(std::int32_t)));
+            std::vector<sealhip_rgsw *> raw(count, nullptr);
+            throw_on(sealhip_generate_blind_rotation_keys(ctx_.get(), sk.ptr(), reinterpret_cast<const std::int32_t *>(ss.ptr()),
+                                                          std::uint32_t(n_lwe), ternary ? 1 : 0, std::uint32_t(level ? level : k_first),
+                                                          seeds.data(), reinterpret_cast<const std::int32_t *>(e.ptr()), raw.data()));
+            std::vector<std::unique_ptr<RgswCiphertext>> made;
+            for (auto *h : raw)
+                made.push_back(std::make_unique<RgswCiphertext>(ctx_, h));
+            return std::make_unique<BlindRotationKeys>(std::move(made), ternary);
         }
 
     private:

@@ -288,6 +288,10 @@ SYMBOLS = {
     "sealhip_evaluator_cmux": [_vp, _u32, _vp, _vp, _sz, _vp, _vp],
     "sealhip_evaluator_select": [_vp, _u32, _vp, _sz, _u32, C.POINTER(_vp), _vp],
     "sealhip_debug_ext_mac_plan": [_vp, _u32, _sz, C.POINTER(_i32)],
+    "sealhip_evaluator_multiply_monomial": [_vp, _u32, _vp, _sz, _sz, _vp, _sz, _i32, _vp],
+    "sealhip_lwe_mod_switch": [_vp, _vp, _vp, _sz, _i32, _u32, _vp],
+    "sealhip_generate_blind_rotation_keys": [_vp, _vp, _vp, _u32, _i32, _u32, _vp, _vp, C.POINTER(_vp)],
+    "sealhip_evaluator_blind_rotate": [_vp, _u32, _vp, _sz, _sz, _vp, _u32, C.POINTER(_vp), _vp],
     "sealhip_evaluator_bootstrap_encapsulated": [_vp, _vp, _u32, _vp, _sz, C.POINTER(_u32), C.POINTER(_vp), _u32, C.POINTER(_vp), _u32, _vp, _vp, _vp],
     "sealhip_memset_zero": [_vp, _vp, _sz],
     "sealhip_ciphertext_load_many": [_vp, _vp, _vp, _sz, _vp, _vp, _sz],
@@ -498,6 +502,13 @@ class Rgsw:
                 self.handle = None
         except Exception:
             pass
+
+
+def lut_test_vector(f, t, n):
+    """The test vector of a lookup table for blind rotation: the plaintext coefficients
+    tv[j] = f(floor(j t / 2N)), j < N, as int64. Messages are restricted to [0, t/2); with b_offset = N / t in
+    Context.lwe_mod_switch the windows are centred, and the constant coefficient of X^(-phi~) tv is f(m)."""
+    return np.array([f((j * t) // (2 * n)) for j in range(n)], dtype=np.int64)
 
 
 def blake2xb(outlen, data, key=b""):
@@ -1017,6 +1028,31 @@ class Context:
         _check(lib().sealhip_debug_ext_mac_plan(self.handle, k, count, out))
         return dict(family={1: "loop", 2: "items"}.get(out[0], "refused"), nd2=out[1], split=bool(out[2]), group=out[3])
 
+    def upload_u32(self, host):
+        """uint32 words (exponents) -> device; an odd count is padded with one zero word"""
+        host = np.ascontiguousarray(host, dtype=np.uint32).reshape(-1)
+        if host.size % 2:
+            host = np.concatenate([host, np.zeros(1, dtype=np.uint32)])
+        return DeviceBuffer(self, host.size // 2).upload(host.view(np.uint64))
+
+    def lwe_mod_switch(self, lwe_a, lwe_b, n_samples, ternary, b_offset, exps_out):
+        """sealhip_lwe_mod_switch: level-1 samples lwe_a (n x 1 x N) and lwe_b (n x 1) to the exponent
+        rows of Evaluator.blind_rotate, n x (1 + N) uint32 for a binary secret and n x (1 + 2N) for a ternary one"""
+        _check(lib().sealhip_lwe_mod_switch(self.handle, _ptr(lwe_a), _ptr(lwe_b), n_samples, 1 if ternary else 0, b_offset,
+                                            _ptr(exps_out)))
+
+    def generate_blind_rotation_keys(self, sk_ntt, lwe_secret, n_lwe, ternary, level, seeds, noise):
+        """sealhip_generate_blind_rotation_keys: the n_steps = n_lwe (binary) or 2 n_lwe (ternary) Rgsw encryptions of the
+        indicators [s_j = 1] (and [s_j = -1]) of lwe_secret (n_lwe int32, device). seeds: n_steps x 2 x digits x 8 words (host),
+        noise: n_steps x 2 x digits x N int32 (device), as generate_rgsw takes them."""
+        n = n_lwe * (2 if ternary else 1)
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        out = (C.c_void_p * max(1, n))()
+        _check(lib().sealhip_generate_blind_rotation_keys(self.handle, _ptr(sk_ntt), _ptr(lwe_secret) if lwe_secret is not None else None,
+                                                          n_lwe, 1 if ternary else 0, level, seeds.ctypes.data if seeds.size else None,
+                                                          _ptr(noise) if noise is not None else None, out))
+        return [Rgsw._adopt(self, out[i]) for i in range(n)]
+
     def memset_zero(self, buf, nbytes):
         """stream-ordered zero fill of device memory (sealhip_memset_zero)"""
         _check(lib().sealhip_memset_zero(self.handle, _ptr(buf), nbytes))
@@ -1271,6 +1307,21 @@ class Evaluator:
         l = len(rgsw_bits)
         handles = (C.c_void_p * max(1, l))(*[g.handle for g in rgsw_bits])
         _check(lib().sealhip_evaluator_select(self.ctx.handle, k, _ptr(cts), count, l, handles if l else None, _ptr(out)))
+
+    def multiply_monomial(self, ct, k, count, exps, out, n_ct=None, exps_stride=1, minus_one=False):
+        """out[i] = X^(e_i) ct[i] - minus_one * ct[i] (sealhip_evaluator_multiply_monomial): e_i =
+        exps[i * exps_stride] (uint32, device, reduced mod 2N); ct holds n_ct = count ciphertexts (the default) or 1 shared"""
+        _check(lib().sealhip_evaluator_multiply_monomial(self.ctx.handle, k, _ptr(ct), count if n_ct is None else n_ct, count,
+                                                         _ptr(exps), exps_stride, 1 if minus_one else 0, _ptr(out)))
+
+    def blind_rotate(self, tv, k, count, exps, rgsw_list, out, n_tv=1):
+        """out[i] = X^(exps[i][0]) tv prod_t (1 + (X^(exps[i][t]) - 1) beta_t) in the phase (sealhip_evaluator_blind_rotate):
+        tv: n_tv = 1 (shared) or count size-2 ciphertexts; exps: count x (1 + len(rgsw_list)) uint32 (device); rgsw_list[t - 1]
+        encrypts the bit beta_t. One streaming launch and one external product per step, the accumulator in out."""
+        n = len(rgsw_list)
+        handles = (C.c_void_p * max(1, n))(*[g.handle for g in rgsw_list])
+        _check(lib().sealhip_evaluator_blind_rotate(self.ctx.handle, k, _ptr(tv), n_tv, count, _ptr(exps), n,
+                                                    handles if n else None, _ptr(out)))
 
     def dot_plain(self, cts, plain, k, count, n_terms, n_sums, out, size=2):
         """Sums against plaintext rows (sealhip_evaluator_dot_plain): out[s] = sum_i ct_i (.) P[s][i],

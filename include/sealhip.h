@@ -1591,6 +1591,69 @@ long sealhip_evaluator_cmux(sealhip_context *ctx, uint32_t k, const uint64_t *ct
 long sealhip_evaluator_select(sealhip_context *ctx, uint32_t k, const uint64_t *cts, size_t count, uint32_t l,
                               const sealhip_rgsw *const *rgsw_bits, uint64_t *out);
 long sealhip_debug_ext_mac_plan(sealhip_context *ctx, uint32_t k, size_t count, int32_t out[4]);
+/* Blind rotation: the accumulator loop of programmable bootstrapping (Chillotti, Gama, Georgieva,
+   Izabachene, "TFHE", J. Cryptology 2020, Alg. 3) over the external product above, with the two pieces a caller cannot
+   compose without leaving the device per sample: a monomial product whose exponent differs per batch item, and the LWE
+   modulus switch from q to 2N that makes those exponents. The fork has no such method; tests/blind_rotate_ref.py restates
+   every entry over the oracle on top of tests/rgsw_ref.py.
+
+   The ring is Z_q[X]/(X^N + 1); an exponent e is an integer in [0, 2N) with X^N = -1; e' = e mod N, sgn = -1 for e >= N.
+   Coefficient form (BFV, STRICT): (X^e c)[x] = sgn c[x - e'] for x >= e' and -sgn c[N + x - e'] for x < e'. NTT form (CKKS,
+   both modes): position c of row r holds the value at psi_r^(2 brev(c) + 1), so NTT(X^e)[c] = psi_r^(e (2 brev(c) + 1) mod 2N)
+   with psi^(N + j) = -psi^j: the words of the forward transform of the one-hot row followed by the dyadic product. The
+   powers come from a resident table of psi_r^j, j < N, per ciphertext prime (16 N bytes per prime, 512 KiB at N = 2^15),
+   built on first use. An exponent >= 2N is reduced mod 2N by the kernel; the array is not scanned on the host.
+
+   sealhip_evaluator_multiply_monomial: out[i] = X^(e_i) ct[i] - minus_one * ct[i] on both components, count size-2
+     ciphertexts at level k in the scheme's form, e_i = exps_dev[i * exps_stride] (uint32, DEVICE). ct holds n_ct = 1
+     ciphertext (shared by the batch) or n_ct = count. minus_one != 0 gives (X^e - 1) ct, the target of a blind-rotation step.
+   sealhip_evaluator_blind_rotate: tv: n_tv size-2 ciphertexts, n_tv = 1 (shared) or count; exps_dev: count x (1 + n_steps)
+     uint32 (DEVICE); rgsw_list[0 .. n_steps).
+         acc_0[i] = X^(exps[i][0]) tv[i]
+         acc_t[i] = acc_(t-1)[i] + ((X^(exps[i][t]) - 1) acc_(t-1)[i]) (x) rgsw_list[t-1],   t = 1 .. n_steps
+         out[i]   = acc_(n_steps)[i]
+     Where rgsw_list[t-1] encrypts a bit beta_t the phase of out[i] is X^(exps[i][0] + sum_t beta_t exps[i][t]) phase(tv) plus
+     n_steps key-switch errors; nothing multiplies. The words are those of the step-by-step composition
+     multiply_monomial(minus_one = 1) then sealhip_evaluator_external_product(target, base = acc). The accumulator lives in
+     out from step 0 on; a step is one streaming launch (reads acc, writes the target into the arena) and one external
+     product whose mod-down adds into acc in place. A batch that does not fit the arena is walked in chunks of items with
+     the whole step loop inside a chunk; sealhip_debug_chunk_log ends with (count, items per chunk). No host read or
+     synchronisation between steps; capturable after one call of the same shape. With a transparency sink: one flag per
+     output, from the last step's mod-down, or from a read pass when n_steps == 0 (and for multiply_monomial).
+   Checks of these two, in this order: NULL ctx, ct / tv, exps_dev, out, (n_steps > 0) the list and every entry -> E_POINTER;
+   then, also on host-only contexts: k outside the ciphertext levels, n_ct / n_tv neither 1 nor count, BFV in PARITY mode, ct / tv
+   or out not 16-byte aligned, exps_dev not 4-byte aligned, out overlapping ct / tv or exps -> E_INVALIDARG; then a host-only
+   context -> COR_E_INVALIDOPERATION; then an rgsw that does not serve level k ("rgsw is not valid for encryption
+   parameters") -> E_INVALIDARG; then count == 0 -> S_OK, nothing launched.
+
+   sealhip_lwe_mod_switch: lwe_a[n_samples][1][N], lwe_b[n_samples][1] (DEVICE) are samples at level 1 (one prime q = q_0) as
+     sealhip_evaluator_extract_lwe writes them at k = 1. With ms(x) = floor((2N x + floor(q / 2)) / q) mod 2N, exact in integers
+     (a value that rounds to 2N wraps to 0), exps_out (DEVICE) receives blind_rotate's layout, n_samples x (1 + n_steps):
+         exps[i][0] = -(ms(b_i) + b_offset) mod 2N
+         binary secret  (ternary == 0): n_steps = N,  exps[i][1 + j] = -ms(a_ij) mod 2N
+         ternary secret (ternary != 0): n_steps = 2N, exps[i][1 + 2j] = -ms(a_ij) mod 2N against RGSW([s_j = 1]) and
+                                                      exps[i][2 + 2j] = +ms(a_ij)        against RGSW([s_j = -1])
+     so that blind_rotate's out = X^(-phi~) tv with phi~ = ms(b) + b_offset + sum_j ms(a_j) s_j, and
+     |phi~ - b_offset - 2N phi / q| <= (1 + ||s||_1) / 2. The constant coefficient of X^(-phi~) tv is tv[phi~] for phi~ < N and
+     -tv[phi~ - N] above. Checks: NULL ctx, lwe_a, lwe_b, exps_out -> E_POINTER; then, also on host-only contexts: a context
+     whose level 1 is not a ciphertext level, lwe_a not 16-byte, lwe_b not 8-byte or exps_out not 4-byte aligned, exps_out
+     overlapping an input -> E_INVALIDARG; then a host-only context -> COR_E_INVALIDOPERATION; n_samples == 0 -> S_OK.
+   sealhip_generate_blind_rotation_keys: out receives n_steps = n_lwe (binary) or 2 n_lwe (ternary) owned sealhip_rgsw, the
+     encryptions of the constant polynomials [s_j = 1] (at 2j for ternary, with [s_j = -1] at 2j + 1) of lwe_secret_dev
+     (n_lwe int32, DEVICE, values in {-1, 0, 1}). A kernel writes the indicators as m_coeff and the code behind
+     sealhip_generate_rgsw does the rest: every word is that entry's for the indicator messages with the same samples
+     (seeds_host: n_steps x 2 x digits x 8 words, HOST; noise: n_steps x 2 x digits x N int32, DEVICE). The indicators are
+     erased in stream order. Checks and behaviour as sealhip_generate_rgsw with n = n_steps. */
+long sealhip_evaluator_multiply_monomial(sealhip_context *ctx, uint32_t k, const uint64_t *ct, size_t n_ct, size_t count,
+                                         const uint32_t *exps_dev, size_t exps_stride, int32_t minus_one, uint64_t *out);
+long sealhip_lwe_mod_switch(sealhip_context *ctx, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t n_samples,
+                            int32_t ternary, uint32_t b_offset, uint32_t *exps_out);
+long sealhip_generate_blind_rotation_keys(sealhip_context *ctx, const uint64_t *sk_ntt, const int32_t *lwe_secret_dev,
+                                          uint32_t n_lwe, int32_t ternary, uint32_t level, const uint64_t *seeds_host,
+                                          const int32_t *noise, sealhip_rgsw **out);
+long sealhip_evaluator_blind_rotate(sealhip_context *ctx, uint32_t k, const uint64_t *tv, size_t n_tv, size_t count,
+                                    const uint32_t *exps_dev, uint32_t n_steps, const sealhip_rgsw *const *rgsw_list,
+                                    uint64_t *out);
 /* stream-ordered hipMemsetAsync(dptr, 0, bytes) on the calling thread's lane: erases scratch that held secret samples
    before it goes back to a pool (the reference's clear_on_destruction pool, util/rlwe.cpp:141). Does not synchronise. */
 long sealhip_memset_zero(sealhip_context *ctx, void *dptr, size_t bytes);
