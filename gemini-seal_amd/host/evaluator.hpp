@@ -8,867 +8,23 @@
 // and :430-548 mod_switch_to(_next) of plaintexts, and every destination-taking variant), doing
 // the same metadata checks on the host and forwarding raw pointers to the ABI. It is a template over the
 // ciphertext type so that it compiles both against seal::Ciphertext (where the reference headers exist) and
-// against the plain sealhip::HostCiphertext below (everywhere else, e.g. the GPU box).
+// against the plain sealhip::HostCiphertext of adapter_core.hpp (everywhere else, e.g. the GPU box).
 //
 // Required of CT: data() -> uint64_t*, size(), coeff_modulus_size(), poly_modulus_degree(), is_ntt_form()
 // (assignable), resize_raw(size, coeff_modulus_size). For seal::Ciphertext the last one is
 //   ct.resize(context, parms_id_of_level, size)  -- see INTEGRATION.md.
 //
 // Exceptions mirror the reference: std::invalid_argument / std::logic_error (evaluator.cpp:238-271).
+//
+// This is the one header to include. The Evaluator is here; what it stands on (Context, the resident types, the key and
+// table handles) is in adapter_core.hpp, and Decryptor, Encryptor and KeyGenerator are in crypto.hpp.
 #pragma once
 
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <complex>
-#include <cstdint>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <type_traits>
-#include <utility>
-#include <vector>
-
-#include "../../include/sealhip.h"
+#include "adapter_core.hpp"
+#include "crypto.hpp"
 
 namespace sealhip_host
 {
-    inline void throw_on(long hr)
-    {
-        if (hr == SEALHIP_S_OK)
-            return;
-        const std::string msg = sealhip_last_error_string();
-        if (hr == SEALHIP_E_INVALIDARG || hr == SEALHIP_E_POINTER)
-            throw std::invalid_argument(msg);
-        if (hr == SEALHIP_COR_E_INVALIDOPERATION)
-            throw std::logic_error(msg);
-        if (hr == SEALHIP_E_OUTOFMEMORY)
-            throw std::bad_alloc();
-        throw std::runtime_error(msg);
-    }
-
-    // Plain stand-in with the reference's layout (ciphertext.h:359-368): size x k x N uint64, row-major.
-    struct HostCiphertext
-    {
-        std::vector<std::uint64_t> words;
-        std::size_t size_ = 0, k_ = 0, n_ = 0;
-        bool ntt_form_ = false;
-        double scale_ = 1.0;
-        std::uint64_t *data() { return words.data(); }
-        const std::uint64_t *data() const { return words.data(); }
-        std::size_t size() const { return size_; }
-        std::size_t coeff_modulus_size() const { return k_; }
-        std::size_t poly_modulus_degree() const { return n_; }
-        bool &is_ntt_form() { return ntt_form_; }
-        bool is_ntt_form() const { return ntt_form_; }
-        double &scale() { return scale_; }
-        double scale() const { return scale_; }
-        void resize_raw(std::size_t size, std::size_t k)
-        {
-            // like IntArray::resize: keeps the leading words, zero-fills the rest (ciphertext.cpp:84-133)
-            std::vector<std::uint64_t> next(size * k * n_, 0);
-            const std::size_t polys = size < size_ ? size : size_;
-            const std::size_t rows = k < k_ ? k : k_;
-            for (std::size_t s = 0; s < polys; s++)
-                for (std::size_t r = 0; r < rows; r++)
-                    for (std::size_t c = 0; c < n_; c++)
-                        next[(s * k + r) * n_ + c] = words[(s * k_ + r) * n_ + c];
-            words.swap(next);
-            size_ = size;
-            k_ = k;
-        }
-    };
-
-    class Context
-    {
-    public:
-        explicit Context(const sealhip_params &p)
-            : scheme_(p.scheme), n_(std::size_t(1) << p.log_n), t_(p.plain_modulus), n_key_(p.n_key_moduli),
-              key_moduli_(p.key_moduli ? p.key_moduli : nullptr, p.key_moduli ? p.key_moduli + p.n_key_moduli : nullptr)
-        {
-            throw_on(sealhip_context_create(&p, &ctx_));
-        }
-        ~Context()
-        {
-            if (ctx_)
-                sealhip_context_destroy(ctx_); // (frees every pool block, the transparency rings' included)
-        }
-        Context(const Context &) = delete;
-        Context &operator=(const Context &) = delete;
-        sealhip_context *get() const { return ctx_; }
-        std::uint32_t scheme() const { return scheme_; }
-        std::size_t n() const { return n_; }
-        std::uint64_t plain_modulus() const { return t_; }
-        std::size_t n_key() const { return n_key_; } // the highest level the ABI names (key level)
-        std::uint64_t key_modulus(std::size_t i) const { return key_moduli_.at(i); } // q_i; the special primes come last
-
-        // SEALContext's parms_id of level k (sealhip_context_set_parms_id), kept for DeviceCiphertext::save
-        void set_parms_id(std::size_t k, const std::uint64_t parms_id[4])
-        {
-            throw_on(sealhip_context_set_parms_id(ctx_, std::uint32_t(k), parms_id));
-            std::lock_guard<std::mutex> lock(mu_);
-            std::copy(parms_id, parms_id + 4, parms_ids_[k].begin());
-        }
-        bool parms_id(std::size_t k, std::uint64_t out[4]) const
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            auto it = parms_ids_.find(k);
-            if (it == parms_ids_.end())
-                return false;
-            std::copy(it->second.begin(), it->second.end(), out);
-            return true;
-        }
-
-        // The deferred transparency check of the resident Evaluator overloads (SEAL_THROW_ON_TRANSPARENT_CIPHERTEXT,
-        // evaluator.cpp:265-271 and the other #ifdef blocks): a ring of flag words in a pool block per (Evaluator, calling
-        // thread). Each checked operation gets its own slot as the lane's transparency sink; the sink writes a non-zero word
-        // for a result that is NOT transparent. The slots are read at the thread's next host-visible point.
-        static constexpr std::size_t kRingSlots = 256;
-        // (count consecutive slots for an operation with that many results: the hoisted rotations)
-        std::uint32_t *transparency_slot(const void *evaluator, std::size_t count = 1) const
-        {
-            if (count > kRingSlots)
-                throw std::invalid_argument("too many results for one checked operation");
-            Ring &r = ring(evaluator);
-            if (r.used + count > kRingSlots)
-                check_transparency(); // a full ring is a host-visible point
-            std::uint32_t *slot = r.flags + r.used;
-            r.used += count;
-            return slot;
-        }
-        void transparency_unslot(const void *evaluator, std::size_t count = 1) const // the operation failed before its result existed
-        {
-            Ring &r = ring(evaluator);
-            r.used -= count < r.used ? count : r.used;
-        }
-        // reads the calling thread's rings (one synchronisation each); throws the reference's std::logic_error when a
-        // checked result was transparent
-        void check_transparency() const
-        {
-            std::vector<std::pair<std::uint32_t *, std::size_t>> todo;
-            {
-                std::lock_guard<std::mutex> lock(mu_);
-                for (auto &kv : rings_)
-                    if (kv.first.second == std::this_thread::get_id() && kv.second.used)
-                    {
-                        todo.emplace_back(kv.second.flags, kv.second.used);
-                        kv.second.used = 0;
-                    }
-            }
-            bool transparent = false;
-            for (auto &t : todo)
-            {
-                std::vector<std::uint32_t> host(t.second);
-                throw_on(sealhip_memcpy_d2h(ctx_, host.data(), t.first, host.size() * sizeof(std::uint32_t)));
-                transparent = transparent || std::find(host.begin(), host.end(), 0u) != host.end();
-            }
-            if (transparent)
-                throw std::logic_error("result ciphertext is transparent");
-        }
-        // The Evaluator goes away: its rings go back to the pool. Every lane is waited for first (no stream still writes a
-        // flag into them); flags not yet read are dropped unread -- a destructor does not throw, so call
-        // Evaluator::synchronize() before destroying an Evaluator whose resident results must be checked.
-        void drop_transparency(const void *evaluator) const
-        {
-            bool any = false;
-            {
-                std::lock_guard<std::mutex> lock(mu_);
-                for (auto &kv : rings_)
-                    any = any || kv.first.first == evaluator;
-            }
-            if (any)
-                (void)sealhip_synchronize(ctx_);
-            std::lock_guard<std::mutex> lock(mu_);
-            for (auto it = rings_.begin(); it != rings_.end();)
-                if (it->first.first == evaluator)
-                {
-                    sealhip_pool_release(ctx_, it->second.flags);
-                    it = rings_.erase(it);
-                }
-                else
-                    ++it;
-        }
-
-    private:
-        struct Ring
-        {
-            std::uint32_t *flags = nullptr;
-            std::size_t used = 0;
-        };
-        Ring &ring(const void *evaluator) const
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            Ring &r = rings_[{ evaluator, std::this_thread::get_id() }];
-            if (!r.flags)
-            {
-                void *p = nullptr;
-                throw_on(sealhip_pool_alloc(ctx_, kRingSlots * sizeof(std::uint32_t), &p));
-                r.flags = static_cast<std::uint32_t *>(p);
-            }
-            return r;
-        }
-
-        sealhip_context *ctx_ = nullptr;
-        std::uint32_t scheme_;
-        std::size_t n_;
-        std::uint64_t t_;
-        std::size_t n_key_;
-        std::vector<std::uint64_t> key_moduli_;
-        mutable std::mutex mu_;
-        std::map<std::size_t, std::array<std::uint64_t, 4>> parms_ids_;
-        mutable std::map<std::pair<const void *, std::thread::id>, Ring> rings_;
-    };
-
-    // device staging of one host object, in a block of the context's pool (sealhip_pool_alloc): released stream-ordered,
-    // so the host path makes no allocator call once the pool is warm
-    class Staged
-    {
-    public:
-        Staged(const Context &c, std::size_t words) : c_(c), words_(words)
-        {
-            throw_on(sealhip_pool_alloc(c.get(), (words ? words : 1) * 8, &d_));
-        }
-        ~Staged()
-        {
-            if (d_)
-                sealhip_pool_release(c_.get(), d_);
-        }
-        Staged(const Staged &) = delete;
-        Staged &operator=(const Staged &) = delete;
-        void up(const std::uint64_t *h, std::size_t words) { throw_on(sealhip_memcpy_h2d(c_.get(), d_, h, words * 8)); }
-        void down(std::uint64_t *h, std::size_t words) { throw_on(sealhip_memcpy_d2h(c_.get(), h, d_, words * 8)); }
-        std::uint64_t *ptr() { return static_cast<std::uint64_t *>(d_); }
-        std::size_t words() const { return words_; }
-        void *release() // the block changes owner (a DeviceCiphertext adopts it)
-        {
-            void *p = d_;
-            d_ = nullptr;
-            return p;
-        }
-
-    private:
-        const Context &c_;
-        void *d_ = nullptr;
-        std::size_t words_;
-    };
-
-    // Staging that held secret samples (u, the noise, a secret key in coefficient form): erased in stream order before the
-    // block goes back to the pool, as the reference's clear_on_destruction pool does (util/rlwe.cpp:141)
-    class ZeroedStaged : public Staged
-    {
-    public:
-        ZeroedStaged(const Context &c, std::size_t words) : Staged(c, words), ctx_(c) {}
-        ~ZeroedStaged() { sealhip_memset_zero(ctx_.get(), ptr(), (words() ? words() : 1) * 8); }
-
-    private:
-        const Context &ctx_;
-    };
-
-    // Where the random samples come from when they are drawn on the device (sealhip_sample_polys): the
-    // source is asked for one 64-byte seed at a time (a CSPRNG's output; never reuse one). Only seeds cross from the host.
-    using SeedSource = std::function<void(std::uint64_t *seed8)>;
-
-    namespace detail
-    {
-        // two seeds from the source, in order; the second (a noise seed, secret) must not be the first (c_1's, public)
-        inline void draw_seed_pair(const SeedSource &source, std::uint64_t *public_seed, std::uint64_t *noise_seed)
-        {
-            source(public_seed);
-            source(noise_seed);
-            if (std::equal(public_seed, public_seed + 8, noise_seed))
-                throw std::logic_error("the seed source returned the same seed twice");
-        }
-
-        // HostCiphertext needs its N before resize_raw; seal::Ciphertext gets it from its parms_id
-        template <class C>
-        auto prepare_host(C &c, std::size_t n) -> decltype(c.n_ = n, void())
-        {
-            c.n_ = n;
-        }
-        inline void prepare_host(...) {}
-    } // namespace detail
-
-    // A ciphertext resident on the device: size x k x N words in a block of the context's pool, with the
-    // metadata of seal::Ciphertext the adapter uses (size, level k, N, NTT form, scale). Copies take a pool block and a
-    // stream-ordered device copy; moves swap. Only download / save / load synchronise (the host-visible points).
-    class DeviceCiphertext
-    {
-    public:
-        explicit DeviceCiphertext(const Context &context) : ctx_(&context), n_(context.n()) {}
-        DeviceCiphertext(const DeviceCiphertext &o) : ctx_(o.ctx_), n_(o.n_) { *this = o; }
-        DeviceCiphertext(DeviceCiphertext &&o) noexcept { swap(o); }
-        ~DeviceCiphertext() { release(); }
-        DeviceCiphertext &operator=(const DeviceCiphertext &o)
-        {
-            if (this == &o)
-                return *this;
-            if (ctx_ != o.ctx_)
-            {
-                release(); // (to the pool it came from)
-                ctx_ = o.ctx_;
-            }
-            n_ = o.n_;
-            reserve(o.words());
-            if (o.words())
-                throw_on(sealhip_memcpy_d2d(ctx_->get(), ptr_, o.ptr_, o.words() * 8));
-            size_ = o.size_;
-            k_ = o.k_;
-            ntt_ = o.ntt_;
-            scale_ = o.scale_;
-            return *this;
-        }
-        DeviceCiphertext &operator=(DeviceCiphertext &&o) noexcept
-        {
-            swap(o); // o releases what this held
-            return *this;
-        }
-        void swap(DeviceCiphertext &o) noexcept
-        {
-            std::swap(ctx_, o.ctx_);
-            std::swap(ptr_, o.ptr_);
-            std::swap(cap_, o.cap_);
-            std::swap(size_, o.size_);
-            std::swap(k_, o.k_);
-            std::swap(n_, o.n_);
-            std::swap(ntt_, o.ntt_);
-            std::swap(scale_, o.scale_);
-        }
-
-        std::uint64_t *data() { return ptr_; } // a DEVICE pointer
-        const std::uint64_t *data() const { return ptr_; }
-        std::size_t size() const { return size_; }
-        std::size_t coeff_modulus_size() const { return k_; }
-        std::size_t poly_modulus_degree() const { return n_; }
-        bool &is_ntt_form() { return ntt_; }
-        bool is_ntt_form() const { return ntt_; }
-        double &scale() { return scale_; }
-        double scale() const { return scale_; }
-        const Context &context() const { return *ctx_; }
-
-        // host ciphertext -> device (one synchronous copy)
-        template <class H>
-        void upload(const H &h)
-        {
-            if (h.poly_modulus_degree() != n_)
-                throw std::invalid_argument("encrypted is not valid for encryption parameters");
-            const std::size_t words = h.size() * h.coeff_modulus_size() * n_;
-            reserve(words);
-            if (words)
-                throw_on(sealhip_memcpy_h2d(ctx_->get(), ptr_, h.data(), words * 8));
-            size_ = h.size();
-            k_ = h.coeff_modulus_size();
-            ntt_ = h.is_ntt_form();
-            scale_ = h.scale();
-        }
-        // device -> host ciphertext; a host-visible point of the calling thread's deferred transparency checks
-        template <class H>
-        void download(H &h) const
-        {
-            ctx_->check_transparency();
-            detail::prepare_host(h, n_);
-            h.resize_raw(size_, k_);
-            if (words())
-                throw_on(sealhip_memcpy_d2h(ctx_->get(), h.data(), ptr_, words() * 8));
-            h.is_ntt_form() = ntt_;
-            h.scale() = scale_;
-        }
-        // Ciphertext::load (ciphertext.cpp:228-330) straight into the block (sealhip_ciphertext_load)
-        void load(const void *bytes, std::size_t len)
-        {
-            sealhip_ciphertext_info info{};
-            throw_on(sealhip_ciphertext_peek(bytes, len, &info));
-            if (info.poly_modulus_degree != n_)
-                throw std::logic_error("ciphertext data is invalid");
-            reserve(std::size_t(info.size) * info.coeff_modulus_size * n_);
-            throw_on(sealhip_ciphertext_load(ctx_->get(), bytes, len, &info, ptr_, cap_));
-            size_ = info.size;
-            k_ = info.coeff_modulus_size;
-            ntt_ = info.is_ntt_form != 0;
-            scale_ = info.scale;
-        }
-        // Ciphertext::save (compr_mode_type::none) straight from the block (sealhip_ciphertext_save); the level's parms_id
-        // comes from Context::set_parms_id. A host-visible point.
-        void save(std::vector<std::uint8_t> &out) const
-        {
-            ctx_->check_transparency();
-            sealhip_ciphertext_info info{};
-            if (!ctx_->parms_id(k_, info.parms_id))
-                throw std::logic_error("the level's parms_id is not registered (Context::set_parms_id)");
-            info.is_ntt_form = ntt_ ? 1 : 0;
-            info.size = std::uint32_t(size_);
-            info.coeff_modulus_size = std::uint32_t(k_);
-            info.poly_modulus_degree = n_;
-            info.scale = scale_;
-            std::size_t need = 0, written = 0;
-            throw_on(sealhip_ciphertext_save_size(ctx_->get(), std::uint32_t(size_), std::uint32_t(k_), &need));
-            out.resize(need);
-            throw_on(sealhip_ciphertext_save(ctx_->get(), &info, ptr_, out.data(), need, &written));
-            out.resize(written);
-        }
-        // Ciphertext::resize (ciphertext.cpp:84-133): polynomials it adds are zero (sealhip_ciphertext_resize)
-        void resize(std::size_t size)
-        {
-            if (size == size_)
-                return;
-            if ((size < 2 && size != 0) || size > 16)
-                throw std::invalid_argument("invalid size");
-            Staged next(*ctx_, size * k_ * n_);
-            throw_on(sealhip_ciphertext_resize(ctx_->get(), std::uint32_t(k_), ptr_ ? ptr_ : next.ptr(), std::uint32_t(size_),
-                                               next.ptr(), std::uint32_t(size), 1));
-            adopt(next.release(), next.words(), size, k_);
-        }
-
-        // (Evaluator) the result in `block` (a pool block of cap_words words) replaces the words; the old block is
-        // released stream-ordered
-        void adopt(void *block, std::size_t cap_words, std::size_t size, std::size_t k)
-        {
-            release();
-            ptr_ = static_cast<std::uint64_t *>(block);
-            cap_ = cap_words;
-            size_ = size;
-            k_ = k;
-        }
-        void set_size(std::size_t size) { size_ = size; } // (Evaluator) fewer polynomials, the leading words kept
-        void copy_meta(const DeviceCiphertext &o) // (Evaluator) NTT form and scale, not the words
-        {
-            ntt_ = o.ntt_;
-            scale_ = o.scale_;
-        }
-
-    private:
-        std::size_t words() const { return size_ * k_ * n_; }
-        void reserve(std::size_t words)
-        {
-            if (words <= cap_ && ptr_)
-                return;
-            void *p = nullptr;
-            throw_on(sealhip_pool_alloc(ctx_->get(), (words ? words : 1) * 8, &p));
-            release();
-            ptr_ = static_cast<std::uint64_t *>(p);
-            cap_ = words;
-        }
-        void release()
-        {
-            if (ptr_ && ctx_)
-                sealhip_pool_release(ctx_->get(), ptr_);
-            ptr_ = nullptr;
-            cap_ = 0;
-        }
-
-        const Context *ctx_ = nullptr;
-        std::uint64_t *ptr_ = nullptr;
-        std::size_t cap_ = 0, size_ = 0, k_ = 0, n_ = 0;
-        bool ntt_ = false;
-        double scale_ = 1.0;
-    };
-
-    // A plaintext resident on the device, in a pool block: coefficient form (N words, each below t; a shorter plaintext is
-    // zero-padded) or NTT form at level k (k x N words). It serves the plain operations of the resident Evaluator overloads,
-    // transform_to_ntt and mod_switch_to(_next) of plaintexts. upload checks the words like is_valid_for (coefficient form:
-    // every word below t) and is the only call that synchronises.
-    class DevicePlaintext
-    {
-    public:
-        explicit DevicePlaintext(const Context &context) : ctx_(&context) {}
-        DevicePlaintext(const DevicePlaintext &o) : ctx_(o.ctx_) { *this = o; }
-        DevicePlaintext(DevicePlaintext &&o) noexcept { swap(o); }
-        ~DevicePlaintext() { release(); }
-        DevicePlaintext &operator=(const DevicePlaintext &o)
-        {
-            if (this == &o)
-                return *this;
-            if (ctx_ != o.ctx_)
-            {
-                release();
-                ctx_ = o.ctx_;
-            }
-            reserve(o.words_);
-            if (o.words_)
-                throw_on(sealhip_memcpy_d2d(ctx_->get(), ptr_, o.ptr_, o.words_ * 8));
-            words_ = o.words_;
-            k_ = o.k_;
-            ntt_ = o.ntt_;
-            scale_ = o.scale_;
-            return *this;
-        }
-        DevicePlaintext &operator=(DevicePlaintext &&o) noexcept
-        {
-            swap(o);
-            return *this;
-        }
-        void swap(DevicePlaintext &o) noexcept
-        {
-            std::swap(ctx_, o.ctx_);
-            std::swap(ptr_, o.ptr_);
-            std::swap(cap_, o.cap_);
-            std::swap(words_, o.words_);
-            std::swap(k_, o.k_);
-            std::swap(ntt_, o.ntt_);
-            std::swap(scale_, o.scale_);
-        }
-        // coefficient form: up to N coefficients below t; NTT form: k x N words (k = words.size() / N)
-        void upload(const std::vector<std::uint64_t> &words, bool ntt_form)
-        {
-            const std::size_t n = ctx_->n();
-            std::vector<std::uint64_t> padded;
-            const std::uint64_t *src = words.data();
-            std::size_t count = words.size(), k = 0;
-            if (ntt_form)
-            {
-                k = count / n;
-                if (count % n != 0 || k < 1 || k > ctx_->n_key())
-                    throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
-            else
-            {
-                if (count > n || std::any_of(words.begin(), words.end(),
-                                             [&](std::uint64_t v) { return v >= ctx_->plain_modulus(); }))
-                    throw std::invalid_argument("plain is not valid for encryption parameters"); // valcheck.cpp:236-281
-                padded.assign(n, 0);
-                std::copy(words.begin(), words.end(), padded.begin());
-                src = padded.data();
-                count = n;
-            }
-            reserve(count);
-            throw_on(sealhip_memcpy_h2d(ctx_->get(), ptr_, src, count * 8));
-            words_ = count;
-            k_ = k;
-            ntt_ = ntt_form;
-        }
-        void download(std::vector<std::uint64_t> &out) const
-        {
-            out.resize(words_);
-            if (words_)
-                throw_on(sealhip_memcpy_d2h(ctx_->get(), out.data(), ptr_, words_ * 8));
-        }
-        const std::uint64_t *data() const { return ptr_; } // a DEVICE pointer
-        std::size_t words() const { return words_; }
-        std::size_t coeff_modulus_size() const { return k_; } // NTT form: its level; coefficient form: 0
-        bool is_ntt_form() const { return ntt_; }
-        // Plaintext::scale() of a CKKS plaintext (the caller sets it next to upload; 1.0 otherwise): read by
-        // Evaluator::apply_galois_dot_plain, kept by copies
-        double &scale() { return scale_; }
-        double scale() const { return scale_; }
-        // (Evaluator) the words in `block` replace these
-        void adopt(void *block, std::size_t cap_words, std::size_t words, std::size_t k, bool ntt_form)
-        {
-            release();
-            ptr_ = static_cast<std::uint64_t *>(block);
-            cap_ = cap_words;
-            words_ = words;
-            k_ = k;
-            ntt_ = ntt_form;
-        }
-
-    private:
-        void reserve(std::size_t words)
-        {
-            if (words <= cap_ && ptr_)
-                return;
-            void *p = nullptr;
-            throw_on(sealhip_pool_alloc(ctx_->get(), (words ? words : 1) * 8, &p));
-            release();
-            ptr_ = static_cast<std::uint64_t *>(p);
-            cap_ = words;
-        }
-        void release()
-        {
-            if (ptr_ && ctx_)
-                sealhip_pool_release(ctx_->get(), ptr_);
-            ptr_ = nullptr;
-            cap_ = 0;
-        }
-
-        const Context *ctx_ = nullptr;
-        std::uint64_t *ptr_ = nullptr;
-        std::size_t cap_ = 0, words_ = 0, k_ = 0;
-        bool ntt_ = false;
-        double scale_ = 1.0;
-    };
-
-    class KSwitchKeys // one key of RelinKeys / GaloisKeys (kswitchkeys.h:92-130), resident on the device
-    {
-    public:
-        KSwitchKeys(const Context &c, const std::uint64_t *host_key, std::uint32_t n_digits) : c_(c)
-        {
-            throw_on(sealhip_kswitch_key_load(c.get(), host_key, n_digits, 1, &key_));
-        }
-        ~KSwitchKeys()
-        {
-            if (key_)
-                sealhip_kswitch_key_destroy(c_.get(), key_);
-        }
-        KSwitchKeys(const Context &c, sealhip_kswitch_key *adopt) : c_(c), key_(adopt) {} // a handle the ABI made
-        KSwitchKeys(const KSwitchKeys &) = delete;
-        const sealhip_kswitch_key *get() const { return key_; }
-
-    private:
-        const Context &c_;
-        sealhip_kswitch_key *key_ = nullptr;
-    };
-
-    // One RGSW ciphertext, resident on the device: the key-switch keys K_b (new key m) and K_a (new
-    // key m s) of a small polynomial m in one block. Made by KeyGenerator::rgsw, or from two key-switch keys (for example
-    // loaded from a stream; a device copy -- digit counts or levels that differ -> std::invalid_argument).
-    // Evaluator::external_product / cmux / select take it.
-    class RgswCiphertext
-    {
-    public:
-        RgswCiphertext(const Context &c, const KSwitchKeys &key_b, const KSwitchKeys &key_a) : c_(c)
-        {
-            throw_on(sealhip_rgsw_create(c.get(), key_b.get(), key_a.get(), &g_));
-        }
-        RgswCiphertext(const Context &c, sealhip_rgsw *adopt) : c_(c), g_(adopt) {} // a handle the ABI made
-        ~RgswCiphertext()
-        {
-            if (g_)
-                sealhip_rgsw_destroy(c_.get(), g_);
-        }
-        RgswCiphertext(const RgswCiphertext &) = delete;
-        RgswCiphertext &operator=(const RgswCiphertext &) = delete;
-        const sealhip_rgsw *get() const { return g_; }
-        // (K_b, K_a) as two owned key-switch keys holding copies of the halves (sealhip_rgsw_export)
-        std::pair<std::unique_ptr<KSwitchKeys>, std::unique_ptr<KSwitchKeys>> export_keys() const
-        {
-            sealhip_kswitch_key *raw[2] = { nullptr, nullptr };
-            throw_on(sealhip_rgsw_export(c_.get(), g_, raw));
-            return { std::make_unique<KSwitchKeys>(c_, raw[0]), std::make_unique<KSwitchKeys>(c_, raw[1]) };
-        }
-
-    private:
-        const Context &c_;
-        sealhip_rgsw *g_ = nullptr;
-    };
-
-    // The keys of a blind rotation, resident on the device: the RGSW encryptions of the indicators
-    // [s_j = 1] (and, for a ternary secret, [s_j = -1] behind each) of an LWE secret, in step order. Made by
-    // KeyGenerator::blind_rotation_keys; Evaluator::blind_rotate takes them.
-    class BlindRotationKeys
-    {
-    public:
-        BlindRotationKeys(std::vector<std::unique_ptr<RgswCiphertext>> keys, bool ternary) : keys_(std::move(keys)), ternary_(ternary)
-        {
-            for (const auto &g : keys_)
-                raw_.push_back(g->get());
-        }
-        std::size_t n_steps() const { return keys_.size(); }
-        bool ternary() const { return ternary_; }
-        const sealhip_rgsw *const *get() const { return raw_.empty() ? nullptr : raw_.data(); }
-
-    private:
-        std::vector<std::unique_ptr<RgswCiphertext>> keys_;
-        std::vector<const sealhip_rgsw *> raw_;
-        bool ternary_;
-    };
-
-    // The test vector of a lookup table for Evaluator::blind_rotate: the plaintext coefficients tv[j] = f(floor(j t / 2N)),
-    // j < N. Messages are restricted to [0, t/2); with b_offset = N / t in sealhip_lwe_mod_switch the windows are centred
-    // and the constant coefficient of the rotation's result is f(m).
-    inline std::vector<std::uint64_t> lut_test_vector(const std::function<std::uint64_t(std::uint64_t)> &f, std::uint64_t t,
-                                                      std::size_t n)
-    {
-        std::vector<std::uint64_t> tv(n);
-        for (std::size_t j = 0; j < n; j++)
-            tv[j] = f((j * t) / (2 * n));
-        return tv;
-    }
-
-    // What HomomorphicDFT and Bootstrapper share: the tables' handle (destroyed with the object, not copyable), the plan and
-    // its key steps. plan_entry(plan, key_steps, capacity) is the ABI's plan entry over the owner's arguments, called
-    // twice (the plan says how many steps there are); create(tables) its create entry. The plan comes first: its
-    // refusals need no device.
-    template <class Tables, class Plan, long (*Destroy)(Tables *)>
-    class PlannedTables
-    {
-    public:
-        ~PlannedTables()
-        {
-            if (tables_)
-                Destroy(tables_);
-        }
-        PlannedTables(const PlannedTables &) = delete;
-        PlannedTables &operator=(const PlannedTables &) = delete;
-        const Tables *get() const { return tables_; }
-        const Plan &plan() const { return plan_; }
-        std::size_t out_level() const { return plan_.out_level; }
-        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
-
-    protected:
-        PlannedTables() = default;
-        template <class PlanEntry, class Create>
-        void make(PlanEntry plan_entry, Create create)
-        {
-            throw_on(plan_entry(&plan_, nullptr, 0));
-            key_steps_.resize(plan_.n_key_steps);
-            throw_on(plan_entry(&plan_, key_steps_.data(), plan_.n_key_steps));
-            throw_on(create(&tables_));
-        }
-        Tables *tables_ = nullptr;
-        Plan plan_{};
-        std::vector<std::uint32_t> key_steps_;
-    };
-
-    // The plan and the device tables of one homomorphic DFT (sealhip_dft_tables_create): CoeffToSlot
-    // (SEALHIP_DFT_COEFFS_TO_SLOTS) or SlotToCoeff (SEALHIP_DFT_SLOTS_TO_COEFFS) for ciphertexts at level k, as the stages
-    // `stages` (layer counts in application order, summing to log2(N/2)). Evaluator::coeffs_to_slots / slots_to_coeffs take
-    // it; the result is n_stages levels lower at the same scale. key_steps(): the rotation steps whose Galois keys the
-    // client must make (CoeffToSlot also needs the key of element 2N - 1).
-    class HomomorphicDFT : public PlannedTables<sealhip_dft_tables, sealhip_dft_plan, sealhip_dft_tables_destroy>
-    {
-    public:
-        HomomorphicDFT(const Context &c, std::uint32_t direction, std::size_t k, const std::vector<std::uint32_t> &stages,
-                       const std::vector<std::uint32_t> &n_baby = {}, double gain = 1.0)
-        {
-            if (!n_baby.empty() && n_baby.size() != stages.size())
-                throw std::invalid_argument("n_baby and stages differ in length");
-            const std::uint32_t *nb = n_baby.empty() ? nullptr : n_baby.data();
-            const std::uint32_t n_stages = std::uint32_t(stages.size());
-            const auto plan_entry = [&](sealhip_dft_plan *p, std::uint32_t *steps, std::uint32_t capacity) {
-                return sealhip_evaluator_dft_plan(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, p, steps, capacity);
-            };
-            make(plan_entry, [&](sealhip_dft_tables **t) {
-                return sealhip_dft_tables_create(c.get(), direction, std::uint32_t(k), stages.data(), n_stages, nb, gain, t);
-            });
-        }
-        std::uint32_t direction() const { return plan_.direction; }
-        std::size_t in_level() const { return plan_.in_level; }
-    };
-
-    // The plan and the device tables of one bootstrap shape (sealhip_bootstrap_tables_create):
-    // ModRaise to level k_top, CoeffToSlot as `c2s_stages`, EvalMod (K, r, degree, n_baby), SlotToCoeff as `s2c_stages`.
-    // K bounds ModRaise's integer polynomial, K >= max|I| + 1: it grows with the secret's Hamming weight, and the library
-    // does not sample sparse secrets. Evaluator::bootstrap takes it; the result is at out_level() with the operand's scale,
-    // its precision bounded by |m| / q_0 (the sine step's relative error is (2 pi m / q_0)^2 / 6). key_steps(): the rotation
-    // steps whose Galois keys the client must make, next to the key of element 2N - 1.
-    class Bootstrapper : public PlannedTables<sealhip_bootstrap_tables, sealhip_bootstrap_plan, sealhip_bootstrap_tables_destroy>
-    {
-    public:
-        Bootstrapper(const Context &c, std::size_t k_top, const std::vector<std::uint32_t> &c2s_stages,
-                     const std::vector<std::uint32_t> &s2c_stages, std::uint32_t K, std::uint32_t r, std::uint32_t degree,
-                     std::uint32_t n_baby = 0)
-        {
-            const std::uint32_t n1 = std::uint32_t(c2s_stages.size()), n2 = std::uint32_t(s2c_stages.size());
-            const auto plan_entry = [&](sealhip_bootstrap_plan *p, std::uint32_t *steps, std::uint32_t capacity) {
-                return sealhip_evaluator_bootstrap_plan(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
-                                                        s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, p, steps, capacity);
-            };
-            make(plan_entry, [&](sealhip_bootstrap_tables **t) {
-                return sealhip_bootstrap_tables_create(c.get(), std::uint32_t(k_top), c2s_stages.data(), n1, nullptr,
-                                                       s2c_stages.data(), n2, nullptr, K, r, degree, n_baby, t);
-            });
-        }
-    };
-
-    // The device tables of one d x d complex matrix (sealhip_linear_transform_create): the diagonals
-    // that hold a non-zero entry, found, pre-rotated and encoded at the key level on the device, at `scale`. The matrix is
-    // row-major, d a power of two <= N/2; it is read from device memory (16-byte aligned: a torch tensor's data_ptr()), or
-    // from a host vector that is staged through the pool for the making. Evaluator::linear_transform takes the object at
-    // any level; for a ciphertext whose slots are z the result's slots are
-    //     out[p] = sum_c u_c[p] z[(p + c) mod n],  u_c[p] = M[p mod d][(p + c) mod d]
-    // -- M z, tiled, when z is a d-vector tiled N/2d times. n1: the baby stride (0: the default); key_steps(): the rotation
-    // steps whose Galois keys the client must make.
-    class LinearTransform
-    {
-    public:
-        LinearTransform(const Context &c, const double *matrix_dev, std::size_t d, double scale, std::uint32_t n1 = 0,
-                        double gain = 1.0)
-        {
-            make(c, matrix_dev, d, scale, n1, gain);
-        }
-        LinearTransform(const Context &c, const std::vector<std::complex<double>> &matrix, std::size_t d, double scale,
-                        std::uint32_t n1 = 0, double gain = 1.0)
-        {
-            if (matrix.size() != d * d)
-                throw std::invalid_argument("matrix must hold d x d entries");
-            sealhip_lintrans_plan dense; // (d and n1 are refused before the staging needs a device)
-            throw_on(sealhip_linear_transform_plan(c.get(), std::uint32_t(d), nullptr, n1, &dense, nullptr, nullptr, nullptr, 0));
-            Staged m(c, 2 * d * d);
-            m.up(reinterpret_cast<const std::uint64_t *>(matrix.data()), 2 * d * d);
-            make(c, reinterpret_cast<const double *>(m.ptr()), d, scale, n1, gain);
-        }
-        ~LinearTransform()
-        {
-            if (tables_)
-                sealhip_linear_transform_destroy(tables_);
-        }
-        LinearTransform(const LinearTransform &) = delete;
-        LinearTransform &operator=(const LinearTransform &) = delete;
-        const sealhip_linear_transform *get() const { return tables_; }
-        const sealhip_lintrans_plan &plan() const { return plan_; }
-        double scale() const { return scale_; }
-        const std::vector<int> &baby_steps() const { return baby_; }
-        const std::vector<int> &giant_steps() const { return giant_; }
-        const std::vector<std::uint32_t> &key_steps() const { return key_steps_; }
-        const std::uint64_t *plain_ntt() const // device: n_giant x n_baby x n_key x N words
-        {
-            const std::uint64_t *p = nullptr;
-            throw_on(sealhip_linear_transform_tables_plain(tables_, &p));
-            return p;
-        }
-
-    private:
-        void make(const Context &c, const double *matrix_dev, std::size_t d, double scale, std::uint32_t n1, double gain)
-        {
-            throw_on(sealhip_linear_transform_create(c.get(), matrix_dev, std::uint32_t(d), n1, scale, gain, &tables_));
-            throw_on(sealhip_linear_transform_tables_plan(tables_, &plan_, &scale_));
-            std::vector<std::int32_t> b(plan_.n_baby), g(plan_.n_giant);
-            throw_on(sealhip_linear_transform_tables_steps(tables_, b.data(), g.data()));
-            baby_.assign(b.begin(), b.end());
-            giant_.assign(g.begin(), g.end());
-            for (int s : baby_)
-                if (s)
-                    key_steps_.push_back(std::uint32_t(s));
-            for (int s : giant_)
-                if (s)
-                    key_steps_.push_back(std::uint32_t(s));
-            std::sort(key_steps_.begin(), key_steps_.end());
-            key_steps_.erase(std::unique(key_steps_.begin(), key_steps_.end()), key_steps_.end());
-        }
-        sealhip_linear_transform *tables_ = nullptr;
-        sealhip_lintrans_plan plan_{};
-        double scale_ = 0;
-        std::vector<int> baby_, giant_;
-        std::vector<std::uint32_t> key_steps_;
-    };
-
-    // LWE samples of coefficients of one resident ciphertext (Evaluator::extract_lwe / pack_lwes): a is
-    // n x k x N words and b is n x k words, in two blocks of the context's pool, with the level and the scale of the
-    // ciphertext they came from. Move-only.
-    class LweSamples
-    {
-    public:
-        explicit LweSamples(const Context &context) : ctx_(&context) {}
-        LweSamples(LweSamples &&) = default;
-        LweSamples &operator=(LweSamples &&) = default;
-        std::size_t size() const { return n_; } // samples
-        std::size_t coeff_modulus_size() const { return k_; }
-        double &scale() { return scale_; }
-        double scale() const { return scale_; }
-        const std::uint64_t *a() const { return a_ ? a_->ptr() : nullptr; } // DEVICE pointers
-        const std::uint64_t *b() const { return b_ ? b_->ptr() : nullptr; }
-        // (Evaluator) fresh blocks for n samples at level k
-        void reset(std::size_t n, std::size_t k)
-        {
-            a_.reset(new Staged(*ctx_, n * k * ctx_->n()));
-            b_.reset(new Staged(*ctx_, n * k));
-            n_ = n;
-            k_ = k;
-        }
-        std::uint64_t *a_out() { return a_->ptr(); }
-        std::uint64_t *b_out() { return b_->ptr(); }
-
-    private:
-        const Context *ctx_;
-        std::unique_ptr<Staged> a_, b_;
-        std::size_t n_ = 0, k_ = 0;
-        double scale_ = 1.0;
-    };
-
     template <class CT>
     class Evaluator
     {
@@ -939,9 +95,7 @@ namespace sealhip_host
                 throw std::invalid_argument("not enough relinearization keys"); // :793-796
             if (size == 2)
                 return;
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (auto *rk : relin_keys)
-                raw.push_back(rk ? rk->get() : nullptr);
+            const std::vector<const sealhip_kswitch_key *> raw = raw_relin_keys(relin_keys);
             Dev c = dev_in(encrypted, size * k * n);
             Check chk = checked(encrypted);
             throw_on(sealhip_evaluator_relinearize(ctx_.get(), std::uint32_t(k), c.ptr(), std::uint32_t(size), 1,
@@ -994,8 +148,7 @@ namespace sealhip_host
         template <class C, IfCt<C> = 0>
         void rotate_vector_inplace(C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // :1205-1208
+            require_scheme(SEALHIP_SCHEME_CKKS); // :1205-1208
             rotate_vector_like(encrypted, steps, galois_keys);
         }
         // rotate_internal (evaluator.cpp:1945-2000): one automorphism when its key is present, else the NAF of the step count
@@ -1030,8 +183,7 @@ namespace sealhip_host
         template <class C, IfCt<C> = 0>
         void rotate_rows_inplace(C &encrypted, int steps, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                throw std::logic_error("unsupported scheme"); // :1061-1064
+            require_scheme(SEALHIP_SCHEME_BFV); // :1061-1064
             rotate_vector_like(encrypted, steps, galois_keys);
         }
         // Evaluator::rotate_columns_inplace (evaluator.h:1131-1139): BFV only; conjugate_internal = apply_galois with
@@ -1039,16 +191,14 @@ namespace sealhip_host
         template <class C, IfCt<C> = 0>
         void rotate_columns_inplace(C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                throw std::logic_error("unsupported scheme"); // :1134-1137
+            require_scheme(SEALHIP_SCHEME_BFV); // :1134-1137
             conjugate_internal(encrypted, galois_keys);
         }
         // Evaluator::complex_conjugate_inplace (evaluator.h:1269-1277): CKKS only, the same automorphism
         template <class C, IfCt<C> = 0>
         void complex_conjugate_inplace(C &encrypted, const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // :1272-1275
+            require_scheme(SEALHIP_SCHEME_CKKS); // :1272-1275
             conjugate_internal(encrypted, galois_keys);
         }
 
@@ -1067,14 +217,8 @@ namespace sealhip_host
                                const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<C> &destinations)
         {
             check_galois_operand(encrypted);
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (std::uint32_t elt : galois_elts)
-            {
-                auto it = galois_keys.find(elt);
-                if (it == galois_keys.end() || !it->second)
-                    throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
-                raw.push_back(it->second->get());
-            }
+            // (the ABI entry reads a key for every element: the identity is not exempt here)
+            const std::vector<const sealhip_kswitch_key *> raw = keys_of(galois_elts, galois_keys, false);
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), count = galois_elts.size(), words = 2 * k * n;
             if (count == 0)
                 return destinations.clear();
@@ -1092,14 +236,7 @@ namespace sealhip_host
                                 const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<C> &destinations)
         {
             check_galois_operand(encrypted);
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (auto &kv : galois_keys)
-                if (kv.second)
-                {
-                    elts.push_back(kv.first);
-                    raw.push_back(kv.second->get());
-                }
+            const KeyLists keys = key_lists(galois_keys);
             std::vector<std::int32_t> st(steps.begin(), steps.end());
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), count = st.size(), words = 2 * k * n;
             if (count == 0)
@@ -1107,7 +244,8 @@ namespace sealhip_host
             Dev c = dev_in(encrypted, words), o = dev_out(count * words);
             Check chk = checked(encrypted, count);
             throw_on(sealhip_evaluator_rotate_vector_many(ctx_.get(), std::uint32_t(k), c.ptr(), 1, st.data(), std::uint32_t(count),
-                                                          elts.data(), raw.data(), std::uint32_t(elts.size()), o.ptr()));
+                                                          keys.elts.data(), keys.raw.data(), std::uint32_t(keys.elts.size()),
+                                                          o.ptr()));
             chk.done();
             scatter(encrypted, o, count, words, destinations);
         }
@@ -1136,19 +274,13 @@ namespace sealhip_host
         {
             if (!samples.a())
                 throw std::invalid_argument("samples are empty");
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (auto &kv : galois_keys)
-                if (kv.second)
-                {
-                    elts.push_back(kv.first);
-                    raw.push_back(kv.second->get());
-                }
+            const KeyLists keys = key_lists(galois_keys);
             const std::size_t k = samples.coeff_modulus_size(), words = 2 * k * ctx_.n();
             Dev o = dev_out(words);
             Check chk = checked(destination);
-            throw_on(sealhip_evaluator_pack_lwes(ctx_.get(), std::uint32_t(k), samples.a(), samples.b(), samples.size(), 1, elts.data(),
-                                                 raw.data(), std::uint32_t(elts.size()), trace ? 1 : 0, normalize ? 1 : 0, o.ptr()));
+            throw_on(sealhip_evaluator_pack_lwes(ctx_.get(), std::uint32_t(k), samples.a(), samples.b(), samples.size(), 1,
+                                                 keys.elts.data(), keys.raw.data(), std::uint32_t(keys.elts.size()), trace ? 1 : 0,
+                                                 normalize ? 1 : 0, o.ptr()));
             chk.done();
             destination.adopt(o.st->release(), words, 2, k);
             destination.is_ntt_form() = ctx_.scheme() == SEALHIP_SCHEME_CKKS;
@@ -1169,19 +301,12 @@ namespace sealhip_host
             check_galois_operand(encrypted);
             if (n == 0)
                 throw std::invalid_argument("n must be a power of two between 1 and N");
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (auto &kv : galois_keys)
-                if (kv.second)
-                {
-                    elts.push_back(kv.first);
-                    raw.push_back(kv.second->get());
-                }
+            const KeyLists keys = key_lists(galois_keys);
             const std::size_t k = encrypted.coeff_modulus_size(), words = 2 * k * ctx_.n();
             Dev c = dev_in(encrypted, words), o = dev_out(n * words);
             Check chk = checked(encrypted, n);
-            throw_on(sealhip_evaluator_expand(ctx_.get(), std::uint32_t(k), c.ptr(), 1, n, elts.data(), raw.data(),
-                                              std::uint32_t(elts.size()), normalize ? 1 : 0, o.ptr()));
+            throw_on(sealhip_evaluator_expand(ctx_.get(), std::uint32_t(k), c.ptr(), 1, n, keys.elts.data(), keys.raw.data(),
+                                              std::uint32_t(keys.elts.size()), normalize ? 1 : 0, o.ptr()));
             chk.done();
             scatter(encrypted, o, n, words, destinations);
         }
@@ -1227,25 +352,17 @@ namespace sealhip_host
                 throw_on(sealhip_memcpy_d2d(ctx_.get(), x.ptr() + i * words, terms[i].data(), words * 8));
             for (std::size_t s = 0; s < n_sums; s++)
                 for (std::size_t i = 0; i < n_terms; i++)
-                    plain_to(*plains[s][i], w.ptr() + (s * n_terms + i) * pw, pw);
+                    plain_to(plain_view(*plains[s][i]), w.ptr() + (s * n_terms + i) * pw, pw);
             Dev o = dev_out(n_sums * words);
             Check chk = checked(terms[0], n_sums);
             throw_on(sealhip_evaluator_dot_plain(ctx_.get(), std::uint32_t(k), x.ptr(), std::uint32_t(n_terms), std::uint32_t(size), 1,
                                                  w.ptr(), std::uint32_t(n_sums), o.ptr()));
             chk.done();
-            std::vector<DeviceCiphertext> next;
-            next.reserve(n_sums);
-            for (std::size_t s = 0; s < n_sums; s++)
-            {
-                next.emplace_back(ctx_);
-                Staged one(ctx_, words); // (each destination owns a pool block of its own)
-                throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), o.ptr() + s * words, words * 8));
-                next[s].adopt(one.release(), words, size, k);
-                next[s].copy_meta(terms[0]);
+            const double scale = terms[0].scale() * plains[0][0]->scale(); // (the destinations may be the terms)
+            scatter(terms[0], o, n_sums, words, destinations, k, size);
+            for (DeviceCiphertext &d : destinations)
                 if (ckks)
-                    next[s].scale() = terms[0].scale() * plains[0][0]->scale();
-            }
-            destinations.swap(next);
+                    d.scale() = scale;
         }
 
         // Plaintext-weighted sums of rotations (sealhip_evaluator_apply_galois_dot_plain):
@@ -1281,49 +398,9 @@ namespace sealhip_host
                                              const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                              const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            require_scheme(SEALHIP_SCHEME_CKKS); // evaluator.h:1205-1208
             dot_plain_internal(encrypted, elts_of_steps(steps), galois_keys, plains, destinations, true);
         }
-
-    private:
-        template <class C, class P>
-        void dot_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &galois_elts,
-                                const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
-                                const std::vector<std::vector<P>> &plains, std::vector<C> &destinations, bool rescale)
-        {
-            check_galois_operand(encrypted);
-            if (rescale)
-                check_rescale_operand(encrypted);
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (std::uint32_t elt : galois_elts)
-            {
-                auto it = galois_keys.find(elt);
-                if (elt != 1 && (it == galois_keys.end() || !it->second))
-                    throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
-                raw.push_back(elt != 1 ? it->second->get() : nullptr);
-            }
-            const std::size_t n_elts = galois_elts.size(), n_sums = plains.size();
-            const double scale = check_dot_plains(plains, n_elts);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
-            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
-            Dev c = dev_in(encrypted, words), o = dev_out((n_sums ? n_sums : 1) * out_words);
-            Staged w(ctx_, n_sums * n_elts ? n_sums * n_elts * pw : 1);
-            for (std::size_t s = 0; s < n_sums; s++)
-                for (std::size_t i = 0; i < n_elts; i++)
-                    plain_to(plains[s][i], w.ptr() + (s * n_elts + i) * pw, pw);
-            Check chk = checked(encrypted, n_sums ? n_sums : 1);
-            throw_on((rescale ? sealhip_evaluator_apply_galois_dot_plain_rescale : sealhip_evaluator_apply_galois_dot_plain)(
-                ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(), raw.data(), std::uint32_t(n_elts), w.ptr(),
-                std::uint32_t(n_sums), o.ptr()));
-            chk.done();
-            scatter(encrypted, o, n_sums, out_words, destinations, k_out);
-            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
-                for (C &d : destinations)
-                    d.scale() = encrypted.scale() * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
-        }
-
-    public:
         // The same by rotation steps (sealhip_evaluator_rotate_vector_dot_plain): CKKS rotate_vector's steps; step 0 is the
         // identity; no non-adjacent-form fallback
         template <class C, class P, IfCt<C> = 0>
@@ -1331,8 +408,7 @@ namespace sealhip_host
                                      const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                      const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            require_scheme(SEALHIP_SCHEME_CKKS); // evaluator.h:1205-1208
             apply_galois_dot_plain(encrypted, elts_of_steps(steps), galois_keys, plains, destinations);
         }
         // ... and BFV rotate_rows' steps
@@ -1341,8 +417,7 @@ namespace sealhip_host
                                    const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                    const std::vector<std::vector<P>> &plains, std::vector<C> &destinations)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1061-1064
+            require_scheme(SEALHIP_SCHEME_BFV); // evaluator.h:1061-1064
             apply_galois_dot_plain(encrypted, elts_of_steps(steps), galois_keys, plains, destinations);
         }
 
@@ -1378,59 +453,11 @@ namespace sealhip_host
                                               const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                               const std::vector<std::vector<P>> &plains, C &destination)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            require_scheme(SEALHIP_SCHEME_CKKS); // evaluator.h:1205-1208
             bsgs_plain_internal(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains, destination,
                                 true);
         }
 
-    private:
-        template <class C, class P>
-        void bsgs_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &baby_elts,
-                                 const std::vector<std::uint32_t> &giant_elts,
-                                 const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
-                                 const std::vector<std::vector<P>> &plains, C &destination, bool rescale)
-        {
-            check_galois_operand(encrypted);
-            if (rescale)
-                check_rescale_operand(encrypted);
-            const auto raw_keys = [&](const std::vector<std::uint32_t> &elts) {
-                std::vector<const sealhip_kswitch_key *> raw;
-                for (std::uint32_t elt : elts)
-                {
-                    auto it = galois_keys.find(elt);
-                    if (elt != 1 && (it == galois_keys.end() || !it->second))
-                        throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
-                    raw.push_back(elt != 1 ? it->second->get() : nullptr);
-                }
-                return raw;
-            };
-            const std::vector<const sealhip_kswitch_key *> bk = raw_keys(baby_elts), gk = raw_keys(giant_elts);
-            const std::size_t n_baby = baby_elts.size(), n_giant = giant_elts.size();
-            if (plains.size() != n_giant)
-                throw std::invalid_argument("plains must hold one row of plaintexts per giant element");
-            const double scale = check_dot_plains(plains, n_baby);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
-            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
-            Dev c = dev_in(encrypted, words), o = dev_out(out_words);
-            Staged w(ctx_, (n_giant && n_baby) ? n_giant * n_baby * pw : 1);
-            for (std::size_t j = 0; j < n_giant; j++)
-                for (std::size_t i = 0; i < n_baby; i++)
-                    plain_to(plains[j][i], w.ptr() + (j * n_baby + i) * pw, pw);
-            Check chk = checked(encrypted, 1);
-            throw_on((rescale ? sealhip_evaluator_apply_galois_bsgs_plain_rescale : sealhip_evaluator_apply_galois_bsgs_plain)(
-                ctx_.get(), std::uint32_t(k), c.ptr(), 1, baby_elts.data(), bk.data(), std::uint32_t(n_baby), giant_elts.data(),
-                gk.data(), std::uint32_t(n_giant), w.ptr(), o.ptr()));
-            chk.done();
-            const double in_scale = encrypted.scale(); // (the destination may be the operand)
-            std::vector<C> one;
-            scatter(encrypted, o, 1, out_words, one, k_out);
-            destination = std::move(one[0]);
-            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
-                destination.scale() = in_scale * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
-        }
-
-    public:
         // CoeffToSlot in one call (sealhip_evaluator_coeffs_to_slots): slot j of destination_re /
         // destination_im holds coefficient bitrev(j) / bitrev(j) + N/2 of the operand's message over its scale. The results
         // are dft.out_level() primes long at the operand's scale. galois_keys: element -> key, with the keys of
@@ -1441,14 +468,12 @@ namespace sealhip_host
                              C &destination_im)
         {
             check_dft_operand(encrypted, dft, SEALHIP_DFT_COEFFS_TO_SLOTS);
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            dft_keys(galois_keys, elts, raw);
+            const KeyLists keys = key_lists(galois_keys);
             const std::size_t n = ctx_.n(), words = 2 * dft.in_level() * n, out_words = 2 * dft.out_level() * n;
             Dev c = dev_in(encrypted, words), o = dev_out(2 * out_words);
             Check chk = checked(encrypted, 2);
-            throw_on(sealhip_evaluator_coeffs_to_slots(ctx_.get(), dft.get(), c.ptr(), 1, elts.data(), raw.data(),
-                                                       std::uint32_t(elts.size()), o.ptr(), o.ptr() + out_words));
+            throw_on(sealhip_evaluator_coeffs_to_slots(ctx_.get(), dft.get(), c.ptr(), 1, keys.elts.data(), keys.raw.data(),
+                                                       std::uint32_t(keys.elts.size()), o.ptr(), o.ptr() + out_words));
             chk.done();
             std::vector<C> two;
             scatter(encrypted, o, 2, out_words, two, dft.out_level());
@@ -1464,18 +489,12 @@ namespace sealhip_host
             check_dft_operand(encrypted_im, dft, SEALHIP_DFT_SLOTS_TO_COEFFS);
             if (encrypted_re.scale() != encrypted_im.scale())
                 throw std::invalid_argument("scale mismatch");
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            dft_keys(galois_keys, elts, raw);
-            const std::size_t n = ctx_.n(), words = 2 * dft.in_level() * n, out_words = 2 * dft.out_level() * n;
-            Dev a = dev_in(encrypted_re, words), b = dev_in(encrypted_im, words), o = dev_out(out_words);
-            Check chk = checked(encrypted_re, 1);
-            throw_on(sealhip_evaluator_slots_to_coeffs(ctx_.get(), dft.get(), a.ptr(), b.ptr(), 1, elts.data(), raw.data(),
-                                                       std::uint32_t(elts.size()), o.ptr()));
-            chk.done();
-            std::vector<C> one;
-            scatter(encrypted_re, o, 1, out_words, one, dft.out_level());
-            destination = std::move(one[0]);
+            const KeyLists keys = key_lists(galois_keys);
+            Dev im = dev_in(encrypted_im, 2 * dft.in_level() * ctx_.n());
+            to_size2(encrypted_re, 2, dft.out_level(), destination, nullptr, [&](const std::uint64_t *re, std::uint64_t *o) {
+                return sealhip_evaluator_slots_to_coeffs(ctx_.get(), dft.get(), re, im.ptr(), 1, keys.elts.data(), keys.raw.data(),
+                                                         std::uint32_t(keys.elts.size()), o);
+            });
         }
 
         // The matrix of `lt` applied to the slots of `encrypted` (sealhip_evaluator_linear_transform),
@@ -1486,59 +505,18 @@ namespace sealhip_host
         void linear_transform(const C &encrypted, const LinearTransform &lt,
                               const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, C &destination, bool rescale = false)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme");
-            check_galois_operand(encrypted);
+            check_ckks_operand(encrypted); // (CKKS, the scheme's form, size 2)
             if (rescale)
                 check_rescale_operand(encrypted);
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            dft_keys(galois_keys, elts, raw);
-            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n;
-            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
-            Dev c = dev_in(encrypted, words), o = dev_out(out_words);
-            Check chk = checked(encrypted, 1);
-            throw_on(sealhip_evaluator_linear_transform(ctx_.get(), lt.get(), std::uint32_t(k), c.ptr(), 1, elts.data(), raw.data(),
-                                                        std::uint32_t(elts.size()), rescale ? 1 : 0, o.ptr()));
-            chk.done();
-            const double in_scale = encrypted.scale(); // (the destination may be the operand)
-            std::vector<C> one;
-            scatter(encrypted, o, 1, out_words, one, k_out);
-            destination = std::move(one[0]);
-            destination.scale() = in_scale * lt.scale() / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
+            const KeyLists keys = key_lists(galois_keys);
+            const std::size_t k = encrypted.coeff_modulus_size();
+            const double scale = encrypted.scale() * lt.scale() / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
+            to_size2(encrypted, 2, rescale ? k - 1 : k, destination, &scale, [&](const std::uint64_t *c, std::uint64_t *o) {
+                return sealhip_evaluator_linear_transform(ctx_.get(), lt.get(), std::uint32_t(k), c, 1, keys.elts.data(),
+                                                          keys.raw.data(), std::uint32_t(keys.elts.size()), rescale ? 1 : 0, o);
+            });
         }
 
-    private:
-        template <class C>
-        void check_dft_operand(const C &encrypted, const HomomorphicDFT &dft, std::uint32_t direction) const
-        {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme");
-            check_galois_operand(encrypted);
-            if (dft.direction() != direction)
-                throw std::invalid_argument("the DFT tables were made for the other direction");
-            if (encrypted.coeff_modulus_size() != dft.in_level())
-                throw std::invalid_argument("encrypted is not at the level of the DFT tables");
-        }
-        template <class C>
-        void check_bootstrap_operand(const C &encrypted) const
-        {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme");
-            check_galois_operand(encrypted);
-        }
-        static void dft_keys(const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys, std::vector<std::uint32_t> &elts,
-                             std::vector<const sealhip_kswitch_key *> &raw)
-        {
-            for (const auto &kv : galois_keys)
-                if (kv.second)
-                {
-                    elts.push_back(kv.first);
-                    raw.push_back(kv.second->get());
-                }
-        }
-
-    public:
         // The same by rotation steps (sealhip_evaluator_rotate_vector_bsgs_plain): CKKS rotate_vector's steps; step 0 is the
         // identity; no non-adjacent-form fallback
         template <class C, class P, IfCt<C> = 0>
@@ -1546,8 +524,7 @@ namespace sealhip_host
                                       const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                       const std::vector<std::vector<P>> &plains, C &destination)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1205-1208
+            require_scheme(SEALHIP_SCHEME_CKKS); // evaluator.h:1205-1208
             apply_galois_bsgs_plain(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains,
                                     destination);
         }
@@ -1557,8 +534,7 @@ namespace sealhip_host
                                     const std::map<std::uint32_t, const KSwitchKeys *> &galois_keys,
                                     const std::vector<std::vector<P>> &plains, C &destination)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                throw std::logic_error("unsupported scheme"); // evaluator.h:1061-1064
+            require_scheme(SEALHIP_SCHEME_BFV); // evaluator.h:1061-1064
             apply_galois_bsgs_plain(encrypted, elts_of_steps(baby_steps), elts_of_steps(giant_steps), galois_keys, plains,
                                     destination);
         }
@@ -1817,12 +793,8 @@ namespace sealhip_host
         void evaluate_polynomial(const C &encrypted, const std::vector<std::uint64_t> &coeffs,
                                  const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                throw std::logic_error("unsupported scheme");
-            if (encrypted.is_ntt_form())
-                throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-            if (encrypted.size() != 2)
-                throw std::invalid_argument("encrypted size must be 2");
+            require_scheme(SEALHIP_SCHEME_BFV);
+            check_galois_operand(encrypted);
             if (coeffs.empty())
                 throw std::invalid_argument("coeffs must not be empty");
             const std::size_t k = encrypted.coeff_modulus_size();
@@ -1850,12 +822,7 @@ namespace sealhip_host
                                  const std::vector<const KSwitchKeys *> &relin_keys, C &destination, std::uint32_t basis = 0,
                                  double scale_out = 0.0)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme");
-            if (!encrypted.is_ntt_form())
-                throw std::invalid_argument("CKKS encrypted must be in NTT form");
-            if (encrypted.size() != 2)
-                throw std::invalid_argument("encrypted size must be 2");
+            check_ckks_operand(encrypted);
             if (coeffs.empty())
                 throw std::invalid_argument("coeffs must not be empty");
             const std::size_t k = encrypted.coeff_modulus_size();
@@ -1903,7 +870,7 @@ namespace sealhip_host
         template <class C, IfCt<C> = 0>
         void mod_raise(const C &encrypted, std::size_t k_out, C &destination)
         {
-            check_bootstrap_operand(encrypted);
+            check_ckks_operand(encrypted);
             const std::size_t k = encrypted.coeff_modulus_size();
             if (k_out < 2)
                 throw std::invalid_argument("k_out must be at least 2");
@@ -1915,7 +882,7 @@ namespace sealhip_host
         template <class C, IfCt<C> = 0>
         void double_angle(const C &encrypted, const std::vector<const KSwitchKeys *> &relin_keys, C &destination)
         {
-            check_bootstrap_operand(encrypted);
+            check_ckks_operand(encrypted);
             const sealhip_kswitch_key *raw = first_relin_key(relin_keys);
             const std::size_t k = encrypted.coeff_modulus_size();
             if (k < 2)
@@ -1932,7 +899,7 @@ namespace sealhip_host
                       const std::vector<const KSwitchKeys *> &relin_keys, C &destination, std::uint32_t n_baby = 0,
                       double scale_out = 0.0)
         {
-            check_bootstrap_operand(encrypted);
+            check_ckks_operand(encrypted);
             const std::size_t k = encrypted.coeff_modulus_size();
             sealhip_evalmod_plan plan{};
             throw_on(sealhip_evaluator_evalmod_plan(ctx_.get(), std::uint32_t(k), encrypted.scale(), K, r, degree, n_baby, scale_out,
@@ -2097,9 +1064,7 @@ namespace sealhip_host
                 dev.push_back(dev_in(c, words));
                 ptrs.push_back(dev.back().ptr());
             }
-            std::vector<const sealhip_kswitch_key *> raw;
-            for (auto *rk : relin_keys)
-                raw.push_back(rk ? rk->get() : nullptr);
+            const std::vector<const sealhip_kswitch_key *> raw = raw_relin_keys(relin_keys);
             Dev o = dev_out(words);
             Check chk = checked(destination); // the composite entry leaves the sink alone: the read pass notes the product
             throw_on(sealhip_evaluator_multiply_many(ctx_.get(), std::uint32_t(k), ptrs.data(), std::uint32_t(ptrs.size()), 1,
@@ -2147,8 +1112,7 @@ namespace sealhip_host
             const std::size_t dest = s1 + s2 - 1, out_size = relin_keys && dest > 2 ? 2 : dest;
             std::vector<const sealhip_kswitch_key *> raw;
             if (relin_keys)
-                for (auto *rk : *relin_keys)
-                    raw.push_back(rk ? rk->get() : nullptr);
+                raw = raw_relin_keys(*relin_keys);
             // the results land in fresh buffers of the final size, then replace the operands' storage
             std::vector<std::vector<std::uint64_t>> res(count, std::vector<std::uint64_t>(out_size * k * ctx_.n()));
             std::vector<const std::uint64_t *> pa(count), pb(count);
@@ -2180,15 +1144,11 @@ namespace sealhip_host
                     throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
                 p.push_back(ct->data());
             }
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> keys;
-            for (auto &kv : galois_keys)
-            {
-                elts.push_back(kv.first);
-                keys.push_back(kv.second ? kv.second->get() : nullptr);
-            }
-            throw_on(sealhip_evaluator_rotate_vector_host(ctx_.get(), std::uint32_t(k), p.data(), p.size(), steps, elts.data(),
-                                                          keys.data(), std::uint32_t(elts.size())));
+            // (an entry without a key stays on the lists: the ABI refuses its element, it does not fall back on the
+            // non-adjacent form)
+            const KeyLists keys = key_lists(galois_keys, true);
+            throw_on(sealhip_evaluator_rotate_vector_host(ctx_.get(), std::uint32_t(k), p.data(), p.size(), steps, keys.elts.data(),
+                                                          keys.raw.data(), std::uint32_t(keys.elts.size())));
         }
 
         // The vector entries above read / write the ciphertexts' own buffers; a pool block (mempool.cpp:45,145) pinned here
@@ -2389,6 +1349,105 @@ namespace sealhip_host
         }
 
     private:
+        // A method is: the checks of this section, in the reference's order; the key lists; the operands as Dev; a Check around
+        // the ABI entry; and the result delivered by commit / to_size2 / scatter. A new method calls these helpers; it does
+        // not restate them.
+
+        // ---- checks
+        void require_scheme(std::uint32_t scheme) const
+        {
+            if (ctx_.scheme() != scheme)
+                throw std::logic_error("unsupported scheme");
+        }
+        // the scheme's form of a ciphertext operand (evaluator.cpp:1304-1311)
+        template <class C>
+        void check_form(const C &encrypted) const
+        {
+            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
+            if (bfv && encrypted.is_ntt_form())
+                throw std::invalid_argument("BFV encrypted cannot be in NTT form");
+            if (!bfv && !encrypted.is_ntt_form())
+                throw std::invalid_argument("CKKS encrypted must be in NTT form");
+        }
+        // apply_galois_inplace's checks on the operand (evaluator.cpp:1848-1887)
+        template <class C>
+        void check_galois_operand(const C &encrypted) const
+        {
+            check_form(encrypted);
+            if (encrypted.size() != 2)
+                throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
+        }
+        // what every *_rescale method adds to the unmerged method's checks (DESIGN.md section 19)
+        template <class C>
+        void check_rescale_operand(const C &encrypted) const
+        {
+            require_scheme(SEALHIP_SCHEME_CKKS); // (rescale_to_next: evaluator.cpp:1098-1101)
+            check_form(encrypted);
+            if (encrypted.coeff_modulus_size() < 2)
+                throw std::invalid_argument("end of modulus switching chain reached"); // :1005-1008
+        }
+        // a size-2 operand of a CKKS-only method
+        template <class C>
+        void check_ckks_operand(const C &encrypted) const
+        {
+            require_scheme(SEALHIP_SCHEME_CKKS);
+            check_galois_operand(encrypted);
+        }
+        template <class C>
+        void check_dft_operand(const C &encrypted, const HomomorphicDFT &dft, std::uint32_t direction) const
+        {
+            check_ckks_operand(encrypted);
+            if (dft.direction() != direction)
+                throw std::invalid_argument("the DFT tables were made for the other direction");
+            if (encrypted.coeff_modulus_size() != dft.in_level())
+                throw std::invalid_argument("encrypted is not at the level of the DFT tables");
+        }
+
+        // ---- key lists, as the ABI takes them
+        using GaloisKeyMap = std::map<std::uint32_t, const KSwitchKeys *>;
+        struct KeyLists
+        {
+            std::vector<std::uint32_t> elts;
+            std::vector<const sealhip_kswitch_key *> raw;
+        };
+        // every key of the map as parallel (element, handle) lists; an entry without a key is left out, or kept with a null
+        // handle
+        static KeyLists key_lists(const GaloisKeyMap &galois_keys, bool keep_null = false)
+        {
+            KeyLists keys;
+            for (const auto &kv : galois_keys)
+                if (kv.second || keep_null)
+                {
+                    keys.elts.push_back(kv.first);
+                    keys.raw.push_back(kv.second ? kv.second->get() : nullptr);
+                }
+            return keys;
+        }
+        // the key of each listed element; identity_exempt: element 1 needs no key and gets a null handle
+        static std::vector<const sealhip_kswitch_key *> keys_of(const std::vector<std::uint32_t> &galois_elts,
+                                                                const GaloisKeyMap &galois_keys, bool identity_exempt)
+        {
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (std::uint32_t elt : galois_elts)
+            {
+                const bool exempt = identity_exempt && elt == 1;
+                auto it = galois_keys.find(elt);
+                if (!exempt && (it == galois_keys.end() || !it->second))
+                    throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
+                raw.push_back(exempt ? nullptr : it->second->get());
+            }
+            return raw;
+        }
+        // relin_keys[i] = key of get_index(i + 2), or null
+        static std::vector<const sealhip_kswitch_key *> raw_relin_keys(const std::vector<const KSwitchKeys *> &relin_keys)
+        {
+            std::vector<const sealhip_kswitch_key *> raw;
+            for (auto *rk : relin_keys)
+                raw.push_back(rk ? rk->get() : nullptr);
+            return raw;
+        }
+
+        // ---- operands and results on the device
         // The words of an operand on the device for one call: a host ciphertext is staged through a pool block (up, and
         // down again for an in-place result), a resident one is its own block.
         struct Dev
@@ -2397,42 +1456,28 @@ namespace sealhip_host
             std::uint64_t *p = nullptr;
             std::uint64_t *ptr() const { return p; }
         };
-        Dev dev_in(const CT &c, std::size_t words)
+        Dev dev_out(std::size_t words) // a fresh pool block
         {
             Dev d;
             d.st.reset(new Staged(ctx_, words));
-            d.st->up(c.data(), words);
             d.p = d.st->ptr();
             return d;
         }
-        Dev dev_in(const DeviceCiphertext &c, std::size_t)
+        Dev dev_staged(const std::uint64_t *host, std::size_t words) // ... holding the host words
         {
-            Dev d;
-            d.p = const_cast<std::uint64_t *>(c.data());
+            Dev d = dev_out(words);
+            d.st->up(host, words);
             return d;
         }
-        Dev dev_plain(const std::uint64_t *plain, std::size_t words, bool)
-        {
-            Dev d;
-            d.st.reset(new Staged(ctx_, words));
-            d.st->up(plain, words);
-            d.p = d.st->ptr();
-            return d;
-        }
+        static Dev dev_resident(const std::uint64_t *device) { return Dev{ nullptr, const_cast<std::uint64_t *>(device) }; }
+        Dev dev_in(const CT &c, std::size_t words) { return dev_staged(c.data(), words); }
+        Dev dev_in(const DeviceCiphertext &c, std::size_t) { return dev_resident(c.data()); }
+        Dev dev_plain(const std::uint64_t *plain, std::size_t words, bool) { return dev_staged(plain, words); }
         Dev dev_plain(const DevicePlaintext &plain, std::size_t words, bool ntt_form)
         {
             if (plain.is_ntt_form() != ntt_form || plain.words() != words)
                 throw std::invalid_argument("plain is not valid for encryption parameters");
-            Dev d;
-            d.p = const_cast<std::uint64_t *>(plain.data());
-            return d;
-        }
-        Dev dev_out(std::size_t words)
-        {
-            Dev d;
-            d.st.reset(new Staged(ctx_, words));
-            d.p = d.st->ptr();
-            return d;
+            return dev_resident(plain.data());
         }
         void dev_back(CT &c, Dev &d, std::size_t words) { d.st->down(c.data(), words); }
         void dev_back(DeviceCiphertext &, Dev &, std::size_t) {}
@@ -2547,19 +1592,16 @@ namespace sealhip_host
                                 const std::vector<const KSwitchKeys *> &relin_keys, const sealhip_kswitch_key *to_sparse,
                                 const sealhip_kswitch_key *to_dense, C &destination)
         {
-            check_bootstrap_operand(encrypted);
+            check_ckks_operand(encrypted);
             const sealhip_kswitch_key *relin = first_relin_key(relin_keys);
-            std::vector<std::uint32_t> elts;
-            std::vector<const sealhip_kswitch_key *> raw;
-            dft_keys(galois_keys, elts, raw);
-            const std::size_t k = encrypted.coeff_modulus_size();
+            const KeyLists keys = key_lists(galois_keys);
+            const std::uint32_t k = std::uint32_t(encrypted.coeff_modulus_size()), n_keys = std::uint32_t(keys.elts.size());
             to_size2(encrypted, 2, boot.out_level(), destination, nullptr, [&](const std::uint64_t *c, std::uint64_t *o) {
                 if (to_sparse)
-                    return sealhip_evaluator_bootstrap_encapsulated(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(),
-                                                                    raw.data(), std::uint32_t(elts.size()), &relin, 1, to_sparse,
-                                                                    to_dense, o);
-                return sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), std::uint32_t(k), c, 1, elts.data(), raw.data(),
-                                                   std::uint32_t(elts.size()), &relin, 1, o);
+                    return sealhip_evaluator_bootstrap_encapsulated(ctx_.get(), boot.get(), k, c, 1, keys.elts.data(),
+                                                                    keys.raw.data(), n_keys, &relin, 1, to_sparse, to_dense, o);
+                return sealhip_evaluator_bootstrap(ctx_.get(), boot.get(), k, c, 1, keys.elts.data(), keys.raw.data(), n_keys,
+                                                   &relin, 1, o);
             });
         }
 
@@ -2576,17 +1618,18 @@ namespace sealhip_host
         }
 
         // the n results of a hoisted rotation, back to back in `o`, become the destinations (metadata of the operand)
-        // (k: the level of the results when it is not the operand's -- the *_rescale methods)
-        void scatter(const CT &src, Dev &o, std::size_t n, std::size_t words, std::vector<CT> &dst, std::size_t k = 0)
+        // (k: the level of the results when it is not the operand's -- the *_rescale methods; size: their polynomials)
+        void scatter(const CT &src, Dev &o, std::size_t n, std::size_t words, std::vector<CT> &dst, std::size_t k = 0,
+                     std::size_t size = 2)
         {
             dst.assign(n, src);
             for (std::size_t i = 0; k && i < n; i++)
-                dst[i].resize_raw(2, k);
+                dst[i].resize_raw(size, k);
             for (std::size_t i = 0; i < n; i++)
                 throw_on(sealhip_memcpy_d2h(ctx_.get(), dst[i].data(), o.ptr() + i * words, words * 8));
         }
         void scatter(const DeviceCiphertext &src, Dev &o, std::size_t n, std::size_t words, std::vector<DeviceCiphertext> &dst,
-                     std::size_t k = 0)
+                     std::size_t k = 0, std::size_t size = 2)
         {
             k = k ? k : src.coeff_modulus_size();
             std::vector<DeviceCiphertext> next;
@@ -2594,42 +1637,35 @@ namespace sealhip_host
             for (std::size_t i = 0; i < n; i++)
             {
                 next.emplace_back(ctx_);
-                if (n == 1)
-                    next[i].adopt(o.st->release(), o.st->words(), 2, k);
-                else
-                {
-                    Staged one(ctx_, words); // (each destination owns a pool block of its own)
-                    throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), o.ptr() + i * words, words * 8));
-                    next[i].adopt(one.release(), words, 2, k);
-                }
+                next[i].adopt_result(*o.st, i, n, words, size, k);
                 next[i].copy_meta(src);
             }
             dst.swap(next);
         }
-        // the plaintexts of apply_galois_dot_plain: a DevicePlaintext, or a host plaintext of HostPlaintext's shape
-        static const std::uint64_t *plain_data(const DevicePlaintext &p) { return p.data(); }
-        static std::size_t plain_words(const DevicePlaintext &p) { return p.words(); }
-        static std::size_t plain_k(const DevicePlaintext &p) { return p.coeff_modulus_size(); }
-        static bool plain_ntt(const DevicePlaintext &p) { return p.is_ntt_form(); }
-        static double plain_scale(const DevicePlaintext &p) { return p.scale(); }
-        template <class P>
-        static const std::uint64_t *plain_data(const P &p) { return p.words.data(); }
-        template <class P>
-        static std::size_t plain_words(const P &p) { return p.words.size(); }
-        template <class P>
-        static std::size_t plain_k(const P &p) { return p.k; }
-        template <class P>
-        static bool plain_ntt(const P &p) { return p.ntt_form; }
-        template <class P>
-        static double plain_scale(const P &p) { return p.scale; }
-        void plain_to(const DevicePlaintext &p, std::uint64_t *dst, std::size_t words)
+
+        // ---- plaintext operands
+        // A plaintext of apply_galois_dot_plain / dot_plain as the checks and the staging read it: a DevicePlaintext, or a host
+        // plaintext of HostPlaintext's shape (words, k, ntt_form, scale)
+        struct PlainView
         {
-            throw_on(sealhip_memcpy_d2d(ctx_.get(), dst, p.data(), words * 8));
+            const std::uint64_t *data;
+            std::size_t words, k;
+            bool ntt_form;
+            double scale;
+            bool on_device;
+        };
+        static PlainView plain_view(const DevicePlaintext &p)
+        {
+            return { p.data(), p.words(), p.coeff_modulus_size(), p.is_ntt_form(), p.scale(), true };
         }
         template <class P>
-        void plain_to(const P &p, std::uint64_t *dst, std::size_t words)
+        static PlainView plain_view(const P &p)
         {
-            throw_on(sealhip_memcpy_h2d(ctx_.get(), dst, p.words.data(), words * 8));
+            return { p.words.data(), p.words.size(), p.k, p.ntt_form, p.scale, false };
+        }
+        void plain_to(const PlainView &p, std::uint64_t *dst, std::size_t words)
+        {
+            throw_on((p.on_device ? sealhip_memcpy_d2d : sealhip_memcpy_h2d)(ctx_.get(), dst, p.data, words * 8));
         }
         // every plains[s] has n_elts plaintexts in key-level NTT form; returns their common scale (CKKS; 1.0 if none)
         template <class P>
@@ -2642,14 +1678,15 @@ namespace sealhip_host
             {
                 if (row.size() != n_elts)
                     throw std::invalid_argument("plains must hold one plaintext per Galois element in every sum");
-                for (const P &p : row)
+                for (const P &plain : row)
                 {
-                    if (!plain_ntt(p) || plain_k(p) != n_key || plain_words(p) != n_key * n)
+                    const PlainView p = plain_view(plain);
+                    if (!p.ntt_form || p.k != n_key || p.words != n_key * n)
                         throw std::invalid_argument("plain must be in NTT form at the key level");
-                    if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && !first && plain_scale(p) != scale)
+                    if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && !first && p.scale != scale)
                         throw std::invalid_argument("scale mismatch");
                     if (first)
-                        scale = plain_scale(p);
+                        scale = p.scale;
                     first = false;
                 }
             }
@@ -2663,29 +1700,62 @@ namespace sealhip_host
                     throw_on(sealhip_galois_elt_from_step(ctx_.get(), steps[i], &elts[i]));
             return elts;
         }
-        // apply_galois_inplace's checks on the operand (evaluator.cpp:1848-1887)
-        template <class C>
-        void check_galois_operand(const C &encrypted) const
-        {
-            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            if (bfv && encrypted.is_ntt_form())
-                throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-            if (!bfv && !encrypted.is_ntt_form())
-                throw std::invalid_argument("CKKS encrypted must be in NTT form");
-            if (encrypted.size() != 2)
-                throw std::invalid_argument("encrypted size must be 2"); // :1884-1887
-        }
 
-        // what every *_rescale method adds to the unmerged method's checks (DESIGN.md section 19)
-        template <class C>
-        void check_rescale_operand(const C &encrypted) const
+        // ---- the methods behind several public names
+        template <class C, class P>
+        void dot_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &galois_elts, const GaloisKeyMap &galois_keys,
+                                const std::vector<std::vector<P>> &plains, std::vector<C> &destinations, bool rescale)
         {
-            if (ctx_.scheme() != SEALHIP_SCHEME_CKKS)
-                throw std::logic_error("unsupported scheme"); // (rescale_to_next: evaluator.cpp:1098-1101)
-            if (!encrypted.is_ntt_form())
-                throw std::invalid_argument("CKKS encrypted must be in NTT form");
-            if (encrypted.coeff_modulus_size() < 2)
-                throw std::invalid_argument("end of modulus switching chain reached"); // :1005-1008
+            check_galois_operand(encrypted);
+            if (rescale)
+                check_rescale_operand(encrypted);
+            const std::vector<const sealhip_kswitch_key *> raw = keys_of(galois_elts, galois_keys, true);
+            const std::size_t n_elts = galois_elts.size(), n_sums = plains.size();
+            const double scale = check_dot_plains(plains, n_elts);
+            const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), words = 2 * k * n, pw = ctx_.n_key() * n;
+            const std::size_t k_out = rescale ? k - 1 : k, out_words = 2 * k_out * n;
+            Dev c = dev_in(encrypted, words), o = dev_out((n_sums ? n_sums : 1) * out_words);
+            Staged w(ctx_, n_sums * n_elts ? n_sums * n_elts * pw : 1);
+            for (std::size_t s = 0; s < n_sums; s++)
+                for (std::size_t i = 0; i < n_elts; i++)
+                    plain_to(plain_view(plains[s][i]), w.ptr() + (s * n_elts + i) * pw, pw);
+            Check chk = checked(encrypted, n_sums ? n_sums : 1);
+            throw_on((rescale ? sealhip_evaluator_apply_galois_dot_plain_rescale : sealhip_evaluator_apply_galois_dot_plain)(
+                ctx_.get(), std::uint32_t(k), c.ptr(), 1, galois_elts.data(), raw.data(), std::uint32_t(n_elts), w.ptr(),
+                std::uint32_t(n_sums), o.ptr()));
+            chk.done();
+            scatter(encrypted, o, n_sums, out_words, destinations, k_out);
+            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS)
+                for (C &d : destinations)
+                    d.scale() = encrypted.scale() * scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
+        }
+        template <class C, class P>
+        void bsgs_plain_internal(const C &encrypted, const std::vector<std::uint32_t> &baby_elts,
+                                 const std::vector<std::uint32_t> &giant_elts, const GaloisKeyMap &galois_keys,
+                                 const std::vector<std::vector<P>> &plains, C &destination, bool rescale)
+        {
+            check_galois_operand(encrypted);
+            if (rescale)
+                check_rescale_operand(encrypted);
+            const std::vector<const sealhip_kswitch_key *> bk = keys_of(baby_elts, galois_keys, true),
+                                                           gk = keys_of(giant_elts, galois_keys, true);
+            const std::size_t n_baby = baby_elts.size(), n_giant = giant_elts.size();
+            if (plains.size() != n_giant)
+                throw std::invalid_argument("plains must hold one row of plaintexts per giant element");
+            const double plain_scale = check_dot_plains(plains, n_baby);
+            const std::size_t k = encrypted.coeff_modulus_size(), pw = ctx_.n_key() * ctx_.n();
+            Staged w(ctx_, (n_giant && n_baby) ? n_giant * n_baby * pw : 1);
+            for (std::size_t j = 0; j < n_giant; j++)
+                for (std::size_t i = 0; i < n_baby; i++)
+                    plain_to(plain_view(plains[j][i]), w.ptr() + (j * n_baby + i) * pw, pw);
+            const bool ckks = ctx_.scheme() == SEALHIP_SCHEME_CKKS;
+            const double scale = encrypted.scale() * plain_scale / (rescale ? double(ctx_.key_modulus(k - 1)) : 1.0);
+            to_size2(encrypted, 2, rescale ? k - 1 : k, destination, ckks ? &scale : nullptr,
+                     [&](const std::uint64_t *c, std::uint64_t *o) {
+                         return (rescale ? sealhip_evaluator_apply_galois_bsgs_plain_rescale : sealhip_evaluator_apply_galois_bsgs_plain)(
+                             ctx_.get(), std::uint32_t(k), c, 1, baby_elts.data(), bk.data(), std::uint32_t(n_baby),
+                             giant_elts.data(), gk.data(), std::uint32_t(n_giant), w.ptr(), o);
+                     });
         }
 
         template <class C>
@@ -2741,10 +1811,7 @@ namespace sealhip_host
             const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
             for (const C &c : terms)
             {
-                if (bfv && c.is_ntt_form())
-                    throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-                if (!bfv && !c.is_ntt_form())
-                    throw std::invalid_argument("CKKS encrypted must be in NTT form");
+                check_form(c);
                 if (c.size() < 2 || c.size() != terms[0].size())
                     throw std::invalid_argument("terms must have one size of at least 2");
                 if (c.coeff_modulus_size() != terms[0].coeff_modulus_size() || c.poly_modulus_degree() != ctx_.n())
@@ -2798,18 +1865,13 @@ namespace sealhip_host
         {
             std::uint32_t elt = 0;
             throw_on(sealhip_galois_elt_from_step(ctx_.get(), 0, &elt));
-            auto it = galois_keys.find(elt);
-            if (it == galois_keys.end() || !it->second)
-                throw std::invalid_argument("Galois key not present"); // evaluator.cpp:1871-1874
-            apply_galois_inplace(encrypted, elt, *it->second);
+            keys_of({ elt }, galois_keys, false); // (refuses an absent key: evaluator.cpp:1871-1874)
+            apply_galois_inplace(encrypted, elt, *galois_keys.at(elt));
         }
         template <class C, class P>
         void plain_linear(C &encrypted, const P &plain, bool plain_is_ntt_form, bool sub)
         {
-            if (ctx_.scheme() == SEALHIP_SCHEME_BFV && encrypted.is_ntt_form())
-                throw std::invalid_argument("BFV encrypted cannot be in NTT form"); // :1304-1307
-            if (ctx_.scheme() == SEALHIP_SCHEME_CKKS && !encrypted.is_ntt_form())
-                throw std::invalid_argument("CKKS encrypted must be in NTT form"); // :1308-1311
+            check_form(encrypted); // :1304-1311
             if (encrypted.is_ntt_form() != plain_is_ntt_form)
                 throw std::invalid_argument("NTT form mismatch"); // :1312-1315
             const std::size_t k = encrypted.coeff_modulus_size(), n = ctx_.n(), size = encrypted.size();
@@ -2893,823 +1955,5 @@ namespace sealhip_host
             dev_back(ct, c, size * k * n);
         }
         const Context &ctx_;
-    };
-
-    // Decryptor (decryptor.h / decryptor.cpp) over a context and the secret key in NTT form (n_key x N words, host). The powers
-    // s^1..s^m live on the device and grow on demand, as compute_secret_key_array does (:152-216), by dyadic products on the
-    // device. A plaintext is a vector of words: BFV, the coefficients mod t trimmed like bfv_decrypt (:112-116); CKKS, the
-    // k x N words in NTT form. The batch overloads decrypt runs of ciphertexts of equal level and size with one call each.
-    template <class CT>
-    class Decryptor
-    {
-    public:
-        Decryptor(const Context &context, const std::uint64_t *secret_key_ntt)
-            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n())
-        {}
-
-        // decrypt (:51-75). The DeviceCiphertext overloads read the resident words in place (no upload) and are a
-        // host-visible point of the Evaluator's deferred transparency check.
-        void decrypt(const CT &encrypted, std::vector<std::uint64_t> &destination)
-        {
-            std::vector<std::vector<std::uint64_t>> out;
-            decrypt(std::vector<const CT *>{ &encrypted }, out);
-            destination.swap(out[0]);
-        }
-        void decrypt(const std::vector<const CT *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
-        {
-            decrypt_impl(encrypted, destination);
-        }
-        void decrypt(const DeviceCiphertext &encrypted, std::vector<std::uint64_t> &destination)
-        {
-            std::vector<std::vector<std::uint64_t>> out;
-            decrypt_impl(std::vector<const DeviceCiphertext *>{ &encrypted }, out);
-            destination.swap(out[0]);
-        }
-        void decrypt(const std::vector<const DeviceCiphertext *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
-        {
-            decrypt_impl(encrypted, destination);
-        }
-
-        // invariant_noise_budget (:269-325)
-        int invariant_noise_budget(const CT &encrypted)
-        {
-            return invariant_noise_budget(std::vector<const CT *>{ &encrypted })[0];
-        }
-        std::vector<int> invariant_noise_budget(const std::vector<const CT *> &encrypted) { return budget_impl(encrypted); }
-        int invariant_noise_budget(const DeviceCiphertext &encrypted)
-        {
-            return budget_impl(std::vector<const DeviceCiphertext *>{ &encrypted })[0];
-        }
-        std::vector<int> invariant_noise_budget(const std::vector<const DeviceCiphertext *> &encrypted)
-        {
-            return budget_impl(encrypted);
-        }
-
-    private:
-        template <class C>
-        void decrypt_impl(const std::vector<const C *> &encrypted, std::vector<std::vector<std::uint64_t>> &destination)
-        {
-            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            for (const C *ct : encrypted)
-            {
-                check_valid(*ct);
-                if (bfv && ct->is_ntt_form())
-                    throw std::invalid_argument("encrypted cannot be in NTT form"); // :79-82
-                if (!bfv && !ct->is_ntt_form())
-                    throw std::invalid_argument("encrypted must be in NTT form"); // :124-127
-            }
-            destination.assign(encrypted.size(), {});
-            for_runs(encrypted, [&](std::size_t first, std::size_t count, std::size_t k, std::size_t size, const std::uint64_t *c,
-                                    const std::uint64_t *powers) {
-                const std::size_t n = ctx_.n(), words = bfv ? n : k * n;
-                Staged o(ctx_, count * words);
-                throw_on(sealhip_decryptor_decrypt(ctx_.get(), std::uint32_t(k), c, std::uint32_t(size), count, powers,
-                                                   bfv ? 0 : 1, o.ptr()));
-                std::vector<std::uint64_t> all(count * words);
-                o.down(all.data(), all.size());
-                for (std::size_t i = 0; i < count; i++)
-                {
-                    const std::uint64_t *p = all.data() + i * words;
-                    std::size_t keep = words;
-                    if (bfv) // get_significant_uint64_count_uint, at least one coefficient (:112-116)
-                    {
-                        while (keep > 1 && p[keep - 1] == 0)
-                            keep--;
-                    }
-                    destination[first + i].assign(p, p + keep);
-                }
-            });
-        }
-
-        template <class C>
-        std::vector<int> budget_impl(const std::vector<const C *> &encrypted)
-        {
-            for (const C *ct : encrypted)
-            {
-                check_valid(*ct);
-                if (ctx_.scheme() != SEALHIP_SCHEME_BFV)
-                    throw std::logic_error("unsupported scheme"); // :276-279
-                if (ct->is_ntt_form())
-                    throw std::invalid_argument("encrypted cannot be in NTT form"); // :280-283
-            }
-            std::vector<int> out(encrypted.size(), 0);
-            for_runs(encrypted, [&](std::size_t first, std::size_t count, std::size_t k, std::size_t size, const std::uint64_t *c,
-                                    const std::uint64_t *powers) {
-                std::vector<std::int32_t> b(count);
-                throw_on(sealhip_decryptor_invariant_noise_budget(ctx_.get(), std::uint32_t(k), c, std::uint32_t(size), count,
-                                                                  powers, b.data()));
-                std::copy(b.begin(), b.end(), out.begin() + static_cast<std::ptrdiff_t>(first));
-            });
-            return out;
-        }
-
-        // is_valid_for (valcheck.cpp), the metadata the ABI cannot see
-        template <class C>
-        void check_valid(const C &ct) const
-        {
-            if (ct.size() < 2 || ct.size() > 16 || ct.coeff_modulus_size() < 1 || ct.coeff_modulus_size() > ctx_.n_key() ||
-                ct.poly_modulus_degree() != ctx_.n())
-                throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        }
-
-        // compute_secret_key_array (:152-216): s^1..s^max_power on the device, kept, and rebuilt longer on demand
-        const std::uint64_t *powers(std::size_t max_power)
-        {
-            if (max_power <= n_powers_)
-                return powers_->ptr();
-            const std::size_t poly = ctx_.n_key() * ctx_.n();
-            std::uint32_t k_first = 0; // the key base of the first data level: all n_key key primes
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            auto next = std::make_unique<Staged>(ctx_, max_power * poly);
-            next->up(sk_.data(), poly);
-            for (std::size_t i = 1; i < max_power; i++)
-                throw_on(sealhip_dyadic_product_coeffmod(ctx_.get(), next->ptr() + (i - 1) * poly, next->ptr(), 1, k_first,
-                                                         SEALHIP_BASE_KEY, next->ptr() + i * poly));
-            powers_ = std::move(next);
-            n_powers_ = max_power;
-            return powers_->ptr();
-        }
-
-        // resident ciphertexts: each is its own run, read in place
-        template <class F>
-        void for_runs(const std::vector<const DeviceCiphertext *> &encrypted, F &&body)
-        {
-            ctx_.check_transparency();
-            for (std::size_t i = 0; i < encrypted.size(); i++)
-            {
-                const DeviceCiphertext &c = *encrypted[i];
-                const std::uint64_t *pw = powers(c.size() - 1);
-                body(i, 1, c.coeff_modulus_size(), c.size(), c.data(), pw);
-            }
-        }
-        // calls body(first, count, k, size, device ciphertexts, device powers) for each run of equal level and size
-        template <class F>
-        void for_runs(const std::vector<const CT *> &encrypted, F &&body)
-        {
-            for (std::size_t first = 0; first < encrypted.size();)
-            {
-                const std::size_t k = encrypted[first]->coeff_modulus_size(), size = encrypted[first]->size();
-                std::size_t end = first + 1;
-                while (end < encrypted.size() && encrypted[end]->coeff_modulus_size() == k && encrypted[end]->size() == size)
-                    end++;
-                const std::size_t words = size * k * ctx_.n(), count = end - first;
-                const std::uint64_t *pw = powers(size - 1);
-                Staged c(ctx_, count * words);
-                for (std::size_t i = 0; i < count; i++)
-                    throw_on(sealhip_memcpy_h2d(ctx_.get(), c.ptr() + i * words, encrypted[first + i]->data(), words * 8));
-                body(first, count, k, size, c.ptr(), pw);
-                first = end;
-            }
-        }
-
-        const Context &ctx_;
-        std::vector<std::uint64_t> sk_;
-        std::unique_ptr<Staged> powers_;
-        std::size_t n_powers_ = 0;
-    };
-
-    // A plaintext as Encryptor takes it: BFV, up to N coefficients < t in coefficient form (shorter is zero-padded);
-    // CKKS, the k x N words of an NTT-form plaintext at level k, with its scale.
-    struct HostPlaintext
-    {
-        std::vector<std::uint64_t> words;
-        std::size_t k = 0; // CKKS: the level (coeff_modulus_size); BFV: unused
-        bool ntt_form = false;
-        double scale = 1.0;
-    };
-
-    // Encryptor (encryptor.h / encryptor.cpp:106-259) over a context and an optional public key (2 x n_key x N host words,
-    // as KeyGenerator::public_key() returns) and an optional secret key (n_key x N, NTT form). Sampling stays with the
-    // caller: asym_sampler(u, e0, e1) is asked once per public-key encryption for the N ternary values of
-    // u and the N + N values of e_0, e_1; sym_sampler(seed, noise) once per secret-key encryption for the 8-word
-    // BlakePRNGFactory().create() seed of c_1 and the N values of e. Ciphertexts are made on the device
-    // (sealhip_encryptor_encrypt, sealhip_encryptor_encrypt_symmetric); the batch overloads make one call per run of equal
-    // level. The seeded forms return the Serializable<Ciphertext> stream (the level's parms_id must be registered with
-    // sealhip_context_set_parms_id). Built with a SeedSource instead of the samplers, it draws u and the noise on the device
-    // from seeds: the library's own streams, the reference's noise law.
-    template <class CT>
-    class Encryptor
-    {
-    public:
-        using AsymSampler = std::function<void(std::int32_t *u, std::int32_t *e0, std::int32_t *e1)>;
-        using SymSampler = std::function<void(std::uint64_t *seed, std::int32_t *noise)>;
-
-        Encryptor(const Context &context, const std::uint64_t *public_key, const std::uint64_t *secret_key_ntt,
-                  AsymSampler asym_sampler, SymSampler sym_sampler)
-            : ctx_(context), asym_(std::move(asym_sampler)), sym_(std::move(sym_sampler))
-        {
-            const std::size_t n = context.n(), nk = context.n_key();
-            if (public_key)
-                pk_.assign(public_key, public_key + 2 * nk * n);
-            if (secret_key_ntt)
-                sk_.assign(secret_key_ntt, secret_key_ntt + nk * n);
-            std::uint32_t k_first = 0;
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            k_first_ = k_first;
-        }
-        // The samples drawn on the device: a public-key encryption asks `seeds` for one seed and samples (1, 2) = u, e_0,
-        // e_1 from it; a secret-key encryption asks for two, c_1's seed and then a separate noise seed sampled as (0, 1) --
-        // c_1's seed is public in a seeded stream, the noise seed never leaves this call. The scratch that held the samples
-        // is erased before it goes back to the pool.
-        Encryptor(const Context &context, const std::uint64_t *public_key, const std::uint64_t *secret_key_ntt, SeedSource seeds)
-            : Encryptor(context, public_key, secret_key_ntt, AsymSampler(), SymSampler())
-        {
-            if (!seeds)
-                throw std::invalid_argument("seed source is empty");
-            seeds_ = std::move(seeds);
-        }
-        // where the samples of the last seed-source encryption lay on the device (pointer, bytes), for tests: the blocks
-        // are back in the pool, erased
-        const std::vector<std::pair<const void *, std::size_t>> &last_sample_scratch() const { return scratch_; }
-        void set_public_key(const std::uint64_t *public_key)
-        {
-            pk_.assign(public_key, public_key + 2 * ctx_.n_key() * ctx_.n());
-            dpk_.reset();
-        }
-        void set_secret_key(const std::uint64_t *secret_key_ntt)
-        {
-            sk_.assign(secret_key_ntt, secret_key_ntt + ctx_.n_key() * ctx_.n());
-            dsk_.reset();
-        }
-
-        // the same into resident ciphertexts: the words stay on the device (the samples still come from the samplers)
-        void encrypt(const HostPlaintext &plain, DeviceCiphertext &destination)
-        {
-            std::vector<DeviceCiphertext *> d{ &destination };
-            run(true, std::vector<const HostPlaintext *>{ &plain }, d, 0, false);
-        }
-        void encrypt_zero(DeviceCiphertext &destination) { encrypt_zero(k_first_, destination); }
-        void encrypt_zero(std::size_t k, DeviceCiphertext &destination)
-        {
-            std::vector<DeviceCiphertext *> d{ &destination };
-            run(true, {}, d, k, false);
-        }
-        void encrypt_symmetric(const HostPlaintext &plain, DeviceCiphertext &destination)
-        {
-            std::vector<DeviceCiphertext *> d{ &destination };
-            run(false, std::vector<const HostPlaintext *>{ &plain }, d, 0, false);
-        }
-        void encrypt_zero_symmetric(DeviceCiphertext &destination) { encrypt_zero_symmetric(k_first_, destination); }
-        void encrypt_zero_symmetric(std::size_t k, DeviceCiphertext &destination)
-        {
-            std::vector<DeviceCiphertext *> d{ &destination };
-            run(false, {}, d, k, false);
-        }
-
-        // encrypt (:205-253) / encrypt_zero() at the first level / encrypt_zero(parms_id) at level k
-        void encrypt(const HostPlaintext &plain, CT &destination) { encrypt(std::vector<const HostPlaintext *>{ &plain }, one(destination)); }
-        void encrypt(const std::vector<const HostPlaintext *> &plain, std::vector<CT *> destination)
-        {
-            run(true, plain, destination, 0, false);
-        }
-        void encrypt_zero(CT &destination) { encrypt_zero(k_first_, destination); }
-        void encrypt_zero(std::size_t k, CT &destination) { encrypt_zero(k, one(destination)); }
-        void encrypt_zero(std::size_t k, std::vector<CT *> destination) { run(true, {}, destination, k, false); }
-
-        // encrypt_symmetric / encrypt_zero_symmetric (rlwe.cpp:204-300)
-        void encrypt_symmetric(const HostPlaintext &plain, CT &destination)
-        {
-            encrypt_symmetric(std::vector<const HostPlaintext *>{ &plain }, one(destination));
-        }
-        void encrypt_symmetric(const std::vector<const HostPlaintext *> &plain, std::vector<CT *> destination)
-        {
-            run(false, plain, destination, 0, false);
-        }
-        void encrypt_zero_symmetric(CT &destination) { encrypt_zero_symmetric(k_first_, destination); }
-        void encrypt_zero_symmetric(std::size_t k, CT &destination) { encrypt_zero_symmetric(k, one(destination)); }
-        void encrypt_zero_symmetric(std::size_t k, std::vector<CT *> destination) { run(false, {}, destination, k, false); }
-
-        // encrypt_symmetric(plain) returning Serializable<Ciphertext> (encryptor.h:371-376): the stream of c_0 and the seed.
-        // parms_id: that of the ciphertext's level (it is written into the stream and must be registered with
-        // sealhip_context_set_parms_id); destination (optional) receives the ciphertext with c_1 expanded.
-        std::vector<unsigned char> encrypt_symmetric_seeded(const HostPlaintext &plain, const std::uint64_t parms_id[4],
-                                                            CT *destination = nullptr)
-        {
-            return seeded(&plain, k_first_, parms_id, destination);
-        }
-        std::vector<unsigned char> encrypt_zero_symmetric_seeded(std::size_t k, const std::uint64_t parms_id[4],
-                                                                 CT *destination = nullptr)
-        {
-            return seeded(nullptr, k, parms_id, destination);
-        }
-
-    private:
-        static std::vector<CT *> one(CT &c) { return std::vector<CT *>{ &c }; }
-
-        // is_metadata_valid_for / the form checks of encrypt_internal (:185-238) on the host; returns the level
-        std::size_t check_plain(const HostPlaintext &p) const
-        {
-            const std::size_t n = ctx_.n();
-            if (ctx_.scheme() == SEALHIP_SCHEME_BFV)
-            {
-                if (p.words.size() > n || std::any_of(p.words.begin(), p.words.end(),
-                                                      [&](std::uint64_t v) { return v >= ctx_.plain_modulus(); }))
-                    throw std::invalid_argument("plain is not valid for encryption parameters");
-                if (p.ntt_form)
-                    throw std::invalid_argument("plain cannot be in NTT form");
-                return k_first_;
-            }
-            if (p.k < 1 || p.k > k_first_ || p.words.size() != p.k * n)
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            if (!p.ntt_form)
-                throw std::invalid_argument("plain must be in NTT form");
-            return p.k;
-        }
-        void check_keys(bool asymmetric) const
-        {
-            if (asymmetric && pk_.empty())
-                throw std::logic_error("public key is not set");
-            if (!asymmetric && sk_.empty())
-                throw std::logic_error("secret key is not set");
-        }
-
-        // one device call per run of plaintexts of equal level (plain empty: destination.size() zero encryptions at k)
-        // the key on the device, uploaded once and kept across calls
-        const std::uint64_t *device_key(bool asymmetric)
-        {
-            const std::size_t words = (asymmetric ? 2 : 1) * ctx_.n_key() * ctx_.n();
-            std::unique_ptr<Staged> &key = asymmetric ? dpk_ : dsk_;
-            if (!key)
-            {
-                std::unique_ptr<Staged> up(new Staged(ctx_, words));
-                up->up(asymmetric ? pk_.data() : sk_.data(), words);
-                key = std::move(up);
-            }
-            return key->ptr();
-        }
-        // item i of the `count` encryptions in `ct` becomes the destination's words
-        void deliver(CT &d, Staged &ct, std::size_t i, std::size_t count, std::size_t words, std::size_t k)
-        {
-            (void)count;
-            d.resize_raw(2, k);
-            throw_on(sealhip_memcpy_d2h(ctx_.get(), d.data(), ct.ptr() + i * words, words * 8));
-        }
-        void deliver(DeviceCiphertext &d, Staged &ct, std::size_t i, std::size_t count, std::size_t words, std::size_t k)
-        {
-            if (count == 1) // the block itself changes owner
-            {
-                d.adopt(ct.release(), ct.words(), 2, k);
-                return;
-            }
-            Staged one(ctx_, words);
-            throw_on(sealhip_memcpy_d2d(ctx_.get(), one.ptr(), ct.ptr() + i * words, words * 8));
-            d.adopt(one.release(), words, 2, k);
-        }
-
-        template <class D>
-        void run(bool asymmetric, const std::vector<const HostPlaintext *> &plain, std::vector<D *> &destination,
-                 std::size_t k_zero, bool save_seed, std::vector<std::uint64_t> *seeds_out = nullptr)
-        {
-            check_keys(asymmetric);
-            const bool zero = plain.empty();
-            if (!zero && plain.size() != destination.size())
-                throw std::invalid_argument("destination count does not match");
-            if (zero && (k_zero < 1 || k_zero > ctx_.n_key()))
-                throw std::invalid_argument("parms_id is not valid for encryption parameters");
-            std::vector<std::size_t> level(destination.size(), k_zero);
-            for (std::size_t i = 0; !zero && i < plain.size(); i++)
-                level[i] = check_plain(*plain[i]);
-            const std::size_t n = ctx_.n();
-            const bool bfv = ctx_.scheme() == SEALHIP_SCHEME_BFV;
-            const std::uint64_t *key = device_key(asymmetric);
-            for (std::size_t first = 0; first < destination.size();)
-            {
-                const std::size_t k = level[first];
-                std::size_t end = first + 1;
-                while (end < destination.size() && level[end] == k)
-                    end++;
-                const std::size_t count = end - first, words = 2 * k * n;
-                const std::size_t pw = bfv ? n : k * n; // plaintext words per item
-                std::vector<std::uint64_t> host_plain(zero ? 0 : count * pw, 0);
-                for (std::size_t i = 0; !zero && i < count; i++) // BFV plaintexts shorter than N are zero-padded
-                    std::copy(plain[first + i]->words.begin(), plain[first + i]->words.end(), host_plain.begin() + i * pw);
-                std::unique_ptr<Staged> dp(zero ? nullptr : new Staged(ctx_, host_plain.size()));
-                if (dp)
-                    dp->up(host_plain.data(), host_plain.size());
-                Staged ct(ctx_, count * words);
-                if (seeds_)
-                {
-                    std::vector<std::uint64_t> seeds(count * 8), noise_seeds(asymmetric ? 0 : count * 8);
-                    for (std::size_t i = 0; i < count; i++)
-                    {
-                        if (asymmetric)
-                            seeds_(seeds.data() + 8 * i);
-                        else
-                            detail::draw_seed_pair(seeds_, seeds.data() + 8 * i, noise_seeds.data() + 8 * i);
-                    }
-                    ZeroedStaged du(ctx_, asymmetric ? (count * n + 1) / 2 : 0), de(ctx_, (count * (asymmetric ? 2 : 1) * n + 1) / 2);
-                    auto *u32 = reinterpret_cast<std::int32_t *>(du.ptr()), *e32 = reinterpret_cast<std::int32_t *>(de.ptr());
-                    scratch_.assign({ { de.ptr(), de.words() * 8 } });
-                    if (asymmetric)
-                        scratch_.push_back({ du.ptr(), du.words() * 8 });
-                    if (asymmetric)
-                    {
-                        throw_on(sealhip_sample_polys_split(ctx_.get(), seeds.data(), count, 1, 2, u32, e32));
-                        throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key, dp ? dp->ptr() : nullptr, pw, u32,
-                                                           e32, count, ct.ptr()));
-                        std::fill(seeds.begin(), seeds.end(), 0); // (u and the noise follow from them)
-                    }
-                    else
-                    {
-                        throw_on(sealhip_sample_polys(ctx_.get(), noise_seeds.data(), count, 0, 1, e32, 0));
-                        throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key,
-                                                                     dp ? dp->ptr() : nullptr, pw, seeds.data(), e32,
-                                                                     save_seed ? 1 : 0, count, ct.ptr()));
-                        std::fill(noise_seeds.begin(), noise_seeds.end(), 0);
-                        if (seeds_out) // c_1's seeds only: the noise seeds stay here
-                            seeds_out->insert(seeds_out->end(), seeds.begin(), seeds.end());
-                    }
-                }
-                else if (asymmetric)
-                {
-                    std::vector<std::int32_t> u(count * n), e(count * 2 * n);
-                    for (std::size_t i = 0; i < count; i++)
-                        asym_(u.data() + i * n, e.data() + 2 * i * n, e.data() + (2 * i + 1) * n);
-                    Staged du(ctx_, (u.size() + 1) / 2), de(ctx_, (e.size() + 1) / 2);
-                    throw_on(sealhip_memcpy_h2d(ctx_.get(), du.ptr(), u.data(), u.size() * 4));
-                    throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
-                    throw_on(sealhip_encryptor_encrypt(ctx_.get(), std::uint32_t(k), key, dp ? dp->ptr() : nullptr, pw,
-                                                       reinterpret_cast<const std::int32_t *>(du.ptr()),
-                                                       reinterpret_cast<const std::int32_t *>(de.ptr()), count, ct.ptr()));
-                }
-                else
-                {
-                    std::vector<std::uint64_t> seeds(count * 8);
-                    std::vector<std::int32_t> e(count * n);
-                    for (std::size_t i = 0; i < count; i++)
-                        sym_(seeds.data() + 8 * i, e.data() + i * n);
-                    Staged de(ctx_, (e.size() + 1) / 2);
-                    throw_on(sealhip_memcpy_h2d(ctx_.get(), de.ptr(), e.data(), e.size() * 4));
-                    throw_on(sealhip_encryptor_encrypt_symmetric(ctx_.get(), std::uint32_t(k), key,
-                                                                 dp ? dp->ptr() : nullptr, pw, seeds.data(),
-                                                                 reinterpret_cast<const std::int32_t *>(de.ptr()),
-                                                                 save_seed ? 1 : 0, count, ct.ptr()));
-                    if (seeds_out)
-                        seeds_out->insert(seeds_out->end(), seeds.begin(), seeds.end());
-                }
-                for (std::size_t i = 0; i < count; i++)
-                {
-                    D &d = *destination[first + i];
-                    deliver(d, ct, i, count, words, k);
-                    d.is_ntt_form() = !bfv;
-                    // encrypt_zero_* set 1.0; CKKS encrypt takes the plaintext's scale (:252)
-                    d.scale() = (!zero && !bfv) ? plain[first + i]->scale : 1.0;
-                }
-                first = end;
-            }
-        }
-
-        std::vector<unsigned char> seeded(const HostPlaintext *plain, std::size_t k, const std::uint64_t *pid, CT *destination)
-        {
-            CT local{};
-            CT &d = destination ? *destination : local;
-            if (!destination)
-                prepare(local);
-            std::vector<CT *> dst{ &d };
-            std::vector<std::uint64_t> seed;
-            if (plain)
-                run(false, std::vector<const HostPlaintext *>{ plain }, dst, 0, true, &seed);
-            else
-                run(false, {}, dst, k, true, &seed);
-            const std::size_t kk = d.coeff_modulus_size(), n = ctx_.n();
-            if (kk * n < 9) // rlwe.cpp:225-230: the reference drops save_seed and saves both polynomials
-                throw std::logic_error("polynomial is too small to store a seed");
-            sealhip_ciphertext_info info{};
-            std::copy(pid, pid + 4, info.parms_id);
-            info.is_ntt_form = d.is_ntt_form() ? 1 : 0;
-            info.size = 2;
-            info.coeff_modulus_size = std::uint32_t(kk);
-            info.poly_modulus_degree = n;
-            info.scale = d.scale();
-            Staged c(ctx_, 2 * kk * n);
-            c.up(d.data(), 2 * kk * n);
-            std::size_t need = 0;
-            throw_on(sealhip_ciphertext_save_seeded(ctx_.get(), &info, c.ptr(), seed.data(), nullptr, 0, &need));
-            std::vector<unsigned char> bytes(need);
-            std::size_t written = 0;
-            throw_on(sealhip_ciphertext_save_seeded(ctx_.get(), &info, c.ptr(), seed.data(), bytes.data(), need, &written));
-            bytes.resize(written);
-            return bytes;
-        }
-        template <class C = CT>
-        auto prepare(C &c) -> decltype(c.n_ = 0, void()) { c.n_ = ctx_.n(); }
-        void prepare(...) {}
-
-        const Context &ctx_;
-        std::vector<std::uint64_t> pk_, sk_;
-        std::unique_ptr<Staged> dpk_, dsk_; // the keys on the device (device_key)
-        AsymSampler asym_;
-        SymSampler sym_;
-        SeedSource seeds_; // set: the samples are drawn on the device
-        std::vector<std::pair<const void *, std::size_t>> scratch_;
-        std::size_t k_first_ = 0;
-    };
-
-    // KeyGenerator (keygenerator.h / keygenerator.cpp:105-240) over a context and a secret key in NTT form (n_key x N words,
-    // host). Sampling stays with the caller: `sampler(seed, noise)` is asked once per encrypt_zero_symmetric, in the
-    // reference's order (key by key, digit by digit), for the 8-word BlakePRNGFactory().create() seed of c_1 and the N
-    // signed values of sample_poly_normal. The keys are made on the device (sealhip_generate_*_keys).
-    // Built with a SeedSource instead of the sampler, it draws the noise on the device from seeds.
-    class KeyGenerator
-    {
-    public:
-        using Sampler = std::function<void(std::uint64_t *seed, std::int32_t *noise)>;
-        using Keys = std::vector<std::unique_ptr<KSwitchKeys>>;
-        using GaloisKeys = std::map<std::uint32_t, std::unique_ptr<KSwitchKeys>>; // galois_elt -> key (GaloisKeys::get_index)
-
-        KeyGenerator(const Context &context, const std::uint64_t *secret_key_ntt, Sampler sampler)
-            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n()), sampler_(std::move(sampler))
-        {}
-        // The noise drawn on the device: every encrypt_zero_symmetric (a key digit, the public key) asks `seeds` for two
-        // seeds, c_1's and then a separate noise seed sampled as (0, 1). save_seed keeps c_1's seeds only.
-        KeyGenerator(const Context &context, const std::uint64_t *secret_key_ntt, SeedSource seeds)
-            : ctx_(context), sk_(secret_key_ntt, secret_key_ntt + context.n_key() * context.n()), seeds_(std::move(seeds))
-        {
-            if (!seeds_)
-                throw std::invalid_argument("seed source is empty");
-        }
-
-        // generate_sk (keygenerator.cpp:66-103) on the device from one seed of `seeds` (sealhip_generate_secret_key): the
-        // n_key x N words of the secret key in NTT form
-        static std::vector<std::uint64_t> generate_secret_key(const Context &context, const SeedSource &seeds)
-        {
-            return secret_key(context, seeds, 0);
-        }
-        // the same with the fixed-weight polynomial of Hamming weight h, 1 .. N, in place of the ternary one
-        // (sealhip_generate_sparse_secret_key)
-        static std::vector<std::uint64_t> generate_sparse_secret_key(const Context &context, const SeedSource &seeds, std::uint32_t h)
-        {
-            if (h < 1 || h > context.n())
-                throw std::invalid_argument("h must be 1 .. N");
-            return secret_key(context, seeds, h);
-        }
-
-        // Key-switch keys from OTHER secrets to this generator's (sealhip_generate_switching_keys): keys[i] switches what is
-        // encrypted under from_secret_keys_ntt[i] (count x n_key x N words, NTT form) to the secret key this generator was
-        // built with. level 0 or n_ct: the full key; a smaller level: a key for key switches at levels <= level only, which
-        // publishes nothing above it and cannot keep its seeds (encapsulation's dense -> sparse key takes level 1). Samples
-        // are drawn as for relin_keys, key by key, digit by digit.
-        Keys switching_keys(const std::uint64_t *from_secret_keys_ntt, std::size_t count, std::size_t level = 0,
-                            bool save_seed = false)
-        {
-            if (!count || count > 14)
-                throw std::invalid_argument("invalid count");
-            if (!from_secret_keys_ntt)
-                throw std::invalid_argument("from_secret_keys_ntt is null");
-            std::uint32_t k_first = 0;
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            if (level > k_first)
-                throw std::invalid_argument("level k out of range");
-            return generate(nullptr, count, save_seed, from_secret_keys_ntt, level ? level : k_first);
-        }
-
-        // RGSW encryptions of small polynomials under this generator's secret key (sealhip_generate_rgsw, DESIGN.md section
-        // 29): messages[i] holds the N signed coefficients of m_i. level as switching_keys. Samples are drawn as for
-        // relin_keys: message by message, K_b's digits before K_a's.
-        std::vector<std::unique_ptr<RgswCiphertext>> rgsw(const std::vector<std::vector<std::int32_t>> &messages, std::size_t level = 0)
-        {
-            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), count = messages.size();
-            if (!count)
-                throw std::invalid_argument("invalid count");
-            for (const auto &m : messages)
-                if (m.size() != n)
-                    throw std::invalid_argument("an rgsw message has N coefficients");
-            std::uint32_t k_first = 0, digits = 0;
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            if (level > k_first)
-                throw std::invalid_argument("level k out of range");
-            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
-            const std::size_t items = count * 2 * digits;
-            std::vector<std::uint64_t> seeds(items * 8);
-            Drawn drawn = draw(seeds.data(), items);
-            Staged sk(ctx_, nk * n);
-            ZeroedStaged e(ctx_, (items * n + 1) / 2), mm(ctx_, (count * n + 1) / 2);
-            sk.up(sk_.data(), nk * n);
-            to_device(drawn, items, e);
-            for (std::size_t i = 0; i < count; i++)
-                throw_on(sealhip_memcpy_h2d(ctx_.get(), reinterpret_cast<std::int32_t *>(mm.ptr()) + i * n, messages[i].data(),
-                                            n * sizeof(std::int32_t)));
-            std::vector<sealhip_rgsw *> raw(count, nullptr);
-            throw_on(sealhip_generate_rgsw(ctx_.get(), sk.ptr(), reinterpret_cast<const std::int32_t *>(mm.ptr()), std::uint32_t(count),
-                                           std::uint32_t(level ? level : k_first), seeds.data(),
-                                           reinterpret_cast<const std::int32_t *>(e.ptr()), raw.data()));
-            std::vector<std::unique_ptr<RgswCiphertext>> out;
-            for (auto *h : raw)
-                out.push_back(std::make_unique<RgswCiphertext>(ctx_, h));
-            return out;
-        }
-
-        // The keys of a blind rotation under this generator's secret key (sealhip_generate_blind_rotation_keys, DESIGN.md
-        // section 30) for an LWE secret with coefficients in {-1, 0, 1} (binary: {0, 1}): n_steps = lwe_secret.size(), or twice
-        // that with `ternary`. level as switching_keys. Samples are drawn as for rgsw: step by step, K_b's digits before
-        // K_a's. The staged secret is erased in stream order.
-        std::unique_ptr<BlindRotationKeys> blind_rotation_keys(const std::vector<std::int32_t> &lwe_secret, bool ternary,
-                                                               std::size_t level = 0)
-        {
-            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), n_lwe = lwe_secret.size(), count = n_lwe * (ternary ? 2 : 1);
-            if (!n_lwe)
-                throw std::invalid_argument("invalid count");
-            for (std::int32_t s : lwe_secret)
-                if (s > 1 || s < (ternary ? -1 : 0))
-                    throw std::invalid_argument("an LWE secret has coefficients in {-1, 0, 1} (binary: {0, 1})");
-            std::uint32_t k_first = 0, digits = 0;
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            if (level > k_first)
-                throw std::invalid_argument("level k out of range");
-            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
-            const std::size_t items = count * 2 * digits;
-            std::vector<std::uint64_t> seeds(items * 8);
-            Drawn drawn = draw(seeds.data(), items);
-            Staged sk(ctx_, nk * n);
-            ZeroedStaged e(ctx_, (items * n + 1) / 2), ss(ctx_, (n_lwe + 1) / 2);
-            sk.up(sk_.data(), nk * n);
-            to_device(drawn, items, e);
-            throw_on(sealhip_memcpy_h2d(ctx_.get(), ss.ptr(), lwe_secret.data(), n_lwe * sizeof(std::int32_t)));
-            std::vector<sealhip_rgsw *> raw(count, nullptr);
-            throw_on(sealhip_generate_blind_rotation_keys(ctx_.get(), sk.ptr(), reinterpret_cast<const std::int32_t *>(ss.ptr()),
-                                                          std::uint32_t(n_lwe), ternary ? 1 : 0, std::uint32_t(level ? level : k_first),
-                                                          seeds.data(), reinterpret_cast<const std::int32_t *>(e.ptr()), raw.data()));
-            std::vector<std::unique_ptr<RgswCiphertext>> made;
-            for (auto *h : raw)
-                made.push_back(std::make_unique<RgswCiphertext>(ctx_, h));
-            return std::make_unique<BlindRotationKeys>(std::move(made), ternary);
-        }
-
-    private:
-        // h = 0: the ternary polynomial
-        static std::vector<std::uint64_t> secret_key(const Context &context, const SeedSource &seeds, std::uint32_t h)
-        {
-            std::uint64_t seed[8];
-            seeds(seed);
-            const std::size_t words = context.n_key() * context.n();
-            ZeroedStaged sk(context, words);
-            throw_on(h ? sealhip_generate_sparse_secret_key(context.get(), seed, h, sk.ptr())
-                       : sealhip_generate_secret_key(context.get(), seed, sk.ptr()));
-            std::fill(seed, seed + 8, 0);
-            std::vector<std::uint64_t> out(words);
-            sk.down(out.data(), words);
-            return out;
-        }
-
-    public:
-        // relin_keys(count, save_seed) (:146-175): keys[i] is the key of sk^(i+2) (RelinKeys::get_index(i + 2) = i)
-        Keys relin_keys(std::size_t count, bool save_seed = false)
-        {
-            if (!count || count > 14) // SEAL_CIPHERTEXT_SIZE_MAX - 2
-                throw std::invalid_argument("invalid count");
-            return generate(nullptr, count, save_seed);
-        }
-
-        // galois_keys(galois_elts, save_seed) (:177-240): invalid elements throw before any sample is drawn; an element that
-        // is already present is skipped and draws no samples (has_key)
-        GaloisKeys galois_keys(const std::vector<std::uint32_t> &galois_elts, bool save_seed = false)
-        {
-            std::int32_t batching = 0;
-            throw_on(sealhip_context_using_batching(ctx_.get(), &batching));
-            if (!batching && ctx_.scheme() == SEALHIP_SCHEME_BFV)
-                throw std::logic_error("encryption parameters do not support batching");
-            std::vector<std::uint32_t> elts;
-            for (std::uint32_t elt : galois_elts)
-            {
-                if (!(elt & 1) || elt >= 2 * ctx_.n())
-                    throw std::invalid_argument("Galois element is not valid");
-                if (std::find(elts.begin(), elts.end(), elt) == elts.end())
-                    elts.push_back(elt);
-            }
-            Keys made = generate(elts.data(), elts.size(), save_seed);
-            GaloisKeys out;
-            for (std::size_t i = 0; i < elts.size(); i++)
-                out.emplace(elts[i], std::move(made[i]));
-            return out;
-        }
-        // galois_keys(steps) (keygenerator.h:180-208): GaloisTool::get_elts_from_steps
-        GaloisKeys galois_keys(const std::vector<int> &steps, bool save_seed = false)
-        {
-            std::vector<std::uint32_t> elts;
-            for (int step : steps)
-            {
-                std::uint32_t elt = 0;
-                throw_on(sealhip_galois_elt_from_step(ctx_.get(), step, &elt));
-                elts.push_back(elt);
-            }
-            return galois_keys(elts, save_seed);
-        }
-        // galois_keys() (keygenerator.h:224-247): GaloisTool::get_elts_all (galois.cpp:102-127), in its order
-        GaloisKeys galois_keys(bool save_seed = false) { return galois_keys(elts_all(), save_seed); }
-
-        // generate_pk (keygenerator.cpp:105-136): encrypt_zero_symmetric at the key level in NTT form, no seed kept; returns
-        // the 2 x n_key x N words of the public key
-        std::vector<std::uint64_t> public_key()
-        {
-            const std::size_t n = ctx_.n(), nk = ctx_.n_key();
-            std::uint64_t seed[8];
-            Drawn drawn = draw(seed, 1);
-            Staged sk(ctx_, nk * n), a(ctx_, nk * n), ct(ctx_, 2 * nk * n);
-            ZeroedStaged e(ctx_, (n + 1) / 2);
-            sk.up(sk_.data(), nk * n);
-            to_device(drawn, 1, e);
-            throw_on(sealhip_expand_seed(ctx_.get(), std::uint32_t(nk), seed, 1, a.ptr(), 0));
-            throw_on(sealhip_encrypt_zero_symmetric(ctx_.get(), std::uint32_t(nk), 1, a.ptr(),
-                                                    reinterpret_cast<const std::int32_t *>(e.ptr()), sk.ptr(), 1, ct.ptr()));
-            std::vector<std::uint64_t> pk(2 * nk * n);
-            ct.down(pk.data(), pk.size());
-            return pk;
-        }
-
-        std::vector<std::uint32_t> elts_all() const
-        {
-            const std::uint64_t m = 2 * static_cast<std::uint64_t>(ctx_.n());
-            std::uint64_t pos = 5, neg = 1; // neg = 5^-1 mod m = 5^(N/2 - 1): the order of 5 is N/2
-            for (std::size_t i = 0; i + 1 < ctx_.n() / 2; i++)
-                neg = (neg * 5) & (m - 1);
-            std::vector<std::uint32_t> out{ static_cast<std::uint32_t>(m - 1) };
-            for (std::size_t i = 0; (std::size_t(2) << i) < ctx_.n(); i++) // coeff_count_power - 1 rounds
-            {
-                out.push_back(static_cast<std::uint32_t>(pos));
-                pos = (pos * pos) & (m - 1);
-                out.push_back(static_cast<std::uint32_t>(neg));
-                neg = (neg * neg) & (m - 1);
-            }
-            return out;
-        }
-
-    private:
-        // from (n_keys x n_key x N, with elts == nullptr): switching keys from those secrets at `level`
-        Keys generate(const std::uint32_t *elts, std::size_t n_keys, bool save_seed, const std::uint64_t *from = nullptr,
-                      std::size_t level = 0)
-        {
-            Keys out;
-            if (!n_keys)
-                return out;
-            std::uint32_t k_first = 0, digits = 0;
-            throw_on(sealhip_context_first_level(ctx_.get(), &k_first));
-            throw_on(sealhip_kswitch_digits(ctx_.get(), k_first, &digits));
-            const std::size_t n = ctx_.n(), nk = ctx_.n_key(), d = digits, items = n_keys * d;
-            std::vector<std::uint64_t> seeds(items * 8);
-            Drawn drawn = draw(seeds.data(), items);
-            Staged sk(ctx_, nk * n);
-            ZeroedStaged e(ctx_, (items * n + 1) / 2);
-            sk.up(sk_.data(), nk * n);
-            to_device(drawn, items, e);
-            std::vector<sealhip_kswitch_key *> raw(n_keys, nullptr);
-            const auto *en = reinterpret_cast<const std::int32_t *>(e.ptr());
-            if (from)
-            {
-                ZeroedStaged other(ctx_, n_keys * nk * n);
-                other.up(from, n_keys * nk * n);
-                throw_on(sealhip_generate_switching_keys(ctx_.get(), sk.ptr(), other.ptr(), std::uint32_t(n_keys),
-                                                         std::uint32_t(level), seeds.data(), en, save_seed ? 1 : 0, raw.data()));
-            }
-            else if (elts)
-                throw_on(sealhip_generate_galois_keys(ctx_.get(), sk.ptr(), elts, std::uint32_t(n_keys), seeds.data(), en,
-                                                      save_seed ? 1 : 0, raw.data()));
-            else
-                throw_on(sealhip_generate_relin_keys(ctx_.get(), sk.ptr(), std::uint32_t(n_keys), seeds.data(), en,
-                                                     save_seed ? 1 : 0, raw.data()));
-            for (auto *h : raw)
-                out.push_back(std::make_unique<KSwitchKeys>(ctx_, h));
-            return out;
-        }
-
-        // What `items` encrypt_zero_symmetric calls draw on the host, item by item in the reference's order, before any
-        // device work: c_1's seed (into seeds, 8 words per item) and either the N noise values from the sampler, or a second
-        // seed from the seed source, from which to_device samples them as (0, 1) and which is dropped there
-        struct Drawn
-        {
-            std::vector<std::int32_t> noise;
-            std::vector<std::uint64_t> noise_seeds;
-        };
-        Drawn draw(std::uint64_t *seeds, std::size_t items)
-        {
-            Drawn d;
-            const std::size_t n = ctx_.n();
-            if (seeds_)
-            {
-                d.noise_seeds.resize(items * 8);
-                for (std::size_t i = 0; i < items; i++)
-                    detail::draw_seed_pair(seeds_, seeds + 8 * i, d.noise_seeds.data() + 8 * i);
-                return d;
-            }
-            d.noise.resize(items * n);
-            for (std::size_t i = 0; i < items; i++)
-                sampler_(seeds + 8 * i, d.noise.data() + n * i);
-            return d;
-        }
-        void to_device(Drawn &d, std::size_t items, Staged &e)
-        {
-            auto *e32 = reinterpret_cast<std::int32_t *>(e.ptr());
-            if (seeds_)
-            {
-                throw_on(sealhip_sample_polys(ctx_.get(), d.noise_seeds.data(), items, 0, 1, e32, 0));
-                std::fill(d.noise_seeds.begin(), d.noise_seeds.end(), 0);
-            }
-            else
-                throw_on(sealhip_memcpy_h2d(ctx_.get(), e32, d.noise.data(), d.noise.size() * sizeof(std::int32_t)));
-        }
-
-        const Context &ctx_;
-        std::vector<std::uint64_t> sk_;
-        Sampler sampler_;
-        SeedSource seeds_; // set: the noise is drawn on the device
     };
 } // namespace sealhip_host

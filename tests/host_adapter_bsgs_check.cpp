@@ -40,6 +40,13 @@ static int host_checks()
                                             "Galois key not present");
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 3 }, none, one, out); },
                                             "Galois key not present");
+        // element 1 needs no key on either axis: the call gets past the key lookup (to the missing device); element 3 next
+        // to it does not, on the baby axis or on the giant axis
+        ok &= throws<std::logic_error>([&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 1 }, none, one, out); }, "host-only");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1, 3 }, { 1 }, none, two, out); },
+                                            "Galois key not present");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1 }, { 1, 3 }, none, Plains{ { w }, { w } }, out); },
+                                            "Galois key not present");
         // the plaintexts: rows per giant, a ragged row, a level below the key level, coefficient form, unequal scales (CKKS)
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain(good, { 1, 1 }, { 1 }, none, square, out); },
                                             "one row of plaintexts per giant element");

@@ -28,6 +28,15 @@ static int host_checks()
     d.is_ntt_form() = true;
     ok &= throws<std::invalid_argument>([&] { ev.expand(d, 4, none, outs); }, "encrypted size must be 2");
     ok &= throws<std::invalid_argument>([&] { ev.dot_plain(terms, no_plains, outs); }, "must not be empty");
+    // a term of size 3 among size-2 terms (shapes without words: the checks come before any device work)
+    for (std::size_t i = 0; i < 2; i++)
+    {
+        terms.emplace_back(ctx);
+        terms[i].adopt(nullptr, 0, 2 + i, 2);
+        terms[i].is_ntt_form() = true;
+    }
+    const std::vector<std::vector<const DevicePlaintext *>> null_plains{ { nullptr, nullptr } };
+    ok &= throws<std::invalid_argument>([&] { ev.dot_plain(terms, null_plains, outs); }, "encrypted parameter mismatch");
     ok &= outs.empty();
     if (!ok)
         return 1;

@@ -34,6 +34,12 @@ static int host_checks()
         ok &= throws<std::invalid_argument>([&] { ev.rotate_vector_many(three, { 1 }, none, out); }, "encrypted size must be 2");
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_many(good, { 3 }, none, out); }, "Galois key not present");
         ok &= out.size() == 3; // (a refused call leaves the destinations alone)
+        // the ABI entry reads a key for every element: the identity is not exempt here
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_many(good, { 1 }, none, out); }, "Galois key not present");
+        // a map entry without a key is left out of rotate_vector_many's lists: the refusal is the missing device's
+        const std::map<std::uint32_t, const KSwitchKeys *> null_entry{ { 3, nullptr } };
+        ok &= throws<std::logic_error>([&] { ev.rotate_vector_many(good, { 0 }, null_entry, out); }, "host-only");
+        ok &= out.size() == 3;
         ev.apply_galois_many(good, {}, none, out);
         ok &= out.empty();
         out.resize(2);

@@ -38,6 +38,10 @@ static int host_checks()
                                             "encrypted size must be 2");
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_dot_plain(good, { 3 }, none, one, out); },
                                             "Galois key not present");
+        // element 1 needs no key: the call gets past the key lookup (to the missing device); element 3 next to it does not
+        ok &= throws<std::logic_error>([&] { ev.apply_galois_dot_plain(good, { 1 }, none, one, out); }, "host-only");
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_dot_plain(good, { 1, 3 }, none, two, out); },
+                                            "Galois key not present");
         // the plaintexts: a ragged matrix, a level below the key level, coefficient form, unequal scales (CKKS)
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_dot_plain(good, { 1 }, none, two, out); },
                                             "one plaintext per Galois element");

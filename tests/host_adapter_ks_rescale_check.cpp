@@ -49,6 +49,12 @@ static int host_checks()
             ok &= throws<std::logic_error>([&] { ev.rotate_vector_bsgs_plain_rescale(good, { 0 }, { 0 }, none, one, out); },
                                            "unsupported scheme");
             ok &= throws<std::logic_error>([&] { ev.relinearize_rescale(three, no_keys, out); }, "unsupported scheme");
+            // an operand at the last level breaks two rules: the scheme's refusal comes first
+            ok &= throws<std::logic_error>([&] { ev.apply_galois_dot_plain_rescale(last, { 1 }, none, one, outs); },
+                                           "unsupported scheme");
+            ok &= throws<std::logic_error>([&] { ev.apply_galois_bsgs_plain_rescale(last, { 1 }, { 1 }, none, one, out); },
+                                           "unsupported scheme");
+            ok &= throws<std::logic_error>([&] { ev.relinearize_rescale(last3, no_keys, out); }, "unsupported scheme");
             ok &= out.size() == 3 && out.coeff_modulus_size() == 1 && outs.size() == 1;
             continue;
         }
@@ -80,6 +86,12 @@ static int host_checks()
         ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain_rescale(last, { 1 }, { 1 }, none, one, out); }, chain);
         ok &= throws<std::invalid_argument>([&] { ev.rotate_vector_bsgs_plain_rescale(last, { 0 }, { 0 }, none, one, out); }, chain);
         ok &= throws<std::invalid_argument>([&] { ev.relinearize_rescale(last3, no_keys, out); }, chain);
+        // a coefficient-form operand at the last level breaks two rules: the form's refusal comes first
+        const HostCiphertext last_coeff = host_ct(2, 1, n, false), last3_coeff = host_ct(3, 1, n, false);
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_dot_plain_rescale(last_coeff, { 1 }, none, one, outs); }, form);
+        ok &= throws<std::invalid_argument>([&] { ev.apply_galois_bsgs_plain_rescale(last_coeff, { 1 }, { 1 }, none, one, out); },
+                                            form);
+        ok &= throws<std::invalid_argument>([&] { ev.relinearize_rescale(last3_coeff, no_keys, out); }, form);
         ok &= out.size() == 3 && out.coeff_modulus_size() == 1 && outs.size() == 1; // (a refused call leaves the destinations alone)
         // a valid call (element 1 / step 0 needs no key) reaches the device, which a host-only context does not have
         ok &= throws<std::logic_error>([&] { ev.apply_galois_dot_plain_rescale(good, { 1 }, none, one, outs); }, "host-only");

@@ -195,6 +195,15 @@ int main(int argc, char **argv)
                                             "encrypted size must be 2");
         ok &= throws<std::invalid_argument>([&] { ev.linear_transform(host_ct(2, 1, N, true, delta), lt, gk, keep, true); },
                                             "end of modulus switching chain reached");
+        // an operand that breaks two rules gets the first one's message: the form before the end of the chain, and on a BFV
+        // context (host-only: the call stops at the scheme) "unsupported scheme" before any form message
+        ok &= throws<std::invalid_argument>([&] { ev.linear_transform(host_ct(2, 1, N, false, delta), lt, gk, keep, true); },
+                                            "CKKS encrypted must be in NTT form");
+        sealhip_params b{ SEALHIP_SCHEME_BFV, 10, 4, 1, mods, 786433ULL, SEALHIP_MODE_STRICT, -1 };
+        Context bfv(b);
+        Evaluator<HostCiphertext> ev_bfv(bfv);
+        ok &= throws<std::logic_error>([&] { ev_bfv.linear_transform(host_ct(2, k, N, true), lt, gk, keep, true); },
+                                       "unsupported scheme");
         ok &= keep.size() == 3 && keep.coeff_modulus_size() == 1; // (a refused call leaves the destination alone)
 
         // decrypted and decoded against M z

@@ -51,8 +51,10 @@ def test_new_exports():
     for word in ("N^2 / 2^64", "rank_i", "(h + 1) / 2 + 1", "level = 1"):
         assert word in design, word
     assert "does not sample sparse secrets" in header and "sealhip_generate_sparse_secret_key makes" in header
-    with open(os.path.join(ROOT, "gemini-seal_amd", "host", "evaluator.hpp")) as f:
-        adapter = f.read()
+    adapter = ""
+    for name in ("evaluator.hpp", "crypto.hpp"):  # Evaluator; KeyGenerator
+        with open(os.path.join(ROOT, "gemini-seal_amd", "host", name)) as f:
+            adapter += f.read()
     for word in ("generate_sparse_secret_key(const Context &context, const SeedSource &seeds, std::uint32_t h)",
                  "Keys switching_keys(", "void switch_secret(const C &encrypted, const KSwitchKeys &key, C &destination)",
                  "const KSwitchKeys &to_sparse, const KSwitchKeys &to_dense"):
